@@ -27,6 +27,9 @@ headline panel (and of c4 over 4, c5 over 8) timed alone with the iteration rate
 closing collectives of the real message sizes on a ONE-rank RCCL communicator.  The parent process of that mode never touches HIP.
 
 Other workloads: --config c2|c3|c4|c5 (BASELINE.json configs), --solver fw|adagrad|ascg|smo|ip|as, --task svr, ...
+
+--dump-outputs DIR writes what the timed run computed (iterate, gradient, per-step records) as .npy files, so that two builds of
+the library can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -49,6 +52,7 @@ STEADY_STATE_PRODUCTS = 1e9
 FP64_MFMA_PEAK_TF = 78.6
 
 LINE_LIMIT = 4096       # bytes of the last stdout line (the driver keeps a 12.8 KB tail of stdout: r04's 25.6 KB line was cut)
+DUMP_LIMIT = 64 << 20   # bytes of --dump-outputs in all
 
 SIDE_RECORDS = ('c2', 'c4', 'c5', 'shares', 'collective', 'shares_c4', 'shares_c5', 'fixed_cap', 'fixed_cap_c5', 'as_c2', 'dense_c2')   # in the order they are measured
 
@@ -153,6 +157,11 @@ def parse(argv=None):
     ap.add_argument('--cpu-study', action='store_true',
                     help='CPU only (SURVEY 8d): the oracle timed at three sizes to check the n^2 (PG) / n^3 (Cholesky) laws '
                          'behind the extrapolated baseline, plus a blocked Gram-streaming product at the full n')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='iteration-rate workloads: after the timed steps, write what the timed solver run hands its caller as '
+                         'DIR/<name>.npy (float64): x = the iterate after the last timed step, g = its gradient, stats = one row per '
+                         'timed step (iter, f, r1, r2, r3).  Inputs are seeded: the same arguments give the same inputs.  At most '
+                         f'{DUMP_LIMIT >> 20} MB in all: past that, each array is cut to a fixed seeded sample of its entries')
     args = ap.parse_args(argv)
     # no workload flag at all = the driver's command: the line then carries the side records too
     args.default_workload = args.config is None and all(getattr(args, k) is None for k in ('n', 'd', 'solver', 'task', 'kernel', 'storage'))
@@ -926,7 +935,10 @@ def orchestrate(args):
         return args.budget_s - (time.perf_counter() - t_start)
 
     print('[bench] headline record (child process)', file=sys.stderr, flush=True)
-    head, err, dt = _run_child(sys.argv[1:], max(left(), 60.0))
+    argv = sys.argv[1:]
+    if args.dump_outputs:   # the child runs in the repository root: the caller's DIR, not one of the same name there
+        argv = argv + ['--dump-outputs', os.path.abspath(args.dump_outputs)]
+    head, err, dt = _run_child(argv, max(left(), 60.0))
     if head is None or err is not None:
         print(f'[bench] the headline run failed: {err}', file=sys.stderr, flush=True)
         raise SystemExit(1)
@@ -1300,9 +1312,27 @@ def emit(full, args, stream=None):
     print('[bench] complete record: ' + json.dumps(full), file=sys.stderr, flush=True)
     print(json.dumps(compact_line(full, path)), file=stream, flush=True)
 
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as PATH/<name>.npy in float64.  When they hold more than DUMP_LIMIT bytes in all, each one with
+    more than its equal share of entries is cut to a sample of that many: the same sorted indices (RandomState(0)) for arrays of
+    the same size, in every run, so that the files of two builds compare entry for entry."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    keep = None
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (8 * len(arrays))
+    for name, a in arrays.items():
+        if keep is not None and a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+
 # ---------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse()
+    if args.dump_outputs and (args.cpu_study or args.dense or args.emulate_shares or args.collective_floor or args.fixed_cap > 0
+                              or args.solver in ('ip', 'as', 'smo')):
+        raise SystemExit('--dump-outputs: the iteration-rate workloads only (--solver pg | fw | adagrad | ascg, no record mode)')
     if args.cpu_study:
         return cpu_study(args)
     if args.dense:
@@ -1448,6 +1478,9 @@ def main():
     ex_ms, ex_cnt = ctx.profile_read(_lib.PROF_EXCH, reset=True)
     pcs_ms, pcs_cnt = ctx.profile_read(_lib.PROF_PCSHARD, reset=True) if ascg else (0.0, 0)
     inner = (solver.inner_iters() - inner0) if ascg else 0
+    if args.dump_outputs and rank == 0:   # outside the timed region; x and g as minimize() hands them back after a run that did not stop
+        stats = np.stack([rows[k].astype(np.float64) for k in rows.dtype.names], axis=1)
+        dump_outputs(args.dump_outputs, {'x': solver.get(_lib.GET_X_NOW), 'g': solver.get(_lib.GET_G_NOW), 'stats': stats})
     per_rank = None
     if comm is not None:   # every rank's share and timings in the one line rank 0 prints
         cols = [comm.allgather_float(v) for v in (own_elapsed * 1e3 / max(done, 1), mv_ms / max(mv_cnt, 1),

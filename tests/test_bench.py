@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import set_hooks, hooks_env, hook_value
@@ -272,6 +273,79 @@ def test_compact_line_stays_under_the_limit_whatever_the_record_holds():
     full['fixed_cap'].update({f'x{k}': {'iterations': k, 'proj_grad_norm_2': 1.5, 'wall_s': 2.5} for k in range(200)})
     line = bench.compact_line(full, None)
     assert len(json.dumps(line)) < 4096 and line['dropped'] and line['roofline']['frac'] and line['cpu_baseline']['value']
+
+
+def test_dump_outputs_float64_and_a_fixed_sample_past_the_limit(monkeypatch, tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; past DUMP_LIMIT bytes each array is cut to the same seeded sample of
+    its entries in every run (x and g of one size share the indices), and the files stay under the limit."""
+    sys.path.insert(0, REPO)
+    import bench
+    x, stats = np.linspace(0., 1., 1000), np.arange(15, dtype=np.int64).reshape(3, 5)
+    bench.dump_outputs(str(tmp_path / 'a'), {'x': x, 'stats': stats})
+    got = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in ('x', 'stats')}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got['x'], x) and np.array_equal(got['stats'], stats)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 8 * 300)
+    g = 2. * x
+    for run in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / run), {'x': x, 'g': g, 'stats': stats})
+    b = {k: np.load(tmp_path / 'b' / f'{k}.npy') for k in ('x', 'g', 'stats')}
+    assert b['x'].shape == (100,) and np.array_equal(b['g'], 2. * b['x']) and np.array_equal(b['stats'], stats)
+    assert sum(v.nbytes for v in b.values()) <= bench.DUMP_LIMIT
+    assert np.all(np.diff(b['x']) > 0) and np.isin(b['x'], x).all()                      # sorted entries of x itself
+    assert all(np.array_equal(b[k], np.load(tmp_path / 'c' / f'{k}.npy')) for k in b)     # the same sample in every run
+
+
+def test_dump_outputs_is_refused_where_there_is_no_timed_solver_run(tmp_path):
+    """The record modes and the time-to-KKT solvers time something else than one solver run: --dump-outputs is an error there, said
+    before anything touches the GPU."""
+    for extra in (['--dense'], ['--solver', 'smo'], ['--emulate-shares', '2']):
+        r = _run(extra + ['--dump-outputs', str(tmp_path / 'out')], timeout=120)
+        assert r.returncode != 0 and 'iteration-rate workloads only' in r.stderr, (extra, r.stderr[-2000:])
+        assert not (tmp_path / 'out').exists()
+
+
+def test_default_line_hands_the_dump_directory_to_the_headline_child(monkeypatch, capsys, tmp_path):
+    """The headline child runs in the repository root: a relative --dump-outputs DIR reaches it as the caller's absolute DIR."""
+    sys.path.insert(0, REPO)
+    import bench
+    argv = ['--gpus', '1', '--steps', '20', '--warmup', '5', '--dump-outputs', 'dump']
+    args = bench.parse(argv)
+    assert args.default_workload and args.dump_outputs == 'dump'
+    args.records_file, args.budget_s = str(tmp_path / 'bench_records.json'), 1.0
+    calls = []
+
+    def child(argv, timeout):
+        calls.append(list(argv))
+        return {'metric': 'dual_qp_iterations_per_sec', 'value': 160.0, 'ms_per_step': 6.25, 'steps': 20}, None, 1.0
+
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(bench, '_run_child', child)
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    bench.orchestrate(args)
+    capsys.readouterr()
+    assert len(calls) == 1 and calls[0][:len(argv)] == argv
+    assert bench.parse(calls[0]).dump_outputs == str(tmp_path / 'dump')
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_with_the_same_arguments_agree(tmp_path):
+    """--dump-outputs: x, g and one stats row per timed step (--steps of them) of the timed run; the inputs are seeded, so two
+    processes with the same arguments dump the same outputs."""
+    common = ['--samples', '6000', '--features', '16', '--steps', '8', '--warmup', '2', '--no-cpu', '--kkt', 'none']
+    recs, dumps = [], []
+    for run in ('a', 'b'):
+        r = _run(common + ['--dump-outputs', str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append({k: np.load(tmp_path / run / f'{k}.npy') for k in ('x', 'g', 'stats')})
+    rec, d = recs[0], dumps[0]
+    assert rec['steps'] == rec['steps_done'] == 8 and rec['ms_per_step'] > 0
+    assert d['x'].shape == d['g'].shape == (6000,) and d['stats'].shape == (8, 5)
+    assert all(v.dtype == np.float64 for v in d.values())
+    assert np.array_equal(d['stats'][:, 0], d['stats'][0, 0] + np.arange(8)) and d['stats'][-1, 1] == rec['f_last']
+    assert np.all((d['x'] >= -1e-9) & (d['x'] <= 1 + 1e-9))   # x + t d at the largest feasible t: on the box up to rounding
+    assert all(np.array_equal(d[k], dumps[1][k]) for k in d)
 
 
 def test_default_line_without_a_gpu_fails_loudly():
