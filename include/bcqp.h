@@ -47,11 +47,13 @@ extern "C" {
 
 /* 2 (round 6): bq_ctx_probe_stall takes behind_collective, bq_problem_create_dense takes layout flags, bq_problem_layout,
  * bq_ctx_release_held and the state snapshot were added: a consumer built against version 1 must be rebuilt */
-#define BQ_ABI_VERSION 2
+/* 3: the batched one-vs-rest solver (bq_msolver_*) and bq_problem_gram_matmat were added */
+#define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
 typedef struct bq_problem bq_problem;
 typedef struct bq_solver bq_solver;
+typedef struct bq_msolver bq_msolver;
 
 /* panel storage: fp64, fp32 (fp64 accumulation), or none at all — BQ_STREAM recomputes the Gram tiles on the MFMA inside
  * every product (kernel problems with an inner-product kernel; PG / FW / augmented-Lagrangian solvers only): the
@@ -222,6 +224,11 @@ int bq_problem_eval(bq_problem *p, const double *x, double *f, double *g);
 int bq_problem_x_star(bq_problem *p, double *x_out, int *method, int64_t *minres_iters);
 /* out = K w with the raw Gram panel (kernel problems only; n-vectors)  svm/_base.py:877-880 */
 int bq_problem_gram_matvec(bq_problem *p, const double *w, double *out);
+/* OUT[c] = K W[c], c < k: W and OUT are k x n row-major host arrays, one panel stream per chunk of 4 columns (the k masked
+ * products of the one-vs-rest intercepts, svm/_base.py:877-880 once per class).  Single-rank context, resident packed panel.
+ * Column c has the same bits whatever the other columns and its position are (not the bits of bq_problem_gram_matvec: agrees to
+ * rounding). */
+int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out);
 /* copy rows [row0,row0+nrows) of this rank's resident panel (n columns each) to the host as fp64 */
 int bq_problem_panel_rows(bq_problem *p, int64_t row0, int64_t nrows, double *out);
 /* time `reps` launches of the panel product with HIP events; returns the mean in ms */
@@ -278,6 +285,23 @@ int bq_solver_inner_iters(bq_solver *s, int64_t *total);
 #define BQ_COUNT_NO_PRODUCT 4
 int bq_solver_counter(bq_solver *s, int which, int64_t *value);
 int bq_solver_get(bq_solver *s, int what, double *out);
+
+/* ---- batched one-vs-rest ProjectedGradient / FrankWolfe (sklearn OneVsRestClassifier over SVC.fit, svm/_base.py:547-559 once
+ * per class, on ONE Gram panel) -----------------------------------------------------------------------------------------------
+ * p: a kernel-built BQ_SVC problem (its own labels are not used) on a single-rank context with a resident packed panel (not
+ * BQ_STREAM, not BQ_FULL_PANEL): anything else is BQ_ERR_BADARG.  Y: k x n labels (+-1) of the k binary problems; ub: n (shared,
+ * lb = 0); x0: k x n or NULL (mid-box); eps, max_iter, fw_t: as bq_solver_create, for every class.  Class c runs the iteration of
+ * bq_solver_create(kind) on Q_c = diag(y_c) P diag(y_c) — same formulas, thresholds, stop tests and records; the k products of an
+ * iteration are one multi-column panel stream per 4 live classes, and a class that stops leaves the batch.  Class c's iterates
+ * have the same bits alone or in any batch.
+ * run: at most max_steps iterations of every class still running; stats: k x stats_cap rows (class c at c * stats_cap), n_stats
+ * and status: k entries.  get / state: bq_solver_get / bq_solver_state of class cls. */
+int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, const double *x0, double eps,
+                      int64_t max_iter, double fw_t, bq_msolver **out);
+int bq_msolver_run(bq_msolver *s, int64_t max_steps, bq_iter_stat *stats, int64_t stats_cap, int64_t *n_stats, int *status);
+int bq_msolver_state(const bq_msolver *s, int cls, int64_t *iter, int *status, double *f_x);
+int bq_msolver_get(bq_msolver *s, int cls, int what, double *out);
+int bq_msolver_destroy(bq_msolver *s);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

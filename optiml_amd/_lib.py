@@ -30,7 +30,7 @@ MOM = {'none': 0, 'polyak': 1, 'nesterov': 2}
 PROF_MATVEC, PROF_GRAM, PROF_CHOL, PROF_EXCH, PROF_PCSHARD = range(5)
 COUNT_INNER, COUNT_MINRES, COUNT_REFACTOR, COUNT_REUSED, COUNT_NO_PRODUCT = range(5)
 STATE_X, STATE_G, STATE_MULT, STATE_MASKS = 1, 2, 4, 8
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 
 class IterStat(C.Structure):
@@ -94,6 +94,7 @@ PROTOTYPES = {
     'bq_problem_eval': (C.c_int, [_vp, _dp, _dp, _dp]),
     'bq_problem_x_star': (C.c_int, [_vp, _dp, C.POINTER(C.c_int), C.POINTER(_i64)]),
     'bq_problem_gram_matvec': (C.c_int, [_vp, _dp, _dp]),
+    'bq_problem_gram_matmat': (C.c_int, [_vp, C.c_int, _dp, _dp]),
     'bq_problem_panel_rows': (C.c_int, [_vp, _i64, _i64, _dp]),
     'bq_problem_time_matvec': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_problem_placement': (C.c_int, [_vp, C.POINTER(C.c_int), _dp, C.c_int]),
@@ -107,6 +108,11 @@ PROTOTYPES = {
     'bq_solver_counter': (C.c_int, [_vp, C.c_int, C.POINTER(_i64)]),
     'bq_solver_get_state': (C.c_int, [_vp, C.POINTER(SolverState)]),
     'bq_solver_set_state': (C.c_int, [_vp, C.POINTER(SolverState)]),
+    'bq_msolver_create': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
+    'bq_msolver_run': (C.c_int, [_vp, _i64, C.POINTER(IterStat), _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),
+    'bq_msolver_state': (C.c_int, [_vp, C.c_int, C.POINTER(_i64), C.POINTER(C.c_int), _dp]),
+    'bq_msolver_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
+    'bq_msolver_destroy': (C.c_int, [_vp]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     'bq_al_solver_dual_size': (C.c_int, [_vp, C.POINTER(_i64)]),
     'bq_al_solver_set_schedules': (C.c_int, [_vp, _dp, _dp, _i64]),

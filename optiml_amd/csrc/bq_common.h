@@ -318,6 +318,13 @@ void bq_sym_seg_table(const bq_problem *p, bq_seg_table *tab);
 // -> p->s (complete on all ranks).  epi: fuse the PG / FW epilogue into the closing kernel where the path has one (*fused says so)
 int bq_panel_product(bq_problem *p, bool add_one, const double *w, const int *done, const bq_epilogue *epi = nullptr,
                      bool *fused = nullptr);
+// bq_symm.hip: out[:, s] = P W[:, s] for the slots s < *nlive (device) of W (column stride ldw >= nb*256), one panel stream per
+// chunk of BQ_SYMM_CK slots; the host launches the chunks that cover `slots` (an upper bound of *nlive).  Resident packed panel,
+// one rank.  slab: bq_symm_slab_len(nb) doubles.
+constexpr int BQ_SYMM_CK = 4;
+int64_t bq_symm_slab_len(int64_t nb);
+int bq_launch_symm(bq_problem *p, bool add_one, const double *W, int64_t ldw, int slots, double *slab, double *out,
+                   const int *nlive);
 
 // bq_dense.hip: a dense host Hessian into the resident panel — packed lower tile rows when Q == Q' exactly (checked on the device
 // while uploading, agreed across ranks), else row blocks

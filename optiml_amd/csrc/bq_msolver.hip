@@ -1,0 +1,379 @@
+// Batched ProjectedGradient / FrankWolfe on k SVC duals that share one Gram panel (one-vs-rest multi-class: class c has labels
+// y_c = +-1 and Q_c = diag(y_c) (K + 1) diag(y_c)).  Each class is an ordinary bq_solver (x, g, d, Qd, bounds, scalar state, records)
+// and its iteration is the single-class one (bq_vec.hip: pgfw_update_kernel, bq_epilogue.h); what is batched is the launches:
+//   update   (n/256 x k blocks)  the pending step and the new direction of every live class, W[:, pos[c]] = y_c o d_c
+//   product  bq_launch_symm: one panel stream per chunk of BQ_SYMM_CK live classes
+//   closing  (n/256 x k blocks)  Qd_c = y_c o OUT[:, pos[c]] and every class's sums and decisions (bq_epi_finish, per-class ticket)
+//   live     (one wave)  the classes still running, in class order -> pos[], *nlive
+// A class that stops leaves the product at the next iteration (its slot goes to the next live class); when none is left every
+// kernel returns at once and the host stops enqueueing at its next lagged look at *nlive (bq_solver_run's polling scheme).
+// Column c of the product has the same bits for any batch (bq_symm.hip), so every class follows the same trajectory in any batch.
+#include "bq_common.h"
+#include "bq_epilogue.h"
+
+#include <cmath>
+#include <vector>
+
+struct bq_msolver {
+    bq_problem *p = nullptr;
+    int kind = BQ_PG, k = 0;
+    int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ldN >= nb * 256)
+    std::vector<bq_solver *> cls;
+    double *sgn = nullptr, *W = nullptr, *out = nullptr, *slab = nullptr;
+    bq_epilogue *epi = nullptr;   // 2 x k: do_update 0 (a class's first iteration) and 1
+    bq_scal **scs = nullptr;      // k
+    int *pos = nullptr, *nlive = nullptr;
+    int *nlive_host = nullptr;    // pinned copy of *nlive + its event (lagged polling)
+    hipEvent_t flag_event = nullptr;
+    int live_host = 0;            // upper bound of *nlive known to the host
+    bool initialised = false, started = false;
+};
+
+__global__ __launch_bounds__(256) void mstart_prep_kernel(const bq_epilogue *__restrict__ epi, double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < e.n) W[blockIdx.y * ldw + i] = e.sgn[i] * e.x[i];
+}
+
+// prep_kernel + finish_kernel + grad_init_kernel of bq_pgfw_start, per class: Qd = y o (P (y o x)) (+ diag_add x), g = Qd + q
+__global__ __launch_bounds__(256) void mstart_finish_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.N) return;
+    double r = e.sgn[i] * out[blockIdx.y * ldw + i];
+    if (e.diag_add != 0.0) r += e.diag_add * e.x[i];
+    e.Qd[i] = r;
+    e.g[i] = r + e.q[i];
+}
+
+// pgfw_update_kernel (bq_vec.hip) for BQ_SVC, class blockIdx.y, writing its product input to its slot
+__global__ __launch_bounds__(256) void mpgfw_update_kernel(const bq_epilogue *__restrict__ epi, const int *__restrict__ pos,
+                                                           double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    if (e.sc->done) return;
+    double t, tr;
+    bq_epi_scalars(e, t, tr);
+    const bool upd = e.do_update != 0;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const bq_pgfw_elem a = bq_pgfw_compute(e.kind, bq_pgfw_load(e, i, upd), upd, t, tr);
+    if (upd) {
+        e.x[i] = a.x;
+        e.g[i] = a.g;
+    }
+    e.d[i] = a.d;
+    W[pos[blockIdx.y] * ldw + i] = e.sgn[i] * a.d;
+}
+
+// finish_den_kernel (bq_vec.hip) for class blockIdx.y: the same rows per block, the same tree, the class's own ticket
+__global__ __launch_bounds__(256) void mfinish_kernel(const bq_epilogue *__restrict__ epi, const int *__restrict__ pos,
+                                                      const double *__restrict__ out, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    if (e.sc->done) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bq_epi_pre pre = bq_epi_preload(e, i, true);
+    const double sv = i < e.n ? out[pos[blockIdx.y] * ldw + i] : 0.0;
+    bq_epi_finish(e, blockIdx.x, gridDim.x, bq_epi_element(e, pre, i, sv), gridDim.x);
+}
+
+__global__ void mlive_kernel(bq_scal *const *__restrict__ scs, int k, int *__restrict__ pos, int *__restrict__ nlive) {
+    if (threadIdx.x != 0) return;
+    int s = 0;
+    for (int c = 0; c < k; ++c)
+        if (!scs[c]->done) pos[c] = s++;
+    *nlive = s;
+}
+
+extern "C" int bq_msolver_destroy(bq_msolver *m) {
+    if (m == nullptr) return BQ_OK;
+    hipSetDevice(m->p->ctx->device);
+    (void)bq_ctx_sync(m->p->ctx);
+    for (void *ptr : {(void *)m->sgn, (void *)m->W, (void *)m->out, (void *)m->slab, (void *)m->epi, (void *)m->scs, (void *)m->pos,
+                      (void *)m->nlive})
+        if (ptr) hipFree(ptr);
+    if (m->nlive_host) {
+        hipHostFree(m->nlive_host);
+        hipEventDestroy(m->flag_event);
+    }
+    for (bq_solver *s : m->cls) bq_solver_destroy(s);
+    bq_problem *p = m->p;
+    delete m;
+    bq_problem_unref(p);
+    return BQ_OK;
+}
+
+static void fill_epi(bq_msolver *m, int c, int do_update, bq_epilogue &e) {
+    const bq_solver *s = m->cls[c];
+    const bq_problem *p = m->p;
+    e = bq_epilogue{};
+    e.structure = p->structure;
+    e.kind = m->kind == BQ_PG ? 0 : 1;
+    e.do_update = do_update;
+    e.n = p->n;
+    e.N = p->N;
+    e.diag_add = p->diag_add;
+    e.x = s->x;
+    e.g = s->g;
+    e.d = s->d;
+    e.q = p->q;
+    e.lb = s->lb;
+    e.ub = s->ub;
+    e.sgn = m->sgn + c * m->ldw;
+    e.Qd = s->Qd;
+    e.sc = s->sc;
+    e.part = s->partials;
+    e.stats = s->stats;
+}
+
+// the device epilogue table: the records' buffers may have been re-allocated by a run with more steps
+static int upload_epi(bq_msolver *m) {
+    std::vector<bq_epilogue> h(2 * (size_t)m->k);
+    for (int c = 0; c < m->k; ++c) {
+        fill_epi(m, c, 0, h[c]);
+        fill_epi(m, c, 1, h[m->k + c]);
+    }
+    BQ_HIP(hipMemcpyAsync(m->epi, h.data(), sizeof(bq_epilogue) * h.size(), hipMemcpyHostToDevice, m->p->ctx->stream));
+    BQ_SYNC(m->p->ctx);   // h goes out of scope
+    return BQ_OK;
+}
+
+extern "C" int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, const double *x0, double eps,
+                                 int64_t max_iter, double fw_t, bq_msolver **out) {
+    BQ_ARG(p && Y && ub && out, "NULL argument");
+    BQ_ARG(kind == BQ_PG || kind == BQ_FW, "the batched solver is ProjectedGradient or FrankWolfe");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->structure == BQ_SVC && p->kernel >= 0, "the batched solver takes a kernel-built SVC problem");
+    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
+        bq_set_error("the batched solver needs a single-rank context and a resident packed panel (not streamed, not full rows)");
+        return BQ_ERR_BADARG;
+    }
+    for (int64_t i = 0; i < (int64_t)k * p->n; ++i) BQ_ARG(Y[i] == 1.0 || Y[i] == -1.0, "labels must be +1 or -1");
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    bq_msolver *m = new bq_msolver();
+    m->p = p;
+    p->refs += 1;
+    m->kind = kind;
+    m->k = k;
+    m->ldw = p->ldN;
+    const int slots = (int)bq_round_up(k, BQ_SYMM_CK);
+    int rc = BQ_OK;
+    for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
+        bq_solver *s = nullptr;
+        rc = bq_solver_create(p, kind, nullptr, ub, x0 ? x0 + (int64_t)cl * p->n : nullptr, eps, max_iter, fw_t, &s);
+        if (rc == BQ_OK) m->cls.push_back(s);
+    }
+    auto fail = [&](int code) {
+        bq_msolver_destroy(m);
+        return code;
+    };
+    if (rc != BQ_OK) return fail(rc);
+    hipError_t e = hipMalloc(&m->sgn, sizeof(double) * m->ldw * k);
+    if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
+    if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
+    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * bq_symm_slab_len(p->nb));
+    if (e == hipSuccess) e = hipMalloc(&m->epi, sizeof(bq_epilogue) * 2 * k);
+    if (e == hipSuccess) e = hipMalloc(&m->scs, sizeof(bq_scal *) * k);
+    if (e == hipSuccess) e = hipMalloc(&m->pos, sizeof(int) * k);
+    if (e == hipSuccess) e = hipMalloc(&m->nlive, sizeof(int));
+    if (e != hipSuccess) {
+        bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
+        return fail(BQ_ERR_NOMEM);
+    }
+    std::vector<bq_scal *> scs(k);
+    std::vector<int> pos(k);
+    for (int cl = 0; cl < k; ++cl) {
+        scs[cl] = m->cls[cl]->sc;
+        pos[cl] = cl;
+    }
+    hipStream_t st = c->stream;
+    e = hipMemsetAsync(m->sgn, 0, sizeof(double) * m->ldw * k, st);
+    if (e == hipSuccess) e = hipMemsetAsync(m->W, 0, sizeof(double) * m->ldw * slots, st);
+    if (e == hipSuccess) e = hipMemsetAsync(m->out, 0, sizeof(double) * m->ldw * slots, st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(m->sgn, sizeof(double) * m->ldw, Y, sizeof(double) * p->n, sizeof(double) * p->n, k,
+                                              hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->scs, scs.data(), sizeof(bq_scal *) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->pos, pos.data(), sizeof(int) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->nlive, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+        bq_set_error("batched solver setup failed: %s", hipGetErrorString(e));
+        return fail(BQ_ERR_HIP);
+    }
+    if (hipHostMalloc((void **)&m->nlive_host, sizeof(int), hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&m->flag_event, hipEventDisableTiming) != hipSuccess) {
+        if (m->nlive_host) hipHostFree(m->nlive_host);
+        m->nlive_host = nullptr;
+        (void)hipGetLastError();
+    }
+    m->live_host = k;
+    rc = upload_epi(m);
+    if (rc != BQ_OK) return fail(rc);
+    *out = m;
+    return BQ_OK;
+}
+
+static int msolver_first(bq_msolver *m) {
+    bq_problem *p = m->p;
+    hipStream_t st = p->ctx->stream;
+    const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
+    mstart_prep_kernel<<<grid, 256, 0, st>>>(m->epi, m->W, m->ldw);
+    BQ_HIP(hipGetLastError());
+    BQ_TRY(bq_launch_symm(p, p->add_one, m->W, m->ldw, m->k, m->slab, m->out, m->nlive));
+    mstart_finish_kernel<<<grid, 256, 0, st>>>(m->epi, m->out, m->ldw);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+static int msolver_iterate(bq_msolver *m) {
+    bq_problem *p = m->p;
+    hipStream_t st = p->ctx->stream;
+    const bq_epilogue *epi = m->epi + (m->started ? m->k : 0);
+    m->started = true;
+    const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
+    mpgfw_update_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->W, m->ldw);
+    BQ_HIP(hipGetLastError());
+    BQ_TRY(bq_launch_symm(p, p->add_one, m->W, m->ldw, m->live_host, m->slab, m->out, m->nlive));
+    mfinish_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->out, m->ldw);
+    mlive_kernel<<<1, 64, 0, st>>>(m->scs, m->k, m->pos, m->nlive);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *stats, int64_t stats_cap, int64_t *n_stats,
+                              int *status) {
+    BQ_ARG(m && n_stats && status, "NULL argument");
+    BQ_ARG(max_steps > 0, "max_steps must be > 0");
+    BQ_ARG(stats == nullptr || stats_cap >= max_steps, "stats capacity must be >= max_steps");
+    bq_ctx *c = m->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    bool any = false, grown = false;
+    std::vector<char> was_done(m->k);
+    for (int cl = 0; cl < m->k; ++cl) {
+        bq_solver *s = m->cls[cl];
+        n_stats[cl] = 0;
+        status[cl] = s->host.status;
+        was_done[cl] = s->host.done != 0;
+        any = any || !s->host.done;
+        if (s->stats_cap < max_steps) {
+            if (s->stats) BQ_HIP(hipFree(s->stats));
+            s->stats = nullptr;
+            BQ_HIP(hipMalloc(&s->stats, sizeof(bq_iter_stat) * max_steps));
+            s->stats_cap = max_steps;
+            grown = true;
+        }
+        long long hdr[2] = {s->host.iter, (long long)max_steps};
+        BQ_HIP(hipMemcpyAsync(&s->sc->stat_base, hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream));
+        BQ_SYNC(c);   // hdr goes out of scope
+    }
+    if (!any) return BQ_OK;
+    if (grown) BQ_TRY(upload_epi(m));
+    if (!m->initialised) {
+        BQ_TRY(msolver_first(m));
+        m->initialised = true;
+    }
+    // bq_solver_run's lagged look at the device, here at the number of live classes: about every 20 ms of estimated streaming
+    const double esz = m->p->storage == BQ_F64 ? 8.0 : 4.0;
+    const double passes = (double)((m->live_host + BQ_SYMM_CK - 1) / BQ_SYMM_CK);
+    const double iter_s = passes * (double)m->p->n * (double)m->p->n * esz * 0.5 / 5.0e12 + 30e-6 * m->k;
+    int64_t poll = (int64_t)(20.0e-3 / iter_s);
+    poll = poll < 1 ? 1 : (poll > 64 ? 64 : poll);
+    bool pending = false;
+    for (int64_t it = 0; it < max_steps; ++it) {
+        BQ_TRY(msolver_iterate(m));
+        if ((it + 1) % poll == 0 && it + 1 < max_steps) {
+            if (m->nlive_host) {
+                if (pending) {
+                    BQ_TRY(bq_ctx_event_sync(c, m->flag_event));
+                    m->live_host = *m->nlive_host;
+                    if (m->live_host == 0) break;
+                }
+                BQ_HIP(hipMemcpyAsync(m->nlive_host, m->nlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                BQ_HIP(hipEventRecord(m->flag_event, c->stream));
+                pending = true;
+            } else {
+                int nl = 0;
+                BQ_HIP(hipMemcpyAsync(&nl, m->nlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                BQ_SYNC(c);
+                m->live_host = nl;
+                if (nl == 0) break;
+            }
+        }
+    }
+    int nl = 0;
+    BQ_HIP(hipMemcpyAsync(&nl, m->nlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    for (int cl = 0; cl < m->k; ++cl) {
+        bq_solver *s = m->cls[cl];
+        BQ_HIP(hipMemcpyAsync(&s->host, s->sc, sizeof(bq_scal), hipMemcpyDeviceToHost, c->stream));
+    }
+    BQ_SYNC(c);
+    m->live_host = nl;
+    for (int cl = 0; cl < m->k; ++cl) {
+        bq_solver *s = m->cls[cl];
+        s->initialised = s->started = true;   // bq_solver_get / _state on the class see a solver that has run
+        if (s->host.status < 0) {
+            bq_set_error("non-finite values in the solver state of class %d", cl);
+            return s->host.status;
+        }
+        const long long base = s->host.stat_base;
+        int64_t rows = was_done[cl] ? 0 : s->host.iter - base + (s->host.done ? 1 : 0);   // a class done before this run has no rows
+        if (rows > max_steps) rows = max_steps;
+        if (rows < 0) rows = 0;
+        if (stats && rows > 0) BQ_HIP(hipMemcpyAsync(stats + cl * stats_cap, s->stats, sizeof(bq_iter_stat) * rows, hipMemcpyDeviceToHost, c->stream));
+        n_stats[cl] = rows;
+        status[cl] = s->host.status;
+    }
+    BQ_SYNC(c);
+    return BQ_OK;
+}
+
+extern "C" int bq_msolver_state(const bq_msolver *m, int cls, int64_t *iter, int *status, double *f_x) {
+    BQ_ARG(m != nullptr && cls >= 0 && cls < m->k, "solver is NULL or class out of range");
+    return bq_solver_state(m->cls[cls], iter, status, f_x);
+}
+
+extern "C" int bq_msolver_get(bq_msolver *m, int cls, int what, double *out) {
+    BQ_ARG(m != nullptr && cls >= 0 && cls < m->k, "solver is NULL or class out of range");
+    return bq_solver_get(m->cls[cls], what, out);
+}
+
+extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out) {
+    BQ_ARG(p && W && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->kernel >= 0, "not a kernel-structured problem");
+    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
+        bq_set_error("the multi-column product needs a single-rank context and a resident packed panel");
+        return BQ_ERR_BADARG;
+    }
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    const int64_t ldw = p->ldN, slots = bq_round_up(k, BQ_SYMM_CK);
+    double *dW = nullptr, *dO = nullptr, *slab = nullptr;
+    int *nl = nullptr;
+    hipError_t e = hipMalloc(&dW, sizeof(double) * ldw * slots);
+    if (e == hipSuccess) e = hipMalloc(&dO, sizeof(double) * ldw * slots);
+    if (e == hipSuccess) e = hipMalloc(&slab, sizeof(double) * bq_symm_slab_len(p->nb));
+    if (e == hipSuccess) e = hipMalloc(&nl, sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(dW, 0, sizeof(double) * ldw * slots, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(dW, sizeof(double) * ldw, W, sizeof(double) * p->n, sizeof(double) * p->n, k,
+                                              hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(nl, &k, sizeof(int), hipMemcpyHostToDevice, c->stream);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("gram_matmat setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) rc = bq_launch_symm(p, false, dW, ldw, k, slab, dO, nl);
+    if (rc == BQ_OK) {
+        e = hipMemcpy2DAsync(out, sizeof(double) * p->n, dO, sizeof(double) * ldw, sizeof(double) * p->n, k, hipMemcpyDeviceToHost,
+                             c->stream);
+        if (e != hipSuccess) {
+            bq_set_error("gram_matmat copy: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    if (rc == BQ_OK) rc = bq_ctx_sync(c);
+    else (void)bq_ctx_sync(c);
+    for (void *ptr : {(void *)dW, (void *)dO, (void *)slab, (void *)nl})
+        if (ptr) hipFree(ptr);
+    return rc;
+}

@@ -23,41 +23,9 @@
 
 #include "bq_common.h"
 #include "bq_epilogue.h"
+#include "bq_symv_tile.h"
 
-typedef double d2_t __attribute__((ext_vector_type(2)));
-
-constexpr int ST = 256;   // tile edge (== BQ_SYM_TILE)
 constexpr int JG_DEFAULT = 8;   // tiles per strip (8 x 2 KiB contiguous per row; best of the measured variants)
-
-typedef float f4_t __attribute__((ext_vector_type(4)));
-
-// One 16-byte non-temporal load per lane and row.  fp64: a lane owns columns {2l, 2l+1} and {128+2l, 128+2l+1} of a tile
-// (two loads); fp32: columns {4l .. 4l+3} (one float4 load).  c0 / c1 are the first columns of the two pairs.
-template <typename T> struct tile_ld;
-template <> struct tile_ld<double> {
-    static __device__ __forceinline__ int c0(int lane) { return 2 * lane; }
-    static __device__ __forceinline__ int c1(int lane) { return 128 + 2 * lane; }
-    static __device__ __forceinline__ void get(const double *row, int lane, d2_t &a, d2_t &b) {
-        a = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(row + 2 * lane));
-        b = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(row + 128 + 2 * lane));
-    }
-};
-template <> struct tile_ld<float> {
-    static __device__ __forceinline__ int c0(int lane) { return 4 * lane; }
-    static __device__ __forceinline__ int c1(int lane) { return 4 * lane + 2; }
-    static __device__ __forceinline__ void get(const float *row, int lane, d2_t &a, d2_t &b) {
-        const f4_t v = __builtin_nontemporal_load(reinterpret_cast<const f4_t *>(row + 4 * lane));
-        a = (d2_t){(double)v.x, (double)v.y};
-        b = (d2_t){(double)v.z, (double)v.w};
-    }
-};
-
-// strips of tile row I: g = 0 .. I / JG ; linear index over tile rows [I0, I1)
-template <int JG>
-__device__ __host__ __forceinline__ int64_t strips_before(int64_t I) {  // sum_{i < I} (i / JG + 1)
-    const int64_t qq = I / JG, rr = I % JG;
-    return JG * qq * (qq + 1) / 2 + rr * (qq + 1);
-}
 
 // One workgroup of four waves streams all 256 rows of a strip: wave `wv` owns rows [64 wv, 64 wv + 64).
 // (Round 4 also carried a row-cut variant — two 128-thread workgroups per strip with a three-entry column slab — for short grids: built,
@@ -194,50 +162,6 @@ __global__ __launch_bounds__(256, 2) void symv_tiles_kernel(const T *__restrict_
             slab[entry * ST + tid] = ((colred[0][tid] + colred[1][tid]) + colred[2][tid]) + colred[3][tid];
         }
     }
-}
-
-// Partial sum of output block a over the slab entries S[a][b] that the tile rows [c0, c1) produced, b ascending:
-//   row parts live at b = first tile of a strip (b % JG == 0, b <= a) when tile row a lies in [c0, c1),
-//   col parts at every b > a inside [c0, c1).
-// 1024 threads: thread (r, q) sums every 4th entry of that fixed entry list (two independent chains each for load-level
-// parallelism); the four partial sums are combined in the fixed order q = 0..3.  Every thread returns the combined value.
-template <int JG>
-__device__ __forceinline__ double seg_thread_sum(const double *__restrict__ p, int64_t a, int64_t c0, int64_t c1, int q) {
-    double s0 = 0.0, s1 = 0.0;
-    int64_t e = 0;   // running index over the entry list: row parts (b = 0, JG, 2JG, ... <= a) then col parts (b > a)
-    // Two chains (s0: entries k, k + 8, ...; s1: k + 4, k + 12, ...), each added in its own order — but the LOADS of four turns are
-    // issued together (round 5): written as one load per turn the loop was a chain of L2 round trips (~11 of them at nb = 79, ~50 at
-    // nb = 391: most of this kernel's 7 us on short grids); the association, and with it every bit, is what it was.
-    auto walk = [&](const double *base, int64_t first, int64_t count, int64_t stride) {
-        int64_t k = first;
-        for (; k + 28 < count; k += 32) {   // four turns of both chains: all eight entries exist
-            const double a0 = base[(k) * stride], b0 = base[(k + 4) * stride], a1 = base[(k + 8) * stride], b1 = base[(k + 12) * stride];
-            const double a2 = base[(k + 16) * stride], b2 = base[(k + 20) * stride], a3 = base[(k + 24) * stride], b3 = base[(k + 28) * stride];
-            s0 += a0;
-            s1 += b0;
-            s0 += a1;
-            s1 += b1;
-            s0 += a2;
-            s1 += b2;
-            s0 += a3;
-            s1 += b3;
-        }
-        for (; k < count; k += 8) {
-            s0 += base[k * stride];
-            if (k + 4 < count) s1 += base[(k + 4) * stride];
-        }
-    };
-    if (a >= c0 && a < c1) {
-        const int64_t nrow = a / JG + 1;
-        walk(p, q, nrow, (int64_t)JG * ST);
-        e = nrow;
-    }
-    const int64_t bs = (a + 1 > c0) ? a + 1 : c0;
-    const int64_t ncol = c1 > bs ? c1 - bs : 0;
-    // keep the q-assignment a function of the position in the whole list (row parts first)
-    const int64_t shift = (4 - (e & 3)) & 3;
-    walk(p + bs * ST, (q + shift) & 3, ncol, ST);
-    return s0 + s1;   // this thread's share (every 4th entry, q = its phase) of the segment's entry list
 }
 
 // the four phases of a segment's sum combined in the fixed order q = 0..3; every thread returns the combined value

@@ -25,6 +25,21 @@ def make_blobs(n, d, seed=0, sigma=8.0, dtype=np.float64):
     return np.ascontiguousarray(X, dtype=dtype), y
 
 
+def make_multiclass_blobs(n, d, k, seed=0, sigma=8.0, dtype=np.float64):
+    """k d-dimensional Gaussian blobs with centers U(-10,10)^d, std `sigma`, standardised columns (as `make_blobs`).
+
+    Returns (X, y) with X (n, d) C-contiguous and y in {0, ..., k-1} (int64), the classes as equal as n allows.
+    """
+    if k < 2:
+        raise ValueError('k must be >= 2')
+    rs = np.random.RandomState(seed)
+    centers = rs.uniform(-10.0, 10.0, (k, d))
+    label = (np.arange(n) * k // n)[rs.permutation(n)]
+    X = centers[label] + sigma * rs.standard_normal((n, d))
+    X = (X - X.mean(axis=0)) / X.std(axis=0)
+    return np.ascontiguousarray(X, dtype=dtype), label.astype(np.int64)
+
+
 def make_regression(n, d, seed=0, sigma=8.0, noise=0.1, dtype=np.float64):
     """Same X as `make_blobs`; targets y = X w / sqrt(d) + noise * N(0,1)."""
     X, _ = make_blobs(n, d, seed=seed, sigma=sigma)

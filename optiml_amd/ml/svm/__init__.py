@@ -1,3 +1,4 @@
-__all__ = ['SVM', 'SVC', 'SVR']
+__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC']
 
 from ._base import SVM, SVC, SVR
+from .multiclass import OneVsRestSVC
