@@ -48,6 +48,7 @@ extern "C" {
 /* 2 (round 6): bq_ctx_probe_stall takes behind_collective, bq_problem_create_dense takes layout flags, bq_problem_layout,
  * bq_ctx_release_held and the state snapshot were added: a consumer built against version 1 must be rebuilt */
 /* 3: the batched one-vs-rest solver (bq_msolver_*) and bq_problem_gram_matmat were added */
+/* (still 3: bq_msolver_create_boxes and bq_problem_gram_matmat_wide were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -229,6 +230,15 @@ int bq_problem_gram_matvec(bq_problem *p, const double *w, double *out);
  * Column c has the same bits whatever the other columns and its position are (not the bits of bq_problem_gram_matvec: agrees to
  * rounding). */
 int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out);
+/* bq_problem_gram_matmat on the fp64 matrix cores, one panel stream per chunk of 16 columns: the held-out decision values and
+ * intercepts of every (fold, C, class) column of a cross-validated search (sklearn GridSearchCV: svm/_base.py:877-880 and
+ * decision_function once per fold and candidate).  Column c's bits are a function of W[c] alone (not those of
+ * bq_problem_gram_matmat: agrees to rounding). */
+int bq_problem_gram_matmat_wide(bq_problem *p, int k, const double *W, double *out);
+/* device memory free / in all on the context's device (hipMemGetInfo), and the bytes of the slab that a boxes solver or a wide
+ * product allocates for p: what the search's column cap per solve is computed from (GridSearchCV keeps one fit per process) */
+int bq_ctx_mem_info(bq_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
+int64_t bq_problem_wide_slab_bytes(const bq_problem *p);
 /* copy rows [row0,row0+nrows) of this rank's resident panel (n columns each) to the host as fp64 */
 int bq_problem_panel_rows(bq_problem *p, int64_t row0, int64_t nrows, double *out);
 /* time `reps` launches of the panel product with HIP events; returns the mean in ms */
@@ -302,6 +312,14 @@ int bq_msolver_run(bq_msolver *s, int64_t max_steps, bq_iter_stat *stats, int64_
 int bq_msolver_state(const bq_msolver *s, int cls, int64_t *iter, int *status, double *f_x);
 int bq_msolver_get(bq_msolver *s, int cls, int what, double *out);
 int bq_msolver_destroy(bq_msolver *s);
+/* The same batched solver with ONE BOX PER COLUMN, for cross-validated searches: sklearn GridSearchCV's per-fold SVC.fit
+ * (svm/_base.py:547-559 once per fold, C and class) on ONE Gram panel of all n rows.  UB: k x n (lb = 0): column c = (fold, C,
+ * class) has ub = C on the fold's training rows and 0 on its held-out rows, which is the training fold's dual exactly (the held-out
+ * entries start at 0 and never move).  Every pass, however few columns are live, takes the 16-column product of
+ * bq_problem_gram_matmat_wide, so column c's iterates have the same bits alone, at any position and in any batch.  Y, x0, eps,
+ * max_iter, fw_t, run / state / get / destroy: as bq_msolver_create. */
+int bq_msolver_create_boxes(bq_problem *p, int kind, int k, const double *Y, const double *UB, const double *x0, double eps,
+                            int64_t max_iter, double fw_t, bq_msolver **out);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

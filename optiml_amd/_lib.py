@@ -95,6 +95,9 @@ PROTOTYPES = {
     'bq_problem_x_star': (C.c_int, [_vp, _dp, C.POINTER(C.c_int), C.POINTER(_i64)]),
     'bq_problem_gram_matvec': (C.c_int, [_vp, _dp, _dp]),
     'bq_problem_gram_matmat': (C.c_int, [_vp, C.c_int, _dp, _dp]),
+    'bq_problem_gram_matmat_wide': (C.c_int, [_vp, C.c_int, _dp, _dp]),
+    'bq_ctx_mem_info': (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    'bq_problem_wide_slab_bytes': (_i64, [_vp]),
     'bq_problem_panel_rows': (C.c_int, [_vp, _i64, _i64, _dp]),
     'bq_problem_time_matvec': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_problem_placement': (C.c_int, [_vp, C.POINTER(C.c_int), _dp, C.c_int]),
@@ -113,6 +116,7 @@ PROTOTYPES = {
     'bq_msolver_state': (C.c_int, [_vp, C.c_int, C.POINTER(_i64), C.POINTER(C.c_int), _dp]),
     'bq_msolver_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     'bq_msolver_destroy': (C.c_int, [_vp]),
+    'bq_msolver_create_boxes': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     'bq_al_solver_dual_size': (C.c_int, [_vp, C.POINTER(_i64)]),
     'bq_al_solver_set_schedules': (C.c_int, [_vp, _dp, _dp, _i64]),

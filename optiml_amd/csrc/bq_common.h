@@ -325,6 +325,12 @@ constexpr int BQ_SYMM_CK = 4;
 int64_t bq_symm_slab_len(int64_t nb);
 int bq_launch_symm(bq_problem *p, bool add_one, const double *W, int64_t ldw, int slots, double *slab, double *out,
                    const int *nlive);
+// bq_symmw.hip: the same product on the fp64 matrix cores, one panel stream per chunk of BQ_SYMMW_CK slots (W, out: at least
+// round_up(slots, BQ_SYMMW_CK) columns).  slab: bq_symmw_slab_len(nb) doubles.
+constexpr int BQ_SYMMW_CK = 16;
+int64_t bq_symmw_slab_len(int64_t nb);
+int bq_launch_symmw(bq_problem *p, bool add_one, const double *W, int64_t ldw, int slots, double *slab, double *out,
+                    const int *nlive);
 
 // bq_dense.hip: a dense host Hessian into the resident panel — packed lower tile rows when Q == Q' exactly (checked on the device
 // while uploading, agreed across ranks), else row blocks

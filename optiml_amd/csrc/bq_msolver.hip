@@ -8,6 +8,12 @@
 // A class that stops leaves the product at the next iteration (its slot goes to the next live class); when none is left every
 // kernel returns at once and the host stops enqueueing at its next lagged look at *nlive (bq_solver_run's polling scheme).
 // Column c of the product has the same bits for any batch (bq_symm.hip), so every class follows the same trajectory in any batch.
+//
+// bq_msolver_create_boxes is the same solver with one box per column (UB: k x n, lb = 0) and the wide product (bq_symmw.hip, 16
+// columns per panel stream) for every pass: the columns of a cross-validated search, (fold, C, class) with ub = C on the fold's
+// training rows and 0 on its held-out rows.  A zero-width box keeps x = 0 there: the mid-box start is 0, PG zeroes d where
+// ub - x <= ACT_TOL and x - lb <= ACT_TOL, FW's vertex is y = ub = lb = 0, so d = 0 and every sum of the column is its training
+// fold's.
 #include "bq_common.h"
 #include "bq_epilogue.h"
 
@@ -17,6 +23,7 @@
 struct bq_msolver {
     bq_problem *p = nullptr;
     int kind = BQ_PG, k = 0;
+    bool wide = false;   // bq_msolver_create_boxes: the 16-column product (bq_symmw.hip) for every pass
     int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ldN >= nb * 256)
     std::vector<bq_solver *> cls;
     double *sgn = nullptr, *W = nullptr, *out = nullptr, *slab = nullptr;
@@ -137,8 +144,17 @@ static int upload_epi(bq_msolver *m) {
     return BQ_OK;
 }
 
-extern "C" int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, const double *x0, double eps,
-                                 int64_t max_iter, double fw_t, bq_msolver **out) {
+static int msolver_ck(const bq_msolver *m) { return m->wide ? BQ_SYMMW_CK : BQ_SYMM_CK; }
+
+static int msolver_product(bq_msolver *m, int slots) {
+    bq_problem *p = m->p;
+    if (m->wide) return bq_launch_symmw(p, p->add_one, m->W, m->ldw, slots, m->slab, m->out, m->nlive);
+    return bq_launch_symm(p, p->add_one, m->W, m->ldw, slots, m->slab, m->out, m->nlive);
+}
+
+// ub_ld: 0 (one box for every class) or n (class c's box at ub + c * n)
+static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, int64_t ub_ld, bool wide,
+                          const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
     BQ_ARG(p && Y && ub && out, "NULL argument");
     BQ_ARG(kind == BQ_PG || kind == BQ_FW, "the batched solver is ProjectedGradient or FrankWolfe");
     BQ_ARG(k >= 1, "k must be >= 1");
@@ -156,11 +172,12 @@ extern "C" int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y
     m->kind = kind;
     m->k = k;
     m->ldw = p->ldN;
-    const int slots = (int)bq_round_up(k, BQ_SYMM_CK);
+    m->wide = wide;
+    const int slots = (int)bq_round_up(k, msolver_ck(m));
     int rc = BQ_OK;
     for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
         bq_solver *s = nullptr;
-        rc = bq_solver_create(p, kind, nullptr, ub, x0 ? x0 + (int64_t)cl * p->n : nullptr, eps, max_iter, fw_t, &s);
+        rc = bq_solver_create(p, kind, nullptr, ub + cl * ub_ld, x0 ? x0 + (int64_t)cl * p->n : nullptr, eps, max_iter, fw_t, &s);
         if (rc == BQ_OK) m->cls.push_back(s);
     }
     auto fail = [&](int code) {
@@ -171,7 +188,7 @@ extern "C" int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y
     hipError_t e = hipMalloc(&m->sgn, sizeof(double) * m->ldw * k);
     if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
     if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
-    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * bq_symm_slab_len(p->nb));
+    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * (wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb)));
     if (e == hipSuccess) e = hipMalloc(&m->epi, sizeof(bq_epilogue) * 2 * k);
     if (e == hipSuccess) e = hipMalloc(&m->scs, sizeof(bq_scal *) * k);
     if (e == hipSuccess) e = hipMalloc(&m->pos, sizeof(int) * k);
@@ -212,13 +229,25 @@ extern "C" int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y
     return BQ_OK;
 }
 
+extern "C" int bq_msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, const double *x0, double eps,
+                                 int64_t max_iter, double fw_t, bq_msolver **out) {
+    return msolver_create(p, kind, k, Y, ub, 0, false, x0, eps, max_iter, fw_t, out);
+}
+
+extern "C" int bq_msolver_create_boxes(bq_problem *p, int kind, int k, const double *Y, const double *UB, const double *x0,
+                                       double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
+    BQ_ARG(p && UB, "NULL argument");
+    for (int64_t i = 0; i < (int64_t)k * p->n; ++i) BQ_ARG(UB[i] >= 0.0, "upper bounds must be >= 0 (lb = 0)");
+    return msolver_create(p, kind, k, Y, UB, p->n, true, x0, eps, max_iter, fw_t, out);
+}
+
 static int msolver_first(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
     const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
     mstart_prep_kernel<<<grid, 256, 0, st>>>(m->epi, m->W, m->ldw);
     BQ_HIP(hipGetLastError());
-    BQ_TRY(bq_launch_symm(p, p->add_one, m->W, m->ldw, m->k, m->slab, m->out, m->nlive));
+    BQ_TRY(msolver_product(m, m->k));
     mstart_finish_kernel<<<grid, 256, 0, st>>>(m->epi, m->out, m->ldw);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
@@ -232,7 +261,7 @@ static int msolver_iterate(bq_msolver *m) {
     const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
     mpgfw_update_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->W, m->ldw);
     BQ_HIP(hipGetLastError());
-    BQ_TRY(bq_launch_symm(p, p->add_one, m->W, m->ldw, m->live_host, m->slab, m->out, m->nlive));
+    BQ_TRY(msolver_product(m, m->live_host));
     mfinish_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->out, m->ldw);
     mlive_kernel<<<1, 64, 0, st>>>(m->scs, m->k, m->pos, m->nlive);
     BQ_HIP(hipGetLastError());
@@ -273,7 +302,7 @@ extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *st
     }
     // bq_solver_run's lagged look at the device, here at the number of live classes: about every 20 ms of estimated streaming
     const double esz = m->p->storage == BQ_F64 ? 8.0 : 4.0;
-    const double passes = (double)((m->live_host + BQ_SYMM_CK - 1) / BQ_SYMM_CK);
+    const double passes = (double)((m->live_host + msolver_ck(m) - 1) / msolver_ck(m));
     const double iter_s = passes * (double)m->p->n * (double)m->p->n * esz * 0.5 / 5.0e12 + 30e-6 * m->k;
     int64_t poll = (int64_t)(20.0e-3 / iter_s);
     poll = poll < 1 ? 1 : (poll > 64 ? 64 : poll);
@@ -336,7 +365,7 @@ extern "C" int bq_msolver_get(bq_msolver *m, int cls, int what, double *out) {
     return bq_solver_get(m->cls[cls], what, out);
 }
 
-extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out) {
+static int gram_matmat(bq_problem *p, int k, const double *W, double *out, bool wide) {
     BQ_ARG(p && W && out, "NULL argument");
     BQ_ARG(k >= 1, "k must be >= 1");
     BQ_ARG(p->kernel >= 0, "not a kernel-structured problem");
@@ -346,12 +375,12 @@ extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, dou
     }
     bq_ctx *c = p->ctx;
     BQ_HIP(hipSetDevice(c->device));
-    const int64_t ldw = p->ldN, slots = bq_round_up(k, BQ_SYMM_CK);
+    const int64_t ldw = p->ldN, slots = bq_round_up(k, wide ? BQ_SYMMW_CK : BQ_SYMM_CK);
     double *dW = nullptr, *dO = nullptr, *slab = nullptr;
     int *nl = nullptr;
     hipError_t e = hipMalloc(&dW, sizeof(double) * ldw * slots);
     if (e == hipSuccess) e = hipMalloc(&dO, sizeof(double) * ldw * slots);
-    if (e == hipSuccess) e = hipMalloc(&slab, sizeof(double) * bq_symm_slab_len(p->nb));
+    if (e == hipSuccess) e = hipMalloc(&slab, sizeof(double) * (wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb)));
     if (e == hipSuccess) e = hipMalloc(&nl, sizeof(int));
     if (e == hipSuccess) e = hipMemsetAsync(dW, 0, sizeof(double) * ldw * slots, c->stream);
     if (e == hipSuccess) e = hipMemcpy2DAsync(dW, sizeof(double) * ldw, W, sizeof(double) * p->n, sizeof(double) * p->n, k,
@@ -362,7 +391,8 @@ extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, dou
         bq_set_error("gram_matmat setup failed: %s", hipGetErrorString(e));
         rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
     }
-    if (rc == BQ_OK) rc = bq_launch_symm(p, false, dW, ldw, k, slab, dO, nl);
+    if (rc == BQ_OK)
+        rc = wide ? bq_launch_symmw(p, false, dW, ldw, k, slab, dO, nl) : bq_launch_symm(p, false, dW, ldw, k, slab, dO, nl);
     if (rc == BQ_OK) {
         e = hipMemcpy2DAsync(out, sizeof(double) * p->n, dO, sizeof(double) * ldw, sizeof(double) * p->n, k, hipMemcpyDeviceToHost,
                              c->stream);
@@ -376,4 +406,24 @@ extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, dou
     for (void *ptr : {(void *)dW, (void *)dO, (void *)slab, (void *)nl})
         if (ptr) hipFree(ptr);
     return rc;
+}
+
+extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out) { return gram_matmat(p, k, W, out, false); }
+
+extern "C" int bq_problem_gram_matmat_wide(bq_problem *p, int k, const double *W, double *out) {
+    return gram_matmat(p, k, W, out, true);
+}
+
+extern "C" int bq_ctx_mem_info(bq_ctx *c, int64_t *free_bytes, int64_t *total_bytes) {
+    BQ_ARG(c && free_bytes && total_bytes, "NULL argument");
+    BQ_HIP(hipSetDevice(c->device));
+    size_t f = 0, t = 0;
+    BQ_HIP(hipMemGetInfo(&f, &t));
+    *free_bytes = (int64_t)f;
+    *total_bytes = (int64_t)t;
+    return BQ_OK;
+}
+
+extern "C" int64_t bq_problem_wide_slab_bytes(const bq_problem *p) {
+    return p == nullptr ? 0 : (int64_t)sizeof(double) * bq_symmw_slab_len(p->nb);
 }

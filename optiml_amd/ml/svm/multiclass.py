@@ -52,10 +52,12 @@ class _DeviceMultiSolver:
         self.k, self.n = Y.shape
         self._h = C.c_void_p()
         Y = _lib.as_f64(Y, self.k * self.n, 'Y')
-        ub = _lib.as_f64(ub, self.n, 'ub')
+        boxes = np.ndim(ub) == 2   # one box per column (k x n): bq_msolver_create_boxes and the 16-column product
+        ub = _lib.as_f64(ub, self.k * self.n if boxes else self.n, 'ub')
         x0 = None if x0 is None else _lib.as_f64(x0, self.k * self.n, 'x0')
-        _lib.check(self._lib.bq_msolver_create(problem.handle, kind, self.k, _lib.ptr(Y), _lib.ptr(ub), _lib.ptr(x0), float(eps),
-                                               int(max_iter), float(t), C.byref(self._h)))
+        create = self._lib.bq_msolver_create_boxes if boxes else self._lib.bq_msolver_create
+        _lib.check(create(problem.handle, kind, self.k, _lib.ptr(Y), _lib.ptr(ub), _lib.ptr(x0), float(eps), int(max_iter), float(t),
+                          C.byref(self._h)))
 
     def run(self, max_steps):
         stats = np.zeros((self.k, max_steps), dtype=_lib.STAT_DTYPE)
@@ -90,7 +92,8 @@ class _DeviceMultiSolver:
 
 
 def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256):
-    """Run the batched solver (`problem`: a device problem of KernelQuadratic 'svc'; Y: k x n labels +-1; ub: n; x0: k x n or None)
+    """Run the batched solver (`problem`: a device problem of KernelQuadratic 'svc'; Y: k x n labels +-1; ub: n, or k x n for one box
+    per column (bq_msolver_create_boxes); x0: k x n or None)
     to the end: per class a dict (rows: the iteration records, status, iter, f_x, x, g) as a single-class optimizer ends them."""
     solver = _DeviceMultiSolver(problem, kind, Y, ub, eps, max_iter, t, x0)
     k = Y.shape[0]
@@ -205,9 +208,11 @@ class OneVsRestSVC(ClassifierMixin, BaseEstimator):
         return self.classes_[np.argmax(scores, axis=1)]
 
 
-def _gram_matmat(problem, W):
-    """OUT[c] = K W[c] for the rows of W, one multi-column product (bq_problem_gram_matmat)."""
+def _gram_matmat(problem, W, wide=False):
+    """OUT[c] = K W[c] for the rows of W, one multi-column product (bq_problem_gram_matmat; wide: the 16-column
+    bq_problem_gram_matmat_wide)."""
     W = np.ascontiguousarray(W, dtype=float)
     out = np.empty_like(W)
-    _lib.check(_lib.load().bq_problem_gram_matmat(problem.handle, W.shape[0], _lib.ptr(W), _lib.ptr(out)))
+    fn = _lib.load().bq_problem_gram_matmat_wide if wide else _lib.load().bq_problem_gram_matmat
+    _lib.check(fn(problem.handle, W.shape[0], _lib.ptr(W), _lib.ptr(out)))
     return out
