@@ -49,6 +49,7 @@ extern "C" {
  * bq_ctx_release_held and the state snapshot were added: a consumer built against version 1 must be rebuilt */
 /* 3: the batched one-vs-rest solver (bq_msolver_*) and bq_problem_gram_matmat were added */
 /* (still 3: bq_msolver_create_boxes and bq_problem_gram_matmat_wide were added; nothing existing changed) */
+/* (still 3: bq_msolver_create_pairs, bq_problem_gram_matmat_pairs, bq_pairs_slab_bytes and bq_pairs_work_list were added) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -239,6 +240,25 @@ int bq_problem_gram_matmat_wide(bq_problem *p, int k, const double *W, double *o
  * product allocates for p: what the search's column cap per solve is computed from (GridSearchCV keeps one fit per process) */
 int bq_ctx_mem_info(bq_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
 int64_t bq_problem_wide_slab_bytes(const bq_problem *p);
+/* ---- one-vs-one pairs on a class-sorted panel (sklearn OneVsOneClassifier._fit_ovo_binary: SVC.fit once per class pair; the
+ * reference's SVC refuses more than two labels, svm/_base.py:231) ---------------------------------------------------------------
+ * The panel's rows are sorted by class and every class owns whole 256-row tile rows: class c is tile rows [cls_tiles[c],
+ * cls_tiles[c + 1]), cls_tiles[0] = 0, strictly increasing, cls_tiles[ncls] = the panel's tile rows (ceil(n / 256)).  pairs: m
+ * pairs (a, b), 2m ints, 0 <= a < b < ncls.  Anything else is BQ_ERR_BADARG.
+ * bq_problem_gram_matmat_pairs: OUT[p] = K W[p] on the rows of classes a and b of pair p and exactly 0 on every other row; W[p]
+ * outside the pair's rows is never read (the pairs' intercepts, svm/_base.py:877-880 once per pair).  W, OUT: m x n row-major host
+ * arrays.  One panel stream for all pairs: an off-diagonal class block is read for its one pair, a class's diagonal block once per
+ * 16 pairs containing the class (bq_symmp.hip).  Column p's bits are a function of W[p] and its pair's classes alone (not those of
+ * bq_problem_gram_matmat_wide: agrees to rounding).  Single-rank context, resident packed panel. */
+int bq_problem_gram_matmat_pairs(bq_problem *p, int ncls, const int *cls_tiles, int m, const int *pairs, const double *W,
+                                 double *out);
+/* device bytes of the slab of a pair solver / product with these pairs (what the number of pairs per solve is sized from) */
+int bq_pairs_slab_bytes(int64_t nb, int ncls, const int *cls_tiles, int m, const int *pairs, int64_t *bytes);
+/* the routed product's strips (host only, for inspection): 5 ints per strip (kind: 0 one pair's off-diagonal block, 1 a class's
+ * diagonal block; tile row I; first tile J0; tiles; the pair (kind 0) or the class (kind 1)); *count: the number of strips,
+ * items == NULL: only *count. */
+int bq_pairs_work_list(int64_t nb, int ncls, const int *cls_tiles, int m, const int *pairs, int *items, int64_t cap,
+                       int64_t *count);
 /* copy rows [row0,row0+nrows) of this rank's resident panel (n columns each) to the host as fp64 */
 int bq_problem_panel_rows(bq_problem *p, int64_t row0, int64_t nrows, double *out);
 /* time `reps` launches of the panel product with HIP events; returns the mean in ms */
@@ -320,6 +340,14 @@ int bq_msolver_destroy(bq_msolver *s);
  * max_iter, fw_t, run / state / get / destroy: as bq_msolver_create. */
 int bq_msolver_create_boxes(bq_problem *p, int kind, int k, const double *Y, const double *UB, const double *x0, double eps,
                             int64_t max_iter, double fw_t, bq_msolver **out);
+/* The boxes solver with one column per one-vs-one pair on a class-sorted panel (sklearn OneVsOneClassifier._fit_ovo_binary:
+ * SVC.fit on the rows of classes a and b, once per pair; the reference's SVC refuses more than two labels, svm/_base.py:231).
+ * cls_tiles, pairs: as bq_problem_gram_matmat_pairs.  Y: m x n labels (+-1); UB: m x n, >= 0 on the rows of the pair's classes and
+ * exactly 0 on every other row (else BQ_ERR_BADARG).  Every pass takes the pair-routed product, which streams the panel once for
+ * all live pairs; a pair that stops leaves the stream at the next iteration.  Pair p's iterates have the same bits alone, at any
+ * position and in any batch.  x0, eps, max_iter, fw_t, run / state / get / destroy: as bq_msolver_create (cls = the pair). */
+int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const int *cls_tiles, int m, const int *pairs, const double *Y,
+                            const double *UB, const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

@@ -57,6 +57,7 @@ EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64,
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
+_ip = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); every symbol include/bcqp.h declares
 PROTOTYPES = {
@@ -98,6 +99,9 @@ PROTOTYPES = {
     'bq_problem_gram_matmat_wide': (C.c_int, [_vp, C.c_int, _dp, _dp]),
     'bq_ctx_mem_info': (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     'bq_problem_wide_slab_bytes': (_i64, [_vp]),
+    'bq_problem_gram_matmat_pairs': (C.c_int, [_vp, C.c_int, _ip, C.c_int, _ip, _dp, _dp]),
+    'bq_pairs_slab_bytes': (C.c_int, [_i64, C.c_int, _ip, C.c_int, _ip, C.POINTER(_i64)]),
+    'bq_pairs_work_list': (C.c_int, [_i64, C.c_int, _ip, C.c_int, _ip, _ip, _i64, C.POINTER(_i64)]),
     'bq_problem_panel_rows': (C.c_int, [_vp, _i64, _i64, _dp]),
     'bq_problem_time_matvec': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_problem_placement': (C.c_int, [_vp, C.POINTER(C.c_int), _dp, C.c_int]),
@@ -117,6 +121,8 @@ PROTOTYPES = {
     'bq_msolver_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     'bq_msolver_destroy': (C.c_int, [_vp]),
     'bq_msolver_create_boxes': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
+    'bq_msolver_create_pairs': (C.c_int, [_vp, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.c_double,
+                                          C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     'bq_al_solver_dual_size': (C.c_int, [_vp, C.POINTER(_i64)]),
     'bq_al_solver_set_schedules': (C.c_int, [_vp, _dp, _dp, _i64]),
@@ -175,3 +181,14 @@ def as_f64(a, n=None, name='array'):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def as_i32(a, n=None, name='array'):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if n is not None and a.size != n:
+        raise ValueError(f'{name} has {a.size} elements, expected {n}')
+    return a
+
+
+def iptr(a):
+    return None if a is None else a.ctypes.data_as(_ip)

@@ -331,6 +331,16 @@ constexpr int BQ_SYMMW_CK = 16;
 int64_t bq_symmw_slab_len(int64_t nb);
 int bq_launch_symmw(bq_problem *p, bool add_one, const double *W, int64_t ldw, int slots, double *slab, double *out,
                     const int *nlive);
+// bq_symmp.hip: the pair-routed product of a class-sorted panel (class c: tile rows [cls_tiles[c], cls_tiles[c + 1])): OUT[:, p] =
+// P W[:, p] on the rows of pair p = (a, b), 0 elsewhere (never written: OUT starts at 0), for the live pairs of the plan.  The plan
+// holds the work lists, the per-pair slab layout and the device liveness (every pair live at creation; bq_launch_pairs_live
+// refreshes it from the pairs' solver states).  slab: bq_pairs_slab_len(plan) doubles.
+struct bq_pairs_plan;
+int bq_pairs_plan_create(bq_problem *p, int ncls, const int *cls_tiles, int m, const int *pairs, bq_pairs_plan **out);
+void bq_pairs_plan_destroy(bq_pairs_plan *pl);
+int64_t bq_pairs_slab_len(const bq_pairs_plan *pl);
+int bq_launch_symmp(bq_problem *p, const bq_pairs_plan *pl, bool add_one, const double *W, int64_t ldw, double *slab, double *out);
+int bq_launch_pairs_live(const bq_pairs_plan *pl, bq_scal *const *scs, int *nlive, hipStream_t st);
 
 // bq_dense.hip: a dense host Hessian into the resident panel — packed lower tile rows when Q == Q' exactly (checked on the device
 // while uploading, agreed across ranks), else row blocks

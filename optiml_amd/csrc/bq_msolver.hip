@@ -14,6 +14,11 @@
 // training rows and 0 on its held-out rows.  A zero-width box keeps x = 0 there: the mid-box start is 0, PG zeroes d where
 // ub - x <= ACT_TOL and x - lb <= ACT_TOL, FW's vertex is y = ub = lb = 0, so d = 0 and every sum of the column is its training
 // fold's.
+//
+// bq_msolver_create_pairs is the boxes solver on a class-sorted panel with one column per one-vs-one pair (a, b): ub = C on the rows
+// of a and b, 0 elsewhere, and the pair-routed product (bq_symmp.hip) for every pass, which streams the panel once for all pairs.
+// The live kernel is the plan's: it keeps pos[] the identity (column = pair) and gathers every class's live pairs into the slots of
+// its diagonal block; a stopped pair's blocks leave the stream at the next iteration.
 #include "bq_common.h"
 #include "bq_epilogue.h"
 
@@ -24,6 +29,7 @@ struct bq_msolver {
     bq_problem *p = nullptr;
     int kind = BQ_PG, k = 0;
     bool wide = false;   // bq_msolver_create_boxes: the 16-column product (bq_symmw.hip) for every pass
+    bq_pairs_plan *plan = nullptr;   // bq_msolver_create_pairs: the pair-routed product (bq_symmp.hip) for every pass
     int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ldN >= nb * 256)
     std::vector<bq_solver *> cls;
     double *sgn = nullptr, *W = nullptr, *out = nullptr, *slab = nullptr;
@@ -103,6 +109,7 @@ extern "C" int bq_msolver_destroy(bq_msolver *m) {
         hipEventDestroy(m->flag_event);
     }
     for (bq_solver *s : m->cls) bq_solver_destroy(s);
+    bq_pairs_plan_destroy(m->plan);
     bq_problem *p = m->p;
     delete m;
     bq_problem_unref(p);
@@ -148,13 +155,17 @@ static int msolver_ck(const bq_msolver *m) { return m->wide ? BQ_SYMMW_CK : BQ_S
 
 static int msolver_product(bq_msolver *m, int slots) {
     bq_problem *p = m->p;
+    if (m->plan) return bq_launch_symmp(p, m->plan, p->add_one, m->W, m->ldw, m->slab, m->out);
     if (m->wide) return bq_launch_symmw(p, p->add_one, m->W, m->ldw, slots, m->slab, m->out, m->nlive);
     return bq_launch_symm(p, p->add_one, m->W, m->ldw, slots, m->slab, m->out, m->nlive);
 }
 
-// ub_ld: 0 (one box for every class) or n (class c's box at ub + c * n)
+// ub_ld: 0 (one box for every class) or n (class c's box at ub + c * n); plan: the pair-routed product (taken over by the solver)
 static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, int64_t ub_ld, bool wide,
-                          const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
+                          const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out,
+                          bq_pairs_plan *plan = nullptr);
+
+static int msolver_check(bq_problem *p, int kind, int k, const double *Y, const double *ub, bq_msolver **out) {
     BQ_ARG(p && Y && ub && out, "NULL argument");
     BQ_ARG(kind == BQ_PG || kind == BQ_FW, "the batched solver is ProjectedGradient or FrankWolfe");
     BQ_ARG(k >= 1, "k must be >= 1");
@@ -164,6 +175,15 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
         return BQ_ERR_BADARG;
     }
     for (int64_t i = 0; i < (int64_t)k * p->n; ++i) BQ_ARG(Y[i] == 1.0 || Y[i] == -1.0, "labels must be +1 or -1");
+    return BQ_OK;
+}
+
+static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, int64_t ub_ld, bool wide,
+                          const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out, bq_pairs_plan *plan) {
+    if (int rc = msolver_check(p, kind, k, Y, ub, out)) {
+        bq_pairs_plan_destroy(plan);
+        return rc;
+    }
     bq_ctx *c = p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     bq_msolver *m = new bq_msolver();
@@ -173,6 +193,7 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
     m->k = k;
     m->ldw = p->ldN;
     m->wide = wide;
+    m->plan = plan;
     const int slots = (int)bq_round_up(k, msolver_ck(m));
     int rc = BQ_OK;
     for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
@@ -188,7 +209,8 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
     hipError_t e = hipMalloc(&m->sgn, sizeof(double) * m->ldw * k);
     if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
     if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
-    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * (wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb)));
+    const int64_t slab_len = plan ? bq_pairs_slab_len(plan) : wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb);
+    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * slab_len);
     if (e == hipSuccess) e = hipMalloc(&m->epi, sizeof(bq_epilogue) * 2 * k);
     if (e == hipSuccess) e = hipMalloc(&m->scs, sizeof(bq_scal *) * k);
     if (e == hipSuccess) e = hipMalloc(&m->pos, sizeof(int) * k);
@@ -241,6 +263,29 @@ extern "C" int bq_msolver_create_boxes(bq_problem *p, int kind, int k, const dou
     return msolver_create(p, kind, k, Y, UB, p->n, true, x0, eps, max_iter, fw_t, out);
 }
 
+extern "C" int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const int *cls_tiles, int m, const int *pairs,
+                                       const double *Y, const double *UB, const double *x0, double eps, int64_t max_iter, double fw_t,
+                                       bq_msolver **out) {
+    BQ_TRY(msolver_check(p, kind, m, Y, UB, out));
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    bq_pairs_plan *plan = nullptr;
+    BQ_TRY(bq_pairs_plan_create(p, ncls, cls_tiles, m, pairs, &plan));   // validates cls_tiles and pairs
+    for (int q = 0; q < m; ++q) {
+        const int64_t a0 = (int64_t)cls_tiles[pairs[2 * q]] * BQ_SYM_TILE, a1 = (int64_t)cls_tiles[pairs[2 * q] + 1] * BQ_SYM_TILE;
+        const int64_t b0 = (int64_t)cls_tiles[pairs[2 * q + 1]] * BQ_SYM_TILE, b1 = (int64_t)cls_tiles[pairs[2 * q + 1] + 1] * BQ_SYM_TILE;
+        for (int64_t i = 0; i < p->n; ++i) {
+            const double u = UB[q * p->n + i];
+            const bool mine = (i >= a0 && i < a1) || (i >= b0 && i < b1);
+            if (!(u >= 0.0) || (!mine && u != 0.0)) {
+                bq_pairs_plan_destroy(plan);
+                bq_set_error("bad argument: upper bounds must be >= 0 on the pair's rows and 0 on every other row");
+                return BQ_ERR_BADARG;
+            }
+        }
+    }
+    return msolver_create(p, kind, m, Y, UB, p->n, false, x0, eps, max_iter, fw_t, out, plan);
+}
+
 static int msolver_first(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
@@ -263,6 +308,7 @@ static int msolver_iterate(bq_msolver *m) {
     BQ_HIP(hipGetLastError());
     BQ_TRY(msolver_product(m, m->live_host));
     mfinish_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->out, m->ldw);
+    if (m->plan) return bq_launch_pairs_live(m->plan, m->scs, m->nlive, st);
     mlive_kernel<<<1, 64, 0, st>>>(m->scs, m->k, m->pos, m->nlive);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
@@ -302,7 +348,7 @@ extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *st
     }
     // bq_solver_run's lagged look at the device, here at the number of live classes: about every 20 ms of estimated streaming
     const double esz = m->p->storage == BQ_F64 ? 8.0 : 4.0;
-    const double passes = (double)((m->live_host + msolver_ck(m) - 1) / msolver_ck(m));
+    const double passes = m->plan ? 1.0 : (double)((m->live_host + msolver_ck(m) - 1) / msolver_ck(m));
     const double iter_s = passes * (double)m->p->n * (double)m->p->n * esz * 0.5 / 5.0e12 + 30e-6 * m->k;
     int64_t poll = (int64_t)(20.0e-3 / iter_s);
     poll = poll < 1 ? 1 : (poll > 64 ? 64 : poll);

@@ -1,5 +1,6 @@
-__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'SVCGridSearchCV']
+__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
+from .onevsone import OneVsOneSVC
 from .model_selection import SVCGridSearchCV

@@ -27,6 +27,7 @@ from ...opti.constrained import ProjectedGradient
 from ._base import SVC
 from .kernels import BaseEstimator, LinearKernel
 from .multiclass import OneVsRestSVC, uses_batched_path, binarize, solve_batched, _gram_matmat
+from .onevsone import OneVsOneSVC
 
 __all__ = ['SVCGridSearchCV', 'parameter_grid', 'check_cv_splits', 'plan_columns', 'aggregate_scores', 'uses_batched_search']
 
@@ -64,7 +65,7 @@ def check_cv_splits(cv, X, y):
 
 
 def _base_params(estimator):
-    return {name: getattr(estimator, name) for name in estimator._kw} if isinstance(estimator, OneVsRestSVC) else \
+    return {name: getattr(estimator, name) for name in estimator._kw} if isinstance(estimator, (OneVsRestSVC, OneVsOneSVC)) else \
         dict(estimator.get_params(deep=False))
 
 
@@ -193,7 +194,8 @@ def _device_column_cap(dev, n):
 
 
 class SVCGridSearchCV(BaseEstimator):
-    """Exhaustive search over `param_grid` for an `SVC` or `OneVsRestSVC` scored by accuracy, as sklearn's GridSearchCV.
+    """Exhaustive search over `param_grid` for an `SVC` or `OneVsRestSVC` scored by accuracy, as sklearn's GridSearchCV.  A
+    `OneVsOneSVC` runs GridSearchCV's per-fold calls, each fold's fit one batched one-vs-one solve.
 
     After `fit`: `cv_results_` (params, param_<key>, split<i>_test_score, mean / std / rank_test_score — no timing keys: the
     candidates' fits are one batched solve and have no fit time of their own), `best_index_` (first among ties), `best_params_`,
@@ -212,8 +214,8 @@ class SVCGridSearchCV(BaseEstimator):
     def fit(self, X, y):
         if self.scoring is not None:
             raise NotImplementedError('only accuracy scoring (scoring=None) is implemented')
-        if not isinstance(self.estimator, (SVC, OneVsRestSVC)):
-            raise TypeError('estimator must be an SVC or a OneVsRestSVC')
+        if not isinstance(self.estimator, (SVC, OneVsRestSVC, OneVsOneSVC)):
+            raise TypeError('estimator must be an SVC, a OneVsRestSVC or a OneVsOneSVC')
         X = np.ascontiguousarray(X, dtype=float)
         y = np.asarray(y)
         candidates = parameter_grid(self.param_grid)
@@ -243,7 +245,7 @@ class SVCGridSearchCV(BaseEstimator):
             for f, (tr, te) in enumerate(splits):
                 est = _make(etype, base, {}).set_params(**p).fit(X[tr], y[tr])
                 scores[ci, f] = est.score(X[te], y[te])
-                fits = est.estimators_ if isinstance(est, OneVsRestSVC) else [est]
+                fits = est.estimators_ if isinstance(est, (OneVsRestSVC, OneVsOneSVC)) else [est]
                 recs[ci][f] = [(int(getattr(e.optimizer, 'iter', -1)), str(getattr(e.optimizer, 'status', ''))) for e in fits]
         width = max(len(r) for row in recs for r in row)
         n_iter = np.full((nc, ns, width), -1, dtype=np.int64)

@@ -91,11 +91,12 @@ class _DeviceMultiSolver:
             pass
 
 
-def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256):
+def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None):
     """Run the batched solver (`problem`: a device problem of KernelQuadratic 'svc'; Y: k x n labels +-1; ub: n, or k x n for one box
     per column (bq_msolver_create_boxes); x0: k x n or None)
-    to the end: per class a dict (rows: the iteration records, status, iter, f_x, x, g) as a single-class optimizer ends them."""
-    solver = _DeviceMultiSolver(problem, kind, Y, ub, eps, max_iter, t, x0)
+    to the end: per class a dict (rows: the iteration records, status, iter, f_x, x, g) as a single-class optimizer ends them.
+    solver: an already created solver of these columns (the one-vs-one pair solver) instead of bq_msolver_create(_boxes)."""
+    solver = _DeviceMultiSolver(problem, kind, Y, ub, eps, max_iter, t, x0) if solver is None else solver
     k = Y.shape[0]
     try:
         rows = [[] for _ in range(k)]
