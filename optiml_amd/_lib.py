@@ -23,6 +23,7 @@ GET_X, GET_G, GET_LP, GET_LM, GET_D, GET_MASK_L, GET_MASK_U, GET_X_NOW, GET_G_NO
 NO_RANK_ONE = 16
 FULL_PANEL = 32
 PLACE_PANEL = 64
+PLAIN_PANEL = 128
 DENSE_ROWS, DENSE_LOWER = 256, 512   # OR-ed into the storage of bq_problem_create_dense
 SMO_ALPHAS, SMO_ERRORS, SMO_SCALARS, SMO_STATS = range(4)
 RULE_SGD, RULE_ADAM, RULE_AMSGRAD, RULE_ADAMAX, RULE_ADAGRAD, RULE_ADADELTA, RULE_RMSPROP = range(7)

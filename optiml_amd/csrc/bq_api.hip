@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "bq_al.h"
+#include "bq_c7.h"
 
 static thread_local std::string g_last_error;
 
@@ -381,10 +382,12 @@ static int problem_layout(bq_problem *p, int64_t n, int64_t N) {
         rows = p->r1 - p->r0;
     }
     if (p->streamed) return BQ_OK;   // no resident panel
-    const size_t esz = p->storage == BQ_F64 ? 8 : 4;
+    // compact fp64 panels (bq_c7.h, packed layout only) take 7 bytes per element
+    const size_t esz = p->compact ? 7 : p->storage == BQ_F64 ? 8 : 4;
     // symmetric panels are stored packed: tile row I keeps (I+1)*256 columns
     const size_t elems = p->symmetric ? (size_t)(bq_sym_off(p->I1) - bq_sym_off(p->I0))
                                       : (size_t)(rows > 0 ? rows : 1) * (size_t)p->ld;
+    p->panel_elems = (int64_t)elems;
     size_t bytes = (elems > 0 ? elems : 1) * esz;
     const size_t data_bytes = bytes;
     hipError_t e = hipSuccess;
@@ -565,10 +568,10 @@ static int place_panel(bq_problem *p, double first_alloc_ms) {
     BQ_HIP(hipEventCreate(&sc.e0));
     BQ_HIP(hipEventCreate(&sc.e1));
     auto time_on = [&](void *panel, double *ms_out) -> int {
-        int rc = bq_launch_symv(c, panel, p->storage, p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);   // warm
+        int rc = bq_launch_symv(c, bq_problem_panel(p, panel), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);   // warm
         hipEventRecord(sc.e0, c->stream);
         for (int i = 0; rc == BQ_OK && i < 4; ++i)
-            rc = bq_launch_symv(c, panel, p->storage, p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);
+            rc = bq_launch_symv(c, bq_problem_panel(p, panel), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);
         hipEventRecord(sc.e1, c->stream);
         hipError_t he = hipEventSynchronize(sc.e1);
         float ms = 0.f;
@@ -650,8 +653,8 @@ extern "C" int bq_problem_create_kernel(bq_ctx *c, int structure, int64_t n, int
                                         double diag_add, const double *q, int storage, bq_problem **out) {
     BQ_ARG(c && X && q && out, "NULL argument");
     const bool no_rank_one = (structure & BQ_NO_RANK_ONE) != 0, full_panel = (structure & BQ_FULL_PANEL) != 0;
-    const bool place = (structure & BQ_PLACE_PANEL) != 0;
-    structure &= ~(BQ_NO_RANK_ONE | BQ_FULL_PANEL | BQ_PLACE_PANEL);
+    const bool place = (structure & BQ_PLACE_PANEL) != 0, plain_panel = (structure & BQ_PLAIN_PANEL) != 0;
+    structure &= ~(BQ_NO_RANK_ONE | BQ_FULL_PANEL | BQ_PLACE_PANEL | BQ_PLAIN_PANEL);
     BQ_ARG(structure == BQ_PLAIN || structure == BQ_SVC || structure == BQ_SVR, "structure");
     BQ_ARG(structure != BQ_SVC || y != nullptr, "labels required for BQ_SVC");
     BQ_ARG(kernel >= BQ_KERNEL_LINEAR && kernel <= BQ_KERNEL_LAPLACIAN, "kernel");
@@ -676,13 +679,6 @@ extern "C" int bq_problem_create_kernel(bq_ctx *c, int structure, int64_t n, int
     // Gram panels are symmetric: store and stream only the tiles on/below the diagonal, unless the caller asked for whole rows
     // (BQ_FULL_PANEL).  Streamed problems take the same segment partition of the tile rows and form each lower-triangle tile once.
     p->symmetric = p->streamed || !full_panel;
-    int rc = problem_layout(p, n, structure == BQ_SVR ? 2 * n : n);
-    if (rc == BQ_OK) rc = problem_alloc_common(p, q);
-    if (rc == BQ_OK && place) rc = place_panel(p, p->alloc_ms);
-    if (rc != BQ_OK) {
-        bq_problem_destroy(p);
-        return rc;
-    }
     auto fail = [&](hipError_t e) {
         bq_set_error("kernel problem setup failed: %s", hipGetErrorString(e));
         bq_problem_destroy(p);
@@ -691,15 +687,46 @@ extern "C" int bq_problem_create_kernel(bq_ctx *c, int structure, int64_t n, int
     hipError_t e;
     if ((e = hipMalloc(&p->X, sizeof(double) * n * d)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(p->X, X, sizeof(double) * n * d, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e);
+    int rc = BQ_OK;
+    // An RBF panel in fp64 whose every element lies in [2^-14, 1] (bq_c7_eligible: a function of X and gamma only, so every rank
+    // decides alike) is stored in the compact 7-byte layout; BQ_PLAIN_PANEL (SMO) and hook compact_panel=0 keep the plain one
+    if (kernel == BQ_KERNEL_RBF && storage == BQ_F64 && p->symmetric && !p->streamed && !plain_panel && bq_compact_allowed()) {
+        double m2 = 0.0;
+        rc = bq_max_sq_norm(c, p->X, n, d, &m2);
+        p->compact = rc == BQ_OK && bq_c7_eligible(gamma, m2);
+    }
+    if (rc == BQ_OK) rc = problem_layout(p, n, structure == BQ_SVR ? 2 * n : n);
+    if (rc == BQ_OK) rc = problem_alloc_common(p, q);
+    if (rc == BQ_OK && place) rc = place_panel(p, p->alloc_ms);
+    if (rc != BQ_OK) {
+        bq_problem_destroy(p);
+        return rc;
+    }
     if (structure == BQ_SVC) {
         if ((e = hipMalloc(&p->sgn, sizeof(double) * p->ld)) != hipSuccess) return fail(e);
         if ((e = hipMemsetAsync(p->sgn, 0, sizeof(double) * p->ld, c->stream)) != hipSuccess) return fail(e);
         if ((e = hipMemcpyAsync(p->sgn, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e);
     }
+    int bad = 0;
     if (p->streamed)
         rc = bq_stream_prepare(c, p->X, n, d, p->I0 * BQ_SYM_TILE, p->I1 * BQ_SYM_TILE, &p->stream_img);
     else
-        rc = bq_launch_gram(c, p->X, n, d, p->r0, p->r1, kernel, gamma, coef0, degree, p->panel, storage, p->ld, p->symmetric);
+        rc = bq_launch_gram(c, p->X, n, d, p->r0, p->r1, kernel, gamma, coef0, degree, p->panel, p->compact ? BQ_F64C : storage, p->ld,
+                            p->symmetric, p->panel_elems, &bad);
+    if (rc == BQ_OK && p->compact) {
+        // the safety net of the compact layout: an element the build could not store (the eligibility bound makes this
+        // unreachable) on ANY rank sends every rank back to the plain layout — a wrong panel is never streamed
+        bool any = bad != 0;
+        rc = bq_dense_agree(c, bad != 0, &any);
+        if (rc == BQ_OK && any) {
+            hipFree(p->panel_alloc);
+            p->panel = p->panel_alloc = nullptr;
+            p->compact = false;
+            rc = problem_layout(p, n, structure == BQ_SVR ? 2 * n : n);
+            if (rc == BQ_OK)
+                rc = bq_launch_gram(c, p->X, n, d, p->r0, p->r1, kernel, gamma, coef0, degree, p->panel, storage, p->ld, p->symmetric);
+        }
+    }
     if (rc != BQ_OK) {
         bq_problem_destroy(p);
         return rc;
@@ -777,6 +804,27 @@ extern "C" int bq_problem_panel_rows(bq_problem *p, int64_t row0, int64_t nrows,
     bq_ctx *c = p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     if (nrows == 0) return BQ_OK;
+    if (p->symmetric && p->compact) {   // the compact layout: the row's stretch of each plane, decoded here
+        const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
+        std::vector<uint32_t> lo((size_t)p->n);
+        std::vector<uint16_t> mid((size_t)p->n);
+        std::vector<uint8_t> top((size_t)p->n);
+        for (int64_t r = 0; r < nrows; ++r) {
+            const int64_t i = row0 + r;
+            const int64_t len = std::min(p->n, bq_sym_pitch(i / BQ_SYM_TILE)), a = bq_sym_addr(i, 0, p->I0);
+            BQ_HIP(hipMemcpyAsync(lo.data(), pv.lo + a, (size_t)len * 4, hipMemcpyDeviceToHost, c->stream));
+            BQ_HIP(hipMemcpyAsync(mid.data(), pv.mid + a, (size_t)len * 2, hipMemcpyDeviceToHost, c->stream));
+            BQ_HIP(hipMemcpyAsync(top.data(), pv.top + a, (size_t)len, hipMemcpyDeviceToHost, c->stream));
+            BQ_SYNC(c);
+            double *o = out + r * p->n;
+            for (int64_t j = 0; j < len; ++j) {
+                const uint64_t b = bq_c7_bits(lo[j], mid[j], top[j]);
+                std::memcpy(&o[j], &b, sizeof(double));
+            }
+            for (int64_t j = len; j < p->n; ++j) o[j] = 0.0;
+        }
+        return BQ_OK;
+    }
     if (p->symmetric) {
         // packed layout: row i holds its (I+1)*256 leading columns; the rest of the output row (strictly-upper tiles) is 0
         const size_t esz = p->storage == BQ_F64 ? 8 : 4;
@@ -824,7 +872,7 @@ extern "C" int bq_problem_time_matvec(bq_problem *p, int reps, double *mean_ms) 
         if (p->streamed)
             return bq_stream_sym_product(c, p->stream_img, p->n, p->nb, tab, p->kernel, p->gamma, p->coef0, p->degree, p->add_one, p->w,
                                          p->s, 0, nullptr);
-        return p->symmetric ? bq_launch_symv(c, p->panel, p->storage, p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr)
+        return p->symmetric ? bq_launch_symv(c, bq_problem_panel(p), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr)
                             : bq_launch_gemv(c, p->panel, p->storage, p->add_one, p->r1 - p->r0, p->ld, p->w,
                                              p->s + p->r0, nullptr);
     };

@@ -86,7 +86,7 @@ __global__ void as_schur_rhs0_kernel(int64_t n0, int64_t np0, const int *__restr
 // the column of a new slot: e_pos for a base variable that reached a bound, Q[A0, var] for a freed variable
 template <typename T>
 __global__ void as_schur_col_kernel(int kind, int var, int pos, int64_t n0, int64_t np0, const int *__restrict__ idx0,
-                                    int structure, const T *__restrict__ panel, int64_t ldp, int packed, int64_t n,
+                                    int structure, bq_pptr<T> panel, int64_t ldp, int packed, int64_t n,
                                     const double *__restrict__ sgn, double diag_add, double *__restrict__ out,
                                     double *__restrict__ out2) {
     const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void as_schur_dots_kernel(int mode, int k, con
                                                             const double *__restrict__ v, const double *__restrict__ v1,
                                                             int64_t cap, int64_t np0,
                                                             const int *__restrict__ meta, int structure,
-                                                            const T *__restrict__ panel, int64_t ldp, int packed, int64_t n,
+                                                            bq_pptr<T> panel, int64_t ldp, int packed, int64_t n,
                                                             const double *__restrict__ sgn, double diag_add,
                                                             const unsigned char *__restrict__ mU,
                                                             const double *__restrict__ lb, const double *__restrict__ ub,
@@ -348,7 +348,7 @@ bool as_schur_enabled() {
     return bq_hook_on("as_schur");
 }
 
-#define AS_PANEL_ARGS(T) p->structure, (const T *)p->panel, p->ld, p->symmetric ? 1 : 0, p->n, p->sgn, p->diag_add
+#define AS_PANEL_ARGS(T) p->structure, bq_panel_as<T>(p), p->ld, p->symmetric ? 1 : 0, p->n, p->sgn, p->diag_add
 
 void as_schur_free(as_ws *w) {
     as_schur *c = w->sch;
@@ -623,7 +623,9 @@ int as_schur_step(bq_solver *s, as_ws *w, int64_t nA, bool *solved) {
             c->reused += 1;
         }
         bool good = false;
-        if (s->p->storage == BQ_F64)
+        if (s->p->compact)
+            BQ_TRY(as_schur_solve_t<bq_c7>(s, w, computed, &good));
+        else if (s->p->storage == BQ_F64)
             BQ_TRY(as_schur_solve_t<double>(s, w, computed, &good));
         else
             BQ_TRY(as_schur_solve_t<float>(s, w, computed, &good));

@@ -697,7 +697,7 @@ int bq_chol_solve(bq_chol_ws *ws, int64_t np, int64_t first_nonzero, double *als
 // H assembly: H[a][b] = Q[idx[a]][idx[b]] (+ hd[a] on the diagonal) for b <= a < m; identity on the pad
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-__global__ void build_h_kernel(int structure, const T *__restrict__ panel, int64_t ldp, int packed, int64_t n,
+__global__ void build_h_kernel(int structure, bq_pptr<T> panel, int64_t ldp, int packed, int64_t n,
                                const double *__restrict__ sgn, double diag_add, const int *__restrict__ idx, int64_t m,
                                int64_t np, const double *__restrict__ hd, double *__restrict__ H, int64_t ldh, int full) {
     const int64_t a0 = (int64_t)blockIdx.y * 32, b0 = (int64_t)blockIdx.x * 32;
@@ -727,7 +727,10 @@ int bq_chol_build_h(bq_chol_ws *ws, bq_problem *p, const int *idx, int64_t m, co
     BQ_ARG(np <= ws->cap, "H larger than the workspace");
     BQ_ARG(p->r0 == 0 && p->r1 == p->n, "the factorisation needs the whole panel on this rank");
     dim3 grid((unsigned)((np + 31) / 32), (unsigned)((np + 31) / 32));
-    if (p->storage == BQ_F64)
+    if (p->compact)
+        build_h_kernel<bq_c7><<<grid, 256, 0, ws->ctx->stream>>>(structure, bq_c7_view(p->panel, p->panel_elems), p->ld, 1, p->n, p->sgn,
+                                                                p->diag_add, idx, m, np, hd, ws->H, ws->ldh, full ? 1 : 0);
+    else if (p->storage == BQ_F64)
         build_h_kernel<double><<<grid, 256, 0, ws->ctx->stream>>>(structure, (const double *)p->panel, p->ld, p->symmetric ? 1 : 0, p->n, p->sgn,
                                                                  p->diag_add, idx, m, np, hd, ws->H, ws->ldh, full ? 1 : 0);
     else

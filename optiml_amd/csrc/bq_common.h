@@ -45,7 +45,7 @@ void bq_set_error(const char *fmt, ...);
 // can hold it against the long way — nothing a user of the library needs (round 6: these were eighteen BQ_* variables).
 //   rows_per_step=4|8  stream_unit=U  minres_big_min=N  as_schur=0  as_schur_min=N  as_schur_limit=N  as_mailbox=0  as_f_chain=0
 //   as_cg_warm=0  as_cg_incq=0  as_cg_colq=0  as_cg_pc_incr=0  as_cg_pc_class=0..3  ip_svr_reduced=0  smo_helpers=N
-//   panel_good_gbs=G  alloc_fail_above=BYTES  decision_chunk_rows=R  sweep_block=1024|2048|4096
+//   panel_good_gbs=G  alloc_fail_above=BYTES  decision_chunk_rows=R  sweep_block=1024|2048|4096  compact_panel=0
 // ---------------------------------------------------------------------------------------------
 bool bq_hook(const char *name, double *value);                       // true (and *value) when the hook is set
 static inline double bq_hook_value(const char *name, double dflt) {
@@ -165,6 +165,9 @@ struct bq_problem {
     // symmetric mode (kernel-built panels): only tiles on/below the diagonal are stored and streamed; this rank owns
     // the 256-row tile rows [I0, I1) of nb, panel row 0 is global row I0*256
     size_t panel_bytes = 0;    // allocated size of `panel_alloc`
+    // fp64 panel in the compact 7-byte layout of bq_c7.h (eligible RBF panels; storage stays BQ_F64): three planes of panel_elems
+    bool compact = false;
+    int64_t panel_elems = 0;
     void *panel_alloc = nullptr;   // what the allocator handed out; `panel` = panel_alloc (round 4's offset experiment — no effect — is gone)
     int place_tried = 0;       // BQ_PLACE_PANEL: placements timed, and the product's launch time on each
     double place_ms[32] = {0.0};
@@ -278,6 +281,20 @@ void bq_ctx_cache_put(bq_ctx *ctx, void *panel, size_t bytes);
 void bq_ctx_hold(bq_ctx *ctx, void *ptr, size_t bytes, const void *owner);   // keep an unused allocation until bq_ctx_release_held
 void bq_ctx_release_held(bq_ctx *ctx, const void *owner);                    // owner's blocks (null: all) go back to the driver
 
+// A resident panel as the launchers take it: storage BQ_F64 / BQ_F32, or BQ_F64C — internal, never a public storage code: an fp64
+// panel in the compact layout of bq_c7.h, whose three planes lie `elems` elements apart in the one allocation at `base`.
+constexpr int BQ_F64C = 16;
+struct bq_panel_ref {
+    const void *base;
+    int storage;
+    int64_t elems;
+};
+static inline bq_panel_ref bq_problem_panel(const bq_problem *p, const void *base = nullptr) {   // base: a candidate allocation
+    return {base ? base : p->panel, p->compact ? BQ_F64C : p->storage, p->panel_elems};
+}
+// hook compact_panel=0: eligible RBF panels keep the plain fp64 layout (the A/B of the two layouts in one build)
+static inline bool bq_compact_allowed() { return bq_hook_on("compact_panel"); }
+
 // bq_symv.hip: symmetric tile product over tile rows [I0, I1) -> out (nb*256 partial sums)
 constexpr int64_t BQ_SYM_TILE = 256;
 // Packed layout of a symmetric (kernel-built) panel: tile row I (256 rows) keeps only its columns [0, (I+1)*256), stored
@@ -306,11 +323,11 @@ struct bq_seg_table {
 };
 // tiles of the segments [tab.lo, tab.hi) + their sum in segment order -> out (nb*256)
 struct bq_epilogue;   // bq_epilogue.h: the PG / FW step fused into the kernel that finishes the product (null: none)
-int bq_launch_symv(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nb, const bq_seg_table &tab,
+int bq_launch_symv(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,
                    const double *w, double *slab, double *out, const int *done, const bq_epilogue *epi = nullptr);
 // the same with the segment partials written to `gath` (slots of this rank) instead of one summed vector; and the closing
 // sum of all S gathered segment vectors -> out
-int bq_launch_symv_segments(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nb, const bq_seg_table &tab,
+int bq_launch_symv_segments(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,
                             const double *w, double *slab, double *gath, const int *done);
 int bq_launch_symv_segsum(bq_ctx *ctx, int64_t nb, const bq_seg_table &tab, const double *gath, double *out, const int *done,
                           const bq_epilogue *epi = nullptr);
@@ -353,9 +370,13 @@ int bq_dense_upload_rows(bq_problem *p, const double *Q);
 int bq_launch_gemv(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nrows, int64_t ld,
                    const double *w, double *s_rows, const int *done_flag);
 
-// bq_gram.hip: panel rows [r0,r1) of kernel(X, X) (n x n), written in `storage` dtype with row pitch ld
+// bq_gram.hip: panel rows [r0,r1) of kernel(X, X) (n x n), written in `storage` dtype with row pitch ld.  storage BQ_F64C (RBF,
+// packed): the compact layout of `elems` elements; *bad (device word, cleared here) is raised when an element cannot be stored
 int bq_launch_gram(bq_ctx *ctx, const double *X, int64_t n, int64_t d, int64_t r0, int64_t r1, int kernel,
-                   double gamma, double coef0, int degree, void *panel, int storage, int64_t ld, bool sym_packed);
+                   double gamma, double coef0, int degree, void *panel, int storage, int64_t ld, bool sym_packed,
+                   int64_t elems = 0, int *bad = nullptr);
+// max_i |x_i|^2 of the n x d device matrix X (the eligibility test of the compact layout)
+int bq_max_sq_norm(bq_ctx *ctx, const double *X, int64_t n, int64_t d, double *out);
 // rectangular cross-Gram fused with a coefficient contraction (decision function)
 int bq_launch_decision(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                        const double *SV, const double *coef, double intercept, int64_t t, const double *Xt,

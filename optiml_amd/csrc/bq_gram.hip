@@ -11,6 +11,7 @@
 // chunks of 16 through double-buffered LDS (row pitch 144 doubles: the four k-slices a wave reads in one
 // ds_read_b64 land on disjoint bank halves).  The kernel epilogue applies the RBF / polynomial map and
 // stores in the panel's storage dtype.
+#include "bq_c7.h"
 #include "bq_common.h"
 
 #include "bq_mfma_tile.h"
@@ -52,6 +53,15 @@ __global__ void row_norms_kernel(const double *__restrict__ X, int64_t n, int64_
     out[i] = s;
 }
 
+// the output "pointer" of the Gram kernel: T * for fp64 / fp32 panels, the three planes (+ the flag word) of the compact layout
+template <typename T> struct gram_out {
+    typedef T *__restrict__ ptr;
+    typedef T *row;
+};
+template <> struct gram_out<bq_c7> {
+    typedef bq_c7w ptr;
+    typedef bq_c7w row;
+};
 template <typename T> __device__ __forceinline__ void store_elem(T *p, double v);
 template <> __device__ __forceinline__ void store_elem<double>(double *p, double v) { __builtin_nontemporal_store(v, p); }
 template <> __device__ __forceinline__ void store_elem<float>(float *p, double v) { __builtin_nontemporal_store((float)v, p); }
@@ -68,6 +78,30 @@ __device__ __forceinline__ void store_pair(float *p, double a, double b) {
     v.x = (float)a;
     v.y = (float)b;
     __builtin_nontemporal_store(v, reinterpret_cast<f2 *>(p));
+}
+
+// compact layout (bq_c7.h): an element pair is one 8-byte, one 4-byte and one 2-byte store; an element that has no 7-byte code raises
+// the flag word (the library then builds the panel again in the plain layout: a wrong panel is never streamed)
+__device__ __forceinline__ void c7_flag(const bq_c7w &p, uint64_t a, uint64_t b) {
+    if (!bq_c7_encodable(a) || !bq_c7_encodable(b)) *p.bad = 1;
+}
+__device__ __forceinline__ void store_pair(const bq_c7w &p, double a, double b) {
+    typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
+    const uint64_t ua = (uint64_t)__double_as_longlong(a), ub = (uint64_t)__double_as_longlong(b);
+    c7_flag(p, ua, ub);
+    u2_t lo;
+    lo.x = (uint32_t)ua;
+    lo.y = (uint32_t)ub;
+    __builtin_nontemporal_store(lo, reinterpret_cast<u2_t *>(p.lo));
+    __builtin_nontemporal_store((uint32_t)((ua >> 32) & 0xFFFFu) | ((uint32_t)(ub >> 32) << 16), reinterpret_cast<uint32_t *>(p.mid));
+    __builtin_nontemporal_store((uint16_t)(((ua >> 48) & 0xFFu) | (((ub >> 48) & 0xFFu) << 8)), reinterpret_cast<uint16_t *>(p.top));
+}
+__device__ __forceinline__ void store_elem(const bq_c7w &p, double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    c7_flag(p, u, 0);
+    __builtin_nontemporal_store((uint32_t)u, p.lo);
+    __builtin_nontemporal_store((uint16_t)(u >> 32), p.mid);
+    __builtin_nontemporal_store((uint8_t)(u >> 48), p.top);
 }
 
 // (gamma <x, y> + coef0)^degree: degrees 2 and 3 (the reference's default) by multiplication — pow() is ~150 vector
@@ -112,7 +146,7 @@ constexpr int GRAM_RECT_R = 16, GRAM_RECT_S = 4;
 // lane with the matrix pipe idle, chip-wide in phase — by delaying the first round of workgroups by a phase: five modes x three
 // units measured 25.7 - 26.4 ms against 25.7 - 26.2 ms without, profiles/r04/gram_stagger.txt.  No effect; removed in round 5.)
 template <typename T, int KIND>
-__global__ __launch_bounds__(256, 2) void gram_mfma_kernel(gram_params P, T *__restrict__ out) {
+__global__ __launch_bounds__(256, 2) void gram_mfma_kernel(gram_params P, typename gram_out<T>::ptr out) {
     __shared__ __attribute__((aligned(16))) bq_tile_smem sm;
     int64_t bx = blockIdx.x, by = blockIdx.y;
     if (P.rect_rb > 0) {
@@ -153,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void gram_mfma_kernel(gram_params P, T *__r
         // instead of four).  A row's address is this lane's base (once per tile) + a uniform multiple of the pitch.
         const int64_t pitch = P.lower_only ? bq_sym_pitch(arow / BQ_SYM_TILE) : P.ld;
         const int64_t tile0 = P.lower_only ? bq_sym_addr(arow, 0, I0) : (arow - P.arow0) * P.ld;   // uniform
-        T *const lane_base = out + tile0 + (int64_t)(wr * 64 + 2 * crow) * pitch + bcol + wc * 64 + 2 * ccol;
+        const typename gram_out<T>::row lane_base = out + tile0 + (int64_t)(wr * 64 + 2 * crow) * pitch + bcol + wc * 64 + 2 * ccol;
         double bj[4];   // the squared norms of this lane's four columns, once per tile (b2 is padded to the image pitch)
 #pragma unroll
         for (int j = 0; j < 4; ++j) bj[j] = KIND == BQ_KERNEL_RBF ? P.b2[bcol + bq_acc_col(2 * (j >> 1)) + (j & 1)] : 0.0;
@@ -164,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void gram_mfma_kernel(gram_params P, T *__r
                 for (int v = 0; v < 4; ++v) {
                     const int64_t gi = opaque + arow + bq_acc_row(i, v);
                     if (decltype(on_edge)::value && gi >= P.arow1) continue;
-                    T *rowp = lane_base + (opaque + (i >> 1) * 32 + 8 * v + (i & 1)) * pitch;
+                    const auto rowp = lane_base + (opaque + (i >> 1) * 32 + 8 * v + (i & 1)) * pitch;
                     const double ai = rowsq[wv][bq_acc_row64(i, v)];
 #pragma unroll
                     for (int jp = 0; jp < 2; ++jp) {   // columns j = 2 jp and 2 jp + 1 of this lane are adjacent (even, odd)
@@ -192,7 +226,7 @@ __global__ __launch_bounds__(256, 2) void gram_mfma_kernel(gram_params P, T *__r
                         if (!decltype(on_edge)::value || gj + 1 < P.n)
                             store_pair(rowp + jp * 32, kv[0], kv[1]);
                         else
-                            store_elem<T>(rowp + jp * 32, kv[0]);
+                            store_elem(rowp + jp * 32, kv[0]);
                     }
                     if (KIND == BQ_KERNEL_RBF || KIND == BQ_KERNEL_POLY) __builtin_amdgcn_sched_barrier(0);   // four chains in flight
                 }
@@ -291,7 +325,8 @@ static void free_image(gram_images *img) {
 
 static int run_gram(bq_ctx *ctx, const gram_images &A, const gram_images &B, int64_t m_rows0, int64_t m_rows1,
                     int64_t n, bool same, int kernel, double gamma, double coef0, int degree, void *out,
-                    int storage, int64_t ld, bool lower_only = false) {
+                    int storage, int64_t ld, bool lower_only = false, int64_t elems = 0, int *bad = nullptr) {
+    BQ_ARG(storage != BQ_F64C || (kernel == BQ_KERNEL_RBF && lower_only && bad != nullptr), "compact panels are packed RBF panels");
     gram_params P;
     P.rect_rb = P.rect_sb = P.tiles_m = P.strips = 0;
     P.lower_only = lower_only ? 1 : 0;
@@ -348,7 +383,9 @@ static int run_gram(bq_ctx *ctx, const gram_images &A, const gram_images &B, int
         else                                                                                                           \
             gram_mfma_kernel<float, KIND><<<grid, 256, 0, ctx->stream>>>(P, reinterpret_cast<float *>(out));          \
     } while (0)
-        switch (kernel) {
+        if (storage == BQ_F64C)
+            gram_mfma_kernel<bq_c7, BQ_KERNEL_RBF><<<grid, 256, 0, ctx->stream>>>(P, bq_c7_wview(out, elems, bad));
+        else switch (kernel) {
             case BQ_KERNEL_RBF: BQ_GRAM_LAUNCH(BQ_KERNEL_RBF); break;
             case BQ_KERNEL_POLY: BQ_GRAM_LAUNCH(BQ_KERNEL_POLY); break;
             case BQ_KERNEL_SIGMOID: BQ_GRAM_LAUNCH(BQ_KERNEL_SIGMOID); break;
@@ -362,8 +399,26 @@ static int run_gram(bq_ctx *ctx, const gram_images &A, const gram_images &B, int
 }
 
 int bq_launch_gram(bq_ctx *ctx, const double *X, int64_t n, int64_t d, int64_t r0, int64_t r1, int kernel,
-                   double gamma, double coef0, int degree, void *panel, int storage, int64_t ld, bool sym_packed) {
+                   double gamma, double coef0, int degree, void *panel, int storage, int64_t ld, bool sym_packed,
+                   int64_t elems, int *bad) {
+    if (bad) *bad = 0;
     if (r1 <= r0) return BQ_OK;   // a rank that owns no rows (more ranks than tile rows) has nothing to build
+    int *dbad = nullptr;
+    if (storage == BQ_F64C) {
+        BQ_ARG(bad != nullptr, "the compact layout needs its flag word");
+        BQ_HIP(hipMalloc(&dbad, sizeof(int)));
+        hipError_t e = hipMemsetAsync(dbad, 0, sizeof(int), ctx->stream);
+        if (e != hipSuccess) {
+            hipFree(dbad);
+            BQ_HIP(e);
+        }
+    }
+    struct flag_guard {
+        int *p;
+        ~flag_guard() {
+            if (p) hipFree(p);
+        }
+    } fg{dbad};
     gram_images img;
     // pad the image so that a tile starting at any r0 stays inside it
     int rc = make_image(ctx, X, n, d, &img);
@@ -377,11 +432,28 @@ int bq_launch_gram(bq_ctx *ctx, const double *X, int64_t n, int64_t d, int64_t r
         bq_set_error("row block start %lld is not a multiple of %d", (long long)r0, GT);
         return BQ_ERR_BADARG;
     }
-    rc = run_gram(ctx, img, img, r0, r1, n, true, kernel, gamma, coef0, degree, panel, storage, ld, sym_packed);
+    rc = run_gram(ctx, img, img, r0, r1, n, true, kernel, gamma, coef0, degree, panel, storage, ld, sym_packed, elems, dbad);
     hipError_t e = hipStreamSynchronize(ctx->stream);
     free_image(&img);
     if (rc != BQ_OK) return rc;
     BQ_HIP(e);
+    if (dbad) BQ_HIP(hipMemcpy(bad, dbad, sizeof(int), hipMemcpyDeviceToHost));
+    return BQ_OK;
+}
+
+int bq_max_sq_norm(bq_ctx *ctx, const double *X, int64_t n, int64_t d, double *out) {
+    double *nrm = nullptr;
+    BQ_HIP(hipMalloc(&nrm, sizeof(double) * n));
+    std::vector<double> h((size_t)n);
+    row_norms_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(X, n, d, nrm, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), nrm, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipFree(nrm);
+    BQ_HIP(e);
+    double m = 0.0;
+    for (double v : h) m = (v > m || v != v) ? v : m;   // a NaN norm stays NaN: not eligible
+    *out = m;
     return BQ_OK;
 }
 

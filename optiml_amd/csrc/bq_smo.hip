@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <algorithm>
 
+#include "bq_c7.h"
 #include "bq_common.h"
 
 // -DBQ_SMO_STAMPS: thread 0 of the SVC walker accumulates the time of each phase of a full-sweep round (100 MHz
@@ -190,7 +191,7 @@ __device__ __forceinline__ unsigned int dot_check(long long bits) {
 
 template <typename T>
 struct KView {
-    const T *panel;
+    bq_pview<T> panel;
     int64_t ld;   // 0: packed lower-triangular tile rows; else the pitch of a full square panel (BQ_FULL_PANEL)
     __device__ __forceinline__ double at(int64_t i, int64_t j) const {
         if (ld != 0) return (double)panel[i * ld + j];
@@ -1488,14 +1489,20 @@ extern "C" int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, in
         const SupGlobal G{s->nz, s->cf};
         const int64_t ld = p->symmetric ? 0 : p->ld;
         if (s->task == BQ_SVC) {
-            if (p->storage == BQ_F64)
+            if (p->compact)
+                smo_svc_kernel<bq_c7><<<grid, SMO_T, 0, c->stream>>>(KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, s->n, s->y,
+                                                                      s->a, s->err, G, s->C, s->tol, s->sc, P);
+            else if (p->storage == BQ_F64)
                 smo_svc_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y, s->a,
                                                                        s->err, G, s->C, s->tol, s->sc, P);
             else
                 smo_svc_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y, s->a,
                                                                      s->err, G, s->C, s->tol, s->sc, P);
         } else {
-            if (p->storage == BQ_F64)
+            if (p->compact)
+                smo_svr_kernel<bq_c7><<<grid, SMO_T, 0, c->stream>>>(KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, s->n, s->y,
+                                                                      s->a, s->am, s->err, G, s->C, s->eps, s->tol, s->sc, P);
+            else if (p->storage == BQ_F64)
                 smo_svr_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y, s->a,
                                                                        s->am, s->err, G, s->C, s->eps, s->tol, s->sc, P);
             else

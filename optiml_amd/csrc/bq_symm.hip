@@ -27,7 +27,7 @@ constexpr int SSR = 2;   // rows per step and wave
 static_assert(BQ_SYMM_CK * SSR == 8, "the row partials of a step are the eight values of the halving butterfly");
 
 template <typename T, bool ADD_ONE>
-__global__ __launch_bounds__(256, 2) void symm_tiles_kernel(const T *__restrict__ panel, int64_t nb, const double *__restrict__ W,
+__global__ __launch_bounds__(256, 2) void symm_tiles_kernel(bq_pptr<T> panel, int64_t nb, const double *__restrict__ W,
                                                           int64_t ldw, double *__restrict__ slab, const int *__restrict__ nlive, int ch) {
     constexpr int CK = BQ_SYMM_CK;
     if (ch * CK >= *nlive) return;
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256, 2) void symm_tiles_kernel(const T *__restrict_
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t pitch = bq_sym_pitch(I);
-    const T *rows = panel + bq_sym_off(I) + (int64_t)(wv * 64) * pitch + J0 * ST;
+    const auto rows = panel + bq_sym_off(I) + (int64_t)(wv * 64) * pitch + J0 * ST;
     const double *Wc = W + (int64_t)ch * CK * ldw;
     const int c0 = tile_ld<T>::c0(lane), c1 = tile_ld<T>::c1(lane);
     d2_t wj0[CK][SJG], wj1[CK][SJG];
@@ -175,7 +175,13 @@ int bq_launch_symm(bq_problem *p, bool add_one, const double *W, int64_t ldw, in
     const dim3 tiles((unsigned)strips_before<SJG>(nb)), red((unsigned)nb, BQ_SYMM_CK);
     hipStream_t st = p->ctx->stream;
     for (int ch = 0; ch * BQ_SYMM_CK < slots; ++ch) {
-        if (p->storage == BQ_F64) {
+        if (p->compact) {
+            const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
+            if (add_one)
+                symm_tiles_kernel<bq_c7, true><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
+            else
+                symm_tiles_kernel<bq_c7, false><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
+        } else if (p->storage == BQ_F64) {
             if (add_one)
                 symm_tiles_kernel<double, true><<<tiles, 256, 0, st>>>((const double *)p->panel, nb, W, ldw, slab, nlive, ch);
             else

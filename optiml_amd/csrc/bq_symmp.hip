@@ -23,6 +23,8 @@
 #include <algorithm>
 #include <vector>
 
+#include <type_traits>
+
 #include "bq_common.h"
 #include "bq_symv_tile.h"
 #include "bq_symmw_step.h"
@@ -103,7 +105,7 @@ static int64_t slab_len(const int *ct, int m, const int *pairs) {
 
 // bq_symv.hip's symv_tiles_kernel on one strip of an off-diagonal class block (every tile off the panel's diagonal), one column
 template <typename T, bool ADD_ONE, int SR>
-__global__ __launch_bounds__(256, 2) void symmp_single_kernel(const T *__restrict__ panel, const pitem *__restrict__ items,
+__global__ __launch_bounds__(256, 2) void symmp_single_kernel(bq_pptr<T> panel, const pitem *__restrict__ items,
                                                               const pinfo *__restrict__ info, const int *__restrict__ plive,
                                                               const double *__restrict__ W, int64_t ldw, double *__restrict__ slab) {
     const pitem it = items[blockIdx.x];
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void symmp_single_kernel(const T *__restric
     const int nj = it.nj;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t pitch = bq_sym_pitch(I);
-    const T *rows = panel + bq_sym_off(I) + (int64_t)(wv * 64) * pitch + J0 * ST;
+    const auto rows = panel + bq_sym_off(I) + (int64_t)(wv * 64) * pitch + J0 * ST;
     const double *w = W + (int64_t)it.id * ldw;
     const double *wI = w + I * ST + wv * 64;
     const int c0 = tile_ld<T>::c0(lane), c1 = tile_ld<T>::c1(lane);
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void symmp_single_kernel(const T *__restric
                 d2_t a[SR], b[SR];
 #pragma unroll
                 for (int k = 0; k < SR; ++k) {
-                    const T *row = rows + (int64_t)(step * SR + k) * pitch + j * ST;
+                    const auto row = rows + (int64_t)(step * SR + k) * pitch + j * ST;
                     tile_ld<T>::get(row, lane, a[k], b[k]);
                 }
 #pragma unroll
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void symmp_single_kernel(const T *__restric
 
 // bq_symmw.hip's symmw_tiles_kernel on one strip of class c's diagonal block, the slots being chunk blockIdx.y of c's live pairs
 template <typename T, bool ADD_ONE>
-__global__ __launch_bounds__(256, 2) void symmp_diag_kernel(const T *__restrict__ panel, const pitem *__restrict__ items,
+__global__ __launch_bounds__(256, 2) void symmp_diag_kernel(bq_pptr<T> panel, const pitem *__restrict__ items,
                                                             const pinfo *__restrict__ info, const int *__restrict__ pairs,
                                                             const int *__restrict__ ct, const int *__restrict__ ccnt,
                                                             const int *__restrict__ cslot, int kpad, const double *__restrict__ W,
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void symmp_diag_kernel(const T *__restrict_
     __syncthreads();
 
     const int64_t pitch = bq_sym_pitch(I);
-    const T *base = panel + bq_sym_off(I) + (int64_t)(wv * 64 + s) * pitch + J0 * ST;
+    const auto base = panel + bq_sym_off(I) + (int64_t)(wv * 64 + s) * pitch + J0 * ST;
     auto rowp = [&](int j, int cq, int st) { return base + (int64_t)(16 * st) * pitch + j * ST + 64 * cq; };
 
     const int myq = spair[s];
@@ -506,17 +508,19 @@ int bq_launch_pairs_live(const bq_pairs_plan *pl, bq_scal *const *scs, int *nliv
 }
 
 template <typename T, bool ADD_ONE>
-static void launch_typed(const bq_pairs_plan *pl, const void *panel, bool f32, const double *W, int64_t ldw, double *slab,
+static void launch_typed(const bq_pairs_plan *pl, bq_pptr<T> panel, bool f32, const double *W, int64_t ldw, double *slab,
                          hipStream_t st) {
     if (pl->nsingle > 0) {
-        if (f32)
-            symmp_single_kernel<T, ADD_ONE, 8><<<(unsigned)pl->nsingle, 256, 0, st>>>((const T *)panel, pl->single, pl->info, pl->plive, W, ldw, slab);
+        if constexpr (std::is_same<T, bq_c7>::value)   // the compact layout: 4 rows per step (its decode spills at 8)
+            symmp_single_kernel<T, ADD_ONE, 4><<<(unsigned)pl->nsingle, 256, 0, st>>>(panel, pl->single, pl->info, pl->plive, W, ldw, slab);
+        else if (f32)
+            symmp_single_kernel<T, ADD_ONE, 8><<<(unsigned)pl->nsingle, 256, 0, st>>>(panel, pl->single, pl->info, pl->plive, W, ldw, slab);
         else
-            symmp_single_kernel<T, ADD_ONE, 4><<<(unsigned)pl->nsingle, 256, 0, st>>>((const T *)panel, pl->single, pl->info, pl->plive, W, ldw, slab);
+            symmp_single_kernel<T, ADD_ONE, 4><<<(unsigned)pl->nsingle, 256, 0, st>>>(panel, pl->single, pl->info, pl->plive, W, ldw, slab);
     }
     if (pl->ndiag > 0)
         symmp_diag_kernel<T, ADD_ONE><<<dim3((unsigned)pl->ndiag, (unsigned)pl->nch), 256, 0, st>>>(
-            (const T *)panel, pl->diag, pl->info, pl->dpairs, pl->dct, pl->ccnt, pl->cslot, pl->kpad, W, ldw, slab);
+            panel, pl->diag, pl->info, pl->dpairs, pl->dct, pl->ccnt, pl->cslot, pl->kpad, W, ldw, slab);
 }
 
 int bq_launch_symmp(bq_problem *p, const bq_pairs_plan *pl, bool add_one, const double *W, int64_t ldw, double *slab, double *out) {
@@ -524,12 +528,18 @@ int bq_launch_symmp(bq_problem *p, const bq_pairs_plan *pl, bool add_one, const 
     BQ_ARG(ldw >= p->nb * ST && pl->nb == p->nb, "column stride shorter than the panel, or a plan of another panel");
     hipStream_t st = p->ctx->stream;
     // fp32 tiles are half as wide in bytes: 8 rows per step keep the same bytes in flight per lane (bq_symv.hip)
-    if (p->storage == BQ_F64) {
-        if (add_one) launch_typed<double, true>(pl, p->panel, false, W, ldw, slab, st);
-        else launch_typed<double, false>(pl, p->panel, false, W, ldw, slab, st);
+    if (p->compact) {
+        const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
+        if (add_one) launch_typed<bq_c7, true>(pl, pv, false, W, ldw, slab, st);
+        else launch_typed<bq_c7, false>(pl, pv, false, W, ldw, slab, st);
+    } else if (p->storage == BQ_F64) {
+        const double *pv = (const double *)p->panel;
+        if (add_one) launch_typed<double, true>(pl, pv, false, W, ldw, slab, st);
+        else launch_typed<double, false>(pl, pv, false, W, ldw, slab, st);
     } else {
-        if (add_one) launch_typed<float, true>(pl, p->panel, true, W, ldw, slab, st);
-        else launch_typed<float, false>(pl, p->panel, true, W, ldw, slab, st);
+        const float *pv = (const float *)p->panel;
+        if (add_one) launch_typed<float, true>(pl, pv, true, W, ldw, slab, st);
+        else launch_typed<float, false>(pl, pv, true, W, ldw, slab, st);
     }
     symmp_reduce_kernel<<<dim3((unsigned)pl->lmax, (unsigned)pl->m), 1024, 0, st>>>(slab, pl->info, pl->plive, out, ldw);
     BQ_HIP(hipGetLastError());

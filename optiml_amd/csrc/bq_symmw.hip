@@ -35,7 +35,7 @@ constexpr int WP = 17;     // pitch of the W_J stage (256 rows x 16 slots)
 static_assert(CK == 16, "the column chunk is the MFMA's N");
 
 template <typename T, bool ADD_ONE>
-__global__ __launch_bounds__(256, 2) void symmw_tiles_kernel(const T *__restrict__ panel, int64_t nb, const double *__restrict__ W,
+__global__ __launch_bounds__(256, 2) void symmw_tiles_kernel(bq_pptr<T> panel, int64_t nb, const double *__restrict__ W,
                                                           int64_t ldw, double *__restrict__ slab, const int *__restrict__ nlive, int ch) {
     const int live = *nlive - ch * CK;   // live slots of this chunk
     if (live <= 0) return;
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256, 2) void symmw_tiles_kernel(const T *__restrict
     const double *Wc = W + (int64_t)ch * CK * ldw;
     const int64_t cs = nb * nb * ST;   // slab stride of one column
     // this wave's row r of tile (I, J0 + j), quarter cq, step st: lane row = 64 wv + 16 st + (lane & 15)
-    const T *base = panel + bq_sym_off(I) + (int64_t)(wv * 64 + s) * pitch + J0 * ST;
+    const auto base = panel + bq_sym_off(I) + (int64_t)(wv * 64 + s) * pitch + J0 * ST;
     auto rowp = [&](int j, int cq, int st) { return base + (int64_t)(16 * st) * pitch + j * ST + 64 * cq; };
 
     double wi[4][4];   // W_I[64 wv + 16 st + 4 u + h][s]
@@ -160,7 +160,13 @@ int bq_launch_symmw(bq_problem *p, bool add_one, const double *W, int64_t ldw, i
     const dim3 tiles((unsigned)strips_before<WJG>(nb)), red((unsigned)nb, CK);
     hipStream_t st = p->ctx->stream;
     for (int ch = 0; ch * CK < slots; ++ch) {
-        if (p->storage == BQ_F64) {
+        if (p->compact) {
+            const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
+            if (add_one)
+                symmw_tiles_kernel<bq_c7, true><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
+            else
+                symmw_tiles_kernel<bq_c7, false><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
+        } else if (p->storage == BQ_F64) {
             if (add_one)
                 symmw_tiles_kernel<double, true><<<tiles, 256, 0, st>>>((const double *)p->panel, nb, W, ldw, slab, nlive, ch);
             else

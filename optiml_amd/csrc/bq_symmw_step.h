@@ -16,6 +16,15 @@ template <> struct step_ld<double> {
     }
     static __device__ __forceinline__ double get(const raw &r, int t) { return (t & 1) ? r.v[t >> 1].y : r.v[t >> 1].x; }
 };
+template <> struct step_ld<bq_c7> {   // the compact layout: the fp64 columns, decoded at load
+    struct raw { d2_t v[8]; };
+    static __device__ __forceinline__ int f(int t, int h) { return step_ld<double>::f(t, h); }
+    static __device__ __forceinline__ void load(const bq_c7p &row, int h, raw &r) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) r.v[q] = row.pair(8 * q + 2 * h);
+    }
+    static __device__ __forceinline__ double get(const raw &r, int t) { return (t & 1) ? r.v[t >> 1].y : r.v[t >> 1].x; }
+};
 template <> struct step_ld<float> {
     struct raw { f4_t v[4]; };
     static __device__ __forceinline__ int f(int t, int h) { return 16 * (t >> 2) + 4 * h + (t & 3); }

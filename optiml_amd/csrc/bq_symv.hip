@@ -32,7 +32,7 @@ constexpr int JG_DEFAULT = 8;   // tiles per strip (8 x 2 KiB contiguous per row
 // bit-identical, measured no faster (1/8 shares 0.796 - 0.885 ms cut against 0.801 - 0.832 ms uncut, profiles/r04/symv_row_cut_strips.txt)
 // and removed in round 5 together with the <4,4> <4,8> <2,8> <2,4> tuning variants: HISTORY.md.)
 template <typename T, bool ADD_ONE, int JG, int SR>
-__global__ __launch_bounds__(256, 2) void symv_tiles_kernel(const T *__restrict__ panel, int64_t I0, int64_t nb,
+__global__ __launch_bounds__(256, 2) void symv_tiles_kernel(bq_pptr<T> panel, int64_t I0, int64_t nb,
                                                           const double *__restrict__ w, double *__restrict__ slab,
                                                           const int *__restrict__ done, int *__restrict__ skip, int skip_seq) {
     if (done != nullptr && *done) {
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void symv_tiles_kernel(const T *__restrict_
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // packed symmetric layout: tile row I has pitch (I+1)*256 and starts at bq_sym_off(I) - bq_sym_off(I0)
     const int64_t pitch = bq_sym_pitch(I);
-    const T *rows = panel + (bq_sym_off(I) - bq_sym_off(I0)) + (int64_t)(wv * 64) * pitch + J0 * ST;
+    const auto rows = panel + (bq_sym_off(I) - bq_sym_off(I0)) + (int64_t)(wv * 64) * pitch + J0 * ST;
     const double *wI = w + I * ST + wv * 64;
     const int c0 = tile_ld<T>::c0(lane), c1 = tile_ld<T>::c1(lane);
     d2_t wj0[JG], wj1[JG];
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void symv_tiles_kernel(const T *__restrict_
                 d2_t a[SR], b[SR];
 #pragma unroll
                 for (int k = 0; k < SR; ++k) {
-                    const T *row = rows + (int64_t)(step * SR + k) * pitch + j * ST;
+                    const auto row = rows + (int64_t)(step * SR + k) * pitch + j * ST;
                     tile_ld<T>::get(row, lane, a[k], b[k]);
                 }
 #pragma unroll
@@ -259,7 +259,7 @@ static hipError_t launch_timed(bq_ctx *ctx, bool ext, hipEvent_t e0, hipEvent_t 
 }
 
 template <int JG, int SR>
-static int launch_tiles(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t I0, int64_t I1, int64_t nb,
+static int launch_tiles(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t I0, int64_t I1, int64_t nb,
                         const double *w, double *slab, const int *done) {
     constexpr bool bracket = false;   // (round 4's BQ_PROF_BRACKET=1 — events recorded around the launch — cost 1-2 us per product: removed)
     const int64_t nstrips = strips_before<JG>(I1) - strips_before<JG>(I0);
@@ -277,16 +277,28 @@ static int launch_tiles(bq_ctx *ctx, const void *panel, int storage, bool add_on
     const bool ext = !bracket && e0 != nullptr;
     const dim3 grid((unsigned)nstrips), block(256);
     hipError_t err;
-    if (storage == BQ_F64) {
+    if (panel.storage == BQ_F64C) {
+        if constexpr (SR == 4) {
+            const bq_c7p pv = bq_c7_view(panel.base, panel.elems);
+            if (add_one)
+                err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<bq_c7, true, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
+            else
+                err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<bq_c7, false, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
+        } else {
+            err = hipErrorInvalidValue;   // not built: launch_any keeps the compact layout at 4 rows per step
+        }
+    } else if (panel.storage == BQ_F64) {
+        const double *pv = (const double *)panel.base;
         if (add_one)
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<double, true, JG, SR>, grid, block, (const double *)panel, I0, nb, w, slab, done, skip, skip_seq);
+            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<double, true, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
         else
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<double, false, JG, SR>, grid, block, (const double *)panel, I0, nb, w, slab, done, skip, skip_seq);
+            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<double, false, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
     } else {
+        const float *pv = (const float *)panel.base;
         if (add_one)
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<float, true, JG, SR>, grid, block, (const float *)panel, I0, nb, w, slab, done, skip, skip_seq);
+            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<float, true, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
         else
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<float, false, JG, SR>, grid, block, (const float *)panel, I0, nb, w, slab, done, skip, skip_seq);
+            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<float, false, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
     }
     if (err != hipSuccess) {
         bq_prof_drop(ctx, e0, e1);
@@ -298,10 +310,10 @@ static int launch_tiles(bq_ctx *ctx, const void *panel, int storage, bool add_on
 
 // mode 0: tiles + the sum over this launch's segments -> out (nb*256);  mode 1: tiles + one vector per segment -> gath slots
 template <int SR>
-static int launch_variant(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nb, const bq_seg_table &tab,
+static int launch_variant(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,
                           const double *w, double *slab, double *out, int mode, const int *done, const bq_epilogue *epi) {
     constexpr int JG = JG_DEFAULT;
-    BQ_TRY((launch_tiles<JG, SR>(ctx, panel, storage, add_one, tab.cut[tab.lo], tab.cut[tab.hi], nb, w, slab, done)));
+    BQ_TRY((launch_tiles<JG, SR>(ctx, panel, add_one, tab.cut[tab.lo], tab.cut[tab.hi], nb, w, slab, done)));
     if (mode == 0 && bq_epi_mode(epi) == BQ_EPI_PGFW)
         symv_reduce_kernel<JG, BQ_EPI_PGFW><<<(unsigned)nb, 1024, 0, ctx->stream>>>(slab, nb, tab, out, done, *epi);
     else if (mode == 0 && bq_epi_mode(epi) == BQ_EPI_AL)
@@ -314,7 +326,7 @@ static int launch_variant(bq_ctx *ctx, const void *panel, int storage, bool add_
     return BQ_OK;
 }
 
-static int launch_any(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nb, const bq_seg_table &tab,
+static int launch_any(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,
                       const double *w, double *slab, double *out, int mode, const int *done, const bq_epilogue *epi = nullptr) {
     // Rows per step (loads in flight per wave).  fp32 tiles are half as wide in bytes: 8 rows per step keep the same bytes in
     // flight per lane.  fp64: 4 rows per step, except on short grids whose LAST round of workgroups is sparsely filled (two
@@ -327,19 +339,20 @@ static int launch_any(bq_ctx *ctx, const void *panel, int storage, bool add_one,
     const int64_t strips = strips_before<JG_DEFAULT>(tab.cut[tab.hi]) - strips_before<JG_DEFAULT>(tab.cut[tab.lo]);
     const int64_t slots = 2 * (int64_t)(ctx->num_cu > 0 ? ctx->num_cu : 256);
     const bool sparse_tail = strips >= slots && strips < 8 * slots && 2 * (strips % slots) < slots;
-    const bool eight = force == 8 || (force != 4 && (storage == BQ_F32 || sparse_tail));
-    if (eight) return launch_variant<8>(ctx, panel, storage, add_one, nb, tab, w, slab, out, mode, done, epi);
-    return launch_variant<4>(ctx, panel, storage, add_one, nb, tab, w, slab, out, mode, done, epi);
+    // The compact layout (bq_c7.h) always takes 4: its decode makes the 8-row step spill (12 bytes per lane of scratch).
+    const bool eight = panel.storage != BQ_F64C && (force == 8 || (force != 4 && (panel.storage == BQ_F32 || sparse_tail)));
+    if (eight) return launch_variant<8>(ctx, panel, add_one, nb, tab, w, slab, out, mode, done, epi);
+    return launch_variant<4>(ctx, panel, add_one, nb, tab, w, slab, out, mode, done, epi);
 }
 
-int bq_launch_symv(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nb, const bq_seg_table &tab,
+int bq_launch_symv(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,
                    const double *w, double *slab, double *out, const int *done, const bq_epilogue *epi) {
-    return launch_any(ctx, panel, storage, add_one, nb, tab, w, slab, out, 0, done, epi);
+    return launch_any(ctx, panel, add_one, nb, tab, w, slab, out, 0, done, epi);
 }
 
-int bq_launch_symv_segments(bq_ctx *ctx, const void *panel, int storage, bool add_one, int64_t nb, const bq_seg_table &tab,
+int bq_launch_symv_segments(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,
                             const double *w, double *slab, double *gath, const int *done) {
-    return launch_any(ctx, panel, storage, add_one, nb, tab, w, slab, gath, 1, done);
+    return launch_any(ctx, panel, add_one, nb, tab, w, slab, gath, 1, done);
 }
 
 int bq_launch_symv_segsum(bq_ctx *ctx, int64_t nb, const bq_seg_table &tab, const double *gath, double *out, const int *done,

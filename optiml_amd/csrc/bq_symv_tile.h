@@ -1,6 +1,7 @@
 // Pieces shared by the symmetric panel products (bq_symv.hip: one column; bq_symm.hip: several): the 16-byte tile loads, the
 // linear strip index of a tile row and the fixed-order walk of a slab column.
 #pragma once
+#include "bq_c7.h"
 #include "bq_common.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -18,6 +19,14 @@ template <> struct tile_ld<double> {
     static __device__ __forceinline__ void get(const double *row, int lane, d2_t &a, d2_t &b) {
         a = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(row + 2 * lane));
         b = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(row + 128 + 2 * lane));
+    }
+};
+template <> struct tile_ld<bq_c7> {   // the compact layout (bq_c7.h): per pair one 8-, one 4- and one 2-byte load, same columns as fp64
+    static __device__ __forceinline__ int c0(int lane) { return 2 * lane; }
+    static __device__ __forceinline__ int c1(int lane) { return 128 + 2 * lane; }
+    static __device__ __forceinline__ void get(const bq_c7p &row, int lane, d2_t &a, d2_t &b) {
+        a = row.pair(2 * lane);
+        b = row.pair(128 + 2 * lane);
     }
 };
 template <> struct tile_ld<float> {

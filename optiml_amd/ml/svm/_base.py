@@ -237,7 +237,7 @@ class SVC(ClassifierMixin, SVM):
         if self._is_smo():
             if self.loss != Hinge or self.reg_intercept:
                 raise NotImplementedError('SMO solves the hinge dual with an unregularised intercept')   # :571-573
-            obj = KernelQuadratic(X, -np.ones(n), 'svc', self.kernel, y=y, storage=self.storage, rank_one=False)
+            obj = KernelQuadratic(X, -np.ones(n), 'svc', self.kernel, y=y, storage=self.storage, rank_one=False, compact=False)
             self.obj = obj
             self.optimizer = SMOClassifier(obj, X, y, None, self.kernel, self.C, self.tol, self.verbose).minimize()
             self.alphas_ = self.optimizer.alphas
@@ -313,7 +313,7 @@ class SVR(RegressorMixin, SVM):
         if self._is_smo():
             if self.loss != EpsilonInsensitive or self.reg_intercept:
                 raise NotImplementedError('SMO solves the epsilon-insensitive dual with an unregularised intercept')
-            obj = KernelQuadratic(X, q, 'svr', self.kernel, storage=self.storage, rank_one=False)
+            obj = KernelQuadratic(X, q, 'svr', self.kernel, storage=self.storage, rank_one=False, compact=False)
             self.obj = obj
             self.optimizer = SMORegression(obj, X, y, None, self.kernel, self.C, self.epsilon, self.tol,
                                            self.verbose).minimize()

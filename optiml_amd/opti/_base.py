@@ -231,7 +231,7 @@ class KernelQuadratic(Quadratic):
     _STRUCT = {'plain': _lib.PLAIN, 'svc': _lib.SVC, 'svr': _lib.SVR}
 
     def __init__(self, X, q, structure, kernel, y=None, diag=0.0, storage='f64', rank_one=True, full_panel=False,
-                 tune_placement=False, expected_products=0):
+                 tune_placement=False, expected_products=0, compact=True):
         X = np.ascontiguousarray(X, dtype=float)
         if structure not in self._STRUCT:
             raise ValueError(f'unknown structure {structure}')
@@ -256,6 +256,8 @@ class KernelQuadratic(Quadratic):
         # >= 1 GB; for solvers whose every iteration streams the panel)
         self.tune_placement = bool(tune_placement)
         self.expected_products = float(expected_products or 0)
+        # BQ_PLAIN_PANEL when False: an eligible fp64 RBF panel keeps 8 bytes per element (SMO's single-element gathers)
+        self.compact = bool(compact)
         self.storage = storage
         self.kind, self.gamma, self.coef0, self.degree = kernel.device_spec(X)
         self._dev = None
@@ -268,7 +270,8 @@ class KernelQuadratic(Quadratic):
             ctx.set_placement_budget(self.expected_products)
         _lib.check(lib.bq_problem_create_kernel(
             ctx.handle, self._STRUCT[self.structure] | (0 if self.rank_one else _lib.NO_RANK_ONE) |
-            (_lib.FULL_PANEL if self.full_panel else 0) | (_lib.PLACE_PANEL if self.tune_placement else 0), n, d, _lib.ptr(self.X), _lib.ptr(self.y), self.kind,
+            (_lib.FULL_PANEL if self.full_panel else 0) | (_lib.PLACE_PANEL if self.tune_placement else 0) |
+            (0 if self.compact else _lib.PLAIN_PANEL), n, d, _lib.ptr(self.X), _lib.ptr(self.y), self.kind,
             self.gamma, self.coef0, self.degree, self.diag, _lib.ptr(self.q),
             _lib.STORAGE[self.storage], C.byref(h)))
         return _DeviceProblem(ctx, h)
