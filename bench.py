@@ -17,14 +17,21 @@ communicator cannot be created the run FAILS (exit 3) unless --allow-host-exchan
 
 Rank 0 prints ONE JSON line with `roofline` (HIP-event timing of the panel-product kernel on its own stream against
 8 TB/s HBM, on the bytes that kernel has to move: its lower-triangle tiles + partial-product slab; `frac_survey_8d_bytes`
-restates it in SURVEY 8(d)'s n^2*s bytes, which the kernel does not move), `cpu_baseline` (the NumPy oracle in the reference
-formulation timed at two sizes that fit the host and extrapolated with the fitted exponent) and `time_to_kkt`.
+restates it in SURVEY 8(d)'s n^2*s bytes, which the kernel does not move).
 
-The DEFAULT single-GPU line (no workload flag: what the driver runs) also carries, after the headline record is complete and each
-in a fresh child process of its own with a time budget (`--records`, `--budget-s`): `configs` = BASELINE's other GPU configs on
-this one GPU (c2, c4, c5, each with its own roofline), `shares` = every rank's share of the 2-, 4- and 8-way partitions of the
-headline panel (and of c4 over 4, c5 over 8) timed alone with the iteration rate they predict, and `collective_floor_us` = the
-closing collectives of the real message sizes on a ONE-rank RCCL communicator.  The parent process of that mode never touches HIP.
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything
+else the benchmark measures is behind --full:
+  - `cpu_baseline` (the NumPy oracle in the reference formulation timed at two sizes that fit the host and extrapolated with the
+    fitted exponent) and `time_to_kkt` (--kkt),
+  - the measured HBM streaming ceiling beside the roofline (`measured_stream_read_GBs`) and, for N > 1, `exchange_compare`,
+  - on the default single-GPU workload (no workload flag), after the headline record is complete and each in a fresh child
+    process of its own with a time budget (`--records`, `--budget-s`): `configs` = BASELINE's other GPU configs on this one GPU
+    (c2, c4, c5, each with its own roofline), `shares` = every rank's share of the 2-, 4- and 8-way partitions of the headline
+    panel (and of c4 over 4, c5 over 8) timed alone with the iteration rate they predict, and `collective_floor_us` = the
+    closing collectives of the real message sizes on a ONE-rank RCCL communicator.  The parent process of that mode never
+    touches HIP.
+
+    python bench.py --gpus 1 --steps K --warmup W --full   # the headline and every record beside it (about 4 minutes)
 
 Other workloads: --config c2|c3|c4|c5 (BASELINE.json configs), --solver fw|adagrad|ascg|smo|ip|as, --task svr, ...
 
@@ -100,16 +107,20 @@ def parse(argv=None):
                     help='sample sizes of the CPU baseline leg (SURVEY 8d); a size whose dense fp64 Q (+ one temporary of the same size) '
                          'does not fit into half of the host\'s free memory is left out, and the record says so')
     ap.add_argument('--cpu-seconds', type=float, default=6.0, help='timed seconds per CPU sample size')
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: leave the CPU baselines out')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: CPU baselines, time_to_kkt (--kkt), the HBM streaming probe, '
+                         'exchange_compare (N > 1) and, with no workload flag, the side records (--records).  Without it a run '
+                         'sets up, warms up, times --steps, writes --dump-outputs and prints the line')
     ap.add_argument('--no-placement', action='store_true',
                     help='take the panel where the first allocation puts it.  Default: the library\'s placement choice (BQ_PLACE_PANEL / '
                          'KernelQuadratic(tune_placement=True), opt-in for SVC / SVR): the product is timed on the empty panel and up to '
                          'two more allocations are tried if it streams below ~6.5 TB/s, the fastest is kept; the times of all candidates '
                          'are in config.panel_placement_ms, the cost in problem_setup_s')
     ap.add_argument('--records', default=None, metavar='all|none|NAME[,NAME...]',
-                    help='side records of the default single-GPU line, each measured in a fresh child process after the headline '
-                         'record is complete: ' + ','.join(SIDE_RECORDS) + '.  Default: all when no workload flag is given '
-                         '(the driver\'s command), none otherwise')
+                    help='--full: side records of the default single-GPU line, each measured in a fresh child process after the '
+                         'headline record is complete: ' + ','.join(SIDE_RECORDS) + '.  Default: all with --full when no workload '
+                         'flag is given, none otherwise')
     ap.add_argument('--line', default='compact', choices=['compact', 'full'],
                     help='what the LAST stdout line is: compact (default) = the headline record cut to what the driver parses, under '
                          f'{LINE_LIMIT} bytes, with the complete record written to --records-file; full = the complete record itself '
@@ -117,7 +128,7 @@ def parse(argv=None):
     ap.add_argument('--records-file', default=os.path.join(REPO, 'bench_records.json'),
                     help='where the complete (uncut) record of this run is written as indented JSON (also one line on stderr)')
     ap.add_argument('--budget-s', type=float, default=400.0,
-                    help='wall-clock budget of the whole default line: a side record that would not fit is skipped (and says so)')
+                    help='--full: wall-clock budget of the whole default line: a side record that would not fit is skipped (and says so)')
     ap.add_argument('--fixed-cap', type=int, default=0, metavar='CAP',
                     help='SURVEY 8(d): the solvers that do not reach their tolerance at these sizes, run to a fixed iteration cap: for '
                          'each workload of --fixed-cap-configs (default: this one) iterations done, status, f and the projected-gradient '
@@ -130,10 +141,11 @@ def parse(argv=None):
     ap.add_argument('--cpu-stream-iters', type=int, default=1,
                     help='also time a blocked Gram-streaming CPU product at the FULL n this many times (~35 s each at n=100000): a '
                          'measured CPU bound beside the extrapolated reference-formulation figure (SURVEY 8d)')
-    ap.add_argument('--kkt', default='all', choices=['none', 'smo', 'ip', 'all', 'ip100k'],
-                    help="time_to_kkt sub-records of the default line (N=1): smo = SVC.fit(optimizer='smo') at the workload's "
+    ap.add_argument('--kkt', default=None, choices=['none', 'smo', 'ip', 'all', 'ip100k'],
+                    help="time_to_kkt sub-records of the line (N=1, PG): smo = SVC.fit(optimizer='smo') at the workload's "
                          'n (tol 1e-3), ip = InteriorPoint at BASELINE config 3 shape n=50000 d=128 (gap 1e-10, ~50 s); ip100k = all of '
-                         'these + InteriorPoint at the HEADLINE size n=100000 d=128 (~6.5 min: not in the default line)')
+                         'these + InteriorPoint at the HEADLINE size n=100000 d=128 (~6.5 min: not in the --full line).  '
+                         'Default: all with --full, none otherwise')
     ap.add_argument('--sigma', type=float, default=8.0, help='blob spread of the synthetic data (SURVEY 8d: 8 overlapping, 3 separable)')
     ap.add_argument('--inner-tol', type=float, default=1e-8, help='ascg: relative residual of the inner conjugate gradients')
     ap.add_argument('--emulate-shares', default=None, metavar='G[,G...]',
@@ -163,10 +175,15 @@ def parse(argv=None):
                          'timed step (iter, f, r1, r2, r3).  Inputs are seeded: the same arguments give the same inputs.  At most '
                          f'{DUMP_LIMIT >> 20} MB in all: past that, each array is cut to a fixed seeded sample of its entries')
     args = ap.parse_args(argv)
-    # no workload flag at all = the driver's command: the line then carries the side records too
+    # no workload flag at all = the headline workload: with --full its line carries the side records too
     args.default_workload = args.config is None and all(getattr(args, k) is None for k in ('n', 'd', 'solver', 'task', 'kernel', 'storage'))
     if args.records is None:
-        args.records = 'all' if args.default_workload else 'none'
+        args.records = 'all' if args.full and args.default_workload else 'none'
+    elif args.records != 'none' and not args.full:
+        ap.error('--records: the side records are measured with --full only')
+    if args.kkt is None:
+        args.kkt = 'all' if args.full else 'none'
+    args.cpu = args.full and not args.no_cpu   # the CPU legs
     preset = CONFIGS[args.config or 'headline']
     for k, v in preset.items():
         if getattr(args, k) is None:
@@ -640,9 +657,9 @@ def bench_kkt_line(args):
     from optiml_amd import device
     ctx = device.get_context()
     if args.solver == 'smo':
-        rec = kkt_smo(args.n, args.d, args.sigma, cpu=not args.no_cpu)
+        rec = kkt_smo(args.n, args.d, args.sigma, cpu=args.cpu)
     else:
-        rec = kkt_box(args.solver, args.n, args.d, args.sigma, cpu=not args.no_cpu, wall_limit=args.wall_limit)
+        rec = kkt_box(args.solver, args.n, args.d, args.sigma, cpu=args.cpu, wall_limit=args.wall_limit)
     steps = rec.get('iterations', rec.get('outer_iterations', 0))
     out = {'metric': 'time_to_kkt_tol', 'value': rec['value'], 'unit': 's', 'n_gpus': 1, 'steps': int(steps), 'warmup': 0,
            'ms_per_step': 1e3 * rec['value'] / max(steps, 1), 'higher_is_better': False, 'scaling': 'strong', 'vs_baseline': None,
@@ -832,7 +849,7 @@ def dense_record(args):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the default line: headline record + side records, each measured in a fresh child process (this parent never touches HIP)
+# the default line with --full: headline record + side records, each measured in a fresh child process (this parent never touches HIP)
 # ---------------------------------------------------------------------------------------------------------------------
 SIDE_COMMANDS = {   # name -> (arguments of the child, its time cap in seconds)
     'c2': (['--config', 'c2', '--steps', '400', '--warmup', '20', '--no-cpu', '--kkt', 'none'], 90.0),
@@ -853,11 +870,12 @@ SIDE_COMMANDS = {   # name -> (arguments of the child, its time cap in seconds)
 
 
 def _run_child(argv, timeout):
-    """One fresh `python bench.py ... --records none` process; (last JSON object on its stdout | None, error text | None,
+    """One fresh `python bench.py ... --full --records none` process; (last JSON object on its stdout | None, error text | None,
     seconds).  Its stderr is this process's stderr (progress stays visible).  On expiry exactly that child is killed."""
     t0 = time.perf_counter()
-    proc = subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv + ['--records', 'none', '--line', 'full'], stdout=subprocess.PIPE,
-                            text=True, cwd=REPO)
+    full = [] if '--full' in argv else ['--full']
+    proc = subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv + full + ['--records', 'none', '--line', 'full'],
+                            stdout=subprocess.PIPE, text=True, cwd=REPO)
     try:
         out, _ = proc.communicate(timeout=timeout)
     except subprocess.TimeoutExpired:
@@ -921,7 +939,7 @@ def prefetch_rccl():
 
 
 def orchestrate(args):
-    """`python bench.py [--gpus 1 --steps K --warmup W]`: the headline record from a child running exactly this command, then
+    """`python bench.py [--gpus 1 --steps K --warmup W] --full`: the headline record from a child running exactly this command, then
     the side records (SIDE_RECORDS) from one child each, skipped with a reason when the budget would not hold them, then ONE
     JSON line.  A failing side record never costs the line; a failing headline child is this process's failure."""
     t_start = time.perf_counter()
@@ -1493,8 +1511,8 @@ def main():
                              'ms_per_step': cols[0][k], 'symv_tiles_ms': cols[1][k], 'exchange_ms_per_product': cols[2][k]})
 
     esz = 8 if args.storage == 'f64' else 4
-    probe = (0.0, 0.0)
-    if rank == 0:
+    probe = (None, None)
+    if rank == 0 and args.full:
         try:   # outside the timed region: what a plain streaming read / copy reaches on this GPU (4 GiB scratch)
             probe = ctx.probe_bandwidth(4 << 30, 5)
         except Exception as exc:  # noqa: BLE001  (e.g. not enough free HBM beside a very large panel)
@@ -1596,7 +1614,7 @@ def main():
                                'row_block_equivalent_TFs': full / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0,
                                'note': 'frac counts the MFMA flops actually issued (the tiles on/below the diagonal in this rank\'s tile rows); '
                                        'row_block_equivalent_TFs prices the launch at 2 rows n d, which is not what runs'}
-    if comm is not None and not al and not ascg and args.storage != 'stream':
+    if args.full and comm is not None and not al and not ascg and args.storage != 'stream':
         # AFTER the headline record is complete and OUTSIDE the timed region: the same few iterations with the OTHER closing
         # collective of the symmetric product, so that one multi-GPU run shows both (all-gather of 8 segment vectors + ordered sum,
         # bit-identical for any N, against one all-reduce of n doubles) — collective time per product, max over ranks.  A side
@@ -1660,15 +1678,15 @@ def main():
             kk = {}
             try:
                 if args.kkt in ('smo', 'all', 'ip100k'):
-                    kk['smo'] = kkt_smo(n, d, args.sigma, X=X, y=y, cpu=not args.no_cpu)
+                    kk['smo'] = kkt_smo(n, d, args.sigma, X=X, y=y, cpu=args.cpu)
                 if args.kkt in ('ip', 'all', 'ip100k'):
-                    kk['ip_config3'] = kkt_box('ip', 50000, 128, args.sigma, cpu=not args.no_cpu)
+                    kk['ip_config3'] = kkt_box('ip', 50000, 128, args.sigma, cpu=args.cpu)
                 if args.kkt == 'ip100k':
                     kk['ip_headline'] = kkt_box('ip', n, d, args.sigma, cpu=False)
             except Exception as exc:  # noqa: BLE001 — the headline number must survive a failing side record
                 kk['error'] = repr(exc)
             out['time_to_kkt'] = kk
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.cpu:
             out['cpu_baseline'] = cpu_baseline(args)
             out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
         else:

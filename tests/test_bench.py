@@ -34,6 +34,72 @@ def test_presets_and_argument_checks():
     assert r.returncode != 0 and 'replicas only' in r.stderr
 
 
+def test_a_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """A plain run sets up, warms up, times the steps and prints the line; the CPU baselines, time_to_kkt and the side records of
+    the default line are behind --full (explicit --kkt / --no-cpu still choose among them)."""
+    sys.path.insert(0, REPO)
+    import bench
+    for argv in ([], ['--gpus', '1', '--steps', '20', '--warmup', '5'], ['--config', 'c2'], ['--samples', '5000']):
+        a = bench.parse(argv)
+        assert (a.full, a.records, a.kkt, a.cpu) == (False, 'none', 'none', False), argv
+    a = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
+    assert (a.full, a.records, a.kkt, a.cpu) == (True, 'all', 'all', True)
+    a = bench.parse(['--config', 'c2', '--full', '--no-cpu', '--kkt', 'smo'])
+    assert (a.records, a.kkt, a.cpu) == ('none', 'smo', False)
+    with pytest.raises(SystemExit):
+        bench.parse(['--records', 'c2'])
+
+
+def test_every_child_of_the_full_line_runs_with_full(monkeypatch):
+    """The side records are measured by children of `--full`: each child gets --full once, so it measures what it did before."""
+    sys.path.insert(0, REPO)
+    import bench
+    cmds = []
+
+    class Proc:
+        returncode = 0
+
+        def __init__(self, cmd, **kw):
+            cmds.append(cmd)
+
+        def communicate(self, timeout=None):
+            return '[bench] progress\n{"value": 1.0}\n', None
+
+    monkeypatch.setattr(bench.subprocess, 'Popen', Proc)
+    for argv in (['--config', 'c2', '--no-cpu'], ['--gpus', '1', '--full']):
+        rec, err, _ = bench._run_child(argv, 10.0)
+        assert rec == {'value': 1.0} and err is None
+    assert [c[2:] for c in cmds] == [['--config', 'c2', '--no-cpu', '--full', '--records', 'none', '--line', 'full'],
+                                     ['--gpus', '1', '--full', '--records', 'none', '--line', 'full']]
+
+
+def test_plain_run_without_a_gpu_fails_loudly():
+    """No GPU here: a plain run measures the headline in its own process (no child) and fails there: no JSON line, non-zero."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip('needs a box without a GPU')
+    r = _run(['--gpus', '1', '--steps', '2', '--warmup', '1'], timeout=300)
+    assert r.returncode != 0 and r.stdout.strip() == ''
+    assert 'child process' not in r.stderr and 'headline run failed' not in r.stderr
+
+
+@pytest.mark.gpu
+def test_a_plain_run_measures_nothing_beside_the_headline():
+    """The plain line: the timed steps and the roofline of their own product kernel, no CPU baseline, no time_to_kkt, no streaming
+    probe; --full adds them to the same line."""
+    common = ['--samples', '6000', '--features', '16', '--steps', '4', '--warmup', '1']
+    r = _run(common)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec['steps_done'] == 4 and rec['value'] > 0 and rec['ms_per_step'] > 0 and rec['roofline']['frac'] > 0
+    assert rec['cpu_baseline'] is None and 'time_to_kkt' not in rec and rec['roofline']['measured_stream_read_GBs'] is None
+    r = _run(common + ['--full', '--kkt', 'smo', '--no-cpu'])
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec['steps_done'] == 4 and rec['cpu_baseline'] is None
+    assert rec['time_to_kkt']['smo']['n'] == 6000 and rec['roofline']['measured_stream_read_GBs'] > 0
+
+
 def test_self_launch_without_a_gpu_fails_fast_and_loudly():
     """No GPU in the build container: both spawned ranks fail to create a device context; the parent reports it and returns
     non-zero within seconds — no hang, no fallback."""
@@ -70,7 +136,7 @@ def test_self_launch_without_torch_rendezvous():
     """BQ_RENDEZVOUS=socket: the ranks meet over the package's own TCP communicator (what a host without torch gets); the N > 1
     line carries every rank's share and timings."""
     common = ['--samples', '6000', '--features', '16', '--steps', '6', '--warmup', '2', '--no-cpu', '--kkt', 'none']
-    r = _run(common + ['--gpus', '2', '--exchange', 'host'], env={'BQ_RENDEZVOUS': 'socket'})
+    r = _run(common + ['--gpus', '2', '--exchange', 'host', '--full'], env={'BQ_RENDEZVOUS': 'socket'})
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec['n_gpus'] == 2 and rec['steps_done'] == 6 and rec['config']['exchange'] == 'host'
@@ -110,7 +176,7 @@ def test_launched_by_torch_distributed_run_like_the_driver(tmp_path):
     e = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), BENCH, '--gpus', '2', '--exchange', 'host', '--samples', '5000', '--features', '16',
-           '--steps', '6', '--warmup', '2', '--no-cpu', '--kkt', 'none', '--records-file', str(tmp_path / 'full.json')]
+           '--steps', '6', '--warmup', '2', '--no-cpu', '--kkt', 'none', '--full', '--records-file', str(tmp_path / 'full.json')]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=e, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -124,14 +190,14 @@ def test_launched_by_torch_distributed_run_like_the_driver(tmp_path):
 
 
 def test_default_line_is_composed_from_child_records(monkeypatch, capsys, tmp_path):
-    """`python bench.py` with no workload flag: the parent composes ONE line from the headline child's record and the side
+    """`python bench.py --full` with no workload flag: the parent composes ONE line from the headline child's record and the side
     records (configs / shares / collective floor), never touching HIP itself; a failing or over-budget side record is reported
     inside the line, not fatal."""
     sys.path.insert(0, REPO)
     import bench
-    args = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    args = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     assert args.default_workload and args.records == 'all' and args.cpu_stream_iters == 1
-    assert bench.parse(['--samples', '5000']).records == 'none'
+    assert bench.parse(['--samples', '5000', '--full']).records == 'none'
     assert args.line == 'compact'
     args.records_file = str(tmp_path / 'bench_records.json')
     calls = []
@@ -170,7 +236,7 @@ def test_default_line_is_composed_from_child_records(monkeypatch, capsys, tmp_pa
                 'roofline': {'frac': 0.82, 'avg_launch_ms': 6.1}, 'cpu_baseline': {'value': 0.2}}, None, 100.0
 
     monkeypatch.setattr(bench, '_run_child', fake_child)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     bench.orchestrate(args)
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     # the LAST stdout line is the compact record (r04's 25.6 KB line overflowed the driver's 12.8 KB tail); the one before it is the
@@ -188,7 +254,7 @@ def test_default_line_is_composed_from_child_records(monkeypatch, capsys, tmp_pa
     assert line['side']['predicted_x_at_2_4_8'][2] == pytest.approx(1e3 / (6.0 / 8 + 0.1) / 160.0, rel=1e-5)
     assert line['side']['collective_floor_us'] == {'gather_8_segments': 5.0, 'allreduce': 4.0}
     rec = json.load(open(args.records_file))                                      # the complete record, beside the line
-    assert calls[0][0] == ['--gpus', '1', '--steps', '20', '--warmup', '5']       # the headline child runs exactly the caller's command
+    assert calls[0][0] == ['--gpus', '1', '--steps', '20', '--warmup', '5', '--full']   # the headline child runs exactly the caller's command
     assert [c[0][:2] for c in calls[1:4]] == [['--config', 'c2'], ['--config', 'c4'], ['--config', 'c5']]
     assert rec['value'] == 160.0 and rec['steps'] == 20 and rec['cpu_baseline'] == {'value': 0.2}   # headline fields untouched
     assert set(rec['configs']) == {'c2', 'c4', 'c5'} and 'cpu_baseline' not in rec['configs']['c2']
@@ -217,7 +283,7 @@ def test_a_run_cut_after_the_headline_child_leaves_a_parseable_last_line(monkeyp
     returns (the parent is interrupted inside it), and the last stdout line still parses with every contract field."""
     sys.path.insert(0, REPO)
     import bench
-    args = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    args = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     args.records_file = str(tmp_path / 'bench_records.json')
     head = {'metric': 'dual_qp_iterations_per_sec', 'value': 163.0, 'unit': 'iter/s', 'n_gpus': 1, 'steps': 20, 'warmup': 5, 'ms_per_step': 6.13,
             'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
@@ -235,7 +301,7 @@ def test_a_run_cut_after_the_headline_child_leaves_a_parseable_last_line(monkeyp
         raise KeyboardInterrupt   # the cut: what a SIGINT / the end of the caller's patience looks like from inside the parent
 
     monkeypatch.setattr(bench, '_run_child', child)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     with pytest.raises(KeyboardInterrupt):
         bench.orchestrate(args)
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
@@ -309,7 +375,7 @@ def test_default_line_hands_the_dump_directory_to_the_headline_child(monkeypatch
     """The headline child runs in the repository root: a relative --dump-outputs DIR reaches it as the caller's absolute DIR."""
     sys.path.insert(0, REPO)
     import bench
-    argv = ['--gpus', '1', '--steps', '20', '--warmup', '5', '--dump-outputs', 'dump']
+    argv = ['--gpus', '1', '--steps', '20', '--warmup', '5', '--full', '--dump-outputs', 'dump']
     args = bench.parse(argv)
     assert args.default_workload and args.dump_outputs == 'dump'
     args.records_file, args.budget_s = str(tmp_path / 'bench_records.json'), 1.0
@@ -349,11 +415,11 @@ def test_dump_outputs_of_two_runs_with_the_same_arguments_agree(tmp_path):
 
 
 def test_default_line_without_a_gpu_fails_loudly():
-    """No GPU here: the headline child cannot create a context; the parent prints no JSON line and returns non-zero."""
+    """No GPU here: the headline child of `--full` cannot create a context; the parent prints no JSON line and returns non-zero."""
     import torch
     if torch.cuda.is_available():
         pytest.skip('needs a box without a GPU')
-    r = _run(['--steps', '2', '--warmup', '1', '--no-cpu', '--kkt', 'none'], timeout=300)
+    r = _run(['--steps', '2', '--warmup', '1', '--no-cpu', '--kkt', 'none', '--full'], timeout=300)
     assert r.returncode != 0 and r.stdout.strip() == ''
     assert 'headline run failed' in r.stderr
 
