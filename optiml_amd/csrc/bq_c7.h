@@ -7,6 +7,8 @@
 // pattern 0x3F00000000000000 (2^-15 exactly) cannot be stored.  Every stored element comes back bit for bit.
 #pragma once
 #include <cmath>
+#include <type_traits>
+#include <utility>
 
 #include "bq_common.h"
 
@@ -84,3 +86,22 @@ template <typename T> using bq_pview = typename bq_pan<T>::view;
 // a problem's resident panel as a T reader takes it
 template <typename T> static inline bq_pview<T> bq_panel_as(const bq_problem *p) { return (const T *)p->panel; }
 template <> inline bq_c7p bq_panel_as<bq_c7>(const bq_problem *p) { return bq_c7_view(p->panel, p->panel_elems); }
+
+// the element type T of a typed panel view, and the storage dispatch of the T-templated launchers: f(the panel's typed view,
+// std::bool_constant<add_one>) — `f` is a generic lambda that launches kernel<bq_pelem<decltype(view)>, decltype(one)::value>
+template <typename V> struct bq_view_elem { typedef std::remove_cv_t<std::remove_pointer_t<V>> type; };
+template <> struct bq_view_elem<bq_c7p> { typedef bq_c7 type; };
+template <typename V> using bq_pelem = typename bq_view_elem<V>::type;
+
+template <typename F> static inline void bq_panel_dispatch(const bq_panel_ref &panel, bool add_one, F &&f) {
+    auto typed = [&](auto pv) {
+        if (add_one) f(pv, std::true_type{});
+        else f(pv, std::false_type{});
+    };
+    if (panel.storage == BQ_F64C) typed(bq_c7_view(panel.base, panel.elems));
+    else if (panel.storage == BQ_F64) typed((const double *)panel.base);
+    else typed((const float *)panel.base);
+}
+template <typename F> static inline void bq_panel_dispatch(const bq_problem *p, bool add_one, F &&f) {
+    bq_panel_dispatch(bq_problem_panel(p), add_one, std::forward<F>(f));
+}

@@ -359,6 +359,14 @@ int64_t bq_pairs_slab_len(const bq_pairs_plan *pl);
 int bq_launch_symmp(bq_problem *p, const bq_pairs_plan *pl, bool add_one, const double *W, int64_t ldw, double *slab, double *out);
 int bq_launch_pairs_live(const bq_pairs_plan *pl, bq_scal *const *scs, int *nlive, hipStream_t st);
 
+// bq_msolver.hip: one multi-column product from host arrays, the body of bq_problem_gram_matmat(_wide) and
+// bq_problem_gram_matmat_pairs.  W's k rows (p->n each) go into `slots` zeroed device columns of stride p->ldN,
+// launch(arg, dW, ldw, slab, dOUT, nlive) runs on them with a slab of slab_len doubles and *nlive = k, and OUT's first k columns come
+// back into out; zero_out zero-fills OUT before the launch.  Synchronises and frees; `name` heads the error messages.
+typedef int (*bq_product_launch)(void *arg, const double *dW, int64_t ldw, double *slab, double *dOUT, const int *nlive);
+int bq_product_once(bq_problem *p, const char *name, int k, int64_t slots, int64_t slab_len, bool zero_out, const double *W,
+                    double *out, bq_product_launch launch, void *arg);
+
 // bq_dense.hip: a dense host Hessian into the resident panel — packed lower tile rows when Q == Q' exactly (checked on the device
 // while uploading, agreed across ranks), else row blocks
 bool bq_dense_host_spot_symmetric(const double *Q, int64_t n);

@@ -411,39 +411,32 @@ extern "C" int bq_msolver_get(bq_msolver *m, int cls, int what, double *out) {
     return bq_solver_get(m->cls[cls], what, out);
 }
 
-static int gram_matmat(bq_problem *p, int k, const double *W, double *out, bool wide) {
-    BQ_ARG(p && W && out, "NULL argument");
-    BQ_ARG(k >= 1, "k must be >= 1");
-    BQ_ARG(p->kernel >= 0, "not a kernel-structured problem");
-    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
-        bq_set_error("the multi-column product needs a single-rank context and a resident packed panel");
-        return BQ_ERR_BADARG;
-    }
+int bq_product_once(bq_problem *p, const char *name, int k, int64_t slots, int64_t slab_len, bool zero_out, const double *W,
+                    double *out, bq_product_launch launch, void *arg) {
     bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    const int64_t ldw = p->ldN, slots = bq_round_up(k, wide ? BQ_SYMMW_CK : BQ_SYMM_CK);
+    const int64_t ldw = p->ldN;
     double *dW = nullptr, *dO = nullptr, *slab = nullptr;
     int *nl = nullptr;
     hipError_t e = hipMalloc(&dW, sizeof(double) * ldw * slots);
     if (e == hipSuccess) e = hipMalloc(&dO, sizeof(double) * ldw * slots);
-    if (e == hipSuccess) e = hipMalloc(&slab, sizeof(double) * (wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb)));
+    if (e == hipSuccess) e = hipMalloc(&slab, sizeof(double) * slab_len);
     if (e == hipSuccess) e = hipMalloc(&nl, sizeof(int));
     if (e == hipSuccess) e = hipMemsetAsync(dW, 0, sizeof(double) * ldw * slots, c->stream);
+    if (e == hipSuccess && zero_out) e = hipMemsetAsync(dO, 0, sizeof(double) * ldw * slots, c->stream);
     if (e == hipSuccess) e = hipMemcpy2DAsync(dW, sizeof(double) * ldw, W, sizeof(double) * p->n, sizeof(double) * p->n, k,
                                               hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(nl, &k, sizeof(int), hipMemcpyHostToDevice, c->stream);
     int rc = BQ_OK;
     if (e != hipSuccess) {
-        bq_set_error("gram_matmat setup failed: %s", hipGetErrorString(e));
+        bq_set_error("%s setup failed: %s", name, hipGetErrorString(e));
         rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
     }
-    if (rc == BQ_OK)
-        rc = wide ? bq_launch_symmw(p, false, dW, ldw, k, slab, dO, nl) : bq_launch_symm(p, false, dW, ldw, k, slab, dO, nl);
+    if (rc == BQ_OK) rc = launch(arg, dW, ldw, slab, dO, nl);
     if (rc == BQ_OK) {
         e = hipMemcpy2DAsync(out, sizeof(double) * p->n, dO, sizeof(double) * ldw, sizeof(double) * p->n, k, hipMemcpyDeviceToHost,
                              c->stream);
         if (e != hipSuccess) {
-            bq_set_error("gram_matmat copy: %s", hipGetErrorString(e));
+            bq_set_error("%s copy: %s", name, hipGetErrorString(e));
             rc = BQ_ERR_HIP;
         }
     }
@@ -452,6 +445,27 @@ static int gram_matmat(bq_problem *p, int k, const double *W, double *out, bool 
     for (void *ptr : {(void *)dW, (void *)dO, (void *)slab, (void *)nl})
         if (ptr) hipFree(ptr);
     return rc;
+}
+
+static int gram_matmat(bq_problem *p, int k, const double *W, double *out, bool wide) {
+    BQ_ARG(p && W && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->kernel >= 0, "not a kernel-structured problem");
+    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
+        bq_set_error("the multi-column product needs a single-rank context and a resident packed panel");
+        return BQ_ERR_BADARG;
+    }
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    struct call { bq_problem *p; int k; bool wide; } cl{p, k, wide};
+    return bq_product_once(
+        p, "gram_matmat", k, bq_round_up(k, wide ? BQ_SYMMW_CK : BQ_SYMM_CK), wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb),
+        false, W, out,
+        [](void *arg, const double *dW, int64_t ldw, double *slab, double *dO, const int *nl) {
+            const call *c = (const call *)arg;
+            return c->wide ? bq_launch_symmw(c->p, false, dW, ldw, c->k, slab, dO, nl)
+                           : bq_launch_symm(c->p, false, dW, ldw, c->k, slab, dO, nl);
+        },
+        &cl);
 }
 
 extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out) { return gram_matmat(p, k, W, out, false); }

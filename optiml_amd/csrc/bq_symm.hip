@@ -19,6 +19,10 @@
 // for every slot and every chunk, and no atomics are used.  So a class gives the same bits alone, in any batch and at any position.
 // It is NOT bit-identical to the one-column kernel (its association is tied to JG = 8 and to the canonical segments); it agrees with
 // it to rounding.
+//
+// This file's own part is the 4-column VALU strip kernel; its association is its own, so it shares no body with the other product
+// kernels.  Shared: the storage dispatch of bq_launch_symm (bq_panel_dispatch, bq_c7.h), the slab walk (slab_walk under
+// seg_thread_sum, bq_symv_tile.h) and the one-off host product around the launcher (bq_product_once, bq_msolver.hip).
 #include "bq_common.h"
 #include "bq_symv_tile.h"
 
@@ -175,23 +179,9 @@ int bq_launch_symm(bq_problem *p, bool add_one, const double *W, int64_t ldw, in
     const dim3 tiles((unsigned)strips_before<SJG>(nb)), red((unsigned)nb, BQ_SYMM_CK);
     hipStream_t st = p->ctx->stream;
     for (int ch = 0; ch * BQ_SYMM_CK < slots; ++ch) {
-        if (p->compact) {
-            const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
-            if (add_one)
-                symm_tiles_kernel<bq_c7, true><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
-            else
-                symm_tiles_kernel<bq_c7, false><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
-        } else if (p->storage == BQ_F64) {
-            if (add_one)
-                symm_tiles_kernel<double, true><<<tiles, 256, 0, st>>>((const double *)p->panel, nb, W, ldw, slab, nlive, ch);
-            else
-                symm_tiles_kernel<double, false><<<tiles, 256, 0, st>>>((const double *)p->panel, nb, W, ldw, slab, nlive, ch);
-        } else {
-            if (add_one)
-                symm_tiles_kernel<float, true><<<tiles, 256, 0, st>>>((const float *)p->panel, nb, W, ldw, slab, nlive, ch);
-            else
-                symm_tiles_kernel<float, false><<<tiles, 256, 0, st>>>((const float *)p->panel, nb, W, ldw, slab, nlive, ch);
-        }
+        bq_panel_dispatch(p, add_one, [&](auto pv, auto one) {
+            symm_tiles_kernel<bq_pelem<decltype(pv)>, decltype(one)::value><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
+        });
         symm_reduce_kernel<<<red, 1024, 0, st>>>(slab, nb, out, ldw, nlive, ch);
         BQ_HIP(hipGetLastError());
     }

@@ -15,28 +15,23 @@
 // Slab: pair p has its own L_p x L_p region of 256-entry vectors, L_p = tiles of a + tiles of b, in pair-local tile numbering (a's
 // tiles first).  Entry (A, B): B > A holds the column part of tile (B, A); B <= A holds the row part of the h-th strip of tile row A
 // (h = B: row parts are numbered, not placed at their first tile).  The reduce adds row A's row parts in strip order, then its column
-// parts in tile order, in four fixed phases (bq_symv_tile.h's seg_thread_sum walk) — no atomics.
+// parts in tile order, in four fixed phases (bq_symv_tile.h's slab_walk, as seg_thread_sum) — no atomics.
 //
 // Determinism and batch invariance: each column's chain (tile walk, MFMA k order, four-wave sum, reduce walk) depends only on its
 // pair's class layout and its W column; an MFMA output D[i][s] depends on column s of B only.  So column p's bits are the same
 // alone, at any slot, and whatever other pairs are live.  They are not the bits of bq_symmw.hip (another association).
 #include <algorithm>
-#include <vector>
-
 #include <type_traits>
+#include <vector>
 
 #include "bq_common.h"
 #include "bq_symv_tile.h"
 #include "bq_symmw_step.h"
+using namespace bq_mfma;
 
 namespace {
 
-constexpr int JG = 8;      // tiles per single-column strip (bq_symv.hip's default)
-constexpr int WJG = 4;     // tiles per diagonal strip (bq_symmw.hip)
-constexpr int CK = BQ_SYMMW_CK;
-constexpr int TP = 72;
-constexpr int RP = 65;
-constexpr int WP = 17;
+constexpr int JG = 8;      // tiles per single-column strip (bq_symv.hip's default); diagonal strips: WJG (bq_symmw_step.h)
 
 struct pitem {
     int I, J0, nj, id;   // tile row, first tile, tiles; single: the pair, diagonal: the class
@@ -103,7 +98,9 @@ static int64_t slab_len(const int *ct, int m, const int *pairs) {
 // kernels
 // ---------------------------------------------------------------------------------------------------------------------------------
 
-// bq_symv.hip's symv_tiles_kernel on one strip of an off-diagonal class block (every tile off the panel's diagonal), one column
+// bq_symv.hip's symv_tiles_kernel on one strip of an off-diagonal class block (every tile off the panel's diagonal), one column.
+// The walk is written out here and there: called as one inlined body, symv_tiles_kernel compiles to other code
+// (profiles/refactor/isa_diff.txt), and that kernel is the headline product.
 template <typename T, bool ADD_ONE, int SR>
 __global__ __launch_bounds__(256, 2) void symmp_single_kernel(bq_pptr<T> panel, const pitem *__restrict__ items,
                                                               const pinfo *__restrict__ info, const int *__restrict__ plive,
@@ -228,7 +225,9 @@ __global__ __launch_bounds__(256, 2) void symmp_single_kernel(bq_pptr<T> panel, 
     }
 }
 
-// bq_symmw.hip's symmw_tiles_kernel on one strip of class c's diagonal block, the slots being chunk blockIdx.y of c's live pairs
+// bq_symmw.hip's symmw_tiles_kernel on one strip of class c's diagonal block, the slots being chunk blockIdx.y of c's live pairs.
+// Written out in both files: as one inlined body with the slot's column and the slab destinations as callables, the fp32 and fp64
+// instantiations took 3 to 8 VGPRs more (of 256 at two waves per SIMD).  The blocking constants are bq_symmw_step.h's.
 template <typename T, bool ADD_ONE>
 __global__ __launch_bounds__(256, 2) void symmp_diag_kernel(bq_pptr<T> panel, const pitem *__restrict__ items,
                                                             const pinfo *__restrict__ info, const int *__restrict__ pairs,
@@ -348,31 +347,12 @@ __global__ __launch_bounds__(256, 2) void symmp_diag_kernel(bq_pptr<T> panel, co
     }
 }
 
-// the fixed-phase walk of bq_symv_tile.h's seg_thread_sum over entries [0, nh) then [c0, L) of one slab row
+// seg_thread_sum's phase rule over the entries [0, nh) then [c0, L) of one slab row (bq_symv_tile.h: slab_walk)
 __device__ __forceinline__ double list_sum(const double *__restrict__ p, int64_t nh, int64_t c0, int64_t L, int q) {
     double s0 = 0.0, s1 = 0.0;
-    auto walk = [&](const double *base, int64_t first, int64_t count) {
-        int64_t k = first;
-        for (; k + 28 < count; k += 32) {
-            const double a0 = base[(k) * ST], b0 = base[(k + 4) * ST], a1 = base[(k + 8) * ST], b1 = base[(k + 12) * ST];
-            const double a2 = base[(k + 16) * ST], b2 = base[(k + 20) * ST], a3 = base[(k + 24) * ST], b3 = base[(k + 28) * ST];
-            s0 += a0;
-            s1 += b0;
-            s0 += a1;
-            s1 += b1;
-            s0 += a2;
-            s1 += b2;
-            s0 += a3;
-            s1 += b3;
-        }
-        for (; k < count; k += 8) {
-            s0 += base[k * ST];
-            if (k + 4 < count) s1 += base[(k + 4) * ST];
-        }
-    };
-    walk(p, q, nh);
+    slab_walk(p, q, nh, ST, s0, s1);
     const int64_t shift = (4 - (nh & 3)) & 3;
-    walk(p + c0 * ST, (q + shift) & 3, L - c0);
+    slab_walk(p + c0 * ST, (q + shift) & 3, L - c0, ST, s0, s1);
     return s0 + s1;
 }
 
@@ -507,40 +487,22 @@ int bq_launch_pairs_live(const bq_pairs_plan *pl, bq_scal *const *scs, int *nliv
     return BQ_OK;
 }
 
-template <typename T, bool ADD_ONE>
-static void launch_typed(const bq_pairs_plan *pl, bq_pptr<T> panel, bool f32, const double *W, int64_t ldw, double *slab,
-                         hipStream_t st) {
-    if (pl->nsingle > 0) {
-        if constexpr (std::is_same<T, bq_c7>::value)   // the compact layout: 4 rows per step (its decode spills at 8)
-            symmp_single_kernel<T, ADD_ONE, 4><<<(unsigned)pl->nsingle, 256, 0, st>>>(panel, pl->single, pl->info, pl->plive, W, ldw, slab);
-        else if (f32)
-            symmp_single_kernel<T, ADD_ONE, 8><<<(unsigned)pl->nsingle, 256, 0, st>>>(panel, pl->single, pl->info, pl->plive, W, ldw, slab);
-        else
-            symmp_single_kernel<T, ADD_ONE, 4><<<(unsigned)pl->nsingle, 256, 0, st>>>(panel, pl->single, pl->info, pl->plive, W, ldw, slab);
-    }
-    if (pl->ndiag > 0)
-        symmp_diag_kernel<T, ADD_ONE><<<dim3((unsigned)pl->ndiag, (unsigned)pl->nch), 256, 0, st>>>(
-            panel, pl->diag, pl->info, pl->dpairs, pl->dct, pl->ccnt, pl->cslot, pl->kpad, W, ldw, slab);
-}
-
 int bq_launch_symmp(bq_problem *p, const bq_pairs_plan *pl, bool add_one, const double *W, int64_t ldw, double *slab, double *out) {
     BQ_ARG(p->symmetric && !p->streamed && p->ctx->world == 1, "the routed product needs a resident packed panel on one rank");
     BQ_ARG(ldw >= p->nb * ST && pl->nb == p->nb, "column stride shorter than the panel, or a plan of another panel");
     hipStream_t st = p->ctx->stream;
-    // fp32 tiles are half as wide in bytes: 8 rows per step keep the same bytes in flight per lane (bq_symv.hip)
-    if (p->compact) {
-        const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
-        if (add_one) launch_typed<bq_c7, true>(pl, pv, false, W, ldw, slab, st);
-        else launch_typed<bq_c7, false>(pl, pv, false, W, ldw, slab, st);
-    } else if (p->storage == BQ_F64) {
-        const double *pv = (const double *)p->panel;
-        if (add_one) launch_typed<double, true>(pl, pv, false, W, ldw, slab, st);
-        else launch_typed<double, false>(pl, pv, false, W, ldw, slab, st);
-    } else {
-        const float *pv = (const float *)p->panel;
-        if (add_one) launch_typed<float, true>(pl, pv, true, W, ldw, slab, st);
-        else launch_typed<float, false>(pl, pv, true, W, ldw, slab, st);
-    }
+    bq_panel_dispatch(p, add_one, [&](auto pv, auto one) {
+        using T = bq_pelem<decltype(pv)>;
+        constexpr bool ADD_ONE = decltype(one)::value;
+        // fp32 tiles are half as wide in bytes: 8 rows per step keep the same bytes in flight per lane (bq_symv.hip); fp64 and the
+        // compact layout (its decode spills at 8): 4
+        constexpr int SR = std::is_same<T, float>::value ? 8 : 4;
+        if (pl->nsingle > 0)
+            symmp_single_kernel<T, ADD_ONE, SR><<<(unsigned)pl->nsingle, 256, 0, st>>>(pv, pl->single, pl->info, pl->plive, W, ldw, slab);
+        if (pl->ndiag > 0)
+            symmp_diag_kernel<T, ADD_ONE><<<dim3((unsigned)pl->ndiag, (unsigned)pl->nch), 256, 0, st>>>(
+                pv, pl->diag, pl->info, pl->dpairs, pl->dct, pl->ccnt, pl->cslot, pl->kpad, W, ldw, slab);
+    });
     symmp_reduce_kernel<<<dim3((unsigned)pl->lmax, (unsigned)pl->m), 1024, 0, st>>>(slab, pl->info, pl->plive, out, ldw);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
@@ -588,37 +550,18 @@ extern "C" int bq_problem_gram_matmat_pairs(bq_problem *p, int ncls, const int *
         bq_set_error("the routed product needs a single-rank context and a resident packed panel");
         return BQ_ERR_BADARG;
     }
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
+    BQ_HIP(hipSetDevice(p->ctx->device));
     bq_pairs_plan *pl = nullptr;
     BQ_TRY(bq_pairs_plan_create(p, ncls, cls_tiles, m, pairs, &pl));
-    const int64_t ldw = p->ldN;
-    double *dW = nullptr, *dO = nullptr, *slab = nullptr;
-    hipError_t e = hipMalloc(&dW, sizeof(double) * ldw * m);
-    if (e == hipSuccess) e = hipMalloc(&dO, sizeof(double) * ldw * m);
-    if (e == hipSuccess) e = hipMalloc(&slab, sizeof(double) * pl->slab_len);
-    if (e == hipSuccess) e = hipMemsetAsync(dW, 0, sizeof(double) * ldw * m, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dO, 0, sizeof(double) * ldw * m, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(dW, sizeof(double) * ldw, W, sizeof(double) * p->n, sizeof(double) * p->n, m,
-                                              hipMemcpyHostToDevice, c->stream);
-    int rc = BQ_OK;
-    if (e != hipSuccess) {
-        bq_set_error("gram_matmat_pairs setup failed: %s", hipGetErrorString(e));
-        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
-    }
-    if (rc == BQ_OK) rc = bq_launch_symmp(p, pl, false, dW, ldw, slab, dO);
-    if (rc == BQ_OK) {
-        e = hipMemcpy2DAsync(out, sizeof(double) * p->n, dO, sizeof(double) * ldw, sizeof(double) * p->n, m, hipMemcpyDeviceToHost,
-                             c->stream);
-        if (e != hipSuccess) {
-            bq_set_error("gram_matmat_pairs copy: %s", hipGetErrorString(e));
-            rc = BQ_ERR_HIP;
-        }
-    }
-    if (rc == BQ_OK) rc = bq_ctx_sync(c);
-    else (void)bq_ctx_sync(c);
-    for (void *ptr : {(void *)dW, (void *)dO, (void *)slab})
-        if (ptr) hipFree(ptr);
+    // OUT is zero-filled first: the rows outside a pair's classes are never written and must read exact 0.0
+    struct call { bq_problem *p; const bq_pairs_plan *pl; } cl{p, pl};
+    const int rc = bq_product_once(
+        p, "gram_matmat_pairs", m, m, pl->slab_len, true, W, out,
+        [](void *arg, const double *dW, int64_t ldw, double *slab, double *dO, const int *) {
+            const call *c = (const call *)arg;
+            return bq_launch_symmp(c->p, c->pl, false, dW, ldw, slab, dO);
+        },
+        &cl);
     bq_pairs_plan_destroy(pl);
     return rc;
 }

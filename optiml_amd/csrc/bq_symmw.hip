@@ -26,14 +26,9 @@
 #include "bq_common.h"
 #include "bq_symv_tile.h"
 #include "bq_symmw_step.h"
+using namespace bq_mfma;
 
-constexpr int WJG = 4;     // tiles per strip
-constexpr int CK = BQ_SYMMW_CK;
-constexpr int TP = 72;     // pitch (doubles) of a wave's 16 x 64 transpose image; also its 16 x 64 reduction image (pitch RP)
-constexpr int RP = 65;
-constexpr int WP = 17;     // pitch of the W_J stage (256 rows x 16 slots)
-static_assert(CK == 16, "the column chunk is the MFMA's N");
-
+// WJG = 4 tiles per strip, CK, and the LDS pitches TP / RP / WP: bq_symmw_step.h (bq_symmp.hip uses the same blocking)
 template <typename T, bool ADD_ONE>
 __global__ __launch_bounds__(256, 2) void symmw_tiles_kernel(bq_pptr<T> panel, int64_t nb, const double *__restrict__ W,
                                                           int64_t ldw, double *__restrict__ slab, const int *__restrict__ nlive, int ch) {
@@ -160,23 +155,9 @@ int bq_launch_symmw(bq_problem *p, bool add_one, const double *W, int64_t ldw, i
     const dim3 tiles((unsigned)strips_before<WJG>(nb)), red((unsigned)nb, CK);
     hipStream_t st = p->ctx->stream;
     for (int ch = 0; ch * CK < slots; ++ch) {
-        if (p->compact) {
-            const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
-            if (add_one)
-                symmw_tiles_kernel<bq_c7, true><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
-            else
-                symmw_tiles_kernel<bq_c7, false><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
-        } else if (p->storage == BQ_F64) {
-            if (add_one)
-                symmw_tiles_kernel<double, true><<<tiles, 256, 0, st>>>((const double *)p->panel, nb, W, ldw, slab, nlive, ch);
-            else
-                symmw_tiles_kernel<double, false><<<tiles, 256, 0, st>>>((const double *)p->panel, nb, W, ldw, slab, nlive, ch);
-        } else {
-            if (add_one)
-                symmw_tiles_kernel<float, true><<<tiles, 256, 0, st>>>((const float *)p->panel, nb, W, ldw, slab, nlive, ch);
-            else
-                symmw_tiles_kernel<float, false><<<tiles, 256, 0, st>>>((const float *)p->panel, nb, W, ldw, slab, nlive, ch);
-        }
+        bq_panel_dispatch(p, add_one, [&](auto pv, auto one) {
+            symmw_tiles_kernel<bq_pelem<decltype(pv)>, decltype(one)::value><<<tiles, 256, 0, st>>>(pv, nb, W, ldw, slab, nlive, ch);
+        });
         symmw_reduce_kernel<<<red, 1024, 0, st>>>(slab, nb, out, ldw, nlive, ch);
         BQ_HIP(hipGetLastError());
     }

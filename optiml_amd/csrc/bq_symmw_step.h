@@ -1,7 +1,16 @@
 // Pieces of the fp64-MFMA symmetric panel products (bq_symmw.hip: every tile for up to 16 columns; bq_symmp.hip: the class-routed
-// one-vs-one product): the 16-element step loads of a lane's row, the f64 MFMA and the wave-local LDS barrier.
+// one-vs-one product): the blocking constants, the 16-element step loads of a lane's row, the f64 MFMA and the wave-local LDS barrier.
 #pragma once
 #include "bq_symv_tile.h"
+
+namespace bq_mfma {   // the two product files take these short names with a using-directive
+constexpr int WJG = 4;     // tiles per strip
+constexpr int CK = BQ_SYMMW_CK;
+constexpr int TP = 72;     // pitch (doubles) of a wave's 16 x 64 transpose image; also its 16 x 64 reduction image (pitch RP)
+constexpr int RP = 65;
+constexpr int WP = 17;     // pitch of the W_J stage (256 rows x 16 slots)
+static_assert(CK == 16, "the column chunk is the MFMA's N");
+}  // namespace bq_mfma
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 

@@ -17,6 +17,11 @@
 // all-gather per product hands every rank all S segment vectors, which are then added in segment order — the same
 // association for any rank count, so 1/2/4/8-GPU iterates are bit-identical.  (BQ_SYM_EXCHANGE=allreduce: each rank adds
 // its own segments and the rank partials meet in one ncclAllReduce — the sum's association then depends on the ring.)
+//
+// Shared with the other product files: the storage dispatch of the launchers (bq_panel_dispatch, bq_c7.h; launch_tiles hands it the
+// timed launch, and the compact layout at 8 rows per step, which is not built, is an error there) and the fixed-order walk of a slab
+// column (slab_walk under seg_thread_sum, bq_symv_tile.h).  The strip body of symv_tiles_kernel is its own: bq_symmp.hip's single
+// kernel repeats it, because as one inlined function template this kernel compiled to other code than it has alone.
 #include <cstdlib>
 
 #include <hip/hip_ext.h>
@@ -276,30 +281,15 @@ static int launch_tiles(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, in
     if (done != nullptr) bq_prof_skip_arg(ctx, e0, &skip, &skip_seq);
     const bool ext = !bracket && e0 != nullptr;
     const dim3 grid((unsigned)nstrips), block(256);
-    hipError_t err;
-    if (panel.storage == BQ_F64C) {
-        if constexpr (SR == 4) {
-            const bq_c7p pv = bq_c7_view(panel.base, panel.elems);
-            if (add_one)
-                err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<bq_c7, true, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
-            else
-                err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<bq_c7, false, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
-        } else {
+    hipError_t err = hipSuccess;
+    bq_panel_dispatch(panel, add_one, [&](auto pv, auto one) {
+        using T = bq_pelem<decltype(pv)>;
+        if constexpr (std::is_same<T, bq_c7>::value && SR != 4)
             err = hipErrorInvalidValue;   // not built: launch_any keeps the compact layout at 4 rows per step
-        }
-    } else if (panel.storage == BQ_F64) {
-        const double *pv = (const double *)panel.base;
-        if (add_one)
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<double, true, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
         else
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<double, false, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
-    } else {
-        const float *pv = (const float *)panel.base;
-        if (add_one)
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<float, true, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
-        else
-            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<float, false, JG, SR>, grid, block, pv, I0, nb, w, slab, done, skip, skip_seq);
-    }
+            err = launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<T, decltype(one)::value, JG, SR>, grid, block, pv, I0, nb, w, slab,
+                               done, skip, skip_seq);
+    });
     if (err != hipSuccess) {
         bq_prof_drop(ctx, e0, e1);
         bq_set_error("symv_tiles launch: %s", hipGetErrorString(err));

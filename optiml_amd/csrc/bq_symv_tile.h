@@ -1,5 +1,5 @@
-// Pieces shared by the symmetric panel products (bq_symv.hip: one column; bq_symm.hip: several): the 16-byte tile loads, the
-// linear strip index of a tile row and the fixed-order walk of a slab column.
+// Pieces shared by the symmetric panel products (bq_symv.hip: one column; bq_symm.hip, bq_symmw.hip: several; bq_symmp.hip: one per
+// class pair): the 16-byte tile loads, the linear strip index of a tile row and the fixed-order walk of a slab column.
 #pragma once
 #include "bq_c7.h"
 #include "bq_common.h"
@@ -46,47 +46,48 @@ __device__ __host__ __forceinline__ int64_t strips_before(int64_t I) {  // sum_{
     return JG * qq * (qq + 1) / 2 + rr * (qq + 1);
 }
 
+// The fixed-order walk of a slab column: entries first, first + 4, ... < count of `base` (stride doubles apart) are added to two
+// chains (s0: entries k, k + 8, ...; s1: k + 4, k + 12, ...), each in its own order — but the LOADS of four turns are issued
+// together (round 5): written as one load per turn the loop was a chain of L2 round trips (~11 of them at nb = 79, ~50 at nb = 391:
+// most of the reduce kernel's 7 us on short grids); the association, and with it every bit, is what it was.
+__device__ __forceinline__ void slab_walk(const double *base, int64_t first, int64_t count, int64_t stride, double &s0, double &s1) {
+    int64_t k = first;
+    for (; k + 28 < count; k += 32) {   // four turns of both chains: all eight entries exist
+        const double a0 = base[(k) * stride], b0 = base[(k + 4) * stride], a1 = base[(k + 8) * stride], b1 = base[(k + 12) * stride];
+        const double a2 = base[(k + 16) * stride], b2 = base[(k + 20) * stride], a3 = base[(k + 24) * stride], b3 = base[(k + 28) * stride];
+        s0 += a0;
+        s1 += b0;
+        s0 += a1;
+        s1 += b1;
+        s0 += a2;
+        s1 += b2;
+        s0 += a3;
+        s1 += b3;
+    }
+    for (; k < count; k += 8) {
+        s0 += base[k * stride];
+        if (k + 4 < count) s1 += base[(k + 4) * stride];
+    }
+}
+
 // Partial sum of output block a over the slab entries S[a][b] that the tile rows [c0, c1) produced, b ascending:
 //   row parts live at b = first tile of a strip (b % JG == 0, b <= a) when tile row a lies in [c0, c1),
 //   col parts at every b > a inside [c0, c1).
-// 1024 threads: thread (r, q) sums every 4th entry of that fixed entry list (two independent chains each for load-level
-// parallelism); the four partial sums are combined in the fixed order q = 0..3.  Every thread returns the combined value.
+// 1024 threads: thread (r, q) sums every 4th entry of that fixed entry list (slab_walk's two chains); the four partial sums are
+// combined in the fixed order q = 0..3.  Every thread returns the combined value.
 template <int JG>
 __device__ __forceinline__ double seg_thread_sum(const double *__restrict__ p, int64_t a, int64_t c0, int64_t c1, int q) {
     double s0 = 0.0, s1 = 0.0;
     int64_t e = 0;   // running index over the entry list: row parts (b = 0, JG, 2JG, ... <= a) then col parts (b > a)
-    // Two chains (s0: entries k, k + 8, ...; s1: k + 4, k + 12, ...), each added in its own order — but the LOADS of four turns are
-    // issued together (round 5): written as one load per turn the loop was a chain of L2 round trips (~11 of them at nb = 79, ~50 at
-    // nb = 391: most of this kernel's 7 us on short grids); the association, and with it every bit, is what it was.
-    auto walk = [&](const double *base, int64_t first, int64_t count, int64_t stride) {
-        int64_t k = first;
-        for (; k + 28 < count; k += 32) {   // four turns of both chains: all eight entries exist
-            const double a0 = base[(k) * stride], b0 = base[(k + 4) * stride], a1 = base[(k + 8) * stride], b1 = base[(k + 12) * stride];
-            const double a2 = base[(k + 16) * stride], b2 = base[(k + 20) * stride], a3 = base[(k + 24) * stride], b3 = base[(k + 28) * stride];
-            s0 += a0;
-            s1 += b0;
-            s0 += a1;
-            s1 += b1;
-            s0 += a2;
-            s1 += b2;
-            s0 += a3;
-            s1 += b3;
-        }
-        for (; k < count; k += 8) {
-            s0 += base[k * stride];
-            if (k + 4 < count) s1 += base[(k + 4) * stride];
-        }
-    };
     if (a >= c0 && a < c1) {
         const int64_t nrow = a / JG + 1;
-        walk(p, q, nrow, (int64_t)JG * ST);
+        slab_walk(p, q, nrow, (int64_t)JG * ST, s0, s1);
         e = nrow;
     }
     const int64_t bs = (a + 1 > c0) ? a + 1 : c0;
     const int64_t ncol = c1 > bs ? c1 - bs : 0;
     // keep the q-assignment a function of the position in the whole list (row parts first)
     const int64_t shift = (4 - (e & 3)) & 3;
-    walk(p + bs * ST, (q + shift) & 3, ncol, ST);
+    slab_walk(p + bs * ST, (q + shift) & 3, ncol, ST, s0, s1);
     return s0 + s1;   // this thread's share (every 4th entry, q = its phase) of the segment's entry list
 }
-

@@ -1,0 +1,188 @@
+"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`): the device solver of many columns on one
+Gram panel, the one-off multi-column products, the device memory budget of a solve, and the way a column's result becomes the
+`SVC` that `SVC.fit` leaves.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ... import _lib
+from ...device import get_context
+from ...opti.constrained import ProjectedGradient
+from ._base import SVC, ClassifierMixin, BaseEstimator
+from .kernels import LinearKernel, gaussian
+from .losses import squared_hinge
+
+MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
+
+
+def column_bytes(n):
+    """Device state of one column on n rows: about 16 n-vectors (the solver's x, g, d, Qd, bounds, labels, product input and
+    output), each padded by a tile."""
+    return 16 * 8 * (n + 256)
+
+
+def device_free_bytes():
+    free, total = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().bq_ctx_mem_info(get_context().handle, C.byref(free), C.byref(total)))
+    return free.value
+
+
+def solver_kind(optimizer):
+    return _lib.PG if issubclass(optimizer, ProjectedGradient) else _lib.FW
+
+
+def _pair_array(pairs):
+    return _lib.as_i32(np.asarray(pairs, dtype=np.int32).reshape(-1))
+
+
+class _DeviceMultiSolver:
+    def __init__(self, problem, kind, Y, ub, eps, max_iter, t=0.0, x0=None):
+        self._lib = _lib.load()
+        self.k, self.n = Y.shape
+        self._h = C.c_void_p()
+        Y = _lib.as_f64(Y, self.k * self.n, 'Y')
+        _lib.check(self._create(problem.handle, kind, Y, ub, x0, float(eps), int(max_iter), float(t)))
+
+    def _x0(self, x0):
+        return None if x0 is None else _lib.as_f64(x0, self.k * self.n, 'x0')
+
+    def _create(self, handle, kind, Y, ub, x0, eps, max_iter, t):
+        """The create call, the one part a subclass replaces; it converts ub, then x0 (`_x0`)."""
+        boxes = np.ndim(ub) == 2   # one box per column (k x n): bq_msolver_create_boxes and the 16-column product
+        ub = _lib.as_f64(ub, self.k * self.n if boxes else self.n, 'ub')
+        x0 = self._x0(x0)
+        create = self._lib.bq_msolver_create_boxes if boxes else self._lib.bq_msolver_create
+        return create(handle, kind, self.k, _lib.ptr(Y), _lib.ptr(ub), _lib.ptr(x0), eps, max_iter, t, C.byref(self._h))
+
+    def run(self, max_steps):
+        stats = np.zeros((self.k, max_steps), dtype=_lib.STAT_DTYPE)
+        n = np.zeros(self.k, dtype=np.int64)
+        status = np.zeros(self.k, dtype=np.int32)
+        _lib.check(self._lib.bq_msolver_run(self._h, max_steps, stats.ctypes.data_as(C.POINTER(_lib.IterStat)), max_steps,
+                                            n.ctypes.data_as(C.POINTER(C.c_int64)), status.ctypes.data_as(C.POINTER(C.c_int))))
+        if (status < 0).any():
+            raise ValueError('array must not contain infs or NaNs')
+        return [stats[c, :n[c]] for c in range(self.k)], [_lib.STATUS[int(s)] for s in status]
+
+    def state(self, c):
+        it, st, f = C.c_int64(0), C.c_int(0), C.c_double(0)
+        _lib.check(self._lib.bq_msolver_state(self._h, c, C.byref(it), C.byref(st), C.byref(f)))
+        return it.value, _lib.STATUS.get(st.value, 'unknown'), f.value
+
+    def get(self, c, what):
+        out = np.empty(self.n)
+        _lib.check(self._lib.bq_msolver_get(self._h, c, what, _lib.ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.bq_msolver_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None):
+    """Run the batched solver (`problem`: a device problem of KernelQuadratic 'svc'; Y: k x n labels +-1; ub: n, or k x n for one box
+    per column (bq_msolver_create_boxes); x0: k x n or None)
+    to the end: per class a dict (rows: the iteration records, status, iter, f_x, x, g) as a single-class optimizer ends them.
+    solver: an already created solver of these columns instead of bq_msolver_create(_boxes)."""
+    solver = _DeviceMultiSolver(problem, kind, Y, ub, eps, max_iter, t, x0) if solver is None else solver
+    k = Y.shape[0]
+    try:
+        rows = [[] for _ in range(k)]
+        status = ['unknown'] * k
+        while 'unknown' in status:
+            recs, status = solver.run(chunk)
+            for c in range(k):
+                rows[c].append(recs[c])
+        out = []
+        for c in range(k):
+            it, st, f = solver.state(c)
+            out.append(dict(rows=np.concatenate(rows[c]), status=st, iter=it, f_x=f, x=solver.get(c, _lib.GET_X_NOW),
+                            g=solver.get(c, _lib.GET_G_NOW)))
+        return out
+    finally:
+        solver.close()
+
+
+def _gram_matmat(problem, W, wide=False):
+    """OUT[c] = K W[c] for the rows of W, one multi-column product (bq_problem_gram_matmat; wide: the 16-column
+    bq_problem_gram_matmat_wide)."""
+    W = np.ascontiguousarray(W, dtype=float)
+    out = np.empty_like(W)
+    fn = _lib.load().bq_problem_gram_matmat_wide if wide else _lib.load().bq_problem_gram_matmat
+    _lib.check(fn(problem.handle, W.shape[0], _lib.ptr(W), _lib.ptr(out)))
+    return out
+
+
+def gram_matmat_pairs(problem, cls_tiles, pairs, W):
+    """OUT[p] = K W[p] on the rows of pair p's classes and 0 elsewhere, one routed product (bq_problem_gram_matmat_pairs)."""
+    W = np.ascontiguousarray(W, dtype=float)
+    out = np.empty_like(W)
+    ct, pr = _lib.as_i32(cls_tiles), _pair_array(pairs)
+    _lib.check(_lib.load().bq_problem_gram_matmat_pairs(problem.handle, len(ct) - 1, _lib.iptr(ct), W.shape[0], _lib.iptr(pr),
+                                                        _lib.ptr(W), _lib.ptr(out)))
+    return out
+
+
+def fitted_svc(est, quad, r, X, y, pos=None):
+    """Make `est`, a fresh SVC of the configuration, the SVC that SVC.fit on (X, y: +-1) leaves, from its column's result `r` of
+    `solve_batched` on `quad`'s panel (pos: the panel rows of X's rows, in their order, where the panel holds other rows too).
+    Returns the support mask; the intercept needs a product and is left to the caller (`intercept`)."""
+    n = len(y)
+    x, g = (r['x'], r['g']) if pos is None else (r['x'][pos], r['g'][pos])
+    # the optimizer as SVC.fit leaves it (constrained/_base.py: minimize) — constructed, not run
+    opt = est.optimizer(quad=quad, ub=np.ones(n) * est.C, tol=est.tol, max_iter=est.max_iter, verbose=est.verbose)
+    if len(r['rows']):
+        opt.iter = int(r['rows'][-1]['iter'])
+        opt._after_row(r['rows'][-1])
+    opt.status, opt.f_x, opt.x, opt.g_x = r['status'], r['f_x'], x, g
+    est.train_loss_history = [float(f) for f in r['rows']['f']]
+    est.optimizer = opt
+    est.classes_ = np.array([0, 1])   # OneVsRestClassifier and OneVsOneClassifier fit each SVC on 0 / 1 labels
+    est.alphas_ = opt.x
+    sv = est.alphas_ > 1e-6
+    est.support_ = np.arange(n)[sv]
+    est.support_vectors_ = X[sv]
+    est.dual_coef_ = est.alphas_[sv] * y[sv]
+    if isinstance(est.kernel, LinearKernel):
+        est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
+    return sv
+
+
+def intercept(y, u, sv):
+    """SVC.fit's intercept of the regularised-intercept dual from u = K (alpha y) on the support vectors `sv`, statement for
+    statement."""
+    b = 0.
+    b += float(np.sum(y[sv] - u[sv]))
+    b /= int(sv.sum())
+    return b
+
+
+class _MultiClassSVC(ClassifierMixin, BaseEstimator):
+    """Constructor and prototype of the multi-class estimators: SVC's arguments, SVC's checks."""
+
+    def __init__(self, loss=squared_hinge, kernel=gaussian, C=1, rho=1, mu=1, fit_intercept=True, intercept_scaling=1,
+                 reg_intercept=False, dual=False, optimizer=ProjectedGradient, master_solver='clarabel', learning_rate='auto',
+                 momentum_type='none', momentum=0.9, max_iter=1000, max_f_eval=15000, tol=1e-4, batch_size=None, shuffle=True,
+                 random_state=None, early_stopping=False, validation_split=0., patience=5, verbose=False, master_verbose=False,
+                 storage='f64'):
+        self._kw = dict(loss=loss, kernel=kernel, C=C, rho=rho, mu=mu, fit_intercept=fit_intercept,
+                        intercept_scaling=intercept_scaling, reg_intercept=reg_intercept, dual=dual, optimizer=optimizer,
+                        master_solver=master_solver, learning_rate=learning_rate, momentum_type=momentum_type,
+                        momentum=momentum, max_iter=max_iter, max_f_eval=max_f_eval, tol=tol, batch_size=batch_size,
+                        shuffle=shuffle, random_state=random_state, early_stopping=early_stopping,
+                        validation_split=validation_split, patience=patience, verbose=verbose,
+                        master_verbose=master_verbose, storage=storage)
+        SVC(**self._kw)   # SVC's checks, SVC's exceptions
+        for name, value in self._kw.items():
+            setattr(self, name, value)
+
+    def _prototype(self):
+        return SVC(**{name: getattr(self, name) for name in self._kw})   # set_params may have changed them

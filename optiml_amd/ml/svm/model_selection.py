@@ -15,7 +15,6 @@ time.  Every other configuration runs exactly GridSearchCV's calls: `estimator.s
 y[te])` per candidate and fold.
 """
 import copy
-import ctypes as C
 import itertools
 
 import numpy as np
@@ -23,17 +22,16 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ...opti.constrained import ProjectedGradient
 from ._base import SVC
+from ._batched import MEMORY_SHARE, _gram_matmat, column_bytes, device_free_bytes, intercept, solve_batched, solver_kind
 from .kernels import BaseEstimator, LinearKernel
-from .multiclass import OneVsRestSVC, uses_batched_path, binarize, solve_batched, _gram_matmat
+from .multiclass import OneVsRestSVC, uses_batched_path, binarize
 from .onevsone import OneVsOneSVC
 
 __all__ = ['SVCGridSearchCV', 'parameter_grid', 'check_cv_splits', 'plan_columns', 'aggregate_scores', 'uses_batched_search']
 
 BATCHED_KEYS = frozenset({'C', 'kernel'})
 MAX_COLUMNS = 4096   # columns per batched solve at most (see _column_cap)
-MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
 
 
 def parameter_grid(param_grid):
@@ -178,19 +176,10 @@ def aggregate_scores(candidates, scores):
 
 def column_cap(n, free_bytes, slab_bytes):
     """Columns one batched solve may take with `free_bytes` of device memory free after the panel: MEMORY_SHARE of it, less the
-    solver's 16-column slab (`slab_bytes`), over the device state of a column (about 16 n-vectors: the solver's x, g, d, Qd,
-    bounds, labels, product input and output); at most MAX_COLUMNS, at least 16.  Larger grids run in several solves; the split
-    does not change any column's bits (the product is batch-invariant)."""
-    per_col = 16 * 8 * (n + 256)
+    solver's 16-column slab (`slab_bytes`), over the device state of a column (`column_bytes`); at most MAX_COLUMNS, at least 16.
+    Larger grids run in several solves; the split does not change any column's bits (the product is batch-invariant)."""
     budget = int(free_bytes * MEMORY_SHARE) - int(slab_bytes)
-    return int(max(16, min(MAX_COLUMNS, budget // per_col)))
-
-
-def _device_column_cap(dev, n):
-    lib = _lib.load()
-    free, total = C.c_int64(0), C.c_int64(0)
-    _lib.check(lib.bq_ctx_mem_info(get_context().handle, C.byref(free), C.byref(total)))
-    return column_cap(n, free.value, lib.bq_problem_wide_slab_bytes(dev.handle))
+    return int(max(16, min(MAX_COLUMNS, budget // column_bytes(n))))
 
 
 class SVCGridSearchCV(BaseEstimator):
@@ -266,13 +255,13 @@ class SVCGridSearchCV(BaseEstimator):
         n_iter = np.full((nc, ns, width), -1, dtype=np.int64)
         status = np.full((nc, ns, width), '', dtype=object)
         dec = [[[None] * len(folds[f][1]) for f in range(ns)] for _ in range(nc)]   # held-out decision values per column
-        kind = _lib.PG if issubclass(proto.optimizer, ProjectedGradient) else _lib.FW
+        kind = solver_kind(proto.optimizer)
         for g in groups:   # one panel at a time
             m = len(g['cols'])
             obj = KernelQuadratic(X, -np.ones(n), 'svc', g['kernel'], y=g['Y'][0], storage=proto.storage,
                                   tune_placement=proto._streams_panel(), expected_products=proto.max_iter * ((m + 15) // 16))
             dev = obj.device_problem()
-            cap = _device_column_cap(dev, n)
+            cap = column_cap(n, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle))
             for c0 in range(0, m, cap):
                 cols = g['cols'][c0:c0 + cap]
                 Y, UB = g['Y'][c0:c0 + cap], g['UB'][c0:c0 + cap]
@@ -286,9 +275,7 @@ class SVCGridSearchCV(BaseEstimator):
                 U = _gram_matmat(dev, W, wide=True)
                 for j, (ci, f, row, C) in enumerate(cols):
                     sv = svs[j]
-                    b = 0.
-                    b += float(np.sum(Y[j][sv] - U[j][sv]))
-                    b /= int(sv.sum())
+                    b = intercept(Y[j], U[j], sv)
                     n_iter[ci, f, row], status[ci, f, row] = res[j]['iter'], res[j]['status']
                     te = splits[f][1]
                     kernel = candidates[ci].get('kernel', proto.kernel)

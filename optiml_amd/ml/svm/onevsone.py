@@ -22,16 +22,14 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ...opti.constrained import ProjectedGradient
-from ._base import SVC, ClassifierMixin, BaseEstimator
-from .kernels import LinearKernel, gaussian
-from .losses import squared_hinge
-from .multiclass import _DeviceMultiSolver, solve_batched, uses_batched_path
+from ._batched import (MEMORY_SHARE, _DeviceMultiSolver, _MultiClassSVC, _pair_array, column_bytes, device_free_bytes, fitted_svc,
+                       gram_matmat_pairs, intercept, solve_batched, solver_kind)
+from .kernels import LinearKernel
+from .multiclass import uses_batched_path
 
 __all__ = ['OneVsOneSVC', 'uses_batched_ovo', 'sort_plan', 'ovo_pairs', 'pair_problem', 'ovo_decision']
 
 TILE = 256
-MEMORY_SHARE = 0.5   # share of the free device memory (after the panel) that one solve's columns and slab may take
 
 
 def uses_batched_ovo(svc, world):
@@ -90,34 +88,18 @@ def ovo_decision(predictions, confidences, ncls):
     return votes + conf / (3 * (np.abs(conf) + 1))
 
 
-def _pair_array(pairs):
-    return _lib.as_i32(np.asarray(pairs, dtype=np.int32).reshape(-1))
-
-
 class _DevicePairSolver(_DeviceMultiSolver):
     """`bq_msolver_create_pairs`: one column per pair on a class-sorted panel."""
 
     def __init__(self, problem, kind, cls_tiles, pairs, Y, UB, eps, max_iter, t=0.0, x0=None):
-        self._lib = _lib.load()
-        self.k, self.n = Y.shape
-        self._h = C.c_void_p()
-        Y = _lib.as_f64(Y, self.k * self.n, 'Y')
+        self._ct, self._pr = _lib.as_i32(cls_tiles), _pair_array(pairs)
+        super().__init__(problem, kind, Y, UB, eps, max_iter, t, x0)
+
+    def _create(self, handle, kind, Y, UB, x0, eps, max_iter, t):
         UB = _lib.as_f64(UB, self.k * self.n, 'UB')
-        x0 = None if x0 is None else _lib.as_f64(x0, self.k * self.n, 'x0')
-        ct, pr = _lib.as_i32(cls_tiles), _pair_array(pairs)
-        _lib.check(self._lib.bq_msolver_create_pairs(problem.handle, kind, len(ct) - 1, _lib.iptr(ct), self.k, _lib.iptr(pr),
-                                                     _lib.ptr(Y), _lib.ptr(UB), _lib.ptr(x0), float(eps), int(max_iter), float(t),
-                                                     C.byref(self._h)))
-
-
-def gram_matmat_pairs(problem, cls_tiles, pairs, W):
-    """OUT[p] = K W[p] on the rows of pair p's classes and 0 elsewhere, one routed product (bq_problem_gram_matmat_pairs)."""
-    W = np.ascontiguousarray(W, dtype=float)
-    out = np.empty_like(W)
-    ct, pr = _lib.as_i32(cls_tiles), _pair_array(pairs)
-    _lib.check(_lib.load().bq_problem_gram_matmat_pairs(problem.handle, len(ct) - 1, _lib.iptr(ct), W.shape[0], _lib.iptr(pr),
-                                                        _lib.ptr(W), _lib.ptr(out)))
-    return out
+        x0 = self._x0(x0)
+        return self._lib.bq_msolver_create_pairs(handle, kind, len(self._ct) - 1, _lib.iptr(self._ct), self.k, _lib.iptr(self._pr),
+                                                 _lib.ptr(Y), _lib.ptr(UB), _lib.ptr(x0), eps, max_iter, t, C.byref(self._h))
 
 
 def pairs_slab_bytes(cls_tiles, pairs):
@@ -130,7 +112,7 @@ def pairs_slab_bytes(cls_tiles, pairs):
 def pair_chunks(pairs, cls_tiles, n_pad, free_bytes):
     """The pairs split into solves that fit MEMORY_SHARE of `free_bytes`: per pair about 16 device n-vectors (the solver's x, g,
     d, Qd, bounds, labels, product input and output) plus its slab region.  The split does not change any pair's bits."""
-    per = [16 * 8 * (n_pad + TILE) + pairs_slab_bytes(cls_tiles, [p]) for p in pairs]
+    per = [column_bytes(n_pad) + pairs_slab_bytes(cls_tiles, [p]) for p in pairs]
     budget = int(free_bytes * MEMORY_SHARE)
     chunks, cur, used = [], [], 0
     for p, b in zip(pairs, per):
@@ -143,7 +125,7 @@ def pair_chunks(pairs, cls_tiles, n_pad, free_bytes):
     return chunks
 
 
-class OneVsOneSVC(ClassifierMixin, BaseEstimator):
+class OneVsOneSVC(_MultiClassSVC):
     """One-vs-one multi-class SVC; constructor arguments and their checks are SVC's.
 
     After `fit`: `classes_`, `n_classes_`, `estimators_` (one fitted SVC per class pair (i, j), i < j, in OneVsOneClassifier's
@@ -151,25 +133,6 @@ class OneVsOneSVC(ClassifierMixin, BaseEstimator):
     `decision_function` (votes plus normalised confidences, m x k; 1-D with two classes), `predict`, `score` as sklearn's
     OneVsOneClassifier(SVC(**kw)).  gamma='scale' resolves on each pair's rows and runs one SVC per pair (see the module).
     """
-
-    def __init__(self, loss=squared_hinge, kernel=gaussian, C=1, rho=1, mu=1, fit_intercept=True, intercept_scaling=1,
-                 reg_intercept=False, dual=False, optimizer=ProjectedGradient, master_solver='clarabel', learning_rate='auto',
-                 momentum_type='none', momentum=0.9, max_iter=1000, max_f_eval=15000, tol=1e-4, batch_size=None, shuffle=True,
-                 random_state=None, early_stopping=False, validation_split=0., patience=5, verbose=False, master_verbose=False,
-                 storage='f64'):
-        self._kw = dict(loss=loss, kernel=kernel, C=C, rho=rho, mu=mu, fit_intercept=fit_intercept,
-                        intercept_scaling=intercept_scaling, reg_intercept=reg_intercept, dual=dual, optimizer=optimizer,
-                        master_solver=master_solver, learning_rate=learning_rate, momentum_type=momentum_type,
-                        momentum=momentum, max_iter=max_iter, max_f_eval=max_f_eval, tol=tol, batch_size=batch_size,
-                        shuffle=shuffle, random_state=random_state, early_stopping=early_stopping,
-                        validation_split=validation_split, patience=patience, verbose=verbose,
-                        master_verbose=master_verbose, storage=storage)
-        SVC(**self._kw)   # SVC's checks, SVC's exceptions
-        for name, value in self._kw.items():
-            setattr(self, name, value)
-
-    def _prototype(self):
-        return SVC(**{name: getattr(self, name) for name in self._kw})   # set_params may have changed them
 
     @property
     def n_classes_(self):
@@ -205,11 +168,9 @@ class OneVsOneSVC(ClassifierMixin, BaseEstimator):
         obj = KernelQuadratic(Xp, -np.ones(n_pad), 'svc', proto.kernel, y=np.ones(n_pad), storage=proto.storage,
                               tune_placement=proto._streams_panel(), expected_products=proto.max_iter)
         dev = obj.device_problem()
-        kind = _lib.PG if issubclass(proto.optimizer, ProjectedGradient) else _lib.FW
-        free, total = C.c_int64(0), C.c_int64(0)
-        _lib.check(_lib.load().bq_ctx_mem_info(get_context().handle, C.byref(free), C.byref(total)))
+        kind = solver_kind(proto.optimizer)
         ests = []
-        for chunk in pair_chunks(pairs, cls_tiles, n_pad, free.value):
+        for chunk in pair_chunks(pairs, cls_tiles, n_pad, device_free_bytes()):
             Y = np.stack([np.where(pcode == j, 1., -1.) for _, j in chunk])
             UB = np.stack([np.where(((pcode == i) | (pcode == j)) & ~ghost, float(proto.C), 0.) for i, j in chunk])
             solver = _DevicePairSolver(dev, kind, cls_tiles, chunk, Y, UB, 1e-6, proto.max_iter)
@@ -219,39 +180,16 @@ class OneVsOneSVC(ClassifierMixin, BaseEstimator):
             for p, (i, j) in enumerate(chunk):
                 rows, yp = pair_problem(codes, i, j)
                 pos = index[rows]
-                est, sv = self._estimator(proto, obj, res[p], X[rows], yp, pos)
+                est = self._prototype()
+                sv = fitted_svc(est, obj, res[p], X[rows], yp, pos)
                 W[p][pos[sv]] = est.dual_coef_
                 fits.append((est, yp, pos, sv))
             U = gram_matmat_pairs(dev, cls_tiles, chunk, W)
             for p, (est, yp, pos, sv) in enumerate(fits):
-                est.intercept_ = 0.
-                est.intercept_ += float(np.sum(yp[sv] - U[p][pos][sv]))
-                est.intercept_ /= int(sv.sum())
+                est.intercept_ = intercept(yp, U[p][pos], sv)
                 ests.append(est)
         del dev, obj
         return ests
-
-    def _estimator(self, proto, obj, r, Xpair, yp, pos):
-        """The SVC that SVC.fit on the pair's rows leaves, from the pair's column (its panel rows `pos`, in the rows' order)."""
-        est = self._prototype()
-        ub = np.ones(len(pos)) * proto.C
-        # the optimizer as SVC.fit leaves it (constrained/_base.py: minimize) — constructed, not run
-        opt = proto.optimizer(quad=obj, ub=ub, tol=proto.tol, max_iter=proto.max_iter, verbose=proto.verbose)
-        if len(r['rows']):
-            opt.iter = int(r['rows'][-1]['iter'])
-            opt._after_row(r['rows'][-1])
-        opt.status, opt.f_x, opt.x, opt.g_x = r['status'], r['f_x'], r['x'][pos], r['g'][pos]
-        est.train_loss_history = [float(f) for f in r['rows']['f']]
-        est.optimizer = opt
-        est.classes_ = np.array([0, 1])   # OneVsOneClassifier fits each SVC on 0 / 1 labels
-        est.alphas_ = opt.x
-        sv = est.alphas_ > 1e-6
-        est.support_ = np.arange(len(pos))[sv]
-        est.support_vectors_ = Xpair[sv]
-        est.dual_coef_ = est.alphas_[sv] * yp[sv]
-        if isinstance(est.kernel, LinearKernel):
-            est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
-        return est, sv
 
     def decision_function(self, X):
         X = np.ascontiguousarray(X, dtype=float)
