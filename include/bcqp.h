@@ -51,6 +51,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_boxes and bq_problem_gram_matmat_wide were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_pairs, bq_problem_gram_matmat_pairs, bq_pairs_slab_bytes and bq_pairs_work_list were added) */
 /* (still 3: the structure flag BQ_PLAIN_PANEL was added) */
+/* (still 3: bq_msolver_create_svr was added) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -355,6 +356,16 @@ int bq_msolver_create_boxes(bq_problem *p, int kind, int k, const double *Y, con
  * position and in any batch.  x0, eps, max_iter, fw_t, run / state / get / destroy: as bq_msolver_create (cls = the pair). */
 int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const int *cls_tiles, int m, const int *pairs, const double *Y,
                             const double *UB, const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out);
+/* The batched solver on k epsilon-insensitive SVR duals (sklearn MultiOutputRegressor over SVR.fit, svm/_base.py:1091-1104 once per
+ * target, on ONE Gram panel).  p: a kernel-built BQ_SVR problem on a single-rank context with a resident packed panel (anything else
+ * is BQ_ERR_BADARG); its own q is not used.  QL: k x 2n, the linear term of column c ([-y_c; y_c] + epsilon); ub: 2n (shared,
+ * lb = 0); x0: k x 2n or NULL (mid-box).  Column c runs the iteration of bq_solver_create(kind) on the SVR problem with linear term
+ * QL[c] — same formulas, thresholds, stop tests and records; an iteration's products are one panel stream per 4 live targets of
+ * the n-vectors d+ - d-, and a target that stops leaves the batch.  Target c's iterates have the same bits alone, at any position
+ * and in any batch (they agree with bq_solver_create's to rounding: another product kernel).  eps, max_iter, fw_t, run / state /
+ * get / destroy: as bq_msolver_create, on vectors of 2n (cls = the target). */
+int bq_msolver_create_svr(bq_problem *p, int kind, int k, const double *QL, const double *ub, const double *x0, double eps,
+                          int64_t max_iter, double fw_t, bq_msolver **out);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

@@ -19,6 +19,11 @@
 // of a and b, 0 elsewhere, and the pair-routed product (bq_symmp.hip) for every pass, which streams the panel once for all pairs.
 // The live kernel is the plan's: it keeps pos[] the identity (column = pair) and gathers every class's live pairs into the slots of
 // its diagonal block; a stopped pair's blocks leave the stream at the next iteration.
+//
+// bq_msolver_create_svr is the same batch on a BQ_SVR problem (multi-output regression: target c has the linear term
+// q_c = [-y_c; y_c] + eps and every target the Hessian [P -P; -P P]): the columns are vectors of 2n, one thread of the start-up and
+// update kernels owns the elements i and n + i of a target (mstart_*_svr_kernel, mpgfw_update_svr_kernel), the product input is
+// d+ - d- (n), and the closing kernel is mfinish_kernel, whose element code handles both halves (bq_epi_element).
 #include "bq_common.h"
 #include "bq_epilogue.h"
 
@@ -30,8 +35,9 @@ struct bq_msolver {
     int kind = BQ_PG, k = 0;
     bool wide = false;   // bq_msolver_create_boxes: the 16-column product (bq_symmw.hip) for every pass
     bq_pairs_plan *plan = nullptr;   // bq_msolver_create_pairs: the pair-routed product (bq_symmp.hip) for every pass
-    int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ldN >= nb * 256)
+    int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ld >= nb * 256)
     std::vector<bq_solver *> cls;
+    double *ql = nullptr;   // bq_msolver_create_svr: k x p->ldN, the linear term of every column (else every column has p->q)
     double *sgn = nullptr, *W = nullptr, *out = nullptr, *slab = nullptr;
     bq_epilogue *epi = nullptr;   // 2 x k: do_update 0 (a class's first iteration) and 1
     bq_scal **scs = nullptr;      // k
@@ -78,6 +84,57 @@ __global__ __launch_bounds__(256) void mpgfw_update_kernel(const bq_epilogue *__
     W[pos[blockIdx.y] * ldw + i] = e.sgn[i] * a.d;
 }
 
+// mstart_prep_kernel for BQ_SVR: W[:, c] = x+ - x-
+__global__ __launch_bounds__(256) void mstart_prep_svr_kernel(const bq_epilogue *__restrict__ epi, double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < e.n) W[blockIdx.y * ldw + i] = e.x[i] - e.x[e.n + i];
+}
+
+// mstart_finish_kernel for BQ_SVR, both halves of panel column i: Qd = [u; -u] (+ diag_add x), g = Qd + q_c, u = P (x+ - x-)
+__global__ __launch_bounds__(256) void mstart_finish_svr_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
+                                                                int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const long long j = e.n + i;
+    const double u = out[blockIdx.y * ldw + i], q0 = e.q[i], q1 = e.q[j];
+    double r0 = u, r1 = -u;
+    if (e.diag_add != 0.0) {
+        r0 += e.diag_add * e.x[i];
+        r1 += e.diag_add * e.x[j];
+    }
+    e.Qd[i] = r0;
+    e.Qd[j] = r1;
+    e.g[i] = r0 + q0;
+    e.g[j] = r1 + q1;
+}
+
+// pgfw_update_kernel (bq_vec.hip) for BQ_SVR, target blockIdx.y: the elements i and n + i of one thread, both loaded before the
+// first use, and the product input d+ - d- to the target's slot
+__global__ __launch_bounds__(256) void mpgfw_update_svr_kernel(const bq_epilogue *__restrict__ epi, const int *__restrict__ pos,
+                                                               double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    if (e.sc->done) return;
+    double t, tr;
+    bq_epi_scalars(e, t, tr);
+    const bool upd = e.do_update != 0;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const long long j = e.n + i;
+    const bq_pgfw_raw r0 = bq_pgfw_load(e, i, upd), r1 = bq_pgfw_load(e, j, upd);
+    const bq_pgfw_elem a = bq_pgfw_compute(e.kind, r0, upd, t, tr), b = bq_pgfw_compute(e.kind, r1, upd, t, tr);
+    if (upd) {
+        e.x[i] = a.x;
+        e.g[i] = a.g;
+        e.x[j] = b.x;
+        e.g[j] = b.g;
+    }
+    e.d[i] = a.d;
+    e.d[j] = b.d;
+    W[pos[blockIdx.y] * ldw + i] = a.d - b.d;
+}
+
 // finish_den_kernel (bq_vec.hip) for class blockIdx.y: the same rows per block, the same tree, the class's own ticket
 __global__ __launch_bounds__(256) void mfinish_kernel(const bq_epilogue *__restrict__ epi, const int *__restrict__ pos,
                                                       const double *__restrict__ out, int64_t ldw) {
@@ -101,7 +158,7 @@ extern "C" int bq_msolver_destroy(bq_msolver *m) {
     if (m == nullptr) return BQ_OK;
     hipSetDevice(m->p->ctx->device);
     (void)bq_ctx_sync(m->p->ctx);
-    for (void *ptr : {(void *)m->sgn, (void *)m->W, (void *)m->out, (void *)m->slab, (void *)m->epi, (void *)m->scs, (void *)m->pos,
+    for (void *ptr : {(void *)m->ql, (void *)m->sgn, (void *)m->W, (void *)m->out, (void *)m->slab, (void *)m->epi, (void *)m->scs, (void *)m->pos,
                       (void *)m->nlive})
         if (ptr) hipFree(ptr);
     if (m->nlive_host) {
@@ -129,10 +186,10 @@ static void fill_epi(bq_msolver *m, int c, int do_update, bq_epilogue &e) {
     e.x = s->x;
     e.g = s->g;
     e.d = s->d;
-    e.q = p->q;
+    e.q = m->ql ? m->ql + c * p->ldN : p->q;
     e.lb = s->lb;
     e.ub = s->ub;
-    e.sgn = m->sgn + c * m->ldw;
+    e.sgn = m->sgn ? m->sgn + c * m->ldw : nullptr;
     e.Qd = s->Qd;
     e.sc = s->sc;
     e.part = s->partials;
@@ -160,27 +217,37 @@ static int msolver_product(bq_msolver *m, int slots) {
     return bq_launch_symm(p, p->add_one, m->W, m->ldw, slots, m->slab, m->out, m->nlive);
 }
 
-// ub_ld: 0 (one box for every class) or n (class c's box at ub + c * n); plan: the pair-routed product (taken over by the solver)
+// ub_ld: 0 (one box for every class) or n (class c's box at ub + c * n); plan: the pair-routed product (taken over by the solver);
+// QL: null (a BQ_SVC problem, Y: k x n labels), or the k x 2n linear terms of a BQ_SVR problem (Y null)
 static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, int64_t ub_ld, bool wide,
                           const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out,
-                          bq_pairs_plan *plan = nullptr);
+                          bq_pairs_plan *plan = nullptr, const double *QL = nullptr);
 
-static int msolver_check(bq_problem *p, int kind, int k, const double *Y, const double *ub, bq_msolver **out) {
-    BQ_ARG(p && Y && ub && out, "NULL argument");
+static int msolver_check(bq_problem *p, int kind, int k, const double *Y, const double *ub, bq_msolver **out,
+                         const double *QL = nullptr) {
+    BQ_ARG(p && (Y || QL) && ub && out, "NULL argument");
     BQ_ARG(kind == BQ_PG || kind == BQ_FW, "the batched solver is ProjectedGradient or FrankWolfe");
     BQ_ARG(k >= 1, "k must be >= 1");
-    BQ_ARG(p->structure == BQ_SVC && p->kernel >= 0, "the batched solver takes a kernel-built SVC problem");
+    if (QL)
+        BQ_ARG(p->structure == BQ_SVR && p->kernel >= 0, "the batched SVR solver takes a kernel-built SVR problem");
+    else
+        BQ_ARG(p->structure == BQ_SVC && p->kernel >= 0, "the batched solver takes a kernel-built SVC problem");
     if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
         bq_set_error("the batched solver needs a single-rank context and a resident packed panel (not streamed, not full rows)");
         return BQ_ERR_BADARG;
+    }
+    if (QL) {
+        for (int64_t i = 0; i < (int64_t)k * p->N; ++i) BQ_ARG(std::isfinite(QL[i]), "the linear terms must be finite");
+        return BQ_OK;
     }
     for (int64_t i = 0; i < (int64_t)k * p->n; ++i) BQ_ARG(Y[i] == 1.0 || Y[i] == -1.0, "labels must be +1 or -1");
     return BQ_OK;
 }
 
 static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, int64_t ub_ld, bool wide,
-                          const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out, bq_pairs_plan *plan) {
-    if (int rc = msolver_check(p, kind, k, Y, ub, out)) {
+                          const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out, bq_pairs_plan *plan,
+                          const double *QL) {
+    if (int rc = msolver_check(p, kind, k, Y, ub, out, QL)) {
         bq_pairs_plan_destroy(plan);
         return rc;
     }
@@ -191,14 +258,14 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
     p->refs += 1;
     m->kind = kind;
     m->k = k;
-    m->ldw = p->ldN;
+    m->ldw = p->ld;   // (= p->ldN for BQ_SVC)
     m->wide = wide;
     m->plan = plan;
     const int slots = (int)bq_round_up(k, msolver_ck(m));
     int rc = BQ_OK;
     for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
         bq_solver *s = nullptr;
-        rc = bq_solver_create(p, kind, nullptr, ub + cl * ub_ld, x0 ? x0 + (int64_t)cl * p->n : nullptr, eps, max_iter, fw_t, &s);
+        rc = bq_solver_create(p, kind, nullptr, ub + cl * ub_ld, x0 ? x0 + (int64_t)cl * p->N : nullptr, eps, max_iter, fw_t, &s);
         if (rc == BQ_OK) m->cls.push_back(s);
     }
     auto fail = [&](int code) {
@@ -206,7 +273,11 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
         return code;
     };
     if (rc != BQ_OK) return fail(rc);
-    hipError_t e = hipMalloc(&m->sgn, sizeof(double) * m->ldw * k);
+    // the per-column host array and its device copy: the labels (k x n -> sgn, stride ldw) or the linear terms (k x 2n -> ql, stride ldN)
+    const double *col_src = QL ? QL : Y;
+    double **col_dev = QL ? &m->ql : &m->sgn;
+    const int64_t col_len = QL ? p->N : p->n, col_ld = QL ? p->ldN : m->ldw;
+    hipError_t e = hipMalloc(col_dev, sizeof(double) * col_ld * k);
     if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
     if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
     const int64_t slab_len = plan ? bq_pairs_slab_len(plan) : wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb);
@@ -226,11 +297,11 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
         pos[cl] = cl;
     }
     hipStream_t st = c->stream;
-    e = hipMemsetAsync(m->sgn, 0, sizeof(double) * m->ldw * k, st);
+    e = hipMemsetAsync(*col_dev, 0, sizeof(double) * col_ld * k, st);
     if (e == hipSuccess) e = hipMemsetAsync(m->W, 0, sizeof(double) * m->ldw * slots, st);
     if (e == hipSuccess) e = hipMemsetAsync(m->out, 0, sizeof(double) * m->ldw * slots, st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(m->sgn, sizeof(double) * m->ldw, Y, sizeof(double) * p->n, sizeof(double) * p->n, k,
-                                              hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(*col_dev, sizeof(double) * col_ld, col_src, sizeof(double) * col_len,
+                                              sizeof(double) * col_len, k, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(m->scs, scs.data(), sizeof(bq_scal *) * k, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(m->pos, pos.data(), sizeof(int) * k, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(m->nlive, &k, sizeof(int), hipMemcpyHostToDevice, st);
@@ -286,14 +357,22 @@ extern "C" int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const 
     return msolver_create(p, kind, m, Y, UB, p->n, false, x0, eps, max_iter, fw_t, out, plan);
 }
 
+extern "C" int bq_msolver_create_svr(bq_problem *p, int kind, int k, const double *QL, const double *ub, const double *x0,
+                                     double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
+    return msolver_create(p, kind, k, nullptr, ub, 0, false, x0, eps, max_iter, fw_t, out, nullptr, QL);
+}
+
 static int msolver_first(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
     const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
-    mstart_prep_kernel<<<grid, 256, 0, st>>>(m->epi, m->W, m->ldw);
+    const bool svr = p->structure == BQ_SVR;
+    if (svr) mstart_prep_svr_kernel<<<grid, 256, 0, st>>>(m->epi, m->W, m->ldw);
+    else mstart_prep_kernel<<<grid, 256, 0, st>>>(m->epi, m->W, m->ldw);
     BQ_HIP(hipGetLastError());
     BQ_TRY(msolver_product(m, m->k));
-    mstart_finish_kernel<<<grid, 256, 0, st>>>(m->epi, m->out, m->ldw);
+    if (svr) mstart_finish_svr_kernel<<<grid, 256, 0, st>>>(m->epi, m->out, m->ldw);
+    else mstart_finish_kernel<<<grid, 256, 0, st>>>(m->epi, m->out, m->ldw);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
@@ -304,7 +383,8 @@ static int msolver_iterate(bq_msolver *m) {
     const bq_epilogue *epi = m->epi + (m->started ? m->k : 0);
     m->started = true;
     const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
-    mpgfw_update_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->W, m->ldw);
+    if (p->structure == BQ_SVR) mpgfw_update_svr_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->W, m->ldw);
+    else mpgfw_update_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->W, m->ldw);
     BQ_HIP(hipGetLastError());
     BQ_TRY(msolver_product(m, m->live_host));
     mfinish_kernel<<<grid, 256, 0, st>>>(epi, m->pos, m->out, m->ldw);

@@ -1,6 +1,7 @@
-__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV']
+__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
 from .onevsone import OneVsOneSVC
 from .model_selection import SVCGridSearchCV
+from .multioutput import MultiOutputSVR

@@ -1,6 +1,6 @@
-"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`): the device solver of many columns on one
-Gram panel, the one-off multi-column products, the device memory budget of a solve, and the way a column's result becomes the
-`SVC` that `SVC.fit` leaves.
+"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`): the device solver of many
+columns on one Gram panel, the one-off multi-column products, the device memory budget of a solve, and the way a column's result
+becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
 """
 import ctypes as C
 
@@ -8,10 +8,11 @@ import numpy as np
 
 from ... import _lib
 from ...device import get_context
+from ...opti import KernelQuadratic
 from ...opti.constrained import ProjectedGradient
-from ._base import SVC, ClassifierMixin, BaseEstimator
+from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator
 from .kernels import LinearKernel, gaussian
-from .losses import squared_hinge
+from .losses import squared_hinge, squared_epsilon_insensitive
 
 MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
 
@@ -37,6 +38,9 @@ def _pair_array(pairs):
 
 
 class _DeviceMultiSolver:
+    """k columns on one panel.  `n` is the length of a column's vectors, the dual dimension: Y's row length — the panel's n for
+    the SVC solvers, 2n for `_DeviceSVRSolver`, whose rows are the linear terms."""
+
     def __init__(self, problem, kind, Y, ub, eps, max_iter, t=0.0, x0=None):
         self._lib = _lib.load()
         self.k, self.n = Y.shape
@@ -87,11 +91,23 @@ class _DeviceMultiSolver:
             pass
 
 
+class _DeviceSVRSolver(_DeviceMultiSolver):
+    """`bq_msolver_create_svr`: one column per target on a 'svr' problem.  QL: k x 2n linear terms ([-y_c; y_c] + epsilon), ub: 2n,
+    x0: k x 2n or None; every vector the solver hands out has 2n entries."""
+
+    def _create(self, handle, kind, QL, ub, x0, eps, max_iter, t):
+        ub = _lib.as_f64(ub, self.n, 'ub')
+        x0 = self._x0(x0)
+        return self._lib.bq_msolver_create_svr(handle, kind, self.k, _lib.ptr(QL), _lib.ptr(ub), _lib.ptr(x0), eps, max_iter, t,
+                                               C.byref(self._h))
+
+
 def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None):
     """Run the batched solver (`problem`: a device problem of KernelQuadratic 'svc'; Y: k x n labels +-1; ub: n, or k x n for one box
     per column (bq_msolver_create_boxes); x0: k x n or None)
     to the end: per class a dict (rows: the iteration records, status, iter, f_x, x, g) as a single-class optimizer ends them.
-    solver: an already created solver of these columns instead of bq_msolver_create(_boxes)."""
+    solver: an already created solver of these columns instead of bq_msolver_create(_boxes); only Y's row count is read then, and
+    x, g have the solver's column length (2n for a `_DeviceSVRSolver`)."""
     solver = _DeviceMultiSolver(problem, kind, Y, ub, eps, max_iter, t, x0) if solver is None else solver
     k = Y.shape[0]
     try:
@@ -165,6 +181,78 @@ def intercept(y, u, sv):
     return b
 
 
+class TargetQuadratic(KernelQuadratic):
+    """One target's dual on the panel of a shared 'svr' `KernelQuadratic`: the same X, kernel and device problem, its own linear
+    term q.  `function` / `jacobian` are 1/2 x'Qx + q'x and Qx + q with Qx from the shared panel (`bq_problem_matvec`, which does
+    not read the device problem's q); `release` is left to the shared object, and `x_star`, which the device takes from the
+    problem's own q, is not offered."""
+
+    def __init__(self, shared, q):
+        self.__dict__.update(shared.__dict__)
+        self._shared = shared
+        self._dev = None
+        self.q = np.array(q, dtype=float)
+        if self.q.size != self.ndim:
+            raise ValueError('q size does not match with Q')
+
+    def device_problem(self, ctx=None):
+        return self._shared.device_problem(ctx)
+
+    def release(self):
+        pass
+
+    def x_star(self):
+        raise NotImplementedError('a target\'s view of a shared panel has no x_star: build KernelQuadratic(X, q, \'svr\', kernel)')
+
+    def function_jacobian(self, x):
+        x = np.asarray(x, dtype=float)
+        Qx = self.device_problem().matvec(x)
+        return 0.5 * float(x @ Qx) + float(self.q @ x), Qx + self.q
+
+    def function(self, x):
+        return self.function_jacobian(x)[0]
+
+    def jacobian(self, x):
+        return self.function_jacobian(x)[1]
+
+
+def fitted_svr(est, quad, r, X, y):
+    """Make `est`, a fresh SVR of the configuration, the SVR that SVR.fit on (X, y) leaves, from its column's result `r` (x, g: 2n)
+    of `solve_batched` on `quad`'s panel.  Its optimizer's function is the target's own dual (`TargetQuadratic`: the shared panel
+    with q = [-y; y] + epsilon).  Returns the support mask; the intercept needs a product and is left to the caller
+    (`svr_intercept`)."""
+    n = len(y)
+    quad = TargetQuadratic(quad, np.hstack((-y, y)) + est.epsilon)
+    # the optimizer as SVR.fit leaves it (constrained/_base.py: minimize) — constructed, not run
+    opt = est.optimizer(quad=quad, ub=np.ones(2 * n) * est.C, tol=est.tol, max_iter=est.max_iter, verbose=est.verbose)
+    if len(r['rows']):
+        opt.iter = int(r['rows'][-1]['iter'])
+        opt._after_row(r['rows'][-1])
+    opt.status, opt.f_x, opt.x, opt.g_x = r['status'], r['f_x'], r['x'], r['g']
+    est.train_loss_history = [float(f) for f in r['rows']['f']]
+    est.optimizer = opt
+    est.obj = quad
+    est.alphas_ = opt.x
+    alphas_p, alphas_n = np.split(est.alphas_, 2)
+    sv = np.logical_or(alphas_p > 1e-6, alphas_n > 1e-6)
+    est.support_ = np.arange(n)[sv]
+    est.support_vectors_ = X[sv]
+    est.dual_coef_ = alphas_p[sv] - alphas_n[sv]
+    if isinstance(est.kernel, LinearKernel):
+        est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
+    return sv
+
+
+def svr_intercept(y, u, sv, epsilon):
+    """SVR.fit's intercept of the regularised-intercept dual from u = K (alpha+ - alpha-) on the support vectors `sv`, statement
+    for statement."""
+    b = 0.
+    b += float(np.sum(y[sv] - u[sv]))
+    b -= epsilon
+    b /= int(sv.sum())
+    return b
+
+
 class _MultiClassSVC(ClassifierMixin, BaseEstimator):
     """Constructor and prototype of the multi-class estimators: SVC's arguments, SVC's checks."""
 
@@ -186,3 +274,26 @@ class _MultiClassSVC(ClassifierMixin, BaseEstimator):
 
     def _prototype(self):
         return SVC(**{name: getattr(self, name) for name in self._kw})   # set_params may have changed them
+
+
+class _MultiTargetSVR(RegressorMixin, BaseEstimator):
+    """Constructor and prototype of the multi-output regressor: SVR's arguments, SVR's checks."""
+
+    def __init__(self, loss=squared_epsilon_insensitive, epsilon=0.1, kernel=gaussian, C=1, rho=1, mu=1, fit_intercept=True,
+                 intercept_scaling=1, reg_intercept=False, dual=False, optimizer=ProjectedGradient, master_solver='clarabel',
+                 learning_rate='auto', momentum_type='none', momentum=0.9, max_iter=1000, max_f_eval=15000, tol=1e-4,
+                 batch_size=None, shuffle=True, random_state=None, early_stopping=False, validation_split=0., patience=5,
+                 verbose=False, master_verbose=False, storage='f64'):
+        self._kw = dict(loss=loss, epsilon=epsilon, kernel=kernel, C=C, rho=rho, mu=mu, fit_intercept=fit_intercept,
+                        intercept_scaling=intercept_scaling, reg_intercept=reg_intercept, dual=dual, optimizer=optimizer,
+                        master_solver=master_solver, learning_rate=learning_rate, momentum_type=momentum_type,
+                        momentum=momentum, max_iter=max_iter, max_f_eval=max_f_eval, tol=tol, batch_size=batch_size,
+                        shuffle=shuffle, random_state=random_state, early_stopping=early_stopping,
+                        validation_split=validation_split, patience=patience, verbose=verbose,
+                        master_verbose=master_verbose, storage=storage)
+        SVR(**self._kw)   # SVR's checks, SVR's exceptions
+        for name, value in self._kw.items():
+            setattr(self, name, value)
+
+    def _prototype(self):
+        return SVR(**{name: getattr(self, name) for name in self._kw})   # set_params may have changed them

@@ -1,0 +1,81 @@
+"""Multi-output SVR: the result of sklearn's `MultiOutputRegressor(SVR(**kw))`, with the k duals solved together on ONE Gram panel.
+
+The panel of the 'svr' structure is K (+ 1 for the regularised intercept) and depends on neither the targets nor epsilon: target c
+differs only in the linear term q_c = [-y_c; y_c] + epsilon.  The batched path (`bq_msolver_create_svr`) streams the panel once per
+iteration for every 4 targets still running (bq_symm.hip) instead of once per target, and takes the intercepts' k masked products in
+one multi-column product (`bq_problem_gram_matmat`).  Each target follows the iteration of `SVR.fit` with the same optimizer — same
+formulas, thresholds, stop tests and records — and its iterates have the same bits whatever the other targets do.
+
+Configurations the batched path does not cover (see `uses_batched_svr_path`) fit the k targets one after another with `SVR`:
+exactly what `MultiOutputRegressor(SVR)` does.
+"""
+import numpy as np
+
+from ...device import get_context
+from ...opti import KernelQuadratic
+from ...opti.constrained import FrankWolfe, ProjectedGradient
+from ._batched import _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat, fitted_svr, solve_batched, solver_kind, svr_intercept
+from .losses import EpsilonInsensitive
+
+__all__ = ['MultiOutputSVR', 'uses_batched_svr_path']
+
+
+def uses_batched_svr_path(svr, world):
+    """True when `MultiOutputSVR` solves the targets of `svr`'s configuration together on one panel: the epsilon-insensitive dual
+    with a regularised intercept by ProjectedGradient or FrankWolfe, a resident panel ('f64' / 'f32') and a single-rank context
+    (`world` ranks).  Every other configuration fits one `SVR` per target."""
+    opt = svr.optimizer
+    return bool(svr.dual and svr.reg_intercept and svr.loss == EpsilonInsensitive and isinstance(opt, type) and
+                issubclass(opt, (ProjectedGradient, FrankWolfe)) and svr.storage in ('f64', 'f32') and int(world) == 1)
+
+
+class MultiOutputSVR(_MultiTargetSVR):
+    """Multi-output SVR; constructor arguments and their checks are SVR's.
+
+    After `fit(X, Y)`, Y of shape n x k: `estimators_` (one fitted SVR per target), `batched_` (which path ran), and `predict`
+    (m x k), `score` as sklearn's MultiOutputRegressor(SVR(**kw)).  On the batched path the estimators share one device panel;
+    each one's `obj` / `optimizer.f` is its own target's dual on it (`TargetQuadratic`).
+    """
+
+    def fit(self, X, Y):
+        X = np.ascontiguousarray(X, dtype=float)
+        Y = np.asarray(Y, dtype=float)
+        if Y.ndim == 1:
+            raise ValueError('y must have at least two dimensions for multi-output regression but has only one.')
+        proto = self._prototype()
+        self.batched_ = uses_batched_svr_path(proto, get_context().world)
+        if not self.batched_:
+            self.estimators_ = [self._prototype().fit(X, Y[:, c]) for c in range(Y.shape[1])]
+            return self
+        self.estimators_ = self._fit_batched(proto, X, np.ascontiguousarray(Y.T))
+        return self
+
+    def _fit_batched(self, proto, X, Y):
+        k, n = Y.shape
+        ub = np.ones(2 * n) * proto.C
+        QL = np.hstack((-Y, Y)) + proto.epsilon   # row c: SVR.fit's q of target c
+        # one panel for every target: the 'svr' structure's own linear term is never used by the batched solver
+        obj = KernelQuadratic(X, QL[0], 'svr', proto.kernel, storage=proto.storage, tune_placement=proto._streams_panel(),
+                              expected_products=proto.max_iter * ((k + 3) // 4))
+        dev = obj.device_problem()
+        kind = solver_kind(proto.optimizer)
+        res = solve_batched(dev, kind, QL, ub, solver=_DeviceSVRSolver(dev, kind, QL, ub, 1e-6, proto.max_iter))
+        ests, masks, coefs = [], [], []
+        for c in range(k):
+            est = self._prototype()
+            sv = fitted_svr(est, obj, res[c], X, Y[c])
+            w = np.zeros(n)
+            w[sv] = est.dual_coef_
+            ests.append(est)
+            masks.append(sv)
+            coefs.append(w)
+            if self.verbose:
+                print('target %d: %s after %d iterations, f = %1.6e' % (c, est.optimizer.status, est.optimizer.iter,
+                                                                         est.optimizer.f_x))
+        U = _gram_matmat(dev, np.stack(coefs))
+        for c, est in enumerate(ests):
+            est.intercept_ = svr_intercept(Y[c], U[c], masks[c], proto.epsilon)
+        return ests
+
+    def predict(self, X):
+        return np.stack([e.predict(X) for e in self.estimators_], axis=1)
