@@ -455,6 +455,13 @@ int bq_decision_function(bq_ctx *ctx, int kernel, double gamma, double coef0, in
                          int64_t d, const double *SV, const double *coef, double intercept, int64_t t,
                          const double *Xt, double *out);
 
+/* OUT (k x t, row-major) = W (k x m) . kernel(SV, Xt) + b; b == NULL: no intercepts.  One pass over the kernel values
+   for all k columns; nothing of size t x m is held.  Row c's bits depend on W[c] and b[c] alone, not on k, on the other
+   columns or on c's place among them.  BQ_ERR_BADARG for BQ_KERNEL_LAPLACIAN (no GEMM form). */
+int bq_decision_function_multi(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
+                               const double *SV, int k, const double *W, const double *b, int64_t t, const double *Xt,
+                               double *out);
+
 /* dense Gram matrix out (m x t, row-major) = kernel(A (m x d), B (t x d)); B == NULL means B is A (t ignored)
  * — the kernel functors' __call__, optiml/ml/svm/kernels.py:49-51 / 91-95 / 125-129 */
 int bq_gram_matrix(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,

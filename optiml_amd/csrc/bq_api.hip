@@ -1664,6 +1664,18 @@ extern "C" int bq_decision_function(bq_ctx *c, int kernel, double gamma, double 
     return bq_launch_decision(c, kernel, gamma, coef0, degree, m, d, SV, coef, intercept, t, Xt, out);
 }
 
+extern "C" int bq_decision_function_multi(bq_ctx *c, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
+                                          const double *SV, int k, const double *W, const double *b, int64_t t,
+                                          const double *Xt, double *out) {
+    BQ_ARG(c && SV && W && Xt && out, "NULL argument");
+    BQ_ARG(m >= 1 && d >= 1 && t >= 1 && k >= 1, "m/d/t/k");
+    BQ_ARG(kernel != BQ_KERNEL_LAPLACIAN, "the Laplacian kernel has no GEMM form: use bq_decision_function per column");
+    BQ_ARG(kernel == BQ_KERNEL_LINEAR || kernel == BQ_KERNEL_POLY || kernel == BQ_KERNEL_RBF || kernel == BQ_KERNEL_SIGMOID,
+           "unknown kernel");
+    BQ_HIP(hipSetDevice(c->device));
+    return bq_launch_decision_multi(c, kernel, gamma, coef0, degree, m, d, SV, k, W, b, t, Xt, out);
+}
+
 extern "C" int bq_gram_matrix(bq_ctx *c, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                               const double *A, int64_t t, const double *B, double *out) {
     BQ_ARG(c && A && out, "NULL argument");

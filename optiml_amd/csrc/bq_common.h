@@ -45,7 +45,7 @@ void bq_set_error(const char *fmt, ...);
 // can hold it against the long way — nothing a user of the library needs (round 6: these were eighteen BQ_* variables).
 //   rows_per_step=4|8  stream_unit=U  minres_big_min=N  as_schur=0  as_schur_min=N  as_schur_limit=N  as_mailbox=0  as_f_chain=0
 //   as_cg_warm=0  as_cg_incq=0  as_cg_colq=0  as_cg_pc_incr=0  as_cg_pc_class=0..3  ip_svr_reduced=0  smo_helpers=N
-//   panel_good_gbs=G  alloc_fail_above=BYTES  decision_chunk_rows=R  sweep_block=1024|2048|4096  compact_panel=0
+//   panel_good_gbs=G  alloc_fail_above=BYTES  decision_chunk_rows=R  decision_multi_unit=TILES  decision_multi_chunk_rows=R  sweep_block=1024|2048|4096  compact_panel=0
 // ---------------------------------------------------------------------------------------------
 bool bq_hook(const char *name, double *value);                       // true (and *value) when the hook is set
 static inline double bq_hook_value(const char *name, double dflt) {
@@ -389,6 +389,10 @@ int bq_max_sq_norm(bq_ctx *ctx, const double *X, int64_t n, int64_t d, double *o
 int bq_launch_decision(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                        const double *SV, const double *coef, double intercept, int64_t t, const double *Xt,
                        double *out);
+// the decision values of k coefficient columns in one pass over the kernel values (bq_decide.hip)
+int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
+                             const double *SV, int k, const double *W, const double *b, int64_t t, const double *Xt,
+                             double *out);
 
 // streamed mode (bq_gram.hip): persistent k-major image of X + the fused Gram-tile x vector product
 // rows [r0, r1): this rank's 256-row tile rows (whole canonical segments; r1 may exceed n)

@@ -15,43 +15,15 @@
 #include "bq_common.h"
 
 #include "bq_mfma_tile.h"
+#include "bq_gram_image.h"
 
 #include <type_traits>
 #include <vector>
 
 constexpr int GT = BQ_GT;
-constexpr int GK = BQ_GK;
 #ifndef BQ_STREAM_FOLD
 #define BQ_STREAM_FOLD 0
 #endif
-
-__global__ void transpose_pad_kernel(const double *__restrict__ X, int64_t n, int64_t d, double *__restrict__ Xt,
-                                     int64_t np, int64_t dp) {
-    __shared__ double tile[32][33];
-    const int64_t r0 = (int64_t)blockIdx.x * 32, k0 = (int64_t)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    for (int j = ty; j < 32; j += 8) {
-        int64_t r = r0 + j, k = k0 + tx;
-        tile[j][tx] = (r < n && k < d) ? X[r * d + k] : 0.0;
-    }
-    __syncthreads();
-    for (int j = ty; j < 32; j += 8) {
-        int64_t k = k0 + j, r = r0 + tx;
-        if (k < dp && r < np) Xt[k * np + r] = tile[tx][j];
-    }
-}
-
-__global__ void row_norms_kernel(const double *__restrict__ X, int64_t n, int64_t d, double *__restrict__ out,
-                                 int64_t np) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= np) return;
-    double s = 0.0;
-    if (i < n) {
-        const double *row = X + i * d;
-        for (int64_t k = 0; k < d; ++k) s = fma(row[k], row[k], s);
-    }
-    out[i] = s;
-}
 
 // the output "pointer" of the Gram kernel: T * for fp64 / fp32 panels, the three planes (+ the flag word) of the compact layout
 template <typename T> struct gram_out {
@@ -103,18 +75,6 @@ __device__ __forceinline__ void store_elem(const bq_c7w &p, double v) {
     __builtin_nontemporal_store((uint16_t)(u >> 32), p.mid);
     __builtin_nontemporal_store((uint8_t)(u >> 48), p.top);
 }
-
-// (gamma <x, y> + coef0)^degree: degrees 2 and 3 (the reference's default) by multiplication — pow() is ~150 vector
-// instructions per element, x * x * x two; <= 1 ulp from the reference's pow(x, 3.0).  DEG = 0: any degree, pow().
-template <int DEG>
-__device__ __forceinline__ double bq_poly_map(double x, int degree) {
-    if (DEG == 2) return x * x;
-    if (DEG == 3) return x * x * x;
-    return pow(x, (double)degree);
-}
-#define BQ_EXP_ATTR __device__ __forceinline__
-#define BQ_EXP_LOINT(t) __double2loint(t)
-#include "bq_exp.h"
 
 struct gram_params {
     const double *At, *Bt;   // k-major padded images: At[dp][mp], Bt[dp][np]
@@ -298,29 +258,6 @@ __global__ __launch_bounds__(256) void gram_l1_kernel(gram_params P, T *__restri
                 store_elem<T>(out + (P.lower_only ? bq_sym_addr(gi, gj, P.arow0 / BQ_SYM_TILE) : (gi - P.arow0) * P.ld + gj),
                               bq_exp(-P.gamma * acc[u][v]));
         }
-}
-
-struct gram_images {
-    double *At = nullptr, *a2 = nullptr;
-    int64_t mp = 0, dp = 0;
-};
-
-static int make_image(bq_ctx *ctx, const double *Xdev, int64_t n, int64_t d, gram_images *img) {
-    img->mp = bq_round_up(n, GT);
-    img->dp = bq_round_up(d, GK);
-    BQ_HIP(hipMalloc(&img->At, sizeof(double) * img->mp * img->dp));
-    BQ_HIP(hipMalloc(&img->a2, sizeof(double) * img->mp));
-    dim3 grid((unsigned)((img->mp + 31) / 32), (unsigned)((img->dp + 31) / 32));
-    transpose_pad_kernel<<<grid, 256, 0, ctx->stream>>>(Xdev, n, d, img->At, img->mp, img->dp);
-    row_norms_kernel<<<(unsigned)((img->mp + 255) / 256), 256, 0, ctx->stream>>>(Xdev, n, d, img->a2, img->mp);
-    BQ_HIP(hipGetLastError());
-    return BQ_OK;
-}
-
-static void free_image(gram_images *img) {
-    if (img->At) hipFree(img->At);
-    if (img->a2) hipFree(img->a2);
-    img->At = img->a2 = nullptr;
 }
 
 static int run_gram(bq_ctx *ctx, const gram_images &A, const gram_images &B, int64_t m_rows0, int64_t m_rows1,

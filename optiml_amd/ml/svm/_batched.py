@@ -11,7 +11,7 @@ from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import ProjectedGradient
 from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator
-from .kernels import LinearKernel, gaussian
+from .kernels import GaussianKernel, LinearKernel, PolyKernel, SigmoidKernel, gaussian
 from .losses import squared_hinge, squared_epsilon_insensitive
 
 MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
@@ -145,6 +145,57 @@ def gram_matmat_pairs(problem, cls_tiles, pairs, W):
     _lib.check(_lib.load().bq_problem_gram_matmat_pairs(problem.handle, len(ct) - 1, _lib.iptr(ct), W.shape[0], _lib.iptr(pr),
                                                         _lib.ptr(W), _lib.ptr(out)))
     return out
+
+
+def uses_batched_decision(kernel, k, world, batched):
+    """True when the k estimators of a batched fit predict through one fused pass (`batched_decision`) instead of one
+    `decision_function` call each: the fit ran on the batched path (`batched`), k >= 2, a single-rank context (`world` ranks) and a
+    Gaussian, polynomial or sigmoid kernel whose gamma is not 'scale'.  'scale' resolves against each estimator's own support
+    vectors at prediction (`SVM.decision_function`), so the estimators have different kernels and share no kernel value; the
+    linear kernel predicts from `coef_` on the host; the Laplacian kernel has no GEMM form.  The fallback fits promise the bits of
+    the per-estimator calls and keep them."""
+    return bool(batched and int(k) >= 2 and int(world) == 1 and isinstance(kernel, (GaussianKernel, PolyKernel, SigmoidKernel)) and
+                getattr(kernel, 'gamma', None) != 'scale')
+
+
+def batched_decision(spec, SV, W, b, X):
+    """t x k decision values of k coefficient rows on shared support vectors in one pass over the kernel values
+    (`bq_decision_function_multi`): kernel(X, SV) W' + b.  spec: the kernel's `device_spec` (gamma resolved); SV: m x d; W: k x m;
+    b: k intercepts; X: t x d."""
+    kind, gamma, coef0, degree = spec
+    SV = np.ascontiguousarray(SV, dtype=float)
+    X = np.ascontiguousarray(X, dtype=float)
+    W = np.ascontiguousarray(W, dtype=float)
+    k, m = W.shape
+    if SV.shape[0] != m or X.shape[1] != SV.shape[1]:
+        raise ValueError('shapes of SV (%d x %d), W (%d x %d) and X (%d x %d) do not match' % (SV.shape + W.shape + X.shape))
+    b = _lib.as_f64(b, k, 'b')
+    out = np.empty((k, X.shape[0]))
+    _lib.check(_lib.load().bq_decision_function_multi(get_context().handle, kind, gamma, coef0, degree, m, SV.shape[1],
+                                                      _lib.ptr(SV), k, _lib.ptr(W), _lib.ptr(b), X.shape[0], _lib.ptr(X),
+                                                      _lib.ptr(out)))
+    return np.ascontiguousarray(out.T)
+
+
+class DecisionBatch:
+    """What a batched fit keeps for `batched_decision`: the kernel spec, the union of the estimators' support vectors (the rows
+    with a nonzero coefficient in any column), the k x m coefficients on that union and the k intercepts — the estimators as `fit`
+    left them; later changes to `estimators_` are not seen.  coefs: k x n on the rows of X; `keep` masks rows that may enter
+    (OneVsOneSVC's ghost rows may not)."""
+
+    def __init__(self, kernel, X, coefs, intercepts, keep=None):
+        coefs = np.asarray(coefs, dtype=float)
+        rows = (coefs != 0).any(axis=0)
+        if keep is not None:
+            rows &= keep
+        self.spec = kernel.device_spec(X)   # gamma is numeric or 'auto' here: it does not depend on the rows
+        self.rows = np.flatnonzero(rows)
+        self.SV = np.ascontiguousarray(X[self.rows])
+        self.W = np.ascontiguousarray(coefs[:, self.rows])
+        self.b = np.array(intercepts, dtype=float)
+
+    def __call__(self, X):
+        return batched_decision(self.spec, self.SV, self.W, self.b, X)
 
 
 def fitted_svc(est, quad, r, X, y, pos=None):

@@ -15,7 +15,8 @@ import numpy as np
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
-from ._batched import _DeviceMultiSolver, _MultiClassSVC, _gram_matmat, fitted_svc, intercept, solve_batched, solver_kind
+from ._batched import (DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _gram_matmat, fitted_svc, intercept, solve_batched,
+                       solver_kind, uses_batched_decision)
 from .losses import Hinge
 
 __all__ = ['OneVsRestSVC', 'uses_batched_path', 'binarize']
@@ -47,6 +48,10 @@ class OneVsRestSVC(_MultiClassSVC):
 
     After `fit`: `classes_`, `estimators_` (one fitted SVC per class — per binary problem with two classes), and
     `decision_function` (m x k; 1-D with two classes), `predict`, `score` as sklearn's OneVsRestClassifier(SVC(**kw)).
+
+    `batched_decision_`: True when `decision_function` and `predict` take every class's values from one fused pass over the kernel
+    values of the union of the support vectors (`uses_batched_decision`) instead of one call per estimator.  The stored batch
+    (`decision_batch_`) describes the estimators as `fit` left them.
     """
 
     def fit(self, X, y):
@@ -54,6 +59,8 @@ class OneVsRestSVC(_MultiClassSVC):
         self.classes_, Y = binarize(y)
         proto = self._prototype()
         self.batched_ = uses_batched_path(proto, get_context().world)
+        self.batched_decision_ = uses_batched_decision(proto.kernel, len(Y), get_context().world, self.batched_)
+        self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, (Yc > 0).astype(int)) for Yc in Y]
             return self
@@ -87,9 +94,13 @@ class OneVsRestSVC(_MultiClassSVC):
         U = _gram_matmat(dev, np.stack(coefs))
         for c, est in enumerate(ests):
             est.intercept_ = intercept(Y[c], U[c], masks[c])
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
         return ests
 
     def decision_function(self, X):
+        if self.batched_decision_:
+            return self.decision_batch_(X)   # k >= 2 columns: more than two classes
         scores = np.stack([e.decision_function(X) for e in self.estimators_], axis=1)
         return scores[:, 0] if len(self.classes_) == 2 else scores
 

@@ -14,7 +14,8 @@ import numpy as np
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
-from ._batched import _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat, fitted_svr, solve_batched, solver_kind, svr_intercept
+from ._batched import (DecisionBatch, _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat, fitted_svr, solve_batched, solver_kind,
+                       svr_intercept, uses_batched_decision)
 from .losses import EpsilonInsensitive
 
 __all__ = ['MultiOutputSVR', 'uses_batched_svr_path']
@@ -35,6 +36,10 @@ class MultiOutputSVR(_MultiTargetSVR):
     After `fit(X, Y)`, Y of shape n x k: `estimators_` (one fitted SVR per target), `batched_` (which path ran), and `predict`
     (m x k), `score` as sklearn's MultiOutputRegressor(SVR(**kw)).  On the batched path the estimators share one device panel;
     each one's `obj` / `optimizer.f` is its own target's dual on it (`TargetQuadratic`).
+
+    `batched_decision_`: True when `predict` takes every target's values from one fused pass over the kernel values of the union
+    of the support vectors (`uses_batched_decision`) instead of one call per estimator.  The stored batch (`decision_batch_`)
+    describes the estimators as `fit` left them.
     """
 
     def fit(self, X, Y):
@@ -44,6 +49,8 @@ class MultiOutputSVR(_MultiTargetSVR):
             raise ValueError('y must have at least two dimensions for multi-output regression but has only one.')
         proto = self._prototype()
         self.batched_ = uses_batched_svr_path(proto, get_context().world)
+        self.batched_decision_ = uses_batched_decision(proto.kernel, Y.shape[1], get_context().world, self.batched_)
+        self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, Y[:, c]) for c in range(Y.shape[1])]
             return self
@@ -75,7 +82,11 @@ class MultiOutputSVR(_MultiTargetSVR):
         U = _gram_matmat(dev, np.stack(coefs))
         for c, est in enumerate(ests):
             est.intercept_ = svr_intercept(Y[c], U[c], masks[c], proto.epsilon)
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
         return ests
 
     def predict(self, X):
+        if self.batched_decision_:
+            return self.decision_batch_(X)
         return np.stack([e.predict(X) for e in self.estimators_], axis=1)

@@ -22,8 +22,9 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ._batched import (MEMORY_SHARE, _DeviceMultiSolver, _MultiClassSVC, _pair_array, column_bytes, device_free_bytes, fitted_svc,
-                       gram_matmat_pairs, intercept, solve_batched, solver_kind)
+from ._batched import (MEMORY_SHARE, DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _pair_array, column_bytes,
+                       device_free_bytes, fitted_svc, gram_matmat_pairs, intercept, solve_batched, solver_kind,
+                       uses_batched_decision)
 from .kernels import LinearKernel
 from .multiclass import uses_batched_path
 
@@ -132,6 +133,11 @@ class OneVsOneSVC(_MultiClassSVC):
     order, fitted on the rows of classes i and j with j as the positive class), `batched_` (which path ran), and
     `decision_function` (votes plus normalised confidences, m x k; 1-D with two classes), `predict`, `score` as sklearn's
     OneVsOneClassifier(SVC(**kw)).  gamma='scale' resolves on each pair's rows and runs one SVC per pair (see the module).
+
+    `batched_decision_`: True when `decision_function` and `predict` take every pair's confidences from one fused pass over the
+    kernel values of the union of the support vectors (`uses_batched_decision`; a training row is in up to k - 1 pairs and in the
+    union once) instead of one call per estimator.  The stored batch (`decision_batch_`) describes the estimators as `fit` left
+    them.
     """
 
     @property
@@ -147,6 +153,9 @@ class OneVsOneSVC(_MultiClassSVC):
         codes = np.searchsorted(self.classes_, y)
         proto = self._prototype()
         self.batched_ = uses_batched_ovo(proto, get_context().world)
+        ncls = len(self.classes_)
+        self.batched_decision_ = uses_batched_decision(proto.kernel, ncls * (ncls - 1) // 2, get_context().world, self.batched_)
+        self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = []
             for i, j in ovo_pairs(len(self.classes_)):
@@ -169,7 +178,7 @@ class OneVsOneSVC(_MultiClassSVC):
                               tune_placement=proto._streams_panel(), expected_products=proto.max_iter)
         dev = obj.device_problem()
         kind = solver_kind(proto.optimizer)
-        ests = []
+        ests, coefs = [], []
         for chunk in pair_chunks(pairs, cls_tiles, n_pad, device_free_bytes()):
             Y = np.stack([np.where(pcode == j, 1., -1.) for _, j in chunk])
             UB = np.stack([np.where(((pcode == i) | (pcode == j)) & ~ghost, float(proto.C), 0.) for i, j in chunk])
@@ -188,12 +197,20 @@ class OneVsOneSVC(_MultiClassSVC):
             for p, (est, yp, pos, sv) in enumerate(fits):
                 est.intercept_ = intercept(yp, U[p][pos], sv)
                 ests.append(est)
+            if self.batched_decision_:
+                coefs.append(W)
         del dev, obj
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, Xp, np.vstack(coefs), [est.intercept_ for est in ests],
+                                                 keep=~ghost)
         return ests
 
     def decision_function(self, X):
         X = np.ascontiguousarray(X, dtype=float)
-        conf = np.stack([np.ravel(e.decision_function(X)) for e in self.estimators_], axis=1)
+        if self.batched_decision_:
+            conf = self.decision_batch_(X)
+        else:
+            conf = np.stack([np.ravel(e.decision_function(X)) for e in self.estimators_], axis=1)
         Y = ovo_decision((conf > 0).astype(int), conf, len(self.classes_))
         return Y[:, 1] if len(self.classes_) == 2 else Y
 
