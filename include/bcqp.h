@@ -52,6 +52,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_pairs, bq_problem_gram_matmat_pairs, bq_pairs_slab_bytes and bq_pairs_work_list were added) */
 /* (still 3: the structure flag BQ_PLAIN_PANEL was added) */
 /* (still 3: bq_msolver_create_svr was added) */
+/* (still 3: bq_msolver_create_svr_boxes and bq_msolver_svr_heldout were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -366,6 +367,23 @@ int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const int *cls_ti
  * get / destroy: as bq_msolver_create, on vectors of 2n (cls = the target). */
 int bq_msolver_create_svr(bq_problem *p, int kind, int k, const double *QL, const double *ub, const double *x0, double eps,
                           int64_t max_iter, double fw_t, bq_msolver **out);
+/* The SVR batch with ONE BOX PER COLUMN, for cross-validated searches over C and epsilon: sklearn GridSearchCV's per-fold SVR.fit
+ * on ONE Gram panel of all n rows.  QL: k x 2n, column c = (fold, C, epsilon) has [-y; y] + epsilon; UB: k x 2n, >= 0: C on both
+ * halves of the fold's training rows and 0 on both halves of its held-out rows, which is the training fold's dual exactly (those
+ * entries start at 0 and never move).  Row i is held out for column c exactly when UB[c][i] == 0 and UB[c][n + i] == 0; a row with
+ * exactly one half zero is BQ_ERR_BADARG.  Every pass takes the 16-column product, so column c's iterates have the same bits alone,
+ * at any position and in any batch.  p, x0, eps, max_iter, fw_t, run / state / get / destroy: as bq_msolver_create_svr. */
+int bq_msolver_create_svr_boxes(bq_problem *p, int kind, int k, const double *QL, const double *UB, const double *x0,
+                                double eps, int64_t max_iter, double fw_t, bq_msolver **out);
+/* Held-out scores of every column of a bq_msolver_create_svr_boxes solver (any other solver: BQ_ERR_BADARG), from its state on the
+ * device, after any run: no k x n array crosses the bus.  y: n targets; epsilon: k.  Per column, with coef = x+ - x- on the support
+ * rows (x+ or x- above 1e-6, SVR.fit's threshold) and u = K coef (one 16-column product per 16 columns):
+ *   n_sv       the support rows;        intercept  (sum over them of (y - u) - epsilon) / n_sv, SVR.fit's order of operations
+ *   n_held     the held-out rows;       sse        sum over them of (y - (u + intercept))^2
+ * Every sum has a fixed order and reads its own column only, so a column's results have the same bits in any batch.  n_sv = 0 gives
+ * intercept = sse = NaN (SVR.fit divides by zero there). */
+int bq_msolver_svr_heldout(bq_msolver *s, const double *y, const double *epsilon, double *intercept, int64_t *n_sv, double *sse,
+                           int64_t *n_held);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

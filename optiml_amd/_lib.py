@@ -123,6 +123,8 @@ PROTOTYPES = {
     'bq_msolver_destroy': (C.c_int, [_vp]),
     'bq_msolver_create_boxes': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_msolver_create_svr': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
+    'bq_msolver_create_svr_boxes': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
+    'bq_msolver_svr_heldout': (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(_i64), _dp, C.POINTER(_i64)]),
     'bq_msolver_create_pairs': (C.c_int, [_vp, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.c_double,
                                           C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),

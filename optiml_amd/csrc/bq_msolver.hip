@@ -33,7 +33,8 @@
 struct bq_msolver {
     bq_problem *p = nullptr;
     int kind = BQ_PG, k = 0;
-    bool wide = false;   // bq_msolver_create_boxes: the 16-column product (bq_symmw.hip) for every pass
+    bool wide = false;   // bq_msolver_create_boxes / _svr_boxes: the 16-column product (bq_symmw.hip) for every pass
+    bool svr_boxes = false;   // bq_msolver_create_svr_boxes: bq_msolver_svr_heldout may score it
     bq_pairs_plan *plan = nullptr;   // bq_msolver_create_pairs: the pair-routed product (bq_symmp.hip) for every pass
     int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ld >= nb * 256)
     std::vector<bq_solver *> cls;
@@ -144,6 +145,76 @@ __global__ __launch_bounds__(256) void mfinish_kernel(const bq_epilogue *__restr
     const bq_epi_pre pre = bq_epi_preload(e, i, true);
     const double sv = i < e.n ? out[pos[blockIdx.y] * ldw + i] : 0.0;
     bq_epi_finish(e, blockIdx.x, gridDim.x, bq_epi_element(e, pre, i, sv), gridDim.x);
+}
+
+// bq_msolver_svr_heldout, column blockIdx.y: the coefficients of fitted_svr (svm/_batched.py), its threshold and its expression, to the
+// column's own slot (not pos[]: every column is scored, live or not)
+__global__ __launch_bounds__(256) void msvr_coef_kernel(const bq_epilogue *__restrict__ epi, double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const double xp = e.x[i], xn = e.x[e.n + i];
+    W[blockIdx.y * ldw + i] = (xp > 1e-6 || xn > 1e-6) ? xp - xn : 0.0;
+}
+
+// the fixed tree over the workgroup's 1024 partial sums and counts; every thread returns with the totals in s[0], c[0]
+__device__ inline void msvr_tree(double *s, int *c, int tid) {
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if (tid < st) {
+            s[tid] += s[tid + st];
+            c[tid] += c[tid + st];
+        }
+        __syncthreads();
+    }
+}
+
+// bq_msolver_svr_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1, the support rows (x+ or x- above 1e-6):
+// S = sum (y - u), n_sv, b = (S - epsilon) / n_sv in svr_intercept's order.  Pass 2, the held-out rows (ub = 0 on both halves):
+// sse = sum (y - (u + b))^2, n_held.  Thread t sums the rows t, t + 1024, ... in ascending order, then the tree: no atomics, and
+// nothing of another column enters.  n_sv = 0: intercept = sse = NaN.
+__global__ __launch_bounds__(1024) void msvr_score_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out, int64_t ldw,
+                                                          const double *__restrict__ y, const double *__restrict__ epsilon,
+                                                          double *__restrict__ intercept, long long *__restrict__ n_sv,
+                                                          double *__restrict__ sse, long long *__restrict__ n_held) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_epilogue &e = epi[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = e.n;
+    double s = 0.0;
+    int cnt = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool sv = e.x[i] > 1e-6 || e.x[n + i] > 1e-6;
+        s += sv ? y[i] - u[i] : 0.0;
+        cnt += sv ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = cnt;
+    msvr_tree(sd, sc, tid);
+    const int nsv = sc[0];
+    double b = sd[0];
+    b -= epsilon[blockIdx.x];
+    b = nsv > 0 ? b / (double)nsv : NAN;
+    __syncthreads();   // sd[0], sc[0] are read: pass 2 may overwrite them
+    s = 0.0;
+    cnt = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool held = e.ub[i] == 0.0 && e.ub[n + i] == 0.0;
+        const double r = y[i] - (u[i] + b);
+        s += held ? r * r : 0.0;
+        cnt += held ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = cnt;
+    msvr_tree(sd, sc, tid);
+    if (tid == 0) {
+        intercept[blockIdx.x] = b;
+        n_sv[blockIdx.x] = nsv;
+        sse[blockIdx.x] = sd[0];   // NaN with b
+        n_held[blockIdx.x] = sc[0];
+    }
 }
 
 __global__ void mlive_kernel(bq_scal *const *__restrict__ scs, int k, int *__restrict__ pos, int *__restrict__ nlive) {
@@ -360,6 +431,74 @@ extern "C" int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const 
 extern "C" int bq_msolver_create_svr(bq_problem *p, int kind, int k, const double *QL, const double *ub, const double *x0,
                                      double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
     return msolver_create(p, kind, k, nullptr, ub, 0, false, x0, eps, max_iter, fw_t, out, nullptr, QL);
+}
+
+extern "C" int bq_msolver_create_svr_boxes(bq_problem *p, int kind, int k, const double *QL, const double *UB, const double *x0,
+                                           double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
+    BQ_ARG(p && UB && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->structure == BQ_SVR, "the batched SVR solver takes a kernel-built SVR problem");
+    for (int c = 0; c < k; ++c) {
+        const double *ub = UB + (int64_t)c * p->N;
+        for (int64_t i = 0; i < p->N; ++i) BQ_ARG(ub[i] >= 0.0, "upper bounds must be >= 0 (lb = 0)");
+        for (int64_t i = 0; i < p->n; ++i)
+            BQ_ARG((ub[i] == 0.0) == (ub[p->n + i] == 0.0), "a held-out row has ub = 0 on both halves: one half alone is zero");
+    }
+    BQ_TRY(msolver_create(p, kind, k, nullptr, UB, p->N, true, x0, eps, max_iter, fw_t, out, nullptr, QL));
+    (*out)->svr_boxes = true;
+    return BQ_OK;
+}
+
+extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const double *epsilon, double *intercept, int64_t *n_sv,
+                                      double *sse, int64_t *n_held) {
+    BQ_ARG(m && y && epsilon && intercept && n_sv && sse && n_held, "NULL argument");
+    BQ_ARG(m->svr_boxes, "held-out scoring takes a solver of bq_msolver_create_svr_boxes");
+    bq_problem *p = m->p;
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int k = m->k;
+    const int64_t n = p->n;
+    double *dy = nullptr, *deps = nullptr, *db = nullptr, *dsse = nullptr;
+    long long *dnsv = nullptr, *dnheld = nullptr;
+    int *count = nullptr;   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    hipError_t e = hipMalloc(&dy, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc(&deps, sizeof(double) * k);
+    if (e == hipSuccess) e = hipMalloc(&db, sizeof(double) * k);
+    if (e == hipSuccess) e = hipMalloc(&dsse, sizeof(double) * k);
+    if (e == hipSuccess) e = hipMalloc(&dnsv, sizeof(long long) * k);
+    if (e == hipSuccess) e = hipMalloc(&dnheld, sizeof(long long) * k);
+    if (e == hipSuccess) e = hipMalloc(&count, sizeof(int));
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(deps, epsilon, sizeof(double) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("held-out scoring setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) {
+        msvr_coef_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, m->W, m->ldw);
+        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+    }
+    if (rc == BQ_OK) {
+        msvr_score_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dy, deps, db, dnsv, dsse, dnheld);
+        static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(sse, dsse, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("held-out scoring: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    if (rc == BQ_OK) rc = bq_ctx_sync(c);   // y, epsilon, k and the results are the caller's and this frame's
+    else (void)bq_ctx_sync(c);
+    for (void *ptr : {(void *)dy, (void *)deps, (void *)db, (void *)dsse, (void *)dnsv, (void *)dnheld, (void *)count})
+        if (ptr) hipFree(ptr);
+    return rc;
 }
 
 static int msolver_first(bq_msolver *m) {

@@ -1,7 +1,7 @@
-__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR']
+__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
 from .onevsone import OneVsOneSVC
-from .model_selection import SVCGridSearchCV
+from .model_selection import SVCGridSearchCV, SVRGridSearchCV
 from .multioutput import MultiOutputSVR

@@ -1,6 +1,6 @@
-"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`): the device solver of many
-columns on one Gram panel, the one-off multi-column products, the device memory budget of a solve, and the way a column's result
-becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
+"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`, `SVRGridSearchCV`): the
+device solver of many columns on one Gram panel, the one-off multi-column products, the device memory budget of a solve, and the
+way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
 """
 import ctypes as C
 
@@ -93,21 +93,39 @@ class _DeviceMultiSolver:
 
 class _DeviceSVRSolver(_DeviceMultiSolver):
     """`bq_msolver_create_svr`: one column per target on a 'svr' problem.  QL: k x 2n linear terms ([-y_c; y_c] + epsilon), ub: 2n,
-    x0: k x 2n or None; every vector the solver hands out has 2n entries."""
+    or k x 2n for one box per column (`bq_msolver_create_svr_boxes` and the 16-column product: the columns of a search, which
+    `heldout` scores), x0: k x 2n or None; every vector the solver hands out has 2n entries."""
 
     def _create(self, handle, kind, QL, ub, x0, eps, max_iter, t):
-        ub = _lib.as_f64(ub, self.n, 'ub')
+        boxes = np.ndim(ub) == 2
+        ub = _lib.as_f64(ub, self.k * self.n if boxes else self.n, 'ub')
         x0 = self._x0(x0)
-        return self._lib.bq_msolver_create_svr(handle, kind, self.k, _lib.ptr(QL), _lib.ptr(ub), _lib.ptr(x0), eps, max_iter, t,
-                                               C.byref(self._h))
+        create = self._lib.bq_msolver_create_svr_boxes if boxes else self._lib.bq_msolver_create_svr
+        return create(handle, kind, self.k, _lib.ptr(QL), _lib.ptr(ub), _lib.ptr(x0), eps, max_iter, t, C.byref(self._h))
+
+    def heldout(self, y, epsilons):
+        """(intercept, n_sv, sse, n_held), k entries each, of the columns as they stand (`bq_msolver_svr_heldout`): SVR.fit's
+        intercept and support count, and the squared error and count of the rows whose box is 0 on both halves.  y: n targets,
+        epsilons: k.  A column without support vectors has intercept = sse = NaN."""
+        y = _lib.as_f64(y, self.n // 2, 'y')
+        eps = _lib.as_f64(epsilons, self.k, 'epsilons')
+        b, sse = np.empty(self.k), np.empty(self.k)
+        n_sv, n_held = np.empty(self.k, dtype=np.int64), np.empty(self.k, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        _lib.check(self._lib.bq_msolver_svr_heldout(self._h, _lib.ptr(y), _lib.ptr(eps), _lib.ptr(b), n_sv.ctypes.data_as(i64),
+                                                    _lib.ptr(sse), n_held.ctypes.data_as(i64)))
+        return b, n_sv, sse, n_held
 
 
-def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None):
+def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None, before_close=None,
+                  vectors=True):
     """Run the batched solver (`problem`: a device problem of KernelQuadratic 'svc'; Y: k x n labels +-1; ub: n, or k x n for one box
     per column (bq_msolver_create_boxes); x0: k x n or None)
     to the end: per class a dict (rows: the iteration records, status, iter, f_x, x, g) as a single-class optimizer ends them.
     solver: an already created solver of these columns instead of bq_msolver_create(_boxes); only Y's row count is read then, and
-    x, g have the solver's column length (2n for a `_DeviceSVRSolver`)."""
+    x, g have the solver's column length (2n for a `_DeviceSVRSolver`).
+    before_close: called as before_close(solver, out) on the live solver after the last run, before it is closed (a search scores
+    its columns there, `_DeviceSVRSolver.heldout`); vectors=False leaves x and g on the device (no such keys)."""
     solver = _DeviceMultiSolver(problem, kind, Y, ub, eps, max_iter, t, x0) if solver is None else solver
     k = Y.shape[0]
     try:
@@ -120,8 +138,11 @@ def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None,
         out = []
         for c in range(k):
             it, st, f = solver.state(c)
-            out.append(dict(rows=np.concatenate(rows[c]), status=st, iter=it, f_x=f, x=solver.get(c, _lib.GET_X_NOW),
-                            g=solver.get(c, _lib.GET_G_NOW)))
+            out.append(dict(rows=np.concatenate(rows[c]), status=st, iter=it, f_x=f))
+            if vectors:
+                out[c].update(x=solver.get(c, _lib.GET_X_NOW), g=solver.get(c, _lib.GET_G_NOW))
+        if before_close is not None:
+            before_close(solver, out)
         return out
     finally:
         solver.close()

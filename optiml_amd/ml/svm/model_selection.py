@@ -13,6 +13,12 @@ and `kernel`.  Candidates are grouped by resolved kernel: a numeric gamma (or a 
 string gamma is resolved on each fold's training rows as `SVC.fit` would, which gives one panel per fold.  Panels are built one at a
 time.  Every other configuration runs exactly GridSearchCV's calls: `estimator.set_params(**p).fit(X[tr], y[tr]).score(X[te],
 y[te])` per candidate and fold.
+
+`SVRGridSearchCV` is the same search over `SVR` scored by R^2.  There C is only the box and epsilon only the linear term
+[-y; y] + epsilon; the 'svr' panel depends on neither, so every (fold, C, epsilon) of one resolved kernel is one column of
+`bq_msolver_create_svr_boxes` (ub = 0 on both halves of the held-out rows), and the columns are scored where the solver's state
+lives (`bq_msolver_svr_heldout`): per column an intercept, a support count, a held-out squared error and a held-out count come
+back, no k x n array.
 """
 import copy
 import itertools
@@ -22,15 +28,19 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ._base import SVC
-from ._batched import MEMORY_SHARE, _gram_matmat, column_bytes, device_free_bytes, intercept, solve_batched, solver_kind
+from ._base import SVC, SVR
+from ._batched import (MEMORY_SHARE, _DeviceSVRSolver, _gram_matmat, column_bytes, device_free_bytes, fitted_svr, intercept,
+                       solve_batched, solver_kind, svr_intercept)
 from .kernels import BaseEstimator, LinearKernel
 from .multiclass import OneVsRestSVC, uses_batched_path, binarize
+from .multioutput import uses_batched_svr_path
 from .onevsone import OneVsOneSVC
 
-__all__ = ['SVCGridSearchCV', 'parameter_grid', 'check_cv_splits', 'plan_columns', 'aggregate_scores', 'uses_batched_search']
+__all__ = ['SVCGridSearchCV', 'SVRGridSearchCV', 'parameter_grid', 'check_cv_splits', 'plan_columns', 'plan_svr_columns',
+           'aggregate_scores', 'uses_batched_search', 'uses_batched_svr_search', 'r2_from_sse']
 
 BATCHED_KEYS = frozenset({'C', 'kernel'})
+SVR_BATCHED_KEYS = frozenset({'C', 'epsilon', 'kernel'})
 MAX_COLUMNS = 4096   # columns per batched solve at most (see _column_cap)
 
 
@@ -49,12 +59,13 @@ def parameter_grid(param_grid):
     return out
 
 
-def check_cv_splits(cv, X, y):
-    """(train, test) index arrays: an int is StratifiedKFold(cv) without shuffling (what GridSearchCV gives a classifier), an object
-    with `split` is called as split(X, y), anything else is an iterable of (train, test) pairs."""
+def check_cv_splits(cv, X, y, stratified=True):
+    """(train, test) index arrays: an int is StratifiedKFold(cv) without shuffling (what GridSearchCV gives a classifier;
+    stratified=False: KFold(cv), what it gives a regressor), an object with `split` is called as split(X, y), anything else is an
+    iterable of (train, test) pairs."""
     if isinstance(cv, (int, np.integer)) and not isinstance(cv, bool):
-        from sklearn.model_selection import StratifiedKFold
-        cv = StratifiedKFold(n_splits=int(cv))
+        from sklearn.model_selection import KFold, StratifiedKFold
+        cv = StratifiedKFold(n_splits=int(cv)) if stratified else KFold(n_splits=int(cv))
     it = cv.split(X, y) if hasattr(cv, 'split') else cv
     splits = [(np.asarray(tr, dtype=np.intp), np.asarray(te, dtype=np.intp)) for tr, te in it]
     if not splits:
@@ -308,6 +319,188 @@ class SVCGridSearchCV(BaseEstimator):
 
     def decision_function(self, X):
         return self.best_estimator_.decision_function(X)
+
+    def predict(self, X):
+        return self.best_estimator_.predict(X)
+
+    def score(self, X, y):
+        return self.best_estimator_.score(X, y)
+
+
+def uses_batched_svr_search(estimator, candidates, world):
+    """True when `SVRGridSearchCV` solves every (candidate, fold) on shared panels: the estimator (an `SVR`) is on
+    `MultiOutputSVR`'s batched path (`uses_batched_svr_path`) and the grid varies only C, epsilon and kernel."""
+    if not isinstance(estimator, SVR):
+        return False
+    if any(not set(p) <= SVR_BATCHED_KEYS for p in candidates):
+        return False
+    return uses_batched_svr_path(estimator, world)
+
+
+def plan_svr_columns(X, y, splits, candidates, base_C, base_epsilon, base_kernel):
+    """The batched SVR search's panels and columns: a list of dicts {kernel: the resolved kernel of the panel, cols: [(candidate,
+    fold, C, epsilon)], QL: m x 2n linear terms [-y; y] + epsilon, UB: m x 2n boxes, C on both halves of the fold's training rows
+    and 0 on both halves of its held-out rows} — one group per resolved kernel, as `plan_columns` groups them."""
+    X = np.ascontiguousarray(X, dtype=float)
+    y = np.asarray(y, dtype=float)
+    n = len(y)
+    q0 = np.hstack((-y, y))
+    groups, index = [], {}
+    for ci, p in enumerate(candidates):
+        C, epsilon = p.get('C', base_C), p.get('epsilon', base_epsilon)
+        kernel = p.get('kernel', base_kernel)
+        for f, (tr, _) in enumerate(splits):
+            rk = _resolved_kernel(kernel, X[tr])
+            key = _kernel_key(rk)
+            if key not in index:
+                index[key] = len(groups)
+                groups.append(dict(kernel=rk, cols=[], QL=[], UB=[]))
+            g = groups[index[key]]
+            ub = np.zeros(2 * n)
+            ub[tr] = C
+            ub[n + tr] = C
+            g['cols'].append((ci, f, C, epsilon))
+            g['QL'].append(q0 + epsilon)
+            g['UB'].append(ub)
+    for g in groups:
+        g['QL'] = np.stack(g['QL'])
+        g['UB'] = np.stack(g['UB'])
+    return groups
+
+
+def svr_column_cap(n, free_bytes, slab_bytes):
+    """`column_cap` for the columns of an SVR search on n rows, whose vectors have 2n entries: `column_bytes(2 * n)` per column.
+    That budgets 16 vectors of 2n; a column holds 7 (x, g, d, Qd, both bounds, its linear term) and two n-vectors (product input
+    and output), so the cap errs on the small side by about a half, which leaves room for the host's records and the scoring's
+    few vectors."""
+    budget = int(free_bytes * MEMORY_SHARE) - int(slab_bytes)
+    return int(max(16, min(MAX_COLUMNS, budget // column_bytes(2 * n))))
+
+
+def r2_from_sse(sse, y_test):
+    """sklearn's `r2_score` from the squared error of the predictions on y_test: 1 - sse / sum (y - mean(y))^2; a constant y_test
+    scores 1 for a perfect prediction and 0 otherwise (r2_score's force_finite), and a NaN error scores NaN."""
+    y_test = np.asarray(y_test, dtype=float)
+    den = float(((y_test - np.average(y_test)) ** 2).sum())
+    if np.isnan(sse):
+        return float('nan')
+    if den == 0.:
+        return 1. if sse == 0. else 0.
+    return 1. - float(sse) / den
+
+
+class SVRGridSearchCV(BaseEstimator):
+    """Exhaustive search over `param_grid` for an `SVR` scored by R^2, as sklearn's GridSearchCV.  An int `cv` is KFold(cv)
+    without shuffling.
+
+    After `fit`: the attributes of `SVCGridSearchCV` — `cv_results_`, `best_index_`, `best_params_`, `best_score_`, `n_splits_`,
+    `best_estimator_` (a plain `SVR.fit` on all the data, refit=True) — with `n_iter_` / `status_` of shape (candidates, splits),
+    and `batched_`, which says which path ran.  A fit that ends without support vectors scores NaN on either path (`SVR.fit`
+    divides by zero there; GridSearchCV's error_score).  `predict` and `score` are the best estimator's.
+    """
+
+    def __init__(self, estimator, param_grid, scoring=None, cv=5, refit=True):
+        self.estimator = estimator
+        self.param_grid = param_grid
+        self.scoring = scoring
+        self.cv = cv
+        self.refit = refit
+
+    def fit(self, X, y):
+        if self.scoring is not None:
+            raise NotImplementedError('only R^2 scoring (scoring=None) is implemented')
+        if not isinstance(self.estimator, SVR):
+            raise TypeError('estimator must be an SVR')
+        X = np.ascontiguousarray(X, dtype=float)
+        y = np.asarray(y, dtype=float)
+        if y.ndim != 1:
+            raise ValueError('use MultiOutputSVR to train a model over more than one target')
+        candidates = parameter_grid(self.param_grid)
+        splits = check_cv_splits(self.cv, X, y, stratified=False)
+        base = _base_params(self.estimator)
+        protos = [_make(SVR, base, p) for p in candidates]   # SVR's own checks on every candidate
+        self.batched_ = uses_batched_svr_search(protos[0], candidates, get_context().world)
+        fit = self._fit_batched if self.batched_ else self._fit_fallback
+        scores, self.n_iter_, self.status_ = fit(X, y, splits, candidates, base)
+        self.n_splits_ = len(splits)
+        self.cv_results_ = aggregate_scores(candidates, scores)
+        self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
+        self.best_params_ = candidates[self.best_index_]
+        self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
+        if self.refit:
+            self.best_estimator_ = _make(SVR, base, self.best_params_).fit(X, y)
+        return self
+
+    def _fit_fallback(self, X, y, splits, candidates, base):
+        nc, ns = len(candidates), len(splits)
+        scores = np.empty((nc, ns))
+        n_iter = np.full((nc, ns), -1, dtype=np.int64)
+        status = np.full((nc, ns), '', dtype=object)
+        for ci, p in enumerate(candidates):
+            for f, (tr, te) in enumerate(splits):
+                est = _make(SVR, base, {}).set_params(**p)
+                try:
+                    scores[ci, f] = est.fit(X[tr], y[tr]).score(X[te], y[te])
+                except ZeroDivisionError:   # no support vector
+                    scores[ci, f] = np.nan
+                n_iter[ci, f] = int(getattr(est.optimizer, 'iter', -1))
+                status[ci, f] = str(getattr(est.optimizer, 'status', ''))
+        return scores, n_iter, status
+
+    def _fit_batched(self, X, y, splits, candidates, base):
+        proto = _make(SVR, base, {})
+        n = len(y)
+        nc, ns = len(candidates), len(splits)
+        scores = np.empty((nc, ns))
+        n_iter = np.full((nc, ns), -1, dtype=np.int64)
+        status = np.full((nc, ns), '', dtype=object)
+        kind = solver_kind(proto.optimizer)
+        for g in plan_svr_columns(X, y, splits, candidates, proto.C, proto.epsilon, proto.kernel):   # one panel at a time
+            m = len(g['cols'])
+            # the 'svr' structure's own linear term is never used by the batched solver
+            obj = KernelQuadratic(X, g['QL'][0], 'svr', g['kernel'], storage=proto.storage, tune_placement=proto._streams_panel(),
+                                  expected_products=proto.max_iter * ((m + 15) // 16))
+            dev = obj.device_problem()
+            cap = svr_column_cap(n, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle))
+            for c0 in range(0, m, cap):
+                cols = g['cols'][c0:c0 + cap]
+                QL, UB = g['QL'][c0:c0 + cap], g['UB'][c0:c0 + cap]
+                # the fp64 panel of a numeric gamma holds the decision kernel's values: such columns are scored on the device
+                on_device = [proto.storage == 'f64' and not isinstance(getattr(candidates[ci].get('kernel', proto.kernel), 'gamma',
+                                                                               None), str) for ci, _, _, _ in cols]
+                held = {}
+
+                def score(solver, _):
+                    if any(on_device):
+                        held['b'], _, held['sse'], _ = solver.heldout(y, [eps for _, _, _, eps in cols])
+
+                res = solve_batched(dev, kind, QL, UB, solver=_DeviceSVRSolver(dev, kind, QL, UB, 1e-6, proto.max_iter),
+                                    before_close=score, vectors=not all(on_device))
+                ests, svs = {}, {}
+                for j, (ci, f, _, _) in enumerate(cols):
+                    n_iter[ci, f], status[ci, f] = res[j]['iter'], res[j]['status']
+                    if on_device[j]:
+                        scores[ci, f] = r2_from_sse(held['sse'][j], y[splits[f][1]])
+                    else:
+                        # decision_function resolves a string gamma on the support vectors and evaluates the kernel in fp64, not
+                        # from an fp32 panel: score through the fold's SVR
+                        ests[j] = _make(SVR, base, candidates[ci])
+                        svs[j] = fitted_svr(ests[j], obj, res[j], X, y)
+                if ests:
+                    W = np.zeros((len(ests), n))
+                    for r, j in enumerate(ests):
+                        W[r][svs[j]] = ests[j].dual_coef_
+                    U = _gram_matmat(dev, W, wide=True)
+                    for r, j in enumerate(ests):
+                        ci, f, _, eps = cols[j]
+                        te = splits[f][1]
+                        try:
+                            ests[j].intercept_ = svr_intercept(y, U[r], svs[j], eps)
+                            scores[ci, f] = ests[j].score(X[te], y[te])
+                        except ZeroDivisionError:   # no support vector
+                            scores[ci, f] = np.nan
+            del dev, obj
+        return scores, n_iter, status
 
     def predict(self, X):
         return self.best_estimator_.predict(X)
