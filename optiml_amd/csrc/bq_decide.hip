@@ -48,7 +48,7 @@ struct decide_params {
     double gamma, coef0;
 };
 
-// DEG: the polynomial kernel's degree when it is 2 or 3, else 0 (pow).  A template argument, not a branch around three epilogues
+// DEG: the polynomial kernel's degree when it is 1, 2 or 3, else 0 (pow).  A template argument, not a branch around three epilogues
 // as in gram_mfma_kernel: with the output accumulators live across it the joined paths spilled (68 VGPRs at GMAX = 1).
 template <int KIND, int GMAX, int DEG>
 __global__ __launch_bounds__(256, GMAX == 1 ? 2 : 1) void decide_multi_kernel(decide_params P) {
@@ -272,6 +272,8 @@ int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0
                     BQ_DECIDE_LAUNCH(BQ_KERNEL_POLY, 3);
                 else if (degree == 2)
                     BQ_DECIDE_LAUNCH(BQ_KERNEL_POLY, 2);
+                else if (degree == 1)
+                    BQ_DECIDE_LAUNCH(BQ_KERNEL_POLY, 1);
                 else
                     BQ_DECIDE_LAUNCH(BQ_KERNEL_POLY, 0);
                 break;

@@ -35,9 +35,12 @@ static __global__ void row_norms_kernel(const double *__restrict__ X, int64_t n,
 }
 
 // (gamma <x, y> + coef0)^degree: degrees 2 and 3 (the reference's default) by multiplication — pow() is ~150 vector
-// instructions per element, x * x * x two; <= 1 ulp from the reference's pow(x, 3.0).  DEG = 0: any degree, pow().
+// instructions per element, x * x * x two; <= 1 ulp from the reference's pow(x, 3.0).  DEG = 0: any degree, pow().  DEG = 1: x
+// itself, as the reference's x ** 1 — the device's pow(x, 1.0) is not x for every x; an instantiation, not a test of `degree`
+// beside pow(), which spilled (decide_multi_kernel<POLY, 1, 0>: 79 VGPRs, gram_stream_sym_kernel<POLY>: 213).
 template <int DEG>
 __device__ __forceinline__ double bq_poly_map(double x, int degree) {
+    if (DEG == 1) return x;
     if (DEG == 2) return x * x;
     if (DEG == 3) return x * x * x;
     return pow(x, (double)degree);

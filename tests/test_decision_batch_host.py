@@ -55,6 +55,40 @@ def test_bad_arguments_are_answered_before_any_device_call(lib):
         _lib.check(call(kernel=_lib.KERNEL_LAPLACIAN, b=None))
 
 
+def test_no_support_vector_at_all_is_the_same_error_on_both_routes(lib, monkeypatch):
+    """No estimator has a support vector: the union of `DecisionBatch` is empty.  The loop over the estimators does not return
+    intercepts there: `SVM.decision_function` with an empty `support_vectors_` hands m = 0 to `bq_decision_function`, which
+    answers ERR_BADARG before any device call, and `_lib.check` raises.  The batched route does the same through
+    `bq_decision_function_multi`.  (The context is a block of zeroed host memory, as above.)"""
+    from optiml_amd import _lib
+    from optiml_amd.ml.svm import SVC
+    from optiml_amd.ml.svm import _base, _batched
+    from optiml_amd.ml.svm._batched import DecisionBatch
+    from optiml_amd.ml.svm.kernels import GaussianKernel
+    from optiml_amd.ml.svm.losses import hinge
+
+    class FakeContext:
+        handle = C.cast(C.create_string_buffer(1 << 16), C.c_void_p)
+        world = 1
+
+    monkeypatch.setattr(_base, 'get_context', lambda: FakeContext)
+    monkeypatch.setattr(_batched, 'get_context', lambda: FakeContext)
+    rs = np.random.RandomState(0)
+    X, Xte = rs.standard_normal((20, 4)), rs.standard_normal((7, 4))
+    kernel = GaussianKernel(gamma=0.5)
+    est = SVC(loss=hinge, kernel=kernel, C=1.0, reg_intercept=True, dual=True)
+    est.support_ = np.zeros(0, dtype=int)   # as `fitted_svc` and `SVC.fit` leave an estimator none of whose alphas passes 1e-6
+    est.support_vectors_, est.dual_coef_, est.intercept_ = X[est.support_], np.zeros(0), 0.25
+    with pytest.raises(_lib.BcqpError) as loop:
+        est.decision_function(Xte)
+    batch = DecisionBatch(kernel, X, np.zeros((3, 20)), [0.25, -1.0, 2.0])
+    assert batch.SV.shape == (0, 4) and batch.W.shape == (3, 0) and len(batch.rows) == 0
+    with pytest.raises(_lib.BcqpError) as batched:
+        batch(Xte)
+    assert loop.value.code == batched.value.code == _lib.ERR_BADARG
+    assert 'm/d/t' in str(loop.value) and 'm/d/t/k' in str(batched.value)
+
+
 def test_the_rule():
     from optiml_amd.ml.svm._batched import uses_batched_decision
     from optiml_amd.ml.svm.kernels import GaussianKernel, LaplacianKernel, PolyKernel, SigmoidKernel, gaussian, linear
