@@ -804,41 +804,52 @@ extern "C" int bq_problem_panel_rows(bq_problem *p, int64_t row0, int64_t nrows,
     bq_ctx *c = p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     if (nrows == 0) return BQ_OK;
-    if (p->symmetric && p->compact) {   // the compact layout: the row's stretch of each plane, decoded here
-        const bq_c7p pv = bq_c7_view(p->panel, p->panel_elems);
-        std::vector<uint32_t> lo((size_t)p->n);
-        std::vector<uint16_t> mid((size_t)p->n);
-        std::vector<uint8_t> top((size_t)p->n);
-        for (int64_t r = 0; r < nrows; ++r) {
-            const int64_t i = row0 + r;
-            const int64_t len = std::min(p->n, bq_sym_pitch(i / BQ_SYM_TILE)), a = bq_sym_addr(i, 0, p->I0);
-            BQ_HIP(hipMemcpyAsync(lo.data(), pv.lo + a, (size_t)len * 4, hipMemcpyDeviceToHost, c->stream));
-            BQ_HIP(hipMemcpyAsync(mid.data(), pv.mid + a, (size_t)len * 2, hipMemcpyDeviceToHost, c->stream));
-            BQ_HIP(hipMemcpyAsync(top.data(), pv.top + a, (size_t)len, hipMemcpyDeviceToHost, c->stream));
-            BQ_SYNC(c);
-            double *o = out + r * p->n;
-            for (int64_t j = 0; j < len; ++j) {
-                const uint64_t b = bq_c7_bits(lo[j], mid[j], top[j]);
-                std::memcpy(&o[j], &b, sizeof(double));
-            }
-            for (int64_t j = len; j < p->n; ++j) o[j] = 0.0;
-        }
-        return BQ_OK;
-    }
     if (p->symmetric) {
-        // packed layout: row i holds its (I+1)*256 leading columns; the rest of the output row (strictly-upper tiles) is 0
-        const size_t esz = p->storage == BQ_F64 ? 8 : 4;
-        std::vector<unsigned char> tmp((size_t)p->n * esz);
-        for (int64_t r = 0; r < nrows; ++r) {
-            const int64_t i = row0 + r;
-            const int64_t len = std::min(p->n, bq_sym_pitch(i / BQ_SYM_TILE));
-            BQ_HIP(hipMemcpyAsync(tmp.data(), (const unsigned char *)p->panel + (size_t)bq_sym_addr(i, 0, p->I0) * esz,
-                                  (size_t)len * esz, hipMemcpyDeviceToHost, c->stream));
+        // packed layout: row i holds its (I+1)*256 leading columns, strip by strip (bq_sym_addr); the rest of the output row
+        // (strictly-upper tiles) is 0.  The requested rows are taken tile row by tile row: within one, a strip's stretch of these rows
+        // is ONE 2-D copy per plane (source pitch: the strip's; destination: a staging block of whole rows), decoded / widened here.
+        const int64_t n = p->n;
+        const size_t esz = p->compact ? 4 : p->storage == BQ_F64 ? 8 : 4;   // compact: the lo plane; mid and top beside it
+        const int64_t cap = std::min<int64_t>(nrows, BQ_SYM_TILE);
+        std::vector<unsigned char> lo((size_t)cap * n * esz);
+        std::vector<uint16_t> mid(p->compact ? (size_t)cap * n : 0);
+        std::vector<uint8_t> top(p->compact ? (size_t)cap * n : 0);
+        const bq_c7p pv = p->compact ? bq_c7_view(p->panel, p->panel_elems) : bq_c7p{nullptr, nullptr, nullptr};
+        for (int64_t r = 0; r < nrows;) {
+            const int64_t i0 = row0 + r, I = i0 / BQ_SYM_TILE;
+            const int64_t rb = std::min(nrows - r, (I + 1) * BQ_SYM_TILE - i0);   // rows of this tile row
+            const int64_t len = std::min(n, bq_sym_cols(I));
+            for (int64_t j0 = 0; j0 < len; j0 += BQ_SYM_STRIP_COLS) {
+                const int64_t a = bq_sym_addr(i0, j0, p->I0), m = std::min(len - j0, BQ_SYM_STRIP_COLS);
+                const int64_t w = bq_sym_strip_w(I, j0 / BQ_SYM_STRIP_COLS);
+                const unsigned char *src = p->compact ? (const unsigned char *)(pv.lo + a) : (const unsigned char *)p->panel + (size_t)a * esz;
+                BQ_HIP(hipMemcpy2DAsync(lo.data() + (size_t)j0 * esz, (size_t)n * esz, src, (size_t)w * esz, (size_t)m * esz, (size_t)rb,
+                                        hipMemcpyDeviceToHost, c->stream));
+                if (p->compact) {
+                    BQ_HIP(hipMemcpy2DAsync(mid.data() + j0, (size_t)n * 2, pv.mid + a, (size_t)w * 2, (size_t)m * 2, (size_t)rb,
+                                            hipMemcpyDeviceToHost, c->stream));
+                    BQ_HIP(hipMemcpy2DAsync(top.data() + j0, (size_t)n, pv.top + a, (size_t)w, (size_t)m, (size_t)rb,
+                                            hipMemcpyDeviceToHost, c->stream));
+                }
+            }
             BQ_SYNC(c);
-            double *o = out + r * p->n;
-            for (int64_t j = 0; j < len; ++j)
-                o[j] = p->storage == BQ_F64 ? ((const double *)tmp.data())[j] : (double)((const float *)tmp.data())[j];
-            for (int64_t j = len; j < p->n; ++j) o[j] = 0.0;
+            for (int64_t k = 0; k < rb; ++k) {
+                double *o = out + (r + k) * n;
+                if (p->compact) {
+                    const uint32_t *l = (const uint32_t *)lo.data() + k * n;
+                    for (int64_t j = 0; j < len; ++j) {
+                        const uint64_t b = bq_c7_bits(l[j], mid[(size_t)(k * n + j)], top[(size_t)(k * n + j)]);
+                        std::memcpy(&o[j], &b, sizeof(double));
+                    }
+                } else if (p->storage == BQ_F64) {
+                    std::memcpy(o, (const double *)lo.data() + k * n, (size_t)len * 8);
+                } else {
+                    const float *f = (const float *)lo.data() + k * n;
+                    for (int64_t j = 0; j < len; ++j) o[j] = (double)f[j];
+                }
+                for (int64_t j = len; j < n; ++j) o[j] = 0.0;
+            }
+            r += rb;
         }
         return BQ_OK;
     }

@@ -1,6 +1,6 @@
 // The compact fp64 panel layout: an RBF Gram entry lies in (0, 1], and every fp64 value in [2^-15, 2) has the top byte 0x3F
 // (sign 0, the upper seven exponent bits).  An eligible panel (bq_c7_eligible) therefore stores each element in 7 bytes, in three
-// planes over the packed lower-triangle index of bq_sym_addr: `lo` bits 0-31 (4 B), `mid` bits 32-47 (2 B), `top` bits 48-55 (1 B),
+// planes over the packed lower-triangle index of bq_sym_addr (strip after strip: bq_sym_layout.h; one index for all three planes): `lo` bits 0-31 (4 B), `mid` bits 32-47 (2 B), `top` bits 48-55 (1 B),
 // in one allocation of elems x 7 bytes (lo plane, then mid, then top).  Columns keep their natural order within a row, so an
 // adjacent column pair is 8 + 4 + 2 naturally aligned bytes and one element 4 + 2 + 1.
 // Zero code: all 56 stored bits zero decode to +0.0 (the memset panel and the zero pad of the ragged last tile row / column), so the

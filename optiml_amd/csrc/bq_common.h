@@ -296,16 +296,9 @@ static inline bq_panel_ref bq_problem_panel(const bq_problem *p, const void *bas
 static inline bool bq_compact_allowed() { return bq_hook_on("compact_panel"); }
 
 // bq_symv.hip: symmetric tile product over tile rows [I0, I1) -> out (nb*256 partial sums)
-constexpr int64_t BQ_SYM_TILE = 256;
-// Packed layout of a symmetric (kernel-built) panel: tile row I (256 rows) keeps only its columns [0, (I+1)*256), stored
-// row-major with pitch (I+1)*256; tile rows are concatenated.  Element (i, j), j's tile <= i's tile, of a panel whose
-// first stored tile row is I0:
-__host__ __device__ inline int64_t bq_sym_off(int64_t I) { return BQ_SYM_TILE * BQ_SYM_TILE * (I * (I + 1) / 2); }
-__host__ __device__ inline int64_t bq_sym_pitch(int64_t I) { return (I + 1) * BQ_SYM_TILE; }
-__host__ __device__ inline int64_t bq_sym_addr(int64_t i, int64_t j, int64_t I0) {
-    const int64_t I = i / BQ_SYM_TILE;
-    return bq_sym_off(I) - bq_sym_off(I0) + (i - I * BQ_SYM_TILE) * bq_sym_pitch(I) + j;
-}
+// Packed layout of a symmetric (kernel-built) panel — BQ_SYM_STRIP, bq_sym_off, bq_sym_strip_w, bq_sym_strip_off, bq_sym_addr: a header
+// of its own, free of HIP, so that tests/c/sym_layout_check.cpp compiles the same address function for the host
+#include "bq_sym_layout.h"
 // Canonical segments of a symmetric panel's tile rows.  The partial products of the lower-triangle tiles are summed per
 // SEGMENT (a contiguous range of tile rows holding 1/S of the triangle's tiles, boundaries a function of nb and S only) and the
 // S segment vectors are then added in segment order on every rank, so the product is bit-identical for any number of

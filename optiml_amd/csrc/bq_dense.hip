@@ -3,7 +3,7 @@
 // Two layouts.  ROW BLOCKS: all of Q, this rank's 128-aligned rows, pitch round_up(n, 1024) — what gemv_rows_kernel streams
 // (n^2 s bytes per product); the only layout a Q that is NOT symmetric can have (the reference never checks symmetry,
 // opti/_base.py:249-256, and `Q @ x` of such a Q is what it computes).  PACKED LOWER TILE ROWS: the layout of the kernel-built
-// Gram panels (bq_common.h: bq_sym_addr) — tile row I keeps its (I+1)*256 leading columns — which symv_tiles_kernel streams once
+// Gram panels (bq_common.h: bq_sym_addr) — tile row I keeps its (I+1)*256 leading columns, strip after strip — which symv_tiles_kernel streams once
 // for both the row and the column contributions: half the HBM and half the bytes per product.  Every Hessian the reference's
 // formulas are valid for is symmetric (`Qx + q` is the gradient of 1/2 x'Qx only then, opti/_base.py:291), so the packed layout is
 // the default WHEN Q == Q' HOLDS EXACTLY, element for element as stored (fp64 bits; fp32 storage: the rounded values) — checked on
@@ -28,13 +28,13 @@ template <> struct bits_of<float> {
     static __device__ __forceinline__ long long get(float v) { return (long long)__float_as_int(v); }
 };
 
-// rows x width block of fp64 values (pitch ldt) -> storage type, row-major with the given pitch
+// rows x width block of fp64 values (pitch ldt) -> storage type, tile row I of the packed panel (bq_sym_addr: strip after strip)
 template <typename T>
 __global__ __launch_bounds__(256) void dense_pack_kernel(const double *__restrict__ tmp, int64_t ldt, int64_t width,
-                                                         T *__restrict__ dst, int64_t pitch) {
+                                                         T *__restrict__ panel, int64_t I, int64_t I0) {
     const int64_t r = blockIdx.y;
     for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < width; c += (int64_t)gridDim.x * 256)
-        dst[r * pitch + c] = (T)tmp[r * ldt + c];
+        panel[bq_sym_addr(I * BQ_SYM_TILE + r, c, I0)] = (T)tmp[r * ldt + c];
 }
 
 // BQ_DENSE_LOWER: the diagonal tile is stored whole (the tile kernel reads all of it for its row part), so its upper half is
@@ -112,10 +112,10 @@ int upload_sym_t(bq_problem *p, const double *Q, bool check, int *symmetric) {
         BQ_HIP(hipMemcpy2DAsync(s.tmp, (size_t)ldt * 8, Q + I * T256 * n, (size_t)n * 8, (size_t)width * 8, (size_t)rows,
                                 hipMemcpyHostToDevice, c->stream));
         dense_pack_kernel<T><<<dim3((unsigned)std::min<int64_t>((lower + 255) / 256, 1024), (unsigned)rows), 256, 0, c->stream>>>(
-            s.tmp, ldt, lower, panel + (bq_sym_off(I) - bq_sym_off(p->I0)), bq_sym_pitch(I));
-        if (!check)
-            dense_mirror_diag_kernel<T><<<(unsigned)rows, 256, 0, c->stream>>>(panel + (bq_sym_off(I) - bq_sym_off(p->I0)) + I * T256,
-                                                                                bq_sym_pitch(I), rows);
+            s.tmp, ldt, lower, panel, I, p->I0);
+        if (!check)   // the diagonal tile lies in the last strip of its tile row
+            dense_mirror_diag_kernel<T><<<(unsigned)rows, 256, 0, c->stream>>>(panel + bq_sym_addr(I * T256, I * T256, p->I0),
+                                                                                bq_sym_strip_w(I, I / BQ_SYM_STRIP), rows);
         if (check) {
             const int64_t c_lo = I * T256;
             dense_symcheck_kernel<T><<<dim3((unsigned)((col_end - c_lo + 31) / 32), (unsigned)((rows + 31) / 32)), 256, 0, c->stream>>>(

@@ -21,6 +21,7 @@
 #include <vector>
 
 constexpr int GT = BQ_GT;
+static_assert(BQ_SYM_STRIP_COLS % GT == 0 && BQ_SYM_TILE % GT == 0, "a Gram tile lies inside one strip of the packed layout");
 #ifndef BQ_STREAM_FOLD
 #define BQ_STREAM_FOLD 0
 #endif
@@ -145,9 +146,11 @@ __global__ __launch_bounds__(256, 2) void gram_mfma_kernel(gram_params P, typena
         // diagonal of a symmetric build pays for the "exact zero distance at i == j" test, only tiles that stick out of the
         // matrix for the bounds tests (their branches also cut the rows into separate blocks: two exp chains in flight
         // instead of four).  A row's address is this lane's base (once per tile) + a uniform multiple of the pitch.
-        const int64_t pitch = P.lower_only ? bq_sym_pitch(arow / BQ_SYM_TILE) : P.ld;
-        const int64_t tile0 = P.lower_only ? bq_sym_addr(arow, 0, I0) : (arow - P.arow0) * P.ld;   // uniform
-        const typename gram_out<T>::row lane_base = out + tile0 + (int64_t)(wr * 64 + 2 * crow) * pitch + bcol + wc * 64 + 2 * ccol;
+        // A packed panel keeps the strips of a tile row apart (bq_sym_addr): a 128-column tile lies inside one strip, so its rows have
+        // that strip's pitch and no store crosses a strip seam.
+        const int64_t pitch = P.lower_only ? bq_sym_strip_w(arow / BQ_SYM_TILE, bcol / BQ_SYM_STRIP_COLS) : P.ld;
+        const int64_t tile0 = P.lower_only ? bq_sym_addr(arow, bcol, I0) : (arow - P.arow0) * P.ld + bcol;   // uniform
+        const typename gram_out<T>::row lane_base = out + tile0 + (int64_t)(wr * 64 + 2 * crow) * pitch + wc * 64 + 2 * ccol;
         double bj[4];   // the squared norms of this lane's four columns, once per tile (b2 is padded to the image pitch)
 #pragma unroll
         for (int j = 0; j < 4; ++j) bj[j] = KIND == BQ_KERNEL_RBF ? P.b2[bcol + bq_acc_col(2 * (j >> 1)) + (j & 1)] : 0.0;

@@ -14,7 +14,7 @@
 // The index sets I0..I4 of the reference are functions of (alpha, y) and are not stored.
 // TIE RULE: where the reference's `for i in self.I0` loop (CPython set order) decides between two free samples with
 // bit-identical cached errors, this kernel takes the smaller index (oracle/smo_oracle.py, tie='index').
-// K[i][j] comes from the packed lower-triangular tile-row panel (bq_sym_addr: the row part is contiguous, the part right
+// K[i][j] comes from the packed lower-triangular tile-row panel (bq_sym_addr: the row part is contiguous strip by strip, the part right
 // of the diagonal tile is read down the column of the later tile rows — one page per support vector) or, preferably, from
 // a full square panel (BQ_FULL_PANEL: every row contiguous, one page per examined sample).
 #include <cfloat>

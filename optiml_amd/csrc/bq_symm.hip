@@ -45,8 +45,10 @@ __global__ __launch_bounds__(256, 2) void symm_tiles_kernel(bq_pptr<T> panel, in
     const int nj = (int)((J0 + SJG <= I + 1) ? SJG : (I + 1 - J0));
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t pitch = bq_sym_pitch(I);
-    const auto rows = panel + bq_sym_off(I) + (int64_t)(wv * 64) * pitch + J0 * ST;
+    // packed layout (bq_sym_addr): SJG tiles from a multiple of SJG lie inside ONE strip of the layout, whose pitch their rows have
+    static_assert(BQ_SYM_STRIP % SJG == 0, "a strip of this kernel lies inside one strip of the layout");
+    const int64_t gl = J0 / BQ_SYM_STRIP, pitch = bq_sym_strip_w(I, gl);
+    const auto rows = panel + (bq_sym_strip_off(I, gl) + (int64_t)(__builtin_amdgcn_readfirstlane(wv) * 64) * pitch + (J0 - gl * BQ_SYM_STRIP) * ST);
     const double *Wc = W + (int64_t)ch * CK * ldw;
     const int c0 = tile_ld<T>::c0(lane), c1 = tile_ld<T>::c1(lane);
     d2_t wj0[CK][SJG], wj1[CK][SJG];

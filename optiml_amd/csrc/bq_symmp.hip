@@ -112,16 +112,25 @@ __global__ __launch_bounds__(256, 2) void symmp_single_kernel(bq_pptr<T> panel, 
     const int64_t I = it.I, J0 = it.J0;
     const int nj = it.nj;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t pitch = bq_sym_pitch(I);
-    const auto rows = panel + bq_sym_off(I) + (int64_t)(wv * 64) * pitch + J0 * ST;
     const double *w = W + (int64_t)it.id * ldw;
     const double *wI = w + I * ST + wv * 64;
     const int c0 = tile_ld<T>::c0(lane), c1 = tile_ld<T>::c1(lane);
     d2_t wj0[JG], wj1[JG];
     double ca[JG][4];
+    // A class block starts at any tile, so this strip may straddle two strips of the packed layout (bq_sym_addr): tiles j < jsplit lie
+    // in layout strip gA, the others in gA + 1, each with its strip's base and row pitch — tile j of this wave's first row is at
+    // oA + j * ST or oB + j * ST (all wave-uniform; strip gA + 1 is looked at only when a tile of this strip lies in it)
+    static_assert(JG <= BQ_SYM_STRIP, "a strip of this kernel straddles at most two strips of the layout");
+    const int64_t gA = J0 / BQ_SYM_STRIP;
+    const int jsplit = (int)((gA + 1) * BQ_SYM_STRIP - J0);
+    const int64_t pA = bq_sym_strip_w(I, gA), pB = bq_sym_strip_w(I, gA + 1);
+    const int64_t wrow = (int64_t)(__builtin_amdgcn_readfirstlane(wv) * 64);
+    const int64_t oA = bq_sym_strip_off(I, gA) + wrow * pA + (J0 - gA * BQ_SYM_STRIP) * ST;
+    const int64_t oB = bq_sym_strip_off(I, gA + 1) + wrow * pB - jsplit * ST;
 #pragma unroll
     for (int j = 0; j < JG; ++j) {
-        const double *wJ = w + (J0 + (j < nj ? j : 0)) * ST;
+        const int64_t J = J0 + (j < nj ? j : 0);
+        const double *wJ = w + J * ST;
         wj0[j] = *reinterpret_cast<const d2_t *>(wJ + c0);
         wj1[j] = *reinterpret_cast<const d2_t *>(wJ + c1);
         ca[j][0] = ca[j][1] = ca[j][2] = ca[j][3] = 0.0;
@@ -140,13 +149,16 @@ __global__ __launch_bounds__(256, 2) void symmp_single_kernel(bq_pptr<T> panel, 
             rp[k] = 0.0;
             wi[k] = wI[step * SR + k];
         }
+        int so = step * SR;   // opaque: the row offsets are scalar arithmetic of THIS step (hoisted out of the loop they spill)
+        asm volatile("" : "+s"(so));
 #pragma unroll
         for (int j = 0; j < JG; ++j) {
             if (j < nj) {
                 d2_t a[SR], b[SR];
 #pragma unroll
                 for (int k = 0; k < SR; ++k) {
-                    const auto row = rows + (int64_t)(step * SR + k) * pitch + j * ST;
+                    const int64_t rel = (int64_t)(unsigned)((so + k) * (j < jsplit ? (int)pA : (int)pB) + j * ST);
+                    const auto row = panel + ((j < jsplit ? oA : oB) + rel);
                     tile_ld<T>::get(row, lane, a[k], b[k]);
                 }
 #pragma unroll
@@ -260,9 +272,12 @@ __global__ __launch_bounds__(256, 2) void symmp_diag_kernel(bq_pptr<T> panel, co
     }
     __syncthreads();
 
-    const int64_t pitch = bq_sym_pitch(I);
-    const auto base = panel + bq_sym_off(I) + (int64_t)(wv * 64 + s) * pitch + J0 * ST;
-    auto rowp = [&](int j, int cq, int st) { return base + (int64_t)(16 * st) * pitch + j * ST + 64 * cq; };
+    // A class block starts at any tile, so this strip may straddle two strips of the packed layout (bq_sym_addr): the tile of every
+    // step is decoded through the address function (uniform), this lane's row within the wave's 64 times the tile's pitch on top
+    auto rowp = [&](int j, int cq, int st) {
+        const int64_t J = J0 + j, gl = J / BQ_SYM_STRIP, pitch = bq_sym_strip_w(I, gl);
+        return panel + (bq_sym_strip_off(I, gl) + (J - gl * BQ_SYM_STRIP) * ST + 64 * cq) + (int64_t)(wv * 64 + 16 * st + s) * pitch;
+    };
 
     const int myq = spair[s];
     double wi[4][4];   // W_I[64 wv + 16 st + 4 u + h][slot s]

@@ -45,11 +45,13 @@ __global__ __launch_bounds__(256, 2) void symmw_tiles_kernel(bq_pptr<T> panel, i
     const int nj = (int)((J0 + WJG <= I + 1) ? WJG : (I + 1 - J0));
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, h = lane >> 4, s = lane & 15;
-    const int64_t pitch = bq_sym_pitch(I);
+    // packed layout (bq_sym_addr): WJG tiles from a multiple of WJG lie inside ONE strip of the layout, whose pitch their rows have
+    static_assert(BQ_SYM_STRIP % WJG == 0, "a strip of this kernel lies inside one strip of the layout");
+    const int64_t gl = J0 / BQ_SYM_STRIP, pitch = bq_sym_strip_w(I, gl);
     const double *Wc = W + (int64_t)ch * CK * ldw;
     const int64_t cs = nb * nb * ST;   // slab stride of one column
     // this wave's row r of tile (I, J0 + j), quarter cq, step st: lane row = 64 wv + 16 st + (lane & 15)
-    const auto base = panel + bq_sym_off(I) + (int64_t)(wv * 64 + s) * pitch + J0 * ST;
+    const auto base = panel + bq_sym_strip_off(I, gl) + (int64_t)(wv * 64 + s) * pitch + (J0 - gl * BQ_SYM_STRIP) * ST;
     auto rowp = [&](int j, int cq, int st) { return base + (int64_t)(16 * st) * pitch + j * ST + 64 * cq; };
 
     double wi[4][4];   // W_I[64 wv + 16 st + 4 u + h][s]

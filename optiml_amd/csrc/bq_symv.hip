@@ -2,8 +2,9 @@
 // row-block product for the (symmetric) Gram panels of the SVM dual.
 //
 // The panel is cut into 256 x 256 tiles (I, J), J <= I, and stored PACKED: tile row I keeps only its (I+1)*256 leading
-// columns (row-major), so the lower triangle costs half the HBM of the square panel.  A work item is a STRIP: up to JG consecutive tiles of one
-// tile row, i.e. 256 rows x (JG * 2 KiB) contiguous bytes per row.  The workgroup streams the strip once (16-byte
+// columns, so the lower triangle costs half the HBM of the square panel.  A work item is a STRIP: up to JG consecutive tiles of one
+// tile row, i.e. 256 rows x (JG * 2 KiB) contiguous bytes per row — and the layout stores a strip as ONE row-major block
+// (bq_sym_layout.h), so the workgroup reads one contiguous run of up to 4 MiB.  The workgroup streams the strip once (16-byte
 // non-temporal loads, lanes along the columns) and produces BOTH contributions the strip is responsible for:
 //   row part   S[I][J0][r]  = sum over the strip's columns of elem(K[I*T+r][c]) * w[c]        (to output block I)
 //   col parts  S[J][I][c]   = sum_r elem(K[I*T+r][J*T+c]) * w[I*T+r],  each J != I of the strip  (to output block J)
@@ -56,9 +57,12 @@ __global__ __launch_bounds__(256, 2) void symv_tiles_kernel(bq_pptr<T> panel, in
     const int nj = (int)((J0 + JG <= I + 1) ? JG : (I + 1 - J0));  // tiles in this strip (J <= I)
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // packed symmetric layout: tile row I has pitch (I+1)*256 and starts at bq_sym_off(I) - bq_sym_off(I0)
-    const int64_t pitch = bq_sym_pitch(I);
-    const auto rows = panel + (bq_sym_off(I) - bq_sym_off(I0)) + (int64_t)(wv * 64) * pitch + J0 * ST;
+    // packed symmetric layout (bq_sym_addr): the strip is one contiguous row-major 256 x (nj * 256) block.  The wave's first row is
+    // told to the compiler as the wave-uniform value it is: the strip base and every row offset then stay in scalar registers (with
+    // the wave index in a vector register the 8-row and the compact instantiations spilled: profiles/strip_layout).
+    static_assert(JG == BQ_SYM_STRIP, "the strip of the kernel is the strip of the layout");
+    const int64_t pitch = bq_sym_strip_w(I, g);
+    const auto rows = panel + ((bq_sym_strip_off(I, g) - bq_sym_off(I0)) + (int64_t)(__builtin_amdgcn_readfirstlane(wv) * 64) * pitch);
     const double *wI = w + I * ST + wv * 64;
     const int c0 = tile_ld<T>::c0(lane), c1 = tile_ld<T>::c1(lane);
     d2_t wj0[JG], wj1[JG];
