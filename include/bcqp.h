@@ -53,6 +53,7 @@ extern "C" {
 /* (still 3: the structure flag BQ_PLAIN_PANEL was added) */
 /* (still 3: bq_msolver_create_svr was added) */
 /* (still 3: bq_msolver_create_svr_boxes and bq_msolver_svr_heldout were added; nothing existing changed) */
+/* (still 3: bq_msolver_create_al was added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -447,6 +448,24 @@ int bq_al_solver_create(bq_problem *p, const bq_al_params *prm, const double *a_
 int bq_al_solver_set_schedules(bq_solver *s, const double *step_sizes, const double *momenta, int64_t count);
 /* number of multipliers (length of BQ_GET_DUAL) */
 int bq_al_solver_dual_size(const bq_solver *s, int64_t *n_dual);
+/* The batch of k augmented-Lagrangian solvers on ONE Gram panel: sklearn OneVsRestClassifier over SVC.fit and
+ * MultiOutputRegressor over SVR.fit on the stochastic-optimizer branch (optiml/ml/svm/_base.py:638-723, :776-860 once per class;
+ * :1188-1270, :1330-1415 once per target) — the only box-type route to reg_intercept=False (equality row y_c / [1; -1]) and to the
+ * squared losses (diag = 1/(2C), no upper bound).  p: a kernel-built BQ_SVC or BQ_SVR problem on a single-rank context with a
+ * resident packed panel (anything else is BQ_ERR_BADARG); its own labels are not used.  Column c is the solver that
+ * bq_al_solver_create(p, prm, a_eq_c, lb, ub, x0_c, dual0_c) makes, with Q_c = diag(y_c) P diag(y_c) (BQ_SVC, Y: k x n labels +-1)
+ * or the linear term QL[c] (BQ_SVR, QL: k x 2n; NULL: every column has p's q) — same formulas, rules, multiplier update, stop tests
+ * and records (optiml/opti/_base.py:129-146 and the seven rule files); an iteration's products are one panel stream per 4 live
+ * columns, and a column that stops leaves the batch.  Column c's iterates have the same bits alone, at any position, in any batch
+ * and however the iterations are cut into runs (they agree with bq_al_solver_create's to rounding: another product kernel).
+ * a_eq: NULL (no equality row), one row of N for every column (a_ld = 0) or one per column (a_ld = N); lb, ub: N each or NULL,
+ * shared; x0: k x N (required); dual0: k x n_dual in the layout of BQ_GET_DUAL, or NULL = zeros.  Constant step size and momentum;
+ * momentum none or Polyak: BQ_MOM_NESTEROV is BQ_ERR_BADARG (it needs a jump and a close per iteration), and there are no
+ * schedules.  run / state / get / destroy: as bq_msolver_create, on vectors of N; get takes BQ_GET_DUAL, _X, _X_NOW, _G, _D per
+ * column as bq_solver_get does for an augmented-Lagrangian solver. */
+int bq_msolver_create_al(bq_problem *p, const bq_al_params *prm, int k, const double *Y, const double *QL, const double *a_eq,
+                         int64_t a_ld, const double *lb, const double *ub, const double *x0, const double *dual0,
+                         bq_msolver **out);
 
 /* ---- SMO on the resident Gram panel (optiml/ml/svm/smo.py) -----------------------------------------
  * SMOClassifier (:99-357) / SMORegression (:386-797): the reg_intercept=False duals through SVC/SVR(optimizer='smo')

@@ -128,6 +128,7 @@ PROTOTYPES = {
     'bq_msolver_create_pairs': (C.c_int, [_vp, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.c_double,
                                           C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
+    'bq_msolver_create_al': (C.c_int, [_vp, C.POINTER(AlParams), C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     'bq_al_solver_dual_size': (C.c_int, [_vp, C.POINTER(_i64)]),
     'bq_al_solver_set_schedules': (C.c_int, [_vp, _dp, _dp, _i64]),
     'bq_smo_create': (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.POINTER(_vp)]),

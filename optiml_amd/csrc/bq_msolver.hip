@@ -24,6 +24,21 @@
 // q_c = [-y_c; y_c] + eps and every target the Hessian [P -P; -P P]): the columns are vectors of 2n, one thread of the start-up and
 // update kernels owns the elements i and n + i of a target (mstart_*_svr_kernel, mpgfw_update_svr_kernel), the product input is
 // d+ - d- (n), and the closing kernel is mfinish_kernel, whose element code handles both halves (bq_epi_element).
+//
+// bq_msolver_create_al is the batch of k augmented-Lagrangian solvers (bq_al.hip; one-vs-rest SVC and multi-output SVR with the
+// first-order rules: the unregularised intercept's equality row, the squared losses).  Column c is the bq_solver that
+// bq_al_solver_create makes, with its own labels (BQ_SVC) or linear term (BQ_SVR); an iteration of all live columns is
+//   [prep    (n/256 x k blocks)  BQ_SVR only: W[:, pos[c]] = x+ - x-, as the single solver's own launch for it]
+//   product  bq_launch_symm, as above
+//   closing  (n/256 x k blocks)  mal_finish_kernel: finish_al_kernel per column (bq_al_epi_*, the column's own ticket and partials)
+//   live     mlive_kernel, BEFORE the update: the closing kernel is the one that stops a column, and the update writes the next
+//            product's input, so it must see the slots of the next product
+//   update   (N/256 x k blocks)  mal_update_kernel: al_update_body per column (bq_al_update.h), W[:, pos[c]] = y_c o x_new (BQ_SVC)
+// A bq_msolver_run starts with the prep kernel (the flush of the run before may have stopped a column and moved the slots) and ends
+// with mal_flush_kernel (al_flush_kernel per column) and the live kernel: a column's bits do not depend on how the iterations are
+// cut into runs.  Nesterov momentum (a jump kernel and a flush per iteration) and schedules are not batched.
+#include "bq_al.h"
+#include "bq_al_update.h"
 #include "bq_common.h"
 #include "bq_epilogue.h"
 
@@ -46,6 +61,9 @@ struct bq_msolver {
     int *nlive_host = nullptr;    // pinned copy of *nlive + its event (lagged polling)
     hipEvent_t flag_event = nullptr;
     int live_host = 0;            // upper bound of *nlive known to the host
+    bool al = false;              // bq_msolver_create_al: the columns are augmented-Lagrangian solvers (epi: k entries of kind 2)
+    bq_al_params al_prm = {};
+    struct bq_al_col *al_cols = nullptr;   // k: what mal_update_kernel reads of a column
     bool initialised = false, started = false;
 };
 
@@ -217,6 +235,51 @@ __global__ __launch_bounds__(1024) void msvr_score_kernel(const bq_epilogue *__r
     }
 }
 
+// ---- the augmented-Lagrangian batch: what al_update_kernel takes as arguments, per column
+struct bq_al_col {
+    bq_al_vecs V;
+    bq_scal *sc;
+    const double *sgn;   // the column's labels (BQ_SVC), else null
+};
+
+// the product input of every live column from its point: y_c o x (BQ_SVC) or x+ - x- (BQ_SVR), to the column's slot
+__global__ __launch_bounds__(256) void mal_prep_kernel(const bq_epilogue *__restrict__ epi, const int *__restrict__ pos,
+                                                       double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    if (e.sc->done) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    W[pos[blockIdx.y] * ldw + i] = e.structure == BQ_SVR ? e.x[i] - e.x[e.n + i] : e.sgn[i] * e.x[i];
+}
+
+// finish_al_kernel (bq_al.hip) for column blockIdx.y: the same rows per block, the same tree, the column's own ticket and partials
+__global__ __launch_bounds__(256) void mal_finish_kernel(const bq_epilogue *__restrict__ epi, const int *__restrict__ pos,
+                                                         const double *__restrict__ out, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    if (e.sc->done) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bq_al_pre pre = bq_al_epi_preload(e, i, true, true);
+    const double sv = i < e.n ? out[pos[blockIdx.y] * ldw + i] : 0.0;
+    bq_al_epi_finish<true>(e, blockIdx.x, gridDim.x, bq_al_epi_element(e, pre, i, sv, true), gridDim.x);
+}
+
+// al_flush_kernel (bq_al.hip) for column blockIdx.y
+__global__ __launch_bounds__(256) void mal_flush_kernel(const bq_epilogue *__restrict__ epi) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    if (e.sc->done || !e.sc->al_pending) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bq_al_pre pre = bq_al_epi_preload(e, i, true, false);
+    bq_al_epi_finish<false>(e, blockIdx.x, gridDim.x, bq_al_epi_element(e, pre, i, 0.0, false), gridDim.x);
+}
+
+// al_update_kernel (bq_al.hip) for column blockIdx.y, writing the next product's input to the column's slot (BQ_SVC).  A column
+// that the closing kernel has just stopped has a stale pos[] entry (< k): al_update_body writes no input for it
+__global__ __launch_bounds__(256) void mal_update_kernel(int64_t N, int64_t ldN, const bq_al_col *__restrict__ cols, bq_al_params prm,
+                                                         const int *__restrict__ pos, double *__restrict__ W, int64_t ldw) {
+    const bq_al_col &c = cols[blockIdx.y];
+    al_update_body(N, ldN, c.V, prm, c.sc, c.sgn, c.sgn != nullptr ? W + pos[blockIdx.y] * ldw : nullptr);
+}
+
 __global__ void mlive_kernel(bq_scal *const *__restrict__ scs, int k, int *__restrict__ pos, int *__restrict__ nlive) {
     if (threadIdx.x != 0) return;
     int s = 0;
@@ -230,7 +293,7 @@ extern "C" int bq_msolver_destroy(bq_msolver *m) {
     hipSetDevice(m->p->ctx->device);
     (void)bq_ctx_sync(m->p->ctx);
     for (void *ptr : {(void *)m->ql, (void *)m->sgn, (void *)m->W, (void *)m->out, (void *)m->slab, (void *)m->epi, (void *)m->scs, (void *)m->pos,
-                      (void *)m->nlive})
+                      (void *)m->nlive, (void *)m->al_cols})
         if (ptr) hipFree(ptr);
     if (m->nlive_host) {
         hipHostFree(m->nlive_host);
@@ -269,6 +332,20 @@ static void fill_epi(bq_msolver *m, int c, int do_update, bq_epilogue &e) {
 
 // the device epilogue table: the records' buffers may have been re-allocated by a run with more steps
 static int upload_epi(bq_msolver *m) {
+    if (m->al) {
+        std::vector<bq_epilogue> h((size_t)m->k);
+        std::vector<bq_al_col> cols((size_t)m->k);
+        for (int c = 0; c < m->k; ++c) {
+            const double *sgn = m->sgn ? m->sgn + c * m->ldw : nullptr;
+            h[c] = bq_al_epilogue(m->cls[c]);   // q: the column's own (V.q, bq_msolver_create_al)
+            h[c].sgn = sgn;
+            cols[c] = bq_al_col{m->cls[c]->al->V, m->cls[c]->sc, sgn};
+        }
+        BQ_HIP(hipMemcpyAsync(m->epi, h.data(), sizeof(bq_epilogue) * h.size(), hipMemcpyHostToDevice, m->p->ctx->stream));
+        BQ_HIP(hipMemcpyAsync(m->al_cols, cols.data(), sizeof(bq_al_col) * cols.size(), hipMemcpyHostToDevice, m->p->ctx->stream));
+        BQ_SYNC(m->p->ctx);   // h, cols go out of scope
+        return BQ_OK;
+    }
     std::vector<bq_epilogue> h(2 * (size_t)m->k);
     for (int c = 0; c < m->k; ++c) {
         fill_epi(m, c, 0, h[c]);
@@ -315,6 +392,62 @@ static int msolver_check(bq_problem *p, int kind, int k, const double *Y, const 
     return BQ_OK;
 }
 
+// everything of a batched solver but its columns' solvers (m->cls, m->k, m->ldw, m->wide, m->plan are set): the per-column labels or
+// linear terms (both null: none), the product's W / OUT / slab, the tables.  The caller destroys m on failure.
+static int msolver_alloc(bq_msolver *m, const double *Y, const double *QL) {
+    bq_problem *p = m->p;
+    bq_ctx *c = p->ctx;
+    const int k = m->k;
+    const bool wide = m->wide;
+    const bq_pairs_plan *plan = m->plan;
+    const int slots = (int)bq_round_up(k, msolver_ck(m));
+    // the per-column host array and its device copy: the labels (k x n -> sgn, stride ldw) or the linear terms (k x 2n -> ql, stride ldN)
+    const double *col_src = QL ? QL : Y;
+    double **col_dev = QL ? &m->ql : &m->sgn;
+    const int64_t col_len = QL ? p->N : p->n, col_ld = QL ? p->ldN : m->ldw;
+    hipError_t e = col_src ? hipMalloc(col_dev, sizeof(double) * col_ld * k) : hipSuccess;
+    if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
+    if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
+    const int64_t slab_len = plan ? bq_pairs_slab_len(plan) : wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb);
+    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * slab_len);
+    if (e == hipSuccess) e = hipMalloc(&m->epi, sizeof(bq_epilogue) * 2 * k);
+    if (e == hipSuccess && m->al) e = hipMalloc(&m->al_cols, sizeof(bq_al_col) * k);
+    if (e == hipSuccess) e = hipMalloc(&m->scs, sizeof(bq_scal *) * k);
+    if (e == hipSuccess) e = hipMalloc(&m->pos, sizeof(int) * k);
+    if (e == hipSuccess) e = hipMalloc(&m->nlive, sizeof(int));
+    if (e != hipSuccess) {
+        bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
+        return BQ_ERR_NOMEM;
+    }
+    std::vector<bq_scal *> scs(k);
+    std::vector<int> pos(k);
+    for (int cl = 0; cl < k; ++cl) {
+        scs[cl] = m->cls[cl]->sc;
+        pos[cl] = cl;
+    }
+    hipStream_t st = c->stream;
+    if (col_src) e = hipMemsetAsync(*col_dev, 0, sizeof(double) * col_ld * k, st);
+    if (e == hipSuccess) e = hipMemsetAsync(m->W, 0, sizeof(double) * m->ldw * slots, st);
+    if (e == hipSuccess) e = hipMemsetAsync(m->out, 0, sizeof(double) * m->ldw * slots, st);
+    if (e == hipSuccess && col_src) e = hipMemcpy2DAsync(*col_dev, sizeof(double) * col_ld, col_src, sizeof(double) * col_len,
+                                              sizeof(double) * col_len, k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->scs, scs.data(), sizeof(bq_scal *) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->pos, pos.data(), sizeof(int) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->nlive, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+        bq_set_error("batched solver setup failed: %s", hipGetErrorString(e));
+        return BQ_ERR_HIP;
+    }
+    if (hipHostMalloc((void **)&m->nlive_host, sizeof(int), hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&m->flag_event, hipEventDisableTiming) != hipSuccess) {
+        if (m->nlive_host) hipHostFree(m->nlive_host);
+        m->nlive_host = nullptr;
+        (void)hipGetLastError();
+    }
+    m->live_host = k;
+    return BQ_OK;
+}
+
 static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const double *ub, int64_t ub_ld, bool wide,
                           const double *x0, double eps, int64_t max_iter, double fw_t, bq_msolver **out, bq_pairs_plan *plan,
                           const double *QL) {
@@ -332,7 +465,6 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
     m->ldw = p->ld;   // (= p->ldN for BQ_SVC)
     m->wide = wide;
     m->plan = plan;
-    const int slots = (int)bq_round_up(k, msolver_ck(m));
     int rc = BQ_OK;
     for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
         bq_solver *s = nullptr;
@@ -344,49 +476,8 @@ static int msolver_create(bq_problem *p, int kind, int k, const double *Y, const
         return code;
     };
     if (rc != BQ_OK) return fail(rc);
-    // the per-column host array and its device copy: the labels (k x n -> sgn, stride ldw) or the linear terms (k x 2n -> ql, stride ldN)
-    const double *col_src = QL ? QL : Y;
-    double **col_dev = QL ? &m->ql : &m->sgn;
-    const int64_t col_len = QL ? p->N : p->n, col_ld = QL ? p->ldN : m->ldw;
-    hipError_t e = hipMalloc(col_dev, sizeof(double) * col_ld * k);
-    if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
-    if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
-    const int64_t slab_len = plan ? bq_pairs_slab_len(plan) : wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb);
-    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * slab_len);
-    if (e == hipSuccess) e = hipMalloc(&m->epi, sizeof(bq_epilogue) * 2 * k);
-    if (e == hipSuccess) e = hipMalloc(&m->scs, sizeof(bq_scal *) * k);
-    if (e == hipSuccess) e = hipMalloc(&m->pos, sizeof(int) * k);
-    if (e == hipSuccess) e = hipMalloc(&m->nlive, sizeof(int));
-    if (e != hipSuccess) {
-        bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
-        return fail(BQ_ERR_NOMEM);
-    }
-    std::vector<bq_scal *> scs(k);
-    std::vector<int> pos(k);
-    for (int cl = 0; cl < k; ++cl) {
-        scs[cl] = m->cls[cl]->sc;
-        pos[cl] = cl;
-    }
-    hipStream_t st = c->stream;
-    e = hipMemsetAsync(*col_dev, 0, sizeof(double) * col_ld * k, st);
-    if (e == hipSuccess) e = hipMemsetAsync(m->W, 0, sizeof(double) * m->ldw * slots, st);
-    if (e == hipSuccess) e = hipMemsetAsync(m->out, 0, sizeof(double) * m->ldw * slots, st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(*col_dev, sizeof(double) * col_ld, col_src, sizeof(double) * col_len,
-                                              sizeof(double) * col_len, k, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->scs, scs.data(), sizeof(bq_scal *) * k, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->pos, pos.data(), sizeof(int) * k, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->nlive, &k, sizeof(int), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-        bq_set_error("batched solver setup failed: %s", hipGetErrorString(e));
-        return fail(BQ_ERR_HIP);
-    }
-    if (hipHostMalloc((void **)&m->nlive_host, sizeof(int), hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&m->flag_event, hipEventDisableTiming) != hipSuccess) {
-        if (m->nlive_host) hipHostFree(m->nlive_host);
-        m->nlive_host = nullptr;
-        (void)hipGetLastError();
-    }
-    m->live_host = k;
+    rc = msolver_alloc(m, Y, QL);
+    if (rc != BQ_OK) return fail(rc);
     rc = upload_epi(m);
     if (rc != BQ_OK) return fail(rc);
     *out = m;
@@ -446,6 +537,55 @@ extern "C" int bq_msolver_create_svr_boxes(bq_problem *p, int kind, int k, const
     }
     BQ_TRY(msolver_create(p, kind, k, nullptr, UB, p->N, true, x0, eps, max_iter, fw_t, out, nullptr, QL));
     (*out)->svr_boxes = true;
+    return BQ_OK;
+}
+
+extern "C" int bq_msolver_create_al(bq_problem *p, const bq_al_params *prm, int k, const double *Y, const double *QL,
+                                    const double *a_eq, int64_t a_ld, const double *lb, const double *ub, const double *x0,
+                                    const double *dual0, bq_msolver **out) {
+    BQ_ARG(p && prm && x0 && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->kernel >= 0 && (p->structure == BQ_SVC || p->structure == BQ_SVR),
+           "the batched augmented-Lagrangian solver takes a kernel-built SVC or SVR problem");
+    if (p->structure == BQ_SVC) BQ_ARG(Y != nullptr && QL == nullptr, "a BQ_SVC problem takes the labels Y and no linear terms");
+    else BQ_ARG(Y == nullptr, "a BQ_SVR problem takes no labels");
+    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
+        bq_set_error("the batched solver needs a single-rank context and a resident packed panel (not streamed, not full rows)");
+        return BQ_ERR_BADARG;
+    }
+    BQ_ARG(prm->momentum_type != BQ_MOM_NESTEROV, "Nesterov momentum is not batched: one bq_al_solver_create per column");
+    BQ_ARG(a_eq == nullptr || a_ld == 0 || a_ld == p->N, "a_ld is 0 (one equality row for every column) or N (one per column)");
+    if (Y)
+        for (int64_t i = 0; i < (int64_t)k * p->n; ++i) BQ_ARG(Y[i] == 1.0 || Y[i] == -1.0, "labels must be +1 or -1");
+    if (QL)
+        for (int64_t i = 0; i < (int64_t)k * p->N; ++i) BQ_ARG(std::isfinite(QL[i]), "the linear terms must be finite");
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    bq_msolver *m = new bq_msolver();
+    m->p = p;
+    p->refs += 1;
+    m->al = true;
+    m->al_prm = *prm;
+    m->k = k;
+    m->ldw = p->ld;
+    const int64_t n_dual = (a_eq ? 1 : 0) + (lb ? p->N : 0) + (ub ? p->N : 0);
+    int rc = BQ_OK;
+    for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
+        bq_solver *s = nullptr;   // the rule's parameters are checked here, as for a single solver
+        rc = bq_al_solver_create(p, prm, a_eq ? a_eq + cl * a_ld : nullptr, lb, ub, x0 + (int64_t)cl * p->N,
+                                 dual0 && n_dual > 0 ? dual0 + cl * n_dual : nullptr, &s);
+        if (rc == BQ_OK) m->cls.push_back(s);
+    }
+    if (rc == BQ_OK) rc = msolver_alloc(m, Y, QL);
+    if (rc == BQ_OK && m->ql)
+        for (int cl = 0; cl < k; ++cl) m->cls[cl]->al->V.q = m->ql + cl * p->ldN;   // not the solver's to free (as p->q)
+    if (rc == BQ_OK) rc = upload_epi(m);
+    if (rc != BQ_OK) {
+        bq_msolver_destroy(m);
+        return rc;
+    }
+    m->initialised = true;   // no start-up product: every iteration evaluates Q x afresh
+    *out = m;
     return BQ_OK;
 }
 
@@ -533,6 +673,31 @@ static int msolver_iterate(bq_msolver *m) {
     return BQ_OK;
 }
 
+// one iteration of every live augmented-Lagrangian column (the header comment); prep: the product's input is formed from x first
+// (the first iteration of a run; every iteration of BQ_SVR)
+static int msolver_al_iterate(bq_msolver *m, bool prep) {
+    bq_problem *p = m->p;
+    hipStream_t st = p->ctx->stream;
+    const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k), gridN((unsigned)((p->N + 255) / 256), (unsigned)m->k);
+    if (prep || p->structure == BQ_SVR) mal_prep_kernel<<<grid, 256, 0, st>>>(m->epi, m->pos, m->W, m->ldw);
+    BQ_HIP(hipGetLastError());
+    BQ_TRY(msolver_product(m, m->live_host));
+    mal_finish_kernel<<<grid, 256, 0, st>>>(m->epi, m->pos, m->out, m->ldw);
+    mlive_kernel<<<1, 64, 0, st>>>(m->scs, m->k, m->pos, m->nlive);
+    mal_update_kernel<<<gridN, 256, 0, st>>>(p->N, p->ldN, m->al_cols, m->al_prm, m->pos, m->W, m->ldw);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+// the end of a run of the augmented-Lagrangian batch: no column's stop test stays pending across the call (bq_al_flush)
+static int msolver_al_flush(bq_msolver *m) {
+    hipStream_t st = m->p->ctx->stream;
+    mal_flush_kernel<<<dim3((unsigned)((m->p->n + 255) / 256), (unsigned)m->k), 256, 0, st>>>(m->epi);
+    mlive_kernel<<<1, 64, 0, st>>>(m->scs, m->k, m->pos, m->nlive);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
 extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *stats, int64_t stats_cap, int64_t *n_stats,
                               int *status) {
     BQ_ARG(m && n_stats && status, "NULL argument");
@@ -573,7 +738,7 @@ extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *st
     poll = poll < 1 ? 1 : (poll > 64 ? 64 : poll);
     bool pending = false;
     for (int64_t it = 0; it < max_steps; ++it) {
-        BQ_TRY(msolver_iterate(m));
+        BQ_TRY(m->al ? msolver_al_iterate(m, it == 0) : msolver_iterate(m));
         if ((it + 1) % poll == 0 && it + 1 < max_steps) {
             if (m->nlive_host) {
                 if (pending) {
@@ -593,6 +758,7 @@ extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *st
             }
         }
     }
+    if (m->al) BQ_TRY(msolver_al_flush(m));
     int nl = 0;
     BQ_HIP(hipMemcpyAsync(&nl, m->nlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     for (int cl = 0; cl < m->k; ++cl) {

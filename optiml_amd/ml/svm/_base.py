@@ -181,19 +181,25 @@ class SVM(BaseEstimator, ABC):
                                         callback=hook, verbose=self.verbose).minimize()
         self.alphas_ = self.optimizer.x
 
-    def _run_lagrangian(self, primal, a, ub):
-        """svm/_base.py:674-723 (SVC) / :1188-1270 (SVR): augmented Lagrangian of the dual + a stochastic optimizer."""
-        import warnings
+    def _lagrangian(self, primal, a, ub):
+        """The objective and the optimizer of the augmented-Lagrangian branch as `_run_lagrangian` constructs them, not run: the
+        batched fits take every column's start point and multipliers from here."""
         if isinstance(self.learning_rate, str) or not self.learning_rate > 0:
             raise ValueError('the dual needs a numeric learning_rate > 0')
         n = primal.ndim
-        self.obj = AugmentedLagrangianQuadratic(primal=primal, A=a, b=None if a is None else np.zeros(1),
-                                                lb=np.zeros(n), ub=ub, rho=self.rho)
-        kw = dict(f=self.obj, tol=self.tol, step_size=self.learning_rate, epochs=self.max_iter,
+        obj = AugmentedLagrangianQuadratic(primal=primal, A=a, b=None if a is None else np.zeros(1),
+                                           lb=np.zeros(n), ub=ub, rho=self.rho)
+        kw = dict(f=obj, tol=self.tol, step_size=self.learning_rate, epochs=self.max_iter,
                   random_state=self.random_state, callback=self._store_train_info, verbose=self.verbose)
         if issubclass(self.optimizer, StochasticMomentumOptimizer):
             kw.update(momentum_type=self.momentum_type, momentum=self.momentum)
-        self.optimizer = self.optimizer(**kw).minimize()
+        return obj, self.optimizer(**kw)
+
+    def _run_lagrangian(self, primal, a, ub):
+        """svm/_base.py:674-723 (SVC) / :1188-1270 (SVR): augmented Lagrangian of the dual + a stochastic optimizer."""
+        import warnings
+        self.obj, opt = self._lagrangian(primal, a, ub)
+        self.optimizer = opt.minimize()
         if self.optimizer.status == 'stopped':
             warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
         self.alphas_ = self.optimizer.x

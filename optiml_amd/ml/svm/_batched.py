@@ -1,8 +1,11 @@
 """What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`, `SVRGridSearchCV`): the
-device solver of many columns on one Gram panel, the one-off multi-column products, the device memory budget of a solve, and the
-way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
+device solver of many columns on one Gram panel (`_DeviceMultiSolver`: ProjectedGradient / FrankWolfe; `_DeviceALSolver`: the
+augmented-Lagrangian dual with the first-order rules), the one-off multi-column products, the device memory budget of a solve, and
+the way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
 """
 import ctypes as C
+import warnings
+from collections.abc import Iterable
 
 import numpy as np
 
@@ -10,7 +13,8 @@ from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import ProjectedGradient
-from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator
+from ...opti.unconstrained.stochastic import StochasticOptimizer, StochasticMomentumOptimizer
+from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator, ConvergenceWarning
 from .kernels import GaussianKernel, LinearKernel, PolyKernel, SigmoidKernel, gaussian
 from .losses import squared_hinge, squared_epsilon_insensitive
 
@@ -115,6 +119,72 @@ class _DeviceSVRSolver(_DeviceMultiSolver):
         _lib.check(self._lib.bq_msolver_svr_heldout(self._h, _lib.ptr(y), _lib.ptr(eps), _lib.ptr(b), n_sv.ctypes.data_as(i64),
                                                     _lib.ptr(sse), n_held.ctypes.data_as(i64)))
         return b, n_sv, sse, n_held
+
+
+class _DeviceALSolver(_DeviceMultiSolver):
+    """`bq_msolver_create_al`: k augmented-Lagrangian columns on one 'svc' or 'svr' problem.  prm: the rule's `_lib.AlParams`
+    (`StochasticOptimizer._params`); x0: k x N, required; Y: k x n labels +-1 ('svc') or QL: k x 2n linear terms ('svr'); a: the
+    equality row, None, N entries (one row for every column) or k x N (one per column); lb, ub: N each or None, shared; dual0:
+    k x n_dual or None (zeros).  `get(c, _lib.GET_DUAL)` has `n_dual` entries, every other vector N."""
+
+    def __init__(self, problem, prm, x0, Y=None, QL=None, a=None, lb=None, ub=None, dual0=None):
+        self._lib = _lib.load()
+        x0 = np.ascontiguousarray(x0, dtype=float)
+        self.k, self.n = x0.shape
+        self._h = C.c_void_p()
+        k, N = self.k, self.n
+        vec = lambda v, size, name: None if v is None else _lib.as_f64(v, size, name)   # noqa: E731
+        per_column = a is not None and np.ndim(a) == 2
+        Y = vec(Y, k * problem.dims()[1], 'Y')
+        QL, a = vec(QL, k * N, 'QL'), vec(a, k * N if per_column else N, 'A')
+        lb, ub = vec(lb, N, 'lb'), vec(ub, N, 'ub')
+        self.n_dual = (a is not None) + N * ((lb is not None) + (ub is not None))
+        dual0 = None if dual0 is None or self.n_dual == 0 else _lib.as_f64(dual0, k * self.n_dual, 'dual_x')
+        _lib.check(self._lib.bq_msolver_create_al(problem.handle, C.byref(prm), k, _lib.ptr(Y), _lib.ptr(QL), _lib.ptr(a),
+                                                  N if per_column else 0, _lib.ptr(lb), _lib.ptr(ub), _lib.ptr(x0),
+                                                  _lib.ptr(dual0), C.byref(self._h)))
+
+    def get(self, c, what):
+        out = np.empty(self.n_dual if what == _lib.GET_DUAL else self.n)
+        if out.size:
+            _lib.check(self._lib.bq_msolver_get(self._h, c, what, _lib.ptr(out)))
+        return out
+
+
+def solve_batched_al(solver, chunk=256):
+    """Run a `_DeviceALSolver` to the end and close it: per column a dict as a single `StochasticOptimizer.minimize` ends (rows:
+    the iteration records, status, iter, f_x; x: the current point, past_x: the point of the last record, g, step, dual)."""
+    try:
+        rows = [[] for _ in range(solver.k)]
+        status = ['unknown'] * solver.k
+        while 'unknown' in status:
+            recs, status = solver.run(chunk)
+            for c in range(solver.k):
+                rows[c].append(recs[c])
+        out = []
+        for c in range(solver.k):
+            it, st, f = solver.state(c)
+            out.append(dict(rows=np.concatenate(rows[c]), status=st, iter=it, f_x=f, x=solver.get(c, _lib.GET_X_NOW),
+                            past_x=solver.get(c, _lib.GET_X), g=solver.get(c, _lib.GET_G), step=solver.get(c, _lib.GET_D),
+                            dual=solver.get(c, _lib.GET_DUAL)))
+        return out
+    finally:
+        solver.close()
+
+
+def uses_batched_lagrangian(est, losses, world, ndim=None):
+    """What `uses_batched_lagrangian_path` (multiclass.py) and `uses_batched_lagrangian_svr_path` (multioutput.py) share: `est`'s
+    configuration takes the augmented-Lagrangian branch of its `fit` (dual, a `StochasticOptimizer`, a loss of `losses`) in the form
+    `bq_msolver_create_al` batches: momentum 'none' or 'polyak' and constant (Nesterov momentum and schedules run one fit per
+    column), a resident panel ('f64' / 'f32'), a single-rank context (`world` ranks) and, where the dual's size `ndim` is given,
+    more than 3 variables (with <= 3 the optimizer keeps per-iteration x histories and runs step by step)."""
+    opt = est.optimizer
+    if not (est.dual and isinstance(opt, type) and issubclass(opt, StochasticOptimizer)):
+        return False
+    if issubclass(opt, StochasticMomentumOptimizer) and isinstance(est.momentum, Iterable):
+        return False
+    return bool(est.momentum_type in ('none', 'polyak') and est.loss in losses and est.storage in ('f64', 'f32') and
+                int(world) == 1 and (ndim is None or int(ndim) > 3))
 
 
 def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None, before_close=None,
@@ -233,10 +303,15 @@ def fitted_svc(est, quad, r, X, y, pos=None):
     opt.status, opt.f_x, opt.x, opt.g_x = r['status'], r['f_x'], x, g
     est.train_loss_history = [float(f) for f in r['rows']['f']]
     est.optimizer = opt
+    return _svc_attributes(est, X, y)
+
+
+def _svc_attributes(est, X, y):
+    """What SVC.fit derives from `est.optimizer.x` (y: +-1) but the intercept; returns the support mask."""
     est.classes_ = np.array([0, 1])   # OneVsRestClassifier and OneVsOneClassifier fit each SVC on 0 / 1 labels
-    est.alphas_ = opt.x
+    est.alphas_ = est.optimizer.x
     sv = est.alphas_ > 1e-6
-    est.support_ = np.arange(n)[sv]
+    est.support_ = np.arange(len(y))[sv]
     est.support_vectors_ = X[sv]
     est.dual_coef_ = est.alphas_[sv] * y[sv]
     if isinstance(est.kernel, LinearKernel):
@@ -304,15 +379,68 @@ def fitted_svr(est, quad, r, X, y):
     est.train_loss_history = [float(f) for f in r['rows']['f']]
     est.optimizer = opt
     est.obj = quad
-    est.alphas_ = opt.x
+    return _svr_attributes(est, X, y)
+
+
+def _svr_attributes(est, X, y):
+    """What SVR.fit derives from `est.optimizer.x` (2n) but the intercept; returns the support mask."""
+    est.alphas_ = est.optimizer.x
     alphas_p, alphas_n = np.split(est.alphas_, 2)
     sv = np.logical_or(alphas_p > 1e-6, alphas_n > 1e-6)
-    est.support_ = np.arange(n)[sv]
+    est.support_ = np.arange(len(y))[sv]
     est.support_vectors_ = X[sv]
     est.dual_coef_ = alphas_p[sv] - alphas_n[sv]
     if isinstance(est.kernel, LinearKernel):
         est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
     return sv
+
+
+class ClassQuadratic(TargetQuadratic):
+    """One class's dual on the panel of a shared 'svc' `KernelQuadratic`: the same X, kernel, q and device problem, its own labels
+    y_c, so Q_c = diag(y_c) P diag(y_c) (+ diag I).  The device problem applies the shared labels y_0: with s = y_c o y_0,
+    Q_c x = s o (Q_0 (s o x)) — the diagonal term passes through, s o s = 1.  `Q` and `gram` read `self.y`, the class's."""
+
+    def __init__(self, shared, y):
+        TargetQuadratic.__init__(self, shared, shared.q)
+        self.y = np.ascontiguousarray(y, dtype=float)
+        if self.y.shape != shared.y.shape:
+            raise ValueError('labels size does not match with Q')
+        self._flip = self.y * shared.y
+
+    def function_jacobian(self, x):
+        x = np.asarray(x, dtype=float)
+        Qx = self._flip * self.device_problem().matvec(self._flip * x)
+        return 0.5 * float(x @ Qx) + float(self.q @ x), Qx + self.q
+
+
+def lagrangian_columns(ests, views, a, ub):
+    """Per column the objective and the optimizer of `SVM._lagrangian` on its view of the shared panel, constructed in column order
+    (a loop of single fits draws its start points in that order), and the batched solver's x0 (k x N) and multipliers (k x n_dual).
+    a: one equality row per column, or None."""
+    pairs = [est._lagrangian(view, None if a is None else a[c], ub) for c, (est, view) in enumerate(zip(ests, views))]
+    x0 = np.stack([opt.x for _, opt in pairs])
+    dual0 = np.stack([obj.dual_x for obj, _ in pairs])
+    return pairs, x0, dual0
+
+
+def fitted_lagrangian(est, obj, opt, r):
+    """Make `est.obj` / `est.optimizer` / `est.train_loss_history` / `est.alphas_` what `SVM._run_lagrangian` leaves, from the
+    column's objective and optimizer (`lagrangian_columns`) and its result `r` of `solve_batched_al`; warns as it does."""
+    rows = r['rows']
+    if len(rows):
+        opt.iter = int(rows[-1]['iter'])
+        opt.epoch = opt.iter + 1   # full batch: one epoch per evaluation
+        opt.f_x, opt.primal_f_x = float(rows[-1]['f']), float(rows[-1]['r1'])
+        opt.dgap = abs((opt.primal_f_x - opt.f_x) / max(abs(opt.primal_f_x), 1))
+    opt.status = r['status']
+    opt.x, opt.g_x, opt.step, opt.past_x = r['x'], r['g'], r['step'], r['past_x']
+    obj.past_dual_x = obj.dual_x.copy()
+    obj.dual_x = r['dual']
+    est.train_loss_history = [float(f) for f in rows['r1']]   # the primal values, as `_store_train_info` keeps them
+    est.obj, est.optimizer = obj, opt
+    if opt.status == 'stopped':
+        warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
+    est.alphas_ = opt.x
 
 
 def svr_intercept(y, u, sv, epsilon):

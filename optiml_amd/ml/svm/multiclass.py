@@ -7,19 +7,24 @@ per iteration for every 4 classes still running (bq_symm.hip) instead of once pe
 products in one multi-column product (`bq_problem_gram_matmat`).  Each class follows the iteration of `SVC.fit` with the same
 optimizer — same formulas, thresholds, stop tests and records — and its iterates have the same bits whatever the other classes do.
 
-Configurations the batched path does not cover (see `uses_batched_path`) fit the k binary problems one after another with `SVC`:
-exactly what `OneVsRestClassifier(SVC)` does.
+The augmented-Lagrangian branch of `SVC.fit` (a stochastic optimizer: the unregularised intercept's equality row, the squared
+hinge) is batched the same way (`uses_batched_lagrangian_path`, `bq_msolver_create_al`): every class is the solver of the single fit,
+started where that fit starts, and equals it to rounding — the 4-column product sums in another order than the one-column one.
+
+Configurations neither batched path covers fit the k binary problems one after another with `SVC`: exactly what
+`OneVsRestClassifier(SVC)` does.
 """
 import numpy as np
 
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
-from ._batched import (DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _gram_matmat, fitted_svc, intercept, solve_batched,
-                       solver_kind, uses_batched_decision)
-from .losses import Hinge
+from ._batched import (ClassQuadratic, DecisionBatch, _DeviceALSolver, _DeviceMultiSolver, _MultiClassSVC, _gram_matmat,
+                       _svc_attributes, fitted_lagrangian, fitted_svc, intercept, lagrangian_columns, solve_batched,
+                       solve_batched_al, solver_kind, uses_batched_decision, uses_batched_lagrangian)
+from .losses import Hinge, SquaredHinge
 
-__all__ = ['OneVsRestSVC', 'uses_batched_path', 'binarize']
+__all__ = ['OneVsRestSVC', 'uses_batched_path', 'uses_batched_lagrangian_path', 'binarize']
 
 
 def uses_batched_path(svc, world):
@@ -29,6 +34,14 @@ def uses_batched_path(svc, world):
     opt = svc.optimizer
     return bool(svc.dual and svc.reg_intercept and svc.loss == Hinge and isinstance(opt, type) and
                 issubclass(opt, (ProjectedGradient, FrankWolfe)) and svc.storage in ('f64', 'f32') and int(world) == 1)
+
+
+def uses_batched_lagrangian_path(svc, world, ndim=None):
+    """True when `OneVsRestSVC` solves the classes of `svc`'s configuration together on one panel by the batched
+    augmented-Lagrangian solver: `dual`, a `StochasticOptimizer` subclass, `momentum_type` 'none' or 'polyak' (constant momentum),
+    the hinge or squared hinge loss, a resident panel ('f64' / 'f32'), a single-rank context (`world` ranks), either intercept;
+    ndim (the number of samples, when given): more than 3, as the optimizers run step by step on smaller duals."""
+    return uses_batched_lagrangian(svc, (Hinge, SquaredHinge), world, ndim)
 
 
 def binarize(y):
@@ -46,7 +59,8 @@ def binarize(y):
 class OneVsRestSVC(_MultiClassSVC):
     """One-vs-rest multi-class SVC; constructor arguments and their checks are SVC's.
 
-    After `fit`: `classes_`, `estimators_` (one fitted SVC per class — per binary problem with two classes), and
+    After `fit`: `classes_`, `estimators_` (one fitted SVC per class — per binary problem with two classes), `batched_` (the
+    classes were solved together) with `lagrangian_` (by the augmented-Lagrangian solver, not ProjectedGradient / FrankWolfe), and
     `decision_function` (m x k; 1-D with two classes), `predict`, `score` as sklearn's OneVsRestClassifier(SVC(**kw)).
 
     `batched_decision_`: True when `decision_function` and `predict` take every class's values from one fused pass over the kernel
@@ -58,13 +72,14 @@ class OneVsRestSVC(_MultiClassSVC):
         X = np.ascontiguousarray(X, dtype=float)
         self.classes_, Y = binarize(y)
         proto = self._prototype()
-        self.batched_ = uses_batched_path(proto, get_context().world)
+        self.lagrangian_ = uses_batched_lagrangian_path(proto, get_context().world, X.shape[0])
+        self.batched_ = self.lagrangian_ or uses_batched_path(proto, get_context().world)
         self.batched_decision_ = uses_batched_decision(proto.kernel, len(Y), get_context().world, self.batched_)
         self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, (Yc > 0).astype(int)) for Yc in Y]
             return self
-        self.estimators_ = self._fit_batched(proto, X, Y)
+        self.estimators_ = (self._fit_lagrangian if self.lagrangian_ else self._fit_batched)(proto, X, Y)
         return self
 
     def _fit_batched(self, proto, X, Y):
@@ -78,13 +93,39 @@ class OneVsRestSVC(_MultiClassSVC):
         # the solver is created here, as OneVsOneSVC creates its pair solver, and handed over: solve_batched's own eps / max_iter
         # are not read on this call
         res = solve_batched(dev, kind, Y, ub, solver=_DeviceMultiSolver(dev, kind, Y, ub, 1e-6, proto.max_iter))
-        ests, masks, coefs = [], [], []
-        for c in range(k):
-            est = self._prototype()
-            sv = fitted_svc(est, obj, res[c], X, Y[c])
+        return self._finish(proto, obj, X, Y, [self._prototype() for _ in range(k)],
+                            lambda c, est: fitted_svc(est, obj, res[c], X, Y[c]))
+
+    def _fit_lagrangian(self, proto, X, Y):
+        """SVC.fit's stochastic branch for every class on one panel: its KernelQuadratic (diag = 1/(2C) for the squared hinge,
+        rank_one = reg_intercept), per class the objective and optimizer it constructs, one batched solve."""
+        k, n = Y.shape
+        sq = proto.loss == SquaredHinge
+        obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Y[0], storage=proto.storage,
+                              diag=1. / (2 * proto.C) if sq else 0., rank_one=proto.reg_intercept,
+                              tune_placement=proto._streams_panel(), expected_products=proto.max_iter * ((k + 3) // 4))
+        dev = obj.device_problem()
+        ests = [self._prototype() for _ in range(k)]
+        ub = None if sq else np.ones(n) * proto.C
+        a = None if proto.reg_intercept else Y
+        cols, x0, dual0 = lagrangian_columns(ests, [ClassQuadratic(obj, Yc) for Yc in Y], a, ub)
+        res = solve_batched_al(_DeviceALSolver(dev, cols[0][1]._params(), x0, Y=Y, a=a, lb=np.zeros(n), ub=ub, dual0=dual0))
+
+        def fitted(c, est):
+            fitted_lagrangian(est, *cols[c], res[c])
+            return _svc_attributes(est, X, Y[c])
+        return self._finish(proto, obj, X, Y, ests, fitted)
+
+    def _finish(self, proto, obj, X, Y, ests, fitted):
+        """The estimators from their columns' results (`fitted(c, est)`: the support mask), the intercepts from one multi-column
+        product, the decision batch."""
+        k, n = Y.shape
+        dev = obj.device_problem()
+        masks, coefs = [], []
+        for c, est in enumerate(ests):
+            sv = fitted(c, est)
             w = np.zeros(n)
             w[sv] = est.dual_coef_
-            ests.append(est)
             masks.append(sv)
             coefs.append(w)
             if self.verbose:

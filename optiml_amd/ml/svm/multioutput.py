@@ -6,19 +6,25 @@ iteration for every 4 targets still running (bq_symm.hip) instead of once per ta
 one multi-column product (`bq_problem_gram_matmat`).  Each target follows the iteration of `SVR.fit` with the same optimizer — same
 formulas, thresholds, stop tests and records — and its iterates have the same bits whatever the other targets do.
 
-Configurations the batched path does not cover (see `uses_batched_svr_path`) fit the k targets one after another with `SVR`:
-exactly what `MultiOutputRegressor(SVR)` does.
+The augmented-Lagrangian branch of `SVR.fit` (a stochastic optimizer: the unregularised intercept's equality row, the squared
+epsilon-insensitive loss) is batched the same way (`uses_batched_lagrangian_svr_path`, `bq_msolver_create_al`): every target is the
+solver of the single fit, started where that fit starts, and equals it to rounding — the 4-column product sums in another order
+than the one-column one.
+
+Configurations neither batched path covers fit the k targets one after another with `SVR`: exactly what
+`MultiOutputRegressor(SVR)` does.
 """
 import numpy as np
 
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
-from ._batched import (DecisionBatch, _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat, fitted_svr, solve_batched, solver_kind,
-                       svr_intercept, uses_batched_decision)
-from .losses import EpsilonInsensitive
+from ._batched import (DecisionBatch, TargetQuadratic, _DeviceALSolver, _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat,
+                       _svr_attributes, fitted_lagrangian, fitted_svr, lagrangian_columns, solve_batched, solve_batched_al,
+                       solver_kind, svr_intercept, uses_batched_decision, uses_batched_lagrangian)
+from .losses import EpsilonInsensitive, SquaredEpsilonInsensitive
 
-__all__ = ['MultiOutputSVR', 'uses_batched_svr_path']
+__all__ = ['MultiOutputSVR', 'uses_batched_svr_path', 'uses_batched_lagrangian_svr_path']
 
 
 def uses_batched_svr_path(svr, world):
@@ -30,10 +36,20 @@ def uses_batched_svr_path(svr, world):
                 issubclass(opt, (ProjectedGradient, FrankWolfe)) and svr.storage in ('f64', 'f32') and int(world) == 1)
 
 
+def uses_batched_lagrangian_svr_path(svr, world, ndim=None):
+    """True when `MultiOutputSVR` solves the targets of `svr`'s configuration together on one panel by the batched
+    augmented-Lagrangian solver: `dual`, a `StochasticOptimizer` subclass, `momentum_type` 'none' or 'polyak' (constant momentum),
+    the epsilon-insensitive or squared epsilon-insensitive loss, a resident panel ('f64' / 'f32'), a single-rank context (`world`
+    ranks), either intercept; ndim (the dual's 2n variables, when given): more than 3, as the optimizers run step by step on
+    smaller duals."""
+    return uses_batched_lagrangian(svr, (EpsilonInsensitive, SquaredEpsilonInsensitive), world, ndim)
+
+
 class MultiOutputSVR(_MultiTargetSVR):
     """Multi-output SVR; constructor arguments and their checks are SVR's.
 
-    After `fit(X, Y)`, Y of shape n x k: `estimators_` (one fitted SVR per target), `batched_` (which path ran), and `predict`
+    After `fit(X, Y)`, Y of shape n x k: `estimators_` (one fitted SVR per target), `batched_` (the targets were solved together)
+    with `lagrangian_` (by the augmented-Lagrangian solver, not ProjectedGradient / FrankWolfe), and `predict`
     (m x k), `score` as sklearn's MultiOutputRegressor(SVR(**kw)).  On the batched path the estimators share one device panel;
     each one's `obj` / `optimizer.f` is its own target's dual on it (`TargetQuadratic`).
 
@@ -48,13 +64,14 @@ class MultiOutputSVR(_MultiTargetSVR):
         if Y.ndim == 1:
             raise ValueError('y must have at least two dimensions for multi-output regression but has only one.')
         proto = self._prototype()
-        self.batched_ = uses_batched_svr_path(proto, get_context().world)
+        self.lagrangian_ = uses_batched_lagrangian_svr_path(proto, get_context().world, 2 * X.shape[0])
+        self.batched_ = self.lagrangian_ or uses_batched_svr_path(proto, get_context().world)
         self.batched_decision_ = uses_batched_decision(proto.kernel, Y.shape[1], get_context().world, self.batched_)
         self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, Y[:, c]) for c in range(Y.shape[1])]
             return self
-        self.estimators_ = self._fit_batched(proto, X, np.ascontiguousarray(Y.T))
+        self.estimators_ = (self._fit_lagrangian if self.lagrangian_ else self._fit_batched)(proto, X, np.ascontiguousarray(Y.T))
         return self
 
     def _fit_batched(self, proto, X, Y):
@@ -67,13 +84,40 @@ class MultiOutputSVR(_MultiTargetSVR):
         dev = obj.device_problem()
         kind = solver_kind(proto.optimizer)
         res = solve_batched(dev, kind, QL, ub, solver=_DeviceSVRSolver(dev, kind, QL, ub, 1e-6, proto.max_iter))
-        ests, masks, coefs = [], [], []
-        for c in range(k):
-            est = self._prototype()
-            sv = fitted_svr(est, obj, res[c], X, Y[c])
+        return self._finish(proto, obj, X, Y, [self._prototype() for _ in range(k)],
+                            lambda c, est: fitted_svr(est, obj, res[c], X, Y[c]))
+
+    def _fit_lagrangian(self, proto, X, Y):
+        """SVR.fit's stochastic branch for every target on one panel: its KernelQuadratic (diag = 1/(2C) for the squared loss,
+        rank_one = reg_intercept), per target the objective and optimizer it constructs, one batched solve."""
+        k, n = Y.shape
+        sq = proto.loss == SquaredEpsilonInsensitive
+        QL = np.hstack((-Y, Y)) + proto.epsilon   # row c: SVR.fit's q of target c
+        obj = KernelQuadratic(X, QL[0], 'svr', proto.kernel, storage=proto.storage, diag=1. / (2 * proto.C) if sq else 0.,
+                              rank_one=proto.reg_intercept, tune_placement=proto._streams_panel(),
+                              expected_products=proto.max_iter * ((k + 3) // 4))
+        dev = obj.device_problem()
+        ests = [self._prototype() for _ in range(k)]
+        ub = None if sq else np.ones(2 * n) * proto.C
+        e = None if proto.reg_intercept else np.hstack((np.ones(n), -np.ones(n)))   # equality row, the same for every target
+        cols, x0, dual0 = lagrangian_columns(ests, [TargetQuadratic(obj, q) for q in QL], None if e is None else [e] * k, ub)
+        res = solve_batched_al(_DeviceALSolver(dev, cols[0][1]._params(), x0, QL=QL, a=e, lb=np.zeros(2 * n), ub=ub, dual0=dual0))
+
+        def fitted(c, est):
+            fitted_lagrangian(est, *cols[c], res[c])
+            return _svr_attributes(est, X, Y[c])
+        return self._finish(proto, obj, X, Y, ests, fitted)
+
+    def _finish(self, proto, obj, X, Y, ests, fitted):
+        """The estimators from their columns' results (`fitted(c, est)`: the support mask), the intercepts from one multi-column
+        product, the decision batch."""
+        k, n = Y.shape
+        dev = obj.device_problem()
+        masks, coefs = [], []
+        for c, est in enumerate(ests):
+            sv = fitted(c, est)
             w = np.zeros(n)
             w[sv] = est.dual_coef_
-            ests.append(est)
             masks.append(sv)
             coefs.append(w)
             if self.verbose:
