@@ -54,6 +54,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_svr was added) */
 /* (still 3: bq_msolver_create_svr_boxes and bq_msolver_svr_heldout were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_al was added; nothing existing changed) */
+/* (still 3: bq_platt_fit and bq_msolver_svc_heldout were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -385,6 +386,34 @@ int bq_msolver_create_svr_boxes(bq_problem *p, int kind, int k, const double *QL
  * intercept = sse = NaN (SVR.fit divides by zero there). */
 int bq_msolver_svr_heldout(bq_msolver *s, const double *y, const double *epsilon, double *intercept, int64_t *n_sv, double *sse,
                            int64_t *n_held);
+
+/* ---- Platt calibration (sklearn CalibratedClassifierCV(method='sigmoid'): calibration.py _sigmoid_calibration, once per (fold,
+ * class)) -----------------------------------------------------------------------------------------------------------------------
+ * bq_platt_fit: ncal sigmoid fits p = 1 / (1 + exp(A f + B)) in one launch, one workgroup each.  D, L: ncal x n host arrays;
+ * D[j] the decision values of calibrator j, L[j] its labels: > 0 positive, < 0 negative, 0 a row that is not in its sample and enters
+ * no sum.  The iteration is libsvm's sigmoid_train (Lin, Lin & Weng 2007): targets (N+ + 1) / (N+ + 2) and 1 / (N- + 2), start
+ * A = 0, B = log((N- + 1) / (N+ + 1)), Newton's direction with 1e-12 on the Hessian's diagonal, step halving while
+ * f_new >= f + 1e-4 step g'd down to a step of 1e-10, stop when both gradient entries are below 1e-5, at most 100 iterations.
+ * Per calibrator: A, B, iters (Newton steps taken), loss (the final value), n_pos, n_neg, flags (BQ_PLATT_*: libsvm's two
+ * warnings; the values at that point are returned).  A calibrator without a labelled row gets A = B = 0 and BQ_PLATT_EMPTY.
+ * Every sum has a fixed order and reads its own calibrator only: (A, B) have the same bits alone, at any position, in any batch.
+ * ncal < 1, n < 1 or a NULL pointer: BQ_ERR_BADARG. */
+#define BQ_PLATT_LINE_SEARCH 1 /* the line search failed (the step fell below 1e-10) */
+#define BQ_PLATT_MAX_ITER 2    /* the iteration cap was reached */
+#define BQ_PLATT_EMPTY 4       /* no labelled row */
+int bq_platt_fit(bq_ctx *ctx, int ncal, int64_t n, const double *D, const double *L, double *A, double *B, int *iters, double *loss,
+                 int64_t *n_pos, int64_t *n_neg, int *flags);
+/* Held-out decision values and Platt fits of the columns of a bq_msolver_create_boxes solver (any other solver: BQ_ERR_BADARG),
+ * from its state on the device, after any run.  cal_of: k ints, column c's calibrator in [0, ncal) or -1 for a column that feeds
+ * none (a fit on all the data).  Per column, with coef = x y on the support rows (x above 1e-6, SVC.fit's threshold) and u = K coef
+ * (one 16-column product per 16 columns):
+ *   n_sv       the support rows;        intercept  (sum over them of (y - u)) / n_sv, SVC.fit's order of operations (n_sv = 0: NaN)
+ * and on the column's held-out rows (UB[c][i] == 0) the decision value u + intercept and the label y go to row cal_of[c] of two
+ * zeroed ncal x n device buffers, on which bq_platt_fit's kernel runs: A, B, iters, loss, n_pos, n_neg, flags have ncal entries.
+ * Columns that share a calibrator must have disjoint held-out rows (else BQ_ERR_BADARG).  dec: NULL, or ncal x n, which receives
+ * the decision buffer (0 on the rows no column of the calibrator holds out). */
+int bq_msolver_svc_heldout(bq_msolver *s, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A, double *B,
+                           int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags, double *dec);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

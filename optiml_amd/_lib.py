@@ -31,6 +31,7 @@ MOM = {'none': 0, 'polyak': 1, 'nesterov': 2}
 PROF_MATVEC, PROF_GRAM, PROF_CHOL, PROF_EXCH, PROF_PCSHARD = range(5)
 COUNT_INNER, COUNT_MINRES, COUNT_REFACTOR, COUNT_REUSED, COUNT_NO_PRODUCT = range(5)
 STATE_X, STATE_G, STATE_MULT, STATE_MASKS = 1, 2, 4, 8
+PLATT_LINE_SEARCH, PLATT_MAX_ITER, PLATT_EMPTY = 1, 2, 4
 ABI_VERSION = 3
 
 
@@ -125,6 +126,9 @@ PROTOTYPES = {
     'bq_msolver_create_svr': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_msolver_create_svr_boxes': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_msolver_svr_heldout': (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(_i64), _dp, C.POINTER(_i64)]),
+    'bq_platt_fit': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, _ip, _dp, C.POINTER(_i64), C.POINTER(_i64), _ip]),
+    'bq_msolver_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp, C.POINTER(_i64),
+                                         C.POINTER(_i64), _ip, _dp]),
     'bq_msolver_create_pairs': (C.c_int, [_vp, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.c_double,
                                           C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),

@@ -360,6 +360,11 @@ typedef int (*bq_product_launch)(void *arg, const double *dW, int64_t ldw, doubl
 int bq_product_once(bq_problem *p, const char *name, int k, int64_t slots, int64_t slab_len, bool zero_out, const double *W,
                     double *out, bq_product_launch launch, void *arg);
 
+// bq_platt.hip: platt_fit_kernel on ncal rows of device decision values D and labels L (row stride n), one workgroup each; the
+// outputs are device arrays of ncal entries
+int bq_launch_platt(int ncal, int64_t n, const double *D, const double *L, double *A, double *B, int *iters, double *loss,
+                    long long *n_pos, long long *n_neg, int *flags, hipStream_t st);
+
 // bq_dense.hip: a dense host Hessian into the resident panel — packed lower tile rows when Q == Q' exactly (checked on the device
 // while uploading, agreed across ranks), else row blocks
 bool bq_dense_host_spot_symmetric(const double *Q, int64_t n);

@@ -43,6 +43,7 @@
 #include "bq_epilogue.h"
 
 #include <cmath>
+#include <new>
 #include <vector>
 
 struct bq_msolver {
@@ -50,6 +51,8 @@ struct bq_msolver {
     int kind = BQ_PG, k = 0;
     bool wide = false;   // bq_msolver_create_boxes / _svr_boxes: the 16-column product (bq_symmw.hip) for every pass
     bool svr_boxes = false;   // bq_msolver_create_svr_boxes: bq_msolver_svr_heldout may score it
+    bool svc_boxes = false;   // bq_msolver_create_boxes: bq_msolver_svc_heldout may calibrate it
+    std::vector<unsigned char> held;   // svc_boxes: k x n, 1 where UB is 0 (the column's held-out rows), as given at creation
     bq_pairs_plan *plan = nullptr;   // bq_msolver_create_pairs: the pair-routed product (bq_symmp.hip) for every pass
     int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ld >= nb * 256)
     std::vector<bq_solver *> cls;
@@ -232,6 +235,57 @@ __global__ __launch_bounds__(1024) void msvr_score_kernel(const bq_epilogue *__r
         n_sv[blockIdx.x] = nsv;
         sse[blockIdx.x] = sd[0];   // NaN with b
         n_held[blockIdx.x] = sc[0];
+    }
+}
+
+// bq_msolver_svc_heldout, column blockIdx.y: the coefficients of fitted_svc (svm/_batched.py), its threshold and its expression, to the
+// column's own slot (not pos[]: every column is scored, live or not)
+__global__ __launch_bounds__(256) void msvc_coef_kernel(const bq_epilogue *__restrict__ epi, double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const double x = e.x[i];
+    W[blockIdx.y * ldw + i] = x > 1e-6 ? x * e.sgn[i] : 0.0;
+}
+
+// bq_msolver_svc_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1, the support rows (x above 1e-6): S = sum (y - u),
+// n_sv, b = S / n_sv in intercept()'s order (svm/_batched.py), summed as msvr_score_kernel sums.  Pass 2, the held-out rows
+// (ub = 0): the decision value u + b and the label y to row cal_of[column] of D and L (row stride n; zeroed by the caller; the
+// columns of a calibrator hold out disjoint rows, so no two workgroups write one entry).  n_sv = 0: b = NaN.
+__global__ __launch_bounds__(1024) void msvc_heldout_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
+                                                            int64_t ldw, const int *__restrict__ cal_of, double *__restrict__ D,
+                                                            double *__restrict__ L, double *__restrict__ intercept,
+                                                            long long *__restrict__ n_sv) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_epilogue &e = epi[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = e.n;
+    double s = 0.0;
+    int cnt = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool sv = e.x[i] > 1e-6;
+        s += sv ? e.sgn[i] - u[i] : 0.0;
+        cnt += sv ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = cnt;
+    msvr_tree(sd, sc, tid);
+    const int nsv = sc[0];
+    const double b = nsv > 0 ? sd[0] / (double)nsv : NAN;
+    if (tid == 0) {
+        intercept[blockIdx.x] = b;
+        n_sv[blockIdx.x] = nsv;
+    }
+    const int cal = cal_of[blockIdx.x];
+    if (cal < 0) return;
+    double *d = D + (long long)cal * n, *l = L + (long long)cal * n;
+    for (long long i = tid; i < n; i += 1024) {
+        if (e.ub[i] == 0.0) {
+            d[i] = u[i] + b;
+            l[i] = e.sgn[i];
+        }
     }
 }
 
@@ -493,7 +547,19 @@ extern "C" int bq_msolver_create_boxes(bq_problem *p, int kind, int k, const dou
                                        double eps, int64_t max_iter, double fw_t, bq_msolver **out) {
     BQ_ARG(p && UB, "NULL argument");
     for (int64_t i = 0; i < (int64_t)k * p->n; ++i) BQ_ARG(UB[i] >= 0.0, "upper bounds must be >= 0 (lb = 0)");
-    return msolver_create(p, kind, k, Y, UB, p->n, true, x0, eps, max_iter, fw_t, out);
+    BQ_TRY(msolver_create(p, kind, k, Y, UB, p->n, true, x0, eps, max_iter, fw_t, out));
+    bq_msolver *m = *out;
+    try {
+        m->held.resize((size_t)k * (size_t)p->n);
+    } catch (const std::bad_alloc &) {   // no exception leaves the C ABI, and the solver does not outlive the failure
+        bq_msolver_destroy(m);
+        *out = nullptr;
+        bq_set_error("batched solver: no host memory for the held-out masks");
+        return BQ_ERR_NOMEM;
+    }
+    for (size_t i = 0; i < m->held.size(); ++i) m->held[i] = UB[i] == 0.0;
+    m->svc_boxes = true;
+    return BQ_OK;
 }
 
 extern "C" int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const int *cls_tiles, int m, const int *pairs,
@@ -637,6 +703,109 @@ extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const doub
     if (rc == BQ_OK) rc = bq_ctx_sync(c);   // y, epsilon, k and the results are the caller's and this frame's
     else (void)bq_ctx_sync(c);
     for (void *ptr : {(void *)dy, (void *)deps, (void *)db, (void *)dsse, (void *)dnsv, (void *)dnheld, (void *)count})
+        if (ptr) hipFree(ptr);
+    return rc;
+}
+
+extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A,
+                                      double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags,
+                                      double *dec) {
+    BQ_ARG(m && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
+    BQ_ARG(m->svc_boxes, "held-out calibration takes a solver of bq_msolver_create_boxes");
+    BQ_ARG(ncal >= 1, "ncal must be >= 1");
+    bq_problem *p = m->p;
+    bq_ctx *c = p->ctx;
+    const int k = m->k;
+    const int64_t n = p->n;
+    {   // the columns of a calibrator hold out disjoint rows: two columns may not write one entry of its sample
+        std::vector<std::vector<int>> cols((size_t)ncal);
+        for (int cl = 0; cl < k; ++cl) {
+            BQ_ARG(cal_of[cl] >= -1 && cal_of[cl] < ncal, "cal_of entries are -1 or a calibrator in [0, ncal)");
+            if (cal_of[cl] >= 0) cols[cal_of[cl]].push_back(cl);
+        }
+        std::vector<unsigned char> seen;
+        for (const std::vector<int> &cs : cols) {
+            if (cs.size() < 2) continue;
+            seen.assign((size_t)n, 0);
+            for (int cl : cs) {
+                const unsigned char *h = m->held.data() + (size_t)cl * (size_t)n;
+                for (int64_t i = 0; i < n; ++i) {
+                    BQ_ARG(!(h[i] && seen[i]), "columns that share a calibrator must have disjoint held-out rows");
+                    seen[i] |= h[i];
+                }
+            }
+        }
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t len = (size_t)ncal * (size_t)n;
+    double *dD = nullptr, *dL = nullptr, *db = nullptr, *dA = nullptr, *dB = nullptr, *dloss = nullptr;
+    long long *dnsv = nullptr, *dpos = nullptr, *dneg = nullptr;
+    int *dcal = nullptr, *diters = nullptr, *dflags = nullptr;
+    int *count = nullptr;   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    hipError_t e = hipMalloc(&dD, sizeof(double) * len);
+    if (e == hipSuccess) e = hipMalloc(&dL, sizeof(double) * len);
+    if (e == hipSuccess) e = hipMalloc(&db, sizeof(double) * k);
+    if (e == hipSuccess) e = hipMalloc(&dnsv, sizeof(long long) * k);
+    if (e == hipSuccess) e = hipMalloc(&dcal, sizeof(int) * k);
+    if (e == hipSuccess) e = hipMalloc(&dA, sizeof(double) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&dB, sizeof(double) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&dloss, sizeof(double) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&dpos, sizeof(long long) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&dneg, sizeof(long long) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&diters, sizeof(int) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&dflags, sizeof(int) * ncal);
+    if (e == hipSuccess) e = hipMalloc(&count, sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(dD, 0, sizeof(double) * len, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dL, 0, sizeof(double) * len, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dcal, cal_of, sizeof(int) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("held-out calibration setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) {
+        msvc_coef_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, m->W, m->ldw);
+        e = hipGetLastError();
+        if (e != hipSuccess) {
+            bq_set_error("held-out calibration: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    if (rc == BQ_OK) {
+        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+    }
+    if (rc == BQ_OK) {
+        msvc_heldout_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dcal, dD, dL, db, dnsv);
+        e = hipGetLastError();
+        if (e != hipSuccess) {
+            bq_set_error("held-out calibration: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    if (rc == BQ_OK) rc = bq_launch_platt(ncal, n, dD, dL, dA, dB, diters, dloss, dpos, dneg, dflags, st);
+    if (rc == BQ_OK) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
+        e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(A, dA, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(B, dB, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(loss, dloss, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_pos, dpos, sizeof(int64_t) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_neg, dneg, sizeof(int64_t) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(iters, diters, sizeof(int) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(flags, dflags, sizeof(int) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && dec) e = hipMemcpyAsync(dec, dD, sizeof(double) * len, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("held-out calibration: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    if (rc == BQ_OK) rc = bq_ctx_sync(c);   // cal_of, k and the results are the caller's and this frame's
+    else (void)bq_ctx_sync(c);
+    for (void *ptr : {(void *)dD, (void *)dL, (void *)db, (void *)dnsv, (void *)dcal, (void *)dA, (void *)dB, (void *)dloss,
+                      (void *)dpos, (void *)dneg, (void *)diters, (void *)dflags, (void *)count})
         if (ptr) hipFree(ptr);
     return rc;
 }

@@ -1,7 +1,9 @@
-__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV']
+__all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV',
+           'CalibratedSVC']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
 from .onevsone import OneVsOneSVC
 from .model_selection import SVCGridSearchCV, SVRGridSearchCV
 from .multioutput import MultiOutputSVR
+from .calibration import CalibratedSVC

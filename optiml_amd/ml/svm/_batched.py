@@ -83,6 +83,22 @@ class _DeviceMultiSolver:
         _lib.check(self._lib.bq_msolver_get(self._h, c, what, _lib.ptr(out)))
         return out
 
+    def heldout_svc(self, cal_of, ncal, decisions=False):
+        """The columns of a one-box-per-column SVC solver as they stand (`bq_msolver_svc_heldout`): per column SVC.fit's
+        intercept and support count (NaN without a support vector), and per calibrator the Platt fit (`platt_fit`'s dict) on the
+        held-out decision values of the columns c with cal_of[c] == that calibrator (-1: the column feeds none); with
+        `decisions`, the dict also holds 'dec', the ncal x n decision values (0 on the rows no column of the calibrator holds
+        out).  Returns (intercept, n_sv, fit)."""
+        cal_of = _lib.as_i32(cal_of, self.k, 'cal_of')
+        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
+        fit, args = _platt_outputs(ncal)
+        dec = np.empty((ncal, self.n)) if decisions else None
+        _lib.check(self._lib.bq_msolver_svc_heldout(self._h, int(ncal), _lib.iptr(cal_of), _lib.ptr(b),
+                                                    n_sv.ctypes.data_as(C.POINTER(C.c_int64)), *args, _lib.ptr(dec)))
+        if decisions:
+            fit['dec'] = dec
+        return b, n_sv, fit
+
     def close(self):
         if self._h:
             self._lib.bq_msolver_destroy(self._h)
@@ -93,6 +109,30 @@ class _DeviceMultiSolver:
             self.close()
         except Exception:
             pass
+
+
+def _platt_outputs(ncal):
+    """The per-calibrator result arrays of `bq_platt_fit` / `bq_msolver_svc_heldout` and their pointers in the C argument order"""
+    fit = dict(A=np.empty(ncal), B=np.empty(ncal), iters=np.empty(ncal, dtype=np.int32), loss=np.empty(ncal),
+               n_pos=np.empty(ncal, dtype=np.int64), n_neg=np.empty(ncal, dtype=np.int64), flags=np.empty(ncal, dtype=np.int32))
+    i64 = C.POINTER(C.c_int64)
+    args = (_lib.ptr(fit['A']), _lib.ptr(fit['B']), _lib.iptr(fit['iters']), _lib.ptr(fit['loss']),
+            fit['n_pos'].ctypes.data_as(i64), fit['n_neg'].ctypes.data_as(i64), _lib.iptr(fit['flags']))
+    return fit, args
+
+
+def platt_fit(D, L):
+    """Platt's sigmoid p = 1 / (1 + exp(A f + B)) of every row of D (ncal x n decision values) with the labels L (ncal x n: +1, -1,
+    or 0 for a row outside the calibrator's sample), all on the device in one launch (`bq_platt_fit`): a dict of the arrays A, B,
+    iters, loss, n_pos, n_neg and flags (`_lib.PLATT_*`), ncal entries each."""
+    D = np.ascontiguousarray(np.atleast_2d(D), dtype=float)
+    L = np.ascontiguousarray(np.atleast_2d(L), dtype=float)
+    if D.shape != L.shape:
+        raise ValueError('decision values (%d x %d) and labels (%d x %d) do not match' % (D.shape + L.shape))
+    ncal, n = D.shape
+    fit, args = _platt_outputs(ncal)
+    _lib.check(_lib.load().bq_platt_fit(get_context().handle, ncal, n, _lib.ptr(D), _lib.ptr(L), *args))
+    return fit
 
 
 class _DeviceSVRSolver(_DeviceMultiSolver):
