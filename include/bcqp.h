@@ -55,6 +55,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_svr_boxes and bq_msolver_svr_heldout were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_al was added; nothing existing changed) */
 /* (still 3: bq_platt_fit and bq_msolver_svc_heldout were added; nothing existing changed) */
+/* (still 3: bq_problem_hessian_image and the test entry bq_problem_last_product were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -290,6 +291,29 @@ int bq_ctx_set_placement_budget(bq_ctx *ctx, double min_ms, double max_ms, doubl
  * (another allocator in the process, a communicator about to be created).  *bytes (optional): what was released.  The ~0.5 s
  * transient that follows a large release (everything streams 1.5 - 4.5 % slower) is then the caller's. */
 int bq_ctx_release_held_memory(bq_ctx *ctx, int64_t *bytes);
+/* The Hessian image of a rank-one RBF dual: fl(K + 1) of this rank's tile rows in 6.5 bytes per element, a second allocation beside
+ * the compact panel that the one-column product of ProjectedGradient / FrankWolfe streams in the panel's place (every output bit as
+ * from the panel).  Built when the first such solver is created on the problem, if the problem is a packed, compact, resident RBF
+ * panel with the rank-one term, a tenth of the device stays free beside it and the products announced through
+ * bq_ctx_set_placement_budget's expected_products (unknown = 0) repay its allocation and conversion, and if the product, timed on it, is faster than on the panel.  *state: BQ_HIMG_* — built, or
+ * why not; *bytes: its size (0 if not built); *build_ms: the conversion; *tried, ms[0 .. min(*tried, cap)): the product's launch time
+ * on each allocation tried for it (the placement choice of BQ_PLACE_PANEL, run for the image). */
+enum {
+    BQ_HIMG_NONE = 0,        /* no ProjectedGradient / FrankWolfe solver was created yet */
+    BQ_HIMG_BUILT = 1,
+    BQ_HIMG_NOT_ELIGIBLE = 2, /* not (rank-one term, compact, packed, resident), or this rank owns no tile row */
+    BQ_HIMG_SWITCHED_OFF = 3, /* test hook hessian_image=0 */
+    BQ_HIMG_NO_ROOM = 4,      /* a tenth of the device would not stay free beside it */
+    BQ_HIMG_NO_REPAY = 5,     /* expected_products unknown or too few to repay allocation + conversion */
+    BQ_HIMG_ALLOC_FAILED = 6,
+    BQ_HIMG_OUT_OF_DOMAIN = 7, /* an element of K + 1 could not be encoded: the image was dropped */
+    BQ_HIMG_GIVEN_BACK = 8,   /* released when a later device allocation of the library failed */
+    BQ_HIMG_NOT_FASTER = 9    /* timed on this problem, the product on the (empty) image was no faster than on the panel: short grids */
+};
+/* TEST ENTRY (fails with BQ_ERR_BADARG unless BQ_TEST_HOOKS holds product_rows=1): the output vector of the last panel product as the
+ * device holds it — *len = nb * 256 entries for a packed panel (the pad rows past n included), n otherwise; out == NULL: only *len */
+int bq_problem_last_product(bq_problem *p, double *out, int64_t cap, int64_t *len);
+int bq_problem_hessian_image(const bq_problem *p, int *state, int64_t *bytes, double *build_ms, int *tried, double *ms, int cap);
 
 /* ---- solvers (optiml/opti/constrained/, the four .py files) --------------------------------------------------- */
 /* lb/ub/x0: dual-dim fp64 host vectors (lb, x0 may be NULL: 0 and mid-box, constrained/_base.py:61-65).

@@ -107,6 +107,8 @@ PROTOTYPES = {
     'bq_problem_panel_rows': (C.c_int, [_vp, _i64, _i64, _dp]),
     'bq_problem_time_matvec': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_problem_placement': (C.c_int, [_vp, C.POINTER(C.c_int), _dp, C.c_int]),
+    'bq_problem_last_product': (C.c_int, [_vp, _dp, _i64, C.POINTER(_i64)]),
+    'bq_problem_hessian_image': (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_int), _dp, C.c_int]),
     'bq_solver_create': (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_solver_destroy': (C.c_int, [_vp]),
     'bq_solver_run': (C.c_int, [_vp, _i64, C.POINTER(IterStat), _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),

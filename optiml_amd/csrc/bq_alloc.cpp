@@ -3,12 +3,18 @@
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
+#include <thread>
 
 #include "bq_common.h"
 
 namespace {
 std::mutex g_mu;
 std::vector<bq_ctx *> g_live;   // contexts that may hold a cached panel
+struct image_owner {
+    bq_problem *p;
+    std::thread::id thread;
+};
+std::vector<image_owner> g_images;   // problems that hold a Hessian image (bq_problem::himg), and the thread that built it
 }  // namespace
 
 void bq_ctx_register(bq_ctx *c, bool alive) {
@@ -51,6 +57,48 @@ static bool release_held_locked(bq_ctx *c, const void *owner) {
         } else {
             ++k;
         }
+    }
+    if (any) hipSetDevice(dev);
+    return any;
+}
+
+void bq_image_register(bq_problem *p, bool alive) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = std::find_if(g_images.begin(), g_images.end(), [&](const image_owner &o) { return o.p == p; });
+    if (alive && it == g_images.end()) g_images.push_back({p, std::this_thread::get_id()});
+    if (!alive && it != g_images.end()) g_images.erase(it);
+}
+
+// The Hessian images go back to the driver like the held candidates: the product reads the panel again, with the same bits.  Unlike
+// those, an image is memory IN USE: its owner reads bq_problem::himg for every product, outside this mutex.  So only the images
+// built on the calling thread are given back — that thread is here and not between the read and the launch of a product; hipFree
+// waits for the device, so a product already in flight on the image finishes first.  Images of other threads stay.
+static bool mine_locked() {
+    const auto me = std::this_thread::get_id();
+    for (const image_owner &o : g_images)
+        if (o.thread == me && o.p->himg != nullptr) return true;
+    return false;
+}
+static bool release_images_locked() {
+    bool any = false;
+    int dev = 0;
+    hipGetDevice(&dev);
+    const auto me = std::this_thread::get_id();
+    for (size_t k = 0; k < g_images.size();) {
+        bq_problem *p = g_images[k].p;
+        if (g_images[k].thread != me) {
+            ++k;
+            continue;
+        }
+        if (p->himg != nullptr) {
+            hipSetDevice(p->ctx->device);
+            hipFree(p->himg);
+            p->himg = nullptr;
+            p->himg_bytes = 0;
+            p->himg_state = BQ_HIMG_GIVEN_BACK;
+            any = true;
+        }
+        g_images.erase(g_images.begin() + (long)k);
     }
     if (any) hipSetDevice(dev);
     return any;
@@ -124,6 +172,7 @@ hipError_t bq_device_malloc(void **ptr, size_t bytes) {
     if (fail_above >= 0 && (long long)bytes > fail_above) {
         std::lock_guard<std::mutex> lk(g_mu);
         for (bq_ctx *c : g_live) simulated = simulated || c->panel_cache != nullptr || !c->held.empty();
+        simulated = simulated || mine_locked();
     }
     // (hipExtMallocWithFlags(hipDeviceMallocContiguous) for the panels was tried in round 4: the launch-time spread of the panel
     // product is the same with it — profiles/r04/placement_contiguous_flag.txt)
@@ -142,6 +191,7 @@ hipError_t bq_device_malloc(void **ptr, size_t bytes) {
             }
             if (release_held_locked(c, nullptr)) dropped = true;
         }
+        if (release_images_locked()) dropped = true;
     }
     // a failed hipMalloc leaves its error pending: the next hipGetLastError() of an unrelated call would report "out of
     // memory" (seen: after a panel that does not fit, the next — small — problem failed once).  The caller gets the code.

@@ -4,9 +4,11 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
+#include <functional>
 
 #include "bq_al.h"
 #include "bq_c7.h"
+#include "bq_h52.h"
 
 static thread_local std::string g_last_error;
 
@@ -437,7 +439,8 @@ extern "C" int bq_problem_destroy(bq_problem *p) {
     }
     p->panel = nullptr;
     bq_ctx_release_held(p->ctx, p);
-    for (void *ptr : {(void *)p->panel_alloc, (void *)p->q, (void *)p->sgn, (void *)p->X, (void *)p->w, (void *)p->s,
+    bq_image_register(p, false);   // (after this no failing allocation touches p->himg)
+    for (void *ptr : {(void *)p->himg, (void *)p->panel_alloc, (void *)p->q, (void *)p->sgn, (void *)p->X, (void *)p->w, (void *)p->s,
                       (void *)p->va, (void *)p->vb, (void *)p->partials, (void *)p->scal, (void *)p->slab, (void *)p->gath})
         if (ptr) hipFree(ptr);
     bq_stream_free(p->stream_img);
@@ -542,52 +545,60 @@ extern "C" int bq_problem_create_dense(bq_ctx *c, int64_t n, const double *Q, co
 // as many further candidates as fit, each priced at what the FIRST allocation of this size cost (freshly released device memory
 // is cleared by the driver before it is handed out: seconds, not milliseconds — then no candidate fits the budget).
 // Per rank and before the first collective of a multi-rank job: the other ranks wait at most the budget.
-static int place_panel(bq_problem *p, double first_alloc_ms) {
-    bq_ctx *c = p->ctx;
-    if (!p->symmetric || p->streamed || p->panel == nullptr || p->panel_bytes < ((size_t)1 << 30) || p->I1 <= p->I0) return BQ_OK;
-    const int want = 3;   // allocations tried at most (a 4th never won in round 4's sweeps: profiles/r04/placement_*.txt)
-    const double good_gbs = bq_hook_value("panel_good_gbs", 6500.0);
-    const char *e = getenv("BQ_PLACE_BUDGET_MS");
-    const double budget_min = c->place_min_ms >= 0.0 ? c->place_min_ms : (e ? atof(e) : 200.0);
-    double budget_ms = budget_min;   // grows with the work the caller expects once the product's time is known (below)
-    const auto t_start = std::chrono::steady_clock::now();
-    auto elapsed_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
-    bq_seg_table tab;
-    bq_sym_seg_table(p, &tab);
-    struct scope {   // events and the profiling switch go back on every exit path
-        bq_ctx *c;
-        bool prof;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~scope() {
-            if (e0) hipEventDestroy(e0);
-            if (e1) hipEventDestroy(e1);
-            c->profiling = prof;
-        }
-    } sc{c, c->profiling};
-    c->profiling = false;
-    BQ_HIP(hipEventCreate(&sc.e0));
-    BQ_HIP(hipEventCreate(&sc.e1));
-    auto time_on = [&](void *panel, double *ms_out) -> int {
-        int rc = bq_launch_symv(c, bq_problem_panel(p, panel), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);   // warm
-        hipEventRecord(sc.e0, c->stream);
-        for (int i = 0; rc == BQ_OK && i < 4; ++i)
-            rc = bq_launch_symv(c, bq_problem_panel(p, panel), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);
-        hipEventRecord(sc.e1, c->stream);
-        hipError_t he = hipEventSynchronize(sc.e1);
+// The choice itself, for any allocation a one-column product streams (the panel; the Hessian image): `launch(alloc)` enqueues one product
+// on `alloc`, `*alloc` comes in as the first allocation (already zeroed on the stream) and goes out as the fastest; the others are held
+// for `owner`.  tried / ms: the placements timed and the launch time on each.
+namespace {
+struct place_timer {   // events and the profiling switch go back on every exit path
+    bq_ctx *c;
+    bool prof;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit place_timer(bq_ctx *ctx) : c(ctx), prof(ctx->profiling) { c->profiling = false; }
+    ~place_timer() {
+        if (e0) hipEventDestroy(e0);
+        if (e1) hipEventDestroy(e1);
+        c->profiling = prof;
+    }
+    int init() {
+        BQ_HIP(hipEventCreate(&e0));
+        BQ_HIP(hipEventCreate(&e1));
+        return BQ_OK;
+    }
+    // five products: one to warm, the mean of four
+    int time_on(const std::function<int(void *)> &launch, void *alloc, double *ms_out) {
+        int rc = launch(alloc);   // warm
+        hipEventRecord(e0, c->stream);
+        for (int i = 0; rc == BQ_OK && i < 4; ++i) rc = launch(alloc);
+        hipEventRecord(e1, c->stream);
+        hipError_t he = hipEventSynchronize(e1);
         float ms = 0.f;
-        if (he == hipSuccess) he = hipEventElapsedTime(&ms, sc.e0, sc.e1);
+        if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
         if (rc == BQ_OK && he != hipSuccess) {
             bq_set_error("timing a panel placement failed: %s", hipGetErrorString(he));
             rc = BQ_ERR_HIP;
         }
         *ms_out = (double)ms / 4.0;
         return rc;
-    };
+    }
+};
+}  // namespace
+
+static int place_candidates(bq_ctx *c, const void *owner, size_t bytes, double first_alloc_ms, const std::function<int(void *)> &launch,
+                            void **alloc, int *tried, double *ms, int max_tried) {
+    const int want = std::min(3, max_tried);   // allocations tried at most (a 4th never won in round 4's sweeps: profiles/r04/placement_*.txt)
+    const double good_gbs = bq_hook_value("panel_good_gbs", 6500.0);
+    const char *e = getenv("BQ_PLACE_BUDGET_MS");
+    const double budget_min = c->place_min_ms >= 0.0 ? c->place_min_ms : (e ? atof(e) : 200.0);
+    double budget_ms = budget_min;   // grows with the work the caller expects once the product's time is known (below)
+    const auto t_start = std::chrono::steady_clock::now();
+    auto elapsed_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
+    place_timer timer(c);
+    BQ_TRY(timer.init());
     std::vector<void *> losers;
     double best = 0.0;
-    int rc = time_on(p->panel, &best);
-    p->place_tried = 1;
-    p->place_ms[0] = best;
+    int rc = timer.time_on(launch, *alloc, &best);
+    *tried = 1;
+    ms[0] = best;
     // a panel that came from the context's cache (a destroyed problem of the same size left it: fit loops) was chosen when IT was
     // allocated, and a fresh allocation right after that release is the slow kind: it is kept as it is
     if (first_alloc_ms <= 0.0) return rc;
@@ -596,40 +607,172 @@ static int place_panel(bq_problem *p, double first_alloc_ms) {
     if (c->place_products > 0.0 && c->place_max_ms > budget_min)
         budget_ms = std::min(c->place_max_ms, std::max(budget_min, 0.02 * c->place_products * best));
     // what one more candidate costs: an allocation like the first one + clearing it + five products on it
-    const double cand_ms = first_alloc_ms + (double)p->panel_bytes / 4.0e9 + 6.0 * best;
-    while (rc == BQ_OK && p->place_tried < want && (double)p->panel_bytes / (best * 1e-3) / 1e9 < good_gbs &&
-           elapsed_ms() + cand_ms <= budget_ms) {
+    const double cand_ms = first_alloc_ms + (double)bytes / 4.0e9 + 6.0 * best;
+    while (rc == BQ_OK && *tried < want && (double)bytes / (best * 1e-3) / 1e9 < good_gbs && elapsed_ms() + cand_ms <= budget_ms) {
         size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < p->panel_bytes + p->panel_bytes / 16) break;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + bytes / 16) break;
         // the losers are held while the problem lives (bq_ctx::held): a second copy only if a tenth of the device stays free beside
         // the two (config 5's 125 GB panel on 288 GB: yes, once; a failing allocation later gives the held one back: bq_alloc.cpp)
-        if (2 * p->panel_bytes + total_b / 10 > total_b || free_b < p->panel_bytes + total_b / 10) break;
+        if (2 * bytes + total_b / 10 > total_b || free_b < bytes + total_b / 10) break;
         void *cand = nullptr;
-        if (hipMalloc(&cand, p->panel_bytes) != hipSuccess) {
+        if (hipMalloc(&cand, bytes) != hipSuccess) {
             (void)hipGetLastError();
             break;
         }
-        hipError_t he = hipMemsetAsync(cand, 0, p->panel_bytes, c->stream);
+        hipError_t he = hipMemsetAsync(cand, 0, bytes, c->stream);
         double t = 0.0;
-        if (he == hipSuccess) rc = time_on(cand, &t);
+        if (he == hipSuccess) rc = timer.time_on(launch, cand, &t);
         if (he != hipSuccess || rc != BQ_OK) {
             hipFree(cand);
             if (he != hipSuccess) (void)hipGetLastError();
             break;
         }
-        p->place_ms[p->place_tried++] = t;
+        ms[(*tried)++] = t;
         if (t < best) {
-            losers.push_back(p->panel);
-            p->panel = cand;
-            p->panel_alloc = cand;
+            losers.push_back(*alloc);
+            *alloc = cand;
             best = t;
         } else {
             losers.push_back(cand);
         }
     }
     // not released here: a large hipFree is followed by a transient in which the whole process streams slower (bq_ctx::held)
-    for (void *l : losers) bq_ctx_hold(c, l, p->panel_bytes, p);
+    for (void *l : losers) bq_ctx_hold(c, l, bytes, owner);
     return rc;
+}
+
+static int place_panel(bq_problem *p, double first_alloc_ms) {
+    bq_ctx *c = p->ctx;
+    if (!p->symmetric || p->streamed || p->panel == nullptr || p->panel_bytes < ((size_t)1 << 30) || p->I1 <= p->I0) return BQ_OK;
+    bq_seg_table tab;
+    bq_sym_seg_table(p, &tab);
+    auto launch = [&](void *panel) {
+        return bq_launch_symv(c, bq_problem_panel(p, panel), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr);
+    };
+    void *chosen = p->panel;
+    const int rc = place_candidates(c, p, p->panel_bytes, first_alloc_ms, launch, &chosen, &p->place_tried, p->place_ms, 32);
+    p->panel = chosen;
+    p->panel_alloc = chosen;
+    return rc;
+}
+
+// The Hessian image (bq_h52.h; the rules: bq_problem_hessian_image in bcqp.h).  "Not built" is a state, never an error: the product
+// reads the panel then, with the same bits.  The image is placed like the panel — the streaming time belongs to the physical region
+// that is streamed, and that is now the image: a zero-filled image decodes to 1.0 everywhere, so it is timed empty as the panel is.
+int bq_hessian_image_ensure(bq_problem *p) {
+    bq_ctx *c = p->ctx;
+    if (p->himg_state != BQ_HIMG_NONE) return BQ_OK;   // decided once per problem
+    auto decided = [&](int state) {
+        p->himg_state = state;
+        return BQ_OK;
+    };
+    if (!p->add_one || !p->compact || !p->symmetric || p->streamed || p->panel == nullptr || p->I1 <= p->I0) return decided(BQ_HIMG_NOT_ELIGIBLE);
+    if (!bq_hook_on("hessian_image")) return decided(BQ_HIMG_SWITCHED_OFF);
+    const size_t bytes = (size_t)bq_h52_bytes(p->panel_elems);
+    size_t free_b = 0, total_b = 0;
+    BQ_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (free_b < bytes + total_b / 10) return decided(BQ_HIMG_NO_ROOM);   // place_panel's rule for a second panel
+    if (!(p->expected_products > 0.0)) return decided(BQ_HIMG_NO_REPAY);   // unknown counts as 0
+    bq_seg_table tab;
+    bq_sym_seg_table(p, &tab);
+    double t_prod = 0.0;   // the product as place_panel measured it on the panel kept; else five products now
+    for (int i = 0; i < p->place_tried; ++i) t_prod = (i == 0 || p->place_ms[i] < t_prod) ? p->place_ms[i] : t_prod;
+    if (p->place_tried == 0) {
+        place_timer timer(c);
+        BQ_TRY(timer.init());
+        BQ_TRY(timer.time_on([&](void *panel) {
+            return bq_launch_symv(c, bq_problem_panel(p, panel), true, p->nb, tab, p->w, p->slab, p->s, nullptr);
+        }, p->panel, &t_prod));
+    }
+    const size_t panel_data = (size_t)p->panel_elems * 7;
+    const double good_gbs = bq_hook_value("panel_good_gbs", 6500.0);
+    const double cost_ms = p->alloc_ms * (double)bytes / (double)std::max<size_t>(p->panel_bytes, 1) + (double)(panel_data + bytes) / (good_gbs * 1e6);
+    if (cost_ms > p->expected_products * (1.0 - 6.5 / 7.0) * t_prod) return decided(BQ_HIMG_NO_REPAY);
+    // hook alloc_fail_above: a request above the threshold is refused here (the allocator's own simulation only fails a request that
+    // giving something back could serve)
+    const long long fail_above = (long long)bq_hook_value("alloc_fail_above", -1.0);
+    void *img = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((fail_above >= 0 && (long long)bytes > fail_above) || hipMalloc(&img, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return decided(BQ_HIMG_ALLOC_FAILED);
+    }
+    const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    int *bad_dev = nullptr;
+    int rc = BQ_OK;
+    auto give_up = [&](int err) {
+        if (img) hipFree(img);
+        if (bad_dev) hipFree(bad_dev);
+        return err;
+    };
+    if (hipMemsetAsync(img, 0, bytes, c->stream) != hipSuccess || hipMalloc(&bad_dev, sizeof(int)) != hipSuccess) {
+        bq_set_error("Hessian image setup failed: %s", hipGetErrorString(hipGetLastError()));
+        return give_up(BQ_ERR_HIP);
+    }
+    {   // timed on every image; further candidates as for the panel: from 1 GiB on
+        auto launch = [&](void *image) {
+            return bq_launch_symv(c, bq_problem_image(p, image), false, p->nb, tab, p->w, p->slab, p->s, nullptr);
+        };
+        rc = place_candidates(c, p, bytes, alloc_ms, launch, &img, &p->himg_tried, p->himg_ms, bytes >= ((size_t)1 << 30) ? 3 : 1);
+        if (rc != BQ_OK) return give_up(rc);
+    }
+    // The bytes are not the whole story: a grid of one round of workgroups or less lasts as long as one strip takes, and there the
+    // image's product was measured SLOWER than the panel's (C2, 435 strips: profiles/hessian_image/c2_ab_duplicate_load.json: with the 16-byte load issued twice).  So the panel's
+    // product is timed again NOW, with the same five launches as the image's a moment ago (the time place_panel took at problem
+    // creation is another moment of the device), and the image stays only if the MEASURED saving per product is positive and repays
+    // what the allocation did cost and the conversion will (hook hessian_image_gain=G: the image's product must be G times faster;
+    // 0 keeps it regardless, for the tests' small sizes).
+    double t_img = p->himg_ms[0], t_now = 0.0;
+    for (int i = 1; i < p->himg_tried; ++i) t_img = std::min(t_img, p->himg_ms[i]);
+    {
+        place_timer timer(c);
+        rc = timer.init();
+        if (rc == BQ_OK)
+            rc = timer.time_on([&](void *panel) {
+                return bq_launch_symv(c, bq_problem_panel(p, panel), true, p->nb, tab, p->w, p->slab, p->s, nullptr);
+            }, p->panel, &t_now);
+        if (rc != BQ_OK) return give_up(rc);
+    }
+    const double gain = bq_hook_value("hessian_image_gain", 1.0);
+    const double spent_ms = alloc_ms + (double)(panel_data + bytes) / (good_gbs * 1e6);
+    if (gain > 0.0 && (t_img * gain >= t_now || p->expected_products * (t_now - t_img) < spent_ms)) {
+        // held like a candidate that lost, until the first solver of the problem goes (bq_solver_destroy): a large release slows
+        // the solve that follows (bq_ctx::held)
+        bq_ctx_hold(c, img, bytes, p);
+        img = nullptr;
+        give_up(BQ_OK);
+        return decided(BQ_HIMG_NOT_FASTER);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    rc = bq_launch_h52_convert(c, p, img, bad_dev, bq_hook_value("hessian_image_bad", 0.0) != 0.0);
+    int bad = 0;
+    if (rc == BQ_OK && hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+        bq_set_error("Hessian image conversion failed: %s", hipGetErrorString(hipGetLastError()));
+        rc = BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) rc = bq_ctx_sync(c);
+    if (rc != BQ_OK) return give_up(rc);
+    p->himg_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    hipFree(bad_dev);
+    bad_dev = nullptr;
+    if (bad) {   // never reached from a compact panel (K in {0} u [2^-15, 1]): the safety net, as for the compact panel itself
+        give_up(BQ_OK);
+        return decided(BQ_HIMG_OUT_OF_DOMAIN);
+    }
+    p->himg = img;
+    p->himg_bytes = bytes;
+    bq_image_register(p, true);
+    return decided(BQ_HIMG_BUILT);
+}
+
+extern "C" int bq_problem_hessian_image(const bq_problem *p, int *state, int64_t *bytes, double *build_ms, int *tried, double *ms, int cap) {
+    BQ_ARG(p != nullptr && state != nullptr, "NULL argument");
+    *state = p->himg_state;
+    if (bytes) *bytes = p->himg ? (int64_t)p->himg_bytes : 0;
+    if (build_ms) *build_ms = p->himg_build_ms;
+    if (tried) *tried = p->himg_tried;
+    for (int i = 0; ms != nullptr && i < cap && i < p->himg_tried; ++i) ms[i] = p->himg_ms[i];
+    return BQ_OK;
 }
 
 extern "C" int bq_ctx_set_placement_budget(bq_ctx *c, double min_ms, double max_ms, double expected_products) {
@@ -676,6 +819,7 @@ extern "C" int bq_problem_create_kernel(bq_ctx *c, int structure, int64_t n, int
     p->diag_add = diag_add;
     p->d = d;
     p->streamed = storage == BQ_STREAM;
+    p->expected_products = c->place_products;
     // Gram panels are symmetric: store and stream only the tiles on/below the diagonal, unless the caller asked for whole rows
     // (BQ_FULL_PANEL).  Streamed problems take the same segment partition of the tile rows and form each lower-triangle tile once.
     p->symmetric = p->streamed || !full_panel;
@@ -794,6 +938,20 @@ extern "C" int bq_problem_gram_matvec(bq_problem *p, const double *w, double *ou
     BQ_TRY(bq_panel_product(p, false, p->w, nullptr));
     BQ_HIP(hipMemcpyAsync(out, p->s, sizeof(double) * p->n, hipMemcpyDeviceToHost, c->stream));
     BQ_SYNC(c);
+    return BQ_OK;
+}
+
+// test-only (hook product_rows=1): the output vector of the last panel product as the device holds it, pad rows included
+extern "C" int bq_problem_last_product(bq_problem *p, double *out, int64_t cap, int64_t *len) {
+    BQ_ARG(p && len, "NULL argument");
+    BQ_ARG(bq_hook_value("product_rows", 0.0) != 0.0, "bq_problem_last_product is a test entry: BQ_TEST_HOOKS product_rows=1");
+    const int64_t rows = p->symmetric ? p->nb * BQ_SYM_TILE : p->n;
+    *len = rows;
+    if (out == nullptr) return BQ_OK;
+    BQ_ARG(cap >= rows, "out is too short");
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    BQ_HIP(hipMemcpyAsync(out, p->s, sizeof(double) * rows, hipMemcpyDeviceToHost, p->ctx->stream));
+    BQ_SYNC(p->ctx);
     return BQ_OK;
 }
 
@@ -1176,6 +1334,13 @@ extern "C" int bq_solver_create(bq_problem *p, int kind, const double *lb, const
         bq_set_error("solver setup failed: %s", hipGetErrorString(e));
         bq_solver_destroy(s);
         return BQ_ERR_HIP;
+    }
+    if (kind == BQ_PG || kind == BQ_FW) {   // their every iteration is one product with the rank-one term: the Hessian image (bq_h52.h)
+        rc = bq_hessian_image_ensure(p);
+        if (rc != BQ_OK) {
+            bq_solver_destroy(s);
+            return rc;
+        }
     }
     if ((kind == BQ_IP || kind == BQ_AS) && !as_cg) {
         // InteriorPoint on the SVR structure factorises the reduced n x n system (bq_ip.hip)

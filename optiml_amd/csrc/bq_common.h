@@ -46,6 +46,9 @@ void bq_set_error(const char *fmt, ...);
 //   rows_per_step=4|8  stream_unit=U  minres_big_min=N  as_schur=0  as_schur_min=N  as_schur_limit=N  as_mailbox=0  as_f_chain=0
 //   as_cg_warm=0  as_cg_incq=0  as_cg_colq=0  as_cg_pc_incr=0  as_cg_pc_class=0..3  ip_svr_reduced=0  smo_helpers=N
 //   panel_good_gbs=G  alloc_fail_above=BYTES  decision_chunk_rows=R  decision_multi_unit=TILES  decision_multi_chunk_rows=R  sweep_block=1024|2048|4096  compact_panel=0
+//   hessian_image=0 (no Hessian image is built and none is read: the A/B of one build)  hessian_image_bad=1 (the conversion raises its flag)
+//   product_rows=1 (bq_problem_last_product answers)
+//   hessian_image_gain=G (the image is kept if its product is G times faster than the panel's; default 1, 0: always)
 // ---------------------------------------------------------------------------------------------
 bool bq_hook(const char *name, double *value);                       // true (and *value) when the hook is set
 static inline double bq_hook_value(const char *name, double dflt) {
@@ -188,6 +191,16 @@ struct bq_problem {
     int64_t d = 0;
     double gamma = 0, coef0 = 0, diag_add = 0;
     int degree = 0;
+    // The Hessian image (bq_h52.h): fl(K + 1) of this rank's tile rows in 6.5 bytes per element, lane-ordered — a second, private
+    // allocation with one writer (bq_launch_h52_convert) and one reader (symv_tiles_kernel<bq_h52> through bq_panel_product).  Built
+    // when the first PG / FW solver is created (bq_hessian_image_ensure); himg_state says whether, or why not (BQ_HIMG_*).
+    void *himg = nullptr;
+    size_t himg_bytes = 0;
+    int himg_state = BQ_HIMG_NONE;
+    double himg_build_ms = 0.0;
+    int himg_tried = 0;
+    double himg_ms[4] = {0.0};
+    double expected_products = 0.0;   // bq_ctx_set_placement_budget's, as it stood when the problem was created (0: unknown)
     double *w = nullptr;   // ld: panel-product input
     double *s = nullptr;   // world*blk (>= n): panel-product output, gathered
     double *va = nullptr, *vb = nullptr;  // ldN scratch for the host-vector entry points
@@ -284,6 +297,7 @@ void bq_ctx_release_held(bq_ctx *ctx, const void *owner);                    // 
 // A resident panel as the launchers take it: storage BQ_F64 / BQ_F32, or BQ_F64C — internal, never a public storage code: an fp64
 // panel in the compact layout of bq_c7.h, whose three planes lie `elems` elements apart in the one allocation at `base`.
 constexpr int BQ_F64C = 16;
+constexpr int BQ_F64H = 17;   // the Hessian image of bq_h52.h (elements already K + 1): bq_launch_symv / bq_launch_symv_segments only
 struct bq_panel_ref {
     const void *base;
     int storage;
@@ -292,6 +306,21 @@ struct bq_panel_ref {
 static inline bq_panel_ref bq_problem_panel(const bq_problem *p, const void *base = nullptr) {   // base: a candidate allocation
     return {base ? base : p->panel, p->compact ? BQ_F64C : p->storage, p->panel_elems};
 }
+// the image in the panel's place for a product with the rank-one term (hook hessian_image=0: never), else the panel
+static inline bool bq_problem_reads_image(const bq_problem *p, bool add_one) {
+    return add_one && p->himg != nullptr && bq_hook_on("hessian_image");
+}
+static inline bq_panel_ref bq_problem_image(const bq_problem *p, const void *base = nullptr) {
+    return {base ? base : p->himg, BQ_F64H, p->panel_elems};
+}
+// bq_api.hip: builds the image if the rules of bq_problem_hessian_image (bcqp.h) allow it; never an error for "not built"
+int bq_hessian_image_ensure(bq_problem *p);
+// bq_symv.hip: image = encode(fl(K + 1)) of every element of the resident compact panel; *bad (device word, cleared here) is raised
+// when an element is outside the domain of bq_h52_encode (or force_bad: the hook)
+int bq_launch_h52_convert(bq_ctx *ctx, const bq_problem *p, void *image, int *bad, bool force_bad);
+// bq_alloc.cpp: the problems that hold an image a failing allocation may take back — an allocation failing on the THREAD that
+// registered the image (the thread that built it and runs its products): an image is memory in use, and no other thread may free it
+void bq_image_register(bq_problem *p, bool alive);
 // hook compact_panel=0: eligible RBF panels keep the plain fp64 layout (the A/B of the two layouts in one build)
 static inline bool bq_compact_allowed() { return bq_hook_on("compact_panel"); }
 

@@ -23,6 +23,7 @@
 // timed launch, and the compact layout at 8 rows per step, which is not built, is an error there) and the fixed-order walk of a slab
 // column (slab_walk under seg_thread_sum, bq_symv_tile.h).  The strip body of symv_tiles_kernel is its own: bq_symmp.hip's single
 // kernel repeats it, because as one inlined function template this kernel compiled to other code than it has alone.
+#include <algorithm>
 #include <cstdlib>
 
 #include <hip/hip_ext.h>
@@ -95,8 +96,10 @@ __global__ __launch_bounds__(256, 2) void symv_tiles_kernel(bq_pptr<T> panel, in
                     const auto row = rows + (int64_t)(step * SR + k) * pitch + j * ST;
                     tile_ld<T>::get(row, lane, a[k], b[k]);
                 }
+                tile_post<T>::issued();
 #pragma unroll
                 for (int k = 0; k < SR; ++k) {
+                    tile_post<T>::decode(a[k], b[k]);
                     if (ADD_ONE) {
                         a[k].x += 1.0;
                         a[k].y += 1.0;
@@ -286,7 +289,14 @@ static int launch_tiles(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, in
     const bool ext = !bracket && e0 != nullptr;
     const dim3 grid((unsigned)nstrips), block(256);
     hipError_t err = hipSuccess;
-    bq_panel_dispatch(panel, add_one, [&](auto pv, auto one) {
+    if (panel.storage == BQ_F64H) {   // the Hessian image (bq_h52.h): its elements are fl(K + 1) already; 4 rows per step as for the compact panel
+        if constexpr (SR == 4)
+            err = add_one ? hipErrorInvalidValue
+                          : launch_timed(ctx, ext, e0, e1, symv_tiles_kernel<bq_h52, false, JG, 4>, grid, block,
+                                         bq_h52_view(panel.base, panel.elems), I0, nb, w, slab, done, skip, skip_seq);
+        else
+            err = hipErrorInvalidValue;
+    } else bq_panel_dispatch(panel, add_one, [&](auto pv, auto one) {
         using T = bq_pelem<decltype(pv)>;
         if constexpr (std::is_same<T, bq_c7>::value && SR != 4)
             err = hipErrorInvalidValue;   // not built: launch_any keeps the compact layout at 4 rows per step
@@ -334,9 +344,54 @@ static int launch_any(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int6
     const int64_t slots = 2 * (int64_t)(ctx->num_cu > 0 ? ctx->num_cu : 256);
     const bool sparse_tail = strips >= slots && strips < 8 * slots && 2 * (strips % slots) < slots;
     // The compact layout (bq_c7.h) always takes 4: its decode makes the 8-row step spill (12 bytes per lane of scratch).
-    const bool eight = panel.storage != BQ_F64C && (force == 8 || (force != 4 && (panel.storage == BQ_F32 || sparse_tail)));
+    const bool eight = panel.storage != BQ_F64C && panel.storage != BQ_F64H && (force == 8 || (force != 4 && (panel.storage == BQ_F32 || sparse_tail)));
     if (eight) return launch_variant<8>(ctx, panel, add_one, nb, tab, w, slab, out, mode, done, epi);
     return launch_variant<4>(ctx, panel, add_one, nb, tab, w, slab, out, mode, done, epi);
+}
+
+// The writer of the Hessian image (bq_h52.h).  Every aligned run of 256 packed indices is one row of one tile (bq_sym_layout.h), so the
+// conversion needs no tile geometry: a wave takes one run, lane l reads the column pairs {2l, 2l + 1} and {128 + 2l, 129 + 2l} through
+// the decode the product uses (bq_c7p::pair), adds 1.0 in fp64 — the operand the product's first FMA sees today — and writes the four
+// codes to positions 4l .. 4l + 3: one 16-byte, one 8-byte and one 2-byte store.
+__global__ __launch_bounds__(256) void h52_convert_kernel(bq_c7p panel, int64_t runs, uint32_t *__restrict__ lo, uint16_t *__restrict__ mid,
+                                                          uint8_t *__restrict__ nib, int *__restrict__ bad, int force_bad) {
+    typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+    typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    bool any_bad = force_bad != 0 && blockIdx.x == 0 && threadIdx.x == 0;
+    for (int64_t run = wave; run < runs; run += nwaves) {
+        const int64_t base = run * BQ_H52_ROW;
+        const d2_t a = panel.pair(base + 2 * lane), b = panel.pair(base + 128 + 2 * lane);
+        const double h[4] = {a.x + 1.0, a.y + 1.0, b.x + 1.0, b.y + 1.0};
+        uint64_t c[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c[q] = bq_h52_encode((uint64_t)__double_as_longlong(h[q]), &any_bad);
+        const u4_t l = {(uint32_t)c[0], (uint32_t)c[1], (uint32_t)c[2], (uint32_t)c[3]};
+        const u2_t m = {((uint32_t)(c[0] >> 32) & 0xFFFFu) | ((uint32_t)(c[1] >> 32) << 16),
+                        ((uint32_t)(c[2] >> 32) & 0xFFFFu) | ((uint32_t)(c[3] >> 32) << 16)};
+        const uint32_t t = (uint32_t)(c[0] >> 48) | ((uint32_t)(c[1] >> 48) << 4) | ((uint32_t)(c[2] >> 48) << 8) | ((uint32_t)(c[3] >> 48) << 12);
+        *reinterpret_cast<u4_t *>(lo + base + 4 * lane) = l;
+        *reinterpret_cast<u2_t *>(mid + base + 4 * lane) = m;
+        *reinterpret_cast<uint16_t *>(nib + (base >> 1) + 2 * lane) = (uint16_t)t;
+    }
+    if (any_bad) *bad = 1;
+}
+
+int bq_launch_h52_convert(bq_ctx *ctx, const bq_problem *p, void *image, int *bad, bool force_bad) {
+    if (!p->compact || p->panel == nullptr || p->panel_elems <= 0 || p->panel_elems % BQ_H52_ROW != 0) {
+        bq_set_error("the Hessian image is built from a resident compact panel");
+        return BQ_ERR_BADARG;
+    }
+    BQ_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    const int64_t runs = p->panel_elems / BQ_H52_ROW;
+    unsigned char *b = (unsigned char *)image;
+    const int64_t blocks = std::min<int64_t>((runs + 3) / 4, 8 * (int64_t)(ctx->num_cu > 0 ? ctx->num_cu : 256));
+    h52_convert_kernel<<<(unsigned)blocks, 256, 0, ctx->stream>>>(bq_c7_view(p->panel, p->panel_elems), runs, (uint32_t *)b,
+                                                                  (uint16_t *)(b + 4 * p->panel_elems), b + 6 * p->panel_elems, bad,
+                                                                  force_bad ? 1 : 0);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
 }
 
 int bq_launch_symv(bq_ctx *ctx, const bq_panel_ref &panel, bool add_one, int64_t nb, const bq_seg_table &tab,

@@ -3,6 +3,7 @@
 #pragma once
 #include "bq_c7.h"
 #include "bq_common.h"
+#include "bq_h52.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -29,6 +30,25 @@ template <> struct tile_ld<bq_c7> {   // the compact layout (bq_c7.h): per pair 
         b = row.pair(128 + 2 * lane);
     }
 };
+// The Hessian image (bq_h52.h): a tile row lies in lane order, so the lane's four columns are one 16-byte, one 8-byte and one 2-byte
+// load — three requests per row and tile where the compact panel takes six.  The values are fl(K + 1): the kernel adds nothing.
+template <> struct bq_pan<bq_h52> {
+    typedef bq_h52p ptr;
+    typedef bq_h52p view;
+};
+template <> struct tile_ld<bq_h52> {
+    static __device__ __forceinline__ int c0(int lane) { return 2 * lane; }
+    static __device__ __forceinline__ int c1(int lane) { return 128 + 2 * lane; }
+    // the loads only: the 7 loaded words travel in a / b as they came (a: lo of the four columns, b.x: their mid, b.y: their nib) and
+    // tile_post<bq_h52>::decode turns them into the values — so that the kernel can keep every load of a step ahead of the first decode.
+    // Each plane is loaded AS the type it travels in: repacked from an integer vector, the 16-byte load came out twice in the ISA (a
+    // dwordx4 and a dwordx2 of the same address).
+    static __device__ __forceinline__ void get(const bq_h52p &row, int lane, d2_t &a, d2_t &b) {
+        a = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(row.lo + 4 * lane));
+        b.x = __builtin_nontemporal_load(reinterpret_cast<const double *>(row.mid + 4 * lane));
+        b.y = __hiloint2double(0, (int)(uint32_t)__builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(row.nib + 2 * lane)));
+    }
+};
 template <> struct tile_ld<float> {
     static __device__ __forceinline__ int c0(int lane) { return 4 * lane; }
     static __device__ __forceinline__ int c1(int lane) { return 4 * lane + 2; }
@@ -36,6 +56,32 @@ template <> struct tile_ld<float> {
         const f4_t v = __builtin_nontemporal_load(reinterpret_cast<const f4_t *>(row + 4 * lane));
         a = (d2_t){(double)v.x, (double)v.y};
         b = (d2_t){(double)v.z, (double)v.w};
+    }
+};
+
+// What a layout does between the loads of a step and its FMAs; nothing for the layouts whose tile_ld::get returns values.
+template <typename T> struct tile_post {
+    static __device__ __forceinline__ void issued() {}
+    static __device__ __forceinline__ void decode(d2_t &, d2_t &) {}
+};
+// The image: left to itself the compiler sinks the loads of the later rows of a step below the waits and decodes of the earlier
+// ones (at most six loads in flight, the step's latency paid row after row: 6.15 - 6.33 ms at the headline where the compact panel takes
+// 5.47 - 5.60, profiles/hessian_image/headline_ab_first_schedule.json) — the scheduling barrier keeps all of a step's loads ahead.
+template <> struct tile_post<bq_h52> {
+    static __device__ __forceinline__ void issued() { __builtin_amdgcn_sched_barrier(0); }
+    // bq_h52_bits with its two-sided escape test folded into one compare: z = m20 | (lo ^ 1) is 0 for the code 1 alone
+    static __device__ __forceinline__ double val(uint32_t lo, uint32_t m20) {
+        const uint32_t z = m20 | (lo ^ 1u);
+        return __hiloint2double((int)(z ? (0x3FF00000u | m20) : 0x40000000u), (int)(z ? lo : 0u));
+    }
+    static __device__ __forceinline__ void decode(d2_t &a, d2_t &b) {
+        const uint32_t l0 = (uint32_t)__double2loint(a.x), l1 = (uint32_t)__double2hiint(a.x);
+        const uint32_t l2 = (uint32_t)__double2loint(a.y), l3 = (uint32_t)__double2hiint(a.y);
+        const uint32_t m0 = (uint32_t)__double2loint(b.x), m1 = (uint32_t)__double2hiint(b.x), t = (uint32_t)__double2loint(b.y);
+        a.x = val(l0, ((t & 0xFu) << 16) | (m0 & 0xFFFFu));
+        a.y = val(l1, ((t & 0xF0u) << 12) | (m0 >> 16));
+        b.x = val(l2, ((t & 0xF00u) << 8) | (m1 & 0xFFFFu));
+        b.y = val(l3, ((t & 0xF000u) << 4) | (m1 >> 16));
     }
 };
 

@@ -106,14 +106,20 @@ int bq_panel_product(bq_problem *p, bool add_one, const double *w, const int *do
     if (p->symmetric) {
         bq_seg_table tab;
         bq_sym_seg_table(p, &tab);
+        // the one switch point of the Hessian image (bq_h52.h): a product with the rank-one term streams fl(K + 1) in 6.5 bytes per
+        // element where the problem holds the image, and adds nothing — the same operands, the same bits; every other product, and
+        // every other reader of the panel, knows nothing of it
+        const bool image = bq_problem_reads_image(p, add_one);
+        const bq_panel_ref panel = image ? bq_problem_image(p) : bq_problem_panel(p);
+        if (image) add_one = false;
         if (ctx->comm_kind == BQ_COMM_NONE) {
-            BQ_TRY(bq_launch_symv(ctx, bq_problem_panel(p), add_one, p->nb, tab, w, p->slab, p->s, done, epi));
+            BQ_TRY(bq_launch_symv(ctx, panel, add_one, p->nb, tab, w, p->slab, p->s, done, epi));
             if (fused) *fused = epi != nullptr;
         } else if (ctx->sym_allreduce) {   // rank partials meet in one all-reduce(sum): association depends on the transport
-            BQ_TRY(bq_launch_symv(ctx, bq_problem_panel(p), add_one, p->nb, tab, w, p->slab, p->s, done));
+            BQ_TRY(bq_launch_symv(ctx, panel, add_one, p->nb, tab, w, p->slab, p->s, done));
             BQ_TRY(bq_exchange_sum(ctx, p->s, p->nb * BQ_SYM_TILE));
         } else {   // default: all-gather of the segment vectors, summed in segment order on every rank (bit-identical for any world)
-            BQ_TRY(bq_launch_symv_segments(ctx, bq_problem_panel(p), add_one, p->nb, tab, w, p->slab, p->gath, done));
+            BQ_TRY(bq_launch_symv_segments(ctx, panel, add_one, p->nb, tab, w, p->slab, p->gath, done));
             BQ_TRY(bq_exchange_gather(ctx, p->gath, (int64_t)p->seg_cmax * p->nb * BQ_SYM_TILE));
             BQ_TRY(bq_launch_symv_segsum(ctx, p->nb, tab, p->gath, p->s, done, epi));
             if (fused) *fused = epi != nullptr;

@@ -199,7 +199,14 @@ class Context:
     def set_placement_budget(self, expected_products=0., min_ms=-1., max_ms=5000.):
         """Budget of the panel placement choice (`KernelQuadratic(tune_placement=True)`) for problems created from now on: up to 2 %
         of `expected_products` products of the panel, within [min_ms (default: BQ_PLACE_BUDGET_MS / 200 ms), max_ms]."""
+        self._place_limits = (float(min_ms), float(max_ms))
         _lib.check(self._lib.bq_ctx_set_placement_budget(self.handle, float(min_ms), float(max_ms), float(expected_products)))
+
+    def announce_products(self, expected_products=0.):
+        """The products the caller expects on the problems created from now on, WITHOUT touching the time limits of the placement
+        choice a caller set with `set_placement_budget` (the count also decides whether a Hessian image repays its build)."""
+        lo, hi = getattr(self, '_place_limits', (-1., 5000.))
+        _lib.check(self._lib.bq_ctx_set_placement_budget(self.handle, lo, hi, float(expected_products)))
 
     def release_held_memory(self):
         """Give the panel-sized allocations the placement choice is holding back (until the solve they were tried for is over) to

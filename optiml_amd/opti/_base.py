@@ -114,6 +114,29 @@ class _DeviceProblem:
         _lib.check(self._lib.bq_problem_placement(self._h, C.byref(tried), _lib.ptr(ms), 32))
         return [float(v) for v in ms[:tried.value]]
 
+    HESSIAN_IMAGE_STATES = ('none', 'built', 'not_eligible', 'switched_off', 'no_room', 'no_repay', 'alloc_failed', 'out_of_domain',
+                            'given_back', 'not_faster')
+
+    def hessian_image(self):
+        """State of the Hessian image (`bq_problem_hessian_image`: fl(K + 1) in 6.5 bytes per element beside a compact RBF panel, which
+        ProjectedGradient / FrankWolfe stream in the panel's place): {'state': 'built' or why not, 'bytes', 'build_ms',
+        'placement_ms': the product's launch time on each allocation tried for it}."""
+        state, tried, nbytes, build = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0)
+        ms = np.zeros(4)
+        _lib.check(self._lib.bq_problem_hessian_image(self._h, C.byref(state), C.byref(nbytes), C.byref(build), C.byref(tried),
+                                                      _lib.ptr(ms), 4))
+        return {'state': self.HESSIAN_IMAGE_STATES[state.value], 'bytes': nbytes.value, 'build_ms': build.value,
+                'placement_ms': [float(v) for v in ms[:tried.value]]}
+
+    def last_product(self):
+        """TEST ENTRY (BQ_TEST_HOOKS product_rows=1): the output vector of the last panel product as the device holds it, pad rows
+        included (nb * 256 entries for a packed panel)."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.bq_problem_last_product(self._h, None, 0, C.byref(n)))
+        out = np.empty(n.value)
+        _lib.check(self._lib.bq_problem_last_product(self._h, _lib.ptr(out), n.value, C.byref(n)))
+        return out
+
     def time_matvec(self, reps=10):
         ms = C.c_double(0)
         _lib.check(self._lib.bq_problem_time_matvec(self._h, reps, C.byref(ms)))
@@ -266,8 +289,9 @@ class KernelQuadratic(Quadratic):
         lib = _lib.load()
         h = C.c_void_p()
         n, d = self.X.shape
-        if self.tune_placement:
-            ctx.set_placement_budget(self.expected_products)
+        # (always: the products announced also decide whether a Hessian image repays its build — `_DeviceProblem.hessian_image`;
+        # the time limits a caller gave the placement choice stay as they are)
+        ctx.announce_products(self.expected_products)
         _lib.check(lib.bq_problem_create_kernel(
             ctx.handle, self._STRUCT[self.structure] | (0 if self.rank_one else _lib.NO_RANK_ONE) |
             (_lib.FULL_PANEL if self.full_panel else 0) | (_lib.PLACE_PANEL if self.tune_placement else 0) |
