@@ -56,6 +56,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_al was added; nothing existing changed) */
 /* (still 3: bq_platt_fit and bq_msolver_svc_heldout were added; nothing existing changed) */
 /* (still 3: bq_problem_hessian_image and the test entry bq_problem_last_product were added; nothing existing changed) */
+/* (still 3: bq_msolver_pairs_heldout, bq_pairwise_coupling and bq_decision_coupled were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -438,6 +439,18 @@ int bq_platt_fit(bq_ctx *ctx, int ncal, int64_t n, const double *D, const double
  * the decision buffer (0 on the rows no column of the calibrator holds out). */
 int bq_msolver_svc_heldout(bq_msolver *s, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A, double *B,
                            int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags, double *dec);
+/* bq_msolver_svc_heldout for the columns of a bq_msolver_create_pairs solver (any other solver: BQ_ERR_BADARG): the folds of a
+ * one-vs-one calibration, column (pair, fold) with UB = 0 on the fold's held-out rows of the pair's classes.  data_row: n bytes, 1 a
+ * data row, 0 a ghost row of the class-sorted panel.  Per column coef, n_sv and intercept as there, with u = K coef by ONE pair-routed
+ * product over all columns, every pair live as in bq_problem_gram_matmat_pairs (the solver's own liveness is restored from its
+ * columns' states: a later run continues as if this call had not been made).  Column c's held-out rows are the data rows of its pair's
+ * two classes with UB[c][i] == 0 — never a ghost row, never a row of another class; each writes u + intercept and its label to row
+ * cal_of[c] of the two zeroed ncal x n buffers.  cal_of, the disjointness rule (on those rows), n_sv = 0, the Platt outputs and dec:
+ * as bq_msolver_svc_heldout.  Every sum has a fixed order and reads its own column only: a column's results have the same bits in
+ * any batch. */
+int bq_msolver_pairs_heldout(bq_msolver *s, const unsigned char *data_row, int ncal, const int *cal_of, double *intercept,
+                             int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg,
+                             int *flags, double *dec);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's
@@ -551,6 +564,25 @@ int bq_decision_function(bq_ctx *ctx, int kernel, double gamma, double coef0, in
 int bq_decision_function_multi(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                                const double *SV, int k, const double *W, const double *b, int64_t t, const double *Xt,
                                double *out);
+
+/* ---- pairwise coupling (libsvm svm.cpp multiclass_probability: Wu, Lin & Weng 2004, second method; what
+ * sklearn.svm.SVC(probability=True).predict_proba evaluates) ----------------------------------------------------------------------
+ * ncls classes, P = ncls (ncls - 1) / 2 pair columns in the order (0,1), (0,2), ..., (1,2), ...; column q = (a, b), a < b, has class b
+ * positive: s = 1 / (1 + exp(f A[q] + B[q])), evaluated without overflow and clipped to [1e-7, 1 - 1e-7], is the probability of b
+ * against a (r[b][a] = s, r[a][b] = 1 - s).  Per test point p starts at 1 / ncls and takes libsvm's Gauss-Seidel sweeps until
+ * max_t |(Qp)_t - p'Qp| < 0.005 / ncls, at most max(100, ncls) of them, one wavefront per point: no fused multiply-add, every sum
+ * sequential in ascending index, IEEE division, so the same statements in NumPy on the same s give the same bits and sweep count.
+ * A point's result has the same bits alone, at any position and in any batch.
+ * F: t x P decision values (row-major, host); A, B: P; prob: t x ncls; iters: t sweeps taken (the cap when it was reached), or NULL;
+ * R: t x P, the clipped s, or NULL.  ncls < 2, ncls > 64, t < 1 or a NULL required pointer: BQ_ERR_BADARG, before any device call. */
+int bq_pairwise_coupling(bq_ctx *ctx, int ncls, int64_t t, const double *F, const double *A, const double *B, double *prob,
+                         int *iters, double *R);
+/* bq_decision_function_multi with k = P pair columns, and the coupling of each test point's P decision values where they lie on the
+ * device, chunk of test points by chunk: prob, iters, R as above; dec: NULL, or k x t, which receives bq_decision_function_multi's
+ * out (the same bits).  The checks are those of both; BQ_ERR_BADARG for BQ_KERNEL_LAPLACIAN and for k != ncls (ncls - 1) / 2. */
+int bq_decision_coupled(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d, const double *SV,
+                        int k, const double *W, const double *b, int64_t t, const double *Xt, int ncls, const double *A,
+                        const double *B, double *prob, int *iters, double *R, double *dec);
 
 /* dense Gram matrix out (m x t, row-major) = kernel(A (m x d), B (t x d)); B == NULL means B is A (t ignored)
  * — the kernel functors' __call__, optiml/ml/svm/kernels.py:49-51 / 91-95 / 125-129 */

@@ -131,6 +131,8 @@ PROTOTYPES = {
     'bq_platt_fit': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, _ip, _dp, C.POINTER(_i64), C.POINTER(_i64), _ip]),
     'bq_msolver_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp, C.POINTER(_i64),
                                          C.POINTER(_i64), _ip, _dp]),
+    'bq_msolver_pairs_heldout': (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp,
+                                           C.POINTER(_i64), C.POINTER(_i64), _ip, _dp]),
     'bq_msolver_create_pairs': (C.c_int, [_vp, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.c_double,
                                           C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
@@ -145,6 +147,9 @@ PROTOTYPES = {
                                        C.c_double, _i64, _dp, _dp]),
     'bq_decision_function_multi': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, C.c_int, _dp, _dp,
                                              _i64, _dp, _dp]),
+    'bq_pairwise_coupling': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, _ip, _dp]),
+    'bq_decision_coupled': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, C.c_int, _dp, _dp, _i64, _dp,
+                                      C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
     'bq_gram_matrix': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, _i64, _dp, _dp]),
     'bq_cholesky_solve': (C.c_int, [_vp, _i64, _dp, _dp, _dp, _dp]),
 }

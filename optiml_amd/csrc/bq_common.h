@@ -380,6 +380,11 @@ void bq_pairs_plan_destroy(bq_pairs_plan *pl);
 int64_t bq_pairs_slab_len(const bq_pairs_plan *pl);
 int bq_launch_symmp(bq_problem *p, const bq_pairs_plan *pl, bool add_one, const double *W, int64_t ldw, double *slab, double *out);
 int bq_launch_pairs_live(const bq_pairs_plan *pl, bq_scal *const *scs, int *nlive, hipStream_t st);
+// every pair live, whatever its solver's state (the plan's state at creation): a product that scores every column
+int bq_launch_pairs_all_live(const bq_pairs_plan *pl, hipStream_t st);
+// the plan's device copies of cls_tiles (ncls + 1) and pairs (2 m)
+const int *bq_pairs_plan_tiles(const bq_pairs_plan *pl);
+const int *bq_pairs_plan_pairs(const bq_pairs_plan *pl);
 
 // bq_msolver.hip: one multi-column product from host arrays, the body of bq_problem_gram_matmat(_wide) and
 // bq_problem_gram_matmat_pairs.  W's k rows (p->n each) go into `slots` zeroed device columns of stride p->ldN,
@@ -416,10 +421,14 @@ int bq_max_sq_norm(bq_ctx *ctx, const double *X, int64_t n, int64_t d, double *o
 int bq_launch_decision(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                        const double *SV, const double *coef, double intercept, int64_t t, const double *Xt,
                        double *out);
-// the decision values of k coefficient columns in one pass over the kernel values (bq_decide.hip)
+// the decision values of k coefficient columns in one pass over the kernel values (bq_decide.hip).  The device-output form:
+// after_chunk(arg, dout, r0, r1) is called once the kernels of the test points [r0, r1) are enqueued on the context's stream, dout
+// being the k x t device array of all decision values (column c of point i at dout[c * t + i]); what it enqueues on that stream
+// reads those rows where they lie.  out may then be null (no copy to the host).  Synchronises the stream before it returns.
+typedef int (*bq_decision_chunk_fn)(void *arg, const double *dout, int64_t r0, int64_t r1);
 int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                              const double *SV, int k, const double *W, const double *b, int64_t t, const double *Xt,
-                             double *out);
+                             double *out, bq_decision_chunk_fn after_chunk = nullptr, void *arg = nullptr);
 
 // streamed mode (bq_gram.hip): persistent k-major image of X + the fused Gram-tile x vector product
 // rows [r0, r1): this rank's 256-row tile rows (whole canonical segments; r1 may exceed n)

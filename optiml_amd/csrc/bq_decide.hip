@@ -176,7 +176,7 @@ static int64_t decide_unit_tiles(int64_t t, int64_t m, int64_t d) {
 
 int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                              const double *SV, int k, const double *W, const double *b, int64_t t, const double *Xt,
-                             double *out) {
+                             double *out, bq_decision_chunk_fn after_chunk, void *arg) {
     gram_images A, B;
     double *dSV = nullptr, *dXt = nullptr, *dW = nullptr, *db = nullptr, *part = nullptr, *dout = nullptr;
     const int64_t kp = bq_round_up(k, 16), mp = bq_round_up(m, BQ_GT), tp = bq_round_up(t, BQ_GT);
@@ -286,8 +286,13 @@ int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0
         decide_reduce_kernel<<<(unsigned)((cells + 255) / 256), 256, 0, ctx->stream>>>(part, (int)units, chunk, kp, r1 - r0, k, db,
                                                                                       dout, t, r0);
         DEC_HIP(hipGetLastError());
+        if (after_chunk && (rc = after_chunk(arg, dout, r0, r1)) != BQ_OK) {
+            (void)hipStreamSynchronize(ctx->stream);
+            cleanup();
+            return rc;
+        }
     }
-    DEC_HIP(hipMemcpyAsync(out, dout, sizeof(double) * (int64_t)k * t, hipMemcpyDeviceToHost, ctx->stream));
+    if (out) DEC_HIP(hipMemcpyAsync(out, dout, sizeof(double) * (int64_t)k * t, hipMemcpyDeviceToHost, ctx->stream));
     DEC_HIP(hipStreamSynchronize(ctx->stream));
     cleanup();
 #undef DEC_HIP

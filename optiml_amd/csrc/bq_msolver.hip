@@ -18,7 +18,9 @@
 // bq_msolver_create_pairs is the boxes solver on a class-sorted panel with one column per one-vs-one pair (a, b): ub = C on the rows
 // of a and b, 0 elsewhere, and the pair-routed product (bq_symmp.hip) for every pass, which streams the panel once for all pairs.
 // The live kernel is the plan's: it keeps pos[] the identity (column = pair) and gathers every class's live pairs into the slots of
-// its diagonal block; a stopped pair's blocks leave the stream at the next iteration.
+// its diagonal block; a stopped pair's blocks leave the stream at the next iteration.  bq_msolver_pairs_heldout scores its columns as
+// bq_msolver_svc_heldout scores a boxes solver's (the folds of a one-vs-one calibration: ub = 0 on a fold's held-out rows of the pair's
+// classes), with one routed product in which every pair is live.
 //
 // bq_msolver_create_svr is the same batch on a BQ_SVR problem (multi-output regression: target c has the linear term
 // q_c = [-y_c; y_c] + eps and every target the Hessian [P -P; -P P]): the columns are vectors of 2n, one thread of the start-up and
@@ -42,6 +44,7 @@
 #include "bq_common.h"
 #include "bq_epilogue.h"
 
+#include <algorithm>
 #include <cmath>
 #include <new>
 #include <vector>
@@ -52,7 +55,9 @@ struct bq_msolver {
     bool wide = false;   // bq_msolver_create_boxes / _svr_boxes: the 16-column product (bq_symmw.hip) for every pass
     bool svr_boxes = false;   // bq_msolver_create_svr_boxes: bq_msolver_svr_heldout may score it
     bool svc_boxes = false;   // bq_msolver_create_boxes: bq_msolver_svc_heldout may calibrate it
-    std::vector<unsigned char> held;   // svc_boxes: k x n, 1 where UB is 0 (the column's held-out rows), as given at creation
+    // svc_boxes: k x n, 1 where UB is 0 (the column's held-out rows), as given at creation; a bq_msolver_create_pairs solver: the
+    // same on the rows of the pair's classes and 0 on every other row (bq_msolver_pairs_heldout)
+    std::vector<unsigned char> held;
     bq_pairs_plan *plan = nullptr;   // bq_msolver_create_pairs: the pair-routed product (bq_symmp.hip) for every pass
     int64_t ldw = 0;   // column stride of W / OUT / sgn (= p->ld >= nb * 256)
     std::vector<bq_solver *> cls;
@@ -248,19 +253,11 @@ __global__ __launch_bounds__(256) void msvc_coef_kernel(const bq_epilogue *__res
     W[blockIdx.y * ldw + i] = x > 1e-6 ? x * e.sgn[i] : 0.0;
 }
 
-// bq_msolver_svc_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1, the support rows (x above 1e-6): S = sum (y - u),
-// n_sv, b = S / n_sv in intercept()'s order (svm/_batched.py), summed as msvr_score_kernel sums.  Pass 2, the held-out rows
-// (ub = 0): the decision value u + b and the label y to row cal_of[column] of D and L (row stride n; zeroed by the caller; the
-// columns of a calibrator hold out disjoint rows, so no two workgroups write one entry).  n_sv = 0: b = NaN.
-__global__ __launch_bounds__(1024) void msvc_heldout_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
-                                                            int64_t ldw, const int *__restrict__ cal_of, double *__restrict__ D,
-                                                            double *__restrict__ L, double *__restrict__ intercept,
-                                                            long long *__restrict__ n_sv) {
-    __shared__ double sd[1024];
-    __shared__ int sc[1024];
-    const bq_epilogue &e = epi[blockIdx.x];
-    const double *u = out + blockIdx.x * ldw;
-    const int tid = threadIdx.x;
+// the first pass of the held-out kernels of an SVC column, u = K coef: over the support rows (x above 1e-6) S = sum (y - u) and
+// n_sv, summed as msvr_score_kernel sums; returns b = S / n_sv in intercept()'s order (svm/_batched.py; n_sv = 0: NaN) to every
+// thread and writes both figures
+__device__ inline double msvc_intercept(const bq_epilogue &e, const double *__restrict__ u, double *sd, int *sc, int tid,
+                                        double *__restrict__ intercept, long long *__restrict__ n_sv) {
     const long long n = e.n;
     double s = 0.0;
     int cnt = 0;
@@ -275,9 +272,26 @@ __global__ __launch_bounds__(1024) void msvc_heldout_kernel(const bq_epilogue *_
     const int nsv = sc[0];
     const double b = nsv > 0 ? sd[0] / (double)nsv : NAN;
     if (tid == 0) {
-        intercept[blockIdx.x] = b;
-        n_sv[blockIdx.x] = nsv;
+        *intercept = b;
+        *n_sv = nsv;
     }
+    return b;
+}
+
+// bq_msolver_svc_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1: msvc_intercept.  Pass 2, the held-out rows
+// (ub = 0): the decision value u + b and the label y to row cal_of[column] of D and L (row stride n; zeroed by the caller; the
+// columns of a calibrator hold out disjoint rows, so no two workgroups write one entry).  n_sv = 0: b = NaN.
+__global__ __launch_bounds__(1024) void msvc_heldout_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
+                                                            int64_t ldw, const int *__restrict__ cal_of, double *__restrict__ D,
+                                                            double *__restrict__ L, double *__restrict__ intercept,
+                                                            long long *__restrict__ n_sv) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_epilogue &e = epi[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = e.n;
+    const double b = msvc_intercept(e, u, sd, sc, tid, intercept + blockIdx.x, n_sv + blockIdx.x);
     const int cal = cal_of[blockIdx.x];
     if (cal < 0) return;
     double *d = D + (long long)cal * n, *l = L + (long long)cal * n;
@@ -285,6 +299,37 @@ __global__ __launch_bounds__(1024) void msvc_heldout_kernel(const bq_epilogue *_
         if (e.ub[i] == 0.0) {
             d[i] = u[i] + b;
             l[i] = e.sgn[i];
+        }
+    }
+}
+
+// bq_msolver_pairs_heldout, column blockIdx.x = pair (a, b) of a class-sorted panel: msvc_heldout_kernel, whose held-out rows are
+// the data rows (data_row: 1; a ghost row: 0) of the tile rows of a and of b with ub = 0 — ub is 0 on every row of another class
+// too, and such a row is in no pair's sample
+__global__ __launch_bounds__(1024) void mpairs_heldout_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
+                                                              int64_t ldw, const int *__restrict__ pairs, const int *__restrict__ ct,
+                                                              const unsigned char *__restrict__ data_row,
+                                                              const int *__restrict__ cal_of, double *__restrict__ D,
+                                                              double *__restrict__ L, double *__restrict__ intercept,
+                                                              long long *__restrict__ n_sv) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_epilogue &e = epi[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = e.n;
+    const double b = msvc_intercept(e, u, sd, sc, tid, intercept + blockIdx.x, n_sv + blockIdx.x);
+    const int cal = cal_of[blockIdx.x];
+    if (cal < 0) return;
+    double *d = D + (long long)cal * n, *l = L + (long long)cal * n;
+    for (int side = 0; side < 2; ++side) {
+        const int cls = pairs[2 * blockIdx.x + side];
+        const long long r1 = (long long)ct[cls + 1] * BQ_SYM_TILE < n ? (long long)ct[cls + 1] * BQ_SYM_TILE : n;
+        for (long long i = (long long)ct[cls] * BQ_SYM_TILE + tid; i < r1; i += 1024) {
+            if (data_row[i] && e.ub[i] == 0.0) {
+                d[i] = u[i] + b;
+                l[i] = e.sgn[i];
+            }
         }
     }
 }
@@ -582,7 +627,23 @@ extern "C" int bq_msolver_create_pairs(bq_problem *p, int kind, int ncls, const 
             }
         }
     }
-    return msolver_create(p, kind, m, Y, UB, p->n, false, x0, eps, max_iter, fw_t, out, plan);
+    BQ_TRY(msolver_create(p, kind, m, Y, UB, p->n, false, x0, eps, max_iter, fw_t, out, plan));
+    bq_msolver *s = *out;
+    try {
+        s->held.assign((size_t)m * (size_t)p->n, 0);
+    } catch (const std::bad_alloc &) {   // as bq_msolver_create_boxes
+        bq_msolver_destroy(s);
+        *out = nullptr;
+        bq_set_error("batched solver: no host memory for the held-out masks");
+        return BQ_ERR_NOMEM;
+    }
+    for (int q = 0; q < m; ++q)
+        for (int e = 0; e < 2; ++e) {
+            const int64_t r0 = (int64_t)cls_tiles[pairs[2 * q + e]] * BQ_SYM_TILE;
+            const int64_t r1 = std::min<int64_t>((int64_t)cls_tiles[pairs[2 * q + e] + 1] * BQ_SYM_TILE, p->n);
+            for (int64_t i = r0; i < r1; ++i) s->held[(size_t)q * (size_t)p->n + i] = UB[q * p->n + i] == 0.0;
+        }
+    return BQ_OK;
 }
 
 extern "C" int bq_msolver_create_svr(bq_problem *p, int kind, int k, const double *QL, const double *ub, const double *x0,
@@ -707,11 +768,11 @@ extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const doub
     return rc;
 }
 
-extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A,
-                                      double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags,
-                                      double *dec) {
-    BQ_ARG(m && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
-    BQ_ARG(m->svc_boxes, "held-out calibration takes a solver of bq_msolver_create_boxes");
+// bq_msolver_svc_heldout (data_row null: the 16-column product, msvc_heldout_kernel) and bq_msolver_pairs_heldout (the pair-routed
+// product with every pair live, mpairs_heldout_kernel), after their own argument checks
+static int msolver_heldout(bq_msolver *m, const unsigned char *data_row, int ncal, const int *cal_of, double *intercept,
+                           int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags,
+                           double *dec) {
     BQ_ARG(ncal >= 1, "ncal must be >= 1");
     bq_problem *p = m->p;
     bq_ctx *c = p->ctx;
@@ -730,8 +791,9 @@ extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of
             for (int cl : cs) {
                 const unsigned char *h = m->held.data() + (size_t)cl * (size_t)n;
                 for (int64_t i = 0; i < n; ++i) {
-                    BQ_ARG(!(h[i] && seen[i]), "columns that share a calibrator must have disjoint held-out rows");
-                    seen[i] |= h[i];
+                    const unsigned char hi = h[i] && (data_row == nullptr || data_row[i]);
+                    BQ_ARG(!(hi && seen[i]), "columns that share a calibrator must have disjoint held-out rows");
+                    seen[i] |= hi;
                 }
             }
         }
@@ -743,7 +805,10 @@ extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of
     long long *dnsv = nullptr, *dpos = nullptr, *dneg = nullptr;
     int *dcal = nullptr, *diters = nullptr, *dflags = nullptr;
     int *count = nullptr;   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    unsigned char *drow = nullptr;
     hipError_t e = hipMalloc(&dD, sizeof(double) * len);
+    if (e == hipSuccess && data_row) e = hipMalloc(&drow, (size_t)n);
+    if (e == hipSuccess && data_row) e = hipMemcpyAsync(drow, data_row, (size_t)n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMalloc(&dL, sizeof(double) * len);
     if (e == hipSuccess) e = hipMalloc(&db, sizeof(double) * k);
     if (e == hipSuccess) e = hipMalloc(&dnsv, sizeof(long long) * k);
@@ -773,11 +838,24 @@ extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of
             rc = BQ_ERR_HIP;
         }
     }
-    if (rc == BQ_OK) {
+    if (rc == BQ_OK && m->plan) {
+        // every pair live for this product, as bq_problem_gram_matmat_pairs has them; then the liveness of the columns' states
+        // again, which is what the last iteration left (bq_launch_pairs_live is a function of the states alone)
+        rc = bq_launch_pairs_all_live(m->plan, st);
+        if (rc == BQ_OK) {
+            rc = bq_launch_symmp(p, m->plan, false, m->W, m->ldw, m->slab, m->out);
+            const int back = bq_launch_pairs_live(m->plan, m->scs, m->nlive, st);   // also when the product could not be launched
+            if (rc == BQ_OK) rc = back;
+        }
+    } else if (rc == BQ_OK) {
         rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
     }
     if (rc == BQ_OK) {
-        msvc_heldout_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dcal, dD, dL, db, dnsv);
+        if (m->plan)
+            mpairs_heldout_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, bq_pairs_plan_pairs(m->plan),
+                                                      bq_pairs_plan_tiles(m->plan), drow, dcal, dD, dL, db, dnsv);
+        else
+            msvc_heldout_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dcal, dD, dL, db, dnsv);
         e = hipGetLastError();
         if (e != hipSuccess) {
             bq_set_error("held-out calibration: %s", hipGetErrorString(e));
@@ -805,9 +883,25 @@ extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of
     if (rc == BQ_OK) rc = bq_ctx_sync(c);   // cal_of, k and the results are the caller's and this frame's
     else (void)bq_ctx_sync(c);
     for (void *ptr : {(void *)dD, (void *)dL, (void *)db, (void *)dnsv, (void *)dcal, (void *)dA, (void *)dB, (void *)dloss,
-                      (void *)dpos, (void *)dneg, (void *)diters, (void *)dflags, (void *)count})
+                      (void *)dpos, (void *)dneg, (void *)diters, (void *)dflags, (void *)count, (void *)drow})
         if (ptr) hipFree(ptr);
     return rc;
+}
+
+extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A,
+                                      double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags,
+                                      double *dec) {
+    BQ_ARG(m && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
+    BQ_ARG(m->svc_boxes, "held-out calibration takes a solver of bq_msolver_create_boxes");
+    return msolver_heldout(m, nullptr, ncal, cal_of, intercept, n_sv, A, B, iters, loss, n_pos, n_neg, flags, dec);
+}
+
+extern "C" int bq_msolver_pairs_heldout(bq_msolver *m, const unsigned char *data_row, int ncal, const int *cal_of,
+                                        double *intercept, int64_t *n_sv, double *A, double *B, int *iters, double *loss,
+                                        int64_t *n_pos, int64_t *n_neg, int *flags, double *dec) {
+    BQ_ARG(m && data_row && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
+    BQ_ARG(m->plan != nullptr && !m->held.empty(), "held-out calibration of pairs takes a solver of bq_msolver_create_pairs");
+    return msolver_heldout(m, data_row, ncal, cal_of, intercept, n_sv, A, B, iters, loss, n_pos, n_neg, flags, dec);
 }
 
 static int msolver_first(bq_msolver *m) {

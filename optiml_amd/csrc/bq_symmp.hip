@@ -407,6 +407,18 @@ __global__ __launch_bounds__(64) void symmp_live_kernel(bq_scal *const *__restri
     if (threadIdx.x == 0) *nlive = nl;
 }
 
+// symmp_live_kernel with every pair taken as live, whatever its solver's state (a product that scores every column)
+__global__ __launch_bounds__(64) void symmp_all_live_kernel(const int *__restrict__ pairs, int m, int ncls, int kpad,
+                                                           int *__restrict__ plive, int *__restrict__ ccnt, int *__restrict__ cslot) {
+    for (int c = threadIdx.x; c < ncls; c += 64) {
+        int k = 0;
+        for (int p = 0; p < m; ++p)
+            if (pairs[2 * p] == c || pairs[2 * p + 1] == c) cslot[c * kpad + k++] = p;
+        ccnt[c] = k;
+    }
+    for (int p = threadIdx.x; p < m; p += 64) plive[p] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -420,6 +432,9 @@ void bq_pairs_plan_destroy(bq_pairs_plan *pl) {
 }
 
 int64_t bq_pairs_slab_len(const bq_pairs_plan *pl) { return pl->slab_len; }
+
+const int *bq_pairs_plan_tiles(const bq_pairs_plan *pl) { return pl->dct; }
+const int *bq_pairs_plan_pairs(const bq_pairs_plan *pl) { return pl->dpairs; }
 
 // every pair live: the plan's start state (and what a one-off product takes)
 static int plan_all_live(bq_pairs_plan *pl, hipStream_t st) {
@@ -498,6 +513,12 @@ int bq_pairs_plan_create(bq_problem *p, int ncls, const int *cls_tiles, int m, c
 
 int bq_launch_pairs_live(const bq_pairs_plan *pl, bq_scal *const *scs, int *nlive, hipStream_t st) {
     symmp_live_kernel<<<1, 64, 0, st>>>(scs, pl->dpairs, pl->m, pl->ncls, pl->kpad, pl->plive, pl->ccnt, pl->cslot, nlive);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+int bq_launch_pairs_all_live(const bq_pairs_plan *pl, hipStream_t st) {
+    symmp_all_live_kernel<<<1, 64, 0, st>>>(pl->dpairs, pl->m, pl->ncls, pl->kpad, pl->plive, pl->ccnt, pl->cslot);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }

@@ -1,5 +1,5 @@
 __all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV',
-           'CalibratedSVC']
+           'CalibratedSVC', 'PairwiseCoupledSVC']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
@@ -7,3 +7,4 @@ from .onevsone import OneVsOneSVC
 from .model_selection import SVCGridSearchCV, SVRGridSearchCV
 from .multioutput import MultiOutputSVR
 from .calibration import CalibratedSVC
+from .coupling import PairwiseCoupledSVC

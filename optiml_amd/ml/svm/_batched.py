@@ -99,6 +99,24 @@ class _DeviceMultiSolver:
             fit['dec'] = dec
         return b, n_sv, fit
 
+    def heldout_pairs(self, data_row, cal_of, ncal, decisions=False):
+        """`heldout_svc` for the columns of a pair solver (`_DevicePairSolver`, `bq_msolver_pairs_heldout`): a column's held-out
+        rows are the data rows (data_row: n entries, 1 a data row, 0 a ghost row) of its pair's two classes whose box is 0.
+        Returns (intercept, n_sv, fit)."""
+        cal_of = _lib.as_i32(cal_of, self.k, 'cal_of')
+        data_row = np.ascontiguousarray(data_row, dtype=np.uint8)
+        if data_row.shape != (self.n,):
+            raise ValueError('data_row must have %d entries' % self.n)
+        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
+        fit, args = _platt_outputs(ncal)
+        dec = np.empty((ncal, self.n)) if decisions else None
+        _lib.check(self._lib.bq_msolver_pairs_heldout(self._h, data_row.ctypes.data_as(C.POINTER(C.c_ubyte)), int(ncal),
+                                                      _lib.iptr(cal_of), _lib.ptr(b), n_sv.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      *args, _lib.ptr(dec)))
+        if decisions:
+            fit['dec'] = dec
+        return b, n_sv, fit
+
     def close(self):
         if self._h:
             self._lib.bq_msolver_destroy(self._h)
