@@ -57,6 +57,7 @@ extern "C" {
 /* (still 3: bq_platt_fit and bq_msolver_svc_heldout were added; nothing existing changed) */
 /* (still 3: bq_problem_hessian_image and the test entry bq_problem_last_product were added; nothing existing changed) */
 /* (still 3: bq_msolver_pairs_heldout, bq_pairwise_coupling and bq_decision_coupled were added; nothing existing changed) */
+/* (still 3: bq_msolver_create_simplex, bq_msolver_simplex_offsets and bq_simplex_project were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -411,6 +412,35 @@ int bq_msolver_create_svr_boxes(bq_problem *p, int kind, int k, const double *QL
  * intercept = sse = NaN (SVR.fit divides by zero there). */
 int bq_msolver_svr_heldout(bq_msolver *s, const double *y, const double *epsilon, double *intercept, int64_t *n_sv, double *sse,
                            int64_t *n_held);
+
+/* ---- nu-one-class duals on a capped simplex (sklearn.svm.OneClassSVM, Schoelkopf et al.; libsvm's ONE_CLASS) ------------------
+ * Column c solves  min 1/2 x'Kx  s.t.  0 <= x <= UB[c], sum x = mass[c]  on the Gram panel of p, a kernel-built BQ_PLAIN problem
+ * without a diagonal term on a single-rank context with a resident packed panel (anything else is BQ_ERR_BADARG).  OneClassSVM is
+ * UB = 1, mass = nu n (libsvm's scaling: the solution is sklearn's dual_coef_); a row with UB[c][i] = 0 is a row the column does
+ * not train on.  The equality row is kept (without it x = 0 is optimal), so the step is the Euclidean projection onto the capped
+ * simplex, P(v) = clip(v - tau, 0, u) with sum P = mass, inside a nonmonotone spectral projected-gradient loop:
+ *   x = P(0) (or x0); g = K x; f = 1/2 x'g; s = 1; at the top of iteration it
+ *     viol = max_{x_i > 0} g_i - min_{x_i < u_i} g_i over the rows with u_i > 0 (libsvm's maximal violating pair; -inf if a set is empty)
+ *     record (it, f, r1 = viol, r2 = the last step length a, r3 = s); viol <= tol: optimal; it == max_iter: stopped
+ *     d = P(x - s g) - x; g'd >= 0: optimal; a = 1 if f + g'd + 1/2 d'Kd <= max(the last 10 f) + 1e-4 g'd, else -g'd / d'Kd
+ *     x += a d; g += a K d; f += a g'd + 1/2 a^2 d'Kd; s = clamp(d'd / d'Kd, 1e-10, 1e10), 1e10 where d'Kd <= 0
+ * so tol is sklearn.svm.OneClassSVM's tol.  An iteration's products are one panel stream per 16 live columns (the product of
+ * bq_problem_gram_matmat_wide); a column that stops leaves the stream.  Column c's iterates and records have the same bits alone,
+ * at any position and in any batch.
+ * UB: k x n, in [0, 2^1021]; mass: k, 0 < mass[c] <= sum UB[c] (a mass within n roundings of the sum is the whole box, the single
+ * point x = UB[c]); x0: k x n inside its set, or NULL (P(0)); tol >= 0; max_iter > 0.  A NULL argument, k < 1 or any of the above
+ * violated: BQ_ERR_BADARG.  run / state / get / destroy: as bq_msolver_create (a run of max_steps iterations writes at most
+ * max_steps records per column).
+ * bq_msolver_simplex_offsets: libsvm's calculate_rho of every column from its state on the device, after a run, over the rows with
+ * UB > 0 and with exact comparisons: rho = the mean of g over the free rows (0 < x < UB), summed in index order; without a free
+ * row (min_{x = 0} g + max_{x = UB} g) / 2.  n_sv: the rows with x > 0; n_free: the free rows.  k entries each.
+ * bq_simplex_project: P[c] = the projection of V[c] onto {0 <= p <= UB[c], sum p = mass[c]}, k x n host arrays, by the solver's
+ * projection kernel: one workgroup per column, tau by an 8-section search on the sum that ends exactly on the linear piece holding
+ * the root (|V| at most 2^1021, so that the first bracket's width is finite; else BQ_ERR_BADARG).  0 <= P <= UB holds bitwise, P = 0 where UB = 0, and row c's bits depend on (V[c], UB[c], mass[c]) alone. */
+int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB, const double *mass, const double *x0, double tol,
+                              int64_t max_iter, bq_msolver **out);
+int bq_msolver_simplex_offsets(bq_msolver *s, double *rho, int64_t *n_sv, int64_t *n_free);
+int bq_simplex_project(bq_ctx *ctx, int k, int64_t n, const double *V, const double *UB, const double *mass, double *P);
 
 /* ---- Platt calibration (sklearn CalibratedClassifierCV(method='sigmoid'): calibration.py _sigmoid_calibration, once per (fold,
  * class)) -----------------------------------------------------------------------------------------------------------------------

@@ -128,6 +128,9 @@ PROTOTYPES = {
     'bq_msolver_create_svr': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_msolver_create_svr_boxes': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.c_double, C.POINTER(_vp)]),
     'bq_msolver_svr_heldout': (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(_i64), _dp, C.POINTER(_i64)]),
+    'bq_msolver_create_simplex': (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.POINTER(_vp)]),
+    'bq_msolver_simplex_offsets': (C.c_int, [_vp, _dp, C.POINTER(_i64), C.POINTER(_i64)]),
+    'bq_simplex_project': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp]),
     'bq_platt_fit': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, _ip, _dp, C.POINTER(_i64), C.POINTER(_i64), _ip]),
     'bq_msolver_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp, C.POINTER(_i64),
                                          C.POINTER(_i64), _ip, _dp]),

@@ -39,10 +39,20 @@
 // A bq_msolver_run starts with the prep kernel (the flush of the run before may have stopped a column and moved the slots) and ends
 // with mal_flush_kernel (al_flush_kernel per column) and the live kernel: a column's bits do not depend on how the iterations are
 // cut into runs.  Nesterov momentum (a jump kernel and a flush per iteration) and schedules are not batched.
+//
+// bq_msolver_create_simplex is the batch of k nu-one-class duals on a BQ_PLAIN problem (bq_simplex.hip: the capped simplex
+// {0 <= x <= UB[c], sum x = mass[c]} per column, spectral projected gradient).  Column c keeps its vectors, scalars and records in a
+// bq_solver as the others do (x, g, d, ub, sc, stats), its step state in a bq_sx_state; an iteration of all live columns is
+//   top      sx_top_kernel: the record and the stop tests of every live column, then mlive_kernel's numbering — BEFORE the projection,
+//            which writes the product's input to the slots of this iteration's product
+//   project  sx_project_kernel (one workgroup per column), product  bq_launch_symmw, close  sx_close_kernel
+// so a run of max_steps iterations writes at most max_steps records per column, and a column's state after its last close waits
+// for the next run's top.
 #include "bq_al.h"
 #include "bq_al_update.h"
 #include "bq_common.h"
 #include "bq_epilogue.h"
+#include "bq_simplex.h"
 
 #include <algorithm>
 #include <cmath>
@@ -71,6 +81,14 @@ struct bq_msolver {
     int live_host = 0;            // upper bound of *nlive known to the host
     bool al = false;              // bq_msolver_create_al: the columns are augmented-Lagrangian solvers (epi: k entries of kind 2)
     bq_al_params al_prm = {};
+    bool simplex = false;         // bq_msolver_create_simplex: the columns are capped-simplex solvers (bq_simplex.hip)
+    bq_sx_col *sx_cols = nullptr;       // k: the device table of the columns
+    bq_sx_state *sx_state = nullptr;    // k
+    double *sx_rho = nullptr;           // k: bq_msolver_simplex_offsets' results on the device
+    long long *sx_counts = nullptr;     // 2 k: its support and free counts
+    std::vector<double> sx_mass;
+    std::vector<int> sx_full;
+    bool sx_has_x0 = false;
     struct bq_al_col *al_cols = nullptr;   // k: what mal_update_kernel reads of a column
     bool initialised = false, started = false;
 };
@@ -392,7 +410,7 @@ extern "C" int bq_msolver_destroy(bq_msolver *m) {
     hipSetDevice(m->p->ctx->device);
     (void)bq_ctx_sync(m->p->ctx);
     for (void *ptr : {(void *)m->ql, (void *)m->sgn, (void *)m->W, (void *)m->out, (void *)m->slab, (void *)m->epi, (void *)m->scs, (void *)m->pos,
-                      (void *)m->nlive, (void *)m->al_cols})
+                      (void *)m->nlive, (void *)m->al_cols, (void *)m->sx_cols, (void *)m->sx_state, (void *)m->sx_rho, (void *)m->sx_counts})
         if (ptr) hipFree(ptr);
     if (m->nlive_host) {
         hipHostFree(m->nlive_host);
@@ -431,6 +449,17 @@ static void fill_epi(bq_msolver *m, int c, int do_update, bq_epilogue &e) {
 
 // the device epilogue table: the records' buffers may have been re-allocated by a run with more steps
 static int upload_epi(bq_msolver *m) {
+    if (m->simplex) {
+        std::vector<bq_sx_col> h((size_t)m->k);
+        for (int c = 0; c < m->k; ++c) {
+            const bq_solver *s = m->cls[c];
+            h[c] = bq_sx_col{(long long)m->p->n, s->x, s->g, s->d, s->ub, m->sx_mass[c], m->sx_full[c], m->sx_has_x0 ? 1 : 0,
+                             s->sc, m->sx_state + c, s->stats};
+        }
+        BQ_HIP(hipMemcpyAsync(m->sx_cols, h.data(), sizeof(bq_sx_col) * h.size(), hipMemcpyHostToDevice, m->p->ctx->stream));
+        BQ_SYNC(m->p->ctx);   // h goes out of scope
+        return BQ_OK;
+    }
     if (m->al) {
         std::vector<bq_epilogue> h((size_t)m->k);
         std::vector<bq_al_col> cols((size_t)m->k);
@@ -716,6 +745,97 @@ extern "C" int bq_msolver_create_al(bq_problem *p, const bq_al_params *prm, int 
     return BQ_OK;
 }
 
+extern "C" int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB, const double *mass, const double *x0, double tol,
+                                         int64_t max_iter, bq_msolver **out) {
+    BQ_ARG(p && UB && mass && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->structure == BQ_PLAIN && p->kernel >= 0, "the simplex solver takes a kernel-built BQ_PLAIN problem");
+    BQ_ARG(p->diag_add == 0.0, "the simplex solver takes a problem without a diagonal term");
+    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
+        bq_set_error("the batched solver needs a single-rank context and a resident packed panel (not streamed, not full rows)");
+        return BQ_ERR_BADARG;
+    }
+    BQ_ARG(tol >= 0.0, "tol must be >= 0");
+    const int64_t n = p->n;
+    std::vector<int> full((size_t)k);
+    BQ_TRY(bq_sx_check(k, n, UB, mass, full.data()));
+    if (x0)   // inside its set: the box exactly, the mass to the rounding of a sum of n terms
+        for (int c = 0; c < k; ++c) {
+            long double sum = 0.0L;
+            for (int64_t i = 0; i < n; ++i) {
+                const double x = x0[(int64_t)c * n + i];
+                BQ_ARG(x >= 0.0 && x <= UB[(int64_t)c * n + i], "x0 must lie in its box");
+                sum += x;
+            }
+            BQ_ARG(std::fabs((double)sum - mass[c]) <= (double)n * 2.220446049250313e-16 * mass[c], "x0 must sum to its column's mass");
+        }
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    bq_msolver *m = new bq_msolver();
+    m->p = p;
+    p->refs += 1;
+    m->kind = BQ_PG;
+    m->k = k;
+    m->ldw = p->ld;
+    m->wide = true;
+    m->simplex = true;
+    m->sx_has_x0 = x0 != nullptr;
+    m->sx_mass.assign(mass, mass + k);
+    m->sx_full = full;
+    const std::vector<double> zero(x0 ? 0 : (size_t)n, 0.0);
+    int rc = BQ_OK;
+    for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
+        bq_solver *s = nullptr;   // the column's vectors, scalars (eps = tol) and records
+        rc = bq_solver_create(p, BQ_PG, nullptr, UB + (int64_t)cl * n, x0 ? x0 + (int64_t)cl * n : zero.data(), tol, max_iter, 0.0, &s);
+        if (rc == BQ_OK) m->cls.push_back(s);
+    }
+    if (rc == BQ_OK) rc = msolver_alloc(m, nullptr, nullptr);
+    if (rc == BQ_OK) {
+        hipError_t e = hipMalloc(&m->sx_cols, sizeof(bq_sx_col) * k);
+        if (e == hipSuccess) e = hipMalloc(&m->sx_state, sizeof(bq_sx_state) * k);
+        if (e == hipSuccess) e = hipMalloc(&m->sx_rho, sizeof(double) * k);
+        if (e == hipSuccess) e = hipMalloc(&m->sx_counts, sizeof(long long) * 2 * k);
+        if (e == hipSuccess) e = hipMemsetAsync(m->sx_state, 0, sizeof(bq_sx_state) * k, c->stream);
+        if (e != hipSuccess) {
+            bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
+            rc = BQ_ERR_NOMEM;
+        }
+    }
+    if (rc == BQ_OK) rc = upload_epi(m);
+    if (rc != BQ_OK) {
+        bq_msolver_destroy(m);
+        return rc;
+    }
+    *out = m;
+    return BQ_OK;
+}
+
+extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n_sv, int64_t *n_free) {
+    BQ_ARG(m && rho && n_sv && n_free, "NULL argument");
+    BQ_ARG(m->simplex, "the offsets take a solver of bq_msolver_create_simplex");
+    BQ_ARG(m->initialised, "the offsets take a solver that has run");
+    bq_ctx *c = m->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int k = m->k;
+    double *dr = m->sx_rho;
+    long long *dn = m->sx_counts;
+    int rc = bq_sx_launch_offsets(m->sx_cols, k, dr, dn, dn + k, st);
+    if (rc == BQ_OK) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
+        hipError_t e = hipMemcpyAsync(rho, dr, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + k, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("simplex offsets: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    if (rc == BQ_OK) rc = bq_ctx_sync(c);
+    else (void)bq_ctx_sync(c);
+    return rc;
+}
+
 extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const double *epsilon, double *intercept, int64_t *n_sv,
                                       double *sse, int64_t *n_held) {
     BQ_ARG(m && y && epsilon && intercept && n_sv && sse && n_held, "NULL argument");
@@ -907,6 +1027,11 @@ extern "C" int bq_msolver_pairs_heldout(bq_msolver *m, const unsigned char *data
 static int msolver_first(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
+    if (m->simplex) {   // x = P(0) where no start point was given, g = K x, f, the violation
+        BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->pos, m->W, m->ldw, true, st));
+        BQ_TRY(msolver_product(m, m->k));
+        return bq_sx_launch_start(m->sx_cols, m->k, m->out, m->ldw, st);
+    }
     const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);
     const bool svr = p->structure == BQ_SVR;
     if (svr) mstart_prep_svr_kernel<<<grid, 256, 0, st>>>(m->epi, m->W, m->ldw);
@@ -922,6 +1047,12 @@ static int msolver_first(bq_msolver *m) {
 static int msolver_iterate(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
+    if (m->simplex) {
+        BQ_TRY(bq_sx_launch_top(m->sx_cols, m->k, m->pos, m->nlive, st));
+        BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->pos, m->W, m->ldw, false, st));
+        BQ_TRY(msolver_product(m, m->live_host));
+        return bq_sx_launch_close(m->sx_cols, m->k, m->pos, m->out, m->ldw, st);
+    }
     const bq_epilogue *epi = m->epi + (m->started ? m->k : 0);
     m->started = true;
     const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)m->k);

@@ -1,5 +1,5 @@
 __all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV',
-           'CalibratedSVC', 'PairwiseCoupledSVC']
+           'CalibratedSVC', 'PairwiseCoupledSVC', 'OneClassSVM', 'one_class_nu_path']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
@@ -8,3 +8,4 @@ from .model_selection import SVCGridSearchCV, SVRGridSearchCV
 from .multioutput import MultiOutputSVR
 from .calibration import CalibratedSVC
 from .coupling import PairwiseCoupledSVC
+from .oneclass import OneClassSVM, one_class_nu_path

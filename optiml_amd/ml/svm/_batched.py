@@ -1,6 +1,7 @@
-"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`, `SVRGridSearchCV`): the
-device solver of many columns on one Gram panel (`_DeviceMultiSolver`: ProjectedGradient / FrankWolfe; `_DeviceALSolver`: the
-augmented-Lagrangian dual with the first-order rules), the one-off multi-column products, the device memory budget of a solve, and
+"""What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`, `SVRGridSearchCV`,
+`OneClassSVM`): the device solver of many columns on one Gram panel (`_DeviceMultiSolver`: ProjectedGradient / FrankWolfe;
+`_DeviceALSolver`: the augmented-Lagrangian dual with the first-order rules; `_DeviceSimplexSolver`: the nu-one-class dual on its
+capped simplex), the one-off multi-column products, the device memory budget of a solve, and
 the way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
 """
 import ctypes as C
@@ -177,6 +178,44 @@ class _DeviceSVRSolver(_DeviceMultiSolver):
         _lib.check(self._lib.bq_msolver_svr_heldout(self._h, _lib.ptr(y), _lib.ptr(eps), _lib.ptr(b), n_sv.ctypes.data_as(i64),
                                                     _lib.ptr(sse), n_held.ctypes.data_as(i64)))
         return b, n_sv, sse, n_held
+
+
+class _DeviceSimplexSolver(_DeviceMultiSolver):
+    """`bq_msolver_create_simplex`: k nu-one-class duals min 1/2 x'Kx over {0 <= x <= UB[c], sum x = mass[c]} on one 'plain'
+    problem.  UB: k x n boxes (a zero-width entry: a row the column does not train on), mass: k, x0: k x n or None (the projection
+    of 0); tol: the bound on libsvm's maximal-violating-pair measure.  The records' r1, r2, r3 are that measure, the step length
+    and the spectral step."""
+
+    def __init__(self, problem, UB, mass, tol, max_iter, x0=None):
+        UB = np.ascontiguousarray(np.atleast_2d(UB), dtype=float)
+        self._mass = _lib.as_f64(mass, UB.shape[0], 'mass')
+        _DeviceMultiSolver.__init__(self, problem, None, UB, None, tol, max_iter, x0=x0)
+
+    def _create(self, handle, kind, UB, ub, x0, eps, max_iter, t):
+        x0 = self._x0(x0)
+        return self._lib.bq_msolver_create_simplex(handle, self.k, _lib.ptr(UB), _lib.ptr(self._mass), _lib.ptr(x0), eps, max_iter,
+                                                   C.byref(self._h))
+
+    def offsets(self):
+        """(rho, n_sv, n_free), k entries each, of the columns as they stand (`bq_msolver_simplex_offsets`): libsvm's
+        calculate_rho, the rows with x > 0 and the rows strictly inside their box."""
+        rho = np.empty(self.k)
+        n_sv, n_free = np.empty(self.k, dtype=np.int64), np.empty(self.k, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        _lib.check(self._lib.bq_msolver_simplex_offsets(self._h, _lib.ptr(rho), n_sv.ctypes.data_as(i64), n_free.ctypes.data_as(i64)))
+        return rho, n_sv, n_free
+
+
+def simplex_project(V, UB, mass):
+    """The Euclidean projection of every row of V (k x n) onto {0 <= p <= UB[c], sum p = mass[c]} by the simplex solver's projection
+    kernel (`bq_simplex_project`), one workgroup per row."""
+    V = np.ascontiguousarray(np.atleast_2d(V), dtype=float)
+    k, n = V.shape
+    UB = _lib.as_f64(UB, k * n, 'UB')
+    mass = _lib.as_f64(mass, k, 'mass')
+    P = np.empty_like(V)
+    _lib.check(_lib.load().bq_simplex_project(get_context().handle, k, n, _lib.ptr(V), _lib.ptr(UB), _lib.ptr(mass), _lib.ptr(P)))
+    return P
 
 
 class _DeviceALSolver(_DeviceMultiSolver):
