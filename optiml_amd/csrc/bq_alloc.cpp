@@ -201,3 +201,6 @@ hipError_t bq_device_malloc(void **ptr, size_t bytes) {
     if (e != hipSuccess) (void)hipGetLastError();
     return e;
 }
+
+// the counterpart of bq_device_malloc for what it handed out (bq_scratch.h frees through it)
+hipError_t bq_device_free(void *ptr) { return hipFree(ptr); }

@@ -1869,3 +1869,12 @@ extern "C" int bq_cholesky_solve(bq_ctx *c, int64_t n, const double *A, const do
     return bq_chol_solve_dense_impl(c, n, A, b, x, factor_ms);
 }
 
+extern "C" int bq_ctx_mem_info(bq_ctx *c, int64_t *free_bytes, int64_t *total_bytes) {
+    BQ_ARG(c && free_bytes && total_bytes, "NULL argument");
+    BQ_HIP(hipSetDevice(c->device));
+    size_t f = 0, t = 0;
+    BQ_HIP(hipMemGetInfo(&f, &t));
+    *free_bytes = (int64_t)f;
+    *total_bytes = (int64_t)t;
+    return BQ_OK;
+}

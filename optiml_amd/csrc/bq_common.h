@@ -62,6 +62,7 @@ static inline bool bq_hook_on(const char *name) { return bq_hook_value(name, 1.0
 // live contexts keep cached (bq_ctx.panel_cache) back to the driver and tries once more
 // ---------------------------------------------------------------------------------------------
 hipError_t bq_device_malloc(void **ptr, size_t bytes);
+hipError_t bq_device_free(void *ptr);
 template <typename T>
 static inline hipError_t bq_device_malloc(T **ptr, size_t bytes) { return bq_device_malloc((void **)ptr, bytes); }
 #ifndef BQ_NO_MALLOC_REDIRECT
@@ -153,6 +154,12 @@ int bq_ctx_event_sync(bq_ctx *ctx, hipEvent_t ev);
 int bq_ctx_wait_flag(bq_ctx *ctx, const volatile int *flag, int want);   // a word the device posts into mapped pinned memory
 void bq_watchdog_stop(bq_ctx *ctx);   // joins the thread (context destruction)
 #define BQ_SYNC(ctx) BQ_TRY(bq_ctx_sync(ctx))
+// the close of a one-shot entry point: synchronise whatever rc says (host arrays of the caller and of the frame are in flight, and
+// the call's bq_scratch is freed after it); the earlier failure is the one reported
+static inline int bq_ctx_sync_after(bq_ctx *ctx, int rc) {
+    const int synced = bq_ctx_sync(ctx);
+    return rc != BQ_OK ? rc : synced;
+}
 
 struct bq_problem {
     bq_ctx *ctx = nullptr;
@@ -386,7 +393,14 @@ int bq_launch_pairs_all_live(const bq_pairs_plan *pl, hipStream_t st);
 const int *bq_pairs_plan_tiles(const bq_pairs_plan *pl);
 const int *bq_pairs_plan_pairs(const bq_pairs_plan *pl);
 
-// bq_msolver.hip: one multi-column product from host arrays, the body of bq_problem_gram_matmat(_wide) and
+// the refusal of what takes one rank and the resident packed lower triangle; `subject` heads the sentence, `detail` ends it
+static inline int bq_need_resident_panel(const bq_problem *p, const char *subject, const char *detail = "") {
+    if (p->ctx->world == 1 && !p->streamed && p->symmetric) return BQ_OK;
+    bq_set_error("%s needs a single-rank context and a resident packed panel%s", subject, detail);
+    return BQ_ERR_BADARG;
+}
+
+// bq_symm.hip: one multi-column product from host arrays, the body of bq_problem_gram_matmat(_wide) and
 // bq_problem_gram_matmat_pairs.  W's k rows (p->n each) go into `slots` zeroed device columns of stride p->ldN,
 // launch(arg, dW, ldw, slab, dOUT, nlive) runs on them with a slab of slab_len doubles and *nlive = k, and OUT's first k columns come
 // back into out; zero_out zero-fills OUT before the launch.  Synchronises and frees; `name` heads the error messages.

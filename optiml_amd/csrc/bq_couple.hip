@@ -18,6 +18,7 @@
 // the same bits and the same sweep count from the same clipped s (R).  No atomics and nothing of another point: a point's result
 // has the same bits alone, at any position and in any batch.  The wave leaves when its own point has converged.
 #include "bq_common.h"
+#include "bq_scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -129,6 +130,7 @@ static int couple_launch(int k, int64_t points, const double *F, int64_t f_row, 
 struct couple_buffers {
     int k = 0;
     int64_t t = 0, P = 0;
+    bq_scratch mem;   // every device buffer of the call, the caller's own included: freed when the buffers go out of scope
     double *A = nullptr, *B = nullptr, *prob = nullptr, *R = nullptr;
     int *iters = nullptr;
 
@@ -136,11 +138,12 @@ struct couple_buffers {
         k = ncls;
         t = points;
         P = (int64_t)ncls * (ncls - 1) / 2;
-        hipError_t e = hipMalloc(&A, sizeof(double) * P);
-        if (e == hipSuccess) e = hipMalloc(&B, sizeof(double) * P);
-        if (e == hipSuccess) e = hipMalloc(&prob, sizeof(double) * t * k);
-        if (e == hipSuccess) e = hipMalloc(&iters, sizeof(int) * t);
-        if (e == hipSuccess && want_R) e = hipMalloc(&R, sizeof(double) * t * P);
+        A = mem.dev<double>(P);
+        B = mem.dev<double>(P);
+        prob = mem.dev<double>(t * k);
+        iters = mem.dev<int>(t);
+        if (want_R) R = mem.dev<double>(t * P);
+        hipError_t e = mem.error();
         if (e == hipSuccess) e = hipMemcpyAsync(A, hA, sizeof(double) * P, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(B, hB, sizeof(double) * P, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
@@ -159,10 +162,6 @@ struct couple_buffers {
         }
         return BQ_OK;
     }
-    void release() {
-        for (void *ptr : {(void *)A, (void *)B, (void *)prob, (void *)R, (void *)iters})
-            if (ptr) hipFree(ptr);
-    }
 };
 
 extern "C" int bq_pairwise_coupling(bq_ctx *c, int ncls, int64_t t, const double *F, const double *A, const double *B, double *prob,
@@ -170,11 +169,12 @@ extern "C" int bq_pairwise_coupling(bq_ctx *c, int ncls, int64_t t, const double
     BQ_TRY(couple_check(c, ncls, t, F, A, B, prob));
     BQ_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    couple_buffers buf;
+    couple_buffers buf;   // freed after the closing sync
     double *dF = nullptr;
     int rc = buf.alloc(ncls, t, A, B, R != nullptr, st);
     if (rc == BQ_OK) {
-        hipError_t e = hipMalloc(&dF, sizeof(double) * t * buf.P);
+        dF = buf.mem.dev<double>(t * buf.P);
+        hipError_t e = buf.mem.error();
         if (e == hipSuccess) e = hipMemcpyAsync(dF, F, sizeof(double) * t * buf.P, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
             bq_set_error("pairwise coupling setup failed: %s", hipGetErrorString(e));
@@ -183,11 +183,7 @@ extern "C" int bq_pairwise_coupling(bq_ctx *c, int ncls, int64_t t, const double
     }
     if (rc == BQ_OK) rc = couple_launch(ncls, t, dF, buf.P, 1, buf.A, buf.B, buf.prob, buf.iters, buf.R, st);
     if (rc == BQ_OK) rc = buf.download(prob, iters, R, st);
-    if (rc == BQ_OK) rc = bq_ctx_sync(c);   // F, A, B and the results are the caller's
-    else (void)bq_ctx_sync(c);
-    buf.release();
-    if (dF) hipFree(dF);
-    return rc;
+    return bq_ctx_sync_after(c, rc);   // F, A, B and the results are the caller's
 }
 
 extern "C" int bq_decision_coupled(bq_ctx *c, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
@@ -202,7 +198,7 @@ extern "C" int bq_decision_coupled(bq_ctx *c, int kernel, double gamma, double c
            "unknown kernel");
     BQ_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    couple_buffers buf;
+    couple_buffers buf;   // freed after the closing sync
     int rc = buf.alloc(ncls, t, A, B, R != nullptr, st);
     if (rc == BQ_OK) {
         // the decision values of a chunk of test points are coupled where the reduce kernel left them: column q of point i at
@@ -219,8 +215,5 @@ extern "C" int bq_decision_coupled(bq_ctx *c, int kernel, double gamma, double c
             &cl);
     }
     if (rc == BQ_OK) rc = buf.download(prob, iters, R, st);
-    if (rc == BQ_OK) rc = bq_ctx_sync(c);
-    else (void)bq_ctx_sync(c);
-    buf.release();
-    return rc;
+    return bq_ctx_sync_after(c, rc);
 }

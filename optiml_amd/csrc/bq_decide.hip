@@ -27,6 +27,7 @@
 // unit in ascending order in the registers; then the units in ascending order (decide_reduce_kernel).  The SV range is cut
 // into units of U tiles so that few test points still fill the chip; U depends on (t, m, d) only.
 #include "bq_common.h"
+#include "bq_scratch.h"
 
 #include "bq_gram_image.h"
 #include "bq_mfma_tile.h"
@@ -177,8 +178,8 @@ static int64_t decide_unit_tiles(int64_t t, int64_t m, int64_t d) {
 int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                              const double *SV, int k, const double *W, const double *b, int64_t t, const double *Xt,
                              double *out, bq_decision_chunk_fn after_chunk, void *arg) {
+    bq_scratch mem;   // declared first: freed after every path's last use of the stream
     gram_images A, B;
-    double *dSV = nullptr, *dXt = nullptr, *dW = nullptr, *db = nullptr, *part = nullptr, *dout = nullptr;
     const int64_t kp = bq_round_up(k, 16), mp = bq_round_up(m, BQ_GT), tp = bq_round_up(t, BQ_GT);
     const int64_t tiles_m = mp / BQ_GT;
     int64_t U = decide_unit_tiles(t, m, d);
@@ -198,11 +199,10 @@ int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0
     BQ_ARG(units <= 65535 && chunk / BQ_GT <= 2147483647, "decision grid too large");
     const int gmax = kp <= 16 ? 1 : 4;
     const int64_t groups = kp / 16, passes = (groups + gmax - 1) / gmax;
-    auto cleanup = [&]() {
+    auto cleanup = [&]() {   // every return past this point: nothing of this frame (hW, hb, mem) is in flight afterwards
+        (void)hipStreamSynchronize(ctx->stream);
         free_image(&A);
         free_image(&B);
-        for (double *p : {dSV, dXt, dW, db, part, dout})
-            if (p) hipFree(p);
     };
 #define DEC_HIP(e)                                                          \
     do {                                                                    \
@@ -221,12 +221,9 @@ int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0
         for (int64_t j = 0; j < m; ++j) hW[(size_t)(j * kp + c)] = wc[j];
         if (b) hb[(size_t)c] = b[c];
     }
-    DEC_HIP(hipMalloc(&dSV, sizeof(double) * m * d));
-    DEC_HIP(hipMalloc(&dXt, sizeof(double) * t * d));
-    DEC_HIP(hipMalloc(&dW, sizeof(double) * mp * kp));
-    DEC_HIP(hipMalloc(&db, sizeof(double) * kp));
-    DEC_HIP(hipMalloc(&part, sizeof(double) * units * chunk * kp));
-    DEC_HIP(hipMalloc(&dout, sizeof(double) * (int64_t)k * t));
+    double *dSV = mem.dev<double>(m * d), *dXt = mem.dev<double>(t * d), *dW = mem.dev<double>(mp * kp), *db = mem.dev<double>(kp);
+    double *part = mem.dev<double>(units * chunk * kp), *dout = mem.dev<double>((int64_t)k * t);
+    DEC_HIP(mem.error());
     DEC_HIP(hipMemcpyAsync(dSV, SV, sizeof(double) * m * d, hipMemcpyHostToDevice, ctx->stream));
     DEC_HIP(hipMemcpyAsync(dXt, Xt, sizeof(double) * t * d, hipMemcpyHostToDevice, ctx->stream));
     DEC_HIP(hipMemcpyAsync(dW, hW.data(), sizeof(double) * mp * kp, hipMemcpyHostToDevice, ctx->stream));
@@ -287,7 +284,6 @@ int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0
                                                                                       dout, t, r0);
         DEC_HIP(hipGetLastError());
         if (after_chunk && (rc = after_chunk(arg, dout, r0, r1)) != BQ_OK) {
-            (void)hipStreamSynchronize(ctx->stream);
             cleanup();
             return rc;
         }

@@ -1,0 +1,322 @@
+// What scores a finished batch of the batched solver (bq_msolver.hip): from every column's point, its coefficients to the column's
+// own slot (not pos[]: every column is scored, live or not), one product in which every column is live, and per column a workgroup
+// of 1024 threads that sums in a fixed order (thread t the rows t, t + 1024, ... ascending, then a fixed tree: no atomics, and nothing
+// of another column enters).  bq_msolver_svr_heldout: the intercept and the held-out squared error of a column of a
+// cross-validated SVR search.  bq_msolver_svc_heldout / _pairs_heldout: the intercept, the held-out decision values and their Platt
+// fit (bq_platt.hip) per calibrator.  bq_msolver_simplex_offsets: the offsets of the nu-one-class columns (bq_simplex.hip).
+#include "bq_msolver.h"
+#include "bq_scratch.h"
+
+#include <cmath>
+
+static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
+
+// the coefficients of fitted_svc / fitted_svr (svm/_batched.py), their threshold and their expression
+template <bool SVR>
+__global__ __launch_bounds__(256) void mcoef_kernel(const bq_epilogue *__restrict__ epi, double *__restrict__ W, int64_t ldw) {
+    const bq_epilogue &e = epi[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const bool sv = SVR ? (e.x[i] > 1e-6 || e.x[e.n + i] > 1e-6) : e.x[i] > 1e-6;
+    W[blockIdx.y * ldw + i] = sv ? bq_mcol_input(e, i, SVR) : 0.0;
+}
+
+// the fixed tree over the workgroup's 1024 partial sums and counts; every thread returns with the totals in s[0], c[0]
+__device__ inline void msvr_tree(double *s, int *c, int tid) {
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if (tid < st) {
+            s[tid] += s[tid + st];
+            c[tid] += c[tid + st];
+        }
+        __syncthreads();
+    }
+}
+
+// bq_msolver_svr_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1, the support rows (x+ or x- above 1e-6):
+// S = sum (y - u), n_sv, b = (S - epsilon) / n_sv in svr_intercept's order.  Pass 2, the held-out rows (ub = 0 on both halves):
+// sse = sum (y - (u + b))^2, n_held.  Thread t sums the rows t, t + 1024, ... in ascending order, then the tree: no atomics, and
+// nothing of another column enters.  n_sv = 0: intercept = sse = NaN.
+__global__ __launch_bounds__(1024) void msvr_score_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out, int64_t ldw,
+                                                          const double *__restrict__ y, const double *__restrict__ epsilon,
+                                                          double *__restrict__ intercept, long long *__restrict__ n_sv,
+                                                          double *__restrict__ sse, long long *__restrict__ n_held) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_epilogue &e = epi[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = e.n;
+    double s = 0.0;
+    int cnt = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool sv = e.x[i] > 1e-6 || e.x[n + i] > 1e-6;
+        s += sv ? y[i] - u[i] : 0.0;
+        cnt += sv ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = cnt;
+    msvr_tree(sd, sc, tid);
+    const int nsv = sc[0];
+    double b = sd[0];
+    b -= epsilon[blockIdx.x];
+    b = nsv > 0 ? b / (double)nsv : NAN;
+    __syncthreads();   // sd[0], sc[0] are read: pass 2 may overwrite them
+    s = 0.0;
+    cnt = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool held = e.ub[i] == 0.0 && e.ub[n + i] == 0.0;
+        const double r = y[i] - (u[i] + b);
+        s += held ? r * r : 0.0;
+        cnt += held ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = cnt;
+    msvr_tree(sd, sc, tid);
+    if (tid == 0) {
+        intercept[blockIdx.x] = b;
+        n_sv[blockIdx.x] = nsv;
+        sse[blockIdx.x] = sd[0];   // NaN with b
+        n_held[blockIdx.x] = sc[0];
+    }
+}
+
+// the first pass of the held-out kernels of an SVC column, u = K coef: over the support rows (x above 1e-6) S = sum (y - u) and
+// n_sv, summed as msvr_score_kernel sums; returns b = S / n_sv in intercept()'s order (svm/_batched.py; n_sv = 0: NaN) to every
+// thread and writes both figures
+__device__ inline double msvc_intercept(const bq_epilogue &e, const double *__restrict__ u, double *sd, int *sc, int tid,
+                                        double *__restrict__ intercept, long long *__restrict__ n_sv) {
+    const long long n = e.n;
+    double s = 0.0;
+    int cnt = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool sv = e.x[i] > 1e-6;
+        s += sv ? e.sgn[i] - u[i] : 0.0;
+        cnt += sv ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = cnt;
+    msvr_tree(sd, sc, tid);
+    const int nsv = sc[0];
+    const double b = nsv > 0 ? sd[0] / (double)nsv : NAN;
+    if (tid == 0) {
+        *intercept = b;
+        *n_sv = nsv;
+    }
+    return b;
+}
+
+// bq_msolver_svc_heldout and bq_msolver_pairs_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1: msvc_intercept.
+// Pass 2, the held-out rows: the decision value u + b and the label y to row cal_of[column] of D and L (row stride n; zeroed by the
+// caller; the columns of a calibrator hold out disjoint rows, so no two workgroups write one entry).  n_sv = 0: b = NaN.
+// The held-out rows are those with ub = 0 of [0, n) (pairs null), or, for column = pair (a, b) of a class-sorted panel, the data rows
+// (data_row: 1; a ghost row: 0) with ub = 0 of the tile rows of a and of b — ub is 0 on every row of another class too, and such a
+// row is in no pair's sample
+__global__ __launch_bounds__(1024) void mheldout_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
+                                                        int64_t ldw, const int *__restrict__ pairs, const int *__restrict__ ct,
+                                                        const unsigned char *__restrict__ data_row, const int *__restrict__ cal_of,
+                                                        double *__restrict__ D, double *__restrict__ L, double *__restrict__ intercept,
+                                                        long long *__restrict__ n_sv) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_epilogue &e = epi[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = e.n;
+    const double b = msvc_intercept(e, u, sd, sc, tid, intercept + blockIdx.x, n_sv + blockIdx.x);
+    const int cal = cal_of[blockIdx.x];
+    if (cal < 0) return;
+    double *d = D + (long long)cal * n, *l = L + (long long)cal * n;
+    for (int side = 0; side < (pairs ? 2 : 1); ++side) {
+        long long r0 = 0, r1 = n;
+        if (pairs) {
+            const int cls = pairs[2 * blockIdx.x + side];
+            r0 = (long long)ct[cls] * BQ_SYM_TILE;
+            r1 = (long long)ct[cls + 1] * BQ_SYM_TILE < n ? (long long)ct[cls + 1] * BQ_SYM_TILE : n;
+        }
+        for (long long i = r0 + tid; i < r1; i += 1024) {
+            if ((pairs == nullptr || data_row[i]) && e.ub[i] == 0.0) {
+                d[i] = u[i] + b;
+                l[i] = e.sgn[i];
+            }
+        }
+    }
+}
+
+extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n_sv, int64_t *n_free) {
+    BQ_ARG(m && rho && n_sv && n_free, "NULL argument");
+    BQ_ARG(m->method == BQ_M_SIMPLEX, "the offsets take a solver of bq_msolver_create_simplex");
+    BQ_ARG(m->initialised, "the offsets take a solver that has run");
+    bq_ctx *c = m->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int k = m->k;
+    double *dr = m->sx_rho;
+    long long *dn = m->sx_counts;
+    int rc = bq_sx_launch_offsets(m->sx_cols, k, dr, dn, dn + k, st);
+    if (rc == BQ_OK) {
+        hipError_t e = hipMemcpyAsync(rho, dr, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + k, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("simplex offsets: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    return bq_ctx_sync_after(c, rc);
+}
+
+extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const double *epsilon, double *intercept, int64_t *n_sv,
+                                      double *sse, int64_t *n_held) {
+    BQ_ARG(m && y && epsilon && intercept && n_sv && sse && n_held, "NULL argument");
+    BQ_ARG(bq_msolver_is_boxes(m, BQ_SVR), "held-out scoring takes a solver of bq_msolver_create_svr_boxes");
+    bq_problem *p = m->p;
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int k = m->k;
+    const int64_t n = p->n;
+    bq_scratch mem;   // freed after the closing sync
+    double *dy = mem.dev<double>(n), *deps = mem.dev<double>(k), *db = mem.dev<double>(k), *dsse = mem.dev<double>(k);
+    long long *dnsv = mem.dev<long long>(k), *dnheld = mem.dev<long long>(k);
+    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    hipError_t e = mem.error();
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(deps, epsilon, sizeof(double) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("held-out scoring setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) {
+        mcoef_kernel<true><<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, m->W, m->ldw);
+        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+    }
+    if (rc == BQ_OK) {
+        msvr_score_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dy, deps, db, dnsv, dsse, dnheld);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(sse, dsse, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("held-out scoring: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    return bq_ctx_sync_after(c, rc);   // y, epsilon, k and the results are the caller's and this frame's
+}
+
+// bq_msolver_svc_heldout (data_row null: the 16-column product) and bq_msolver_pairs_heldout (the pair-routed product with every
+// pair live), after their own argument checks
+static int msolver_heldout(bq_msolver *m, const unsigned char *data_row, int ncal, const int *cal_of, double *intercept,
+                           int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags,
+                           double *dec) {
+    BQ_ARG(ncal >= 1, "ncal must be >= 1");
+    bq_problem *p = m->p;
+    bq_ctx *c = p->ctx;
+    const int k = m->k;
+    const int64_t n = p->n;
+    {   // the columns of a calibrator hold out disjoint rows: two columns may not write one entry of its sample
+        std::vector<std::vector<int>> cols((size_t)ncal);
+        for (int cl = 0; cl < k; ++cl) {
+            BQ_ARG(cal_of[cl] >= -1 && cal_of[cl] < ncal, "cal_of entries are -1 or a calibrator in [0, ncal)");
+            if (cal_of[cl] >= 0) cols[cal_of[cl]].push_back(cl);
+        }
+        std::vector<unsigned char> seen;
+        for (const std::vector<int> &cs : cols) {
+            if (cs.size() < 2) continue;
+            seen.assign((size_t)n, 0);
+            for (int cl : cs) {
+                const unsigned char *h = m->held.data() + (size_t)cl * (size_t)n;
+                for (int64_t i = 0; i < n; ++i) {
+                    const unsigned char hi = h[i] && (data_row == nullptr || data_row[i]);
+                    BQ_ARG(!(hi && seen[i]), "columns that share a calibrator must have disjoint held-out rows");
+                    seen[i] |= hi;
+                }
+            }
+        }
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t len = (size_t)ncal * (size_t)n;
+    bq_scratch mem;   // freed after the closing sync
+    double *dD = mem.dev<double>(len);
+    unsigned char *drow = data_row ? mem.dev<unsigned char>((size_t)n) : nullptr;
+    double *dL = mem.dev<double>(len), *db = mem.dev<double>(k);
+    long long *dnsv = mem.dev<long long>(k);
+    int *dcal = mem.dev<int>(k);
+    double *dA = mem.dev<double>(ncal), *dB = mem.dev<double>(ncal), *dloss = mem.dev<double>(ncal);
+    long long *dpos = mem.dev<long long>(ncal), *dneg = mem.dev<long long>(ncal);
+    int *diters = mem.dev<int>(ncal), *dflags = mem.dev<int>(ncal);
+    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    hipError_t e = mem.error();
+    if (e == hipSuccess && data_row) e = hipMemcpyAsync(drow, data_row, (size_t)n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dD, 0, sizeof(double) * len, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dL, 0, sizeof(double) * len, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dcal, cal_of, sizeof(int) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("held-out calibration setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    auto failed = [&](hipError_t err) {   // of a launch or a copy past the set-up
+        if (err == hipSuccess) return;
+        bq_set_error("held-out calibration: %s", hipGetErrorString(err));
+        rc = BQ_ERR_HIP;
+    };
+    if (rc == BQ_OK) {
+        mcoef_kernel<false><<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, m->W, m->ldw);
+        failed(hipGetLastError());
+    }
+    if (rc == BQ_OK && m->plan) {
+        // every pair live for this product, as bq_problem_gram_matmat_pairs has them; then the liveness of the columns' states
+        // again, which is what the last iteration left (bq_launch_pairs_live is a function of the states alone)
+        rc = bq_launch_pairs_all_live(m->plan, st);
+        if (rc == BQ_OK) {
+            rc = bq_launch_symmp(p, m->plan, false, m->W, m->ldw, m->slab, m->out);
+            const int back = bq_launch_pairs_live(m->plan, m->scs, m->nlive, st);   // also when the product could not be launched
+            if (rc == BQ_OK) rc = back;
+        }
+    } else if (rc == BQ_OK) {
+        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+    }
+    if (rc == BQ_OK) {
+        mheldout_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, m->plan ? bq_pairs_plan_pairs(m->plan) : nullptr,
+                                            m->plan ? bq_pairs_plan_tiles(m->plan) : nullptr, drow, dcal, dD, dL, db, dnsv);
+        failed(hipGetLastError());
+    }
+    if (rc == BQ_OK) rc = bq_launch_platt(ncal, n, dD, dL, dA, dB, diters, dloss, dpos, dneg, dflags, st);
+    if (rc == BQ_OK) {
+        e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(A, dA, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(B, dB, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(loss, dloss, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_pos, dpos, sizeof(int64_t) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_neg, dneg, sizeof(int64_t) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(iters, diters, sizeof(int) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(flags, dflags, sizeof(int) * ncal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && dec) e = hipMemcpyAsync(dec, dD, sizeof(double) * len, hipMemcpyDeviceToHost, st);
+        failed(e);
+    }
+    return bq_ctx_sync_after(c, rc);   // cal_of, k and the results are the caller's and this frame's
+}
+
+extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A,
+                                      double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg, int *flags,
+                                      double *dec) {
+    BQ_ARG(m && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
+    BQ_ARG(bq_msolver_is_boxes(m, BQ_SVC), "held-out calibration takes a solver of bq_msolver_create_boxes");
+    return msolver_heldout(m, nullptr, ncal, cal_of, intercept, n_sv, A, B, iters, loss, n_pos, n_neg, flags, dec);
+}
+
+extern "C" int bq_msolver_pairs_heldout(bq_msolver *m, const unsigned char *data_row, int ncal, const int *cal_of,
+                                        double *intercept, int64_t *n_sv, double *A, double *B, int *iters, double *loss,
+                                        int64_t *n_pos, int64_t *n_neg, int *flags, double *dec) {
+    BQ_ARG(m && data_row && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
+    BQ_ARG(m->plan != nullptr && !m->held.empty(), "held-out calibration of pairs takes a solver of bq_msolver_create_pairs");
+    return msolver_heldout(m, data_row, ncal, cal_of, intercept, n_sv, A, B, iters, loss, n_pos, n_neg, flags, dec);
+}

@@ -5,11 +5,12 @@
 // f_new >= f + 1e-4 step g'd down to 1e-10, at most 100 iterations.
 //
 // A calibrator reads its own row of D (decision values) and L (labels: > 0 positive, < 0 negative, 0 not in the sample: such a
-// row enters no sum).  Every sum is taken as msvr_score_kernel (bq_msolver.hip) takes its sums: thread t adds the rows t, t + 1024,
+// row enters no sum).  Every sum is taken as msvr_score_kernel (bq_mscore.hip) takes its sums: thread t adds the rows t, t + 1024,
 // ... in ascending order, then a fixed tree over LDS; no atomics, nothing of another calibrator, so (A, B) have the same bits alone,
 // at any position and in any batch.  Every thread reads the reduced values from LDS and so the whole workgroup takes every branch
 // together; workgroups do not communicate.  The kernel is latency-bound (a handful of iterations over n values that stay in L2).
 #include "bq_common.h"
+#include "bq_scratch.h"
 
 #include <cmath>
 
@@ -164,18 +165,12 @@ extern "C" int bq_platt_fit(bq_ctx *c, int ncal, int64_t n, const double *D, con
     hipStream_t st = c->stream;
     static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
     const size_t len = (size_t)ncal * (size_t)n;
-    double *dD = nullptr, *dL = nullptr, *dA = nullptr, *dB = nullptr, *dloss = nullptr;
-    long long *dpos = nullptr, *dneg = nullptr;
-    int *diters = nullptr, *dflags = nullptr;
-    hipError_t e = hipMalloc(&dD, sizeof(double) * len);
-    if (e == hipSuccess) e = hipMalloc(&dL, sizeof(double) * len);
-    if (e == hipSuccess) e = hipMalloc(&dA, sizeof(double) * ncal);
-    if (e == hipSuccess) e = hipMalloc(&dB, sizeof(double) * ncal);
-    if (e == hipSuccess) e = hipMalloc(&dloss, sizeof(double) * ncal);
-    if (e == hipSuccess) e = hipMalloc(&dpos, sizeof(long long) * ncal);
-    if (e == hipSuccess) e = hipMalloc(&dneg, sizeof(long long) * ncal);
-    if (e == hipSuccess) e = hipMalloc(&diters, sizeof(int) * ncal);
-    if (e == hipSuccess) e = hipMalloc(&dflags, sizeof(int) * ncal);
+    bq_scratch mem;   // freed after the closing sync
+    double *dD = mem.dev<double>(len), *dL = mem.dev<double>(len);
+    double *dA = mem.dev<double>(ncal), *dB = mem.dev<double>(ncal), *dloss = mem.dev<double>(ncal);
+    long long *dpos = mem.dev<long long>(ncal), *dneg = mem.dev<long long>(ncal);
+    int *diters = mem.dev<int>(ncal), *dflags = mem.dev<int>(ncal);
+    hipError_t e = mem.error();
     if (e == hipSuccess) e = hipMemcpyAsync(dD, D, sizeof(double) * len, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dL, L, sizeof(double) * len, hipMemcpyHostToDevice, st);
     int rc = BQ_OK;
@@ -197,10 +192,5 @@ extern "C" int bq_platt_fit(bq_ctx *c, int ncal, int64_t n, const double *D, con
             rc = BQ_ERR_HIP;
         }
     }
-    if (rc == BQ_OK) rc = bq_ctx_sync(c);   // D, L and the results are the caller's
-    else (void)bq_ctx_sync(c);
-    for (void *ptr : {(void *)dD, (void *)dL, (void *)dA, (void *)dB, (void *)dloss, (void *)dpos, (void *)dneg, (void *)diters,
-                      (void *)dflags})
-        if (ptr) hipFree(ptr);
-    return rc;
+    return bq_ctx_sync_after(c, rc);   // D, L and the results are the caller's
 }

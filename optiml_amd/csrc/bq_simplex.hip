@@ -17,6 +17,7 @@
 // tree of sx_block (a butterfly inside each wavefront, the 16 wavefronts in order), so a column's bits depend on its own
 // (x, g, s, u, r) alone: not on the batch, not on its slot.  A column is one workgroup; nothing waits on another workgroup.
 #include "bq_common.h"
+#include "bq_scratch.h"
 #include "bq_simplex.h"
 
 #include <cmath>
@@ -547,13 +548,11 @@ extern "C" int bq_simplex_project(bq_ctx *c, int k, int64_t n, const double *V, 
     BQ_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t len = sizeof(double) * (size_t)k * (size_t)n;
-    double *dV = nullptr, *dU = nullptr, *dP = nullptr, *dm = nullptr;
-    int *df = nullptr;
-    hipError_t e = hipMalloc(&dV, len);
-    if (e == hipSuccess) e = hipMalloc(&dU, len);
-    if (e == hipSuccess) e = hipMalloc(&dP, len);
-    if (e == hipSuccess) e = hipMalloc(&dm, sizeof(double) * k);
-    if (e == hipSuccess) e = hipMalloc(&df, sizeof(int) * k);
+    bq_scratch mem;   // freed after the closing sync
+    const size_t cells = (size_t)k * (size_t)n;
+    double *dV = mem.dev<double>(cells), *dU = mem.dev<double>(cells), *dP = mem.dev<double>(cells), *dm = mem.dev<double>(k);
+    int *df = mem.dev<int>(k);
+    hipError_t e = mem.error();
     if (e == hipSuccess) e = hipMemcpyAsync(dV, V, len, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dU, UB, len, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dm, mass, sizeof(double) * k, hipMemcpyHostToDevice, st);
@@ -568,9 +567,5 @@ extern "C" int bq_simplex_project(bq_ctx *c, int k, int64_t n, const double *V, 
         bq_set_error("bq_simplex_project: %s", hipGetErrorString(e));
         rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
     }
-    if (rc == BQ_OK) rc = bq_ctx_sync(c);   // the host arrays are the caller's and this frame's
-    else (void)bq_ctx_sync(c);
-    for (void *ptr : {(void *)dV, (void *)dU, (void *)dP, (void *)dm, (void *)df})
-        if (ptr) (void)hipFree(ptr);
-    return rc;
+    return bq_ctx_sync_after(c, rc);   // the host arrays are the caller's and this frame's
 }

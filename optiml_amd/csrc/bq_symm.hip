@@ -22,8 +22,9 @@
 //
 // This file's own part is the 4-column VALU strip kernel; its association is its own, so it shares no body with the other product
 // kernels.  Shared: the storage dispatch of bq_launch_symm (bq_panel_dispatch, bq_c7.h), the slab walk (slab_walk under
-// seg_thread_sum, bq_symv_tile.h) and the one-off host product around the launcher (bq_product_once, bq_msolver.hip).
+// seg_thread_sum, bq_symv_tile.h) and the one-off host product around the launcher (bq_product_once, below).
 #include "bq_common.h"
+#include "bq_scratch.h"
 #include "bq_symv_tile.h"
 
 constexpr int SJG = 2;   // tiles per strip
@@ -188,4 +189,58 @@ int bq_launch_symm(bq_problem *p, bool add_one, const double *W, int64_t ldw, in
         BQ_HIP(hipGetLastError());
     }
     return BQ_OK;
+}
+
+int bq_product_once(bq_problem *p, const char *name, int k, int64_t slots, int64_t slab_len, bool zero_out, const double *W,
+                    double *out, bq_product_launch launch, void *arg) {
+    bq_ctx *c = p->ctx;
+    const int64_t ldw = p->ldN;
+    bq_scratch mem;   // freed after the closing sync
+    double *dW = mem.dev<double>(ldw * slots), *dO = mem.dev<double>(ldw * slots), *slab = mem.dev<double>(slab_len);
+    int *nl = mem.dev<int>(1);
+    hipError_t e = mem.error();
+    if (e == hipSuccess) e = hipMemsetAsync(dW, 0, sizeof(double) * ldw * slots, c->stream);
+    if (e == hipSuccess && zero_out) e = hipMemsetAsync(dO, 0, sizeof(double) * ldw * slots, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(dW, sizeof(double) * ldw, W, sizeof(double) * p->n, sizeof(double) * p->n, k,
+                                              hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(nl, &k, sizeof(int), hipMemcpyHostToDevice, c->stream);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("%s setup failed: %s", name, hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) rc = launch(arg, dW, ldw, slab, dO, nl);
+    if (rc == BQ_OK) {
+        e = hipMemcpy2DAsync(out, sizeof(double) * p->n, dO, sizeof(double) * ldw, sizeof(double) * p->n, k, hipMemcpyDeviceToHost,
+                             c->stream);
+        if (e != hipSuccess) {
+            bq_set_error("%s copy: %s", name, hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    return bq_ctx_sync_after(c, rc);
+}
+
+static int gram_matmat(bq_problem *p, int k, const double *W, double *out, bool wide) {
+    BQ_ARG(p && W && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->kernel >= 0, "not a kernel-structured problem");
+    BQ_TRY(bq_need_resident_panel(p, "the multi-column product"));
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    struct call { bq_problem *p; int k; bool wide; } cl{p, k, wide};
+    return bq_product_once(
+        p, "gram_matmat", k, bq_round_up(k, wide ? BQ_SYMMW_CK : BQ_SYMM_CK), wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb),
+        false, W, out,
+        [](void *arg, const double *dW, int64_t ldw, double *slab, double *dO, const int *nl) {
+            const call *c = (const call *)arg;
+            return c->wide ? bq_launch_symmw(c->p, false, dW, ldw, c->k, slab, dO, nl)
+                           : bq_launch_symm(c->p, false, dW, ldw, c->k, slab, dO, nl);
+        },
+        &cl);
+}
+
+extern "C" int bq_problem_gram_matmat(bq_problem *p, int k, const double *W, double *out) { return gram_matmat(p, k, W, out, false); }
+
+extern "C" int bq_problem_gram_matmat_wide(bq_problem *p, int k, const double *W, double *out) {
+    return gram_matmat(p, k, W, out, true);
 }

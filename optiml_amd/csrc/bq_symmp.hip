@@ -582,10 +582,7 @@ extern "C" int bq_problem_gram_matmat_pairs(bq_problem *p, int ncls, const int *
                                             double *out) {
     BQ_ARG(p && W && out, "NULL argument");
     BQ_ARG(p->kernel >= 0, "not a kernel-structured problem");
-    if (p->ctx->world != 1 || p->streamed || !p->symmetric) {
-        bq_set_error("the routed product needs a single-rank context and a resident packed panel");
-        return BQ_ERR_BADARG;
-    }
+    BQ_TRY(bq_need_resident_panel(p, "the routed product"));
     BQ_HIP(hipSetDevice(p->ctx->device));
     bq_pairs_plan *pl = nullptr;
     BQ_TRY(bq_pairs_plan_create(p, ncls, cls_tiles, m, pairs, &pl));

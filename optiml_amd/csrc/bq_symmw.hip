@@ -165,3 +165,7 @@ int bq_launch_symmw(bq_problem *p, bool add_one, const double *W, int64_t ldw, i
     }
     return BQ_OK;
 }
+
+extern "C" int64_t bq_problem_wide_slab_bytes(const bq_problem *p) {
+    return p == nullptr ? 0 : (int64_t)sizeof(double) * bq_symmw_slab_len(p->nb);
+}

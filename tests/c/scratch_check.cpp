@@ -1,0 +1,124 @@
+// bq_scratch (optiml_amd/csrc/bq_scratch.h), the owner of a one-shot entry point's device buffers, against counting stubs of
+// bq_device_malloc / bq_device_free: no HIP runtime is linked.  For m = 0..6 requests with request f failing (every f < m, and
+// none): every request after the failure returns null without reaching the allocator, error() is the first failure, and the
+// destructor frees exactly the pointers handed out, once each.  A zero-count request is hipMalloc(0) as the converted functions
+// had it: the allocator IS asked (so the retry and its test hook see the request), answers success with a null pointer, the
+// chain goes on, and nothing is freed for it.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+enum hipError_t { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2 };
+#include "bq_scratch.h"
+
+static int g_calls = 0, g_fail_at = -1;
+static hipError_t g_fail_code = hipErrorOutOfMemory;
+static std::vector<void *> g_live, g_freed;
+static std::vector<size_t> g_sizes;
+
+hipError_t bq_device_malloc(void **ptr, size_t bytes) {
+    const int call = g_calls++;
+    g_sizes.push_back(bytes);
+    if (call == g_fail_at) return g_fail_code;
+    *ptr = bytes ? malloc(bytes) : nullptr;   // hipMalloc(0): success and a null pointer
+    if (*ptr) g_live.push_back(*ptr);
+    return hipSuccess;
+}
+
+hipError_t bq_device_free(void *ptr) {
+    g_freed.push_back(ptr);
+    free(ptr);   // a double free or a pointer never handed out is AddressSanitizer's to report
+    return hipSuccess;
+}
+
+#define CHECK(cond)                                                       \
+    do {                                                                  \
+        if (!(cond)) {                                                    \
+            printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);      \
+            exit(1);                                                      \
+        }                                                                 \
+    } while (0)
+
+static void reset(int fail_at, hipError_t code) {
+    g_calls = 0;
+    g_fail_at = fail_at;
+    g_fail_code = code;
+    g_live.clear();
+    g_freed.clear();
+    g_sizes.clear();
+}
+
+// m requests of different types and sizes, request `fail` (or none: -1) refused with `code`
+static void chain(int m, int fail, hipError_t code) {
+    reset(fail, code);
+    std::vector<void *> got;
+    {
+        bq_scratch mem;
+        CHECK(mem.error() == hipSuccess);
+        for (int r = 0; r < m; ++r) {
+            void *p = r % 3 == 0 ? (void *)mem.dev<double>(r + 1) : r % 3 == 1 ? (void *)mem.dev<long long>(2 * r + 1) : (void *)mem.dev<int>(r + 5);
+            if (fail >= 0 && r >= fail) {
+                CHECK(p == nullptr);
+                CHECK(mem.error() == code);               // the first failure, and it stays
+                CHECK(g_calls == fail + 1);               // no request after it reaches the allocator
+            } else {
+                CHECK(p != nullptr);
+                CHECK(mem.error() == hipSuccess);
+                CHECK(g_calls == r + 1);                  // one allocation per request
+                const size_t want = r % 3 == 0 ? sizeof(double) * (r + 1) : r % 3 == 1 ? sizeof(long long) * (2 * r + 1) : sizeof(int) * (r + 5);
+                CHECK(g_sizes.back() == want);            // of exactly the request's bytes
+                got.push_back(p);
+            }
+        }
+        CHECK(g_freed.empty());                           // nothing is freed before the owner goes
+    }
+    CHECK(got == g_live);
+    CHECK(g_freed.size() == got.size());                  // exactly the pointers handed out, once each (any order)
+    for (void *p : got) {
+        int n = 0;
+        for (void *q : g_freed) n += q == p;
+        CHECK(n == 1);
+    }
+}
+
+static void zero_count() {
+    reset(-1, hipSuccess);
+    void *a = nullptr, *c = nullptr;
+    {
+        bq_scratch mem;
+        a = mem.dev<double>(3);
+        double *z = mem.dev<double>(0);
+        CHECK(z == nullptr && mem.error() == hipSuccess);   // success, a null pointer
+        CHECK(g_calls == 2 && g_sizes.back() == 0);         // and the allocator was asked
+        c = mem.dev<int>(2);
+        CHECK(c != nullptr && g_calls == 3);                // the chain goes on
+    }
+    CHECK(g_freed.size() == 2);                             // nothing is freed for the empty request
+    CHECK((g_freed[0] == a && g_freed[1] == c) || (g_freed[0] == c && g_freed[1] == a));
+}
+
+// more requests than the owner has room for: refused as a failed allocation, what was handed out is still freed
+static void over_capacity() {
+    reset(-1, hipSuccess);
+    {
+        bq_scratch mem;
+        for (int r = 0; r < bq_scratch::CAP; ++r) CHECK(mem.dev<int>(1) != nullptr);
+        CHECK(mem.dev<int>(1) == nullptr && mem.error() == hipErrorOutOfMemory);
+        CHECK(g_calls == bq_scratch::CAP);
+    }
+    CHECK((int)g_freed.size() == bq_scratch::CAP);
+}
+
+int main() {
+    for (int m = 0; m <= 6; ++m) {
+        chain(m, -1, hipSuccess);
+        for (int f = 0; f < m; ++f) {
+            chain(m, f, hipErrorOutOfMemory);
+            chain(m, f, hipErrorInvalidValue);
+        }
+    }
+    zero_count();
+    over_capacity();
+    printf("scratch_check ok\n");
+    return 0;
+}

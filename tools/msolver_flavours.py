@@ -1,0 +1,219 @@
+#!/usr/bin/env python3
+"""One fit per flavour of the batched solver (csrc/bq_msolver.hip, bq_mscore.hip) at the smallest shapes that reach its edges, and a
+SHA-256 of everything a column produces: x, g, its iteration records, and every output of the held-out calls and of the simplex
+offsets.  Two builds of the library that print the same file compute the same bits:
+
+    python3 tools/msolver_flavours.py [path/to/libbcqp_hip.so] > flavours.txt
+
+n = 300 (two 256-row tiles, the second ragged); k = 5 on the 4-column product and k = 17 on the 16-column one (a full chunk and a
+ragged one); three classes of unequal sizes for the pairs (the class-sorted panel has ghost rows); two calibrators over disjoint
+held-out folds; the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
+iteration counts), so pos[] renumbers.
+"""
+import hashlib
+import os
+import sys
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from optiml_amd import _lib  # noqa: E402
+
+if len(sys.argv) > 1:
+    _lib.LIB_PATH = os.path.abspath(sys.argv[1])   # as tools/bench_with_lib.py
+
+from optiml_amd.ml.svm import MultiOutputSVR, OneVsRestSVC, multiclass, multioutput  # noqa: E402
+from optiml_amd.ml.svm._batched import _DeviceMultiSolver, _DeviceSimplexSolver, _DeviceSVRSolver  # noqa: E402
+from optiml_amd.ml.svm.coupling import chunk_calibrators, coupling_columns  # noqa: E402
+from optiml_amd.ml.svm.kernels import GaussianKernel  # noqa: E402
+from optiml_amd.ml.svm.losses import epsilon_insensitive, hinge  # noqa: E402
+from optiml_amd.ml.svm.onevsone import _DevicePairSolver  # noqa: E402
+from optiml_amd.opti import KernelQuadratic  # noqa: E402
+from optiml_amd.opti.unconstrained.stochastic import AdaGrad  # noqa: E402
+
+N, D = 300, 6
+KERNEL = GaussianKernel(gamma=0.5)
+warnings.simplefilter('ignore')
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def show(name, **arrays):
+    for key, a in arrays.items():
+        print('%-34s %-10s %s' % (name, key, sha(a)))
+
+
+def data(seed=0):
+    rs = np.random.RandomState(seed)
+    X = rs.standard_normal((N, D))
+    return rs, X
+
+
+def labels(rs, X, k):
+    """k label rows +-1 of different difficulty: column c separates along its own random direction with its own offset"""
+    W = rs.standard_normal((k, D))
+    off = np.linspace(-1.0, 1.0, k)
+    return np.where(X @ W.T + off > 0, 1.0, -1.0).T.copy()
+
+
+def folds(k, nfold, C=1.0):
+    """k x N boxes: column c holds out fold c % nfold (rows r with r % nfold == fold), except every (nfold + 1)-th column, which
+    trains on all rows; cal_of: two calibrators, each fed by the nfold fold columns of one label row"""
+    UB = np.full((k, N), C)
+    cal_of = np.full(k, -1, dtype=np.int32)
+    rows = np.arange(N)
+    for c in range(k):
+        f = c % (nfold + 1)
+        if f < nfold:
+            UB[c, rows % nfold == f] = 0.0
+            if c // (nfold + 1) < 2:
+                cal_of[c] = c // (nfold + 1)
+    return UB, cal_of
+
+
+def run_to_end(solver, name, steps=48, rounds=12):
+    """bq_msolver_run in pieces of `steps` until every column has stopped; the records of every piece, then the state"""
+    recs = [[] for _ in range(solver.k)]
+    for _ in range(rounds):
+        part, status = solver.run(steps)
+        for c in range(solver.k):
+            recs[c].append(part[c])
+        if 'unknown' not in status:
+            break
+    iters = []
+    for c in range(solver.k):
+        it, st, f = solver.state(c)
+        iters.append(it)
+        show('%s[%d]' % (name, c), x=solver.get(c, _lib.GET_X_NOW), g=solver.get(c, _lib.GET_G_NOW),
+             records=np.concatenate(recs[c]), state=np.array([it, f]))
+        print('%-34s %-10s %s' % ('%s[%d]' % (name, c), 'status', st))
+    print('%-34s %-10s %s' % (name, 'iters', iters))
+
+
+def fit_show(name, fit):
+    show(name, **{k: v for k, v in fit.items()})
+
+
+def plain(kind, kname, eps):
+    rs, X = data(1)
+    Y = labels(rs, X, 5)
+    obj = KernelQuadratic(X, -np.ones(N), 'svc', KERNEL, y=Y[0])
+    s = _DeviceMultiSolver(obj.device_problem(), kind, Y, np.ones(N), eps, 400)
+    run_to_end(s, 'svc_%s_k5' % kname)
+    s.close()
+    obj.release()
+
+
+def boxes():
+    rs, X = data(2)
+    Y = np.repeat(labels(rs, X, 6), 3, axis=0)[:17]   # (label row, fold 0 / fold 1 / all the data)
+    UB, cal_of = folds(17, 2)
+    obj = KernelQuadratic(X, -np.ones(N), 'svc', KERNEL, y=Y[0])
+    s = _DeviceMultiSolver(obj.device_problem(), _lib.PG, Y, UB, 1e-4, 400)
+    run_to_end(s, 'svc_boxes_k17')
+    b, n_sv, fit = s.heldout_svc(cal_of, 2, decisions=True)
+    show('svc_boxes_k17.heldout', intercept=b, n_sv=n_sv)
+    fit_show('svc_boxes_k17.heldout', fit)
+    s.close()
+    obj.release()
+
+
+def pairs():
+    rs, X = data(3)
+    codes = np.repeat([0, 1, 2], [150, 100, 50])[rs.permutation(N)]
+    X = X + 0.8 * rs.standard_normal((3, D))[codes]
+    rows = np.arange(N)
+    splits = [(rows[rows % 2 != f], rows[rows % 2 == f]) for f in range(2)]
+    plan = coupling_columns(codes, 3, splits, 1.0)
+    Xp = np.zeros((plan['n_pad'], D))
+    Xp[plan['index']] = X
+    obj = KernelQuadratic(Xp, -np.ones(plan['n_pad']), 'svc', KERNEL, y=np.ones(plan['n_pad']))
+    cal_of, cal_pairs = chunk_calibrators(plan['cols'])
+    chunk = [plan['pairs'][p] for p, _ in plan['cols']]
+    s = _DevicePairSolver(obj.device_problem(), _lib.PG, plan['cls_tiles'], chunk, plan['Y'], plan['UB'], 1e-4, 400)
+    run_to_end(s, 'svc_pairs_k%d' % len(chunk))
+    b, n_sv, fit = s.heldout_pairs(plan['data_row'], cal_of, len(cal_pairs), decisions=True)
+    show('svc_pairs.heldout', intercept=b, n_sv=n_sv)
+    fit_show('svc_pairs.heldout', fit)
+    s.close()
+    obj.release()
+
+
+def svr(k, with_boxes):
+    rs, X = data(4 + k)
+    T = np.sin(X @ rs.standard_normal((D, k))).T + 0.1 * rs.standard_normal((k, N))
+    T[2] = 0.0   # q > 0: the column ends at x = 0 after a few iterations, and is scored without a support vector (NaN)
+    eps = np.linspace(0.05, 0.3, k)
+    QL = np.concatenate([-T, T], axis=1) + eps[:, None]
+    obj = KernelQuadratic(X, QL[0], 'svr', KERNEL)
+    if with_boxes:
+        UB1, _ = folds(k, 2)
+        ub = np.concatenate([UB1, UB1], axis=1)
+    else:
+        ub = np.ones(2 * N)
+    name = 'svr_boxes_k%d' % k if with_boxes else 'svr_k%d' % k
+    s = _DeviceSVRSolver(obj.device_problem(), _lib.PG, QL, ub, 1e-4, 400)
+    run_to_end(s, name)
+    if with_boxes:
+        # every column is scored against one target vector: what is compared is the sums' bits
+        b, n_sv, sse, n_held = s.heldout(T[0], eps)
+        show(name + '.heldout', intercept=b, n_sv=n_sv, sse=sse, n_held=n_held)
+    s.close()
+    obj.release()
+
+
+def simplex():
+    rs, X = data(9)
+    nus = np.linspace(0.05, 0.85, 17)
+    UB, _ = folds(17, 2, C=1.0)
+    mass = np.array([nus[c] * np.count_nonzero(UB[c]) for c in range(17)])
+    obj = KernelQuadratic(X, np.zeros(N), 'plain', KERNEL)
+    s = _DeviceSimplexSolver(obj.device_problem(), UB, mass, 1e-4, 400)
+    run_to_end(s, 'simplex_k17')
+    rho, n_sv, n_free = s.offsets()
+    show('simplex_k17.offsets', rho=rho, n_sv=n_sv, n_free=n_free)
+    s.close()
+    obj.release()
+
+
+def lagrangian():
+    """the augmented-Lagrangian batch through its estimators (the rule's parameters are theirs to build): what
+    solve_batched_al hands back for every column"""
+    def hashed(module, name):
+        inner = module.solve_batched_al
+
+        def wrapped(solver, *a, **kw):
+            out = inner(solver, *a, **kw)
+            for c, r in enumerate(out):
+                show('%s[%d]' % (name, c), x=r['x'], past_x=r['past_x'], g=r['g'], step=r['step'], dual=r['dual'], records=r['rows'],
+                     state=np.array([r['iter'], r['f_x']]))
+            print('%-34s %-10s %s' % (name, 'iters', [int(r['iter']) for r in out]))
+            return out
+        module.solve_batched_al = wrapped
+
+    hashed(multiclass, 'al_svc_k5')
+    hashed(multioutput, 'al_svr_k5')
+    rs, X = data(10)
+    codes = rs.randint(0, 5, N)
+    X = X + 1.5 * rs.standard_normal((5, D))[codes]
+    kw = dict(kernel=KERNEL, C=1.0, reg_intercept=False, dual=True, optimizer=AdaGrad, learning_rate=1., max_iter=300, tol=0.05, random_state=1)
+    est = OneVsRestSVC(loss=hinge, **kw).fit(X, codes)
+    assert est.batched_ and est.lagrangian_
+    T = np.sin(X @ rs.standard_normal((D, 5)))
+    est = MultiOutputSVR(loss=epsilon_insensitive, epsilon=0.1, **kw).fit(X, T)
+    assert est.batched_ and est.lagrangian_
+
+
+if __name__ == '__main__':
+    plain(_lib.PG, 'pg', 1e-2)
+    plain(_lib.FW, 'fw', 1e-1)
+    boxes()
+    pairs()
+    svr(5, False)
+    svr(17, True)
+    simplex()
+    lagrangian()
