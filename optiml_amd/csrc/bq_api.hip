@@ -1,4 +1,5 @@
-// C-ABI entry points (include/bcqp.h): contexts, the device-resident quadratic, solver drivers.
+// C-ABI entry points (include/bcqp.h): contexts, the device-resident quadratic, the one-shot wrappers (the solvers: bq_solver.hip;
+// the probes and bq_problem_time_matvec: bq_probe.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -6,7 +7,7 @@
 #include <cstdlib>
 #include <functional>
 
-#include "bq_al.h"
+#include "bq_common.h"
 #include "bq_c7.h"
 #include "bq_h52.h"
 
@@ -336,28 +337,21 @@ extern "C" int bq_sym_row_block(int64_t n, int rank, int world, int64_t *begin, 
 static int problem_alloc_common(bq_problem *p, const double *q_host) {
     bq_ctx *c = p->ctx;
     const int64_t nblk = p->ldN / BQ_VEC_TILE;
-    BQ_HIP(hipMalloc(&p->q, sizeof(double) * p->ldN));
-    BQ_HIP(hipMemsetAsync(p->q, 0, sizeof(double) * p->ldN, c->stream));
-    BQ_HIP(hipMemcpyAsync(p->q, q_host, sizeof(double) * p->N, hipMemcpyHostToDevice, c->stream));
-    BQ_HIP(hipMalloc(&p->w, sizeof(double) * p->ld));
-    BQ_HIP(hipMemsetAsync(p->w, 0, sizeof(double) * p->ld, c->stream));
+    hipError_t e = bq_dev_zeroed(hipSuccess, p->mem, &p->q, p->ldN, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->q, q_host, sizeof(double) * p->N, hipMemcpyHostToDevice, c->stream);
+    e = bq_dev_zeroed(e, p->mem, &p->w, p->ld, c->stream);
     const int64_t slen = bq_round_up(std::max(p->blk * c->world, p->nb * BQ_SYM_TILE), BQ_PAD);
     if (p->symmetric) {
-        if (!p->streamed) BQ_HIP(hipMalloc(&p->slab, sizeof(double) * p->nb * p->nb * BQ_SYM_TILE));   // streamed: its own scratch
-        if (c->comm_kind != BQ_COMM_NONE) {   // the gathered segment vectors of every rank (also a one-rank communicator)
-            const size_t gl = sizeof(double) * (size_t)c->world * p->seg_cmax * p->nb * BQ_SYM_TILE;
-            BQ_HIP(hipMalloc(&p->gath, gl));
-            BQ_HIP(hipMemsetAsync(p->gath, 0, gl, c->stream));
-        }
+        if (e == hipSuccess && !p->streamed) e = p->mem.dev(&p->slab, p->nb * p->nb * BQ_SYM_TILE);   // streamed: its own scratch
+        // the gathered segment vectors of every rank (also a one-rank communicator)
+        if (c->comm_kind != BQ_COMM_NONE) e = bq_dev_zeroed(e, p->mem, &p->gath, (size_t)c->world * p->seg_cmax * p->nb * BQ_SYM_TILE, c->stream);
     }
-    BQ_HIP(hipMalloc(&p->s, sizeof(double) * slen));
-    BQ_HIP(hipMemsetAsync(p->s, 0, sizeof(double) * slen, c->stream));
-    BQ_HIP(hipMalloc(&p->va, sizeof(double) * p->ldN));
-    BQ_HIP(hipMalloc(&p->vb, sizeof(double) * p->ldN));
-    BQ_HIP(hipMemsetAsync(p->va, 0, sizeof(double) * p->ldN, c->stream));
-    BQ_HIP(hipMemsetAsync(p->vb, 0, sizeof(double) * p->ldN, c->stream));
-    BQ_HIP(hipMalloc(&p->partials, sizeof(double) * BQ_MAX_PARTIAL_Q * nblk));
-    BQ_HIP(hipMalloc(&p->scal, sizeof(double) * 16));
+    e = bq_dev_zeroed(e, p->mem, &p->s, slen, c->stream);
+    e = bq_dev_zeroed(e, p->mem, &p->va, p->ldN, c->stream);
+    e = bq_dev_zeroed(e, p->mem, &p->vb, p->ldN, c->stream);
+    if (e == hipSuccess) e = p->mem.dev(&p->partials, BQ_MAX_PARTIAL_Q * nblk);
+    if (e == hipSuccess) e = p->mem.dev(&p->scal, 16);
+    BQ_HIP_CHAIN(e, "problem setup");
     return BQ_OK;
 }
 
@@ -440,9 +434,8 @@ extern "C" int bq_problem_destroy(bq_problem *p) {
     p->panel = nullptr;
     bq_ctx_release_held(p->ctx, p);
     bq_image_register(p, false);   // (after this no failing allocation touches p->himg)
-    for (void *ptr : {(void *)p->himg, (void *)p->panel_alloc, (void *)p->q, (void *)p->sgn, (void *)p->X, (void *)p->w, (void *)p->s,
-                      (void *)p->va, (void *)p->vb, (void *)p->partials, (void *)p->scal, (void *)p->slab, (void *)p->gath})
-        if (ptr) hipFree(ptr);
+    if (p->himg) hipFree(p->himg);   // the panel family is not the owner's (bq_problem::mem)
+    if (p->panel_alloc) hipFree(p->panel_alloc);
     bq_stream_free(p->stream_img);
     bq_ctx *c = p->ctx;
     delete p;
@@ -698,14 +691,14 @@ int bq_hessian_image_ensure(bq_problem *p) {
         return decided(BQ_HIMG_ALLOC_FAILED);
     }
     const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    bq_scratch mem;   // the conversion's flag; the image itself is the allocator's to take back (bq_problem::mem)
     int *bad_dev = nullptr;
     int rc = BQ_OK;
     auto give_up = [&](int err) {
         if (img) hipFree(img);
-        if (bad_dev) hipFree(bad_dev);
         return err;
     };
-    if (hipMemsetAsync(img, 0, bytes, c->stream) != hipSuccess || hipMalloc(&bad_dev, sizeof(int)) != hipSuccess) {
+    if (hipMemsetAsync(img, 0, bytes, c->stream) != hipSuccess || mem.dev(&bad_dev, 1) != hipSuccess) {
         bq_set_error("Hessian image setup failed: %s", hipGetErrorString(hipGetLastError()));
         return give_up(BQ_ERR_HIP);
     }
@@ -753,8 +746,6 @@ int bq_hessian_image_ensure(bq_problem *p) {
     if (rc == BQ_OK) rc = bq_ctx_sync(c);
     if (rc != BQ_OK) return give_up(rc);
     p->himg_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    hipFree(bad_dev);
-    bad_dev = nullptr;
     if (bad) {   // never reached from a compact panel (K in {0} u [2^-15, 1]): the safety net, as for the compact panel itself
         give_up(BQ_OK);
         return decided(BQ_HIMG_OUT_OF_DOMAIN);
@@ -829,7 +820,7 @@ extern "C" int bq_problem_create_kernel(bq_ctx *c, int structure, int64_t n, int
         return BQ_ERR_HIP;
     };
     hipError_t e;
-    if ((e = hipMalloc(&p->X, sizeof(double) * n * d)) != hipSuccess) return fail(e);
+    if ((e = p->mem.dev(&p->X, n * d)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(p->X, X, sizeof(double) * n * d, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e);
     int rc = BQ_OK;
     // An RBF panel in fp64 whose every element lies in [2^-14, 1] (bq_c7_eligible: a function of X and gamma only, so every rank
@@ -847,8 +838,7 @@ extern "C" int bq_problem_create_kernel(bq_ctx *c, int structure, int64_t n, int
         return rc;
     }
     if (structure == BQ_SVC) {
-        if ((e = hipMalloc(&p->sgn, sizeof(double) * p->ld)) != hipSuccess) return fail(e);
-        if ((e = hipMemsetAsync(p->sgn, 0, sizeof(double) * p->ld, c->stream)) != hipSuccess) return fail(e);
+        if ((e = bq_dev_zeroed(hipSuccess, p->mem, &p->sgn, p->ld, c->stream)) != hipSuccess) return fail(e);
         if ((e = hipMemcpyAsync(p->sgn, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e);
     }
     int bad = 0;
@@ -1025,811 +1015,6 @@ extern "C" int bq_problem_panel_rows(bq_problem *p, int64_t row0, int64_t nrows,
     }
     return BQ_OK;
 }
-
-extern "C" int bq_problem_time_matvec(bq_problem *p, int reps, double *mean_ms) {
-    BQ_ARG(p && mean_ms && reps > 0, "argument");
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    hipEvent_t e0, e1;
-    BQ_HIP(hipEventCreate(&e0));
-    BQ_HIP(hipEventCreate(&e1));
-    const bool prof = c->profiling;
-    c->profiling = false;
-    bq_seg_table tab;
-    if (p->symmetric) bq_sym_seg_table(p, &tab);
-    auto local = [&]() {
-        if (p->streamed)
-            return bq_stream_sym_product(c, p->stream_img, p->n, p->nb, tab, p->kernel, p->gamma, p->coef0, p->degree, p->add_one, p->w,
-                                         p->s, 0, nullptr);
-        return p->symmetric ? bq_launch_symv(c, bq_problem_panel(p), p->add_one, p->nb, tab, p->w, p->slab, p->s, nullptr)
-                            : bq_launch_gemv(c, p->panel, p->storage, p->add_one, p->r1 - p->r0, p->ld, p->w,
-                                             p->s + p->r0, nullptr);
-    };
-    int rc = local();  // warm
-    hipEventRecord(e0, c->stream);
-    for (int i = 0; rc == BQ_OK && i < reps; ++i) rc = local();
-    hipEventRecord(e1, c->stream);
-    hipError_t e = hipEventSynchronize(e1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    c->profiling = prof;
-    BQ_TRY(rc);
-    BQ_HIP(e);
-    *mean_ms = (double)ms / reps;
-    return BQ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// HBM streaming probe: what a plain read-only sweep and a device-to-device copy reach on this GPU, so that a roofline
-// fraction can be quoted against the measured ceiling as well as the nominal 8 TB/s
-// ---------------------------------------------------------------------------------------------
-typedef double probe_d2 __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(256) void probe_read_kernel(const probe_d2 *__restrict__ src, int64_t n2,
-                                                         double *__restrict__ sink) {
-    double acc = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
-        const probe_d2 v = __builtin_nontemporal_load(src + i);
-        acc += v.x + v.y;
-    }
-    if (acc == 12345.678) *sink = acc;   // keeps the loads alive, practically never true
-}
-
-extern "C" int bq_ctx_probe_bandwidth(bq_ctx *c, int64_t bytes, int reps, double *read_gbs, double *copy_gbs) {
-    BQ_ARG(c && read_gbs && copy_gbs, "NULL argument");
-    BQ_ARG(bytes >= (1 << 20) && reps >= 1, "bytes >= 1 MiB, reps >= 1");
-    BQ_HIP(hipSetDevice(c->device));
-    bytes &= ~(int64_t)4095;
-    double *a = nullptr, *b = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&a, (size_t)bytes);
-    if (e == hipSuccess) e = hipMalloc(&b, (size_t)bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(a, 0, (size_t)bytes, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(b, 0, (size_t)bytes, c->stream);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float ms_read = 0.f, ms_copy = 0.f;
-    if (e == hipSuccess) {
-        const int64_t n2 = bytes / 16;
-        const unsigned grid = (unsigned)(c->num_cu * 16);
-        probe_read_kernel<<<grid, 256, 0, c->stream>>>((const probe_d2 *)a, n2, b);   // warm
-        hipEventRecord(e0, c->stream);
-        for (int r = 0; r < reps; ++r) probe_read_kernel<<<grid, 256, 0, c->stream>>>((const probe_d2 *)a, n2, b);
-        hipEventRecord(e1, c->stream);
-        e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms_read, e0, e1);
-    }
-    if (e == hipSuccess) {
-        hipMemcpyAsync(b, a, (size_t)bytes, hipMemcpyDeviceToDevice, c->stream);   // warm
-        hipEventRecord(e0, c->stream);
-        for (int r = 0; r < reps; ++r) hipMemcpyAsync(b, a, (size_t)bytes, hipMemcpyDeviceToDevice, c->stream);
-        hipEventRecord(e1, c->stream);
-        e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms_copy, e0, e1);
-    }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (a) hipFree(a);
-    if (b) hipFree(b);
-    if (e != hipSuccess) {
-        bq_set_error("bandwidth probe failed: %s", hipGetErrorString(e));
-        return BQ_ERR_HIP;
-    }
-    *read_gbs = (double)bytes * reps / (ms_read * 1e-3) / 1e9;
-    *copy_gbs = 2.0 * (double)bytes * reps / (ms_copy * 1e-3) / 1e9;   // bytes read + bytes written
-    return BQ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// fp64 MFMA probe: what back-to-back v_mfma_f64_16x16x4_f64 with register operands sustain on this GPU at the clock it
-// holds under that load — the yardstick beside the nominal 78.6 TFLOP/s for the Cholesky's roofline fraction
-// ---------------------------------------------------------------------------------------------
-typedef double probe_d4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256, 2) void probe_mfma_kernel(double *sink, int iters, double seed) {
-    probe_d4 acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = (probe_d4){0.0, 0.0, 0.0, 0.0};
-    double a = seed + 1e-3 * (double)(threadIdx.x & 15), b = 1.0 - 1e-3 * (double)(threadIdx.x >> 4);
-    for (int it = 0; it < iters; ++it) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
-        a = -a;   // keeps the sums bounded without touching the MFMA stream's shape
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += acc[i].x + acc[i].y + acc[i].z + acc[i].w;
-    if (s == 12345.678) *sink = s;   // keeps the MFMAs alive, practically never true
-}
-
-extern "C" int bq_ctx_probe_mfma_f64(bq_ctx *c, double seconds, double *tflops) {
-    BQ_ARG(c && tflops, "NULL argument");
-    BQ_ARG(seconds > 0.0 && seconds <= 10.0, "seconds in (0, 10]");
-    BQ_HIP(hipSetDevice(c->device));
-    double *sink = nullptr;
-    BQ_HIP(hipMalloc(&sink, sizeof(double)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const int iters = 4096;
-    const unsigned grid = (unsigned)(c->num_cu * 2);           // 2 workgroups of 4 waves per CU: two waves per SIMD
-    const double flop_per_launch = (double)grid * 4.0 * iters * 16.0 * 2048.0;   // waves x iterations x MFMAs x 2*16*16*4
-    float ms = 0.f;
-    int launches = 0;
-    if (e == hipSuccess) {
-        // warm up for half the requested time so that the clock has settled under the load, then time the other half
-        probe_mfma_kernel<<<grid, 256, 0, c->stream>>>(sink, iters, 0.5);
-        hipEventRecord(e0, c->stream);
-        probe_mfma_kernel<<<grid, 256, 0, c->stream>>>(sink, iters, 0.5);
-        hipEventRecord(e1, c->stream);
-        e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        const int per_half = ms > 0.f ? std::max(1, (int)(seconds * 500.0 / ms)) : 1;
-        for (int i = 0; e == hipSuccess && i < per_half; ++i) probe_mfma_kernel<<<grid, 256, 0, c->stream>>>(sink, iters, 0.5);
-        if (e == hipSuccess) {
-            hipEventRecord(e0, c->stream);
-            for (int i = 0; i < per_half; ++i) probe_mfma_kernel<<<grid, 256, 0, c->stream>>>(sink, iters, 0.5);
-            hipEventRecord(e1, c->stream);
-            e = hipEventSynchronize(e1);
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-            launches = per_half;
-        }
-    }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    hipFree(sink);
-    if (e != hipSuccess || ms <= 0.f) {
-        bq_set_error("MFMA probe failed: %s", hipGetErrorString(e));
-        return BQ_ERR_HIP;
-    }
-    *tflops = flop_per_launch * launches / (ms * 1e-3) / 1e12;
-    return BQ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Stream occupancy probe (tests of the collective watchdog): ONE lane spins on the constant-rate wall clock for the given
-// time and then returns — it always terminates by itself, whatever the host does
-// ---------------------------------------------------------------------------------------------
-__global__ void probe_stall_kernel(long long ticks, long long *sink) {
-    const long long t0 = wall_clock64();
-    long long t = t0;
-    while (t - t0 < ticks) t = wall_clock64();
-    if (ticks < 0) *sink = t;   // never: keeps the loop
-}
-
-extern "C" int bq_ctx_probe_stall(bq_ctx *c, double milliseconds, int behind_collective) {
-    BQ_ARG(c != nullptr, "ctx is NULL");
-    BQ_ARG(milliseconds > 0.0 && milliseconds <= 5000.0, "milliseconds in (0, 5000]");
-    BQ_HIP(hipSetDevice(c->device));
-    int rate_khz = 0;
-    BQ_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, c->device));
-    if (rate_khz <= 0) rate_khz = 100000;   // 100 MHz on every part this library is built for
-    double *one = nullptr;
-    if (behind_collective) {
-        BQ_HIP(hipMalloc(&one, sizeof(double)));
-        BQ_HIP(hipMemsetAsync(one, 0, sizeof(double), c->stream));
-    }
-    probe_stall_kernel<<<1, 1, 0, c->stream>>>((long long)(milliseconds * (double)rate_khz), nullptr);
-    int rc = hipGetLastError() == hipSuccess ? BQ_OK : BQ_ERR_HIP;
-    if (rc == BQ_OK && behind_collective) rc = bq_exchange_sum(c, one, 1);
-    if (rc == BQ_OK) rc = bq_ctx_sync(c);
-    if (one) hipFree(one);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------------------
-// solvers
-// ---------------------------------------------------------------------------------------------
-static int alloc_vec(bq_solver *s, double **v) {
-    BQ_HIP(hipMalloc(v, sizeof(double) * s->ldN));
-    BQ_HIP(hipMemsetAsync(*v, 0, sizeof(double) * s->ldN, s->p->ctx->stream));
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_destroy(bq_solver *s) {
-    if (s == nullptr) return BQ_OK;
-    hipSetDevice(s->p->ctx->device);
-    (void)bq_ctx_sync(s->p->ctx);   // may sit behind a collective: bounded when a collective timeout is set
-    for (void *ptr : {(void *)s->x, (void *)s->g, (void *)s->d, (void *)s->Qd, (void *)s->lb, (void *)s->ub,
-                      (void *)s->lp, (void *)s->lm, (void *)s->rhs, (void *)s->hd, (void *)s->dlp, (void *)s->dlm,
-                      (void *)s->mL, (void *)s->mU, (void *)s->partials, (void *)s->sc, (void *)s->stats})
-        if (ptr) hipFree(ptr);
-    if (s->chol) bq_chol_ws_destroy(s->chol);
-    if (s->flag_host) {
-        hipHostFree(s->flag_host);
-        hipEventDestroy(s->flag_event);
-    }
-    bq_as_free(s);
-    delete s->resume;
-    if (s->al) {
-        bq_al_vecs &V = s->al->V;   // x, g, step (= s->d) and Qx (= s->Qd) are owned by the common slots above
-        for (void *ptr : {(void *)V.xe, (void *)V.chk, (void *)V.s1, (void *)V.s2, (void *)V.s3, (void *)V.a, (void *)V.llb, (void *)V.lub,
-                          (void *)V.lr_sched, (void *)V.mom_sched})
-            if (ptr) hipFree(ptr);
-        delete s->al;
-    }
-    bq_problem *p = s->p;
-    delete s;
-    // the solve the placement choice was made for is over: what it held back to keep this solve undisturbed can go now (bq_ctx::held)
-    bq_ctx_release_held(p->ctx, p);
-    bq_problem_unref(p);
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_create(bq_problem *p, int kind, const double *lb, const double *ub, const double *x0,
-                                double eps, int64_t max_iter, double fw_t, bq_solver **out) {
-    BQ_ARG(p && ub && out, "NULL argument");
-    BQ_ARG(kind == BQ_PG || kind == BQ_FW || kind == BQ_AS || kind == BQ_IP || kind == BQ_AS_CG, "solver kind");
-    const bool as_cg = kind == BQ_AS_CG;   // ActiveSet on products only: none of the dense-factor restrictions below
-    if (as_cg) kind = BQ_AS;
-    BQ_ARG(max_iter > 0, "max_iter must be > 0");             // optiml/opti/_base.py:73-74
-    BQ_ARG(fw_t >= 0.0 && fw_t < 1.0, "t has to lie in [0, 1)");  // frank_wolfe.py:84-85
-    if ((kind == BQ_IP || kind == BQ_AS) && !as_cg && p->ctx->world > 1) {
-        bq_set_error("InteriorPoint/ActiveSet factorise the whole Hessian: use a single-rank context (replicas only)");
-        return BQ_ERR_BADARG;
-    }
-    if ((kind == BQ_IP || kind == BQ_AS) && !as_cg && p->streamed) {
-        bq_set_error("InteriorPoint/ActiveSet assemble their systems from the resident panel: not available in the streamed mode");
-        return BQ_ERR_BADARG;
-    }
-    if ((kind == BQ_IP || kind == BQ_AS) && p->structure != BQ_PLAIN && !p->add_one) {
-        bq_set_error("InteriorPoint/ActiveSet are not built for the BQ_NO_RANK_ONE duals (svm/_base.py:621-624)");
-        return BQ_ERR_BADARG;
-    }
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    bq_solver *s = new bq_solver();
-    s->p = p;
-    p->refs += 1;
-    s->kind = kind;
-    s->as_cg = as_cg;
-    s->N = p->N;
-    s->ldN = p->ldN;
-    s->nblk = p->ldN / BQ_VEC_TILE;
-    int rc = BQ_OK;
-    for (double **v : {&s->x, &s->g, &s->d, &s->Qd, &s->lb, &s->ub})
-        if (rc == BQ_OK) rc = alloc_vec(s, v);
-    if (rc == BQ_OK && kind == BQ_IP)
-        for (double **v : {&s->lp, &s->lm, &s->rhs, &s->hd, &s->dlp, &s->dlm})
-            if (rc == BQ_OK) rc = alloc_vec(s, v);
-    if (rc != BQ_OK) {
-        bq_solver_destroy(s);
-        return rc;
-    }
-    std::vector<double> h((size_t)s->N);
-    auto up = [&](double *dev, const double *src) {
-        return hipMemcpyAsync(dev, src, sizeof(double) * s->N, hipMemcpyHostToDevice, c->stream);
-    };
-    hipError_t e = up(s->ub, ub);
-    if (e == hipSuccess && lb) e = up(s->lb, lb);
-    if (e == hipSuccess) {
-        if (x0) {
-            e = up(s->x, x0);
-        } else {
-            for (int64_t i = 0; i < s->N; ++i) h[i] = ((lb ? lb[i] : 0.0) + ub[i]) / 2;  // constrained/_base.py:65
-            e = up(s->x, h.data());
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc(&s->partials, sizeof(double) * BQ_MAX_PARTIAL_Q * s->nblk);
-    if (e == hipSuccess) e = hipMalloc(&s->sc, sizeof(bq_scal));
-    if (e == hipSuccess) {
-        memset(&s->host, 0, sizeof(bq_scal));
-        s->host.max_iter = max_iter;
-        s->host.eps = eps;
-        s->host.fw_t = fw_t;
-        s->host.status = BQ_STATUS_UNKNOWN;
-        s->host.best_lb = -INFINITY;
-        s->host.f = NAN;
-        e = hipMemcpyAsync(s->sc, &s->host, sizeof(bq_scal), hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) {   // may sit behind a collective of an earlier solve: the bounded wait
-        const int src = bq_ctx_sync(c);
-        if (src != BQ_OK) {
-            bq_solver_destroy(s);
-            return src;
-        }
-    }
-    if (e != hipSuccess) {
-        bq_set_error("solver setup failed: %s", hipGetErrorString(e));
-        bq_solver_destroy(s);
-        return BQ_ERR_HIP;
-    }
-    if (kind == BQ_PG || kind == BQ_FW) {   // their every iteration is one product with the rank-one term: the Hessian image (bq_h52.h)
-        rc = bq_hessian_image_ensure(p);
-        if (rc != BQ_OK) {
-            bq_solver_destroy(s);
-            return rc;
-        }
-    }
-    if ((kind == BQ_IP || kind == BQ_AS) && !as_cg) {
-        // InteriorPoint on the SVR structure factorises the reduced n x n system (bq_ip.hip)
-        rc = bq_chol_ws_create(c, (kind == BQ_IP && p->structure == BQ_SVR && bq_ip_svr_reduced()) ? p->n : s->N,
-                               &s->chol);
-        if (rc != BQ_OK) {
-            bq_solver_destroy(s);
-            return rc;
-        }
-    }
-    *out = s;
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_set_inner(bq_solver *s, double rtol, int64_t max_iter) {
-    BQ_ARG(s, "NULL solver");
-    BQ_ARG(s->kind == BQ_AS && s->as_cg, "only the conjugate-gradient ActiveSet (BQ_AS_CG) has an inner iteration");
-    BQ_ARG(rtol > 0.0 && rtol < 1.0, "inner tolerance must lie in (0, 1)");
-    BQ_ARG(max_iter >= 0, "inner iteration cap must be >= 0 (0: 2 |A| + 50)");
-    s->inner_rtol = rtol;
-    s->inner_max = max_iter;
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_inner_iters(bq_solver *s, int64_t *total) {
-    BQ_ARG(s && total, "NULL argument");
-    *total = s->kind == BQ_AS ? bq_as_inner_iters(s) : 0;
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_counter(bq_solver *s, int which, int64_t *value) {
-    BQ_ARG(s && value, "NULL argument");
-    BQ_ARG(which >= BQ_COUNT_INNER && which <= BQ_COUNT_NO_PRODUCT, "which: BQ_COUNT_*");
-    *value = s->kind == BQ_AS ? bq_as_counter(s, which) : 0;
-    return BQ_OK;
-}
-
-extern "C" int bq_al_solver_create(bq_problem *p, const bq_al_params *prm, const double *a_eq, const double *lb,
-                                   const double *ub, const double *x0, const double *dual0, bq_solver **out) {
-    BQ_ARG(p && prm && x0 && out, "NULL argument");
-    BQ_ARG(prm->rule >= BQ_RULE_SGD && prm->rule <= BQ_RULE_RMSPROP, "update rule");
-    BQ_ARG(prm->momentum_type >= BQ_MOM_NONE && prm->momentum_type <= BQ_MOM_NESTEROV, "unknown momentum type");
-    BQ_ARG(prm->momentum_type == BQ_MOM_NONE || (prm->rule != BQ_RULE_ADAGRAD && prm->rule != BQ_RULE_ADADELTA),
-           "AdaGrad / AdaDelta take no momentum");
-    BQ_ARG(prm->step_size > 0.0, "step_size must be > 0");                       // stochastic/_base.py:86-87
-    BQ_ARG(prm->momentum >= 0.0 && prm->momentum < 1.0, "momentum must be between 0 and 1");   // :240-241
-    BQ_ARG(prm->epochs > 0, "max_iter must be > 0");                             // optiml/opti/_base.py:73-74
-    BQ_ARG(prm->rho > 0.0, "rho must be must > 0");                              // constrained/_base.py:276-277
-    BQ_ARG(prm->offset > 0.0 || prm->rule == BQ_RULE_SGD, "offset must be > 0");
-    BQ_ARG(prm->beta1 >= 0.0 && prm->beta1 < 1.0, "beta1 has to lie in [0, 1)");
-    BQ_ARG(prm->beta2 >= 0.0 && prm->beta2 < 1.0, "beta2 has to lie in [0, 1)");
-    BQ_ARG(prm->decay >= 0.0 && prm->decay < 1.0, "decay has to lie in [0, 1)");
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    bq_solver *s = new bq_solver();
-    s->p = p;
-    p->refs += 1;
-    s->kind = BQ_AL;
-    s->N = p->N;
-    s->ldN = p->ldN;
-    s->nblk = p->ldN / BQ_VEC_TILE;
-    s->al = new bq_al_state();
-    s->al->prm = *prm;
-    bq_al_vecs &V = s->al->V;
-    memset(&V, 0, sizeof(V));
-    int rc = BQ_OK;
-    for (double **v : {&s->x, &s->g, &s->d, &s->Qd, &V.xe, &V.s1})
-        if (rc == BQ_OK) rc = alloc_vec(s, v);
-    if (rc == BQ_OK && hipMalloc(&V.chk, sizeof(double) * 3 * s->ldN) != hipSuccess) {
-        bq_set_error("cannot allocate the solver's vectors");
-        rc = BQ_ERR_NOMEM;
-    }
-    if (rc == BQ_OK) BQ_HIP(hipMemsetAsync(V.chk, 0, sizeof(double) * 3 * s->ldN, c->stream));
-    const bool two = prm->rule == BQ_RULE_ADAM || prm->rule == BQ_RULE_AMSGRAD || prm->rule == BQ_RULE_ADAMAX ||
-                     prm->rule == BQ_RULE_ADADELTA;
-    if (rc == BQ_OK && two) rc = alloc_vec(s, &V.s2);
-    if (rc == BQ_OK && prm->rule == BQ_RULE_AMSGRAD) rc = alloc_vec(s, &V.s3);
-    if (rc == BQ_OK && a_eq) rc = alloc_vec(s, &V.a);
-    if (rc == BQ_OK && lb) rc = alloc_vec(s, &s->lb);
-    if (rc == BQ_OK && lb) rc = alloc_vec(s, &V.llb);
-    if (rc == BQ_OK && ub) rc = alloc_vec(s, &s->ub);
-    if (rc == BQ_OK && ub) rc = alloc_vec(s, &V.lub);
-    if (rc != BQ_OK) {
-        bq_solver_destroy(s);
-        return rc;
-    }
-    V.x = s->x;
-    V.g = s->g;
-    V.step = s->d;
-    V.Qx = s->Qd;
-    V.q = p->q;
-    V.lb = lb ? s->lb : nullptr;
-    V.ub = ub ? s->ub : nullptr;
-    auto up = [&](double *dev, const double *src) {
-        return hipMemcpyAsync(dev, src, sizeof(double) * s->N, hipMemcpyHostToDevice, c->stream);
-    };
-    hipError_t e = up(s->x, x0);
-    if (e == hipSuccess) e = up(V.xe, x0);
-    if (e == hipSuccess && a_eq) e = up(V.a, a_eq);
-    if (e == hipSuccess && lb) e = up(s->lb, lb);
-    if (e == hipSuccess && ub) e = up(s->ub, ub);
-    std::vector<double> ones;
-    if (e == hipSuccess && prm->rule == BQ_RULE_RMSPROP) {   // rmsprop.py: moving_mean_squared starts at ones
-        ones.assign((size_t)s->N, 1.0);
-        e = up(V.s1, ones.data());
-    }
-    memset(&s->host, 0, sizeof(bq_scal));
-    if (dual0) {
-        const double *d0 = dual0;
-        if (a_eq) s->host.al_mu = *d0++;
-        if (e == hipSuccess && lb) {
-            e = up(V.llb, d0);
-            d0 += s->N;
-        }
-        if (e == hipSuccess && ub) e = up(V.lub, d0);
-    }
-    if (e == hipSuccess) e = hipMalloc(&s->partials, sizeof(double) * BQ_MAX_PARTIAL_Q * s->nblk);
-    if (e == hipSuccess) e = hipMalloc(&s->sc, sizeof(bq_scal));
-    if (e == hipSuccess) {
-        s->host.max_iter = prm->epochs;
-        s->host.eps = prm->tol;
-        s->host.status = BQ_STATUS_UNKNOWN;
-        s->host.f = NAN;
-        s->host.al_pf = NAN;
-        e = hipMemcpyAsync(s->sc, &s->host, sizeof(bq_scal), hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) {   // may sit behind a collective of an earlier solve: the bounded wait
-        const int src = bq_ctx_sync(c);
-        if (src != BQ_OK) {
-            bq_solver_destroy(s);
-            return src;
-        }
-    }
-    if (e != hipSuccess) {
-        bq_set_error("solver setup failed: %s", hipGetErrorString(e));
-        bq_solver_destroy(s);
-        return BQ_ERR_HIP;
-    }
-    *out = s;
-    return BQ_OK;
-}
-
-extern "C" int bq_al_solver_set_schedules(bq_solver *s, const double *step_sizes, const double *momenta, int64_t count) {
-    BQ_ARG(s != nullptr && s->al != nullptr, "not an augmented-Lagrangian solver");
-    BQ_ARG(count >= 1 && (step_sizes || momenta), "count >= 1 and at least one schedule");
-    BQ_ARG(!s->initialised && s->host.iter == 0, "schedules are set before the first run");
-    bq_ctx *c = s->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    for (int64_t i = 0; i < count; ++i) {
-        BQ_ARG(!step_sizes || step_sizes[i] > 0.0, "step sizes must be > 0");
-        BQ_ARG(!momenta || (momenta[i] >= 0.0 && momenta[i] < 1.0), "momentum must be between 0 and 1");
-    }
-    bq_al_vecs &V = s->al->V;
-    for (int k = 0; k < 2; ++k) {
-        const double *src = k == 0 ? step_sizes : momenta;
-        if (!src) continue;
-        double *dev = nullptr;
-        BQ_HIP(hipMalloc(&dev, sizeof(double) * count));
-        BQ_HIP(hipMemcpy(dev, src, sizeof(double) * count, hipMemcpyHostToDevice));
-        if (k == 0) {
-            if (V.lr_sched) hipFree((void *)V.lr_sched);
-            V.lr_sched = dev;
-        } else {
-            if (V.mom_sched) hipFree((void *)V.mom_sched);
-            V.mom_sched = dev;
-        }
-    }
-    V.sched_len = count;
-    return BQ_OK;
-}
-
-extern "C" int bq_al_solver_dual_size(const bq_solver *s, int64_t *n_dual) {
-    BQ_ARG(s && n_dual, "NULL argument");
-    BQ_ARG(s->al != nullptr, "not an augmented-Lagrangian solver");
-    const bq_al_vecs &V = s->al->V;
-    *n_dual = (V.a ? 1 : 0) + (V.llb ? s->N : 0) + (V.lub ? s->N : 0);
-    return BQ_OK;
-}
-
-static int solver_first(bq_solver *s) {
-    if (s->kind == BQ_AL) return BQ_OK;   // nothing to prepare: every iteration evaluates Q x afresh
-    bq_solver::resume_t *r = s->resume;
-    const int have = r ? r->have : 0;
-    hipStream_t st = s->p->ctx->stream;
-    auto up = [&](double *dev, const std::vector<double> &src) {
-        return hipMemcpyAsync(dev, src.data(), sizeof(double) * s->N, hipMemcpyHostToDevice, st);
-    };
-    switch (s->kind) {
-        case BQ_PG:
-        case BQ_FW:
-            // g given: the start product is not needed — (x, g) is the whole state of these two (bq_solver_set_state)
-            if (have & BQ_STATE_G) BQ_HIP(up(s->g, r->g));
-            else BQ_TRY(bq_pgfw_start(s));
-            break;
-        case BQ_IP:
-            // interior_point.py:180-186 where something is missing; what was given then replaces what the start formed
-            if ((have & (BQ_STATE_G | BQ_STATE_MULT)) != (BQ_STATE_G | BQ_STATE_MULT)) BQ_TRY(bq_ip_start(s));
-            if (have & BQ_STATE_G) BQ_HIP(up(s->g, r->g));
-            if (have & BQ_STATE_MULT) {
-                BQ_HIP(up(s->lp, r->lp));
-                BQ_HIP(up(s->lm, r->lm));
-            }
-            break;
-        default:
-            BQ_TRY(bq_as_start(s));   // takes the masks from s->resume itself (they are allocated there)
-            if (have & BQ_STATE_G) BQ_HIP(up(s->g, r->g));
-            break;
-    }
-    if (r) {
-        BQ_SYNC(s->p->ctx);   // the uploads read the vectors about to be released
-        delete r;
-        s->resume = nullptr;
-    }
-    return BQ_OK;
-}
-
-static int solver_iterate(bq_solver *s) {
-    if (s->kind == BQ_AL) return bq_al_iterate(s);
-    switch (s->kind) {
-        case BQ_PG:
-        case BQ_FW:
-            return bq_pgfw_iterate(s);
-        case BQ_IP:
-            return bq_ip_iterate(s);
-        default:
-            return bq_as_iterate(s);
-    }
-}
-
-extern "C" int bq_solver_run(bq_solver *s, int64_t max_steps, bq_iter_stat *stats, int64_t stats_cap, int64_t *n_stats,
-                             int *status) {
-    BQ_ARG(s && n_stats && status, "NULL argument");
-    BQ_ARG(max_steps > 0, "max_steps must be > 0");
-    BQ_ARG(stats == nullptr || stats_cap >= max_steps, "stats capacity must be >= max_steps");
-    bq_ctx *c = s->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    *n_stats = 0;
-    *status = s->host.status;
-    if (s->host.done) return BQ_OK;
-    if (s->stats_cap < max_steps) {
-        if (s->stats) BQ_HIP(hipFree(s->stats));
-        s->stats = nullptr;
-        BQ_HIP(hipMalloc(&s->stats, sizeof(bq_iter_stat) * max_steps));
-        s->stats_cap = max_steps;
-    }
-    if (s->flag_host == nullptr) {   // pinned flag + event of the lagged done-flag polling (best effort)
-        if (hipHostMalloc((void **)&s->flag_host, sizeof(int), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&s->flag_event, hipEventDisableTiming) != hipSuccess) {
-            if (s->flag_host) hipHostFree(s->flag_host);
-            s->flag_host = nullptr;
-            (void)hipGetLastError();
-        } else {
-            *s->flag_host = 0;
-        }
-    }
-    if (s->al) s->al->w_ready = false;   // p->w belongs to the problem: anything may have used it since the last run
-    const long long base = s->host.iter;
-    long long hdr[2] = {base, (long long)max_steps};
-    BQ_HIP(hipMemcpyAsync(&s->sc->stat_base, hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream));
-    if (!s->initialised) {
-        BQ_TRY(solver_first(s));
-        s->initialised = true;
-    }
-    // How often the host looks at the device `done` flag: kernels early-exit on the flag, so a late look only costs a few
-    // no-op launches (~20 us per skipped iteration).  The factorising solvers are host-enqueued O(n^3) work per iteration
-    // and look every time; PG/FW look about every 20 ms of estimated panel streaming time.  A look is a 4-byte copy to the
-    // host plus an event on the stream — not free between two short kernels: at 2 ms (round 3) BASELINE config 2 ran 0.3035 ms
-    // per iteration, at 20 ms 0.286 ms (profiles/r04/share_gaps_events.txt).
-    int64_t poll = 1;
-    if (s->kind == BQ_PG || s->kind == BQ_FW || s->kind == BQ_AL) {
-        // The interval must be the SAME on every rank (each iteration contains a collective: ranks that stopped enqueueing at
-        // different iterations would leave the others inside it), so it is computed from the mean share n / world, not from
-        // this rank's own rows.
-        const double esz = s->p->storage == BQ_F64 ? 8.0 : 4.0;
-        const double rows = (double)s->p->n / (double)c->world;
-        const double iter_s = rows * (double)s->p->n * esz * (s->p->symmetric ? 0.5 : 1.0) / 5.0e12 + 30e-6;
-        poll = (int64_t)(20.0e-3 / iter_s);
-        poll = poll < 1 ? 1 : (poll > 64 ? 64 : poll);
-    }
-    // The product-bound solvers look at the flag with a LAG of one chunk: the copy of the flag is followed by an event,
-    // the next chunk is enqueued at once, and only then does the host wait for that event — the device never runs dry
-    // while the host decides (the extra chunk early-exits on the flag).  The factorising solvers enqueue O(n^3) work per
-    // iteration from the host and check before every iteration.
-    const bool lagged = poll > 0 && (s->kind == BQ_PG || s->kind == BQ_FW || s->kind == BQ_AL) && s->flag_host != nullptr;
-    bool pending = false;
-    for (int64_t k = 0; k < max_steps; ++k) {
-        BQ_TRY(solver_iterate(s));
-        if (s->kind == BQ_AS) {
-            // ActiveSet looks at the device at the top of every iteration anyway (bq_as_iterate: the order of the restricted
-            // system comes from there) and leaves s->host current: a second look here was one more stream drain per iteration
-            if (s->host.done) break;
-            continue;
-        }
-        if ((k + 1) % poll == 0 && k + 1 < max_steps) {
-            if (lagged) {
-                if (pending) {
-                    BQ_TRY(bq_ctx_event_sync(c, s->flag_event));
-                    if (*s->flag_host) break;
-                }
-                BQ_HIP(hipMemcpyAsync(s->flag_host, &s->sc->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                BQ_HIP(hipEventRecord(s->flag_event, c->stream));
-                pending = true;
-            } else {
-                BQ_HIP(hipMemcpyAsync(&s->host, s->sc, sizeof(bq_scal), hipMemcpyDeviceToHost, c->stream));
-                BQ_SYNC(c);
-                if (s->host.done) break;
-            }
-        }
-    }
-    if (s->al) BQ_TRY(bq_al_flush(s));
-    BQ_HIP(hipMemcpyAsync(&s->host, s->sc, sizeof(bq_scal), hipMemcpyDeviceToHost, c->stream));
-    BQ_SYNC(c);
-    if (s->host.status < 0) {  // a kernel flagged a numerical failure (codes mirror BQ_ERR_*)
-        bq_set_error(s->host.status == BQ_ERR_NOT_PD ? "Cholesky met a non-positive pivot"
-                                                     : "non-finite values in the solver state");
-        return s->host.status;
-    }
-    int64_t rows = s->host.iter - base + (s->host.done ? 1 : 0);
-    if (rows > max_steps) rows = max_steps;
-    if (rows < 0) rows = 0;
-    if (stats && rows > 0) {
-        BQ_HIP(hipMemcpyAsync(stats, s->stats, sizeof(bq_iter_stat) * rows, hipMemcpyDeviceToHost, c->stream));
-        BQ_SYNC(c);
-    }
-    *n_stats = rows;
-    *status = s->host.status;
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_state(const bq_solver *s, int64_t *iter, int *status, double *f_x) {
-    BQ_ARG(s != nullptr, "solver is NULL");
-    if (iter) *iter = s->host.iter;
-    if (status) *status = s->host.status;
-    if (f_x) *f_x = s->host.f;
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_get(bq_solver *s, int what, double *out) {
-    BQ_ARG(s && out, "NULL argument");
-    bq_ctx *c = s->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    const double *src = nullptr;
-    if (what == BQ_GET_DUAL) {
-        BQ_ARG(s->al != nullptr, "multipliers exist for the augmented-Lagrangian solver only");
-        const bq_al_vecs &V = s->al->V;
-        double *o = out;
-        if (V.a) *o++ = s->host.al_mu;
-        for (const double *v : {(const double *)V.llb, (const double *)V.lub})
-            if (v) {
-                BQ_HIP(hipMemcpyAsync(o, v, sizeof(double) * s->N, hipMemcpyDeviceToHost, c->stream));
-                o += s->N;
-            }
-        BQ_SYNC(c);
-        return BQ_OK;
-    }
-    switch (what) {
-        case BQ_GET_X: src = s->kind == BQ_AS ? bq_as_view(s, BQ_GET_X) : (s->al ? s->al->V.xe : s->x); break;
-        case BQ_GET_G: src = s->kind == BQ_AS ? bq_as_view(s, BQ_GET_G) : s->g; break;
-        case BQ_GET_X_NOW: src = s->x; break;
-        case BQ_GET_G_NOW: src = s->g; break;
-        case BQ_GET_D: src = s->d; break;
-        case BQ_GET_LP: src = s->lp; break;
-        case BQ_GET_LM: src = s->lm; break;
-        default: break;
-    }
-    if (what == BQ_GET_MASK_L || what == BQ_GET_MASK_U) {
-        const unsigned char *m = what == BQ_GET_MASK_L ? s->mL : s->mU;
-        BQ_ARG(m != nullptr, "masks exist for ActiveSet only");
-        std::vector<unsigned char> tmp((size_t)s->N);
-        BQ_HIP(hipMemcpyAsync(tmp.data(), m, (size_t)s->N, hipMemcpyDeviceToHost, c->stream));
-        BQ_SYNC(c);
-        for (int64_t i = 0; i < s->N; ++i) out[i] = tmp[i] ? 1.0 : 0.0;
-        return BQ_OK;
-    }
-    BQ_ARG(src != nullptr, "vector not available for this solver");
-    BQ_HIP(hipMemcpyAsync(out, src, sizeof(double) * s->N, hipMemcpyDeviceToHost, c->stream));
-    BQ_SYNC(c);
-    return BQ_OK;
-}
-
-// ---- checkpoint / resume (bcqp.h) -----------------------------------------------------------------------------
-// v + t dv with the device's rounding: one rounded product, one sum (pgfw_update_kernel / ip_update_kernel use __dmul_rn).
-#pragma clang fp contract(off)
-static void state_apply_step(std::vector<double> &v, const std::vector<double> &dv, double t) {
-    for (size_t i = 0; i < v.size(); ++i) {
-        const double prod = t * dv[i];
-        v[i] = v[i] + prod;
-    }
-}
-
-extern "C" int bq_solver_get_state(bq_solver *s, bq_solver_snapshot *out) {
-    BQ_ARG(s && out, "NULL argument");
-    BQ_ARG(s->kind != BQ_AL, "the augmented-Lagrangian solver keeps its state in x and BQ_GET_DUAL");
-    bq_ctx *c = s->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    const size_t N = (size_t)s->N;
-    out->iter = s->host.iter;
-    out->kind = s->as_cg ? BQ_AS_CG : s->kind;
-    out->f = s->host.f;
-    out->best_lb = s->host.best_lb;
-    out->have = 0;
-    // a decided step waits on the device until the next iteration's first kernel applies it — unless the run has ended
-    // (the deciding kernels return before they form one) or has not begun
-    const bool pending = s->started && !s->host.done && s->kind != BQ_AS;
-    const double t = s->kind == BQ_IP ? s->host.step : s->host.t;
-    std::vector<double> v(N), dv(N);
-    auto down = [&](std::vector<double> &dst, const double *src) {
-        return hipMemcpyAsync(dst.data(), src, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream);
-    };
-    auto fetch = [&](double *dst, const double *vec, const double *dvec) -> int {
-        BQ_HIP(down(v, vec));
-        if (pending) BQ_HIP(down(dv, dvec));
-        BQ_SYNC(c);
-        if (pending) state_apply_step(v, dv, t);
-        memcpy(dst, v.data(), sizeof(double) * N);
-        return BQ_OK;
-    };
-    const bool pgfw = s->kind == BQ_PG || s->kind == BQ_FW;
-    if (out->x) {
-        BQ_TRY(fetch(out->x, s->x, s->d));   // d: PG / FW direction, IP dx (ip_vecs)
-        out->have |= BQ_STATE_X;
-    }
-    // the gradient exists once the start-up has run (PG / FW keep it current: g + t Qd; IP and ActiveSet keep the reference's
-    // stale self.g_x: interior_point.py:180, active_set.py:157)
-    if (out->g && s->initialised) {
-        if (pgfw) {
-            BQ_TRY(fetch(out->g, s->g, s->Qd));
-        } else {
-            BQ_HIP(down(v, s->g));
-            BQ_SYNC(c);
-            memcpy(out->g, v.data(), sizeof(double) * N);
-        }
-        out->have |= BQ_STATE_G;
-    }
-    if (s->kind == BQ_IP && out->lp && out->lm && s->initialised) {
-        BQ_TRY(fetch(out->lp, s->lp, s->dlp));
-        BQ_TRY(fetch(out->lm, s->lm, s->dlm));
-        out->have |= BQ_STATE_MULT;
-    }
-    if (s->kind == BQ_AS && out->mask_l && out->mask_u && s->mL && s->mU) {
-        BQ_TRY(bq_solver_get(s, BQ_GET_MASK_L, out->mask_l));
-        BQ_TRY(bq_solver_get(s, BQ_GET_MASK_U, out->mask_u));
-        out->have |= BQ_STATE_MASKS;
-    }
-    return BQ_OK;
-}
-
-extern "C" int bq_solver_set_state(bq_solver *s, const bq_solver_snapshot *in) {
-    BQ_ARG(s && in, "NULL argument");
-    BQ_ARG(s->kind != BQ_AL, "the augmented-Lagrangian solver is resumed through x0 / dual0 of bq_al_solver_create");
-    BQ_ARG(!s->initialised, "the state can only be set before the solver's first run");
-    BQ_ARG(in->kind == -1 || in->kind == (s->as_cg ? BQ_AS_CG : s->kind), "the state was taken from another kind of solver");
-    BQ_ARG((in->have & BQ_STATE_X) && in->x, "a state holds x at least");
-    BQ_ARG(in->iter >= 0, "iter must be >= 0");
-    BQ_ARG(!(in->have & BQ_STATE_G) || in->g, "BQ_STATE_G without g");
-    BQ_ARG(!(in->have & BQ_STATE_MULT) || (s->kind == BQ_IP && in->lp && in->lm), "BQ_STATE_MULT: lp and lm, InteriorPoint only");
-    BQ_ARG(!(in->have & BQ_STATE_MASKS) || (s->kind == BQ_AS && in->mask_l && in->mask_u), "BQ_STATE_MASKS: mask_l and mask_u, ActiveSet only");
-    bq_ctx *c = s->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    const size_t N = (size_t)s->N;
-    delete s->resume;
-    s->resume = new bq_solver::resume_t();
-    bq_solver::resume_t *r = s->resume;
-    r->have = in->have & (BQ_STATE_G | BQ_STATE_MULT | BQ_STATE_MASKS);
-    if (r->have & BQ_STATE_G) r->g.assign(in->g, in->g + N);
-    if (r->have & BQ_STATE_MULT) {
-        r->lp.assign(in->lp, in->lp + N);
-        r->lm.assign(in->lm, in->lm + N);
-    }
-    if (r->have & BQ_STATE_MASKS) {
-        r->mL.resize(N);
-        r->mU.resize(N);
-        for (size_t i = 0; i < N; ++i) {
-            r->mL[i] = in->mask_l[i] != 0.0;
-            r->mU[i] = in->mask_u[i] != 0.0;
-            if (r->mL[i] && r->mU[i]) {
-                bq_set_error("state: index %zu is in both masks (L and U are disjoint: active_set.py:85)", i);
-                return BQ_ERR_BADARG;
-            }
-        }
-    }
-    s->host.iter = in->iter;
-    if (s->kind == BQ_FW && in->best_lb == in->best_lb) s->host.best_lb = in->best_lb;
-    BQ_HIP(hipMemcpyAsync(s->x, in->x, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-    BQ_HIP(hipMemcpyAsync(s->sc, &s->host, sizeof(bq_scal), hipMemcpyHostToDevice, c->stream));
-    BQ_SYNC(c);
-    return BQ_OK;
-}
-#pragma clang fp contract(on)
 
 extern "C" int bq_decision_function(bq_ctx *c, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                                     const double *SV, const double *coef, double intercept, int64_t t,

@@ -53,6 +53,7 @@ struct as_pc_part {
 // Phi_i = y_i e^{-g|x_i|^2} [1, sqrt(2g) x_i] (+ the y_i column of the rank-one term): the d + 1 directions whose eigenvalues
 // grow like n.  Linear panels: Phi = y o [X, 1] is exact.  The other kernels run unpreconditioned.
 struct as_pc {
+    bq_owner mem;            // every device buffer below (the remainder r2 and the workspace ws own theirs)
     int m = 0;               // features
     int64_t mp = 0;          // m padded to the factorisation block
     float *Phi = nullptr;    // m8 x ldN fp32, feature-major (a column of the N x m matrix is contiguous; rows m .. m8 are zero).
@@ -92,6 +93,7 @@ struct as_pc {
 };
 
 struct as_ws {
+    bq_owner mem;              // every device buffer below, the inner solver's (as_cg_create) included; pc and sch own theirs
     int *idx = nullptr;        // compacted free set
     int *ints = nullptr;       // [0] nA, [1] nB, [2] feasible, [3] h_lower, [4] h_upper, [5] nL_new, [6] nU_new
     double *cand = nullptr;    // candidate point (ldN)
@@ -325,6 +327,7 @@ static inline void as_tick(as_ws *w, int slot) {   // BQ_AS_TIMING: the time sin
 
 // ---- factor re-use (bq_as_schur.hip) ---------------------------------------------------------------------------
 struct as_schur {
+    bq_owner mem;                     // the device buffers below
     bool valid = false;
     int64_t n0 = 0, np0 = 0, cap = 0;
     int *idx0 = nullptr;              // device: the base set, ascending

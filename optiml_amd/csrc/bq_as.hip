@@ -421,10 +421,8 @@ int bq_as_start(bq_solver *s) {
     bq_ctx *ctx = s->p->ctx;
     as_ws *w = new as_ws();
     s->as_ws = w;
-    BQ_HIP(hipMalloc(&w->idx, sizeof(int) * (s->N + 1)));
-    BQ_HIP(hipMemsetAsync(w->idx, 0, sizeof(int) * (s->N + 1), ctx->stream));
-    BQ_HIP(hipMalloc(&w->ints, sizeof(int) * 32));
-    BQ_HIP(hipMemsetAsync(w->ints, 0, sizeof(int) * 32, ctx->stream));
+    BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->idx, s->N + 1, ctx->stream));
+    BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->ints, 32, ctx->stream));
     BQ_HIP(hipHostMalloc(&w->host_ints, sizeof(int) * 32, AS_MAPPED));
     BQ_HIP(hipHostMalloc(&w->host_scal, sizeof(bq_scal), AS_MAPPED));
     BQ_HIP(hipHostMalloc(&w->mail, sizeof(int) * 16, AS_MAPPED));
@@ -432,8 +430,7 @@ int bq_as_start(bq_solver *s) {
     w->mail_d = as_dev(w->mail);
     w->host_ints_d = as_dev(w->host_ints);
     w->host_scal_d = reinterpret_cast<int *>(as_dev(w->host_scal));
-    BQ_HIP(hipMalloc(&w->mail_ticket, sizeof(unsigned int) * 2));
-    BQ_HIP(hipMemsetAsync(w->mail_ticket, 0, sizeof(unsigned int) * 2, s->p->ctx->stream));
+    BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->mail_ticket, 2, ctx->stream));
     w->mailbox = !s->as_cg && bq_hook_on("as_mailbox");
     w->f_chain = !s->as_cg && bq_hook_on("as_f_chain");
 #ifdef BQ_AS_TIMING   // diagnostic build (BQ_EXTRA_CXXFLAGS=-DBQ_AS_TIMING): where the host's time goes per iteration, printed by bq_as_free
@@ -443,15 +440,10 @@ int bq_as_start(bq_solver *s) {
     BQ_HIP(hipHostMalloc(&w->host_cg, sizeof(as_cg_scal)));
     memset(w->host_ints, 0, sizeof(int) * 32);
     memset(w->host_info, 0, sizeof(int) * 8);
-    for (double **v : {&w->cand, &w->z, &w->Qz, &w->x_eval, &w->g_eval}) {
-        BQ_HIP(hipMalloc(v, sizeof(double) * s->ldN));
-        BQ_HIP(hipMemsetAsync(*v, 0, sizeof(double) * s->ldN, ctx->stream));
-    }
+    for (double **v : {&w->cand, &w->z, &w->Qz, &w->x_eval, &w->g_eval}) BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, v, s->ldN, ctx->stream));
     if (s->as_cg) BQ_TRY(as_cg_create(s, w));
-    BQ_HIP(hipMalloc(&s->mL, (size_t)s->ldN));
-    BQ_HIP(hipMalloc(&s->mU, (size_t)s->ldN));
-    BQ_HIP(hipMemsetAsync(s->mL, 0, (size_t)s->ldN, ctx->stream));
-    BQ_HIP(hipMemsetAsync(s->mU, 0, (size_t)s->ldN, ctx->stream));
+    BQ_HIP(bq_dev_zeroed(hipSuccess, s->mem, &s->mL, s->ldN, ctx->stream));   // fields of the solver: its owner's, not the workspace's
+    BQ_HIP(bq_dev_zeroed(hipSuccess, s->mem, &s->mU, s->ldN, ctx->stream));
     // bq_solver_set_state: continue from given masks L / U (the reference starts with both empty, active_set.py:91-92).  The host
     // vectors live until solver_first has synchronised.
     const bool resumed = s->resume && (s->resume->have & BQ_STATE_MASKS);
@@ -462,8 +454,7 @@ int bq_as_start(bq_solver *s) {
     if (w->f_chain && resumed) {
         // the product-free f of ratio steps needs a point that solves its restricted system and the gradient there: neither is
         // known for a restored point, so the first run starts at the next release (as_finish_iteration), as after a minres step
-        BQ_HIP(hipMalloc(&w->g0, sizeof(double) * s->ldN));
-        BQ_HIP(hipMemsetAsync(w->g0, 0, sizeof(double) * s->ldN, ctx->stream));
+        BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->g0, s->ldN, ctx->stream));
         static const double one = 1.0;
         BQ_HIP(hipMemcpyAsync(&s->sc->aux[0], &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         w->gref = nullptr;
@@ -473,8 +464,7 @@ int bq_as_start(bq_solver *s) {
     if (w->f_chain) {
         // the gradient at x0 rides on the product of f(x0): with every index free, x0 + t d obeys the ratio step's identity from the
         // first iteration on (as_step_min_kernel).  Kept apart from s->g, which the reference does not touch before a release.
-        BQ_HIP(hipMalloc(&w->g0, sizeof(double) * s->ldN));
-        BQ_HIP(hipMemsetAsync(w->g0, 0, sizeof(double) * s->ldN, ctx->stream));
+        BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->g0, s->ldN, ctx->stream));
         static const double one = 1.0;   // gamma of the first run (as_release_mb_kernel sets it for the later ones)
         BQ_HIP(hipMemcpyAsync(&s->sc->aux[0], &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         w->gref = w->g0;
@@ -502,11 +492,6 @@ void bq_as_free(bq_solver *s) {
                     w->sch->reused + w->sch->refreshes, (double)w->sch->rows_solved / std::max(1.0, (double)(w->sch->reused + w->sch->refreshes)),
                     (double)w->sch->rows_extended / std::max(1.0, (double)(w->sch->reused + w->sch->refreshes)), w->sch->drops, w->sch->refreshes);
     }
-    for (void *p : {(void *)w->idx, (void *)w->ints, (void *)w->cand, (void *)w->z, (void *)w->Qz, (void *)w->x_eval,
-                    (void *)w->g_eval, (void *)w->dlt, (void *)w->r, (void *)w->pv, (void *)w->Qp, (void *)w->sol,
-                    (void *)w->cg, (void *)w->Qdl, (void *)w->Qcand, (void *)w->sq, (void *)w->zchg, (void *)w->zdl,
-                    (void *)w->mail_ticket, (void *)w->g0})
-        if (p) hipFree(p);
     for (void *hp : {(void *)w->host_ints, (void *)w->host_scal, (void *)w->host_info, (void *)w->host_cg, (void *)w->mail})
         if (hp) hipHostFree(hp);
     if (w->cg_flag_host) hipHostFree(w->cg_flag_host);
@@ -611,7 +596,7 @@ int bq_as_iterate(bq_solver *s) {
         // Q[A,A] is not positive definite: the reference's bare `except` switches to scipy's minres on the normal
         // equations (active_set.py:142-151).  Rebuild the (destroyed) restricted Hessian with both triangles, solve,
         // and redo the feasibility test on the minimum-residual candidate.
-        if (!ws->mr_vec) BQ_HIP(hipMalloc(&ws->mr_vec, sizeof(double) * 10 * ws->cap));
+        if (!ws->mr_vec) BQ_HIP(ws->mem.dev(&ws->mr_vec, 10 * ws->cap));
         BQ_TRY(bq_chol_build_h(ws, s->p, w->idx, nA, nullptr, &np, true));
         as_gather_rhs_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w->ints, w->idx, s->p->q, w->Qz, ws->rhs, np);
         BQ_TRY(bq_minres_normal(ws, w->ints, nA, np, ws->mr_vec, w->ints + 7));

@@ -435,12 +435,8 @@ int as_cg_iterate(bq_solver *s, as_ws *w) {
 // buffers, switches and the preconditioner of a BQ_AS_CG solver (bq_as_start)
 int as_cg_create(bq_solver *s, as_ws *w) {
     bq_ctx *ctx = s->p->ctx;
-    for (double **v : {&w->dlt, &w->r, &w->pv, &w->Qp, &w->sol, &w->Qdl, &w->Qcand}) {
-        BQ_HIP(hipMalloc(v, sizeof(double) * s->ldN));
-        BQ_HIP(hipMemsetAsync(*v, 0, sizeof(double) * s->ldN, ctx->stream));
-    }
-    BQ_HIP(hipMalloc(&w->cg, sizeof(as_cg_scal)));
-    BQ_HIP(hipMemsetAsync(w->cg, 0, sizeof(as_cg_scal), ctx->stream));
+    for (double **v : {&w->dlt, &w->r, &w->pv, &w->Qp, &w->sol, &w->Qdl, &w->Qcand}) BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, v, s->ldN, ctx->stream));
+    BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->cg, 1, ctx->stream));
     BQ_HIP(hipHostMalloc(&w->cg_flag_host, 2 * sizeof(int)));
     BQ_HIP(hipEventCreateWithFlags(&w->cg_event, hipEventDisableTiming));
     w->warm = bq_hook_on("as_cg_warm");
@@ -451,10 +447,9 @@ int as_cg_create(bq_solver *s, as_ws *w) {
                   (p->structure == BQ_PLAIN || p->structure == BQ_SVC) && p->kernel >= BQ_KERNEL_LINEAR &&
                   p->kernel <= BQ_KERNEL_SIGMOID;
         if (w->colq) {
-            BQ_HIP(hipMalloc(&w->sq, sizeof(double) * s->ldN));
-            BQ_HIP(hipMalloc(&w->zchg, sizeof(int) * (2 + AS_MAX_COLS)));
-            BQ_HIP(hipMemsetAsync(w->zchg, 0, sizeof(int) * (2 + AS_MAX_COLS), ctx->stream));
-            BQ_HIP(hipMalloc(&w->zdl, sizeof(double) * AS_MAX_COLS));
+            BQ_HIP(w->mem.dev(&w->sq, s->ldN));
+            BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->zchg, 2 + AS_MAX_COLS, ctx->stream));
+            BQ_HIP(w->mem.dev(&w->zdl, AS_MAX_COLS));
             as_row_norms_kernel<<<(unsigned)(s->ldN / 256), 256, 0, ctx->stream>>>(p->X, p->n, p->d, w->sq, s->ldN);
         }
     }

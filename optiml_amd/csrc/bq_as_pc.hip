@@ -717,44 +717,32 @@ int as_pc_create(bq_solver *s, as_pc **out) {
         pc->m = m;
         pc->mp = bq_round_up(m, 128);
         int rc = bq_chol_ws_create(ctx, pc->mp, &pc->ws);
-        hipError_t e = hipSuccess;
         pc->m8 = bq_round_up(m, PC_FG);
-        // (PC_FG spare zero rows: the t kernel walks feature groups of PC_FG from any first column — the Phi_top block of the remainder)
-        if (rc == BQ_OK) e = hipMalloc(&pc->Phi, sizeof(float) * (size_t)(pc->m8 + PC_FG) * s->ldN);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMemsetAsync(pc->Phi, 0, sizeof(float) * (size_t)(pc->m8 + PC_FG) * s->ldN, ctx->stream);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->tpart, sizeof(double) * (size_t)s->nblk * pc->mp);
         as_pc_make_part(ctx, s->nblk, &pc->part);
-        {
-            const size_t tgl = sizeof(double) * (size_t)ctx->world * pc->part.cmax * pc->mp;
-            const size_t zgl = sizeof(double) * (size_t)ctx->world * pc->part.cmax * pc->part.maxlen * BQ_VEC_TILE;
-            if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->tg, tgl);
-            if (rc == BQ_OK && e == hipSuccess) e = hipMemsetAsync(pc->tg, 0, tgl, ctx->stream);
-            if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->zg, zgl);
-            if (rc == BQ_OK && e == hipSuccess) e = hipMemsetAsync(pc->zg, 0, zgl, ctx->stream);
-        }
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->dinv, sizeof(double) * s->ldN);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->z, sizeof(double) * s->ldN);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->Gpart, sizeof(double) * PC_SLICES * pc->mp * pc->mp);
-        if (rc == BQ_OK && e == hipSuccess)
-            e = hipMemsetAsync(pc->Gpart, 0, sizeof(double) * PC_SLICES * pc->mp * pc->mp, ctx->stream);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->Ginv, sizeof(double) * pc->mp * pc->mp);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->u, sizeof(double) * pc->mp);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->sm_fail, sizeof(int));
-        if (rc == BQ_OK && e == hipSuccess) e = hipMemsetAsync(pc->sm_fail, 0, sizeof(int), ctx->stream);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->prev, (size_t)s->ldN);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMemsetAsync(pc->prev, 0, (size_t)s->ldN, ctx->stream);
-        if (rc == BQ_OK && e == hipSuccess) e = hipMalloc(&pc->chg, sizeof(int) * (2 + 2 * PC_MAX_CHG));
-        if (rc == BQ_OK && e == hipSuccess) e = hipMemsetAsync(pc->chg, 0, sizeof(int) * (2 + 2 * PC_MAX_CHG), ctx->stream);
-        if (rc == BQ_OK && e == hipSuccess && classes) {
-            e = hipMalloc(&pc->cls, sizeof(double) * (2 * p->d + 2));
-            if (e == hipSuccess) e = hipMemsetAsync(pc->cls, 0, sizeof(double) * (2 * p->d + 2), ctx->stream);
-        }
-        // fam2 == 2: per-sample numbers and the orthonormalising factor (set-up only) — allocated HERE, with everything else a rank may
-        // have no room for, so that their failure lands in the agreed flag (they used to come after the agreement)
+        bq_owner &mem = pc->mem;
+        hipStream_t st = ctx->stream;
+        hipError_t e = hipSuccess;
+        // fam2 == 2: raw, rinv_d — per-sample numbers and the orthonormalising factor (set-up only: released after the build) — are
+        // allocated HERE, with everything else a rank may have no room for, so that their failure lands in the agreed flag (ADVICE r5:
+        // they used to come after the agreement)
         double *raw = nullptr, *rinv_d = nullptr;
-        if (rc == BQ_OK && e == hipSuccess && fam2 == 2) {
-            e = hipMalloc(&raw, sizeof(double) * 3 * s->ldN);
-            if (e == hipSuccess) e = hipMalloc(&rinv_d, sizeof(double) * (size_t)(2 * p->d) * (size_t)(2 * p->d));
+        if (rc == BQ_OK) {
+            // (PC_FG spare zero rows: the t kernel walks feature groups of PC_FG from any first column — the Phi_top block of the remainder)
+            e = bq_dev_zeroed(e, mem, &pc->Phi, (size_t)(pc->m8 + PC_FG) * s->ldN, st);
+            if (e == hipSuccess) e = mem.dev(&pc->tpart, (size_t)s->nblk * pc->mp);
+            e = bq_dev_zeroed(e, mem, &pc->tg, (size_t)ctx->world * pc->part.cmax * pc->mp, st);
+            e = bq_dev_zeroed(e, mem, &pc->zg, (size_t)ctx->world * pc->part.cmax * pc->part.maxlen * BQ_VEC_TILE, st);
+            if (e == hipSuccess) e = mem.dev(&pc->dinv, s->ldN);
+            if (e == hipSuccess) e = mem.dev(&pc->z, s->ldN);
+            e = bq_dev_zeroed(e, mem, &pc->Gpart, PC_SLICES * pc->mp * pc->mp, st);
+            if (e == hipSuccess) e = mem.dev(&pc->Ginv, pc->mp * pc->mp);
+            if (e == hipSuccess) e = mem.dev(&pc->u, pc->mp);
+            e = bq_dev_zeroed(e, mem, &pc->sm_fail, 1, st);
+            e = bq_dev_zeroed(e, mem, &pc->prev, s->ldN, st);
+            e = bq_dev_zeroed(e, mem, &pc->chg, 2 + 2 * PC_MAX_CHG, st);
+            if (classes) e = bq_dev_zeroed(e, mem, &pc->cls, 2 * p->d + 2, st);
+            if (e == hipSuccess && fam2 == 2) e = mem.dev(&raw, 3 * s->ldN);
+            if (e == hipSuccess && fam2 == 2) e = mem.dev(&rinv_d, (size_t)(2 * p->d) * (size_t)(2 * p->d));
         }
         // Do ALL ranks hold their features?  Every rank must run the SAME inner iteration (each product is a collective): a rank
         // that fell back to plain conjugate gradients alone — or returned an error alone — would leave the others waiting in the
@@ -762,12 +750,12 @@ int as_pc_create(bq_solver *s, as_pc **out) {
         // runs unpreconditioned.
         // the implicit order-2 remainder (family 2 only): its images and buffers — a rank without room for them drops IT on every rank
         // (the 1e-3 digit of the agreed flag), not the explicit model
+        // (the last requests to the owner: one refused here leaves it refusing, and the explicit model asks for nothing more)
         double *bdiag = nullptr;
         if (rc == BQ_OK && e == hipSuccess && fam2 == 2 && want_r2) {
-            hipError_t re = hipMalloc(&bdiag, sizeof(double) * s->ldN);
-            for (double **v : {&pc->y1, &pc->v2, &pc->z2, &pc->ones})
-                if (re == hipSuccess) re = hipMalloc(v, sizeof(double) * s->ldN);
-            if (re == hipSuccess) re = hipMalloc(&pc->ttop, sizeof(double) * pc->mp);
+            hipError_t re = mem.dev(&bdiag, s->ldN);
+            for (double **v : {&pc->y1, &pc->v2, &pc->z2, &pc->ones}) re = mem.dev(v, s->ldN);
+            re = mem.dev(&pc->ttop, pc->mp);
             if (re == hipSuccess && as_pc2_create(s, bdiag, pc->mp, &pc->r2) != BQ_OK) re = hipErrorOutOfMemory;
             if (re == hipSuccess && pc->r2 != nullptr) {
                 as_pc_fill_kernel<<<(unsigned)(s->ldN / 256), 256, 0, ctx->stream>>>(s->ldN, 1.0, pc->ones);
@@ -785,17 +773,11 @@ int as_pc_create(bq_solver *s, as_pc **out) {
         {
             const int arc = agree(&failed);
             if (arc != BQ_OK) {
-                if (bdiag) hipFree(bdiag);
-                if (raw) hipFree(raw);
-                if (rinv_d) hipFree(rinv_d);
                 as_pc_free(pc);
                 return arc;
             }
         }
         if (failed >= 0.5) {   // no room for the features on some rank: all ranks run plain conjugate gradients
-            if (bdiag) hipFree(bdiag);
-            if (raw) hipFree(raw);
-            if (rinv_d) hipFree(rinv_d);
             as_pc_free(pc);
             return BQ_OK;
         }
@@ -876,9 +858,9 @@ int as_pc_create(bq_solver *s, as_pc **out) {
         }
         if (fe == hipSuccess && frc == BQ_OK) fe = hipMemcpyAsync(share.data(), pc->z, sizeof(double) * p->n, hipMemcpyDeviceToHost, ctx->stream);
         if (fe == hipSuccess && frc == BQ_OK) frc = bq_ctx_sync(ctx);
-        if (raw) hipFree(raw);
-        if (rinv_d) hipFree(rinv_d);
-        if (bdiag) hipFree(bdiag);
+        mem.release(raw);   // the set-up's own
+        mem.release(rinv_d);
+        mem.release(bdiag);
         // the feature build is rank-local work that can fail on one rank alone (a launch, a copy, a bounded wait): a second agreement,
         // so that EVERY rank leaves solver creation with an error when any of them has one — none enters the solve's
         // collectives without the others
@@ -909,11 +891,6 @@ void as_pc_free(as_pc *pc) {
     if (!pc) return;
     if (pc->ws) bq_chol_ws_destroy(pc->ws);
     as_pc2_free(pc->r2);
-    for (void *ptr : {(void *)pc->y1, (void *)pc->v2, (void *)pc->z2, (void *)pc->ones, (void *)pc->ttop})
-        if (ptr) hipFree(ptr);
-    for (void *ptr : {(void *)pc->Phi, (void *)pc->dinv, (void *)pc->z, (void *)pc->Gpart, (void *)pc->cls, (void *)pc->Ginv,
-                      (void *)pc->u, (void *)pc->sm_fail, (void *)pc->prev, (void *)pc->chg, (void *)pc->tpart, (void *)pc->tg, (void *)pc->zg})
-        if (ptr) hipFree(ptr);
     delete pc;
 }
 

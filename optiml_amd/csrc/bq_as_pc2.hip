@@ -23,6 +23,7 @@
 #include "bq_mfma_tile.h"
 
 struct as_pc2 {
+    bq_owner mem;                           // the device buffers below
     int64_t n = 0, d = 0, dp = 0, ld = 0;   // samples, features, features padded to 128, vector pitch (s->ldN)
     int64_t rows = 0;                       // rows of Xp / W (= ld)
     // the sample segments (in blocks of 1024 samples) and their slices (<= 2 blocks each: the split-K of M)
@@ -185,9 +186,6 @@ __global__ void pc2_coef_kernel(int64_t n, int64_t d, int64_t ld, const double *
 
 void as_pc2_free(as_pc2 *r) {
     if (!r) return;
-    for (void *p : {(void *)r->Xp, (void *)r->Xt, (void *)r->W, (void *)r->Mpart, (void *)r->M, (void *)r->ypart, (void *)r->c, (void *)r->sl_row,
-                    (void *)r->sl_k, (void *)r->sl_first, (void *)r->Mg, (void *)r->vg})
-        if (p) hipFree(p);
     delete r;
 }
 
@@ -226,24 +224,23 @@ int as_pc2_create(bq_solver *s, double *bdiag_out, int64_t tail, as_pc2 **out) {
     if (pt.hi <= pt.lo) r->own_sl_lo = r->own_sl_hi = 0;
     r->nsl = (int)sl_row.size();
     const size_t nsl1 = (size_t)std::max(r->nsl, 1);
-    hipError_t e = hipMalloc(&r->Xp, sizeof(double) * r->rows * r->dp);
-    if (e == hipSuccess) e = hipMalloc(&r->sl_row, sizeof(long long) * nsl1);
-    if (e == hipSuccess) e = hipMalloc(&r->sl_k, sizeof(long long) * nsl1);
-    if (e == hipSuccess) e = hipMalloc(&r->sl_first, sizeof(int) * ((size_t)pt.S + 1));
-    if (e == hipSuccess) e = hipMalloc(&r->Mg, sizeof(double) * (size_t)ctx->world * pt.cmax * r->gstride);
-    if (e == hipSuccess) e = hipMemsetAsync(r->Mg, 0, sizeof(double) * (size_t)ctx->world * pt.cmax * r->gstride, st);
-    if (e == hipSuccess) e = hipMalloc(&r->vg, sizeof(double) * (size_t)ctx->world * pt.cmax * pt.maxlen * BQ_VEC_TILE);
-    if (e == hipSuccess) e = hipMemsetAsync(r->vg, 0, sizeof(double) * (size_t)ctx->world * pt.cmax * pt.maxlen * BQ_VEC_TILE, st);
+    bq_owner &mem = r->mem;
+    hipError_t e = mem.dev(&r->Xp, r->rows * r->dp);
+    if (e == hipSuccess) e = mem.dev(&r->sl_row, nsl1);
+    if (e == hipSuccess) e = mem.dev(&r->sl_k, nsl1);
+    if (e == hipSuccess) e = mem.dev(&r->sl_first, (size_t)pt.S + 1);
+    e = bq_dev_zeroed(e, mem, &r->Mg, (size_t)ctx->world * pt.cmax * r->gstride, st);
+    e = bq_dev_zeroed(e, mem, &r->vg, (size_t)ctx->world * pt.cmax * pt.maxlen * BQ_VEC_TILE, st);
     if (e == hipSuccess && r->nsl > 0) e = hipMemcpyAsync(r->sl_row, sl_row.data(), sizeof(long long) * r->nsl, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && r->nsl > 0) e = hipMemcpyAsync(r->sl_k, sl_k.data(), sizeof(long long) * r->nsl, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(r->sl_first, sl_first.data(), sizeof(int) * ((size_t)pt.S + 1), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && bq_ctx_sync(ctx) != BQ_OK) e = hipErrorUnknown;   // the three tables leave this scope (the bounded wait: the stream may hold collectives)
-    if (e == hipSuccess) e = hipMalloc(&r->Xt, sizeof(double) * r->dp * r->ld);
-    if (e == hipSuccess) e = hipMalloc(&r->W, sizeof(double) * r->rows * r->dp);
-    if (e == hipSuccess) e = hipMalloc(&r->Mpart, sizeof(double) * nsl1 * r->dp * r->dp);
-    if (e == hipSuccess) e = hipMalloc(&r->M, sizeof(double) * r->dp * r->dp);
-    if (e == hipSuccess) e = hipMalloc(&r->ypart, sizeof(double) * T * r->ld);
-    if (e == hipSuccess) e = hipMalloc(&r->c, sizeof(double) * r->ld);
+    if (e == hipSuccess) e = mem.dev(&r->Xt, r->dp * r->ld);
+    if (e == hipSuccess) e = mem.dev(&r->W, r->rows * r->dp);
+    if (e == hipSuccess) e = mem.dev(&r->Mpart, nsl1 * r->dp * r->dp);
+    if (e == hipSuccess) e = mem.dev(&r->M, r->dp * r->dp);
+    if (e == hipSuccess) e = mem.dev(&r->ypart, T * r->ld);
+    if (e == hipSuccess) e = mem.dev(&r->c, r->ld);
     if (e == hipSuccess) e = hipMemsetAsync(r->Xp, 0, sizeof(double) * r->rows * r->dp, st);
     if (e == hipSuccess) e = hipMemsetAsync(r->W, 0, sizeof(double) * r->rows * r->dp, st);
     if (e != hipSuccess) {

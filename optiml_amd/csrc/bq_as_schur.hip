@@ -353,9 +353,6 @@ bool as_schur_enabled() {
 void as_schur_free(as_ws *w) {
     as_schur *c = w->sch;
     if (!c) return;
-    for (void *ptr : {(void *)c->idx0, (void *)c->pos0, (void *)c->U, (void *)c->W, (void *)c->y0, (void *)c->y,
-                      (void *)c->small, (void *)c->meta})
-        if (ptr) hipFree(ptr);
     for (void *ptr : {(void *)c->meta_pin, (void *)c->small_pin, (void *)c->coef_pin})
         if (ptr) hipHostFree(ptr);
     delete c;
@@ -368,14 +365,15 @@ static int as_schur_setup(bq_solver *s, as_ws *w) {
     w->sch = c;
     c->timing = w->timing;
     c->cap = s->chol->cap;
-    BQ_HIP(hipMalloc(&c->idx0, sizeof(int) * (s->N + 1)));
-    BQ_HIP(hipMalloc(&c->pos0, sizeof(int) * (s->N + 1)));
-    BQ_HIP(hipMalloc(&c->U, sizeof(double) * AS_SCHUR_MAX * c->cap));
-    BQ_HIP(hipMalloc(&c->W, sizeof(double) * AS_SCHUR_MAX * c->cap));
-    BQ_HIP(hipMalloc(&c->y0, sizeof(double) * c->cap));
-    BQ_HIP(hipMalloc(&c->y, sizeof(double) * c->cap));
-    BQ_HIP(hipMalloc(&c->small, sizeof(double) * 3 * AS_SCHUR_MAX));   // dots of a new column | coefficients | dots with y0
-    BQ_HIP(hipMalloc(&c->meta, sizeof(int) * 2 * AS_SCHUR_MAX));
+    c->idx0 = c->mem.dev<int>(s->N + 1);
+    c->pos0 = c->mem.dev<int>(s->N + 1);
+    c->U = c->mem.dev<double>(AS_SCHUR_MAX * c->cap);
+    c->W = c->mem.dev<double>(AS_SCHUR_MAX * c->cap);
+    c->y0 = c->mem.dev<double>(c->cap);
+    c->y = c->mem.dev<double>(c->cap);
+    c->small = c->mem.dev<double>(3 * AS_SCHUR_MAX);   // dots of a new column | coefficients | dots with y0
+    c->meta = c->mem.dev<int>(2 * AS_SCHUR_MAX);
+    BQ_HIP(c->mem.error());
     BQ_HIP(hipHostMalloc(&c->meta_pin, sizeof(int) * 2 * AS_SCHUR_MAX, AS_MAPPED));
     BQ_HIP(hipHostMalloc(&c->small_pin, sizeof(double) * 2 * AS_SCHUR_MAX, AS_MAPPED));
     BQ_HIP(hipHostMalloc(&c->coef_pin, sizeof(double) * AS_SCHUR_MAX, AS_MAPPED));

@@ -4,6 +4,7 @@
 
 struct bq_chol_ws {
     bq_ctx *ctx = nullptr;
+    bq_owner mem;      // every device buffer below, those allocated on first use (mr_*, bigM ..., pivot_thr) included
     int64_t cap = 0;   // largest padded order the workspace can hold (multiple of 128)
     int64_t ldh = 0;   // row pitch of H
     double *H = nullptr;      // cap x ldh, row-major; lower triangle = matrix, then its Cholesky factor

@@ -271,7 +271,8 @@ int bq_chol_ws_create(bq_ctx *ctx, int64_t n, bq_chol_ws **out) {
     ws->ldh = ws->cap;
     const int64_t nblk = ws->cap / NB;
     // bq_device_malloc: a panel kept for re-use that is in the way is dropped and the allocation retried
-    hipError_t e = hipMalloc(&ws->H, sizeof(double) * ws->ldh * ws->cap);
+    bq_owner &mem = ws->mem;
+    hipError_t e = mem.dev(&ws->H, ws->ldh * ws->cap);
     if (e != hipSuccess) {
         bq_set_error("cannot allocate the %lld x %lld factorisation workspace (%.1f GB): %s", (long long)ws->cap,
                      (long long)ws->cap, 8e-9 * ws->ldh * ws->cap, hipGetErrorString(e));
@@ -279,12 +280,13 @@ int bq_chol_ws_create(bq_ctx *ctx, int64_t n, bq_chol_ws **out) {
         return BQ_ERR_NOMEM;
     }
     ws->super_max = ws->cap >= 24576 ? 4 : 2;   // passes per super-pass the image buffers are sized for
-    if (e == hipSuccess) e = hipMalloc(&ws->Wt, sizeof(double) * 2 * ws->super_max * 2 * NB * ws->ldh);   // 2 super-passes of images
-    if (e == hipSuccess) e = hipMalloc(&ws->LinvT, sizeof(double) * nblk * NB * NB);
-    if (e == hipSuccess) e = hipMalloc(&ws->rhs, sizeof(double) * (ws->cap + NB));
-    if (e == hipSuccess) e = hipMalloc(&ws->tmp, sizeof(double) * 4 * NB);   // up to four column slices of a block row
-    if (e == hipSuccess) e = hipMalloc(&ws->info, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&ws->ticket, sizeof(unsigned int));
+    ws->Wt = mem.dev<double>(2 * ws->super_max * 2 * NB * ws->ldh);   // 2 super-passes of images
+    ws->LinvT = mem.dev<double>(nblk * NB * NB);
+    ws->rhs = mem.dev<double>(ws->cap + NB);
+    ws->tmp = mem.dev<double>(4 * NB);   // up to four column slices of a block row
+    ws->info = mem.dev<int>(1);
+    ws->ticket = mem.dev<unsigned int>(1);
+    e = mem.error();
     if (e == hipSuccess) e = hipMemset(ws->ticket, 0, sizeof(unsigned int));
     if (e == hipSuccess && bq_potrf_diag_setup() != BQ_OK) e = hipErrorUnknown;
     if (e != hipSuccess) {
@@ -332,10 +334,6 @@ void bq_chol_ws_destroy(bq_chol_ws *ws) {
         if (e) hipEventDestroy(e);
     if (ws->s_main) hipStreamDestroy(ws->s_main);
     if (ws->s_side) hipStreamDestroy(ws->s_side);
-    for (void *p : {(void *)ws->H, (void *)ws->Wt, (void *)ws->LinvT, (void *)ws->rhs, (void *)ws->tmp, (void *)ws->info, (void *)ws->ticket,
-                    (void *)ws->mr_vec, (void *)ws->mr_state, (void *)ws->mr_part, (void *)ws->bigM, (void *)ws->bigMT,
-                    (void *)ws->big_scratch, (void *)ws->sw_t, (void *)ws->pivot_thr})
-        if (p) hipFree(p);
     if (ws->mr_flag) hipHostFree(ws->mr_flag);
     delete ws;
 }
@@ -357,7 +355,7 @@ int bq_chol_factor(bq_chol_ws *ws, int64_t np) {
     const int64_t ldh = ws->ldh;
     const double *thr = nullptr;
     if (ws->pivot_rel > 0.0) {   // thresholds from the diagonal as given, before any update touches it
-        if (!ws->pivot_thr) BQ_HIP(hipMalloc(&ws->pivot_thr, sizeof(double) * ws->cap));
+        if (!ws->pivot_thr) BQ_HIP(ws->mem.dev(&ws->pivot_thr, ws->cap));
         pivot_thr_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(ws->H, ldh, np, ws->pivot_rel, ws->pivot_thr);
         thr = ws->pivot_thr;
     }
@@ -607,17 +605,17 @@ int bq_chol_prepare_sweeps(bq_chol_ws *ws, int64_t np) {
     }
     const int64_t nbb = (np + BB - 1) / BB;
     if (ws->big_cap < nbb || ws->bb != BB) {
-        for (double **p : {&ws->bigM, &ws->bigMT, &ws->big_scratch, &ws->sw_t})
-            if (*p) {
-                hipFree(*p);
-                *p = nullptr;
-            }
+        for (double **p : {&ws->bigM, &ws->bigMT, &ws->big_scratch, &ws->sw_t}) {
+            ws->mem.release(*p);
+            *p = nullptr;
+        }
         ws->big_cap = 0;
         const int64_t want = (ws->cap + BB - 1) / BB;
-        BQ_HIP(hipMalloc(&ws->bigM, sizeof(double) * want * BB * BB));
-        BQ_HIP(hipMalloc(&ws->bigMT, sizeof(double) * want * BB * BB));
-        BQ_HIP(hipMalloc(&ws->big_scratch, sizeof(double) * want * (BB / NB) * NB * NB));
-        BQ_HIP(hipMalloc(&ws->sw_t, sizeof(double) * BB));
+        ws->bigM = ws->mem.dev<double>(want * BB * BB);
+        ws->bigMT = ws->mem.dev<double>(want * BB * BB);
+        ws->big_scratch = ws->mem.dev<double>(want * (BB / NB) * NB * NB);
+        ws->sw_t = ws->mem.dev<double>(BB);
+        BQ_HIP(ws->mem.error());
         ws->big_cap = want;
         ws->bb = BB;
     }

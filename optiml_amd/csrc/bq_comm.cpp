@@ -462,8 +462,9 @@ extern "C" int bq_ctx_probe_exchange(bq_ctx *ctx, int kind, int64_t count, int r
     BQ_ARG(count >= 1 && reps >= 1 && reps <= 10000, "count >= 1, 1 <= reps <= 10000");
     BQ_HIP(hipSetDevice(ctx->device));
     const size_t len = (size_t)count * (kind == 0 ? (size_t)ctx->world : 1);
-    double *buf = nullptr;
-    BQ_HIP(hipMalloc(&buf, sizeof(double) * len));
+    bq_scratch mem;
+    double *buf = mem.dev<double>(len);
+    BQ_HIP(mem.error());
     std::vector<hipEvent_t> ev((size_t)2 * reps, nullptr);
     const bool prof = ctx->profiling;
     ctx->profiling = false;
@@ -487,7 +488,6 @@ extern "C" int bq_ctx_probe_exchange(bq_ctx *ctx, int kind, int64_t count, int r
     }
     for (hipEvent_t x : ev)
         if (x) hipEventDestroy(x);
-    hipFree(buf);
     ctx->profiling = prof;
     BQ_TRY(rc);
     if (e != hipSuccess) {

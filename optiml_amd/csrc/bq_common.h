@@ -25,6 +25,16 @@ void bq_set_error(const char *fmt, ...);
         }                                                                                     \
     } while (0)
 
+// the end of a hipError_t chain (bq_scratch.h, bq_dev_zeroed): `what` names the function or the object being set up
+#define BQ_HIP_CHAIN(e, what)                                                     \
+    do {                                                                          \
+        const hipError_t _e = (e);                                                \
+        if (_e != hipSuccess) {                                                   \
+            bq_set_error("%s failed: %s", what, hipGetErrorString(_e));           \
+            return BQ_ERR_HIP;                                                    \
+        }                                                                         \
+    } while (0)
+
 #define BQ_TRY(expr)              \
     do {                          \
         int _rc = (expr);         \
@@ -68,6 +78,15 @@ static inline hipError_t bq_device_malloc(T **ptr, size_t bytes) { return bq_dev
 #ifndef BQ_NO_MALLOC_REDIRECT
 #define hipMalloc(ptr, bytes) bq_device_malloc((ptr), (bytes))
 #endif
+// every device buffer except the panel family (bq_problem) belongs to a bq_scratch (one call) or a bq_owner (one object)
+#include "bq_scratch.h"
+// allocate-and-zero, the commonest pair: *field = `count` elements from `mem`, cleared on `st`; continues the caller's chain `e`
+template <class Owner, class T>
+static inline hipError_t bq_dev_zeroed(hipError_t e, Owner &mem, T **field, size_t count, hipStream_t st) {
+    if (e != hipSuccess) return e;
+    if ((e = mem.dev(field, count)) != hipSuccess) return e;
+    return hipMemsetAsync(*field, 0, sizeof(T) * count, st);
+}
 
 // ---------------------------------------------------------------------------------------------
 // layout constants
@@ -165,6 +184,10 @@ struct bq_problem {
     bq_ctx *ctx = nullptr;
     int refs = 0;          // solvers alive on this problem; destroyed while some are: marked, goes with the last of them
     bool zombie = false;
+    // Owns q, sgn, X, w, s, va, vb, partials, scal, slab and gath.  NOT the panel (panel_alloc: the context's cache and its `held`
+    // list take and give it), the Hessian image (himg: bq_alloc.cpp may take it back when an allocation fails) or the placement
+    // candidates (place_candidates): the allocator itself moves those between lifetimes, and bq_problem_destroy frees them by hand.
+    bq_owner mem;
     int structure = BQ_PLAIN, storage = BQ_F64, kernel = -1;
     bool add_one = false;  // panel holds K and the Hessian entry is +-(K+1)
     int64_t n = 0;         // panel columns (= samples for kernel problems)
@@ -249,6 +272,7 @@ struct bq_al_state {
 
 struct bq_solver {
     bq_problem *p = nullptr;
+    bq_owner mem;   // every device buffer below, the masks bq_as_start allocates and the vectors of `al` included
     int kind = BQ_PG;
     int64_t N = 0, ldN = 0, nblk = 0;
     double *x = nullptr, *g = nullptr, *d = nullptr, *Qd = nullptr, *lb = nullptr, *ub = nullptr;
@@ -281,7 +305,7 @@ struct bq_solver {
 // ---------------------------------------------------------------------------------------------
 // cross-file launchers (each defined next to its kernels)
 // ---------------------------------------------------------------------------------------------
-// bq_ctx.cpp / bq_api.hip
+// bq_api.hip
 int bq_prof_begin(bq_ctx *ctx, int which, hipEvent_t *e0, hipEvent_t *e1, bool bracket = true);
 int bq_prof_end(bq_ctx *ctx, int which, hipEvent_t e0, hipEvent_t e1, bool recorded = false);
 void bq_prof_drop(bq_ctx *ctx, hipEvent_t e0, hipEvent_t e1);   // a pair that was taken and never used goes back to the pool

@@ -199,10 +199,8 @@ int bq_launch_decision_multi(bq_ctx *ctx, int kernel, double gamma, double coef0
     BQ_ARG(units <= 65535 && chunk / BQ_GT <= 2147483647, "decision grid too large");
     const int gmax = kp <= 16 ? 1 : 4;
     const int64_t groups = kp / 16, passes = (groups + gmax - 1) / gmax;
-    auto cleanup = [&]() {   // every return past this point: nothing of this frame (hW, hb, mem) is in flight afterwards
+    auto cleanup = [&]() {   // every return past this point: nothing of this frame (hW, hb, the images, mem) is in flight afterwards
         (void)hipStreamSynchronize(ctx->stream);
-        free_image(&A);
-        free_image(&B);
     };
 #define DEC_HIP(e)                                                          \
     do {                                                                    \

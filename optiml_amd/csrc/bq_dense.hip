@@ -82,23 +82,16 @@ int upload_sym_t(bq_problem *p, const double *Q, bool check, int *symmetric) {
     const int64_t n = p->n, T256 = BQ_SYM_TILE;
     *symmetric = 1;
     if (p->I1 <= p->I0) return BQ_OK;   // this rank owns no tile row
-    struct scratch {
-        double *tmp = nullptr;
-        int *flag = nullptr;
-        ~scratch() {
-            if (tmp) hipFree(tmp);
-            if (flag) hipFree(flag);
-        }
-    } s;
     const int64_t ldt = p->ld;
-    BQ_HIP(hipMalloc(&s.tmp, sizeof(double) * (size_t)T256 * (size_t)ldt));
-    BQ_HIP(hipMalloc(&s.flag, sizeof(int)));
-    BQ_HIP(hipMemsetAsync(s.flag, 0, sizeof(int), c->stream));
+    bq_scratch mem;
+    double *tmp = mem.dev<double>((size_t)T256 * (size_t)ldt);
+    int *flag = nullptr;
+    BQ_HIP(bq_dev_zeroed(mem.error(), mem, &flag, 1, c->stream));
     T *panel = reinterpret_cast<T *>(p->panel);
     const int64_t col_end = std::min(n, p->I1 * T256);
     int seen = 0, blocks = 0;
     auto look = [&]() -> int {   // has a difference been seen so far?  (one 4-byte copy; the stream is drained by it)
-        BQ_HIP(hipMemcpyAsync(&seen, s.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipMemcpyAsync(&seen, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         BQ_SYNC(c);
         return BQ_OK;
     };
@@ -109,17 +102,17 @@ int upload_sym_t(bq_problem *p, const double *Q, bool check, int *symmetric) {
         const int64_t width = check ? col_end : lower;
         // the host call returns when the pageable source has been staged: tmp is free again for the next block only after the
         // kernels of this one, which the stream orders
-        BQ_HIP(hipMemcpy2DAsync(s.tmp, (size_t)ldt * 8, Q + I * T256 * n, (size_t)n * 8, (size_t)width * 8, (size_t)rows,
+        BQ_HIP(hipMemcpy2DAsync(tmp, (size_t)ldt * 8, Q + I * T256 * n, (size_t)n * 8, (size_t)width * 8, (size_t)rows,
                                 hipMemcpyHostToDevice, c->stream));
         dense_pack_kernel<T><<<dim3((unsigned)std::min<int64_t>((lower + 255) / 256, 1024), (unsigned)rows), 256, 0, c->stream>>>(
-            s.tmp, ldt, lower, panel, I, p->I0);
+            tmp, ldt, lower, panel, I, p->I0);
         if (!check)   // the diagonal tile lies in the last strip of its tile row
             dense_mirror_diag_kernel<T><<<(unsigned)rows, 256, 0, c->stream>>>(panel + bq_sym_addr(I * T256, I * T256, p->I0),
                                                                                 bq_sym_strip_w(I, I / BQ_SYM_STRIP), rows);
         if (check) {
             const int64_t c_lo = I * T256;
             dense_symcheck_kernel<T><<<dim3((unsigned)((col_end - c_lo + 31) / 32), (unsigned)((rows + 31) / 32)), 256, 0, c->stream>>>(
-                s.tmp, ldt, 0, I, rows, c_lo, col_end, panel, p->I0, s.flag);
+                tmp, ldt, 0, I, rows, c_lo, col_end, panel, p->I0, flag);
             // a Q that is symmetric only up to rounding (a Gram matrix assembled as sklearn does) shows on the first block
             if (blocks == 0 || blocks % 32 == 31) {
                 BQ_TRY(look());
@@ -133,10 +126,10 @@ int upload_sym_t(bq_problem *p, const double *Q, bool check, int *symmetric) {
     if (check && !seen && p->I0 > 0) {
         const int64_t c_lo = p->I0 * T256;
         for (int64_t Ib = 0; Ib < p->I0; ++Ib) {
-            BQ_HIP(hipMemcpy2DAsync(s.tmp, (size_t)ldt * 8, Q + Ib * T256 * n + c_lo, (size_t)n * 8, (size_t)(col_end - c_lo) * 8,
+            BQ_HIP(hipMemcpy2DAsync(tmp, (size_t)ldt * 8, Q + Ib * T256 * n + c_lo, (size_t)n * 8, (size_t)(col_end - c_lo) * 8,
                                     (size_t)T256, hipMemcpyHostToDevice, c->stream));
             dense_symcheck_kernel<T><<<dim3((unsigned)((col_end - c_lo + 31) / 32), (unsigned)(T256 / 32)), 256, 0, c->stream>>>(
-                s.tmp, ldt, c_lo, Ib, (int)T256, c_lo, col_end, panel, p->I0, s.flag);
+                tmp, ldt, c_lo, Ib, (int)T256, c_lo, col_end, panel, p->I0, flag);
             if (Ib % 32 == 31) {
                 BQ_TRY(look());
                 if (seen) break;
@@ -177,9 +170,10 @@ bool bq_dense_host_spot_symmetric(const double *Q, int64_t n) {
 int bq_dense_agree(bq_ctx *c, bool mine, bool *any) {
     *any = mine;
     if (c->comm_kind == BQ_COMM_NONE || c->comm_kind == BQ_COMM_SHARE) return BQ_OK;
+    bq_scratch mem;
     double *fd = nullptr;
     const double bad = mine ? 1.0 : 0.0;
-    if (hipMalloc(&fd, sizeof(double)) != hipSuccess) {
+    if (mem.dev(&fd, 1) != hipSuccess) {
         bq_set_error("cannot allocate the agreement flag");
         return BQ_ERR_HIP;
     }
@@ -189,7 +183,6 @@ int bq_dense_agree(bq_ctx *c, bool mine, bool *any) {
     double total = 0.0;
     if (rc == BQ_OK && hipMemcpyAsync(&total, fd, sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BQ_ERR_HIP;
     if (rc == BQ_OK) rc = bq_ctx_sync(c);
-    hipFree(fd);
     if (rc == BQ_OK) *any = total > 0.0;
     return rc;
 }
@@ -216,8 +209,9 @@ int bq_dense_upload_rows(bq_problem *p, const double *Q) {
         return BQ_OK;
     }
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(256ll << 20) / (n * 8));
+    bq_scratch mem;   // every pass below ends in a synchronisation
     double *tmp = nullptr;
-    hipError_t e = hipMalloc(&tmp, sizeof(double) * chunk * n);
+    hipError_t e = mem.dev(&tmp, chunk * n);
     for (int64_t r = 0; e == hipSuccess && r < rows; r += chunk) {
         const int64_t cr = std::min(chunk, rows - r);
         e = hipMemcpyAsync(tmp, Q + (p->r0 + r) * n, sizeof(double) * cr * n, hipMemcpyHostToDevice, c->stream);
@@ -226,10 +220,6 @@ int bq_dense_upload_rows(bq_problem *p, const double *Q) {
         f64_to_f32_rows_kernel<<<grid, 256, 0, c->stream>>>(tmp, n, (float *)p->panel + r * p->ld, p->ld);
         e = hipStreamSynchronize(c->stream);
     }
-    if (tmp) hipFree(tmp);
-    if (e != hipSuccess) {
-        bq_set_error("panel upload failed: %s", hipGetErrorString(e));
-        return BQ_ERR_HIP;
-    }
+    BQ_HIP_CHAIN(e, "panel upload");
     return BQ_OK;
 }

@@ -343,53 +343,37 @@ int bq_launch_gram(bq_ctx *ctx, const double *X, int64_t n, int64_t d, int64_t r
                    int64_t elems, int *bad) {
     if (bad) *bad = 0;
     if (r1 <= r0) return BQ_OK;   // a rank that owns no rows (more ranks than tile rows) has nothing to build
+    bq_scratch mem;   // the flag word; freed, after the image, behind the closing sync
+    gram_images img;
     int *dbad = nullptr;
     if (storage == BQ_F64C) {
         BQ_ARG(bad != nullptr, "the compact layout needs its flag word");
-        BQ_HIP(hipMalloc(&dbad, sizeof(int)));
-        hipError_t e = hipMemsetAsync(dbad, 0, sizeof(int), ctx->stream);
-        if (e != hipSuccess) {
-            hipFree(dbad);
-            BQ_HIP(e);
-        }
+        BQ_HIP(bq_dev_zeroed(hipSuccess, mem, &dbad, 1, ctx->stream));
     }
-    struct flag_guard {
-        int *p;
-        ~flag_guard() {
-            if (p) hipFree(p);
-        }
-    } fg{dbad};
-    gram_images img;
     // pad the image so that a tile starting at any r0 stays inside it
     int rc = make_image(ctx, X, n, d, &img);
-    if (rc != BQ_OK) {
-        free_image(&img);
-        return rc;
-    }
-    if (r0 % GT != 0) {
+    if (rc == BQ_OK && r0 % GT != 0) {
         // row blocks are handed out tile-aligned by bq_row_block; anything else needs a larger pad
-        free_image(&img);
         bq_set_error("row block start %lld is not a multiple of %d", (long long)r0, GT);
-        return BQ_ERR_BADARG;
+        rc = BQ_ERR_BADARG;
     }
-    rc = run_gram(ctx, img, img, r0, r1, n, true, kernel, gamma, coef0, degree, panel, storage, ld, sym_packed, elems, dbad);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    free_image(&img);
-    if (rc != BQ_OK) return rc;
+    if (rc == BQ_OK) rc = run_gram(ctx, img, img, r0, r1, n, true, kernel, gamma, coef0, degree, panel, storage, ld, sym_packed, elems, dbad);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    BQ_TRY(rc);
     BQ_HIP(e);
     if (dbad) BQ_HIP(hipMemcpy(bad, dbad, sizeof(int), hipMemcpyDeviceToHost));
     return BQ_OK;
 }
 
 int bq_max_sq_norm(bq_ctx *ctx, const double *X, int64_t n, int64_t d, double *out) {
-    double *nrm = nullptr;
-    BQ_HIP(hipMalloc(&nrm, sizeof(double) * n));
+    bq_scratch mem;   // freed behind the closing sync
+    double *nrm = mem.dev<double>(n);
+    BQ_HIP(mem.error());
     std::vector<double> h((size_t)n);
     row_norms_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(X, n, d, nrm, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), nrm, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(nrm);
     BQ_HIP(e);
     double m = 0.0;
     for (double v : h) m = (v > m || v != v) ? v : m;   // a NaN norm stays NaN: not eligible
@@ -405,8 +389,8 @@ int bq_max_sq_norm(bq_ctx *ctx, const double *X, int64_t n, int64_t d, double *o
 int bq_launch_decision(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                        const double *SV, const double *coef, double intercept, int64_t t, const double *Xt,
                        double *out) {
+    bq_scratch mem;   // declared first: freed, after the images, behind the closing sync
     gram_images A, B;
-    double *dSV = nullptr, *dXt = nullptr, *panel = nullptr, *w = nullptr, *s = nullptr;
     const int64_t ld = bq_round_up(m, BQ_PAD);
     int64_t chunk = std::max<int64_t>(GT, ((int64_t)1 << 28) / ld / GT * GT);   // rows of test points per pass: <= 2 GiB of panel
     {
@@ -414,54 +398,28 @@ int bq_launch_decision(bq_ctx *ctx, int kernel, double gamma, double coef0, int 
         if (bq_hook("decision_chunk_rows", &hv) && hv >= 1.0) chunk = bq_round_up((int64_t)hv, GT);
     }
     chunk = std::min(chunk, bq_round_up(t, GT));
+    hipStream_t st = ctx->stream;
+    double *dSV = mem.dev<double>(m * d), *dXt = mem.dev<double>(t * d), *panel = mem.dev<double>(chunk * ld), *w = mem.dev<double>(ld);
+    double *s = mem.dev<double>(bq_round_up(t, GT));
+    hipError_t e = mem.error();
+    if (e == hipSuccess) e = hipMemcpyAsync(dSV, SV, sizeof(double) * m * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dXt, Xt, sizeof(double) * t * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(panel, 0, sizeof(double) * chunk * ld, st);   // the pad columns m .. ld stay zero: the row product reads them
+    if (e == hipSuccess) e = hipMemsetAsync(w, 0, sizeof(double) * ld, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(w, coef, sizeof(double) * m, hipMemcpyHostToDevice, st);
     int rc = BQ_OK;
-    auto cleanup = [&]() {
-        free_image(&A);
-        free_image(&B);
-        if (dSV) hipFree(dSV);
-        if (dXt) hipFree(dXt);
-        if (panel) hipFree(panel);
-        if (w) hipFree(w);
-        if (s) hipFree(s);
-    };
-#define DEC_HIP(e)                                                          \
-    do {                                                                    \
-        hipError_t _e = (e);                                                \
-        if (_e != hipSuccess) {                                             \
-            bq_set_error("%s failed: %s", #e, hipGetErrorString(_e));       \
-            cleanup();                                                      \
-            return BQ_ERR_HIP;                                              \
-        }                                                                   \
-    } while (0)
-    DEC_HIP(hipMalloc(&dSV, sizeof(double) * m * d));
-    DEC_HIP(hipMalloc(&dXt, sizeof(double) * t * d));
-    DEC_HIP(hipMalloc(&panel, sizeof(double) * chunk * ld));
-    DEC_HIP(hipMalloc(&w, sizeof(double) * ld));
-    DEC_HIP(hipMalloc(&s, sizeof(double) * bq_round_up(t, GT)));
-    DEC_HIP(hipMemcpyAsync(dSV, SV, sizeof(double) * m * d, hipMemcpyHostToDevice, ctx->stream));
-    DEC_HIP(hipMemcpyAsync(dXt, Xt, sizeof(double) * t * d, hipMemcpyHostToDevice, ctx->stream));
-    DEC_HIP(hipMemsetAsync(panel, 0, sizeof(double) * chunk * ld, ctx->stream));   // the pad columns m .. ld stay zero: the row product reads them
-    DEC_HIP(hipMemsetAsync(w, 0, sizeof(double) * ld, ctx->stream));
-    DEC_HIP(hipMemcpyAsync(w, coef, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = make_image(ctx, dXt, t, d, &A)) != BQ_OK || (rc = make_image(ctx, dSV, m, d, &B)) != BQ_OK) {
-        cleanup();
-        return rc;
-    }
+    if (e == hipSuccess && (rc = make_image(ctx, dXt, t, d, &A)) == BQ_OK) rc = make_image(ctx, dSV, m, d, &B);
     // kernel(SV, Xt)[m][t] == kernel(Xt, SV)[t][m] for all the kernels (gamma is passed in resolved)
-    for (int64_t r0 = 0; rc == BQ_OK && r0 < t; r0 += chunk) {
+    for (int64_t r0 = 0; e == hipSuccess && rc == BQ_OK && r0 < t; r0 += chunk) {
         const int64_t r1 = std::min(t, r0 + chunk);
         rc = run_gram(ctx, A, B, r0, r1, m, false, kernel, gamma, coef0, degree, panel, BQ_F64, ld);
         if (rc == BQ_OK) rc = bq_launch_gemv(ctx, panel, BQ_F64, false, r1 - r0, ld, w, s + r0, nullptr);
     }
-    if (rc != BQ_OK) {
-        cleanup();
-        return rc;
-    }
-    DEC_HIP(hipMemcpyAsync(out, s, sizeof(double) * t, hipMemcpyDeviceToHost, ctx->stream));
-    DEC_HIP(hipStreamSynchronize(ctx->stream));
+    if (e == hipSuccess && rc == BQ_OK) e = hipMemcpyAsync(out, s, sizeof(double) * t, hipMemcpyDeviceToHost, st);
+    const hipError_t synced = hipStreamSynchronize(st);   // whatever happened: nothing of this frame is in flight afterwards
+    BQ_TRY(rc);
+    BQ_HIP_CHAIN(e != hipSuccess ? e : synced, "decision function");
     for (int64_t i = 0; i < t; ++i) out[i] += intercept;
-    cleanup();
-#undef DEC_HIP
     return BQ_OK;
 }
 
@@ -469,40 +427,26 @@ int bq_launch_decision(bq_ctx *ctx, int kernel, double gamma, double coef0, int 
 // B is A (exact zero distance on the diagonal, as sklearn does when Y is X).
 int bq_launch_gram_matrix(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                           const double *A, int64_t t, const double *B, double *out) {
+    bq_scratch mem;   // declared first: freed, after the images, behind the closing sync
     gram_images ia, ib;
-    double *dA = nullptr, *dB = nullptr, *panel = nullptr;
     const bool same = (B == nullptr);
     if (same) t = m;
     const int64_t ld = bq_round_up(t, BQ_PAD);
+    hipStream_t st = ctx->stream;
+    double *dA = nullptr, *dB = nullptr, *panel = nullptr;
+    hipError_t e = mem.dev(&dA, m * d);
+    if (e == hipSuccess) e = hipMemcpyAsync(dA, A, sizeof(double) * m * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !same) e = mem.dev(&dB, t * d);
+    if (e == hipSuccess && !same) e = hipMemcpyAsync(dB, B, sizeof(double) * t * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = mem.dev(&panel, m * ld);
     int rc = BQ_OK;
-    hipError_t e = hipSuccess;
-    auto cleanup = [&]() {
-        free_image(&ia);
-        if (!same) free_image(&ib);
-        if (dA) hipFree(dA);
-        if (dB) hipFree(dB);
-        if (panel) hipFree(panel);
-    };
-    do {
-        if ((e = hipMalloc(&dA, sizeof(double) * m * d)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(dA, A, sizeof(double) * m * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if (!same) {
-            if ((e = hipMalloc(&dB, sizeof(double) * t * d)) != hipSuccess) break;
-            if ((e = hipMemcpyAsync(dB, B, sizeof(double) * t * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        }
-        if ((e = hipMalloc(&panel, sizeof(double) * m * ld)) != hipSuccess) break;
-        if ((rc = make_image(ctx, dA, m, d, &ia)) != BQ_OK) break;
-        if (!same && (rc = make_image(ctx, dB, t, d, &ib)) != BQ_OK) break;
-        if ((rc = run_gram(ctx, ia, same ? ia : ib, 0, m, t, same, kernel, gamma, coef0, degree, panel, BQ_F64, ld)) != BQ_OK) break;
-        if ((e = hipMemcpy2DAsync(out, t * 8, panel, ld * 8, t * 8, m, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    cleanup();
-    if (rc != BQ_OK) return rc;
-    if (e != hipSuccess) {
-        bq_set_error("gram matrix failed: %s", hipGetErrorString(e));
-        return BQ_ERR_HIP;
-    }
+    if (e == hipSuccess) rc = make_image(ctx, dA, m, d, &ia);
+    if (e == hipSuccess && rc == BQ_OK && !same) rc = make_image(ctx, dB, t, d, &ib);
+    if (e == hipSuccess && rc == BQ_OK) rc = run_gram(ctx, ia, same ? ia : ib, 0, m, t, same, kernel, gamma, coef0, degree, panel, BQ_F64, ld);
+    if (e == hipSuccess && rc == BQ_OK) e = hipMemcpy2DAsync(out, t * 8, panel, ld * 8, t * 8, m, hipMemcpyDeviceToHost, st);
+    const hipError_t synced = hipStreamSynchronize(st);   // whatever happened: nothing of this frame is in flight afterwards
+    BQ_TRY(rc);
+    BQ_HIP_CHAIN(e != hipSuccess ? e : synced, "gram matrix");
     return BQ_OK;
 }
 
@@ -517,6 +461,7 @@ int bq_launch_gram_matrix(bq_ctx *ctx, int kernel, double gamma, double coef0, i
 #define STREAM_SYM_EXP_ILP 4   // measured 24.7 / 24.3 / 24.0 ms per n = 100 000 product for 1 / 2 / 4
 #endif
 struct bq_stream_images {
+    bq_owner mem;   // unit, SU and slab (the image owns its two)
     gram_images img;
     // this rank owns the 128-row tiles [t0, t1) (whole canonical segments) and forms every tile (I, J), J <= I, of those rows
     // once; work units = (row tile, range of U column tiles)
@@ -758,9 +703,10 @@ int bq_stream_prepare(bq_ctx *ctx, const double *Xdev, int64_t n, int64_t d, int
         st->nunits = (int64_t)unit.size() / 4;
         const int64_t rows = t1 > t0 ? t1 - t0 : 0;
         const int64_t nslab = rows > 0 ? (t1 * (t1 - 1) - t0 * (t0 - 1)) / 2 : 0;
-        hipError_t e = hipMalloc(&st->unit, sizeof(int) * (unit.size() + 4));
-        if (e == hipSuccess) e = hipMalloc(&st->SU, sizeof(double) * (rows * kmax + 1) * 128);
-        if (e == hipSuccess) e = hipMalloc(&st->slab, sizeof(double) * (nslab + 1) * 128);
+        st->unit = st->mem.dev<int>(unit.size() + 4);
+        st->SU = st->mem.dev<double>((rows * kmax + 1) * 128);
+        st->slab = st->mem.dev<double>((nslab + 1) * 128);
+        hipError_t e = st->mem.error();
         if (e == hipSuccess && !unit.empty()) e = hipMemcpy(st->unit, unit.data(), sizeof(int) * unit.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             bq_set_error("cannot allocate the symmetric streamed-product scratch: %s", hipGetErrorString(e));
@@ -774,12 +720,7 @@ int bq_stream_prepare(bq_ctx *ctx, const double *Xdev, int64_t n, int64_t d, int
 
 void bq_stream_free(void *h) {
     if (!h) return;
-    bq_stream_images *st = (bq_stream_images *)h;
-    free_image(&st->img);
-    if (st->unit) hipFree(st->unit);
-    if (st->SU) hipFree(st->SU);
-    if (st->slab) hipFree(st->slab);
-    delete st;
+    delete (bq_stream_images *)h;
 }
 
 // mode 0: out (nb * 256) = the sum of this rank's segment vectors in segment order; mode 1: each of this

@@ -50,6 +50,7 @@ __device__ __forceinline__ double bq_poly_map(double x, int degree) {
 #include "bq_exp.h"
 
 struct gram_images {
+    bq_buffers<2> mem;   // At and a2: freed with the image, which a call declares after its bq_scratch and lets go behind its closing sync
     double *At = nullptr, *a2 = nullptr;
     int64_t mp = 0, dp = 0;
 };
@@ -57,18 +58,13 @@ struct gram_images {
 static int make_image(bq_ctx *ctx, const double *Xdev, int64_t n, int64_t d, gram_images *img) {
     img->mp = bq_round_up(n, BQ_GT);
     img->dp = bq_round_up(d, BQ_GK);
-    BQ_HIP(hipMalloc(&img->At, sizeof(double) * img->mp * img->dp));
-    BQ_HIP(hipMalloc(&img->a2, sizeof(double) * img->mp));
+    img->At = img->mem.dev<double>(img->mp * img->dp);
+    img->a2 = img->mem.dev<double>(img->mp);
+    BQ_HIP(img->mem.error());
     dim3 grid((unsigned)((img->mp + 31) / 32), (unsigned)((img->dp + 31) / 32));
     transpose_pad_kernel<<<grid, 256, 0, ctx->stream>>>(Xdev, n, d, img->At, img->mp, img->dp);
     row_norms_kernel<<<(unsigned)((img->mp + 255) / 256), 256, 0, ctx->stream>>>(Xdev, n, d, img->a2, img->mp);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
-}
-
-static void free_image(gram_images *img) {
-    if (img->At) hipFree(img->At);
-    if (img->a2) hipFree(img->a2);
-    img->At = img->a2 = nullptr;
 }
 

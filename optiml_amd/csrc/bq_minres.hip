@@ -403,13 +403,13 @@ static int minres_normal_big(bq_chol_ws *ws, const int *nA_dev, int64_t nA, int6
     hipStream_t stm = ws->ctx->stream;
     const unsigned vb = (unsigned)((np + MV_TILE - 1) / MV_TILE), gb = (unsigned)((np + 3) / 4);
     if (!ws->mr_state) {
-        BQ_HIP(hipMalloc(&ws->mr_state, 256));
+        ws->mr_state = ws->mem.dev<char>(256);
+        BQ_HIP(ws->mem.error());
         BQ_HIP(hipHostMalloc((void **)&ws->mr_flag, 2 * sizeof(int), hipHostMallocDefault));
     }
     if (ws->mr_part_cap < (int64_t)vb) {
-        if (ws->mr_part) BQ_HIP(hipFree(ws->mr_part));
-        ws->mr_part = nullptr;
-        BQ_HIP(hipMalloc(&ws->mr_part, sizeof(double) * vb));
+        ws->mem.release(ws->mr_part);
+        BQ_HIP(ws->mem.dev(&ws->mr_part, vb));
         ws->mr_part_cap = vb;
     }
     mr_state *st = (mr_state *)ws->mr_state;

@@ -33,6 +33,7 @@ enum bq_mproduct {
 
 struct bq_msolver {
     bq_problem *p = nullptr;
+    bq_owner mem;   // the device buffers below (the columns' solvers in `cls` and the plan own theirs)
     int kind = BQ_PG, k = 0;
     bq_mmethod method = BQ_M_PGFW;
     bq_mproduct product = BQ_MP_SYMM4;

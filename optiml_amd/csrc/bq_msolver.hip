@@ -192,9 +192,6 @@ extern "C" int bq_msolver_destroy(bq_msolver *m) {
     if (m == nullptr) return BQ_OK;
     hipSetDevice(m->p->ctx->device);
     (void)bq_ctx_sync(m->p->ctx);
-    for (void *ptr : {(void *)m->ql, (void *)m->sgn, (void *)m->W, (void *)m->out, (void *)m->slab, (void *)m->epi, (void *)m->scs, (void *)m->pos,
-                      (void *)m->nlive, (void *)m->al_cols, (void *)m->sx_cols, (void *)m->sx_state, (void *)m->sx_rho, (void *)m->sx_counts})
-        if (ptr) hipFree(ptr);
     if (m->nlive_host) {
         hipHostFree(m->nlive_host);
         hipEventDestroy(m->flag_event);
@@ -318,17 +315,19 @@ static int msolver_alloc(bq_msolver *m, const double *Y, const double *QL) {
     const double *col_src = QL ? QL : Y;
     double **col_dev = QL ? &m->ql : &m->sgn;
     const int64_t col_len = QL ? p->N : p->n, col_ld = QL ? p->ldN : m->ldw;
-    hipError_t e = col_src ? hipMalloc(col_dev, sizeof(double) * col_ld * k) : hipSuccess;
-    if (e == hipSuccess) e = hipMalloc(&m->W, sizeof(double) * m->ldw * slots);
-    if (e == hipSuccess) e = hipMalloc(&m->out, sizeof(double) * m->ldw * slots);
     const bool wide = m->product == BQ_MP_SYMM16;
     const int64_t slab_len = m->plan ? bq_pairs_slab_len(m->plan) : wide ? bq_symmw_slab_len(p->nb) : bq_symm_slab_len(p->nb);
-    if (e == hipSuccess) e = hipMalloc(&m->slab, sizeof(double) * slab_len);
-    if (e == hipSuccess) e = hipMalloc(&m->epi, sizeof(bq_epilogue) * 2 * k);
-    if (e == hipSuccess && m->method == BQ_M_AL) e = hipMalloc(&m->al_cols, sizeof(bq_al_col) * k);
-    if (e == hipSuccess) e = hipMalloc(&m->scs, sizeof(bq_scal *) * k);
-    if (e == hipSuccess) e = hipMalloc(&m->pos, sizeof(int) * k);
-    if (e == hipSuccess) e = hipMalloc(&m->nlive, sizeof(int));
+    bq_owner &mem = m->mem;
+    if (col_src) *col_dev = mem.dev<double>(col_ld * k);
+    m->W = mem.dev<double>(m->ldw * slots);
+    m->out = mem.dev<double>(m->ldw * slots);
+    m->slab = mem.dev<double>(slab_len);
+    m->epi = mem.dev<bq_epilogue>(2 * k);
+    if (m->method == BQ_M_AL) m->al_cols = mem.dev<bq_al_col>(k);
+    m->scs = mem.dev<bq_scal *>(k);
+    m->pos = mem.dev<int>(k);
+    m->nlive = mem.dev<int>(1);
+    hipError_t e = mem.error();
     if (e != hipSuccess) {
         bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
         return BQ_ERR_NOMEM;
@@ -570,10 +569,11 @@ extern "C" int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB,
     }
     if (rc == BQ_OK) rc = msolver_alloc(m, nullptr, nullptr);
     if (rc == BQ_OK) {
-        hipError_t e = hipMalloc(&m->sx_cols, sizeof(bq_sx_col) * k);
-        if (e == hipSuccess) e = hipMalloc(&m->sx_state, sizeof(bq_sx_state) * k);
-        if (e == hipSuccess) e = hipMalloc(&m->sx_rho, sizeof(double) * k);
-        if (e == hipSuccess) e = hipMalloc(&m->sx_counts, sizeof(long long) * 2 * k);
+        m->sx_cols = m->mem.dev<bq_sx_col>(k);
+        m->sx_state = m->mem.dev<bq_sx_state>(k);
+        m->sx_rho = m->mem.dev<double>(k);
+        m->sx_counts = m->mem.dev<long long>(2 * k);
+        hipError_t e = m->mem.error();
         if (e == hipSuccess) e = hipMemsetAsync(m->sx_state, 0, sizeof(bq_sx_state) * k, c->stream);
         if (e != hipSuccess) {
             bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
@@ -686,9 +686,8 @@ extern "C" int bq_msolver_run(bq_msolver *m, int64_t max_steps, bq_iter_stat *st
         was_done[cl] = s->host.done != 0;
         any = any || !s->host.done;
         if (s->stats_cap < max_steps) {
-            if (s->stats) BQ_HIP(hipFree(s->stats));
-            s->stats = nullptr;
-            BQ_HIP(hipMalloc(&s->stats, sizeof(bq_iter_stat) * max_steps));
+            s->mem.release(s->stats);
+            BQ_HIP(s->mem.dev(&s->stats, max_steps));
             s->stats_cap = max_steps;
             grown = true;
         }

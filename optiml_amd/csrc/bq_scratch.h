@@ -1,7 +1,10 @@
-// The device scratch of one call: every buffer a one-shot entry point allocates is handed out by, and freed with, one bq_scratch.
-// Declare it before the first buffer and let it go out of scope after the call's closing bq_ctx_sync: the destructor is the only
-// place that frees.  Copies, launches and the NOMEM-versus-HIP decision stay with the caller, which continues its hipError_t chain
-// from error().  One allocation per request (no arena): bq_device_malloc retries, and its test hook compares, per request.
+// The owner of device buffers: every buffer a one-shot entry point allocates (bq_scratch), and every buffer a long-lived object —
+// a problem, a solver, a workspace — keeps (bq_owner, a member of that object), is handed out by, and freed with, one owner.
+// A call declares its bq_scratch before the first buffer and lets it go out of scope after the call's closing bq_ctx_sync; an object's
+// destroy function synchronises, tears down what is not device memory, and deletes the object.  The destructor (and release, for a
+// buffer that regrows or serves the set-up only) is the only place that frees.  Copies, launches and the NOMEM-versus-HIP decision
+// stay with the caller, which continues its hipError_t chain from error().  One allocation per request (no arena): bq_device_malloc
+// retries, and its test hook compares, per request.
 // Needs hipError_t / hipSuccess from the includer and nothing else of HIP (tests/c/scratch_check.cpp compiles it against stubs).
 #pragma once
 #include <cstddef>
@@ -9,13 +12,14 @@
 hipError_t bq_device_malloc(void **ptr, size_t bytes);
 hipError_t bq_device_free(void *ptr);
 
-struct bq_scratch {
-    static constexpr int CAP = 16;   // the largest user (held-out calibration) takes 14
+template <int N>
+struct bq_buffers {
+    static constexpr int CAP = N;
 
-    bq_scratch() = default;
-    bq_scratch(const bq_scratch &) = delete;
-    bq_scratch &operator=(const bq_scratch &) = delete;
-    ~bq_scratch() {
+    bq_buffers() = default;
+    bq_buffers(const bq_buffers &) = delete;
+    bq_buffers &operator=(const bq_buffers &) = delete;
+    ~bq_buffers() {
         for (int i = 0; i < n_; ++i) (void)bq_device_free(ptrs_[i]);
     }
 
@@ -34,6 +38,23 @@ struct bq_scratch {
         if (p != nullptr) ptrs_[n_++] = p;
         return (T *)p;
     }
+    // the same into a field of the owning object: *field = dev<T>(count), null on failure
+    template <class T>
+    hipError_t dev(T **field, size_t count) {
+        *field = dev<T>(count);
+        return err_;
+    }
+
+    // frees one buffer now and forgets it (its slot is free for the next request); null or a pointer this owner did not hand
+    // out: nothing happens.  The caller clears its own copy of the pointer.
+    void release(const void *ptr) {
+        for (int i = 0; ptr != nullptr && i < n_; ++i)
+            if (ptrs_[i] == ptr) {
+                (void)bq_device_free(ptrs_[i]);
+                ptrs_[i] = ptrs_[--n_];
+                return;
+            }
+    }
 
     hipError_t error() const { return err_; }   // the first failure
 
@@ -42,3 +63,6 @@ struct bq_scratch {
     int n_ = 0;
     hipError_t err_ = hipSuccess;
 };
+
+using bq_scratch = bq_buffers<16>;   // one call: the largest user (held-out calibration) takes 14
+using bq_owner = bq_buffers<64>;     // one object: the largest (the active-set workspace with its CG vectors) takes about 30

@@ -51,6 +51,7 @@ struct bq_smo_scal {
 
 struct bq_smo {
     bq_problem *p = nullptr;
+    bq_owner mem;   // every device buffer below
     int task = BQ_SVC;
     int64_t n = 0;
     double C = 1.0, eps = 0.0, tol = 1e-3;
@@ -1382,9 +1383,6 @@ extern "C" int bq_smo_destroy(bq_smo *s) {
     if (s == nullptr) return BQ_OK;
     hipSetDevice(s->p->ctx->device);
     hipStreamSynchronize(s->p->ctx->stream);
-    for (void *ptr : {(void *)s->y, (void *)s->a, (void *)s->am, (void *)s->err, (void *)s->nz, (void *)s->cf, (void *)s->sc,
-                      (void *)s->ctl, (void *)s->spec_res})
-        if (ptr) hipFree(ptr);
     bq_problem *p = s->p;
     delete s;
     bq_problem_unref(p);
@@ -1424,13 +1422,10 @@ extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C,
     s->eps = epsilon;
     s->tol = tol;
     hipError_t e = hipSuccess;
-    for (double **v : {&s->y, &s->a, &s->am, &s->err}) {
-        if (e == hipSuccess) e = hipMalloc(v, sizeof(double) * n);
-        if (e == hipSuccess) e = hipMemsetAsync(*v, 0, sizeof(double) * n, c->stream);
-    }
-    if (e == hipSuccess) e = hipMalloc(&s->nz, sizeof(int) * n);
-    if (e == hipSuccess) e = hipMalloc(&s->cf, sizeof(double) * n);
-    if (e == hipSuccess) e = hipMalloc(&s->sc, sizeof(bq_smo_scal));
+    for (double **v : {&s->y, &s->a, &s->am, &s->err}) e = bq_dev_zeroed(e, s->mem, v, n, c->stream);
+    if (e == hipSuccess) e = s->mem.dev(&s->nz, n);
+    if (e == hipSuccess) e = s->mem.dev(&s->cf, n);
+    if (e == hipSuccess) e = s->mem.dev(&s->sc, 1);
     // helper workgroups of the full sweeps: hook smo_helpers (0 = the walker alone).  Default 48: measured at n = 100 000
     // the sweeps take 455 / 357 / 344 / 355 / 365 / 380 / 433 / 479 ms with 16 / 32 / 48 / 64 / 96 / 128 / 192 / 255
     // helpers — past ~48 the extra pollers of the control line cost the walker more than the extra gather rate brings
@@ -1442,10 +1437,11 @@ extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C,
     if (s->helpers < SMO_T / 64) s->helpers = 0;   // the first batch after a pair step wants one CU per sample
     if (e == hipSuccess && s->helpers) {
         const unsigned int ctl0[SPEC_WORDS] = {2u};   // version 2: a zeroed result (version 0) never matches
-        e = hipMalloc(&s->ctl, sizeof(ctl0));
+        e = s->mem.dev(&s->ctl, SPEC_WORDS);
         if (e == hipSuccess) e = hipMemcpyAsync(s->ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, c->stream);
         if (n * 16 >= ((int64_t)1 << 31)) e = hipErrorInvalidValue;   // 32-bit byte offsets of the result buffer
-        if (e == hipSuccess) e = hipMalloc(&s->spec_res, (size_t)16 * n);
+        if (e == hipSuccess) s->spec_res = s->mem.dev<smo_u4>(n);
+        if (e == hipSuccess) e = s->mem.error();
         if (e == hipSuccess) e = hipMemsetAsync(s->spec_res, 0, (size_t)16 * n, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // ctl0 lives on this stack frame
     }

@@ -45,6 +45,7 @@ struct pinfo {
 }  // namespace
 
 struct bq_pairs_plan {
+    bq_owner mem;   // the device buffers below
     int ncls = 0, m = 0, kpad = 0, nch = 0, lmax = 0;
     int64_t nb = 0, slab_len = 0, nsingle = 0, ndiag = 0;
     std::vector<int> ct, pairs;
@@ -425,9 +426,6 @@ __global__ __launch_bounds__(64) void symmp_all_live_kernel(const int *__restric
 
 void bq_pairs_plan_destroy(bq_pairs_plan *pl) {
     if (pl == nullptr) return;
-    for (void *ptr : {(void *)pl->single, (void *)pl->diag, (void *)pl->info, (void *)pl->dct, (void *)pl->dpairs, (void *)pl->plive,
-                      (void *)pl->ccnt, (void *)pl->cslot})
-        if (ptr) hipFree(ptr);
     delete pl;
 }
 
@@ -482,14 +480,15 @@ int bq_pairs_plan_create(bq_problem *p, int ncls, const int *cls_tiles, int m, c
         pl->lmax = std::max(pl->lmax, pi.L);
     }
     pl->slab_len = base;
-    hipError_t e = hipMalloc(&pl->single, sizeof(pitem) * std::max<size_t>(1, single.size()));
-    if (e == hipSuccess) e = hipMalloc(&pl->diag, sizeof(pitem) * std::max<size_t>(1, diag.size()));
-    if (e == hipSuccess) e = hipMalloc(&pl->info, sizeof(pinfo) * m);
-    if (e == hipSuccess) e = hipMalloc(&pl->dct, sizeof(int) * (ncls + 1));
-    if (e == hipSuccess) e = hipMalloc(&pl->dpairs, sizeof(int) * 2 * m);
-    if (e == hipSuccess) e = hipMalloc(&pl->plive, sizeof(int) * m);
-    if (e == hipSuccess) e = hipMalloc(&pl->ccnt, sizeof(int) * ncls);
-    if (e == hipSuccess) e = hipMalloc(&pl->cslot, sizeof(int) * ncls * pl->kpad);
+    pl->single = pl->mem.dev<pitem>(std::max<size_t>(1, single.size()));
+    pl->diag = pl->mem.dev<pitem>(std::max<size_t>(1, diag.size()));
+    pl->info = pl->mem.dev<pinfo>(m);
+    pl->dct = pl->mem.dev<int>(ncls + 1);
+    pl->dpairs = pl->mem.dev<int>(2 * m);
+    pl->plive = pl->mem.dev<int>(m);
+    pl->ccnt = pl->mem.dev<int>(ncls);
+    pl->cslot = pl->mem.dev<int>((size_t)ncls * pl->kpad);
+    hipError_t e = pl->mem.error();
     hipStream_t st = p->ctx->stream;
     if (e == hipSuccess && !single.empty()) e = hipMemcpyAsync(pl->single, single.data(), sizeof(pitem) * single.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && !diag.empty()) e = hipMemcpyAsync(pl->diag, diag.data(), sizeof(pitem) * diag.size(), hipMemcpyHostToDevice, st);

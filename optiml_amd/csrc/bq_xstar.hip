@@ -104,21 +104,14 @@ __global__ void xs_neg_kernel(int64_t N, int64_t np, const double *__restrict__ 
     if (i < np) rhs[i] = i < N ? -q[i] : 0.0;
 }
 
-struct dev_vecs {
-    double *buf = nullptr;
-    ~dev_vecs() {
-        if (buf) hipFree(buf);
-    }
-};
-
 int minres_solve(bq_problem *p, double *x_host, int64_t *iters) {
     bq_ctx *c = p->ctx;
     hipStream_t st = c->stream;
     const int64_t N = p->N, ld = p->ldN;
-    dev_vecs mem;
-    BQ_HIP(hipMalloc(&mem.buf, sizeof(double) * (8 * ld + 8)));
-    BQ_HIP(hipMemsetAsync(mem.buf, 0, sizeof(double) * (8 * ld + 8), st));
-    double *x = mem.buf, *r1 = x + ld, *r2 = r1 + ld, *y = r2 + ld, *v = y + ld, *w = v + ld, *w1 = w + ld, *w2 = w1 + ld,
+    bq_scratch mem;
+    double *buf = nullptr;
+    BQ_HIP(bq_dev_zeroed(hipSuccess, mem, &buf, 8 * ld + 8, st));
+    double *x = buf, *r1 = x + ld, *r2 = r1 + ld, *y = r2 + ld, *v = y + ld, *w = v + ld, *w1 = w + ld, *w2 = w1 + ld,
            *sc = w2 + ld;
     double h[2] = {0.0, 0.0};
     auto fetch = [&](int k) {

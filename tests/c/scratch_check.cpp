@@ -3,7 +3,8 @@
 // none): every request after the failure returns null without reaching the allocator, error() is the first failure, and the
 // destructor frees exactly the pointers handed out, once each.  A zero-count request is hipMalloc(0) as the converted functions
 // had it: the allocator IS asked (so the retry and its test hook see the request), answers success with a null pointer, the
-// chain goes on, and nothing is freed for it.
+// chain goes on, and nothing is freed for it.  release(ptr) frees one buffer at once and forgets it (null or a pointer never handed
+// out: nothing happens), and the object owner bq_owner takes 40 requests and frees all 40 once.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -109,6 +110,78 @@ static void over_capacity() {
     CHECK((int)g_freed.size() == bq_scratch::CAP);
 }
 
+static int freed_times(void *p) {
+    int n = 0;
+    for (void *q : g_freed) n += q == p;
+    return n;
+}
+
+// release: the pointer is freed once, at the release, and not again at destruction; null and foreign pointers are no-ops; a
+// request after a release is served, and destruction frees exactly the live set
+static void release_cases() {
+    reset(-1, hipSuccess);
+    void *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr;
+    int foreign = 0;
+    {
+        bq_owner mem;
+        a = mem.dev<double>(4);
+        b = mem.dev<int>(3);
+        c = mem.dev<long long>(2);
+        mem.release(nullptr);
+        mem.release(&foreign);                              // never handed out
+        CHECK(g_freed.empty());
+        mem.release(b);
+        CHECK(g_freed.size() == 1 && g_freed[0] == b);      // freed now
+        mem.release(b);                                     // forgotten: a second release finds nothing
+        CHECK(g_freed.size() == 1);
+        d = mem.dev<double>(7);                             // the regrow: a new request after the release
+        CHECK(d != nullptr && mem.error() == hipSuccess && g_calls == 4);
+    }
+    CHECK(g_freed.size() == 4);
+    CHECK(freed_times(a) == 1 && freed_times(b) == 1 && freed_times(c) == 1 && freed_times(d) == 1);
+    // releasing the first, the last and the only buffer
+    reset(-1, hipSuccess);
+    {
+        bq_scratch mem;
+        a = mem.dev<int>(1);
+        mem.release(a);
+        CHECK(g_freed.size() == 1);
+        a = mem.dev<int>(1);
+        b = mem.dev<int>(1);
+        c = mem.dev<int>(1);
+        mem.release(a);
+        mem.release(c);
+        CHECK(g_freed.size() == 3);
+    }
+    CHECK(g_freed.size() == 4 && freed_times(b) == 1);
+    // a release makes room again in a full owner
+    reset(-1, hipSuccess);
+    {
+        bq_scratch mem;
+        for (int r = 0; r < bq_scratch::CAP; ++r) a = mem.dev<int>(1);
+        mem.release(a);
+        CHECK(mem.dev<int>(1) != nullptr && mem.error() == hipSuccess);
+    }
+    CHECK((int)g_freed.size() == bq_scratch::CAP + 1);
+}
+
+// the object owner: 40 requests succeed, and all 40 are freed once
+static void growth() {
+    reset(-1, hipSuccess);
+    std::vector<void *> got;
+    {
+        bq_owner mem;
+        for (int r = 0; r < 40; ++r) {
+            double *p = nullptr;
+            CHECK(mem.dev(&p, (size_t)r + 1) == hipSuccess && p != nullptr);   // the form that fills a field of the object
+            got.push_back(p);
+        }
+        CHECK(g_calls == 40 && g_freed.empty());
+    }
+    CHECK(got == g_live && g_freed.size() == 40);
+    for (void *p : got) CHECK(freed_times(p) == 1);
+}
+
 int main() {
     for (int m = 0; m <= 6; ++m) {
         chain(m, -1, hipSuccess);
@@ -119,6 +192,8 @@ int main() {
     }
     zero_count();
     over_capacity();
+    release_cases();
+    growth();
     printf("scratch_check ok\n");
     return 0;
 }

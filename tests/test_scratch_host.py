@@ -1,8 +1,10 @@
-"""The owner of a one-shot entry point's device buffers (optiml_amd/csrc/bq_scratch.h) is compiled into a stand-alone host program,
-tests/c/scratch_check.cpp, against counting stubs of bq_device_malloc / bq_device_free (no HIP runtime): for 0..6 requests with
-any one of them refused, every later request returns null without reaching the allocator, error() is the first failure, and the
-destructor frees exactly what was handed out, once each; a zero-count request asks the allocator, gets a null pointer and frees
-nothing.  The program is built with AddressSanitizer and UndefinedBehaviorSanitizer, which own the double-free and leak reports."""
+"""The owner of device buffers (optiml_amd/csrc/bq_scratch.h: bq_scratch for a one-shot entry point, bq_owner as a member of a
+long-lived object) is compiled into a stand-alone host program, tests/c/scratch_check.cpp, against counting stubs of
+bq_device_malloc / bq_device_free (no HIP runtime): for 0..6 requests with any one of them refused, every later request returns
+null without reaching the allocator, error() is the first failure, and the destructor frees exactly what was handed out, once each;
+a zero-count request asks the allocator, gets a null pointer and frees nothing; release() frees one buffer at once and never again
+(null and foreign pointers: nothing), a request after it is served, and bq_owner takes 40 requests and frees all 40 once.  The
+program is built with AddressSanitizer and UndefinedBehaviorSanitizer, which own the double-free and leak reports."""
 import os
 import shutil
 import subprocess
