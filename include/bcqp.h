@@ -58,6 +58,7 @@ extern "C" {
 /* (still 3: bq_problem_hessian_image and the test entry bq_problem_last_product were added; nothing existing changed) */
 /* (still 3: bq_msolver_pairs_heldout, bq_pairwise_coupling and bq_decision_coupled were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_simplex, bq_msolver_simplex_offsets and bq_simplex_project were added; nothing existing changed) */
+/* (still 3: bq_msolver_create_simplex2 and bq_msolver_simplex2_offsets were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -441,6 +442,30 @@ int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB, const doub
                               int64_t max_iter, bq_msolver **out);
 int bq_msolver_simplex_offsets(bq_msolver *s, double *rho, int64_t *n_sv, int64_t *n_free);
 int bq_simplex_project(bq_ctx *ctx, int k, int64_t n, const double *V, const double *UB, const double *mass, double *P);
+
+/* ---- nu-SVC and nu-SVR duals on two capped simplices (sklearn.svm.NuSVC / NuSVR; libsvm's solve_nu_svc / solve_nu_svr) ------------
+ * Column c solves  min 1/2 b'Kb + q'x  over m variables in two disjoint groups, group t being the capped simplex
+ * {0 <= x <= UB on its variables, sum x = mass[c][t]}, with b = sum_j s_j x_j scattered to panel row j mod n and gradient
+ * g_j = q_j + s_j (K b)_{j mod n}.  The two equality rows of the nu-duals (sum s x = 0, sum x = R) are these two masses, R / 2 each,
+ * and the projection onto the product of the two sets is the two one-group projections taken independently.
+ *   BQ_SX_LABELS  m = n, s = S[c] (+-1 per row), group 0 the rows with S = +1, group 1 those with S = -1.  nu-SVC: UB = 1 on the
+ *                 training rows, mass = nu n / 2 twice, q NULL.  A row with UB = 0 is not trained on and its S is not read.
+ *   BQ_SX_PAIRED  m = 2n, s = +1 on j < n (group 0) and -1 on j >= n (group 1); S is NULL.  nu-SVR: UB = C, mass = C nu n / 2 twice,
+ *                 q = (-y, +y).
+ * The iteration is bq_msolver_create_simplex's with f = 1/2 x'(g - q) + q'x at the start, d'Kd = sum_j d_j s_j (K e)_{j mod n} for
+ * the folded direction e (LABELS: S o d; PAIRED: d_i - d_{n + i}), one n-row product per iteration for either layout, and the
+ * violation libsvm's Solver_NU measure: the maximum over the two groups of the group's maximal-violating-pair value (-inf for a
+ * group with an empty side).  The problem is as for bq_msolver_create_simplex.  UB: k x m in [0, 2^1021]; mass: k x 2 with
+ * 0 < mass[c][t] <= the sum of group t's box (within n roundings of it: the whole box); a group without a row of positive box,
+ * an S entry other than +-1 on a row with UB > 0, a non-finite q or an x0 (k x m) outside its set: BQ_ERR_BADARG.  Column c's
+ * iterates and records have the same bits alone, at any position and in any batch; bq_msolver_get hands out m entries.
+ * bq_msolver_simplex2_offsets: libsvm's Solver_NU::calculate_rho after a run: r_t = the mean of g over group t's free rows, summed
+ * in index order, else (min_{x = 0} g + max_{x = UB} g) / 2 over the group; r1, r2: k each; n_sv, n_free: k x 2 (the group's rows
+ * with x > 0 and its free rows).  The caller forms r = (r1 + r2) / 2 and rho = (r1 - r2) / 2. */
+enum { BQ_SX_LABELS = 0, BQ_SX_PAIRED = 1 };
+int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, const double *S, const double *UB, const double *mass,
+                               const double *q, const double *x0, double tol, int64_t max_iter, bq_msolver **out);
+int bq_msolver_simplex2_offsets(bq_msolver *s, double *r1, double *r2, int64_t *n_sv, int64_t *n_free);
 
 /* ---- Platt calibration (sklearn CalibratedClassifierCV(method='sigmoid'): calibration.py _sigmoid_calibration, once per (fold,
  * class)) -----------------------------------------------------------------------------------------------------------------------

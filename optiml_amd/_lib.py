@@ -17,6 +17,7 @@ STORAGE = {'f64': 0, 'f32': 1, 'stream': 2}
 KERNEL_LINEAR, KERNEL_POLY, KERNEL_RBF, KERNEL_SIGMOID, KERNEL_LAPLACIAN = 0, 1, 2, 3, 4
 PLAIN, SVC, SVR = 0, 1, 2
 PG, FW, AS, IP = 0, 1, 2, 3
+SX_LABELS, SX_PAIRED = 0, 1   # bq_msolver_create_simplex2's layouts
 AS_CG = 5   # ActiveSet with conjugate-gradient restricted solves (BQ_AS_CG)
 STATUS = {0: 'unknown', 1: 'optimal', 2: 'stopped'}
 GET_X, GET_G, GET_LP, GET_LM, GET_D, GET_MASK_L, GET_MASK_U, GET_X_NOW, GET_G_NOW, GET_DUAL = range(10)
@@ -131,6 +132,8 @@ PROTOTYPES = {
     'bq_msolver_create_simplex': (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, _i64, C.POINTER(_vp)]),
     'bq_msolver_simplex_offsets': (C.c_int, [_vp, _dp, C.POINTER(_i64), C.POINTER(_i64)]),
     'bq_simplex_project': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp]),
+    'bq_msolver_create_simplex2': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, _i64, C.POINTER(_vp)]),
+    'bq_msolver_simplex2_offsets': (C.c_int, [_vp, _dp, _dp, C.POINTER(_i64), C.POINTER(_i64)]),
     'bq_platt_fit': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, _ip, _dp, C.POINTER(_i64), C.POINTER(_i64), _ip]),
     'bq_msolver_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp, C.POINTER(_i64),
                                          C.POINTER(_i64), _ip, _dp]),

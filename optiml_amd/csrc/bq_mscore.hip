@@ -3,7 +3,8 @@
 // of 1024 threads that sums in a fixed order (thread t the rows t, t + 1024, ... ascending, then a fixed tree: no atomics, and nothing
 // of another column enters).  bq_msolver_svr_heldout: the intercept and the held-out squared error of a column of a
 // cross-validated SVR search.  bq_msolver_svc_heldout / _pairs_heldout: the intercept, the held-out decision values and their Platt
-// fit (bq_platt.hip) per calibrator.  bq_msolver_simplex_offsets: the offsets of the nu-one-class columns (bq_simplex.hip).
+// fit (bq_platt.hip) per calibrator.  bq_msolver_simplex_offsets / _simplex2_offsets: the offsets of the nu-one-class and of the
+// two-group (nu-SVC / nu-SVR) columns (bq_simplex.hip).
 #include "bq_msolver.h"
 #include "bq_scratch.h"
 
@@ -164,6 +165,35 @@ extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n
         }
     }
     return bq_ctx_sync_after(c, rc);
+}
+
+extern "C" int bq_msolver_simplex2_offsets(bq_msolver *m, double *r1, double *r2, int64_t *n_sv, int64_t *n_free) {
+    BQ_ARG(m && r1 && r2 && n_sv && n_free, "NULL argument");
+    BQ_ARG(m->method == BQ_M_SIMPLEX2, "the offsets take a solver of bq_msolver_create_simplex2");
+    BQ_ARG(m->initialised, "the offsets take a solver that has run");
+    bq_ctx *c = m->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int k = m->k;
+    long long *dn = m->sx_counts;
+    std::vector<double> r((size_t)(2 * k));
+    int rc = bq_sx2_launch_offsets(m->sx2_cols, k, m->sx2_paired, m->sx_rho, dn, dn + 2 * k, st);
+    if (rc == BQ_OK) {
+        hipError_t e = hipMemcpyAsync(r.data(), m->sx_rho, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + 2 * k, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("simplex offsets: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    rc = bq_ctx_sync_after(c, rc);
+    if (rc == BQ_OK)
+        for (int cl = 0; cl < k; ++cl) {
+            r1[cl] = r[2 * cl];
+            r2[cl] = r[2 * cl + 1];
+        }
+    return rc;
 }
 
 extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const double *epsilon, double *intercept, int64_t *n_sv,

@@ -20,10 +20,12 @@ struct bq_al_col {
 //   _create_pairs                   PGFW     PAIRS    boxes
 //   _create_al                      AL       SYMM4
 //   _create_simplex                 SIMPLEX  SYMM16
+//   _create_simplex2                SIMPLEX2 SYMM16
 enum bq_mmethod {
     BQ_M_PGFW,      // ProjectedGradient / FrankWolfe columns (bq_msolver::kind says which)
     BQ_M_AL,        // augmented-Lagrangian columns (bq_al.hip); epi: k entries of kind 2
     BQ_M_SIMPLEX,   // capped-simplex columns (bq_simplex.hip)
+    BQ_M_SIMPLEX2,  // two-group capped-simplex columns (bq_simplex.hip: bq_sx2_col), which own their vectors (sx2_vec)
 };
 enum bq_mproduct {
     BQ_MP_SYMM4,    // bq_symm.hip, 4 columns per panel stream
@@ -58,8 +60,14 @@ struct bq_msolver {
     bq_sx_state *sx_state = nullptr;    // k
     double *sx_rho = nullptr;           // k: bq_msolver_simplex_offsets' results on the device
     long long *sx_counts = nullptr;     // 2 k: its support and free counts
-    std::vector<double> sx_mass;
+    std::vector<double> sx_mass;        // k (BQ_M_SIMPLEX2: k x 2)
     std::vector<int> sx_full;
+    // BQ_M_SIMPLEX2: the columns' x, g, d, ub (k x sx2_m each, in this order), their labels (k x n) or null, their linear terms
+    // (k x sx2_m) or null, the groups' tau (k x 8) and the table; the bq_solver of a column holds its scalars and records only
+    bq_sx2_col *sx2_cols = nullptr;
+    double *sx2_vec = nullptr, *sx2_sgn = nullptr, *sx2_q = nullptr, *sx2_tau = nullptr;
+    int64_t sx2_m = 0;
+    bool sx2_paired = false;
     bool sx_has_x0 = false;
     bool initialised = false, started = false;
 };

@@ -25,6 +25,32 @@ struct bq_sx_col {
     bq_iter_stat *stats;
 };
 
+// one two-group column (the nu-SVC / nu-SVR duals): min 1/2 b'Kb + q'x over the product of two capped simplices, group t being
+// {0 <= x <= ub on its rows, sum x = mass[t]}, with b = sum_j s_j x_j scattered to panel row j mod n.  LABELS: m = n variables, s = sgn,
+// group 0 the rows with sgn = +1; PAIRED: m = 2n variables, s = +1 on j < n (group 0) and -1 on j >= n (group 1).
+struct bq_sx2_col {
+    long long n, m;      // panel rows; variables
+    double *x, *g, *d;   // m
+    const double *ub;    // m
+    const double *sgn;   // LABELS: n, exactly +-1 (+1 where ub = 0: such a row has no box in either group); PAIRED: null
+    const double *q;     // m, or null (0)
+    double mass[2];
+    int full[2];         // mass[t] >= the sum of group t's box
+    int has_x0;
+    double *tau;         // 8: the two groups' tau (lo, hi, th, tl each), from the search's workgroups to the direction pass
+    bq_scal *sc;
+    bq_sx_state *st;
+    bq_iter_stat *stats;
+};
+
+// the two-group column's kernels; the iteration is the one-group one (top, project, product, close) with the search on one
+// workgroup per (column, group).  offsets: libsvm's Solver_NU::calculate_rho per group, r / n_sv / n_free: k x 2
+int bq_sx2_launch_project(const bq_sx2_col *cols, int k, bool paired, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st);
+int bq_sx2_launch_start(const bq_sx2_col *cols, int k, bool paired, const double *out, int64_t ldw, hipStream_t st);
+int bq_sx2_launch_close(const bq_sx2_col *cols, int k, bool paired, const int *pos, const double *out, int64_t ldw, hipStream_t st);
+int bq_sx2_launch_top(const bq_sx2_col *cols, int k, int *pos, int *nlive, hipStream_t st);
+int bq_sx2_launch_offsets(const bq_sx2_col *cols, int k, bool paired, double *r, long long *n_sv, long long *n_free, hipStream_t st);
+
 // cols: device table of k columns; pos, nlive: as in bq_msolver.hip.  init: the start point and W[:, c] = x of every column
 int bq_sx_launch_project(const bq_sx_col *cols, int k, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st);
 int bq_sx_launch_start(const bq_sx_col *cols, int k, const double *out, int64_t ldw, hipStream_t st);

@@ -16,6 +16,13 @@
 // breakpoint lies strictly inside the bracket, phi is one linear piece there and tau is its root.  Every reduction is the fixed
 // tree of sx_block (a butterfly inside each wavefront, the 16 wavefronts in order), so a column's bits depend on its own
 // (x, g, s, u, r) alone: not on the batch, not on its slot.  A column is one workgroup; nothing waits on another workgroup.
+//
+// The two-group flavour (bq_sx2_col: the nu-SVC / nu-SVR duals, libsvm's solve_nu_svc / solve_nu_svr) is min 1/2 b'Kb + q'x with
+// b the signed, folded x, over the product of two capped simplices on disjoint groups of variables.  The projection onto a product
+// is the two projections taken independently: the search (sx_find_tau<2>) runs on one workgroup per (column, group), sx2_tau_kernel,
+// each leaving its tau in the column's state, and the column's direction pass, sx2_dir_kernel, follows.  top, the scalar step of
+// the close (sx_step_of, sx_commit) and the offsets' body (sx_offsets_of) are shared with the one-group column, whose
+// instantiations (GROUPS = 1) compile to what they were.
 #include "bq_common.h"
 #include "bq_scratch.h"
 #include "bq_simplex.h"
@@ -165,15 +172,28 @@ __device__ inline void sx_block_dd(double &h, double &l, double *lds) {
     l = sx_uniform(lds[2 * SX_WAVES + 1]);
 }
 
+// the box of row i as one group's search sees it.  GROUPS = 1: ub[i].  GROUPS = 2 with labels: ub[i] on the rows whose sign is the
+// group's (want), 0 on the others, which the search then passes over like any row without a box (a group that is an index range has
+// sgn null and its own pointers)
+template <int GROUPS>
+__device__ inline double sx_box(const double *__restrict__ ub, const double *__restrict__ sgn, double want, long long i) {
+    if constexpr (GROUPS == 2) {
+        if (sgn != nullptr && sgn[i] != want) return 0.0;
+    }
+    return ub[i];
+}
+
 // tau of P(x - s g) onto {0 <= p <= ub, sum p = mass}; full: mass >= sum ub (P = ub).  Every thread returns the same value.
+template <int GROUPS>
 __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restrict__ x, const double *__restrict__ g, double s,
-                                              const double *__restrict__ ub, double mass, int full, double *lds) {
+                                              const double *__restrict__ ub, const double *__restrict__ sgn, double want, double mass,
+                                              int full, double *lds) {
     const int tid = threadIdx.x;
     double lo, hi;
     {   // the bracket: phi(min (v - u)) = sum u >= mass > 0 = phi(max v)
         double m[2] = {-INFINITY, -INFINITY};
         for (long long i = tid; i < n; i += SX_T) {
-            const double u = ub[i];
+            const double u = sx_box<GROUPS>(ub, sgn, want, i);
             if (u > 0.0) {
                 const double v = sx_v(x, g, s, i);
                 m[0] = fmax(m[0], v);
@@ -201,7 +221,7 @@ __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restr
         for (int j = 0; j <= SX_M; ++j) below[j] = upto[j] = 0;
 #pragma unroll 1
         for (long long i = tid; i < n; i += SX_T) {
-            const double u = ub[i];
+            const double u = sx_box<GROUPS>(ub, sgn, want, i);
             if (!(u > 0.0)) continue;
             const double v = sx_v(x, g, s, i), b = v - u;
 #pragma unroll
@@ -241,7 +261,7 @@ __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restr
     double sh = 0.0, sl = 0.0;
     int cnt[1] = {0};
     for (long long i = tid; i < n; i += SX_T) {
-        const double u = ub[i];
+        const double u = sx_box<GROUPS>(ub, sgn, want, i);
         if (!(u > 0.0)) continue;
         const double v = sx_v(x, g, s, i), b = v - u;
         if (v <= lo) continue;
@@ -276,7 +296,7 @@ __global__ __launch_bounds__(SX_T) void sx_project_kernel(const bq_sx_col *__res
     if (init) {
         double *w = W + (int64_t)blockIdx.x * ldw;
         if (!c.has_x0) {
-            const sx_tau tau = sx_find_tau(n, nullptr, nullptr, 0.0, c.ub, c.mass, c.full, lds);
+            const sx_tau tau = sx_find_tau<1>(n, nullptr, nullptr, 0.0, c.ub, nullptr, 0.0, c.mass, c.full, lds);
             for (long long i = tid; i < n; i += SX_T) {
                 const double u = c.ub[i];
                 c.x[i] = u > 0.0 ? sx_point(0.0, 0.0 - u, u, tau) : 0.0;
@@ -288,7 +308,7 @@ __global__ __launch_bounds__(SX_T) void sx_project_kernel(const bq_sx_col *__res
     }
     if (c.sc->done) return;
     const double s = c.st->s;
-    const sx_tau tau = sx_find_tau(n, c.x, c.g, s, c.ub, c.mass, c.full, lds);
+    const sx_tau tau = sx_find_tau<1>(n, c.x, c.g, s, c.ub, nullptr, 0.0, c.mass, c.full, lds);
     double *w = W + (int64_t)pos[blockIdx.x] * ldw;
     double a[2] = {0.0, 0.0};
     for (long long i = tid; i < n; i += SX_T) {
@@ -319,7 +339,7 @@ __global__ __launch_bounds__(SX_T) void sx_project_only_kernel(long long n, cons
     __shared__ double lds[SX_LDS];
     const double *v = V + (long long)blockIdx.x * n, *ub = UB + (long long)blockIdx.x * n;
     double *p = P + (long long)blockIdx.x * n;
-    const sx_tau tau = sx_find_tau(n, v, nullptr, 0.0, ub, mass[blockIdx.x], full[blockIdx.x], lds);
+    const sx_tau tau = sx_find_tau<1>(n, v, nullptr, 0.0, ub, nullptr, 0.0, mass[blockIdx.x], full[blockIdx.x], lds);
     for (long long i = threadIdx.x; i < n; i += SX_T) {
         const double u = ub[i], vi = v[i];
         p[i] = u > 0.0 ? sx_point(vi, vi - u, u, tau) : 0.0;
@@ -337,6 +357,59 @@ __device__ inline double sx_viol(const double (&m)[2]) {
     return (m[0] > -INFINITY && m[1] > -INFINITY) ? m[0] + m[1] : -INFINITY;
 }
 
+// one thread: the state of a column at its start point: f, the violation, s = 1 and the window [f]
+__device__ inline void sx_begin(bq_scal *sc, bq_sx_state &st, double f, double viol) {
+    sc->f = f;
+    st.viol = viol;
+    st.s = 1.0;
+    st.alpha = 0.0;
+    st.win[0] = f;
+    st.nwin = 1;
+    if (!(fabs(f) <= 1.7976931348623157e308)) {
+        sc->status = BQ_ERR_NONFINITE;
+        sc->done = 1;
+    }
+}
+
+// the step of an iteration from d'Qd and the column's state (every thread, before thread 0 writes the state): a = 1 if
+// f + g'd + 1/2 d'Qd <= max(window) + 1e-4 g'd, else the minimiser -g'd / d'Qd of the segment; f at the new point;
+// s = clamp(d'd / d'Qd) (1e10 where d'Qd <= 0)
+struct sx_step {
+    double alpha, fnew, snew;
+    int nwin;
+};
+__device__ inline sx_step sx_step_of(const bq_scal *sc, const bq_sx_state *st, double dQd) {
+    const double f = sc->f, gd = st->gd, dd = st->dd;
+    const int nwin = st->nwin;
+    double fmx = st->win[0];
+    for (int j = 1; j < nwin; ++j) fmx = fmax(fmx, st->win[j]);
+    double alpha = 1.0;
+    if (!(f + gd + 0.5 * dQd <= fmx + 1e-4 * gd)) alpha = -gd / dQd;
+    const double fnew = f + (alpha * gd + 0.5 * alpha * alpha * dQd);
+    const double snew = dQd > 0.0 ? fmin(fmax(dd / dQd, 1e-10), 1e10) : 1e10;
+    return sx_step{alpha, fnew, snew, nwin};
+}
+
+// one thread: the state at the new point, the window, iter + 1
+__device__ inline void sx_commit(bq_scal *sc, bq_sx_state &st, const sx_step &p, double viol) {
+    sc->f = p.fnew;
+    st.alpha = p.alpha;
+    st.s = p.snew;
+    st.viol = viol;
+    if (p.nwin < BQ_SX_WINDOW) {
+        st.win[p.nwin] = p.fnew;
+        st.nwin = p.nwin + 1;
+    } else {
+        for (int j = 1; j < BQ_SX_WINDOW; ++j) st.win[j - 1] = st.win[j];
+        st.win[BQ_SX_WINDOW - 1] = p.fnew;
+    }
+    sc->iter += 1;
+    if (!(fabs(p.fnew) <= 1.7976931348623157e308)) {
+        sc->status = BQ_ERR_NONFINITE;
+        sc->done = 1;
+    }
+}
+
 // after the start-up product, column blockIdx.x: g = K x, f = 1/2 x'g, the violation, s = 1 and the window [f]
 __global__ __launch_bounds__(SX_T) void sx_start_kernel(const bq_sx_col *__restrict__ cols, const double *__restrict__ out, int64_t ldw) {
     __shared__ double lds[SX_LDS];
@@ -351,20 +424,7 @@ __global__ __launch_bounds__(SX_T) void sx_start_kernel(const bq_sx_col *__restr
     }
     sx_block<SX_SUM>(a, lds);
     sx_block<SX_MAX>(m, lds);
-    if (threadIdx.x == 0) {
-        bq_sx_state &st = *c.st;
-        const double f = 0.5 * a[0];
-        c.sc->f = f;
-        st.viol = sx_viol(m);
-        st.s = 1.0;
-        st.alpha = 0.0;
-        st.win[0] = f;
-        st.nwin = 1;
-        if (!(fabs(f) <= 1.7976931348623157e308)) {
-            c.sc->status = BQ_ERR_NONFINITE;
-            c.sc->done = 1;
-        }
-    }
+    if (threadIdx.x == 0) sx_begin(c.sc, *c.st, 0.5 * a[0], sx_viol(m));
 }
 
 // the close of an iteration, live column blockIdx.x, Qd = OUT[:, pos[column]]: d'Qd; a = 1 if f + g'd + 1/2 d'Qd <= max(window)
@@ -380,48 +440,24 @@ __global__ __launch_bounds__(SX_T) void sx_close_kernel(const bq_sx_col *__restr
     double a[1] = {0.0};
     for (long long i = tid; i < c.n; i += SX_T) a[0] += c.d[i] * Qd[i];
     sx_block<SX_SUM>(a, lds);
-    const double dQd = a[0], f = c.sc->f, gd = c.st->gd, dd = c.st->dd;
-    const int nwin = c.st->nwin;
-    double fmx = c.st->win[0];
-    for (int j = 1; j < nwin; ++j) fmx = fmax(fmx, c.st->win[j]);
-    double alpha = 1.0;
-    if (!(f + gd + 0.5 * dQd <= fmx + 1e-4 * gd)) alpha = -gd / dQd;
-    const double fnew = f + (alpha * gd + 0.5 * alpha * alpha * dQd);
-    const double snew = dQd > 0.0 ? fmin(fmax(dd / dQd, 1e-10), 1e10) : 1e10;
+    const sx_step p = sx_step_of(c.sc, c.st, a[0]);
     double m[2] = {-INFINITY, -INFINITY};
     for (long long i = tid; i < c.n; i += SX_T) {
-        const double xi = c.x[i] + alpha * c.d[i], gi = c.g[i] + alpha * Qd[i];
+        const double xi = c.x[i] + p.alpha * c.d[i], gi = c.g[i] + p.alpha * Qd[i];
         c.x[i] = xi;
         c.g[i] = gi;
         sx_viol_add(m, xi, gi, c.ub[i]);
     }
     sx_block<SX_MAX>(m, lds);   // (its barriers: every thread has read the state before thread 0 writes it)
-    if (tid == 0) {
-        bq_sx_state &st = *c.st;
-        c.sc->f = fnew;
-        st.alpha = alpha;
-        st.s = snew;
-        st.viol = sx_viol(m);
-        if (nwin < BQ_SX_WINDOW) {
-            st.win[nwin] = fnew;
-            st.nwin = nwin + 1;
-        } else {
-            for (int j = 1; j < BQ_SX_WINDOW; ++j) st.win[j - 1] = st.win[j];
-            st.win[BQ_SX_WINDOW - 1] = fnew;
-        }
-        c.sc->iter += 1;
-        if (!(fabs(fnew) <= 1.7976931348623157e308)) {
-            c.sc->status = BQ_ERR_NONFINITE;
-            c.sc->done = 1;
-        }
-    }
+    if (tid == 0) sx_commit(c.sc, *c.st, p, sx_viol(m));
 }
 
 // the top of an iteration (one workgroup): thread c, c + 1024, ... writes the record of its live column (iter, f, violation, the
 // last step length, s) and takes the stop tests; then thread 0 numbers the live columns in column order (mlive_kernel)
-__global__ __launch_bounds__(SX_T) void sx_top_kernel(const bq_sx_col *__restrict__ cols, int k, int *__restrict__ pos, int *__restrict__ nlive) {
+template <class COL>   // bq_sx_col or bq_sx2_col
+__global__ __launch_bounds__(SX_T) void sx_top_kernel(const COL *__restrict__ cols, int k, int *__restrict__ pos, int *__restrict__ nlive) {
     for (int c = threadIdx.x; c < k; c += SX_T) {
-        const bq_sx_col &col = cols[c];
+        const COL &col = cols[c];
         bq_scal *sc = col.sc;
         if (sc->done) continue;
         const bq_sx_state &st = *col.st;
@@ -443,17 +479,17 @@ __global__ __launch_bounds__(SX_T) void sx_top_kernel(const bq_sx_col *__restric
     *nlive = s;
 }
 
-// libsvm's calculate_rho of column blockIdx.x over the rows with u > 0, exact comparisons: the support and free counts, the
-// largest g at the upper bound and the smallest at 0 by the tree; the free rows' sum of g in index order — the first wavefront
-// loads 64 rows at a time and adds the free ones among them one after another, lowest row first
-__global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__restrict__ cols, double *__restrict__ rho,
-                                                          long long *__restrict__ n_sv, long long *__restrict__ n_free) {
-    __shared__ double lds[SX_LDS];
-    const bq_sx_col c = cols[blockIdx.x];
+// libsvm's calculate_rho over the rows with a box (sx_box: of one group where GROUPS = 2), exact comparisons: the support and free
+// counts, the largest g at the upper bound and the smallest at 0 by the tree; the free rows' sum of g in index order — the first
+// wavefront loads 64 rows at a time and adds the free ones among them one after another, lowest row first.  Thread 0 writes.
+template <int GROUPS>
+__device__ inline void sx_offsets_of(long long n, const double *__restrict__ xs, const double *__restrict__ gs,
+                                     const double *__restrict__ ub, const double *__restrict__ sgn, double want, double *lds,
+                                     double *__restrict__ rho, long long *__restrict__ n_sv, long long *__restrict__ n_free) {
     double m[2] = {-INFINITY, -INFINITY};   // m[0]: max g at x = u; m[1]: max -g at x = 0
     int cnt[2] = {0, 0};                    // rows with x > 0; rows with 0 < x < u
-    for (long long i = threadIdx.x; i < c.n; i += SX_T) {
-        const double u = c.ub[i], x = c.x[i], g = c.g[i];
+    for (long long i = threadIdx.x; i < n; i += SX_T) {
+        const double u = sx_box<GROUPS>(ub, sgn, want, i), x = xs[i], g = gs[i];
         if (!(u > 0.0)) continue;
         cnt[0] += x > 0.0;
         cnt[1] += x > 0.0 && x < u;
@@ -466,14 +502,14 @@ __global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__res
     double r;
     if (cnt[1] > 0) {
         double s = 0.0;
-        for (long long base = 0; base < c.n; base += 64) {
+        for (long long base = 0; base < n; base += 64) {
             const long long i = base + threadIdx.x;
             bool fr = false;
             double gv = 0.0;
-            if (i < c.n) {
-                const double u = c.ub[i], x = c.x[i];
+            if (i < n) {
+                const double u = sx_box<GROUPS>(ub, sgn, want, i), x = xs[i];
                 fr = u > 0.0 && x > 0.0 && x < u;
-                gv = c.g[i];
+                gv = gs[i];
             }
             unsigned long long mask = __ballot(fr);
             while (mask) {   // (the same for every lane)
@@ -486,9 +522,253 @@ __global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__res
         r = (-m[1] + m[0]) / 2;
     }
     if (threadIdx.x != 0) return;
-    rho[blockIdx.x] = r;
-    n_sv[blockIdx.x] = cnt[0];
-    n_free[blockIdx.x] = cnt[1];
+    *rho = r;
+    *n_sv = cnt[0];
+    *n_free = cnt[1];
+}
+
+__global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__restrict__ cols, double *__restrict__ rho,
+                                                          long long *__restrict__ n_sv, long long *__restrict__ n_free) {
+    __shared__ double lds[SX_LDS];
+    const bq_sx_col c = cols[blockIdx.x];
+    sx_offsets_of<1>(c.n, c.x, c.g, c.ub, nullptr, 0.0, lds, rho + blockIdx.x, n_sv + blockIdx.x, n_free + blockIdx.x);
+}
+
+// ---- the two-group column (bq_sx2_col) ------------------------------------------------------------------------------------------
+// group t of a column as the search and the offsets take it: an index range with its own pointers (PAIRED: the rows t n ... t n + n - 1,
+// sgn null) or a predicate on the labels (LABELS: all n rows, the rows with sgn = +1 for t = 0, -1 for t = 1)
+struct sx_group {
+    long long off;
+    const double *sgn;
+    double want;
+};
+template <bool PAIRED>
+__device__ inline sx_group sx_group_of(const bq_sx2_col &c, int t) {
+    if constexpr (PAIRED) return sx_group{t * c.n, nullptr, 0.0};
+    else return sx_group{0, c.sgn, t == 0 ? 1.0 : -1.0};
+}
+
+// the search of a projection: workgroup (column blockIdx.x, group blockIdx.y) leaves its group's tau in the column's tau[4 t ...].
+// init: of P(0), for the columns without an x0; else of P(x - s g), for the live columns
+template <bool PAIRED>
+__global__ __launch_bounds__(SX_T) void sx2_tau_kernel(const bq_sx2_col *__restrict__ cols, int init) {
+    __shared__ double lds[SX_LDS];
+    const bq_sx2_col c = cols[blockIdx.x];
+    const int t = blockIdx.y;
+    if (init ? c.has_x0 : c.sc->done) return;
+    const sx_group gr = sx_group_of<PAIRED>(c, t);
+    const double mass = t == 0 ? c.mass[0] : c.mass[1];   // (constant indices: the column stays in registers)
+    const int full = t == 0 ? c.full[0] : c.full[1];
+    const sx_tau tau = sx_find_tau<2>(c.n, init ? nullptr : c.x + gr.off, init ? nullptr : c.g + gr.off, init ? 0.0 : c.st->s,
+                                      c.ub + gr.off, gr.sgn, gr.want, mass, full, lds);
+    if (threadIdx.x == 0) {
+        double *o = c.tau + 4 * t;
+        o[0] = tau.lo;
+        o[1] = tau.hi;
+        o[2] = tau.th;
+        o[3] = tau.tl;
+    }
+}
+
+__device__ inline sx_tau sx2_load_tau(const double *tau, int t) {
+    return sx_tau{sx_uniform(tau[4 * t]), sx_uniform(tau[4 * t + 1]), sx_uniform(tau[4 * t + 2]), sx_uniform(tau[4 * t + 3])};
+}
+
+// the direction pass of column blockIdx.x after sx2_tau_kernel, thread i, i + 1024, ... on panel row i (LABELS: the variable i of the
+// group its label names; PAIRED: the variables i of group 0 and n + i of group 1).  init: x = P(0) per group (the columns without an
+// x0) and W[:, column] = the signed, folded x.  Else, for a live column: d = P(x - s g) - x with each variable's own group's tau,
+// W[:, pos[column]] = sgn o d (LABELS) or d_i - d_{n + i} (PAIRED), g'd and d'd over all m variables; g'd >= 0: 'optimal'
+template <bool PAIRED>
+__global__ __launch_bounds__(SX_T) void sx2_dir_kernel(const bq_sx2_col *__restrict__ cols, const int *__restrict__ pos,
+                                                       double *__restrict__ W, int64_t ldw, int init) {
+    __shared__ double lds[SX_LDS];
+    const bq_sx2_col c = cols[blockIdx.x];
+    const long long n = c.n;
+    const int tid = threadIdx.x;
+    if (!init && c.sc->done) return;
+    const bool fresh = init && !c.has_x0;   // x is written here
+    sx_tau tau[2] = {sx_tau{0.0, 0.0, 0.0, 0.0}, sx_tau{0.0, 0.0, 0.0, 0.0}};
+    if (!init || fresh) {
+        tau[0] = sx2_load_tau(c.tau, 0);
+        tau[1] = sx2_load_tau(c.tau, 1);
+    }
+    const double s = init ? 0.0 : c.st->s;
+    double *w = W + (int64_t)(init ? (int)blockIdx.x : pos[blockIdx.x]) * ldw;
+    double a[2] = {0.0, 0.0};
+    // the new value of variable j in group t: the start point, or the direction (its terms of g'd and d'd added)
+    auto variable = [&](long long j, int t) -> double {
+        const double u = c.ub[j];
+        if (init) {
+            if (fresh) c.x[j] = u > 0.0 ? sx_point(0.0, 0.0 - u, u, tau[t]) : 0.0;
+            return c.x[j];
+        }
+        const double xj = c.x[j], gj = c.g[j];
+        const double v = xj - s * gj;
+        const double p = u > 0.0 ? sx_point(v, v - u, u, tau[t]) : 0.0;
+        const double d = p - xj;
+        c.d[j] = d;
+        a[0] += gj * d;
+        a[1] += d * d;
+        return d;
+    };
+    for (long long i = tid; i < n; i += SX_T) {
+        if constexpr (PAIRED) {
+            const double lo = variable(i, 0), hi = variable(n + i, 1);
+            w[i] = lo - hi;
+        } else {
+            const double sg = c.sgn[i];
+            w[i] = sg * variable(i, sg > 0.0 ? 0 : 1);
+        }
+    }
+    if (init) return;
+    sx_block<SX_SUM>(a, lds);
+    if (tid == 0) {
+        c.st->gd = a[0];
+        c.st->dd = a[1];
+        if (a[0] >= 0.0) {
+            c.sc->status = BQ_STATUS_OPTIMAL;
+            c.sc->done = 1;
+        }
+    }
+}
+
+// libsvm's Solver_NU measure: the maximum over the two groups of the group's maximal-violating-pair value (m: group 0's max g over
+// x > 0 and max -g over x < u, then group 1's; a group with an empty side gives -inf)
+__device__ inline double sx2_viol(const double (&m)[4]) {
+    const double m0[2] = {m[0], m[1]}, m1[2] = {m[2], m[3]};
+    return fmax(sx_viol(m0), sx_viol(m1));
+}
+__device__ inline void sx2_viol_add(double (&m)[4], int t, double x, double g, double u) {
+    if (u > 0.0) {
+        if (x > 0.0) m[2 * t] = fmax(m[2 * t], g);
+        if (x < u) m[2 * t + 1] = fmax(m[2 * t + 1], -g);
+    }
+}
+
+// after the start-up product (OUT[:, column] = K b, b the folded x), column blockIdx.x: g_j = q_j + s_j (K b)_{j mod n},
+// f = 1/2 x'(g - q) + q'x, the violation, s = 1 and the window [f]
+template <bool PAIRED>
+__global__ __launch_bounds__(SX_T) void sx2_start_kernel(const bq_sx2_col *__restrict__ cols, const double *__restrict__ out, int64_t ldw) {
+    __shared__ double lds[SX_LDS];
+    const bq_sx2_col c = cols[blockIdx.x];
+    const double *Kb = out + (int64_t)blockIdx.x * ldw;
+    double a[2] = {0.0, 0.0}, m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    auto variable = [&](long long j, int t, double sKb) {
+        const double qj = c.q ? c.q[j] : 0.0, xj = c.x[j];
+        const double gj = qj + sKb;
+        c.g[j] = gj;
+        a[0] += xj * (gj - qj);
+        a[1] += qj * xj;
+        sx2_viol_add(m, t, xj, gj, c.ub[j]);
+    };
+    for (long long i = threadIdx.x; i < c.n; i += SX_T) {
+        const double kb = Kb[i];
+        if constexpr (PAIRED) {
+            variable(i, 0, kb);
+            variable(c.n + i, 1, -kb);
+        } else {
+            const double sg = c.sgn[i];
+            variable(i, sg > 0.0 ? 0 : 1, sg * kb);
+        }
+    }
+    sx_block<SX_SUM>(a, lds);
+    sx_block<SX_MAX>(m, lds);
+    if (threadIdx.x == 0) sx_begin(c.sc, *c.st, 0.5 * a[0] + a[1], sx2_viol(m));
+}
+
+// the close of an iteration, live column blockIdx.x, Qd_j = s_j OUT[j mod n, pos[column]]: d'Qd over all m variables, then
+// sx_close_kernel's step and state
+template <bool PAIRED>
+__global__ __launch_bounds__(SX_T) void sx2_close_kernel(const bq_sx2_col *__restrict__ cols, const int *__restrict__ pos,
+                                                         const double *__restrict__ out, int64_t ldw) {
+    __shared__ double lds[SX_LDS];
+    const bq_sx2_col c = cols[blockIdx.x];
+    if (c.sc->done) return;
+    const double *Kd = out + (int64_t)pos[blockIdx.x] * ldw;
+    const int tid = threadIdx.x;
+    const long long n = c.n;
+    double a[1] = {0.0};
+    for (long long i = tid; i < n; i += SX_T) {
+        const double kd = Kd[i];
+        if constexpr (PAIRED) {
+            a[0] += c.d[i] * kd;
+            a[0] += c.d[n + i] * -kd;
+        } else {
+            a[0] += c.d[i] * (c.sgn[i] * kd);
+        }
+    }
+    sx_block<SX_SUM>(a, lds);
+    const sx_step p = sx_step_of(c.sc, c.st, a[0]);
+    double m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    auto variable = [&](long long j, int t, double Qd) {
+        const double xj = c.x[j] + p.alpha * c.d[j], gj = c.g[j] + p.alpha * Qd;
+        c.x[j] = xj;
+        c.g[j] = gj;
+        sx2_viol_add(m, t, xj, gj, c.ub[j]);
+    };
+    for (long long i = tid; i < n; i += SX_T) {
+        const double kd = Kd[i];
+        if constexpr (PAIRED) {
+            variable(i, 0, kd);
+            variable(n + i, 1, -kd);
+        } else {
+            const double sg = c.sgn[i];
+            variable(i, sg > 0.0 ? 0 : 1, sg * kd);
+        }
+    }
+    sx_block<SX_MAX>(m, lds);   // (its barriers: every thread has read the state before thread 0 writes it)
+    if (tid == 0) sx_commit(c.sc, *c.st, p, sx2_viol(m));
+}
+
+// libsvm's Solver_NU::calculate_rho: workgroup (column blockIdx.x, group blockIdx.y) -> r / n_sv / n_free[2 column + group]
+template <bool PAIRED>
+__global__ __launch_bounds__(SX_T) void sx2_offsets_kernel(const bq_sx2_col *__restrict__ cols, double *__restrict__ r,
+                                                           long long *__restrict__ n_sv, long long *__restrict__ n_free) {
+    __shared__ double lds[SX_LDS];
+    const bq_sx2_col c = cols[blockIdx.x];
+    const sx_group gr = sx_group_of<PAIRED>(c, blockIdx.y);
+    const int o = 2 * blockIdx.x + blockIdx.y;
+    sx_offsets_of<2>(c.n, c.x + gr.off, c.g + gr.off, c.ub + gr.off, gr.sgn, gr.want, lds, r + o, n_sv + o, n_free + o);
+}
+
+int bq_sx2_launch_project(const bq_sx2_col *cols, int k, bool paired, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st) {
+    const int in = init ? 1 : 0;
+    if (paired) {
+        sx2_tau_kernel<true><<<dim3(k, 2), SX_T, 0, st>>>(cols, in);
+        sx2_dir_kernel<true><<<k, SX_T, 0, st>>>(cols, pos, W, ldw, in);
+    } else {
+        sx2_tau_kernel<false><<<dim3(k, 2), SX_T, 0, st>>>(cols, in);
+        sx2_dir_kernel<false><<<k, SX_T, 0, st>>>(cols, pos, W, ldw, in);
+    }
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+int bq_sx2_launch_start(const bq_sx2_col *cols, int k, bool paired, const double *out, int64_t ldw, hipStream_t st) {
+    if (paired) sx2_start_kernel<true><<<k, SX_T, 0, st>>>(cols, out, ldw);
+    else sx2_start_kernel<false><<<k, SX_T, 0, st>>>(cols, out, ldw);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+int bq_sx2_launch_close(const bq_sx2_col *cols, int k, bool paired, const int *pos, const double *out, int64_t ldw, hipStream_t st) {
+    if (paired) sx2_close_kernel<true><<<k, SX_T, 0, st>>>(cols, pos, out, ldw);
+    else sx2_close_kernel<false><<<k, SX_T, 0, st>>>(cols, pos, out, ldw);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+int bq_sx2_launch_top(const bq_sx2_col *cols, int k, int *pos, int *nlive, hipStream_t st) {
+    sx_top_kernel<<<1, SX_T, 0, st>>>(cols, k, pos, nlive);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
+}
+
+int bq_sx2_launch_offsets(const bq_sx2_col *cols, int k, bool paired, double *r, long long *n_sv, long long *n_free, hipStream_t st) {
+    if (paired) sx2_offsets_kernel<true><<<dim3(k, 2), SX_T, 0, st>>>(cols, r, n_sv, n_free);
+    else sx2_offsets_kernel<false><<<dim3(k, 2), SX_T, 0, st>>>(cols, r, n_sv, n_free);
+    BQ_HIP(hipGetLastError());
+    return BQ_OK;
 }
 
 int bq_sx_launch_project(const bq_sx_col *cols, int k, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st) {

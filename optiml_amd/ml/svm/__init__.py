@@ -1,5 +1,6 @@
 __all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV',
-           'CalibratedSVC', 'PairwiseCoupledSVC', 'OneClassSVM', 'one_class_nu_path']
+           'CalibratedSVC', 'PairwiseCoupledSVC', 'OneClassSVM', 'one_class_nu_path', 'NuSVC', 'NuSVR',
+           'nu_svc_path', 'nu_svr_path']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
@@ -9,3 +10,4 @@ from .multioutput import MultiOutputSVR
 from .calibration import CalibratedSVC
 from .coupling import PairwiseCoupledSVC
 from .oneclass import OneClassSVM, one_class_nu_path
+from .nu import NuSVC, NuSVR, nu_svc_path, nu_svr_path

@@ -1,7 +1,7 @@
 """What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`, `SVRGridSearchCV`,
 `OneClassSVM`): the device solver of many columns on one Gram panel (`_DeviceMultiSolver`: ProjectedGradient / FrankWolfe;
 `_DeviceALSolver`: the augmented-Lagrangian dual with the first-order rules; `_DeviceSimplexSolver`: the nu-one-class dual on its
-capped simplex), the one-off multi-column products, the device memory budget of a solve, and
+capped simplex; `_DeviceSimplex2Solver`: the nu-SVC / nu-SVR duals on two of them), the one-off multi-column products, the device memory budget of a solve, and
 the way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
 """
 import ctypes as C
@@ -204,6 +204,41 @@ class _DeviceSimplexSolver(_DeviceMultiSolver):
         i64 = C.POINTER(C.c_int64)
         _lib.check(self._lib.bq_msolver_simplex_offsets(self._h, _lib.ptr(rho), n_sv.ctypes.data_as(i64), n_free.ctypes.data_as(i64)))
         return rho, n_sv, n_free
+
+
+class _DeviceSimplex2Solver(_DeviceMultiSolver):
+    """`bq_msolver_create_simplex2`: k two-group columns (the nu-SVC / nu-SVR duals) on one 'plain' problem of n rows.  S: k x n
+    labels +-1 (the LABELS layout, m = n variables, group 0 the rows with +1) or None (PAIRED, m = 2n, group 0 the first n); UB:
+    k x m boxes; mass: k x 2, one per group; q: k x m linear terms or None (0); x0: k x m or None (the projection of 0 per group).
+    Every vector the solver hands out has m entries; the records are `_DeviceSimplexSolver`'s."""
+
+    def __init__(self, problem, S, UB, mass, q, tol, max_iter, x0=None):
+        UB = np.ascontiguousarray(np.atleast_2d(UB), dtype=float)
+        k, m = UB.shape
+        n = problem.dims()[1]
+        if m != (2 * n if S is None else n):   # (the library reads k x m entries of UB, q and x0)
+            raise ValueError('UB has %d columns, expected %d' % (m, 2 * n if S is None else n))
+        self._layout = _lib.SX_PAIRED if S is None else _lib.SX_LABELS
+        self._S = None if S is None else _lib.as_f64(S, k * m, 'S')
+        self._mass = _lib.as_f64(mass, 2 * k, 'mass')
+        self._q = None if q is None else _lib.as_f64(q, k * m, 'q')
+        _DeviceMultiSolver.__init__(self, problem, None, UB, None, tol, max_iter, x0=x0)
+
+    def _create(self, handle, kind, UB, ub, x0, eps, max_iter, t):
+        x0 = self._x0(x0)
+        return self._lib.bq_msolver_create_simplex2(handle, self.k, self._layout, _lib.ptr(self._S), _lib.ptr(UB),
+                                                    _lib.ptr(self._mass), _lib.ptr(self._q), _lib.ptr(x0), eps, max_iter,
+                                                    C.byref(self._h))
+
+    def offsets(self):
+        """(r1, r2, n_sv, n_free) of the columns as they stand (`bq_msolver_simplex2_offsets`): libsvm's Solver_NU::calculate_rho
+        per group (k entries each), and per (column, group) the rows with x > 0 and the rows strictly inside their box (k x 2)."""
+        r1, r2 = np.empty(self.k), np.empty(self.k)
+        n_sv, n_free = np.empty((self.k, 2), dtype=np.int64), np.empty((self.k, 2), dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        _lib.check(self._lib.bq_msolver_simplex2_offsets(self._h, _lib.ptr(r1), _lib.ptr(r2), n_sv.ctypes.data_as(i64),
+                                                         n_free.ctypes.data_as(i64)))
+        return r1, r2, n_sv, n_free
 
 
 def simplex_project(V, UB, mass):
