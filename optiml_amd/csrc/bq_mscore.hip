@@ -144,21 +144,20 @@ __global__ __launch_bounds__(1024) void mheldout_kernel(const bq_epilogue *__res
     }
 }
 
-extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n_sv, int64_t *n_free) {
-    BQ_ARG(m && rho && n_sv && n_free, "NULL argument");
-    BQ_ARG(m->method == BQ_M_SIMPLEX, "the offsets take a solver of bq_msolver_create_simplex");
+// libsvm's calculate_rho of every group from its state on the device: r (one per group), n_sv and n_free in group order (ONE: the
+// columns; else column-major k x 2)
+static int msolver_sx_offsets(bq_msolver *m, double *r, int64_t *n_sv, int64_t *n_free) {
     BQ_ARG(m->initialised, "the offsets take a solver that has run");
     bq_ctx *c = m->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const int k = m->k;
-    double *dr = m->sx_rho;
+    const int groups = m->sx_layout == BQ_SX_ONE ? m->k : 2 * m->k;
     long long *dn = m->sx_counts;
-    int rc = bq_sx_launch_offsets(m->sx_cols, k, dr, dn, dn + k, st);
+    int rc = bq_sx_launch_offsets(m->sx_cols, m->k, m->sx_layout, m->sx_rho, dn, dn + groups, st);
     if (rc == BQ_OK) {
-        hipError_t e = hipMemcpyAsync(rho, dr, sizeof(double) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + k, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        hipError_t e = hipMemcpyAsync(r, m->sx_rho, sizeof(double) * groups, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * groups, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + groups, sizeof(int64_t) * groups, hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) {
             bq_set_error("simplex offsets: %s", hipGetErrorString(e));
             rc = BQ_ERR_HIP;
@@ -167,33 +166,22 @@ extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n
     return bq_ctx_sync_after(c, rc);
 }
 
+extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n_sv, int64_t *n_free) {
+    BQ_ARG(m && rho && n_sv && n_free, "NULL argument");
+    BQ_ARG(m->method == BQ_M_SIMPLEX && m->sx_layout == BQ_SX_ONE, "the offsets take a solver of bq_msolver_create_simplex");
+    return msolver_sx_offsets(m, rho, n_sv, n_free);
+}
+
 extern "C" int bq_msolver_simplex2_offsets(bq_msolver *m, double *r1, double *r2, int64_t *n_sv, int64_t *n_free) {
     BQ_ARG(m && r1 && r2 && n_sv && n_free, "NULL argument");
-    BQ_ARG(m->method == BQ_M_SIMPLEX2, "the offsets take a solver of bq_msolver_create_simplex2");
-    BQ_ARG(m->initialised, "the offsets take a solver that has run");
-    bq_ctx *c = m->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int k = m->k;
-    long long *dn = m->sx_counts;
-    std::vector<double> r((size_t)(2 * k));
-    int rc = bq_sx2_launch_offsets(m->sx2_cols, k, m->sx2_paired, m->sx_rho, dn, dn + 2 * k, st);
-    if (rc == BQ_OK) {
-        hipError_t e = hipMemcpyAsync(r.data(), m->sx_rho, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + 2 * k, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            bq_set_error("simplex offsets: %s", hipGetErrorString(e));
-            rc = BQ_ERR_HIP;
-        }
+    BQ_ARG(m->method == BQ_M_SIMPLEX && m->sx_layout != BQ_SX_ONE, "the offsets take a solver of bq_msolver_create_simplex2");
+    std::vector<double> r((size_t)(2 * m->k));
+    BQ_TRY(msolver_sx_offsets(m, r.data(), n_sv, n_free));
+    for (int cl = 0; cl < m->k; ++cl) {
+        r1[cl] = r[2 * cl];
+        r2[cl] = r[2 * cl + 1];
     }
-    rc = bq_ctx_sync_after(c, rc);
-    if (rc == BQ_OK)
-        for (int cl = 0; cl < k; ++cl) {
-            r1[cl] = r[2 * cl];
-            r2[cl] = r[2 * cl + 1];
-        }
-    return rc;
+    return BQ_OK;
 }
 
 extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const double *epsilon, double *intercept, int64_t *n_sv,

@@ -19,13 +19,11 @@ struct bq_al_col {
 //   _create_boxes, _svr_boxes       PGFW     SYMM16   boxes
 //   _create_pairs                   PGFW     PAIRS    boxes
 //   _create_al                      AL       SYMM4
-//   _create_simplex                 SIMPLEX  SYMM16
-//   _create_simplex2                SIMPLEX2 SYMM16
+//   _create_simplex, _simplex2      SIMPLEX  SYMM16   sx_layout: ONE; LABELS or PAIRED
 enum bq_mmethod {
     BQ_M_PGFW,      // ProjectedGradient / FrankWolfe columns (bq_msolver::kind says which)
     BQ_M_AL,        // augmented-Lagrangian columns (bq_al.hip); epi: k entries of kind 2
-    BQ_M_SIMPLEX,   // capped-simplex columns (bq_simplex.hip)
-    BQ_M_SIMPLEX2,  // two-group capped-simplex columns (bq_simplex.hip: bq_sx2_col), which own their vectors (sx2_vec)
+    BQ_M_SIMPLEX,   // capped-simplex columns of one or two groups (bq_simplex.hip: bq_sx_col), which own their vectors (sx_vec)
 };
 enum bq_mproduct {
     BQ_MP_SYMM4,    // bq_symm.hip, 4 columns per panel stream
@@ -56,18 +54,18 @@ struct bq_msolver {
     int live_host = 0;            // upper bound of *nlive known to the host
     bq_al_params al_prm = {};
     bq_al_col *al_cols = nullptr;       // BQ_M_AL, k: what mal_update_kernel reads of a column
-    bq_sx_col *sx_cols = nullptr;       // BQ_M_SIMPLEX, k: the device table of the columns
-    bq_sx_state *sx_state = nullptr;    // k
-    double *sx_rho = nullptr;           // k: bq_msolver_simplex_offsets' results on the device
-    long long *sx_counts = nullptr;     // 2 k: its support and free counts
-    std::vector<double> sx_mass;        // k (BQ_M_SIMPLEX2: k x 2)
+    // BQ_M_SIMPLEX: the device table of the columns (k), their step states (k), their x, g, d, ub (k x sx_m each, in this order;
+    // sx_m = n, or 2n for PAIRED), their labels (LABELS: k x n), their linear terms (k x sx_m, or null), the groups' tau (two groups:
+    // k x 8), the offsets' results on the device (one r, two counts per group) and the groups' masses with bq_sx_check's `full`.  The
+    // bq_solver of a column holds its scalars and records only
+    bq_sx_col *sx_cols = nullptr;
+    bq_sx_state *sx_state = nullptr;
+    double *sx_vec = nullptr, *sx_sgn = nullptr, *sx_q = nullptr, *sx_tau = nullptr, *sx_rho = nullptr;
+    long long *sx_counts = nullptr;
+    std::vector<double> sx_mass;
     std::vector<int> sx_full;
-    // BQ_M_SIMPLEX2: the columns' x, g, d, ub (k x sx2_m each, in this order), their labels (k x n) or null, their linear terms
-    // (k x sx2_m) or null, the groups' tau (k x 8) and the table; the bq_solver of a column holds its scalars and records only
-    bq_sx2_col *sx2_cols = nullptr;
-    double *sx2_vec = nullptr, *sx2_sgn = nullptr, *sx2_q = nullptr, *sx2_tau = nullptr;
-    int64_t sx2_m = 0;
-    bool sx2_paired = false;
+    int64_t sx_m = 0;
+    int sx_layout = BQ_SX_ONE;
     bool sx_has_x0 = false;
     bool initialised = false, started = false;
 };

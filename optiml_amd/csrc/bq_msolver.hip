@@ -40,21 +40,18 @@
 // with mal_flush_kernel (al_flush_kernel per column) and the live kernel: a column's bits do not depend on how the iterations are
 // cut into runs.  Nesterov momentum (a jump kernel and a flush per iteration) and schedules are not batched.
 //
-// bq_msolver_create_simplex is the batch of k nu-one-class duals on a BQ_PLAIN problem (bq_simplex.hip: the capped simplex
-// {0 <= x <= UB[c], sum x = mass[c]} per column, spectral projected gradient).  Column c keeps its vectors, scalars and records in a
-// bq_solver as the others do (x, g, d, ub, sc, stats), its step state in a bq_sx_state; an iteration of all live columns is
+// bq_msolver_create_simplex and _create_simplex2 are the batch of k capped-simplex duals on a BQ_PLAIN problem (bq_simplex.hip,
+// spectral projected gradient): the nu-one-class dual, one set {0 <= x <= UB[c], sum x = mass[c]} per column (layout ONE), and the
+// nu-SVC / nu-SVR duals, whose two equality rows make the set the product of two such simplices over disjoint groups of variables
+// (LABELS, PAIRED).  A column's vectors x, g, d, ub are the solver's own (sx_vec: m = n entries each, 2n for PAIRED), its bq_solver
+// holds the scalars and records, a bq_sx_state its step state; an iteration of all live columns is
 //   top      sx_top_kernel: the record and the stop tests of every live column, then mlive_kernel's numbering — BEFORE the projection,
 //            which writes the product's input to the slots of this iteration's product
-//   project  sx_project_kernel (one workgroup per column), product  bq_launch_symmw, close  sx_close_kernel
+//   project  sx_dir_kernel (one workgroup per column; two groups: after sx_tau_kernel, the search on one workgroup per group)
+//   product  bq_launch_symmw on the signed, folded direction (n rows also for PAIRED's 2n variables, as in bq_msolver_create_svr)
+//   close    sx_close_kernel
 // so a run of max_steps iterations writes at most max_steps records per column, and a column's state after its last close waits
 // for the next run's top.
-//
-// bq_msolver_create_simplex2 is the same batch for the nu-SVC / nu-SVR duals: two equality rows, so the feasible set of a column is
-// the product of two capped simplices over disjoint groups of variables and its projection the two projections taken independently
-// (bq_sx2_col).  The projection's search runs on one workgroup per (column, group), sx2_tau_kernel, before the column's direction
-// pass, sx2_dir_kernel; the product's input is the signed, folded direction (n rows for the 2n variables of nu-SVR, as in
-// bq_msolver_create_svr), so the product is the one-class one.  A column's vectors are the solver's own (sx2_vec): the problem is
-// BQ_PLAIN and its bq_solver's vectors have n entries.
 //
 // The object and what the scoring file shares with this one are in bq_msolver.h; what scores a finished batch (held-out scoring and
 // calibration, the simplex offsets) is bq_mscore.hip.
@@ -241,27 +238,18 @@ static int upload_epi(bq_msolver *m) {
     std::vector<bq_epilogue> h;
     std::vector<bq_al_col> cols;
     std::vector<bq_sx_col> sx;
-    std::vector<bq_sx2_col> sx2;
     switch (m->method) {
-        case BQ_M_SIMPLEX2:
-            sx2.resize(k);
-            for (int c = 0; c < m->k; ++c) {
-                const bq_solver *s = m->cls[c];
-                const int64_t n = m->p->n, mm = m->sx2_m;
-                double *v = m->sx2_vec + 4 * mm * c;
-                sx2[c] = bq_sx2_col{(long long)n, (long long)mm, v, v + mm, v + 2 * mm, v + 3 * mm,
-                                    m->sx2_sgn ? m->sx2_sgn + n * c : nullptr, m->sx2_q ? m->sx2_q + mm * c : nullptr,
-                                    {m->sx_mass[2 * c], m->sx_mass[2 * c + 1]}, {m->sx_full[2 * c], m->sx_full[2 * c + 1]},
-                                    m->sx_has_x0 ? 1 : 0, m->sx2_tau + 8 * c, s->sc, m->sx_state + c, s->stats};
-            }
-            BQ_HIP(hipMemcpyAsync(m->sx2_cols, sx2.data(), sizeof(bq_sx2_col) * k, hipMemcpyHostToDevice, st));
-            break;
         case BQ_M_SIMPLEX:
             sx.resize(k);
             for (int c = 0; c < m->k; ++c) {
                 const bq_solver *s = m->cls[c];
-                sx[c] = bq_sx_col{(long long)m->p->n, s->x, s->g, s->d, s->ub, m->sx_mass[c], m->sx_full[c], m->sx_has_x0 ? 1 : 0,
-                                  s->sc, m->sx_state + c, s->stats};
+                const int64_t n = m->p->n, mm = m->sx_m;
+                const int t0 = m->sx_layout == BQ_SX_ONE ? c : 2 * c, t1 = m->sx_layout == BQ_SX_ONE ? c : 2 * c + 1;   // its groups
+                double *v = m->sx_vec + 4 * mm * c;
+                sx[c] = bq_sx_col{(long long)n, (long long)mm, v, v + mm, v + 2 * mm, v + 3 * mm,
+                                  m->sx_sgn ? m->sx_sgn + n * c : nullptr, m->sx_q ? m->sx_q + mm * c : nullptr,
+                                  {m->sx_mass[t0], m->sx_mass[t1]}, {m->sx_full[t0], m->sx_full[t1]},
+                                  m->sx_has_x0 ? 1 : 0, m->sx_tau ? m->sx_tau + 8 * c : nullptr, s->sc, m->sx_state + c, s->stats};
             }
             BQ_HIP(hipMemcpyAsync(m->sx_cols, sx.data(), sizeof(bq_sx_col) * k, hipMemcpyHostToDevice, st));
             break;
@@ -547,27 +535,32 @@ extern "C" int bq_msolver_create_al(bq_problem *p, const bq_al_params *prm, int 
     return BQ_OK;
 }
 
-extern "C" int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB, const double *mass, const double *x0, double tol,
-                                         int64_t max_iter, bq_msolver **out) {
-    BQ_ARG(p && UB && mass && out, "NULL argument");
-    BQ_ARG(k >= 1, "k must be >= 1");
+// the simplex batch of any layout.  GU: the boxes of the groups (ONE: the k columns; else 2 k) as one-group columns of n rows, a row
+// outside its group having none; mass: one per group; UB (k x m), sgn (LABELS: k x n, else null), q (k x m or null), x0 (k x m or
+// null): the columns' vectors as the device takes them
+static int msolver_create_sx(bq_problem *p, int k, int layout, const double *GU, const double *UB, const double *sgn,
+                             const double *mass, const double *q, const double *x0, double tol, int64_t max_iter, bq_msolver **out) {
     BQ_ARG(p->structure == BQ_PLAIN && p->kernel >= 0, "the simplex solver takes a kernel-built BQ_PLAIN problem");
     BQ_ARG(p->diag_add == 0.0, "the simplex solver takes a problem without a diagonal term");
     BQ_TRY(bq_need_resident_panel(p, "the batched solver", " (not streamed, not full rows)"));
     BQ_ARG(tol >= 0.0, "tol must be >= 0");
-    const int64_t n = p->n;
-    std::vector<int> full((size_t)k);
-    BQ_TRY(bq_sx_check(k, n, UB, mass, full.data()));
-    if (x0)   // inside its set: the box exactly, the mass to the rounding of a sum of n terms
-        for (int c = 0; c < k; ++c) {
+    const bool one = layout == BQ_SX_ONE;
+    const int groups = one ? k : 2 * k;
+    const int64_t n = p->n, mm = layout == BQ_SX_PAIRED ? 2 * n : n;
+    std::vector<int> full((size_t)groups);
+    BQ_TRY(bq_sx_check(groups, n, GU, mass, full.data()));
+    if (q) BQ_TRY(check_linear_terms(q, (int64_t)k * mm));
+    if (x0) {   // inside its set: the box exactly, each group's mass to the rounding of a sum of n terms
+        for (int64_t j = 0; j < (int64_t)k * mm; ++j) BQ_ARG(x0[j] >= 0.0 && x0[j] <= UB[j], "x0 must lie in its box");
+        for (int g = 0; g < groups; ++g) {
+            const double *x = x0 + (layout == BQ_SX_LABELS ? g / 2 : g) * n;   // the n variables that hold group g
             long double sum = 0.0L;
-            for (int64_t i = 0; i < n; ++i) {
-                const double x = x0[(int64_t)c * n + i];
-                BQ_ARG(x >= 0.0 && x <= UB[(int64_t)c * n + i], "x0 must lie in its box");
-                sum += x;
-            }
-            BQ_ARG(std::fabs((double)sum - mass[c]) <= (double)n * 2.220446049250313e-16 * mass[c], "x0 must sum to its column's mass");
+            for (int64_t i = 0; i < n; ++i)
+                if (GU[(int64_t)g * n + i] > 0.0) sum += x[i];
+            BQ_ARG(std::fabs((double)sum - mass[g]) <= (double)n * 2.220446049250313e-16 * mass[g],
+                   one ? "x0 must sum to its column's mass" : "x0 must sum to its group's mass");
         }
+    }
     bq_ctx *c = p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     bq_msolver *m = new bq_msolver();
@@ -579,35 +572,59 @@ extern "C" int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB,
     m->method = BQ_M_SIMPLEX;
     m->product = BQ_MP_SYMM16;
     m->sx_has_x0 = x0 != nullptr;
-    m->sx_mass.assign(mass, mass + k);
+    m->sx_mass.assign(mass, mass + groups);
     m->sx_full = full;
-    const std::vector<double> zero(x0 ? 0 : (size_t)n, 0.0);
+    m->sx_m = mm;
+    m->sx_layout = layout;
+    const std::vector<double> zero((size_t)n, 0.0);
     int rc = BQ_OK;
     for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
-        bq_solver *s = nullptr;   // the column's vectors, scalars (eps = tol) and records
-        rc = bq_solver_create(p, BQ_PG, nullptr, UB + (int64_t)cl * n, x0 ? x0 + (int64_t)cl * n : zero.data(), tol, max_iter, 0.0, &s);
+        bq_solver *s = nullptr;   // the column's scalars (eps = tol) and records; its vectors are sx_vec
+        rc = bq_solver_create(p, BQ_PG, nullptr, zero.data(), zero.data(), tol, max_iter, 0.0, &s);
         if (rc == BQ_OK) m->cls.push_back(s);
     }
     if (rc == BQ_OK) rc = msolver_alloc(m, nullptr, nullptr);
     if (rc == BQ_OK) {
+        const size_t cells = (size_t)k * (size_t)mm;
         m->sx_cols = m->mem.dev<bq_sx_col>(k);
         m->sx_state = m->mem.dev<bq_sx_state>(k);
-        m->sx_rho = m->mem.dev<double>(k);
-        m->sx_counts = m->mem.dev<long long>(2 * k);
+        m->sx_rho = m->mem.dev<double>(groups);
+        m->sx_counts = m->mem.dev<long long>(2 * groups);
+        m->sx_vec = m->mem.dev<double>(4 * cells);
+        if (!one) m->sx_tau = m->mem.dev<double>(8 * k);
+        if (sgn) m->sx_sgn = m->mem.dev<double>((size_t)k * (size_t)n);
+        if (q) m->sx_q = m->mem.dev<double>(cells);
         hipError_t e = m->mem.error();
-        if (e == hipSuccess) e = hipMemsetAsync(m->sx_state, 0, sizeof(bq_sx_state) * k, c->stream);
+        hipStream_t st = c->stream;
+        if (e == hipSuccess) e = hipMemsetAsync(m->sx_state, 0, sizeof(bq_sx_state) * k, st);
+        if (e == hipSuccess) e = hipMemsetAsync(m->sx_vec, 0, sizeof(double) * 4 * cells, st);
+        if (e == hipSuccess && !one) e = hipMemsetAsync(m->sx_tau, 0, sizeof(double) * 8 * k, st);
+        for (int cl = 0; cl < k && e == hipSuccess; ++cl) {   // x (where given) and ub of column cl
+            double *v = m->sx_vec + 4 * mm * cl;
+            if (x0) e = hipMemcpyAsync(v, x0 + mm * cl, sizeof(double) * mm, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(v + 3 * mm, UB + mm * cl, sizeof(double) * mm, hipMemcpyHostToDevice, st);
+        }
+        if (e == hipSuccess && sgn) e = hipMemcpyAsync(m->sx_sgn, sgn, sizeof(double) * k * n, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && q) e = hipMemcpyAsync(m->sx_q, q, sizeof(double) * cells, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
             bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
             rc = BQ_ERR_NOMEM;
         }
     }
-    if (rc == BQ_OK) rc = upload_epi(m);
+    if (rc == BQ_OK) rc = upload_epi(m);   // (its closing sync: the host arrays of the callers have been read)
     if (rc != BQ_OK) {
         bq_msolver_destroy(m);
         return rc;
     }
     *out = m;
     return BQ_OK;
+}
+
+extern "C" int bq_msolver_create_simplex(bq_problem *p, int k, const double *UB, const double *mass, const double *x0, double tol,
+                                         int64_t max_iter, bq_msolver **out) {
+    BQ_ARG(p && UB && mass && out, "NULL argument");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    return msolver_create_sx(p, k, BQ_SX_ONE, UB, UB, nullptr, mass, nullptr, x0, tol, max_iter, out);
 }
 
 extern "C" int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, const double *S, const double *UB, const double *mass,
@@ -617,13 +634,9 @@ extern "C" int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, cons
     BQ_ARG(layout == BQ_SX_LABELS || layout == BQ_SX_PAIRED, "layout is BQ_SX_LABELS or BQ_SX_PAIRED");
     const bool paired = layout == BQ_SX_PAIRED;
     BQ_ARG(paired ? S == nullptr : S != nullptr, "the labels S belong to BQ_SX_LABELS (k x n) and to no other layout");
-    BQ_ARG(p->structure == BQ_PLAIN && p->kernel >= 0, "the simplex solver takes a kernel-built BQ_PLAIN problem");
-    BQ_ARG(p->diag_add == 0.0, "the simplex solver takes a problem without a diagonal term");
-    BQ_TRY(bq_need_resident_panel(p, "the batched solver", " (not streamed, not full rows)"));
-    BQ_ARG(tol >= 0.0, "tol must be >= 0");
-    const int64_t n = p->n, mm = paired ? 2 * n : n;
-    // the boxes of the 2 k groups as k' = 2 k one-group columns of n rows: PAIRED has them so already; LABELS: a row of the other
-    // group is a row without a box.  The device's labels are +1 where UB = 0 (S is not read there)
+    const int64_t n = p->n;
+    // the boxes of the 2 k groups as one-group columns of n rows: PAIRED has them so already; LABELS: a row of the other group is a
+    // row without a box.  The device's labels are +1 where UB = 0 (S is not read there)
     std::vector<double> grouped, sgn;
     if (!paired) {
         grouped.assign((size_t)(2 * k) * (size_t)n, 0.0);
@@ -646,89 +659,17 @@ extern "C" int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, cons
         for (int64_t i = 0; i < n && !any; ++i) any = GU[(int64_t)g * n + i] > 0.0;
         BQ_ARG(any, "each of a column's two groups needs a row with UB > 0");
     }
-    std::vector<int> full((size_t)(2 * k));
-    BQ_TRY(bq_sx_check(2 * k, n, GU, mass, full.data()));
-    if (q) BQ_TRY(check_linear_terms(q, (int64_t)k * mm));
-    if (x0) {   // inside its set: the box exactly, each group's mass to the rounding of a sum of n terms
-        for (int64_t j = 0; j < (int64_t)k * mm; ++j) BQ_ARG(x0[j] >= 0.0 && x0[j] <= UB[j], "x0 must lie in its box");
-        for (int g = 0; g < 2 * k; ++g) {
-            long double sum = 0.0L;
-            for (int64_t i = 0; i < n; ++i)
-                if (GU[(int64_t)g * n + i] > 0.0) sum += x0[paired ? (int64_t)g * n + i : (int64_t)(g / 2) * n + i];
-            BQ_ARG(std::fabs((double)sum - mass[g]) <= (double)n * 2.220446049250313e-16 * mass[g], "x0 must sum to its group's mass");
-        }
-    }
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    bq_msolver *m = new bq_msolver();
-    m->p = p;
-    p->refs += 1;
-    m->kind = BQ_PG;
-    m->k = k;
-    m->ldw = p->ld;
-    m->method = BQ_M_SIMPLEX2;
-    m->product = BQ_MP_SYMM16;
-    m->sx_has_x0 = x0 != nullptr;
-    m->sx_mass.assign(mass, mass + 2 * k);
-    m->sx_full = full;
-    m->sx2_m = mm;
-    m->sx2_paired = paired;
-    const std::vector<double> zero((size_t)n, 0.0);
-    int rc = BQ_OK;
-    for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
-        bq_solver *s = nullptr;   // the column's scalars (eps = tol) and records; its vectors are sx2_vec
-        rc = bq_solver_create(p, BQ_PG, nullptr, zero.data(), zero.data(), tol, max_iter, 0.0, &s);
-        if (rc == BQ_OK) m->cls.push_back(s);
-    }
-    if (rc == BQ_OK) rc = msolver_alloc(m, nullptr, nullptr);
-    if (rc == BQ_OK) {
-        const size_t cells = (size_t)k * (size_t)mm;
-        m->sx2_cols = m->mem.dev<bq_sx2_col>(k);
-        m->sx_state = m->mem.dev<bq_sx_state>(k);
-        m->sx_rho = m->mem.dev<double>(2 * k);
-        m->sx_counts = m->mem.dev<long long>(4 * k);
-        m->sx2_vec = m->mem.dev<double>(4 * cells);
-        m->sx2_tau = m->mem.dev<double>(8 * k);
-        if (!paired) m->sx2_sgn = m->mem.dev<double>((size_t)k * (size_t)n);
-        if (q) m->sx2_q = m->mem.dev<double>(cells);
-        hipError_t e = m->mem.error();
-        hipStream_t st = c->stream;
-        if (e == hipSuccess) e = hipMemsetAsync(m->sx_state, 0, sizeof(bq_sx_state) * k, st);
-        if (e == hipSuccess) e = hipMemsetAsync(m->sx2_vec, 0, sizeof(double) * 4 * cells, st);
-        if (e == hipSuccess) e = hipMemsetAsync(m->sx2_tau, 0, sizeof(double) * 8 * k, st);
-        for (int cl = 0; cl < k && e == hipSuccess; ++cl) {   // x (where given) and ub of column cl
-            double *v = m->sx2_vec + 4 * mm * cl;
-            if (x0) e = hipMemcpyAsync(v, x0 + mm * cl, sizeof(double) * mm, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(v + 3 * mm, UB + mm * cl, sizeof(double) * mm, hipMemcpyHostToDevice, st);
-        }
-        if (e == hipSuccess && !paired) e = hipMemcpyAsync(m->sx2_sgn, sgn.data(), sizeof(double) * k * n, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && q) e = hipMemcpyAsync(m->sx2_q, q, sizeof(double) * cells, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            bq_set_error("batched solver: device allocation failed: %s", hipGetErrorString(e));
-            rc = BQ_ERR_NOMEM;
-        }
-    }
-    if (rc == BQ_OK) rc = upload_epi(m);   // (its closing sync: the host arrays of this frame and of the caller have been read)
-    if (rc != BQ_OK) {
-        bq_msolver_destroy(m);
-        return rc;
-    }
-    *out = m;
-    return BQ_OK;
+    return msolver_create_sx(p, k, layout, GU, UB, paired ? nullptr : sgn.data(), mass, q, x0, tol, max_iter, out);
 }
 
 static int msolver_first(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
     switch (m->method) {
-        case BQ_M_SIMPLEX:   // x = P(0) where no start point was given, g = K x, f, the violation
-            BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->pos, m->W, m->ldw, true, st));
+        case BQ_M_SIMPLEX:   // x = P(0) per group where no start point was given, the folded x as the product's input, g, f, the violation
+            BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->sx_layout, m->pos, m->W, m->ldw, true, st));
             BQ_TRY(msolver_product(m, m->k));
-            return bq_sx_launch_start(m->sx_cols, m->k, m->out, m->ldw, st);
-        case BQ_M_SIMPLEX2:   // the same with x = P(0) per group, the folded x as the product's input and g = q + s o K b
-            BQ_TRY(bq_sx2_launch_project(m->sx2_cols, m->k, m->sx2_paired, m->pos, m->W, m->ldw, true, st));
-            BQ_TRY(msolver_product(m, m->k));
-            return bq_sx2_launch_start(m->sx2_cols, m->k, m->sx2_paired, m->out, m->ldw, st);
+            return bq_sx_launch_start(m->sx_cols, m->k, m->sx_layout, m->out, m->ldw, st);
         case BQ_M_AL: return BQ_OK;   // no start-up product (created initialised): every iteration evaluates Q x afresh
         case BQ_M_PGFW: break;
     }
@@ -768,14 +709,9 @@ static int msolver_iterate(bq_msolver *m, bool first_of_run) {
     switch (m->method) {
         case BQ_M_SIMPLEX:
             BQ_TRY(bq_sx_launch_top(m->sx_cols, m->k, m->pos, m->nlive, st));
-            BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->pos, m->W, m->ldw, false, st));
+            BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->sx_layout, m->pos, m->W, m->ldw, false, st));
             BQ_TRY(msolver_product(m, m->live_host));
-            return bq_sx_launch_close(m->sx_cols, m->k, m->pos, m->out, m->ldw, st);
-        case BQ_M_SIMPLEX2:
-            BQ_TRY(bq_sx2_launch_top(m->sx2_cols, m->k, m->pos, m->nlive, st));
-            BQ_TRY(bq_sx2_launch_project(m->sx2_cols, m->k, m->sx2_paired, m->pos, m->W, m->ldw, false, st));
-            BQ_TRY(msolver_product(m, m->live_host));
-            return bq_sx2_launch_close(m->sx2_cols, m->k, m->sx2_paired, m->pos, m->out, m->ldw, st);
+            return bq_sx_launch_close(m->sx_cols, m->k, m->sx_layout, m->pos, m->out, m->ldw, st);
         case BQ_M_AL: return msolver_al_iterate(m, first_of_run);
         case BQ_M_PGFW: break;
     }
@@ -798,8 +734,7 @@ static int msolver_flush(bq_msolver *m) {
     switch (m->method) {
         case BQ_M_AL: break;
         case BQ_M_PGFW:
-        case BQ_M_SIMPLEX:
-        case BQ_M_SIMPLEX2: return BQ_OK;
+        case BQ_M_SIMPLEX: return BQ_OK;
     }
     hipStream_t st = m->p->ctx->stream;
     mal_flush_kernel<<<dim3((unsigned)((m->p->n + 255) / 256), (unsigned)m->k), 256, 0, st>>>(m->epi);
@@ -902,13 +837,13 @@ extern "C" int bq_msolver_state(const bq_msolver *m, int cls, int64_t *iter, int
 
 extern "C" int bq_msolver_get(bq_msolver *m, int cls, int what, double *out) {
     BQ_ARG(m != nullptr && cls >= 0 && cls < m->k, "solver is NULL or class out of range");
-    if (m->method == BQ_M_SIMPLEX2) {   // the column's own vectors, sx2_m entries
+    if (m->method == BQ_M_SIMPLEX) {   // the column's own vectors, sx_m entries
         BQ_ARG(out, "NULL argument");
         const int v = (what == BQ_GET_X || what == BQ_GET_X_NOW) ? 0 : (what == BQ_GET_G || what == BQ_GET_G_NOW) ? 1 : what == BQ_GET_D ? 2 : -1;
         BQ_ARG(v >= 0, "vector not available for this solver");
         bq_ctx *c = m->p->ctx;
         BQ_HIP(hipSetDevice(c->device));
-        BQ_HIP(hipMemcpyAsync(out, m->sx2_vec + (4 * cls + v) * m->sx2_m, sizeof(double) * m->sx2_m, hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipMemcpyAsync(out, m->sx_vec + (4 * cls + v) * m->sx_m, sizeof(double) * m->sx_m, hipMemcpyDeviceToHost, c->stream));
         BQ_SYNC(c);
         return BQ_OK;
     }

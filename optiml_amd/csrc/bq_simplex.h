@@ -12,50 +12,35 @@ struct bq_sx_state {
     int nwin, pad;
 };
 
-// one column as the kernels take it
-struct bq_sx_col {
-    long long n;
-    double *x, *g, *d;
-    const double *ub;
-    double mass;
-    int full;     // mass >= sum ub: the set is the single point ub
-    int has_x0;   // x holds the caller's start point (else the start is P(0))
-    bq_scal *sc;
-    bq_sx_state *st;
-    bq_iter_stat *stats;
-};
+// a column's layout: bcqp.h's BQ_SX_LABELS and BQ_SX_PAIRED (two groups), and the one-group column of bq_msolver_create_simplex
+enum { BQ_SX_ONE = 2 };
 
-// one two-group column (the nu-SVC / nu-SVR duals): min 1/2 b'Kb + q'x over the product of two capped simplices, group t being
-// {0 <= x <= ub on its rows, sum x = mass[t]}, with b = sum_j s_j x_j scattered to panel row j mod n.  LABELS: m = n variables, s = sgn,
-// group 0 the rows with sgn = +1; PAIRED: m = 2n variables, s = +1 on j < n (group 0) and -1 on j >= n (group 1).
-struct bq_sx2_col {
+// one column as the kernels take it: min 1/2 b'Kb + q'x over the product of its capped simplices, group t being {0 <= x <= ub on its
+// rows, sum x = mass[t]}, with b = sum_j s_j x_j scattered to panel row j mod n.  ONE: m = n variables in one group, s = 1, q = 0 (the
+// nu-one-class dual; sgn, q, tau null, mass[1] and full[1] unused).  LABELS: m = n, s = sgn, group 0 the rows with sgn = +1.  PAIRED:
+// m = 2n, s = +1 on j < n (group 0) and -1 on j >= n (group 1)
+struct bq_sx_col {
     long long n, m;      // panel rows; variables
     double *x, *g, *d;   // m
     const double *ub;    // m
-    const double *sgn;   // LABELS: n, exactly +-1 (+1 where ub = 0: such a row has no box in either group); PAIRED: null
+    const double *sgn;   // LABELS: n, exactly +-1 (+1 where ub = 0: such a row has no box in either group); else null
     const double *q;     // m, or null (0)
     double mass[2];
-    int full[2];         // mass[t] >= the sum of group t's box
-    int has_x0;
+    int full[2];         // mass[t] >= the sum of group t's box: the set is the single point ub
+    int has_x0;          // x holds the caller's start point (else the start is P(0) per group)
     double *tau;         // 8: the two groups' tau (lo, hi, th, tl each), from the search's workgroups to the direction pass
     bq_scal *sc;
     bq_sx_state *st;
     bq_iter_stat *stats;
 };
 
-// the two-group column's kernels; the iteration is the one-group one (top, project, product, close) with the search on one
-// workgroup per (column, group).  offsets: libsvm's Solver_NU::calculate_rho per group, r / n_sv / n_free: k x 2
-int bq_sx2_launch_project(const bq_sx2_col *cols, int k, bool paired, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st);
-int bq_sx2_launch_start(const bq_sx2_col *cols, int k, bool paired, const double *out, int64_t ldw, hipStream_t st);
-int bq_sx2_launch_close(const bq_sx2_col *cols, int k, bool paired, const int *pos, const double *out, int64_t ldw, hipStream_t st);
-int bq_sx2_launch_top(const bq_sx2_col *cols, int k, int *pos, int *nlive, hipStream_t st);
-int bq_sx2_launch_offsets(const bq_sx2_col *cols, int k, bool paired, double *r, long long *n_sv, long long *n_free, hipStream_t st);
-
-// cols: device table of k columns; pos, nlive: as in bq_msolver.hip.  init: the start point and W[:, c] = x of every column
-int bq_sx_launch_project(const bq_sx_col *cols, int k, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st);
-int bq_sx_launch_start(const bq_sx_col *cols, int k, const double *out, int64_t ldw, hipStream_t st);
-int bq_sx_launch_close(const bq_sx_col *cols, int k, const int *pos, const double *out, int64_t ldw, hipStream_t st);
+// cols: device table of k columns of one layout; pos, nlive: as in bq_msolver.hip.  project: the search (two groups: one workgroup per
+// (column, group), a launch of its own; ONE: inside the direction pass) and the direction pass; init: the start point and
+// W[:, c] = the signed, folded x of every column.  offsets: libsvm's calculate_rho per group, r / n_sv / n_free: k, or k x 2
+int bq_sx_launch_project(const bq_sx_col *cols, int k, int layout, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st);
+int bq_sx_launch_start(const bq_sx_col *cols, int k, int layout, const double *out, int64_t ldw, hipStream_t st);
+int bq_sx_launch_close(const bq_sx_col *cols, int k, int layout, const int *pos, const double *out, int64_t ldw, hipStream_t st);
 int bq_sx_launch_top(const bq_sx_col *cols, int k, int *pos, int *nlive, hipStream_t st);
-int bq_sx_launch_offsets(const bq_sx_col *cols, int k, double *rho, long long *n_sv, long long *n_free, hipStream_t st);
+int bq_sx_launch_offsets(const bq_sx_col *cols, int k, int layout, double *r, long long *n_sv, long long *n_free, hipStream_t st);
 // the host checks of k boxes (k x n, finite, >= 0) and masses (0 < mass <= sum of the box); full[c]: mass[c] is the whole box
 int bq_sx_check(int k, int64_t n, const double *UB, const double *mass, int *full);

@@ -17,17 +17,18 @@
 // tree of sx_block (a butterfly inside each wavefront, the 16 wavefronts in order), so a column's bits depend on its own
 // (x, g, s, u, r) alone: not on the batch, not on its slot.  A column is one workgroup; nothing waits on another workgroup.
 //
-// The two-group flavour (bq_sx2_col: the nu-SVC / nu-SVR duals, libsvm's solve_nu_svc / solve_nu_svr) is min 1/2 b'Kb + q'x with
-// b the signed, folded x, over the product of two capped simplices on disjoint groups of variables.  The projection onto a product
-// is the two projections taken independently: the search (sx_find_tau<2>) runs on one workgroup per (column, group), sx2_tau_kernel,
-// each leaving its tau in the column's state, and the column's direction pass, sx2_dir_kernel, follows.  top, the scalar step of
-// the close (sx_step_of, sx_commit) and the offsets' body (sx_offsets_of) are shared with the one-group column, whose
-// instantiations (GROUPS = 1) compile to what they were.
+// The two-group layouts (LABELS, PAIRED: the nu-SVC / nu-SVR duals, libsvm's solve_nu_svc / solve_nu_svr) are min 1/2 b'Kb + q'x
+// with b the signed, folded x, over the product of two capped simplices on disjoint groups of variables.  The projection onto a
+// product is the two projections taken independently: the search runs on one workgroup per (column, group), sx_tau_kernel, each
+// leaving its tau in the column's state, and the column's direction pass, sx_dir_kernel, follows.  Every kernel is one template over
+// the layout; ONE (one group, no labels, no linear term) is decided at compile time, so its instantiations hold none of the other
+// layouts' arithmetic (q + K b would turn a -0.0 of K b into +0.0) and search inside the direction pass, as one launch.
 #include "bq_common.h"
 #include "bq_scratch.h"
 #include "bq_simplex.h"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #pragma clang fp contract(off)   // x - s g, x + a d, the scalar recurrences: the roundings of the NumPy statements, no fused multiply-add
@@ -172,19 +173,15 @@ __device__ inline void sx_block_dd(double &h, double &l, double *lds) {
     l = sx_uniform(lds[2 * SX_WAVES + 1]);
 }
 
-// the box of row i as one group's search sees it.  GROUPS = 1: ub[i].  GROUPS = 2 with labels: ub[i] on the rows whose sign is the
-// group's (want), 0 on the others, which the search then passes over like any row without a box (a group that is an index range has
-// sgn null and its own pointers)
-template <int GROUPS>
+// the box of row i as one group's search sees it: ub[i], or with labels ub[i] on the rows whose sign is the group's (want) and 0 on
+// the others, which the search then passes over like any row without a box (sgn null: the group is an index range with its own
+// pointers; a null the caller writes as such is decided at compile time)
 __device__ inline double sx_box(const double *__restrict__ ub, const double *__restrict__ sgn, double want, long long i) {
-    if constexpr (GROUPS == 2) {
-        if (sgn != nullptr && sgn[i] != want) return 0.0;
-    }
+    if (sgn != nullptr && sgn[i] != want) return 0.0;
     return ub[i];
 }
 
 // tau of P(x - s g) onto {0 <= p <= ub, sum p = mass}; full: mass >= sum ub (P = ub).  Every thread returns the same value.
-template <int GROUPS>
 __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restrict__ x, const double *__restrict__ g, double s,
                                               const double *__restrict__ ub, const double *__restrict__ sgn, double want, double mass,
                                               int full, double *lds) {
@@ -193,7 +190,7 @@ __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restr
     {   // the bracket: phi(min (v - u)) = sum u >= mass > 0 = phi(max v)
         double m[2] = {-INFINITY, -INFINITY};
         for (long long i = tid; i < n; i += SX_T) {
-            const double u = sx_box<GROUPS>(ub, sgn, want, i);
+            const double u = sx_box(ub, sgn, want, i);
             if (u > 0.0) {
                 const double v = sx_v(x, g, s, i);
                 m[0] = fmax(m[0], v);
@@ -221,7 +218,7 @@ __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restr
         for (int j = 0; j <= SX_M; ++j) below[j] = upto[j] = 0;
 #pragma unroll 1
         for (long long i = tid; i < n; i += SX_T) {
-            const double u = sx_box<GROUPS>(ub, sgn, want, i);
+            const double u = sx_box(ub, sgn, want, i);
             if (!(u > 0.0)) continue;
             const double v = sx_v(x, g, s, i), b = v - u;
 #pragma unroll
@@ -261,7 +258,7 @@ __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restr
     double sh = 0.0, sl = 0.0;
     int cnt[1] = {0};
     for (long long i = tid; i < n; i += SX_T) {
-        const double u = sx_box<GROUPS>(ub, sgn, want, i);
+        const double u = sx_box(ub, sgn, want, i);
         if (!(u > 0.0)) continue;
         const double v = sx_v(x, g, s, i), b = v - u;
         if (v <= lo) continue;
@@ -285,42 +282,129 @@ __device__ __forceinline__ sx_tau sx_find_tau(long long n, const double *__restr
     return t;
 }
 
-// column blockIdx.x.  init: the start point, x = P(0) (the columns without an x0) and W[:, column] = x.  Else, for a live column:
-// d = P(x - s g) - x, W[:, pos[column]] = d, g'd and d'd to the state; g'd >= 0: 'optimal'
-__global__ __launch_bounds__(SX_T) void sx_project_kernel(const bq_sx_col *__restrict__ cols, const int *__restrict__ pos,
-                                                          double *__restrict__ W, int64_t ldw, int init) {
+// bq_simplex_project: P[:, column] = P(V[:, column]), the same search and the same clip
+__global__ __launch_bounds__(SX_T) void sx_project_only_kernel(long long n, const double *__restrict__ V, const double *__restrict__ UB,
+                                                               const double *__restrict__ mass, const int *__restrict__ full,
+                                                               double *__restrict__ P) {
+    __shared__ double lds[SX_LDS];
+    const double *v = V + (long long)blockIdx.x * n, *ub = UB + (long long)blockIdx.x * n;
+    double *p = P + (long long)blockIdx.x * n;
+    const sx_tau tau = sx_find_tau(n, v, nullptr, 0.0, ub, nullptr, 0.0, mass[blockIdx.x], full[blockIdx.x], lds);
+    for (long long i = threadIdx.x; i < n; i += SX_T) {
+        const double u = ub[i], vi = v[i];
+        p[i] = u > 0.0 ? sx_point(vi, vi - u, u, tau) : 0.0;
+    }
+}
+
+// group t of a column as the search and the offsets take it: an index range with its own pointers (ONE: the column; PAIRED: the rows
+// t n ... t n + n - 1; sgn null) or a predicate on the labels (LABELS: all n rows, the rows with sgn = +1 for t = 0, -1 for t = 1)
+struct sx_group {
+    long long off;
+    const double *sgn;
+    double want;
+};
+template <int L>
+__device__ inline sx_group sx_group_of(const bq_sx_col &c, int t) {
+    if constexpr (L == BQ_SX_LABELS) return sx_group{0, c.sgn, t == 0 ? 1.0 : -1.0};
+    else return sx_group{t * c.n, nullptr, 0.0};
+}
+template <int L>
+constexpr int SX_GROUPS = L == BQ_SX_ONE ? 1 : 2;
+
+// the variables of panel row i, fn(j, group, s_j v): the variable, its group and the panel's value v there under the variable's sign
+template <int L, class F>
+__device__ inline void sx_row(const bq_sx_col &c, long long i, double v, F &&fn) {
+    if constexpr (L == BQ_SX_PAIRED) {
+        fn(i, 0, v);
+        fn(c.n + i, 1, -v);
+    } else if constexpr (L == BQ_SX_LABELS) {
+        const double sg = c.sgn[i];
+        fn(i, sg > 0.0 ? 0 : 1, sg * v);
+    } else {
+        fn(i, 0, v);
+    }
+}
+
+// the search of a two-group projection: workgroup (column blockIdx.x, group blockIdx.y) leaves its group's tau in the column's
+// tau[4 t ...].  init: of P(0), for the columns without an x0; else of P(x - s g), for the live columns
+template <int L>
+__global__ __launch_bounds__(SX_T) void sx_tau_kernel(const bq_sx_col *__restrict__ cols, int init) {
+    static_assert(L != BQ_SX_ONE, "the one-group column searches inside sx_dir_kernel");
+    __shared__ double lds[SX_LDS];
+    const bq_sx_col c = cols[blockIdx.x];
+    const int t = blockIdx.y;
+    if (init ? c.has_x0 : c.sc->done) return;
+    const sx_group gr = sx_group_of<L>(c, t);
+    const double mass = t == 0 ? c.mass[0] : c.mass[1];   // (constant indices: the column stays in registers)
+    const int full = t == 0 ? c.full[0] : c.full[1];
+    const sx_tau tau = sx_find_tau(c.n, init ? nullptr : c.x + gr.off, init ? nullptr : c.g + gr.off, init ? 0.0 : c.st->s,
+                                   c.ub + gr.off, gr.sgn, gr.want, mass, full, lds);
+    if (threadIdx.x == 0) {
+        double *o = c.tau + 4 * t;
+        o[0] = tau.lo;
+        o[1] = tau.hi;
+        o[2] = tau.th;
+        o[3] = tau.tl;
+    }
+}
+
+__device__ inline sx_tau sx_load_tau(const double *tau, int t) {
+    return sx_tau{sx_uniform(tau[4 * t]), sx_uniform(tau[4 * t + 1]), sx_uniform(tau[4 * t + 2]), sx_uniform(tau[4 * t + 3])};
+}
+
+// the direction pass of column blockIdx.x (two groups: after sx_tau_kernel; ONE: the search first, here), thread i, i + 1024, ... on
+// panel row i (ONE: the variable i; LABELS: the variable i of the group its label names; PAIRED: the variables i of group 0 and n + i
+// of group 1).  init: x = P(0) per group (the columns without an x0) and W[:, column] = the signed, folded x.  Else, for a live
+// column: d = P(x - s g) - x with each variable's own group's tau, W[:, pos[column]] = d (ONE), sgn o d (LABELS) or d_i - d_{n + i}
+// (PAIRED), g'd and d'd over all m variables; g'd >= 0: 'optimal'
+template <int L>
+__global__ __launch_bounds__(SX_T) void sx_dir_kernel(const bq_sx_col *__restrict__ cols, const int *__restrict__ pos,
+                                                      double *__restrict__ W, int64_t ldw, int init) {
     __shared__ double lds[SX_LDS];
     const bq_sx_col c = cols[blockIdx.x];
     const long long n = c.n;
     const int tid = threadIdx.x;
-    if (init) {
-        double *w = W + (int64_t)blockIdx.x * ldw;
-        if (!c.has_x0) {
-            const sx_tau tau = sx_find_tau<1>(n, nullptr, nullptr, 0.0, c.ub, nullptr, 0.0, c.mass, c.full, lds);
-            for (long long i = tid; i < n; i += SX_T) {
-                const double u = c.ub[i];
-                c.x[i] = u > 0.0 ? sx_point(0.0, 0.0 - u, u, tau) : 0.0;
-            }
-        }
-        __syncthreads();
-        for (long long i = tid; i < n; i += SX_T) w[i] = c.x[i];
-        return;
+    if (!init && c.sc->done) return;
+    const bool fresh = init && !c.has_x0;   // x is written here
+    const double s = init ? 0.0 : c.st->s;
+    sx_tau tau[2] = {sx_tau{0.0, 0.0, 0.0, 0.0}, sx_tau{0.0, 0.0, 0.0, 0.0}};
+    if constexpr (L == BQ_SX_ONE) {
+        if (fresh) tau[0] = sx_find_tau(n, nullptr, nullptr, 0.0, c.ub, nullptr, 0.0, c.mass[0], c.full[0], lds);
+        else if (!init) tau[0] = sx_find_tau(n, c.x, c.g, s, c.ub, nullptr, 0.0, c.mass[0], c.full[0], lds);
+    } else if (!init || fresh) {
+        tau[0] = sx_load_tau(c.tau, 0);
+        tau[1] = sx_load_tau(c.tau, 1);
     }
-    if (c.sc->done) return;
-    const double s = c.st->s;
-    const sx_tau tau = sx_find_tau<1>(n, c.x, c.g, s, c.ub, nullptr, 0.0, c.mass, c.full, lds);
-    double *w = W + (int64_t)pos[blockIdx.x] * ldw;
+    double *w = W + (int64_t)(init ? (int)blockIdx.x : pos[blockIdx.x]) * ldw;
     double a[2] = {0.0, 0.0};
-    for (long long i = tid; i < n; i += SX_T) {
-        const double u = c.ub[i], xi = c.x[i], gi = c.g[i];
-        const double v = xi - s * gi;
-        const double p = u > 0.0 ? sx_point(v, v - u, u, tau) : 0.0;
-        const double d = p - xi;
-        c.d[i] = d;
-        w[i] = d;
-        a[0] += gi * d;
+    // the new value of variable j in group t: the start point, or the direction (its terms of g'd and d'd added)
+    auto variable = [&](long long j, int t) -> double {
+        const double u = c.ub[j];
+        if (init) {
+            if (fresh) c.x[j] = u > 0.0 ? sx_point(0.0, 0.0 - u, u, tau[t]) : 0.0;
+            return c.x[j];
+        }
+        const double xj = c.x[j], gj = c.g[j];
+        const double v = xj - s * gj;
+        const double p = u > 0.0 ? sx_point(v, v - u, u, tau[t]) : 0.0;
+        const double d = p - xj;
+        c.d[j] = d;
+        a[0] += gj * d;
         a[1] += d * d;
+        return d;
+    };
+    for (long long i = tid; i < n; i += SX_T) {
+        if constexpr (L == BQ_SX_PAIRED) {
+            const double lo = variable(i, 0), hi = variable(n + i, 1);
+            w[i] = lo - hi;
+        } else if constexpr (L == BQ_SX_LABELS) {
+            const double sg = c.sgn[i];
+            w[i] = sg * variable(i, sg > 0.0 ? 0 : 1);
+        } else {
+            w[i] = variable(i, 0);
+        }
     }
+    if (init) return;
     sx_block<SX_SUM>(a, lds);
     if (tid == 0) {
         c.st->gd = a[0];
@@ -332,29 +416,20 @@ __global__ __launch_bounds__(SX_T) void sx_project_kernel(const bq_sx_col *__res
     }
 }
 
-// bq_simplex_project: P[:, column] = P(V[:, column]), the same search and the same clip
-__global__ __launch_bounds__(SX_T) void sx_project_only_kernel(long long n, const double *__restrict__ V, const double *__restrict__ UB,
-                                                               const double *__restrict__ mass, const int *__restrict__ full,
-                                                               double *__restrict__ P) {
-    __shared__ double lds[SX_LDS];
-    const double *v = V + (long long)blockIdx.x * n, *ub = UB + (long long)blockIdx.x * n;
-    double *p = P + (long long)blockIdx.x * n;
-    const sx_tau tau = sx_find_tau<1>(n, v, nullptr, 0.0, ub, nullptr, 0.0, mass[blockIdx.x], full[blockIdx.x], lds);
-    for (long long i = threadIdx.x; i < n; i += SX_T) {
-        const double u = ub[i], vi = v[i];
-        p[i] = u > 0.0 ? sx_point(vi, vi - u, u, tau) : 0.0;
-    }
-}
-
-// max_{u > 0, x > 0} g - min_{u > 0, x < u} g of the elements this thread holds in m (m[0]: the max, m[1]: the max of -g)
-__device__ inline void sx_viol_add(double (&m)[2], double x, double g, double u) {
+// libsvm's measure, per group max_{u > 0, x > 0} g - min_{u > 0, x < u} g (a group with an empty side gives -inf) and the maximum
+// over the groups (Solver_NU).  m: per group the max of g over x > 0 and the max of -g over x < u, of the elements a thread holds
+template <int NM>
+__device__ inline void sx_viol_add(double (&m)[NM], int t, double x, double g, double u) {
     if (u > 0.0) {
-        if (x > 0.0) m[0] = fmax(m[0], g);
-        if (x < u) m[1] = fmax(m[1], -g);
+        if (x > 0.0) m[2 * t] = fmax(m[2 * t], g);
+        if (x < u) m[2 * t + 1] = fmax(m[2 * t + 1], -g);
     }
 }
-__device__ inline double sx_viol(const double (&m)[2]) {
-    return (m[0] > -INFINITY && m[1] > -INFINITY) ? m[0] + m[1] : -INFINITY;
+template <int NM>
+__device__ inline double sx_viol(const double (&m)[NM]) {
+    double v = (m[0] > -INFINITY && m[1] > -INFINITY) ? m[0] + m[1] : -INFINITY;
+    if constexpr (NM == 4) v = fmax(v, (m[2] > -INFINITY && m[3] > -INFINITY) ? m[2] + m[3] : -INFINITY);
+    return v;
 }
 
 // one thread: the state of a column at its start point: f, the violation, s = 1 and the window [f]
@@ -410,54 +485,71 @@ __device__ inline void sx_commit(bq_scal *sc, bq_sx_state &st, const sx_step &p,
     }
 }
 
-// after the start-up product, column blockIdx.x: g = K x, f = 1/2 x'g, the violation, s = 1 and the window [f]
+// after the start-up product (OUT[:, column] = K b, b the folded x), column blockIdx.x: g_j = q_j + s_j (K b)_{j mod n},
+// f = 1/2 x'(g - q) + q'x (ONE: g = K x, f = 1/2 x'g, nothing added), the violation, s = 1 and the window [f]
+template <int L>
 __global__ __launch_bounds__(SX_T) void sx_start_kernel(const bq_sx_col *__restrict__ cols, const double *__restrict__ out, int64_t ldw) {
     __shared__ double lds[SX_LDS];
     const bq_sx_col c = cols[blockIdx.x];
-    const double *q = out + (int64_t)blockIdx.x * ldw;
-    double a[1] = {0.0}, m[2] = {-INFINITY, -INFINITY};
-    for (long long i = threadIdx.x; i < c.n; i += SX_T) {
-        const double gi = q[i], xi = c.x[i];
-        c.g[i] = gi;
-        a[0] += xi * gi;
-        sx_viol_add(m, xi, gi, c.ub[i]);
-    }
+    const double *Kb = out + (int64_t)blockIdx.x * ldw;
+    double a[L == BQ_SX_ONE ? 1 : 2] = {}, m[2 * SX_GROUPS<L>];
+    for (double &v : m) v = -INFINITY;
+    for (long long i = threadIdx.x; i < c.n; i += SX_T)
+        sx_row<L>(c, i, Kb[i], [&](long long j, int t, double sKb) {
+            const double xj = c.x[j];
+            double gj = sKb;
+            if constexpr (L == BQ_SX_ONE) {
+                a[0] += xj * gj;
+            } else {
+                const double qj = c.q ? c.q[j] : 0.0;
+                gj = qj + sKb;
+                a[0] += xj * (gj - qj);
+                a[1] += qj * xj;
+            }
+            c.g[j] = gj;
+            sx_viol_add(m, t, xj, gj, c.ub[j]);
+        });
     sx_block<SX_SUM>(a, lds);
     sx_block<SX_MAX>(m, lds);
-    if (threadIdx.x == 0) sx_begin(c.sc, *c.st, 0.5 * a[0], sx_viol(m));
+    double f = 0.5 * a[0];
+    if constexpr (L != BQ_SX_ONE) f += a[1];
+    if (threadIdx.x == 0) sx_begin(c.sc, *c.st, f, sx_viol(m));
 }
 
-// the close of an iteration, live column blockIdx.x, Qd = OUT[:, pos[column]]: d'Qd; a = 1 if f + g'd + 1/2 d'Qd <= max(window)
-// + 1e-4 g'd, else the minimiser -g'd / d'Qd of the segment; f, x, g at the new point, the window, s = clamp(d'd / d'Qd) (1e10
-// where d'Qd <= 0), the violation there, iter + 1
+// the close of an iteration, live column blockIdx.x, Qd_j = s_j OUT[j mod n, pos[column]]: d'Qd over all m variables; a = 1 if
+// f + g'd + 1/2 d'Qd <= max(window) + 1e-4 g'd, else the minimiser -g'd / d'Qd of the segment; f, x, g at the new point, the window,
+// s = clamp(d'd / d'Qd) (1e10 where d'Qd <= 0), the violation there, iter + 1
+template <int L>
 __global__ __launch_bounds__(SX_T) void sx_close_kernel(const bq_sx_col *__restrict__ cols, const int *__restrict__ pos,
                                                         const double *__restrict__ out, int64_t ldw) {
     __shared__ double lds[SX_LDS];
     const bq_sx_col c = cols[blockIdx.x];
     if (c.sc->done) return;
-    const double *Qd = out + (int64_t)pos[blockIdx.x] * ldw;
+    const double *Kd = out + (int64_t)pos[blockIdx.x] * ldw;
     const int tid = threadIdx.x;
     double a[1] = {0.0};
-    for (long long i = tid; i < c.n; i += SX_T) a[0] += c.d[i] * Qd[i];
+    for (long long i = tid; i < c.n; i += SX_T)
+        sx_row<L>(c, i, Kd[i], [&](long long j, int, double Qd) { a[0] += c.d[j] * Qd; });
     sx_block<SX_SUM>(a, lds);
     const sx_step p = sx_step_of(c.sc, c.st, a[0]);
-    double m[2] = {-INFINITY, -INFINITY};
-    for (long long i = tid; i < c.n; i += SX_T) {
-        const double xi = c.x[i] + p.alpha * c.d[i], gi = c.g[i] + p.alpha * Qd[i];
-        c.x[i] = xi;
-        c.g[i] = gi;
-        sx_viol_add(m, xi, gi, c.ub[i]);
-    }
+    double m[2 * SX_GROUPS<L>];
+    for (double &v : m) v = -INFINITY;
+    for (long long i = tid; i < c.n; i += SX_T)
+        sx_row<L>(c, i, Kd[i], [&](long long j, int t, double Qd) {
+            const double xj = c.x[j] + p.alpha * c.d[j], gj = c.g[j] + p.alpha * Qd;
+            c.x[j] = xj;
+            c.g[j] = gj;
+            sx_viol_add(m, t, xj, gj, c.ub[j]);
+        });
     sx_block<SX_MAX>(m, lds);   // (its barriers: every thread has read the state before thread 0 writes it)
     if (tid == 0) sx_commit(c.sc, *c.st, p, sx_viol(m));
 }
 
 // the top of an iteration (one workgroup): thread c, c + 1024, ... writes the record of its live column (iter, f, violation, the
 // last step length, s) and takes the stop tests; then thread 0 numbers the live columns in column order (mlive_kernel)
-template <class COL>   // bq_sx_col or bq_sx2_col
-__global__ __launch_bounds__(SX_T) void sx_top_kernel(const COL *__restrict__ cols, int k, int *__restrict__ pos, int *__restrict__ nlive) {
+__global__ __launch_bounds__(SX_T) void sx_top_kernel(const bq_sx_col *__restrict__ cols, int k, int *__restrict__ pos, int *__restrict__ nlive) {
     for (int c = threadIdx.x; c < k; c += SX_T) {
-        const COL &col = cols[c];
+        const bq_sx_col &col = cols[c];
         bq_scal *sc = col.sc;
         if (sc->done) continue;
         const bq_sx_state &st = *col.st;
@@ -479,17 +571,16 @@ __global__ __launch_bounds__(SX_T) void sx_top_kernel(const COL *__restrict__ co
     *nlive = s;
 }
 
-// libsvm's calculate_rho over the rows with a box (sx_box: of one group where GROUPS = 2), exact comparisons: the support and free
+// libsvm's calculate_rho over the rows with a box (sx_box: of one group), exact comparisons: the support and free
 // counts, the largest g at the upper bound and the smallest at 0 by the tree; the free rows' sum of g in index order — the first
 // wavefront loads 64 rows at a time and adds the free ones among them one after another, lowest row first.  Thread 0 writes.
-template <int GROUPS>
 __device__ inline void sx_offsets_of(long long n, const double *__restrict__ xs, const double *__restrict__ gs,
                                      const double *__restrict__ ub, const double *__restrict__ sgn, double want, double *lds,
                                      double *__restrict__ rho, long long *__restrict__ n_sv, long long *__restrict__ n_free) {
     double m[2] = {-INFINITY, -INFINITY};   // m[0]: max g at x = u; m[1]: max -g at x = 0
     int cnt[2] = {0, 0};                    // rows with x > 0; rows with 0 < x < u
     for (long long i = threadIdx.x; i < n; i += SX_T) {
-        const double u = sx_box<GROUPS>(ub, sgn, want, i), x = xs[i], g = gs[i];
+        const double u = sx_box(ub, sgn, want, i), x = xs[i], g = gs[i];
         if (!(u > 0.0)) continue;
         cnt[0] += x > 0.0;
         cnt[1] += x > 0.0 && x < u;
@@ -507,7 +598,7 @@ __device__ inline void sx_offsets_of(long long n, const double *__restrict__ xs,
             bool fr = false;
             double gv = 0.0;
             if (i < n) {
-                const double u = sx_box<GROUPS>(ub, sgn, want, i), x = xs[i];
+                const double u = sx_box(ub, sgn, want, i), x = xs[i];
                 fr = u > 0.0 && x > 0.0 && x < u;
                 gv = gs[i];
             }
@@ -527,264 +618,43 @@ __device__ inline void sx_offsets_of(long long n, const double *__restrict__ xs,
     *n_free = cnt[1];
 }
 
-__global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__restrict__ cols, double *__restrict__ rho,
+// workgroup (column blockIdx.x, group blockIdx.y) -> r / n_sv / n_free[groups x column + group]
+template <int L>
+__global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__restrict__ cols, double *__restrict__ r,
                                                           long long *__restrict__ n_sv, long long *__restrict__ n_free) {
     __shared__ double lds[SX_LDS];
     const bq_sx_col c = cols[blockIdx.x];
-    sx_offsets_of<1>(c.n, c.x, c.g, c.ub, nullptr, 0.0, lds, rho + blockIdx.x, n_sv + blockIdx.x, n_free + blockIdx.x);
+    const sx_group gr = sx_group_of<L>(c, blockIdx.y);
+    const int o = SX_GROUPS<L> * blockIdx.x + blockIdx.y;
+    sx_offsets_of(c.n, c.x + gr.off, c.g + gr.off, c.ub + gr.off, gr.sgn, gr.want, lds, r + o, n_sv + o, n_free + o);
 }
 
-// ---- the two-group column (bq_sx2_col) ------------------------------------------------------------------------------------------
-// group t of a column as the search and the offsets take it: an index range with its own pointers (PAIRED: the rows t n ... t n + n - 1,
-// sgn null) or a predicate on the labels (LABELS: all n rows, the rows with sgn = +1 for t = 0, -1 for t = 1)
-struct sx_group {
-    long long off;
-    const double *sgn;
-    double want;
-};
-template <bool PAIRED>
-__device__ inline sx_group sx_group_of(const bq_sx2_col &c, int t) {
-    if constexpr (PAIRED) return sx_group{t * c.n, nullptr, 0.0};
-    else return sx_group{0, c.sgn, t == 0 ? 1.0 : -1.0};
+// fn(the layout as a constant): the instantiations of a launcher, chosen once
+template <class F>
+static void sx_with_layout(int layout, F &&fn) {
+    if (layout == BQ_SX_ONE) fn(std::integral_constant<int, BQ_SX_ONE>{});
+    else if (layout == BQ_SX_PAIRED) fn(std::integral_constant<int, BQ_SX_PAIRED>{});
+    else fn(std::integral_constant<int, BQ_SX_LABELS>{});
 }
 
-// the search of a projection: workgroup (column blockIdx.x, group blockIdx.y) leaves its group's tau in the column's tau[4 t ...].
-// init: of P(0), for the columns without an x0; else of P(x - s g), for the live columns
-template <bool PAIRED>
-__global__ __launch_bounds__(SX_T) void sx2_tau_kernel(const bq_sx2_col *__restrict__ cols, int init) {
-    __shared__ double lds[SX_LDS];
-    const bq_sx2_col c = cols[blockIdx.x];
-    const int t = blockIdx.y;
-    if (init ? c.has_x0 : c.sc->done) return;
-    const sx_group gr = sx_group_of<PAIRED>(c, t);
-    const double mass = t == 0 ? c.mass[0] : c.mass[1];   // (constant indices: the column stays in registers)
-    const int full = t == 0 ? c.full[0] : c.full[1];
-    const sx_tau tau = sx_find_tau<2>(c.n, init ? nullptr : c.x + gr.off, init ? nullptr : c.g + gr.off, init ? 0.0 : c.st->s,
-                                      c.ub + gr.off, gr.sgn, gr.want, mass, full, lds);
-    if (threadIdx.x == 0) {
-        double *o = c.tau + 4 * t;
-        o[0] = tau.lo;
-        o[1] = tau.hi;
-        o[2] = tau.th;
-        o[3] = tau.tl;
-    }
-}
-
-__device__ inline sx_tau sx2_load_tau(const double *tau, int t) {
-    return sx_tau{sx_uniform(tau[4 * t]), sx_uniform(tau[4 * t + 1]), sx_uniform(tau[4 * t + 2]), sx_uniform(tau[4 * t + 3])};
-}
-
-// the direction pass of column blockIdx.x after sx2_tau_kernel, thread i, i + 1024, ... on panel row i (LABELS: the variable i of the
-// group its label names; PAIRED: the variables i of group 0 and n + i of group 1).  init: x = P(0) per group (the columns without an
-// x0) and W[:, column] = the signed, folded x.  Else, for a live column: d = P(x - s g) - x with each variable's own group's tau,
-// W[:, pos[column]] = sgn o d (LABELS) or d_i - d_{n + i} (PAIRED), g'd and d'd over all m variables; g'd >= 0: 'optimal'
-template <bool PAIRED>
-__global__ __launch_bounds__(SX_T) void sx2_dir_kernel(const bq_sx2_col *__restrict__ cols, const int *__restrict__ pos,
-                                                       double *__restrict__ W, int64_t ldw, int init) {
-    __shared__ double lds[SX_LDS];
-    const bq_sx2_col c = cols[blockIdx.x];
-    const long long n = c.n;
-    const int tid = threadIdx.x;
-    if (!init && c.sc->done) return;
-    const bool fresh = init && !c.has_x0;   // x is written here
-    sx_tau tau[2] = {sx_tau{0.0, 0.0, 0.0, 0.0}, sx_tau{0.0, 0.0, 0.0, 0.0}};
-    if (!init || fresh) {
-        tau[0] = sx2_load_tau(c.tau, 0);
-        tau[1] = sx2_load_tau(c.tau, 1);
-    }
-    const double s = init ? 0.0 : c.st->s;
-    double *w = W + (int64_t)(init ? (int)blockIdx.x : pos[blockIdx.x]) * ldw;
-    double a[2] = {0.0, 0.0};
-    // the new value of variable j in group t: the start point, or the direction (its terms of g'd and d'd added)
-    auto variable = [&](long long j, int t) -> double {
-        const double u = c.ub[j];
-        if (init) {
-            if (fresh) c.x[j] = u > 0.0 ? sx_point(0.0, 0.0 - u, u, tau[t]) : 0.0;
-            return c.x[j];
-        }
-        const double xj = c.x[j], gj = c.g[j];
-        const double v = xj - s * gj;
-        const double p = u > 0.0 ? sx_point(v, v - u, u, tau[t]) : 0.0;
-        const double d = p - xj;
-        c.d[j] = d;
-        a[0] += gj * d;
-        a[1] += d * d;
-        return d;
-    };
-    for (long long i = tid; i < n; i += SX_T) {
-        if constexpr (PAIRED) {
-            const double lo = variable(i, 0), hi = variable(n + i, 1);
-            w[i] = lo - hi;
-        } else {
-            const double sg = c.sgn[i];
-            w[i] = sg * variable(i, sg > 0.0 ? 0 : 1);
-        }
-    }
-    if (init) return;
-    sx_block<SX_SUM>(a, lds);
-    if (tid == 0) {
-        c.st->gd = a[0];
-        c.st->dd = a[1];
-        if (a[0] >= 0.0) {
-            c.sc->status = BQ_STATUS_OPTIMAL;
-            c.sc->done = 1;
-        }
-    }
-}
-
-// libsvm's Solver_NU measure: the maximum over the two groups of the group's maximal-violating-pair value (m: group 0's max g over
-// x > 0 and max -g over x < u, then group 1's; a group with an empty side gives -inf)
-__device__ inline double sx2_viol(const double (&m)[4]) {
-    const double m0[2] = {m[0], m[1]}, m1[2] = {m[2], m[3]};
-    return fmax(sx_viol(m0), sx_viol(m1));
-}
-__device__ inline void sx2_viol_add(double (&m)[4], int t, double x, double g, double u) {
-    if (u > 0.0) {
-        if (x > 0.0) m[2 * t] = fmax(m[2 * t], g);
-        if (x < u) m[2 * t + 1] = fmax(m[2 * t + 1], -g);
-    }
-}
-
-// after the start-up product (OUT[:, column] = K b, b the folded x), column blockIdx.x: g_j = q_j + s_j (K b)_{j mod n},
-// f = 1/2 x'(g - q) + q'x, the violation, s = 1 and the window [f]
-template <bool PAIRED>
-__global__ __launch_bounds__(SX_T) void sx2_start_kernel(const bq_sx2_col *__restrict__ cols, const double *__restrict__ out, int64_t ldw) {
-    __shared__ double lds[SX_LDS];
-    const bq_sx2_col c = cols[blockIdx.x];
-    const double *Kb = out + (int64_t)blockIdx.x * ldw;
-    double a[2] = {0.0, 0.0}, m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    auto variable = [&](long long j, int t, double sKb) {
-        const double qj = c.q ? c.q[j] : 0.0, xj = c.x[j];
-        const double gj = qj + sKb;
-        c.g[j] = gj;
-        a[0] += xj * (gj - qj);
-        a[1] += qj * xj;
-        sx2_viol_add(m, t, xj, gj, c.ub[j]);
-    };
-    for (long long i = threadIdx.x; i < c.n; i += SX_T) {
-        const double kb = Kb[i];
-        if constexpr (PAIRED) {
-            variable(i, 0, kb);
-            variable(c.n + i, 1, -kb);
-        } else {
-            const double sg = c.sgn[i];
-            variable(i, sg > 0.0 ? 0 : 1, sg * kb);
-        }
-    }
-    sx_block<SX_SUM>(a, lds);
-    sx_block<SX_MAX>(m, lds);
-    if (threadIdx.x == 0) sx_begin(c.sc, *c.st, 0.5 * a[0] + a[1], sx2_viol(m));
-}
-
-// the close of an iteration, live column blockIdx.x, Qd_j = s_j OUT[j mod n, pos[column]]: d'Qd over all m variables, then
-// sx_close_kernel's step and state
-template <bool PAIRED>
-__global__ __launch_bounds__(SX_T) void sx2_close_kernel(const bq_sx2_col *__restrict__ cols, const int *__restrict__ pos,
-                                                         const double *__restrict__ out, int64_t ldw) {
-    __shared__ double lds[SX_LDS];
-    const bq_sx2_col c = cols[blockIdx.x];
-    if (c.sc->done) return;
-    const double *Kd = out + (int64_t)pos[blockIdx.x] * ldw;
-    const int tid = threadIdx.x;
-    const long long n = c.n;
-    double a[1] = {0.0};
-    for (long long i = tid; i < n; i += SX_T) {
-        const double kd = Kd[i];
-        if constexpr (PAIRED) {
-            a[0] += c.d[i] * kd;
-            a[0] += c.d[n + i] * -kd;
-        } else {
-            a[0] += c.d[i] * (c.sgn[i] * kd);
-        }
-    }
-    sx_block<SX_SUM>(a, lds);
-    const sx_step p = sx_step_of(c.sc, c.st, a[0]);
-    double m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    auto variable = [&](long long j, int t, double Qd) {
-        const double xj = c.x[j] + p.alpha * c.d[j], gj = c.g[j] + p.alpha * Qd;
-        c.x[j] = xj;
-        c.g[j] = gj;
-        sx2_viol_add(m, t, xj, gj, c.ub[j]);
-    };
-    for (long long i = tid; i < n; i += SX_T) {
-        const double kd = Kd[i];
-        if constexpr (PAIRED) {
-            variable(i, 0, kd);
-            variable(n + i, 1, -kd);
-        } else {
-            const double sg = c.sgn[i];
-            variable(i, sg > 0.0 ? 0 : 1, sg * kd);
-        }
-    }
-    sx_block<SX_MAX>(m, lds);   // (its barriers: every thread has read the state before thread 0 writes it)
-    if (tid == 0) sx_commit(c.sc, *c.st, p, sx2_viol(m));
-}
-
-// libsvm's Solver_NU::calculate_rho: workgroup (column blockIdx.x, group blockIdx.y) -> r / n_sv / n_free[2 column + group]
-template <bool PAIRED>
-__global__ __launch_bounds__(SX_T) void sx2_offsets_kernel(const bq_sx2_col *__restrict__ cols, double *__restrict__ r,
-                                                           long long *__restrict__ n_sv, long long *__restrict__ n_free) {
-    __shared__ double lds[SX_LDS];
-    const bq_sx2_col c = cols[blockIdx.x];
-    const sx_group gr = sx_group_of<PAIRED>(c, blockIdx.y);
-    const int o = 2 * blockIdx.x + blockIdx.y;
-    sx_offsets_of<2>(c.n, c.x + gr.off, c.g + gr.off, c.ub + gr.off, gr.sgn, gr.want, lds, r + o, n_sv + o, n_free + o);
-}
-
-int bq_sx2_launch_project(const bq_sx2_col *cols, int k, bool paired, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st) {
-    const int in = init ? 1 : 0;
-    if (paired) {
-        sx2_tau_kernel<true><<<dim3(k, 2), SX_T, 0, st>>>(cols, in);
-        sx2_dir_kernel<true><<<k, SX_T, 0, st>>>(cols, pos, W, ldw, in);
-    } else {
-        sx2_tau_kernel<false><<<dim3(k, 2), SX_T, 0, st>>>(cols, in);
-        sx2_dir_kernel<false><<<k, SX_T, 0, st>>>(cols, pos, W, ldw, in);
-    }
+int bq_sx_launch_project(const bq_sx_col *cols, int k, int layout, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st) {
+    sx_with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        if constexpr (L != BQ_SX_ONE) sx_tau_kernel<L><<<dim3(k, 2), SX_T, 0, st>>>(cols, init ? 1 : 0);
+        sx_dir_kernel<L><<<k, SX_T, 0, st>>>(cols, pos, W, ldw, init ? 1 : 0);
+    });
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
 
-int bq_sx2_launch_start(const bq_sx2_col *cols, int k, bool paired, const double *out, int64_t ldw, hipStream_t st) {
-    if (paired) sx2_start_kernel<true><<<k, SX_T, 0, st>>>(cols, out, ldw);
-    else sx2_start_kernel<false><<<k, SX_T, 0, st>>>(cols, out, ldw);
+int bq_sx_launch_start(const bq_sx_col *cols, int k, int layout, const double *out, int64_t ldw, hipStream_t st) {
+    sx_with_layout(layout, [&](auto l) { sx_start_kernel<decltype(l)::value><<<k, SX_T, 0, st>>>(cols, out, ldw); });
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
 
-int bq_sx2_launch_close(const bq_sx2_col *cols, int k, bool paired, const int *pos, const double *out, int64_t ldw, hipStream_t st) {
-    if (paired) sx2_close_kernel<true><<<k, SX_T, 0, st>>>(cols, pos, out, ldw);
-    else sx2_close_kernel<false><<<k, SX_T, 0, st>>>(cols, pos, out, ldw);
-    BQ_HIP(hipGetLastError());
-    return BQ_OK;
-}
-
-int bq_sx2_launch_top(const bq_sx2_col *cols, int k, int *pos, int *nlive, hipStream_t st) {
-    sx_top_kernel<<<1, SX_T, 0, st>>>(cols, k, pos, nlive);
-    BQ_HIP(hipGetLastError());
-    return BQ_OK;
-}
-
-int bq_sx2_launch_offsets(const bq_sx2_col *cols, int k, bool paired, double *r, long long *n_sv, long long *n_free, hipStream_t st) {
-    if (paired) sx2_offsets_kernel<true><<<dim3(k, 2), SX_T, 0, st>>>(cols, r, n_sv, n_free);
-    else sx2_offsets_kernel<false><<<dim3(k, 2), SX_T, 0, st>>>(cols, r, n_sv, n_free);
-    BQ_HIP(hipGetLastError());
-    return BQ_OK;
-}
-
-int bq_sx_launch_project(const bq_sx_col *cols, int k, const int *pos, double *W, int64_t ldw, bool init, hipStream_t st) {
-    sx_project_kernel<<<k, SX_T, 0, st>>>(cols, pos, W, ldw, init ? 1 : 0);
-    BQ_HIP(hipGetLastError());
-    return BQ_OK;
-}
-
-int bq_sx_launch_start(const bq_sx_col *cols, int k, const double *out, int64_t ldw, hipStream_t st) {
-    sx_start_kernel<<<k, SX_T, 0, st>>>(cols, out, ldw);
-    BQ_HIP(hipGetLastError());
-    return BQ_OK;
-}
-
-int bq_sx_launch_close(const bq_sx_col *cols, int k, const int *pos, const double *out, int64_t ldw, hipStream_t st) {
-    sx_close_kernel<<<k, SX_T, 0, st>>>(cols, pos, out, ldw);
+int bq_sx_launch_close(const bq_sx_col *cols, int k, int layout, const int *pos, const double *out, int64_t ldw, hipStream_t st) {
+    sx_with_layout(layout, [&](auto l) { sx_close_kernel<decltype(l)::value><<<k, SX_T, 0, st>>>(cols, pos, out, ldw); });
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
@@ -795,8 +665,11 @@ int bq_sx_launch_top(const bq_sx_col *cols, int k, int *pos, int *nlive, hipStre
     return BQ_OK;
 }
 
-int bq_sx_launch_offsets(const bq_sx_col *cols, int k, double *rho, long long *n_sv, long long *n_free, hipStream_t st) {
-    sx_offsets_kernel<<<k, SX_T, 0, st>>>(cols, rho, n_sv, n_free);
+int bq_sx_launch_offsets(const bq_sx_col *cols, int k, int layout, double *r, long long *n_sv, long long *n_free, hipStream_t st) {
+    sx_with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        sx_offsets_kernel<L><<<dim3(k, SX_GROUPS<L>), SX_T, 0, st>>>(cols, r, n_sv, n_free);
+    });
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }

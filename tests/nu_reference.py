@@ -10,7 +10,7 @@ independently.
   LABELS (nu-SVC, libsvm solve_nu_svc): m = n, s = the labels, group 0 the rows with s = +1, u = 1, mass = nu n / 2, q = 0
   PAIRED (nu-SVR, libsvm solve_nu_svr): m = 2n, s = (+1, -1), group 0 the first n, u = C, mass = C nu n / 2, q = (-y, +y)
 
-The device code (csrc/bq_simplex.hip: the sx2_* kernels) follows these statements; the tests hold it against this file.
+The device code (csrc/bq_simplex.hip: the LABELS and PAIRED instantiations of the sx_* kernels) follows these statements; the tests hold it against this file.
 """
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""NuSVC and NuSVR on the device: the two-group simplex solver (bq_msolver_create_simplex2: sx_top / sx2_tau / sx2_dir / sx2_close
+"""NuSVC and NuSVR on the device: the two-group simplex solver (bq_msolver_create_simplex2: sx_top / sx_tau / sx_dir / sx_close
 around the 16-column panel product) against the NumPy reference (tests/nu_reference.py), the group handling at its edges, one box
 per column, the estimators against sklearn, the paths, the refusals and fp32 panels."""
 import functools

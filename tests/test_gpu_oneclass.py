@@ -1,5 +1,5 @@
 """OneClassSVM on the device: the capped-simplex projection kernel alone (bq_simplex_project), the batched nu-one-class solver
-(bq_msolver_create_simplex: sx_top / sx_project / sx_close around the 16-column panel product) against the NumPy reference
+(bq_msolver_create_simplex: sx_top / sx_dir / sx_close around the 16-column panel product) against the NumPy reference
 (tests/oneclass_reference.py), the estimator against sklearn, one box per column, and the nu path."""
 import functools
 
@@ -304,6 +304,18 @@ def test_start_point_and_bad_columns(amd):
     for UB, mass, x0 in ((u, [n + 1.0], None), (u, [0.0], None), (-u, [1.0], None), (u, [10.0], 2 * u), (u, [10.0], u * 0.5)):
         with pytest.raises(_lib.BcqpError):
             _DeviceSimplexSolver(dev, UB, mass, 1e-3, 10, x0)
+    # the start point is the solver's x before any run; after one the direction is served and other vectors are refused
+    x0 = np.stack([a['x'], np.full(n, 0.3)])
+    s = _DeviceSimplexSolver(dev, np.ones((2, n)), [a['x'].sum(), 0.3 * n], 1e-6, 50, x0)
+    for c in range(2):
+        assert np.array_equal(s.get(c, _lib.GET_X_NOW), x0[c])
+    s.run(5)
+    for c in range(2):
+        d = s.get(c, _lib.GET_D)
+        assert d.shape == (n,) and np.isfinite(d).all()
+        with pytest.raises(_lib.BcqpError, match='vector not available'):
+            s.get(c, _lib.GET_LP)
+    s.close()
     quad.release()
     svc = KernelQuadratic(X, -np.ones(n), 'svc', GaussianKernel(gamma=1.0), y=np.where(np.arange(n) % 2, 1., -1.))
     with pytest.raises(_lib.BcqpError):

@@ -7,8 +7,8 @@ iter      n = 100 000, d = 128, RBF (gamma = 1 / d), fp64 panel built once, 16 c
           three figures, their median and their spread (max - min); the one-class figure is the yardstick, and its spread over the
           three repeats the run-to-run spread the comparison is read against.
 oneclass | labels | paired   one such solve alone, for `rocprofv3 --kernel-trace --stats` (a run of its own): the trace splits the
-          iteration into the product (symmw_tiles_kernel + symmw_reduce_kernel), the projection (sx_project_kernel, or sx2_tau_kernel
-          + sx2_dir_kernel) and the closing (sx_close_kernel / sx2_close_kernel + sx_top_kernel).
+          iteration into the product (symmw_tiles_kernel + symmw_reduce_kernel), the projection (sx_dir_kernel, after sx_tau_kernel for
+          the two-group layouts) and the closing (sx_close_kernel + sx_top_kernel).
 One JSON line."""
 import json
 import os

@@ -5,7 +5,7 @@ iter     n = 100 000, d = 128, RBF (gamma = 1 / d), fp64 panel, 16 columns (a nu
          timed by the host clock around bq_msolver_run — not by device events: the library hands out none,
          and the run ends in a synchronising copy, so the figure includes the lagged polls and the final state copies.  Under
          `rocprofv3 --kernel-trace --stats` (a run of its own: the device-side figure) the trace splits the iteration into the product
-         (symmw_tiles_kernel + symmw_reduce_kernel), the projection (sx_project_kernel) and the closing (sx_close_kernel + sx_top_kernel).
+         (symmw_tiles_kernel + symmw_reduce_kernel), the projection (sx_dir_kernel) and the closing (sx_close_kernel + sx_top_kernel).
 fit      OneClassSVM(nu = 0.2, tol = 1e-3).fit wall time on the same data, panel build included, after a small warm-up fit.
 sklearn  sklearn.svm.OneClassSVM(nu = 0.2, tol = 1e-3).fit on the CPU at n = 20 000 by default (a size it finishes), the same d.
 One JSON line each."""

@@ -7,7 +7,8 @@ offsets.  Two builds of the library that print the same file compute the same bi
 
 n = 300 (two 256-row tiles, the second ragged); k = 5 on the 4-column product and k = 17 on the 16-column one (a full chunk and a
 ragged one); three classes of unequal sizes for the pairs (the class-sorted panel has ghost rows); two calibrators over disjoint
-held-out folds; the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
+held-out folds; the simplex solver in its three layouts (one group; labels with a start point; paired with a linear term), all with
+zero-width rows; the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
 iteration counts), so pos[] renumbers.
 """
 import hashlib
@@ -25,7 +26,7 @@ if len(sys.argv) > 1:
     _lib.LIB_PATH = os.path.abspath(sys.argv[1])   # as tools/bench_with_lib.py
 
 from optiml_amd.ml.svm import MultiOutputSVR, OneVsRestSVC, multiclass, multioutput  # noqa: E402
-from optiml_amd.ml.svm._batched import _DeviceMultiSolver, _DeviceSimplexSolver, _DeviceSVRSolver  # noqa: E402
+from optiml_amd.ml.svm._batched import _DeviceMultiSolver, _DeviceSimplex2Solver, _DeviceSimplexSolver, _DeviceSVRSolver  # noqa: E402
 from optiml_amd.ml.svm.coupling import chunk_calibrators, coupling_columns  # noqa: E402
 from optiml_amd.ml.svm.kernels import GaussianKernel  # noqa: E402
 from optiml_amd.ml.svm.losses import epsilon_insensitive, hinge  # noqa: E402
@@ -180,6 +181,37 @@ def simplex():
     obj.release()
 
 
+def simplex2(paired):
+    """the two-group solver at simplex()'s shapes: LABELS with a start point (a vertex of every group's set), PAIRED from P(0) with
+    a linear term; both with the fold boxes (zero-width rows) and NuSVC's own bound on the masses, nu min(n0, n1)"""
+    rs, X = data(11)
+    S = labels(rs, X, 17)
+    t = np.sin(X @ rs.standard_normal(D)) + 0.1 * rs.standard_normal(N)
+    nus = np.linspace(0.05, 0.85, 17)
+    UB, _ = folds(17, 2, C=1.0)
+    groups = [[np.flatnonzero((UB[c] > 0) & (S[c] == sg)) for sg in (1.0, -1.0)] for c in range(17)]
+    mass = np.array([[nus[c] * min(len(g) for g in groups[c])] * 2 for c in range(17)])
+    obj = KernelQuadratic(X, np.zeros(N), 'plain', KERNEL)
+    if paired:
+        name = 'simplex2_paired_k17'
+        s = _DeviceSimplex2Solver(obj.device_problem(), None, np.concatenate([UB, UB], axis=1), mass,
+                                  np.tile(np.concatenate((-t, t)), (17, 1)), 1e-4, 400)
+    else:
+        name = 'simplex2_labels_k17'
+        x0 = np.zeros((17, N))
+        for c in range(17):
+            for g, rows in enumerate(groups[c]):   # ones on the group's first rows, the remainder on the next
+                whole = int(mass[c, g])
+                x0[c, rows[:whole]] = 1.0
+                x0[c, rows[whole]] = mass[c, g] - whole
+        s = _DeviceSimplex2Solver(obj.device_problem(), S, UB, mass, None, 1e-4, 400, x0=x0)
+    run_to_end(s, name)
+    r1, r2, n_sv, n_free = s.offsets()
+    show(name + '.offsets', r1=r1, r2=r2, n_sv=n_sv, n_free=n_free)
+    s.close()
+    obj.release()
+
+
 def lagrangian():
     """the augmented-Lagrangian batch through its estimators (the rule's parameters are theirs to build): what
     solve_batched_al hands back for every column"""
@@ -216,4 +248,6 @@ if __name__ == '__main__':
     svr(5, False)
     svr(17, True)
     simplex()
+    simplex2(False)
+    simplex2(True)
     lagrangian()
