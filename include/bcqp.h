@@ -59,6 +59,7 @@ extern "C" {
 /* (still 3: bq_msolver_pairs_heldout, bq_pairwise_coupling and bq_decision_coupled were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_simplex, bq_msolver_simplex_offsets and bq_simplex_project were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_simplex2 and bq_msolver_simplex2_offsets were added; nothing existing changed) */
+/* (still 3: bq_msolver_create_simplex2_pairs was added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -466,6 +467,22 @@ enum { BQ_SX_LABELS = 0, BQ_SX_PAIRED = 1 };
 int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, const double *S, const double *UB, const double *mass,
                                const double *q, const double *x0, double tol, int64_t max_iter, bq_msolver **out);
 int bq_msolver_simplex2_offsets(bq_msolver *s, double *r1, double *r2, int64_t *n_sv, int64_t *n_free);
+/* The two-group columns of one-vs-one nu-SVC on a class-sorted panel (sklearn OneVsOneClassifier(NuSVC): NuSVC.fit on the rows of
+ * classes a and b, once per pair and nu), with the pair-routed product of bq_msolver_create_pairs.  cls_tiles, pairs: as
+ * bq_problem_gram_matmat_pairs; the same pair may appear in several columns (one per nu).  Column c of pair (a, b), a < b, has m = n
+ * variables in panel order; group 0 is the row range of class b with s = +1 (OneVsOneClassifier makes the larger label positive),
+ * group 1 the row range of class a with s = -1; there is no S and no linear term.  UB: m x n, >= 0 on the rows of the pair's classes
+ * and exactly 0 on every other row (a class's ghost rows and held-out rows have UB = 0 too); mass: m x 2, one per group, as
+ * bq_msolver_create_simplex2; x0: m x n inside its set, or NULL.  nu-SVC of pair (a, b): UB = 1 on the pair's data rows,
+ * mass = nu (n_a + n_b) / 2 twice.  The iteration, the stop test and the records are bq_msolver_create_simplex2's; every pass takes
+ * the routed product, which streams the panel at most once for all live columns and reads and writes a column on its pair's rows
+ * only, and a column's own kernels walk the rows of its two classes only: x, d and g stay exactly 0 on every other row.  Column c's
+ * iterates and records have the same bits alone, at any position and in any batch.  A NULL argument or m < 1 (checked first), a
+ * problem other than bq_msolver_create_simplex's, bad cls_tiles or pairs, a group without a row of positive box, a mass above its
+ * group's box or an x0 outside its set: BQ_ERR_BADARG.  run / state / get / destroy: as bq_msolver_create (cls = the column; get
+ * hands out n entries); bq_msolver_simplex2_offsets takes the solver as it takes bq_msolver_create_simplex2's. */
+int bq_msolver_create_simplex2_pairs(bq_problem *p, int ncls, const int *cls_tiles, int m, const int *pairs, const double *UB,
+                                     const double *mass, const double *x0, double tol, int64_t max_iter, bq_msolver **out);
 
 /* ---- Platt calibration (sklearn CalibratedClassifierCV(method='sigmoid'): calibration.py _sigmoid_calibration, once per (fold,
  * class)) -----------------------------------------------------------------------------------------------------------------------

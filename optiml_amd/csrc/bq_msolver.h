@@ -20,6 +20,7 @@ struct bq_al_col {
 //   _create_pairs                   PGFW     PAIRS    boxes
 //   _create_al                      AL       SYMM4
 //   _create_simplex, _simplex2      SIMPLEX  SYMM16   sx_layout: ONE; LABELS or PAIRED
+//   _create_simplex2_pairs          SIMPLEX  PAIRS    sx_layout: BLOCKS
 enum bq_mmethod {
     BQ_M_PGFW,      // ProjectedGradient / FrankWolfe columns (bq_msolver::kind says which)
     BQ_M_AL,        // augmented-Lagrangian columns (bq_al.hip); epi: k entries of kind 2
@@ -64,6 +65,7 @@ struct bq_msolver {
     long long *sx_counts = nullptr;
     std::vector<double> sx_mass;
     std::vector<int> sx_full;
+    std::vector<long long> sx_ranges;   // BLOCKS: k x 4, the row offset and length of group 0 (class b), then of group 1 (class a)
     int64_t sx_m = 0;
     int sx_layout = BQ_SX_ONE;
     bool sx_has_x0 = false;

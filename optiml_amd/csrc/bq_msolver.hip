@@ -53,6 +53,12 @@
 // so a run of max_steps iterations writes at most max_steps records per column, and a column's state after its last close waits
 // for the next run's top.
 //
+// bq_msolver_create_simplex2_pairs is the two-group simplex batch on a class-sorted panel with the routed product: column c belongs
+// to pair (a, b) and its groups are the row ranges of the two classes (layout BLOCKS: class b +1, class a -1, no labels vector, no
+// linear term), so the nu-SVC duals of every class pair, at any number of nu, share one panel stream per iteration and a column's
+// kernels walk its two classes' rows only.  pos[] stays the identity (the routed product indexes W and OUT by column): the top kernel
+// takes the records and the stop tests, and the plan's live kernel follows it, before the projection.
+//
 // The object and what the scoring file shares with this one are in bq_msolver.h; what scores a finished batch (held-out scoring and
 // calibration, the simplex offsets) is bq_mscore.hip.
 #include "bq_al_update.h"
@@ -246,10 +252,12 @@ static int upload_epi(bq_msolver *m) {
                 const int64_t n = m->p->n, mm = m->sx_m;
                 const int t0 = m->sx_layout == BQ_SX_ONE ? c : 2 * c, t1 = m->sx_layout == BQ_SX_ONE ? c : 2 * c + 1;   // its groups
                 double *v = m->sx_vec + 4 * mm * c;
+                const long long *rg = m->sx_ranges.empty() ? nullptr : m->sx_ranges.data() + 4 * c;   // BLOCKS: off, len per group
                 sx[c] = bq_sx_col{(long long)n, (long long)mm, v, v + mm, v + 2 * mm, v + 3 * mm,
                                   m->sx_sgn ? m->sx_sgn + n * c : nullptr, m->sx_q ? m->sx_q + mm * c : nullptr,
                                   {m->sx_mass[t0], m->sx_mass[t1]}, {m->sx_full[t0], m->sx_full[t1]},
-                                  m->sx_has_x0 ? 1 : 0, m->sx_tau ? m->sx_tau + 8 * c : nullptr, s->sc, m->sx_state + c, s->stats};
+                                  m->sx_has_x0 ? 1 : 0, m->sx_tau ? m->sx_tau + 8 * c : nullptr,
+                                  {rg ? rg[0] : 0, rg ? rg[2] : 0}, {rg ? rg[1] : 0, rg ? rg[3] : 0}, s->sc, m->sx_state + c, s->stats};
             }
             BQ_HIP(hipMemcpyAsync(m->sx_cols, sx.data(), sizeof(bq_sx_col) * k, hipMemcpyHostToDevice, st));
             break;
@@ -535,14 +543,25 @@ extern "C" int bq_msolver_create_al(bq_problem *p, const bq_al_params *prm, int 
     return BQ_OK;
 }
 
-// the simplex batch of any layout.  GU: the boxes of the groups (ONE: the k columns; else 2 k) as one-group columns of n rows, a row
-// outside its group having none; mass: one per group; UB (k x m), sgn (LABELS: k x n, else null), q (k x m or null), x0 (k x m or
-// null): the columns' vectors as the device takes them
-static int msolver_create_sx(bq_problem *p, int k, int layout, const double *GU, const double *UB, const double *sgn,
-                             const double *mass, const double *q, const double *x0, double tol, int64_t max_iter, bq_msolver **out) {
+// the problem a simplex batch takes
+static int sx_check_problem(bq_problem *p) {
     BQ_ARG(p->structure == BQ_PLAIN && p->kernel >= 0, "the simplex solver takes a kernel-built BQ_PLAIN problem");
     BQ_ARG(p->diag_add == 0.0, "the simplex solver takes a problem without a diagonal term");
-    BQ_TRY(bq_need_resident_panel(p, "the batched solver", " (not streamed, not full rows)"));
+    return bq_need_resident_panel(p, "the batched solver", " (not streamed, not full rows)");
+}
+// the classes and pairs of the routed product (BLOCKS), checked by the caller
+struct sx_routed {
+    int ncls;
+    const int *cls_tiles, *pairs;
+};
+// the simplex batch of any layout.  GU: the boxes of the groups (ONE: the k columns; else 2 k) as one-group columns of n rows, a row
+// outside its group having none; mass: one per group; UB (k x m), sgn (LABELS: k x n, else null), q (k x m or null), x0 (k x m or
+// null): the columns' vectors as the device takes them.  BLOCKS: rt, the routed product's classes and pairs (checked by the caller),
+// and ranges, k x 4: the row offset and length of group 0, then of group 1
+static int msolver_create_sx(bq_problem *p, int k, int layout, const double *GU, const double *UB, const double *sgn,
+                             const double *mass, const double *q, const double *x0, double tol, int64_t max_iter, bq_msolver **out,
+                             const sx_routed *rt = nullptr, const long long *ranges = nullptr) {
+    BQ_TRY(sx_check_problem(p));
     BQ_ARG(tol >= 0.0, "tol must be >= 0");
     const bool one = layout == BQ_SX_ONE;
     const int groups = one ? k : 2 * k;
@@ -553,7 +572,7 @@ static int msolver_create_sx(bq_problem *p, int k, int layout, const double *GU,
     if (x0) {   // inside its set: the box exactly, each group's mass to the rounding of a sum of n terms
         for (int64_t j = 0; j < (int64_t)k * mm; ++j) BQ_ARG(x0[j] >= 0.0 && x0[j] <= UB[j], "x0 must lie in its box");
         for (int g = 0; g < groups; ++g) {
-            const double *x = x0 + (layout == BQ_SX_LABELS ? g / 2 : g) * n;   // the n variables that hold group g
+            const double *x = x0 + (layout == BQ_SX_LABELS || layout == BQ_SX_BLOCKS ? g / 2 : g) * n;   // the n variables that hold group g
             long double sum = 0.0L;
             for (int64_t i = 0; i < n; ++i)
                 if (GU[(int64_t)g * n + i] > 0.0) sum += x[i];
@@ -570,14 +589,15 @@ static int msolver_create_sx(bq_problem *p, int k, int layout, const double *GU,
     m->k = k;
     m->ldw = p->ld;
     m->method = BQ_M_SIMPLEX;
-    m->product = BQ_MP_SYMM16;
+    m->product = rt ? BQ_MP_PAIRS : BQ_MP_SYMM16;
+    if (ranges) m->sx_ranges.assign(ranges, ranges + 4 * (size_t)k);
     m->sx_has_x0 = x0 != nullptr;
     m->sx_mass.assign(mass, mass + groups);
     m->sx_full = full;
     m->sx_m = mm;
     m->sx_layout = layout;
     const std::vector<double> zero((size_t)n, 0.0);
-    int rc = BQ_OK;
+    int rc = rt ? bq_pairs_plan_create(p, rt->ncls, rt->cls_tiles, k, rt->pairs, &m->plan) : BQ_OK;
     for (int cl = 0; cl < k && rc == BQ_OK; ++cl) {
         bq_solver *s = nullptr;   // the column's scalars (eps = tol) and records; its vectors are sx_vec
         rc = bq_solver_create(p, BQ_PG, nullptr, zero.data(), zero.data(), tol, max_iter, 0.0, &s);
@@ -662,6 +682,40 @@ extern "C" int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, cons
     return msolver_create_sx(p, k, layout, GU, UB, paired ? nullptr : sgn.data(), mass, q, x0, tol, max_iter, out);
 }
 
+extern "C" int bq_msolver_create_simplex2_pairs(bq_problem *p, int ncls, const int *cls_tiles, int m, const int *pairs, const double *UB,
+                                                const double *mass, const double *x0, double tol, int64_t max_iter, bq_msolver **out) {
+    BQ_ARG(p && cls_tiles && pairs && UB && mass && out, "NULL argument");
+    BQ_ARG(m >= 1, "m must be >= 1");
+    BQ_TRY(sx_check_problem(p));
+    int64_t slab_bytes = 0;
+    BQ_TRY(bq_pairs_slab_bytes(p->nb, ncls, cls_tiles, m, pairs, &slab_bytes));   // validates cls_tiles and pairs
+    const int64_t n = p->n;
+    // the boxes of the 2 m groups as one-group columns of n rows (class b's rows, then class a's), and the groups' row ranges
+    std::vector<double> grouped((size_t)(2 * m) * (size_t)n, 0.0);
+    std::vector<long long> ranges(4 * (size_t)m);
+    for (int c = 0; c < m; ++c) {
+        long long *rg = ranges.data() + 4 * c;
+        for (int t = 0; t < 2; ++t) {   // group 0: the larger class, +1
+            const int cls = pairs[2 * c + (t == 0 ? 1 : 0)];
+            rg[2 * t] = (long long)cls_tiles[cls] * BQ_SYM_TILE;
+            rg[2 * t + 1] = std::min<long long>((long long)cls_tiles[cls + 1] * BQ_SYM_TILE, n) - rg[2 * t];
+        }
+        for (int64_t i = 0; i < n; ++i) {
+            const double u = UB[(int64_t)c * n + i];
+            const int t = (i >= rg[0] && i < rg[0] + rg[1]) ? 0 : (i >= rg[2] && i < rg[2] + rg[3]) ? 1 : -1;
+            BQ_ARG(u >= 0.0 && (t >= 0 || u == 0.0), "upper bounds must be >= 0 on the pair's rows and 0 on every other row");
+            if (t >= 0) grouped[(size_t)(2 * c + t) * n + i] = u;
+        }
+    }
+    for (int g = 0; g < 2 * m; ++g) {
+        bool any = false;
+        for (int64_t i = 0; i < n && !any; ++i) any = grouped[(int64_t)g * n + i] > 0.0;
+        BQ_ARG(any, "each of a column's two groups needs a row with UB > 0");
+    }
+    const sx_routed rt{ncls, cls_tiles, pairs};
+    return msolver_create_sx(p, m, BQ_SX_BLOCKS, grouped.data(), UB, nullptr, mass, nullptr, x0, tol, max_iter, out, &rt, ranges.data());
+}
+
 static int msolver_first(bq_msolver *m) {
     bq_problem *p = m->p;
     hipStream_t st = p->ctx->stream;
@@ -708,7 +762,12 @@ static int msolver_iterate(bq_msolver *m, bool first_of_run) {
     hipStream_t st = p->ctx->stream;
     switch (m->method) {
         case BQ_M_SIMPLEX:
-            BQ_TRY(bq_sx_launch_top(m->sx_cols, m->k, m->pos, m->nlive, st));
+            if (m->product == BQ_MP_PAIRS) {   // pos[] stays the identity; the plan's live pairs, class slots and *nlive
+                BQ_TRY(bq_sx_launch_top(m->sx_cols, m->k, nullptr, m->nlive, st));
+                BQ_TRY(bq_launch_pairs_live(m->plan, m->scs, m->nlive, st));
+            } else {
+                BQ_TRY(bq_sx_launch_top(m->sx_cols, m->k, m->pos, m->nlive, st));
+            }
             BQ_TRY(bq_sx_launch_project(m->sx_cols, m->k, m->sx_layout, m->pos, m->W, m->ldw, false, st));
             BQ_TRY(msolver_product(m, m->live_host));
             return bq_sx_launch_close(m->sx_cols, m->k, m->sx_layout, m->pos, m->out, m->ldw, st);

@@ -23,6 +23,12 @@
 // leaving its tau in the column's state, and the column's direction pass, sx_dir_kernel, follows.  Every kernel is one template over
 // the layout; ONE (one group, no labels, no linear term) is decided at compile time, so its instantiations hold none of the other
 // layouts' arithmetic (q + K b would turn a -0.0 of K b into +0.0) and search inside the direction pass, as one launch.
+//
+// BLOCKS is the two-group column of a class pair (a, b), a < b, on a class-sorted panel (bq_symmp.hip: class c is the rows
+// [256 ct[c], 256 ct[c + 1])), the nu-SVC dual of one-vs-one classification: group 0 is class b's row range with sign +1, group 1
+// class a's with sign -1, with no labels vector and no linear term.  The search and the offsets run on a group's own range (no
+// predicate), the other passes walk the concatenation of the two ranges, class a's rows first, and no row outside them is read or
+// written: the routed product (bq_launch_symmp) reads W and writes OUT on the pair's rows only, by column, so pos[] is the identity.
 #include "bq_common.h"
 #include "bq_scratch.h"
 #include "bq_simplex.h"
@@ -298,18 +304,36 @@ __global__ __launch_bounds__(SX_T) void sx_project_only_kernel(long long n, cons
 
 // group t of a column as the search and the offsets take it: an index range with its own pointers (ONE: the column; PAIRED: the rows
 // t n ... t n + n - 1; sgn null) or a predicate on the labels (LABELS: all n rows, the rows with sgn = +1 for t = 0, -1 for t = 1)
+// (BLOCKS: the group's own row range of the class-sorted panel, len rows of it: no predicate, and no row of another class is read)
 struct sx_group {
     long long off;
     const double *sgn;
     double want;
+    long long len;
 };
 template <int L>
 __device__ inline sx_group sx_group_of(const bq_sx_col &c, int t) {
-    if constexpr (L == BQ_SX_LABELS) return sx_group{0, c.sgn, t == 0 ? 1.0 : -1.0};
-    else return sx_group{t * c.n, nullptr, 0.0};
+    if constexpr (L == BQ_SX_LABELS) return sx_group{0, c.sgn, t == 0 ? 1.0 : -1.0, c.n};
+    else if constexpr (L == BQ_SX_BLOCKS) return sx_group{t == 0 ? c.goff[0] : c.goff[1], nullptr, 0.0, t == 0 ? c.glen[0] : c.glen[1]};
+    else return sx_group{t * c.n, nullptr, 0.0, c.n};
 }
 template <int L>
 constexpr int SX_GROUPS = L == BQ_SX_ONE ? 1 : 2;
+template <int L>
+constexpr bool SX_LINEAR = L == BQ_SX_LABELS || L == BQ_SX_PAIRED;   // the layouts with a linear term q
+
+// the panel rows a column's kernels walk: e = 0 ... sx_rows - 1 is panel row sx_row_at(e).  BLOCKS: the concatenation of the two
+// ranges, class a's rows (group 1) first; else the n rows
+template <int L>
+__device__ inline long long sx_rows(const bq_sx_col &c) {
+    if constexpr (L == BQ_SX_BLOCKS) return c.glen[1] + c.glen[0];
+    else return c.n;
+}
+template <int L>
+__device__ inline long long sx_row_at(const bq_sx_col &c, long long e) {
+    if constexpr (L == BQ_SX_BLOCKS) return e < c.glen[1] ? c.goff[1] + e : c.goff[0] + (e - c.glen[1]);
+    else return e;
+}
 
 // the variables of panel row i, fn(j, group, s_j v): the variable, its group and the panel's value v there under the variable's sign
 template <int L, class F>
@@ -320,6 +344,9 @@ __device__ inline void sx_row(const bq_sx_col &c, long long i, double v, F &&fn)
     } else if constexpr (L == BQ_SX_LABELS) {
         const double sg = c.sgn[i];
         fn(i, sg > 0.0 ? 0 : 1, sg * v);
+    } else if constexpr (L == BQ_SX_BLOCKS) {   // (class a's range lies below class b's)
+        if (i >= c.goff[0]) fn(i, 0, v);
+        else fn(i, 1, -v);
     } else {
         fn(i, 0, v);
     }
@@ -337,7 +364,7 @@ __global__ __launch_bounds__(SX_T) void sx_tau_kernel(const bq_sx_col *__restric
     const sx_group gr = sx_group_of<L>(c, t);
     const double mass = t == 0 ? c.mass[0] : c.mass[1];   // (constant indices: the column stays in registers)
     const int full = t == 0 ? c.full[0] : c.full[1];
-    const sx_tau tau = sx_find_tau(c.n, init ? nullptr : c.x + gr.off, init ? nullptr : c.g + gr.off, init ? 0.0 : c.st->s,
+    const sx_tau tau = sx_find_tau(gr.len, init ? nullptr : c.x + gr.off, init ? nullptr : c.g + gr.off, init ? 0.0 : c.st->s,
                                    c.ub + gr.off, gr.sgn, gr.want, mass, full, lds);
     if (threadIdx.x == 0) {
         double *o = c.tau + 4 * t;
@@ -356,7 +383,8 @@ __device__ inline sx_tau sx_load_tau(const double *tau, int t) {
 // panel row i (ONE: the variable i; LABELS: the variable i of the group its label names; PAIRED: the variables i of group 0 and n + i
 // of group 1).  init: x = P(0) per group (the columns without an x0) and W[:, column] = the signed, folded x.  Else, for a live
 // column: d = P(x - s g) - x with each variable's own group's tau, W[:, pos[column]] = d (ONE), sgn o d (LABELS) or d_i - d_{n + i}
-// (PAIRED), g'd and d'd over all m variables; g'd >= 0: 'optimal'
+// (PAIRED), g'd and d'd over all m variables; g'd >= 0: 'optimal'.  BLOCKS: thread e, e + 1024, ... on element e of the two ranges'
+// concatenation (sx_row_at), the variable of that row in the group whose range holds it, W = d on class b's rows and -d on class a's
 template <int L>
 __global__ __launch_bounds__(SX_T) void sx_dir_kernel(const bq_sx_col *__restrict__ cols, const int *__restrict__ pos,
                                                       double *__restrict__ W, int64_t ldw, int init) {
@@ -393,13 +421,18 @@ __global__ __launch_bounds__(SX_T) void sx_dir_kernel(const bq_sx_col *__restric
         a[1] += d * d;
         return d;
     };
-    for (long long i = tid; i < n; i += SX_T) {
+    const long long rows = sx_rows<L>(c);
+    for (long long e = tid; e < rows; e += SX_T) {
+        const long long i = sx_row_at<L>(c, e);
         if constexpr (L == BQ_SX_PAIRED) {
             const double lo = variable(i, 0), hi = variable(n + i, 1);
             w[i] = lo - hi;
         } else if constexpr (L == BQ_SX_LABELS) {
             const double sg = c.sgn[i];
             w[i] = sg * variable(i, sg > 0.0 ? 0 : 1);
+        } else if constexpr (L == BQ_SX_BLOCKS) {
+            if (i >= c.goff[0]) w[i] = variable(i, 0);
+            else w[i] = -variable(i, 1);
         } else {
             w[i] = variable(i, 0);
         }
@@ -492,13 +525,15 @@ __global__ __launch_bounds__(SX_T) void sx_start_kernel(const bq_sx_col *__restr
     __shared__ double lds[SX_LDS];
     const bq_sx_col c = cols[blockIdx.x];
     const double *Kb = out + (int64_t)blockIdx.x * ldw;
-    double a[L == BQ_SX_ONE ? 1 : 2] = {}, m[2 * SX_GROUPS<L>];
+    double a[SX_LINEAR<L> ? 2 : 1] = {}, m[2 * SX_GROUPS<L>];
     for (double &v : m) v = -INFINITY;
-    for (long long i = threadIdx.x; i < c.n; i += SX_T)
+    const long long rows = sx_rows<L>(c);
+    for (long long e = threadIdx.x; e < rows; e += SX_T) {
+        const long long i = sx_row_at<L>(c, e);
         sx_row<L>(c, i, Kb[i], [&](long long j, int t, double sKb) {
             const double xj = c.x[j];
             double gj = sKb;
-            if constexpr (L == BQ_SX_ONE) {
+            if constexpr (!SX_LINEAR<L>) {
                 a[0] += xj * gj;
             } else {
                 const double qj = c.q ? c.q[j] : 0.0;
@@ -509,10 +544,11 @@ __global__ __launch_bounds__(SX_T) void sx_start_kernel(const bq_sx_col *__restr
             c.g[j] = gj;
             sx_viol_add(m, t, xj, gj, c.ub[j]);
         });
+    }
     sx_block<SX_SUM>(a, lds);
     sx_block<SX_MAX>(m, lds);
     double f = 0.5 * a[0];
-    if constexpr (L != BQ_SX_ONE) f += a[1];
+    if constexpr (SX_LINEAR<L>) f += a[1];
     if (threadIdx.x == 0) sx_begin(c.sc, *c.st, f, sx_viol(m));
 }
 
@@ -528,19 +564,24 @@ __global__ __launch_bounds__(SX_T) void sx_close_kernel(const bq_sx_col *__restr
     const double *Kd = out + (int64_t)pos[blockIdx.x] * ldw;
     const int tid = threadIdx.x;
     double a[1] = {0.0};
-    for (long long i = tid; i < c.n; i += SX_T)
+    const long long rows = sx_rows<L>(c);
+    for (long long e = tid; e < rows; e += SX_T) {
+        const long long i = sx_row_at<L>(c, e);
         sx_row<L>(c, i, Kd[i], [&](long long j, int, double Qd) { a[0] += c.d[j] * Qd; });
+    }
     sx_block<SX_SUM>(a, lds);
     const sx_step p = sx_step_of(c.sc, c.st, a[0]);
     double m[2 * SX_GROUPS<L>];
     for (double &v : m) v = -INFINITY;
-    for (long long i = tid; i < c.n; i += SX_T)
+    for (long long e = tid; e < rows; e += SX_T) {
+        const long long i = sx_row_at<L>(c, e);
         sx_row<L>(c, i, Kd[i], [&](long long j, int t, double Qd) {
             const double xj = c.x[j] + p.alpha * c.d[j], gj = c.g[j] + p.alpha * Qd;
             c.x[j] = xj;
             c.g[j] = gj;
             sx_viol_add(m, t, xj, gj, c.ub[j]);
         });
+    }
     sx_block<SX_MAX>(m, lds);   // (its barriers: every thread has read the state before thread 0 writes it)
     if (tid == 0) sx_commit(c.sc, *c.st, p, sx_viol(m));
 }
@@ -563,6 +604,7 @@ __global__ __launch_bounds__(SX_T) void sx_top_kernel(const bq_sx_col *__restric
             sc->done = 1;
         }
     }
+    if (pos == nullptr) return;   // the routed product: column = pair, and its plan's live kernel follows
     __syncthreads();
     if (threadIdx.x != 0) return;
     int s = 0;
@@ -626,7 +668,7 @@ __global__ __launch_bounds__(SX_T) void sx_offsets_kernel(const bq_sx_col *__res
     const bq_sx_col c = cols[blockIdx.x];
     const sx_group gr = sx_group_of<L>(c, blockIdx.y);
     const int o = SX_GROUPS<L> * blockIdx.x + blockIdx.y;
-    sx_offsets_of(c.n, c.x + gr.off, c.g + gr.off, c.ub + gr.off, gr.sgn, gr.want, lds, r + o, n_sv + o, n_free + o);
+    sx_offsets_of(gr.len, c.x + gr.off, c.g + gr.off, c.ub + gr.off, gr.sgn, gr.want, lds, r + o, n_sv + o, n_free + o);
 }
 
 // fn(the layout as a constant): the instantiations of a launcher, chosen once
@@ -634,6 +676,7 @@ template <class F>
 static void sx_with_layout(int layout, F &&fn) {
     if (layout == BQ_SX_ONE) fn(std::integral_constant<int, BQ_SX_ONE>{});
     else if (layout == BQ_SX_PAIRED) fn(std::integral_constant<int, BQ_SX_PAIRED>{});
+    else if (layout == BQ_SX_BLOCKS) fn(std::integral_constant<int, BQ_SX_BLOCKS>{});
     else fn(std::integral_constant<int, BQ_SX_LABELS>{});
 }
 

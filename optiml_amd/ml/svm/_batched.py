@@ -1,7 +1,8 @@
 """What the batched SVM fits share (`OneVsRestSVC`, `OneVsOneSVC`, `SVCGridSearchCV`, `MultiOutputSVR`, `SVRGridSearchCV`,
 `OneClassSVM`): the device solver of many columns on one Gram panel (`_DeviceMultiSolver`: ProjectedGradient / FrankWolfe;
 `_DeviceALSolver`: the augmented-Lagrangian dual with the first-order rules; `_DeviceSimplexSolver`: the nu-one-class dual on its
-capped simplex; `_DeviceSimplex2Solver`: the nu-SVC / nu-SVR duals on two of them), the one-off multi-column products, the device memory budget of a solve, and
+capped simplex; `_DeviceSimplex2Solver`: the nu-SVC / nu-SVR duals on two of them; `_DeviceSimplexPairSolver`: the nu-SVC duals of class pairs on a
+class-sorted panel), the one-off multi-column products, the device memory budget of a solve, and
 the way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.fit`) leaves.
 """
 import ctypes as C
@@ -239,6 +240,31 @@ class _DeviceSimplex2Solver(_DeviceMultiSolver):
         _lib.check(self._lib.bq_msolver_simplex2_offsets(self._h, _lib.ptr(r1), _lib.ptr(r2), n_sv.ctypes.data_as(i64),
                                                          n_free.ctypes.data_as(i64)))
         return r1, r2, n_sv, n_free
+
+
+class _DeviceSimplexPairSolver(_DeviceSimplex2Solver):
+    """`bq_msolver_create_simplex2_pairs`: k two-group columns on a class-sorted 'plain' problem of n rows with the pair-routed
+    product.  cls_tiles: the classes' tile rows (`sort_plan`); pairs: k class pairs (a, b), a < b, one per column (a pair may
+    repeat); UB: k x n boxes, 0 outside the pair's rows; mass: k x 2, group 0 class b (+1), group 1 class a (-1); x0: k x n or
+    None.  Every vector the solver hands out has n entries, in panel order; `offsets()` as `_DeviceSimplex2Solver`'s."""
+
+    def __init__(self, problem, cls_tiles, pairs, UB, mass, tol, max_iter, x0=None):
+        UB = np.ascontiguousarray(np.atleast_2d(UB), dtype=float)
+        k, m = UB.shape
+        n = problem.dims()[1]
+        if m != n:   # (the library reads k x n entries of UB and x0)
+            raise ValueError('UB has %d columns, expected %d' % (m, n))
+        self._ct, self._pr = _lib.as_i32(cls_tiles), _pair_array(pairs)
+        if self._pr.size != 2 * k:
+            raise ValueError('%d pairs for %d columns' % (self._pr.size // 2, k))
+        self._mass = _lib.as_f64(mass, 2 * k, 'mass')
+        _DeviceMultiSolver.__init__(self, problem, None, UB, None, tol, max_iter, x0=x0)
+
+    def _create(self, handle, kind, UB, ub, x0, eps, max_iter, t):
+        x0 = self._x0(x0)
+        return self._lib.bq_msolver_create_simplex2_pairs(handle, len(self._ct) - 1, _lib.iptr(self._ct), self.k,
+                                                          _lib.iptr(self._pr), _lib.ptr(UB), _lib.ptr(self._mass), _lib.ptr(x0),
+                                                          eps, max_iter, C.byref(self._h))
 
 
 def simplex_project(V, UB, mass):

@@ -8,7 +8,8 @@ offsets.  Two builds of the library that print the same file compute the same bi
 n = 300 (two 256-row tiles, the second ragged); k = 5 on the 4-column product and k = 17 on the 16-column one (a full chunk and a
 ragged one); three classes of unequal sizes for the pairs (the class-sorted panel has ghost rows); two calibrators over disjoint
 held-out folds; the simplex solver in its three layouts (one group; labels with a start point; paired with a linear term), all with
-zero-width rows; the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
+zero-width rows, and its two-group columns on the pairs' class-sorted panel with the routed product (a pair twice, a start point
+that is a vertex on one column); the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
 iteration counts), so pos[] renumbers.
 """
 import hashlib
@@ -26,11 +27,12 @@ if len(sys.argv) > 1:
     _lib.LIB_PATH = os.path.abspath(sys.argv[1])   # as tools/bench_with_lib.py
 
 from optiml_amd.ml.svm import MultiOutputSVR, OneVsRestSVC, multiclass, multioutput  # noqa: E402
-from optiml_amd.ml.svm._batched import _DeviceMultiSolver, _DeviceSimplex2Solver, _DeviceSimplexSolver, _DeviceSVRSolver  # noqa: E402
+from optiml_amd.ml.svm._batched import (_DeviceMultiSolver, _DeviceSimplex2Solver, _DeviceSimplexPairSolver,  # noqa: E402
+                                        _DeviceSimplexSolver, _DeviceSVRSolver)
 from optiml_amd.ml.svm.coupling import chunk_calibrators, coupling_columns  # noqa: E402
 from optiml_amd.ml.svm.kernels import GaussianKernel  # noqa: E402
 from optiml_amd.ml.svm.losses import epsilon_insensitive, hinge  # noqa: E402
-from optiml_amd.ml.svm.onevsone import _DevicePairSolver  # noqa: E402
+from optiml_amd.ml.svm.onevsone import _DevicePairSolver, sort_plan  # noqa: E402
 from optiml_amd.opti import KernelQuadratic  # noqa: E402
 from optiml_amd.opti.unconstrained.stochastic import AdaGrad  # noqa: E402
 
@@ -212,6 +214,47 @@ def simplex2(paired):
     obj.release()
 
 
+def simplex2_blocks_pairs():
+    """the two-group columns of the class pairs on pairs()'s three unequal classes (the class-sorted panel has ghost rows) with the
+    routed product: five columns, pairs (0, 1) and (0, 2) twice, four of them holding out a third of their rows (zero-width
+    rows); every column starts from a point of its set, column 1 from a vertex (ones on each group's first rows), the others
+    from the uniform point"""
+    rs, X = data(12)
+    codes = np.repeat([0, 1, 2], [150, 100, 50])[rs.permutation(N)]
+    X = X + 0.8 * rs.standard_normal((3, D))[codes]
+    index, cls_tiles, n_pad = sort_plan(codes, 3)
+    Xp = np.zeros((n_pad, D))
+    Xp[index] = X
+    chunk = [(0, 1), (0, 2), (1, 2), (0, 2), (0, 1)]
+    nus = [0.3, 0.5, 0.7, 0.15, 0.6]
+    k = len(chunk)
+    UB, mass, x0 = np.zeros((k, n_pad)), np.zeros((k, 2)), np.zeros((k, n_pad))
+    for c, (i, j) in enumerate(chunk):
+        groups = []
+        for cls in (j, i):   # group 0: the larger class
+            rows = np.flatnonzero(codes == cls)
+            if c != 4:
+                rows = rows[rows % 3 != c % 3]
+            groups.append(index[rows])
+            UB[c, index[rows]] = 1.0
+        for g, prow in enumerate(groups):
+            mass[c, g] = nus[c] * min(len(q) for q in groups)
+            if c == 1:
+                whole = int(mass[c, g])
+                x0[c, prow[:whole]] = 1.0
+                x0[c, prow[whole]] = mass[c, g] - whole
+            else:
+                x0[c, prow] = mass[c, g] / len(prow)
+    obj = KernelQuadratic(Xp, np.zeros(n_pad), 'plain', KERNEL)
+    s = _DeviceSimplexPairSolver(obj.device_problem(), cls_tiles, chunk, UB, mass, 1e-4, 400, x0=x0)
+    name = 'simplex2_blocks_pairs_k%d' % k
+    run_to_end(s, name)
+    r1, r2, n_sv, n_free = s.offsets()
+    show(name + '.offsets', r1=r1, r2=r2, n_sv=n_sv, n_free=n_free)
+    s.close()
+    obj.release()
+
+
 def lagrangian():
     """the augmented-Lagrangian batch through its estimators (the rule's parameters are theirs to build): what
     solve_batched_al hands back for every column"""
@@ -251,3 +294,4 @@ if __name__ == '__main__':
     simplex2(False)
     simplex2(True)
     lagrangian()
+    simplex2_blocks_pairs()
