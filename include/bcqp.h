@@ -667,6 +667,16 @@ int bq_gram_matrix(bq_ctx *ctx, int kernel, double gamma, double coef0, int degr
  * factorisation alone. */
 int bq_cholesky_solve(bq_ctx *ctx, int64_t n, const double *A, const double *b, double *x, double *factor_ms);
 
+/* DIAGNOSTIC ENTRY: the factor and the solves of bq_cholesky_solve's kernels, as the solvers use them.  A (n x n row-major, lower
+ * triangle read) is factored once; if sweeps != 0 the fast sweeps are prepared; then row j of B (nrhs x n, one right-hand side per
+ * row) is solved as a right-hand side that vanishes before entry first_nonzero[j] (nrhs entries, or NULL for zeros) and the solution
+ * arrives in row j of X (nrhs x n) through the solve's second output, the path ActiveSet takes.  L: NULL, or n x n, which receives
+ * the lower triangle of the factor with zeros above it.  info: LAPACK's potrf value, 0 or 1 + the index of the first rejected
+ * pivot; a non-zero info returns BQ_OK and leaves X and L untouched.  An entry of first_nonzero outside [0, n), or a row of B with
+ * a non-zero before its entry: BQ_ERR_BADARG. */
+int bq_cholesky_probe(bq_ctx *ctx, int64_t n, const double *A, int nrhs, const double *B, const int64_t *first_nonzero, int sweeps,
+                      double *X, double *L, int *info);
+
 #ifdef __cplusplus
 }
 #endif

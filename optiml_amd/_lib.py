@@ -159,6 +159,7 @@ PROTOTYPES = {
                                       C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
     'bq_gram_matrix': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, _i64, _dp, _dp]),
     'bq_cholesky_solve': (C.c_int, [_vp, _i64, _dp, _dp, _dp, _dp]),
+    'bq_cholesky_probe': (C.c_int, [_vp, _i64, _dp, C.c_int, _dp, C.POINTER(_i64), C.c_int, _dp, _dp, _ip]),
 }
 
 

@@ -1054,6 +1054,22 @@ extern "C" int bq_cholesky_solve(bq_ctx *c, int64_t n, const double *A, const do
     return bq_chol_solve_dense_impl(c, n, A, b, x, factor_ms);
 }
 
+int bq_chol_probe_impl(bq_ctx *ctx, int64_t n, const double *A, int nrhs, const double *B, const int64_t *first_nonzero, int sweeps,
+                       double *X, double *L, int *info);
+
+extern "C" int bq_cholesky_probe(bq_ctx *c, int64_t n, const double *A, int nrhs, const double *B, const int64_t *first_nonzero,
+                                 int sweeps, double *X, double *L, int *info) {
+    BQ_ARG(c && A && info && nrhs >= 0 && (nrhs == 0 || (B && X)), "NULL argument");
+    BQ_ARG(n >= 1, "n");
+    for (int j = 0; j < nrhs; ++j) {
+        const int64_t f = first_nonzero ? first_nonzero[j] : 0;
+        BQ_ARG(f >= 0 && f < n, "first_nonzero outside [0, n)");
+        for (int64_t i = 0; i < f; ++i) BQ_ARG(B[(int64_t)j * n + i] == 0.0, "a right-hand side has a non-zero before its first_nonzero");
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    return bq_chol_probe_impl(c, n, A, nrhs, B, first_nonzero, sweeps, X, L, info);
+}
+
 extern "C" int bq_ctx_mem_info(bq_ctx *c, int64_t *free_bytes, int64_t *total_bytes) {
     BQ_ARG(c && free_bytes && total_bytes, "NULL argument");
     BQ_HIP(hipSetDevice(c->device));

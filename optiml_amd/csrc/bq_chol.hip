@@ -17,10 +17,12 @@
 #include <cstdlib>
 
 #include "bq_chol.h"
+#include "bq_chol_sched.h"
 #include "bq_qelem.h"
 #include "bq_mfma_tile.h"
 
 constexpr int NB = 128;
+static_assert(NB == BQ_CHOL_NB && sizeof(bq_chol_ws::ev) / sizeof(hipEvent_t) == BQ_CHOL_EVENTS, "the schedule header's block order and event ring");
 // 1. diagonal block (factor + invert): bq_potrf_diag.hip
 int bq_potrf_diag_setup();
 void bq_launch_potrf_diag(hipStream_t st, double *H, int64_t ldh, int64_t k0, double *LinvT, int *info, const double *thr);
@@ -55,26 +57,8 @@ __global__ __launch_bounds__(256, 2) void trsm_gemm_kernel(double *__restrict__ 
 __global__ __launch_bounds__(256, 2) void syrk_kernel(double *__restrict__ H, int64_t ldh, int64_t i0,
                                                       const double *__restrict__ Wt, int kdim, int64_t T, int64_t nsuper) {
     __shared__ __attribute__((aligned(16))) bq_tile_smem sm;
-    const int64_t bid = blockIdx.x, slot = bid / 8;
     int64_t ti, tj;
-    if (nsuper == 0) {   // small grids (a few rounds at most): plain row-major triangle, every XCD equally loaded
-        if (bid >= T * (T + 1) / 2) return;
-        ti = (int64_t)((sqrt(8.0 * (double)bid + 1.0) - 1.0) * 0.5);
-        while ((ti + 1) * (ti + 2) / 2 <= bid) ++ti;
-        while (ti * (ti + 1) / 2 > bid) --ti;
-        tj = bid - ti * (ti + 1) / 2;
-    } else {
-        const int64_t sidx = (slot / 64) * 8 + bid % 8;
-        if (sidx >= nsuper) return;
-        int64_t si = (int64_t)((sqrt(8.0 * (double)sidx + 1.0) - 1.0) * 0.5);
-        while ((si + 1) * (si + 2) / 2 <= sidx) ++si;
-        while (si * (si + 1) / 2 > sidx) --si;
-        const int64_t sj = sidx - si * (si + 1) / 2;
-        const int local = (int)(slot % 64);
-        ti = 8 * si + local / 8;
-        tj = 8 * sj + local % 8;
-        if (ti >= T || tj > ti) return;
-    }
+    if (!bq_chol_syrk_decode(blockIdx.x, T, nsuper, &ti, &tj)) return;   // both orders: bq_chol_sched.h
     const int64_t arow = i0 + ti * NB, bcol = i0 + tj * NB;
     bq_d4 acc[4][4];
     double *Ct = H + arow * ldh + bcol;
@@ -102,13 +86,8 @@ __global__ __launch_bounds__(256, 2) void syrk_col_kernel(double *__restrict__ H
 __global__ __launch_bounds__(256, 2) void syrk_head_kernel(double *__restrict__ H, int64_t ldh, int64_t r0,
                                                            const double *__restrict__ Wt, int kdim, int64_t T, int nc) {
     __shared__ __attribute__((aligned(16))) bq_tile_smem sm;
-    int64_t b = blockIdx.x, tj = 0;
-    while (tj < nc - 1 && b >= T - tj) {   // column tj holds T - tj tiles
-        b -= T - tj;
-        ++tj;
-    }
-    const int64_t ti = b + tj;
-    if (ti >= T) return;
+    int64_t ti, tj;
+    if (!bq_chol_head_decode(blockIdx.x, T, nc, &ti, &tj)) return;
     const int64_t arow = r0 + ti * NB, bcol = r0 + tj * NB;
     bq_d4 acc[4][4];
     double *Ct = H + arow * ldh + bcol;
@@ -141,7 +120,8 @@ __global__ __launch_bounds__(256) void fwd_panel_kernel(const double *__restrict
     __shared__ double comb[NB];
     const int r = blockIdx.x, tid = threadIdx.x;
     const double *row = H + (k0 + r) * ldh;
-    const int64_t lo = c0 + (int64_t)blockIdx.y * slice, hi = lo + slice < k0 ? lo + slice : k0;
+    int64_t lo, hi;
+    bq_chol_fwd_slice_range(c0, k0, slice, blockIdx.y, &lo, &hi);
     double a = 0.0;
     // c0: the right-hand side is known to vanish before column c0 (a multiple of 128)
     for (int64_t c = lo + 2 * tid; c < hi; c += 512) {  // slices are multiples of 512, k0 of 128: pairs never straddle
@@ -279,11 +259,11 @@ int bq_chol_ws_create(bq_ctx *ctx, int64_t n, bq_chol_ws **out) {
         delete ws;
         return BQ_ERR_NOMEM;
     }
-    ws->super_max = ws->cap >= 24576 ? 4 : 2;   // passes per super-pass the image buffers are sized for
+    ws->super_max = bq_chol_super_max(ws->cap, bq_hook("chol_passes", nullptr));   // passes per super-pass the image buffers are sized for
     ws->Wt = mem.dev<double>(2 * ws->super_max * 2 * NB * ws->ldh);   // 2 super-passes of images
     ws->LinvT = mem.dev<double>(nblk * NB * NB);
     ws->rhs = mem.dev<double>(ws->cap + NB);
-    ws->tmp = mem.dev<double>(4 * NB);   // up to four column slices of a block row
+    ws->tmp = mem.dev<double>(BQ_CHOL_MAX_SLICES * NB);   // up to four column slices of a block row
     ws->info = mem.dev<int>(1);
     ws->ticket = mem.dev<unsigned int>(1);
     e = mem.error();
@@ -359,107 +339,43 @@ int bq_chol_factor(bq_chol_ws *ws, int64_t np) {
         pivot_thr_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(ws->H, ldh, np, ws->pivot_rel, ws->pivot_thr);
         thr = ws->pivot_thr;
     }
-    // Two block columns per pass p (A_p = 2p*NB, B_p = A_p + NB), two passes per SUPER-PASS q (passes 2q, 2q+1):
-    //   narrow(p): diag(A) ; TRSM(A) ; narrow update of column B ; diag(B) ; TRSM(B)        -> images of pass p
-    //   head_in(p): the two block columns pass p+1 factors next  -= the images of the super-pass so far
-    //   wide(q)  : everything behind the super-pass -= X X^T with ALL its images in ONE K = P * 256 pass — a C tile is read
-    //              and written once per P * 256 columns factored (tools/syrk_probe.hip, final tile kernel: 69.5 / 73.6 /
-    //              74.3 TFLOP/s at K = 512 / 768 / 1024; with the round-1 kernel it was 0.71 of the MFMA peak at K = 256);
-    //              split into head (the 2P block columns the next chain works on) and rest.
-    // The images of a super-pass are contiguous in k, two buffers.
-    // With look-ahead the narrow chain of super-pass q+1 (it touches only the 2P block columns head(q) has finished) runs on
-    // the high-priority side stream while rest(q) keeps the chip busy.
-    // P passes per super-pass (by size): the wide update then has K = P * 256.  A larger P cuts the C
-    // traffic and the per-tile prologue per flop further but lengthens the narrow chain between two wide updates.
-    const int P = [&] {
-        int v = np >= 65536 ? 4 : (np >= 24576 ? 3 : 2);   // measured (final kernel): n=50k 622 / 608 / 621 ms, n=32k 192 / 190 / 194 ms for P = 2 / 3 / 4
-        return v < 1 ? 1 : (v > ws->super_max ? ws->super_max : v);
-    }();
-    auto wimg = [&](int64_t p) {   // images of a super-pass are contiguous in k; two buffers
-        return ws->Wt + ((p / P) & 1) * (int64_t)(P * 2 * NB) * ldh + (p % P) * (int64_t)(2 * NB) * ldh;
-    };
-    auto narrow = [&](int64_t p, hipStream_t s) {
-        const int64_t a0 = 2 * p * NB;
-        if (a0 >= np) return;
-        double *WtA = wimg(p), *WtB = WtA + (int64_t)NB * ldh;
-        auto panel = [&](int64_t k0, double *Wimg) {   // diag(k0) done: TRSM the rows below, leave their image in Wimg
-            const int64_t i0 = k0 + NB;
-            const int64_t T = (np - i0) / NB;
-            const double *LinvT = ws->LinvT + (k0 / NB) * NB * NB;
-            trsm_gemm_kernel<<<(unsigned)T, 256, 0, s>>>(ws->H, ldh, k0, i0, Wimg, LinvT);
-        };
-        bq_launch_potrf_diag(s, ws->H, ldh, a0, ws->LinvT + (a0 / NB) * NB * NB, ws->info, thr);
-        const int64_t b0 = a0 + NB;
-        if (b0 >= np) return;
-        panel(a0, WtA);
-        syrk_col_kernel<<<(unsigned)((np - b0) / NB), 256, 0, s>>>(ws->H, ldh, b0, WtA);
-        bq_launch_potrf_diag(s, ws->H, ldh, b0, ws->LinvT + (b0 / NB) * NB * NB, ws->info, thr);
-        if (b0 + NB >= np) return;
-        panel(b0, WtB);
-    };
-    auto head_grid = [](int64_t T, int nc) {
-        int64_t g = 0;
-        for (int c = 0; c < nc && c < T; ++c) g += T - c;
-        return (unsigned)g;
-    };
-    // the two block columns pass p+1 factors  -=  the images of ALL passes of p's super-pass so far (K = 256 .. (P-1) 256)
-    auto head_in = [&](int64_t p, hipStream_t s) {
-        const int64_t r0 = 2 * p * NB + 2 * NB;
-        if (r0 >= np) return;
-        const int64_t T = (np - r0) / NB;
-        const int64_t first = p / P * P;
-        syrk_head_kernel<<<head_grid(T, 2), 256, 0, s>>>(ws->H, ldh, r0, wimg(first), (int)((p - first + 1) * 2 * NB), T, 2);
-    };
-    // the narrow chain of super-pass q: narrow, head_in, narrow, ..., narrow
-    auto chain = [&](int64_t q, hipStream_t s) {
-        for (int j = 0; j < P; ++j) {
-            narrow(q * P + j, s);
-            if (j + 1 < P) head_in(q * P + j, s);
+    // the steps and their order: bq_chol_plan (bq_chol_sched.h); hooks chol_passes, chol_lookahead, chol_super_min force the
+    // paths that the size would not take (tests)
+    double hv = 0.0;
+    const int P = bq_chol_passes(np, ws->super_max, bq_hook("chol_passes", &hv) ? (int)hv : 0);
+    const bool two_streams = bq_chol_use_lookahead(np, ws->lookahead, bq_hook("chol_lookahead", &hv) ? (hv != 0.0 ? 1 : 0) : -1);
+    const int64_t super_min = bq_hook("chol_super_min", &hv) && hv >= 1.0 ? (int64_t)hv : BQ_CHOL_SUPER_MIN;
+    const hipStream_t streams[3] = {st, ws->s_main, ws->s_side};
+    hipError_t err = hipSuccess;
+    bq_chol_plan(np, P, two_streams, super_min, [&](const bq_chol_step &t) {
+        if (err != hipSuccess) return;
+        hipStream_t s = streams[t.stream];
+        double *img = ws->Wt + t.img * ldh;
+        switch (t.op) {
+        case BQ_CHOL_DIAG:
+            bq_launch_potrf_diag(s, ws->H, ldh, t.row, ws->LinvT + (t.row / NB) * NB * NB, ws->info, thr);
+            break;
+        case BQ_CHOL_TRSM:   // diag(row) done: TRSM the rows below, leave their image in img
+            trsm_gemm_kernel<<<(unsigned)t.T, 256, 0, s>>>(ws->H, ldh, t.row, t.row + NB, img, ws->LinvT + (t.row / NB) * NB * NB);
+            break;
+        case BQ_CHOL_COL:
+            syrk_col_kernel<<<(unsigned)t.T, 256, 0, s>>>(ws->H, ldh, t.row, img);
+            break;
+        case BQ_CHOL_HEAD:
+            syrk_head_kernel<<<(unsigned)bq_chol_head_grid(t.T, (int)t.nc), 256, 0, s>>>(ws->H, ldh, t.row, img, t.kdim, t.T, (int)t.nc);
+            break;
+        case BQ_CHOL_REST:
+            syrk_kernel<<<(unsigned)bq_chol_syrk_grid(t.T, t.nc), 256, 0, s>>>(ws->H, ldh, t.row, img, t.kdim, t.T, t.nc);
+            break;
+        case BQ_CHOL_RECORD:
+            err = hipEventRecord(ws->ev[t.nc], s);
+            break;
+        case BQ_CHOL_WAIT:
+            err = hipStreamWaitEvent(s, ws->ev[t.nc], 0);
+            break;
         }
-    };
-    // everything behind super-pass q  -=  X X^T with its 2P images in one K = P * 256 pass: first the 2P block columns the next
-    // chain works on, then the rest
-    auto wide_head = [&](int64_t q, hipStream_t s) {
-        const int64_t r0 = (q + 1) * P * 2 * NB;
-        if (r0 >= np) return;
-        const int64_t T = (np - r0) / NB;
-        syrk_head_kernel<<<head_grid(T, 2 * P), 256, 0, s>>>(ws->H, ldh, r0, wimg(q * P), P * 2 * NB, T, 2 * P);
-    };
-    auto wide_rest = [&](int64_t q, hipStream_t s) {
-        const int64_t r0 = (q + 1) * P * 2 * NB + 2 * P * NB;
-        if (r0 >= np) return;
-        const int64_t T = (np - r0) / NB;
-        const int64_t S = (T + 7) / 8, ntiles = T * (T + 1) / 2;
-        // super-tiles pay off once an XCD has many of them; below ~8 rounds of the chip the even split wins
-        const int64_t nsuper = ntiles >= 8 * 512 ? S * (S + 1) / 2 : 0;
-        const unsigned grid = nsuper ? (unsigned)(((nsuper + 7) / 8) * 8 * 64) : (unsigned)ntiles;
-        syrk_kernel<<<grid, 256, 0, s>>>(ws->H, ldh, r0, wimg(q * P), P * 2 * NB, T, nsuper);
-    };
-    const int64_t npass = (np + 2 * NB - 1) / (2 * NB), nsup = (npass + P - 1) / P;
-    if (!ws->lookahead || np < 16 * NB) {
-        for (int64_t q = 0; q < nsup; ++q) {
-            chain(q, st);
-            wide_head(q, st);
-            wide_rest(q, st);
-        }
-    } else {
-        hipStream_t sm = ws->s_main, ss = ws->s_side;
-        BQ_HIP(hipEventRecord(ws->ev[0], st));       // everything enqueued so far (H assembly) precedes the factorisation
-        BQ_HIP(hipStreamWaitEvent(sm, ws->ev[0], 0));
-        chain(0, sm);
-        for (int64_t q = 0; q < nsup; ++q) {
-            hipEvent_t e_head = ws->ev[1 + (q % 3)], e_narrow = ws->ev[4 + (q % 3)];
-            wide_head(q, sm);
-            BQ_HIP(hipEventRecord(e_head, sm));
-            BQ_HIP(hipStreamWaitEvent(ss, e_head, 0));
-            chain(q + 1, ss);
-            BQ_HIP(hipEventRecord(e_narrow, ss));
-            wide_rest(q, sm);
-            BQ_HIP(hipStreamWaitEvent(sm, e_narrow, 0));
-        }
-        BQ_HIP(hipEventRecord(ws->ev[7], sm));
-        BQ_HIP(hipStreamWaitEvent(st, ws->ev[7], 0));   // the solves (on the context stream) follow the factorisation
-    }
+    });
+    BQ_HIP(err);
     BQ_HIP(hipGetLastError());
     BQ_TRY(bq_prof_end(ctx, BQ_PROF_CHOL, e0, e1));
     return BQ_OK;
@@ -598,11 +514,8 @@ int bq_chol_prepare_sweeps(bq_chol_ws *ws, int64_t np) {
     // the price of more inverse-block traffic (np * bb * 8 B per direction); hook sweep_block forces it (tests, the sweep)
     // measured (profiles/r06/as_sweep_block.txt, dense ActiveSet to 'optimal'): n = 20 000 9.91 / 9.16 / 9.07 / 10.18 s and n = 50 000
     // 79.2 / 72.2 / 70.6 / 73.5 s with 1024 / 2048 / 4096 / 8192
-    int64_t BB = ws->cap >= 8192 ? 4096 : (ws->cap >= 4096 ? 2048 : 1024);
-    {
-        double hv = 0.0;
-        if (bq_hook("sweep_block", &hv) && (hv == 1024.0 || hv == 2048.0 || hv == 4096.0 || hv == 8192.0)) BB = (int64_t)hv;
-    }
+    double hv = 0.0;
+    const int64_t BB = bq_chol_big_block(ws->cap, bq_hook("sweep_block", &hv) ? (int64_t)hv : 0);
     const int64_t nbb = (np + BB - 1) / BB;
     if (ws->big_cap < nbb || ws->bb != BB) {
         for (double **p : {&ws->bigM, &ws->bigMT, &ws->big_scratch, &ws->sw_t}) {
@@ -674,10 +587,12 @@ int bq_chol_solve(bq_chol_ws *ws, int64_t np, int64_t first_nonzero, double *als
     // y = 0 there, so the sweep starts at that row's block.
     const int64_t kb = (first_nonzero / NB) * NB;
     diag_mv_kernel<<<1, 256, 0, st>>>(Linv(kb), 0, ws->rhs + kb, ws->rhs + kb);
+    double hv = 0.0;
+    const int64_t unit = bq_hook("chol_fwd_slice", &hv) && hv >= 1.0 ? (int64_t)hv : BQ_CHOL_FWD_SLICE;   // tests: 2 - 4 slices at small orders
     for (int64_t k0 = kb + NB; k0 < np; k0 += NB) {
-        const int64_t span = k0 - kb;
-        const int slices = (int)std::min<int64_t>(4, (span + 16383) / 16384);
-        const int64_t slice = ((span + slices - 1) / slices + 511) / 512 * 512;
+        int slices;
+        int64_t slice;
+        bq_chol_fwd_slices(k0 - kb, unit, &slices, &slice);
         fwd_panel_kernel<<<dim3(NB, (unsigned)slices), 256, 0, st>>>(ws->H, ldh, k0, ws->rhs, ws->tmp, Linv(k0), ws->ticket, kb,
                                                                     slice);
     }
@@ -784,5 +699,51 @@ int bq_chol_solve_dense_impl(bq_ctx *ctx, int64_t n, const double *A, const doub
         bq_set_error("%d-th leading minor of the array is not positive definite", info);
         return BQ_ERR_NOT_PD;
     }
+    return BQ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// diagnostic entry (bq_cholesky_probe): the factor itself, LAPACK's info, and solves the way the ActiveSet issues them — a start row
+// per right-hand side, the solution through `also`, block by block or with the prepared sweeps
+// ---------------------------------------------------------------------------------------------
+int bq_chol_probe_impl(bq_ctx *ctx, int64_t n, const double *A, int nrhs, const double *B, const int64_t *first_nonzero, int sweeps,
+                       double *X, double *L, int *info_out) {
+    bq_chol_ws *ws = nullptr;
+    BQ_TRY(bq_chol_ws_create(ctx, n, &ws));
+    const int64_t np = bq_round_up(n, NB);
+    hipStream_t st = ctx->stream;
+    int rc = BQ_OK, info = 0;
+    double *also = ws->mem.dev<double>(np);
+    hipError_t e = ws->mem.error();
+    if (e == hipSuccess) e = hipMemcpy2DAsync(ws->H, ws->ldh * 8, A, n * 8, n * 8, n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && np > n) pad_identity_kernel<<<(unsigned)(np - n), 128, 0, st>>>(ws->H, ws->ldh, n, np);
+    if (e == hipSuccess) rc = bq_chol_factor(ws, np);
+    if (e == hipSuccess && rc == BQ_OK) e = hipMemcpyAsync(&info, ws->info, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == BQ_OK) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && rc == BQ_OK && info == 0) {   // a rejected pivot: nothing below runs, X and L stay as they are
+        if (sweeps != 0) rc = bq_chol_prepare_sweeps(ws, np);
+        for (int j = 0; j < nrhs && rc == BQ_OK && e == hipSuccess; ++j) {
+            e = hipMemsetAsync(ws->rhs, 0, sizeof(double) * np, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(ws->rhs, B + (int64_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemsetAsync(also, 0xff, sizeof(double) * np, st);   // NaNs: only what the solve writes arrives
+            if (e == hipSuccess) rc = bq_chol_solve(ws, np, first_nonzero ? first_nonzero[j] : 0, also);
+            if (e == hipSuccess && rc == BQ_OK)
+                e = hipMemcpyAsync(X + (int64_t)j * n, also, sizeof(double) * n, hipMemcpyDeviceToHost, st);
+        }
+        if (e == hipSuccess && rc == BQ_OK && L != nullptr)
+            e = hipMemcpy2DAsync(L, n * 8, ws->H, ws->ldh * 8, n * 8, n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        // the device's upper triangle holds what was uploaded there or, once the sweeps are prepared, L^T: not part of the factor
+        if (e == hipSuccess && rc == BQ_OK && L != nullptr)
+            for (int64_t i = 0; i < n; ++i) std::fill(L + i * n + i + 1, L + (i + 1) * n, 0.0);
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    bq_chol_ws_destroy(ws);
+    if (rc != BQ_OK) return rc;
+    if (e != hipSuccess) {
+        bq_set_error("Cholesky probe failed: %s", hipGetErrorString(e));
+        return BQ_ERR_HIP;
+    }
+    *info_out = info;
     return BQ_OK;
 }

@@ -58,6 +58,11 @@ void bq_set_error(const char *fmt, ...);
 //   panel_good_gbs=G  alloc_fail_above=BYTES  decision_chunk_rows=R  decision_multi_unit=TILES  decision_multi_chunk_rows=R  sweep_block=1024|2048|4096  compact_panel=0
 //   hessian_image=0 (no Hessian image is built and none is read: the A/B of one build)  hessian_image_bad=1 (the conversion raises its flag)
 //   product_rows=1 (bq_problem_last_product answers)
+//   the blocked Cholesky's large-order paths at small orders (bq_chol.hip, bq_chol_sched.h):
+//   chol_lookahead=0|1 (single-stream / two-stream issue order at every order; 1 still needs the workspace's streams and events)
+//   chol_passes=1..4 (P passes per super-pass; a workspace created under this hook sizes its image buffers for 4)
+//   chol_super_min=N (tiles of a trailing triangle from which the wide update takes the super-tile order; default 4096)
+//   chol_fwd_slice=N (columns per slice of the block-by-block forward sweep; default 16384)
 //   hessian_image_gain=G (the image is kept if its product is G times faster than the panel's; default 1, 0: always)
 // ---------------------------------------------------------------------------------------------
 bool bq_hook(const char *name, double *value);                       // true (and *value) when the hook is set
