@@ -532,7 +532,8 @@ int bq_msolver_pairs_heldout(bq_msolver *s, const unsigned char *data_row, int n
  *
  * bq_solver_get_state: the state at the top of the NEXT iteration (iteration `iter`): a step that has been decided but not yet
  * applied to the device vectors (PG / FW: x + t d, g + t Qd; IP: x + t dx, lp + t dlp, lm + t dlm) is applied to the copies
- * handed out, with the device's own rounding (one rounded product, one sum).  Vector pointers that are NULL are skipped; `have`
+ * handed out, with the device's own rounding (one rounded product, one sum; PG / FW: x then kept in [lb, ub], as the device keeps
+ * it: the step is feasible and only its rounding can pass a bound).  Vector pointers that are NULL are skipped; `have`
  * says which of the others were filled (BQ_STATE_*): lp / lm exist for BQ_IP, the masks (1.0 / 0.0 per index) for BQ_AS / BQ_AS_CG.
  *
  * bq_solver_set_state: into a solver that has not run yet (same problem, kind, bounds).  x is required; g, lp & lm, the masks are

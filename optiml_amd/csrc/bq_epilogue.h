@@ -79,6 +79,10 @@ __device__ __forceinline__ bq_pgfw_elem bq_pgfw_compute(int kind, const bq_pgfw_
     double xi = in.x, gi = in.g;
     if (update) {
         xi = xi + __dmul_rn(t, in.d);
+        // The step is feasible in exact arithmetic (PG: t <= the minimum ratio; FW: a <= 1), but fl(x + fl(t d)) of the entry that
+        // sets the ratio need not be its bound (measured: -2.8e-17 for 0, ub + 2.1e-22).  The box holds bitwise; comparisons, so
+        // that a NaN stays one.
+        xi = xi < in.lb ? in.lb : (xi > in.ub ? in.ub : xi);
         gi = gi + __dmul_rn(t, in.Qd);
     }
     double di;

@@ -533,6 +533,13 @@ extern "C" int bq_solver_get_state(bq_solver *s, bq_solver_snapshot *out) {
     const bool pgfw = s->kind == BQ_PG || s->kind == BQ_FW;
     if (out->x) {
         BQ_TRY(fetch(out->x, s->x, s->d));   // d: PG / FW direction, IP dx (ip_vecs)
+        if (pgfw && pending) {   // bq_pgfw_compute keeps the stepped x in its box
+            std::vector<double> lb(N), ub(N);
+            BQ_HIP(down(lb, s->lb));
+            BQ_HIP(down(ub, s->ub));
+            BQ_SYNC(c);
+            for (size_t i = 0; i < N; ++i) out->x[i] = out->x[i] < lb[i] ? lb[i] : (out->x[i] > ub[i] ? ub[i] : out->x[i]);
+        }
         out->have |= BQ_STATE_X;
     }
     // the gradient exists once the start-up has run (PG / FW keep it current: g + t Qd; IP and ActiveSet keep the reference's
