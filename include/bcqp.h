@@ -60,6 +60,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_simplex, bq_msolver_simplex_offsets and bq_simplex_project were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_simplex2 and bq_msolver_simplex2_offsets were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_simplex2_pairs was added; nothing existing changed) */
+/* (still 3: bq_msolver_simplex2_heldout was added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -467,6 +468,22 @@ enum { BQ_SX_LABELS = 0, BQ_SX_PAIRED = 1 };
 int bq_msolver_create_simplex2(bq_problem *p, int k, int layout, const double *S, const double *UB, const double *mass,
                                const double *q, const double *x0, double tol, int64_t max_iter, bq_msolver **out);
 int bq_msolver_simplex2_offsets(bq_msolver *s, double *r1, double *r2, int64_t *n_sv, int64_t *n_free);
+/* Held-out scores of every column of a bq_msolver_create_simplex2 solver that has run (a NULL argument, any other solver — the
+ * one-group and the pair-routed simplex solvers included — or a solver before its first run: BQ_ERR_BADARG), from its state on the
+ * device: sklearn GridSearchCV's per-fold NuSVC / NuSVR score of a column whose box is 0 on the fold's held-out rows, and no k x n
+ * array crosses the bus.  y: n entries; BQ_SX_LABELS: the labels of all rows, each exactly +-1 (the solver's own S is not read on
+ * held-out rows, so they come in here); BQ_SX_PAIRED: the targets, all finite; anything else is BQ_ERR_BADARG.
+ *   r1, r2 (k), n_sv, n_free (k x 2)   the bits of bq_msolver_simplex2_offsets on the same state
+ *   u = K b, b the signed, folded x (S o x; x_i - x_{n + i}), by one 16-column product per 16 columns, every column in its own slot,
+ *   live or not; the solver's incrementally updated g is not read.  rho = (r1 - r2) / 2, r = (r1 + r2) / 2
+ *   n_held (k)      the held-out rows: UB[c][i] == 0 (LABELS), both halves 0 (PAIRED)
+ *   n_correct (k)   LABELS: the held-out rows whose prediction, +1 exactly when (u_i - rho) / r > 0 in that form (NuSVC.predict: a
+ *                   NaN or a non-positive r predicts as np.where(decision > 0, ...) does), equals y_i; PAIRED: 0
+ *   sse (k)         PAIRED: the sum over the held-out rows of (y_i - (u_i - rho))^2 (NuSVR.predict is u - rho); LABELS: 0
+ * One workgroup per column sums in a fixed order and reads its own column only, so a column's results have the same bits alone, at
+ * any position and in any batch.  The solver's state and liveness are untouched: a later run continues as without the call. */
+int bq_msolver_simplex2_heldout(bq_msolver *s, const double *y, double *r1, double *r2, int64_t *n_sv, int64_t *n_free,
+                                int64_t *n_held, int64_t *n_correct, double *sse);
 /* The two-group columns of one-vs-one nu-SVC on a class-sorted panel (sklearn OneVsOneClassifier(NuSVC): NuSVC.fit on the rows of
  * classes a and b, once per pair and nu), with the pair-routed product of bq_msolver_create_pairs.  cls_tiles, pairs: as
  * bq_problem_gram_matmat_pairs; the same pair may appear in several columns (one per nu).  Column c of pair (a, b), a < b, has m = n

@@ -134,6 +134,8 @@ PROTOTYPES = {
     'bq_simplex_project': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp]),
     'bq_msolver_create_simplex2': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, _i64, C.POINTER(_vp)]),
     'bq_msolver_simplex2_offsets': (C.c_int, [_vp, _dp, _dp, C.POINTER(_i64), C.POINTER(_i64)]),
+    'bq_msolver_simplex2_heldout': (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+                                              C.POINTER(_i64), _dp]),
     'bq_msolver_create_simplex2_pairs': (C.c_int, [_vp, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.POINTER(_vp)]),
     'bq_platt_fit': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, _ip, _dp, C.POINTER(_i64), C.POINTER(_i64), _ip]),
     'bq_msolver_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp, C.POINTER(_i64),

@@ -4,7 +4,8 @@
 // of another column enters).  bq_msolver_svr_heldout: the intercept and the held-out squared error of a column of a
 // cross-validated SVR search.  bq_msolver_svc_heldout / _pairs_heldout: the intercept, the held-out decision values and their Platt
 // fit (bq_platt.hip) per calibrator.  bq_msolver_simplex_offsets / _simplex2_offsets: the offsets of the nu-one-class and of the
-// two-group (nu-SVC / nu-SVR) columns (bq_simplex.hip).
+// two-group (nu-SVC / nu-SVR) columns (bq_simplex.hip).  bq_msolver_simplex2_heldout: those offsets and the held-out accuracy
+// (nu-SVC) or squared error (nu-SVR) of a column of a cross-validated nu-search.
 #include "bq_msolver.h"
 #include "bq_scratch.h"
 
@@ -178,6 +179,125 @@ extern "C" int bq_msolver_simplex2_offsets(bq_msolver *m, double *r1, double *r2
     std::vector<double> r((size_t)(2 * m->k));
     BQ_TRY(msolver_sx_offsets(m, r.data(), n_sv, n_free));
     for (int cl = 0; cl < m->k; ++cl) {
+        r1[cl] = r[2 * cl];
+        r2[cl] = r[2 * cl + 1];
+    }
+    return BQ_OK;
+}
+
+// the product's input of a two-group simplex column (bq_sx_col), to the column's own slot: the signed, folded x, S o x (LABELS: the
+// device's labels are +1 where ub = 0, and x is 0 there) or x_i - x_{n + i} (PAIRED), in sx_dir_kernel's expressions.  Reads x only
+template <bool PAIRED>
+__global__ __launch_bounds__(256) void msx_fold_kernel(const bq_sx_col *__restrict__ cols, double *__restrict__ W, int64_t ldw) {
+    const bq_sx_col &c = cols[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= c.n) return;
+    W[blockIdx.y * ldw + i] = PAIRED ? c.x[i] - c.x[c.n + i] : c.sgn[i] * c.x[i];
+}
+
+// bq_msolver_simplex2_heldout, column blockIdx.x, u = out[:, column] = K b; r = the column's two offsets (r1, r2), as
+// sx_offsets_kernel left them.  rho = (r1 - r2) / 2, scale = (r1 + r2) / 2.  Over the held-out rows (LABELS: ub = 0; PAIRED: ub = 0 on
+// both halves): n_held, and LABELS: the rows whose prediction ((u - rho) / scale > 0: +1, else -1; a NaN or a non-positive scale as
+// np.where(decision > 0, ...) takes them) equals y, sse = 0; PAIRED: sse = sum (y - (u - rho))^2, n_correct = 0.  Thread t sums the
+// rows t, t + 1024, ... in ascending order, then msvr_tree: no atomics, and nothing of another column enters
+template <bool PAIRED>
+__global__ __launch_bounds__(1024) void msx_score_kernel(const bq_sx_col *__restrict__ cols, const double *__restrict__ out, int64_t ldw,
+                                                         const double *__restrict__ y, const double *__restrict__ r,
+                                                         long long *__restrict__ n_held, long long *__restrict__ n_correct,
+                                                         double *__restrict__ sse) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    const bq_sx_col &c = cols[blockIdx.x];
+    const double *u = out + blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    const long long n = c.n;
+    const double r1 = r[2 * blockIdx.x], r2 = r[2 * blockIdx.x + 1];
+    const double rho = (r1 - r2) / 2, scale = (r1 + r2) / 2;
+    double s = 0.0;
+    int held = 0, right = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool h = PAIRED ? (c.ub[i] == 0.0 && c.ub[n + i] == 0.0) : c.ub[i] == 0.0;
+        if (PAIRED) {
+            const double e = y[i] - (u[i] - rho);
+            s += h ? e * e : 0.0;
+        } else {
+            const double pred = (u[i] - rho) / scale > 0.0 ? 1.0 : -1.0;
+            right += (h && pred == y[i]) ? 1 : 0;
+        }
+        held += h ? 1 : 0;
+    }
+    sd[tid] = s;
+    sc[tid] = held;
+    msvr_tree(sd, sc, tid);
+    const double total = sd[0];
+    const int nheld = sc[0];
+    __syncthreads();   // sd[0], sc[0] are read: the second tree may overwrite them
+    sd[tid] = 0.0;
+    sc[tid] = right;
+    msvr_tree(sd, sc, tid);
+    if (tid == 0) {
+        n_held[blockIdx.x] = nheld;
+        n_correct[blockIdx.x] = sc[0];
+        sse[blockIdx.x] = total;
+    }
+}
+
+extern "C" int bq_msolver_simplex2_heldout(bq_msolver *m, const double *y, double *r1, double *r2, int64_t *n_sv, int64_t *n_free,
+                                           int64_t *n_held, int64_t *n_correct, double *sse) {
+    BQ_ARG(m && y && r1 && r2 && n_sv && n_free && n_held && n_correct && sse, "NULL argument");
+    BQ_ARG(m->method == BQ_M_SIMPLEX && m->product == BQ_MP_SYMM16 && (m->sx_layout == BQ_SX_LABELS || m->sx_layout == BQ_SX_PAIRED),
+           "held-out scoring takes a solver of bq_msolver_create_simplex2");
+    BQ_ARG(m->initialised, "held-out scoring takes a solver that has run");
+    bq_problem *p = m->p;
+    const bool paired = m->sx_layout == BQ_SX_PAIRED;
+    const int k = m->k;
+    const int64_t n = p->n;
+    for (int64_t i = 0; i < n; ++i) {
+        if (paired) BQ_ARG(std::isfinite(y[i]), "the targets must be finite");
+        else BQ_ARG(y[i] == 1.0 || y[i] == -1.0, "labels must be +1 or -1");
+    }
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    std::vector<double> r((size_t)(2 * k));   // (r1, r2) per column; split after the closing sync
+    bq_scratch mem;                           // freed after the closing sync
+    double *dy = mem.dev<double>(n), *dsse = mem.dev<double>(k);
+    long long *dnheld = mem.dev<long long>(k), *dnright = mem.dev<long long>(k);
+    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    long long *dn = m->sx_counts;   // n_sv, then n_free, 2 k each
+    hipError_t e = mem.error();
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("held-out scoring setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) rc = bq_sx_launch_offsets(m->sx_cols, k, m->sx_layout, m->sx_rho, dn, dn + 2 * k, st);
+    if (rc == BQ_OK) {   // u = K b afresh: the solver's g is updated incrementally and holds the unread labels on LABELS held-out rows
+        const dim3 grid((unsigned)((n + 255) / 256), (unsigned)k);
+        if (paired) msx_fold_kernel<true><<<grid, 256, 0, st>>>(m->sx_cols, m->W, m->ldw);
+        else msx_fold_kernel<false><<<grid, 256, 0, st>>>(m->sx_cols, m->W, m->ldw);
+        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+    }
+    if (rc == BQ_OK) {
+        if (paired) msx_score_kernel<true><<<k, 1024, 0, st>>>(m->sx_cols, m->out, m->ldw, dy, m->sx_rho, dnheld, dnright, dsse);
+        else msx_score_kernel<false><<<k, 1024, 0, st>>>(m->sx_cols, m->out, m->ldw, dy, m->sx_rho, dnheld, dnright, dsse);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(r.data(), m->sx_rho, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + 2 * k, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_correct, dnright, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(sse, dsse, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("held-out scoring: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    rc = bq_ctx_sync_after(c, rc);   // y, k and the results are the caller's and this frame's
+    if (rc != BQ_OK) return rc;
+    for (int cl = 0; cl < k; ++cl) {
         r1[cl] = r[2 * cl];
         r2[cl] = r[2 * cl + 1];
     }

@@ -1,6 +1,6 @@
 __all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV',
            'CalibratedSVC', 'PairwiseCoupledSVC', 'OneClassSVM', 'one_class_nu_path', 'NuSVC', 'NuSVR',
-           'nu_svc_path', 'nu_svr_path', 'OneVsOneNuSVC', 'ovo_nu_svc_path']
+           'nu_svc_path', 'nu_svr_path', 'OneVsOneNuSVC', 'ovo_nu_svc_path', 'NuSVCGridSearchCV', 'NuSVRGridSearchCV']
 
 from ._base import SVM, SVC, SVR
 from .multiclass import OneVsRestSVC
@@ -12,3 +12,4 @@ from .coupling import PairwiseCoupledSVC
 from .oneclass import OneClassSVM, one_class_nu_path
 from .nu import NuSVC, NuSVR, nu_svc_path, nu_svr_path
 from .nu_ovo import OneVsOneNuSVC, ovo_nu_svc_path
+from .nu_search import NuSVCGridSearchCV, NuSVRGridSearchCV

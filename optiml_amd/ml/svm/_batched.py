@@ -219,6 +219,7 @@ class _DeviceSimplex2Solver(_DeviceMultiSolver):
         n = problem.dims()[1]
         if m != (2 * n if S is None else n):   # (the library reads k x m entries of UB, q and x0)
             raise ValueError('UB has %d columns, expected %d' % (m, 2 * n if S is None else n))
+        self._rows = n
         self._layout = _lib.SX_PAIRED if S is None else _lib.SX_LABELS
         self._S = None if S is None else _lib.as_f64(S, k * m, 'S')
         self._mass = _lib.as_f64(mass, 2 * k, 'mass')
@@ -241,6 +242,22 @@ class _DeviceSimplex2Solver(_DeviceMultiSolver):
                                                          n_free.ctypes.data_as(i64)))
         return r1, r2, n_sv, n_free
 
+    def heldout(self, y):
+        """(r1, r2, n_sv, n_free, n_held, n_correct, sse) of the columns as they stand (`bq_msolver_simplex2_heldout`): `offsets()`'s
+        four, and per column (k entries each) the rows whose box is 0 (on both halves), how many of them the column's NuSVC predicts
+        as y says (LABELS; y: the n labels +-1) and the squared error of its NuSVR's predictions on them (PAIRED; y: the n
+        targets).  The count is 0 for PAIRED, the squared error 0 for LABELS.  The solver must have run; a
+        `_DeviceSimplexPairSolver` is refused."""
+        y = _lib.as_f64(y, self._rows, 'y')
+        r1, r2, sse = np.empty(self.k), np.empty(self.k), np.empty(self.k)
+        n_sv, n_free = np.empty((self.k, 2), dtype=np.int64), np.empty((self.k, 2), dtype=np.int64)
+        n_held, n_correct = np.empty(self.k, dtype=np.int64), np.empty(self.k, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        _lib.check(self._lib.bq_msolver_simplex2_heldout(self._h, _lib.ptr(y), _lib.ptr(r1), _lib.ptr(r2), n_sv.ctypes.data_as(i64),
+                                                         n_free.ctypes.data_as(i64), n_held.ctypes.data_as(i64),
+                                                         n_correct.ctypes.data_as(i64), _lib.ptr(sse)))
+        return r1, r2, n_sv, n_free, n_held, n_correct, sse
+
 
 class _DeviceSimplexPairSolver(_DeviceSimplex2Solver):
     """`bq_msolver_create_simplex2_pairs`: k two-group columns on a class-sorted 'plain' problem of n rows with the pair-routed
@@ -254,6 +271,7 @@ class _DeviceSimplexPairSolver(_DeviceSimplex2Solver):
         n = problem.dims()[1]
         if m != n:   # (the library reads k x n entries of UB and x0)
             raise ValueError('UB has %d columns, expected %d' % (m, n))
+        self._rows = n
         self._ct, self._pr = _lib.as_i32(cls_tiles), _pair_array(pairs)
         if self._pr.size != 2 * k:
             raise ValueError('%d pairs for %d columns' % (self._pr.size // 2, k))
