@@ -61,6 +61,7 @@ extern "C" {
 /* (still 3: bq_msolver_create_simplex2 and bq_msolver_simplex2_offsets were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_simplex2_pairs was added; nothing existing changed) */
 /* (still 3: bq_msolver_simplex2_heldout was added; nothing existing changed) */
+/* (still 3: bq_ovo_vote and bq_msolver_pairs_vote_heldout were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -540,6 +541,35 @@ int bq_msolver_svc_heldout(bq_msolver *s, int ncal, const int *cal_of, double *i
 int bq_msolver_pairs_heldout(bq_msolver *s, const unsigned char *data_row, int ncal, const int *cal_of, double *intercept,
                              int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos, int64_t *n_neg,
                              int *flags, double *dec);
+
+/* ---- one-vs-one vote (sklearn OneVsOneClassifier.predict: multiclass.py _ovr_decision_function and argmax, once per test row; a
+ * GridSearchCV over a one-vs-one SVC evaluates it on every fold's held-out rows) --------------------------------------------------
+ * bq_ovo_vote: t rows of P = ncls (ncls - 1) / 2 pair decision values, D t x P row-major (host), the pairs in the order (0,1),
+ * (0,2), ..., (1,2), ..., positive towards the pair's larger class.  Per row, for k = 0..P-1 over the pairs (i, j) in that order:
+ * conf[i] -= D[k]; conf[j] += D[k]; votes[D[k] > 0 ? j : i] += 1; then Y[c] = votes[c] + conf[c] / (3 (|conf[c]| + 1)), evaluated
+ * without fused multiply-adds and with IEEE division, so Y has the bits of the NumPy statements.  pred[row] is np.argmax of the row's
+ * Y: the first NaN if there is one, else the first maximum.  With ncls = 2 that is OneVsOneSVC.predict's class, 1 exactly when
+ * Y[1] > 0.  pred: t ints; Y: NULL, or t x ncls, which receives the decision matrix.  One thread per row, no atomics: a row's
+ * result depends on that row alone.  ncls < 2, ncls > 64, t < 1 or a NULL ctx / D / pred: BQ_ERR_BADARG, before any device call. */
+int bq_ovo_vote(bq_ctx *ctx, int ncls, int64_t t, const double *D, int *pred, double *Y);
+/* Held-out accuracy of the (candidate, fold) groups of a bq_msolver_create_pairs solver (any other solver: BQ_ERR_BADARG), from its
+ * state on the device, after any run: sklearn GridSearchCV's per-fold score of a one-vs-one SVC, and no columns x n array crosses
+ * the bus.  group_of: k ints in [0, ngroups); every group holds every pair of the ncls classes exactly once, so k = ngroups x P
+ * (else BQ_ERR_BADARG).  data_row: n bytes, 1 a data row, 0 a ghost row.  held: ngroups x n bytes, 1 a row the group scores; such a
+ * row must be a data row and must have UB = 0 in every column of its group — it was not trained on — else BQ_ERR_BADARG (checked
+ * on the host against the solver's copy of the boxes; a box is 0 on ghost rows and on the rows of other classes too, so the held-out
+ * rows cannot be read off the boxes).
+ * Per column: coef, n_sv and intercept exactly as bq_msolver_svc_heldout forms them (n_sv = 0: NaN), with u = K coef by the
+ * 16-column product, every column in its own slot, live or not, in scratch of the call's own — u on ALL rows, where the routed
+ * product leaves 0 outside the pair's classes.
+ * Per group: n_held, the held rows; every held row votes as bq_ovo_vote's rows do on conf_k = u_k[row] + intercept_k over the
+ * group's P columns in pair order; n_correct, the held rows whose predicted class is the class whose tile rows (cls_tiles) hold the
+ * row; a group with a NaN intercept reports n_correct = -1 (a failed fit).  pred: NULL, or ngroups x n ints, the predicted class on
+ * the held rows and -1 elsewhere.  Integer sums in a fixed order: a group's results have the same bits alone, at any position and in
+ * any batch.  The solver's state, buffers and liveness are untouched: a later run continues as without the call. */
+int bq_msolver_pairs_vote_heldout(bq_msolver *s, const unsigned char *data_row, int ngroups, const int *group_of,
+                                  const unsigned char *held, double *intercept, int64_t *n_sv, int64_t *n_held,
+                                  int64_t *n_correct, int *pred);
 
 /* ---- checkpoint / resume (SURVEY 5 "checkpoint / resume") -------------------------------------------------------
  * What the reference's loop holds at the TOP of an iteration, so that a run which was stopped (max_iter, a callback's

@@ -142,6 +142,9 @@ PROTOTYPES = {
                                          C.POINTER(_i64), _ip, _dp]),
     'bq_msolver_pairs_heldout': (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip, _dp,
                                            C.POINTER(_i64), C.POINTER(_i64), _ip, _dp]),
+    'bq_ovo_vote': (C.c_int, [_vp, C.c_int, _i64, _dp, _ip, _dp]),
+    'bq_msolver_pairs_vote_heldout': (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int, _ip, C.POINTER(C.c_ubyte), _dp, C.POINTER(_i64),
+                                                C.POINTER(_i64), C.POINTER(_i64), _ip]),
     'bq_msolver_create_pairs': (C.c_int, [_vp, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _i64, C.c_double,
                                           C.POINTER(_vp)]),
     'bq_al_solver_create': (C.c_int, [_vp, C.POINTER(AlParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),

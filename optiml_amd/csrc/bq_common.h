@@ -421,6 +421,10 @@ int bq_launch_pairs_all_live(const bq_pairs_plan *pl, hipStream_t st);
 // the plan's device copies of cls_tiles (ncls + 1) and pairs (2 m)
 const int *bq_pairs_plan_tiles(const bq_pairs_plan *pl);
 const int *bq_pairs_plan_pairs(const bq_pairs_plan *pl);
+// the plan's class count and its host copies of the same two arrays
+int bq_pairs_plan_ncls(const bq_pairs_plan *pl);
+const int *bq_pairs_plan_host_tiles(const bq_pairs_plan *pl);
+const int *bq_pairs_plan_host_pairs(const bq_pairs_plan *pl);
 
 // the refusal of what takes one rank and the resident packed lower triangle; `subject` heads the sentence, `detail` ends it
 static inline int bq_need_resident_panel(const bq_problem *p, const char *subject, const char *detail = "") {

@@ -5,10 +5,14 @@
 // cross-validated SVR search.  bq_msolver_svc_heldout / _pairs_heldout: the intercept, the held-out decision values and their Platt
 // fit (bq_platt.hip) per calibrator.  bq_msolver_simplex_offsets / _simplex2_offsets: the offsets of the nu-one-class and of the
 // two-group (nu-SVC / nu-SVR) columns (bq_simplex.hip).  bq_msolver_simplex2_heldout: those offsets and the held-out accuracy
-// (nu-SVC) or squared error (nu-SVR) of a column of a cross-validated nu-search.
+// (nu-SVC) or squared error (nu-SVR) of a column of a cross-validated nu-search.  bq_msolver_pairs_vote_heldout: the intercepts of
+// the pair columns of a cross-validated one-vs-one search, their decision values on ALL rows (the 16-column product, not the routed
+// one), the one-vs-one vote of every held-out row (bq_vote.h) and the held-out accuracy per (candidate, fold).
 #include "bq_msolver.h"
 #include "bq_scratch.h"
+#include "bq_vote.h"
 
+#include <algorithm>
 #include <cmath>
 
 static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
@@ -457,4 +461,157 @@ extern "C" int bq_msolver_pairs_heldout(bq_msolver *m, const unsigned char *data
     BQ_ARG(m && data_row && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
     BQ_ARG(m->plan != nullptr && !m->held.empty(), "held-out calibration of pairs takes a solver of bq_msolver_create_pairs");
     return msolver_heldout(m, data_row, ncal, cal_of, intercept, n_sv, A, B, iters, loss, n_pos, n_neg, flags, dec);
+}
+
+// bq_msolver_pairs_vote_heldout, the rows [64 blockIdx.x, + 64) of group blockIdx.y, one thread per row.  A held row (held: ngroups x
+// n) votes over the group's P columns in pair order (col_of: ngroups x P, the column of the group's pair q) with the decision value
+// out[column][row] + b[column] and writes its class to pred (ngroups x n); every other row writes -1.  A workgroup's 64 rows lie in
+// one tile row, so in one class (ct: the classes' tile rows): the wave counts its held rows and those whose vote is that class into
+// part[group][block][0 / 1].  Integer counts of ballots: no atomics, nothing of another group
+__global__ __launch_bounds__(BQ_VOTE_ROWS) void mvote_kernel(int ncls, long long n, const double *__restrict__ out, int64_t ldw,
+                                                             const double *__restrict__ b, const int *__restrict__ col_of,
+                                                             const int *__restrict__ ct, const unsigned char *__restrict__ held,
+                                                             int *__restrict__ pred, int *__restrict__ part) {
+    extern __shared__ double vote_lds[];
+    const int g = blockIdx.y, tid = threadIdx.x;
+    const long long i = (long long)blockIdx.x * BQ_VOTE_ROWS + tid;
+    const int *cols = col_of + (long long)g * (ncls * (ncls - 1) / 2);
+    const bool h = i < n && held[(long long)g * n + i] != 0;
+    int p = -1;
+    if (h) {
+        const double *u = out + i;
+        p = bq_ovo_vote_row(ncls, [=](int k) { return u[cols[k] * ldw] + b[cols[k]]; }, vote_lds, tid, nullptr);
+    }
+    if (i < n) pred[(long long)g * n + i] = p;
+    const int tile = (int)(((long long)blockIdx.x * BQ_VOTE_ROWS) / BQ_SYM_TILE);
+    int cls = 0;
+    while (cls + 1 < ncls && ct[cls + 1] <= tile) ++cls;
+    const unsigned long long hm = __ballot(h), rm = __ballot(h && p == cls);
+    if (tid == 0) {
+        int *dst = part + 2 * ((long long)g * gridDim.x + blockIdx.x);
+        dst[0] = __popcll(hm);
+        dst[1] = __popcll(rm);
+    }
+}
+
+// group blockIdx.x: the sums of mvote_kernel's nblk pairs of counts (thread t the blocks t, t + 1024, ... ascending, then a fixed
+// tree of integers) -> n_held, n_correct; a NaN among the intercepts of the group's P columns -> n_correct = -1
+__global__ __launch_bounds__(1024) void mvote_count_kernel(int P, int nblk, const int *__restrict__ part, const double *__restrict__ b,
+                                                           const int *__restrict__ col_of, long long *__restrict__ n_held,
+                                                           long long *__restrict__ n_correct) {
+    __shared__ int sh[1024], sr[1024], sb[1024];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    int h = 0, r = 0, bad = 0;
+    for (int j = tid; j < nblk; j += 1024) {
+        h += part[2 * ((long long)g * nblk + j)];
+        r += part[2 * ((long long)g * nblk + j) + 1];
+    }
+    for (int q = tid; q < P; q += 1024) bad |= std::isnan(b[col_of[(long long)g * P + q]]) ? 1 : 0;
+    sh[tid] = h;
+    sr[tid] = r;
+    sb[tid] = bad;
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if (tid < st) {
+            sh[tid] += sh[tid + st];
+            sr[tid] += sr[tid + st];
+            sb[tid] |= sb[tid + st];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        n_held[g] = sh[0];
+        n_correct[g] = sb[0] ? -1 : sr[0];
+    }
+}
+
+extern "C" int bq_msolver_pairs_vote_heldout(bq_msolver *m, const unsigned char *data_row, int ngroups, const int *group_of,
+                                             const unsigned char *held, double *intercept, int64_t *n_sv, int64_t *n_held,
+                                             int64_t *n_correct, int *pred) {
+    BQ_ARG(m && data_row && group_of && held && intercept && n_sv && n_held && n_correct, "NULL argument");
+    BQ_ARG(m->method == BQ_M_PGFW && m->plan != nullptr && !m->held.empty(),
+           "the held-out vote takes a solver of bq_msolver_create_pairs");
+    bq_problem *p = m->p;
+    bq_ctx *c = p->ctx;
+    const int k = m->k, ncls = bq_pairs_plan_ncls(m->plan);
+    const int64_t n = p->n;
+    const int P = ncls * (ncls - 1) / 2;
+    BQ_ARG(ncls <= BQ_VOTE_MAX_CLS, "the one-vs-one vote takes at most 64 classes");
+    BQ_ARG(ngroups >= 1 && ngroups <= 65535 && (int64_t)ngroups * P == k, "the columns must be ngroups x the ncls (ncls - 1) / 2 pairs");
+    const int *hp = bq_pairs_plan_host_pairs(m->plan), *hct = bq_pairs_plan_host_tiles(m->plan);
+    std::vector<int> col_of((size_t)k, -1);   // ngroups x P: the column of (group, pair number in ovo_pairs order)
+    for (int cl = 0; cl < k; ++cl) {
+        BQ_ARG(group_of[cl] >= 0 && group_of[cl] < ngroups, "group_of entries are groups in [0, ngroups)");
+        const int a = hp[2 * cl], b = hp[2 * cl + 1];
+        int &slot = col_of[(size_t)group_of[cl] * P + (a * ncls - a * (a + 1) / 2 + (b - a - 1))];
+        BQ_ARG(slot < 0, "a group must hold every pair exactly once");
+        slot = cl;
+    }   // (k = ngroups x P columns in k distinct slots: every slot is filled)
+    // a held row is a data row that no column of its group trained on: UB = 0 there.  A column's box is 0 outside its pair's classes
+    // (checked at creation), and m->held has it on the rows of the pair's classes
+    for (int g = 0; g < ngroups; ++g) {
+        const unsigned char *hg = held + (size_t)g * (size_t)n;
+        for (int cls = 0; cls < ncls; ++cls) {
+            const int64_t r0 = (int64_t)hct[cls] * BQ_SYM_TILE, r1 = std::min<int64_t>((int64_t)hct[cls + 1] * BQ_SYM_TILE, n);
+            bool any = false;
+            for (int64_t i = r0; i < r1; ++i) {
+                BQ_ARG(!hg[i] || data_row[i], "a held row must be a data row");
+                any |= hg[i] != 0;
+            }
+            if (!any) continue;
+            for (int q = 0; q < P; ++q) {
+                const int cl = col_of[(size_t)g * P + q];
+                if (hp[2 * cl] != cls && hp[2 * cl + 1] != cls) continue;
+                const unsigned char *zero = m->held.data() + (size_t)cl * (size_t)n;
+                for (int64_t i = r0; i < r1; ++i) BQ_ARG(!hg[i] || zero[i], "a held row must have UB = 0 in every column of its group");
+            }
+        }
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // The product's own scratch: symmw_tiles_kernel stages all 16 slots of a chunk whatever is live, and a pair solver's W / out have
+    // round_up(k, 4) slots and its slab the routed product's layout
+    const int64_t slots = bq_round_up(k, BQ_SYMMW_CK), ldw = m->ldw;
+    const int nblk = (int)((n + BQ_VOTE_ROWS - 1) / BQ_VOTE_ROWS);
+    bq_scratch mem;   // freed after the closing sync
+    double *W = mem.dev<double>(ldw * slots), *OUT = mem.dev<double>(ldw * slots), *slab = mem.dev<double>(bq_symmw_slab_len(p->nb));
+    double *db = mem.dev<double>(k);
+    long long *dnsv = mem.dev<long long>(k), *dnheld = mem.dev<long long>(ngroups), *dnright = mem.dev<long long>(ngroups);
+    int *dcal = mem.dev<int>(k), *dcol = mem.dev<int>(k), *dpred = mem.dev<int>((size_t)ngroups * (size_t)n);
+    int *part = mem.dev<int>((size_t)2 * ngroups * nblk);
+    unsigned char *dheld = mem.dev<unsigned char>((size_t)ngroups * (size_t)n);
+    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
+    hipError_t e = mem.error();
+    if (e == hipSuccess) e = hipMemsetAsync(W, 0, sizeof(double) * ldw * slots, st);
+    if (e == hipSuccess) e = hipMemsetAsync(OUT, 0, sizeof(double) * ldw * slots, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dcal, 0xff, sizeof(int) * k, st);   // -1: mheldout_kernel stops after the intercept
+    if (e == hipSuccess) e = hipMemcpyAsync(dcol, col_of.data(), sizeof(int) * k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dheld, held, (size_t)ngroups * (size_t)n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
+    int rc = BQ_OK;
+    if (e != hipSuccess) {
+        bq_set_error("held-out vote setup failed: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    if (rc == BQ_OK) {
+        mcoef_kernel<false><<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, W, ldw);
+        rc = bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count);   // u on ALL rows: the routed product leaves 0 outside a pair's classes
+    }
+    if (rc == BQ_OK) {
+        mheldout_kernel<<<k, 1024, 0, st>>>(m->epi, OUT, ldw, nullptr, nullptr, nullptr, dcal, nullptr, nullptr, db, dnsv);
+        mvote_kernel<<<dim3((unsigned)nblk, (unsigned)ngroups), BQ_VOTE_ROWS, bq_vote_lds_bytes(ncls), st>>>(
+            ncls, (long long)n, OUT, ldw, db, dcol, bq_pairs_plan_tiles(m->plan), dheld, dpred, part);
+        mvote_count_kernel<<<ngroups, 1024, 0, st>>>(P, nblk, part, db, dcol, dnheld, dnright);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * ngroups, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(n_correct, dnright, sizeof(int64_t) * ngroups, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && pred) e = hipMemcpyAsync(pred, dpred, sizeof(int) * (size_t)ngroups * (size_t)n, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            bq_set_error("held-out vote: %s", hipGetErrorString(e));
+            rc = BQ_ERR_HIP;
+        }
+    }
+    return bq_ctx_sync_after(c, rc);   // held, k, the tables and the results are the caller's and this frame's
 }

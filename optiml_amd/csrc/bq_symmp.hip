@@ -433,6 +433,9 @@ int64_t bq_pairs_slab_len(const bq_pairs_plan *pl) { return pl->slab_len; }
 
 const int *bq_pairs_plan_tiles(const bq_pairs_plan *pl) { return pl->dct; }
 const int *bq_pairs_plan_pairs(const bq_pairs_plan *pl) { return pl->dpairs; }
+int bq_pairs_plan_ncls(const bq_pairs_plan *pl) { return pl->ncls; }
+const int *bq_pairs_plan_host_tiles(const bq_pairs_plan *pl) { return pl->ct.data(); }
+const int *bq_pairs_plan_host_pairs(const bq_pairs_plan *pl) { return pl->pairs.data(); }
 
 // every pair live: the plan's start state (and what a one-off product takes)
 static int plan_all_live(bq_pairs_plan *pl, hipStream_t st) {

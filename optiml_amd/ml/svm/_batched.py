@@ -119,6 +119,31 @@ class _DeviceMultiSolver:
             fit['dec'] = dec
         return b, n_sv, fit
 
+    def vote_heldout_pairs(self, data_row, group_of, held, predictions=False):
+        """The (candidate, fold) groups of a pair solver's columns as they stand (`_DevicePairSolver`,
+        `bq_msolver_pairs_vote_heldout`): group_of, the group of every column, each group holding every class pair once; held,
+        groups x n, 1 on the rows a group scores (data rows none of its columns trained on).  Returns (intercept, n_sv, n_held,
+        n_correct[, pred]): per column SVC.fit's intercept and support count (NaN without a support vector), per group the held rows
+        and those whose one-vs-one vote is their class (-1 for a group with a NaN intercept) and, with `predictions`, groups x n
+        predicted classes (-1 on the rows a group does not score)."""
+        group_of = _lib.as_i32(group_of, self.k, 'group_of')
+        data_row = np.ascontiguousarray(data_row, dtype=np.uint8)
+        held = np.ascontiguousarray(np.atleast_2d(held), dtype=np.uint8)
+        if data_row.shape != (self.n,):
+            raise ValueError('data_row must have %d entries' % self.n)
+        groups = held.shape[0]
+        if held.shape != (groups, self.n):
+            raise ValueError('held must be groups x %d' % self.n)
+        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
+        n_held, n_correct = np.empty(groups, dtype=np.int64), np.empty(groups, dtype=np.int64)
+        pred = np.empty((groups, self.n), dtype=np.int32) if predictions else None
+        i64, u8 = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+        _lib.check(self._lib.bq_msolver_pairs_vote_heldout(self._h, data_row.ctypes.data_as(u8), groups, _lib.iptr(group_of),
+                                                           held.ctypes.data_as(u8), _lib.ptr(b), n_sv.ctypes.data_as(i64),
+                                                           n_held.ctypes.data_as(i64), n_correct.ctypes.data_as(i64),
+                                                           _lib.iptr(pred)))
+        return (b, n_sv, n_held, n_correct, pred) if predictions else (b, n_sv, n_held, n_correct)
+
     def close(self):
         if self._h:
             self._lib.bq_msolver_destroy(self._h)
