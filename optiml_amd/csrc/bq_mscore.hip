@@ -1,7 +1,8 @@
 // What scores a finished batch of the batched solver (bq_msolver.hip): from every column's point, its coefficients to the column's
 // own slot (not pos[]: every column is scored, live or not), one product in which every column is live, and per column a workgroup
 // of 1024 threads that sums in a fixed order (thread t the rows t, t + 1024, ... ascending, then a fixed tree: no atomics, and nothing
-// of another column enters).  bq_msolver_svr_heldout: the intercept and the held-out squared error of a column of a
+// of another column enters; mscore_sum).  The host side of every held-out call is one bq_score_pass (bq_score_pass.h): argument
+// checks, requests, launches, finish.  bq_msolver_svr_heldout: the intercept and the held-out squared error of a column of a
 // cross-validated SVR search.  bq_msolver_svc_heldout / _pairs_heldout: the intercept, the held-out decision values and their Platt
 // fit (bq_platt.hip) per calibrator.  bq_msolver_simplex_offsets / _simplex2_offsets: the offsets of the nu-one-class and of the
 // two-group (nu-SVC / nu-SVR) columns (bq_simplex.hip).  bq_msolver_simplex2_heldout: those offsets and the held-out accuracy
@@ -9,7 +10,7 @@
 // the pair columns of a cross-validated one-vs-one search, their decision values on ALL rows (the 16-column product, not the routed
 // one), the one-vs-one vote of every held-out row (bq_vote.h) and the held-out accuracy per (candidate, fold).
 #include "bq_msolver.h"
-#include "bq_scratch.h"
+#include "bq_score_pass.h"
 #include "bq_vote.h"
 
 #include <algorithm>
@@ -27,109 +28,104 @@ __global__ __launch_bounds__(256) void mcoef_kernel(const bq_epilogue *__restric
     W[blockIdx.y * ldw + i] = sv ? bq_mcol_input(e, i, SVR) : 0.0;
 }
 
-// the fixed tree over the workgroup's 1024 partial sums and counts; every thread returns with the totals in s[0], c[0]
-__device__ inline void msvr_tree(double *s, int *c, int tid) {
+// The workgroup's totals of its 1024 threads' partial sum s and count cnt, handed back to every thread in s and cnt: the two LDS
+// stores, the barrier, the fixed tree (512, 256, ..., 1), the read of the totals, and the barrier after which the next pass may
+// overwrite them.  Thread t's partials are of the rows t, t + 1024, ... in ascending order: no atomics, and nothing of another
+// column enters
+__device__ inline void mscore_sum(int tid, double &s, int &cnt) {
+    __shared__ double sd[1024];
+    __shared__ int sc[1024];
+    sd[tid] = s;
+    sc[tid] = cnt;
     __syncthreads();
     for (int st = 512; st > 0; st >>= 1) {
         if (tid < st) {
-            s[tid] += s[tid + st];
-            c[tid] += c[tid + st];
+            sd[tid] += sd[tid + st];
+            sc[tid] += sc[tid + st];
         }
         __syncthreads();
     }
+    s = sd[0];
+    cnt = sc[0];
+    __syncthreads();   // every thread has read the totals: the next pass may overwrite them
 }
 
-// bq_msolver_svr_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1, the support rows (x+ or x- above 1e-6):
-// S = sum (y - u), n_sv, b = (S - epsilon) / n_sv in svr_intercept's order.  Pass 2, the held-out rows (ub = 0 on both halves):
-// sse = sum (y - (u + b))^2, n_held.  Thread t sums the rows t, t + 1024, ... in ascending order, then the tree: no atomics, and
-// nothing of another column enters.  n_sv = 0: intercept = sse = NaN.
+// a row the column does not train on: ub = 0, on both halves when the column has 2n variables
+template <class COL>
+__device__ inline bool mscore_held(const COL &c, long long i, bool both) {
+    return c.ub[i] == 0.0 && (!both || c.ub[c.n + i] == 0.0);
+}
+
+// the first pass of the held-out kernels of a column, u = K coef, t its targets (SVC: the labels e.sgn; SVR: y): over the support
+// rows (x above 1e-6; SVR: on either half) S = sum (t - u) and nsv, summed by mscore_sum; returns to every thread
+// b = (S - epsilon) / nsv in intercept()'s / svr_intercept()'s order (svm/_batched.py; SVC passes 0.0, and S - 0.0 has the bits of
+// S), NaN for nsv = 0
+template <bool SVR>
+__device__ inline double mscore_intercept(const bq_epilogue &e, const double *__restrict__ u, const double *__restrict__ t,
+                                          double epsilon, int tid, int &nsv) {
+    const long long n = e.n;
+    double s = 0.0;
+    nsv = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool sv = SVR ? (e.x[i] > 1e-6 || e.x[n + i] > 1e-6) : e.x[i] > 1e-6;
+        s += sv ? t[i] - u[i] : 0.0;
+        nsv += sv ? 1 : 0;
+    }
+    mscore_sum(tid, s, nsv);
+    s -= epsilon;
+    return nsv > 0 ? s / (double)nsv : NAN;
+}
+
+// bq_msolver_svr_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1: mscore_intercept<true>.  Pass 2, the held-out
+// rows (mscore_held on both halves): sse = sum (y - (u + b))^2, n_held, summed by mscore_sum.  n_sv = 0: intercept = sse = NaN.
 __global__ __launch_bounds__(1024) void msvr_score_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out, int64_t ldw,
                                                           const double *__restrict__ y, const double *__restrict__ epsilon,
                                                           double *__restrict__ intercept, long long *__restrict__ n_sv,
                                                           double *__restrict__ sse, long long *__restrict__ n_held) {
-    __shared__ double sd[1024];
-    __shared__ int sc[1024];
     const bq_epilogue &e = epi[blockIdx.x];
     const double *u = out + blockIdx.x * ldw;
     const int tid = threadIdx.x;
     const long long n = e.n;
+    int nsv;
+    const double b = mscore_intercept<true>(e, u, y, epsilon[blockIdx.x], tid, nsv);
     double s = 0.0;
     int cnt = 0;
     for (long long i = tid; i < n; i += 1024) {
-        const bool sv = e.x[i] > 1e-6 || e.x[n + i] > 1e-6;
-        s += sv ? y[i] - u[i] : 0.0;
-        cnt += sv ? 1 : 0;
-    }
-    sd[tid] = s;
-    sc[tid] = cnt;
-    msvr_tree(sd, sc, tid);
-    const int nsv = sc[0];
-    double b = sd[0];
-    b -= epsilon[blockIdx.x];
-    b = nsv > 0 ? b / (double)nsv : NAN;
-    __syncthreads();   // sd[0], sc[0] are read: pass 2 may overwrite them
-    s = 0.0;
-    cnt = 0;
-    for (long long i = tid; i < n; i += 1024) {
-        const bool held = e.ub[i] == 0.0 && e.ub[n + i] == 0.0;
+        const bool held = mscore_held(e, i, true);
         const double r = y[i] - (u[i] + b);
         s += held ? r * r : 0.0;
         cnt += held ? 1 : 0;
     }
-    sd[tid] = s;
-    sc[tid] = cnt;
-    msvr_tree(sd, sc, tid);
+    mscore_sum(tid, s, cnt);
     if (tid == 0) {
         intercept[blockIdx.x] = b;
         n_sv[blockIdx.x] = nsv;
-        sse[blockIdx.x] = sd[0];   // NaN with b
-        n_held[blockIdx.x] = sc[0];
+        sse[blockIdx.x] = s;   // NaN with b
+        n_held[blockIdx.x] = cnt;
     }
 }
 
-// the first pass of the held-out kernels of an SVC column, u = K coef: over the support rows (x above 1e-6) S = sum (y - u) and
-// n_sv, summed as msvr_score_kernel sums; returns b = S / n_sv in intercept()'s order (svm/_batched.py; n_sv = 0: NaN) to every
-// thread and writes both figures
-__device__ inline double msvc_intercept(const bq_epilogue &e, const double *__restrict__ u, double *sd, int *sc, int tid,
-                                        double *__restrict__ intercept, long long *__restrict__ n_sv) {
-    const long long n = e.n;
-    double s = 0.0;
-    int cnt = 0;
-    for (long long i = tid; i < n; i += 1024) {
-        const bool sv = e.x[i] > 1e-6;
-        s += sv ? e.sgn[i] - u[i] : 0.0;
-        cnt += sv ? 1 : 0;
-    }
-    sd[tid] = s;
-    sc[tid] = cnt;
-    msvr_tree(sd, sc, tid);
-    const int nsv = sc[0];
-    const double b = nsv > 0 ? sd[0] / (double)nsv : NAN;
-    if (tid == 0) {
-        *intercept = b;
-        *n_sv = nsv;
-    }
-    return b;
-}
-
-// bq_msolver_svc_heldout and bq_msolver_pairs_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1: msvc_intercept.
-// Pass 2, the held-out rows: the decision value u + b and the label y to row cal_of[column] of D and L (row stride n; zeroed by the
-// caller; the columns of a calibrator hold out disjoint rows, so no two workgroups write one entry).  n_sv = 0: b = NaN.
-// The held-out rows are those with ub = 0 of [0, n) (pairs null), or, for column = pair (a, b) of a class-sorted panel, the data rows
-// (data_row: 1; a ghost row: 0) with ub = 0 of the tile rows of a and of b — ub is 0 on every row of another class too, and such a
-// row is in no pair's sample
+// bq_msolver_svc_heldout and bq_msolver_pairs_heldout, column blockIdx.x, u = out[:, column] = K coef.  Pass 1:
+// mscore_intercept<false>.  Pass 2, the held-out rows: the decision value u + b and the label y to row cal_of[column] of D and L
+// (row stride n; zeroed by the caller; the columns of a calibrator hold out disjoint rows, so no two workgroups write one entry).
+// n_sv = 0: b = NaN.  The held-out rows are those with ub = 0 of [0, n) (pairs null), or, for column = pair (a, b) of a class-sorted
+// panel, the data rows (data_row: 1; a ghost row: 0) with ub = 0 of the tile rows of a and of b — ub is 0 on every row of another
+// class too, and such a row is in no pair's sample
 __global__ __launch_bounds__(1024) void mheldout_kernel(const bq_epilogue *__restrict__ epi, const double *__restrict__ out,
                                                         int64_t ldw, const int *__restrict__ pairs, const int *__restrict__ ct,
                                                         const unsigned char *__restrict__ data_row, const int *__restrict__ cal_of,
                                                         double *__restrict__ D, double *__restrict__ L, double *__restrict__ intercept,
                                                         long long *__restrict__ n_sv) {
-    __shared__ double sd[1024];
-    __shared__ int sc[1024];
     const bq_epilogue &e = epi[blockIdx.x];
     const double *u = out + blockIdx.x * ldw;
     const int tid = threadIdx.x;
     const long long n = e.n;
-    const double b = msvc_intercept(e, u, sd, sc, tid, intercept + blockIdx.x, n_sv + blockIdx.x);
+    int nsv;
+    const double b = mscore_intercept<false>(e, u, e.sgn, 0.0, tid, nsv);
+    if (tid == 0) {
+        intercept[blockIdx.x] = b;
+        n_sv[blockIdx.x] = nsv;
+    }
     const int cal = cal_of[blockIdx.x];
     if (cal < 0) return;
     double *d = D + (long long)cal * n, *l = L + (long long)cal * n;
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(1024) void mheldout_kernel(const bq_epilogue *__res
             r1 = (long long)ct[cls + 1] * BQ_SYM_TILE < n ? (long long)ct[cls + 1] * BQ_SYM_TILE : n;
         }
         for (long long i = r0 + tid; i < r1; i += 1024) {
-            if ((pairs == nullptr || data_row[i]) && e.ub[i] == 0.0) {
+            if ((pairs == nullptr || data_row[i]) && mscore_held(e, i, false)) {
                 d[i] = u[i] + b;
                 l[i] = e.sgn[i];
             }
@@ -171,6 +167,14 @@ static int msolver_sx_offsets(bq_msolver *m, double *r, int64_t *n_sv, int64_t *
     return bq_ctx_sync_after(c, rc);
 }
 
+// the interleaved offsets (r1, r2) per column, as the device keeps them, into the caller's two arrays
+static void msolver_sx_split(const std::vector<double> &r, double *r1, double *r2) {
+    for (size_t cl = 0; cl < r.size() / 2; ++cl) {
+        r1[cl] = r[2 * cl];
+        r2[cl] = r[2 * cl + 1];
+    }
+}
+
 extern "C" int bq_msolver_simplex_offsets(bq_msolver *m, double *rho, int64_t *n_sv, int64_t *n_free) {
     BQ_ARG(m && rho && n_sv && n_free, "NULL argument");
     BQ_ARG(m->method == BQ_M_SIMPLEX && m->sx_layout == BQ_SX_ONE, "the offsets take a solver of bq_msolver_create_simplex");
@@ -182,10 +186,7 @@ extern "C" int bq_msolver_simplex2_offsets(bq_msolver *m, double *r1, double *r2
     BQ_ARG(m->method == BQ_M_SIMPLEX && m->sx_layout != BQ_SX_ONE, "the offsets take a solver of bq_msolver_create_simplex2");
     std::vector<double> r((size_t)(2 * m->k));
     BQ_TRY(msolver_sx_offsets(m, r.data(), n_sv, n_free));
-    for (int cl = 0; cl < m->k; ++cl) {
-        r1[cl] = r[2 * cl];
-        r2[cl] = r[2 * cl + 1];
-    }
+    msolver_sx_split(r, r1, r2);
     return BQ_OK;
 }
 
@@ -202,25 +203,23 @@ __global__ __launch_bounds__(256) void msx_fold_kernel(const bq_sx_col *__restri
 // bq_msolver_simplex2_heldout, column blockIdx.x, u = out[:, column] = K b; r = the column's two offsets (r1, r2), as
 // sx_offsets_kernel left them.  rho = (r1 - r2) / 2, scale = (r1 + r2) / 2.  Over the held-out rows (LABELS: ub = 0; PAIRED: ub = 0 on
 // both halves): n_held, and LABELS: the rows whose prediction ((u - rho) / scale > 0: +1, else -1; a NaN or a non-positive scale as
-// np.where(decision > 0, ...) takes them) equals y, sse = 0; PAIRED: sse = sum (y - (u - rho))^2, n_correct = 0.  Thread t sums the
-// rows t, t + 1024, ... in ascending order, then msvr_tree: no atomics, and nothing of another column enters
+// np.where(decision > 0, ...) takes them) equals y, sse = 0; PAIRED: sse = sum (y - (u - rho))^2, n_correct = 0.  Summed by
+// mscore_sum, the matches by a second call of it beside a zero sum
 template <bool PAIRED>
 __global__ __launch_bounds__(1024) void msx_score_kernel(const bq_sx_col *__restrict__ cols, const double *__restrict__ out, int64_t ldw,
                                                          const double *__restrict__ y, const double *__restrict__ r,
                                                          long long *__restrict__ n_held, long long *__restrict__ n_correct,
                                                          double *__restrict__ sse) {
-    __shared__ double sd[1024];
-    __shared__ int sc[1024];
     const bq_sx_col &c = cols[blockIdx.x];
     const double *u = out + blockIdx.x * ldw;
     const int tid = threadIdx.x;
     const long long n = c.n;
     const double r1 = r[2 * blockIdx.x], r2 = r[2 * blockIdx.x + 1];
     const double rho = (r1 - r2) / 2, scale = (r1 + r2) / 2;
-    double s = 0.0;
+    double s = 0.0, none = 0.0;
     int held = 0, right = 0;
     for (long long i = tid; i < n; i += 1024) {
-        const bool h = PAIRED ? (c.ub[i] == 0.0 && c.ub[n + i] == 0.0) : c.ub[i] == 0.0;
+        const bool h = mscore_held(c, i, PAIRED);
         if (PAIRED) {
             const double e = y[i] - (u[i] - rho);
             s += h ? e * e : 0.0;
@@ -230,19 +229,12 @@ __global__ __launch_bounds__(1024) void msx_score_kernel(const bq_sx_col *__rest
         }
         held += h ? 1 : 0;
     }
-    sd[tid] = s;
-    sc[tid] = held;
-    msvr_tree(sd, sc, tid);
-    const double total = sd[0];
-    const int nheld = sc[0];
-    __syncthreads();   // sd[0], sc[0] are read: the second tree may overwrite them
-    sd[tid] = 0.0;
-    sc[tid] = right;
-    msvr_tree(sd, sc, tid);
+    mscore_sum(tid, s, held);
+    mscore_sum(tid, none, right);
     if (tid == 0) {
-        n_held[blockIdx.x] = nheld;
-        n_correct[blockIdx.x] = sc[0];
-        sse[blockIdx.x] = total;
+        n_held[blockIdx.x] = held;
+        n_correct[blockIdx.x] = right;
+        sse[blockIdx.x] = s;
     }
 }
 
@@ -264,47 +256,27 @@ extern "C" int bq_msolver_simplex2_heldout(bq_msolver *m, const double *y, doubl
     BQ_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     std::vector<double> r((size_t)(2 * k));   // (r1, r2) per column; split after the closing sync
-    bq_scratch mem;                           // freed after the closing sync
-    double *dy = mem.dev<double>(n), *dsse = mem.dev<double>(k);
-    long long *dnheld = mem.dev<long long>(k), *dnright = mem.dev<long long>(k);
-    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
-    long long *dn = m->sx_counts;   // n_sv, then n_free, 2 k each
-    hipError_t e = mem.error();
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
-    int rc = BQ_OK;
-    if (e != hipSuccess) {
-        bq_set_error("held-out scoring setup failed: %s", hipGetErrorString(e));
-        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
-    }
-    if (rc == BQ_OK) rc = bq_sx_launch_offsets(m->sx_cols, k, m->sx_layout, m->sx_rho, dn, dn + 2 * k, st);
-    if (rc == BQ_OK) {   // u = K b afresh: the solver's g is updated incrementally and holds the unread labels on LABELS held-out rows
+    long long *dn = m->sx_counts;             // n_sv, then n_free, 2 k each
+    bq_score_pass pass("held-out scoring", st);
+    double *dy = pass.in(y, (size_t)n);
+    int *count = pass.columns(k);
+    pass.out_of(r.data(), m->sx_rho, (size_t)(2 * k));
+    pass.out_of(n_sv, dn, (size_t)(2 * k));
+    pass.out_of(n_free, dn + 2 * k, (size_t)(2 * k));
+    long long *dnheld = pass.out<long long>(n_held, k), *dnright = pass.out<long long>(n_correct, k);
+    double *dsse = pass.out<double>(sse, k);
+    if (pass.ready() && pass.step(bq_sx_launch_offsets(m->sx_cols, k, m->sx_layout, m->sx_rho, dn, dn + 2 * k, st))) {
+        // u = K b afresh: the solver's g is updated incrementally and holds the unread labels on LABELS held-out rows
         const dim3 grid((unsigned)((n + 255) / 256), (unsigned)k);
         if (paired) msx_fold_kernel<true><<<grid, 256, 0, st>>>(m->sx_cols, m->W, m->ldw);
         else msx_fold_kernel<false><<<grid, 256, 0, st>>>(m->sx_cols, m->W, m->ldw);
-        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
-    }
-    if (rc == BQ_OK) {
-        if (paired) msx_score_kernel<true><<<k, 1024, 0, st>>>(m->sx_cols, m->out, m->ldw, dy, m->sx_rho, dnheld, dnright, dsse);
-        else msx_score_kernel<false><<<k, 1024, 0, st>>>(m->sx_cols, m->out, m->ldw, dy, m->sx_rho, dnheld, dnright, dsse);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(r.data(), m->sx_rho, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dn, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_free, dn + 2 * k, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_correct, dnright, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(sse, dsse, sizeof(double) * k, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            bq_set_error("held-out scoring: %s", hipGetErrorString(e));
-            rc = BQ_ERR_HIP;
+        if (pass.step(bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count))) {
+            if (paired) msx_score_kernel<true><<<k, 1024, 0, st>>>(m->sx_cols, m->out, m->ldw, dy, m->sx_rho, dnheld, dnright, dsse);
+            else msx_score_kernel<false><<<k, 1024, 0, st>>>(m->sx_cols, m->out, m->ldw, dy, m->sx_rho, dnheld, dnright, dsse);
         }
     }
-    rc = bq_ctx_sync_after(c, rc);   // y, k and the results are the caller's and this frame's
-    if (rc != BQ_OK) return rc;
-    for (int cl = 0; cl < k; ++cl) {
-        r1[cl] = r[2 * cl];
-        r2[cl] = r[2 * cl + 1];
-    }
+    BQ_TRY(bq_ctx_sync_after(c, pass.finish()));   // y and the results are the caller's and this frame's
+    msolver_sx_split(r, r1, r2);
     return BQ_OK;
 }
 
@@ -318,36 +290,17 @@ extern "C" int bq_msolver_svr_heldout(bq_msolver *m, const double *y, const doub
     hipStream_t st = c->stream;
     const int k = m->k;
     const int64_t n = p->n;
-    bq_scratch mem;   // freed after the closing sync
-    double *dy = mem.dev<double>(n), *deps = mem.dev<double>(k), *db = mem.dev<double>(k), *dsse = mem.dev<double>(k);
-    long long *dnsv = mem.dev<long long>(k), *dnheld = mem.dev<long long>(k);
-    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
-    hipError_t e = mem.error();
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(deps, epsilon, sizeof(double) * k, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
-    int rc = BQ_OK;
-    if (e != hipSuccess) {
-        bq_set_error("held-out scoring setup failed: %s", hipGetErrorString(e));
-        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
-    }
-    if (rc == BQ_OK) {
+    bq_score_pass pass("held-out scoring", st);
+    double *dy = pass.in(y, (size_t)n), *deps = pass.in(epsilon, (size_t)k);
+    double *db = pass.out<double>(intercept, k), *dsse = pass.out<double>(sse, k);
+    long long *dnsv = pass.out<long long>(n_sv, k), *dnheld = pass.out<long long>(n_held, k);
+    int *count = pass.columns(k);
+    if (pass.ready()) {
         mcoef_kernel<true><<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, m->W, m->ldw);
-        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+        if (pass.step(bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count)))
+            msvr_score_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dy, deps, db, dnsv, dsse, dnheld);
     }
-    if (rc == BQ_OK) {
-        msvr_score_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, dy, deps, db, dnsv, dsse, dnheld);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(sse, dsse, sizeof(double) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            bq_set_error("held-out scoring: %s", hipGetErrorString(e));
-            rc = BQ_ERR_HIP;
-        }
-    }
-    return bq_ctx_sync_after(c, rc);   // y, epsilon, k and the results are the caller's and this frame's
+    return bq_ctx_sync_after(c, pass.finish());   // y, epsilon and the results are the caller's and this frame's
 }
 
 // bq_msolver_svc_heldout (data_row null: the 16-column product) and bq_msolver_pairs_heldout (the pair-routed product with every
@@ -383,68 +336,39 @@ static int msolver_heldout(bq_msolver *m, const unsigned char *data_row, int nca
     BQ_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t len = (size_t)ncal * (size_t)n;
-    bq_scratch mem;   // freed after the closing sync
-    double *dD = mem.dev<double>(len);
-    unsigned char *drow = data_row ? mem.dev<unsigned char>((size_t)n) : nullptr;
-    double *dL = mem.dev<double>(len), *db = mem.dev<double>(k);
-    long long *dnsv = mem.dev<long long>(k);
-    int *dcal = mem.dev<int>(k);
-    double *dA = mem.dev<double>(ncal), *dB = mem.dev<double>(ncal), *dloss = mem.dev<double>(ncal);
-    long long *dpos = mem.dev<long long>(ncal), *dneg = mem.dev<long long>(ncal);
-    int *diters = mem.dev<int>(ncal), *dflags = mem.dev<int>(ncal);
-    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
-    hipError_t e = mem.error();
-    if (e == hipSuccess && data_row) e = hipMemcpyAsync(drow, data_row, (size_t)n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dD, 0, sizeof(double) * len, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dL, 0, sizeof(double) * len, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dcal, cal_of, sizeof(int) * k, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
-    int rc = BQ_OK;
-    if (e != hipSuccess) {
-        bq_set_error("held-out calibration setup failed: %s", hipGetErrorString(e));
-        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
-    }
-    auto failed = [&](hipError_t err) {   // of a launch or a copy past the set-up
-        if (err == hipSuccess) return;
-        bq_set_error("held-out calibration: %s", hipGetErrorString(err));
-        rc = BQ_ERR_HIP;
-    };
-    if (rc == BQ_OK) {
+    bq_score_pass pass("held-out calibration", st);
+    double *dD = pass.fill<double>(0, len), *dL = pass.fill<double>(0, len);
+    const unsigned char *drow = data_row ? pass.in(data_row, (size_t)n) : nullptr;
+    const int *dcal = pass.in(cal_of, (size_t)k);
+    double *db = pass.out<double>(intercept, k);
+    long long *dnsv = pass.out<long long>(n_sv, k);
+    double *dA = pass.out<double>(A, ncal), *dB = pass.out<double>(B, ncal), *dloss = pass.out<double>(loss, ncal);
+    long long *dpos = pass.out<long long>(n_pos, ncal), *dneg = pass.out<long long>(n_neg, ncal);
+    int *diters = pass.out<int>(iters, ncal), *dflags = pass.out<int>(flags, ncal);
+    pass.out_of(dec, dD, len);
+    int *count = pass.columns(k);
+    if (pass.ready()) {
         mcoef_kernel<false><<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, m->W, m->ldw);
-        failed(hipGetLastError());
+        pass.check(hipGetLastError());
     }
-    if (rc == BQ_OK && m->plan) {
+    if (pass.ok() && m->plan) {
         // every pair live for this product, as bq_problem_gram_matmat_pairs has them; then the liveness of the columns' states
         // again, which is what the last iteration left (bq_launch_pairs_live is a function of the states alone)
-        rc = bq_launch_pairs_all_live(m->plan, st);
-        if (rc == BQ_OK) {
-            rc = bq_launch_symmp(p, m->plan, false, m->W, m->ldw, m->slab, m->out);
+        if (pass.step(bq_launch_pairs_all_live(m->plan, st))) {
+            const int rc = bq_launch_symmp(p, m->plan, false, m->W, m->ldw, m->slab, m->out);
             const int back = bq_launch_pairs_live(m->plan, m->scs, m->nlive, st);   // also when the product could not be launched
-            if (rc == BQ_OK) rc = back;
+            pass.step(rc != BQ_OK ? rc : back);
         }
-    } else if (rc == BQ_OK) {
-        rc = bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count);
+    } else if (pass.ok()) {
+        pass.step(bq_launch_symmw(p, false, m->W, m->ldw, k, m->slab, m->out, count));
     }
-    if (rc == BQ_OK) {
+    if (pass.ok()) {
         mheldout_kernel<<<k, 1024, 0, st>>>(m->epi, m->out, m->ldw, m->plan ? bq_pairs_plan_pairs(m->plan) : nullptr,
                                             m->plan ? bq_pairs_plan_tiles(m->plan) : nullptr, drow, dcal, dD, dL, db, dnsv);
-        failed(hipGetLastError());
+        pass.check(hipGetLastError());
     }
-    if (rc == BQ_OK) rc = bq_launch_platt(ncal, n, dD, dL, dA, dB, diters, dloss, dpos, dneg, dflags, st);
-    if (rc == BQ_OK) {
-        e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(A, dA, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(B, dB, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(loss, dloss, sizeof(double) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_pos, dpos, sizeof(int64_t) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_neg, dneg, sizeof(int64_t) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(iters, diters, sizeof(int) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(flags, dflags, sizeof(int) * ncal, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && dec) e = hipMemcpyAsync(dec, dD, sizeof(double) * len, hipMemcpyDeviceToHost, st);
-        failed(e);
-    }
-    return bq_ctx_sync_after(c, rc);   // cal_of, k and the results are the caller's and this frame's
+    if (pass.ok()) pass.step(bq_launch_platt(ncal, n, dD, dL, dA, dB, diters, dloss, dpos, dneg, dflags, st));
+    return bq_ctx_sync_after(c, pass.finish());   // cal_of and the results are the caller's and this frame's
 }
 
 extern "C" int bq_msolver_svc_heldout(bq_msolver *m, int ncal, const int *cal_of, double *intercept, int64_t *n_sv, double *A,
@@ -573,45 +497,27 @@ extern "C" int bq_msolver_pairs_vote_heldout(bq_msolver *m, const unsigned char 
     // round_up(k, 4) slots and its slab the routed product's layout
     const int64_t slots = bq_round_up(k, BQ_SYMMW_CK), ldw = m->ldw;
     const int nblk = (int)((n + BQ_VOTE_ROWS - 1) / BQ_VOTE_ROWS);
-    bq_scratch mem;   // freed after the closing sync
-    double *W = mem.dev<double>(ldw * slots), *OUT = mem.dev<double>(ldw * slots), *slab = mem.dev<double>(bq_symmw_slab_len(p->nb));
-    double *db = mem.dev<double>(k);
-    long long *dnsv = mem.dev<long long>(k), *dnheld = mem.dev<long long>(ngroups), *dnright = mem.dev<long long>(ngroups);
-    int *dcal = mem.dev<int>(k), *dcol = mem.dev<int>(k), *dpred = mem.dev<int>((size_t)ngroups * (size_t)n);
-    int *part = mem.dev<int>((size_t)2 * ngroups * nblk);
-    unsigned char *dheld = mem.dev<unsigned char>((size_t)ngroups * (size_t)n);
-    int *count = mem.dev<int>(1);   // the product's column count: this call's own (the solver's nlive is 0 once every column has stopped)
-    hipError_t e = mem.error();
-    if (e == hipSuccess) e = hipMemsetAsync(W, 0, sizeof(double) * ldw * slots, st);
-    if (e == hipSuccess) e = hipMemsetAsync(OUT, 0, sizeof(double) * ldw * slots, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dcal, 0xff, sizeof(int) * k, st);   // -1: mheldout_kernel stops after the intercept
-    if (e == hipSuccess) e = hipMemcpyAsync(dcol, col_of.data(), sizeof(int) * k, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dheld, held, (size_t)ngroups * (size_t)n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(count, &k, sizeof(int), hipMemcpyHostToDevice, st);
-    int rc = BQ_OK;
-    if (e != hipSuccess) {
-        bq_set_error("held-out vote setup failed: %s", hipGetErrorString(e));
-        rc = e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
-    }
-    if (rc == BQ_OK) {
+    bq_score_pass pass("held-out vote", st);
+    double *W = pass.fill<double>(0, ldw * slots), *OUT = pass.fill<double>(0, ldw * slots);
+    double *slab = pass.dev<double>(bq_symmw_slab_len(p->nb));
+    double *db = pass.out<double>(intercept, k);
+    long long *dnsv = pass.out<long long>(n_sv, k);
+    long long *dnheld = pass.out<long long>(n_held, ngroups), *dnright = pass.out<long long>(n_correct, ngroups);
+    int *dpred = pass.out<int>(pred, (size_t)ngroups * (size_t)n);   // (pred may be null: the rows' classes stay on the device)
+    const int *dcal = pass.fill<int>(0xff, k);                       // -1: mheldout_kernel stops after the intercept
+    const int *dcol = pass.in(col_of.data(), (size_t)k);
+    int *part = pass.dev<int>((size_t)2 * ngroups * nblk);
+    const unsigned char *dheld = pass.in(held, (size_t)ngroups * (size_t)n);
+    int *count = pass.columns(k);
+    if (pass.ready()) {
         mcoef_kernel<false><<<dim3((unsigned)((n + 255) / 256), (unsigned)k), 256, 0, st>>>(m->epi, W, ldw);
-        rc = bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count);   // u on ALL rows: the routed product leaves 0 outside a pair's classes
-    }
-    if (rc == BQ_OK) {
-        mheldout_kernel<<<k, 1024, 0, st>>>(m->epi, OUT, ldw, nullptr, nullptr, nullptr, dcal, nullptr, nullptr, db, dnsv);
-        mvote_kernel<<<dim3((unsigned)nblk, (unsigned)ngroups), BQ_VOTE_ROWS, bq_vote_lds_bytes(ncls), st>>>(
-            ncls, (long long)n, OUT, ldw, db, dcol, bq_pairs_plan_tiles(m->plan), dheld, dpred, part);
-        mvote_count_kernel<<<ngroups, 1024, 0, st>>>(P, nblk, part, db, dcol, dnheld, dnright);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(intercept, db, sizeof(double) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_sv, dnsv, sizeof(int64_t) * k, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_held, dnheld, sizeof(int64_t) * ngroups, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_correct, dnright, sizeof(int64_t) * ngroups, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && pred) e = hipMemcpyAsync(pred, dpred, sizeof(int) * (size_t)ngroups * (size_t)n, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            bq_set_error("held-out vote: %s", hipGetErrorString(e));
-            rc = BQ_ERR_HIP;
+        // u on ALL rows: the routed product leaves 0 outside a pair's classes
+        if (pass.step(bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count))) {
+            mheldout_kernel<<<k, 1024, 0, st>>>(m->epi, OUT, ldw, nullptr, nullptr, nullptr, dcal, nullptr, nullptr, db, dnsv);
+            mvote_kernel<<<dim3((unsigned)nblk, (unsigned)ngroups), BQ_VOTE_ROWS, bq_vote_lds_bytes(ncls), st>>>(
+                ncls, (long long)n, OUT, ldw, db, dcol, bq_pairs_plan_tiles(m->plan), dheld, dpred, part);
+            mvote_count_kernel<<<ngroups, 1024, 0, st>>>(P, nblk, part, db, dcol, dnheld, dnright);
         }
     }
-    return bq_ctx_sync_after(c, rc);   // held, k, the tables and the results are the caller's and this frame's
+    return bq_ctx_sync_after(c, pass.finish());   // held, the tables and the results are the caller's and this frame's
 }

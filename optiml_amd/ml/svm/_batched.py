@@ -8,6 +8,7 @@ the way a column's result becomes the `SVC` that `SVC.fit` (the `SVR` that `SVR.
 import ctypes as C
 import warnings
 from collections.abc import Iterable
+from contextlib import contextmanager
 
 import numpy as np
 
@@ -21,6 +22,7 @@ from .kernels import GaussianKernel, LinearKernel, PolyKernel, SigmoidKernel, ga
 from .losses import squared_hinge, squared_epsilon_insensitive
 
 MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
+MAX_COLUMNS = 4096   # columns per batched solve at most (see column_cap)
 
 
 def column_bytes(n):
@@ -29,10 +31,32 @@ def column_bytes(n):
     return 16 * 8 * (n + 256)
 
 
+def column_cap(length, free_bytes, slab_bytes):
+    """Columns one batched solve may take with `free_bytes` of device memory free after the panel: MEMORY_SHARE of it, less the
+    solver's 16-column slab (`slab_bytes`), over the device state of a column of `length` variables (`column_bytes`); at most
+    MAX_COLUMNS, at least 16.  Larger grids run in several solves; the split does not change any column's bits (the product is
+    batch-invariant)."""
+    budget = int(free_bytes * MEMORY_SHARE) - int(slab_bytes)
+    return int(max(16, min(MAX_COLUMNS, budget // column_bytes(length))))
+
+
 def device_free_bytes():
     free, total = C.c_int64(0), C.c_int64(0)
     _lib.check(_lib.load().bq_ctx_mem_info(get_context().handle, C.byref(free), C.byref(total)))
     return free.value
+
+
+@contextmanager
+def device_panel(*args, **kwargs):
+    """The Gram panel of `KernelQuadratic(*args, **kwargs)` on the device for the length of a `with` block: yields (obj, dev,
+    free_bytes, wide_slab_bytes) — the quadratic, its device problem, the device memory free after the panel and the 16-column
+    product's slab on it — and releases the panel on exit, also when the body raises."""
+    obj = KernelQuadratic(*args, **kwargs)
+    try:
+        dev = obj.device_problem()
+        yield obj, dev, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle)
+    finally:
+        obj.release()
 
 
 def solver_kind(optimizer):
@@ -41,6 +65,14 @@ def solver_kind(optimizer):
 
 def _pair_array(pairs):
     return _lib.as_i32(np.asarray(pairs, dtype=np.int32).reshape(-1))
+
+
+def _data_row(data_row, n):
+    """the uint8 row mask of a class-sorted panel of n rows (1 a data row, 0 a ghost row)"""
+    data_row = np.ascontiguousarray(data_row, dtype=np.uint8)
+    if data_row.shape != (n,):
+        raise ValueError('data_row must have %d entries' % n)
+    return data_row
 
 
 class _DeviceMultiSolver:
@@ -85,39 +117,32 @@ class _DeviceMultiSolver:
         _lib.check(self._lib.bq_msolver_get(self._h, c, what, _lib.ptr(out)))
         return out
 
+    def _heldout(self, call, cal_of, ncal, decisions, *data_row):
+        """`heldout_svc` and, with a data_row, `heldout_pairs`"""
+        cal_of = _lib.as_i32(cal_of, self.k, 'cal_of')
+        rows = [_data_row(d, self.n).ctypes.data_as(C.POINTER(C.c_ubyte)) for d in data_row]
+        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
+        fit, args = _platt_outputs(ncal)
+        dec = np.empty((ncal, self.n)) if decisions else None
+        _lib.check(call(self._h, *rows, int(ncal), _lib.iptr(cal_of), _lib.ptr(b), n_sv.ctypes.data_as(C.POINTER(C.c_int64)), *args,
+                        _lib.ptr(dec)))
+        if decisions:
+            fit['dec'] = dec
+        return b, n_sv, fit
+
     def heldout_svc(self, cal_of, ncal, decisions=False):
         """The columns of a one-box-per-column SVC solver as they stand (`bq_msolver_svc_heldout`): per column SVC.fit's
         intercept and support count (NaN without a support vector), and per calibrator the Platt fit (`platt_fit`'s dict) on the
         held-out decision values of the columns c with cal_of[c] == that calibrator (-1: the column feeds none); with
         `decisions`, the dict also holds 'dec', the ncal x n decision values (0 on the rows no column of the calibrator holds
         out).  Returns (intercept, n_sv, fit)."""
-        cal_of = _lib.as_i32(cal_of, self.k, 'cal_of')
-        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
-        fit, args = _platt_outputs(ncal)
-        dec = np.empty((ncal, self.n)) if decisions else None
-        _lib.check(self._lib.bq_msolver_svc_heldout(self._h, int(ncal), _lib.iptr(cal_of), _lib.ptr(b),
-                                                    n_sv.ctypes.data_as(C.POINTER(C.c_int64)), *args, _lib.ptr(dec)))
-        if decisions:
-            fit['dec'] = dec
-        return b, n_sv, fit
+        return self._heldout(self._lib.bq_msolver_svc_heldout, cal_of, ncal, decisions)
 
     def heldout_pairs(self, data_row, cal_of, ncal, decisions=False):
         """`heldout_svc` for the columns of a pair solver (`_DevicePairSolver`, `bq_msolver_pairs_heldout`): a column's held-out
         rows are the data rows (data_row: n entries, 1 a data row, 0 a ghost row) of its pair's two classes whose box is 0.
         Returns (intercept, n_sv, fit)."""
-        cal_of = _lib.as_i32(cal_of, self.k, 'cal_of')
-        data_row = np.ascontiguousarray(data_row, dtype=np.uint8)
-        if data_row.shape != (self.n,):
-            raise ValueError('data_row must have %d entries' % self.n)
-        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
-        fit, args = _platt_outputs(ncal)
-        dec = np.empty((ncal, self.n)) if decisions else None
-        _lib.check(self._lib.bq_msolver_pairs_heldout(self._h, data_row.ctypes.data_as(C.POINTER(C.c_ubyte)), int(ncal),
-                                                      _lib.iptr(cal_of), _lib.ptr(b), n_sv.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      *args, _lib.ptr(dec)))
-        if decisions:
-            fit['dec'] = dec
-        return b, n_sv, fit
+        return self._heldout(self._lib.bq_msolver_pairs_heldout, cal_of, ncal, decisions, data_row)
 
     def vote_heldout_pairs(self, data_row, group_of, held, predictions=False):
         """The (candidate, fold) groups of a pair solver's columns as they stand (`_DevicePairSolver`,
@@ -127,10 +152,8 @@ class _DeviceMultiSolver:
         and those whose one-vs-one vote is their class (-1 for a group with a NaN intercept) and, with `predictions`, groups x n
         predicted classes (-1 on the rows a group does not score)."""
         group_of = _lib.as_i32(group_of, self.k, 'group_of')
-        data_row = np.ascontiguousarray(data_row, dtype=np.uint8)
+        data_row = _data_row(data_row, self.n)
         held = np.ascontiguousarray(np.atleast_2d(held), dtype=np.uint8)
-        if data_row.shape != (self.n,):
-            raise ValueError('data_row must have %d entries' % self.n)
         groups = held.shape[0]
         if held.shape != (groups, self.n):
             raise ValueError('held must be groups x %d' % self.n)

@@ -22,15 +22,14 @@ back, no k x n array.
 """
 import copy
 import itertools
+import warnings
 
 import numpy as np
 
-from ... import _lib
 from ...device import get_context
-from ...opti import KernelQuadratic
 from ._base import SVC, SVR
-from ._batched import (MEMORY_SHARE, _DeviceSVRSolver, _gram_matmat, column_bytes, device_free_bytes, fitted_svr, intercept,
-                       solve_batched, solver_kind, svr_intercept)
+from ._batched import (MAX_COLUMNS, MEMORY_SHARE, _DeviceSVRSolver, _gram_matmat, column_cap, device_panel,  # noqa: F401
+                       fitted_svr, intercept, solve_batched, solver_kind, svr_intercept)
 from .kernels import BaseEstimator, LinearKernel
 from .multiclass import OneVsRestSVC, uses_batched_path, binarize
 from .multioutput import uses_batched_svr_path
@@ -41,7 +40,6 @@ __all__ = ['SVCGridSearchCV', 'SVRGridSearchCV', 'parameter_grid', 'check_cv_spl
 
 BATCHED_KEYS = frozenset({'C', 'kernel'})
 SVR_BATCHED_KEYS = frozenset({'C', 'epsilon', 'kernel'})
-MAX_COLUMNS = 4096   # columns per batched solve at most (see _column_cap)
 
 
 def parameter_grid(param_grid):
@@ -126,6 +124,23 @@ def _fold_labels(y_train, multiclass):
     return classes, [classes[-1]]
 
 
+def _group_of(groups, index, kernel, Xtr, vectors):
+    """the group of the kernel resolved on the fold's training rows Xtr, made on first use"""
+    rk = _resolved_kernel(kernel, Xtr)
+    key = _kernel_key(rk)
+    if key not in index:
+        index[key] = len(groups)
+        groups.append(dict({name: [] for name in vectors}, kernel=rk, cols=[]))
+    return groups[index[key]]
+
+
+def _stacked(groups, vectors):
+    for g in groups:
+        for name in vectors:
+            g[name] = np.stack(g[name])
+    return groups
+
+
 def plan_columns(X, y, splits, candidates, base_C, base_kernel, multiclass):
     """The batched search's panels and columns.  Returns (groups, folds): folds[f] = (classes_, positive labels per class row);
     groups: a list of dicts {kernel: the resolved kernel of the panel, cols: [(candidate, fold, class row, C)], Y: m x n labels +-1,
@@ -139,22 +154,14 @@ def plan_columns(X, y, splits, candidates, base_C, base_kernel, multiclass):
         C = p.get('C', base_C)
         kernel = p.get('kernel', base_kernel)
         for f, (tr, _) in enumerate(splits):
-            rk = _resolved_kernel(kernel, X[tr])
-            key = _kernel_key(rk)
-            if key not in index:
-                index[key] = len(groups)
-                groups.append(dict(kernel=rk, cols=[], Y=[], UB=[]))
-            g = groups[index[key]]
+            g = _group_of(groups, index, kernel, X[tr], ('Y', 'UB'))
             ub = np.zeros(n)
             ub[tr] = C
             for r, pos in enumerate(folds[f][1]):
                 g['cols'].append((ci, f, r, C))
                 g['Y'].append(np.where(y == pos, 1., -1.))
                 g['UB'].append(ub)
-    for g in groups:
-        g['Y'] = np.stack(g['Y'])
-        g['UB'] = np.stack(g['UB'])
-    return groups, folds
+    return _stacked(groups, ('Y', 'UB')), folds
 
 
 def aggregate_scores(candidates, scores):
@@ -185,24 +192,18 @@ def aggregate_scores(candidates, scores):
     return res
 
 
-def column_cap(n, free_bytes, slab_bytes):
-    """Columns one batched solve may take with `free_bytes` of device memory free after the panel: MEMORY_SHARE of it, less the
-    solver's 16-column slab (`slab_bytes`), over the device state of a column (`column_bytes`); at most MAX_COLUMNS, at least 16.
-    Larger grids run in several solves; the split does not change any column's bits (the product is batch-invariant)."""
-    budget = int(free_bytes * MEMORY_SHARE) - int(slab_bytes)
-    return int(max(16, min(MAX_COLUMNS, budget // column_bytes(n))))
-
-
-class SVCGridSearchCV(BaseEstimator):
-    """Exhaustive search over `param_grid` for an `SVC` or `OneVsRestSVC` scored by accuracy, as sklearn's GridSearchCV.  A
-    `OneVsOneSVC` runs GridSearchCV's per-fold calls, each fold's fit one batched one-vs-one solve.
-
-    After `fit`: `cv_results_` (params, param_<key>, split<i>_test_score, mean / std / rank_test_score — no timing keys: the
-    candidates' fits are one batched solve and have no fit time of their own), `best_index_` (first among ties), `best_params_`,
-    `best_score_`, `n_splits_`, `best_estimator_` (a plain `fit` on all the data, refit=True), and per column `n_iter_` / `status_`
-    of shape (candidates, splits, classes) (-1 / '' where a fit has no such record).  `batched_` says which path ran.
-    `predict`, `decision_function` and `score` are the best estimator's.
-    """
+class _GridSearchCV(BaseEstimator):
+    """The skeleton of the five searches (`SVCGridSearchCV`, `SVRGridSearchCV`, `NuSVCGridSearchCV`, `NuSVRGridSearchCV`,
+    `OneVsOneGridSearchCV`): the candidates and splits, the estimator's own checks on every candidate, the batched path or
+    GridSearchCV's per-fold calls, `cv_results_`, the best candidate and its refit.  A subclass says its estimator type(s), its
+    messages, whether an int `cv` is stratified, how it checks the targets, when it batches (`_uses_batched`), its
+    `_fit_batched`, what one fallback fit records (`_fallback_fit`) and whether 'failed' fits are counted."""
+    _estimator_type = None      # a class: the candidates are of it; a tuple of classes: they are of the estimator's own type
+    _type_error = ''
+    _scoring = 'accuracy scoring'
+    _stratified = True
+    _column_records = False     # n_iter_ / status_ are (candidates, splits, columns) rather than (candidates, splits)
+    _counts_failed = False      # a fit whose (first) status is 'failed' scores NaN under one RuntimeWarning for the search
 
     def __init__(self, estimator, param_grid, scoring=None, cv=5, refit=True):
         self.estimator = estimator
@@ -213,23 +214,21 @@ class SVCGridSearchCV(BaseEstimator):
 
     def fit(self, X, y):
         if self.scoring is not None:
-            raise NotImplementedError('only accuracy scoring (scoring=None) is implemented')
-        if not isinstance(self.estimator, (SVC, OneVsRestSVC, OneVsOneSVC)):
-            raise TypeError('estimator must be an SVC, a OneVsRestSVC or a OneVsOneSVC')
+            raise NotImplementedError('only %s (scoring=None) is implemented' % self._scoring)
+        if not isinstance(self.estimator, self._estimator_type):
+            raise TypeError(self._type_error)
         X = np.ascontiguousarray(X, dtype=float)
-        y = np.asarray(y)
+        y = self._targets(X, y)
         candidates = parameter_grid(self.param_grid)
-        splits = check_cv_splits(self.cv, X, y)
-        etype, base = type(self.estimator), _base_params(self.estimator)
+        splits = check_cv_splits(self.cv, X, y, stratified=self._stratified)
+        etype = type(self.estimator) if isinstance(self._estimator_type, tuple) else self._estimator_type
+        base = _base_params(self.estimator)
         protos = [_make(etype, base, p) for p in candidates]   # the estimator's own checks on every candidate
-        self.batched_ = uses_batched_search(protos[0], candidates, get_context().world)
-        if self.batched_:
-            scores, n_iter, status = self._fit_batched(X, y, splits, candidates, protos[0])
-        else:
-            scores, n_iter, status = self._fit_fallback(X, y, splits, candidates, etype, base)
+        self.batched_ = self._uses_batched(protos[0], candidates, splits, y)
+        scores, self.n_iter_, self.status_ = self._fits(X, y, splits, candidates, etype, base, protos[0])
+        self._account()
         self.n_splits_ = len(splits)
         self.cv_results_ = aggregate_scores(candidates, scores)
-        self.n_iter_, self.status_ = n_iter, status
         self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
         self.best_params_ = candidates[self.best_index_]
         self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
@@ -237,16 +236,44 @@ class SVCGridSearchCV(BaseEstimator):
             self.best_estimator_ = _make(etype, base, self.best_params_).fit(X, y)
         return self
 
+    @staticmethod
+    def _targets(X, y):
+        return np.asarray(y)
+
+    def _fits(self, X, y, splits, candidates, etype, base, first):
+        """(scores, n_iter, status) of every (candidate, fold), on the batched path or — also when `_fit_batched` declines with
+        None before any solve — by the per-fold calls"""
+        result = self._fit_batched(X, y, splits, candidates, base, first) if self.batched_ else None
+        if result is None:
+            self.batched_ = False
+            result = self._fit_fallback(X, y, splits, candidates, etype, base)
+        return result
+
+    def _account(self):
+        if not self._counts_failed:
+            return
+        fits = self.status_.reshape(self.status_.shape[:2] + (-1,))[:, :, 0]
+        n_failed = int((fits == 'failed').sum())
+        if n_failed == fits.size:
+            raise ValueError('all the %d fits failed' % n_failed)
+        if n_failed:
+            warnings.warn('%d fits failed out of a total of %d: their scores are nan' % (n_failed, fits.size), RuntimeWarning)
+
+    @staticmethod
+    def _fallback_fit(est, Xtr, ytr, Xte, yte):
+        """(score, [(iterations, status) per column]) of GridSearchCV's calls on one candidate and fold"""
+        score = est.fit(Xtr, ytr).score(Xte, yte)
+        fits = est.estimators_ if isinstance(est, (OneVsRestSVC, OneVsOneSVC)) else [est]
+        return score, [(int(getattr(e.optimizer, 'iter', -1)), str(getattr(e.optimizer, 'status', ''))) for e in fits]
+
     def _fit_fallback(self, X, y, splits, candidates, etype, base):
         nc, ns = len(candidates), len(splits)
         scores = np.empty((nc, ns))
         recs = [[None] * ns for _ in range(nc)]
         for ci, p in enumerate(candidates):
             for f, (tr, te) in enumerate(splits):
-                est = _make(etype, base, {}).set_params(**p).fit(X[tr], y[tr])
-                scores[ci, f] = est.score(X[te], y[te])
-                fits = est.estimators_ if isinstance(est, (OneVsRestSVC, OneVsOneSVC)) else [est]
-                recs[ci][f] = [(int(getattr(e.optimizer, 'iter', -1)), str(getattr(e.optimizer, 'status', ''))) for e in fits]
+                est = _make(etype, base, {}).set_params(**p)
+                scores[ci, f], recs[ci][f] = self._fallback_fit(est, X[tr], y[tr], X[te], y[te])
         width = max(len(r) for row in recs for r in row)
         n_iter = np.full((nc, ns, width), -1, dtype=np.int64)
         status = np.full((nc, ns, width), '', dtype=object)
@@ -254,9 +281,37 @@ class SVCGridSearchCV(BaseEstimator):
             for f in range(ns):
                 for c, (it, st) in enumerate(recs[ci][f]):
                     n_iter[ci, f, c], status[ci, f, c] = it, st
-        return scores, n_iter, status
+        return (scores, n_iter, status) if self._column_records else (scores, n_iter[:, :, 0], status[:, :, 0])
 
-    def _fit_batched(self, X, y, splits, candidates, proto_est):
+    def decision_function(self, X):
+        return self.best_estimator_.decision_function(X)
+
+    def predict(self, X):
+        return self.best_estimator_.predict(X)
+
+    def score(self, X, y):
+        return self.best_estimator_.score(X, y)
+
+
+class SVCGridSearchCV(_GridSearchCV):
+    """Exhaustive search over `param_grid` for an `SVC` or `OneVsRestSVC` scored by accuracy, as sklearn's GridSearchCV.  A
+    `OneVsOneSVC` runs GridSearchCV's per-fold calls, each fold's fit one batched one-vs-one solve.
+
+    After `fit`: `cv_results_` (params, param_<key>, split<i>_test_score, mean / std / rank_test_score — no timing keys: the
+    candidates' fits are one batched solve and have no fit time of their own), `best_index_` (first among ties), `best_params_`,
+    `best_score_`, `n_splits_`, `best_estimator_` (a plain `fit` on all the data, refit=True), and per column `n_iter_` / `status_`
+    of shape (candidates, splits, classes) (-1 / '' where a fit has no such record).  `batched_` says which path ran.
+    `predict`, `decision_function` and `score` are the best estimator's.
+    """
+    _estimator_type = (SVC, OneVsRestSVC, OneVsOneSVC)
+    _type_error = 'estimator must be an SVC, a OneVsRestSVC or a OneVsOneSVC'
+    _column_records = True
+
+    @staticmethod
+    def _uses_batched(first, candidates, splits, y):
+        return uses_batched_search(first, candidates, get_context().world)
+
+    def _fit_batched(self, X, y, splits, candidates, base, proto_est):
         multiclass = isinstance(proto_est, OneVsRestSVC)
         proto = _prototype(proto_est)
         n = len(y)
@@ -269,41 +324,40 @@ class SVCGridSearchCV(BaseEstimator):
         kind = solver_kind(proto.optimizer)
         for g in groups:   # one panel at a time
             m = len(g['cols'])
-            obj = KernelQuadratic(X, -np.ones(n), 'svc', g['kernel'], y=g['Y'][0], storage=proto.storage,
-                                  tune_placement=proto._streams_panel(), expected_products=proto.max_iter * ((m + 15) // 16))
-            dev = obj.device_problem()
-            cap = column_cap(n, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle))
-            for c0 in range(0, m, cap):
-                cols = g['cols'][c0:c0 + cap]
-                Y, UB = g['Y'][c0:c0 + cap], g['UB'][c0:c0 + cap]
-                res = solve_batched(dev, kind, Y, UB, eps=1e-6, max_iter=proto.max_iter)
-                W = np.zeros((len(cols), n))
-                svs = []
-                for j, r in enumerate(res):
-                    sv = r['x'] > 1e-6
-                    W[j][sv] = r['x'][sv] * Y[j][sv]
-                    svs.append(sv)
-                U = _gram_matmat(dev, W, wide=True)
-                for j, (ci, f, row, C) in enumerate(cols):
-                    sv = svs[j]
-                    b = intercept(Y[j], U[j], sv)
-                    n_iter[ci, f, row], status[ci, f, row] = res[j]['iter'], res[j]['status']
-                    te = splits[f][1]
-                    kernel = candidates[ci].get('kernel', proto.kernel)
-                    if proto.storage == 'f64' and not isinstance(getattr(kernel, 'gamma', None), str):
-                        dec[ci][f][row] = U[j][te] + b   # the fp64 panel holds the decision kernel's values
-                    else:
-                        # decision_function resolves a string gamma on the support vectors and evaluates the kernel in fp64,
-                        # not from an fp32 panel: score through the fold's SVC
-                        est = copy.copy(proto)
-                        est.kernel, est.C = kernel, C
-                        est.support_vectors_ = X[sv]
-                        est.dual_coef_ = W[j][sv]
-                        if isinstance(kernel, LinearKernel):
-                            est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
-                        est.intercept_ = b
-                        dec[ci][f][row] = est.decision_function(X[te])
-            del dev, obj
+            with device_panel(X, -np.ones(n), 'svc', g['kernel'], y=g['Y'][0], storage=proto.storage,
+                              tune_placement=proto._streams_panel(),
+                              expected_products=proto.max_iter * ((m + 15) // 16)) as (_, dev, free, slab):
+                cap = column_cap(n, free, slab)
+                for c0 in range(0, m, cap):
+                    cols = g['cols'][c0:c0 + cap]
+                    Y, UB = g['Y'][c0:c0 + cap], g['UB'][c0:c0 + cap]
+                    res = solve_batched(dev, kind, Y, UB, eps=1e-6, max_iter=proto.max_iter)
+                    W = np.zeros((len(cols), n))
+                    svs = []
+                    for j, r in enumerate(res):
+                        sv = r['x'] > 1e-6
+                        W[j][sv] = r['x'][sv] * Y[j][sv]
+                        svs.append(sv)
+                    U = _gram_matmat(dev, W, wide=True)
+                    for j, (ci, f, row, C) in enumerate(cols):
+                        sv = svs[j]
+                        b = intercept(Y[j], U[j], sv)
+                        n_iter[ci, f, row], status[ci, f, row] = res[j]['iter'], res[j]['status']
+                        te = splits[f][1]
+                        kernel = candidates[ci].get('kernel', proto.kernel)
+                        if proto.storage == 'f64' and not isinstance(getattr(kernel, 'gamma', None), str):
+                            dec[ci][f][row] = U[j][te] + b   # the fp64 panel holds the decision kernel's values
+                        else:
+                            # decision_function resolves a string gamma on the support vectors and evaluates the kernel in fp64,
+                            # not from an fp32 panel: score through the fold's SVC
+                            est = copy.copy(proto)
+                            est.kernel, est.C = kernel, C
+                            est.support_vectors_ = X[sv]
+                            est.dual_coef_ = W[j][sv]
+                            if isinstance(kernel, LinearKernel):
+                                est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
+                            est.intercept_ = b
+                            dec[ci][f][row] = est.decision_function(X[te])
         self._cv_decisions = dec
         scores = np.empty((nc, ns))
         for ci in range(nc):
@@ -316,15 +370,6 @@ class SVCGridSearchCV(BaseEstimator):
                     pred = classes[np.argmax(np.stack(D, axis=1), axis=1)]
                 scores[ci, f] = float(np.mean(pred == y[te]))
         return scores, n_iter, status
-
-    def decision_function(self, X):
-        return self.best_estimator_.decision_function(X)
-
-    def predict(self, X):
-        return self.best_estimator_.predict(X)
-
-    def score(self, X, y):
-        return self.best_estimator_.score(X, y)
 
 
 def uses_batched_svr_search(estimator, candidates, world):
@@ -350,22 +395,14 @@ def plan_svr_columns(X, y, splits, candidates, base_C, base_epsilon, base_kernel
         C, epsilon = p.get('C', base_C), p.get('epsilon', base_epsilon)
         kernel = p.get('kernel', base_kernel)
         for f, (tr, _) in enumerate(splits):
-            rk = _resolved_kernel(kernel, X[tr])
-            key = _kernel_key(rk)
-            if key not in index:
-                index[key] = len(groups)
-                groups.append(dict(kernel=rk, cols=[], QL=[], UB=[]))
-            g = groups[index[key]]
+            g = _group_of(groups, index, kernel, X[tr], ('QL', 'UB'))
             ub = np.zeros(2 * n)
             ub[tr] = C
             ub[n + tr] = C
             g['cols'].append((ci, f, C, epsilon))
             g['QL'].append(q0 + epsilon)
             g['UB'].append(ub)
-    for g in groups:
-        g['QL'] = np.stack(g['QL'])
-        g['UB'] = np.stack(g['UB'])
-    return groups
+    return _stacked(groups, ('QL', 'UB'))
 
 
 def svr_column_cap(n, free_bytes, slab_bytes):
@@ -373,8 +410,7 @@ def svr_column_cap(n, free_bytes, slab_bytes):
     That budgets 16 vectors of 2n; a column holds 7 (x, g, d, Qd, both bounds, its linear term) and two n-vectors (product input
     and output), so the cap errs on the small side by about a half, which leaves room for the host's records and the scoring's
     few vectors."""
-    budget = int(free_bytes * MEMORY_SHARE) - int(slab_bytes)
-    return int(max(16, min(MAX_COLUMNS, budget // column_bytes(2 * n))))
+    return column_cap(2 * n, free_bytes, slab_bytes)
 
 
 def r2_from_sse(sse, y_test):
@@ -389,7 +425,7 @@ def r2_from_sse(sse, y_test):
     return 1. - float(sse) / den
 
 
-class SVRGridSearchCV(BaseEstimator):
+class SVRGridSearchCV(_GridSearchCV):
     """Exhaustive search over `param_grid` for an `SVR` scored by R^2, as sklearn's GridSearchCV.  An int `cv` is KFold(cv)
     without shuffling.
 
@@ -399,55 +435,31 @@ class SVRGridSearchCV(BaseEstimator):
     divides by zero there; GridSearchCV's error_score).  `predict` and `score` are the best estimator's.
     """
 
-    def __init__(self, estimator, param_grid, scoring=None, cv=5, refit=True):
-        self.estimator = estimator
-        self.param_grid = param_grid
-        self.scoring = scoring
-        self.cv = cv
-        self.refit = refit
+    _estimator_type = SVR
+    _type_error = 'estimator must be an SVR'
+    _scoring = 'R^2 scoring'
+    _stratified = False
 
-    def fit(self, X, y):
-        if self.scoring is not None:
-            raise NotImplementedError('only R^2 scoring (scoring=None) is implemented')
-        if not isinstance(self.estimator, SVR):
-            raise TypeError('estimator must be an SVR')
-        X = np.ascontiguousarray(X, dtype=float)
+    @staticmethod
+    def _targets(X, y):
         y = np.asarray(y, dtype=float)
         if y.ndim != 1:
             raise ValueError('use MultiOutputSVR to train a model over more than one target')
-        candidates = parameter_grid(self.param_grid)
-        splits = check_cv_splits(self.cv, X, y, stratified=False)
-        base = _base_params(self.estimator)
-        protos = [_make(SVR, base, p) for p in candidates]   # SVR's own checks on every candidate
-        self.batched_ = uses_batched_svr_search(protos[0], candidates, get_context().world)
-        fit = self._fit_batched if self.batched_ else self._fit_fallback
-        scores, self.n_iter_, self.status_ = fit(X, y, splits, candidates, base)
-        self.n_splits_ = len(splits)
-        self.cv_results_ = aggregate_scores(candidates, scores)
-        self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
-        self.best_params_ = candidates[self.best_index_]
-        self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
-        if self.refit:
-            self.best_estimator_ = _make(SVR, base, self.best_params_).fit(X, y)
-        return self
+        return y
 
-    def _fit_fallback(self, X, y, splits, candidates, base):
-        nc, ns = len(candidates), len(splits)
-        scores = np.empty((nc, ns))
-        n_iter = np.full((nc, ns), -1, dtype=np.int64)
-        status = np.full((nc, ns), '', dtype=object)
-        for ci, p in enumerate(candidates):
-            for f, (tr, te) in enumerate(splits):
-                est = _make(SVR, base, {}).set_params(**p)
-                try:
-                    scores[ci, f] = est.fit(X[tr], y[tr]).score(X[te], y[te])
-                except ZeroDivisionError:   # no support vector
-                    scores[ci, f] = np.nan
-                n_iter[ci, f] = int(getattr(est.optimizer, 'iter', -1))
-                status[ci, f] = str(getattr(est.optimizer, 'status', ''))
-        return scores, n_iter, status
+    @staticmethod
+    def _uses_batched(first, candidates, splits, y):
+        return uses_batched_svr_search(first, candidates, get_context().world)
 
-    def _fit_batched(self, X, y, splits, candidates, base):
+    @staticmethod
+    def _fallback_fit(est, Xtr, ytr, Xte, yte):
+        try:
+            score = est.fit(Xtr, ytr).score(Xte, yte)
+        except ZeroDivisionError:   # no support vector
+            score = np.nan
+        return score, [(int(getattr(est.optimizer, 'iter', -1)), str(getattr(est.optimizer, 'status', '')))]
+
+    def _fit_batched(self, X, y, splits, candidates, base, first):
         proto = _make(SVR, base, {})
         n = len(y)
         nc, ns = len(candidates), len(splits)
@@ -458,52 +470,44 @@ class SVRGridSearchCV(BaseEstimator):
         for g in plan_svr_columns(X, y, splits, candidates, proto.C, proto.epsilon, proto.kernel):   # one panel at a time
             m = len(g['cols'])
             # the 'svr' structure's own linear term is never used by the batched solver
-            obj = KernelQuadratic(X, g['QL'][0], 'svr', g['kernel'], storage=proto.storage, tune_placement=proto._streams_panel(),
-                                  expected_products=proto.max_iter * ((m + 15) // 16))
-            dev = obj.device_problem()
-            cap = svr_column_cap(n, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle))
-            for c0 in range(0, m, cap):
-                cols = g['cols'][c0:c0 + cap]
-                QL, UB = g['QL'][c0:c0 + cap], g['UB'][c0:c0 + cap]
-                # the fp64 panel of a numeric gamma holds the decision kernel's values: such columns are scored on the device
-                on_device = [proto.storage == 'f64' and not isinstance(getattr(candidates[ci].get('kernel', proto.kernel), 'gamma',
-                                                                               None), str) for ci, _, _, _ in cols]
-                held = {}
+            with device_panel(X, g['QL'][0], 'svr', g['kernel'], storage=proto.storage, tune_placement=proto._streams_panel(),
+                              expected_products=proto.max_iter * ((m + 15) // 16)) as (obj, dev, free, slab):
+                cap = svr_column_cap(n, free, slab)
+                for c0 in range(0, m, cap):
+                    cols = g['cols'][c0:c0 + cap]
+                    QL, UB = g['QL'][c0:c0 + cap], g['UB'][c0:c0 + cap]
+                    # the fp64 panel of a numeric gamma holds the decision kernel's values: such columns are scored on the device
+                    on_device = [proto.storage == 'f64' and not isinstance(getattr(candidates[ci].get('kernel', proto.kernel), 'gamma',
+                                                                                   None), str) for ci, _, _, _ in cols]
+                    held = {}
 
-                def score(solver, _):
-                    if any(on_device):
-                        held['b'], _, held['sse'], _ = solver.heldout(y, [eps for _, _, _, eps in cols])
+                    def score(solver, _):
+                        if any(on_device):
+                            held['b'], _, held['sse'], _ = solver.heldout(y, [eps for _, _, _, eps in cols])
 
-                res = solve_batched(dev, kind, QL, UB, solver=_DeviceSVRSolver(dev, kind, QL, UB, 1e-6, proto.max_iter),
-                                    before_close=score, vectors=not all(on_device))
-                ests, svs = {}, {}
-                for j, (ci, f, _, _) in enumerate(cols):
-                    n_iter[ci, f], status[ci, f] = res[j]['iter'], res[j]['status']
-                    if on_device[j]:
-                        scores[ci, f] = r2_from_sse(held['sse'][j], y[splits[f][1]])
-                    else:
-                        # decision_function resolves a string gamma on the support vectors and evaluates the kernel in fp64, not
-                        # from an fp32 panel: score through the fold's SVR
-                        ests[j] = _make(SVR, base, candidates[ci])
-                        svs[j] = fitted_svr(ests[j], obj, res[j], X, y)
-                if ests:
-                    W = np.zeros((len(ests), n))
-                    for r, j in enumerate(ests):
-                        W[r][svs[j]] = ests[j].dual_coef_
-                    U = _gram_matmat(dev, W, wide=True)
-                    for r, j in enumerate(ests):
-                        ci, f, _, eps = cols[j]
-                        te = splits[f][1]
-                        try:
-                            ests[j].intercept_ = svr_intercept(y, U[r], svs[j], eps)
-                            scores[ci, f] = ests[j].score(X[te], y[te])
-                        except ZeroDivisionError:   # no support vector
-                            scores[ci, f] = np.nan
-            del dev, obj
+                    res = solve_batched(dev, kind, QL, UB, solver=_DeviceSVRSolver(dev, kind, QL, UB, 1e-6, proto.max_iter),
+                                        before_close=score, vectors=not all(on_device))
+                    ests, svs = {}, {}
+                    for j, (ci, f, _, _) in enumerate(cols):
+                        n_iter[ci, f], status[ci, f] = res[j]['iter'], res[j]['status']
+                        if on_device[j]:
+                            scores[ci, f] = r2_from_sse(held['sse'][j], y[splits[f][1]])
+                        else:
+                            # decision_function resolves a string gamma on the support vectors and evaluates the kernel in fp64, not
+                            # from an fp32 panel: score through the fold's SVR
+                            ests[j] = _make(SVR, base, candidates[ci])
+                            svs[j] = fitted_svr(ests[j], obj, res[j], X, y)
+                    if ests:
+                        W = np.zeros((len(ests), n))
+                        for r, j in enumerate(ests):
+                            W[r][svs[j]] = ests[j].dual_coef_
+                        U = _gram_matmat(dev, W, wide=True)
+                        for r, j in enumerate(ests):
+                            ci, f, _, eps = cols[j]
+                            te = splits[f][1]
+                            try:
+                                ests[j].intercept_ = svr_intercept(y, U[r], svs[j], eps)
+                                scores[ci, f] = ests[j].score(X[te], y[te])
+                            except ZeroDivisionError:   # no support vector
+                                scores[ci, f] = np.nan
         return scores, n_iter, status
-
-    def predict(self, X):
-        return self.best_estimator_.predict(X)
-
-    def score(self, X, y):
-        return self.best_estimator_.score(X, y)

@@ -26,7 +26,7 @@ from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ._base import ClassifierMixin, ConvergenceWarning, RegressorMixin
-from ._batched import _DeviceSimplex2Solver, device_free_bytes, solve_batched
+from ._batched import _DeviceSimplex2Solver, column_cap, device_free_bytes, solve_batched
 from .kernels import BaseEstimator, Kernel, gaussian
 from .oneclass import _resolved
 
@@ -58,7 +58,6 @@ def _check_feasible(y, nu):
 def _solve(proto, X, S, UB, mass, q):
     """The k two-group columns (S, UB, mass, q: `_DeviceSimplex2Solver`'s) on one panel of X, in solves of at most `column_cap`
     columns: (kernel_, [(column result, r1, r2), ...])."""
-    from .model_selection import column_cap   # (imports this package's estimators)
     name = type(proto).__name__
     if proto.storage == 'stream':
         raise NotImplementedError(f'{name} needs a resident panel: storage \'f64\' or \'f32\'')

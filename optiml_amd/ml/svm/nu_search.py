@@ -28,14 +28,10 @@ import warnings
 
 import numpy as np
 
-from ... import _lib
 from ...device import get_context
-from ...opti import KernelQuadratic
 from ._base import ConvergenceWarning
-from ._batched import _DeviceSimplex2Solver, device_free_bytes, solve_batched
-from .kernels import BaseEstimator
-from .model_selection import (_kernel_key, _make, _resolved_kernel, aggregate_scores, check_cv_splits, column_cap, parameter_grid,
-                              r2_from_sse)
+from ._batched import _DeviceSimplex2Solver, column_cap, device_panel, solve_batched
+from .model_selection import _GridSearchCV, _group_of, _make, _stacked, r2_from_sse
 from .nu import NuSVC, NuSVR, _check_feasible
 
 __all__ = ['NuSVCGridSearchCV', 'NuSVRGridSearchCV', 'plan_nu_svc_columns', 'plan_nu_svr_columns', 'uses_batched_nu_search']
@@ -54,23 +50,6 @@ def uses_batched_nu_search(estimator, candidates):
     else:
         return False
     return all(set(p) <= keys for p in candidates)
-
-
-def _group_of(groups, index, kernel, Xtr, vectors):
-    """the group of the kernel resolved on the fold's training rows Xtr, made on first use"""
-    rk = _resolved_kernel(kernel, Xtr)
-    key = _kernel_key(rk)
-    if key not in index:
-        index[key] = len(groups)
-        groups.append(dict({name: [] for name in vectors}, kernel=rk, cols=[]))
-    return groups[index[key]]
-
-
-def _stacked(groups, vectors):
-    for g in groups:
-        for name in vectors:
-            g[name] = np.stack(g[name])
-    return groups
 
 
 def plan_nu_svc_columns(X, y, splits, candidates, base_nu, base_kernel):
@@ -132,71 +111,38 @@ def plan_nu_svr_columns(X, y, splits, candidates, base_C, base_nu, base_kernel):
     return _stacked(groups, ('UB', 'mass', 'q'))
 
 
-class _NuGridSearchCV(BaseEstimator):
+class _NuGridSearchCV(_GridSearchCV):
     """What the two searches share; a subclass names its estimator type, whether an int `cv` is stratified, and its columns."""
-    _estimator_type = None
-    _stratified = True
+    _scoring = 'the estimator\'s own score'
+    _counts_failed = True
 
-    def __init__(self, estimator, param_grid, scoring=None, cv=5, refit=True):
-        self.estimator = estimator
-        self.param_grid = param_grid
-        self.scoring = scoring
-        self.cv = cv
-        self.refit = refit
+    @staticmethod
+    def _uses_batched(first, candidates, splits, y):
+        return uses_batched_nu_search(first, candidates)
 
-    def fit(self, X, y):
-        etype = self._estimator_type
-        if self.scoring is not None:
-            raise NotImplementedError('only the estimator\'s own score (scoring=None) is implemented')
-        if not isinstance(self.estimator, etype):
-            raise TypeError('estimator must be a %s' % etype.__name__)
-        X = np.ascontiguousarray(X, dtype=float)
-        y = self._targets(X, y)
-        candidates = parameter_grid(self.param_grid)
-        splits = check_cv_splits(self.cv, X, y, stratified=self._stratified)
-        base = dict(self.estimator.get_params(deep=False))
-        protos = [_make(etype, base, p) for p in candidates]   # the estimator's own checks on every candidate
-        self.batched_ = uses_batched_nu_search(protos[0], candidates)
-        fit = self._fit_batched if self.batched_ else self._fit_fallback
+    def _fits(self, *args):
         with warnings.catch_warnings(record=True) as caught:   # one ConvergenceWarning for the search, not one per fit
             warnings.simplefilter('always')
-            scores, self.n_iter_, self.status_ = fit(X, y, splits, candidates, base)
+            result = _GridSearchCV._fits(self, *args)
         for w in caught:
             if not issubclass(w.category, ConvergenceWarning):
                 warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
-        n_failed = int((self.status_ == 'failed').sum())
-        if n_failed == self.status_.size:
-            raise ValueError('all the %d fits failed' % n_failed)
-        if n_failed:
-            warnings.warn('%d fits failed out of a total of %d: their scores are nan' % (n_failed, self.status_.size), RuntimeWarning)
+        return result
+
+    def _account(self):
+        _GridSearchCV._account(self)
         if (self.status_ == 'stopped').any():
             warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
-        self.n_splits_ = len(splits)
-        self.cv_results_ = aggregate_scores(candidates, scores)
-        self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
-        self.best_params_ = candidates[self.best_index_]
-        self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
-        if self.refit:
-            self.best_estimator_ = _make(etype, base, self.best_params_).fit(X, y)
-        return self
 
-    def _fit_fallback(self, X, y, splits, candidates, base):
-        nc, ns = len(candidates), len(splits)
-        scores = np.full((nc, ns), np.nan)
-        n_iter = np.full((nc, ns), -1, dtype=np.int64)
-        status = np.full((nc, ns), 'failed', dtype=object)
-        for ci, p in enumerate(candidates):
-            for f, (tr, te) in enumerate(splits):
-                est = _make(self._estimator_type, base, {}).set_params(**p)
-                try:
-                    est.fit(X[tr], y[tr])
-                except ValueError:   # GridSearchCV's error_score: the fit is recorded as failed and scores nan
-                    continue
-                scores[ci, f] = est.score(X[te], y[te])
-                n_iter[ci, f], status[ci, f] = est.n_iter_, est.status_
-        return scores, n_iter, status
+    @staticmethod
+    def _fallback_fit(est, Xtr, ytr, Xte, yte):
+        try:
+            est.fit(Xtr, ytr)
+        except ValueError:   # GridSearchCV's error_score: the fit is recorded as failed and scores nan
+            return np.nan, [(-1, 'failed')]
+        return est.score(Xte, yte), [(est.n_iter_, est.status_)]
 
-    def _fit_batched(self, X, y, splits, candidates, base):
+    def _fit_batched(self, X, y, splits, candidates, base, first):
         proto = _make(self._estimator_type, base, {})
         name = type(self).__name__
         if proto.storage == 'stream':
@@ -224,11 +170,10 @@ class _NuGridSearchCV(BaseEstimator):
             var = np.concatenate((order, n + order)) if wide else order   # the variables in the panel's row order
             S = g['S'][:, order] if 'S' in g else None
             UB, q = g['UB'][:, var], g['q'][:, var] if 'q' in g else None
-            obj = KernelQuadratic(X[order], np.zeros(n), 'plain', g['kernel'], storage=proto.storage,
-                                  tune_placement=bool(proto.tune_placement), expected_products=proto.max_iter * ((m + 15) // 16))
-            try:
-                dev = obj.device_problem()
-                cap = column_cap(n, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle))
+            with device_panel(X[order], np.zeros(n), 'plain', g['kernel'], storage=proto.storage,
+                              tune_placement=bool(proto.tune_placement),
+                              expected_products=proto.max_iter * ((m + 15) // 16)) as (_, dev, free, slab):
+                cap = column_cap(n, free, slab)
                 if wide:   # (a column of 2n variables holds twice the vectors the cap counts)
                     cap = max(1, cap // 2)
                 for c0 in range(0, m, cap):
@@ -254,19 +199,7 @@ class _NuGridSearchCV(BaseEstimator):
                             est = self._fold_estimator(_make(self._estimator_type, base, candidates[ci]), X, y, tr, g['kernel'],
                                                        dict(res[j], x=x), float(held['r1'][j]), float(held['r2'][j]))
                             scores[ci, f] = est.score(X[te], y[te])
-                del dev
-            finally:
-                obj.release()
         return scores, n_iter, status
-
-    def decision_function(self, X):
-        return self.best_estimator_.decision_function(X)
-
-    def predict(self, X):
-        return self.best_estimator_.predict(X)
-
-    def score(self, X, y):
-        return self.best_estimator_.score(X, y)
 
 
 class NuSVCGridSearchCV(_NuGridSearchCV):
@@ -282,7 +215,7 @@ class NuSVCGridSearchCV(_NuGridSearchCV):
     `decision_function` and `score` are the best estimator's.
     """
     _estimator_type = NuSVC
-    _stratified = True
+    _type_error = 'estimator must be a NuSVC'
 
     @staticmethod
     def _targets(X, y):
@@ -312,6 +245,7 @@ class NuSVRGridSearchCV(_NuGridSearchCV):
     shuffling.  The attributes, warnings and errors after `fit` are `NuSVCGridSearchCV`'s, with `best_estimator_` a plain
     `NuSVR.fit` on all the data; `predict`, `decision_function` and `score` are the best estimator's."""
     _estimator_type = NuSVR
+    _type_error = 'estimator must be a NuSVR'
     _stratified = False
 
     @staticmethod

@@ -19,7 +19,7 @@ from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ._base import ConvergenceWarning
-from ._batched import _DeviceSimplexSolver, device_free_bytes, solve_batched
+from ._batched import _DeviceSimplexSolver, column_cap, device_free_bytes, solve_batched
 from .kernels import BaseEstimator, Kernel, gaussian
 
 __all__ = ['OneClassSVM', 'one_class_nu_path']
@@ -49,7 +49,6 @@ def _resolved(kernel, X):
 
 def _solve(proto, X, nus):
     """The duals of every nu on one panel of X, in solves of at most `column_cap` columns: (kernel_, [(column result, rho), ...])."""
-    from .model_selection import column_cap   # (imports this package's estimators)
     if proto.storage == 'stream':
         raise NotImplementedError('OneClassSVM needs a resident panel: storage \'f64\' or \'f32\'')
     if get_context().world != 1:

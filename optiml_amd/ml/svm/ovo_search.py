@@ -26,18 +26,13 @@ A (candidate, fold) with a pair that ends without a support vector is a failed f
 GridSearchCV's error_score): it scores NaN, has `n_iter_` -1 and `status_` 'failed', and one RuntimeWarning names the number of such
 fits; if every fit fails the search raises ValueError, as GridSearchCV does.
 """
-import warnings
-
 import numpy as np
 
 from ... import _lib
 from ...device import get_context
-from ...opti import KernelQuadratic
-from ._batched import MEMORY_SHARE, column_bytes, device_free_bytes, solve_batched, solver_kind
+from ._batched import MAX_COLUMNS, MEMORY_SHARE, column_bytes, device_panel, solve_batched, solver_kind
 from .coupling import MAX_CLASSES
-from .kernels import BaseEstimator
-from .model_selection import (BATCHED_KEYS, MAX_COLUMNS, SVCGridSearchCV, _base_params, _kernel_key, _make, aggregate_scores,
-                              check_cv_splits, parameter_grid)
+from .model_selection import BATCHED_KEYS, _base_params, _GridSearchCV, _kernel_key, _make
 from .onevsone import TILE, OneVsOneSVC, _DevicePairSolver, ovo_pairs, pairs_slab_bytes, sort_plan, uses_batched_ovo
 
 __all__ = ['OneVsOneGridSearchCV', 'ovo_vote', 'uses_batched_ovo_search', 'plan_ovo_columns', 'groups_per_solve']
@@ -147,7 +142,7 @@ def groups_per_solve(pairs, cls_tiles, n_pad, free_bytes, wide_slab_bytes):
     return int(max(0, min(MAX_COLUMNS // P, budget // per_group)))
 
 
-class OneVsOneGridSearchCV(BaseEstimator):
+class OneVsOneGridSearchCV(_GridSearchCV):
     """Exhaustive search over `param_grid` for an `OneVsOneSVC` scored by accuracy, as sklearn's GridSearchCV.  An int `cv` is
     StratifiedKFold(cv) without shuffling.
 
@@ -159,48 +154,19 @@ class OneVsOneGridSearchCV(BaseEstimator):
     search whose fits all fail raises ValueError.  `predict`, `decision_function` and `score` are the best estimator's.
     """
 
-    def __init__(self, estimator, param_grid, scoring=None, cv=5, refit=True):
-        self.estimator = estimator
-        self.param_grid = param_grid
-        self.scoring = scoring
-        self.cv = cv
-        self.refit = refit
+    _estimator_type = OneVsOneSVC
+    _type_error = 'estimator must be a OneVsOneSVC'
+    _column_records = True
+    _counts_failed = True
 
-    def fit(self, X, y):
-        if self.scoring is not None:
-            raise NotImplementedError('only accuracy scoring (scoring=None) is implemented')
-        if not isinstance(self.estimator, OneVsOneSVC):
-            raise TypeError('estimator must be a OneVsOneSVC')
-        X = np.ascontiguousarray(X, dtype=float)
-        y = np.asarray(y)
-        candidates = parameter_grid(self.param_grid)
-        splits = check_cv_splits(self.cv, X, y)
-        base = _base_params(self.estimator)
-        protos = [_make(OneVsOneSVC, base, p) for p in candidates]   # the estimator's own checks on every candidate
-        self.batched_ = uses_batched_ovo_search(protos[0], candidates, splits, y, get_context().world)
-        result = self._fit_batched(X, y, splits, candidates, protos[0]._prototype()) if self.batched_ else None
-        if result is None:   # another configuration, or one (candidate, fold) does not fit a solve: the per-fold calls
-            self.batched_ = False
-            result = SVCGridSearchCV._fit_fallback(self, X, y, splits, candidates, OneVsOneSVC, base)   # (reads nothing of self)
-        scores, self.n_iter_, self.status_ = result
-        fits = self.status_[:, :, 0]
-        n_failed = int((fits == 'failed').sum())
-        if n_failed == fits.size:
-            raise ValueError('all the %d fits failed' % n_failed)
-        if n_failed:
-            warnings.warn('%d fits failed out of a total of %d: their scores are nan' % (n_failed, fits.size), RuntimeWarning)
-        self.n_splits_ = len(splits)
-        self.cv_results_ = aggregate_scores(candidates, scores)
-        self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
-        self.best_params_ = candidates[self.best_index_]
-        self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
-        if self.refit:
-            self.best_estimator_ = _make(OneVsOneSVC, base, self.best_params_).fit(X, y)
-        return self
+    @staticmethod
+    def _uses_batched(first, candidates, splits, y):
+        return uses_batched_ovo_search(first, candidates, splits, y, get_context().world)
 
-    def _fit_batched(self, X, y, splits, candidates, proto):
+    def _fit_batched(self, X, y, splits, candidates, base, first):
         """(scores, n_iter, status), or None — decided on the first panel, before any solve — when the P columns of one (candidate,
         fold) do not fit the memory budget of a solve."""
+        proto = first._prototype()
         classes = np.unique(y)
         codes = np.searchsorted(classes, y)
         ncls = len(classes)
@@ -215,12 +181,9 @@ class OneVsOneGridSearchCV(BaseEstimator):
         Xp[index] = X
         kind = solver_kind(proto.optimizer)
         for gi, g in enumerate(plan['groups']):   # one panel at a time
-            obj = KernelQuadratic(Xp, -np.ones(n_pad), 'svc', g['kernel'], y=np.ones(n_pad), storage=proto.storage,
-                                  tune_placement=proto._streams_panel(), expected_products=proto.max_iter)
-            try:
-                dev = obj.device_problem()
-                take = groups_per_solve(pairs, cls_tiles, n_pad, device_free_bytes(),
-                                        _lib.load().bq_problem_wide_slab_bytes(dev.handle))
+            with device_panel(Xp, -np.ones(n_pad), 'svc', g['kernel'], y=np.ones(n_pad), storage=proto.storage,
+                              tune_placement=proto._streams_panel(), expected_products=proto.max_iter) as (_, dev, free, slab):
+                take = groups_per_solve(pairs, cls_tiles, n_pad, free, slab)
                 if take == 0 and gi == 0:
                     return None
                 take = max(1, take)
@@ -245,16 +208,4 @@ class OneVsOneGridSearchCV(BaseEstimator):
                         scores[ci, f] = float(held['n_correct'][j]) / float(held['n_held'][j])
                         for q in range(P):
                             n_iter[ci, f, q], status[ci, f, q] = res[j * P + q]['iter'], res[j * P + q]['status']
-                del dev
-            finally:
-                obj.release()
         return scores, n_iter, status
-
-    def decision_function(self, X):
-        return self.best_estimator_.decision_function(X)
-
-    def predict(self, X):
-        return self.best_estimator_.predict(X)
-
-    def score(self, X, y):
-        return self.best_estimator_.score(X, y)

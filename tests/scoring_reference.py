@@ -3,7 +3,7 @@ statement per figure, every floating sum taken by math.fsum, so exactly rounded.
 inputs u (one row of K coef per column), the boxes and the labels or targets of ONE column.
 
     svr_scores    msvr_score_kernel                       b, n_sv, sse, n_held
-    svc_scores    msvc_intercept / mheldout_kernel        b, n_sv, dec, lab
+    svc_scores    mscore_intercept / mheldout_kernel      b, n_sv, dec, lab
     nu_scores     msx_score_kernel<PAIRED>                n_held, n_correct, sse
     (the vote: ovo_decision(...).argmax, which test_gpu_ovo_search._check_against_host already states on the host)
 
@@ -46,7 +46,7 @@ def svr_scores(x, u, y, ub, eps, b_used=None):
 
 
 def svc_scores(x, u, sgn, ub, b_used=None, pair=None, ct=None, data_row=None):
-    """msvc_intercept and mheldout_kernel for one column of n rows.  b = fsum(sgn - u over x > 1e-6) / n_sv, NaN without one.
+    """mscore_intercept<false> and mheldout_kernel for one column of n rows.  b = fsum(sgn - u over x > 1e-6) / n_sv, NaN without one.
     dec = u + b_used (default b) and lab = sgn on the held rows (ub == 0), 0 on every other row.  With pair = (a, b), ct (the classes'
     tile rows of 256) and data_row (1: a data row, 0: a ghost row), the held rows are the data rows with ub == 0 of the panel rows of
     classes a and b only.  Returns b, n_sv, dec, lab."""

@@ -257,3 +257,25 @@ def test_size_case_column_follows_svc_fit(amd):
     svc = SVC(loss=hinge, dual=True, reg_intercept=True, kernel=kernel, C=1.0, max_iter=20).fit(X[tr], y[tr])
     np.testing.assert_allclose(res[j]['rows']['f'], svc.train_loss_history, rtol=1e-10)
     assert res[j]['iter'] == svc.optimizer.iter and res[j]['status'] == svc.optimizer.status
+
+
+def test_a_failed_solve_releases_the_panel(amd, monkeypatch):
+    """A batched solve that raises leaves no panel behind: `fit` raises the solve's error, and the one panel built so far was
+    released once on the way out (n = 120, two candidates, two folds; the error is a Python exception before any launch)."""
+    from optiml_amd.ml.svm import SVC, SVCGridSearchCV, model_selection
+    from optiml_amd.opti import KernelQuadratic
+    _, kw, _ = _search_case('binary-gauss-num-pg')
+    X, y = _blobs(120, 2)
+    calls, released = [], []
+
+    def failing_solve(*args, **kwargs):
+        calls.append(1)
+        raise RuntimeError('the solve failed')
+
+    release = KernelQuadratic.release
+    monkeypatch.setattr(model_selection, 'solve_batched', failing_solve)
+    monkeypatch.setattr(KernelQuadratic, 'release', lambda self: (released.append(self), release(self))[1])
+    search = SVCGridSearchCV(SVC(**kw), {'C': [0.1, 1.0]}, cv=2)
+    with pytest.raises(RuntimeError, match='the solve failed'):
+        search.fit(X, y)
+    assert len(calls) == 1 and len(released) == 1

@@ -1,4 +1,4 @@
-"""The held-out scoring kernels of bq_mscore.hip (msvr_score_kernel, msvc_intercept / mheldout_kernel, msx_score_kernel<PAIRED>,
+"""The held-out scoring kernels of bq_mscore.hip (msvr_score_kernel, mscore_intercept / mheldout_kernel, msx_score_kernel<PAIRED>,
 mvote_kernel / mvote_count_kernel) on pinned states and past 1024 rows, against tests/scoring_reference.py: the same statements in
 NumPy with exactly rounded sums.
 

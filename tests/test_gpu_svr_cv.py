@@ -326,3 +326,25 @@ def test_size_case_column_follows_svr_fit(amd):
     assert res[j]['iter'] == svr.optimizer.iter and res[j]['status'] == svr.optimizer.status
     assert res[j]['n_held'] == len(te)
     np.testing.assert_allclose(r2_from_sse(res[j]['sse'], y[te]), svr.score(X[te], y[te]), rtol=1e-9)
+
+
+def test_a_failed_solve_releases_the_panel(amd, monkeypatch):
+    """A batched solve that raises leaves no panel behind: `fit` raises the solve's error, and the one panel built so far was
+    released once on the way out (n = 120, two candidates, two folds; the error is a Python exception before any launch)."""
+    from optiml_amd.ml.svm import SVR, SVRGridSearchCV, model_selection
+    from optiml_amd.opti import KernelQuadratic
+    kw, _ = _search_case('gauss-num-pg')
+    X, y = _data(120)
+    calls, released = [], []
+
+    def failing_solve(*args, **kwargs):
+        calls.append(1)
+        raise RuntimeError('the solve failed')
+
+    release = KernelQuadratic.release
+    monkeypatch.setattr(model_selection, 'solve_batched', failing_solve)
+    monkeypatch.setattr(KernelQuadratic, 'release', lambda self: (released.append(self), release(self))[1])
+    search = SVRGridSearchCV(SVR(**kw), {'C': [0.5, 2.0]}, cv=2)
+    with pytest.raises(RuntimeError, match='the solve failed'):
+        search.fit(X, y)
+    assert len(calls) == 1 and len(released) == 1

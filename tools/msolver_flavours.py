@@ -9,7 +9,8 @@ n = 300 (two 256-row tiles, the second ragged); k = 5 on the 4-column product an
 ragged one); three classes of unequal sizes for the pairs (the class-sorted panel has ghost rows); two calibrators over disjoint
 held-out folds; the simplex solver in its three layouts (one group; labels with a start point; paired with a linear term), all with
 zero-width rows, and its two-group columns on the pairs' class-sorted panel with the routed product (a pair twice, a start point
-that is a vertex on one column); the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
+that is a vertex on one column); the held-out scores of the two-group columns (LABELS and PAIRED) and the one-vs-one vote of two
+(candidate, fold) groups on the pairs' panel; the runs are cut into several bq_msolver_run calls, and the columns stop at different iterations (the printed
 iteration counts), so pos[] renumbers.
 """
 import hashlib
@@ -33,6 +34,7 @@ from optiml_amd.ml.svm.coupling import chunk_calibrators, coupling_columns  # no
 from optiml_amd.ml.svm.kernels import GaussianKernel  # noqa: E402
 from optiml_amd.ml.svm.losses import epsilon_insensitive, hinge  # noqa: E402
 from optiml_amd.ml.svm.onevsone import _DevicePairSolver, sort_plan  # noqa: E402
+from optiml_amd.ml.svm.ovo_search import plan_ovo_columns  # noqa: E402
 from optiml_amd.opti import KernelQuadratic  # noqa: E402
 from optiml_amd.opti.unconstrained.stochastic import AdaGrad  # noqa: E402
 
@@ -210,6 +212,32 @@ def simplex2(paired):
     run_to_end(s, name)
     r1, r2, n_sv, n_free = s.offsets()
     show(name + '.offsets', r1=r1, r2=r2, n_sv=n_sv, n_free=n_free)
+    # every column is scored against one label / target vector: what is compared is the sums' bits
+    r1, r2, n_sv, n_free, n_held, n_correct, sse = s.heldout(t if paired else S[0])
+    show(name + '.heldout', r1=r1, r2=r2, n_sv=n_sv, n_free=n_free, n_held=n_held, n_correct=n_correct, sse=sse)
+    s.close()
+    obj.release()
+
+
+def pairs_vote():
+    """the one-vs-one vote on pairs()'s three unequal classes: two (candidate, fold) groups of the three pairs, group g holding out
+    the rows r with r % 2 == g, with different boxes"""
+    rs, X = data(13)
+    codes = np.repeat([0, 1, 2], [150, 100, 50])[rs.permutation(N)]
+    X = X + 0.8 * rs.standard_normal((3, D))[codes]
+    rows = np.arange(N)
+    splits = [(rows[rows % 2 != f], rows[rows % 2 == f]) for f in range(2)]
+    plan = plan_ovo_columns(codes, 3, splits, [{'C': 1.0}], 1.0, KERNEL)
+    g = plan['groups'][0]
+    Xp = np.zeros((plan['n_pad'], D))
+    Xp[plan['index']] = X
+    UB = g['UB'] * np.repeat([1.0, 0.5], 3)[:, None]
+    obj = KernelQuadratic(Xp, -np.ones(plan['n_pad']), 'svc', KERNEL, y=np.ones(plan['n_pad']))
+    s = _DevicePairSolver(obj.device_problem(), _lib.PG, plan['cls_tiles'], plan['pairs'] * 2, g['Y'], UB, 1e-4, 400)
+    run_to_end(s, 'svc_pairs_vote_k6')
+    b, n_sv, n_held, n_correct, pred = s.vote_heldout_pairs(plan['data_row'], np.repeat(np.arange(2, dtype=np.int32), 3), g['held'],
+                                                            predictions=True)
+    show('svc_pairs_vote_k6.vote', intercept=b, n_sv=n_sv, n_held=n_held, n_correct=n_correct, pred=pred)
     s.close()
     obj.release()
 
@@ -295,3 +323,4 @@ if __name__ == '__main__':
     simplex2(True)
     lagrangian()
     simplex2_blocks_pairs()
+    pairs_vote()
