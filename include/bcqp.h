@@ -672,6 +672,30 @@ int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, int *finished
 int bq_smo_get(bq_smo *s, int what, double *out);
 int bq_smo_destroy(bq_smo *s);
 
+/* ---- batched SMO: k duals on one Gram panel, one walker workgroup per column ----------------------------------------
+ * What OneVsRestClassifier(SVC(optimizer='smo')) / MultiOutputRegressor(SVR(optimizer='smo')) and GridSearchCV over them do by
+ * one SMOClassifier / SMORegression per column (optiml/ml/svm/smo.py:99-357, :386-797 through svm/_base.py:560-573, :1106-1120),
+ * each on a Gram matrix of its own.  Column c is the solver bq_smo_create(p, task, Y[c], C[c], epsilon[c], tol) makes, run without
+ * helper workgroups: same sweeps, same tie rule, same summation order, so its multipliers, error cache, thresholds and counts have
+ * the bits of that solver whatever the other columns do, in any batch and however the outer iterations are cut into runs.
+ * p: as bq_smo_create (kernel-built, resident panel, single-rank context).  Y: k x n labels +-1 (BQ_SVC) or targets (BQ_SVR);
+ * C: k; epsilon: k, or NULL (0); row_ptr / rows: NULL, or per column an ascending list rows[row_ptr[c] .. row_ptr[c + 1]) of the
+ * panel rows it trains on (the training rows of a cross-validation fold) — the column is then the solver of the sub-problem on those
+ * rows (its first listed +1 / -1 rows, or its first listed target, start the thresholds) and every other row keeps multiplier 0.
+ * BQ_ERR_BADARG: a streamed or non-kernel problem, world > 1, a list that is not strictly ascending or leaves [0, n), a list (or n)
+ * shorter than 2, a BQ_SVC column without both labels among its rows, C <= 0, epsilon < 0, tol <= 0 — all before any device call.
+ * Device memory: about 36 n (BQ_SVC) / 44 n (BQ_SVR) bytes per column. */
+typedef struct bq_msmo bq_msmo;
+int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *epsilon, double tol,
+                   const int64_t *row_ptr, const int32_t *rows, bq_msmo **out);
+/* At most max_outer launches; each advances every column still running by one outer iteration (smo.py:327-351 / :764-789), finished
+ * columns are not launched.  outer / finished / failed: k each — outer iterations done, the loop has terminated, and the walker
+ * met the reference's 'unexpected status' (smo.py:270-271, :756: such a column is finished too; the others go on). */
+int bq_msmo_run(bq_msmo *s, int64_t max_outer, int64_t *outer, int *finished, int *failed);
+/* column c's BQ_SMO_ALPHAS / BQ_SMO_ERRORS / BQ_SMO_SCALARS, as bq_smo_get (there are no helpers: BQ_SMO_STATS is BQ_ERR_BADARG) */
+int bq_msmo_get(bq_msmo *s, int c, int what, double *out);
+int bq_msmo_destroy(bq_msmo *s);
+
 /* ---- prediction (optiml/ml/svm/_base.py:284-287) ------------------------------- */
 /* out[t] = sum_m coef[m] * kernel(SV[m], Xt[t]) + intercept   (SV: m x d, Xt: t x d, row-major fp64) */
 int bq_decision_function(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m,

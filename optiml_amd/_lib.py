@@ -155,6 +155,11 @@ PROTOTYPES = {
     'bq_smo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),
     'bq_smo_get': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_smo_destroy': (C.c_int, [_vp]),
+    'bq_msmo_create': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.POINTER(_i64), C.POINTER(C.c_int32),
+                                 C.POINTER(_vp)]),
+    'bq_msmo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), _ip, _ip]),
+    'bq_msmo_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
+    'bq_msmo_destroy': (C.c_int, [_vp]),
     'bq_decision_function': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, _dp,
                                        C.c_double, _i64, _dp, _dp]),
     'bq_decision_function_multi': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, C.c_int, _dp, _dp,

@@ -20,7 +20,9 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <algorithm>
+#include <vector>
 
 #include "bq_c7.h"
 #include "bq_common.h"
@@ -595,6 +597,16 @@ __device__ void smo_helper(const KView<T> &K, int64_t n, const SupGlobal &G, con
 
 constexpr int SMO_B = SMO_T / 64;
 
+// The samples a full sweep visits: positions 0 .. m-1 of an ascending list of panel rows, or (rows == nullptr) every row
+// of the panel in order — the identity map, same code path.  Only the full-sweep driver speaks in positions; the support
+// list, the error cache and the thresholds index by panel row and never see an unlisted one (it is never examined, so
+// its multiplier stays 0).
+struct SmoRows {
+    const int *rows;
+    int64_t m;
+    __device__ __forceinline__ int64_t operator()(int64_t pos) const { return rows ? (int64_t)rows[pos] : pos; }
+};
+
 template <typename T>
 __device__ __forceinline__ double wave_dot(const KView<T> &K, const SupList &L, const SupGlobal &G, int nnz, int64_t s,
                                            const SmoSpec &P, unsigned int ver, bool ahead) {
@@ -780,8 +792,8 @@ __device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const S
 // of the intermediate ones — then the sequential examine of the batch reduces to storing the new errors and to a
 // first-minimum / first-maximum over the batch, which the lanes do at once.  Returns false (nothing written) when any
 // sample is a possible violator: the batch then goes down the sequential walk.
-__device__ __forceinline__ bool svc_quiet_batch(SmoShared &S, double *err, double C, double tol, int64_t i, int B, bool in,
-                                                double a2, double y2, double E2) {
+__device__ __forceinline__ bool svc_quiet_batch(SmoShared &S, double *err, double C, double tol, const SmoRows &R, int64_t i,
+                                                int B, bool in, double a2, double y2, double E2) {
     const int w = threadIdx.x & 63;
     const bool free2 = in && a2 > 0.0 && a2 < C;
     const bool up2 = in && ((y2 == 1.0 && a2 == 0.0) || (y2 == -1.0 && a2 == C));
@@ -803,15 +815,15 @@ __device__ __forceinline__ bool svc_quiet_batch(SmoShared &S, double *err, doubl
     const bool viol = in && (((free2 || up2) && bl - E2 > 2 * tol) || ((free2 || low2) && E2 - bu > 2 * tol));
     const bool fast = __ballot(viol) == 0ull;
     if (fast) {
-        if (in && !free2) err[i + w] = E2;
+        if (in && !free2) err[R(i + w)] = E2;
         if (w == 0) {
             if (up_moves) {
                 S.b_up = lo.v;
-                S.i_up = i + lo.i;
+                S.i_up = R(i + lo.i);
             }
             if (low_moves) {
                 S.b_low = hi.v;
-                S.i_low = i + hi.i;
+                S.i_low = R(i + hi.i);
             }
             S.go = 0;
             S.used = B;
@@ -820,14 +832,12 @@ __device__ __forceinline__ bool svc_quiet_batch(SmoShared &S, double *err, doubl
     return fast;
 }
 
+// The walker: one outer iteration (a full sweep over the samples R lists, or free-set sweeps until they stall) of one
+// dual, by one whole workgroup.  Without helpers (P.helpers == 0) it waits for no other workgroup at any point.
 template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
-                                                        double *a, double *err, SupGlobal G, double C,
-                                                        double tol, bq_smo_scal *sc, SmoSpec P) {
-    if (blockIdx.x != 0) {
-        smo_helper(K, n, G, P);
-        return;
-    }
+__device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const SmoRows &R, const double *__restrict__ y,
+                                             double *a, double *err, const SupGlobal &G, double C, double tol,
+                                             bq_smo_scal *sc, const SmoSpec &P) {
     __shared__ SmoShared S;
     __shared__ SupList L;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -853,11 +863,11 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
     sup_fill(L, G, S, [&](int j) { return __dmul_rn(a[j], y[j]); });
     spec_end(P, S, 0);
     if (sweep_all) {
-        int64_t i = 0;
+        int64_t i = 0;   // position in R
 #ifdef BQ_SMO_STAMPS
         unsigned long long stamp_acc[8] = {0}, stamp_cnt[8] = {0}, stamp_t = wall_clock64();
 #endif
-        while (i < n) {
+        while (i < R.m) {
             SMO_STAMP(7)   // loop tail of the previous round
             if (tid == 0 && P.helpers) {   // where the walk stands; a batch without a pair step doubles the look-ahead
                 const unsigned int cap = (unsigned int)(P.helpers * SMO_B);
@@ -872,9 +882,9 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
                 if (wv == 0) {
                     bool wide = false;
                     if (S.win > (unsigned int)SMO_B) {   // same wave as thread 0, which has just written it
-                        const int B = n - i < 64 ? (int)(n - i) : 64;
+                        const int B = R.m - i < 64 ? (int)(R.m - i) : 64;
                         const bool in = lane < B;
-                        const int64_t sw = i + lane;
+                        const int64_t sw = in ? R(i + lane) : 0;
                         const double a2 = in ? a[sw] : 0.0, y2 = in ? y[sw] : 0.0;
                         const bool free2 = in && a2 > 0.0 && a2 < C;
                         const bool need = in && !free2;
@@ -890,7 +900,7 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
                                     E2 = __longlong_as_double(bits) - y2;
                                 else if (in)
                                     E2 = err[sw];
-                                wide = svc_quiet_batch(S, err, C, tol, i, B, in, a2, y2, E2);
+                                wide = svc_quiet_batch(S, err, C, tol, R, i, B, in, a2, y2, E2);
                             }
                         }
                     }
@@ -905,8 +915,8 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
                 }
                 SMO_STAMP(1)       // a wide attempt that fell through
             }
-            const int64_t s = i + wv;
-            if (s < n) {   // wave-uniform
+            if (i + wv < R.m) {   // wave-uniform
+                const int64_t s = R(i + wv);
                 const double as = a[s], ys = y[s];
                 double E = 0.0;
                 if (!(as > 0.0 && as < C)) E = wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B) - ys;
@@ -918,11 +928,11 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
             }
             __syncthreads();
             SMO_STAMP(2)   // the sixteen errors of the batch
-            const int B = n - i < SMO_B ? (int)(n - i) : SMO_B;
+            const int B = R.m - i < SMO_B ? (int)(R.m - i) : SMO_B;
             // fast path: wave 0 examines the whole batch at once when it holds no possible violator
             if (wv == 0) {
                 const bool in = lane < B;
-                const bool fast = svc_quiet_batch(S, err, C, tol, i, B, in, in ? S.ba[lane] : 0.0, in ? S.by[lane] : 0.0,
+                const bool fast = svc_quiet_batch(S, err, C, tol, R, i, B, in, in ? S.ba[lane] : 0.0, in ? S.by[lane] : 0.0,
                                                   in ? S.bE[lane] : 0.0);
                 if (lane == 0) S.fast = fast ? 1 : 0;
             }
@@ -932,7 +942,7 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
                 int used = B;
                 S.go = 0;
                 for (int w = 0; w < B; ++w) {
-                    if (svc_examine(S, K, y, a, err, C, tol, i + w, S.ba[w], S.by[w], S.bE[w])) {
+                    if (svc_examine(S, K, y, a, err, C, tol, R(i + w), S.ba[w], S.by[w], S.bE[w])) {
                         S.go = 1;
                         used = w + 1;
                         break;
@@ -1012,6 +1022,45 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
             st_rel(&P.ctl[SPEC_DONE], P.epoch);
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
+                                                        double *a, double *err, SupGlobal G, double C,
+                                                        double tol, bq_smo_scal *sc, SmoSpec P) {
+    if (blockIdx.x != 0) {
+        smo_helper(K, n, G, P);
+        return;
+    }
+    smo_svc_walk(K, n, SmoRows{nullptr, n}, y, a, err, G, C, tol, sc, P);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Batched form: workgroup b is the walker of column live[b] of k independent duals on ONE panel.  Every piece of state
+// is per column (labels / targets, multipliers, error cache, support list, the bq_smo_scal record, C, epsilon, the row
+// list), there are no helpers, and so no workgroup ever reads a word another one writes: each runs to the end of its
+// sweep alone, and with more columns than CUs the workgroups simply queue.
+// ---------------------------------------------------------------------------------------------------------------
+struct SmoBatch {
+    const int *live;          // grid.x column numbers
+    const double *Y;          // k x n
+    double *A, *AM, *ERR;     // k x n each (AM: regression only)
+    int *NZ;                  // k x n
+    double *CF;               // k x n
+    const double *C, *eps;    // k
+    bq_smo_scal *sc;          // k
+    const int64_t *row_ptr;   // k + 1 offsets into rows, or nullptr: every column on all rows
+    const int *rows;
+    __device__ __forceinline__ SmoRows rows_of(int64_t c, int64_t n) const {
+        return row_ptr ? SmoRows{rows + row_ptr[c], row_ptr[c + 1] - row_ptr[c]} : SmoRows{nullptr, n};
+    }
+};
+
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svc_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
+    const int64_t c = Bt.live[blockIdx.x];
+    smo_svc_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.ERR + c * n, SupGlobal{Bt.NZ + c * n, Bt.CF + c * n},
+                 Bt.C[c], tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1246,14 +1295,11 @@ __device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const S
     __syncthreads();
 }
 
+// the regression walker (see smo_svc_walk)
 template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
-                                                        double *ap, double *an, double *err, SupGlobal G,
-                                                        double C, double eps, double tol, bq_smo_scal *sc, SmoSpec P) {
-    if (blockIdx.x != 0) {
-        smo_helper(K, n, G, P);
-        return;
-    }
+__device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const SmoRows &R, const double *__restrict__ y,
+                                             double *ap, double *an, double *err, const SupGlobal &G, double C, double eps,
+                                             double tol, bq_smo_scal *sc, const SmoSpec &P) {
     __shared__ SmoShared S;
     __shared__ SupList L;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1279,16 +1325,16 @@ __global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, c
     sup_fill(L, G, S, [&](int j) { return ap[j] - an[j]; });
     spec_end(P, S, 0);
     if (sweep_all) {
-        int64_t i = 0;
-        while (i < n) {
+        int64_t i = 0;   // position in R
+        while (i < R.m) {
             if (tid == 0 && P.helpers) {
                 const unsigned int cap = (unsigned int)(P.helpers * SMO_B);
                 if (!S.go) S.win = S.win * 2u < cap ? S.win * 2u : cap;
                 st_rlx64((long long *)&P.ctl[SPEC_POS], (long long)i);
                 st_rlx(&P.ctl[SPEC_WIN], S.win);
             }
-            const int64_t s = i + wv;
-            if (s < n) {   // wave-uniform
+            if (i + wv < R.m) {   // wave-uniform
+                const int64_t s = R(i + wv);
                 const double ps = ap[s], ms = an[s];
                 const bool cached = svr_kind(ps, ms, C) == 0;
                 double E = 0.0;
@@ -1301,11 +1347,11 @@ __global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, c
             }
             __syncthreads();
             if (tid == 0) {
-                const int B = n - i < SMO_B ? (int)(n - i) : SMO_B;
+                const int B = R.m - i < SMO_B ? (int)(R.m - i) : SMO_B;
                 int used = B;
                 S.go = 0;
                 for (int w = 0; w < B; ++w) {
-                    const bool took = svr_examine(S, K, y, ap, an, err, C, eps, tol, i + w, S.ba[w], S.bm[w], S.bE[w]);
+                    const bool took = svr_examine(S, K, y, ap, an, err, C, eps, tol, R(i + w), S.ba[w], S.bm[w], S.bE[w]);
                     if (took || S.fail) {
                         S.go = took ? 1 : 0;
                         used = w + 1;
@@ -1374,6 +1420,24 @@ __global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, c
             st_rel(&P.ctl[SPEC_DONE], P.epoch);
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
+                                                        double *ap, double *an, double *err, SupGlobal G,
+                                                        double C, double eps, double tol, bq_smo_scal *sc, SmoSpec P) {
+    if (blockIdx.x != 0) {
+        smo_helper(K, n, G, P);
+        return;
+    }
+    smo_svr_walk(K, n, SmoRows{nullptr, n}, y, ap, an, err, G, C, eps, tol, sc, P);
+}
+
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svr_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
+    const int64_t c = Bt.live[blockIdx.x];
+    smo_svr_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.AM + c * n, Bt.ERR + c * n,
+                 SupGlobal{Bt.NZ + c * n, Bt.CF + c * n}, Bt.C[c], Bt.eps[c], tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1548,6 +1612,214 @@ extern "C" int bq_smo_get(bq_smo *s, int what, double *out) {
             out[3] = (double)w[SPEC_REJ_CHK];
             break;
         }
+        default:
+            bq_set_error("bad argument: what");
+            return BQ_ERR_BADARG;
+    }
+    BQ_HIP(hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// batched SMO: k columns, one walker workgroup each (smo_*_batch_kernel)
+// ---------------------------------------------------------------------------------------------------------------
+struct bq_msmo {
+    bq_problem *p = nullptr;
+    bq_owner mem;   // every device buffer below
+    int task = BQ_SVC;
+    int k = 0;
+    int64_t n = 0;
+    double tol = 1e-3;
+    double *Y = nullptr, *A = nullptr, *AM = nullptr, *ERR = nullptr, *CF = nullptr;   // k x n each (AM: BQ_SVR only)
+    int *NZ = nullptr;                                                                 // k x n
+    double *C = nullptr, *eps = nullptr;                                               // k
+    bq_smo_scal *sc = nullptr;                                                         // k
+    int *live = nullptr;                                                               // k: the columns of the next launch
+    int64_t *row_ptr = nullptr;                                                        // k + 1, or null: all rows
+    int *rows = nullptr;
+    std::vector<bq_smo_scal> host;   // the k records as of the last launch
+    std::vector<int> failed, live_host;
+};
+
+extern "C" int bq_msmo_destroy(bq_msmo *s) {
+    if (s == nullptr) return BQ_OK;
+    hipSetDevice(s->p->ctx->device);
+    hipStreamSynchronize(s->p->ctx->stream);
+    bq_problem *p = s->p;
+    delete s;
+    bq_problem_unref(p);
+    return BQ_OK;
+}
+
+extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *epsilon,
+                              double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
+    BQ_ARG(p && Y && C && out, "NULL argument");
+    BQ_ARG(task == BQ_SVC || task == BQ_SVR, "task must be BQ_SVC or BQ_SVR");
+    BQ_ARG(k >= 1, "k must be >= 1");
+    BQ_ARG(p->kernel >= 0 && !p->streamed, "SMO needs a kernel-built problem with a resident Gram panel");
+    BQ_ARG(tol > 0.0, "tol must be > 0");
+    BQ_ARG((row_ptr == nullptr) == (rows == nullptr), "row_ptr and rows come together");
+    if (p->ctx->world > 1) {
+        bq_set_error("SMO walks the samples sequentially over the whole panel: use a single-rank context (replicas only)");
+        return BQ_ERR_BADARG;
+    }
+    bq_ctx *c = p->ctx;
+    const int64_t n = p->n;
+    BQ_ARG(n >= 2, "a column needs two rows");
+    std::vector<bq_smo_scal> host((size_t)k);
+    std::vector<int64_t> first((size_t)2 * k, -1);   // BQ_SVC: the first +1 / -1 row of the column's list
+    for (int col = 0; col < k; ++col) {
+        BQ_ARG(C[col] > 0.0, "C must be > 0");
+        BQ_ARG(epsilon == nullptr || epsilon[col] >= 0.0, "epsilon must be >= 0");
+        const double *y = Y + (int64_t)col * n;
+        const int64_t lo = row_ptr ? row_ptr[col] : 0, m = row_ptr ? row_ptr[col + 1] - lo : n;
+        BQ_ARG(lo >= 0 && m >= 2, "a row list needs two rows");
+        for (int64_t q = 0; q < m; ++q) {
+            const int64_t i = rows ? (int64_t)rows[lo + q] : q;
+            BQ_ARG(i >= 0 && i < n, "a listed row lies outside the panel");
+            BQ_ARG(q == 0 || rows == nullptr || i > (int64_t)rows[lo + q - 1], "a row list must be strictly ascending");
+            if (task == BQ_SVC) {
+                BQ_ARG(y[i] == 1.0 || y[i] == -1.0, "labels must be +1 / -1");
+                int64_t &f = first[2 * col + (y[i] == 1.0 ? 0 : 1)];
+                if (f < 0) f = i;
+            }
+        }
+        BQ_ARG(task != BQ_SVC || (first[2 * col] >= 0 && first[2 * col + 1] >= 0), "both classes are needed among a column's rows");
+        bq_smo_scal &h = host[col];
+        memset(&h, 0, sizeof(h));
+        h.sweep_all = 1;
+        if (task == BQ_SVC) {   // smo.py:119-128
+            h.b_up = -1.0;
+            h.b_low = 1.0;
+            h.i_up = first[2 * col];
+            h.i_low = first[2 * col + 1];
+        } else {                // smo.py:442-445
+            const int64_t i0 = rows ? rows[lo] : 0;   // the column's first sample holds both thresholds
+            const double e0 = epsilon ? epsilon[col] : 0.0;
+            h.b_up = y[i0] + e0;
+            h.b_low = y[i0] - e0;
+            h.i_up = h.i_low = i0;
+        }
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    bq_msmo *s = new bq_msmo();
+    s->p = p;
+    p->refs += 1;
+    s->task = task;
+    s->k = k;
+    s->n = n;
+    s->tol = tol;
+    s->host = host;
+    s->failed.assign((size_t)k, 0);
+    s->live_host.reserve((size_t)k);
+    const size_t kn = (size_t)k * (size_t)n;
+    hipError_t e = hipSuccess;
+    for (double **v : {&s->A, &s->ERR}) e = bq_dev_zeroed(e, s->mem, v, kn, c->stream);
+    if (task == BQ_SVR) e = bq_dev_zeroed(e, s->mem, &s->AM, kn, c->stream);
+    if (e == hipSuccess) e = s->mem.dev(&s->Y, kn);
+    if (e == hipSuccess) e = s->mem.dev(&s->CF, kn);
+    if (e == hipSuccess) e = s->mem.dev(&s->NZ, kn);
+    if (e == hipSuccess) e = s->mem.dev(&s->C, (size_t)k);
+    e = bq_dev_zeroed(e, s->mem, &s->eps, (size_t)k, c->stream);
+    if (e == hipSuccess) e = s->mem.dev(&s->sc, (size_t)k);
+    if (e == hipSuccess) e = s->mem.dev(&s->live, (size_t)k);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->Y, Y, sizeof(double) * kn, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->C, C, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && epsilon) e = hipMemcpyAsync(s->eps, epsilon, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
+    if (row_ptr) {
+        const size_t total = (size_t)row_ptr[k];
+        if (e == hipSuccess) e = s->mem.dev(&s->row_ptr, (size_t)k + 1);
+        if (e == hipSuccess) e = s->mem.dev(&s->rows, total);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->row_ptr, row_ptr, sizeof(int64_t) * (k + 1), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->rows, rows, sizeof(int) * total, hipMemcpyHostToDevice, c->stream);
+    }
+    if (task == BQ_SVC) {   // smo.py:119-128: the error cache of the two starting samples
+        static const double m1 = -1.0, p1 = 1.0;
+        for (int col = 0; col < k && e == hipSuccess; ++col) {
+            double *err = s->ERR + (size_t)col * n;
+            e = hipMemcpyAsync(err + first[2 * col], &m1, sizeof(double), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(err + first[2 * col + 1], &p1, sizeof(double), hipMemcpyHostToDevice, c->stream);
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(s->sc, s->host.data(), sizeof(bq_smo_scal) * k, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        bq_set_error("batched SMO setup failed: %s", hipGetErrorString(e));
+        bq_msmo_destroy(s);
+        return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    *out = s;
+    return BQ_OK;
+}
+
+template <typename T>
+static void msmo_launch(const bq_msmo *s, const KView<T> &K, const SmoBatch &Bt, int live, hipStream_t st) {
+    if (s->task == BQ_SVC)
+        smo_svc_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->tol);
+    else
+        smo_svr_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->tol);
+}
+
+extern "C" int bq_msmo_run(bq_msmo *s, int64_t max_outer, int64_t *outer, int *finished, int *failed) {
+    BQ_ARG(s && outer && finished && failed, "NULL argument");
+    BQ_ARG(max_outer > 0, "max_outer must be > 0");
+    bq_problem *p = s->p;
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    const SmoBatch Bt{s->live, s->Y, s->A, s->AM, s->ERR, s->NZ, s->CF, s->C, s->eps, s->sc, s->row_ptr, s->rows};
+    const int64_t ld = p->symmetric ? 0 : p->ld;
+    for (int64_t it = 0; it < max_outer; ++it) {
+        // finished columns are not launched: one workgroup per column still running, one outer iteration each
+        s->live_host.clear();
+        for (int col = 0; col < s->k; ++col)
+            if (!s->host[col].finished) s->live_host.push_back(col);
+        const int live = (int)s->live_host.size();
+        if (live == 0) break;
+        BQ_HIP(hipMemcpyAsync(s->live, s->live_host.data(), sizeof(int) * live, hipMemcpyHostToDevice, c->stream));
+        if (p->compact)
+            msmo_launch(s, KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, Bt, live, c->stream);
+        else if (p->storage == BQ_F64)
+            msmo_launch(s, KView<double>{(const double *)p->panel, ld}, Bt, live, c->stream);
+        else
+            msmo_launch(s, KView<float>{(const float *)p->panel, ld}, Bt, live, c->stream);
+        BQ_HIP(hipGetLastError());
+        BQ_HIP(hipMemcpyAsync(s->host.data(), s->sc, sizeof(bq_smo_scal) * s->k, hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+        for (int col : s->live_host)
+            if (s->host[col].err_flag) s->failed[col] = 1;   // 'unexpected status' (smo.py:270-271, :756): finished, the others go on
+    }
+    for (int col = 0; col < s->k; ++col) {
+        outer[col] = s->host[col].outer;
+        finished[col] = s->host[col].finished;
+        failed[col] = s->failed[col];
+    }
+    return BQ_OK;
+}
+
+extern "C" int bq_msmo_get(bq_msmo *s, int col, int what, double *out) {
+    BQ_ARG(s && out, "NULL argument");
+    BQ_ARG(col >= 0 && col < s->k, "column out of range");
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    const size_t at = (size_t)col * (size_t)s->n;
+    const bq_smo_scal &h = s->host[col];
+    switch (what) {
+        case BQ_SMO_ALPHAS:
+            BQ_HIP(hipMemcpyAsync(out, s->A + at, sizeof(double) * s->n, hipMemcpyDeviceToHost, c->stream));
+            if (s->task == BQ_SVR)
+                BQ_HIP(hipMemcpyAsync(out + s->n, s->AM + at, sizeof(double) * s->n, hipMemcpyDeviceToHost, c->stream));
+            break;
+        case BQ_SMO_ERRORS:
+            BQ_HIP(hipMemcpyAsync(out, s->ERR + at, sizeof(double) * s->n, hipMemcpyDeviceToHost, c->stream));
+            break;
+        case BQ_SMO_SCALARS:
+            out[0] = h.b_up;
+            out[1] = h.b_low;
+            out[2] = (double)h.i_up;
+            out[3] = (double)h.i_low;
+            out[4] = (double)h.steps;
+            out[5] = s->task == BQ_SVC ? -(h.b_low + h.b_up) / 2 : (h.b_low + h.b_up) / 2;
+            break;
         default:
             bq_set_error("bad argument: what");
             return BQ_ERR_BADARG;

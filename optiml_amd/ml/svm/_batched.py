@@ -20,6 +20,7 @@ from ...opti.unconstrained.stochastic import StochasticOptimizer, StochasticMome
 from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator, ConvergenceWarning
 from .kernels import GaussianKernel, LinearKernel, PolyKernel, SigmoidKernel, gaussian
 from .losses import squared_hinge, squared_epsilon_insensitive
+from .smo import SMOClassifier, SMORegression
 
 MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
 MAX_COLUMNS = 4096   # columns per batched solve at most (see column_cap)
@@ -57,6 +58,162 @@ def device_panel(*args, **kwargs):
         yield obj, dev, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle)
     finally:
         obj.release()
+
+
+def smo_column_bytes(n, task):
+    """Device state of one batched-SMO column on n rows (`bq_msmo_create`): labels or targets, multipliers (two vectors for
+    regression), error cache, the support list's coefficients (8 n each) and its indices (4 n)."""
+    return (36 if task == _lib.SVC else 44) * int(n)
+
+
+def smo_column_cap(n, task, free_bytes):
+    """Columns one batched SMO solve may take with `free_bytes` of device memory free after the panel: MEMORY_SHARE of it over
+    `smo_column_bytes`; at most MAX_COLUMNS, at least 1.  Larger sets run in several solves; columns are independent, so the
+    split changes no bits."""
+    return int(max(1, min(MAX_COLUMNS, int(free_bytes * MEMORY_SHARE) // smo_column_bytes(n, task))))
+
+
+# The smallest number of columns that takes the batched SMO path when nothing forces either one (`batch_smo` of the estimators and
+# of the search).  A batched walker has no helper workgroups, so one column is slower than the single solver (n = 20 000: 0.242 s
+# against 0.167 s); two columns already are not (0.234 s against 2 x 0.167 s), and the batch's time stays flat up to one column per
+# CU (profiles/smo_batched/).  The measured break-even is 2; the constant is 4 so that the fits of two and three columns, which
+# earlier commits (and tests/test_gpu_multioutput.py, on three targets) know as per-column fits, stay that — same bits either way.
+SMO_MIN_COLUMNS = 4
+
+
+def takes_batched_smo(k, force=None):
+    """The dispatch between the batched SMO solve and one single solver per column for k columns of a configuration the batched
+    path covers: `force` (True / False) where given, else k >= SMO_MIN_COLUMNS.  Both give the same bits."""
+    return bool(force) if force is not None else int(k) >= SMO_MIN_COLUMNS
+
+
+class _DeviceSMOSolver:
+    """`bq_msmo_create`: k SMO columns on one kernel problem, one walker workgroup each.  task: `_lib.SVC` (Y: k x n labels +-1) or
+    `_lib.SVR` (Y: k x n targets); C: k; epsilon: k or None (0); rows: None (every column trains on all rows) or k ascending
+    arrays of panel rows."""
+
+    def __init__(self, problem, task, Y, C_, epsilon, tol, rows=None):
+        self._lib = _lib.load()
+        Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=float)
+        self.k, self.n = Y.shape
+        self.task = task
+        self._h = C.c_void_p()
+        C_ = _lib.as_f64(np.broadcast_to(np.asarray(C_, dtype=float), (self.k,)), self.k, 'C')
+        eps = None if epsilon is None else _lib.as_f64(np.broadcast_to(np.asarray(epsilon, dtype=float), (self.k,)), self.k,
+                                                       'epsilon')
+        row_ptr = flat = None
+        if rows is not None:
+            if len(rows) != self.k:
+                raise ValueError('%d row lists for %d columns' % (len(rows), self.k))
+            row_ptr = np.zeros(self.k + 1, dtype=np.int64)
+            row_ptr[1:] = np.cumsum([len(r) for r in rows])
+            flat = _lib.as_i32(np.concatenate([np.asarray(r, dtype=np.int64) for r in rows]))
+        _lib.check(self._lib.bq_msmo_create(problem.handle, task, self.k, _lib.ptr(Y), _lib.ptr(C_), _lib.ptr(eps), float(tol),
+                                            None if row_ptr is None else row_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            None if flat is None else flat.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            C.byref(self._h)))
+
+    def run(self, max_outer):
+        """at most max_outer launches; (outer, finished, failed), k entries each"""
+        outer = np.zeros(self.k, dtype=np.int64)
+        fin, failed = np.zeros(self.k, dtype=np.int32), np.zeros(self.k, dtype=np.int32)
+        _lib.check(self._lib.bq_msmo_run(self._h, int(max_outer), outer.ctypes.data_as(C.POINTER(C.c_int64)), _lib.iptr(fin),
+                                         _lib.iptr(failed)))
+        return outer, fin.astype(bool), failed.astype(bool)
+
+    def get(self, c, what):
+        size = {_lib.SMO_ALPHAS: self.n * (2 if self.task == _lib.SVR else 1), _lib.SMO_ERRORS: self.n, _lib.SMO_SCALARS: 6}
+        out = np.empty(size.get(what, 0))
+        _lib.check(self._lib.bq_msmo_get(self._h, int(c), what, _lib.ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.bq_msmo_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, chunk=64):
+    """Run k SMO columns to the end, `cap` columns per solve at most (default: `smo_column_cap` of the memory free now): per column a
+    dict of what `SMO.minimize` leaves — alphas (classification) or alphas_p / alphas_n (regression), b, errors, b_up, b_low,
+    b_up_idx, b_low_idx, iter, steps.  A column that fails raises what the single fit raises."""
+    Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=float)
+    k, n = Y.shape
+    C_ = np.broadcast_to(np.asarray(C_, dtype=float), (k,))
+    epsilon = None if epsilon is None else np.broadcast_to(np.asarray(epsilon, dtype=float), (k,))
+    cap = smo_column_cap(n, task, device_free_bytes()) if cap is None else int(cap)
+    out = []
+    for c0 in range(0, k, cap):
+        sl = slice(c0, min(k, c0 + cap))
+        solver = _DeviceSMOSolver(problem, task, Y[sl], C_[sl], None if epsilon is None else epsilon[sl], tol,
+                                  None if rows is None else rows[sl])
+        try:
+            fin = np.zeros(solver.k, dtype=bool)
+            while not fin.all():
+                outer, fin, failed = solver.run(chunk)
+            if failed.any():   # bq_smo_run's error for that column
+                raise _lib.BcqpError(_lib.ERR_NONFINITE, 'SMO reached an unexpected status (no threshold index)')
+            for c in range(solver.k):
+                a, sc = solver.get(c, _lib.SMO_ALPHAS), solver.get(c, _lib.SMO_SCALARS)
+                r = dict(b_up=sc[0], b_low=sc[1], b_up_idx=int(sc[2]), b_low_idx=int(sc[3]), steps=int(sc[4]), b=sc[5],
+                         iter=int(outer[c]), errors=solver.get(c, _lib.SMO_ERRORS))
+                if task == _lib.SVC:
+                    r['alphas'] = a
+                else:
+                    r['alphas_p'], r['alphas_n'] = a[:n].copy(), a[n:].copy()
+                out.append(r)
+        finally:
+            solver.close()
+    return out
+
+
+def smo_optimizer(quad, X, y, kernel, C_, tol, r, epsilon=None, verbose=False):
+    """The `SMOClassifier` (epsilon None) / `SMORegression` that `minimize()` on `quad` leaves, from its column's result `r` of
+    `solve_batched_smo` — constructed, not run."""
+    opt = SMOClassifier(quad, X, y, None, kernel, C_, tol, verbose) if epsilon is None else \
+        SMORegression(quad, X, y, None, kernel, C_, epsilon, tol, verbose)
+    for name, value in r.items():
+        setattr(opt, name, value)
+    opt.helper_stats = {'helpers': 0, 'delivered': 0, 'rejected_list_hash': 0, 'rejected_checksum': 0}
+    if isinstance(kernel, LinearKernel):
+        opt.w = opt._coefficients() @ opt.X
+    return opt
+
+
+def fitted_smo_svc(est, quad, r, X, y):
+    """Make `est`, a fresh SVC of the configuration, the SVC that SVC.fit's SMO branch on (X, y: +-1) leaves, intercept included,
+    from its column's result `r` of `solve_batched_smo`; quad: the class's view of the shared panel.  Returns the support mask."""
+    est.obj = quad
+    est.optimizer = smo_optimizer(quad, X, y, est.kernel, est.C, est.tol, r, verbose=est.verbose)
+    sv = _svc_attributes(est, X, y, est.optimizer.alphas)
+    if isinstance(est.kernel, LinearKernel):
+        est.coef_ = est.optimizer.w
+    est.intercept_ = est.optimizer.b
+    return sv
+
+
+def fitted_smo_svr(est, quad, r, X, y):
+    """`fitted_smo_svc` for an SVR on the targets y; quad: the target's view of the shared panel."""
+    est.obj = quad
+    est.optimizer = smo_optimizer(quad, X, y, est.kernel, est.C, est.tol, r, epsilon=est.epsilon, verbose=est.verbose)
+    sv = _svr_attributes(est, X, y, np.concatenate((est.optimizer.alphas_p, est.optimizer.alphas_n)))
+    if isinstance(est.kernel, LinearKernel):
+        est.coef_ = est.optimizer.w
+    est.intercept_ = est.optimizer.b
+    return sv
+
+
+def uses_batched_smo(est, loss, world):
+    """What `uses_batched_smo_path` (multiclass.py) and `uses_batched_smo_svr_path` (multioutput.py) share: `est`'s configuration
+    takes the SMO branch of its `fit` (dual, optimizer 'smo' or `SMO`, the loss `loss`, an unregularised intercept) on a resident
+    panel ('f64' / 'f32') in a single-rank context (`world` ranks)."""
+    return bool(est._is_smo() and est.loss == loss and not est.reg_intercept and est.storage in ('f64', 'f32') and int(world) == 1)
 
 
 def solver_kind(optimizer):
@@ -530,10 +687,11 @@ def fitted_svc(est, quad, r, X, y, pos=None):
     return _svc_attributes(est, X, y)
 
 
-def _svc_attributes(est, X, y):
-    """What SVC.fit derives from `est.optimizer.x` (y: +-1) but the intercept; returns the support mask."""
+def _svc_attributes(est, X, y, alphas=None):
+    """What SVC.fit derives from `est.optimizer.x` (y: +-1; alphas: the multipliers of an optimizer that keeps them elsewhere) but
+    the intercept; returns the support mask."""
     est.classes_ = np.array([0, 1])   # OneVsRestClassifier and OneVsOneClassifier fit each SVC on 0 / 1 labels
-    est.alphas_ = est.optimizer.x
+    est.alphas_ = est.optimizer.x if alphas is None else alphas
     sv = est.alphas_ > 1e-6
     est.support_ = np.arange(len(y))[sv]
     est.support_vectors_ = X[sv]
@@ -606,9 +764,10 @@ def fitted_svr(est, quad, r, X, y):
     return _svr_attributes(est, X, y)
 
 
-def _svr_attributes(est, X, y):
-    """What SVR.fit derives from `est.optimizer.x` (2n) but the intercept; returns the support mask."""
-    est.alphas_ = est.optimizer.x
+def _svr_attributes(est, X, y, alphas=None):
+    """What SVR.fit derives from `est.optimizer.x` (2n; alphas: the multipliers of an optimizer that keeps them elsewhere) but
+    the intercept; returns the support mask."""
+    est.alphas_ = est.optimizer.x if alphas is None else alphas
     alphas_p, alphas_n = np.split(est.alphas_, 2)
     sv = np.logical_or(alphas_p > 1e-6, alphas_n > 1e-6)
     est.support_ = np.arange(len(y))[sv]

@@ -26,17 +26,20 @@ import warnings
 
 import numpy as np
 
+from ... import _lib
 from ...device import get_context
 from ._base import SVC, SVR
 from ._batched import (MAX_COLUMNS, MEMORY_SHARE, _DeviceSVRSolver, _gram_matmat, column_cap, device_panel,  # noqa: F401
-                       fitted_svr, intercept, solve_batched, solver_kind, svr_intercept)
+                       fitted_svr, intercept, smo_column_cap, solve_batched, solve_batched_smo, solver_kind, svr_intercept,
+                       takes_batched_smo)
 from .kernels import BaseEstimator, LinearKernel
-from .multiclass import OneVsRestSVC, uses_batched_path, binarize
+from .multiclass import OneVsRestSVC, uses_batched_path, uses_batched_smo_path, binarize
 from .multioutput import uses_batched_svr_path
 from .onevsone import OneVsOneSVC
 
 __all__ = ['SVCGridSearchCV', 'SVRGridSearchCV', 'parameter_grid', 'check_cv_splits', 'plan_columns', 'plan_svr_columns',
-           'aggregate_scores', 'uses_batched_search', 'uses_batched_svr_search', 'r2_from_sse']
+           'plan_smo_columns', 'aggregate_scores', 'uses_batched_search', 'uses_batched_smo_search', 'uses_batched_svr_search',
+           'r2_from_sse']
 
 BATCHED_KEYS = frozenset({'C', 'kernel'})
 SVR_BATCHED_KEYS = frozenset({'C', 'epsilon', 'kernel'})
@@ -162,6 +165,45 @@ def plan_columns(X, y, splits, candidates, base_C, base_kernel, multiclass):
                 g['Y'].append(np.where(y == pos, 1., -1.))
                 g['UB'].append(ub)
     return _stacked(groups, ('Y', 'UB')), folds
+
+
+def uses_batched_smo_search(estimator, candidates, world):
+    """True when `SVCGridSearchCV` can solve every (candidate, fold, class) as one batched-SMO column on shared panels: the
+    estimator (an `SVC` or an `OneVsRestSVC`) is on `OneVsRestSVC`'s batched SMO path (`uses_batched_smo_path`) and the grid varies
+    only C and kernel."""
+    if not isinstance(estimator, (SVC, OneVsRestSVC)):
+        return False
+    if any(not set(p) <= BATCHED_KEYS for p in candidates):
+        return False
+    return uses_batched_smo_path(_prototype(estimator), world)
+
+
+def plan_smo_columns(X, y, splits, candidates, base_C, base_kernel, multiclass):
+    """The batched SMO search's panels and columns, as `plan_columns` groups them: (groups, folds) with groups a list of dicts
+    {kernel: the resolved kernel of the panel, cols: [(candidate, fold, class row, C)], Y: m x n labels +-1, rows: per column the
+    fold's training rows, ascending} — a column trains on its row list instead of carrying a zero box.  None when a fold's
+    training rows miss a class (its own fit has other `classes_`, or none): the search then runs the per-fold calls."""
+    X = np.ascontiguousarray(X, dtype=float)
+    y = np.asarray(y)
+    classes = np.unique(y)
+    if any(not np.array_equal(np.unique(y[tr]), classes) for tr, _ in splits):
+        return None
+    folds = [_fold_labels(y[tr], multiclass) for tr, _ in splits]
+    groups, index = [], {}
+    for ci, p in enumerate(candidates):
+        C = p.get('C', base_C)
+        kernel = p.get('kernel', base_kernel)
+        for f, (tr, _) in enumerate(splits):
+            g = _group_of(groups, index, kernel, X[tr], ('Y',))
+            g.setdefault('rows', [])
+            rows = np.unique(tr)
+            if len(rows) != len(tr):
+                return None   # a repeated training row is another problem than a row list's
+            for r, pos in enumerate(folds[f][1]):
+                g['cols'].append((ci, f, r, C))
+                g['Y'].append(np.where(y == pos, 1., -1.))
+                g['rows'].append(rows)
+    return _stacked(groups, ('Y',)), folds
 
 
 def aggregate_scores(candidates, scores):
@@ -302,16 +344,92 @@ class SVCGridSearchCV(_GridSearchCV):
     `best_score_`, `n_splits_`, `best_estimator_` (a plain `fit` on all the data, refit=True), and per column `n_iter_` / `status_`
     of shape (candidates, splits, classes) (-1 / '' where a fit has no such record).  `batched_` says which path ran.
     `predict`, `decision_function` and `score` are the best estimator's.
+
+    An estimator on the batched SMO path (`uses_batched_smo_search`) has every (candidate, fold, class) solved as one column of
+    `bq_msmo_*` whose row list is the fold's training rows; `smo_` says so, and `batch_smo` (None, True, False) forces that choice
+    where the configuration allows it (None: by the number of columns, `takes_batched_smo`).  A fold that misses a class runs the
+    per-fold calls.
     """
     _estimator_type = (SVC, OneVsRestSVC, OneVsOneSVC)
     _type_error = 'estimator must be an SVC, a OneVsRestSVC or a OneVsOneSVC'
     _column_records = True
+    batch_smo = None
+
+    def _uses_batched(self, first, candidates, splits, y):
+        world = get_context().world
+        self.smo_ = False
+        if uses_batched_smo_search(first, candidates, world):
+            classes = 1 if len(np.unique(y)) == 2 or not isinstance(first, OneVsRestSVC) else len(np.unique(y))
+            self.smo_ = takes_batched_smo(len(candidates) * len(splits) * classes, self.batch_smo)
+        return self.smo_ or uses_batched_search(first, candidates, world)
+
+    def _fit_batched_smo(self, X, y, splits, candidates, proto_est):
+        """every (candidate, fold, class) one batched-SMO column on the panel of its resolved kernel; None (before any solve) when
+        a fold misses a class"""
+        multiclass = isinstance(proto_est, OneVsRestSVC)
+        proto = _prototype(proto_est)
+        n = len(y)
+        nc, ns = len(candidates), len(splits)
+        plan = plan_smo_columns(X, y, splits, candidates, proto.C, proto.kernel, multiclass)
+        if plan is None:
+            self.smo_ = False
+            return None
+        groups, folds = plan
+        width = max(len(rows) for _, rows in folds)
+        n_iter = np.full((nc, ns, width), -1, dtype=np.int64)
+        status = np.full((nc, ns, width), '', dtype=object)   # an SMO fit records no status (`_fallback_fit`)
+        dec = [[[None] * len(folds[f][1]) for f in range(ns)] for _ in range(nc)]
+        for g in groups:   # one panel at a time, built as SVC.fit's SMO branch builds it
+            m = len(g['cols'])
+            with device_panel(X, -np.ones(n), 'svc', g['kernel'], y=g['Y'][0], storage=proto.storage, rank_one=False,
+                              compact=False) as (_, dev, free, slab):
+                cap = smo_column_cap(n, _lib.SVC, free - slab)
+                res = solve_batched_smo(dev, _lib.SVC, g['Y'], [C for _, _, _, C in g['cols']], None, proto.tol, rows=g['rows'],
+                                        cap=cap)
+                W = np.zeros((m, n))
+                for j, r in enumerate(res):
+                    sv = r['alphas'] > 1e-6
+                    W[j][sv] = r['alphas'][sv] * g['Y'][j][sv]
+                U = _gram_matmat(dev, W, wide=True)   # without the rank-one term the panel is K: K w on every row
+                for j, (ci, f, row, C) in enumerate(g['cols']):
+                    n_iter[ci, f, row] = res[j]['iter']
+                    te = splits[f][1]
+                    kernel = candidates[ci].get('kernel', proto.kernel)
+                    if proto.storage == 'f64' and not isinstance(getattr(kernel, 'gamma', None), str):
+                        dec[ci][f][row] = U[j][te] + res[j]['b']   # the fp64 panel holds the decision kernel's values
+                    else:
+                        # decision_function resolves a string gamma on the support vectors and evaluates the kernel in fp64, not
+                        # from an fp32 panel: score through the fold's SVC
+                        sv = W[j] != 0
+                        est = copy.copy(proto)
+                        est.kernel, est.C = kernel, C
+                        est.support_vectors_ = X[sv]
+                        est.dual_coef_ = W[j][sv]
+                        if isinstance(kernel, LinearKernel):
+                            est.coef_ = np.dot(est.dual_coef_, est.support_vectors_)
+                        est.intercept_ = res[j]['b']
+                        dec[ci][f][row] = est.decision_function(X[te])
+        self._cv_decisions = dec
+        return self._scores(dec, folds, splits, y), n_iter, status
 
     @staticmethod
-    def _uses_batched(first, candidates, splits, y):
-        return uses_batched_search(first, candidates, get_context().world)
+    def _scores(dec, folds, splits, y):
+        """accuracy of every (candidate, fold) from its columns' held-out decision values"""
+        scores = np.empty((len(dec), len(splits)))
+        for ci in range(len(dec)):
+            for f, (_, te) in enumerate(splits):
+                classes = folds[f][0]
+                D = dec[ci][f]
+                if len(D) == 1:
+                    pred = np.where(D[0] > 0, classes[-1], classes[0])
+                else:
+                    pred = classes[np.argmax(np.stack(D, axis=1), axis=1)]
+                scores[ci, f] = float(np.mean(pred == y[te]))
+        return scores
 
     def _fit_batched(self, X, y, splits, candidates, base, proto_est):
+        if self.smo_:
+            return self._fit_batched_smo(X, y, splits, candidates, proto_est)
         multiclass = isinstance(proto_est, OneVsRestSVC)
         proto = _prototype(proto_est)
         n = len(y)
@@ -359,17 +477,7 @@ class SVCGridSearchCV(_GridSearchCV):
                             est.intercept_ = b
                             dec[ci][f][row] = est.decision_function(X[te])
         self._cv_decisions = dec
-        scores = np.empty((nc, ns))
-        for ci in range(nc):
-            for f, (_, te) in enumerate(splits):
-                classes = folds[f][0]
-                D = dec[ci][f]
-                if len(D) == 1:
-                    pred = np.where(D[0] > 0, classes[-1], classes[0])
-                else:
-                    pred = classes[np.argmax(np.stack(D, axis=1), axis=1)]
-                scores[ci, f] = float(np.mean(pred == y[te]))
-        return scores, n_iter, status
+        return self._scores(dec, folds, splits, y), n_iter, status
 
 
 def uses_batched_svr_search(estimator, candidates, world):

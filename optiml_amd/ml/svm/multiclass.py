@@ -19,12 +19,14 @@ import numpy as np
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
+from ... import _lib
 from ._batched import (ClassQuadratic, DecisionBatch, _DeviceALSolver, _DeviceMultiSolver, _MultiClassSVC, _gram_matmat,
-                       _svc_attributes, fitted_lagrangian, fitted_svc, intercept, lagrangian_columns, solve_batched,
-                       solve_batched_al, solver_kind, uses_batched_decision, uses_batched_lagrangian)
+                       _svc_attributes, fitted_lagrangian, fitted_smo_svc, fitted_svc, intercept, lagrangian_columns,
+                       solve_batched, solve_batched_al, solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision,
+                       uses_batched_lagrangian, uses_batched_smo)
 from .losses import Hinge, SquaredHinge
 
-__all__ = ['OneVsRestSVC', 'uses_batched_path', 'uses_batched_lagrangian_path', 'binarize']
+__all__ = ['OneVsRestSVC', 'uses_batched_path', 'uses_batched_lagrangian_path', 'uses_batched_smo_path', 'binarize']
 
 
 def uses_batched_path(svc, world):
@@ -42,6 +44,14 @@ def uses_batched_lagrangian_path(svc, world, ndim=None):
     the hinge or squared hinge loss, a resident panel ('f64' / 'f32'), a single-rank context (`world` ranks), either intercept;
     ndim (the number of samples, when given): more than 3, as the optimizers run step by step on smaller duals."""
     return uses_batched_lagrangian(svc, (Hinge, SquaredHinge), world, ndim)
+
+
+def uses_batched_smo_path(svc, world):
+    """True when `OneVsRestSVC` can solve the classes of `svc`'s configuration together by the batched SMO solver (`bq_msmo_*`, one
+    walker workgroup per class on one panel): `dual`, optimizer 'smo' or `SMO`, the hinge loss, `reg_intercept=False`, a resident
+    panel ('f64' / 'f32') and a single-rank context (`world` ranks).  Whether a fit then does is a matter of speed alone
+    (`takes_batched_smo`): both ways give the same bits."""
+    return uses_batched_smo(svc, Hinge, world)
 
 
 def binarize(y):
@@ -66,21 +76,47 @@ class OneVsRestSVC(_MultiClassSVC):
     `batched_decision_`: True when `decision_function` and `predict` take every class's values from one fused pass over the kernel
     values of the union of the support vectors (`uses_batched_decision`) instead of one call per estimator.  The stored batch
     (`decision_batch_`) describes the estimators as `fit` left them.
+
+    `smo_`: the classes were solved together by the batched SMO solver (`uses_batched_smo_path`).  `batch_smo` (None, True,
+    False) forces that choice where the configuration allows it; None leaves it to the number of classes (`takes_batched_smo`).
     """
+    batch_smo = None
 
     def fit(self, X, y):
         X = np.ascontiguousarray(X, dtype=float)
         self.classes_, Y = binarize(y)
         proto = self._prototype()
         self.lagrangian_ = uses_batched_lagrangian_path(proto, get_context().world, X.shape[0])
-        self.batched_ = self.lagrangian_ or uses_batched_path(proto, get_context().world)
+        self.smo_ = uses_batched_smo_path(proto, get_context().world) and takes_batched_smo(len(Y), self.batch_smo)
+        self.batched_ = self.lagrangian_ or self.smo_ or uses_batched_path(proto, get_context().world)
         self.batched_decision_ = uses_batched_decision(proto.kernel, len(Y), get_context().world, self.batched_)
         self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, (Yc > 0).astype(int)) for Yc in Y]
             return self
-        self.estimators_ = (self._fit_lagrangian if self.lagrangian_ else self._fit_batched)(proto, X, Y)
+        fit = self._fit_smo if self.smo_ else self._fit_lagrangian if self.lagrangian_ else self._fit_batched
+        self.estimators_ = fit(proto, X, Y)
         return self
+
+    def _fit_smo(self, proto, X, Y):
+        """SVC.fit's SMO branch for every class on one panel: its KernelQuadratic (rank_one=False, compact=False), one batched
+        solve; the intercepts are the solver's."""
+        k, n = Y.shape
+        obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Y[0], storage=proto.storage, rank_one=False, compact=False)
+        res = solve_batched_smo(obj.device_problem(), _lib.SVC, Y, proto.C, None, proto.tol)
+        ests = [self._prototype() for _ in range(k)]
+        coefs = []
+        for c, est in enumerate(ests):
+            sv = fitted_smo_svc(est, ClassQuadratic(obj, Y[c]), res[c], X, Y[c])
+            w = np.zeros(n)
+            w[sv] = est.dual_coef_
+            coefs.append(w)
+            if self.verbose:
+                print('class %r: %d outer iterations, %d pair steps' % (self.classes_[c if len(self.classes_) > 2 else 1],
+                                                                        est.optimizer.iter, est.optimizer.steps))
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
+        return ests
 
     def _fit_batched(self, proto, X, Y):
         k, n = Y.shape

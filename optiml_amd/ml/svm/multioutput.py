@@ -19,12 +19,14 @@ import numpy as np
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
+from ... import _lib
 from ._batched import (DecisionBatch, TargetQuadratic, _DeviceALSolver, _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat,
-                       _svr_attributes, fitted_lagrangian, fitted_svr, lagrangian_columns, solve_batched, solve_batched_al,
-                       solver_kind, svr_intercept, uses_batched_decision, uses_batched_lagrangian)
+                       _svr_attributes, fitted_lagrangian, fitted_smo_svr, fitted_svr, lagrangian_columns, solve_batched,
+                       solve_batched_al, solve_batched_smo, solver_kind, svr_intercept, takes_batched_smo, uses_batched_decision,
+                       uses_batched_lagrangian, uses_batched_smo)
 from .losses import EpsilonInsensitive, SquaredEpsilonInsensitive
 
-__all__ = ['MultiOutputSVR', 'uses_batched_svr_path', 'uses_batched_lagrangian_svr_path']
+__all__ = ['MultiOutputSVR', 'uses_batched_svr_path', 'uses_batched_lagrangian_svr_path', 'uses_batched_smo_svr_path']
 
 
 def uses_batched_svr_path(svr, world):
@@ -45,6 +47,14 @@ def uses_batched_lagrangian_svr_path(svr, world, ndim=None):
     return uses_batched_lagrangian(svr, (EpsilonInsensitive, SquaredEpsilonInsensitive), world, ndim)
 
 
+def uses_batched_smo_svr_path(svr, world):
+    """True when `MultiOutputSVR` can solve the targets of `svr`'s configuration together by the batched SMO solver (`bq_msmo_*`,
+    one walker workgroup per target on one panel): `dual`, optimizer 'smo' or `SMO`, the epsilon-insensitive loss,
+    `reg_intercept=False`, a resident panel ('f64' / 'f32') and a single-rank context (`world` ranks).  Whether a fit then does is
+    a matter of speed alone (`takes_batched_smo`): both ways give the same bits."""
+    return uses_batched_smo(svr, EpsilonInsensitive, world)
+
+
 class MultiOutputSVR(_MultiTargetSVR):
     """Multi-output SVR; constructor arguments and their checks are SVR's.
 
@@ -56,7 +66,11 @@ class MultiOutputSVR(_MultiTargetSVR):
     `batched_decision_`: True when `predict` takes every target's values from one fused pass over the kernel values of the union
     of the support vectors (`uses_batched_decision`) instead of one call per estimator.  The stored batch (`decision_batch_`)
     describes the estimators as `fit` left them.
+
+    `smo_`: the targets were solved together by the batched SMO solver (`uses_batched_smo_svr_path`).  `batch_smo` (None, True,
+    False) forces that choice where the configuration allows it; None leaves it to the number of targets (`takes_batched_smo`).
     """
+    batch_smo = None
 
     def fit(self, X, Y):
         X = np.ascontiguousarray(X, dtype=float)
@@ -65,14 +79,36 @@ class MultiOutputSVR(_MultiTargetSVR):
             raise ValueError('y must have at least two dimensions for multi-output regression but has only one.')
         proto = self._prototype()
         self.lagrangian_ = uses_batched_lagrangian_svr_path(proto, get_context().world, 2 * X.shape[0])
-        self.batched_ = self.lagrangian_ or uses_batched_svr_path(proto, get_context().world)
+        self.smo_ = uses_batched_smo_svr_path(proto, get_context().world) and takes_batched_smo(Y.shape[1], self.batch_smo)
+        self.batched_ = self.lagrangian_ or self.smo_ or uses_batched_svr_path(proto, get_context().world)
         self.batched_decision_ = uses_batched_decision(proto.kernel, Y.shape[1], get_context().world, self.batched_)
         self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, Y[:, c]) for c in range(Y.shape[1])]
             return self
-        self.estimators_ = (self._fit_lagrangian if self.lagrangian_ else self._fit_batched)(proto, X, np.ascontiguousarray(Y.T))
+        fit = self._fit_smo if self.smo_ else self._fit_lagrangian if self.lagrangian_ else self._fit_batched
+        self.estimators_ = fit(proto, X, np.ascontiguousarray(Y.T))
         return self
+
+    def _fit_smo(self, proto, X, Y):
+        """SVR.fit's SMO branch for every target on one panel: its KernelQuadratic (rank_one=False, compact=False), one batched
+        solve; the intercepts are the solver's."""
+        k, n = Y.shape
+        QL = np.hstack((-Y, Y)) + proto.epsilon   # row c: SVR.fit's q of target c
+        obj = KernelQuadratic(X, QL[0], 'svr', proto.kernel, storage=proto.storage, rank_one=False, compact=False)
+        res = solve_batched_smo(obj.device_problem(), _lib.SVR, Y, proto.C, proto.epsilon, proto.tol)
+        ests = [self._prototype() for _ in range(k)]
+        coefs = []
+        for c, est in enumerate(ests):
+            sv = fitted_smo_svr(est, TargetQuadratic(obj, QL[c]), res[c], X, Y[c])
+            w = np.zeros(n)
+            w[sv] = est.dual_coef_
+            coefs.append(w)
+            if self.verbose:
+                print('target %d: %d outer iterations, %d pair steps' % (c, est.optimizer.iter, est.optimizer.steps))
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
+        return ests
 
     def _fit_batched(self, proto, X, Y):
         k, n = Y.shape
