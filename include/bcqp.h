@@ -62,6 +62,8 @@ extern "C" {
 /* (still 3: bq_msolver_create_simplex2_pairs was added; nothing existing changed) */
 /* (still 3: bq_msolver_simplex2_heldout was added; nothing existing changed) */
 /* (still 3: bq_ovo_vote and bq_msolver_pairs_vote_heldout were added; nothing existing changed) */
+/* (still 3: bq_msmo_create / _run / _get / _destroy were added; nothing existing changed) */
+/* (still 3: bq_msmo_vote_heldout was added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -695,6 +697,27 @@ int bq_msmo_run(bq_msmo *s, int64_t max_outer, int64_t *outer, int *finished, in
 /* column c's BQ_SMO_ALPHAS / BQ_SMO_ERRORS / BQ_SMO_SCALARS, as bq_smo_get (there are no helpers: BQ_SMO_STATS is BQ_ERR_BADARG) */
 int bq_msmo_get(bq_msmo *s, int c, int what, double *out);
 int bq_msmo_destroy(bq_msmo *s);
+/* Held-out accuracy of the (candidate, fold) groups of a BQ_SVC batched SMO solver whose columns are class pairs on an UNSORTED
+ * panel, from the walkers' state on the device, after any run, finished or not: sklearn GridSearchCV's per-fold score of
+ * OneVsOneClassifier(SVC(optimizer='smo')) (multiclass.py _ovr_decision_function and argmax on the fold's test rows), and no
+ * columns x n array crosses the bus.  The sibling of bq_msolver_pairs_vote_heldout for bq_msmo.
+ * ncls in [2, 64]; code: n class codes in [0, ncls); P = ncls (ncls - 1) / 2.  group_of / pair_of: k each, the group of a column in
+ * [0, ngroups) and the number of its pair in the order (0,1), (0,2), ..., (1,2), ...; every group holds every pair exactly once, so
+ * k = ngroups x P, ngroups in [1, 65535].  Every column carries a row list whose rows are of its pair's two classes, with label +1
+ * on the larger class and -1 on the smaller (checked against the solver's host copy of its lists).  held: ngroups x n bytes, 1 a row
+ * the group scores; such a row may be in no row list of its group.  A NULL argument (pred excepted), a BQ_SVR solver or anything
+ * above that does not hold: BQ_ERR_BADARG, before any device call.
+ * Per column: coef_i = a_i y_i where a_i > 1e-6, else 0; n_sv, the count of such rows; intercept = -(b_low + b_up) / 2 from the
+ * column's record on the device, the bits of bq_msmo_get(BQ_SMO_SCALARS)[5]; u = K coef on all rows by the 16-column product, every
+ * column in its own slot, in scratch of the call's own.
+ * Per group: n_held, the held rows; every held row votes as bq_ovo_vote's rows do on u_k[row] + intercept_k over the group's P
+ * columns in pair order; n_correct, the held rows whose predicted class is code[row]; a group with a column whose walker failed
+ * reports n_correct = -1.  pred: NULL, or ngroups x n ints, the predicted class on the held rows and -1 elsewhere.  Integer sums in
+ * a fixed order, no atomics: a group's results have the same bits alone, at any position and in any batch.  The solver's state and
+ * liveness are untouched: a later run continues as without the call. */
+int bq_msmo_vote_heldout(bq_msmo *s, int ncls, const int *code, int ngroups, const int *group_of, const int *pair_of,
+                         const unsigned char *held, double *intercept, int64_t *n_sv, int64_t *n_held, int64_t *n_correct,
+                         int *pred);
 
 /* ---- prediction (optiml/ml/svm/_base.py:284-287) ------------------------------- */
 /* out[t] = sum_m coef[m] * kernel(SV[m], Xt[t]) + intercept   (SV: m x d, Xt: t x d, row-major fp64) */

@@ -160,6 +160,8 @@ PROTOTYPES = {
     'bq_msmo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), _ip, _ip]),
     'bq_msmo_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     'bq_msmo_destroy': (C.c_int, [_vp]),
+    'bq_msmo_vote_heldout': (C.c_int, [_vp, C.c_int, _ip, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _dp, C.POINTER(_i64),
+                                       C.POINTER(_i64), C.POINTER(_i64), _ip]),
     'bq_decision_function': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, _dp,
                                        C.c_double, _i64, _dp, _dp]),
     'bq_decision_function_multi': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, C.c_int, _dp, _dp,

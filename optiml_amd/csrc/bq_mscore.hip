@@ -9,12 +9,16 @@
 // (nu-SVC) or squared error (nu-SVR) of a column of a cross-validated nu-search.  bq_msolver_pairs_vote_heldout: the intercepts of
 // the pair columns of a cross-validated one-vs-one search, their decision values on ALL rows (the 16-column product, not the routed
 // one), the one-vs-one vote of every held-out row (bq_vote.h) and the held-out accuracy per (candidate, fold).
+// bq_msmo_vote_heldout: the same vote and count for the pair columns of a batched SMO solver (bq_smo.hip, read through bq_msmo.h) on
+// an unsorted panel: the coefficients and intercepts from the walkers' state, a row's class from its code.
+#include "bq_msmo.h"
 #include "bq_msolver.h"
 #include "bq_score_pass.h"
 #include "bq_vote.h"
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as int64_t");
 
@@ -387,14 +391,32 @@ extern "C" int bq_msolver_pairs_heldout(bq_msolver *m, const unsigned char *data
     return msolver_heldout(m, data_row, ncal, cal_of, intercept, n_sv, A, B, iters, loss, n_pos, n_neg, flags, dec);
 }
 
-// bq_msolver_pairs_vote_heldout, the rows [64 blockIdx.x, + 64) of group blockIdx.y, one thread per row.  A held row (held: ngroups x
-// n) votes over the group's P columns in pair order (col_of: ngroups x P, the column of the group's pair q) with the decision value
-// out[column][row] + b[column] and writes its class to pred (ngroups x n); every other row writes -1.  A workgroup's 64 rows lie in
-// one tile row, so in one class (ct: the classes' tile rows): the wave counts its held rows and those whose vote is that class into
-// part[group][block][0 / 1].  Integer counts of ballots: no atomics, nothing of another group
+// How mvote_kernel finds the class a held row must get.  mvote_tile_class, a class-sorted, tile-padded panel: a workgroup's 64 rows
+// lie in one tile row, so in one class (ct: the classes' tile rows).  mvote_row_class, any panel: code[row] per lane (code: n class
+// codes; read for held rows only, which lie in [0, n)).
+struct mvote_tile_class {
+    const int *ct;
+    __device__ int operator()(int ncls, long long, bool) const {
+        const int tile = (int)(((long long)blockIdx.x * BQ_VOTE_ROWS) / BQ_SYM_TILE);
+        int cls = 0;
+        while (cls + 1 < ncls && ct[cls + 1] <= tile) ++cls;
+        return cls;
+    }
+};
+struct mvote_row_class {
+    const int *code;
+    __device__ int operator()(int, long long i, bool h) const { return h ? code[i] : -1; }
+};
+
+// bq_msolver_pairs_vote_heldout and bq_msmo_vote_heldout, the rows [64 blockIdx.x, + 64) of group blockIdx.y, one thread per row.  A
+// held row (held: ngroups x n) votes over the group's P columns in pair order (col_of: ngroups x P, the column of the group's pair q)
+// with the decision value out[column][row] + b[column] and writes its class to pred (ngroups x n); every other row writes -1.  The
+// wave counts its held rows and those whose vote is their class (class_of) into part[group][block][0 / 1].  Integer counts of
+// ballots: no atomics, nothing of another group
+template <class ClassOf>
 __global__ __launch_bounds__(BQ_VOTE_ROWS) void mvote_kernel(int ncls, long long n, const double *__restrict__ out, int64_t ldw,
                                                              const double *__restrict__ b, const int *__restrict__ col_of,
-                                                             const int *__restrict__ ct, const unsigned char *__restrict__ held,
+                                                             ClassOf class_of, const unsigned char *__restrict__ held,
                                                              int *__restrict__ pred, int *__restrict__ part) {
     extern __shared__ double vote_lds[];
     const int g = blockIdx.y, tid = threadIdx.x;
@@ -407,9 +429,7 @@ __global__ __launch_bounds__(BQ_VOTE_ROWS) void mvote_kernel(int ncls, long long
         p = bq_ovo_vote_row(ncls, [=](int k) { return u[cols[k] * ldw] + b[cols[k]]; }, vote_lds, tid, nullptr);
     }
     if (i < n) pred[(long long)g * n + i] = p;
-    const int tile = (int)(((long long)blockIdx.x * BQ_VOTE_ROWS) / BQ_SYM_TILE);
-    int cls = 0;
-    while (cls + 1 < ncls && ct[cls + 1] <= tile) ++cls;
+    const int cls = class_of(ncls, i, h);
     const unsigned long long hm = __ballot(h), rm = __ballot(h && p == cls);
     if (tid == 0) {
         int *dst = part + 2 * ((long long)g * gridDim.x + blockIdx.x);
@@ -515,9 +535,122 @@ extern "C" int bq_msolver_pairs_vote_heldout(bq_msolver *m, const unsigned char 
         if (pass.step(bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count))) {
             mheldout_kernel<<<k, 1024, 0, st>>>(m->epi, OUT, ldw, nullptr, nullptr, nullptr, dcal, nullptr, nullptr, db, dnsv);
             mvote_kernel<<<dim3((unsigned)nblk, (unsigned)ngroups), BQ_VOTE_ROWS, bq_vote_lds_bytes(ncls), st>>>(
-                ncls, (long long)n, OUT, ldw, db, dcol, bq_pairs_plan_tiles(m->plan), dheld, dpred, part);
+                ncls, (long long)n, OUT, ldw, db, dcol, mvote_tile_class{bq_pairs_plan_tiles(m->plan)}, dheld, dpred, part);
             mvote_count_kernel<<<ngroups, 1024, 0, st>>>(P, nblk, part, db, dcol, dnheld, dnright);
         }
     }
     return bq_ctx_sync_after(c, pass.finish());   // held, the tables and the results are the caller's and this frame's
+}
+
+// bq_msmo_vote_heldout, column blockIdx.x of a BQ_SVC batched SMO solver, from the state its walker left (Y, A: k x n; sc: k).  The
+// coefficients of fitted_smo_svc (svm/_batched.py: a y where a > 1e-6, else 0) to the column's slot of W (stride ldw; its tail stays
+// 0), n_sv their count (thread t the rows t, t + 1024, ... ascending, then a fixed tree of integers), and from the column's record
+// the intercept -(b_low + b_up) / 2, bq_msmo_get's BQ_SMO_SCALARS[5] statement.  flag: the intercept, or NaN for a column whose
+// walker failed (err_flag) — what mvote_count_kernel reads as a failed fit
+__global__ __launch_bounds__(1024) void msmo_coef_kernel(long long n, const double *__restrict__ Y, const double *__restrict__ A,
+                                                         const bq_smo_scal *__restrict__ sc, double *__restrict__ W, int64_t ldw,
+                                                         double *__restrict__ intercept, double *__restrict__ flag,
+                                                         long long *__restrict__ n_sv) {
+    __shared__ int cnt[1024];
+    const int tid = threadIdx.x;
+    const long long c = blockIdx.x;
+    const double *y = Y + c * n, *a = A + c * n;
+    double *w = W + c * ldw;
+    int mine = 0;
+    for (long long i = tid; i < n; i += 1024) {
+        const bool sv = a[i] > 1e-6;
+        w[i] = sv ? a[i] * y[i] : 0.0;
+        mine += sv ? 1 : 0;
+    }
+    cnt[tid] = mine;
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if (tid < st) cnt[tid] += cnt[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double b = -(sc[c].b_low + sc[c].b_up) / 2;
+        intercept[c] = b;
+        flag[c] = sc[c].err_flag ? NAN : b;
+        n_sv[c] = cnt[0];
+    }
+}
+
+extern "C" int bq_msmo_vote_heldout(bq_msmo *s, int ncls, const int *code, int ngroups, const int *group_of, const int *pair_of,
+                                    const unsigned char *held, double *intercept, int64_t *n_sv, int64_t *n_held,
+                                    int64_t *n_correct, int *pred) {
+    BQ_ARG(s && code && group_of && pair_of && held && intercept && n_sv && n_held && n_correct, "NULL argument");
+    const bq_msmo_view v = bq_msmo_view_of(s);
+    BQ_ARG(v.task == BQ_SVC, "the held-out vote takes a BQ_SVC solver");
+    BQ_ARG(ncls >= 2 && ncls <= BQ_VOTE_MAX_CLS, "the one-vs-one vote takes 2 to 64 classes");
+    bq_problem *p = v.p;
+    bq_ctx *c = p->ctx;
+    const int k = v.k;
+    const int64_t n = v.n;
+    const int P = ncls * (ncls - 1) / 2;
+    BQ_ARG(ngroups >= 1 && ngroups <= 65535 && (int64_t)ngroups * P == k, "the columns must be ngroups x the ncls (ncls - 1) / 2 pairs");
+    BQ_TRY(bq_need_resident_panel(p, "the held-out vote"));
+    BQ_ARG(v.row_ptr != nullptr && v.sign != nullptr, "every column needs a row list");
+    std::vector<int> pairs((size_t)2 * P);   // ovo_pairs order
+    for (int a = 0, q = 0; a < ncls; ++a)
+        for (int b = a + 1; b < ncls; ++b, ++q) {
+            pairs[2 * q] = a;
+            pairs[2 * q + 1] = b;
+        }
+    std::vector<int> col_of((size_t)k, -1);   // ngroups x P: the column of (group, pair number)
+    for (int cl = 0; cl < k; ++cl) {
+        BQ_ARG(group_of[cl] >= 0 && group_of[cl] < ngroups, "group_of entries are groups in [0, ngroups)");
+        BQ_ARG(pair_of[cl] >= 0 && pair_of[cl] < P, "pair_of entries are pair numbers in [0, ncls (ncls - 1) / 2)");
+        int &slot = col_of[(size_t)group_of[cl] * P + pair_of[cl]];
+        BQ_ARG(slot < 0, "a group must hold every pair exactly once");
+        slot = cl;
+    }   // (k = ngroups x P columns in k distinct slots: every slot is filled)
+    for (int64_t i = 0; i < n; ++i) BQ_ARG(code[i] >= 0 && code[i] < ncls, "code entries are classes in [0, ncls)");
+    for (int cl = 0; cl < k; ++cl) {
+        const int a = pairs[2 * pair_of[cl]], b = pairs[2 * pair_of[cl] + 1];
+        for (int64_t q = v.row_ptr[cl]; q < v.row_ptr[cl + 1]; ++q) {
+            const int cd = code[v.rows[q]];
+            BQ_ARG(cd == a || cd == b, "a column's row list holds a row of a class outside its pair");
+            BQ_ARG(v.sign[q] == (cd == b ? 1 : -1), "a column's labels must be +1 on its pair's larger class and -1 on the smaller");
+        }
+    }
+    {
+        std::vector<unsigned char> trained((size_t)n);
+        for (int g = 0; g < ngroups; ++g) {
+            std::fill(trained.begin(), trained.end(), (unsigned char)0);
+            for (int q = 0; q < P; ++q) {
+                const int cl = col_of[(size_t)g * P + q];
+                for (int64_t r = v.row_ptr[cl]; r < v.row_ptr[cl + 1]; ++r) trained[(size_t)v.rows[r]] = 1;
+            }
+            const unsigned char *hg = held + (size_t)g * (size_t)n;
+            for (int64_t i = 0; i < n; ++i) BQ_ARG(!(hg[i] && trained[(size_t)i]), "a held row must not be in a row list of its group");
+        }
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // the product's own scratch: every column in its own slot of a chunk of 16, the padding slots zero
+    const int64_t slots = bq_round_up(k, BQ_SYMMW_CK), ldw = p->ldN;
+    const int nblk = (int)((n + BQ_VOTE_ROWS - 1) / BQ_VOTE_ROWS);
+    bq_score_pass pass("held-out vote", st);
+    double *W = pass.fill<double>(0, ldw * slots), *OUT = pass.fill<double>(0, ldw * slots);
+    double *slab = pass.dev<double>(bq_symmw_slab_len(p->nb));
+    double *db = pass.out<double>(intercept, k);
+    double *dflag = pass.dev<double>(k);
+    long long *dnsv = pass.out<long long>(n_sv, k);
+    long long *dnheld = pass.out<long long>(n_held, ngroups), *dnright = pass.out<long long>(n_correct, ngroups);
+    int *dpred = pass.out<int>(pred, (size_t)ngroups * (size_t)n);   // (pred may be null: the rows' classes stay on the device)
+    const int *dcol = pass.in(col_of.data(), (size_t)k);
+    const int *dcode = pass.in(code, (size_t)n);
+    int *part = pass.dev<int>((size_t)2 * ngroups * nblk);
+    const unsigned char *dheld = pass.in(held, (size_t)ngroups * (size_t)n);
+    int *count = pass.columns(k);
+    if (pass.ready()) {
+        msmo_coef_kernel<<<k, 1024, 0, st>>>((long long)n, v.Y, v.A, v.sc, W, ldw, db, dflag, dnsv);
+        if (pass.step(bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count))) {
+            mvote_kernel<<<dim3((unsigned)nblk, (unsigned)ngroups), BQ_VOTE_ROWS, bq_vote_lds_bytes(ncls), st>>>(
+                ncls, (long long)n, OUT, ldw, db, dcol, mvote_row_class{dcode}, dheld, dpred, part);
+            mvote_count_kernel<<<ngroups, 1024, 0, st>>>(P, nblk, part, dflag, dcol, dnheld, dnright);
+        }
+    }
+    return bq_ctx_sync_after(c, pass.finish());   // the tables and the results are the caller's and this frame's
 }

@@ -26,6 +26,7 @@
 
 #include "bq_c7.h"
 #include "bq_common.h"
+#include "bq_msmo.h"   // bq_smo_scal, the walkers' record, and what a scorer reads of a batched solver
 
 // -DBQ_SMO_STAMPS: thread 0 of the SVC walker accumulates the time of each phase of a full-sweep round (100 MHz
 // wall clock) and prints the totals at the end of the launch — diagnostic builds only
@@ -43,13 +44,6 @@
 #endif
 
 constexpr int SMO_T = 1024;
-
-struct bq_smo_scal {
-    double b_up, b_low;
-    long long i_up, i_low;
-    long long outer, steps, changed;
-    int sweep_all, finished, err_flag, pad;
-};
 
 struct bq_smo {
     bq_problem *p = nullptr;
@@ -1639,7 +1633,17 @@ struct bq_msmo {
     int *rows = nullptr;
     std::vector<bq_smo_scal> host;   // the k records as of the last launch
     std::vector<int> failed, live_host;
+    // host copies of the row lists and, BQ_SVC, of the labels on the listed rows (bq_msmo_vote_heldout's argument checks)
+    std::vector<int64_t> row_ptr_host;
+    std::vector<int> rows_host;
+    std::vector<signed char> sign_host;
 };
+
+bq_msmo_view bq_msmo_view_of(const bq_msmo *s) {
+    const bool lists = !s->row_ptr_host.empty();
+    return bq_msmo_view{s->p, s->task, s->k, s->n, s->Y, s->A, s->sc, lists ? s->row_ptr_host.data() : nullptr,
+                        lists ? s->rows_host.data() : nullptr, lists && s->task == BQ_SVC ? s->sign_host.data() : nullptr};
+}
 
 extern "C" int bq_msmo_destroy(bq_msmo *s) {
     if (s == nullptr) return BQ_OK;
@@ -1712,6 +1716,16 @@ extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, c
     s->host = host;
     s->failed.assign((size_t)k, 0);
     s->live_host.reserve((size_t)k);
+    if (row_ptr) {
+        s->row_ptr_host.assign(row_ptr, row_ptr + k + 1);
+        s->rows_host.assign(rows, rows + row_ptr[k]);
+        if (task == BQ_SVC) {
+            s->sign_host.resize((size_t)row_ptr[k]);
+            for (int col = 0; col < k; ++col)
+                for (int64_t q = row_ptr[col]; q < row_ptr[col + 1]; ++q)
+                    s->sign_host[(size_t)q] = Y[(int64_t)col * n + rows[q]] == 1.0 ? 1 : -1;
+        }
+    }
     const size_t kn = (size_t)k * (size_t)n;
     hipError_t e = hipSuccess;
     for (double **v : {&s->A, &s->ERR}) e = bq_dev_zeroed(e, s->mem, v, kn, c->stream);

@@ -127,6 +127,29 @@ class _DeviceSMOSolver:
         _lib.check(self._lib.bq_msmo_get(self._h, int(c), what, _lib.ptr(out)))
         return out
 
+    def vote_heldout(self, ncls, code, group_of, pair_of, held, predictions=False):
+        """The (candidate, fold) groups of the pair columns of a classification solver as they stand, finished or not
+        (`bq_msmo_vote_heldout`): code, the class code of every row; group_of / pair_of, the group of every column and the number
+        of its pair in `ovo_pairs` order, each group holding every pair once; held, groups x n, 1 on the rows a group scores (rows
+        in no row list of the group).  Returns (intercept, n_sv, n_held, n_correct[, pred]): per column the solver's intercept and
+        the count of multipliers above 1e-6, per group the held rows and those whose one-vs-one vote is their class (-1 for a group
+        with a failed column) and, with `predictions`, groups x n predicted classes (-1 on the rows a group does not score)."""
+        code = _lib.as_i32(code, self.n, 'code')
+        group_of = _lib.as_i32(group_of, self.k, 'group_of')
+        pair_of = _lib.as_i32(pair_of, self.k, 'pair_of')
+        held = np.ascontiguousarray(np.atleast_2d(held), dtype=np.uint8)
+        groups = held.shape[0]
+        if held.shape != (groups, self.n):
+            raise ValueError('held must be groups x %d' % self.n)
+        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
+        n_held, n_correct = np.empty(groups, dtype=np.int64), np.empty(groups, dtype=np.int64)
+        pred = np.empty((groups, self.n), dtype=np.int32) if predictions else None
+        i64, u8 = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+        _lib.check(self._lib.bq_msmo_vote_heldout(self._h, int(ncls), _lib.iptr(code), groups, _lib.iptr(group_of),
+                                                  _lib.iptr(pair_of), held.ctypes.data_as(u8), _lib.ptr(b), n_sv.ctypes.data_as(i64),
+                                                  n_held.ctypes.data_as(i64), n_correct.ctypes.data_as(i64), _lib.iptr(pred)))
+        return (b, n_sv, n_held, n_correct, pred) if predictions else (b, n_sv, n_held, n_correct)
+
     def close(self):
         if self._h:
             self._lib.bq_msmo_destroy(self._h)
@@ -137,6 +160,16 @@ class _DeviceSMOSolver:
             self.close()
         except Exception:
             pass
+
+
+def run_batched_smo(solver, chunk=64):
+    """Run a `_DeviceSMOSolver`'s columns to the end, `chunk` launches per call: (outer, failed), k entries each — the outer
+    iterations done and whether the walker met the reference's 'unexpected status'.  Nothing is raised for a failed column and the
+    solver stays open: a search scores its columns on it (`vote_heldout`) before closing it."""
+    fin = np.zeros(solver.k, dtype=bool)
+    while not fin.all():
+        outer, fin, failed = solver.run(chunk)
+    return outer, failed
 
 
 def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, chunk=64):
@@ -154,9 +187,7 @@ def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, c
         solver = _DeviceSMOSolver(problem, task, Y[sl], C_[sl], None if epsilon is None else epsilon[sl], tol,
                                   None if rows is None else rows[sl])
         try:
-            fin = np.zeros(solver.k, dtype=bool)
-            while not fin.all():
-                outer, fin, failed = solver.run(chunk)
+            outer, failed = run_batched_smo(solver, chunk)
             if failed.any():   # bq_smo_run's error for that column
                 raise _lib.BcqpError(_lib.ERR_NONFINITE, 'SMO reached an unexpected status (no threshold index)')
             for c in range(solver.k):

@@ -14,6 +14,21 @@ The batched path needs `OneVsRestSVC`'s batched configuration (`uses_batched_pat
 X: a numeric gamma, gamma='auto', or the linear kernel.  gamma='scale' is 1 / (d X.var()) of each pair's own rows, so one panel
 cannot serve every pair; that configuration and every other one fit one `SVC` per pair on the pair's rows — exactly the calls of
 `OneVsOneClassifier(SVC)`, with bit-identical results.
+
+SMO (`optimizer='smo'`, `uses_batched_ovo_smo`) has a batched form of its own: every pair is one walker column of the batched SMO
+solver (`bq_msmo_*`) on ONE panel of all n rows that is NOT class-sorted and has no ghost rows.  SMO is a sequential sweep, so its
+result depends on the row order, and `OneVsOneClassifier` hands `SVC.fit` a pair's rows in their original order: pair (i, j) is the
+column whose ascending row list is `pair_problem(codes, i, j)[0]`, the sweep order of the per-pair fit, with +1 on class j.  A
+column follows that fit step for step on the shared panel's own entries (tests/test_gpu_ovo_smo.py holds it to the oracle).  Whether
+it also has the per-pair fit's bits hangs on one fact: is the Gram matrix `KernelQuadratic(X[rows], ...)` builds for a pair equal,
+bit for bit, to the shared panel's entries `K[rows][:, rows]`?  Measured on an MI355X: at n = 240 (4 classes, RBF), where the shared
+panel is one 256-row tile row, it IS bit-equal for every pair, and every pair estimator equals the per-pair `SVC.fit` field for field
+(tests/test_gpu_ovo_smo.py::test_pair_estimators_equal_the_per_pair_fits_field_for_field).  It is NOT in general: at n = 360 (5
+classes, two tile rows) no pair's own build is bit-equal, and at n = 20 000 (10 classes, 45 pairs of about 4 000 rows) the two fits'
+multipliers differ and the pairs take 11 to 19 outer iterations as columns against 11 to 18 per pair — other walks through the same
+tol-optimal sets, with every training row predicted alike (profiles/ovo_smo/).  So `batch_smo` chooses between two fits that agree
+as two SMO runs to `tol` agree, not bit for bit; the default, None, takes the columns from four pairs on because they are faster
+(0.153 s against 1.999 s at that size), and two or three classes stay one `SVC.fit` per pair.
 """
 import ctypes as C
 
@@ -23,12 +38,12 @@ from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ._batched import (MEMORY_SHARE, DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _pair_array, column_bytes,
-                       device_free_bytes, fitted_svc, gram_matmat_pairs, intercept, solve_batched, solver_kind,
-                       uses_batched_decision)
+                       device_free_bytes, fitted_smo_svc, fitted_svc, gram_matmat_pairs, intercept, solve_batched,
+                       solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision)
 from .kernels import LinearKernel
-from .multiclass import uses_batched_path
+from .multiclass import uses_batched_path, uses_batched_smo_path
 
-__all__ = ['OneVsOneSVC', 'uses_batched_ovo', 'sort_plan', 'ovo_pairs', 'pair_problem', 'ovo_decision']
+__all__ = ['OneVsOneSVC', 'uses_batched_ovo', 'uses_batched_ovo_smo', 'sort_plan', 'ovo_pairs', 'pair_problem', 'ovo_decision']
 
 TILE = 256
 
@@ -37,6 +52,15 @@ def uses_batched_ovo(svc, world):
     """True when `OneVsOneSVC` solves the pairs of `svc`'s configuration together on one panel: `uses_batched_path` holds and the
     kernel's parameters do not depend on the rows (numeric gamma, gamma='auto' or a linear kernel)."""
     if not uses_batched_path(svc, world):
+        return False
+    return isinstance(svc.kernel, LinearKernel) or getattr(svc.kernel, 'gamma', None) != 'scale'
+
+
+def uses_batched_ovo_smo(svc, world):
+    """True when `OneVsOneSVC` can solve the pairs of `svc`'s configuration as row-list columns of the batched SMO solver on one
+    unsorted panel: `uses_batched_smo_path` holds and the kernel's parameters do not depend on the rows (numeric gamma,
+    gamma='auto' or a linear kernel).  Whether a fit then does is `takes_batched_smo`'s answer (`OneVsOneSVC.batch_smo`)."""
+    if not uses_batched_smo_path(svc, world):
         return False
     return isinstance(svc.kernel, LinearKernel) or getattr(svc.kernel, 'gamma', None) != 'scale'
 
@@ -138,7 +162,12 @@ class OneVsOneSVC(_MultiClassSVC):
     kernel values of the union of the support vectors (`uses_batched_decision`; a training row is in up to k - 1 pairs and in the
     union once) instead of one call per estimator.  The stored batch (`decision_batch_`) describes the estimators as `fit` left
     them.
+
+    `smo_`: the pairs were solved together as row-list columns of the batched SMO solver (`uses_batched_ovo_smo`); `batched_` is
+    True when either batched path ran.  `batch_smo` (None, True, False) forces that choice where the configuration allows it; None
+    leaves it to the number of pairs (`takes_batched_smo`: two and three classes stay one `SVC.fit` per pair).
     """
+    batch_smo = None
 
     @property
     def n_classes_(self):
@@ -152,9 +181,11 @@ class OneVsOneSVC(_MultiClassSVC):
             raise ValueError('OneVsOneSVC can not be fit when only one class is present.')
         codes = np.searchsorted(self.classes_, y)
         proto = self._prototype()
-        self.batched_ = uses_batched_ovo(proto, get_context().world)
         ncls = len(self.classes_)
-        self.batched_decision_ = uses_batched_decision(proto.kernel, ncls * (ncls - 1) // 2, get_context().world, self.batched_)
+        P = ncls * (ncls - 1) // 2
+        self.smo_ = uses_batched_ovo_smo(proto, get_context().world) and takes_batched_smo(P, self.batch_smo)
+        self.batched_ = self.smo_ or uses_batched_ovo(proto, get_context().world)
+        self.batched_decision_ = uses_batched_decision(proto.kernel, P, get_context().world, self.batched_)
         self.decision_batch_ = None
         if not self.batched_:
             self.estimators_ = []
@@ -162,8 +193,39 @@ class OneVsOneSVC(_MultiClassSVC):
                 rows, yp = pair_problem(codes, i, j)
                 self.estimators_.append(self._prototype().fit(X[rows], (yp > 0).astype(int)))
             return self
-        self.estimators_ = self._fit_batched(proto, X, codes)
+        self.estimators_ = (self._fit_smo if self.smo_ else self._fit_batched)(proto, X, codes)
         return self
+
+    def _fit_smo(self, proto, X, codes):
+        """SVC.fit's SMO branch for every pair on one panel of all rows, built as `OneVsRestSVC._fit_smo` builds it (rank_one=False,
+        compact=False; unsorted, no ghost rows): pair (i, j) is the column with the pair's rows as its ascending row list and +1 on
+        class j; the intercepts are the solver's."""
+        n = len(codes)
+        pairs = ovo_pairs(len(self.classes_))
+        problems = [pair_problem(codes, i, j) for i, j in pairs]
+        Y = np.stack([np.where(codes == j, 1., -1.) for _, j in pairs])
+        obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Y[0], storage=proto.storage, rank_one=False, compact=False)
+        dev = obj.device_problem()
+        # (in solves of `smo_column_cap` columns of the memory free after the panel)
+        res = solve_batched_smo(dev, _lib.SVC, Y, proto.C, None, proto.tol, rows=[rows for rows, _ in problems])
+        ests, coefs = [], []
+        for p, (rows, yp) in enumerate(problems):
+            r = dict(res[p])
+            # the column's n-long state on the pair's rows; the threshold rows as positions among them
+            r['alphas'], r['errors'] = r['alphas'][rows], r['errors'][rows]
+            r['b_up_idx'], r['b_low_idx'] = (int(np.searchsorted(rows, r[name])) for name in ('b_up_idx', 'b_low_idx'))
+            est = self._prototype()
+            sv = fitted_smo_svc(est, obj, r, X[rows], yp)
+            w = np.zeros(n)
+            w[rows[sv]] = est.dual_coef_
+            coefs.append(w)
+            ests.append(est)
+            if self.verbose:
+                print('pair (%r, %r): %d outer iterations, %d pair steps' % (self.classes_[pairs[p][0]], self.classes_[pairs[p][1]],
+                                                                           est.optimizer.iter, est.optimizer.steps))
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
+        return ests
 
     def _fit_batched(self, proto, X, codes):
         ncls = len(self.classes_)
