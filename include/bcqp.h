@@ -64,6 +64,7 @@ extern "C" {
 /* (still 3: bq_ovo_vote and bq_msolver_pairs_vote_heldout were added; nothing existing changed) */
 /* (still 3: bq_msmo_create / _run / _get / _destroy were added; nothing existing changed) */
 /* (still 3: bq_msmo_vote_heldout was added; nothing existing changed) */
+/* (still 3: bq_msmo_svr_heldout and bq_msmo_svc_heldout were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -718,6 +719,30 @@ int bq_msmo_destroy(bq_msmo *s);
 int bq_msmo_vote_heldout(bq_msmo *s, int ncls, const int *code, int ngroups, const int *group_of, const int *pair_of,
                          const unsigned char *held, double *intercept, int64_t *n_sv, int64_t *n_held, int64_t *n_correct,
                          int *pred);
+/* Held-out scores of the row-list columns of a batched SMO solver from the walkers' state on the device, after any run, finished
+ * or not: the siblings of bq_msolver_svr_heldout / bq_msolver_svc_heldout for bq_msmo.  No k x n array crosses the bus, and the
+ * solver's state and liveness are untouched: a later run continues as without the call.
+ * held: nsets x n bytes, 1 on the rows a set scores (the test rows of a fold); set_of: k, the set whose rows column c scores, or -1:
+ * no row.  A scoring column carries a row list, and none of its scored rows is in it.  BQ_ERR_BADARG before any device call: a NULL
+ * argument (dec excepted), a solver of the other task, nsets < 1, an entry of set_of outside [-1, nsets) (of cal_of outside
+ * [-1, ncal)), a problem without a resident panel, a scoring column without a list, a scored row in the column's own list.
+ * Per column: coef_i = a_i y_i where a_i > 1e-6 (BQ_SVR: a+_i - a-_i where a+_i > 1e-6 or a-_i > 1e-6), else 0; n_sv, the count of
+ * such rows; intercept from the column's record on the device, the bits of bq_msmo_get(BQ_SMO_SCALARS)[5] (-(b_low + b_up) / 2,
+ * BQ_SVR: +(b_low + b_up) / 2); u = K coef on all rows by the 16-column product, every column in its own slot, in scratch of the
+ * call's own.  A column whose walker failed reports NaN as its intercept (and sse, and decision values).
+ * bq_msmo_svr_heldout: sse = sum (y_i - (u_i + intercept))^2 over the column's scored rows, y the column's targets as the solver
+ * holds them, and n_held their count; a column without support vectors predicts its intercept (no NaN rule, unlike
+ * bq_msolver_svr_heldout: SVR.fit's SMO branch divides by nothing).  One workgroup per column, sums in a fixed order, no atomics.
+ * bq_msmo_svc_heldout: cal_of: k, column c's calibrator in [0, ncal) or -1; on the scored rows of a column with a calibrator the
+ * decision value u_i + intercept and the label y_i (the solver's Y, which holds +-1 there) enter the calibrator's sample; columns
+ * that share a calibrator score disjoint rows (else BQ_ERR_BADARG).  A, B, iters, loss, n_pos, n_neg, flags (ncal each) and dec
+ * (NULL, or ncal x n: the decision values, 0 on the rows outside the sample) are bq_msolver_svc_heldout's.
+ * Every figure of a column has the same bits alone, at any position and in any batch. */
+int bq_msmo_svr_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned char *held, double *intercept, int64_t *n_sv,
+                        double *sse, int64_t *n_held);
+int bq_msmo_svc_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned char *held, int ncal, const int *cal_of,
+                        double *intercept, int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos,
+                        int64_t *n_neg, int *flags, double *dec);
 
 /* ---- prediction (optiml/ml/svm/_base.py:284-287) ------------------------------- */
 /* out[t] = sum_m coef[m] * kernel(SV[m], Xt[t]) + intercept   (SV: m x d, Xt: t x d, row-major fp64) */

@@ -162,6 +162,9 @@ PROTOTYPES = {
     'bq_msmo_destroy': (C.c_int, [_vp]),
     'bq_msmo_vote_heldout': (C.c_int, [_vp, C.c_int, _ip, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _dp, C.POINTER(_i64),
                                        C.POINTER(_i64), C.POINTER(_i64), _ip]),
+    'bq_msmo_svr_heldout': (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_ubyte), _dp, C.POINTER(_i64), _dp, C.POINTER(_i64)]),
+    'bq_msmo_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_ubyte), C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip,
+                                      _dp, C.POINTER(_i64), C.POINTER(_i64), _ip, _dp]),
     'bq_decision_function': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, _dp,
                                        C.c_double, _i64, _dp, _dp]),
     'bq_decision_function_multi': (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _i64, _i64, _dp, C.c_int, _dp, _dp,

@@ -10,7 +10,9 @@
 // the pair columns of a cross-validated one-vs-one search, their decision values on ALL rows (the 16-column product, not the routed
 // one), the one-vs-one vote of every held-out row (bq_vote.h) and the held-out accuracy per (candidate, fold).
 // bq_msmo_vote_heldout: the same vote and count for the pair columns of a batched SMO solver (bq_smo.hip, read through bq_msmo.h) on
-// an unsorted panel: the coefficients and intercepts from the walkers' state, a row's class from its code.
+// an unsorted panel: the coefficients and intercepts from the walkers' state, a row's class from its code.  bq_msmo_svr_heldout /
+// bq_msmo_svc_heldout: the siblings of bq_msolver_svr_heldout / _svc_heldout for those walkers' row-list columns, the scored rows
+// given as sets (held) instead of zero boxes.
 #include "bq_msmo.h"
 #include "bq_msolver.h"
 #include "bq_score_pass.h"
@@ -542,24 +544,35 @@ extern "C" int bq_msolver_pairs_vote_heldout(bq_msolver *m, const unsigned char 
     return bq_ctx_sync_after(c, pass.finish());   // held, the tables and the results are the caller's and this frame's
 }
 
-// bq_msmo_vote_heldout, column blockIdx.x of a BQ_SVC batched SMO solver, from the state its walker left (Y, A: k x n; sc: k).  The
-// coefficients of fitted_smo_svc (svm/_batched.py: a y where a > 1e-6, else 0) to the column's slot of W (stride ldw; its tail stays
-// 0), n_sv their count (thread t the rows t, t + 1024, ... ascending, then a fixed tree of integers), and from the column's record
-// the intercept -(b_low + b_up) / 2, bq_msmo_get's BQ_SMO_SCALARS[5] statement.  flag: the intercept, or NaN for a column whose
-// walker failed (err_flag) — what mvote_count_kernel reads as a failed fit
+// bq_msmo_vote_heldout / _svr_heldout / _svc_heldout, column blockIdx.x of a batched SMO solver, from the state its walker left (Y,
+// A: k x n; AM: k x n, SVR only; sc: k).  The coefficients of fitted_smo_svc (svm/_batched.py: a y where a > 1e-6, else 0) or, SVR, of
+// _svr_attributes (a+ - a- where a+ > 1e-6 or a- > 1e-6, else 0) to the column's slot of W (stride ldw; its tail stays 0), n_sv their
+// count (thread t the rows t, t + 1024, ... ascending, then a fixed tree of integers), and from the column's record the intercept
+// -(b_low + b_up) / 2 (SVR: +(b_low + b_up) / 2), bq_msmo_get's BQ_SMO_SCALARS[5] statement.  flag: the intercept, or NaN for a
+// column whose walker failed (err_flag) — what mvote_count_kernel and the two score kernels read as a failed fit.  intercept may
+// be null: the two held-out scorers report flag
+template <bool SVR>
 __global__ __launch_bounds__(1024) void msmo_coef_kernel(long long n, const double *__restrict__ Y, const double *__restrict__ A,
-                                                         const bq_smo_scal *__restrict__ sc, double *__restrict__ W, int64_t ldw,
-                                                         double *__restrict__ intercept, double *__restrict__ flag,
-                                                         long long *__restrict__ n_sv) {
+                                                         const double *__restrict__ AM, const bq_smo_scal *__restrict__ sc,
+                                                         double *__restrict__ W, int64_t ldw, double *__restrict__ intercept,
+                                                         double *__restrict__ flag, long long *__restrict__ n_sv) {
     __shared__ int cnt[1024];
     const int tid = threadIdx.x;
     const long long c = blockIdx.x;
-    const double *y = Y + c * n, *a = A + c * n;
+    const double *y = Y + c * n, *a = A + c * n, *am = SVR ? AM + c * n : nullptr;
     double *w = W + c * ldw;
     int mine = 0;
     for (long long i = tid; i < n; i += 1024) {
-        const bool sv = a[i] > 1e-6;
-        w[i] = sv ? a[i] * y[i] : 0.0;
+        bool sv;
+        double coef;
+        if (SVR) {
+            sv = a[i] > 1e-6 || am[i] > 1e-6;
+            coef = a[i] - am[i];
+        } else {
+            sv = a[i] > 1e-6;
+            coef = a[i] * y[i];
+        }
+        w[i] = sv ? coef : 0.0;
         mine += sv ? 1 : 0;
     }
     cnt[tid] = mine;
@@ -569,11 +582,177 @@ __global__ __launch_bounds__(1024) void msmo_coef_kernel(long long n, const doub
         __syncthreads();
     }
     if (tid == 0) {
-        const double b = -(sc[c].b_low + sc[c].b_up) / 2;
-        intercept[c] = b;
+        const double b = SVR ? (sc[c].b_low + sc[c].b_up) / 2 : -(sc[c].b_low + sc[c].b_up) / 2;
+        if (intercept) intercept[c] = b;
         flag[c] = sc[c].err_flag ? NAN : b;
         n_sv[c] = cnt[0];
     }
+}
+
+// bq_msmo_svr_heldout, column blockIdx.x, u = out[:, column] = K coef, y the column's targets (the solver's Y), b = flag[column]
+// (NaN: the walker failed).  Over the rows of set set_of[column] (held: nsets x n bytes; -1: no row): sse = sum (y - (u + b))^2 and
+// n_held, summed by mscore_sum.  A failed column: sse = NaN, also when it scores no row
+__global__ __launch_bounds__(1024) void msmo_svr_score_kernel(long long n, const double *__restrict__ Y, const double *__restrict__ out,
+                                                              int64_t ldw, const double *__restrict__ flag,
+                                                              const int *__restrict__ set_of, const unsigned char *__restrict__ held,
+                                                              double *__restrict__ sse, long long *__restrict__ n_held) {
+    const int tid = threadIdx.x;
+    const long long c = blockIdx.x;
+    const double *y = Y + c * n, *u = out + c * ldw;
+    const double b = flag[c];
+    const int set = set_of[c];
+    double s = 0.0;
+    int cnt = 0;
+    if (set >= 0) {
+        const unsigned char *h = held + (long long)set * n;
+        for (long long i = tid; i < n; i += 1024) {
+            const bool hi = h[i] != 0;
+            const double r = y[i] - (u[i] + b);
+            s += hi ? r * r : 0.0;
+            cnt += hi ? 1 : 0;
+        }
+    }
+    mscore_sum(tid, s, cnt);
+    if (tid == 0) {
+        sse[c] = std::isnan(b) ? NAN : s;
+        n_held[c] = cnt;
+    }
+}
+
+// bq_msmo_svc_heldout, column blockIdx.x, u = out[:, column] = K coef, y the column's labels (the solver's Y), b = flag[column]
+// (NaN: the walker failed, and so are its decision values).  On the rows of set set_of[column] the decision value u + b and the
+// label y to row cal_of[column] of D and L (row stride n; zeroed by the caller; the columns of a calibrator score disjoint rows, so
+// no two workgroups write one entry).  set_of or cal_of -1: nothing is written
+__global__ __launch_bounds__(1024) void msmo_svc_score_kernel(long long n, const double *__restrict__ Y, const double *__restrict__ out,
+                                                              int64_t ldw, const double *__restrict__ flag,
+                                                              const int *__restrict__ set_of, const unsigned char *__restrict__ held,
+                                                              const int *__restrict__ cal_of, double *__restrict__ D,
+                                                              double *__restrict__ L) {
+    const int tid = threadIdx.x;
+    const long long c = blockIdx.x;
+    const int set = set_of[c], cal = cal_of[c];
+    if (set < 0 || cal < 0) return;
+    const double *y = Y + c * n, *u = out + c * ldw;
+    const unsigned char *h = held + (long long)set * n;
+    const double b = flag[c];
+    double *d = D + (long long)cal * n, *l = L + (long long)cal * n;
+    for (long long i = tid; i < n; i += 1024) {
+        if (h[i]) {
+            d[i] = u[i] + b;
+            l[i] = y[i];
+        }
+    }
+}
+
+// The argument checks bq_msmo_svr_heldout and bq_msmo_svc_heldout share, on the host against the solver's host copies of its lists:
+// the task, nsets, the entries of set_of, the resident panel, and per scoring column a row list that holds none of its scored rows
+static int msmo_heldout_args(const bq_msmo_view &v, int task, const char *what, int nsets, const int *set_of,
+                             const unsigned char *held) {
+    BQ_ARG(v.task == task, task == BQ_SVR ? "held-out scoring takes a BQ_SVR solver" : "held-out calibration takes a BQ_SVC solver");
+    BQ_ARG(nsets >= 1, "nsets must be >= 1");
+    for (int cl = 0; cl < v.k; ++cl) BQ_ARG(set_of[cl] >= -1 && set_of[cl] < nsets, "set_of entries are -1 or a set in [0, nsets)");
+    BQ_TRY(bq_need_resident_panel(v.p, what));
+    for (int cl = 0; cl < v.k; ++cl) {
+        if (set_of[cl] < 0) continue;
+        BQ_ARG(v.row_ptr != nullptr, "a column that scores rows needs a row list: without one it trains on every row");
+        const unsigned char *h = held + (size_t)set_of[cl] * (size_t)v.n;
+        for (int64_t q = v.row_ptr[cl]; q < v.row_ptr[cl + 1]; ++q)
+            BQ_ARG(!h[v.rows[q]], "a scored row must not be in the column's own row list");
+    }
+    return BQ_OK;
+}
+
+extern "C" int bq_msmo_svr_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned char *held, double *intercept,
+                                   int64_t *n_sv, double *sse, int64_t *n_held) {
+    BQ_ARG(s && set_of && held && intercept && n_sv && sse && n_held, "NULL argument");
+    const bq_msmo_view v = bq_msmo_view_of(s);
+    BQ_TRY(msmo_heldout_args(v, BQ_SVR, "held-out scoring", nsets, set_of, held));
+    bq_problem *p = v.p;
+    bq_ctx *c = p->ctx;
+    const int k = v.k;
+    const int64_t n = v.n;
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // the product's own scratch: every column in its own slot of a chunk of 16, the padding slots zero
+    const int64_t slots = bq_round_up(k, BQ_SYMMW_CK), ldw = p->ldN;
+    bq_score_pass pass("held-out scoring", st);
+    double *W = pass.fill<double>(0, ldw * slots), *OUT = pass.fill<double>(0, ldw * slots);
+    double *slab = pass.dev<double>(bq_symmw_slab_len(p->nb));
+    double *dflag = pass.out<double>(intercept, k);   // NaN for a failed walker
+    double *dsse = pass.out<double>(sse, k);
+    long long *dnsv = pass.out<long long>(n_sv, k), *dnheld = pass.out<long long>(n_held, k);
+    const int *dset = pass.in(set_of, (size_t)k);
+    const unsigned char *dheld = pass.in(held, (size_t)nsets * (size_t)n);
+    int *count = pass.columns(k);
+    if (pass.ready()) {
+        msmo_coef_kernel<true><<<k, 1024, 0, st>>>((long long)n, v.Y, v.A, v.AM, v.sc, W, ldw, nullptr, dflag, dnsv);
+        if (pass.step(bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count)))
+            msmo_svr_score_kernel<<<k, 1024, 0, st>>>((long long)n, v.Y, OUT, ldw, dflag, dset, dheld, dsse, dnheld);
+    }
+    return bq_ctx_sync_after(c, pass.finish());   // the tables and the results are the caller's and this frame's
+}
+
+extern "C" int bq_msmo_svc_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned char *held, int ncal, const int *cal_of,
+                                   double *intercept, int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos,
+                                   int64_t *n_neg, int *flags, double *dec) {
+    BQ_ARG(s && set_of && held && cal_of && intercept && n_sv && A && B && iters && loss && n_pos && n_neg && flags, "NULL argument");
+    const bq_msmo_view v = bq_msmo_view_of(s);
+    BQ_TRY(msmo_heldout_args(v, BQ_SVC, "held-out calibration", nsets, set_of, held));
+    BQ_ARG(ncal >= 1, "ncal must be >= 1");
+    bq_problem *p = v.p;
+    bq_ctx *c = p->ctx;
+    const int k = v.k;
+    const int64_t n = v.n;
+    {   // the columns of a calibrator score disjoint rows: two columns may not write one entry of its sample
+        std::vector<std::vector<int>> cols((size_t)ncal);
+        for (int cl = 0; cl < k; ++cl) {
+            BQ_ARG(cal_of[cl] >= -1 && cal_of[cl] < ncal, "cal_of entries are -1 or a calibrator in [0, ncal)");
+            if (cal_of[cl] >= 0 && set_of[cl] >= 0) cols[cal_of[cl]].push_back(cl);
+        }
+        std::vector<unsigned char> seen;
+        for (const std::vector<int> &cs : cols) {
+            if (cs.size() < 2) continue;
+            seen.assign((size_t)n, 0);
+            for (int cl : cs) {
+                const unsigned char *h = held + (size_t)set_of[cl] * (size_t)n;
+                for (int64_t i = 0; i < n; ++i) {
+                    BQ_ARG(!(h[i] && seen[i]), "columns that share a calibrator must score disjoint rows");
+                    seen[i] |= h[i];
+                }
+            }
+        }
+    }
+    BQ_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int64_t slots = bq_round_up(k, BQ_SYMMW_CK), ldw = p->ldN;
+    const size_t len = (size_t)ncal * (size_t)n;
+    std::vector<int> tables((size_t)2 * k);   // set_of, then cal_of
+    std::copy(set_of, set_of + k, tables.begin());
+    std::copy(cal_of, cal_of + k, tables.begin() + k);
+    // bq_scratch hands out 16 buffers a call: the product's input and output share one, the calibrators' two samples another,
+    // the two tables a third
+    bq_score_pass pass("held-out calibration", st);
+    double *W = pass.fill<double>(0, 2 * ldw * slots), *OUT = W ? W + ldw * slots : nullptr;
+    double *slab = pass.dev<double>(bq_symmw_slab_len(p->nb));
+    double *dD = pass.fill<double>(0, 2 * len), *dL = dD ? dD + len : nullptr;
+    double *dflag = pass.out<double>(intercept, k);   // NaN for a failed walker
+    long long *dnsv = pass.out<long long>(n_sv, k);
+    double *dA = pass.out<double>(A, ncal), *dB = pass.out<double>(B, ncal), *dloss = pass.out<double>(loss, ncal);
+    long long *dpos = pass.out<long long>(n_pos, ncal), *dneg = pass.out<long long>(n_neg, ncal);
+    int *diters = pass.out<int>(iters, ncal), *dflags = pass.out<int>(flags, ncal);
+    pass.out_of(dec, dD, len);
+    const int *dset = pass.in(tables.data(), tables.size()), *dcal = dset ? dset + k : nullptr;
+    const unsigned char *dheld = pass.in(held, (size_t)nsets * (size_t)n);
+    int *count = pass.columns(k);
+    if (pass.ready()) {
+        msmo_coef_kernel<false><<<k, 1024, 0, st>>>((long long)n, v.Y, v.A, nullptr, v.sc, W, ldw, nullptr, dflag, dnsv);
+        if (pass.step(bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count))) {
+            msmo_svc_score_kernel<<<k, 1024, 0, st>>>((long long)n, v.Y, OUT, ldw, dflag, dset, dheld, dcal, dD, dL);
+            pass.check(hipGetLastError());
+            if (pass.ok()) pass.step(bq_launch_platt(ncal, n, dD, dL, dA, dB, diters, dloss, dpos, dneg, dflags, st));
+        }
+    }
+    return bq_ctx_sync_after(c, pass.finish());   // the tables and the results are the caller's and this frame's
 }
 
 extern "C" int bq_msmo_vote_heldout(bq_msmo *s, int ncls, const int *code, int ngroups, const int *group_of, const int *pair_of,
@@ -645,7 +824,7 @@ extern "C" int bq_msmo_vote_heldout(bq_msmo *s, int ncls, const int *code, int n
     const unsigned char *dheld = pass.in(held, (size_t)ngroups * (size_t)n);
     int *count = pass.columns(k);
     if (pass.ready()) {
-        msmo_coef_kernel<<<k, 1024, 0, st>>>((long long)n, v.Y, v.A, v.sc, W, ldw, db, dflag, dnsv);
+        msmo_coef_kernel<false><<<k, 1024, 0, st>>>((long long)n, v.Y, v.A, nullptr, v.sc, W, ldw, db, dflag, dnsv);
         if (pass.step(bq_launch_symmw(p, false, W, ldw, k, slab, OUT, count))) {
             mvote_kernel<<<dim3((unsigned)nblk, (unsigned)ngroups), BQ_VOTE_ROWS, bq_vote_lds_bytes(ncls), st>>>(
                 ncls, (long long)n, OUT, ldw, db, dcol, mvote_row_class{dcode}, dheld, dpred, part);

@@ -64,5 +64,5 @@ struct bq_buffers {
     hipError_t err_ = hipSuccess;
 };
 
-using bq_scratch = bq_buffers<16>;   // one call: the largest user (held-out calibration) takes 14
+using bq_scratch = bq_buffers<16>;   // one call: the largest user (held-out calibration of SMO columns) takes 15
 using bq_owner = bq_buffers<64>;     // one object: the largest (the active-set workspace with its CG vectors) takes about 30

@@ -1641,7 +1641,7 @@ struct bq_msmo {
 
 bq_msmo_view bq_msmo_view_of(const bq_msmo *s) {
     const bool lists = !s->row_ptr_host.empty();
-    return bq_msmo_view{s->p, s->task, s->k, s->n, s->Y, s->A, s->sc, lists ? s->row_ptr_host.data() : nullptr,
+    return bq_msmo_view{s->p, s->task, s->k, s->n, s->Y, s->A, s->AM, s->sc, lists ? s->row_ptr_host.data() : nullptr,
                         lists ? s->rows_host.data() : nullptr, lists && s->task == BQ_SVC ? s->sign_host.data() : nullptr};
 }
 

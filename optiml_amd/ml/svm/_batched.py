@@ -73,6 +73,23 @@ def smo_column_cap(n, task, free_bytes):
     return int(max(1, min(MAX_COLUMNS, int(free_bytes * MEMORY_SHARE) // smo_column_bytes(n, task))))
 
 
+def smo_heldout_column_cap(n, task, free_bytes, wide_slab_bytes, calibrators=False):
+    """`smo_column_cap` for columns that are scored where they stand (`bq_msmo_svr_heldout` / `bq_msmo_svc_heldout`).  The budget —
+    MEMORY_SHARE of `free_bytes` — holds per column the walker's state (`smo_column_bytes`) and the scoring's scratch, the product's
+    input and output: two n-vectors, each padded by a tile; with `calibrators` (a calibrator per column) also the two n-vectors of
+    its sample; and once the 16-column product's slab (`wide_slab_bytes`) and the two vectors of the last chunk's 15 padding
+    columns.  At most MAX_COLUMNS, at least 1.  The split changes no column's bits."""
+    vec = 8 * (int(n) + 256)
+    per_column = smo_column_bytes(n, task) + (4 if calibrators else 2) * vec
+    budget = int(free_bytes * MEMORY_SHARE) - int(wide_slab_bytes) - 2 * 15 * vec
+    return int(max(1, min(MAX_COLUMNS, budget // per_column)))
+
+
+def smo_failed_error():
+    """what the single fit raises for a walker that met the reference's 'unexpected status': bq_smo_run's error"""
+    return _lib.BcqpError(_lib.ERR_NONFINITE, 'SMO reached an unexpected status (no threshold index)')
+
+
 # The smallest number of columns that takes the batched SMO path when nothing forces either one (`batch_smo` of the estimators and
 # of the search).  A batched walker has no helper workgroups, so one column is slower than the single solver (n = 20 000: 0.242 s
 # against 0.167 s); two columns already are not (0.234 s against 2 x 0.167 s), and the batch's time stays flat up to one column per
@@ -150,6 +167,45 @@ class _DeviceSMOSolver:
                                                   n_held.ctypes.data_as(i64), n_correct.ctypes.data_as(i64), _lib.iptr(pred)))
         return (b, n_sv, n_held, n_correct, pred) if predictions else (b, n_sv, n_held, n_correct)
 
+    def _sets(self, set_of, held):
+        """set_of (k ints) and held (sets x n bytes) as the held-out scorers take them"""
+        set_of = _lib.as_i32(set_of, self.k, 'set_of')
+        held = np.ascontiguousarray(np.atleast_2d(held), dtype=np.uint8)
+        if held.shape[1] != self.n:
+            raise ValueError('held must be sets x %d' % self.n)
+        return set_of, held
+
+    def svr_heldout(self, set_of, held):
+        """(intercept, n_sv, sse, n_held), k entries each, of the columns of a regression solver as they stand, finished or not
+        (`bq_msmo_svr_heldout`): held, sets x n, 1 on the rows a set scores; set_of, the set of every column (-1: it scores no
+        row; else the column carries a row list that holds none of the set's rows).  Per column the solver's intercept, the count
+        of rows with a multiplier above 1e-6, and the squared error and the count of its set's rows.  A column whose walker failed
+        has intercept = sse = NaN."""
+        set_of, held = self._sets(set_of, held)
+        b, sse = np.empty(self.k), np.empty(self.k)
+        n_sv, n_held = np.empty(self.k, dtype=np.int64), np.empty(self.k, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        _lib.check(self._lib.bq_msmo_svr_heldout(self._h, held.shape[0], _lib.iptr(set_of), held.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                 _lib.ptr(b), n_sv.ctypes.data_as(i64), _lib.ptr(sse), n_held.ctypes.data_as(i64)))
+        return b, n_sv, sse, n_held
+
+    def svc_heldout(self, set_of, held, cal_of, ncal, decisions=False):
+        """`_DeviceMultiSolver.heldout_svc` for the columns of a classification solver as they stand (`bq_msmo_svc_heldout`):
+        set_of / held as `svr_heldout` takes them, cal_of the calibrator of every column (-1: none).  Returns (intercept, n_sv,
+        fit): the solver's intercepts (NaN for a failed walker), the support counts and `platt_fit`'s dict, with `decisions` also
+        'dec', the ncal x n decision values (0 on the rows no column of the calibrator scores)."""
+        set_of, held = self._sets(set_of, held)
+        cal_of = _lib.as_i32(cal_of, self.k, 'cal_of')
+        b, n_sv = np.empty(self.k), np.empty(self.k, dtype=np.int64)
+        fit, args = _platt_outputs(ncal)
+        dec = np.empty((ncal, self.n)) if decisions else None
+        _lib.check(self._lib.bq_msmo_svc_heldout(self._h, held.shape[0], _lib.iptr(set_of), held.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                 int(ncal), _lib.iptr(cal_of), _lib.ptr(b), n_sv.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 *args, _lib.ptr(dec)))
+        if decisions:
+            fit['dec'] = dec
+        return b, n_sv, fit
+
     def close(self):
         if self._h:
             self._lib.bq_msmo_destroy(self._h)
@@ -172,6 +228,20 @@ def run_batched_smo(solver, chunk=64):
     return outer, failed
 
 
+def smo_column_result(solver, c, outer):
+    """Column c of a `_DeviceSMOSolver` after `outer` outer iterations as the dict `solve_batched_smo` returns for it, downloaded
+    from the walker's state."""
+    n = solver.n
+    a, sc = solver.get(c, _lib.SMO_ALPHAS), solver.get(c, _lib.SMO_SCALARS)
+    r = dict(b_up=sc[0], b_low=sc[1], b_up_idx=int(sc[2]), b_low_idx=int(sc[3]), steps=int(sc[4]), b=sc[5], iter=int(outer),
+             errors=solver.get(c, _lib.SMO_ERRORS))
+    if solver.task == _lib.SVC:
+        r['alphas'] = a
+    else:
+        r['alphas_p'], r['alphas_n'] = a[:n].copy(), a[n:].copy()
+    return r
+
+
 def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, chunk=64):
     """Run k SMO columns to the end, `cap` columns per solve at most (default: `smo_column_cap` of the memory free now): per column a
     dict of what `SMO.minimize` leaves — alphas (classification) or alphas_p / alphas_n (regression), b, errors, b_up, b_low,
@@ -189,16 +259,8 @@ def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, c
         try:
             outer, failed = run_batched_smo(solver, chunk)
             if failed.any():   # bq_smo_run's error for that column
-                raise _lib.BcqpError(_lib.ERR_NONFINITE, 'SMO reached an unexpected status (no threshold index)')
-            for c in range(solver.k):
-                a, sc = solver.get(c, _lib.SMO_ALPHAS), solver.get(c, _lib.SMO_SCALARS)
-                r = dict(b_up=sc[0], b_low=sc[1], b_up_idx=int(sc[2]), b_low_idx=int(sc[3]), steps=int(sc[4]), b=sc[5],
-                         iter=int(outer[c]), errors=solver.get(c, _lib.SMO_ERRORS))
-                if task == _lib.SVC:
-                    r['alphas'] = a
-                else:
-                    r['alphas_p'], r['alphas_n'] = a[:n].copy(), a[n:].copy()
-                out.append(r)
+                raise smo_failed_error()
+            out.extend(smo_column_result(solver, c, outer[c]) for c in range(solver.k))
         finally:
             solver.close()
     return out

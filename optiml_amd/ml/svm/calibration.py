@@ -9,6 +9,10 @@ lives (`bq_msolver_svc_heldout`): per column an intercept and a support count, t
 one buffer row per calibrator, and on those rows the sigmoid fits (`platt_fit_kernel`, bq_platt.hip: Newton's iteration with
 backtracking of Lin, Lin & Weng as libsvm's `sigmoid_train` states it, one workgroup per calibrator).
 
+An estimator on the batched SMO path (`uses_batched_smo_calibration`: optimizer 'smo', an unregularised intercept, an 'f64' panel, a
+numeric gamma) takes the same route with the walkers of `bq_msmo_*`: every (fold, class) fit is one column whose row list is the fold's
+training rows, and `bq_msmo_svc_heldout` takes the intercepts, the held-out decision values and the sigmoids from the walkers' state.
+
 The batched path applies under the conditions under which `SVCGridSearchCV` takes decision values from the panel: the estimator is
 on `OneVsRestSVC`'s batched path (`uses_batched_path`), the panel is 'f64' and the kernel's gamma is not a string.  Every other
 configuration runs the loop sklearn runs, `fit` on X[tr] and `decision_function` on X[te] per fold, and fits the sigmoids through
@@ -23,13 +27,15 @@ from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
 from ._base import SVC, ClassifierMixin, ConvergenceWarning
-from ._batched import (DecisionBatch, device_free_bytes, fitted_svc, platt_fit, solve_batched, solver_kind,
-                       uses_batched_decision)
+from ._batched import (ClassQuadratic, DecisionBatch, _DeviceSMOSolver, device_free_bytes, fitted_smo_svc, fitted_svc, platt_fit,
+                       run_batched_smo, smo_column_result, smo_failed_error, smo_heldout_column_cap, solve_batched,
+                       solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision)
 from .kernels import BaseEstimator
 from .model_selection import _base_params, _fold_labels, _make, _prototype, check_cv_splits, column_cap
-from .multiclass import OneVsRestSVC, uses_batched_path
+from .multiclass import OneVsRestSVC, uses_batched_path, uses_batched_smo_path
 
-__all__ = ['CalibratedSVC', 'CalibratedClassifier', 'uses_batched_calibration', 'sigmoid_probabilities', 'assemble_probabilities']
+__all__ = ['CalibratedSVC', 'CalibratedClassifier', 'uses_batched_calibration', 'uses_batched_smo_calibration',
+           'sigmoid_probabilities', 'assemble_probabilities']
 
 CalibratedClassifier = namedtuple('CalibratedClassifier', ['estimator', 'A', 'B'])
 CalibratedClassifier.__doc__ = """A fitted classifier (an `SVC`, or an `OneVsRestSVC` with more than two classes) and the sigmoids of
@@ -45,6 +51,29 @@ def uses_batched_calibration(estimator, world):
     proto = _prototype(estimator)
     return bool(uses_batched_path(proto, world) and proto.storage == 'f64' and
                 not isinstance(getattr(proto.kernel, 'gamma', None), str))
+
+
+def uses_batched_smo_calibration(estimator, world):
+    """True when `CalibratedSVC` can solve every (fold, class) as one batched-SMO column on one panel and calibrate on the device
+    (`bq_msmo_svc_heldout`): the estimator (an `SVC` or an `OneVsRestSVC`) is on `OneVsRestSVC`'s batched SMO path
+    (`uses_batched_smo_path`), its panel is 'f64' and its kernel's gamma is not a string."""
+    if not isinstance(estimator, (SVC, OneVsRestSVC)):
+        return False
+    proto = _prototype(estimator)
+    return bool(uses_batched_smo_path(proto, world) and proto.storage == 'f64' and
+                not isinstance(getattr(proto.kernel, 'gamma', None), str))
+
+
+def _row_lists(splits):
+    """per fold its training rows as an ascending row list, or None when a fold repeats a training or test row or trains on a row
+    it tests: that is another problem than a row list's"""
+    lists = []
+    for tr, te in splits:
+        rows = np.unique(tr)
+        if len(rows) != len(tr) or len(np.unique(te)) != len(te) or len(np.intersect1d(rows, te)):
+            return None
+        lists.append(rows)
+    return lists
 
 
 def sigmoid_probabilities(F, A, B):
@@ -90,7 +119,13 @@ class CalibratedSVC(ClassifierMixin, BaseEstimator):
     path ran, and `batched_decision_`: `predict_proba` takes every (fold, class) decision value from one fused pass
     (`DecisionBatch`).  A sigmoid fit that ended on a failed line search or the iteration cap warns (`ConvergenceWarning`) and
     keeps the values reached.
+
+    `smo_`: every (fold, class) fit was one column of the batched SMO solver, its row list the fold's training rows, calibrated on
+    the device from the walkers' state (`uses_batched_smo_calibration`, `bq_msmo_svc_heldout`); `batched_` is True with it.
+    `batch_smo` (None, True, False) forces that choice where the configuration allows it; None leaves it to the number of columns
+    (`takes_batched_smo`).
     """
+    batch_smo = None
 
     def __init__(self, estimator, cv=5, ensemble=True):
         self.estimator = estimator
@@ -113,8 +148,11 @@ class CalibratedSVC(ClassifierMixin, BaseEstimator):
             if not np.array_equal(_fold_labels(y[tr], multiclass)[0], self.classes_):
                 raise ValueError('the training rows of fold %d miss a class' % f)
         world = get_context().world
-        self.batched_ = uses_batched_calibration(self.estimator, world)
-        fit = self._fit_batched if self.batched_ else self._fit_loop
+        self.smo_ = False
+        if uses_batched_smo_calibration(self.estimator, world) and _row_lists(splits) is not None:
+            self.smo_ = takes_batched_smo((len(splits) + (0 if self.ensemble else 1)) * len(rows), self.batch_smo)
+        self.batched_ = self.smo_ or uses_batched_calibration(self.estimator, world)
+        fit = self._fit_batched_smo if self.smo_ else self._fit_batched if self.batched_ else self._fit_loop
         classifiers, cal, coefs = fit(X, y, splits, rows)
         kc = len(rows)
         shape = (len(splits), kc) if self.ensemble else (kc,)
@@ -242,14 +280,95 @@ class CalibratedSVC(ClassifierMixin, BaseEstimator):
             classifiers.append(self._one_vs_rest(mine) if multiclass else mine[0])
         return classifiers, cal, np.stack(coefs)
 
-    def _one_vs_rest(self, ests):
+    def _fit_batched_smo(self, X, y, splits, rows):
+        """One unsorted panel of all n rows, built as `SVCGridSearchCV`'s SMO search builds it; the columns (fold, class) with the
+        fold's training rows as row list, in solves of at most `smo_heldout_column_cap` columns, scored where the walkers' state
+        lives (`svc_heldout`, one set per fold: intercepts, held-out decision values and sigmoids from the device) and, for
+        ensemble=False, the columns (all, class) without a list, one `solve_batched_smo` as `OneVsRestSVC` runs it.  An SMO fit
+        without support vectors is not an error: its intercept is the solver's."""
+        multiclass = isinstance(self.estimator, OneVsRestSVC)
+        proto = _prototype(self.estimator)
+        n, kc, ns = len(y), len(rows), len(splits)
+        Ycls = np.stack([np.where(y == pos, 1., -1.) for pos in rows])
+        lists = _row_lists(splits)
+        held = np.zeros((ns, n), dtype=np.uint8)
+        for f, (_, te) in enumerate(splits):
+            held[f, te] = 1
+        cols = [(f, r) for f in range(ns) for r in range(kc)]
+        obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Ycls[0], storage=proto.storage, rank_one=False, compact=False)
+        ests, fits = [], []
+        oof = None if self.ensemble else np.zeros((kc, n))
+        try:
+            dev = obj.device_problem()
+            cap = smo_heldout_column_cap(n, _lib.SVC, device_free_bytes(), _lib.load().bq_problem_wide_slab_bytes(dev.handle),
+                                         calibrators=self.ensemble)
+            for c0 in range(0, len(cols), cap):
+                chunk = cols[c0:c0 + cap]
+                # ensemble: a calibrator per column; else a calibrator per class, fed by its fold columns (the rows of every class
+                # are held out once over the folds, so a solve's columns of one class score disjoint rows)
+                cal_of = np.arange(len(chunk)) if self.ensemble else np.array([r for _, r in chunk])
+                ncal = len(chunk) if self.ensemble else kc
+                solver = _DeviceSMOSolver(dev, _lib.SVC, np.stack([Ycls[r] for _, r in chunk]), proto.C, None, proto.tol,
+                                          rows=[lists[f] for f, _ in chunk])
+                try:
+                    outer, failed = run_batched_smo(solver)
+                    if failed.any():
+                        raise smo_failed_error()
+                    _, _, fit = solver.svc_heldout([f for f, _ in chunk], held, cal_of, ncal, decisions=not self.ensemble)
+                    # the columns that become estimators: every one with ensemble; else the fold columns leave their held-out
+                    # decision values and nothing else
+                    res = [smo_column_result(solver, j, outer[j]) for j in range(len(chunk))] if self.ensemble else []
+                finally:
+                    solver.close()
+                fits.append(fit)
+                if not self.ensemble:
+                    oof += fit['dec']   # the chunks' rows are disjoint and 0 elsewhere
+                for (f, r), res_j in zip(chunk, res):
+                    tr = lists[f]
+                    # the column's n-long state on the fold's rows; the threshold rows as positions among them
+                    res_j['alphas'], res_j['errors'] = res_j['alphas'][tr], res_j['errors'][tr]
+                    res_j['b_up_idx'], res_j['b_low_idx'] = (int(np.searchsorted(tr, res_j[name])) for name in ('b_up_idx', 'b_low_idx'))
+                    est = _make(SVC, _base_params(proto), {})
+                    fitted_smo_svc(est, obj, res_j, X[tr], Ycls[r][tr])
+                    ests.append((f, est))
+            if not self.ensemble:
+                for r, res_r in enumerate(solve_batched_smo(dev, _lib.SVC, Ycls, proto.C, None, proto.tol)):
+                    est = _make(SVC, _base_params(proto), {})
+                    fitted_smo_svc(est, ClassQuadratic(obj, Ycls[r]), res_r, X, Ycls[r])
+                    ests.append((None, est))
+        except BaseException:
+            obj.release()   # nothing keeps the panel: the estimators that would are dropped with this frame
+            raise
+        del dev
+        if self.ensemble:
+            cal = {key: np.concatenate([fit[key] for fit in fits]) for key in fits[0] if key != 'dec'}
+        elif len(fits) == 1:
+            cal = fits[0]   # every column of a class in one solve: the sigmoids came from the device's own buffers
+        else:
+            cal = platt_fit(oof, Ycls)   # a class's folds were spread over several solves: the same kernel on the gathered rows
+        if not self.ensemble:
+            self.oof_decision_ = oof[0].copy() if kc == 1 else oof.T.copy()
+        classifiers, coefs = [], []
+        for f in list(range(ns)) if self.ensemble else [None]:
+            mine = [est for g, est in ests if g == f]
+            tr = np.arange(n) if f is None else lists[f]
+            for est in mine:
+                if not multiclass:
+                    est.classes_ = self.classes_
+                w = np.zeros(n)
+                w[tr[est.support_]] = est.dual_coef_
+                coefs.append(w)
+            classifiers.append(self._one_vs_rest(mine, smo=True) if multiclass else mine[0])
+        return classifiers, cal, np.stack(coefs)
+
+    def _one_vs_rest(self, ests, smo=False):
         """The `OneVsRestSVC` that a batched `fit` on a fold's rows leaves, from its per-class estimators.  It predicts through
         one call per estimator: a decision batch of its own would hold a second copy of its support rows beside the one
         `decision_batch_` of all folds that `predict_proba` uses."""
         ovr = self._new()
         ovr.classes_ = self.classes_
         ovr.estimators_ = ests
-        ovr.lagrangian_, ovr.batched_ = False, True
+        ovr.lagrangian_, ovr.smo_, ovr.batched_ = False, smo, True
         ovr.batched_decision_, ovr.decision_batch_ = False, None
         return ovr
 

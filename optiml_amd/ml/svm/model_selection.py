@@ -18,7 +18,8 @@ y[te])` per candidate and fold.
 [-y; y] + epsilon; the 'svr' panel depends on neither, so every (fold, C, epsilon) of one resolved kernel is one column of
 `bq_msolver_create_svr_boxes` (ub = 0 on both halves of the held-out rows), and the columns are scored where the solver's state
 lives (`bq_msolver_svr_heldout`): per column an intercept, a support count, a held-out squared error and a held-out count come
-back, no k x n array.
+back, no k x n array.  Over an SMO estimator (`uses_batched_smo_svr_search`) every (fold, C, epsilon) is one walker column of
+`bq_msmo_*` whose row list is the fold's training rows, and `bq_msmo_svr_heldout` scores it from the walkers' state the same way.
 """
 import copy
 import itertools
@@ -29,17 +30,17 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ._base import SVC, SVR
-from ._batched import (MAX_COLUMNS, MEMORY_SHARE, _DeviceSVRSolver, _gram_matmat, column_cap, device_panel,  # noqa: F401
-                       fitted_svr, intercept, smo_column_cap, solve_batched, solve_batched_smo, solver_kind, svr_intercept,
-                       takes_batched_smo)
+from ._batched import (MAX_COLUMNS, MEMORY_SHARE, _DeviceSMOSolver, _DeviceSVRSolver, _gram_matmat, column_cap,  # noqa: F401
+                       device_panel, fitted_svr, intercept, run_batched_smo, smo_column_cap, smo_failed_error,
+                       smo_heldout_column_cap, solve_batched, solve_batched_smo, solver_kind, svr_intercept, takes_batched_smo)
 from .kernels import BaseEstimator, LinearKernel
 from .multiclass import OneVsRestSVC, uses_batched_path, uses_batched_smo_path, binarize
-from .multioutput import uses_batched_svr_path
+from .multioutput import uses_batched_smo_svr_path, uses_batched_svr_path
 from .onevsone import OneVsOneSVC
 
 __all__ = ['SVCGridSearchCV', 'SVRGridSearchCV', 'parameter_grid', 'check_cv_splits', 'plan_columns', 'plan_svr_columns',
-           'plan_smo_columns', 'aggregate_scores', 'uses_batched_search', 'uses_batched_smo_search', 'uses_batched_svr_search',
-           'r2_from_sse']
+           'plan_smo_columns', 'plan_smo_svr_columns', 'aggregate_scores', 'uses_batched_search', 'uses_batched_smo_search',
+           'uses_batched_svr_search', 'uses_batched_smo_svr_search', 'r2_from_sse']
 
 BATCHED_KEYS = frozenset({'C', 'kernel'})
 SVR_BATCHED_KEYS = frozenset({'C', 'epsilon', 'kernel'})
@@ -513,6 +514,48 @@ def plan_svr_columns(X, y, splits, candidates, base_C, base_epsilon, base_kernel
     return _stacked(groups, ('QL', 'UB'))
 
 
+def uses_batched_smo_svr_search(estimator, candidates, world):
+    """True when `SVRGridSearchCV` can solve every (candidate, fold) as one batched-SMO column on shared panels and score it on the
+    device (`bq_msmo_svr_heldout`): the estimator (an `SVR`) is on `MultiOutputSVR`'s batched SMO path
+    (`uses_batched_smo_svr_path`), the grid varies only C, epsilon and kernel, the panel is 'f64' and no kernel of the search has a
+    string gamma — the fp64 panel of a numeric gamma holds the decision kernel's values.  An fp32 panel or gamma='scale' keeps the
+    per-fold calls."""
+    if not isinstance(estimator, SVR):
+        return False
+    if any(not set(p) <= SVR_BATCHED_KEYS for p in candidates):
+        return False
+    kernels = [estimator.kernel] + [p['kernel'] for p in candidates if 'kernel' in p]
+    if any(isinstance(getattr(k, 'gamma', None), str) for k in kernels):
+        return False
+    return bool(uses_batched_smo_svr_path(estimator, world) and estimator.storage == 'f64')
+
+
+def plan_smo_svr_columns(X, y, splits, candidates, base_C, base_epsilon, base_kernel):
+    """The batched SMO SVR search's panels and columns, as `plan_svr_columns` groups them: a list of dicts {kernel: the resolved
+    kernel of the panel, cols: [(candidate, fold, C, epsilon)], Y: m x n targets (every row is y: the held-out rows' targets are
+    what the scorer compares with), rows: per column the fold's training rows, ascending}.  None when a fold repeats a training row
+    or test row, or trains on a row it tests: that is another problem than a row list's."""
+    X = np.ascontiguousarray(X, dtype=float)
+    y = np.asarray(y, dtype=float)
+    lists = []
+    for tr, te in splits:
+        rows = np.unique(tr)
+        if len(rows) != len(tr) or len(np.unique(te)) != len(te) or len(np.intersect1d(rows, te)):
+            return None
+        lists.append(rows)
+    groups, index = [], {}
+    for ci, p in enumerate(candidates):
+        C, epsilon = p.get('C', base_C), p.get('epsilon', base_epsilon)
+        kernel = p.get('kernel', base_kernel)
+        for f, (tr, _) in enumerate(splits):
+            g = _group_of(groups, index, kernel, X[tr], ('Y',))
+            g.setdefault('rows', [])
+            g['cols'].append((ci, f, C, epsilon))
+            g['Y'].append(y)
+            g['rows'].append(lists[f])
+    return _stacked(groups, ('Y',))
+
+
 def svr_column_cap(n, free_bytes, slab_bytes):
     """`column_cap` for the columns of an SVR search on n rows, whose vectors have 2n entries: `column_bytes(2 * n)` per column.
     That budgets 16 vectors of 2n; a column holds 7 (x, g, d, Qd, both bounds, its linear term) and two n-vectors (product input
@@ -541,7 +584,13 @@ class SVRGridSearchCV(_GridSearchCV):
     `best_estimator_` (a plain `SVR.fit` on all the data, refit=True) — with `n_iter_` / `status_` of shape (candidates, splits),
     and `batched_`, which says which path ran.  A fit that ends without support vectors scores NaN on either path (`SVR.fit`
     divides by zero there; GridSearchCV's error_score).  `predict` and `score` are the best estimator's.
+
+    An estimator on the batched SMO path (`uses_batched_smo_svr_search`) has every (candidate, fold) solved as one column of
+    `bq_msmo_*` whose row list is the fold's training rows and scored on the device (`bq_msmo_svr_heldout`); `smo_` says so
+    (`batched_` is True with it), and `batch_smo` (None, True, False) forces that choice where the configuration allows it (None:
+    by the number of columns, `takes_batched_smo`).  An SMO fit without support vectors predicts its intercept and has a score.
     """
+    batch_smo = None
 
     _estimator_type = SVR
     _type_error = 'estimator must be an SVR'
@@ -555,9 +604,12 @@ class SVRGridSearchCV(_GridSearchCV):
             raise ValueError('use MultiOutputSVR to train a model over more than one target')
         return y
 
-    @staticmethod
-    def _uses_batched(first, candidates, splits, y):
-        return uses_batched_svr_search(first, candidates, get_context().world)
+    def _uses_batched(self, first, candidates, splits, y):
+        world = get_context().world
+        self.smo_ = False
+        if uses_batched_smo_svr_search(first, candidates, world):
+            self.smo_ = takes_batched_smo(len(candidates) * len(splits), self.batch_smo)
+        return self.smo_ or uses_batched_svr_search(first, candidates, world)
 
     @staticmethod
     def _fallback_fit(est, Xtr, ytr, Xte, yte):
@@ -567,8 +619,47 @@ class SVRGridSearchCV(_GridSearchCV):
             score = np.nan
         return score, [(int(getattr(est.optimizer, 'iter', -1)), str(getattr(est.optimizer, 'status', '')))]
 
+    def _fit_batched_smo(self, X, y, splits, candidates, proto):
+        """every (candidate, fold) one batched-SMO column on the panel of its kernel, built as `MultiOutputSVR`'s SMO fit builds
+        it, in solves of at most `smo_heldout_column_cap` columns, scored where the walkers' state lives (`svr_heldout`, one set
+        per fold); None (before any solve) when the folds are no row lists"""
+        groups = plan_smo_svr_columns(X, y, splits, candidates, proto.C, proto.epsilon, proto.kernel)
+        if groups is None:
+            self.smo_ = False
+            return None
+        n = len(y)
+        nc, ns = len(candidates), len(splits)
+        scores = np.empty((nc, ns))
+        n_iter = np.full((nc, ns), -1, dtype=np.int64)
+        status = np.full((nc, ns), '', dtype=object)   # an SMO fit records no status (`_fallback_fit`)
+        held = np.zeros((ns, n), dtype=np.uint8)
+        for f, (_, te) in enumerate(splits):
+            held[f, te] = 1
+        for g in groups:   # one panel at a time
+            m = len(g['cols'])
+            with device_panel(X, np.hstack((-y, y)) + proto.epsilon, 'svr', g['kernel'], storage=proto.storage, rank_one=False,
+                              compact=False) as (_, dev, free, slab):
+                cap = smo_heldout_column_cap(n, _lib.SVR, free, slab)
+                for c0 in range(0, m, cap):
+                    cols = g['cols'][c0:c0 + cap]
+                    solver = _DeviceSMOSolver(dev, _lib.SVR, g['Y'][c0:c0 + cap], [C for _, _, C, _ in cols],
+                                              [eps for _, _, _, eps in cols], proto.tol, rows=g['rows'][c0:c0 + cap])
+                    try:
+                        outer, failed = run_batched_smo(solver)
+                        if failed.any():
+                            raise smo_failed_error()
+                        _, _, sse, _ = solver.svr_heldout([f for _, f, _, _ in cols], held)
+                    finally:
+                        solver.close()
+                    for j, (ci, f, _, _) in enumerate(cols):
+                        scores[ci, f] = r2_from_sse(sse[j], y[splits[f][1]])
+                        n_iter[ci, f] = outer[j]
+        return scores, n_iter, status
+
     def _fit_batched(self, X, y, splits, candidates, base, first):
         proto = _make(SVR, base, {})
+        if self.smo_:
+            return self._fit_batched_smo(X, y, splits, candidates, proto)
         n = len(y)
         nc, ns = len(candidates), len(splits)
         scores = np.empty((nc, ns))
