@@ -46,7 +46,7 @@ extern "C" {
 #define BQ_ERR_NOMEM (-6)
 
 /* 2 (round 6): bq_ctx_probe_stall takes behind_collective, bq_problem_create_dense takes layout flags, bq_problem_layout,
- * bq_ctx_release_held and the state snapshot were added: a consumer built against version 1 must be rebuilt */
+ * bq_ctx_release_held_memory and the state snapshot were added: a consumer built against version 1 must be rebuilt */
 /* 3: the batched one-vs-rest solver (bq_msolver_*) and bq_problem_gram_matmat were added */
 /* (still 3: bq_msolver_create_boxes and bq_problem_gram_matmat_wide were added; nothing existing changed) */
 /* (still 3: bq_msolver_create_pairs, bq_problem_gram_matmat_pairs, bq_pairs_slab_bytes and bq_pairs_work_list were added) */
@@ -86,7 +86,8 @@ enum { BQ_PLAIN = 0, BQ_SVC = 1, BQ_SVR = 2 };                       /* Hessian 
 /* OR-ed into the structure: keep the WHOLE n x n Gram panel (row blocks, pitch round_up(n, 1024)) instead of the packed
  * lower-triangular tile rows: twice the memory and twice the bytes per product, but every row is contiguous and K keeps
  * the reference's own (not exactly symmetric) rounding of the RBF distances.  An option, not a default: measured on SMO
- * (single-row gathers) it changes nothing, n=100k fit 0.93 s either way — the sweeps are bound by one CU's gather rate. */
+ * (single-row gathers) it changes nothing, n=100k fit 0.93 s either way — the sweeps are bound by one CU's gather rate.
+ * The factorising solvers and bq_problem_x_star read the upper triangle of such a panel (as of dense row blocks, below). */
 #define BQ_FULL_PANEL 32
 /* OR-ed into the structure: choose WHERE the resident panel lives.  The rate at which the panel product streams a panel is a
  * stable property of the physical region the allocation landed in (five panels of one n = 100 000 problem held at once ran 6.04 -
@@ -210,7 +211,16 @@ int bq_sym_row_block(int64_t n, int rank, int world, int64_t *begin, int64_t *en
  * OR-ed into `storage`:  BQ_DENSE_ROWS   row blocks whatever Q is (the layout of rounds 1-5; what a comparison needs);
  *                        BQ_DENSE_LOWER  the caller vouches for symmetry: only the lower triangle of the host matrix is read
  *                                        (LAPACK's uplo = 'L'), nothing is compared, half the PCIe traffic;
- *                        BQ_PLACE_PANEL  as for kernel problems (packed layout only). */
+ *                        BQ_PLACE_PANEL  as for kernel problems (packed layout only).
+ * Which triangle a FACTORISATION reads (InteriorPoint, ActiveSet, bq_problem_x_star assemble a symmetric H from the resident
+ * copy, one triangle mirrored, as LAPACK's potrf does): of row blocks the UPPER one, H[i][j] = Q[min(i,j)][max(i,j)] — scipy's
+ * cho_factor default (lower=False), i.e. what the reference's cho_factor(Q), cho_factor(Q[A,:][:,A]) and cho_factor(H) read
+ * (opti/_base.py:263, active_set.py:141, interior_point.py:235); of the packed layout the lower one, which for a Q == Q' is the
+ * same matrix and for BQ_DENSE_LOWER is all that was ever read.  Products, f and g always apply Q as given (`Q @ x`).
+ * ActiveSet's kept factor and its product-free f of ratio steps rest on H == Q.  On row blocks they stay on while the resident
+ * copy is symmetric up to rounding, max |Q_ij - Q_ji| <= 64 ulps of max |Q_ij| (measured once per problem: a Q assembled in
+ * floating point); on a Q that is not symmetric every iteration factorises Q[A,A] afresh and forms f by a product, as the
+ * reference does (BQ_COUNT_REUSED and BQ_COUNT_NO_PRODUCT stay 0). */
 #define BQ_DENSE_ROWS 256
 #define BQ_DENSE_LOWER 512
 int bq_problem_create_dense(bq_ctx *ctx, int64_t n, const double *Q, const double *q, int storage,

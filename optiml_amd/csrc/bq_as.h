@@ -121,6 +121,9 @@ struct as_ws {
     // product-free f of a ratio step (as_step_min_kernel): allowed at all / a run is open / its length since f was last formed by a
     // product / how many steps went without a product (bq_solver_counter)
     bool f_chain = true, chain_ok = false;
+    // the factorised H is the matrix the products apply (bq_dense_h_is_q: not so for a non-symmetric dense Q in row blocks, where
+    // the kept factor and the product-free f are off)
+    bool h_is_q = true;
     double *g0 = nullptr;             // the gradient at the starting point (device, ldN)
     const double *gref = nullptr;     // the gradient the run scales: g0 until the first release, s->g after it
     int chain_len = 0;

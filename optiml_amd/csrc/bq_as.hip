@@ -432,7 +432,10 @@ int bq_as_start(bq_solver *s) {
     w->host_scal_d = reinterpret_cast<int *>(as_dev(w->host_scal));
     BQ_HIP(bq_dev_zeroed(hipSuccess, w->mem, &w->mail_ticket, 2, ctx->stream));
     w->mailbox = !s->as_cg && bq_hook_on("as_mailbox");
-    w->f_chain = !s->as_cg && bq_hook_on("as_f_chain");
+    // (never on a dense Q that is not symmetric: Q_AA d_A = -g_A needs the factorised matrix to be the one the gradient comes from, and
+    // there the factor is of the mirrored upper triangle while g = Qx + q takes Q as given — as_step_min_kernel)
+    if (!s->as_cg) BQ_TRY(bq_dense_h_is_q(s->p, &w->h_is_q));
+    w->f_chain = !s->as_cg && w->h_is_q && bq_hook_on("as_f_chain");
 #ifdef BQ_AS_TIMING   // diagnostic build (BQ_EXTRA_CXXFLAGS=-DBQ_AS_TIMING): where the host's time goes per iteration, printed by bq_as_free
     w->timing = true;
 #endif
@@ -563,7 +566,9 @@ int bq_as_iterate(bq_solver *s) {
     if (s->as_cg) return as_cg_iterate(s, w);
     bool solved = false;
     // (an empty free set has nothing to keep: with hook as_schur_min=0 it reached the kept-factor path and launched empty grids)
-    if (as_schur_enabled() && nA > 0 && nA >= as_schur_min()) BQ_TRY(as_schur_step(s, w, nA, &solved));
+    // A dense Q that is not symmetric re-factorises every iteration: a base variable pinned by a multiplier row enters the other
+    // rows through the mirrored H[j][k], the reference's right-hand side takes Q[j][k] as given (active_set.py:132-136)
+    if (as_schur_enabled() && w->h_is_q && nA > 0 && nA >= as_schur_min()) BQ_TRY(as_schur_step(s, w, nA, &solved));
     if (!solved && w->sch) w->sch->valid = false;   // the classic path below overwrites the kept factor
     if (solved) {
         w->last_branch = w->host_ints[2] ? 1 : 0;

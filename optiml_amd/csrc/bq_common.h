@@ -211,6 +211,7 @@ struct bq_problem {
     double place_ms[32] = {0.0};
     double alloc_ms = 0.0;     // what the driver took to hand out the panel (0: it came from the context's cache)
     bool symmetric = false;
+    double rows_asym = -1.0;   // dense row blocks: max |Q_ij - Q_ji| / max |Q_ij| of the resident copy (bq_dense_h_is_q; < 0: not measured)
     bool streamed = false;     // BQ_STREAM: no panel, Gram tiles recomputed inside every product (stream_img)
     void *stream_img = nullptr;
     int64_t I0 = 0, I1 = 0, nb = 0;
@@ -357,6 +358,11 @@ int bq_launch_h52_convert(bq_ctx *ctx, const bq_problem *p, void *image, int *ba
 // bq_alloc.cpp: the problems that hold an image a failing allocation may take back — an allocation failing on the THREAD that
 // registered the image (the thread that built it and runs its products): an image is memory in use, and no other thread may free it
 void bq_image_register(bq_problem *p, bool alive);
+// A dense Q kept in row blocks (BQ_DENSE_ROWS, or a Q that is not symmetric): the panel product applies Q as given while the
+// factorisations work on the symmetric H mirrored from its upper triangle (bq_qelem.h).  What rests on H == Q asks bq_dense_h_is_q
+// (bq_dense.hip) whether the two agree up to rounding.
+static inline bool bq_dense_row_blocks(const bq_problem *p) { return p->kernel < 0 && !p->symmetric; }
+int bq_dense_h_is_q(bq_problem *p, bool *yes);
 // hook compact_panel=0: eligible RBF panels keep the plain fp64 layout (the A/B of the two layouts in one build)
 static inline bool bq_compact_allowed() { return bq_hook_on("compact_panel"); }
 

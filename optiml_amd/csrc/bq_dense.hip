@@ -15,6 +15,8 @@
 // (rows of earlier ranks, its own columns) and compares it with its lower-left rectangle; the ranks then agree on the outcome with
 // one all-reduce of a flag (all of them were handed the same Q).
 #include <algorithm>
+#include <cfloat>
+#include <cstring>
 
 #include "bq_common.h"
 
@@ -197,6 +199,82 @@ __global__ void f64_to_f32_rows_kernel(const double *__restrict__ src, int64_t n
     const int64_t r = blockIdx.y;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x)
         dst[r * ld + j] = (float)src[r * n + j];
+}
+
+// Row blocks of a whole n x n matrix (pitch ld): out[0] = max |Q_ij - Q_ji|, out[1] = max |Q_ij|, as bit patterns of non-negative
+// doubles (they order like the values, so the blocks meet in two atomic maxima; out is zeroed by the caller).  One workgroup per
+// pair of mirrored 32 x 32 tiles on/below the diagonal, both read along their rows and transposed through LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void dense_asym_kernel(const T *__restrict__ panel, int64_t ld, int64_t n,
+                                                         unsigned long long *__restrict__ out) {
+    if (blockIdx.x > blockIdx.y) return;
+    __shared__ double up[32][33];
+    __shared__ double wd[4], wa[4];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t r0 = (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
+    for (int k = ty; k < 32; k += 8) {   // the mirror image: rows c0 .., columns r0 ..
+        const int64_t r = c0 + k, c = r0 + tx;
+        up[k][tx] = (r < n && c < n) ? (double)panel[r * ld + c] : 0.0;
+    }
+    __syncthreads();
+    double d = 0.0, a = 0.0;
+    for (int k = ty; k < 32; k += 8) {
+        const int64_t r = r0 + k, c = c0 + tx;
+        if (r < n && c < n) {
+            const double lo = (double)panel[r * ld + c], hi = up[tx][k];
+            d = fmax(d, fabs(lo - hi));
+            a = fmax(a, fmax(fabs(lo), fabs(hi)));
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        d = fmax(d, __shfl_down(d, off, 64));
+        a = fmax(a, __shfl_down(a, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wd[threadIdx.x >> 6] = d;
+        wa[threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        d = fmax(fmax(wd[0], wd[1]), fmax(wd[2], wd[3]));
+        a = fmax(fmax(wa[0], wa[1]), fmax(wa[2], wa[3]));
+        if (d > 0.0) atomicMax(&out[0], (unsigned long long)__double_as_longlong(d));
+        if (a > 0.0) atomicMax(&out[1], (unsigned long long)__double_as_longlong(a));
+    }
+}
+
+// Is the H a factorisation assembles (one triangle mirrored, bq_qelem.h) the matrix the products apply, up to rounding?  Yes for
+// every packed and every kernel-built panel.  A dense Q in row blocks is measured once (cached in the problem): yes while
+// max |Q_ij - Q_ji| <= 64 ulps of max |Q_ij| — a Q assembled in floating point whose mirror images differ in their last bits, where
+// what rests on H == Q (bq_as.hip: the kept factor, the product-free f) errs by those bits — no for a Q that is not symmetric.
+int bq_dense_h_is_q(bq_problem *p, bool *yes) {
+    *yes = true;
+    if (!bq_dense_row_blocks(p)) return BQ_OK;
+    if (p->rows_asym < 0.0) {
+        if (p->r0 != 0 || p->r1 != p->n || p->panel == nullptr) {   // (a factorisation needs the whole panel anyway)
+            *yes = false;
+            return BQ_OK;
+        }
+        bq_ctx *c = p->ctx;
+        bq_scratch mem;
+        unsigned long long *out = nullptr, host[2] = {0, 0};
+        BQ_HIP(bq_dev_zeroed(hipSuccess, mem, &out, 2, c->stream));
+        const unsigned nt = (unsigned)((p->n + 31) / 32);
+        if (p->storage == BQ_F64)
+            dense_asym_kernel<double><<<dim3(nt, nt), 256, 0, c->stream>>>((const double *)p->panel, p->ld, p->n, out);
+        else
+            dense_asym_kernel<float><<<dim3(nt, nt), 256, 0, c->stream>>>((const float *)p->panel, p->ld, p->n, out);
+        BQ_HIP(hipGetLastError());
+        BQ_HIP(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, c->stream));
+        BQ_SYNC(c);
+        double d, a;
+        memcpy(&d, &host[0], 8);
+        memcpy(&a, &host[1], 8);
+        p->rows_asym = a > 0.0 ? d / a : 0.0;
+    }
+    *yes = p->rows_asym <= 64.0 * DBL_EPSILON;
+    return BQ_OK;
 }
 
 // row blocks: this rank's rows [r0, r1) of Q, all n columns, pitch p->ld

@@ -163,6 +163,10 @@ class Quadratic(OptimizationFunction):
     `Q == Q.T` holds exactly — compared on the device while Q is uploaded — and whole rows otherwise, so a Q that is not
     symmetric keeps NumPy's `Q @ x` (the reference never checks, optiml/opti/_base.py:249-256).  `symmetric=True`: the caller
     vouches for it, only the lower triangle of Q is read (LAPACK's uplo='L').  `symmetric=False`: whole rows whatever Q is.
+    What factorises (`x_star()`, InteriorPoint, ActiveSet) reads the UPPER triangle of whole rows, as the reference's
+    `cho_factor` calls do (scipy's default `lower=False`); products, `function` and `jacobian` apply Q as given.  On a Q that is
+    not symmetric (its mirror images differ by more than 64 ulps of max |Q|) ActiveSet re-factorises in every iteration: the kept
+    factor and the product-free objective need the two matrices to be one.
     `tune_placement=True`: as for `KernelQuadratic` (packed copies of >= 1 GB only).
     """
 

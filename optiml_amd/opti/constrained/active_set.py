@@ -38,6 +38,9 @@ class ActiveSet(BoxConstrainedQuadraticOptimizer):
         self.minres_iterations = solver.counter(_lib.COUNT_MINRES)
         # ratio-step iterations whose f(x) came from the line-search identity instead of a product with Q
         self.product_free_iterations = solver.counter(_lib.COUNT_NO_PRODUCT)
+        # iterations solved through the kept factor of a base set, and the base factorisations behind them (csrc/bq_as_schur.hip)
+        self.reused_factor_iterations = solver.counter(_lib.COUNT_REUSED)
+        self.base_factorisations = solver.counter(_lib.COUNT_REFACTOR)
 
 
 class ActiveSetCG(ActiveSet):
