@@ -681,6 +681,20 @@ enum { BQ_SMO_ALPHAS = 0,   /* n (BQ_SVC) or [alpha+; alpha-] 2n (BQ_SVR) */
                              * entries read did not hash to the published value, results rejected by their own checksum —
                              * the two rejection counts are self-checks of the inter-workgroup hand-off and must be 0 */ };
 int bq_smo_create(bq_problem *p, int task, const double *y, double C, double epsilon, double tol, bq_smo **out);
+/* bq_smo_create with a box per row: 0 <= alpha_i <= Cw[i], Cw[i] = C * sample_weight_i * class_weight[y_i] — what libsvm and
+ * sklearn.svm.SVC / SVR(class_weight=, fit(sample_weight=)) solve; the reference (smo.py:99-357, :386-797) has the one C only.
+ * Index 2 the examined sample, 1 its partner (smo.py:130-224 / :447-600): membership of row i in the free / up / low sets
+ * (classification) and its kind and clipping (regression) use Cw[i]; the pair bounds are
+ *   BQ_SVC  y1 != y2: L = max(0, a2 - a1), H = min(C2, C1 + a2 - a1);  y1 == y2: L = max(0, a2 + a1 - C1), H = min(C2, a2 + a1);
+ *           the new multipliers snap to their own box: n > C - 1e-8 C ? C : (n <= 1e-8 C ? 0 : n), C2 for n2 and C1 for n1;
+ *   BQ_SVR  (p1, p2): L = max(0, g - C1), H = min(C2, g);        (p1, m2): L = max(0, -g), H = min(C2, C1 - g);
+ *           (m1, p2): L = max(0, g), H = min(C2, C1 + g);        (m1, m2): L = max(0, -g - C1), H = min(C2, -g),
+ *           g = (p1 - m1) + (p2 - m2).
+ * With C1 == C2 each is bq_smo_create's expression operation for operation: on a constant vector Cw = C the solver has the
+ * bits of bq_smo_create(p, task, y, C, epsilon, tol), with or without helper workgroups (they form sums over the support list
+ * and never read a box).  Cw: n, every entry finite and > 0, else BQ_ERR_BADARG before any device call; a 7-byte (compact)
+ * panel is BQ_ERR_BADARG too.  Everything else — run, get, destroy, the other argument checks — as bq_smo_create. */
+int bq_smo_create_weighted(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol, bq_smo **out);
 int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, int *finished);
 int bq_smo_get(bq_smo *s, int what, double *out);
 int bq_smo_destroy(bq_smo *s);
@@ -701,6 +715,17 @@ int bq_smo_destroy(bq_smo *s);
 typedef struct bq_msmo bq_msmo;
 int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *epsilon, double tol,
                    const int64_t *row_ptr, const int32_t *rows, bq_msmo **out);
+/* bq_msmo_create with a box per column and row: CW is k x n and column c is the solver bq_smo_create_weighted(p, task, Y[c],
+ * CW[c], epsilon[c], tol) makes (formulas there), run without helper workgroups — what OneVsRestClassifier /
+ * OneVsOneClassifier(SVC(class_weight='balanced')) do by one weighted libsvm fit per column.  A column whose row of CW is
+ * constant has the bits of the bq_msmo_create column with that C; a weighted column has the bits of the weighted single solver,
+ * at any position, beside any other columns and however the outer iterations are cut into runs.  On a row a column trains on
+ * (every row without row lists) CW must be finite and > 0, else BQ_ERR_BADARG before any device call; entries on rows outside
+ * a column's list are never read (they may be NaN).  A 7-byte (compact) panel is BQ_ERR_BADARG.  Everything else — the other
+ * arguments and their checks, run, get, destroy, bq_msmo_vote_heldout / _svr_heldout / _svc_heldout, which read multipliers,
+ * labels and the walkers' records only — as bq_msmo_create.  Device memory: 8 n more bytes per column. */
+int bq_msmo_create_weighted(bq_problem *p, int task, int k, const double *Y, const double *CW, const double *epsilon, double tol,
+                            const int64_t *row_ptr, const int32_t *rows, bq_msmo **out);
 /* At most max_outer launches; each advances every column still running by one outer iteration (smo.py:327-351 / :764-789), finished
  * columns are not launched.  outer / finished / failed: k each — outer iterations done, the loop has terminated, and the walker
  * met the reference's 'unexpected status' (smo.py:270-271, :756: such a column is finished too; the others go on). */

@@ -152,11 +152,14 @@ PROTOTYPES = {
     'bq_al_solver_dual_size': (C.c_int, [_vp, C.POINTER(_i64)]),
     'bq_al_solver_set_schedules': (C.c_int, [_vp, _dp, _dp, _i64]),
     'bq_smo_create': (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.POINTER(_vp)]),
+    'bq_smo_create_weighted': (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, C.POINTER(_vp)]),
     'bq_smo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),
     'bq_smo_get': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_smo_destroy': (C.c_int, [_vp]),
     'bq_msmo_create': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.POINTER(_i64), C.POINTER(C.c_int32),
                                  C.POINTER(_vp)]),
+    'bq_msmo_create_weighted': (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.POINTER(_i64), C.POINTER(C.c_int32),
+                                          C.POINTER(_vp)]),
     'bq_msmo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), _ip, _ip]),
     'bq_msmo_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     'bq_msmo_destroy': (C.c_int, [_vp]),

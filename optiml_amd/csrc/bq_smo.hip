@@ -51,6 +51,7 @@ struct bq_smo {
     int task = BQ_SVC;
     int64_t n = 0;
     double C = 1.0, eps = 0.0, tol = 1e-3;
+    double *Cw = nullptr;   // n per-row boxes (bq_smo_create_weighted), or null: the one C
     double *y = nullptr, *a = nullptr, *am = nullptr, *err = nullptr;   // a: alpha (SVC) / alpha+ (SVR); am: alpha-
     int *nz = nullptr;                                                   // n: support list (ascending indices)
     double *cf = nullptr;                                                // n: and its coefficients
@@ -186,6 +187,28 @@ __device__ __forceinline__ unsigned int dot_check(long long bits) {
     return (unsigned int)(u >> 32) ^ 0x5bd1e995u;
 }
 
+// The box of a dual: 0 <= alpha_i <= C_i.  BoxScalar holds the one C of an unweighted problem and returns it for any row —
+// its instantiations are the kernels as they were.  BoxRows reads C_i = C * sample_weight_i * class_weight[y_i] from a
+// vector by panel row (bq_smo_create_weighted, or column c's row of bq_msmo_create_weighted's k x n array); only rows the
+// walker examines, pairs with or keeps in its support list are read, so entries on rows outside a column's row list never
+// are.  Wherever a formula below says C1 / C2 it is the box of the partner / of the examined sample; with C1 == C2 each is
+// the scalar expression operation for operation, so BoxRows on a constant vector walks BoxScalar's path bit for bit.
+struct BoxScalar {
+    static constexpr bool per_row = false;
+    double C;
+    __device__ __forceinline__ double operator()(int64_t) const { return C; }
+    __device__ __forceinline__ double lane(bool, int64_t) const { return C; }
+    __device__ __forceinline__ double staged(const double *, int) const { return C; }
+};
+struct BoxRows {
+    static constexpr bool per_row = true;
+    const double *Cw;
+    __device__ __forceinline__ double operator()(int64_t i) const { return Cw[i]; }
+    // a lane past the batch reads nothing; `staged`: the batch's copy in LDS (see SmoShared)
+    __device__ __forceinline__ double lane(bool in, int64_t i) const { return in ? Cw[i] : 0.0; }
+    __device__ __forceinline__ double staged(const double *slot, int w) const { return slot[w]; }
+};
+
 template <typename T>
 struct KView {
     bq_pview<T> panel;
@@ -244,6 +267,7 @@ struct SmoShared {
     long long i2;                 // the examined sample of a pair step
     int used, stop, fast;         // batch bookkeeping of the sweep drivers
     double ba[SMO_T / 64], by[SMO_T / 64], bE[SMO_T / 64], bm[SMO_T / 64];   // batch: multiplier(s), label/target, error
+    // BoxRows only: the batch's boxes are staged in the slot the task leaves unused (classification: bm, regression: by)
     int mem1, mem2;               // new list membership of the two touched samples
     double cf1, cf2;              // and their new coefficients
     int nnz;                      // length of the support list
@@ -657,13 +681,15 @@ __device__ __forceinline__ int sup_lower_bound(const SupList &L, const SupGlobal
 // classification (smo.py:130-319)
 // ---------------------------------------------------------------------------------------------------------------
 // thread 0: examine sample i2 (smo.py:278-319) and, if it violates, solve the pair (:130-224).  E2 is the sample's
-// error (cached, or just formed).  Returns true when a pair step was taken; its data is left in S for svc_after_step.
-template <typename T>
+// error (cached, or just formed), C2 its box.  Returns true when a pair step was taken; its data is left in S for
+// svc_after_step.
+template <typename T, typename Box>
 __device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, const double *y, double *a, double *err,
-                                            double C, double tol, long long i2, double a2, double y2, double E2) {
-    const bool free2 = a2 > 0.0 && a2 < C;
-    const bool up2 = (y2 == 1.0 && a2 == 0.0) || (y2 == -1.0 && a2 == C);     // I1 or I2
-    const bool low2 = (y2 == 1.0 && a2 == C) || (y2 == -1.0 && a2 == 0.0);    // I3 or I4
+                                            const Box &Cb, double C2, double tol, long long i2, double a2, double y2,
+                                            double E2) {
+    const bool free2 = a2 > 0.0 && a2 < C2;
+    const bool up2 = (y2 == 1.0 && a2 == 0.0) || (y2 == -1.0 && a2 == C2);     // I1 or I2
+    const bool low2 = (y2 == 1.0 && a2 == C2) || (y2 == -1.0 && a2 == 0.0);    // I3 or I4
     if (!free2) {
         err[i2] = E2;
         if (up2 && E2 < S.b_up) {
@@ -679,14 +705,14 @@ __device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, con
     if ((free2 || low2) && E2 - S.b_up > 2 * tol) i1 = S.i_up;
     if (i1 >= 0 && free2) i1 = (S.b_low - E2 > E2 - S.b_up) ? S.i_low : S.i_up;
     if (i1 < 0 || i1 == i2) return false;
-    const double a1 = a[i1], y1 = y[i1], E1 = err[i1];
-    double L, H;
+    const double a1 = a[i1], y1 = y[i1], E1 = err[i1], C1 = Cb(i1);
+    double L, H;   // 0 <= n2 <= C2 and 0 <= n1 <= C1 along the pair's line
     if (y1 != y2) {
         L = fmax(0.0, a2 - a1);
-        H = fmin(C, C + a2 - a1);
+        H = fmin(C2, C1 + a2 - a1);
     } else {
-        L = fmax(0.0, a2 + a1 - C);
-        H = fmin(C, a2 + a1);
+        L = fmax(0.0, a2 + a1 - C1);
+        H = fmin(C2, a2 + a1);
     }
     if (L == H) return false;
     const double k11 = K.at(i1, i1), k22 = K.at(i2, i2), k12 = K.at(i1, i2);
@@ -704,8 +730,8 @@ __device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, con
     // own entries of the error cache, with the old multipliers (smo.py:203-204)
     err[i1] = E1 + (__dmul_rn(c1, k11) + __dmul_rn(c2, k12));
     err[i2] = E2 + (__dmul_rn(c1, k12) + __dmul_rn(c2, k22));
-    n2 = n2 > C - __dmul_rn(1e-8, C) ? C : (n2 <= __dmul_rn(1e-8, C) ? 0.0 : n2);
-    n1 = n1 > C - __dmul_rn(1e-8, C) ? C : (n1 <= __dmul_rn(1e-8, C) ? 0.0 : n1);
+    n2 = n2 > C2 - __dmul_rn(1e-8, C2) ? C2 : (n2 <= __dmul_rn(1e-8, C2) ? 0.0 : n2);
+    n1 = n1 > C1 - __dmul_rn(1e-8, C1) ? C1 : (n1 <= __dmul_rn(1e-8, C1) ? 0.0 : n1);
     a[i1] = n1;
     a[i2] = n2;
     S.mem1 = n1 != 0.0;
@@ -720,9 +746,9 @@ __device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, con
 }
 
 // all threads, after a pair step: support list, error cache of the free set, thresholds (smo.py:199-201, :241-271)
-template <typename T>
+template <typename T, typename Box>
 __device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const SupGlobal &G, const KView<T> &K,
-                                               const double *y, double *a, double *err, double C, const SmoSpec &P) {
+                                               const double *y, double *a, double *err, const Box &Cb, const SmoSpec &P) {
     const int tid = threadIdx.x;
     const long long i1 = S.i1, i2 = S.i2;
     spec_begin(P, S);
@@ -733,8 +759,8 @@ __device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const S
     ValIdx hi{-DBL_MAX, -1}, lo{DBL_MAX, -1};
     for (int q = tid; q < S.nnz; q += SMO_T) {   // the free set is a subset of the support list
         const int64_t j = sup_idx(L, G, q);
-        const double aj = a[j];
-        if (aj > 0.0 && aj < C) {
+        const double aj = a[j], Cj = Cb(j);
+        if (aj > 0.0 && aj < Cj) {
             double e = err[j];
             if (j != i1 && j != i2) {
                 e += __dmul_rn(c1, K.at(i1, j)) + __dmul_rn(c2, K.at(i2, j));
@@ -762,9 +788,9 @@ __device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const S
         const long long pair[2] = {i1, i2};
         for (int k = 0; k < 2; ++k) {   // the two touched samples when they left the free set (smo.py:253-268)
             const long long i = pair[k];
-            const double ai = a[i], yi = y[i], ei = err[i];
-            if (ai > 0.0 && ai < C) continue;
-            const bool low_i = (yi == 1.0 && ai == C) || (yi == -1.0 && ai == 0.0);
+            const double ai = a[i], yi = y[i], ei = err[i], Ci = Cb(i);
+            if (ai > 0.0 && ai < Ci) continue;
+            const bool low_i = (yi == 1.0 && ai == Ci) || (yi == -1.0 && ai == 0.0);
             if (low_i) {
                 if (ei > S.b_low) {
                     S.b_low = ei;
@@ -780,8 +806,8 @@ __device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const S
     __syncthreads();
 }
 
-// One wave, one lane per sample of a batch of B <= 64 samples starting at i (lane w: multiplier a2, label y2, error E2;
-// `in` = w < B), no side effects until it is known to apply: within a batch without a pair step b_up only falls and
+// One wave, one lane per sample of a batch of B <= 64 samples starting at i (lane w: multiplier a2, label y2, error E2,
+// box C; `in` = w < B), no side effects until it is known to apply: within a batch without a pair step b_up only falls and
 // b_low only rises (smo.py:285-291), so a sample that does not violate the thresholds the batch ENDS with violates none
 // of the intermediate ones — then the sequential examine of the batch reduces to storing the new errors and to a
 // first-minimum / first-maximum over the batch, which the lanes do at once.  Returns false (nothing written) when any
@@ -828,9 +854,9 @@ __device__ __forceinline__ bool svc_quiet_batch(SmoShared &S, double *err, doubl
 
 // The walker: one outer iteration (a full sweep over the samples R lists, or free-set sweeps until they stall) of one
 // dual, by one whole workgroup.  Without helpers (P.helpers == 0) it waits for no other workgroup at any point.
-template <typename T>
+template <typename T, typename Box>
 __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const SmoRows &R, const double *__restrict__ y,
-                                             double *a, double *err, const SupGlobal &G, double C, double tol,
+                                             double *a, double *err, const SupGlobal &G, const Box Cb, double tol,
                                              bq_smo_scal *sc, const SmoSpec &P) {
     __shared__ SmoShared S;
     __shared__ SupList L;
@@ -880,7 +906,8 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
                         const bool in = lane < B;
                         const int64_t sw = in ? R(i + lane) : 0;
                         const double a2 = in ? a[sw] : 0.0, y2 = in ? y[sw] : 0.0;
-                        const bool free2 = in && a2 > 0.0 && a2 < C;
+                        const double C2 = Cb.lane(in, sw);   // the lane's own box, staged beside its multiplier and label
+                        const bool free2 = in && a2 > 0.0 && a2 < C2;
                         const bool need = in && !free2;
                         smo_u4 res = {0u, 0u, 0u, 0u};
                         if (need) res = res_load(P, sw);
@@ -894,7 +921,7 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
                                     E2 = __longlong_as_double(bits) - y2;
                                 else if (in)
                                     E2 = err[sw];
-                                wide = svc_quiet_batch(S, err, C, tol, R, i, B, in, a2, y2, E2);
+                                wide = svc_quiet_batch(S, err, C2, tol, R, i, B, in, a2, y2, E2);
                             }
                         }
                     }
@@ -911,13 +938,14 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
             }
             if (i + wv < R.m) {   // wave-uniform
                 const int64_t s = R(i + wv);
-                const double as = a[s], ys = y[s];
+                const double as = a[s], ys = y[s], Cs = Cb(s);
                 double E = 0.0;
-                if (!(as > 0.0 && as < C)) E = wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B) - ys;
+                if (!(as > 0.0 && as < Cs)) E = wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B) - ys;
                 if (lane == 0) {
                     S.ba[wv] = as;
                     S.by[wv] = ys;
-                    S.bE[wv] = (as > 0.0 && as < C) ? err[s] : E;
+                    S.bE[wv] = (as > 0.0 && as < Cs) ? err[s] : E;
+                    if constexpr (Box::per_row) S.bm[wv] = Cs;
                 }
             }
             __syncthreads();
@@ -926,8 +954,8 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
             // fast path: wave 0 examines the whole batch at once when it holds no possible violator
             if (wv == 0) {
                 const bool in = lane < B;
-                const bool fast = svc_quiet_batch(S, err, C, tol, R, i, B, in, in ? S.ba[lane] : 0.0, in ? S.by[lane] : 0.0,
-                                                  in ? S.bE[lane] : 0.0);
+                const bool fast = svc_quiet_batch(S, err, Cb.staged(S.bm, in ? lane : 0), tol, R, i, B, in, in ? S.ba[lane] : 0.0,
+                                                  in ? S.by[lane] : 0.0, in ? S.bE[lane] : 0.0);
                 if (lane == 0) S.fast = fast ? 1 : 0;
             }
             __syncthreads();
@@ -936,7 +964,7 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
                 int used = B;
                 S.go = 0;
                 for (int w = 0; w < B; ++w) {
-                    if (svc_examine(S, K, y, a, err, C, tol, R(i + w), S.ba[w], S.by[w], S.bE[w])) {
+                    if (svc_examine(S, K, y, a, err, Cb, Cb.staged(S.bm, w), tol, R(i + w), S.ba[w], S.by[w], S.bE[w])) {
                         S.go = 1;
                         used = w + 1;
                         break;
@@ -947,7 +975,7 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
             __syncthreads();
             SMO_STAMP(4)   // sequential walk of the batch (incl. the pair solve)
             if (S.go) {
-                svc_after_step(S, L, G, K, y, a, err, C, P);
+                svc_after_step(S, L, G, K, y, a, err, Cb, P);
                 ++changed;
                 ++steps;
                 SMO_STAMP(5)   // list edit, error cache, thresholds
@@ -974,11 +1002,11 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
                 S.stop = 1;
                 for (int q = sup_lower_bound(L, G, S.nnz, last + 1); q < S.nnz; ++q) {
                     const long long j = sup_idx(L, G, q);
-                    const double aj = a[j];
-                    if (aj > 0.0 && aj < C) {
+                    const double aj = a[j], Cj = Cb(j);
+                    if (aj > 0.0 && aj < Cj) {
                         S.stop = 0;
                         S.i2 = j;
-                        S.go = svc_examine(S, K, y, a, err, C, tol, j, aj, y[j], err[j]) ? 1 : 0;
+                        S.go = svc_examine(S, K, y, a, err, Cb, Cj, tol, j, aj, y[j], err[j]) ? 1 : 0;
                         break;
                     }
                 }
@@ -986,7 +1014,7 @@ __device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const
             __syncthreads();
             if (S.stop) break;
             if (S.go) {
-                svc_after_step(S, L, G, K, y, a, err, C, P);
+                svc_after_step(S, L, G, K, y, a, err, Cb, P);
                 ++changed;
                 ++steps;
             }
@@ -1026,7 +1054,19 @@ __global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, c
         smo_helper(K, n, G, P);
         return;
     }
-    smo_svc_walk(K, n, SmoRows{nullptr, n}, y, a, err, G, C, tol, sc, P);
+    smo_svc_walk(K, n, SmoRows{nullptr, n}, y, a, err, G, BoxScalar{C}, tol, sc, P);
+}
+
+// the same with per-row boxes Cw (n): bq_smo_create_weighted
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svc_rows_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
+                                                             double *a, double *err, SupGlobal G, const double *Cw,
+                                                             double tol, bq_smo_scal *sc, SmoSpec P) {
+    if (blockIdx.x != 0) {
+        smo_helper(K, n, G, P);   // the helpers form sum_q c_q K[s][idx_q] only: no box
+        return;
+    }
+    smo_svc_walk(K, n, SmoRows{nullptr, n}, y, a, err, G, BoxRows{Cw}, tol, sc, P);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1054,7 +1094,16 @@ template <typename T>
 __global__ __launch_bounds__(SMO_T) void smo_svc_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
     const int64_t c = Bt.live[blockIdx.x];
     smo_svc_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.ERR + c * n, SupGlobal{Bt.NZ + c * n, Bt.CF + c * n},
-                 Bt.C[c], tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
+                 BoxScalar{Bt.C[c]}, tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
+}
+
+// the same with column c's boxes in row c of CW (k x n): bq_msmo_create_weighted (Bt.C is not read)
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svc_rows_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, const double *CW,
+                                                                   double tol) {
+    const int64_t c = Bt.live[blockIdx.x];
+    smo_svc_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.ERR + c * n, SupGlobal{Bt.NZ + c * n, Bt.CF + c * n},
+                 BoxRows{CW + c * n}, tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1082,12 +1131,12 @@ __device__ __forceinline__ long long svr_pick(const SmoShared &S, double vlow, d
 }
 
 // thread 0: examine sample i2 (smo.py:677-758) and, if it violates, solve the pair (:447-600).  E2 is its error (cached,
-// or just formed).  Returns true when a pair step was taken; its data is left in S for svr_after_step.
-template <typename T>
+// or just formed), C2 its box.  Returns true when a pair step was taken; its data is left in S for svr_after_step.
+template <typename T, typename Box>
 __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, const double *y, double *ap, double *an,
-                                            double *err, double C, double eps, double tol, long long i2, double p2,
-                                            double m2, double E2) {
-    const int k2 = svr_kind(p2, m2, C);
+                                            double *err, const Box &Cb, double C2, double eps, double tol, long long i2,
+                                            double p2, double m2, double E2) {
+    const int k2 = svr_kind(p2, m2, C2);
     if (k2 != 0) {
         err[i2] = E2;
         if (k2 == 1) {
@@ -1108,9 +1157,9 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
     }
     long long i1 = -1;
     if (k2 == 0) {
-        if (p2 > 0.0 && p2 < C)
+        if (p2 > 0.0 && p2 < C2)
             i1 = svr_pick(S, E2 - eps, E2 - eps, tol);
-        else if (m2 > 0.0 && m2 < C)
+        else if (m2 > 0.0 && m2 < C2)
             i1 = svr_pick(S, E2 + eps, E2 + eps, tol);
     } else if (k2 == 1) {
         i1 = svr_pick(S, E2 + eps, E2 - eps, tol);
@@ -1123,7 +1172,7 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
         return false;
     }
     if (i1 < 0 || i1 == i2) return false;
-    const double p1o = ap[i1], m1o = an[i1];
+    const double p1o = ap[i1], m1o = an[i1], C1 = Cb(i1);   // each case below bounds variable 2 by its own box and by variable 1's
     double p1 = p1o, m1 = m1o, q2 = p2, r2 = m2;   // q2 / r2: working copies of alpha2+ / alpha2-
     const double k11 = K.at(i1, i1), k22 = K.at(i2, i2), k12 = K.at(i1, i2);
     const double eta = fmax(k11 + k22 - 2 * k12, 0.0);
@@ -1133,7 +1182,7 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
     bool moved = false, done = false;
     while (!done) {   // at most three rounds (smo.py:471)
         if (!tried[0] && (p1 > 0 || (m1 == 0 && dE > 0)) && (q2 > 0 || (r2 == 0 && dE < 0))) {
-            const double L = fmax(0.0, gamma - C), H = fmin(C, gamma);
+            const double L = fmax(0.0, gamma - C1), H = fmin(C2, gamma);
             if (L < H) {
                 const double v2 = svr_solve(L, H, q2, -dE, -dE, eta), v1 = p1 - (v2 - q2);
                 if (fabs(v1 - p1) > 1e-12 || fabs(v2 - q2) > 1e-12) {
@@ -1147,7 +1196,7 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
             tried[0] = true;
         } else if (!tried[1] && (p1 > 0 || (m1 == 0 && dE > 2 * eps)) &&
                    (r2 > 0 || (q2 == 0 && dE > 2 * eps))) {
-            const double L = fmax(0.0, -gamma), H = fmin(C, -gamma + C);
+            const double L = fmax(0.0, -gamma), H = fmin(C2, -gamma + C1);
             if (L < H) {
                 const double v2 = svr_solve(L, H, r2, dE - 2 * eps, -2 * eps + dE, eta), v1 = p1 + (v2 - r2);
                 if (fabs(v1 - p1) > 1e-12 || fabs(v2 - r2) > 1e-12) {
@@ -1161,7 +1210,7 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
             tried[1] = true;
         } else if (!tried[2] && (m1 > 0 || (p1 == 0 && dE < -2 * eps)) &&
                    (q2 > 0 || (r2 == 0 && dE < -2 * eps))) {
-            const double L = fmax(0.0, gamma), H = fmin(C, C + gamma);
+            const double L = fmax(0.0, gamma), H = fmin(C2, C1 + gamma);
             if (L < H) {
                 const double v2 = svr_solve(L, H, q2, -(dE + 2 * eps), -(2 * eps + dE), eta);
                 const double v1 = m1 + (v2 - q2);
@@ -1175,7 +1224,7 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
             }
             tried[2] = true;
         } else if (!tried[3] && (m1 > 0 || (p1 == 0 && dE < 0)) && (r2 > 0 || (q2 == 0 && dE > 0))) {
-            const double L = fmax(0.0, -gamma - C), H = fmin(C, -gamma);
+            const double L = fmax(0.0, -gamma - C1), H = fmin(C2, -gamma);
             if (L < H) {
                 const double v2 = svr_solve(L, H, r2, dE, dE, eta), v1 = m1 - (v2 - r2);
                 if (fabs(v1 - m1) > 1e-12 || fabs(v2 - r2) > 1e-12) {
@@ -1196,7 +1245,7 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
         const double c1 = (p1o - m1o) - (p1 - m1), c2 = (p2 - m2) - (q2 - r2);
         err[i1] = err[i1] + (__dmul_rn(c1, k11) + __dmul_rn(c2, k12));
         err[i2] = E2 + (__dmul_rn(c1, k12) + __dmul_rn(c2, k22));
-        const double np1 = svr_clip(p1, C), nm1 = svr_clip(m1, C), np2 = svr_clip(q2, C), nm2 = svr_clip(r2, C);
+        const double np1 = svr_clip(p1, C1), nm1 = svr_clip(m1, C1), np2 = svr_clip(q2, C2), nm2 = svr_clip(r2, C2);
         ap[i1] = np1;
         an[i1] = nm1;
         ap[i2] = np2;
@@ -1215,9 +1264,9 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
 }
 
 // all threads, after a pair step: support list, error cache of the free set, thresholds (smo.py:601-675)
-template <typename T>
+template <typename T, typename Box>
 __device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const SupGlobal &G, const KView<T> &K,
-                                               double *ap, double *an, double *err, double C, double eps,
+                                               double *ap, double *an, double *err, const Box &Cb, double eps,
                                                const SmoSpec &P) {
     const int tid = threadIdx.x;
     const long long i1 = S.i1, i2 = S.i2;
@@ -1229,8 +1278,8 @@ __device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const S
     ValIdx hi{-DBL_MAX, -1}, lo{DBL_MAX, -1};
     for (int q = tid; q < S.nnz; q += SMO_T) {
         const int64_t j = sup_idx(L, G, q);
-        const double pj = ap[j], mj = an[j];
-        const bool pin = pj > 0.0 && pj < C, nin = mj > 0.0 && mj < C;
+        const double pj = ap[j], mj = an[j], Cj = Cb(j);
+        const bool pin = pj > 0.0 && pj < Cj, nin = mj > 0.0 && mj < Cj;
         if (pin || nin) {
             double e = err[j];
             if (j != i1 && j != i2) {
@@ -1266,7 +1315,7 @@ __device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const S
         const long long pair[2] = {i1, (long long)i2};
         for (int k = 0; k < 2; ++k) {   // smo.py:654-668
             const long long i = pair[k];
-            const int ki = svr_kind(ap[i], an[i], C);
+            const int ki = svr_kind(ap[i], an[i], Cb(i));
             const double ei = err[i];
             if (ki == 0) continue;
             if (ki == 2 && ei + eps > S.b_low) {
@@ -1290,9 +1339,9 @@ __device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const S
 }
 
 // the regression walker (see smo_svc_walk)
-template <typename T>
+template <typename T, typename Box>
 __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const SmoRows &R, const double *__restrict__ y,
-                                             double *ap, double *an, double *err, const SupGlobal &G, double C, double eps,
+                                             double *ap, double *an, double *err, const SupGlobal &G, const Box Cb, double eps,
                                              double tol, bq_smo_scal *sc, const SmoSpec &P) {
     __shared__ SmoShared S;
     __shared__ SupList L;
@@ -1329,14 +1378,15 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
             }
             if (i + wv < R.m) {   // wave-uniform
                 const int64_t s = R(i + wv);
-                const double ps = ap[s], ms = an[s];
-                const bool cached = svr_kind(ps, ms, C) == 0;
+                const double ps = ap[s], ms = an[s], Cs = Cb(s);
+                const bool cached = svr_kind(ps, ms, Cs) == 0;
                 double E = 0.0;
                 if (!cached) E = y[s] - wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B);
                 if (lane == 0) {
                     S.ba[wv] = ps;
                     S.bm[wv] = ms;
                     S.bE[wv] = cached ? err[s] : E;
+                    if constexpr (Box::per_row) S.by[wv] = Cs;
                 }
             }
             __syncthreads();
@@ -1345,7 +1395,8 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
                 int used = B;
                 S.go = 0;
                 for (int w = 0; w < B; ++w) {
-                    const bool took = svr_examine(S, K, y, ap, an, err, C, eps, tol, R(i + w), S.ba[w], S.bm[w], S.bE[w]);
+                    const bool took = svr_examine(S, K, y, ap, an, err, Cb, Cb.staged(S.by, w), eps, tol, R(i + w), S.ba[w], S.bm[w],
+                                                  S.bE[w]);
                     if (took || S.fail) {
                         S.go = took ? 1 : 0;
                         used = w + 1;
@@ -1356,7 +1407,7 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
             }
             __syncthreads();
             if (S.go) {
-                svr_after_step(S, L, G, K, ap, an, err, C, eps, P);
+                svr_after_step(S, L, G, K, ap, an, err, Cb, eps, P);
                 ++changed;
                 ++steps;
             }
@@ -1372,11 +1423,11 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
                 S.stop = 1;
                 for (int q = sup_lower_bound(L, G, S.nnz, last + 1); q < S.nnz; ++q) {
                     const long long j = sup_idx(L, G, q);
-                    const double pj = ap[j], mj = an[j];
-                    if (svr_kind(pj, mj, C) == 0) {
+                    const double pj = ap[j], mj = an[j], Cj = Cb(j);
+                    if (svr_kind(pj, mj, Cj) == 0) {
                         S.stop = 0;
                         S.i2 = j;
-                        S.go = svr_examine(S, K, y, ap, an, err, C, eps, tol, j, pj, mj, err[j]) ? 1 : 0;
+                        S.go = svr_examine(S, K, y, ap, an, err, Cb, Cj, eps, tol, j, pj, mj, err[j]) ? 1 : 0;
                         break;
                     }
                 }
@@ -1384,7 +1435,7 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
             __syncthreads();
             if (S.stop) break;
             if (S.go) {
-                svr_after_step(S, L, G, K, ap, an, err, C, eps, P);
+                svr_after_step(S, L, G, K, ap, an, err, Cb, eps, P);
                 ++changed;
                 ++steps;
             }
@@ -1424,14 +1475,36 @@ __global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, c
         smo_helper(K, n, G, P);
         return;
     }
-    smo_svr_walk(K, n, SmoRows{nullptr, n}, y, ap, an, err, G, C, eps, tol, sc, P);
+    smo_svr_walk(K, n, SmoRows{nullptr, n}, y, ap, an, err, G, BoxScalar{C}, eps, tol, sc, P);
+}
+
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svr_rows_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
+                                                             double *ap, double *an, double *err, SupGlobal G,
+                                                             const double *Cw, double eps, double tol, bq_smo_scal *sc,
+                                                             SmoSpec P) {
+    if (blockIdx.x != 0) {
+        smo_helper(K, n, G, P);
+        return;
+    }
+    smo_svr_walk(K, n, SmoRows{nullptr, n}, y, ap, an, err, G, BoxRows{Cw}, eps, tol, sc, P);
 }
 
 template <typename T>
 __global__ __launch_bounds__(SMO_T) void smo_svr_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
     const int64_t c = Bt.live[blockIdx.x];
     smo_svr_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.AM + c * n, Bt.ERR + c * n,
-                 SupGlobal{Bt.NZ + c * n, Bt.CF + c * n}, Bt.C[c], Bt.eps[c], tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
+                 SupGlobal{Bt.NZ + c * n, Bt.CF + c * n}, BoxScalar{Bt.C[c]}, Bt.eps[c], tol, Bt.sc + c,
+                 SmoSpec{nullptr, nullptr, 0u, 0u, 0});
+}
+
+template <typename T>
+__global__ __launch_bounds__(SMO_T) void smo_svr_rows_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, const double *CW,
+                                                                   double tol) {
+    const int64_t c = Bt.live[blockIdx.x];
+    smo_svr_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.AM + c * n, Bt.ERR + c * n,
+                 SupGlobal{Bt.NZ + c * n, Bt.CF + c * n}, BoxRows{CW + c * n}, Bt.eps[c], tol, Bt.sc + c,
+                 SmoSpec{nullptr, nullptr, 0u, 0u, 0});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1447,12 +1520,17 @@ extern "C" int bq_smo_destroy(bq_smo *s) {
     return BQ_OK;
 }
 
-extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C, double epsilon, double tol,
-                             bq_smo **out) {
-    BQ_ARG(p && y && out, "NULL argument");
+// bq_smo_create (Cw == nullptr: the one box C) and bq_smo_create_weighted (Cw: n boxes, C is not used)
+static int smo_create(bq_problem *p, int task, const double *y, double C, const double *Cw, double epsilon, double tol,
+                      bq_smo **out) {
     BQ_ARG(task == BQ_SVC || task == BQ_SVR, "task must be BQ_SVC or BQ_SVR");
     BQ_ARG(p->kernel >= 0 && !p->streamed, "SMO needs a kernel-built problem with a resident Gram panel");
-    BQ_ARG(C > 0.0, "C must be > 0");
+    if (Cw) {
+        BQ_ARG(!p->compact, "per-row boxes need a plain f64 / f32 panel");
+        for (int64_t i = 0; i < p->n; ++i) BQ_ARG(std::isfinite(Cw[i]) && Cw[i] > 0.0, "every row's box must be finite and > 0");
+    } else {
+        BQ_ARG(C > 0.0, "C must be > 0");
+    }
     BQ_ARG(epsilon >= 0.0, "epsilon must be >= 0");
     BQ_ARG(tol > 0.0, "tol must be > 0");
     if (p->ctx->world > 1) {
@@ -1484,6 +1562,8 @@ extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C,
     if (e == hipSuccess) e = s->mem.dev(&s->nz, n);
     if (e == hipSuccess) e = s->mem.dev(&s->cf, n);
     if (e == hipSuccess) e = s->mem.dev(&s->sc, 1);
+    if (e == hipSuccess && Cw) e = s->mem.dev(&s->Cw, n);
+    if (e == hipSuccess && Cw) e = hipMemcpyAsync(s->Cw, Cw, sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
     // helper workgroups of the full sweeps: hook smo_helpers (0 = the walker alone).  Default 48: measured at n = 100 000
     // the sweeps take 455 / 357 / 344 / 355 / 365 / 380 / 433 / 479 ms with 16 / 32 / 48 / 64 / 96 / 128 / 192 / 255
     // helpers — past ~48 the extra pollers of the control line cost the walker more than the extra gather rate brings
@@ -1529,6 +1609,18 @@ extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C,
     return BQ_OK;
 }
 
+extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C, double epsilon, double tol,
+                             bq_smo **out) {
+    BQ_ARG(p && y && out, "NULL argument");
+    return smo_create(p, task, y, C, nullptr, epsilon, tol, out);
+}
+
+extern "C" int bq_smo_create_weighted(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
+                                      bq_smo **out) {
+    BQ_ARG(p && y && Cw && out, "NULL argument");
+    return smo_create(p, task, y, 0.0, Cw, epsilon, tol, out);
+}
+
 extern "C" int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, int *finished) {
     BQ_ARG(s && outer_iters && finished, "NULL argument");
     BQ_ARG(max_outer > 0, "max_outer must be > 0");
@@ -1542,7 +1634,23 @@ extern "C" int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, in
         const dim3 grid(1 + helpers);
         const SupGlobal G{s->nz, s->cf};
         const int64_t ld = p->symmetric ? 0 : p->ld;
-        if (s->task == BQ_SVC) {
+        if (s->Cw) {   // per-row boxes: plain panels only (checked at creation)
+            if (s->task == BQ_SVC) {
+                if (p->storage == BQ_F64)
+                    smo_svc_rows_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y,
+                                                                                s->a, s->err, G, s->Cw, s->tol, s->sc, P);
+                else
+                    smo_svc_rows_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y,
+                                                                              s->a, s->err, G, s->Cw, s->tol, s->sc, P);
+            } else {
+                if (p->storage == BQ_F64)
+                    smo_svr_rows_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y,
+                                                                                s->a, s->am, s->err, G, s->Cw, s->eps, s->tol, s->sc, P);
+                else
+                    smo_svr_rows_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y,
+                                                                              s->a, s->am, s->err, G, s->Cw, s->eps, s->tol, s->sc, P);
+            }
+        } else if (s->task == BQ_SVC) {
             if (p->compact)
                 smo_svc_kernel<bq_c7><<<grid, SMO_T, 0, c->stream>>>(KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, s->n, s->y,
                                                                       s->a, s->err, G, s->C, s->tol, s->sc, P);
@@ -1626,7 +1734,8 @@ struct bq_msmo {
     double tol = 1e-3;
     double *Y = nullptr, *A = nullptr, *AM = nullptr, *ERR = nullptr, *CF = nullptr;   // k x n each (AM: BQ_SVR only)
     int *NZ = nullptr;                                                                 // k x n
-    double *C = nullptr, *eps = nullptr;                                               // k
+    double *C = nullptr, *eps = nullptr;                                               // k (C: null with per-row boxes)
+    double *CW = nullptr;                                                              // k x n per-row boxes, or null
     bq_smo_scal *sc = nullptr;                                                         // k
     int *live = nullptr;                                                               // k: the columns of the next launch
     int64_t *row_ptr = nullptr;                                                        // k + 1, or null: all rows
@@ -1655,14 +1764,15 @@ extern "C" int bq_msmo_destroy(bq_msmo *s) {
     return BQ_OK;
 }
 
-extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *epsilon,
-                              double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
-    BQ_ARG(p && Y && C && out, "NULL argument");
+// bq_msmo_create (CW == nullptr: C holds one box per column) and bq_msmo_create_weighted (CW: k x n boxes, C == nullptr)
+static int msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *CW, const double *epsilon,
+                       double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
     BQ_ARG(task == BQ_SVC || task == BQ_SVR, "task must be BQ_SVC or BQ_SVR");
     BQ_ARG(k >= 1, "k must be >= 1");
     BQ_ARG(p->kernel >= 0 && !p->streamed, "SMO needs a kernel-built problem with a resident Gram panel");
     BQ_ARG(tol > 0.0, "tol must be > 0");
     BQ_ARG((row_ptr == nullptr) == (rows == nullptr), "row_ptr and rows come together");
+    BQ_ARG(CW == nullptr || !p->compact, "per-row boxes need a plain f64 / f32 panel");
     if (p->ctx->world > 1) {
         bq_set_error("SMO walks the samples sequentially over the whole panel: use a single-rank context (replicas only)");
         return BQ_ERR_BADARG;
@@ -1673,7 +1783,7 @@ extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, c
     std::vector<bq_smo_scal> host((size_t)k);
     std::vector<int64_t> first((size_t)2 * k, -1);   // BQ_SVC: the first +1 / -1 row of the column's list
     for (int col = 0; col < k; ++col) {
-        BQ_ARG(C[col] > 0.0, "C must be > 0");
+        BQ_ARG(CW != nullptr || C[col] > 0.0, "C must be > 0");
         BQ_ARG(epsilon == nullptr || epsilon[col] >= 0.0, "epsilon must be >= 0");
         const double *y = Y + (int64_t)col * n;
         const int64_t lo = row_ptr ? row_ptr[col] : 0, m = row_ptr ? row_ptr[col + 1] - lo : n;
@@ -1682,6 +1792,10 @@ extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, c
             const int64_t i = rows ? (int64_t)rows[lo + q] : q;
             BQ_ARG(i >= 0 && i < n, "a listed row lies outside the panel");
             BQ_ARG(q == 0 || rows == nullptr || i > (int64_t)rows[lo + q - 1], "a row list must be strictly ascending");
+            if (CW) {   // only the rows the column trains on: the others are never read
+                const double cw = CW[(int64_t)col * n + i];
+                BQ_ARG(std::isfinite(cw) && cw > 0.0, "the box of every row a column trains on must be finite and > 0");
+            }
             if (task == BQ_SVC) {
                 BQ_ARG(y[i] == 1.0 || y[i] == -1.0, "labels must be +1 / -1");
                 int64_t &f = first[2 * col + (y[i] == 1.0 ? 0 : 1)];
@@ -1733,12 +1847,14 @@ extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, c
     if (e == hipSuccess) e = s->mem.dev(&s->Y, kn);
     if (e == hipSuccess) e = s->mem.dev(&s->CF, kn);
     if (e == hipSuccess) e = s->mem.dev(&s->NZ, kn);
-    if (e == hipSuccess) e = s->mem.dev(&s->C, (size_t)k);
+    if (e == hipSuccess && C) e = s->mem.dev(&s->C, (size_t)k);
+    if (e == hipSuccess && CW) e = s->mem.dev(&s->CW, kn);
     e = bq_dev_zeroed(e, s->mem, &s->eps, (size_t)k, c->stream);
     if (e == hipSuccess) e = s->mem.dev(&s->sc, (size_t)k);
     if (e == hipSuccess) e = s->mem.dev(&s->live, (size_t)k);
     if (e == hipSuccess) e = hipMemcpyAsync(s->Y, Y, sizeof(double) * kn, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->C, C, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && C) e = hipMemcpyAsync(s->C, C, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && CW) e = hipMemcpyAsync(s->CW, CW, sizeof(double) * kn, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && epsilon) e = hipMemcpyAsync(s->eps, epsilon, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
     if (row_ptr) {
         const size_t total = (size_t)row_ptr[k];
@@ -1766,6 +1882,26 @@ extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, c
     return BQ_OK;
 }
 
+extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *epsilon,
+                              double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
+    BQ_ARG(p && Y && C && out, "NULL argument");
+    return msmo_create(p, task, k, Y, C, nullptr, epsilon, tol, row_ptr, rows, out);
+}
+
+extern "C" int bq_msmo_create_weighted(bq_problem *p, int task, int k, const double *Y, const double *CW, const double *epsilon,
+                                       double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
+    BQ_ARG(p && Y && CW && out, "NULL argument");
+    return msmo_create(p, task, k, Y, nullptr, CW, epsilon, tol, row_ptr, rows, out);
+}
+
+template <typename T>
+static void msmo_rows_launch(const bq_msmo *s, const KView<T> &K, const SmoBatch &Bt, int live, hipStream_t st) {
+    if (s->task == BQ_SVC)
+        smo_svc_rows_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->CW, s->tol);
+    else
+        smo_svr_rows_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->CW, s->tol);
+}
+
 template <typename T>
 static void msmo_launch(const bq_msmo *s, const KView<T> &K, const SmoBatch &Bt, int live, hipStream_t st) {
     if (s->task == BQ_SVC)
@@ -1790,7 +1926,11 @@ extern "C" int bq_msmo_run(bq_msmo *s, int64_t max_outer, int64_t *outer, int *f
         const int live = (int)s->live_host.size();
         if (live == 0) break;
         BQ_HIP(hipMemcpyAsync(s->live, s->live_host.data(), sizeof(int) * live, hipMemcpyHostToDevice, c->stream));
-        if (p->compact)
+        if (s->CW && p->storage == BQ_F64)   // per-row boxes: plain panels only (checked at creation)
+            msmo_rows_launch(s, KView<double>{(const double *)p->panel, ld}, Bt, live, c->stream);
+        else if (s->CW)
+            msmo_rows_launch(s, KView<float>{(const float *)p->panel, ld}, Bt, live, c->stream);
+        else if (p->compact)
             msmo_launch(s, KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, Bt, live, c->stream);
         else if (p->storage == BQ_F64)
             msmo_launch(s, KView<double>{(const double *)p->panel, ld}, Bt, live, c->stream);

@@ -43,7 +43,68 @@ except ImportError:  # pragma: no cover
             r = y - self.predict(X)
             return 1.0 - float(r @ r) / float(((y - y.mean()) ** 2).sum())
 
-__all__ = ['SVM', 'SVC', 'SVR']
+__all__ = ['SVM', 'SVC', 'SVR', 'row_boxes', 'has_class_weight']
+
+
+def has_class_weight(est):
+    """True when `est` carries a `class_weight`: every batched path that was not taught about per-row boxes answers False to such an
+    estimator, so that the per-column / per-fold calls of `SVC.fit` apply the weights."""
+    return getattr(est, 'class_weight', None) is not None
+
+
+def row_boxes(C, y=None, classes=None, class_weight=None, sample_weight=None):
+    """The box of every row, C_i = C * sample_weight_i * class_weight[y_i] (libsvm's and sklearn.svm's weighting), or None when
+    neither weight is given.  class_weight: None, a dict {label: weight} (a missing label weighs 1, a key outside `classes` is a
+    ValueError, weights finite and > 0) or 'balanced' = n / (n_classes * bincount(y)) over the rows given, which is
+    sklearn.utils.class_weight.compute_class_weight's formula.  sample_weight: n finite entries >= 0, not all zero.  A row whose box
+    is 0 is one `fit` drops."""
+    if class_weight is None and sample_weight is None:
+        return None
+    if sample_weight is not None:
+        sample_weight = np.asarray(sample_weight, dtype=float)
+        if sample_weight.ndim != 1 or (y is not None and len(sample_weight) != len(y)):
+            raise ValueError('sample_weight must hold one weight per row')
+        if not np.isfinite(sample_weight).all() or (sample_weight < 0).any():
+            raise ValueError('sample_weight must be finite and >= 0')
+        if not (sample_weight > 0).any():
+            raise ValueError('sample_weight must not be zero on every row')
+    if class_weight is None:
+        return C * sample_weight
+    y = np.asarray(y)
+    classes = np.asarray(classes)
+    codes = np.searchsorted(classes, y)
+    if isinstance(class_weight, str):
+        if class_weight != 'balanced':
+            raise ValueError("class_weight must be None, a dict or 'balanced'")
+        w = len(y) / (len(classes) * np.bincount(codes, minlength=len(classes)).astype(np.float64))
+    elif isinstance(class_weight, dict):
+        w = np.ones(len(classes))
+        for label, value in class_weight.items():
+            at = np.flatnonzero(classes == label)
+            if len(at) != 1:
+                raise ValueError('class_weight names the label %r, which is not among the classes %r' % (label, list(classes)))
+            if not (np.isfinite(value) and value > 0):
+                raise ValueError('class weights must be finite and > 0')
+            w[at[0]] = value
+    else:
+        raise ValueError("class_weight must be None, a dict or 'balanced'")
+    return C * w[codes] if sample_weight is None else C * sample_weight * w[codes]
+
+
+def _kept_rows(box, y, n_groups):
+    """the rows a weighted fit keeps (box > 0), or None when it keeps every row; y: the labels (None: regression)"""
+    if box is None or (box > 0).all():
+        return None
+    keep = np.flatnonzero(box > 0)
+    if y is not None and len(np.unique(y[keep])) < n_groups:
+        raise ValueError('the weights leave a class without rows')
+    return keep
+
+
+def _scattered(values, keep, n):
+    out = np.zeros(n)
+    out[keep] = values
+    return out
 
 _OUT_OF_SCOPE = ('only dual=True with a box-constrained optimizer (ProjectedGradient, FrankWolfe, ActiveSet, '
                  'InteriorPoint) or a stochastic optimizer on the augmented-Lagrangian dual is implemented by '
@@ -218,7 +279,7 @@ class SVC(ClassifierMixin, SVM):
                  intercept_scaling=1, reg_intercept=False, dual=False, optimizer=ProjectedGradient,
                  master_solver='clarabel', learning_rate='auto', momentum_type='none', momentum=0.9, max_iter=1000,
                  max_f_eval=15000, tol=1e-4, batch_size=None, shuffle=True, random_state=None, early_stopping=False,
-                 validation_split=0., patience=5, verbose=False, master_verbose=False, storage='f64'):
+                 validation_split=0., patience=5, verbose=False, master_verbose=False, storage='f64', class_weight=None):
         super(SVC, self).__init__(loss=loss, kernel=kernel, C=C, rho=rho, mu=mu, fit_intercept=fit_intercept,
                                   intercept_scaling=intercept_scaling, reg_intercept=reg_intercept, dual=dual,
                                   optimizer=optimizer, master_solver=master_solver, learning_rate=learning_rate,
@@ -229,23 +290,38 @@ class SVC(ClassifierMixin, SVM):
                                   master_verbose=master_verbose, storage=storage)
         if not getattr(loss, '_loss_type', None) == 'classifier':
             raise TypeError(f'{loss} is not an allowed SVC loss function')
+        if not (class_weight is None or isinstance(class_weight, dict) or class_weight == 'balanced'):
+            raise ValueError("class_weight must be None, a dict or 'balanced'")
+        self.class_weight = class_weight
 
-    def fit(self, X, y):
+    def fit(self, X, y, sample_weight=None):
+        """sample_weight / `class_weight`: row i's box is C_i = C * sample_weight_i * class_weight[y_i] (`row_boxes`) in the SMO
+        branch, the box-constrained branch and the augmented-Lagrangian branch of the hinge dual; rows with C_i = 0 are dropped
+        before the panel is built (`alphas_` holds 0 for them, `support_` indexes the rows given).  The squared hinge carries
+        1 / (2C) as one scalar diagonal and refuses weights."""
         y = np.asarray(y)
         self.classes_ = np.unique(y)
         if len(self.classes_) > 2:
             raise ValueError('use OneVsOneClassifier or OneVsRestClassifier from sklearn.multiclass '
                              'to train a model over more than two labels')
+        box = row_boxes(self.C, y, self.classes_, self.class_weight, sample_weight)
         # LabelBinarizer(neg_label=-1): the larger class label maps to +1 (svm/_base.py:419, 436-440)
         y = np.where(y == self.classes_[-1], 1., -1.)
         X = np.ascontiguousarray(X, dtype=float)
+        keep = _kept_rows(box, y, len(self.classes_))
+        if keep is not None:
+            X_all, y_all = X, y
+            X, y, box = np.ascontiguousarray(X[keep]), y[keep], box[keep]
+        if box is not None and self.dual and self.loss == SquaredHinge:
+            raise NotImplementedError('class_weight / sample_weight are not implemented for the squared hinge: its dual carries '
+                                      '1 / (2C) as one scalar diagonal, not a box per row')
         n = len(y)
         if self._is_smo():
             if self.loss != Hinge or self.reg_intercept:
                 raise NotImplementedError('SMO solves the hinge dual with an unregularised intercept')   # :571-573
             obj = KernelQuadratic(X, -np.ones(n), 'svc', self.kernel, y=y, storage=self.storage, rank_one=False, compact=False)
             self.obj = obj
-            self.optimizer = SMOClassifier(obj, X, y, None, self.kernel, self.C, self.tol, self.verbose).minimize()
+            self.optimizer = SMOClassifier(obj, X, y, None, self.kernel, self.C, self.tol, self.verbose, box).minimize()
             self.alphas_ = self.optimizer.alphas
         elif self._is_stochastic():
             if self.loss not in (Hinge, SquaredHinge):
@@ -254,7 +330,8 @@ class SVC(ClassifierMixin, SVM):
             obj = KernelQuadratic(X, -np.ones(n), 'svc', self.kernel, y=y, storage=self.storage,
                                   diag=1. / (2 * self.C) if sq else 0., rank_one=self.reg_intercept,
                                   tune_placement=self._streams_panel(), expected_products=self.max_iter)
-            self._run_lagrangian(obj, None if self.reg_intercept else y, None if sq else np.ones(n) * self.C)
+            self._run_lagrangian(obj, None if self.reg_intercept else y,
+                                 None if sq else np.ones(n) * self.C if box is None else box)
         else:
             self._check_bcqp()
             if self.loss == SquaredHinge:
@@ -264,8 +341,11 @@ class SVC(ClassifierMixin, SVM):
                 raise TypeError(f'{self.loss} is not an allowed loss')
             obj = KernelQuadratic(X, -np.ones(n), 'svc', self.kernel, y=y, storage=self.storage,
                                   tune_placement=self._streams_panel(), expected_products=self.max_iter)
-            self._run(obj, np.ones(n) * self.C)
+            self._run(obj, np.ones(n) * self.C if box is None else box)
 
+        if keep is not None:   # back to the rows given: the dropped ones hold 0
+            self.alphas_ = _scattered(self.alphas_, keep, len(y_all))
+            X, y = X_all, y_all
         sv = self.alphas_ > 1e-6
         self.support_ = np.arange(len(self.alphas_))[sv]
         self.support_vectors_, sv_y, alphas = X[sv], y[sv], self.alphas_[sv]
@@ -277,7 +357,7 @@ class SVC(ClassifierMixin, SVM):
             return self
         if isinstance(self.kernel, LinearKernel):
             self.coef_ = np.dot(self.dual_coef_, self.support_vectors_)
-        self.intercept_ += self._intercept_sum(obj, sv, self.dual_coef_, sv_y)
+        self.intercept_ += self._intercept_sum(obj, sv if keep is None else sv[keep], self.dual_coef_, sv_y)
         self.intercept_ /= len(alphas)
         return self
 
@@ -307,13 +387,23 @@ class SVR(RegressorMixin, SVM):
             raise ValueError('epsilon must be >= 0')
         self.epsilon = epsilon
 
-    def fit(self, X, y):
+    def fit(self, X, y, sample_weight=None):
+        """sample_weight: row i's box is C_i = C * sample_weight_i on both of its multipliers (`row_boxes`), as `SVC.fit` applies it;
+        the squared epsilon-insensitive loss refuses weights."""
         y = np.asarray(y, dtype=float)
         targets = y.shape[1] if y.ndim > 1 else 1
         if targets > 1:
             raise ValueError('use sklearn.multioutput.MultiOutputRegressor '
                              'to train a model over more than one target')
         X = np.ascontiguousarray(X, dtype=float)
+        box = row_boxes(self.C, y, sample_weight=sample_weight)
+        keep = _kept_rows(box, None, 0)
+        if keep is not None:
+            X_all, y_all = X, y
+            X, y, box = np.ascontiguousarray(X[keep]), y[keep], box[keep]
+        if box is not None and self.dual and self.loss == SquaredEpsilonInsensitive:
+            raise NotImplementedError('sample_weight is not implemented for the squared epsilon-insensitive loss: its dual carries '
+                                      '1 / (2C) as one scalar diagonal, not a box per row')
         n = len(y)
         q = np.hstack((-y, y)) + self.epsilon
         if self._is_smo():
@@ -321,8 +411,8 @@ class SVR(RegressorMixin, SVM):
                 raise NotImplementedError('SMO solves the epsilon-insensitive dual with an unregularised intercept')
             obj = KernelQuadratic(X, q, 'svr', self.kernel, storage=self.storage, rank_one=False, compact=False)
             self.obj = obj
-            self.optimizer = SMORegression(obj, X, y, None, self.kernel, self.C, self.epsilon, self.tol,
-                                           self.verbose).minimize()
+            self.optimizer = SMORegression(obj, X, y, None, self.kernel, self.C, self.epsilon, self.tol, self.verbose,
+                                           box).minimize()
             self.alphas_ = np.concatenate((self.optimizer.alphas_p, self.optimizer.alphas_n))
         elif self._is_stochastic():
             if self.loss not in (EpsilonInsensitive, SquaredEpsilonInsensitive):
@@ -332,7 +422,8 @@ class SVR(RegressorMixin, SVM):
                                   diag=1. / (2 * self.C) if sq else 0., rank_one=self.reg_intercept,
                                   tune_placement=self._streams_panel(), expected_products=self.max_iter)
             e = np.hstack((np.ones(n), -np.ones(n)))   # equality row
-            self._run_lagrangian(obj, None if self.reg_intercept else e, None if sq else np.ones(2 * n) * self.C)
+            self._run_lagrangian(obj, None if self.reg_intercept else e,
+                                 None if sq else np.ones(2 * n) * self.C if box is None else np.hstack((box, box)))
         else:
             self._check_bcqp()
             if self.loss == SquaredEpsilonInsensitive:
@@ -342,8 +433,11 @@ class SVR(RegressorMixin, SVM):
             if self.loss != EpsilonInsensitive:
                 raise TypeError(f'{self.loss} is not an allowed loss')
             obj = KernelQuadratic(X, q, 'svr', self.kernel, storage=self.storage, tune_placement=self._streams_panel(), expected_products=self.max_iter)
-            self._run(obj, np.ones(2 * n) * self.C)
+            self._run(obj, np.ones(2 * n) * self.C if box is None else np.hstack((box, box)))
 
+        if keep is not None:   # back to the rows given: the dropped ones hold 0
+            self.alphas_ = np.concatenate([_scattered(half, keep, len(y_all)) for half in np.split(self.alphas_, 2)])
+            X, y = X_all, y_all
         alphas_p, alphas_n = np.split(self.alphas_, 2)
         sv = np.logical_or(alphas_p > 1e-6, alphas_n > 1e-6)
         self.support_ = np.arange(len(alphas_p))[sv]
@@ -356,7 +450,7 @@ class SVR(RegressorMixin, SVM):
             return self
         if isinstance(self.kernel, LinearKernel):
             self.coef_ = np.dot(self.dual_coef_, self.support_vectors_)
-        self.intercept_ += self._intercept_sum(obj, sv, self.dual_coef_, sv_y)
+        self.intercept_ += self._intercept_sum(obj, sv if keep is None else sv[keep], self.dual_coef_, sv_y)
         self.intercept_ -= self.epsilon   # subtracted once before the division, as svm/_base.py:1436-1437
         self.intercept_ /= len(alphas_p)
         return self

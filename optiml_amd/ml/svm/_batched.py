@@ -17,7 +17,7 @@ from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import ProjectedGradient
 from ...opti.unconstrained.stochastic import StochasticOptimizer, StochasticMomentumOptimizer
-from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator, ConvergenceWarning
+from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator, ConvergenceWarning, has_class_weight
 from .kernels import GaussianKernel, LinearKernel, PolyKernel, SigmoidKernel, gaussian
 from .losses import squared_hinge, squared_epsilon_insensitive
 from .smo import SMOClassifier, SMORegression
@@ -60,17 +60,18 @@ def device_panel(*args, **kwargs):
         obj.release()
 
 
-def smo_column_bytes(n, task):
+def smo_column_bytes(n, task, weighted=False):
     """Device state of one batched-SMO column on n rows (`bq_msmo_create`): labels or targets, multipliers (two vectors for
-    regression), error cache, the support list's coefficients (8 n each) and its indices (4 n)."""
-    return (36 if task == _lib.SVC else 44) * int(n)
+    regression), error cache, the support list's coefficients (8 n each) and its indices (4 n); `weighted`
+    (`bq_msmo_create_weighted`): its boxes too (8 n)."""
+    return ((36 if task == _lib.SVC else 44) + (8 if weighted else 0)) * int(n)
 
 
-def smo_column_cap(n, task, free_bytes):
+def smo_column_cap(n, task, free_bytes, weighted=False):
     """Columns one batched SMO solve may take with `free_bytes` of device memory free after the panel: MEMORY_SHARE of it over
     `smo_column_bytes`; at most MAX_COLUMNS, at least 1.  Larger sets run in several solves; columns are independent, so the
     split changes no bits."""
-    return int(max(1, min(MAX_COLUMNS, int(free_bytes * MEMORY_SHARE) // smo_column_bytes(n, task))))
+    return int(max(1, min(MAX_COLUMNS, int(free_bytes * MEMORY_SHARE) // smo_column_bytes(n, task, weighted))))
 
 
 def smo_heldout_column_cap(n, task, free_bytes, wide_slab_bytes, calibrators=False):
@@ -107,9 +108,10 @@ def takes_batched_smo(k, force=None):
 class _DeviceSMOSolver:
     """`bq_msmo_create`: k SMO columns on one kernel problem, one walker workgroup each.  task: `_lib.SVC` (Y: k x n labels +-1) or
     `_lib.SVR` (Y: k x n targets); C: k; epsilon: k or None (0); rows: None (every column trains on all rows) or k ascending
-    arrays of panel rows."""
+    arrays of panel rows; boxes: None, or k x n boxes per column and row (`bq_msmo_create_weighted`; C is not read then, and the
+    entries on rows outside a column's list are not either)."""
 
-    def __init__(self, problem, task, Y, C_, epsilon, tol, rows=None):
+    def __init__(self, problem, task, Y, C_, epsilon, tol, rows=None, boxes=None):
         self._lib = _lib.load()
         Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=float)
         self.k, self.n = Y.shape
@@ -125,10 +127,15 @@ class _DeviceSMOSolver:
             row_ptr = np.zeros(self.k + 1, dtype=np.int64)
             row_ptr[1:] = np.cumsum([len(r) for r in rows])
             flat = _lib.as_i32(np.concatenate([np.asarray(r, dtype=np.int64) for r in rows]))
-        _lib.check(self._lib.bq_msmo_create(problem.handle, task, self.k, _lib.ptr(Y), _lib.ptr(C_), _lib.ptr(eps), float(tol),
-                                            None if row_ptr is None else row_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            None if flat is None else flat.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            C.byref(self._h)))
+        lists = (None if row_ptr is None else row_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                 None if flat is None else flat.ctypes.data_as(C.POINTER(C.c_int32)))
+        if boxes is None:
+            _lib.check(self._lib.bq_msmo_create(problem.handle, task, self.k, _lib.ptr(Y), _lib.ptr(C_), _lib.ptr(eps), float(tol),
+                                                *lists, C.byref(self._h)))
+        else:
+            boxes = _lib.as_f64(boxes, self.k * self.n, 'boxes')
+            _lib.check(self._lib.bq_msmo_create_weighted(problem.handle, task, self.k, _lib.ptr(Y), _lib.ptr(boxes), _lib.ptr(eps),
+                                                         float(tol), *lists, C.byref(self._h)))
 
     def run(self, max_outer):
         """at most max_outer launches; (outer, finished, failed), k entries each"""
@@ -242,20 +249,21 @@ def smo_column_result(solver, c, outer):
     return r
 
 
-def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, chunk=64):
+def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, chunk=64, boxes=None):
     """Run k SMO columns to the end, `cap` columns per solve at most (default: `smo_column_cap` of the memory free now): per column a
     dict of what `SMO.minimize` leaves — alphas (classification) or alphas_p / alphas_n (regression), b, errors, b_up, b_low,
-    b_up_idx, b_low_idx, iter, steps.  A column that fails raises what the single fit raises."""
+    b_up_idx, b_low_idx, iter, steps.  A column that fails raises what the single fit raises.  boxes: None, or k x n boxes per
+    column and row instead of C_ (`_DeviceSMOSolver`)."""
     Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=float)
     k, n = Y.shape
     C_ = np.broadcast_to(np.asarray(C_, dtype=float), (k,))
     epsilon = None if epsilon is None else np.broadcast_to(np.asarray(epsilon, dtype=float), (k,))
-    cap = smo_column_cap(n, task, device_free_bytes()) if cap is None else int(cap)
+    cap = smo_column_cap(n, task, device_free_bytes(), boxes is not None) if cap is None else int(cap)
     out = []
     for c0 in range(0, k, cap):
         sl = slice(c0, min(k, c0 + cap))
         solver = _DeviceSMOSolver(problem, task, Y[sl], C_[sl], None if epsilon is None else epsilon[sl], tol,
-                                  None if rows is None else rows[sl])
+                                  None if rows is None else rows[sl], None if boxes is None else boxes[sl])
         try:
             outer, failed = run_batched_smo(solver, chunk)
             if failed.any():   # bq_smo_run's error for that column
@@ -266,11 +274,11 @@ def solve_batched_smo(problem, task, Y, C_, epsilon, tol, rows=None, cap=None, c
     return out
 
 
-def smo_optimizer(quad, X, y, kernel, C_, tol, r, epsilon=None, verbose=False):
+def smo_optimizer(quad, X, y, kernel, C_, tol, r, epsilon=None, verbose=False, box=None):
     """The `SMOClassifier` (epsilon None) / `SMORegression` that `minimize()` on `quad` leaves, from its column's result `r` of
-    `solve_batched_smo` — constructed, not run."""
-    opt = SMOClassifier(quad, X, y, None, kernel, C_, tol, verbose) if epsilon is None else \
-        SMORegression(quad, X, y, None, kernel, C_, epsilon, tol, verbose)
+    `solve_batched_smo` — constructed, not run.  box: the column's boxes on the rows of X, or None."""
+    opt = SMOClassifier(quad, X, y, None, kernel, C_, tol, verbose, box) if epsilon is None else \
+        SMORegression(quad, X, y, None, kernel, C_, epsilon, tol, verbose, box)
     for name, value in r.items():
         setattr(opt, name, value)
     opt.helper_stats = {'helpers': 0, 'delivered': 0, 'rejected_list_hash': 0, 'rejected_checksum': 0}
@@ -279,11 +287,12 @@ def smo_optimizer(quad, X, y, kernel, C_, tol, r, epsilon=None, verbose=False):
     return opt
 
 
-def fitted_smo_svc(est, quad, r, X, y):
+def fitted_smo_svc(est, quad, r, X, y, box=None):
     """Make `est`, a fresh SVC of the configuration, the SVC that SVC.fit's SMO branch on (X, y: +-1) leaves, intercept included,
-    from its column's result `r` of `solve_batched_smo`; quad: the class's view of the shared panel.  Returns the support mask."""
+    from its column's result `r` of `solve_batched_smo`; quad: the class's view of the shared panel; box: the boxes `est`'s
+    `class_weight` gives the rows of X, or None.  Returns the support mask."""
     est.obj = quad
-    est.optimizer = smo_optimizer(quad, X, y, est.kernel, est.C, est.tol, r, verbose=est.verbose)
+    est.optimizer = smo_optimizer(quad, X, y, est.kernel, est.C, est.tol, r, verbose=est.verbose, box=box)
     sv = _svc_attributes(est, X, y, est.optimizer.alphas)
     if isinstance(est.kernel, LinearKernel):
         est.coef_ = est.optimizer.w
@@ -302,10 +311,13 @@ def fitted_smo_svr(est, quad, r, X, y):
     return sv
 
 
-def uses_batched_smo(est, loss, world):
+def uses_batched_smo(est, loss, world, weighted=False):
     """What `uses_batched_smo_path` (multiclass.py) and `uses_batched_smo_svr_path` (multioutput.py) share: `est`'s configuration
     takes the SMO branch of its `fit` (dual, optimizer 'smo' or `SMO`, the loss `loss`, an unregularised intercept) on a resident
-    panel ('f64' / 'f32') in a single-rank context (`world` ranks)."""
+    panel ('f64' / 'f32') in a single-rank context (`world` ranks).  An estimator with a `class_weight` only where the caller
+    hands its columns their boxes (`weighted`)."""
+    if has_class_weight(est) and not weighted:
+        return False
     return bool(est._is_smo() and est.loss == loss and not est.reg_intercept and est.storage in ('f64', 'f32') and int(world) == 1)
 
 
@@ -651,14 +663,15 @@ def uses_batched_lagrangian(est, losses, world, ndim=None):
     configuration takes the augmented-Lagrangian branch of its `fit` (dual, a `StochasticOptimizer`, a loss of `losses`) in the form
     `bq_msolver_create_al` batches: momentum 'none' or 'polyak' and constant (Nesterov momentum and schedules run one fit per
     column), a resident panel ('f64' / 'f32'), a single-rank context (`world` ranks) and, where the dual's size `ndim` is given,
-    more than 3 variables (with <= 3 the optimizer keeps per-iteration x histories and runs step by step)."""
+    more than 3 variables (with <= 3 the optimizer keeps per-iteration x histories and runs step by step).  An estimator with a
+    `class_weight` fits per column: the batched solver shares one box among its columns."""
     opt = est.optimizer
     if not (est.dual and isinstance(opt, type) and issubclass(opt, StochasticOptimizer)):
         return False
     if issubclass(opt, StochasticMomentumOptimizer) and isinstance(est.momentum, Iterable):
         return False
     return bool(est.momentum_type in ('none', 'polyak') and est.loss in losses and est.storage in ('f64', 'f32') and
-                int(world) == 1 and (ndim is None or int(ndim) > 3))
+                int(world) == 1 and (ndim is None or int(ndim) > 3) and not has_class_weight(est))
 
 
 def solve_batched(problem, kind, Y, ub, eps=1e-6, max_iter=1000, t=0.0, x0=None, chunk=256, solver=None, before_close=None,
@@ -936,14 +949,14 @@ class _MultiClassSVC(ClassifierMixin, BaseEstimator):
                  reg_intercept=False, dual=False, optimizer=ProjectedGradient, master_solver='clarabel', learning_rate='auto',
                  momentum_type='none', momentum=0.9, max_iter=1000, max_f_eval=15000, tol=1e-4, batch_size=None, shuffle=True,
                  random_state=None, early_stopping=False, validation_split=0., patience=5, verbose=False, master_verbose=False,
-                 storage='f64'):
+                 storage='f64', class_weight=None):
         self._kw = dict(loss=loss, kernel=kernel, C=C, rho=rho, mu=mu, fit_intercept=fit_intercept,
                         intercept_scaling=intercept_scaling, reg_intercept=reg_intercept, dual=dual, optimizer=optimizer,
                         master_solver=master_solver, learning_rate=learning_rate, momentum_type=momentum_type,
                         momentum=momentum, max_iter=max_iter, max_f_eval=max_f_eval, tol=tol, batch_size=batch_size,
                         shuffle=shuffle, random_state=random_state, early_stopping=early_stopping,
                         validation_split=validation_split, patience=patience, verbose=verbose,
-                        master_verbose=master_verbose, storage=storage)
+                        master_verbose=master_verbose, storage=storage, class_weight=class_weight)
         SVC(**self._kw)   # SVC's checks, SVC's exceptions
         for name, value in self._kw.items():
             setattr(self, name, value)

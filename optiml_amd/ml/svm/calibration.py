@@ -26,7 +26,7 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ._base import SVC, ClassifierMixin, ConvergenceWarning
+from ._base import SVC, ClassifierMixin, ConvergenceWarning, has_class_weight
 from ._batched import (ClassQuadratic, DecisionBatch, _DeviceSMOSolver, device_free_bytes, fitted_smo_svc, fitted_svc, platt_fit,
                        run_batched_smo, smo_column_result, smo_failed_error, smo_heldout_column_cap, solve_batched,
                        solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision)
@@ -49,7 +49,7 @@ def uses_batched_calibration(estimator, world):
     if not isinstance(estimator, (SVC, OneVsRestSVC)):
         return False
     proto = _prototype(estimator)
-    return bool(uses_batched_path(proto, world) and proto.storage == 'f64' and
+    return bool(not has_class_weight(proto) and uses_batched_path(proto, world) and proto.storage == 'f64' and
                 not isinstance(getattr(proto.kernel, 'gamma', None), str))
 
 
@@ -60,7 +60,7 @@ def uses_batched_smo_calibration(estimator, world):
     if not isinstance(estimator, (SVC, OneVsRestSVC)):
         return False
     proto = _prototype(estimator)
-    return bool(uses_batched_smo_path(proto, world) and proto.storage == 'f64' and
+    return bool(not has_class_weight(proto) and uses_batched_smo_path(proto, world) and proto.storage == 'f64' and
                 not isinstance(getattr(proto.kernel, 'gamma', None), str))
 
 

@@ -28,7 +28,7 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ._base import ClassifierMixin, ConvergenceWarning
+from ._base import ClassifierMixin, ConvergenceWarning, has_class_weight
 from ._batched import DecisionBatch, device_free_bytes, fitted_svc, platt_fit, solve_batched, solver_kind, uses_batched_decision
 from .kernels import BaseEstimator
 from .model_selection import _base_params, _make, check_cv_splits
@@ -46,7 +46,7 @@ def uses_batched_coupling(estimator, world):
     if not isinstance(estimator, OneVsOneSVC):
         return False
     proto = estimator._prototype()
-    return bool(uses_batched_ovo(proto, world) and proto.storage == 'f64' and
+    return bool(not has_class_weight(proto) and uses_batched_ovo(proto, world) and proto.storage == 'f64' and
                 not isinstance(getattr(proto.kernel, 'gamma', None), str))
 
 

@@ -29,7 +29,7 @@ import numpy as np
 
 from ... import _lib
 from ...device import get_context
-from ._base import SVC, SVR
+from ._base import SVC, SVR, has_class_weight
 from ._batched import (MAX_COLUMNS, MEMORY_SHARE, _DeviceSMOSolver, _DeviceSVRSolver, _gram_matmat, column_cap,  # noqa: F401
                        device_panel, fitted_svr, intercept, run_batched_smo, smo_column_cap, smo_failed_error,
                        smo_heldout_column_cap, solve_batched, solve_batched_smo, solver_kind, svr_intercept, takes_batched_smo)
@@ -97,7 +97,8 @@ def uses_batched_search(estimator, candidates, world):
         return False
     if any(not set(p) <= BATCHED_KEYS for p in candidates):
         return False
-    return uses_batched_path(_prototype(estimator), world)
+    proto = _prototype(estimator)
+    return bool(not has_class_weight(proto) and uses_batched_path(proto, world))
 
 
 def _resolved_kernel(kernel, Xfit):
@@ -176,7 +177,8 @@ def uses_batched_smo_search(estimator, candidates, world):
         return False
     if any(not set(p) <= BATCHED_KEYS for p in candidates):
         return False
-    return uses_batched_smo_path(_prototype(estimator), world)
+    proto = _prototype(estimator)
+    return bool(not has_class_weight(proto) and uses_batched_smo_path(proto, world))   # the search's columns carry one C each
 
 
 def plan_smo_columns(X, y, splits, candidates, base_C, base_kernel, multiclass):
@@ -488,7 +490,7 @@ def uses_batched_svr_search(estimator, candidates, world):
         return False
     if any(not set(p) <= SVR_BATCHED_KEYS for p in candidates):
         return False
-    return uses_batched_svr_path(estimator, world)
+    return bool(not has_class_weight(estimator) and uses_batched_svr_path(estimator, world))
 
 
 def plan_svr_columns(X, y, splits, candidates, base_C, base_epsilon, base_kernel):
@@ -527,7 +529,7 @@ def uses_batched_smo_svr_search(estimator, candidates, world):
     kernels = [estimator.kernel] + [p['kernel'] for p in candidates if 'kernel' in p]
     if any(isinstance(getattr(k, 'gamma', None), str) for k in kernels):
         return False
-    return bool(uses_batched_smo_svr_path(estimator, world) and estimator.storage == 'f64')
+    return bool(not has_class_weight(estimator) and uses_batched_smo_svr_path(estimator, world) and estimator.storage == 'f64')
 
 
 def plan_smo_svr_columns(X, y, splits, candidates, base_C, base_epsilon, base_kernel):

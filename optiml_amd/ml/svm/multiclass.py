@@ -24,6 +24,7 @@ from ._batched import (ClassQuadratic, DecisionBatch, _DeviceALSolver, _DeviceMu
                        _svc_attributes, fitted_lagrangian, fitted_smo_svc, fitted_svc, intercept, lagrangian_columns,
                        solve_batched, solve_batched_al, solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision,
                        uses_batched_lagrangian, uses_batched_smo)
+from ._base import has_class_weight, row_boxes
 from .losses import Hinge, SquaredHinge
 
 __all__ = ['OneVsRestSVC', 'uses_batched_path', 'uses_batched_lagrangian_path', 'uses_batched_smo_path', 'binarize']
@@ -32,9 +33,10 @@ __all__ = ['OneVsRestSVC', 'uses_batched_path', 'uses_batched_lagrangian_path', 
 def uses_batched_path(svc, world):
     """True when `OneVsRestSVC` solves the classes of `svc`'s configuration together on one panel: the hinge dual with a regularised
     intercept by ProjectedGradient or FrankWolfe, a resident panel ('f64' / 'f32') and a single-rank context (`world` ranks).
-    Every other configuration fits one `SVC` per class."""
+    Every other configuration, and every one with a `class_weight` (the batched solver's columns share one box), fits one `SVC`
+    per class."""
     opt = svc.optimizer
-    return bool(svc.dual and svc.reg_intercept and svc.loss == Hinge and isinstance(opt, type) and
+    return bool(not has_class_weight(svc) and svc.dual and svc.reg_intercept and svc.loss == Hinge and isinstance(opt, type) and
                 issubclass(opt, (ProjectedGradient, FrankWolfe)) and svc.storage in ('f64', 'f32') and int(world) == 1)
 
 
@@ -50,8 +52,9 @@ def uses_batched_smo_path(svc, world):
     """True when `OneVsRestSVC` can solve the classes of `svc`'s configuration together by the batched SMO solver (`bq_msmo_*`, one
     walker workgroup per class on one panel): `dual`, optimizer 'smo' or `SMO`, the hinge loss, `reg_intercept=False`, a resident
     panel ('f64' / 'f32') and a single-rank context (`world` ranks).  Whether a fit then does is a matter of speed alone
-    (`takes_batched_smo`): both ways give the same bits."""
-    return uses_batched_smo(svc, Hinge, world)
+    (`takes_batched_smo`): both ways give the same bits.  A `class_weight` stays on this path: every class's column gets the boxes
+    of its own binary problem (`bq_msmo_create_weighted`)."""
+    return uses_batched_smo(svc, Hinge, world, weighted=True)
 
 
 def binarize(y):
@@ -86,6 +89,9 @@ class OneVsRestSVC(_MultiClassSVC):
         X = np.ascontiguousarray(X, dtype=float)
         self.classes_, Y = binarize(y)
         proto = self._prototype()
+        if isinstance(proto.class_weight, dict):
+            # every class is fitted on the labels 0 / 1 of its own binary problem: a dict's keys, the data's labels, name none of them
+            raise ValueError("OneVsRestSVC takes class_weight=None or 'balanced': the binary problems' labels are not the data's")
         self.lagrangian_ = uses_batched_lagrangian_path(proto, get_context().world, X.shape[0])
         self.smo_ = uses_batched_smo_path(proto, get_context().world) and takes_batched_smo(len(Y), self.batch_smo)
         self.batched_ = self.lagrangian_ or self.smo_ or uses_batched_path(proto, get_context().world)
@@ -103,11 +109,15 @@ class OneVsRestSVC(_MultiClassSVC):
         solve; the intercepts are the solver's."""
         k, n = Y.shape
         obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Y[0], storage=proto.storage, rank_one=False, compact=False)
-        res = solve_batched_smo(obj.device_problem(), _lib.SVC, Y, proto.C, None, proto.tol)
+        # class_weight='balanced': column c's boxes are those SVC.fit gives the 0 / 1 labels of class c's binary problem
+        boxes = None
+        if has_class_weight(proto):
+            boxes = np.stack([row_boxes(proto.C, (Yc > 0).astype(int), np.arange(2), proto.class_weight) for Yc in Y])
+        res = solve_batched_smo(obj.device_problem(), _lib.SVC, Y, proto.C, None, proto.tol, boxes=boxes)
         ests = [self._prototype() for _ in range(k)]
         coefs = []
         for c, est in enumerate(ests):
-            sv = fitted_smo_svc(est, ClassQuadratic(obj, Y[c]), res[c], X, Y[c])
+            sv = fitted_smo_svc(est, ClassQuadratic(obj, Y[c]), res[c], X, Y[c], None if boxes is None else boxes[c])
             w = np.zeros(n)
             w[sv] = est.dual_coef_
             coefs.append(w)

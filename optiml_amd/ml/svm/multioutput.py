@@ -20,6 +20,7 @@ from ...device import get_context
 from ...opti import KernelQuadratic
 from ...opti.constrained import FrankWolfe, ProjectedGradient
 from ... import _lib
+from ._base import has_class_weight
 from ._batched import (DecisionBatch, TargetQuadratic, _DeviceALSolver, _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat,
                        _svr_attributes, fitted_lagrangian, fitted_smo_svr, fitted_svr, lagrangian_columns, solve_batched,
                        solve_batched_al, solve_batched_smo, solver_kind, svr_intercept, takes_batched_smo, uses_batched_decision,
@@ -34,7 +35,7 @@ def uses_batched_svr_path(svr, world):
     with a regularised intercept by ProjectedGradient or FrankWolfe, a resident panel ('f64' / 'f32') and a single-rank context
     (`world` ranks).  Every other configuration fits one `SVR` per target."""
     opt = svr.optimizer
-    return bool(svr.dual and svr.reg_intercept and svr.loss == EpsilonInsensitive and isinstance(opt, type) and
+    return bool(not has_class_weight(svr) and svr.dual and svr.reg_intercept and svr.loss == EpsilonInsensitive and isinstance(opt, type) and
                 issubclass(opt, (ProjectedGradient, FrankWolfe)) and svr.storage in ('f64', 'f32') and int(world) == 1)
 
 

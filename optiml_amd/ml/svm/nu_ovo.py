@@ -19,7 +19,7 @@ import numpy as np
 
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ._base import ClassifierMixin
+from ._base import ClassifierMixin, has_class_weight
 from ._batched import (MEMORY_SHARE, DecisionBatch, _DeviceSimplexPairSolver, device_free_bytes, solve_batched,
                        uses_batched_decision)
 from .kernels import BaseEstimator, LinearKernel, gaussian
@@ -34,7 +34,7 @@ def uses_batched_ovo_nu(est, world):
     """True when `OneVsOneNuSVC` solves the pairs of `est`'s configuration together on one panel: a resident panel on a single-rank
     context (anything else is refused by `fit`) and a kernel whose parameters do not depend on the rows (numeric gamma,
     gamma='auto' or a linear kernel)."""
-    if est.storage not in ('f64', 'f32') or int(world) != 1:
+    if has_class_weight(est) or est.storage not in ('f64', 'f32') or int(world) != 1:
         return False
     return isinstance(est.kernel, LinearKernel) or getattr(est.kernel, 'gamma', None) != 'scale'
 

@@ -29,7 +29,7 @@ import warnings
 import numpy as np
 
 from ...device import get_context
-from ._base import ConvergenceWarning
+from ._base import ConvergenceWarning, has_class_weight
 from ._batched import _DeviceSimplex2Solver, column_cap, device_panel, solve_batched
 from .model_selection import _GridSearchCV, _group_of, _make, _stacked, r2_from_sse
 from .nu import NuSVC, NuSVR, _check_feasible
@@ -43,6 +43,8 @@ NU_SVR_BATCHED_KEYS = frozenset({'C', 'nu', 'kernel'})
 def uses_batched_nu_search(estimator, candidates):
     """True when the search solves every (candidate, fold) on shared panels: the estimator is a `NuSVC` and the grid varies only nu
     and kernel, or a `NuSVR` and the grid varies only C, nu and kernel."""
+    if has_class_weight(estimator):   # the nu duals carry no per-row boxes
+        return False
     if isinstance(estimator, NuSVC):
         keys = NU_SVC_BATCHED_KEYS
     elif isinstance(estimator, NuSVR):

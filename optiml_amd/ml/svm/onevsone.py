@@ -40,6 +40,7 @@ from ...opti import KernelQuadratic
 from ._batched import (MEMORY_SHARE, DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _pair_array, column_bytes,
                        device_free_bytes, fitted_smo_svc, fitted_svc, gram_matmat_pairs, intercept, solve_batched,
                        solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision)
+from ._base import has_class_weight, row_boxes
 from .kernels import LinearKernel
 from .multiclass import uses_batched_path, uses_batched_smo_path
 
@@ -59,7 +60,8 @@ def uses_batched_ovo(svc, world):
 def uses_batched_ovo_smo(svc, world):
     """True when `OneVsOneSVC` can solve the pairs of `svc`'s configuration as row-list columns of the batched SMO solver on one
     unsorted panel: `uses_batched_smo_path` holds and the kernel's parameters do not depend on the rows (numeric gamma,
-    gamma='auto' or a linear kernel).  Whether a fit then does is `takes_batched_smo`'s answer (`OneVsOneSVC.batch_smo`)."""
+    gamma='auto' or a linear kernel).  Whether a fit then does is `takes_batched_smo`'s answer (`OneVsOneSVC.batch_smo`).  A
+    `class_weight` stays on this path: every pair's column gets the boxes of the pair's own fit."""
     if not uses_batched_smo_path(svc, world):
         return False
     return isinstance(svc.kernel, LinearKernel) or getattr(svc.kernel, 'gamma', None) != 'scale'
@@ -181,6 +183,10 @@ class OneVsOneSVC(_MultiClassSVC):
             raise ValueError('OneVsOneSVC can not be fit when only one class is present.')
         codes = np.searchsorted(self.classes_, y)
         proto = self._prototype()
+        if isinstance(proto.class_weight, dict):
+            for label in proto.class_weight:
+                if not (self.classes_ == label).any():
+                    raise ValueError('class_weight names the label %r, which is not among the classes %r' % (label, list(self.classes_)))
         ncls = len(self.classes_)
         P = ncls * (ncls - 1) // 2
         self.smo_ = uses_batched_ovo_smo(proto, get_context().world) and takes_batched_smo(P, self.batch_smo)
@@ -191,10 +197,18 @@ class OneVsOneSVC(_MultiClassSVC):
             self.estimators_ = []
             for i, j in ovo_pairs(len(self.classes_)):
                 rows, yp = pair_problem(codes, i, j)
-                self.estimators_.append(self._prototype().fit(X[rows], (yp > 0).astype(int)))
+                self.estimators_.append(self._pair_prototype(i, j).fit(X[rows], (yp > 0).astype(int)))
             return self
         self.estimators_ = (self._fit_smo if self.smo_ else self._fit_batched)(proto, X, codes)
         return self
+
+    def _pair_prototype(self, i, j):
+        """The SVC of pair (i, j), fitted on the labels 0 (class i) / 1 (class j): a `class_weight` dict, whose keys are the data's
+        labels, is handed over as the two weights under those labels; 'balanced' resolves on the pair's rows in `SVC.fit`."""
+        est = self._prototype()
+        if isinstance(est.class_weight, dict):
+            est.class_weight = {0: est.class_weight.get(self.classes_[i], 1.), 1: est.class_weight.get(self.classes_[j], 1.)}
+        return est
 
     def _fit_smo(self, proto, X, codes):
         """SVC.fit's SMO branch for every pair on one panel of all rows, built as `OneVsRestSVC._fit_smo` builds it (rank_one=False,
@@ -207,15 +221,21 @@ class OneVsOneSVC(_MultiClassSVC):
         obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Y[0], storage=proto.storage, rank_one=False, compact=False)
         dev = obj.device_problem()
         # (in solves of `smo_column_cap` columns of the memory free after the panel)
-        res = solve_batched_smo(dev, _lib.SVC, Y, proto.C, None, proto.tol, rows=[rows for rows, _ in problems])
+        # class_weight: column p's boxes on its rows are those the pair's own SVC.fit computes from its 0 / 1 labels
+        boxes = None
+        if has_class_weight(proto):
+            boxes = np.zeros((len(pairs), n))
+            for p, ((i, j), (rows, yp)) in enumerate(zip(pairs, problems)):
+                boxes[p, rows] = row_boxes(proto.C, (yp > 0).astype(int), np.arange(2), self._pair_prototype(i, j).class_weight)
+        res = solve_batched_smo(dev, _lib.SVC, Y, proto.C, None, proto.tol, rows=[rows for rows, _ in problems], boxes=boxes)
         ests, coefs = [], []
         for p, (rows, yp) in enumerate(problems):
             r = dict(res[p])
             # the column's n-long state on the pair's rows; the threshold rows as positions among them
             r['alphas'], r['errors'] = r['alphas'][rows], r['errors'][rows]
             r['b_up_idx'], r['b_low_idx'] = (int(np.searchsorted(rows, r[name])) for name in ('b_up_idx', 'b_low_idx'))
-            est = self._prototype()
-            sv = fitted_smo_svc(est, obj, r, X[rows], yp)
+            est = self._pair_prototype(*pairs[p])
+            sv = fitted_smo_svc(est, obj, r, X[rows], yp, None if boxes is None else boxes[p, rows])
             w = np.zeros(n)
             w[rows[sv]] = est.dual_coef_
             coefs.append(w)

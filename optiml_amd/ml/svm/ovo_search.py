@@ -42,6 +42,7 @@ import numpy as np
 
 from ... import _lib
 from ...device import get_context
+from ._base import has_class_weight
 from ._batched import (MAX_COLUMNS, MEMORY_SHARE, _DeviceSMOSolver, column_bytes, device_panel, run_batched_smo, smo_column_bytes,
                        solve_batched, solver_kind, takes_batched_smo)
 from .coupling import MAX_CLASSES
@@ -83,7 +84,7 @@ def uses_batched_ovo_search(estimator, candidates, splits, y, world, path=uses_b
     base = _base_params(estimator)
     for p in candidates:
         proto = _make(OneVsOneSVC, base, p)._prototype()
-        if not path(proto, world) or proto.storage != 'f64':
+        if has_class_weight(proto) or not path(proto, world) or proto.storage != 'f64':   # the search's columns carry one C each
             return False
         if isinstance(getattr(proto.kernel, 'gamma', None), str) and proto.kernel.gamma != 'auto':
             return False

@@ -21,7 +21,7 @@ __all__ = ['SMO', 'SMOClassifier', 'SMORegression']
 class SMO(ABC):
     _task = None
 
-    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False):
+    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None):
         if not isinstance(quad, KernelQuadratic):
             raise TypeError('the device SMO needs a KernelQuadratic (its Gram panel) as quad')
         self.quad = quad
@@ -33,6 +33,8 @@ class SMO(ABC):
             self.w = 0.
         self.b = 0.
         self.C = C
+        # one box per row, C_i = C * sample_weight_i * class_weight[y_i] (bq_smo_create_weighted), or None: the one C
+        self.box = None if box is None else _lib.as_f64(box, len(self.X), 'box')
         self.errors = np.zeros(len(self.X))
         self.tol = tol
         self.iter = 0
@@ -55,8 +57,12 @@ class SMO(ABC):
         lib = _lib.load()
         dev = self.quad.device_problem()
         h = C.c_void_p()
-        _lib.check(lib.bq_smo_create(dev.handle, self._task, _lib.ptr(self.y), float(self.C), float(self._epsilon()),
-                                     float(self.tol), C.byref(h)))
+        if self.box is None:
+            _lib.check(lib.bq_smo_create(dev.handle, self._task, _lib.ptr(self.y), float(self.C), float(self._epsilon()),
+                                         float(self.tol), C.byref(h)))
+        else:
+            _lib.check(lib.bq_smo_create_weighted(dev.handle, self._task, _lib.ptr(self.y), _lib.ptr(self.box),
+                                                  float(self._epsilon()), float(self.tol), C.byref(h)))
         try:
             if self.verbose:
                 print('iter\t cost')
@@ -93,9 +99,9 @@ class SMO(ABC):
 class SMOClassifier(SMO):
     _task = _lib.SVC
 
-    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False):
+    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None):
         self.alphas = np.zeros(len(X))
-        super(SMOClassifier, self).__init__(quad, X, y, K, kernel, C, tol, verbose)
+        super(SMOClassifier, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box)
 
     def _pull(self, lib, h):
         _lib.check(lib.bq_smo_get(h, _lib.SMO_ALPHAS, _lib.ptr(self.alphas)))
@@ -110,10 +116,10 @@ class SMOClassifier(SMO):
 class SMORegression(SMO):
     _task = _lib.SVR
 
-    def __init__(self, quad, X, y, K, kernel, C, epsilon, tol=1e-3, verbose=False):
+    def __init__(self, quad, X, y, K, kernel, C, epsilon, tol=1e-3, verbose=False, box=None):
         self.alphas_p = np.zeros(len(X))
         self.alphas_n = np.zeros(len(X))
-        super(SMORegression, self).__init__(quad, X, y, K, kernel, C, tol, verbose)
+        super(SMORegression, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box)
         self.epsilon = epsilon
 
     def _epsilon(self):
