@@ -17,18 +17,21 @@
 // K[i][j] comes from the packed lower-triangular tile-row panel (bq_sym_addr: the row part is contiguous strip by strip, the part right
 // of the diagonal tile is read down the column of the later tile rows — one page per support vector) or, preferably, from
 // a full square panel (BQ_FULL_PANEL: every row contiguous, one page per examined sample).
+// One walker, smo_walk<Task, T, Box> (SvcTask / SvrTask; panel element; BoxScalar / BoxRows), under two kernels: smo_kernel
+// (the single solver: workgroup 0 walks, the others help) and smo_batch_kernel (one walker per column, no helpers).
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "bq_c7.h"
 #include "bq_common.h"
 #include "bq_msmo.h"   // bq_smo_scal, the walkers' record, and what a scorer reads of a batched solver
 
-// -DBQ_SMO_STAMPS: thread 0 of the SVC walker accumulates the time of each phase of a full-sweep round (100 MHz
+// -DBQ_SMO_STAMPS: thread 0 of the walker accumulates the time of each phase of a full-sweep round (100 MHz
 // wall clock) and prints the totals at the end of the launch — diagnostic builds only
 #ifdef BQ_SMO_STAMPS
 #include <cstdio>
@@ -44,26 +47,6 @@
 #endif
 
 constexpr int SMO_T = 1024;
-
-struct bq_smo {
-    bq_problem *p = nullptr;
-    bq_owner mem;   // every device buffer below
-    int task = BQ_SVC;
-    int64_t n = 0;
-    double C = 1.0, eps = 0.0, tol = 1e-3;
-    double *Cw = nullptr;   // n per-row boxes (bq_smo_create_weighted), or null: the one C
-    double *y = nullptr, *a = nullptr, *am = nullptr, *err = nullptr;   // a: alpha (SVC) / alpha+ (SVR); am: alpha-
-    int *nz = nullptr;                                                   // n: support list (ascending indices)
-    double *cf = nullptr;                                                // n: and its coefficients
-    bq_smo_scal *sc = nullptr;
-    bq_smo_scal host;
-    // helper workgroups of the full sweeps (see "Helpers" below)
-    unsigned int *ctl = nullptr;       // SPEC_* words
-    void *spec_res = nullptr;          // n x 16 bytes: {bit pattern of sum_q c_q K[s][idx_q] formed by a helper, the list
-                                       // version it was formed under, checksum of the bits} — ONE 16-byte store / load
-    unsigned int epoch = 0;            // launch counter
-    int helpers = 0;                   // helper workgroups per full-sweep launch (0: none)
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // Helpers.  What a full sweep spends its time on is gathering panel entries: one error is n_sv scattered 8-byte reads,
@@ -187,30 +170,9 @@ __device__ __forceinline__ unsigned int dot_check(long long bits) {
     return (unsigned int)(u >> 32) ^ 0x5bd1e995u;
 }
 
-// The box of a dual: 0 <= alpha_i <= C_i.  BoxScalar holds the one C of an unweighted problem and returns it for any row —
-// its instantiations are the kernels as they were.  BoxRows reads C_i = C * sample_weight_i * class_weight[y_i] from a
-// vector by panel row (bq_smo_create_weighted, or column c's row of bq_msmo_create_weighted's k x n array); only rows the
-// walker examines, pairs with or keeps in its support list are read, so entries on rows outside a column's row list never
-// are.  Wherever a formula below says C1 / C2 it is the box of the partner / of the examined sample; with C1 == C2 each is
-// the scalar expression operation for operation, so BoxRows on a constant vector walks BoxScalar's path bit for bit.
-struct BoxScalar {
-    static constexpr bool per_row = false;
-    double C;
-    __device__ __forceinline__ double operator()(int64_t) const { return C; }
-    __device__ __forceinline__ double lane(bool, int64_t) const { return C; }
-    __device__ __forceinline__ double staged(const double *, int) const { return C; }
-};
-struct BoxRows {
-    static constexpr bool per_row = true;
-    const double *Cw;
-    __device__ __forceinline__ double operator()(int64_t i) const { return Cw[i]; }
-    // a lane past the batch reads nothing; `staged`: the batch's copy in LDS (see SmoShared)
-    __device__ __forceinline__ double lane(bool in, int64_t i) const { return in ? Cw[i] : 0.0; }
-    __device__ __forceinline__ double staged(const double *slot, int w) const { return slot[w]; }
-};
-
 template <typename T>
 struct KView {
+    using elem = T;
     bq_pview<T> panel;
     int64_t ld;   // 0: packed lower-triangular tile rows; else the pitch of a full square panel (BQ_FULL_PANEL)
     __device__ __forceinline__ double at(int64_t i, int64_t j) const {
@@ -625,6 +587,64 @@ struct SmoRows {
     __device__ __forceinline__ int64_t operator()(int64_t pos) const { return rows ? (int64_t)rows[pos] : pos; }
 };
 
+// One dual as a walker sees it: labels / targets, multipliers (a: alpha, or alpha+; am: alpha-, regression only), error
+// cache, the global copy of its support list, epsilon (regression), its record and the rows it sweeps.
+struct SmoColumn {
+    const double *y;
+    double *a, *am, *err;
+    SupGlobal G;
+    double eps;
+    bq_smo_scal *sc;
+    SmoRows R;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// Batched form: workgroup b is the walker of column live[b] of k independent duals on ONE panel.  Every piece of state
+// is per column (labels / targets, multipliers, error cache, support list, the bq_smo_scal record, C, epsilon, the row
+// list), there are no helpers, and so no workgroup ever reads a word another one writes: each runs to the end of its
+// sweep alone, and with more columns than CUs the workgroups simply queue.
+// ---------------------------------------------------------------------------------------------------------------
+struct SmoBatch {
+    const int *live;          // grid.x column numbers
+    const double *Y;          // k x n
+    double *A, *AM, *ERR;     // k x n each (AM: regression only)
+    int *NZ;                  // k x n
+    double *CF;               // k x n
+    const double *C, *eps;    // k (C: null with per-row boxes)
+    const double *CW;         // k x n per-row boxes (column c's in row c), or null: C
+    bq_smo_scal *sc;          // k
+    const int64_t *row_ptr;   // k + 1 offsets into rows, or nullptr: every column on all rows
+    const int *rows;
+    __device__ __forceinline__ SmoColumn column(int64_t c, int64_t n) const {
+        return SmoColumn{Y + c * n, A + c * n, AM + c * n, ERR + c * n, SupGlobal{NZ + c * n, CF + c * n}, eps[c], sc + c,
+                         row_ptr ? SmoRows{rows + row_ptr[c], row_ptr[c + 1] - row_ptr[c]} : SmoRows{nullptr, n}};
+    }
+};
+
+// The box of a dual: 0 <= alpha_i <= C_i.  BoxScalar holds the one C of an unweighted problem and returns it for any row.
+// BoxRows reads C_i = C * sample_weight_i * class_weight[y_i] from a vector by panel row (bq_smo_create_weighted, or
+// column c's row of bq_msmo_create_weighted's k x n array); only rows the walker examines, pairs with or keeps in its
+// support list are read, so entries on rows outside a column's row list never are.  Wherever a formula below says C1 / C2
+// it is the box of the partner / of the examined sample; with C1 == C2 each is the scalar expression operation for
+// operation, so BoxRows on a constant vector walks BoxScalar's path bit for bit.
+struct BoxScalar {
+    static constexpr bool per_row = false;
+    double C;
+    static __device__ __forceinline__ BoxScalar of(const SmoBatch &Bt, int64_t c, int64_t) { return BoxScalar{Bt.C[c]}; }
+    __device__ __forceinline__ double operator()(int64_t) const { return C; }
+    __device__ __forceinline__ double lane(bool, int64_t) const { return C; }
+    __device__ __forceinline__ double staged(const double *, int) const { return C; }
+};
+struct BoxRows {
+    static constexpr bool per_row = true;
+    const double *Cw;
+    static __device__ __forceinline__ BoxRows of(const SmoBatch &Bt, int64_t c, int64_t n) { return BoxRows{Bt.CW + c * n}; }
+    __device__ __forceinline__ double operator()(int64_t i) const { return Cw[i]; }
+    // a lane past the batch reads nothing; `staged`: the batch's copy in LDS (see SmoShared)
+    __device__ __forceinline__ double lane(bool in, int64_t i) const { return in ? Cw[i] : 0.0; }
+    __device__ __forceinline__ double staged(const double *slot, int w) const { return slot[w]; }
+};
+
 template <typename T>
 __device__ __forceinline__ double wave_dot(const KView<T> &K, const SupList &L, const SupGlobal &G, int nnz, int64_t s,
                                            const SmoSpec &P, unsigned int ver, bool ahead) {
@@ -684,9 +704,10 @@ __device__ __forceinline__ int sup_lower_bound(const SupList &L, const SupGlobal
 // error (cached, or just formed), C2 its box.  Returns true when a pair step was taken; its data is left in S for
 // svc_after_step.
 template <typename T, typename Box>
-__device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, const double *y, double *a, double *err,
-                                            const Box &Cb, double C2, double tol, long long i2, double a2, double y2,
-                                            double E2) {
+__device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, const SmoColumn &col, const Box &Cb, double C2,
+                                            double tol, long long i2, double a2, double y2, double E2) {
+    const double *y = col.y;
+    double *a = col.a, *err = col.err;
     const bool free2 = a2 > 0.0 && a2 < C2;
     const bool up2 = (y2 == 1.0 && a2 == 0.0) || (y2 == -1.0 && a2 == C2);     // I1 or I2
     const bool low2 = (y2 == 1.0 && a2 == C2) || (y2 == -1.0 && a2 == 0.0);    // I3 or I4
@@ -747,8 +768,11 @@ __device__ __forceinline__ bool svc_examine(SmoShared &S, const KView<T> &K, con
 
 // all threads, after a pair step: support list, error cache of the free set, thresholds (smo.py:199-201, :241-271)
 template <typename T, typename Box>
-__device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const SupGlobal &G, const KView<T> &K,
-                                               const double *y, double *a, double *err, const Box &Cb, const SmoSpec &P) {
+__device__ __forceinline__ void svc_after_step(SmoShared &S, SupList &L, const KView<T> &K, const SmoColumn &col, const Box &Cb,
+                                               const SmoSpec &P) {
+    const SupGlobal &G = col.G;
+    const double *y = col.y;
+    double *a = col.a, *err = col.err;
     const int tid = threadIdx.x;
     const long long i1 = S.i1, i2 = S.i2;
     spec_begin(P, S);
@@ -852,260 +876,6 @@ __device__ __forceinline__ bool svc_quiet_batch(SmoShared &S, double *err, doubl
     return fast;
 }
 
-// The walker: one outer iteration (a full sweep over the samples R lists, or free-set sweeps until they stall) of one
-// dual, by one whole workgroup.  Without helpers (P.helpers == 0) it waits for no other workgroup at any point.
-template <typename T, typename Box>
-__device__ __forceinline__ void smo_svc_walk(const KView<T> &K, int64_t n, const SmoRows &R, const double *__restrict__ y,
-                                             double *a, double *err, const SupGlobal &G, const Box Cb, double tol,
-                                             bq_smo_scal *sc, const SmoSpec &P) {
-    __shared__ SmoShared S;
-    __shared__ SupList L;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) {
-        S.b_up = sc->b_up;
-        S.b_low = sc->b_low;
-        S.i_up = sc->i_up;
-        S.i_low = sc->i_low;
-        S.fail = 0;
-        S.go = 0;
-        S.ver = P.helpers ? ld_rlx(&P.ctl[SPEC_VER]) : 0u;
-        S.win = 0;
-    }
-    __syncthreads();
-    if (sc->finished) {
-        if (tid == 0 && P.helpers) st_rel(&P.ctl[SPEC_DONE], P.epoch);
-        return;
-    }
-    const bool sweep_all = sc->sweep_all != 0;
-    long long changed = 0, steps = 0;
-    spec_begin(P, S);
-    smo_rebuild(n, G.nz, S, [&](int64_t j) { return a[j] != 0.0; });
-    sup_fill(L, G, S, [&](int j) { return __dmul_rn(a[j], y[j]); });
-    spec_end(P, S, 0);
-    if (sweep_all) {
-        int64_t i = 0;   // position in R
-#ifdef BQ_SMO_STAMPS
-        unsigned long long stamp_acc[8] = {0}, stamp_cnt[8] = {0}, stamp_t = wall_clock64();
-#endif
-        while (i < R.m) {
-            SMO_STAMP(7)   // loop tail of the previous round
-            if (tid == 0 && P.helpers) {   // where the walk stands; a batch without a pair step doubles the look-ahead
-                const unsigned int cap = (unsigned int)(P.helpers * SMO_B);
-                if (!S.go) S.win = S.win * 2u < cap ? S.win * 2u : cap;
-                st_rlx64((long long *)&P.ctl[SPEC_POS], (long long)i);
-                st_rlx(&P.ctl[SPEC_WIN], S.win);
-            }
-            if (P.helpers) {
-                // Once the look-ahead has grown, the helpers are ahead of the walk: wave 0 tries 64 samples at once, one per
-                // lane — multiplier, label, the helper's tagged sum (or the cached error) — and the same quiet-batch
-                // test as below.  A missing tag or a possible violator leaves everything to the 16-sample batch.
-                if (wv == 0) {
-                    bool wide = false;
-                    if (S.win > (unsigned int)SMO_B) {   // same wave as thread 0, which has just written it
-                        const int B = R.m - i < 64 ? (int)(R.m - i) : 64;
-                        const bool in = lane < B;
-                        const int64_t sw = in ? R(i + lane) : 0;
-                        const double a2 = in ? a[sw] : 0.0, y2 = in ? y[sw] : 0.0;
-                        const double C2 = Cb.lane(in, sw);   // the lane's own box, staged beside its multiplier and label
-                        const bool free2 = in && a2 > 0.0 && a2 < C2;
-                        const bool need = in && !free2;
-                        smo_u4 res = {0u, 0u, 0u, 0u};
-                        if (need) res = res_load(P, sw);
-                        const long long bits = res_bits(res);
-                        if (__ballot(need && res.z != S.ver) == 0ull) {
-                            const unsigned long long bad = __ballot(need && dot_check(bits) != res.w);
-                            if (bad != 0ull && lane == 0) atomicAdd(&P.ctl[SPEC_REJ_CHK], (unsigned int)__popcll(bad));
-                            if (bad == 0ull) {
-                                double E2 = 0.0;
-                                if (need)
-                                    E2 = __longlong_as_double(bits) - y2;
-                                else if (in)
-                                    E2 = err[sw];
-                                wide = svc_quiet_batch(S, err, C2, tol, R, i, B, in, a2, y2, E2);
-                            }
-                        }
-                    }
-                    if (lane == 0) S.fast = wide ? 2 : 0;
-                }
-                __syncthreads();
-                if (S.fast == 2) {
-                    SMO_STAMP(0)   // a wide quiet round
-                    i += S.used;
-                    __syncthreads();   // S.fast / S.used are rewritten in the next round
-                    continue;
-                }
-                SMO_STAMP(1)       // a wide attempt that fell through
-            }
-            if (i + wv < R.m) {   // wave-uniform
-                const int64_t s = R(i + wv);
-                const double as = a[s], ys = y[s], Cs = Cb(s);
-                double E = 0.0;
-                if (!(as > 0.0 && as < Cs)) E = wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B) - ys;
-                if (lane == 0) {
-                    S.ba[wv] = as;
-                    S.by[wv] = ys;
-                    S.bE[wv] = (as > 0.0 && as < Cs) ? err[s] : E;
-                    if constexpr (Box::per_row) S.bm[wv] = Cs;
-                }
-            }
-            __syncthreads();
-            SMO_STAMP(2)   // the sixteen errors of the batch
-            const int B = R.m - i < SMO_B ? (int)(R.m - i) : SMO_B;
-            // fast path: wave 0 examines the whole batch at once when it holds no possible violator
-            if (wv == 0) {
-                const bool in = lane < B;
-                const bool fast = svc_quiet_batch(S, err, Cb.staged(S.bm, in ? lane : 0), tol, R, i, B, in, in ? S.ba[lane] : 0.0,
-                                                  in ? S.by[lane] : 0.0, in ? S.bE[lane] : 0.0);
-                if (lane == 0) S.fast = fast ? 1 : 0;
-            }
-            __syncthreads();
-            SMO_STAMP(3)   // quiet-batch test
-            if (tid == 0 && !S.fast) {
-                int used = B;
-                S.go = 0;
-                for (int w = 0; w < B; ++w) {
-                    if (svc_examine(S, K, y, a, err, Cb, Cb.staged(S.bm, w), tol, R(i + w), S.ba[w], S.by[w], S.bE[w])) {
-                        S.go = 1;
-                        used = w + 1;
-                        break;
-                    }
-                }
-                S.used = used;
-            }
-            __syncthreads();
-            SMO_STAMP(4)   // sequential walk of the batch (incl. the pair solve)
-            if (S.go) {
-                svc_after_step(S, L, G, K, y, a, err, Cb, P);
-                ++changed;
-                ++steps;
-                SMO_STAMP(5)   // list edit, error cache, thresholds
-            }
-            if (S.fail) break;
-            i += S.used;
-            __syncthreads();   // S.used / S.go are rewritten by thread 0 in the next round
-        }
-#ifdef BQ_SMO_STAMPS
-        if (tid == 0) {
-            // phases: 0 wide quiet round, 1 wide attempt that fell through, 2 the sixteen errors of a batch, 3 quiet-batch
-            // test, 4 sequential walk + pair solve, 5 after a step (list edit, error cache, thresholds), 7 loop tail
-            for (int k = 0; k < 8; ++k)
-                if (stamp_cnt[k])
-                    printf("[smo stamps] phase %d: %llu x %.2f us = %.2f ms\n", k, stamp_cnt[k],
-                           0.01 * (double)stamp_acc[k] / (double)stamp_cnt[k], 1e-5 * (double)stamp_acc[k]);
-        }
-#endif
-    } else {
-        long long last = -1;
-        while (true) {
-            if (tid == 0) {
-                S.go = 0;
-                S.stop = 1;
-                for (int q = sup_lower_bound(L, G, S.nnz, last + 1); q < S.nnz; ++q) {
-                    const long long j = sup_idx(L, G, q);
-                    const double aj = a[j], Cj = Cb(j);
-                    if (aj > 0.0 && aj < Cj) {
-                        S.stop = 0;
-                        S.i2 = j;
-                        S.go = svc_examine(S, K, y, a, err, Cb, Cj, tol, j, aj, y[j], err[j]) ? 1 : 0;
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
-            if (S.stop) break;
-            if (S.go) {
-                svc_after_step(S, L, G, K, y, a, err, Cb, P);
-                ++changed;
-                ++steps;
-            }
-            if (S.fail) break;
-            if (S.b_up > S.b_low - 2 * tol) {   // optimality on the free set (smo.py:339-342)
-                changed = 0;
-                break;
-            }
-            last = S.i2;
-            __syncthreads();
-        }
-    }
-    if (tid == 0) {
-        sc->b_up = S.b_up;
-        sc->b_low = S.b_low;
-        sc->i_up = S.i_up;
-        sc->i_low = S.i_low;
-        sc->steps += steps;
-        sc->changed = changed;
-        sc->err_flag = S.fail;
-        int next_all = sweep_all ? 0 : (changed == 0 ? 1 : 0);
-        sc->sweep_all = next_all;
-        sc->outer += 1;
-        sc->finished = (S.fail || !(changed > 0 || next_all)) ? 1 : 0;
-        if (P.helpers) {   // every exit path of the walker ends here (or in the early return above): release the helpers
-            st_rlx(&P.ctl[SPEC_WIN], 0u);
-            st_rel(&P.ctl[SPEC_DONE], P.epoch);
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svc_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
-                                                        double *a, double *err, SupGlobal G, double C,
-                                                        double tol, bq_smo_scal *sc, SmoSpec P) {
-    if (blockIdx.x != 0) {
-        smo_helper(K, n, G, P);
-        return;
-    }
-    smo_svc_walk(K, n, SmoRows{nullptr, n}, y, a, err, G, BoxScalar{C}, tol, sc, P);
-}
-
-// the same with per-row boxes Cw (n): bq_smo_create_weighted
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svc_rows_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
-                                                             double *a, double *err, SupGlobal G, const double *Cw,
-                                                             double tol, bq_smo_scal *sc, SmoSpec P) {
-    if (blockIdx.x != 0) {
-        smo_helper(K, n, G, P);   // the helpers form sum_q c_q K[s][idx_q] only: no box
-        return;
-    }
-    smo_svc_walk(K, n, SmoRows{nullptr, n}, y, a, err, G, BoxRows{Cw}, tol, sc, P);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Batched form: workgroup b is the walker of column live[b] of k independent duals on ONE panel.  Every piece of state
-// is per column (labels / targets, multipliers, error cache, support list, the bq_smo_scal record, C, epsilon, the row
-// list), there are no helpers, and so no workgroup ever reads a word another one writes: each runs to the end of its
-// sweep alone, and with more columns than CUs the workgroups simply queue.
-// ---------------------------------------------------------------------------------------------------------------
-struct SmoBatch {
-    const int *live;          // grid.x column numbers
-    const double *Y;          // k x n
-    double *A, *AM, *ERR;     // k x n each (AM: regression only)
-    int *NZ;                  // k x n
-    double *CF;               // k x n
-    const double *C, *eps;    // k
-    bq_smo_scal *sc;          // k
-    const int64_t *row_ptr;   // k + 1 offsets into rows, or nullptr: every column on all rows
-    const int *rows;
-    __device__ __forceinline__ SmoRows rows_of(int64_t c, int64_t n) const {
-        return row_ptr ? SmoRows{rows + row_ptr[c], row_ptr[c + 1] - row_ptr[c]} : SmoRows{nullptr, n};
-    }
-};
-
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svc_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
-    const int64_t c = Bt.live[blockIdx.x];
-    smo_svc_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.ERR + c * n, SupGlobal{Bt.NZ + c * n, Bt.CF + c * n},
-                 BoxScalar{Bt.C[c]}, tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
-}
-
-// the same with column c's boxes in row c of CW (k x n): bq_msmo_create_weighted (Bt.C is not read)
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svc_rows_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, const double *CW,
-                                                                   double tol) {
-    const int64_t c = Bt.live[blockIdx.x];
-    smo_svc_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.ERR + c * n, SupGlobal{Bt.NZ + c * n, Bt.CF + c * n},
-                 BoxRows{CW + c * n}, tol, Bt.sc + c, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // regression (smo.py:447-758)
 // ---------------------------------------------------------------------------------------------------------------
@@ -1133,9 +903,10 @@ __device__ __forceinline__ long long svr_pick(const SmoShared &S, double vlow, d
 // thread 0: examine sample i2 (smo.py:677-758) and, if it violates, solve the pair (:447-600).  E2 is its error (cached,
 // or just formed), C2 its box.  Returns true when a pair step was taken; its data is left in S for svr_after_step.
 template <typename T, typename Box>
-__device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, const double *y, double *ap, double *an,
-                                            double *err, const Box &Cb, double C2, double eps, double tol, long long i2,
-                                            double p2, double m2, double E2) {
+__device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, const SmoColumn &col, const Box &Cb, double C2,
+                                            double tol, long long i2, double p2, double m2, double E2) {
+    double *ap = col.a, *an = col.am, *err = col.err;
+    const double eps = col.eps;
     const int k2 = svr_kind(p2, m2, C2);
     if (k2 != 0) {
         err[i2] = E2;
@@ -1265,9 +1036,11 @@ __device__ __forceinline__ bool svr_examine(SmoShared &S, const KView<T> &K, con
 
 // all threads, after a pair step: support list, error cache of the free set, thresholds (smo.py:601-675)
 template <typename T, typename Box>
-__device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const SupGlobal &G, const KView<T> &K,
-                                               double *ap, double *an, double *err, const Box &Cb, double eps,
+__device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const KView<T> &K, const SmoColumn &col, const Box &Cb,
                                                const SmoSpec &P) {
+    const SupGlobal &G = col.G;
+    double *ap = col.a, *an = col.am, *err = col.err;
+    const double eps = col.eps;
     const int tid = threadIdx.x;
     const long long i1 = S.i1, i2 = S.i2;
     spec_begin(P, S);
@@ -1338,13 +1111,71 @@ __device__ __forceinline__ void svr_after_step(SmoShared &S, SupList &L, const S
     __syncthreads();
 }
 
-// the regression walker (see smo_svc_walk)
-template <typename T, typename Box>
-__device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const SmoRows &R, const double *__restrict__ y,
-                                             double *ap, double *an, double *err, const SupGlobal &G, const Box Cb, double eps,
-                                             double tol, bq_smo_scal *sc, const SmoSpec &P) {
+// ---------------------------------------------------------------------------------------------------------------
+// The two tasks: everything the walker below does not share.  A sample's state is the pair (u, v): multiplier and label
+// for classification, alpha+ and alpha- for regression.
+// ---------------------------------------------------------------------------------------------------------------
+struct SvcTask {
+    static constexpr bool quiet_batches = true;   // svc_quiet_batch
+    static __device__ __forceinline__ bool listed(const SmoColumn &c, int64_t j) { return c.a[j] != 0.0; }
+    static __device__ __forceinline__ double coef(const SmoColumn &c, int j) { return __dmul_rn(c.a[j], c.y[j]); }
+    static __device__ __forceinline__ double second(const SmoColumn &c, int64_t j) { return c.y[j]; }
+    static __device__ __forceinline__ bool cached(double a, double, double C) { return a > 0.0 && a < C; }   // free
+    // the error of a sample from the sum over the support list: its target, read before the sum is formed, then the sign
+    static __device__ __forceinline__ double target(const SmoColumn &, int64_t, double y) { return y; }
+    static __device__ __forceinline__ double error(double y, double dot) { return dot - y; }
+    // a batch stages (u, v) in (ba, second_slot) and, BoxRows only, its boxes in the slot the task leaves unused
+    static __device__ __forceinline__ double *second_slot(SmoShared &S) { return S.by; }
+    static __device__ __forceinline__ double *box_slot(SmoShared &S) { return S.bm; }
+    template <typename T, typename Box>
+    static __device__ __forceinline__ bool examine(SmoShared &S, const KView<T> &K, const SmoColumn &c, const Box &Cb, double C2,
+                                                   double tol, long long i2, double u, double v, double E2) {
+        return svc_examine(S, K, c, Cb, C2, tol, i2, u, v, E2);
+    }
+    template <typename T, typename Box>
+    static __device__ __forceinline__ void after_step(SmoShared &S, SupList &L, const KView<T> &K, const SmoColumn &c,
+                                                      const Box &Cb, const SmoSpec &P) {
+        svc_after_step(S, L, K, c, Cb, P);
+    }
+};
+struct SvrTask {
+    static constexpr bool quiet_batches = false;
+    static __device__ __forceinline__ bool listed(const SmoColumn &c, int64_t j) {   // a superset of the free set
+        return c.a[j] != 0.0 || c.am[j] != 0.0;
+    }
+    static __device__ __forceinline__ double coef(const SmoColumn &c, int j) { return c.a[j] - c.am[j]; }
+    static __device__ __forceinline__ double second(const SmoColumn &c, int64_t j) { return c.am[j]; }
+    static __device__ __forceinline__ bool cached(double p, double m, double C) { return svr_kind(p, m, C) == 0; }
+    static __device__ __forceinline__ double target(const SmoColumn &c, int64_t s, double) { return c.y[s]; }
+    static __device__ __forceinline__ double error(double y, double dot) { return y - dot; }
+    static __device__ __forceinline__ double *second_slot(SmoShared &S) { return S.bm; }
+    static __device__ __forceinline__ double *box_slot(SmoShared &S) { return S.by; }
+    template <typename T, typename Box>
+    static __device__ __forceinline__ bool examine(SmoShared &S, const KView<T> &K, const SmoColumn &c, const Box &Cb, double C2,
+                                                   double tol, long long i2, double u, double v, double E2) {
+        return svr_examine(S, K, c, Cb, C2, tol, i2, u, v, E2);
+    }
+    template <typename T, typename Box>
+    static __device__ __forceinline__ void after_step(SmoShared &S, SupList &L, const KView<T> &K, const SmoColumn &c,
+                                                      const Box &Cb, const SmoSpec &P) {
+        svr_after_step(S, L, K, c, Cb, P);
+    }
+};
+
+// The walker: one outer iteration (a full sweep over the samples col.R lists, or free-set sweeps until they stall) of one
+// dual, by one whole workgroup.  Without helpers (P.helpers == 0) it waits for no other workgroup at any point.
+// y is c.y once more: nothing the walker writes aliases the labels / targets, and only a parameter can say so (a member of
+// SmoColumn cannot carry __restrict__) — the walker's own column is rebuilt on that pointer.
+template <typename Task, typename T, typename Box>
+__device__ __forceinline__ void smo_walk(const KView<T> &K, int64_t n, const double *__restrict__ y, const SmoColumn &c, const Box Cb,
+                                         double tol, const SmoSpec &P) {
+    const SmoColumn col{y, c.a, c.am, c.err, c.G, c.eps, c.sc, c.R};
     __shared__ SmoShared S;
     __shared__ SupList L;
+    const SmoRows &R = col.R;
+    const SupGlobal &G = col.G;
+    bq_smo_scal *sc = col.sc;
+    double *a = col.a, *err = col.err;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) {
         S.b_up = sc->b_up;
@@ -1364,39 +1195,102 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
     const bool sweep_all = sc->sweep_all != 0;
     long long changed = 0, steps = 0;
     spec_begin(P, S);
-    smo_rebuild(n, G.nz, S, [&](int64_t j) { return ap[j] != 0.0 || an[j] != 0.0; });   // a superset of the free set
-    sup_fill(L, G, S, [&](int j) { return ap[j] - an[j]; });
+    smo_rebuild(n, G.nz, S, [&](int64_t j) { return Task::listed(col, j); });
+    sup_fill(L, G, S, [&](int j) { return Task::coef(col, j); });
     spec_end(P, S, 0);
     if (sweep_all) {
         int64_t i = 0;   // position in R
+#ifdef BQ_SMO_STAMPS
+        unsigned long long stamp_acc[8] = {0}, stamp_cnt[8] = {0}, stamp_t = wall_clock64();
+#endif
         while (i < R.m) {
-            if (tid == 0 && P.helpers) {
+            SMO_STAMP(7)   // loop tail of the previous round
+            if (tid == 0 && P.helpers) {   // where the walk stands; a batch without a pair step doubles the look-ahead
                 const unsigned int cap = (unsigned int)(P.helpers * SMO_B);
                 if (!S.go) S.win = S.win * 2u < cap ? S.win * 2u : cap;
                 st_rlx64((long long *)&P.ctl[SPEC_POS], (long long)i);
                 st_rlx(&P.ctl[SPEC_WIN], S.win);
             }
-            if (i + wv < R.m) {   // wave-uniform
+            if constexpr (Task::quiet_batches) {
+                if (P.helpers) {
+                    // Once the look-ahead has grown, the helpers are ahead of the walk: wave 0 tries 64 samples at once, one
+                    // per lane — multiplier, label, the helper's tagged sum (or the cached error) — and the same quiet-batch
+                    // test as below.  A missing tag or a possible violator leaves everything to the 16-sample batch.
+                    if (wv == 0) {
+                        bool wide = false;
+                        if (S.win > (unsigned int)SMO_B) {   // same wave as thread 0, which has just written it
+                            const int B = R.m - i < 64 ? (int)(R.m - i) : 64;
+                            const bool in = lane < B;
+                            const int64_t sw = in ? R(i + lane) : 0;
+                            const double a2 = in ? a[sw] : 0.0, y2 = in ? col.y[sw] : 0.0;
+                            const double C2 = Cb.lane(in, sw);   // the lane's own box, staged beside its multiplier and label
+                            const bool free2 = in && a2 > 0.0 && a2 < C2;
+                            const bool need = in && !free2;
+                            smo_u4 res = {0u, 0u, 0u, 0u};
+                            if (need) res = res_load(P, sw);
+                            const long long bits = res_bits(res);
+                            if (__ballot(need && res.z != S.ver) == 0ull) {
+                                const unsigned long long bad = __ballot(need && dot_check(bits) != res.w);
+                                if (bad != 0ull && lane == 0) atomicAdd(&P.ctl[SPEC_REJ_CHK], (unsigned int)__popcll(bad));
+                                if (bad == 0ull) {
+                                    double E2 = 0.0;
+                                    if (need)
+                                        E2 = __longlong_as_double(bits) - y2;
+                                    else if (in)
+                                        E2 = err[sw];
+                                    wide = svc_quiet_batch(S, err, C2, tol, R, i, B, in, a2, y2, E2);
+                                }
+                            }
+                        }
+                        if (lane == 0) S.fast = wide ? 2 : 0;
+                    }
+                    __syncthreads();
+                    if (S.fast == 2) {
+                        SMO_STAMP(0)   // a wide quiet round
+                        i += S.used;
+                        __syncthreads();   // S.fast / S.used are rewritten in the next round
+                        continue;
+                    }
+                    SMO_STAMP(1)       // a wide attempt that fell through
+                }
+            }
+            if (i + wv < R.m) {   // wave-uniform: one sample per wave, its state and, unless cached, its error
                 const int64_t s = R(i + wv);
-                const double ps = ap[s], ms = an[s], Cs = Cb(s);
-                const bool cached = svr_kind(ps, ms, Cs) == 0;
+                const double u = a[s], v = Task::second(col, s), Cs = Cb(s);
+                const bool cached = Task::cached(u, v, Cs);
                 double E = 0.0;
-                if (!cached) E = y[s] - wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B);
+                if (!cached) {
+                    const double t = Task::target(col, s, v);
+                    E = Task::error(t, wave_dot(K, L, G, S.nnz, s, P, S.ver, S.win > (unsigned int)SMO_B));
+                }
                 if (lane == 0) {
-                    S.ba[wv] = ps;
-                    S.bm[wv] = ms;
+                    S.ba[wv] = u;
+                    Task::second_slot(S)[wv] = v;
                     S.bE[wv] = cached ? err[s] : E;
-                    if constexpr (Box::per_row) S.by[wv] = Cs;
+                    if constexpr (Box::per_row) Task::box_slot(S)[wv] = Cs;
                 }
             }
             __syncthreads();
-            if (tid == 0) {
-                const int B = R.m - i < SMO_B ? (int)(R.m - i) : SMO_B;
+            SMO_STAMP(2)   // the sixteen errors of the batch
+            if constexpr (Task::quiet_batches) {
+                // fast path: wave 0 examines the whole batch at once when it holds no possible violator
+                if (wv == 0) {
+                    const int B = R.m - i < SMO_B ? (int)(R.m - i) : SMO_B;
+                    const bool in = lane < B;
+                    const bool fast = svc_quiet_batch(S, err, Cb.staged(S.bm, in ? lane : 0), tol, R, i, B, in, in ? S.ba[lane] : 0.0,
+                                                      in ? S.by[lane] : 0.0, in ? S.bE[lane] : 0.0);
+                    if (lane == 0) S.fast = fast ? 1 : 0;
+                }
+                __syncthreads();
+                SMO_STAMP(3)   // quiet-batch test
+            }
+            if (tid == 0 && !(Task::quiet_batches && S.fast)) {   // the sequential walk: the reference's scalar logic, sample by sample
+                const int B = R.m - i < SMO_B ? (int)(R.m - i) : SMO_B;   // formed where it is used, not held across the barrier
                 int used = B;
                 S.go = 0;
                 for (int w = 0; w < B; ++w) {
-                    const bool took = svr_examine(S, K, y, ap, an, err, Cb, Cb.staged(S.by, w), eps, tol, R(i + w), S.ba[w], S.bm[w],
-                                                  S.bE[w]);
+                    const bool took = Task::examine(S, K, col, Cb, Cb.staged(Task::box_slot(S), w), tol, R(i + w), S.ba[w],
+                                                    Task::second_slot(S)[w], S.bE[w]);
                     if (took || S.fail) {
                         S.go = took ? 1 : 0;
                         used = w + 1;
@@ -1406,15 +1300,27 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
                 S.used = used;
             }
             __syncthreads();
+            SMO_STAMP(4)   // sequential walk of the batch (incl. the pair solve)
             if (S.go) {
-                svr_after_step(S, L, G, K, ap, an, err, Cb, eps, P);
+                Task::after_step(S, L, K, col, Cb, P);
                 ++changed;
                 ++steps;
+                SMO_STAMP(5)   // list edit, error cache, thresholds
             }
             if (S.fail) break;
             i += S.used;
             __syncthreads();   // S.used / S.go are rewritten by thread 0 in the next round
         }
+#ifdef BQ_SMO_STAMPS
+        if (tid == 0) {
+            // phases: 0 wide quiet round, 1 wide attempt that fell through, 2 the sixteen errors of a batch, 3 quiet-batch
+            // test, 4 sequential walk + pair solve, 5 after a step (list edit, error cache, thresholds), 7 loop tail
+            for (int k = 0; k < 8; ++k)
+                if (stamp_cnt[k])
+                    printf("[smo stamps] phase %d: %llu x %.2f us = %.2f ms\n", k, stamp_cnt[k],
+                           0.01 * (double)stamp_acc[k] / (double)stamp_cnt[k], 1e-5 * (double)stamp_acc[k]);
+        }
+#endif
     } else {
         long long last = -1;
         while (true) {
@@ -1423,11 +1329,12 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
                 S.stop = 1;
                 for (int q = sup_lower_bound(L, G, S.nnz, last + 1); q < S.nnz; ++q) {
                     const long long j = sup_idx(L, G, q);
-                    const double pj = ap[j], mj = an[j], Cj = Cb(j);
-                    if (svr_kind(pj, mj, Cj) == 0) {
+                    const double u = a[j], Cj = Cb(j);
+                    // the free set: exactly the samples whose error is cached (classification reads the label only of those)
+                    if (Task::cached(u, Task::second(col, j), Cj)) {
                         S.stop = 0;
                         S.i2 = j;
-                        S.go = svr_examine(S, K, y, ap, an, err, Cb, Cj, eps, tol, j, pj, mj, err[j]) ? 1 : 0;
+                        S.go = Task::examine(S, K, col, Cb, Cj, tol, j, u, Task::second(col, j), err[j]) ? 1 : 0;
                         break;
                     }
                 }
@@ -1435,12 +1342,12 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
             __syncthreads();
             if (S.stop) break;
             if (S.go) {
-                svr_after_step(S, L, G, K, ap, an, err, Cb, eps, P);
+                Task::after_step(S, L, K, col, Cb, P);
                 ++changed;
                 ++steps;
             }
             if (S.fail) break;
-            if (S.b_up > S.b_low - 2 * tol) {
+            if (S.b_up > S.b_low - 2 * tol) {   // optimality on the free set (smo.py:339-342)
                 changed = 0;
                 break;
             }
@@ -1467,263 +1374,33 @@ __device__ __forceinline__ void smo_svr_walk(const KView<T> &K, int64_t n, const
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svr_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
-                                                        double *ap, double *an, double *err, SupGlobal G,
-                                                        double C, double eps, double tol, bq_smo_scal *sc, SmoSpec P) {
+// The single solver: workgroup 0 walks column 0 of its one-column batch, every other workgroup is a helper (they form
+// sum_q c_q K[s][idx_q] only: no box).  It sweeps every row, stated as a literal here so that the identity map folds away.
+// The batch comes last among the arguments: in front of the SmoSpec its pointers share one 16-register scalar load with the
+// panel's, and the regression walker then spills and reloads that whole tuple in every block of its pair step.
+template <typename Task, typename T, typename Box>
+__global__ __launch_bounds__(SMO_T) void smo_kernel(KView<T> K, int64_t n, double tol, SmoSpec P, SmoBatch Bt) {
+    const int64_t c = 0;
+    const SmoColumn col = Bt.column(c, n);
     if (blockIdx.x != 0) {
-        smo_helper(K, n, G, P);
+        smo_helper(K, n, col.G, P);
         return;
     }
-    smo_svr_walk(K, n, SmoRows{nullptr, n}, y, ap, an, err, G, BoxScalar{C}, eps, tol, sc, P);
+    smo_walk<Task>(K, n, col.y, SmoColumn{col.y, col.a, col.am, col.err, col.G, col.eps, col.sc, SmoRows{nullptr, n}},
+                   Box::of(Bt, c, n), tol, P);
 }
 
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svr_rows_kernel(KView<T> K, int64_t n, const double *__restrict__ y,
-                                                             double *ap, double *an, double *err, SupGlobal G,
-                                                             const double *Cw, double eps, double tol, bq_smo_scal *sc,
-                                                             SmoSpec P) {
-    if (blockIdx.x != 0) {
-        smo_helper(K, n, G, P);
-        return;
-    }
-    smo_svr_walk(K, n, SmoRows{nullptr, n}, y, ap, an, err, G, BoxRows{Cw}, eps, tol, sc, P);
-}
-
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svr_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
+// The batched solver: workgroup b walks column live[b].  The literal empty SmoSpec folds every helper path away — which is
+// why this is a kernel of its own and not smo_kernel with no helpers.
+template <typename Task, typename T, typename Box>
+__global__ __launch_bounds__(SMO_T) void smo_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, double tol) {
     const int64_t c = Bt.live[blockIdx.x];
-    smo_svr_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.AM + c * n, Bt.ERR + c * n,
-                 SupGlobal{Bt.NZ + c * n, Bt.CF + c * n}, BoxScalar{Bt.C[c]}, Bt.eps[c], tol, Bt.sc + c,
-                 SmoSpec{nullptr, nullptr, 0u, 0u, 0});
-}
-
-template <typename T>
-__global__ __launch_bounds__(SMO_T) void smo_svr_rows_batch_kernel(KView<T> K, int64_t n, SmoBatch Bt, const double *CW,
-                                                                   double tol) {
-    const int64_t c = Bt.live[blockIdx.x];
-    smo_svr_walk(K, n, Bt.rows_of(c, n), Bt.Y + c * n, Bt.A + c * n, Bt.AM + c * n, Bt.ERR + c * n,
-                 SupGlobal{Bt.NZ + c * n, Bt.CF + c * n}, BoxRows{CW + c * n}, Bt.eps[c], tol, Bt.sc + c,
-                 SmoSpec{nullptr, nullptr, 0u, 0u, 0});
+    const SmoColumn col = Bt.column(c, n);
+    smo_walk<Task>(K, n, col.y, col, Box::of(Bt, c, n), tol, SmoSpec{nullptr, nullptr, 0u, 0u, 0});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------------------------------------------
-extern "C" int bq_smo_destroy(bq_smo *s) {
-    if (s == nullptr) return BQ_OK;
-    hipSetDevice(s->p->ctx->device);
-    hipStreamSynchronize(s->p->ctx->stream);
-    bq_problem *p = s->p;
-    delete s;
-    bq_problem_unref(p);
-    return BQ_OK;
-}
-
-// bq_smo_create (Cw == nullptr: the one box C) and bq_smo_create_weighted (Cw: n boxes, C is not used)
-static int smo_create(bq_problem *p, int task, const double *y, double C, const double *Cw, double epsilon, double tol,
-                      bq_smo **out) {
-    BQ_ARG(task == BQ_SVC || task == BQ_SVR, "task must be BQ_SVC or BQ_SVR");
-    BQ_ARG(p->kernel >= 0 && !p->streamed, "SMO needs a kernel-built problem with a resident Gram panel");
-    if (Cw) {
-        BQ_ARG(!p->compact, "per-row boxes need a plain f64 / f32 panel");
-        for (int64_t i = 0; i < p->n; ++i) BQ_ARG(std::isfinite(Cw[i]) && Cw[i] > 0.0, "every row's box must be finite and > 0");
-    } else {
-        BQ_ARG(C > 0.0, "C must be > 0");
-    }
-    BQ_ARG(epsilon >= 0.0, "epsilon must be >= 0");
-    BQ_ARG(tol > 0.0, "tol must be > 0");
-    if (p->ctx->world > 1) {
-        bq_set_error("SMO walks the samples sequentially over the whole panel: use a single-rank context (replicas only)");
-        return BQ_ERR_BADARG;
-    }
-    bq_ctx *c = p->ctx;
-    const int64_t n = p->n;
-    int64_t first_pos = -1, first_neg = -1;
-    if (task == BQ_SVC) {
-        for (int64_t i = 0; i < n; ++i) {
-            BQ_ARG(y[i] == 1.0 || y[i] == -1.0, "labels must be +1 / -1");
-            if (y[i] == 1.0 && first_pos < 0) first_pos = i;
-            if (y[i] == -1.0 && first_neg < 0) first_neg = i;
-        }
-        BQ_ARG(first_pos >= 0 && first_neg >= 0, "both classes are needed");
-    }
-    BQ_HIP(hipSetDevice(c->device));
-    bq_smo *s = new bq_smo();
-    s->p = p;
-    p->refs += 1;
-    s->task = task;
-    s->n = n;
-    s->C = C;
-    s->eps = epsilon;
-    s->tol = tol;
-    hipError_t e = hipSuccess;
-    for (double **v : {&s->y, &s->a, &s->am, &s->err}) e = bq_dev_zeroed(e, s->mem, v, n, c->stream);
-    if (e == hipSuccess) e = s->mem.dev(&s->nz, n);
-    if (e == hipSuccess) e = s->mem.dev(&s->cf, n);
-    if (e == hipSuccess) e = s->mem.dev(&s->sc, 1);
-    if (e == hipSuccess && Cw) e = s->mem.dev(&s->Cw, n);
-    if (e == hipSuccess && Cw) e = hipMemcpyAsync(s->Cw, Cw, sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-    // helper workgroups of the full sweeps: hook smo_helpers (0 = the walker alone).  Default 48: measured at n = 100 000
-    // the sweeps take 455 / 357 / 344 / 355 / 365 / 380 / 433 / 479 ms with 16 / 32 / 48 / 64 / 96 / 128 / 192 / 255
-    // helpers — past ~48 the extra pollers of the control line cost the walker more than the extra gather rate brings
-    int cus = 0;
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    s->helpers = std::min(48, cus / 4);
-    s->helpers = (int)bq_hook_value("smo_helpers", (double)s->helpers);
-    s->helpers = std::max(0, std::min(s->helpers, cus - 1));
-    if (s->helpers < SMO_T / 64) s->helpers = 0;   // the first batch after a pair step wants one CU per sample
-    if (e == hipSuccess && s->helpers) {
-        const unsigned int ctl0[SPEC_WORDS] = {2u};   // version 2: a zeroed result (version 0) never matches
-        e = s->mem.dev(&s->ctl, SPEC_WORDS);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, c->stream);
-        if (n * 16 >= ((int64_t)1 << 31)) e = hipErrorInvalidValue;   // 32-bit byte offsets of the result buffer
-        if (e == hipSuccess) s->spec_res = s->mem.dev<smo_u4>(n);
-        if (e == hipSuccess) e = s->mem.error();
-        if (e == hipSuccess) e = hipMemsetAsync(s->spec_res, 0, (size_t)16 * n, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // ctl0 lives on this stack frame
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(s->y, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-    memset(&s->host, 0, sizeof(s->host));
-    s->host.sweep_all = 1;
-    if (task == BQ_SVC) {   // smo.py:119-128
-        s->host.b_up = -1.0;
-        s->host.b_low = 1.0;
-        s->host.i_up = first_pos;
-        s->host.i_low = first_neg;
-        const double m1 = -1.0, p1 = 1.0;
-        if (e == hipSuccess) e = hipMemcpyAsync(s->err + first_pos, &m1, sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->err + first_neg, &p1, sizeof(double), hipMemcpyHostToDevice, c->stream);
-    } else {                // smo.py:442-445
-        s->host.b_up = y[0] + epsilon;
-        s->host.b_low = y[0] - epsilon;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(s->sc, &s->host, sizeof(bq_smo_scal), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        bq_set_error("SMO setup failed: %s", hipGetErrorString(e));
-        bq_smo_destroy(s);
-        return BQ_ERR_HIP;
-    }
-    *out = s;
-    return BQ_OK;
-}
-
-extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C, double epsilon, double tol,
-                             bq_smo **out) {
-    BQ_ARG(p && y && out, "NULL argument");
-    return smo_create(p, task, y, C, nullptr, epsilon, tol, out);
-}
-
-extern "C" int bq_smo_create_weighted(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
-                                      bq_smo **out) {
-    BQ_ARG(p && y && Cw && out, "NULL argument");
-    return smo_create(p, task, y, 0.0, Cw, epsilon, tol, out);
-}
-
-extern "C" int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, int *finished) {
-    BQ_ARG(s && outer_iters && finished, "NULL argument");
-    BQ_ARG(max_outer > 0, "max_outer must be > 0");
-    bq_problem *p = s->p;
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    for (int64_t k = 0; k < max_outer && !s->host.finished; ++k) {
-        // full sweeps take the helper workgroups along; free-set sweeps walk the (short) support list alone
-        const int helpers = s->host.sweep_all ? s->helpers : 0;
-        const SmoSpec P{s->ctl, (smo_u4 *)s->spec_res, (unsigned int)(16 * s->n), helpers ? ++s->epoch : 0u, helpers};
-        const dim3 grid(1 + helpers);
-        const SupGlobal G{s->nz, s->cf};
-        const int64_t ld = p->symmetric ? 0 : p->ld;
-        if (s->Cw) {   // per-row boxes: plain panels only (checked at creation)
-            if (s->task == BQ_SVC) {
-                if (p->storage == BQ_F64)
-                    smo_svc_rows_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y,
-                                                                                s->a, s->err, G, s->Cw, s->tol, s->sc, P);
-                else
-                    smo_svc_rows_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y,
-                                                                              s->a, s->err, G, s->Cw, s->tol, s->sc, P);
-            } else {
-                if (p->storage == BQ_F64)
-                    smo_svr_rows_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y,
-                                                                                s->a, s->am, s->err, G, s->Cw, s->eps, s->tol, s->sc, P);
-                else
-                    smo_svr_rows_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y,
-                                                                              s->a, s->am, s->err, G, s->Cw, s->eps, s->tol, s->sc, P);
-            }
-        } else if (s->task == BQ_SVC) {
-            if (p->compact)
-                smo_svc_kernel<bq_c7><<<grid, SMO_T, 0, c->stream>>>(KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, s->n, s->y,
-                                                                      s->a, s->err, G, s->C, s->tol, s->sc, P);
-            else if (p->storage == BQ_F64)
-                smo_svc_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y, s->a,
-                                                                       s->err, G, s->C, s->tol, s->sc, P);
-            else
-                smo_svc_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y, s->a,
-                                                                     s->err, G, s->C, s->tol, s->sc, P);
-        } else {
-            if (p->compact)
-                smo_svr_kernel<bq_c7><<<grid, SMO_T, 0, c->stream>>>(KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, s->n, s->y,
-                                                                      s->a, s->am, s->err, G, s->C, s->eps, s->tol, s->sc, P);
-            else if (p->storage == BQ_F64)
-                smo_svr_kernel<double><<<grid, SMO_T, 0, c->stream>>>(KView<double>{(const double *)p->panel, ld}, s->n, s->y, s->a,
-                                                                       s->am, s->err, G, s->C, s->eps, s->tol, s->sc, P);
-            else
-                smo_svr_kernel<float><<<grid, SMO_T, 0, c->stream>>>(KView<float>{(const float *)p->panel, ld}, s->n, s->y, s->a,
-                                                                     s->am, s->err, G, s->C, s->eps, s->tol, s->sc, P);
-        }
-        BQ_HIP(hipGetLastError());
-        BQ_HIP(hipMemcpyAsync(&s->host, s->sc, sizeof(bq_smo_scal), hipMemcpyDeviceToHost, c->stream));
-        BQ_HIP(hipStreamSynchronize(c->stream));
-        if (s->host.err_flag) {
-            bq_set_error("SMO reached an unexpected status (no threshold index)");   // smo.py:270-271, :756
-            return BQ_ERR_NONFINITE;
-        }
-    }
-    *outer_iters = s->host.outer;
-    *finished = s->host.finished;
-    return BQ_OK;
-}
-
-extern "C" int bq_smo_get(bq_smo *s, int what, double *out) {
-    BQ_ARG(s && out, "NULL argument");
-    bq_ctx *c = s->p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
-    switch (what) {
-        case BQ_SMO_ALPHAS:
-            BQ_HIP(hipMemcpyAsync(out, s->a, sizeof(double) * s->n, hipMemcpyDeviceToHost, c->stream));
-            if (s->task == BQ_SVR)
-                BQ_HIP(hipMemcpyAsync(out + s->n, s->am, sizeof(double) * s->n, hipMemcpyDeviceToHost, c->stream));
-            break;
-        case BQ_SMO_ERRORS:
-            BQ_HIP(hipMemcpyAsync(out, s->err, sizeof(double) * s->n, hipMemcpyDeviceToHost, c->stream));
-            break;
-        case BQ_SMO_SCALARS:
-            out[0] = s->host.b_up;
-            out[1] = s->host.b_low;
-            out[2] = (double)s->host.i_up;
-            out[3] = (double)s->host.i_low;
-            out[4] = (double)s->host.steps;
-            out[5] = s->task == BQ_SVC ? -(s->host.b_low + s->host.b_up) / 2 : (s->host.b_low + s->host.b_up) / 2;
-            break;
-        case BQ_SMO_STATS: {
-            unsigned int w[SPEC_WORDS] = {0};
-            if (s->ctl) BQ_HIP(hipMemcpy(w, s->ctl, sizeof(w), hipMemcpyDeviceToHost));
-            out[0] = (double)s->helpers;
-            out[1] = (double)w[SPEC_DELIVERED];
-            out[2] = (double)w[SPEC_REJ_HASH];
-            out[3] = (double)w[SPEC_REJ_CHK];
-            break;
-        }
-        default:
-            bq_set_error("bad argument: what");
-            return BQ_ERR_BADARG;
-    }
-    BQ_HIP(hipStreamSynchronize(c->stream));
-    return BQ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// batched SMO: k columns, one walker workgroup each (smo_*_batch_kernel)
+// C ABI: the batched solver — k columns, one walker workgroup each (smo_batch_kernel)
 // ---------------------------------------------------------------------------------------------------------------
 struct bq_msmo {
     bq_problem *p = nullptr;
@@ -1765,8 +1442,9 @@ extern "C" int bq_msmo_destroy(bq_msmo *s) {
 }
 
 // bq_msmo_create (CW == nullptr: C holds one box per column) and bq_msmo_create_weighted (CW: k x n boxes, C == nullptr)
+// min_rows: 2 for the batched entry points; the single solver takes a one-row regression problem as it always did
 static int msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *CW, const double *epsilon,
-                       double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
+                       double tol, const int64_t *row_ptr, const int32_t *rows, int64_t min_rows, bq_msmo **out) {
     BQ_ARG(task == BQ_SVC || task == BQ_SVR, "task must be BQ_SVC or BQ_SVR");
     BQ_ARG(k >= 1, "k must be >= 1");
     BQ_ARG(p->kernel >= 0 && !p->streamed, "SMO needs a kernel-built problem with a resident Gram panel");
@@ -1779,7 +1457,7 @@ static int msmo_create(bq_problem *p, int task, int k, const double *Y, const do
     }
     bq_ctx *c = p->ctx;
     const int64_t n = p->n;
-    BQ_ARG(n >= 2, "a column needs two rows");
+    BQ_ARG(n >= min_rows, "a column needs two rows");
     std::vector<bq_smo_scal> host((size_t)k);
     std::vector<int64_t> first((size_t)2 * k, -1);   // BQ_SVC: the first +1 / -1 row of the column's list
     for (int col = 0; col < k; ++col) {
@@ -1787,7 +1465,7 @@ static int msmo_create(bq_problem *p, int task, int k, const double *Y, const do
         BQ_ARG(epsilon == nullptr || epsilon[col] >= 0.0, "epsilon must be >= 0");
         const double *y = Y + (int64_t)col * n;
         const int64_t lo = row_ptr ? row_ptr[col] : 0, m = row_ptr ? row_ptr[col + 1] - lo : n;
-        BQ_ARG(lo >= 0 && m >= 2, "a row list needs two rows");
+        BQ_ARG(lo >= 0 && m >= min_rows, "a row list needs two rows");
         for (int64_t q = 0; q < m; ++q) {
             const int64_t i = rows ? (int64_t)rows[lo + q] : q;
             BQ_ARG(i >= 0 && i < n, "a listed row lies outside the panel");
@@ -1885,39 +1563,59 @@ static int msmo_create(bq_problem *p, int task, int k, const double *Y, const do
 extern "C" int bq_msmo_create(bq_problem *p, int task, int k, const double *Y, const double *C, const double *epsilon,
                               double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
     BQ_ARG(p && Y && C && out, "NULL argument");
-    return msmo_create(p, task, k, Y, C, nullptr, epsilon, tol, row_ptr, rows, out);
+    return msmo_create(p, task, k, Y, C, nullptr, epsilon, tol, row_ptr, rows, 2, out);
 }
 
 extern "C" int bq_msmo_create_weighted(bq_problem *p, int task, int k, const double *Y, const double *CW, const double *epsilon,
                                        double tol, const int64_t *row_ptr, const int32_t *rows, bq_msmo **out) {
     BQ_ARG(p && Y && CW && out, "NULL argument");
-    return msmo_create(p, task, k, Y, nullptr, CW, epsilon, tol, row_ptr, rows, out);
+    return msmo_create(p, task, k, Y, nullptr, CW, epsilon, tol, row_ptr, rows, 2, out);
 }
 
-template <typename T>
-static void msmo_rows_launch(const bq_msmo *s, const KView<T> &K, const SmoBatch &Bt, int live, hipStream_t st) {
-    if (s->task == BQ_SVC)
-        smo_svc_rows_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->CW, s->tol);
+// The one place a kernel instantiation is picked: KView<T> from the panel's layout, the task and the box type from the
+// solver.  launch(Task{}, Box{}, K) — the task and the box as types only.  Per-row boxes come with plain panels only
+// (refused at creation), so no bq_c7 walker with BoxRows is built: a solver that asked for one is an error here, not a
+// launch that silently does not happen.
+template <typename F>
+static int smo_dispatch(const bq_msmo *s, F &&launch) {
+    const bq_problem *p = s->p;
+    const int64_t ld = p->symmetric ? 0 : p->ld;
+    bool launched = false;
+    auto with_panel = [&](auto K) {
+        auto with_task = [&](auto task) {
+            if (!s->CW)
+                launch(task, BoxScalar{}, K);
+            else if constexpr (!std::is_same_v<typename decltype(K)::elem, bq_c7>)
+                launch(task, BoxRows{}, K);
+            else
+                return;
+            launched = true;
+        };
+        if (s->task == BQ_SVC)
+            with_task(SvcTask{});
+        else
+            with_task(SvrTask{});
+    };
+    if (p->compact)
+        with_panel(KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld});
+    else if (p->storage == BQ_F64)
+        with_panel(KView<double>{(const double *)p->panel, ld});
     else
-        smo_svr_rows_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->CW, s->tol);
+        with_panel(KView<float>{(const float *)p->panel, ld});
+    BQ_ARG(launched, "per-row boxes need a plain f64 / f32 panel");
+    return BQ_OK;
 }
 
-template <typename T>
-static void msmo_launch(const bq_msmo *s, const KView<T> &K, const SmoBatch &Bt, int live, hipStream_t st) {
-    if (s->task == BQ_SVC)
-        smo_svc_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->tol);
-    else
-        smo_svr_batch_kernel<T><<<dim3(live), SMO_T, 0, st>>>(K, s->n, Bt, s->tol);
+static SmoBatch smo_batch_of(const bq_msmo *s) {
+    return SmoBatch{s->live, s->Y, s->A, s->AM, s->ERR, s->NZ, s->CF, s->C, s->eps, s->CW, s->sc, s->row_ptr, s->rows};
 }
 
 extern "C" int bq_msmo_run(bq_msmo *s, int64_t max_outer, int64_t *outer, int *finished, int *failed) {
     BQ_ARG(s && outer && finished && failed, "NULL argument");
     BQ_ARG(max_outer > 0, "max_outer must be > 0");
-    bq_problem *p = s->p;
-    bq_ctx *c = p->ctx;
+    bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
-    const SmoBatch Bt{s->live, s->Y, s->A, s->AM, s->ERR, s->NZ, s->CF, s->C, s->eps, s->sc, s->row_ptr, s->rows};
-    const int64_t ld = p->symmetric ? 0 : p->ld;
+    const SmoBatch Bt = smo_batch_of(s);
     for (int64_t it = 0; it < max_outer; ++it) {
         // finished columns are not launched: one workgroup per column still running, one outer iteration each
         s->live_host.clear();
@@ -1926,16 +1624,11 @@ extern "C" int bq_msmo_run(bq_msmo *s, int64_t max_outer, int64_t *outer, int *f
         const int live = (int)s->live_host.size();
         if (live == 0) break;
         BQ_HIP(hipMemcpyAsync(s->live, s->live_host.data(), sizeof(int) * live, hipMemcpyHostToDevice, c->stream));
-        if (s->CW && p->storage == BQ_F64)   // per-row boxes: plain panels only (checked at creation)
-            msmo_rows_launch(s, KView<double>{(const double *)p->panel, ld}, Bt, live, c->stream);
-        else if (s->CW)
-            msmo_rows_launch(s, KView<float>{(const float *)p->panel, ld}, Bt, live, c->stream);
-        else if (p->compact)
-            msmo_launch(s, KView<bq_c7>{bq_c7_view(p->panel, p->panel_elems), ld}, Bt, live, c->stream);
-        else if (p->storage == BQ_F64)
-            msmo_launch(s, KView<double>{(const double *)p->panel, ld}, Bt, live, c->stream);
-        else
-            msmo_launch(s, KView<float>{(const float *)p->panel, ld}, Bt, live, c->stream);
+        const int rc = smo_dispatch(s, [&](auto task, auto box, auto K) {
+            smo_batch_kernel<decltype(task), typename decltype(K)::elem, decltype(box)>
+                <<<dim3(live), SMO_T, 0, c->stream>>>(K, s->n, Bt, s->tol);
+        });
+        if (rc != BQ_OK) return rc;
         BQ_HIP(hipGetLastError());
         BQ_HIP(hipMemcpyAsync(s->host.data(), s->sc, sizeof(bq_smo_scal) * s->k, hipMemcpyDeviceToHost, c->stream));
         BQ_HIP(hipStreamSynchronize(c->stream));
@@ -1981,3 +1674,122 @@ extern "C" int bq_msmo_get(bq_msmo *s, int col, int what, double *out) {
     BQ_HIP(hipStreamSynchronize(c->stream));
     return BQ_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// C ABI: the single solver — a one-column batch on all rows, walked by smo_kernel with the helper workgroups of the full
+// sweeps (see "Helpers" above)
+// ---------------------------------------------------------------------------------------------------------------
+struct bq_smo {
+    bq_msmo *m = nullptr;              // the dual and all the walker's state; it holds the reference to the problem
+    bq_owner mem;                      // the two device buffers below
+    unsigned int *ctl = nullptr;       // SPEC_* words
+    void *spec_res = nullptr;          // n x 16 bytes: {bit pattern of sum_q c_q K[s][idx_q] formed by a helper, the list
+                                       // version it was formed under, checksum of the bits} — ONE 16-byte store / load
+    unsigned int epoch = 0;            // launch counter
+    int helpers = 0;                   // helper workgroups per full-sweep launch (0: none)
+};
+
+extern "C" int bq_smo_destroy(bq_smo *s) {
+    if (s == nullptr) return BQ_OK;
+    bq_msmo *m = s->m;
+    hipSetDevice(m->p->ctx->device);
+    hipStreamSynchronize(m->p->ctx->stream);   // no launch is still using the helpers' buffers
+    delete s;
+    return bq_msmo_destroy(m);   // the column's buffers, and the one reference to the problem
+}
+
+// bq_smo_create (Cw == nullptr: the one box *C) and bq_smo_create_weighted (Cw: n boxes, C == nullptr)
+static int smo_create(bq_problem *p, int task, const double *y, const double *C, const double *Cw, double epsilon, double tol,
+                      bq_smo **out) {
+    bq_msmo *m = nullptr;
+    const int rc = msmo_create(p, task, 1, y, C, Cw, &epsilon, tol, nullptr, nullptr, 1, &m);
+    if (rc != BQ_OK) return rc;
+    bq_ctx *c = p->ctx;
+    const int64_t n = p->n;
+    bq_smo *s = new bq_smo();
+    s->m = m;
+    // helper workgroups of the full sweeps: hook smo_helpers (0 = the walker alone).  Default 48: measured at n = 100 000
+    // the sweeps take 455 / 357 / 344 / 355 / 365 / 380 / 433 / 479 ms with 16 / 32 / 48 / 64 / 96 / 128 / 192 / 255
+    // helpers — past ~48 the extra pollers of the control line cost the walker more than the extra gather rate brings
+    int cus = 0;
+    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+    s->helpers = std::min(48, cus / 4);
+    s->helpers = (int)bq_hook_value("smo_helpers", (double)s->helpers);
+    s->helpers = std::max(0, std::min(s->helpers, cus - 1));
+    if (s->helpers < SMO_T / 64) s->helpers = 0;   // the first batch after a pair step wants one CU per sample
+    if (e == hipSuccess && s->helpers) {
+        const unsigned int ctl0[SPEC_WORDS] = {2u};   // version 2: a zeroed result (version 0) never matches
+        e = s->mem.dev(&s->ctl, SPEC_WORDS);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, c->stream);
+        if (n * 16 >= ((int64_t)1 << 31)) e = hipErrorInvalidValue;   // 32-bit byte offsets of the result buffer
+        if (e == hipSuccess) s->spec_res = s->mem.dev<smo_u4>(n);
+        if (e == hipSuccess) e = s->mem.error();
+        if (e == hipSuccess) e = hipMemsetAsync(s->spec_res, 0, (size_t)16 * n, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // ctl0 lives on this stack frame
+    }
+    if (e != hipSuccess) {
+        bq_set_error("SMO setup failed: %s", hipGetErrorString(e));
+        bq_smo_destroy(s);   // both owners, and the reference msmo_create took
+        return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    *out = s;
+    return BQ_OK;
+}
+
+extern "C" int bq_smo_create(bq_problem *p, int task, const double *y, double C, double epsilon, double tol,
+                             bq_smo **out) {
+    BQ_ARG(p && y && out, "NULL argument");
+    return smo_create(p, task, y, &C, nullptr, epsilon, tol, out);
+}
+
+extern "C" int bq_smo_create_weighted(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
+                                      bq_smo **out) {
+    BQ_ARG(p && y && Cw && out, "NULL argument");
+    return smo_create(p, task, y, nullptr, Cw, epsilon, tol, out);
+}
+
+extern "C" int bq_smo_run(bq_smo *s, int64_t max_outer, int64_t *outer_iters, int *finished) {
+    BQ_ARG(s && outer_iters && finished, "NULL argument");
+    BQ_ARG(max_outer > 0, "max_outer must be > 0");
+    bq_msmo *m = s->m;
+    bq_ctx *c = m->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    bq_smo_scal &host = m->host[0];
+    const SmoBatch Bt = smo_batch_of(m);
+    for (int64_t k = 0; k < max_outer && !host.finished; ++k) {
+        // full sweeps take the helper workgroups along; free-set sweeps walk the (short) support list alone
+        const int helpers = host.sweep_all ? s->helpers : 0;
+        const SmoSpec P{s->ctl, (smo_u4 *)s->spec_res, (unsigned int)(16 * m->n), helpers ? ++s->epoch : 0u, helpers};
+        const int rc = smo_dispatch(m, [&](auto task, auto box, auto K) {
+            smo_kernel<decltype(task), typename decltype(K)::elem, decltype(box)>
+                <<<dim3(1 + helpers), SMO_T, 0, c->stream>>>(K, m->n, m->tol, P, Bt);
+        });
+        if (rc != BQ_OK) return rc;
+        BQ_HIP(hipGetLastError());
+        BQ_HIP(hipMemcpyAsync(&host, m->sc, sizeof(bq_smo_scal), hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+        if (host.err_flag) {
+            bq_set_error("SMO reached an unexpected status (no threshold index)");   // smo.py:270-271, :756
+            return BQ_ERR_NONFINITE;
+        }
+    }
+    *outer_iters = host.outer;
+    *finished = host.finished;
+    return BQ_OK;
+}
+
+extern "C" int bq_smo_get(bq_smo *s, int what, double *out) {
+    BQ_ARG(s && out, "NULL argument");
+    if (what != BQ_SMO_STATS) return bq_msmo_get(s->m, 0, what, out);
+    bq_ctx *c = s->m->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    unsigned int w[SPEC_WORDS] = {0};
+    if (s->ctl) BQ_HIP(hipMemcpy(w, s->ctl, sizeof(w), hipMemcpyDeviceToHost));
+    out[0] = (double)s->helpers;
+    out[1] = (double)w[SPEC_DELIVERED];
+    out[2] = (double)w[SPEC_REJ_HASH];
+    out[3] = (double)w[SPEC_REJ_CHK];
+    BQ_HIP(hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+

@@ -452,3 +452,68 @@ def test_search_falls_back_when_a_fold_misses_a_class(amd):
     both.batch_smo = True
     both.fit(X, y)
     assert both.batched_ is True and both.smo_ is True and both.n_iter_.shape == (2, 2, 3) and (both.n_iter_ > 0).all()
+
+
+# ---- 9. the batched walkers no other test launches: the compact 7-byte panel, and regression on the fp32 panel ---------------------
+COVER_C, COVER_EPS = [0.3, 1., 3.], [0.05, 0.1, 0.2]
+COVER_CASES = [('svc', 'compact', False), ('svr', 'compact', False), ('svr', 'f32', False), ('svr', 'f32', True)]
+
+
+def _cover_draw(task):
+    """300 x 6 standard normal rows (two 256-row tiles, the second ragged) and three label / target rows along random directions"""
+    rs = np.random.RandomState(0)
+    X = rs.standard_normal((300, 6))
+    W = rs.standard_normal((6, 3))
+    if task == 'svc':
+        return X, np.where(X @ W + 0.5 * rs.standard_normal((300, 3)) > 0, 1., -1.).T.copy()
+    return X, (np.sin(X @ W) + 0.3 * rs.standard_normal((300, 3))).T.copy()
+
+
+@pytest.mark.parametrize('task,panel,boxes', COVER_CASES, ids=['%s-%s%s' % (t, p, '-rowboxes' if b else '') for t, p, b in COVER_CASES])
+def test_batched_walkers_on_compact_and_fp32_panels_follow_the_oracle(amd, task, panel, boxes):
+    """`smo_batch_kernel` for (classification, 7-byte panel), (regression, 7-byte panel), (regression, fp32 panel) and (regression,
+    fp32 panel, per-row boxes — a constant vector per column, which walks the scalar box's path): three columns with C = 0.3, 1, 3
+    (epsilon = 0.05, 0.1, 0.2), each held bit for bit to oracle/smo_oracle.py (tie='index', dot='tree') on the device's own Gram
+    entries: multipliers, error cache, thresholds, outer iterations, pair steps.
+
+    The oracle alone, on the CPU's Gram matrix of the draw (rounded to fp32 for the fp32 cases), takes per column
+    (outer iterations, pair steps, support vectors):
+      svc compact   (19, 489, 171)  (26, 855, 132)   (34, 1337, 101)
+      svr compact   (23, 644, 288)  (37, 1354, 272)  (69, 4388, 210)
+      svr fp32      (23, 765, 286)  (31, 1796, 271)  (82, 7973, 197)
+    so both sweep kinds occur and every column moves.  On the device's Gram entries, which differ from NumPy's in the last bits, the
+    oracle's compact runs took (17, 492, 171) (29, 888, 132) (25, 1085, 101) and (20, 619, 288) (33, 1293, 271) (76, 4970, 209),
+    its fp32 runs the figures above; the test re-checks the floor (3 outer iterations, 20 steps, 5 support vectors) on the run it
+    compares with and prints the figures."""
+    from types import SimpleNamespace
+    import smo_list_reference as lr
+    from oracle import smo_oracle as smo
+    from optiml_amd import _lib
+    from optiml_amd.ml.svm._batched import solve_batched_smo
+    from optiml_amd.ml.svm.kernels import GaussianKernel
+    from optiml_amd.opti import KernelQuadratic
+    X, Y = _cover_draw(task)
+    n = 300
+    kw, esz, gamma = (dict(compact=True), 7, lr.compact_gamma(X)) if panel == 'compact' else (dict(storage='f32'), 4, lr.rbf_gamma(X))
+    kern = GaussianKernel(gamma=gamma)
+    if task == 'svc':
+        quad = KernelQuadratic(X, -np.ones(n), 'svc', kern, y=Y[0], rank_one=False, **kw)
+    else:
+        quad = KernelQuadratic(X, np.hstack((-Y[0], Y[0])) + 0.1, 'svr', kern, rank_one=False, **kw)
+    # two tile rows of 256: three 256 x 256 tiles of 7 (the panel is in fact compact) or 4 bytes per element
+    assert quad.device_problem().layout()['panel_bytes'] == 3 * 65536 * esz
+    Kdev = quad.gram()
+    eps = None if task == 'svc' else COVER_EPS
+    res = solve_batched_smo(quad.device_problem(), _lib.SVC if task == 'svc' else _lib.SVR, Y, COVER_C, eps, 1e-3,
+                            boxes=np.asarray(COVER_C)[:, None] * np.ones((3, n)) if boxes else None)
+    quad.release()
+    for c, r in enumerate(res):
+        if task == 'svc':
+            ref = smo.smo_svc(Kdev, Y[c], C=COVER_C[c], tol=1e-3, tie='index', dot='tree')
+            n_sv, fields = np.count_nonzero(ref['alphas']), ('alphas',)
+        else:
+            ref = smo.smo_svr(Kdev, Y[c], C=COVER_C[c], epsilon=COVER_EPS[c], tol=1e-3, tie='index', dot='tree')
+            n_sv, fields = np.count_nonzero(ref['alphas_p'] + ref['alphas_n']), ('alphas_p', 'alphas_n')
+        print('%s %s column %d: oracle (outer, steps, support vectors) = (%d, %d, %d)' % (task, panel, c, ref['iter'], ref['steps'], n_sv))
+        assert ref['finished'] and ref['iter'] >= 3 and ref['steps'] >= 20 and n_sv >= 5, (c, ref['iter'], ref['steps'], n_sv)
+        _same(r, SimpleNamespace(**ref), fields + ('errors', 'b', 'b_up', 'b_low', 'iter', 'steps'), (task, panel, c))
