@@ -194,6 +194,13 @@ int bq_ctx_set_collective_timeout(bq_ctx *ctx, double seconds);
  * one GPU (BQ_ERR_RCCL when it fired).  behind_collective == 0: nothing but this rank's own work is ahead of the wait, which the
  * watchdog must leave alone however long it lasts (a factorisation, a preconditioner rebuild). */
 int bq_ctx_probe_stall(bq_ctx *ctx, double milliseconds, int behind_collective);
+/* the last-workgroup hand-off that closes every O(n) kernel of the single-problem solvers (csrc/bq_reduce.h), checked directly:
+ * `rounds` launches of `blocks` workgroups back to back on the stream; in each, every workgroup stores one partial that depends on
+ * (workgroup, round) and takes the ticket, and the workgroup that arrives last compares EVERY partial with its expected word.
+ * uneven != 0: a workgroup-dependent amount of arithmetic first.  bad_words: mismatches over all rounds (0 is the only correct
+ * answer); ticket_after: the ticket once the stream has drained (0: the last workgroup of every round set it back).  No workgroup
+ * waits for another, so the call ends whatever it finds. */
+int bq_ctx_probe_last_block(bq_ctx *ctx, int blocks, int rounds, int uneven, int64_t *bad_words, int *ticket_after);
 /* row block [begin,end) of an n-row panel owned by `rank` out of `world` (pure arithmetic): equal 128-aligned
  * blocks for dense panels; bq_sym_row_block: the balanced triangular partition (256-aligned) of the symmetric
  * kernel panels, whose ranks stream only the tiles on/below the diagonal */

@@ -86,6 +86,7 @@ PROTOTYPES = {
     'bq_ctx_set_placement_budget': (C.c_int, [_vp, C.c_double, C.c_double, C.c_double]),
     'bq_ctx_release_held_memory': (C.c_int, [_vp, C.POINTER(_i64)]),
     'bq_ctx_probe_stall': (C.c_int, [_vp, C.c_double, C.c_int]),
+    'bq_ctx_probe_last_block': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _ip]),
     'bq_row_block': (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     'bq_sym_row_block': (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     'bq_problem_create_dense': (C.c_int, [_vp, _i64, _dp, _dp, C.c_int, C.POINTER(_vp)]),

@@ -31,18 +31,12 @@
 #include "bq_al_update.h"
 #include "bq_epilogue.h"
 
-#define VEC_LOOP(i)                                                             \
-    const int64_t _base = (int64_t)blockIdx.x * BQ_VEC_TILE + threadIdx.x;      \
-    _Pragma("unroll") for (int _j = 0; _j < BQ_VEC_ITEMS; ++_j)                 \
-        for (int64_t i = _base + (int64_t)_j * BQ_VEC_BLOCK, _once = 1; _once; _once = 0)
-
-static inline dim3 vgrid(int64_t ldN) { return dim3((unsigned)(ldN / BQ_VEC_TILE)); }
 
 // nesterov: x += momentum * previous step, before the gradient is taken (gradient_descent.py:78-81 and the like)
 __global__ void al_jump_kernel(int64_t N, bq_al_vecs V, double mom_const, const bq_scal *sc) {
     if (sc->done) return;
     const double mom = al_sched(V.mom_sched, V.sched_len, sc->iter, mom_const);
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) V.x[i] = V.x[i] + __dmul_rn(mom, V.step[i]);
     }
 }
@@ -119,7 +113,7 @@ int bq_al_iterate(bq_solver *s) {
     const int *done = &s->sc->done;
     const bq_al_params &prm = al->prm;
     const bool nesterov = prm.momentum_type == BQ_MOM_NESTEROV;
-    if (nesterov) al_jump_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, al->V, prm.momentum, s->sc);
+    if (nesterov) al_jump_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, al->V, prm.momentum, s->sc);
     // the product's input: x itself (BQ_PLAIN), what the previous update kernel left in p->w (BQ_SVC, nothing has moved x since),
     // else the structure map of x by a launch of its own
     const double *w = al->V.x;

@@ -2,19 +2,7 @@
 // batched solver's mal_update_kernel (bq_msolver.hip): ONE copy of the body, a column of the batch is an ordinary AL bq_solver.
 #pragma once
 #include "bq_common.h"
-
-// the block that takes the last ticket of a launch finishes the reduction and takes the scalar decisions in the same
-// kernel (same fixed-order final sums as a separate one-block kernel: results do not depend on which block is last)
-__device__ __forceinline__ bool al_last_block(unsigned int *ticket) {
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-    }
-    __syncthreads();
-    if (last) __threadfence();
-    return last != 0;
-}
+#include "bq_reduce.h"
 
 // value of a schedule at the current iteration (the last entry continues), or the constant
 __device__ __forceinline__ double al_sched(const double *sched, long long len, long long it, double constant) {
@@ -155,10 +143,7 @@ __device__ __forceinline__ void al_update_body(int64_t N, int64_t ldN, bq_al_vec
         }
     }
     if (last) {   // uniform: no step after the last evaluation; the flag is consumed by the block that finishes last
-        if (al_last_block(&sc->ticket[1]) && threadIdx.x == 0) {
-            sc->al_last = 0;
-            sc->ticket[1] = 0;
-        }
+        if (bq_last_block(&sc->ticket[1], gridDim.x) && threadIdx.x == 0) sc->al_last = 0;
         return;
     }
     if (i == 0) sc->al_pending = 1;   // read by the NEXT kernel (the closing kernel of the next product, or al_flush_kernel)

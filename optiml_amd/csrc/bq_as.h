@@ -14,19 +14,13 @@
 
 #include "bq_chol.h"
 #include "bq_qelem.h"
+#include "bq_reduce.h"
 #define BQ_EXP_ATTR __device__ __forceinline__
 #define BQ_EXP_LOINT(t) __double2loint(t)
 #include "bq_exp.h"
 
 #define ACT_TOL 1e-12
 constexpr int AS_SCHUR_MAX = 1536;   // capacity of the update slots
-
-#define VEC_LOOP(i)                                                             \
-    const int64_t _base = (int64_t)blockIdx.x * BQ_VEC_TILE + threadIdx.x;      \
-    _Pragma("unroll") for (int _j = 0; _j < BQ_VEC_ITEMS; ++_j)                 \
-        for (int64_t i = _base + (int64_t)_j * BQ_VEC_BLOCK, _once = 1; _once; _once = 0)
-
-static inline dim3 vgrid(int64_t ldN) { return dim3((unsigned)(ldN / BQ_VEC_TILE)); }
 
 // device-resident scalar recurrences of the conjugate-gradient inner solver
 struct as_cg_scal {
@@ -159,75 +153,17 @@ struct as_ws {
 };
 
 
-__device__ __forceinline__ double as_wsum_any(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double as_wmin(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-    return v;
-}
-
 // a record for the host: system-scope release store of its sequence number, after the data (as_ws::mail)
 __device__ __forceinline__ void as_post(int *flag, int seq) {
     __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// one wave; lane 0 opens the iteration's record, then (mailbox) the wave hands `ints` and the solver's scalars to the host
 // ---------------------------------------------------------------------------------------------------------------
-// The per-iteration O(N) steps, multi-block (round 2).  Their single-block predecessors walked N elements with 256
+// The per-iteration O(N) steps are multi-block (round 2).  Their single-block predecessors walked N elements with 256
 // threads: 35-110 us each at n = 20 000, four of them per iteration = 16 % of an ActiveSet iteration once the triangular
 // sweeps were fixed.  Same arithmetic, same results (minima, counts and index lists do not depend on the block order);
-// the last-finishing block of a launch closes the step (fixed-order final reduction over the per-block partials).
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool as_last_block_mb(unsigned int *ticket) {
-    __shared__ int last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();   // this block's partials are visible device-wide before the ticket is taken
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-    }
-    __syncthreads();
-    if (last) {
-        __threadfence();
-        if (threadIdx.x == 0) *ticket = 0u;
-    }
-    return last != 0;
-}
-
-__device__ __forceinline__ double as_wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double as_block_sum(double v, double *sh) {
-    v = as_wsum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double as_final_sum(const double *part, int64_t nblk, double *sh) {
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < nblk; i += BQ_VEC_BLOCK) a += part[i];
-    return as_block_sum(a, sh);
-}
-__device__ __forceinline__ bool as_last_block(unsigned int *ticket) {
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-    }
-    __syncthreads();
-    if (last) __threadfence();
-    return last != 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
+// the last-finishing block of a launch closes the step (bq_reduce.h).
+//
 // Short, index-ordered lists of the samples where a per-sample predicate holds (which variables moved since the previous outer
 // iteration), multi-block: pass 1 counts per block of 1024 samples and the last block to finish turns the counts into offsets
 // (the total and the "too many" verdict with them); pass 2 writes entry `offset + rank inside the block` when it is below the
@@ -238,16 +174,12 @@ __device__ __forceinline__ bool as_last_block(unsigned int *ticket) {
 __device__ __forceinline__ void as_list_count(int changed_bits, int *__restrict__ cnt, unsigned int *ticket, int *total_out) {
     // changed_bits: bit j = item j of this thread is in the list
     __shared__ int wt[4];
-    int c = __popc(changed_bits);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(&cnt[blockIdx.x], wt[0] + wt[1] + wt[2] + wt[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (as_last_block_mb(ticket) && threadIdx.x == 0) {
+    const int c = bq_block_sum((int)__popc(changed_bits), wt);
+    if (threadIdx.x == 0) bq_part_put(&cnt[blockIdx.x], c);
+    if (bq_last_block(ticket, gridDim.x) && threadIdx.x == 0) {
         int run = 0;
         for (unsigned int b = 0; b < gridDim.x; ++b) {
-            const int v = __hip_atomic_load(&cnt[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int v = bq_part_get(&cnt[b]);
             cnt[b] = run;
             run += v;
         }
@@ -277,7 +209,7 @@ __device__ __forceinline__ void as_list_positions(int changed_bits, const int *_
 }
 
 static __global__ void as_copy_kernel(int64_t N, const double *__restrict__ src, double *__restrict__ dst) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) dst[i] = src[i];
     }
 }
@@ -287,7 +219,7 @@ static __global__ void as_copy_kernel(int64_t N, const double *__restrict__ src,
 static __global__ void as_cand_fill_kernel(int64_t N, const unsigned char *__restrict__ mL, const unsigned char *__restrict__ mU,
                                     const double *__restrict__ lb, const double *__restrict__ ub, double *__restrict__ cand,
                                     int *__restrict__ ints) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) cand[i] = mU[i] ? ub[i] : (mL[i] ? lb[i] : 0.0);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) ints[2] = 1;

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(64) void as_top_kernel(bq_scal *sc, int *__restrict
 
 __global__ void as_make_z_kernel(int64_t N, const unsigned char *__restrict__ mL, const unsigned char *__restrict__ mU,
                                  const double *__restrict__ lb, const double *__restrict__ ub, double *__restrict__ z) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) z[i] = mU[i] ? ub[i] : (mL[i] ? lb[i] : 0.0);
     }
 }
@@ -89,7 +89,7 @@ __global__ void as_gather_rhs_kernel(const int *__restrict__ ints, const int *__
 // the iteration's snapshot of x and g in one launch
 __global__ void as_copy2_kernel(int64_t N, const double *__restrict__ a, double *__restrict__ da, const double *__restrict__ b,
                                 double *__restrict__ db) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             da[i] = a[i];
             db[i] = b[i];
@@ -104,16 +104,13 @@ __global__ __launch_bounds__(256) void as_count_free_kernel(int64_t N, const uns
                                                             int *__restrict__ ints, unsigned int *ticket) {
     __shared__ int wt[4];
     int c = 0;
-    VEC_LOOP(i) c += (i < N && !(mL[i] | mU[i])) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(&cnt[blockIdx.x], wt[0] + wt[1] + wt[2] + wt[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (as_last_block_mb(ticket) && threadIdx.x == 0) {
+    BQ_VEC_LOOP(i) c += (i < N && !(mL[i] | mU[i])) ? 1 : 0;
+    c = bq_block_sum(c, wt);
+    if (threadIdx.x == 0) bq_part_put(&cnt[blockIdx.x], c);
+    if (bq_last_block(ticket, gridDim.x) && threadIdx.x == 0) {
         int run = 0;
         for (unsigned int b = 0; b < gridDim.x; ++b) {
-            const int v = __hip_atomic_load(&cnt[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int v = bq_part_get(&cnt[b]);
             cnt[b] = run;
             run += v;
         }
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(256) void as_step_min_kernel(int64_t N, const unsig
                                                           double *part_s, bq_scal *sc, int chain) {
     __shared__ double sh[4], shs[4];
     double rmin = INFINITY, sgd = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N && !(mL[i] | mU[i])) {
             const double d = cand[i] - x[i];
             if (d > 0.0) rmin = fmin(rmin, (ub[i] - x[i]) / d);
@@ -175,36 +172,27 @@ __global__ __launch_bounds__(256) void as_step_min_kernel(int64_t N, const unsig
             if (chain == 1) sgd = fma(g0[i], d, sgd);
         }
     }
-    rmin = as_wmin(rmin);
-    if (chain) sgd = as_wsum_any(sgd);
-    if ((threadIdx.x & 63) == 0) {
-        sh[threadIdx.x >> 6] = rmin;
-        shs[threadIdx.x >> 6] = sgd;
-    }
+    bq_wave_put<bq_op_min>(rmin, sh);
+    if (chain) bq_wave_put<bq_op_sum>(sgd, shs);
     __syncthreads();
     if (threadIdx.x == 0) {
-        __hip_atomic_store(&part[blockIdx.x], fmin(fmin(sh[0], sh[1]), fmin(sh[2], sh[3])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (chain) __hip_atomic_store(&part_s[blockIdx.x], ((shs[0] + shs[1]) + shs[2]) + shs[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        bq_part_put(&part[blockIdx.x], bq_waves_min<4>(sh));
+        if (chain) bq_part_put(&part_s[blockIdx.x], bq_waves_sum<4>(shs));
     }
-    if (as_last_block_mb(&sc->ticket[0])) {
+    if (bq_last_block(&sc->ticket[0], gridDim.x)) {
         double m = INFINITY, a = 0.0;
         for (unsigned int b = threadIdx.x; b < gridDim.x; b += 256) {
-            m = fmin(m, __hip_atomic_load(&part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (chain) a += __hip_atomic_load(&part_s[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            m = fmin(m, bq_part_get(&part[b]));
+            if (chain) a += bq_part_get(&part_s[b]);
         }
-        m = as_wmin(m);
-        if (chain) a = as_wsum_any(a);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) {
-            sh[threadIdx.x >> 6] = m;
-            shs[threadIdx.x >> 6] = a;
-        }
+        bq_wave_put<bq_op_min>(m, sh);
+        if (chain) bq_wave_put<bq_op_sum>(a, shs);
         __syncthreads();
         if (threadIdx.x == 0) {
-            const double t = fmin(fmin(sh[0], sh[1]), fmin(sh[2], sh[3]));
+            const double t = bq_waves_min<4>(sh);
             sc->step = t;
             if (chain == 1) {
-                const double gd = sc->aux[0] * (((shs[0] + shs[1]) + shs[2]) + shs[3]);
+                const double gd = sc->aux[0] * bq_waves_sum<4>(shs);
                 sc->f = sc->f + (t - 0.5 * t * t) * gd;
             }
             if (chain) sc->aux[0] = sc->aux[0] * (1.0 - t);   // chain == 2: f comes from a product this time, the run goes on
@@ -214,7 +202,7 @@ __global__ __launch_bounds__(256) void as_step_min_kernel(int64_t N, const unsig
 __global__ void as_step_apply_kernel(int64_t N, const unsigned char *__restrict__ mL, const unsigned char *__restrict__ mU,
                                      const double *__restrict__ cand, double *__restrict__ x, const bq_scal *sc) {
     const double t = sc->step;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N && !(mL[i] | mU[i])) x[i] = x[i] + __dmul_rn(t, cand[i] - x[i]);
     }
 }
@@ -228,7 +216,7 @@ __global__ __launch_bounds__(256) void as_absorb_mb_kernel(int64_t N, unsigned c
                                                            int *__restrict__ cnt, bq_iter_stat *stats) {
     __shared__ int wl[4], wu[4];
     int nl = 0, nu = 0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N && !(mL[i] | mU[i])) {
             bool hit = false;
             // absorbed within the 1e-12 tolerance but further from the bound than the rounding of the step that brought it there (a
@@ -253,25 +241,18 @@ __global__ __launch_bounds__(256) void as_absorb_mb_kernel(int64_t N, unsigned c
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        nl += __shfl_down(nl, off, 64);
-        nu += __shfl_down(nu, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        wl[threadIdx.x >> 6] = nl;
-        wu[threadIdx.x >> 6] = nu;
-    }
+    bq_wave_put<bq_op_sum>(nl, wl);
+    bq_wave_put<bq_op_sum>(nu, wu);
     __syncthreads();
     if (threadIdx.x == 0) {
-        __hip_atomic_store(&cnt[2 * blockIdx.x], wl[0] + wl[1] + wl[2] + wl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&cnt[2 * blockIdx.x + 1], wu[0] + wu[1] + wu[2] + wu[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        bq_part_put(&cnt[2 * blockIdx.x], bq_waves_sum<4>(wl));
+        bq_part_put(&cnt[2 * blockIdx.x + 1], bq_waves_sum<4>(wu));
     }
-    if (as_last_block_mb(&sc->ticket[1]) && threadIdx.x == 0) {
+    if (bq_last_block(&sc->ticket[1], gridDim.x) && threadIdx.x == 0) {
         int tl = 0, tu = 0;
         for (unsigned int b = 0; b < gridDim.x; ++b) {
-            tl += __hip_atomic_load(&cnt[2 * b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tu += __hip_atomic_load(&cnt[2 * b + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tl += bq_part_get(&cnt[2 * b]);
+            tu += bq_part_get(&cnt[2 * b + 1]);
         }
         ints[5] = tl;
         ints[6] = tu;
@@ -298,29 +279,22 @@ __global__ __launch_bounds__(256) void as_release_mb_kernel(int64_t N, const dou
                                                             bq_iter_stat *stats) {
     __shared__ int sl[4], su[4];
     int hl = (int)N, hu = (int)N;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             if (mL[i] && g[i] < -ACT_TOL && (int)i < hl) hl = (int)i;
             if (mU[i] && g[i] > ACT_TOL && (int)i < hu) hu = (int)i;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        hl = min(hl, __shfl_down(hl, off, 64));
-        hu = min(hu, __shfl_down(hu, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sl[threadIdx.x >> 6] = hl;
-        su[threadIdx.x >> 6] = hu;
-    }
+    bq_wave_put<bq_op_min>(hl, sl);
+    bq_wave_put<bq_op_min>(hu, su);
     __syncthreads();
     if (threadIdx.x == 0) {
-        hl = min(min(sl[0], sl[1]), min(sl[2], sl[3]));
-        hu = min(min(su[0], su[1]), min(su[2], su[3]));
+        hl = bq_waves_min<4>(sl);
+        hu = bq_waves_min<4>(su);
         if (hl < (int)N) atomicMin(&ints[27], hl);
         if (hu < (int)N) atomicMin(&ints[28], hu);
     }
-    if (as_last_block_mb(&sc->pad1[1]) && threadIdx.x == 0) {
+    if (bq_last_block(&sc->pad1[1], gridDim.x) && threadIdx.x == 0) {
         const long long ghl = __hip_atomic_load(&ints[27], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const long long ghu = __hip_atomic_load(&ints[28], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ints[3] = (int)ghl;
@@ -356,18 +330,18 @@ __global__ __launch_bounds__(256) void as_release_mb_kernel(int64_t N, const dou
 static_assert(BQ_MAX_PARTIAL_Q >= 3, "as_launch_*: three slices of the partials buffer");
 void as_launch_compact(bq_solver *s, as_ws *w, hipStream_t st) {
     int *cnt = reinterpret_cast<int *>(s->partials + s->nblk);
-    as_count_free_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, cnt, w->ints, &s->sc->pad1[0]);
-    as_write_free_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, cnt, w->idx);
+    as_count_free_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, cnt, w->ints, &s->sc->pad1[0]);
+    as_write_free_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, cnt, w->idx);
 }
 static_assert(BQ_MAX_PARTIAL_Q >= 4, "as_launch_step: a fourth slice of the partials buffer");
 void as_launch_step(bq_solver *s, as_ws *w, hipStream_t st, int chain) {
-    as_step_min_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, w->cand, s->lb, s->ub, s->x, w->gref ? w->gref : s->g,
+    as_step_min_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, w->cand, s->lb, s->ub, s->x, w->gref ? w->gref : s->g,
                                                               s->partials, s->partials + 3 * s->nblk, s->sc, chain);
-    as_step_apply_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, w->cand, s->x, s->sc);
+    as_step_apply_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, w->cand, s->x, s->sc);
 }
 void as_launch_absorb(bq_solver *s, as_ws *w, hipStream_t st) {
     int *cnt = reinterpret_cast<int *>(s->partials + 2 * s->nblk);
-    as_absorb_mb_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, s->x, s->lb, s->ub, s->sc, w->ints, cnt, s->stats);
+    as_absorb_mb_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->mL, s->mU, s->x, s->lb, s->ub, s->sc, w->ints, cnt, s->stats);
 }
 
 int as_eval_f(bq_solver *s, double *g_out) {
@@ -379,15 +353,15 @@ int as_eval_f(bq_solver *s, double *g_out) {
 // the dense iteration's two branches once the candidate is known (w->host_ints[2]: it is feasible).  `exact`: the candidate came
 // from a factorisation (kept or fresh), not from the minimum-residual branch — the condition of the product-free f of a ratio step
 void as_launch_release(bq_solver *s, as_ws *w, hipStream_t st) {
-    as_release_mb_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->g, s->mL, s->mU, s->sc, w->ints, s->stats);
+    as_release_mb_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, s->g, s->mL, s->mU, s->sc, w->ints, s->stats);
 }
 
 int as_finish_iteration(bq_solver *s, as_ws *w, hipStream_t st, bool exact) {
     const int64_t N = s->N;
     if (w->host_ints[2]) {
-        as_copy_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, w->cand, s->x);
+        as_copy_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, w->cand, s->x);
         BQ_TRY(as_eval_f(s, s->g));
-        as_release_mb_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->g, s->mL, s->mU, s->sc, w->ints, s->stats);
+        as_release_mb_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->g, s->mL, s->mU, s->sc, w->ints, s->stats);
         w->chain_ok = exact && w->f_chain;   // x solves its restricted system and g is fresh: a run may start
         w->gref = s->g;
         w->chain_len = 0;
@@ -542,7 +516,7 @@ int bq_as_iterate(bq_solver *s) {
     as_top_kernel<<<1, 64, 0, st>>>(s->sc, w->ints, s->stats, (int)N, w->host_ints_d, w->host_scal_d,
                                    mbx ? w->mail_d : nullptr, mbx ? ++w->mail_seq[0] : 0);
     if (!s->host.done) {  // snapshot of the point this record describes
-        as_copy2_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->x, w->x_eval, s->g, w->g_eval);
+        as_copy2_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->x, w->x_eval, s->g, w->g_eval);
         s->started = true;
     }
     if (s->as_cg && w->pc) as_pc_track(s, w, st);
@@ -584,15 +558,15 @@ int bq_as_iterate(bq_solver *s) {
             if (w->timing) w->tm_classic += ldl_now() - t0;
         }
     } ctail{w, tcl0};
-    as_make_z_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->z);
+    as_make_z_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->z);
     BQ_TRY(bq_problem_apply(s->p, w->z, w->Qz, nullptr));
     int64_t np = 0;
     BQ_TRY(bq_chol_build_h(ws, s->p, w->idx, nA, nullptr, &np));
     as_gather_rhs_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w->ints, w->idx, s->p->q, w->Qz, ws->rhs, np);
     BQ_TRY(bq_chol_factor(ws, np));
     BQ_TRY(bq_chol_solve(ws, np));
-    as_cand_fill_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
-    as_cand_scatter_idx_kernel<<<vgrid(s->ldN).x * (BQ_VEC_TILE / 256), 256, 0, st>>>(w->idx, w->ints, ws->rhs, s->lb, s->ub, w->cand);
+    as_cand_fill_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
+    as_cand_scatter_idx_kernel<<<bq_vec_grid(s->ldN).x * (BQ_VEC_TILE / 256), 256, 0, st>>>(w->idx, w->ints, ws->rhs, s->lb, s->ub, w->cand);
     BQ_HIP(hipMemcpyAsync(w->host_info, ws->info, sizeof(int), hipMemcpyDeviceToHost, st));
     BQ_HIP(hipMemcpyAsync(w->host_ints, w->ints, sizeof(int) * 32, hipMemcpyDeviceToHost, st));
     BQ_SYNC(s->p->ctx);
@@ -605,8 +579,8 @@ int bq_as_iterate(bq_solver *s) {
         BQ_TRY(bq_chol_build_h(ws, s->p, w->idx, nA, nullptr, &np, true));
         as_gather_rhs_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w->ints, w->idx, s->p->q, w->Qz, ws->rhs, np);
         BQ_TRY(bq_minres_normal(ws, w->ints, nA, np, ws->mr_vec, w->ints + 7));
-        as_cand_fill_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
-        as_cand_scatter_idx_kernel<<<vgrid(s->ldN).x * (BQ_VEC_TILE / 256), 256, 0, st>>>(w->idx, w->ints, ws->rhs, s->lb, s->ub, w->cand);
+        as_cand_fill_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
+        as_cand_scatter_idx_kernel<<<bq_vec_grid(s->ldN).x * (BQ_VEC_TILE / 256), 256, 0, st>>>(w->idx, w->ints, ws->rhs, s->lb, s->ub, w->cand);
         BQ_HIP(hipMemcpyAsync(w->host_ints, w->ints, sizeof(int) * 32, hipMemcpyDeviceToHost, st));
         BQ_SYNC(s->p->ctx);
         w->minres_calls += 1;

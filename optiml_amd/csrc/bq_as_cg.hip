@@ -6,7 +6,7 @@
 __global__ void as_make_xt_kernel(int64_t N, const unsigned char *__restrict__ mL, const unsigned char *__restrict__ mU,
                                   const double *__restrict__ lb, const double *__restrict__ ub,
                                   const double *__restrict__ x, double *__restrict__ xt) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) xt[i] = mU[i] ? ub[i] : (mL[i] ? lb[i] : x[i]);
     }
 }
@@ -21,7 +21,7 @@ __global__ void as_cg_init_kernel(int64_t N, const unsigned char *__restrict__ m
                                   as_cg_scal *cg, double rtol, long long max_iters, int pc) {
     __shared__ double sh[4];
     double srr = 0.0, sqx = 0.0, sq = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             const bool fr = !(mL[i] | mU[i]);
             const double a = Qxt[i], b = q[i];
@@ -37,20 +37,19 @@ __global__ void as_cg_init_kernel(int64_t N, const unsigned char *__restrict__ m
             }
         }
     }
-    srr = as_block_sum(srr, sh);
-    sqx = as_block_sum(sqx, sh);
-    sq = as_block_sum(sq, sh);
+    srr = bq_block_sum(srr, sh);
+    sqx = bq_block_sum(sqx, sh);
+    sq = bq_block_sum(sq, sh);
     if (threadIdx.x == 0) {
-        part[blockIdx.x] = srr;
-        part[nblk + blockIdx.x] = sqx;
-        part[2 * nblk + blockIdx.x] = sq;
+        bq_part_put(&part[blockIdx.x], srr);
+        bq_part_put(&part[nblk + blockIdx.x], sqx);
+        bq_part_put(&part[2 * nblk + blockIdx.x], sq);
     }
-    if (as_last_block(&cg->ticket[0])) {
-        const double rr = as_final_sum(part, nblk, sh);
-        const double nqx = as_final_sum(part + nblk, nblk, sh), nq = as_final_sum(part + 2 * nblk, nblk, sh);
+    if (bq_last_block(&cg->ticket[0], gridDim.x)) {
+        const double rr = bq_final_sum(part, nblk, sh);
+        const double nqx = bq_final_sum(part + nblk, nblk, sh), nq = bq_final_sum(part + 2 * nblk, nblk, sh);
         if (threadIdx.x == 0) {
             const double level = rtol * (sqrt(nqx) + sqrt(nq));
-            cg->ticket[0] = 0;
             cg->rr = rr;
             cg->tol2 = level * level;
             cg->alpha = 0.0;
@@ -71,15 +70,14 @@ __global__ void as_cg_pap_kernel(int64_t N, const double *__restrict__ pv, const
     if (cg->done) return;
     __shared__ double sh[4];
     double s = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) s += __dmul_rn(pv[i], Qp[i]);
     }
-    s = as_block_sum(s, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-    if (as_last_block(&cg->ticket[0])) {
-        const double pAp = as_final_sum(part, nblk, sh);
+    s = bq_block_sum(s, sh);
+    if (threadIdx.x == 0) bq_part_put(&part[blockIdx.x], s);
+    if (bq_last_block(&cg->ticket[0], gridDim.x)) {
+        const double pAp = bq_final_sum(part, nblk, sh);
         if (threadIdx.x == 0) {
-            cg->ticket[0] = 0;
             if (!(pAp > 0.0) || !isfinite(pAp)) {
                 cg->info = 1;
                 cg->alpha = 0.0;
@@ -100,7 +98,7 @@ __global__ void as_cg_update_kernel(int64_t N, const unsigned char *__restrict__
     __shared__ double sh[4];
     const double alpha = cg->alpha;
     double s = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) Qdl[i] = Qdl[i] + __dmul_rn(alpha, Qp[i]);
         if (i < N && !(mL[i] | mU[i])) {
             dlt[i] = dlt[i] + __dmul_rn(alpha, pv[i]);
@@ -109,12 +107,11 @@ __global__ void as_cg_update_kernel(int64_t N, const unsigned char *__restrict__
             s += __dmul_rn(ri, ri);
         }
     }
-    s = as_block_sum(s, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-    if (as_last_block(&cg->ticket[1])) {
-        const double rr = as_final_sum(part, nblk, sh);
+    s = bq_block_sum(s, sh);
+    if (threadIdx.x == 0) bq_part_put(&part[blockIdx.x], s);
+    if (bq_last_block(&cg->ticket[1], gridDim.x)) {
+        const double rr = bq_final_sum(part, nblk, sh);
         if (threadIdx.x == 0) {
-            cg->ticket[1] = 0;
             if (!cg->pc) cg->beta = cg->rr > 0.0 ? rr / cg->rr : 0.0;   // preconditioned: beta = rz_new / rz (as_pc_apply_kernel)
             cg->rr = rr;
             cg->iters += 1;
@@ -127,14 +124,14 @@ __global__ void as_cg_update_kernel(int64_t N, const unsigned char *__restrict__
 __global__ void as_cg_dir_kernel(int64_t N, const double *__restrict__ r, double *__restrict__ pv, const as_cg_scal *cg) {
     if (cg->done) return;
     const double beta = cg->beta;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) pv[i] = r[i] + __dmul_rn(beta, pv[i]);
     }
 }
 
 // Q cand = Q z + Q delta (z: the start point with the bound values, delta: what the iteration added on the free set)
 __global__ void as_qcand_kernel(int64_t N, const double *__restrict__ Qz, const double *__restrict__ Qdl, double *__restrict__ Qc) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         Qc[i] = i < N ? Qz[i] + Qdl[i] : 0.0;
     }
 }
@@ -142,7 +139,7 @@ __global__ void as_qcand_kernel(int64_t N, const double *__restrict__ Qz, const 
 // after the ratio step x += t (cand - x):  Q x += t (Q cand - Q x)
 __global__ void as_qx_lerp_kernel(int64_t N, const bq_scal *sc, const double *__restrict__ Qc, double *__restrict__ Qx) {
     const double t = sc->step;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) Qx[i] = Qx[i] + __dmul_rn(t, Qc[i] - Qx[i]);
     }
 }
@@ -279,7 +276,7 @@ static int as_cg_solve_once(bq_solver *s, as_ws *w, int *pc_failed) {
     hipStream_t st = ctx->stream;
     const int64_t N = s->N, nblk = s->nblk;
     const int64_t nA = w->host_ints[0];
-    const dim3 grid = vgrid(s->ldN);
+    const dim3 grid = bq_vec_grid(s->ldN);
     const long long cap = s->inner_max > 0 ? s->inner_max : 2 * (long long)nA + 50;
     as_pc *pc = w->pc;
     const double *start = (w->warm && w->have_cand) ? w->cand : s->x;
@@ -355,8 +352,8 @@ static int as_cg_solve_once(bq_solver *s, as_ws *w, int *pc_failed) {
     }
     as_qcand_kernel<<<grid, BQ_VEC_BLOCK, 0, st>>>(N, w->Qz, w->Qdl, w->Qcand);
     as_cg_gather_kernel<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(w->ints, w->idx, w->z, w->dlt, w->sol, N);
-    as_cand_fill_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
-    as_cand_scatter_idx_kernel<<<vgrid(s->ldN).x * (BQ_VEC_TILE / 256), 256, 0, st>>>(w->idx, w->ints, w->sol, s->lb, s->ub, w->cand);
+    as_cand_fill_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
+    as_cand_scatter_idx_kernel<<<bq_vec_grid(s->ldN).x * (BQ_VEC_TILE / 256), 256, 0, st>>>(w->idx, w->ints, w->sol, s->lb, s->ub, w->cand);
     w->have_cand = true;
     BQ_HIP(hipMemcpyAsync(w->host_ints, w->ints, sizeof(int) * 32, hipMemcpyDeviceToHost, st));
     BQ_SYNC(s->p->ctx);
@@ -410,9 +407,9 @@ int as_cg_iterate(bq_solver *s, as_ws *w) {
         w->anchor = true;
     }
     if (w->host_ints[2]) {
-        as_copy_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, w->cand, s->x);
+        as_copy_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, w->cand, s->x);
         if (inc) {
-            as_copy_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, w->Qcand, s->Qd);
+            as_copy_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, w->Qcand, s->Qd);
             BQ_TRY(bq_vec_eval_f(s->p, s->x, s->Qd, s->g, &s->sc->f));
         } else {
             BQ_TRY(as_eval_f(s, s->g));
@@ -421,7 +418,7 @@ int as_cg_iterate(bq_solver *s, as_ws *w) {
     } else {
         as_launch_step(s, w, st);
         if (inc) {
-            as_qx_lerp_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->sc, w->Qcand, s->Qd);
+            as_qx_lerp_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->sc, w->Qcand, s->Qd);
             BQ_TRY(bq_vec_eval_f(s->p, s->x, s->Qd, nullptr, &s->sc->f));
         } else {
             BQ_TRY(as_eval_f(s, nullptr));

@@ -24,23 +24,23 @@ __global__ __launch_bounds__(256) void as_pc_class_kernel(int64_t n, int64_t d, 
             sm += v;
         }
     }
-    sp = as_block_sum(sp, sh);
-    sm = as_block_sum(sm, sh);
-    cp = as_block_sum(cp, sh);
+    sp = bq_block_sum(sp, sh);
+    sm = bq_block_sum(sm, sh);
+    cp = bq_block_sum(cp, sh);
     if (threadIdx.x == 0) {
         const double cm = (double)n - cp;
         const double mp = cp > 0.0 ? sp / cp : 0.0, mm = cm > 0.0 ? sm / cm : 0.0;
-        cls[k] = (cp > 0.0 && cm > 0.0) ? 0.5 * (mp - mm) : 0.0;
+        bq_part_put(&cls[k], (cp > 0.0 && cm > 0.0) ? 0.5 * (mp - mm) : 0.0);   // read by the last block below
         cls[d + k] = (cp > 0.0 && cm > 0.0) ? 0.5 * (mp + mm) : (cp > 0.0 ? mp : mm);
     }
-    if (as_last_block(ticket)) {
+    if (bq_last_block(ticket, gridDim.x)) {
         double s2 = 0.0;
-        for (int64_t j = threadIdx.x; j < d; j += 256) s2 += cls[j] * cls[j];
-        s2 = as_block_sum(s2, sh);
-        if (threadIdx.x == 0) {
-            cls[2 * d] = sqrt(s2);
-            *ticket = 0;
+        for (int64_t j = threadIdx.x; j < d; j += 256) {
+            const double c = bq_part_get(&cls[j]);
+            s2 += c * c;
         }
+        s2 = bq_block_sum(s2, sh);
+        if (threadIdx.x == 0) cls[2 * d] = sqrt(s2);
     }
 }
 
@@ -539,12 +539,11 @@ __global__ __launch_bounds__(256) void as_pc_zunpack_kernel(int64_t N, as_pc_par
         if (base + q < N) s += __dmul_rn(r[base + q], zi);   // z vanishes outside the free set
     }
     if (!fin) return;
-    s = as_block_sum(s, sh);
-    if (threadIdx.x == 0) pt_sums[blockIdx.x] = s;
-    if (as_last_block(&cg->ticket[0])) {
-        const double rz = as_final_sum(pt_sums, nblk, sh);
+    s = bq_block_sum(s, sh);
+    if (threadIdx.x == 0) bq_part_put(&pt_sums[blockIdx.x], s);
+    if (bq_last_block(&cg->ticket[0], gridDim.x)) {
+        const double rz = bq_final_sum(pt_sums, nblk, sh);
         if (threadIdx.x == 0) {
-            cg->ticket[0] = 0;
             cg->beta = (first || !(cg->rz > 0.0)) ? 0.0 : rz / cg->rz;
             cg->rz = rz;
             if (!(rz > 0.0) || !isfinite(rz)) cg->info = 2;   // P is positive definite: r'z <= 0 means r = 0 or a broken factor
@@ -612,7 +611,7 @@ __global__ __launch_bounds__(256) void as_pc_combine_kernel(int64_t N, double al
     if (cg->done) return;
     __shared__ double sh[4];
     double s = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         double zi = 0.0;
         if (i < N) {
             zi = alpha * y[i] - beta * z2[i];
@@ -620,12 +619,11 @@ __global__ __launch_bounds__(256) void as_pc_combine_kernel(int64_t N, double al
         }
         z[i] = zi;
     }
-    s = as_block_sum(s, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-    if (as_last_block(&cg->ticket[0])) {
-        const double rz = as_final_sum(part, nblk, sh);
+    s = bq_block_sum(s, sh);
+    if (threadIdx.x == 0) bq_part_put(&part[blockIdx.x], s);
+    if (bq_last_block(&cg->ticket[0], gridDim.x)) {
+        const double rz = bq_final_sum(part, nblk, sh);
         if (threadIdx.x == 0) {
-            cg->ticket[0] = 0;
             cg->beta = (first || !(cg->rz > 0.0)) ? 0.0 : rz / cg->rz;
             cg->rz = rz;
             if (!(rz > 0.0) || !isfinite(rz)) cg->info = 2;
@@ -925,7 +923,7 @@ static int as_pc_solve1(bq_solver *s, as_ws *w, const double *in, double *out, i
                                                                        pc->u, pc->zg, w->cg);
     BQ_HIP(hipGetLastError());
     BQ_TRY(bq_exchange_gather(ctx, pc->zg, (int64_t)pt.cmax * pt.maxlen * BQ_VEC_TILE));
-    as_pc_zunpack_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, pt, pc->zg, in, out, s->partials, s->nblk, w->cg, first, fin);
+    as_pc_zunpack_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, pt, pc->zg, in, out, s->partials, s->nblk, w->cg, first, fin);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
@@ -952,7 +950,7 @@ static int as_pc_r_apply(bq_solver *s, as_ws *w, const double *y) {
                                                                           pc->ttop, s->mL, s->mU, vg, w->cg);
     BQ_HIP(hipGetLastError());
     BQ_TRY(bq_exchange_gather(s->p->ctx, vg, (int64_t)pt.cmax * pt.maxlen * BQ_VEC_TILE));
-    as_pc_unpack_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->ldN, pt, vg, pc->v2, w->cg);
+    as_pc_unpack_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->ldN, pt, vg, pc->v2, w->cg);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
@@ -977,7 +975,7 @@ int as_pc_apply(bq_solver *s, as_ws *w, int first) {
         BQ_TRY(as_pc_solve1(s, w, w->r, pc->y1, first, 0));
         BQ_TRY(as_pc_r_apply(s, w, pc->y1));                 // six collectives in all
         BQ_TRY(as_pc_solve1(s, w, pc->v2, pc->z2, first, 0));
-        as_pc_combine_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, alpha, beta, w->r, pc->y1, pc->z2, pc->z, s->partials, s->nblk, w->cg,
+        as_pc_combine_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, alpha, beta, w->r, pc->y1, pc->z2, pc->z, s->partials, s->nblk, w->cg,
                                                                      first);
         BQ_HIP(hipGetLastError());
     }
@@ -992,8 +990,8 @@ void as_pc_track(bq_solver *s, as_ws *w, hipStream_t st) {
     const int64_t N = s->N;
     const int force = (pc->age == 0 || pc->age >= 128 || !bq_hook_on("as_cg_pc_incr")) ? 1 : 0;
     int *lcnt = reinterpret_cast<int *>(s->partials + s->nblk);
-    as_pc_diff_count_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, pc->prev, lcnt, &s->sc->pad1[0], pc->chg, force);
-    as_pc_diff_write_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, pc->prev, lcnt, pc->chg);
+    as_pc_diff_count_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, pc->prev, lcnt, &s->sc->pad1[0], pc->chg, force);
+    as_pc_diff_write_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, pc->prev, lcnt, pc->chg);
     (void)hipMemcpyAsync(w->host_info + 4, pc->chg, 2 * sizeof(int), hipMemcpyDeviceToHost, st);   // pinned, like the rest
 }
 

@@ -26,20 +26,13 @@ __global__ void as_cand_scatter_kernel(int64_t n0, int m, const int *__restrict_
     }
     if (bad) ints[2] = 0;   // benign race: every writer stores 0
     if (mail == nullptr) return;
-    // the last workgroup to get here hands the record (feasibility flag and all) to the host
-    __shared__ int last;
+    // the last workgroup to get here hands the record (feasibility flag and all) to the host; every thread of a workgroup wrote,
+    // so every thread fences before the workgroup's ticket is taken
     __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!bq_last_block(ticket, gridDim.x)) return;
     if (threadIdx.x < 32) mail_ints[threadIdx.x] = __hip_atomic_load(ints + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __threadfence_system();
-    if (threadIdx.x == 0) {
-        *ticket = 0;
-        as_post(mail, seq);
-    }
+    if (threadIdx.x == 0) as_post(mail, seq);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -72,7 +65,7 @@ __global__ void as_schur_pos_kernel(int64_t N, int64_t n0, const int *__restrict
 __global__ void as_schur_z_kernel(int64_t N, const unsigned char *__restrict__ mL, const unsigned char *__restrict__ mU,
                                   const double *__restrict__ lb, const double *__restrict__ ub,
                                   const int *__restrict__ pos0, double *__restrict__ z) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) z[i] = (pos0[i] < 0 && (mL[i] | mU[i])) ? (mU[i] ? ub[i] : lb[i]) : 0.0;
     }
 }
@@ -137,33 +130,27 @@ __global__ __launch_bounds__(256) void as_schur_dots_kernel(int mode, int k, con
     } else {
         for (int64_t a = threadIdx.x; a < np0; a += 256) s += __dmul_rn(u[a], v[a]);
     }
-    s = as_wsum_any(s);
-    if (mode == 2) t = as_wsum_any(t);
-    if ((threadIdx.x & 63) == 0) {
-        sh[threadIdx.x >> 6] = s;
-        sh1[threadIdx.x >> 6] = t;
-    }
+    bq_wave_put<bq_op_sum>(s, sh);
+    if (mode == 2) bq_wave_put<bq_op_sum>(t, sh1);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double dot = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+        const double dot = bq_waves_sum<4>(sh);
         if (mode != 1) {
             double extra = 0.0;
             if (ki == 1 && kk == 1) extra = bq_q_elem(structure, panel, ldp, packed, n, sgn, diag_add, (int64_t)vi, (int64_t)vk);
             out[i] = extra - dot;
         }
         if (mode != 0) {
-            const double d1 = mode == 1 ? dot : ((sh1[0] + sh1[1]) + sh1[2]) + sh1[3];
+            const double d1 = mode == 1 ? dot : bq_waves_sum<4>(sh1);
             const double extra = ki == 0 ? (mU[vi] ? ub[vi] : lb[vi]) : -(q[vi] + Qz[vi]);
             (mode == 1 ? out : out1)[i] = extra - d1;
         }
-        if (mail != nullptr) {   // out / out1 are the host's (mapped) buffers: the last workgroup posts the record
-            __threadfence_system();
-            if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
-                *ticket = 0;
-                __threadfence_system();
-                as_post(mail, seq);
-            }
-        }
+        if (mail != nullptr) __threadfence_system();   // out / out1 are the host's (mapped) buffers
+    }
+    if (mail == nullptr) return;
+    if (bq_last_block(ticket, gridDim.x) && threadIdx.x == 0) {   // the last workgroup posts the record
+        __threadfence_system();
+        as_post(mail, seq);
     }
 }
 
@@ -530,7 +517,7 @@ static int as_schur_solve_t(bq_solver *s, as_ws *w, int computed, bool *good) {
     unsigned int *tk = mbx ? w->mail_ticket : nullptr;
     int *post = mbx ? w->mail_d + 1 : nullptr;
     if (!c->y0_valid) {   // while only base variables reach bounds, b0 and Q00^-1 b0 stay what they were
-        as_schur_z_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, c->pos0, w->z);
+        as_schur_z_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, c->pos0, w->z);
         BQ_TRY(bq_problem_apply(p, w->z, w->Qz, nullptr));
         as_schur_rhs0_kernel<<<gb, 256, 0, st>>>(n0, np0, c->idx0, p->q, w->Qz, ws->rhs);
         BQ_TRY(bq_chol_solve(ws, np0));
@@ -587,7 +574,7 @@ static int as_schur_solve_t(bq_solver *s, as_ws *w, int computed, bool *good) {
     as_tick(w, 3);
     const double *coef_dev = mbx ? c->coef_pin_d : c->small + AS_SCHUR_MAX;
     as_schur_combine_kernel<<<gb, 1024, 0, st>>>(np0, m, c->y0, c->W, c->cap, coef_dev, c->y);
-    as_cand_fill_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
+    as_cand_fill_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(N, s->mL, s->mU, s->lb, s->ub, w->cand, w->ints);
     {
         const int64_t span = n0 > m ? (n0 > 0 ? n0 : 1) : (int64_t)m;
         as_cand_scatter_kernel<<<dim3((unsigned)((span + 255) / 256)), 256, 0, st>>>(n0, m, c->idx0, meta, s->mL, s->mU, s->lb, s->ub,

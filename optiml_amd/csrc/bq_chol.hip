@@ -19,6 +19,7 @@
 #include "bq_chol.h"
 #include "bq_chol_sched.h"
 #include "bq_qelem.h"
+#include "bq_reduce.h"
 #include "bq_mfma_tile.h"
 
 constexpr int NB = 128;
@@ -99,15 +100,8 @@ __global__ __launch_bounds__(256, 2) void syrk_head_kernel(double *__restrict__ 
 // ---------------------------------------------------------------------------------------------
 // triangular solves with the blocked factor (rhs overwritten by the solution)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wsum_c(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 __device__ __forceinline__ void diag_mv_body(const double *__restrict__ LinvT, int transpose, const double *in,
                                              double *out);
-__device__ __forceinline__ bool chol_last_block(unsigned int *ticket);
 
 // part[s][r] = sum_{c in slice s of [c0, k0)} L[k0 + r][c] * rhs[c]      (workgroup (r, s): row r, column slice s)
 // ... and the last workgroup to finish forms tmp = rhs[k0 : k0+128) - sum_s part[s] (fixed order) and applies the inverse
@@ -129,14 +123,15 @@ __global__ __launch_bounds__(256) void fwd_panel_kernel(const double *__restrict
         const bq_d2 y = *reinterpret_cast<const bq_d2 *>(rhs + c);
         a = fma(l.y, y.y, fma(l.x, y.x, a));
     }
-    a = wsum_c(a);
-    if ((tid & 63) == 0) red[tid >> 6] = a;
+    bq_wave_put<bq_op_sum>(a, red);
     __syncthreads();
-    if (tid == 0) part[(int64_t)blockIdx.y * NB + r] = ((red[0] + red[1]) + red[2]) + red[3];
-    if (chol_last_block(ticket)) {
+    if (tid == 0) bq_part_put(&part[(int64_t)blockIdx.y * NB + r], bq_waves_sum<4>(red));
+    // the workgroup that takes the last ticket runs the 128 x 128 product that depends on all of them (one launch and one
+    // dependent-kernel gap less per block step of the solves)
+    if (bq_last_block(ticket, gridDim.x * gridDim.y)) {
         if (tid < NB) {
-            double sum = part[tid];
-            for (unsigned int sl = 1; sl < gridDim.y; ++sl) sum += part[(int64_t)sl * NB + tid];
+            double sum = bq_part_get(&part[tid]);
+            for (unsigned int sl = 1; sl < gridDim.y; ++sl) sum += bq_part_get(&part[(int64_t)sl * NB + tid]);
             comb[tid] = rhs[k0 + tid] - sum;
         }
         __syncthreads();
@@ -188,23 +183,6 @@ __global__ __launch_bounds__(256) void diag_mv_kernel(const double *__restrict__
     diag_mv_body(LinvT, transpose, in, out);
 }
 
-// the block that takes the last ticket of a launch runs the 128 x 128 product that depends on all of them (one launch
-// and one dependent-kernel gap less per block step of the solves)
-__device__ __forceinline__ bool chol_last_block(unsigned int *ticket) {
-    __shared__ int last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x * gridDim.y - 1 ? 1 : 0;
-    }
-    __syncthreads();
-    if (last) {
-        __threadfence();
-        if (threadIdx.x == 0) *ticket = 0;
-    }
-    return last != 0;
-}
-
 // rhs[c] -= sum_{r < 128} L[k0 + r][c] * x[r]  for c < k0; the last block to finish then solves the next (previous)
 // diagonal block in place: rhs[k0-128 : k0) = Linv^T_{k-1} rhs[k0-128 : k0)
 // One workgroup per 128 columns: 64 column pairs x 4 groups of 32 rows, a thread's 32 row loads in flight together, the
@@ -238,7 +216,7 @@ __global__ __launch_bounds__(256) void bwd_update_kernel(const double *__restric
         rhs[c] -= a0;
         rhs[c + 1] -= a1;
     }
-    if (chol_last_block(ticket)) diag_mv_body(LinvT_prev, 1, rhs + k0 - NB, rhs + k0 - NB);
+    if (bq_last_block(ticket, gridDim.x)) diag_mv_body(LinvT_prev, 1, rhs + k0 - NB, rhs + k0 - NB);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -488,7 +466,7 @@ __global__ __launch_bounds__(256) void sweep_gemv_kernel(const double *__restric
     __shared__ double red[4][R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const double s = wsum_c(acc[r]);
+        const double s = bq_wave_sum(acc[r]);
         if (lane == 0) red[wv][r] = s;
     }
     __syncthreads();

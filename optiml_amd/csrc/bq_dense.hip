@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "bq_common.h"
+#include "bq_reduce.h"
 
 namespace {
 
@@ -226,11 +227,8 @@ __global__ __launch_bounds__(256) void dense_asym_kernel(const T *__restrict__ p
             a = fmax(a, fmax(fabs(lo), fabs(hi)));
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        d = fmax(d, __shfl_down(d, off, 64));
-        a = fmax(a, __shfl_down(a, off, 64));
-    }
+    d = bq_wave_max(d);
+    a = bq_wave_max(a);
     if ((threadIdx.x & 63) == 0) {
         wd[threadIdx.x >> 6] = d;
         wa[threadIdx.x >> 6] = a;

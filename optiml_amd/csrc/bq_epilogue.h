@@ -15,6 +15,7 @@
 // unnecessary — two launches per iteration — but costs a single-round grid more than it saves: profiles/r05/pgfw_fused_tile_prologue_probe.txt.)
 #pragma once
 #include "bq_common.h"
+#include "bq_reduce.h"
 
 #define BQ_CURV_TOL 1e-16
 #define BQ_ACT_TOL 1e-12
@@ -43,17 +44,6 @@ struct bq_epilogue {
 #define BQ_EPI_PGFW 1
 #define BQ_EPI_AL 2
 static inline int bq_epi_mode(const bq_epilogue *e) { return e == nullptr ? BQ_EPI_NONE : (e->kind == 2 ? BQ_EPI_AL : BQ_EPI_PGFW); }
-
-__device__ __forceinline__ double bq_epi_wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double bq_epi_wmin(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-    return v;
-}
 
 // element u of the new iterate from element u of the old state (x, g, d, Qd and the pending step t); y0 = FW's unclipped vertex
 // (its lower bound needs it).  `update` clear: (x, g) is the new iterate already and only d is re-derived.  Loading and arithmetic
@@ -179,34 +169,21 @@ __device__ __forceinline__ bq_epi_sums bq_epi_element(const bq_epilogue &e, cons
 // block partials -> part[q][a]; the last block of the grid takes the iteration's decisions and the step length
 __device__ __forceinline__ void bq_epi_finish(const bq_epilogue &e, long long a, long long nblocks, bq_epi_sums c, unsigned int nwg) {
     __shared__ double sh[5][4];
-    __shared__ int last;
     const int tid = threadIdx.x;
     if (tid < 256) {
-        c.den = bq_epi_wsum(c.den);
-        c.a = bq_epi_wsum(c.a);
-        c.gd = bq_epi_wsum(c.gd);
-        c.xg = bq_epi_wsum(c.xg);
-        c.rmin = bq_epi_wmin(c.rmin);
-        if ((tid & 63) == 0) {
-            const int w = tid >> 6;
-            sh[0][w] = c.den;
-            sh[1][w] = c.a;
-            sh[2][w] = c.gd;
-            sh[3][w] = c.xg;
-            sh[4][w] = c.rmin;
-        }
+        bq_wave_put<bq_op_sum>(c.den, sh[0]);
+        bq_wave_put<bq_op_sum>(c.a, sh[1]);
+        bq_wave_put<bq_op_sum>(c.gd, sh[2]);
+        bq_wave_put<bq_op_sum>(c.xg, sh[3]);
+        bq_wave_put<bq_op_min>(c.rmin, sh[4]);
     }
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) e.part[q * nblocks + a] = ((sh[q][0] + sh[q][1]) + sh[q][2]) + sh[q][3];
-        e.part[4 * nblocks + a] = fmin(fmin(sh[4][0], sh[4][1]), fmin(sh[4][2], sh[4][3]));
-        __threadfence();   // this block's partial sums are visible device-wide before the ticket is taken
-        last = atomicAdd(&e.sc->ticket[1], 1u) == nwg - 1 ? 1 : 0;
+        for (int q = 0; q < 4; ++q) bq_part_put(&e.part[q * nblocks + a], bq_waves_sum<4>(sh[q]));
+        bq_part_put(&e.part[4 * nblocks + a], bq_waves_min<4>(sh[4]));
     }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!bq_last_block(&e.sc->ticket[1], nwg)) return;
     // The last block of the grid closes the iteration: the sums over the blocks' partial sums (strided by 256, wave tree, four waves
     // in order), then projected_gradient.py:99-129 / frank_wolfe.py:111-151 — objective, |d| or the gap, the record, the stop tests,
     // the step length.  A stop leaves the state at the iterate it was decided on, with no step pending.
@@ -214,25 +191,17 @@ __device__ __forceinline__ void bq_epi_finish(const bq_epilogue &e, long long a,
     if (tid < 256) {
         for (long long k = tid; k < nblocks; k += 256) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] += e.part[q * nblocks + k];
-            am = fmin(am, e.part[4 * nblocks + k]);
+            for (int q = 0; q < 4; ++q) acc[q] += bq_part_get(&e.part[q * nblocks + k]);
+            am = fmin(am, bq_part_get(&e.part[4 * nblocks + k]));
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = bq_epi_wsum(acc[q]);
-        am = bq_epi_wmin(am);
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sh[q][tid >> 6] = acc[q];
-            sh[4][tid >> 6] = am;
-        }
+        for (int q = 0; q < 4; ++q) bq_wave_put<bq_op_sum>(acc[q], sh[q]);
+        bq_wave_put<bq_op_min>(am, sh[4]);
     }
     __syncthreads();
     if (tid == 0) {
-        const double den = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
-        const double ra = ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3];
-        const double sgd = ((sh[2][0] + sh[2][1]) + sh[2][2]) + sh[2][3];
-        const double sxg = ((sh[3][0] + sh[3][1]) + sh[3][2]) + sh[3][3];
-        const double rmin = fmin(fmin(sh[4][0], sh[4][1]), fmin(sh[4][2], sh[4][3]));
+        const double den = bq_waves_sum<4>(sh[0]), ra = bq_waves_sum<4>(sh[1]), sgd = bq_waves_sum<4>(sh[2]), sxg = bq_waves_sum<4>(sh[3]);
+        const double rmin = bq_waves_min<4>(sh[4]);
         bq_scal *sc = e.sc;
         const double f = 0.5 * sxg;
         bq_iter_stat st;
@@ -281,7 +250,6 @@ __device__ __forceinline__ void bq_epi_finish(const bq_epilogue &e, long long a,
         const long long row = sc->iter - sc->stat_base;
         if (row >= 0 && row < sc->stat_cap) e.stats[row] = st;
         if (!stop) sc->iter += 1;
-        sc->ticket[1] = 0;
     }
 }
 
@@ -387,48 +355,34 @@ __device__ __forceinline__ bq_al_sums bq_al_epi_element(const bq_epilogue &e, co
 template <bool EVAL>
 __device__ __forceinline__ void bq_al_epi_finish(const bq_epilogue &e, long long a, long long nblocks, bq_al_sums c, unsigned int nwg) {
     __shared__ double sh[BQ_AL_NQ][4];
-    __shared__ int last;
     const int tid = threadIdx.x;
     if (tid < 256) {
 #pragma unroll
-        for (int q = 0; q < BQ_AL_NQ; ++q) c.v[q] = bq_epi_wsum(c.v[q]);
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < BQ_AL_NQ; ++q) sh[q][tid >> 6] = c.v[q];
-        }
+        for (int q = 0; q < BQ_AL_NQ; ++q) bq_wave_put<bq_op_sum>(c.v[q], sh[q]);
     }
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int q = 0; q < BQ_AL_NQ; ++q) e.part[q * nblocks + a] = ((sh[q][0] + sh[q][1]) + sh[q][2]) + sh[q][3];
-        __threadfence();
-        last = atomicAdd(&e.sc->ticket[0], 1u) == nwg - 1 ? 1 : 0;
+        for (int q = 0; q < BQ_AL_NQ; ++q) bq_part_put(&e.part[q * nblocks + a], bq_waves_sum<4>(sh[q]));
     }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!bq_last_block(&e.sc->ticket[0], nwg)) return;
     double acc[BQ_AL_NQ];
 #pragma unroll
     for (int q = 0; q < BQ_AL_NQ; ++q) acc[q] = 0.0;
     if (tid < 256) {
         for (long long k = tid; k < nblocks; k += 256) {
 #pragma unroll
-            for (int q = 0; q < BQ_AL_NQ; ++q) acc[q] += e.part[q * nblocks + k];
+            for (int q = 0; q < BQ_AL_NQ; ++q) acc[q] += bq_part_get(&e.part[q * nblocks + k]);
         }
 #pragma unroll
-        for (int q = 0; q < BQ_AL_NQ; ++q) acc[q] = bq_epi_wsum(acc[q]);
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < BQ_AL_NQ; ++q) sh[q][tid >> 6] = acc[q];
-        }
+        for (int q = 0; q < BQ_AL_NQ; ++q) bq_wave_put<bq_op_sum>(acc[q], sh[q]);
     }
     __syncthreads();
     if (tid != 0) return;
     double t[BQ_AL_NQ];
 #pragma unroll
-    for (int q = 0; q < BQ_AL_NQ; ++q) t[q] = ((sh[q][0] + sh[q][1]) + sh[q][2]) + sh[q][3];
+    for (int q = 0; q < BQ_AL_NQ; ++q) t[q] = bq_waves_sum<4>(sh[q]);
     bq_scal *sc = e.sc;
-    sc->ticket[0] = 0;
     const double ax = t[2];
     if (sc->al_pending) {
         // the previous iteration's close (optiml/opti/_base.py:129-146): multiplier of the equality row from a'x at the new point

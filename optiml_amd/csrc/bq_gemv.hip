@@ -10,6 +10,7 @@
 // row sums are combined by a fixed shuffle tree + a fixed 4-wave order -> bit-reproducible on any GPU
 // count.  The kernel is bound by HBM: algorithmic bytes per launch = nrows*n*sizeof(T) + O(n).
 #include "bq_common.h"
+#include "bq_reduce.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
@@ -38,12 +39,6 @@ __device__ __forceinline__ double dot16(f4_t p, d2_t w0, d2_t w1) {
 template <typename VT> struct vt_traits;
 template <> struct vt_traits<d2_t> { static constexpr int elems = 2; };
 template <> struct vt_traits<f4_t> { static constexpr int elems = 4; };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 template <typename VT, int R, bool ADD_ONE, int UNROLL>
 __global__ __launch_bounds__(256) void gemv_rows_kernel(const VT *__restrict__ panel, int64_t ldv, int64_t nrows,
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const VT *__restrict__ p
     const int lane = tid & 63, wv = tid >> 6;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        double s = wave_sum(acc[r]);
+        double s = bq_wave_sum(acc[r]);
         if (lane == 0) red[wv][r] = s;
     }
     __syncthreads();

@@ -10,50 +10,7 @@
 #include <cstdlib>
 
 #include "bq_chol.h"
-
-#define VEC_LOOP(i)                                                             \
-    const int64_t _base = (int64_t)blockIdx.x * BQ_VEC_TILE + threadIdx.x;      \
-    _Pragma("unroll") for (int _j = 0; _j < BQ_VEC_ITEMS; ++_j)                 \
-        for (int64_t i = _base + (int64_t)_j * BQ_VEC_BLOCK, _once = 1; _once; _once = 0)
-
-static inline dim3 vgrid(int64_t ldN) { return dim3((unsigned)(ldN / BQ_VEC_TILE)); }
-
-__device__ __forceinline__ double ip_wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double ip_wmin(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double ip_bsum(double v, double *sh) {
-    v = ip_wsum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double ip_bmin(double v, double *sh) {
-    v = ip_wmin(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = fmin(fmin(sh[0], sh[1]), fmin(sh[2], sh[3]));
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double ip_fsum(const double *part, int64_t nblk, double *sh) {
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < nblk; i += BQ_VEC_BLOCK) a += part[i];
-    return ip_bsum(a, sh);
-}
-__device__ __forceinline__ double ip_fmin(const double *part, int64_t nblk, double *sh) {
-    double a = INFINITY;
-    for (int64_t i = threadIdx.x; i < nblk; i += BQ_VEC_BLOCK) a = fmin(a, part[i]);
-    return ip_bmin(a, sh);
-}
+#include "bq_reduce.h"
 
 struct ipv {
     double *x, *g, *Qx, *q, *lb, *ub, *lp, *lm, *rhs, *hd, *dlp, *dlm, *dx;
@@ -61,7 +18,7 @@ struct ipv {
 
 // g = Qx + q at the start point; lp/lm = 1e-6 + [-g]_+ / [g]_+     (interior_point.py:180-186)
 __global__ void ip_init_kernel(int64_t N, ipv V) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             const double g = V.Qx[i] + V.q[i];
             V.g[i] = g;
@@ -80,7 +37,7 @@ __global__ void ip_init_kernel(int64_t N, ipv V) {
 __global__ void ip_update_kernel(int64_t N, ipv V, const bq_scal *sc) {
     if (sc->done) return;
     const double t = sc->step;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             V.x[i] = V.x[i] + __dmul_rn(t, V.dx[i]);
             V.lp[i] = V.lp[i] + __dmul_rn(t, V.dlp[i]);
@@ -93,7 +50,7 @@ __global__ void ip_eval_kernel(int64_t N, ipv V, const bq_scal *sc, double *__re
     if (sc->done) return;
     __shared__ double sh[4];
     double xr = 0.0, qx = 0.0, lu = 0.0, ll = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             const double x = V.x[i];
             xr += x * V.Qx[i];
@@ -102,15 +59,15 @@ __global__ void ip_eval_kernel(int64_t N, ipv V, const bq_scal *sc, double *__re
             ll += V.lm[i] * V.lb[i];
         }
     }
-    xr = ip_bsum(xr, sh);
-    qx = ip_bsum(qx, sh);
-    lu = ip_bsum(lu, sh);
-    ll = ip_bsum(ll, sh);
+    xr = bq_block_sum(xr, sh);
+    qx = bq_block_sum(qx, sh);
+    lu = bq_block_sum(lu, sh);
+    ll = bq_block_sum(ll, sh);
     if (threadIdx.x == 0) {
-        part[0 * nblk + blockIdx.x] = xr;
-        part[1 * nblk + blockIdx.x] = qx;
-        part[2 * nblk + blockIdx.x] = lu;
-        part[3 * nblk + blockIdx.x] = ll;
+        bq_part_put(&part[0 * nblk + blockIdx.x], xr);
+        bq_part_put(&part[1 * nblk + blockIdx.x], qx);
+        bq_part_put(&part[2 * nblk + blockIdx.x], lu);
+        bq_part_put(&part[3 * nblk + blockIdx.x], ll);
     }
 }
 
@@ -118,10 +75,10 @@ __global__ void ip_decide_kernel(bq_scal *sc, int64_t N, const double *__restric
                                  bq_iter_stat *stats) {
     if (sc->done) return;
     __shared__ double sh[4];
-    const double xr = ip_fsum(part + 0 * nblk, nblk, sh);
-    const double qx = ip_fsum(part + 1 * nblk, nblk, sh);
-    const double lu = ip_fsum(part + 2 * nblk, nblk, sh);
-    const double ll = ip_fsum(part + 3 * nblk, nblk, sh);
+    const double xr = bq_final_sum(part + 0 * nblk, nblk, sh);
+    const double qx = bq_final_sum(part + 1 * nblk, nblk, sh);
+    const double lu = bq_final_sum(part + 2 * nblk, nblk, sh);
+    const double ll = bq_final_sum(part + 3 * nblk, nblk, sh);
     if (threadIdx.x == 0) {
         const double f = 0.5 * xr + qx;
         const double p = -lu + ll - 0.5 * xr;
@@ -157,7 +114,7 @@ __global__ void ip_decide_kernel(bq_scal *sc, int64_t N, const double *__restric
 __global__ void ip_prep_kernel(int64_t N, ipv V, const bq_scal *sc, double *__restrict__ w_out) {
     if (sc->done) return;
     const double mu = sc->mu;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             const double x = V.x[i], ub = V.ub[i], lb = V.lb[i], lp = V.lp[i], lm = V.lm[i];
             const double umx = ub - x, xml = x - lb;
@@ -174,7 +131,7 @@ __global__ void ip_ratio_kernel(int64_t N, ipv V, const bq_scal *sc, const doubl
     __shared__ double sh[4];
     const double mu = sc->mu;
     double rmin = INFINITY;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             const double x = V.x[i], ub = V.ub[i], lb = V.lb[i], lp = V.lp[i], lm = V.lm[i], dx = dxs[i];
             const double umx = ub - x, xml = x - lb;
@@ -189,15 +146,15 @@ __global__ void ip_ratio_kernel(int64_t N, ipv V, const bq_scal *sc, const doubl
             if (dlm < 0.0) rmin = fmin(rmin, -lm / dlm);
         }
     }
-    rmin = ip_bmin(rmin, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = rmin;
+    rmin = bq_block_min(rmin, sh);
+    if (threadIdx.x == 0) bq_part_put(&part[blockIdx.x], rmin);
 }
 
 __global__ void ip_step_kernel(bq_scal *sc, const double *__restrict__ part, int64_t nblk, const int *__restrict__ info,
                                bq_iter_stat *stats) {
     if (sc->done) return;
     __shared__ double sh[4];
-    const double rmin = ip_fmin(part, nblk, sh);
+    const double rmin = bq_final_min(part, nblk, sh);
     if (threadIdx.x == 0) {
         if (*info != 0) {
             sc->status = BQ_ERR_NOT_PD;
@@ -230,7 +187,7 @@ __global__ void ip_copy_kernel(int64_t n, const double *__restrict__ src, double
 __global__ void ip_svr_reduce_kernel(int64_t n, const double *__restrict__ hd, const double *__restrict__ w,
                                      double *__restrict__ cdiag, double *__restrict__ t, const bq_scal *sc) {
     if (sc->done) return;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         double c = 0.0, tv = 0.0;
         if (i < n) {
             const double d1 = hd[i], d2 = hd[n + i], inv = 1.0 / (d1 + d2);
@@ -253,7 +210,7 @@ __global__ void ip_svr_rhs_kernel(int64_t n, int64_t np, const double *__restric
 __global__ void ip_svr_expand_kernel(int64_t n, const double *__restrict__ hd, const double *__restrict__ u,
                                      double *__restrict__ w, const bq_scal *sc) {
     if (sc->done) return;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < n) {
             const double d1 = hd[i], d2 = hd[n + i], inv = 1.0 / (d1 + d2);
             const double sum = w[i] + w[n + i], ui = u[i];
@@ -291,7 +248,7 @@ static ipv ip_vecs(bq_solver *s) {
 int bq_ip_start(bq_solver *s) {
     hipStream_t st = s->p->ctx->stream;
     BQ_TRY(bq_problem_apply(s->p, s->x, s->Qd, nullptr));
-    ip_init_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, ip_vecs(s));
+    ip_init_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, ip_vecs(s));
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
@@ -302,12 +259,12 @@ int bq_ip_iterate(bq_solver *s) {
     bq_chol_ws *ws = s->chol;
     const int *done = &s->sc->done;
     ipv V = ip_vecs(s);
-    if (s->started) ip_update_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc);
+    if (s->started) ip_update_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc);
     s->started = true;
     BQ_TRY(bq_problem_apply(s->p, s->x, s->Qd, done));
-    ip_eval_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, s->partials, s->nblk);
+    ip_eval_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, s->partials, s->nblk);
     ip_decide_kernel<<<1, BQ_VEC_BLOCK, 0, st>>>(s->sc, s->N, s->partials, s->nblk, s->stats);
-    ip_prep_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, s->rhs);
+    ip_prep_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, s->rhs);
     // The factorisation below is host-enqueued and cannot early-exit on the device flag; after `done` it works on
     // stale data and its result is ignored by the (early-exiting) consumers.
     int64_t np = 0;
@@ -315,19 +272,19 @@ int bq_ip_iterate(bq_solver *s) {
         bq_problem *p = s->p;
         const int64_t n = p->n;
         double *cdiag = s->dlp;   // scratch until ip_ratio_kernel rewrites dlp
-        ip_svr_reduce_kernel<<<vgrid(p->ld), BQ_VEC_BLOCK, 0, st>>>(n, s->hd, s->rhs, cdiag, p->w, s->sc);
+        ip_svr_reduce_kernel<<<bq_vec_grid(p->ld), BQ_VEC_BLOCK, 0, st>>>(n, s->hd, s->rhs, cdiag, p->w, s->sc);
         BQ_TRY(bq_chol_build_h(ws, p, nullptr, n, cdiag, &np, false, BQ_H_KPLUS1));
         ip_svr_rhs_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(n, np, p->w, ws->rhs, s->sc);
         BQ_TRY(bq_chol_factor(ws, np));
         BQ_TRY(bq_chol_solve(ws, np));
-        ip_svr_expand_kernel<<<vgrid(p->ld), BQ_VEC_BLOCK, 0, st>>>(n, s->hd, ws->rhs, s->rhs, s->sc);
-        ip_ratio_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, s->rhs, s->partials);
+        ip_svr_expand_kernel<<<bq_vec_grid(p->ld), BQ_VEC_BLOCK, 0, st>>>(n, s->hd, ws->rhs, s->rhs, s->sc);
+        ip_ratio_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, s->rhs, s->partials);
     } else {
         BQ_TRY(bq_chol_build_h(ws, s->p, nullptr, s->N, s->hd, &np));
         ip_copy_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(s->N, s->rhs, ws->rhs, np, s->sc);
         BQ_TRY(bq_chol_factor(ws, np));
         BQ_TRY(bq_chol_solve(ws, np));
-        ip_ratio_kernel<<<vgrid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, ws->rhs, s->partials);
+        ip_ratio_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, V, s->sc, ws->rhs, s->partials);
     }
     ip_step_kernel<<<1, BQ_VEC_BLOCK, 0, st>>>(s->sc, s->partials, s->nblk, ws->info, s->stats);
     BQ_HIP(hipGetLastError());

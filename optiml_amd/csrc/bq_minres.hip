@@ -11,31 +11,15 @@
 #include <cstdlib>
 
 #include "bq_chol.h"
+#include "bq_minres_rec.h"
+#include "bq_reduce.h"
 
 constexpr int MT = 1024;   // threads of the persistent workgroup
-
-__device__ __forceinline__ double mr_wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// every thread receives the block-wide sum (fixed order)
-__device__ __forceinline__ double mr_bsum(double v, double *sh) {
-    v = mr_wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int w = 0; w < MT / 64; ++w) r += sh[w];
-    return r;
-}
 
 __device__ __forceinline__ double mr_dot(const double *a, const double *b, int n, double *sh) {
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += MT) s = fma(a[i], b[i], s);
-    return mr_bsum(s, sh);
+    return bq_block_sum<MT / 64>(s, sh);
 }
 
 // y = H x for the symmetric n x n matrix H (row pitch ld): one wave per row, lanes along the columns
@@ -45,7 +29,7 @@ __device__ __forceinline__ void mr_matvec(const double *__restrict__ H, int64_t 
         const double *row = H + (int64_t)r * ld;
         double s = 0.0;
         for (int c = lane; c < n; c += 64) s = fma(row[c], x[c], s);
-        s = mr_wsum(s);
+        s = bq_wave_sum(s);
         if (lane == 0) y[r] = s;
     }
     __syncthreads();
@@ -61,7 +45,6 @@ __global__ __launch_bounds__(MT) void minres_normal_kernel(const double *__restr
     // Ra/Rb/Rc rotate through the roles (r1, r2 = y, next Lanczos vector) of the three-term recurrence
     double *b = vec, *x = vec + np, *Ra = vec + 2 * np, *Rb = vec + 3 * np, *Rc = vec + 4 * np, *v = vec + 5 * np,
            *w = vec + 6 * np, *w1 = vec + 7 * np, *w2 = vec + 8 * np, *tmp = vec + 9 * np;
-    const double eps = 2.220446049250313e-16;
     const int maxiter = 5 * n;
 
     // b = H q'   (= -(Q_AA^T q_A));  x = 0;  r1 = b;  y = r1
@@ -73,30 +56,27 @@ __global__ __launch_bounds__(MT) void minres_normal_kernel(const double *__restr
         w2[i] = 0.0;
     }
     __syncthreads();
-    double beta1 = mr_dot(Ra, Ra, n, sh);
+    bq_minres_rec m;
+    m.start(mr_dot(Ra, Ra, n, sh));
     int itn = 0;
-    if (beta1 > 0.0) {   // beta1 == 0: the exact solution is x0 = 0 (also covers b == 0)
-        beta1 = sqrt(beta1);
-        double oldb = 0.0, beta = beta1, dbar = 0.0, epsln = 0.0, phibar = beta1, rhs1 = beta1, rhs2 = 0.0;
-        double tnorm2 = 0.0, gmax = 0.0, gmin = 1.7976931348623157e308, cs = -1.0, sn = 0.0;
+    if (m.beta1 > 0.0) {   // beta1 == 0: the exact solution is x0 = 0 (also covers b == 0)
         double *r1p = Ra, *r2p = Ra, *y = Ra;   // r1 = b, r2 = r1, y = psolve(r1) = r1
-        int istop = 0;
         while (itn < maxiter) {
             itn += 1;
-            const double s = 1.0 / beta;
+            const double s = 1.0 / m.beta;
             for (int i = tid; i < n; i += MT) v[i] = s * y[i];
             __syncthreads();
             mr_matvec(H, ld, n, v, tmp);     // operator = H H^T = H H
             double *ynew = (Ra != r1p && Ra != r2p) ? Ra : ((Rb != r1p && Rb != r2p) ? Rb : Rc);
             mr_matvec(H, ld, n, tmp, ynew);
             if (itn >= 2) {
-                const double c = beta / oldb;
+                const double c = m.beta / m.oldb;
                 for (int i = tid; i < n; i += MT) ynew[i] = ynew[i] - c * r1p[i];
                 __syncthreads();
             }
             const double alfa = mr_dot(v, ynew, n, sh);
             {
-                const double c = alfa / beta;
+                const double c = alfa / m.beta;
                 for (int i = tid; i < n; i += MT) ynew[i] = ynew[i] - c * r2p[i];
                 __syncthreads();
             }
@@ -104,28 +84,10 @@ __global__ __launch_bounds__(MT) void minres_normal_kernel(const double *__restr
             r1p = r2p;
             r2p = ynew;
             y = ynew;
-            oldb = beta;
-            beta = mr_dot(r2p, y, n, sh);
-            if (beta < 0.0) {
-                istop = 7;
-                break;
-            }
-            beta = sqrt(beta);
-            tnorm2 += alfa * alfa + oldb * oldb + beta * beta;
-            if (itn == 1 && beta / beta1 <= 10.0 * eps) istop = -1;
-            const double oldeps = epsln;
-            const double delta = cs * dbar + sn * alfa;
-            const double gbar = sn * dbar - cs * alfa;
-            epsln = sn * beta;
-            dbar = -cs * beta;
-            const double root = hypot(gbar, dbar);
-            double gamma = hypot(gbar, beta);
-            gamma = fmax(gamma, eps);
-            cs = gbar / gamma;
-            sn = beta / gamma;
-            const double phi = cs * phibar;
-            phibar = sn * phibar;
-            const double denom = 1.0 / gamma;
+            const double beta2 = mr_dot(r2p, y, n, sh);
+            if (beta2 < 0.0) break;   // scipy's istop = 7
+            m.rotate(alfa, beta2, itn);
+            const double oldeps = m.oldeps, delta = m.delta, denom = m.denom, phi = m.phi;
             // w1 = w2; w2 = w; w = (v - oldeps*w1 - delta*w2) * denom; x += phi*w
             double *wold = w1;
             w1 = w2;
@@ -139,29 +101,7 @@ __global__ __launch_bounds__(MT) void minres_normal_kernel(const double *__restr
                 x[i] = xi;
                 xn = fma(xi, xi, xn);
             }
-            const double ynorm = sqrt(mr_bsum(xn, sh));
-            gmax = fmax(gmax, gamma);
-            gmin = fmin(gmin, gamma);
-            const double z = rhs1 / gamma;
-            rhs1 = rhs2 - delta * z;
-            rhs2 = -epsln * z;
-            const double Anorm = sqrt(tnorm2);
-            const double epsx = Anorm * ynorm * eps;
-            const double rnorm = phibar;
-            const double test1 = (ynorm == 0.0 || Anorm == 0.0) ? INFINITY : rnorm / (Anorm * ynorm);
-            const double test2 = (Anorm == 0.0) ? INFINITY : root / Anorm;
-            const double Acond = gmax / gmin;
-            if (istop == 0) {
-                const double t1 = 1.0 + test1, t2 = 1.0 + test2;
-                if (t2 <= 1.0) istop = 2;
-                if (t1 <= 1.0) istop = 1;
-                if (itn >= maxiter) istop = 6;
-                if (Acond >= 0.1 / eps) istop = 4;
-                if (epsx >= beta1) istop = 3;
-                if (test2 <= rtol) istop = 2;
-                if (test1 <= rtol) istop = 1;
-            }
-            if (istop != 0) break;
+            if (m.stop(bq_block_sum<MT / 64>(xn, sh), itn, maxiter, rtol) != 0) break;
         }
     }
     __syncthreads();
@@ -177,14 +117,14 @@ __global__ __launch_bounds__(MT) void minres_normal_kernel(const double *__restr
 // host enqueues batches of iterations blind and looks at the `done` flag between batches; kernels early-exit on it.
 // ---------------------------------------------------------------------------------------------------------------
 struct mr_state {
-    double beta1, oldb, beta, dbar, epsln, phibar, rhs1, rhs2, tnorm2, gmax, gmin, cs, sn;
-    double alfa, oldeps, delta, denom, phi, root, rtol;
+    bq_minres_rec r;
+    double rtol;
     long long itn, maxiter;
-    int istop, done;
+    int done;
     unsigned int ticket[4];
 };
 
-constexpr int MV_T = 256, MV_ITEMS = 4, MV_TILE = MV_T * MV_ITEMS;
+constexpr int MV_T = BQ_VEC_BLOCK;   // the vector kernels walk BQ_VEC_LOOP; np is a multiple of 128 only: `i < np` at every use
 typedef double mr_d2 __attribute__((ext_vector_type(2)));
 
 // y[r] = sum_c H[r][c] x[c], c < np (np a multiple of 128; rows are 16-byte aligned): one workgroup per 4 rows
@@ -208,79 +148,50 @@ __global__ __launch_bounds__(MV_T) void mr_gemv_kernel(const double *__restrict_
     __shared__ double red[4][R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const double s = mr_wsum(acc[r]);
+        const double s = bq_wave_sum(acc[r]);
         if (lane == 0) red[wv][r] = s;
     }
     __syncthreads();
     if (tid < R && r0 + tid < np) y[r0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// block-wide sum for the 256-thread vector kernels: every thread receives it
-__device__ __forceinline__ double mv_bsum(double v, double *sh) {
-    v = mr_wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-// partial -> part[block]; the block that takes the last ticket gets the total (fixed order), the others NAN-flag false
+// partial -> part[block]; the block that takes the last ticket gets the total (fixed order), the others false
 __device__ __forceinline__ bool mv_total(double local, double *part, unsigned int *ticket, double *sh, double *total) {
-    const double b = mv_bsum(local, sh);
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = b;
-        __threadfence();   // this block's partial is visible device-wide before the ticket is taken ...
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (the compiler may drop the fence's own wait)
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-    }
-    __syncthreads();
-    if (!last) return false;
-    __threadfence();
-    double a = 0.0;
-    for (unsigned int i = threadIdx.x; i < gridDim.x; i += MV_T)
-        a += __hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *total = mv_bsum(a, sh);
-    if (threadIdx.x == 0) *ticket = 0u;
+    const double b = bq_block_sum(local, sh);
+    if (threadIdx.x == 0) bq_part_put(&part[blockIdx.x], b);
+    if (!bq_last_block(ticket, gridDim.x)) return false;
+    *total = bq_final_sum(part, gridDim.x, sh);
     return true;
 }
-
-#define MV_LOOP(i)                                                        \
-    const int64_t _b = (int64_t)blockIdx.x * MV_TILE + threadIdx.x;       \
-    _Pragma("unroll") for (int _j = 0; _j < MV_ITEMS; ++_j)               \
-        for (int64_t i = _b + (int64_t)_j * MV_T, _o = 1; _o && i < np; _o = 0)
 
 // b = H q' is in Ra already: x = 0, w = w2 = 0, |b|^2 -> beta1 and the start values of the recurrences
 __global__ __launch_bounds__(MV_T) void mr_init_kernel(int64_t np, const double *__restrict__ Ra, double *x, double *W0,
                                                        double *W2, double *part, mr_state *st, long long maxiter, double rtol) {
     __shared__ double sh[4];
     double s = 0.0;
-    MV_LOOP(i) {
-        x[i] = 0.0;
-        W0[i] = 0.0;
-        W2[i] = 0.0;
-        s = fma(Ra[i], Ra[i], s);
+    BQ_VEC_LOOP(i) {
+        if (i < np) {
+            x[i] = 0.0;
+            W0[i] = 0.0;
+            W2[i] = 0.0;
+            s = fma(Ra[i], Ra[i], s);
+        }
     }
     double tot;
     if (mv_total(s, part, &st->ticket[0], sh, &tot) && threadIdx.x == 0) {
-        mr_state t;
-        memset(&t, 0, sizeof(t));
-        t.beta1 = tot > 0.0 ? sqrt(tot) : 0.0;
-        t.beta = t.beta1;
-        t.phibar = t.beta1;
-        t.rhs1 = t.beta1;
-        t.gmin = 1.7976931348623157e308;
-        t.cs = -1.0;
-        t.maxiter = maxiter;
-        t.rtol = rtol;
-        t.done = tot > 0.0 ? 0 : 1;   // beta1 == 0: the exact solution is x0 = 0
-        *st = t;
+        st->r.start(tot);   // the host zeroed the state (tickets, itn) before the first product
+        st->maxiter = maxiter;
+        st->rtol = rtol;
+        st->done = tot > 0.0 ? 0 : 1;   // beta1 == 0: the exact solution is x0 = 0
     }
 }
 
 __global__ __launch_bounds__(MV_T) void mr_scale_kernel(int64_t np, const double *__restrict__ y, double *v, const mr_state *st) {
     if (st->done) return;
-    const double s = 1.0 / st->beta;
-    MV_LOOP(i) v[i] = s * y[i];
+    const double s = 1.0 / st->r.beta;
+    BQ_VEC_LOOP(i) {
+        if (i < np) v[i] = s * y[i];
+    }
 }
 
 // after ynew = H H v:  [ynew -= (beta / oldb) r1];  alfa = v . ynew
@@ -288,18 +199,20 @@ __global__ __launch_bounds__(MV_T) void mr_alfa_kernel(int64_t np, int sub_r1, c
                                                        const double *__restrict__ r1, double *part, mr_state *st) {
     if (st->done) return;
     __shared__ double sh[4];
-    const double c = sub_r1 ? st->beta / st->oldb : 0.0;
+    const double c = sub_r1 ? st->r.beta / st->r.oldb : 0.0;
     double s = 0.0;
-    MV_LOOP(i) {
-        double y = ynew[i];
-        if (sub_r1) {
-            y = y - c * r1[i];
-            ynew[i] = y;
+    BQ_VEC_LOOP(i) {
+        if (i < np) {
+            double y = ynew[i];
+            if (sub_r1) {
+                y = y - c * r1[i];
+                ynew[i] = y;
+            }
+            s = fma(v[i], y, s);
         }
-        s = fma(v[i], y, s);
     }
     double tot;
-    if (mv_total(s, part, &st->ticket[1], sh, &tot) && threadIdx.x == 0) st->alfa = tot;
+    if (mv_total(s, part, &st->ticket[1], sh, &tot) && threadIdx.x == 0) st->r.alfa = tot;
 }
 
 // ynew -= (alfa / beta) r2;  beta' = |ynew|;  the Givens rotation and everything scalar up to the solution update
@@ -307,40 +220,20 @@ __global__ __launch_bounds__(MV_T) void mr_beta_kernel(int64_t np, long long itn
                                                        double *part, mr_state *st) {
     if (st->done) return;
     __shared__ double sh[4];
-    const double c = st->alfa / st->beta;
+    const double c = st->r.alfa / st->r.beta;
     double s = 0.0;
-    MV_LOOP(i) {
-        const double y = ynew[i] - c * r2[i];
-        ynew[i] = y;
-        s = fma(y, y, s);
+    BQ_VEC_LOOP(i) {
+        if (i < np) {
+            const double y = ynew[i] - c * r2[i];
+            ynew[i] = y;
+            s = fma(y, y, s);
+        }
     }
     double tot;
     if (mv_total(s, part, &st->ticket[2], sh, &tot) && threadIdx.x == 0) {
-        const double eps = 2.220446049250313e-16;
-        mr_state t = *st;
-        t.oldb = t.beta;
-        t.beta = sqrt(tot);
-        t.tnorm2 += t.alfa * t.alfa + t.oldb * t.oldb + t.beta * t.beta;
-        if (itn == 1 && t.beta / t.beta1 <= 10.0 * eps) t.istop = -1;
-        t.oldeps = t.epsln;
-        t.delta = t.cs * t.dbar + t.sn * t.alfa;
-        const double gbar = t.sn * t.dbar - t.cs * t.alfa;
-        t.epsln = t.sn * t.beta;
-        t.dbar = -t.cs * t.beta;
-        t.root = hypot(gbar, t.dbar);
-        double gamma = hypot(gbar, t.beta);
-        gamma = fmax(gamma, eps);
-        t.cs = gbar / gamma;
-        t.sn = t.beta / gamma;
-        t.phi = t.cs * t.phibar;
-        t.phibar = t.sn * t.phibar;
-        t.denom = 1.0 / gamma;
-        t.gmax = fmax(t.gmax, gamma);
-        t.gmin = fmin(t.gmin, gamma);
-        const double z = t.rhs1 / gamma;
-        t.rhs1 = t.rhs2 - t.delta * z;
-        t.rhs2 = -t.epsln * z;
-        *st = t;
+        bq_minres_rec r = st->r;
+        r.rotate(r.alfa, tot, itn);
+        st->r = r;
     }
 }
 
@@ -350,42 +243,23 @@ __global__ __launch_bounds__(MV_T) void mr_update_kernel(int64_t np, long long i
                                                          double *x, double *part, mr_state *st) {
     if (st->done) return;
     __shared__ double sh[4];
-    const double oldeps = st->oldeps, delta = st->delta, denom = st->denom, phi = st->phi, beta = st->beta;
+    const double oldeps = st->r.oldeps, delta = st->r.delta, denom = st->r.denom, phi = st->r.phi, beta = st->r.beta;
     const double nexts = beta > 0.0 ? 1.0 / beta : 0.0;
     double s = 0.0;
-    MV_LOOP(i) {
-        const double wn = (v[i] - oldeps * w1[i] - delta * w2[i]) * denom;
-        w[i] = wn;
-        const double xi = x[i] + phi * wn;
-        x[i] = xi;
-        s = fma(xi, xi, s);
-        v[i] = nexts * ynew[i];
+    BQ_VEC_LOOP(i) {
+        if (i < np) {
+            const double wn = (v[i] - oldeps * w1[i] - delta * w2[i]) * denom;
+            w[i] = wn;
+            const double xi = x[i] + phi * wn;
+            x[i] = xi;
+            s = fma(xi, xi, s);
+            v[i] = nexts * ynew[i];
+        }
     }
     double tot;
     if (mv_total(s, part, &st->ticket[3], sh, &tot) && threadIdx.x == 0) {
-        const double eps = 2.220446049250313e-16;
-        mr_state t = *st;
-        const double ynorm = sqrt(tot);
-        const double Anorm = sqrt(t.tnorm2);
-        const double epsx = Anorm * ynorm * eps;
-        const double rnorm = t.phibar;
-        const double test1 = (ynorm == 0.0 || Anorm == 0.0) ? INFINITY : rnorm / (Anorm * ynorm);
-        const double test2 = (Anorm == 0.0) ? INFINITY : t.root / Anorm;
-        const double Acond = t.gmax / t.gmin;
-        int istop = t.istop;
-        if (istop == 0) {
-            const double t1 = 1.0 + test1, t2 = 1.0 + test2;
-            if (t2 <= 1.0) istop = 2;
-            if (t1 <= 1.0) istop = 1;
-            if (itn >= t.maxiter) istop = 6;
-            if (Acond >= 0.1 / eps) istop = 4;
-            if (epsx >= t.beta1) istop = 3;
-            if (test2 <= t.rtol) istop = 2;
-            if (test1 <= t.rtol) istop = 1;
-        }
         st->itn = itn;
-        st->istop = istop;
-        if (istop != 0) {
+        if (st->r.stop(tot, itn, st->maxiter, st->rtol) != 0) {
             __threadfence();
             st->done = 1;
         }
@@ -395,13 +269,15 @@ __global__ __launch_bounds__(MV_T) void mr_update_kernel(int64_t np, long long i
 __global__ __launch_bounds__(MV_T) void mr_finish_kernel(int64_t np, const int *nA_ptr, const double *__restrict__ x, double *rhs,
                                                          const mr_state *st, int *iters) {
     const int n = *nA_ptr;
-    MV_LOOP(i) rhs[i] = i < n ? x[i] : 0.0;
+    BQ_VEC_LOOP(i) {
+        if (i < np) rhs[i] = i < n ? x[i] : 0.0;
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0 && iters) *iters = (int)st->itn;
 }
 
 static int minres_normal_big(bq_chol_ws *ws, const int *nA_dev, int64_t nA, int64_t np, double *vec, int *iters_dev) {
     hipStream_t stm = ws->ctx->stream;
-    const unsigned vb = (unsigned)((np + MV_TILE - 1) / MV_TILE), gb = (unsigned)((np + 3) / 4);
+    const unsigned vb = (unsigned)((np + BQ_VEC_TILE - 1) / BQ_VEC_TILE), gb = (unsigned)((np + 3) / 4);
     if (!ws->mr_state) {
         ws->mr_state = ws->mem.dev<char>(256);
         BQ_HIP(ws->mem.error());

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "bq_common.h"
+#include "bq_reduce.h"
 
 extern "C" int bq_problem_time_matvec(bq_problem *p, int reps, double *mean_ms) {
     BQ_ARG(p && mean_ms && reps > 0, "argument");
@@ -188,4 +189,55 @@ extern "C" int bq_ctx_probe_stall(bq_ctx *c, double milliseconds, int behind_col
     int rc = hipGetLastError() == hipSuccess ? BQ_OK : BQ_ERR_HIP;
     if (rc == BQ_OK && behind_collective) rc = bq_exchange_sum(c, one, 1);
     return bq_ctx_sync_after(c, rc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The last-block hand-off of bq_reduce.h, checked word by word: `rounds` launches back to back on the stream, no host
+// synchronisation between them.  In a launch block b puts one partial that depends on (b, round) and takes the ticket; the
+// workgroup that arrives last compares EVERY partial with its expected word.  `uneven`: a block-dependent amount of ALU work
+// first, so that the arrival order differs from the block order.  Every block first reads the partials of the previous round
+// with plain loads (the consumer's L1 is warm with words that must NOT be seen again).  No block waits for another.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double probe_word(unsigned int b, int round) {
+    return (double)(((unsigned long long)(b + 1u) << 20) | (unsigned long long)round);
+}
+__global__ __launch_bounds__(BQ_VEC_BLOCK) void probe_last_block_kernel(double *part, int round, int uneven, unsigned int *ticket,
+                                                                        unsigned long long *bad) {
+    const unsigned int b = blockIdx.x, nb = gridDim.x;
+    double warm = 0.0;   // racing plain loads on purpose: the values are discarded, only the cache lines matter
+    for (unsigned int i = threadIdx.x; i < nb; i += BQ_VEC_BLOCK) warm += part[i];
+    asm volatile("" ::"v"(warm));
+    if (uneven) {
+        unsigned int h = b, spins = ((b * 2654435761u) >> 22) * 4u;   // 0 .. 4092 steps
+        for (unsigned int k = 0; k < spins; ++k) h = h * 1664525u + 1013904223u;
+        asm volatile("" ::"v"(h));
+    }
+    if (threadIdx.x == 0) bq_part_put(&part[b], probe_word(b, round));
+    if (!bq_last_block(ticket, nb)) return;
+    unsigned int wrong = 0;
+    for (unsigned int i = threadIdx.x; i < nb; i += BQ_VEC_BLOCK) wrong += bq_part_get(&part[i]) != probe_word(i, round) ? 1u : 0u;
+    if (wrong) atomicAdd(bad, (unsigned long long)wrong);
+}
+
+extern "C" int bq_ctx_probe_last_block(bq_ctx *c, int blocks, int rounds, int uneven, int64_t *bad_words, int *ticket_after) {
+    BQ_ARG(c != nullptr && bad_words != nullptr && ticket_after != nullptr, "NULL argument");
+    BQ_ARG(blocks >= 1 && blocks <= 65536, "blocks in [1, 65536]");
+    BQ_ARG(rounds >= 1 && rounds <= 100000, "rounds in [1, 100000]");
+    BQ_HIP(hipSetDevice(c->device));
+    bq_scratch mem;
+    double *part = nullptr;
+    unsigned long long *state = nullptr;   // [0] mismatches, [1] the ticket (its low word)
+    BQ_HIP(bq_dev_zeroed(hipSuccess, mem, &part, (size_t)blocks, c->stream));
+    BQ_HIP(bq_dev_zeroed(hipSuccess, mem, &state, 2, c->stream));
+    unsigned int *ticket = reinterpret_cast<unsigned int *>(state + 1);
+    for (int r = 1; r <= rounds; ++r)
+        probe_last_block_kernel<<<(unsigned)blocks, BQ_VEC_BLOCK, 0, c->stream>>>(part, r, uneven, ticket, state);
+    int rc = hipGetLastError() == hipSuccess ? BQ_OK : BQ_ERR_HIP;
+    unsigned long long host[2] = {0, 0};
+    if (rc == BQ_OK && hipMemcpyAsync(host, state, sizeof(host), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BQ_ERR_HIP;
+    rc = bq_ctx_sync_after(c, rc);
+    if (rc != BQ_OK) return rc;
+    *bad_words = (int64_t)host[0];
+    *ticket_after = (int)(unsigned int)host[1];
+    return BQ_OK;
 }

@@ -13,36 +13,11 @@
 // (all under optiml/opti/constrained/), objective/gradient optiml/opti/_base.py:282,291.
 #include "bq_common.h"
 #include "bq_epilogue.h"
+#include "bq_reduce.h"
 
 #include <cmath>
 #include <cstdlib>
 
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-// all threads of a 256-thread block get the result
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    v = wsum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double final_sum(const double *part, int64_t nblk, double *sh) {
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < nblk; i += BQ_VEC_BLOCK) a += part[i];
-    return block_sum(a, sh);
-}
-#define VEC_LOOP(i)                                                             \
-    const int64_t _base = (int64_t)blockIdx.x * BQ_VEC_TILE + threadIdx.x;      \
-    _Pragma("unroll") for (int _j = 0; _j < BQ_VEC_ITEMS; ++_j)                 \
-        for (int64_t i = _base + (int64_t)_j * BQ_VEC_BLOCK, _once = 1; _once; _once = 0)
-
-static inline dim3 vec_grid(int64_t ldN) { return dim3((unsigned)(ldN / BQ_VEC_TILE)); }
 
 // ---------------------------------------------------------------------------------------------
 // Hessian application: prep (v -> panel input w), finish (gathered panel output s -> Q v)
@@ -50,7 +25,7 @@ static inline dim3 vec_grid(int64_t ldN) { return dim3((unsigned)(ldN / BQ_VEC_T
 __global__ void prep_kernel(int structure, int64_t n, const double *__restrict__ v, const double *__restrict__ sgn,
                             double *__restrict__ w, const int *done) {
     if (done != nullptr && *done) return;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         double r = 0.0;
         if (i < n) r = (structure == BQ_SVC) ? sgn[i] * v[i] : v[i] - v[n + i];
         w[i] = r;
@@ -61,7 +36,7 @@ __global__ void finish_kernel(int structure, int64_t n, int64_t N, double diag_a
                               const double *__restrict__ v, const double *__restrict__ sgn, double *__restrict__ out,
                               const int *done) {
     if (done != nullptr && *done) return;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         double r = 0.0;
         if (i < N) {
             if (structure == BQ_PLAIN)
@@ -132,7 +107,7 @@ int bq_panel_product(bq_problem *p, bool add_one, const double *w, const int *do
 }
 
 int bq_launch_prep(bq_problem *p, const double *v, const int *done) {
-    prep_kernel<<<vec_grid(p->ld), BQ_VEC_BLOCK, 0, p->ctx->stream>>>(p->structure, p->n, v, p->sgn, p->w, done);
+    prep_kernel<<<bq_vec_grid(p->ld), BQ_VEC_BLOCK, 0, p->ctx->stream>>>(p->structure, p->n, v, p->sgn, p->w, done);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }
@@ -141,11 +116,11 @@ int bq_problem_apply(bq_problem *p, const double *v, double *out, const int *don
     bq_ctx *ctx = p->ctx;
     const double *w = v;
     if (p->structure != BQ_PLAIN) {
-        prep_kernel<<<vec_grid(p->ld), BQ_VEC_BLOCK, 0, ctx->stream>>>(p->structure, p->n, v, p->sgn, p->w, done);
+        prep_kernel<<<bq_vec_grid(p->ld), BQ_VEC_BLOCK, 0, ctx->stream>>>(p->structure, p->n, v, p->sgn, p->w, done);
         w = p->w;
     }
     BQ_TRY(bq_panel_product(p, p->add_one, w, done));
-    finish_kernel<<<vec_grid(p->ldN), BQ_VEC_BLOCK, 0, ctx->stream>>>(p->structure, p->n, p->N, p->diag_add, p->s, v,
+    finish_kernel<<<bq_vec_grid(p->ldN), BQ_VEC_BLOCK, 0, ctx->stream>>>(p->structure, p->n, p->N, p->diag_add, p->s, v,
                                                                       p->sgn, out, done);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
@@ -157,30 +132,30 @@ __global__ void evalf_partial_kernel(int64_t N, const double *__restrict__ x, co
                                      int64_t nblk) {
     __shared__ double sh[4];
     double a = 0.0, b = 0.0;
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) {
             a += x[i] * Qx[i];
             b += q[i] * x[i];
             if (g != nullptr) g[i] = Qx[i] + q[i];
         }
     }
-    a = block_sum(a, sh);
-    b = block_sum(b, sh);
+    a = bq_block_sum(a, sh);
+    b = bq_block_sum(b, sh);
     if (threadIdx.x == 0) {
-        part[blockIdx.x] = a;
-        part[nblk + blockIdx.x] = b;
+        bq_part_put(&part[blockIdx.x], a);
+        bq_part_put(&part[nblk + blockIdx.x], b);
     }
 }
 __global__ void evalf_final_kernel(const double *part, int64_t nblk, double *f) {
     __shared__ double sh[4];
-    double a = final_sum(part, nblk, sh);
-    double b = final_sum(part + nblk, nblk, sh);
+    double a = bq_final_sum(part, nblk, sh);
+    double b = bq_final_sum(part + nblk, nblk, sh);
     if (threadIdx.x == 0) *f = 0.5 * a + b;
 }
 
 int bq_vec_eval_f(bq_problem *p, const double *x, const double *Qx, double *g_out, double *f_dev) {
     const int64_t nblk = p->ldN / BQ_VEC_TILE;
-    evalf_partial_kernel<<<vec_grid(p->ldN), BQ_VEC_BLOCK, 0, p->ctx->stream>>>(p->N, x, Qx, p->q, g_out, p->partials, nblk);
+    evalf_partial_kernel<<<bq_vec_grid(p->ldN), BQ_VEC_BLOCK, 0, p->ctx->stream>>>(p->N, x, Qx, p->q, g_out, p->partials, nblk);
     evalf_final_kernel<<<1, BQ_VEC_BLOCK, 0, p->ctx->stream>>>(p->partials, nblk, f_dev);
     BQ_HIP(hipGetLastError());
     return BQ_OK;
@@ -195,7 +170,7 @@ struct vecs {
 
 // g = Qx + q from the product already in Qd (first evaluation only)
 __global__ void grad_init_kernel(int64_t N, vecs V) {
-    VEC_LOOP(i) {
+    BQ_VEC_LOOP(i) {
         if (i < N) V.g[i] = V.Qd[i] + V.q[i];
     }
 }
@@ -262,7 +237,7 @@ int bq_pgfw_start(bq_solver *s) {
     // g = Q x0 + q : the only full-gradient product of the run (later iterations update g incrementally)
     hipStream_t st = s->p->ctx->stream;
     BQ_TRY(bq_problem_apply(s->p, s->x, s->Qd, nullptr));
-    grad_init_kernel<<<vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, solver_vecs(s));
+    grad_init_kernel<<<bq_vec_grid(s->ldN), BQ_VEC_BLOCK, 0, st>>>(s->N, solver_vecs(s));
     BQ_HIP(hipGetLastError());
     return BQ_OK;
 }

@@ -10,25 +10,14 @@
 // of the problem, the three-term recurrences run in two single-workgroup kernels with fixed-order reductions, and the
 // scalar rotations + stopping tests (same tests, same order) on the host between them.  Not a hot path: two stream
 // synchronisations per iteration.
-#include <cfloat>
 #include <cmath>
 
 #include "bq_chol.h"
+#include "bq_minres_rec.h"
+#include "bq_reduce.h"
 
 namespace {
 constexpr int XT = 1024;
-
-__device__ __forceinline__ double xs_bsum(double v, double *sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int w = 0; w < XT / 64; ++w) r += sh[w];
-    return r;
-}
 
 // rhs = -q ; r1 = r2 = rhs ; x = w = w2 = 0 ; out[0] = rhs'rhs
 __global__ __launch_bounds__(XT) void xs_init_kernel(int64_t N, const double *__restrict__ q, double *r1, double *r2, double *x,
@@ -44,7 +33,7 @@ __global__ __launch_bounds__(XT) void xs_init_kernel(int64_t N, const double *__
         w2[i] = 0.0;
         s = fma(b, b, s);
     }
-    s = xs_bsum(s, sh);
+    s = bq_block_sum<XT / 64>(s, sh);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -66,7 +55,7 @@ __global__ __launch_bounds__(XT) void xs_lanczos_kernel(int64_t N, int use_r1, d
         y[i] = yi;
         s = fma(v[i], yi, s);
     }
-    const double alfa = xs_bsum(s, sh);
+    const double alfa = bq_block_sum<XT / 64>(s, sh);
     const double c2 = alfa / beta;
     s = 0.0;
     for (int64_t i = threadIdx.x; i < N; i += XT) {
@@ -74,7 +63,7 @@ __global__ __launch_bounds__(XT) void xs_lanczos_kernel(int64_t N, int use_r1, d
         y[i] = yi;
         s = fma(yi, yi, s);
     }
-    s = xs_bsum(s, sh);
+    s = bq_block_sum<XT / 64>(s, sh);
     if (threadIdx.x == 0) {
         out[0] = alfa;
         out[1] = s;
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(XT) void xs_update_kernel(int64_t N, double oldeps,
         x[i] = xi;
         s = fma(xi, xi, s);
     }
-    s = xs_bsum(s, sh);
+    s = bq_block_sum<XT / 64>(s, sh);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -121,51 +110,31 @@ int minres_solve(bq_problem *p, double *x_host, int64_t *iters) {
     };
     xs_init_kernel<<<1, XT, 0, st>>>(N, p->q, r1, r2, x, w, w2, sc);
     BQ_HIP(fetch(1));
-    const double eps = DBL_EPSILON, rtol = 1e-5;
+    const double rtol = 1e-5;
     const int64_t maxiter = 5 * N;
     int64_t itn = 0;
-    double beta1 = h[0];
-    if (beta1 > 0.0) {   // beta1 == 0 (q == 0): x = 0 is returned as is
-        beta1 = std::sqrt(beta1);
-        double oldb = 0.0, beta = beta1, dbar = 0.0, epsln = 0.0, phibar = beta1, rhs1 = beta1, rhs2 = 0.0, tnorm2 = 0.0,
-               gmax = 0.0, gmin = DBL_MAX, cs = -1.0, sn = 0.0;
-        int istop = 0;
+    bq_minres_rec m;
+    m.start(h[0]);
+    if (m.beta1 > 0.0) {   // beta1 == 0 (q == 0): x = 0 is returned as is
         const unsigned vg = (unsigned)((N + 255) / 256);
         while (itn < maxiter) {
             itn += 1;
-            xs_scale_kernel<<<vg, 256, 0, st>>>(N, 1.0 / beta, r2, v);      // y (= r2, no preconditioner) scaled
-            BQ_TRY(bq_problem_apply(p, v, y, nullptr));                      // y = Q v
-            xs_lanczos_kernel<<<1, XT, 0, st>>>(N, itn >= 2 ? 1 : 0, itn >= 2 ? beta / oldb : 0.0, beta, v, r1, r2, y, sc);
+            xs_scale_kernel<<<vg, 256, 0, st>>>(N, 1.0 / m.beta, r2, v);      // y (= r2, no preconditioner) scaled
+            BQ_TRY(bq_problem_apply(p, v, y, nullptr));                        // y = Q v
+            xs_lanczos_kernel<<<1, XT, 0, st>>>(N, itn >= 2 ? 1 : 0, itn >= 2 ? m.beta / m.oldb : 0.0, m.beta, v, r1, r2, y, sc);
             BQ_HIP(fetch(2));
-            const double alfa = h[0];
             {   // r1 = r2; r2 = y; the buffer of the old r1 receives the next product
                 double *t = r1;
                 r1 = r2;
                 r2 = y;
                 y = t;
             }
-            oldb = beta;
             if (h[1] < 0.0 || !std::isfinite(h[1])) {
                 bq_set_error("minres: non-finite Lanczos vector");
                 return BQ_ERR_NONFINITE;
             }
-            beta = std::sqrt(h[1]);
-            tnorm2 += alfa * alfa + oldb * oldb + beta * beta;
-            if (itn == 1 && beta / beta1 <= 10 * eps) istop = -1;
-            const double oldeps = epsln;
-            const double delta = cs * dbar + sn * alfa;
-            const double gbar = sn * dbar - cs * alfa;
-            epsln = sn * beta;
-            dbar = -cs * beta;
-            const double root = std::hypot(gbar, dbar);
-            double gamma = std::hypot(gbar, beta);
-            gamma = std::max(gamma, eps);
-            cs = gbar / gamma;
-            sn = beta / gamma;
-            const double phi = cs * phibar;
-            phibar = sn * phibar;
-            const double denom = 1.0 / gamma;
-            xs_update_kernel<<<1, XT, 0, st>>>(N, oldeps, delta, denom, phi, v, w2, w, w1, x, sc);   // w1: the spare buffer
+            m.rotate(h[0], h[1], itn);
+            xs_update_kernel<<<1, XT, 0, st>>>(N, m.oldeps, m.delta, m.denom, m.phi, v, w2, w, w1, x, sc);   // w1: the spare buffer
             {   // scipy: w1 = w2; w2 = w; w = the new vector — the old w2 becomes the spare
                 double *t = w2;
                 w2 = w;
@@ -173,27 +142,7 @@ int minres_solve(bq_problem *p, double *x_host, int64_t *iters) {
                 w1 = t;
             }
             BQ_HIP(fetch(1));
-            gmax = std::max(gmax, gamma);
-            gmin = std::min(gmin, gamma);
-            const double z = rhs1 / gamma;
-            rhs1 = rhs2 - delta * z;
-            rhs2 = -epsln * z;
-            const double Anorm = std::sqrt(tnorm2), ynorm = std::sqrt(h[0]);
-            const double epsx = Anorm * ynorm * eps;
-            const double rnorm = phibar;
-            const double test1 = (ynorm == 0.0 || Anorm == 0.0) ? INFINITY : rnorm / (Anorm * ynorm);
-            const double test2 = (Anorm == 0.0) ? INFINITY : root / Anorm;
-            const double Acond = gmax / gmin;
-            if (istop == 0) {
-                if (1.0 + test2 <= 1.0) istop = 2;
-                if (1.0 + test1 <= 1.0) istop = 1;
-                if (itn >= maxiter) istop = 6;
-                if (Acond >= 0.1 / eps) istop = 4;
-                if (epsx >= beta1) istop = 3;
-                if (test2 <= rtol) istop = 2;
-                if (test1 <= rtol) istop = 1;
-            }
-            if (istop != 0) break;
+            if (m.stop(h[0], itn, maxiter, rtol) != 0) break;
         }
     }
     BQ_HIP(hipMemcpyAsync(x_host, x, sizeof(double) * N, hipMemcpyDeviceToHost, st));

@@ -224,6 +224,14 @@ class Context:
         collective enqueued behind the occupation, i.e. a peer that is that late (the watchdog's one-GPU test)."""
         _lib.check(self._lib.bq_ctx_probe_stall(self.handle, float(milliseconds), int(bool(behind_collective))))
 
+    def probe_last_block(self, blocks, rounds=200, uneven=False):
+        """(bad_words, ticket_after) of `rounds` back-to-back launches of the last-workgroup hand-off on `blocks` workgroups:
+        every partial is compared by the workgroup that arrived last; (0, 0) is the only correct answer."""
+        bad, ticket = C.c_int64(-1), C.c_int(-1)
+        _lib.check(self._lib.bq_ctx_probe_last_block(self.handle, int(blocks), int(rounds), int(bool(uneven)), C.byref(bad),
+                                                     C.byref(ticket)))
+        return bad.value, ticket.value
+
     def probe_exchange(self, kind, count, reps=50):
         """(mean_us, min_us) of this context's closing collective timed on its own: kind 'gather' = the in-place all-gather of
         `count` doubles per rank, 'allreduce' = the all-reduce(sum) of `count` doubles (every rank calls it alike)."""

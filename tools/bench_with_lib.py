@@ -11,8 +11,8 @@ import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
-from optiml_amd import _lib  # noqa: E402
+from tools._with_lib import use_library  # noqa: E402
 
-_lib.LIB_PATH = os.path.abspath(sys.argv[1])
+use_library(sys.argv[1])
 sys.argv = [os.path.join(root, 'bench.py')] + sys.argv[2:]
 runpy.run_path(sys.argv[0], run_name='__main__')

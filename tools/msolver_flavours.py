@@ -25,7 +25,8 @@ sys.path.insert(0, ROOT)
 from optiml_amd import _lib  # noqa: E402
 
 if len(sys.argv) > 1:
-    _lib.LIB_PATH = os.path.abspath(sys.argv[1])   # as tools/bench_with_lib.py
+    from tools._with_lib import use_library
+    use_library(sys.argv[1])
 
 from optiml_amd.ml.svm import MultiOutputSVR, OneVsRestSVC, multiclass, multioutput  # noqa: E402
 from optiml_amd.ml.svm._batched import (_DeviceMultiSolver, _DeviceSimplex2Solver, _DeviceSimplexPairSolver,  # noqa: E402

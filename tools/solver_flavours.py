@@ -8,7 +8,11 @@ the same file compute the same bits (tools/msolver_flavours.py does the same for
 
 n = 300, d = 6 (two 256-row tiles, the second ragged), RBF gamma 0.5 unless a flavour says otherwise.  Every flavour creates and
 destroys its own problem and solver (one does so twice in a row: destroy, cache, create), and every run is cut into bq_solver_run
-calls of growing length, so that the solver's record buffer regrows.
+calls of growing length, so that the solver's record buffer regrows.  At n = 300 every O(n) kernel is ONE block of 1024 elements,
+so the `several_blocks` flavours repeat one solver of each family at n = 2500 (first-order: three vector blocks, the last ragged,
+ten closing blocks of 256 rows) and n = 1300 (factorising: two vector blocks, three for the 2n of SVR, six to eleven closing
+blocks): there the last-block ticket is taken by a block that is not alone.  The `minres` flavours reach the three forms of the
+MINRES fallback.  No flavour uses an entry point younger than the tool, so it runs on an older build of the library too.
 """
 import ctypes as C
 import hashlib
@@ -22,7 +26,8 @@ sys.path.insert(0, ROOT)
 from optiml_amd import _lib  # noqa: E402
 
 if len(sys.argv) > 1:
-    _lib.LIB_PATH = os.path.abspath(sys.argv[1])   # as tools/bench_with_lib.py
+    from tools._with_lib import use_library
+    use_library(sys.argv[1])
 
 from optiml_amd.device import Context  # noqa: E402
 
@@ -64,28 +69,28 @@ class hooks:
                 os.environ[k] = v
 
 
-def data(seed):
+def data(seed, n=N):
     rs = np.random.RandomState(seed)
-    X = rs.standard_normal((N, D))
-    y = np.where(X @ rs.standard_normal(D) + 0.3 * rs.standard_normal(N) > 0, 1.0, -1.0)
-    t = np.sin(X @ rs.standard_normal(D)) + 0.1 * rs.standard_normal(N)
+    X = rs.standard_normal((n, D))
+    y = np.where(X @ rs.standard_normal(D) + 0.3 * rs.standard_normal(n) > 0, 1.0, -1.0)
+    t = np.sin(X @ rs.standard_normal(D)) + 0.1 * rs.standard_normal(n)
     return rs, X, y, t
 
 
 def kernel_problem(structure, X, y, q, kernel=_lib.KERNEL_RBF, diag_add=0.0, storage=_lib.F64, flags=0):
     h = C.c_void_p()
-    _lib.check(LIB.bq_problem_create_kernel(CTX.handle, structure | flags, N, D, _lib.ptr(X), _lib.ptr(y), kernel, GAMMA, 0.0, 3,
+    _lib.check(LIB.bq_problem_create_kernel(CTX.handle, structure | flags, len(X), D, _lib.ptr(X), _lib.ptr(y), kernel, GAMMA, 0.0, 3,
                                             diag_add, _lib.ptr(q), storage, C.byref(h)))
     return h
 
 
-def svc_problem(seed, **kw):
-    rs, X, y, _ = data(seed)
-    return kernel_problem(_lib.SVC, _lib.as_f64(X), _lib.as_f64(y), -np.ones(N), **kw), y
+def svc_problem(seed, n=N, **kw):
+    rs, X, y, _ = data(seed, n)
+    return kernel_problem(_lib.SVC, _lib.as_f64(X), _lib.as_f64(y), -np.ones(n), **kw), y
 
 
-def svr_problem(seed, **kw):
-    rs, X, _, t = data(seed)
+def svr_problem(seed, n=N, **kw):
+    rs, X, _, t = data(seed, n)
     q = np.concatenate([0.1 - t, 0.1 + t])
     return kernel_problem(_lib.SVR, _lib.as_f64(X), None, _lib.as_f64(q), **kw), t
 
@@ -150,7 +155,11 @@ def first_order():
     solve('svc_pg_stream', svc_problem(4, storage=_lib.STREAM)[0], _lib.PG, N)
 
 
-MASKS = (('mask_l', _lib.GET_MASK_L, N), ('mask_u', _lib.GET_MASK_U, N))
+def masks(n):
+    return (('mask_l', _lib.GET_MASK_L, n), ('mask_u', _lib.GET_MASK_U, n))
+
+
+MASKS = masks(N)
 
 
 def active_set():
@@ -188,21 +197,24 @@ def active_set_resumed():
     LIB.bq_problem_destroy(p)
 
 
+def mult(n):
+    return (('lp', _lib.GET_LP, n), ('lm', _lib.GET_LM, n))
+
+
 def interior_point():
-    mult = lambda n: (('lp', _lib.GET_LP, n), ('lm', _lib.GET_LM, n))   # noqa: E731
     solve('svc_ip', svc_problem(9)[0], _lib.IP, N, mult(N), max_iter=60)
     solve('svr_ip', svr_problem(10)[0], _lib.IP, 2 * N, mult(2 * N), max_iter=60)
 
 
-def lagrangian(name, schedules):
+def lagrangian(name, schedules, n=N):
     """the augmented-Lagrangian solver with an equality row and both bounds; schedules: how often they are set before the run"""
-    p, y = svc_problem(11)
+    p, y = svc_problem(11, n)
     rs = np.random.RandomState(12)
     prm = _lib.AlParams(rule=_lib.RULE_ADAM, momentum_type=_lib.MOM['none'], step_size=0.05, momentum=0.0, beta1=0.9, beta2=0.999,
                         decay=0.9, offset=1e-8, rho=1.0, tol=1e-9, epochs=90)
     s = C.c_void_p()
-    _lib.check(LIB.bq_al_solver_create(p, C.byref(prm), _lib.ptr(_lib.as_f64(y)), _lib.ptr(np.zeros(N)), _lib.ptr(np.ones(N)),
-                                       _lib.ptr(rs.uniform(size=N)), None, C.byref(s)))
+    _lib.check(LIB.bq_al_solver_create(p, C.byref(prm), _lib.ptr(_lib.as_f64(y)), _lib.ptr(np.zeros(n)), _lib.ptr(np.ones(n)),
+                                       _lib.ptr(rs.uniform(size=n)), None, C.byref(s)))
     for k in range(schedules):   # the second call releases the first one's device arrays
         steps = 0.05 / (1.0 + 0.02 * np.arange(40 + 10 * k))
         _lib.check(LIB.bq_al_solver_set_schedules(s, _lib.ptr(steps), None, len(steps)))
@@ -210,7 +222,7 @@ def lagrangian(name, schedules):
     _lib.check(LIB.bq_al_solver_dual_size(s, C.byref(nd)))
     recs, _ = run_cut(s, name)
     it, st, f = state(s)
-    show(name, x=get(s, _lib.GET_X_NOW, N), g=get(s, _lib.GET_G, N), step=get(s, _lib.GET_D, N), dual=get(s, _lib.GET_DUAL, nd.value),
+    show(name, x=get(s, _lib.GET_X_NOW, n), g=get(s, _lib.GET_G, n), step=get(s, _lib.GET_D, n), dual=get(s, _lib.GET_DUAL, nd.value),
          records=recs, state=np.array([it, f]))
     note(name, 'status', '%s after %d iterations' % (_lib.STATUS[st], it))
     LIB.bq_solver_destroy(s)
@@ -245,6 +257,47 @@ def x_star():
     show('x_star', x=x)
     note('x_star', 'method', '%d, %d minres iterations' % (method.value, iters.value))
     LIB.bq_problem_destroy(p)
+
+
+def x_star_minres():
+    """no diagonal term and a linear kernel: the Hessian X X' has rank 6, the factorisation fails and scipy's MINRES takes over
+    (bq_xstar.hip: the recurrence on the host)"""
+    rs, X, _, t = data(17)
+    p = kernel_problem(_lib.PLAIN, _lib.as_f64(X), None, _lib.as_f64(-t), kernel=_lib.KERNEL_LINEAR)
+    x, method, iters = np.zeros(N), C.c_int(0), C.c_int64(0)
+    _lib.check(LIB.bq_problem_x_star(p, _lib.ptr(x), C.byref(method), C.byref(iters)))
+    assert method.value == 1, 'x_star_minres: the factorisation succeeded, MINRES was not reached'
+    show('x_star_minres', x=x)
+    note('x_star_minres', 'method', '%d, %d minres iterations' % (method.value, iters.value))
+    LIB.bq_problem_destroy(p)
+
+
+def active_set_minres():
+    """a linear kernel: Q[A,A] is singular while the free set is larger than the rank, and ActiveSet takes its MINRES branch — in
+    the persistent workgroup, and under minres_big_min=0 in the multi-workgroup form (as tests/test_gpu_parity.py switches it)"""
+    for name, hook in (('svc_as_minres', None), ('svc_as_minres_big', 'minres_big_min=0')):
+        with hooks(hook):
+            p, _ = svc_problem(18, kernel=_lib.KERNEL_LINEAR)
+            s = box_solver(p, _lib.AS, N, max_iter=60)
+            recs, _ = run_cut(s, name)
+            finish(s, name, N, recs, MASKS)
+            calls = C.c_int64(0)
+            _lib.check(LIB.bq_solver_counter(s, _lib.COUNT_MINRES, C.byref(calls)))
+            assert calls.value > 0, name + ': the MINRES branch was not reached'
+            note(name, 'minres', '%d iterations through the fallback' % calls.value)
+            LIB.bq_solver_destroy(s)
+            LIB.bq_problem_destroy(p)
+
+
+def several_blocks():
+    """one solver of each family on more than one vector block (see the module docstring)"""
+    n1, n2 = 2500, 1300
+    solve('svc_pg_n2500', svc_problem(19, n1)[0], _lib.PG, n1, max_iter=60)
+    solve('svr_fw_n1300', svr_problem(20, n2)[0], _lib.FW, 2 * n2, eps=1e-3, max_iter=60)
+    lagrangian('svc_al_n2500', 0, n1)
+    solve('svc_as_cg_n1300', svc_problem(21, n2, diag_add=0.5)[0], _lib.AS_CG, n2, masks(n2), max_iter=40)
+    solve('svc_as_dense_n1300', svc_problem(22, n2)[0], _lib.AS, n2, masks(n2), max_iter=60)
+    solve('svc_ip_n1300', svc_problem(23, n2)[0], _lib.IP, n2, mult(n2), max_iter=30)
 
 
 def dense(name, symmetric, storage):
@@ -298,6 +351,9 @@ if __name__ == '__main__':
     smo('smo_svc', _lib.SVC)
     smo('smo_svr', _lib.SVR)
     x_star()
+    x_star_minres()
+    active_set_minres()
+    several_blocks()
     dense('dense_sym_f64', True, _lib.F64)
     dense('dense_asym_f32', False, _lib.F32)
     one_shots()
