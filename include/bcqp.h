@@ -65,6 +65,7 @@ extern "C" {
 /* (still 3: bq_msmo_create / _run / _get / _destroy were added; nothing existing changed) */
 /* (still 3: bq_msmo_vote_heldout was added; nothing existing changed) */
 /* (still 3: bq_msmo_svr_heldout and bq_msmo_svc_heldout were added; nothing existing changed) */
+/* (still 3: bq_rsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -785,6 +786,36 @@ int bq_msmo_svr_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned
 int bq_msmo_svc_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned char *held, int ncal, const int *cal_of,
                         double *intercept, int64_t *n_sv, double *A, double *B, int *iters, double *loss, int64_t *n_pos,
                         int64_t *n_neg, int *flags, double *dec);
+
+/* ---- panel-free SMO: libsvm's WSS2 decomposition on kernel rows made on demand (bq_rsmo.hip) ---------------------------------
+ * libsvm's Solver::Solve without shrinking (svm.cpp; the scalar rules are csrc/bq_rsmo_step.h, the NumPy restatement
+ * tests/smo_rows_reference.py) on  min 1/2 a'Qa + p'a, y'a = 0, 0 <= a_t <= C_t:
+ *   BQ_SVC  Q = diag(y) K diag(y), p = -1;   BQ_SVR  2n variables, Q = [[K, -K], [-K, K]], p = [epsilon - y; epsilon + y], signs
+ *   [+1 ..; -1 ..], variables t and t + n share kernel row t.
+ * Start alpha = 0, G = p; second-order working-set selection with TAU = 1e-12, ties to the LARGER index; stop when
+ * Gmax + Gmax2 < tol — libsvm's (sklearn's) tol, not the two-threshold tol of bq_smo_create; rho = calculate_rho, intercept = -rho;
+ * iteration cap max(10^7, 100 N) (test hook rsmo_max_steps).  No fused multiply-add on the path: the trajectory has the bits of the
+ * restatement run on the rows bq_rsmo_rows returns.
+ * p: a kernel-built BQ_STREAM problem on a single-rank context (anything else: BQ_ERR_BADARG before any device call); only its
+ *    k-major image of X is read, one pass per kernel row.
+ * task BQ_SVC: y in {+1,-1}, both present; BQ_SVR: targets.  Cw: n boxes, finite and > 0 (SVR: the box of both halves).
+ * cache_rows: >= 2, or 0 = as many as fit the library's share (half) of the free device memory, at most n.  Rows live in an LRU
+ *    cache managed on the device; a row has the same bits whenever it is computed, so nothing in a run depends on cache_rows.
+ * bq_rsmo_run enqueues max_steps steps of two launches each with no host synchronisation in between, then reads the control
+ *    block: *steps = pair updates done so far, *finished = 0 (running), 1 (optimal) or 2 (stopped at the cap).  Launches behind
+ *    the step that finished return at once.  However a run is cut into calls, the iterates are the same.
+ * bq_rsmo_rows: m x n kernel rows as the solver sees them (through the cache; each request counts as a hit or a miss). */
+typedef struct bq_rsmo bq_rsmo;
+enum { BQ_RSMO_ALPHAS = 0,    /* n (BQ_SVC) or [alpha; alpha*] 2n (BQ_SVR) */
+       BQ_RSMO_GRADIENT = 1,  /* n | 2n */
+       BQ_RSMO_SCALARS = 2,   /* 6: rho, Gmax, Gmax2 (of the last selection), last i, last j (of the last update; -1: none), steps */
+       BQ_RSMO_STATS = 3      /* 3: cache hits, misses, cache_rows */ };
+int bq_rsmo_create(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
+                   int64_t cache_rows, bq_rsmo **out);
+int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished);
+int bq_rsmo_get(bq_rsmo *s, int what, double *out);
+int bq_rsmo_rows(bq_rsmo *s, int m, const int64_t *idx, double *out);
+int bq_rsmo_destroy(bq_rsmo *s);
 
 /* ---- prediction (optiml/ml/svm/_base.py:284-287) ------------------------------- */
 /* out[t] = sum_m coef[m] * kernel(SV[m], Xt[t]) + intercept   (SV: m x d, Xt: t x d, row-major fp64) */

@@ -64,6 +64,7 @@ void bq_set_error(const char *fmt, ...);
 //   chol_super_min=N (tiles of a trailing triangle from which the wide update takes the super-tile order; default 4096)
 //   chol_fwd_slice=N (columns per slice of the block-by-block forward sweep; default 16384)
 //   hessian_image_gain=G (the image is kept if its product is G times faster than the panel's; default 1, 0: always)
+//   rsmo_max_steps=N (the iteration cap of a row-based SMO created under the hook, in place of libsvm's max(10^7, 100 N))
 // ---------------------------------------------------------------------------------------------
 bool bq_hook(const char *name, double *value);                       // true (and *value) when the hook is set
 static inline double bq_hook_value(const char *name, double dflt) {
@@ -491,6 +492,8 @@ int bq_stream_prepare(bq_ctx *ctx, const double *Xdev, int64_t n, int64_t d, int
 int bq_stream_sym_product(bq_ctx *ctx, void *h, int64_t n, int64_t nb, const bq_seg_table &tab, int kernel, double gamma, double coef0,
                           int degree, bool add_one, const double *w, double *out, int mode, const int *done);
 void bq_stream_free(void *h);
+// the image itself, for a reader of single rows (bq_rsmo.hip): At[dp][mp] k-major and zero-padded, a2[mp] squared row norms
+void bq_stream_image_view(const void *h, const double **At, const double **a2, int64_t *mp, int64_t *dp);
 
 int bq_launch_gram_matrix(bq_ctx *ctx, int kernel, double gamma, double coef0, int degree, int64_t m, int64_t d,
                           const double *A, int64_t t, const double *B, double *out);

@@ -723,6 +723,14 @@ void bq_stream_free(void *h) {
     delete (bq_stream_images *)h;
 }
 
+void bq_stream_image_view(const void *h, const double **At, const double **a2, int64_t *mp, int64_t *dp) {
+    const bq_stream_images *st = (const bq_stream_images *)h;
+    *At = st->img.At;
+    *a2 = st->img.a2;
+    *mp = st->img.mp;
+    *dp = st->img.dp;
+}
+
 // mode 0: out (nb * 256) = the sum of this rank's segment vectors in segment order; mode 1: each of this
 // rank's segment vectors to its slot of the gathered buffer `out` (slots of nb * 256)
 int bq_stream_sym_product(bq_ctx *ctx, void *h, int64_t n, int64_t nb, const bq_seg_table &tab, int kernel, double gamma, double coef0,

@@ -1,9 +1,10 @@
 __all__ = ['SVM', 'SVC', 'SVR', 'OneVsRestSVC', 'OneVsOneSVC', 'SVCGridSearchCV', 'MultiOutputSVR', 'SVRGridSearchCV',
            'CalibratedSVC', 'PairwiseCoupledSVC', 'OneClassSVM', 'one_class_nu_path', 'NuSVC', 'NuSVR',
            'nu_svc_path', 'nu_svr_path', 'OneVsOneNuSVC', 'ovo_nu_svc_path', 'NuSVCGridSearchCV', 'NuSVRGridSearchCV',
-           'OneVsOneGridSearchCV', 'ovo_vote']
+           'OneVsOneGridSearchCV', 'ovo_vote', 'RowSMOClassifier', 'RowSMORegression']
 
 from ._base import SVM, SVC, SVR
+from .smo_rows import RowSMOClassifier, RowSMORegression
 from .multiclass import OneVsRestSVC
 from .onevsone import OneVsOneSVC
 from .model_selection import SVCGridSearchCV, SVRGridSearchCV

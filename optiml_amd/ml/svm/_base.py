@@ -9,7 +9,8 @@ SVC :366-419, SVR :907-963).  Two dual branches are implemented:
         on the augmented Lagrangian of the dual, reg_intercept True or False, all four losses
         (SVC.fit :638-723, :776-860; SVR.fit :1188-1270, :1330-1415) — SURVEY 8(f).3
     dual=True, reg_intercept=False, optimizer='smo' (or SMO): SMOClassifier / SMORegression on the resident panel
-        (SVC.fit :560-573, SVR.fit :1106-1120) — SURVEY 8(f).4
+        (SVC.fit :560-573, SVR.fit :1106-1120) — SURVEY 8(f).4; with storage='stream' RowSMOClassifier / RowSMORegression
+        (smo_rows.py): libsvm's WSS2 decomposition on kernel rows made on demand, no panel, `tol` libsvm's (sklearn's)
 
 In both the Gram panel is built and kept in HBM, the Wolfe dual never exists as an n x n host matrix
 (`self.obj` is a lazy `KernelQuadratic`), and the support-vector / intercept post-processing uses one masked
@@ -27,6 +28,7 @@ from ...opti.constrained import BoxConstrainedQuadraticOptimizer, ProjectedGradi
 from ...opti.unconstrained.stochastic import StochasticOptimizer, StochasticMomentumOptimizer
 from .kernels import Kernel, LinearKernel, gaussian, BaseEstimator
 from .smo import SMO, SMOClassifier, SMORegression
+from .smo_rows import RowSMOClassifier, RowSMORegression
 from .losses import (Hinge, SquaredHinge, EpsilonInsensitive, SquaredEpsilonInsensitive,
                      squared_hinge, squared_epsilon_insensitive)
 
@@ -210,6 +212,21 @@ class SVM(BaseEstimator, ABC):
     def _is_smo(self):
         return self.dual and (self.optimizer == 'smo' or self.optimizer is SMO)
 
+    def _smo_solver(self, resident, rows, obj, *args):
+        """The SMO branch of `fit`: the walker on the resident panel (`resident`), or, with storage='stream', libsvm's decomposition
+        on kernel rows made on demand (`rows`; single-rank contexts).  The two read `tol` differently: the walker compares every
+        example with its thresholds b_up / b_low under 2 tol (smo.py), the row-based solver stops when libsvm's Gmax + Gmax2 < tol,
+        which is sklearn.svm's tol.  A run that ends at libsvm's iteration cap warns like the augmented-Lagrangian branch."""
+        if self.storage != 'stream':
+            return resident(obj, *args).minimize()
+        if get_context().world != 1:
+            raise NotImplementedError("optimizer='smo' with storage='stream' runs on a single-rank context")
+        opt = rows(obj, *args).minimize()
+        if opt.status == 'stopped':
+            import warnings
+            warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
+        return opt
+
     def _is_stochastic(self):
         return self.dual and isinstance(self.optimizer, type) and issubclass(self.optimizer, StochasticOptimizer)
 
@@ -321,7 +338,8 @@ class SVC(ClassifierMixin, SVM):
                 raise NotImplementedError('SMO solves the hinge dual with an unregularised intercept')   # :571-573
             obj = KernelQuadratic(X, -np.ones(n), 'svc', self.kernel, y=y, storage=self.storage, rank_one=False, compact=False)
             self.obj = obj
-            self.optimizer = SMOClassifier(obj, X, y, None, self.kernel, self.C, self.tol, self.verbose, box).minimize()
+            self.optimizer = self._smo_solver(SMOClassifier, RowSMOClassifier, obj, X, y, None, self.kernel, self.C, self.tol,
+                                              self.verbose, box)
             self.alphas_ = self.optimizer.alphas
         elif self._is_stochastic():
             if self.loss not in (Hinge, SquaredHinge):
@@ -350,7 +368,7 @@ class SVC(ClassifierMixin, SVM):
         self.support_ = np.arange(len(self.alphas_))[sv]
         self.support_vectors_, sv_y, alphas = X[sv], y[sv], self.alphas_[sv]
         self.dual_coef_ = alphas * sv_y
-        if isinstance(self.optimizer, SMOClassifier):   # svm/_base.py:569-571, :872
+        if isinstance(self.optimizer, (SMOClassifier, RowSMOClassifier)):   # svm/_base.py:569-571, :872
             if isinstance(self.kernel, LinearKernel):
                 self.coef_ = self.optimizer.w
             self.intercept_ = self.optimizer.b
@@ -411,8 +429,8 @@ class SVR(RegressorMixin, SVM):
                 raise NotImplementedError('SMO solves the epsilon-insensitive dual with an unregularised intercept')
             obj = KernelQuadratic(X, q, 'svr', self.kernel, storage=self.storage, rank_one=False, compact=False)
             self.obj = obj
-            self.optimizer = SMORegression(obj, X, y, None, self.kernel, self.C, self.epsilon, self.tol, self.verbose,
-                                           box).minimize()
+            self.optimizer = self._smo_solver(SMORegression, RowSMORegression, obj, X, y, None, self.kernel, self.C, self.epsilon,
+                                              self.tol, self.verbose, box)
             self.alphas_ = np.concatenate((self.optimizer.alphas_p, self.optimizer.alphas_n))
         elif self._is_stochastic():
             if self.loss not in (EpsilonInsensitive, SquaredEpsilonInsensitive):
@@ -443,7 +461,7 @@ class SVR(RegressorMixin, SVM):
         self.support_ = np.arange(len(alphas_p))[sv]
         self.support_vectors_, sv_y, alphas_p, alphas_n = X[sv], y[sv], alphas_p[sv], alphas_n[sv]
         self.dual_coef_ = alphas_p - alphas_n
-        if isinstance(self.optimizer, SMORegression):   # svm/_base.py:1116-1118, :1428
+        if isinstance(self.optimizer, (SMORegression, RowSMORegression)):   # svm/_base.py:1116-1118, :1428
             if isinstance(self.kernel, LinearKernel):
                 self.coef_ = self.optimizer.w
             self.intercept_ = self.optimizer.b
