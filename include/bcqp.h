@@ -66,6 +66,7 @@ extern "C" {
 /* (still 3: bq_msmo_vote_heldout was added; nothing existing changed) */
 /* (still 3: bq_msmo_svr_heldout and bq_msmo_svc_heldout were added; nothing existing changed) */
 /* (still 3: bq_rsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
+/* (still 3: bq_rsmo_create_general and BQ_RSMO_NU_SCALARS were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -809,9 +810,28 @@ typedef struct bq_rsmo bq_rsmo;
 enum { BQ_RSMO_ALPHAS = 0,    /* n (BQ_SVC) or [alpha; alpha*] 2n (BQ_SVR) */
        BQ_RSMO_GRADIENT = 1,  /* n | 2n */
        BQ_RSMO_SCALARS = 2,   /* 6: rho, Gmax, Gmax2 (of the last selection), last i, last j (of the last update; -1: none), steps */
-       BQ_RSMO_STATS = 3      /* 3: cache hits, misses, cache_rows */ };
+       BQ_RSMO_STATS = 3,     /* 3: cache hits, misses, cache_rows */
+       BQ_RSMO_NU_SCALARS = 4 /* 7, BQ_RSMO_RULE_NU only: rho, r, Gmaxp + Gmaxp2, Gmaxn + Gmaxn2, last i, last j, steps */ };
 int bq_rsmo_create(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
                    int64_t cache_rows, bq_rsmo **out);
+/* The general dual  min 1/2 a'Qa + lin'a,  0 <= a_v <= boxes_v,  Q_uv = s_u s_v K_row(u) row(v), from a start alpha0:
+ *   BQ_RSMO_RULE_PLAIN  one equality s'a = s'alpha0: libsvm's Solver (bq_rsmo_create is this entry with alpha0 = 0 and its task's signs
+ *                       and linear term; the one-class dual is signs +1, lin 0, boxes 1 and libsvm's start).
+ *   BQ_RSMO_RULE_NU     the mass of each sign is kept: libsvm's Solver_NU (nu-SVC, nu-SVR) — one maximal violator per sign (ip over
+ *                       s = +1 with a < C on -G, in over s = -1 with a > 0 on G), j scored against the row of its own sign, i = ip
+ *                       or in according to s_j, stop when max(Gmaxp + Gmaxp2, Gmaxn + Gmaxn2) < tol, offsets r1 / r2 per sign with
+ *                       rho = (r1 - r2) / 2 and r = (r1 + r2) / 2.  A step holds three rows: cache_rows 0 or >= 3.
+ * N = n, or 2n with signs [+1 ..; -1 ..], the variables t and t + n sharing kernel row t.  max_steps: the iteration cap, 0 = libsvm's
+ * max(10^7, 100 N); the hook rsmo_max_steps overrides either.
+ * The start gradient is G0 = lin + s o (K b), b_t the sum of s_v alpha0_v over the variables of row t: lin's bits and no product
+ * when b = 0, else ONE streamed Gram product of p (the product of bq_problem_matvec).  libsvm sums alpha_i Q_i in ascending i; G0
+ * differs from that in rounding only.  G0 is computed once and depends neither on the cache nor on how the run is cut.
+ * BQ_ERR_BADARG: what bq_rsmo_create refuses, alpha0 outside its box, a non-finite lin, signs other than +-1 (2n: other than
+ * [+1 ..; -1 ..]), BQ_RSMO_RULE_NU with cache_rows 2 or with one sign only.
+ * BQ_RSMO_SCALARS of a BQ_RSMO_RULE_NU solver: the same rho, then Gmaxp, Gmaxp2. */
+enum { BQ_RSMO_RULE_PLAIN = 0, BQ_RSMO_RULE_NU = 1 };
+int bq_rsmo_create_general(bq_problem *p, int rule, int64_t N, const double *signs, const double *lin, const double *boxes,
+                           const double *alpha0, double tol, int64_t max_steps, int64_t cache_rows, bq_rsmo **out);
 int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished);
 int bq_rsmo_get(bq_rsmo *s, int what, double *out);
 int bq_rsmo_rows(bq_rsmo *s, int m, const int64_t *idx, double *out);

@@ -27,7 +27,8 @@ PLACE_PANEL = 64
 PLAIN_PANEL = 128
 DENSE_ROWS, DENSE_LOWER = 256, 512   # OR-ed into the storage of bq_problem_create_dense
 SMO_ALPHAS, SMO_ERRORS, SMO_SCALARS, SMO_STATS = range(4)
-RSMO_ALPHAS, RSMO_GRADIENT, RSMO_SCALARS, RSMO_STATS = range(4)
+RSMO_ALPHAS, RSMO_GRADIENT, RSMO_SCALARS, RSMO_STATS, RSMO_NU_SCALARS = range(5)
+RSMO_RULE_PLAIN, RSMO_RULE_NU = range(2)   # bq_rsmo_create_general's `rule`
 RSMO_STATUS = {0: 'unknown', 1: 'optimal', 2: 'stopped'}   # bq_rsmo_run's `finished`
 RULE_SGD, RULE_ADAM, RULE_AMSGRAD, RULE_ADAMAX, RULE_ADAGRAD, RULE_ADADELTA, RULE_RMSPROP = range(7)
 MOM = {'none': 0, 'polyak': 1, 'nesterov': 2}
@@ -172,6 +173,7 @@ PROTOTYPES = {
     'bq_msmo_svc_heldout': (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_ubyte), C.c_int, _ip, _dp, C.POINTER(_i64), _dp, _dp, _ip,
                                       _dp, C.POINTER(_i64), C.POINTER(_i64), _ip, _dp]),
     'bq_rsmo_create': (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, _i64, C.POINTER(_vp)]),
+    'bq_rsmo_create_general': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, C.c_double, _i64, _i64, C.POINTER(_vp)]),
     'bq_rsmo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),
     'bq_rsmo_get': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_rsmo_rows': (C.c_int, [_vp, C.c_int, C.POINTER(_i64), _dp]),

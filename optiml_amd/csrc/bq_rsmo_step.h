@@ -2,7 +2,9 @@
 // (tests/c/rsmo_step_check.cpp, run by tests/test_rsmo_step_host.py): libsvm's Solver without shrinking (svm.cpp: select_working_set,
 // the two-variable update of Solve, calculate_rho), restated on
 //     min 1/2 a'Qa + p'a,  y'a = 0,  0 <= a_t <= C_t,   Q_st = y_s y_t K_st,
-// plus the victim rule of the row cache.  No HIP types: plain C++ on doubles and integers.
+// plus the victim rule of the row cache; and, for the general entry (bq_rsmo_create_general; host check tests/c/rsmo_nu_step_check.cpp,
+// restatement tests/smo_nu_reference.py), Solver_NU's selection, stop test and r1 / r2 and the victim rule with two slots to keep.
+// No HIP types: plain C++ on doubles and integers.
 //
 // Rounding.  Every sum, product and quotient below is one correctly rounded operation and none is fused (the includer builds with
 // contraction inside a statement at most, and each product here is a statement of its own): the NumPy restatement
@@ -170,6 +172,56 @@ BQ_RSMO_FN double bq_rsmo_rho_value(const bq_rsmo_rho *r) {
     return both / 2.0;
 }
 
+// ---- Solver_NU (svm.cpp: Solver_NU::select_working_set, Solver_NU::calculate_rho) -----------------------------------------------------
+// The nu-duals keep a second equality (each sign's mass), so a pair never crosses the signs.  libsvm scans each sign on its own, and
+// within one sign its sets and values are the ones above: `ip` is the arg-max of -G over y = +1 with a < C and `in` the arg-max of G
+// over y = -1 with a > 0 (bq_rsmo_in_up / bq_rsmo_up_value on one sign), Gmaxp2 / Gmaxn2 the maxima of G over y = +1 with a > 0 and
+// of -G over y = -1 with a < C (bq_rsmo_in_low / bq_rsmo_low_value on one sign).  A candidate j is scored against the row of its own
+// sign: grad_diff = Gmaxp + G_j (y_j = +1) or Gmaxn - G_j (y_j = -1), and y_i = y_j, so QD_i + QD_j - 2 Q_ij is bq_rsmo_quad_coef.
+// A side without a maximal violator has Gmax = -inf and index -1: grad_diff = -inf, no candidate.
+BQ_RSMO_FN double bq_rsmo_nu_score(double y_t, double g_t, double gmaxp, double qd_ip, double k_ip_t, double gmaxn, double qd_in,
+                                   double k_in_t, double qd_t, bool *ok) {
+    if (y_t > 0.0) return bq_rsmo_score(gmaxp, y_t, g_t, qd_ip, qd_t, k_ip_t, ok);
+    return bq_rsmo_score(gmaxn, y_t, g_t, qd_in, qd_t, k_in_t, ok);
+}
+// the two sums of the stop test and the test: max(Gmaxp + Gmaxp2, Gmaxn + Gmaxn2) < tol
+BQ_RSMO_FN double bq_rsmo_nu_gap(double gmax, double gmax2) { return gmax + gmax2; }
+BQ_RSMO_FN bool bq_rsmo_nu_stop(double gmaxp, double gmaxp2, double gmaxn, double gmaxn2, double tol) {
+    const double gp = bq_rsmo_nu_gap(gmaxp, gmaxp2);
+    const double gn = bq_rsmo_nu_gap(gmaxn, gmaxn2);
+    const double worst = gp > gn ? gp : gn;
+    return worst < tol;
+}
+// calculate_rho in ascending t, one set of pieces per sign, on G itself (not y G): r1 over y = +1, r2 over y = -1
+struct bq_rsmo_nu_rho {
+    double ub[2] = {BQ_RSMO_INF, BQ_RSMO_INF}, lb[2] = {-BQ_RSMO_INF, -BQ_RSMO_INF}, sum_free[2] = {0.0, 0.0};
+    long long nr_free[2] = {0, 0};
+};
+BQ_RSMO_FN void bq_rsmo_nu_rho_add(bq_rsmo_nu_rho *r, double y, double a, double C, double G) {
+    const int s = y > 0.0 ? 0 : 1;
+    if (a >= C) {
+        r->lb[s] = G > r->lb[s] ? G : r->lb[s];
+    } else if (a <= 0.0) {
+        r->ub[s] = G < r->ub[s] ? G : r->ub[s];
+    } else {
+        r->nr_free[s] += 1;
+        r->sum_free[s] = r->sum_free[s] + G;
+    }
+}
+BQ_RSMO_FN double bq_rsmo_nu_rho_side(const bq_rsmo_nu_rho *r, int s) {
+    if (r->nr_free[s] > 0) return r->sum_free[s] / (double)r->nr_free[s];
+    const double both = r->ub[s] + r->lb[s];
+    return both / 2.0;
+}
+// rho = (r1 - r2) / 2, r = (r1 + r2) / 2
+BQ_RSMO_FN void bq_rsmo_nu_rho_value(const bq_rsmo_nu_rho *r, double *rho, double *rr) {
+    const double r1 = bq_rsmo_nu_rho_side(r, 0), r2 = bq_rsmo_nu_rho_side(r, 1);
+    const double diff = r1 - r2;
+    const double sum = r1 + r2;
+    *rho = diff / 2.0;
+    *rr = sum / 2.0;
+}
+
 // ---- the row cache -------------------------------------------------------------------------------------------------------------------
 // The victim of a miss: the slot with the smallest stamp (0: never used), the lower slot among equals, never `keep` (the slot of the
 // other row of the pair in hand; -1: none).  slot a goes before slot b:
@@ -180,5 +232,12 @@ BQ_RSMO_FN long long bq_rsmo_victim(const long long *stamp, long long R, long lo
     long long best = -1;
     for (long long s = 0; s < R; ++s)
         if (s != keep && bq_rsmo_victim_before(stamp[s], s, best < 0 ? 0 : stamp[best], best)) best = s;
+    return best;
+}
+// the same with two slots to keep (a Solver_NU step holds the rows of ip and in while it resolves the row of j); -1: none
+BQ_RSMO_FN long long bq_rsmo_victim2(const long long *stamp, long long R, long long keep_a, long long keep_b) {
+    long long best = -1;
+    for (long long s = 0; s < R; ++s)
+        if (s != keep_a && s != keep_b && bq_rsmo_victim_before(stamp[s], s, best < 0 ? 0 : stamp[best], best)) best = s;
     return best;
 }

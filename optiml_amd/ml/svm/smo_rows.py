@@ -28,6 +28,14 @@ class RowSMO(ABC):
     run_steps = 512   # steps enqueued between two looks at the device's `finished` word
 
     def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None):
+        self._setup(quad, X, y, kernel, tol, verbose, cache_rows, ctx)
+        self.K = K
+        self.C = C
+        n = len(self.X)
+        self.box = np.full(n, float(C)) if box is None else _lib.as_f64(box, n, 'box')
+
+    def _setup(self, quad, X, y, kernel, tol, verbose, cache_rows, ctx):
+        """what every dual on rows needs: the streamed problem, the data, the run's parameters and its (empty) results"""
         if not isinstance(quad, KernelQuadratic) or quad.storage != 'stream':
             raise TypeError("the row-based SMO needs a KernelQuadratic(storage='stream') as quad")
         if not (cache_rows == 0 or cache_rows >= 2):
@@ -35,15 +43,11 @@ class RowSMO(ABC):
         self.quad = quad
         self.X = np.ascontiguousarray(X, dtype=float)
         self.y = np.ascontiguousarray(y, dtype=float)
-        self.K = K
         self.kernel = kernel
         if isinstance(kernel, LinearKernel):
             self.w = 0.
         self.b = 0.
         self.rho = 0.
-        self.C = C
-        n = len(self.X)
-        self.box = np.full(n, float(C)) if box is None else _lib.as_f64(box, n, 'box')
         self.tol = tol
         self.cache_rows = int(cache_rows)
         self.ctx = ctx   # None: the default context
@@ -65,6 +69,18 @@ class RowSMO(ABC):
     def _pull(self, lib, h):
         raise NotImplementedError
 
+    def _create(self, lib, dev, h):
+        """the device solver of this dual on the problem `dev`, into the handle `h`"""
+        _lib.check(lib.bq_rsmo_create(dev.handle, self._task, _lib.ptr(self.y), _lib.ptr(self.box), float(self._epsilon()),
+                                      float(self.tol), self.cache_rows, C.byref(h)))
+
+    def _scalars(self, lib, h):
+        """the offsets and the stop measure of the finished run"""
+        sc = np.empty(6)
+        _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_SCALARS, _lib.ptr(sc)))
+        self.rho, self.gmax, self.gmax2 = sc[0], sc[1], sc[2]
+        self.b = -self.rho
+
     def minimize(self):
         lib = _lib.load()
         ctx = self.ctx or get_context()
@@ -72,8 +88,7 @@ class RowSMO(ABC):
             raise NotImplementedError('the row-based SMO runs on a single-rank context')
         dev = self.quad.device_problem(ctx)
         h = C.c_void_p()
-        _lib.check(lib.bq_rsmo_create(dev.handle, self._task, _lib.ptr(self.y), _lib.ptr(self.box), float(self._epsilon()),
-                                      float(self.tol), self.cache_rows, C.byref(h)))
+        self._create(lib, dev, h)
         try:
             if self.verbose:
                 print('iter\t cost')
@@ -90,10 +105,7 @@ class RowSMO(ABC):
             self.iter = steps.value
             self.status = _lib.RSMO_STATUS[fin.value]
             self._pull(lib, h)
-            sc = np.empty(6)
-            _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_SCALARS, _lib.ptr(sc)))
-            self.rho, self.gmax, self.gmax2 = sc[0], sc[1], sc[2]
-            self.b = -self.rho
+            self._scalars(lib, h)
             st = np.empty(3)
             _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_STATS, _lib.ptr(st)))
             self.cache_stats = {'hits': int(st[0]), 'misses': int(st[1]), 'cache_rows': int(st[2])}

@@ -11,6 +11,10 @@ RBF with gamma='scale', d = 128, C = 1, tol 1e-3, seed 0) and write profiles/smo
     python tools/smo_rows_profile.py rate --n N --steps K --json FILE                K steps of the streamed solver, no verdict
     python tools/smo_rows_profile.py product --n N --json FILE                       the streamed Gram product, timed
     python tools/smo_rows_profile.py stages --n N --reps R --json FILE               R fits in one process, problem build and minimize apart
+    python tools/smo_rows_profile.py nu-all [--out profiles/smo_nu_rows] [--sizes a,b]
+        RowOneClassSVM (nu = 0.1) and RowNuSVC (nu = 0.2) on the same blobs: at a = 100 000 beside the resident OneClassSVM / NuSVC
+        at the same tol, at b = 400 000 beside one streamed product
+    python tools/smo_rows_profile.py nu-fit --model oneclass|nusvc --route rows|resident --n N --json FILE   one such fit
 
 Every measurement runs in a process of its own under its own time limit, after a warm-up fit of n = 4000 on the same route; a wall
 time ends after the solver's last read-back, which synchronises the stream."""
@@ -153,6 +157,80 @@ def cmd_product(args):
     print(json.dumps(rec))
 
 
+NU = {'oneclass': 0.1, 'nusvc': 0.2}
+
+
+def _nu_model(model, route):
+    from optiml_amd.ml.svm import NuSVC, OneClassSVM, RowNuSVC, RowOneClassSVM
+    from optiml_amd.ml.svm.kernels import gaussian
+    if route == 'rows':
+        return (RowOneClassSVM if model == 'oneclass' else RowNuSVC)(kernel=gaussian, nu=NU[model], tol=TOL)
+    return (OneClassSVM if model == 'oneclass' else NuSVC)(kernel=gaussian, nu=NU[model], tol=TOL, max_iter=100000, storage='f64')
+
+
+def cmd_nu_fit(args):
+    """one fit of a nu-family model in this (fresh) process after a warm-up fit of n = 4000 on the same route; on the row route
+    also the streamed product of the same data — the start gradient of these duals is one such product"""
+    from optiml_amd.opti import KernelQuadratic
+    fit = (lambda m, X, y: m.fit(X)) if args.model == 'oneclass' else (lambda m, X, y: m.fit(X, y))
+    fit(_nu_model(args.model, args.route), *_data(4000))
+    X, y = _data(args.n)
+    t0 = time.perf_counter()
+    est = fit(_nu_model(args.model, args.route), X, y)
+    wall = time.perf_counter() - t0
+    rec = {'what': 'nu fit', 'model': type(est).__name__, 'nu': NU[args.model], 'n': args.n, 'd': D, 'route': args.route, 'tol': TOL,
+           'wall_s': wall, 'steps': int(est.n_iter_), 'status': est.status_, 'n_sv': int(len(est.support_)),
+           'kkt_violation': float(est.kkt_violation_), 'per_step_us': 1e6 * wall / max(int(est.n_iter_), 1),
+           'includes': 'problem build (image or panel) + start + solve + read-back',
+           'steps_are': 'pair updates' if args.route == 'rows' else 'projected-gradient iterations (one panel product each)'}
+    if args.route == 'rows':
+        st = est.cache_stats_
+        rec.update(hits=st['hits'], misses=st['misses'], cache_rows=st['cache_rows'], hit_rate=st['hits'] / max(st['hits'] + st['misses'], 1),
+                   image_bytes_per_row=_image_bytes(args.n))
+        quad = KernelQuadratic(X, np.zeros(args.n), 'plain', est.kernel_, storage='stream')
+        rec['start_product_s'] = quad.device_problem().time_matvec(3) / 1e3
+        quad.release()
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+def cmd_nu_all(args):
+    out = os.path.join(REPO, args.out)
+    os.makedirs(out, exist_ok=True)
+    a, b = (int(v) for v in args.sizes.split(','))
+    # a step that fails or runs into its limit ends the job: nothing more is started on the device after it
+    plan = [('%s_%s_%s' % (tag, model, route), ['nu-fit', '--model', model, '--route', route, '--n', str(n)])
+            for tag, n, route in (('a', a, 'rows'), ('b', b, 'rows'), ('a', a, 'resident')) for model in ('oneclass', 'nusvc')]
+    have = os.path.join(out, 'records.json')   # records of an earlier call with the same --out are kept: the job may be cut in two
+    R = {k: v for k, v in json.load(open(have)).items() if 'failed' not in v} if os.path.exists(have) else {}
+    for name, argv in plan:
+        if name in args.skip.split(',') or name in R:
+            continue
+        R[name] = _child(out, name, argv, args.fit_limit)
+        _write_nu(out, R, (a, b))
+        if 'failed' in R[name]:
+            break
+
+
+def _write_nu(out, R, sizes):
+    json.dump(R, open(os.path.join(out, 'records.json'), 'w'), indent=1)
+    lines = ['# Row-based one-class SVM and nu-SVC: measurements', '',
+             'Written by `tools/smo_rows_profile.py nu-all` (sizes %s): bench.py\'s headline blobs (d = 128, RBF with gamma = \'scale\'), '
+             'tol 1e-3, each fit in a fresh process warmed by an n = 4 000 fit; raw records: `records.json` and one JSON per measurement.  '
+             'Steps of the row route are pair updates, of the resident route projected-gradient iterations: only the wall times compare.  '
+             '`start product` is one streamed Gram product of the same data, timed apart (the start gradient is one such product).'
+             % (sizes,), '',
+             '| record | model | n | steps | status | wall s | start product s | us / step | hit rate | support vectors | note |',
+             '|---|---|---|---|---|---|---|---|---|---|---|']
+    for name, r in R.items():
+        fmt = lambda key, f: f % r[key] if key in r else ''
+        lines.append('| %s | %s | %s | %s | %s | %s | %s | %s | %s | %s | %s |' % (
+            name, r.get('model', ''), r.get('n', ''), r.get('steps', ''), r.get('status', ''), fmt('wall_s', '%.3f'),
+            fmt('start_product_s', '%.4f'), fmt('per_step_us', '%.1f'), fmt('hit_rate', '%.3f'), r.get('n_sv', ''),
+            r.get('failed') or r.get('steps_are', '')))
+    open(os.path.join(out, 'README.md'), 'w').write('\n'.join(lines) + '\n')
+
+
 def _row_kernel_stats(trace_dir):
     """per kernel of bq_rsmo.hip: all launches, and those that computed a row (a launch on a hit only reads the cache: the two
     populations are split at the midpoint of the 10th and 99th percentile)"""
@@ -267,6 +345,18 @@ def main():
     p.add_argument('--reps', type=int, default=3)
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_stages)
+    p = sub.add_parser('nu-all')
+    p.add_argument('--out', default='profiles/smo_nu_rows')
+    p.add_argument('--sizes', default='100000,400000')
+    p.add_argument('--fit-limit', type=int, default=300, help='time limit of each fit, seconds')
+    p.add_argument('--skip', default='', help='records to leave out, comma-separated')
+    p.set_defaults(fn=cmd_nu_all)
+    p = sub.add_parser('nu-fit')
+    p.add_argument('--model', required=True, choices=['oneclass', 'nusvc'])
+    p.add_argument('--route', default='rows', choices=['rows', 'resident'])
+    p.add_argument('--n', type=int, required=True)
+    p.add_argument('--json', required=True)
+    p.set_defaults(fn=cmd_nu_fit)
     p = sub.add_parser('product')
     p.add_argument('--n', type=int, required=True)
     p.add_argument('--json', required=True)
