@@ -67,6 +67,7 @@ extern "C" {
 /* (still 3: bq_msmo_svr_heldout and bq_msmo_svc_heldout were added; nothing existing changed) */
 /* (still 3: bq_rsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
 /* (still 3: bq_rsmo_create_general and BQ_RSMO_NU_SCALARS were added; nothing existing changed) */
+/* (still 3: bq_mrsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -836,6 +837,27 @@ int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished);
 int bq_rsmo_get(bq_rsmo *s, int what, double *out);
 int bq_rsmo_rows(bq_rsmo *s, int m, const int64_t *idx, double *out);
 int bq_rsmo_destroy(bq_rsmo *s);
+
+/* ---- batched panel-free SMO: k columns on one streamed problem, one row cache, rows made 16 at a time (bq_mrsmo.hip) ---------------
+ * Column c is the dual bq_rsmo_create_general solves with BQ_RSMO_RULE_PLAIN and a zero start on (signs, lin, boxes)[c N .. (c + 1) N),
+ * N = n or 2n ([+1 ..; -1 ..], the row of variable v is v mod n) for all columns: the same scalar rules (csrc/bq_rsmo_step.h), the
+ * same (i, j), stop test and rho as that solver run on the rows bq_mrsmo_rows returns.  The columns share ONE cache of kernel rows
+ * (cache_rows, 0: as many as half of the free memory holds; at least 2 k, what one step keeps live): the rows all live columns
+ * ask for in a phase of a step are resolved together (csrc/bq_mrsmo_cache.h: equal rows share a slot, one miss and otherwise
+ * hits; LRU victims, never a row the step still reads) and the missing ones are made by one pass of the fp64-MFMA row-block
+ * kernel per 16 rows.  A row's bits depend on its two x rows and d only: no trajectory depends on the cache or on the other columns.
+ * BQ_ERR_BADARG: what bq_rsmo_create_general refuses per column, a resident problem, k outside 1 .. 1024, cache_rows in 1 .. 2k - 1.
+ * bq_mrsmo_run enqueues max_steps steps (four launches each) with no host synchronisation; a finished column drops out;
+ * steps[k] / finished[k] as bq_rsmo_run reports them per column.
+ * bq_mrsmo_get: BQ_RSMO_ALPHAS / _GRADIENT / _SCALARS of `column`; BQ_RSMO_STATS of the solver (column is not read).
+ * bq_mrsmo_rows: m x n kernel rows through the cache, any m, repeats allowed. */
+typedef struct bq_mrsmo bq_mrsmo;
+int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
+                    int64_t max_steps, int64_t cache_rows, bq_mrsmo **out);
+int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int *finished);
+int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out);
+int bq_mrsmo_rows(bq_mrsmo *s, int m, const int64_t *idx, double *out);
+int bq_mrsmo_destroy(bq_mrsmo *s);
 
 /* ---- prediction (optiml/ml/svm/_base.py:284-287) ------------------------------- */
 /* out[t] = sum_m coef[m] * kernel(SV[m], Xt[t]) + intercept   (SV: m x d, Xt: t x d, row-major fp64) */

@@ -1,0 +1,664 @@
+// Batched panel-free SMO (bq_mrsmo_*, bcqp.h): k columns of libsvm's WSS2 decomposition (the scalar rules of bq_rsmo_step.h, rule
+// BQ_RSMO_RULE_PLAIN, zero start) on ONE streamed problem, ONE cache of kernel rows, and kernel rows made 16 at a time by fp64 MFMA.
+// A row of K does not depend on the labels: every column asks for rows of the same matrix, so the rows all columns need in a phase
+// of a step are resolved together (bq_mrsmo_cache.h) and the missing ones are made in one pass over the k-major image.
+//
+// A step of all live columns is four launches:
+//   mr_rows_kernel    the missing rows i      grid: column blocks of MR_COLS
+//   mr_select_kernel  WSS2 partner j, update  grid: (slices of RSMO_T columns) x (columns of the batch)
+//   mr_rows_kernel    the missing rows j
+//   mr_update_kernel  gradient, next i, stop  grid: (slices) x (columns)
+// select / update are bq_rsmo.hip's with the row read from its slot.  Per column the slices meet at the column's ticket
+// (bq_reduce.h) and the last one takes the column's decision; the columns meet at the solver's ticket and the last one resolves the
+// cache for all of them and writes the miss list the next mr_rows_kernel reads — the host never sees it.  What crosses workgroups
+// inside a launch (partials, the requested rows) travels as agent-scope atomics; everything else is written by the last workgroup
+// of one launch and read by the next launch.  A column that has finished launches nothing but returning workgroups.
+//
+// The row-block kernel.  A workgroup owns MR_COLS = 256 columns of the image, a wave 64 of them as four independent 16 x 16
+// accumulator tiles: lane (c = lane & 15, q = lane >> 4) feeds tile j the column 4 c + j of the wave's 64, so one k-row of the image
+// is read by a lane as 32 contiguous bytes and by 16 lanes as 512, and each value loaded feeds all 16 rows.  A is the up to 16
+// requested rows of X, staged in LDS in fragment order (As[kb][lane] = x_{row(lane & 15)}[4 kb + (lane >> 4)]), MR_KC features at a
+// time, zero where the group has fewer than 16 rows or the feature index is beyond d - 1 (the image is not read there either).
+// v_mfma_f64_16x16x4_f64 keeps rows and columns of D apart, and every element is the same ascending sequence of k-blocks: the bits
+// of K[r][t] depend on x_r, x_t and d only, and (r, t) and (t, r) are the same products in the same order.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "bq_common.h"
+#include "bq_gram_image.h"
+#include "bq_mrsmo_cache.h"
+#include "bq_reduce.h"
+#include "bq_rsmo_map.h"
+#include "bq_rsmo_pick.h"
+#include "bq_rsmo_step.h"
+
+namespace {
+
+constexpr int MR_COLS = 256;   // image columns per workgroup of the row-block kernel (4 waves x 4 tiles x 16)
+constexpr int MR_G = 16;       // rows per pass: the MFMA's M
+constexpr int MR_KC = 256;     // features of the 16 rows staged at a time (32 KiB of LDS)
+constexpr int MR_REQ = 1024;   // requests per resolution (the tables of the last workgroup): columns of a batch, rows of a bq_mrsmo_rows call
+
+struct mr_col {   // a column's control block
+    long long steps;
+    int i, slot_i;          // the pending selection and the slot of its row
+    int j, slot_j;          // the partner the select kernel chose
+    int finished;           // 0 running, 1 optimal, 2 stopped at the cap
+    int last_i, last_j;
+    unsigned int ticket;
+    double gmax, gmax2, d_i, d_j, y_i, y_j;
+};
+struct mr_glob {
+    bq_mrsmo_cache cache;
+    long long cap;
+    int live;     // columns still running: the arrivals of the solver's ticket
+    int n_miss;   // the miss list's length
+    unsigned int ticket;
+};
+struct mr_dev {
+    int64_t n, N, mp, d, pitch;
+    int k;
+    const double *At, *a2, *X;
+    double gamma, coef0, tol;
+    int degree;
+    double *alpha, *G, *y, *Cb;   // k x N
+    double *QD;                   // n
+    double *cache;                // R x pitch
+    mr_col *col;                  // k
+    mr_glob *glob;
+    int *req_row;                 // k: the row each column asks for in the phase in hand, -1: none
+    int *miss_row, *miss_slot;    // MR_REQ: the distinct missing rows and their slots
+    int *req_in, *req_out;        // MR_REQ: bq_mrsmo_rows' requests and their slots
+    int *res_req, *res_slot, *res_pin;   // MR_REQ each: the tables of a resolution, touched by the launch's last workgroup only
+    double *part_v, *part_k, *part_w;   // k x nblk
+    long long *part_i;
+};
+// The tables of a resolution (requests, their slots, the pins) live in global memory, not in LDS: one workgroup of a launch uses
+// them, and 12 KiB of LDS in every workgroup of the (slices x columns) grid would be carried for nothing.  That workgroup writes
+// them, passes a barrier and reads them back; nobody else touches them inside the launch.
+struct mr_par {   // bq_mrsmo_resolve over the threads of one workgroup
+    rsmo_pick_smem<long long> &sh;
+    __device__ __forceinline__ int tid() const { return threadIdx.x; }
+    __device__ __forceinline__ int size() const { return RSMO_T; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    __device__ __forceinline__ void pick(long long *best, long long *victim) const {
+        double rider = 0.0;
+        rsmo_block_pick<rsmo_victim_order>(*best, *victim, rider, sh);
+    }
+};
+
+// ---- the row-block kernel ---------------------------------------------------------------------------------------------------------
+template <int KIND, int DEG>
+__global__ __launch_bounds__(RSMO_T) void mr_rows_kernel(mr_dev P) {
+    const int n_miss = P.glob->n_miss;
+    if (n_miss == 0) return;
+    __shared__ double As[(MR_KC / 4) * 64];
+    const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4;
+    const int64_t c4 = (int64_t)blockIdx.x * MR_COLS + (tid >> 6) * 64 + 4 * (lane & 15);   // this lane's columns c4 .. c4 + 3
+    const bool active = c4 < P.mp;   // wave-uniform: mp is a multiple of 128
+    const double *bp = P.At + (active ? c4 : 0);
+    for (int g0 = 0; g0 < n_miss; g0 += MR_G) {
+        const int cnt = n_miss - g0 < MR_G ? n_miss - g0 : MR_G;
+        bq_d4 acc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = (bq_d4){0.0, 0.0, 0.0, 0.0};
+        for (int64_t k0 = 0; k0 < P.d; k0 += MR_KC) {
+            const int len = (int)(P.d - k0 < MR_KC ? P.d - k0 : MR_KC), nkb = (len + 3) / 4, nfull = len / 4;
+            __syncthreads();
+            for (int e = tid; e < nkb * 64; e += RSMO_T) {
+                const int r = e & 15;
+                const int64_t kk = k0 + 4 * (e >> 6) + ((e & 63) >> 4);
+                As[e] = r < cnt && kk < P.d ? P.X[(int64_t)P.miss_row[g0 + r] * P.d + kk] : 0.0;
+            }
+            __syncthreads();
+            if (active) {
+                const double *b = bp + (k0 + kq) * P.mp;
+                auto block = [&](int kb) {   // one k-block of 4: 32 bytes of the image per lane, four independent MFMAs
+                    const double a = As[kb * 64 + lane];
+                    const bq_d2 lo = *reinterpret_cast<const bq_d2 *>(b), hi = *reinterpret_cast<const bq_d2 *>(b + 2);
+                    b += 4 * P.mp;
+                    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lo.x, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lo.y, acc[1], 0, 0, 0);
+                    acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, hi.x, acc[2], 0, 0, 0);
+                    acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, hi.y, acc[3], 0, 0, 0);
+                };
+                int kb = 0;
+                for (; kb + 4 <= nfull; kb += 4) {   // four blocks' loads go out before the first MFMA waits
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) block(kb + u);
+                }
+                for (; kb < nfull; ++kb) block(kb);
+                if (nfull < nkb) {   // the k-block that crosses d: zero operands beyond row d - 1, which is not read
+                    const double a = As[nfull * 64 + lane];
+                    bq_d2 lo = (bq_d2){0.0, 0.0}, hi = (bq_d2){0.0, 0.0};
+                    if (k0 + 4 * nfull + kq < P.d) {
+                        lo = *reinterpret_cast<const bq_d2 *>(b);
+                        hi = *reinterpret_cast<const bq_d2 *>(b + 2);
+                    }
+                    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lo.x, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lo.y, acc[1], 0, 0, 0);
+                    acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, hi.x, acc[2], 0, 0, 0);
+                    acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, hi.y, acc[3], 0, 0, 0);
+                }
+            }
+        }
+        if (!active) continue;
+        // D: column lane & 15 of each tile (= column c4 + j), rows (lane >> 4) + 4 v of the group
+        const bool rbf = KIND == BQ_KERNEL_RBF;
+        double a_t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a_t[j] = rbf ? P.a2[c4 + j] : 0.0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = kq + 4 * v;
+            if (r >= cnt) continue;
+            const int64_t rr = P.miss_row[g0 + r];
+            double *out = P.cache + (int64_t)P.miss_slot[g0 + r] * P.pitch + c4;
+            const double a_r = rbf ? P.a2[rr] : 0.0;
+            double val[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) val[j] = rsmo_map<KIND, DEG>(P, acc[j][v], a_r, a_t[j], c4 + j == rr);
+            if (c4 + 3 < P.n) {
+                *reinterpret_cast<bq_d2 *>(out) = (bq_d2){val[0], val[1]};
+                *reinterpret_cast<bq_d2 *>(out + 2) = (bq_d2){val[2], val[3]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c4 + j < P.n) out[j] = val[j];
+            }
+        }
+    }
+}
+
+// QD = diag(K) with the row-block kernel's arithmetic: a wave takes 16 columns as both operands of the same k-blocks
+template <int KIND, int DEG>
+__global__ __launch_bounds__(RSMO_T) void mr_diag_kernel(mr_dev P) {
+    const int lane = threadIdx.x & 63, kq = lane >> 4, c = lane & 15;
+    const int64_t t = ((int64_t)blockIdx.x * (RSMO_T / 64) + (threadIdx.x >> 6)) * 16 + c;
+    if (t - c >= P.mp) return;
+    bq_d4 acc = (bq_d4){0.0, 0.0, 0.0, 0.0};
+    for (int64_t k0 = 0; k0 < P.d; k0 += 4) {
+        const double a = k0 + kq < P.d ? P.At[(k0 + kq) * P.mp + t] : 0.0;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
+    }
+    const double a2 = KIND == BQ_KERNEL_RBF ? P.a2[t] : 0.0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+        if (kq + 4 * v == c && t < P.n) P.QD[t] = rsmo_map<KIND, DEG>(P, acc[v], a2, a2, true);
+}
+
+// ---- the resolution of a phase: every thread of the launch's LAST workgroup --------------------------------------------------------
+// phase_j: the rows j are asked for while the rows i of the same columns are still to be read (pins)
+__device__ __forceinline__ void mr_resolve_last(const mr_dev &P, rsmo_pick_smem<long long> &pick, bool phase_j) {
+    for (int c = threadIdx.x; c < P.k; c += RSMO_T) {
+        const int req = bq_part_get(&P.req_row[c]);
+        P.res_req[c] = req;
+        P.res_pin[c] = phase_j && req >= 0 ? P.col[c].slot_i : -1;
+    }
+    __syncthreads();
+    mr_par par{pick};
+    bq_mrsmo_resolve(&P.glob->cache, phase_j ? P.k : 0, P.res_pin, P.k, P.res_req, P.res_slot, P.miss_row, P.miss_slot, &P.glob->n_miss, par);
+    __syncthreads();
+    for (int c = threadIdx.x; c < P.k; c += RSMO_T) {
+        if (phase_j)
+            P.col[c].slot_j = P.res_slot[c];
+        else
+            P.col[c].slot_i = P.res_slot[c];
+    }
+    if (threadIdx.x == 0) {
+        int live = 0;
+        for (int c = 0; c < P.k; ++c) live += P.res_req[c] >= 0 ? 1 : 0;   // a column that goes on asks for a row in either phase
+        P.glob->live = live;
+    }
+}
+
+// ---- launch 2 of a step: WSS2 candidates against row i, j, the pair update ----------------------------------------------------------
+__global__ __launch_bounds__(RSMO_T) void mr_select_kernel(mr_dev P) {
+    const int c = blockIdx.y;
+    mr_col *cc = &P.col[c];
+    const int live = P.glob->live;
+    if (cc->finished) return;
+    __shared__ rsmo_pick_smem<double> sh;
+    __shared__ rsmo_pick_smem<long long> shl;
+    const double *alpha = P.alpha + (int64_t)c * P.N, *G = P.G + (int64_t)c * P.N, *y = P.y + (int64_t)c * P.N,
+                 *Cb = P.Cb + (int64_t)c * P.N;
+    const int i = cc->i, slot_i = cc->slot_i;
+    const double gmax = cc->gmax;
+    const int64_t r = i >= P.n ? i - P.n : i;
+    const int64_t t = (int64_t)blockIdx.x * RSMO_T + threadIdx.x;
+    const double *row = P.cache + (int64_t)(slot_i < 0 ? 0 : slot_i) * P.pitch;
+    const double k = t < P.n ? row[t] : 0.0;
+    const double qd_i = P.QD[r];
+    double bv = BQ_RSMO_INF, bk = 0.0;
+    long long bi = -1;
+    if (t < P.n) {
+        const double qd_t = P.QD[t];
+        for (int64_t v = t; v < P.N; v += P.n) {   // 2n variables: t and t + n share the row
+            const double y_t = y[v];
+            if (!bq_rsmo_in_low(y_t, alpha[v], Cb[v])) continue;
+            bool ok;
+            const double sc = bq_rsmo_score(gmax, y_t, G[v], qd_i, qd_t, k, &ok);
+            if (ok && bq_rsmo_min_before(sc, v, bv, bi)) {
+                bv = sc;
+                bi = v;
+                bk = k;
+            }
+        }
+    }
+    rsmo_block_pick<rsmo_min_order>(bv, bi, bk, sh);
+    const int64_t pb = (int64_t)c * gridDim.x;
+    if (threadIdx.x == 0) {
+        bq_part_put(&P.part_v[pb + blockIdx.x], bv);
+        bq_part_put(&P.part_i[pb + blockIdx.x], bi);
+        bq_part_put(&P.part_k[pb + blockIdx.x], bk);
+    }
+    if (!bq_last_block(&cc->ticket, gridDim.x)) return;
+    bv = BQ_RSMO_INF;
+    bi = -1;
+    bk = 0.0;
+    for (unsigned int b = threadIdx.x; b < gridDim.x; b += RSMO_T) {
+        const double v2 = bq_part_get(&P.part_v[pb + b]);
+        const long long i2 = bq_part_get(&P.part_i[pb + b]);
+        const double k2 = bq_part_get(&P.part_k[pb + b]);
+        if (bq_rsmo_min_before(v2, i2, bv, bi)) {
+            bv = v2;
+            bi = i2;
+            bk = k2;
+        }
+    }
+    rsmo_block_pick<rsmo_min_order>(bv, bi, bk, sh);
+    if (threadIdx.x == 0) {
+        int req = -1;
+        if (bi < 0) {   // no partner: libsvm's Gmin_idx == -1
+            cc->finished = 1;
+        } else {
+            const int j = (int)bi;
+            const int64_t rj = j >= P.n ? j - P.n : j;
+            double *al = P.alpha + (int64_t)c * P.N;
+            const double y_i = y[i], y_j = y[j];
+            const double old_i = al[i], old_j = al[j];
+            double a_i = old_i, a_j = old_j;
+            bq_rsmo_pair_update(y_i, y_j, G[i], G[j], qd_i, P.QD[rj], bk, Cb[i], Cb[j], &a_i, &a_j);
+            al[i] = a_i;
+            al[j] = a_j;
+            cc->d_i = a_i - old_i;
+            cc->d_j = a_j - old_j;
+            cc->y_i = y_i;
+            cc->y_j = y_j;
+            cc->j = j;
+            cc->last_i = i;
+            cc->last_j = j;
+            req = (int)rj;
+        }
+        bq_part_put(&P.req_row[c], req);
+    }
+    if (!bq_last_block(&P.glob->ticket, (unsigned int)live)) return;
+    mr_resolve_last(P, shl, true);
+}
+
+// ---- launch 4 of a step: the gradient, the next i and the stop test (first: the selection before the first step) --------------------
+__global__ __launch_bounds__(RSMO_T) void mr_update_kernel(mr_dev P, int first) {
+    const int c = blockIdx.y;
+    mr_col *cc = &P.col[c];
+    const int live = P.glob->live;
+    if (cc->finished) return;
+    __shared__ rsmo_pick_smem<double> sh;
+    __shared__ rsmo_pick_smem<long long> shl;
+    __shared__ double shw[RSMO_T / 64];
+    const double *alpha = P.alpha + (int64_t)c * P.N, *y = P.y + (int64_t)c * P.N, *Cb = P.Cb + (int64_t)c * P.N;
+    double *G = P.G + (int64_t)c * P.N;
+    const int64_t t = (int64_t)blockIdx.x * RSMO_T + threadIdx.x;
+    double g[2] = {0.0, 0.0};
+    if (t < P.n) {
+        g[0] = G[t];
+        if (P.N > P.n) g[1] = G[t + P.n];
+    }
+    if (!first && t < P.n) {
+        const double d_i = cc->d_i, d_j = cc->d_j, y_i = cc->y_i, y_j = cc->y_j;
+        const double ki = P.cache[(int64_t)(cc->slot_i < 0 ? 0 : cc->slot_i) * P.pitch + t];
+        const double kj = P.cache[(int64_t)(cc->slot_j < 0 ? 0 : cc->slot_j) * P.pitch + t];
+        int h = 0;
+        for (int64_t v = t; v < P.N; v += P.n, ++h) {
+            const double y_t = y[v];
+            const double s_i = y_i * y_t, s_j = y_j * y_t;   // +-1: exact
+            const double q_i = s_i * ki, q_j = s_j * kj;
+            g[h] = bq_rsmo_grad(g[h], q_i, d_i, q_j, d_j);
+            G[v] = g[h];
+        }
+    }
+    double uv = -BQ_RSMO_INF, rider = 0.0, low = -BQ_RSMO_INF;
+    long long ui = -1;
+    if (t < P.n) {
+        int h = 0;
+        for (int64_t v = t; v < P.N; v += P.n, ++h) {
+            const double y_t = y[v], a = alpha[v], C = Cb[v];
+            if (bq_rsmo_in_up(y_t, a, C)) {
+                const double val = bq_rsmo_up_value(y_t, g[h]);
+                if (bq_rsmo_max_before(val, v, uv, ui)) {
+                    uv = val;
+                    ui = v;
+                }
+            }
+            if (bq_rsmo_in_low(y_t, a, C)) low = fmax(low, bq_rsmo_low_value(y_t, g[h]));
+        }
+    }
+    rsmo_block_pick<rsmo_max_order>(uv, ui, rider, sh);
+    bq_wave_put<bq_op_max>(low, shw);
+    __syncthreads();
+    const int64_t pb = (int64_t)c * gridDim.x;
+    if (threadIdx.x == 0) {
+        double w = shw[0];
+        for (int q = 1; q < RSMO_T / 64; ++q) w = fmax(w, shw[q]);
+        bq_part_put(&P.part_v[pb + blockIdx.x], uv);
+        bq_part_put(&P.part_i[pb + blockIdx.x], ui);
+        bq_part_put(&P.part_w[pb + blockIdx.x], w);
+    }
+    if (!bq_last_block(&cc->ticket, gridDim.x)) return;
+    uv = -BQ_RSMO_INF;
+    ui = -1;
+    low = -BQ_RSMO_INF;
+    for (unsigned int b = threadIdx.x; b < gridDim.x; b += RSMO_T) {
+        const double v2 = bq_part_get(&P.part_v[pb + b]);
+        const long long i2 = bq_part_get(&P.part_i[pb + b]);
+        if (bq_rsmo_max_before(v2, i2, uv, ui)) {
+            uv = v2;
+            ui = i2;
+        }
+        low = fmax(low, bq_part_get(&P.part_w[pb + b]));
+    }
+    rsmo_block_pick<rsmo_max_order>(uv, ui, rider, sh);
+    __syncthreads();
+    bq_wave_put<bq_op_max>(low, shw);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        low = shw[0];
+        for (int q = 1; q < RSMO_T / 64; ++q) low = fmax(low, shw[q]);
+        const long long steps = cc->steps + (first ? 0 : 1);
+        int fin = 0;
+        if (ui < 0 || bq_rsmo_stop(uv, low, P.tol))
+            fin = 1;
+        else if (steps >= P.glob->cap)
+            fin = 2;
+        cc->steps = steps;
+        cc->gmax = uv;
+        cc->gmax2 = low;
+        cc->i = (int)ui;
+        cc->finished = fin;
+        bq_part_put(&P.req_row[c], fin ? -1 : (int)(ui >= P.n ? ui - P.n : ui));
+    }
+    if (!bq_last_block(&P.glob->ticket, (unsigned int)live)) return;
+    mr_resolve_last(P, shl, false);
+}
+
+// ---- bq_mrsmo_rows: m requested rows through the cache, the rows the live columns wait for pinned ------------------------------------
+__global__ __launch_bounds__(RSMO_T) void mr_request_kernel(mr_dev P, int m) {
+    __shared__ rsmo_pick_smem<long long> shl;
+    for (int q = threadIdx.x; q < MR_REQ; q += RSMO_T) {
+        P.res_req[q] = q < m ? P.req_in[q] : -1;
+        P.res_pin[q] = q < P.k && !P.col[q].finished ? P.col[q].slot_i : -1;
+    }
+    __syncthreads();
+    mr_par par{shl};
+    bq_mrsmo_resolve(&P.glob->cache, P.k, P.res_pin, m, P.res_req, P.res_slot, P.miss_row, P.miss_slot, &P.glob->n_miss, par);
+    __syncthreads();
+    for (int q = threadIdx.x; q < m; q += RSMO_T) P.req_out[q] = P.res_slot[q];
+}
+// the list is used up: the next step's first pass makes only what its own resolution misses
+__global__ void mr_clear_kernel(mr_dev P) { P.glob->n_miss = 0; }
+
+}   // namespace
+
+struct bq_mrsmo {
+    bq_problem *p = nullptr;
+    bq_owner mem;
+    mr_dev P = {};
+    unsigned int nblk = 0;
+    int64_t R = 0;
+    std::vector<double> y, Cb;   // host copies for calculate_rho
+    std::vector<mr_col> host;
+    bool done = false;
+};
+
+extern "C" int bq_mrsmo_destroy(bq_mrsmo *s) {
+    if (s == nullptr) return BQ_OK;
+    bq_problem *p = s->p;
+    hipSetDevice(p->ctx->device);
+    hipStreamSynchronize(p->ctx->stream);
+    delete s;
+    bq_problem_unref(p);
+    return BQ_OK;
+}
+
+static int mr_read_cols(bq_mrsmo *s) {
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipMemcpyAsync(s->host.data(), s->P.col, sizeof(mr_col) * (size_t)s->P.k, hipMemcpyDeviceToHost, c->stream));
+    BQ_HIP(hipStreamSynchronize(c->stream));
+    s->done = true;
+    for (const mr_col &cc : s->host) s->done = s->done && cc.finished != 0;
+    return BQ_OK;
+}
+
+template <typename KD>
+static void mr_launch_rows(KD, const bq_mrsmo *s, hipStream_t st) {
+    const unsigned int blocks = (unsigned int)((s->P.mp + MR_COLS - 1) / MR_COLS);
+    mr_rows_kernel<KD::kind, KD::deg><<<blocks, RSMO_T, 0, st>>>(s->P);
+}
+
+extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
+                               int64_t max_steps, int64_t cache_rows, bq_mrsmo **out) {
+    BQ_ARG(p && signs && lin && boxes && out, "NULL argument");
+    BQ_ARG(p->kernel >= 0 && p->streamed && p->stream_img != nullptr && p->ctx->world == 1,
+           "the row-based SMO needs a kernel-built streamed problem (BQ_STREAM) on a single-rank context");
+    BQ_ARG(k >= 1 && k <= MR_REQ, "k must lie in 1 .. 1024");
+    BQ_ARG(tol > 0.0, "tol must be > 0");
+    BQ_ARG(max_steps >= 0, "max_steps must be >= 0 (0: libsvm's cap)");
+    BQ_ARG(cache_rows == 0 || cache_rows >= 2 * (int64_t)k, "cache_rows must be 0 (automatic) or >= 2 k: a step holds two rows per column");
+    const int64_t n = p->n;
+    BQ_ARG(N == n || N == 2 * n, "N must be n or 2n");
+    BQ_ARG(N < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
+    for (int64_t v = 0; v < (int64_t)k * N; ++v) {
+        BQ_ARG(std::isfinite(boxes[v]) && boxes[v] > 0.0, "every box must be finite and > 0");
+        BQ_ARG(signs[v] == 1.0 || signs[v] == -1.0, "signs must be +1 / -1");
+        BQ_ARG(N == n || signs[v] == (v % N < n ? 1.0 : -1.0), "the signs of 2n variables must be [+1 ..; -1 ..]");
+        BQ_ARG(std::isfinite(lin[v]), "the linear term must be finite");
+    }
+    bq_ctx *c = p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    bq_mrsmo *s = new bq_mrsmo();
+    s->p = p;
+    p->refs += 1;
+    mr_dev &P = s->P;
+    int64_t dp = 0;
+    bq_stream_image_view(p->stream_img, &P.At, &P.a2, &P.mp, &dp);
+    P.n = n;
+    P.N = N;
+    P.k = k;
+    P.d = p->d;
+    P.X = p->X;
+    P.gamma = p->gamma;
+    P.coef0 = p->coef0;
+    P.degree = p->degree;
+    P.tol = tol;
+    P.pitch = P.mp;
+    s->nblk = (unsigned int)((n + RSMO_T - 1) / RSMO_T);
+    const size_t kN = (size_t)k * (size_t)N, parts = (size_t)k * s->nblk;
+    s->y.assign(signs, signs + kN);
+    s->Cb.assign(boxes, boxes + kN);
+    s->host.resize((size_t)k);
+    auto fail = [&](hipError_t e, const char *what) {
+        bq_set_error("%s failed: %s", what, hipGetErrorString(e));
+        hipStreamSynchronize(c->stream);
+        bq_mrsmo_destroy(s);
+        return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    };
+    bq_mrsmo_cache cache = {};
+    hipError_t e = s->mem.dev(&P.alpha, kN);
+    if (e == hipSuccess) e = s->mem.dev(&P.G, kN);
+    if (e == hipSuccess) e = s->mem.dev(&P.y, kN);
+    if (e == hipSuccess) e = s->mem.dev(&P.Cb, kN);
+    if (e == hipSuccess) e = s->mem.dev(&P.QD, (size_t)n);
+    if (e == hipSuccess) e = s->mem.dev(&cache.slot_of, (size_t)n);
+    if (e == hipSuccess) e = s->mem.dev(&P.col, (size_t)k);
+    if (e == hipSuccess) e = s->mem.dev(&P.glob, 1);
+    if (e == hipSuccess) e = s->mem.dev(&P.req_row, (size_t)k);
+    if (e == hipSuccess) e = s->mem.dev(&P.miss_row, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.miss_slot, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.req_in, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.req_out, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.res_req, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.res_slot, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.res_pin, (size_t)MR_REQ);
+    if (e == hipSuccess) e = s->mem.dev(&P.part_v, parts);
+    if (e == hipSuccess) e = s->mem.dev(&P.part_k, parts);
+    if (e == hipSuccess) e = s->mem.dev(&P.part_w, parts);
+    if (e == hipSuccess) e = s->mem.dev(&P.part_i, parts);
+    if (e != hipSuccess) return fail(e, "the batched row-based SMO's vectors");
+    // the cache: the rows asked for, or what half of the free memory holds; n rows hold every row there is
+    int64_t R = cache_rows;
+    if (R == 0) {
+        size_t free_b = 0, total_b = 0;
+        if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return fail(e, "hipMemGetInfo");
+        R = std::max<int64_t>((int64_t)(free_b / 2 / (sizeof(double) * (size_t)P.pitch)), 2 * (int64_t)k);
+    }
+    if (R > n) R = n;
+    s->R = cache.R = R;
+    if ((e = s->mem.dev(&P.cache, (size_t)R * (size_t)P.pitch)) != hipSuccess) return fail(e, "the row cache");
+    if ((e = s->mem.dev(&cache.row_of, (size_t)R)) != hipSuccess) return fail(e, "the row cache");
+    e = bq_dev_zeroed(e, s->mem, &cache.stamp, (size_t)R, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(cache.slot_of, 0xFF, sizeof(int) * (size_t)n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(cache.row_of, 0xFF, sizeof(int) * (size_t)R, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(P.req_row, 0xFF, sizeof(int) * (size_t)k, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(P.alpha, 0, sizeof(double) * kN, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(P.G, lin, sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);   // zero start: G0 = lin
+    if (e == hipSuccess) e = hipMemcpyAsync(P.y, s->y.data(), sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(P.Cb, s->Cb.data(), sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
+    mr_col c0 = {};
+    c0.i = c0.j = c0.last_i = c0.last_j = c0.slot_i = c0.slot_j = -1;
+    c0.gmax = c0.gmax2 = -INFINITY;
+    std::fill(s->host.begin(), s->host.end(), c0);
+    mr_glob g0 = {};
+    g0.cache = cache;
+    g0.cap = max_steps > 0 ? (long long)max_steps : std::max<long long>(10000000LL, 100LL * (long long)N);   // libsvm's max_iter
+    g0.cap = (long long)bq_hook_value("rsmo_max_steps", (double)g0.cap);
+    g0.live = k;
+    if (e == hipSuccess) e = hipMemcpyAsync(P.col, s->host.data(), sizeof(mr_col) * (size_t)k, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(P.glob, &g0, sizeof(g0), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return fail(e, "the batched row-based SMO's start");
+    int rc = rsmo_dispatch(p, [&](auto kd) {
+        const unsigned int waves = (unsigned int)(P.mp / 16), per = RSMO_T / 64;
+        mr_diag_kernel<decltype(kd)::kind, decltype(kd)::deg><<<(waves + per - 1) / per, RSMO_T, 0, c->stream>>>(P);
+        mr_update_kernel<<<dim3(s->nblk, (unsigned int)k), RSMO_T, 0, c->stream>>>(P, 1);
+    });
+    if (rc == BQ_OK && (e = hipGetLastError()) != hipSuccess) return fail(e, "the batched row-based SMO's first selection");
+    if (rc == BQ_OK) rc = mr_read_cols(s);   // (g0, c0 and the caller's vectors are read by then)
+    if (rc != BQ_OK) {
+        hipStreamSynchronize(c->stream);
+        bq_mrsmo_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return BQ_OK;
+}
+
+extern "C" int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int *finished) {
+    BQ_ARG(s && steps && finished, "NULL argument");
+    BQ_ARG(max_steps > 0, "max_steps must be > 0");
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    if (!s->done) {
+        const mr_dev &P = s->P;
+        const dim3 grid(s->nblk, (unsigned int)P.k);
+        BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
+            for (int64_t q = 0; q < max_steps; ++q) {
+                mr_launch_rows(kd, s, c->stream);
+                mr_select_kernel<<<grid, RSMO_T, 0, c->stream>>>(P);
+                mr_launch_rows(kd, s, c->stream);
+                mr_update_kernel<<<grid, RSMO_T, 0, c->stream>>>(P, 0);
+            }
+        }));
+        BQ_HIP(hipGetLastError());
+        BQ_TRY(mr_read_cols(s));
+    }
+    for (int q = 0; q < s->P.k; ++q) {
+        steps[q] = s->host[(size_t)q].steps;
+        finished[q] = s->host[(size_t)q].finished;
+    }
+    return BQ_OK;
+}
+
+extern "C" int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out) {
+    BQ_ARG(s && out, "NULL argument");
+    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_STATS, "what");
+    BQ_ARG(what == BQ_RSMO_STATS || (column >= 0 && column < s->P.k), "column");
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    const mr_dev &P = s->P;
+    const size_t N = (size_t)P.N, off = what == BQ_RSMO_STATS ? 0 : (size_t)column * N;
+    if (what == BQ_RSMO_ALPHAS || what == BQ_RSMO_GRADIENT) {
+        BQ_HIP(hipMemcpyAsync(out, (what == BQ_RSMO_ALPHAS ? P.alpha : P.G) + off, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+        return BQ_OK;
+    }
+    if (what == BQ_RSMO_STATS) {
+        mr_glob g;
+        BQ_HIP(hipMemcpyAsync(&g, P.glob, sizeof(g), hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+        out[0] = (double)g.cache.hits;
+        out[1] = (double)g.cache.misses;
+        out[2] = (double)s->R;
+        return BQ_OK;
+    }
+    // calculate_rho in libsvm's order, on the host
+    std::vector<double> a(N), g(N);
+    BQ_HIP(hipMemcpyAsync(a.data(), P.alpha + off, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
+    BQ_HIP(hipMemcpyAsync(g.data(), P.G + off, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
+    BQ_TRY(mr_read_cols(s));
+    bq_rsmo_rho rho;
+    for (size_t t = 0; t < N; ++t) bq_rsmo_rho_add(&rho, s->y[off + t], a[t], s->Cb[off + t], g[t]);
+    const mr_col &cc = s->host[(size_t)column];
+    out[0] = bq_rsmo_rho_value(&rho);
+    out[1] = cc.gmax;
+    out[2] = cc.gmax2;
+    out[3] = (double)cc.last_i;
+    out[4] = (double)cc.last_j;
+    out[5] = (double)cc.steps;
+    return BQ_OK;
+}
+
+extern "C" int bq_mrsmo_rows(bq_mrsmo *s, int m, const int64_t *idx, double *out) {
+    BQ_ARG(s && idx && out, "NULL argument");
+    BQ_ARG(m >= 1, "m must be >= 1");
+    const mr_dev &P = s->P;
+    for (int q = 0; q < m; ++q) BQ_ARG(idx[q] >= 0 && idx[q] < P.n, "a requested row lies outside the problem");
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    // a call resolves what fits beside the rows the live columns wait for
+    const int batch = (int)std::min<int64_t>(MR_REQ, std::max<int64_t>(1, s->R - P.k));
+    std::vector<int> rows((size_t)batch), slots((size_t)batch);
+    int rc = BQ_OK;
+    for (int q0 = 0; q0 < m && rc == BQ_OK; q0 += batch) {
+        const int cnt = std::min(batch, m - q0);
+        for (int q = 0; q < cnt; ++q) rows[(size_t)q] = (int)idx[q0 + q];
+        BQ_HIP(hipMemcpyAsync(P.req_in, rows.data(), sizeof(int) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+        rc = rsmo_dispatch(s->p, [&](auto kd) {
+            mr_launch_rows(kd, s, c->stream);   // the rows the step in hand still waits for
+            mr_request_kernel<<<1, RSMO_T, 0, c->stream>>>(P, cnt);
+            mr_launch_rows(kd, s, c->stream);
+            mr_clear_kernel<<<1, 1, 0, c->stream>>>(P);
+        });
+        BQ_HIP(hipGetLastError());
+        BQ_HIP(hipMemcpyAsync(slots.data(), P.req_out, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+        for (int q = 0; q < cnt; ++q) {
+            if (slots[(size_t)q] < 0) {
+                bq_set_error("the row cache has no free slot beside the rows of the step in hand");
+                return BQ_ERR_BADARG;
+            }
+            BQ_HIP(hipMemcpyAsync(out + (size_t)(q0 + q) * (size_t)P.n, P.cache + (size_t)slots[(size_t)q] * (size_t)P.pitch,
+                                  sizeof(double) * (size_t)P.n, hipMemcpyDeviceToHost, c->stream));
+        }
+        BQ_HIP(hipStreamSynchronize(c->stream));   // the slots may be evicted by the next batch
+    }
+    return rc;
+}

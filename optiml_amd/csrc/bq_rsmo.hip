@@ -29,11 +29,12 @@
 #include "bq_common.h"
 #include "bq_gram_image.h"
 #include "bq_reduce.h"
+#include "bq_rsmo_map.h"
+#include "bq_rsmo_pick.h"
 #include "bq_rsmo_step.h"
 
 namespace {
 
-constexpr int RSMO_T = 256;        // threads per workgroup = columns per workgroup (the slice)
 constexpr int RSMO_XCHUNK = 512;   // features of x_i staged at a time
 
 struct rsmo_ctl {
@@ -67,24 +68,6 @@ struct rsmo_dev {
     long long *part_i2;
     double *rowbuf;                    // n: a row on its way to the host
 };
-
-// ---- the kernel map (bq_gram_image.h / bq_exp.h) on one inner product ------------------------------------------------------------
-template <int KIND, int DEG>
-__device__ __forceinline__ double rsmo_map(const rsmo_dev &P, double dot, double a_r, double a_t, bool diag) {
-    if (KIND == BQ_KERNEL_RBF) {
-        double dist = -2.0 * dot;
-        const double norms = a_r + a_t;   // commutative: K[r][t] and K[t][r] take the same path
-        dist += norms;
-        dist = fmax(dist, 0.0);
-        if (diag) dist = 0.0;
-        return bq_exp(-P.gamma * dist);
-    } else if (KIND == BQ_KERNEL_POLY) {
-        return bq_poly_map<DEG>(P.gamma * dot + P.coef0, P.degree);
-    } else if (KIND == BQ_KERNEL_SIGMOID) {
-        return tanh(P.gamma * dot + P.coef0);
-    }
-    return dot;
-}
 
 // K[r][t] for the column t of this thread (0 beyond n); called by every thread of the workgroup (barriers inside)
 template <int KIND, int DEG>
@@ -135,54 +118,6 @@ __device__ __forceinline__ void rsmo_row_value2(const rsmo_dev &P, int64_t ra, i
     const bool rbf = KIND == BQ_KERNEL_RBF;
     *ka = rsmo_map<KIND, DEG>(P, acc_a, rbf ? P.a2[ra] : 0.0, rbf ? P.a2[t] : 0.0, t == ra);
     *kb = rsmo_map<KIND, DEG>(P, acc_b, rbf ? P.a2[rb] : 0.0, rbf ? P.a2[t] : 0.0, t == rb);
-}
-
-// ---- (value, index, rider) picks over a workgroup: every thread receives the winner --------------------------------------------------
-struct rsmo_min_order {
-    static __device__ __forceinline__ bool before(double va, long long ia, double vb, long long ib) { return bq_rsmo_min_before(va, ia, vb, ib); }
-};
-struct rsmo_max_order {
-    static __device__ __forceinline__ bool before(double va, long long ia, double vb, long long ib) { return bq_rsmo_max_before(va, ia, vb, ib); }
-};
-struct rsmo_victim_order {
-    static __device__ __forceinline__ bool before(long long va, long long ia, long long vb, long long ib) { return bq_rsmo_victim_before(va, ia, vb, ib); }
-};
-template <typename V>
-struct rsmo_pick_smem {
-    V v[RSMO_T / 64];
-    long long i[RSMO_T / 64];
-    double k[RSMO_T / 64];
-};
-template <typename ORDER, typename V>
-__device__ __forceinline__ void rsmo_block_pick(V &v, long long &idx, double &rider, rsmo_pick_smem<V> &sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const V v2 = __shfl_down(v, off, 64);
-        const long long i2 = __shfl_down(idx, off, 64);
-        const double k2 = __shfl_down(rider, off, 64);
-        if (ORDER::before(v2, i2, v, idx)) {
-            v = v2;
-            idx = i2;
-            rider = k2;
-        }
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        sh.v[threadIdx.x >> 6] = v;
-        sh.i[threadIdx.x >> 6] = idx;
-        sh.k[threadIdx.x >> 6] = rider;
-    }
-    __syncthreads();
-    v = sh.v[0];
-    idx = sh.i[0];
-    rider = sh.k[0];
-#pragma unroll
-    for (int w = 1; w < RSMO_T / 64; ++w)
-        if (ORDER::before(sh.v[w], sh.i[w], v, idx)) {
-            v = sh.v[w];
-            idx = sh.i[w];
-            rider = sh.k[w];
-        }
 }
 
 // ---- the cache: slot of row r, called by every thread of ONE workgroup (the last of a launch, or a one-workgroup launch) -----------
@@ -581,28 +516,6 @@ __global__ __launch_bounds__(RSMO_T) void rsmo_fill_kernel(rsmo_dev P, int64_t r
         if (t < P.n) row[t] = k;
     }
     if (t < P.n) P.rowbuf[t] = k;
-}
-
-template <int K, int D>
-struct rsmo_kind {
-    static constexpr int kind = K, deg = D;
-};
-template <typename F>
-int rsmo_dispatch(const bq_problem *p, F f) {
-    switch (p->kernel) {
-    case BQ_KERNEL_LINEAR: f(rsmo_kind<BQ_KERNEL_LINEAR, 0>{}); return BQ_OK;
-    case BQ_KERNEL_RBF: f(rsmo_kind<BQ_KERNEL_RBF, 0>{}); return BQ_OK;
-    case BQ_KERNEL_SIGMOID: f(rsmo_kind<BQ_KERNEL_SIGMOID, 0>{}); return BQ_OK;
-    case BQ_KERNEL_POLY:
-        if (p->degree == 1) f(rsmo_kind<BQ_KERNEL_POLY, 1>{});
-        else if (p->degree == 2) f(rsmo_kind<BQ_KERNEL_POLY, 2>{});
-        else if (p->degree == 3) f(rsmo_kind<BQ_KERNEL_POLY, 3>{});
-        else f(rsmo_kind<BQ_KERNEL_POLY, 0>{});
-        return BQ_OK;
-    default: break;
-    }
-    bq_set_error("bad argument: the row kernel is built for the kernels a streamed problem takes (linear, poly, rbf, sigmoid)");
-    return BQ_ERR_BADARG;
 }
 
 }   // namespace

@@ -21,6 +21,7 @@ from ._base import SVC, SVR, ClassifierMixin, RegressorMixin, BaseEstimator, Con
 from .kernels import GaussianKernel, LinearKernel, PolyKernel, SigmoidKernel, gaussian
 from .losses import squared_hinge, squared_epsilon_insensitive
 from .smo import SMOClassifier, SMORegression
+from .smo_rows import RowSMOBatch, RowSMOClassifier, RowSMORegression
 
 MEMORY_SHARE = 0.5   # share of the device memory free after the panel that one solve's columns and slab may take
 MAX_COLUMNS = 4096   # columns per batched solve at most (see column_cap)
@@ -309,6 +310,29 @@ def fitted_smo_svr(est, quad, r, X, y):
         est.coef_ = est.optimizer.w
     est.intercept_ = est.optimizer.b
     return sv
+
+
+def takes_row_batch(est, batch_smo, loss):
+    """True when `batch_smo` is 'rows': the columns of `est`'s configuration are solved together by the batched panel-free SMO
+    (`RowSMOBatch`, `bq_mrsmo_*`).  The route is opt-in and is the SMO branch of `fit` on a streamed problem only: anything else
+    with 'rows' is a ValueError, not another path."""
+    if not (isinstance(batch_smo, str) and batch_smo == 'rows'):
+        return False
+    if not (est._is_smo() and est.storage == 'stream' and est.loss == loss and not est.reg_intercept):
+        raise ValueError("batch_smo='rows' is the SMO branch on a streamed problem: optimizer='smo', storage='stream', dual=True, "
+                         "the hinge / epsilon-insensitive loss, reg_intercept=False")
+    if get_context().world != 1:
+        raise NotImplementedError("optimizer='smo' with storage='stream' runs on a single-rank context")
+    return True
+
+
+def solve_row_batch(cols):
+    """Run the unrun row-based solvers `cols` (one type, one quad) as the columns of one `RowSMOBatch`; a column that ends at
+    libsvm's iteration cap warns as its own fit does."""
+    RowSMOBatch(cols).minimize()
+    if any(col.status == 'stopped' for col in cols):
+        warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
+    return cols
 
 
 def uses_batched_smo(est, loss, world, weighted=False):

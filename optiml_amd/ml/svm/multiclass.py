@@ -22,9 +22,11 @@ from ...opti.constrained import FrankWolfe, ProjectedGradient
 from ... import _lib
 from ._batched import (ClassQuadratic, DecisionBatch, _DeviceALSolver, _DeviceMultiSolver, _MultiClassSVC, _gram_matmat,
                        _svc_attributes, fitted_lagrangian, fitted_smo_svc, fitted_svc, intercept, lagrangian_columns,
-                       solve_batched, solve_batched_al, solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision,
-                       uses_batched_lagrangian, uses_batched_smo)
+                       solve_batched, solve_batched_al, solve_batched_smo, solve_row_batch, solver_kind, takes_batched_smo,
+                       takes_row_batch, uses_batched_decision, uses_batched_lagrangian, uses_batched_smo)
+from .smo_rows import RowSMOClassifier
 from ._base import has_class_weight, row_boxes
+from .kernels import LinearKernel
 from .losses import Hinge, SquaredHinge
 
 __all__ = ['OneVsRestSVC', 'uses_batched_path', 'uses_batched_lagrangian_path', 'uses_batched_smo_path', 'binarize']
@@ -82,6 +84,10 @@ class OneVsRestSVC(_MultiClassSVC):
 
     `smo_`: the classes were solved together by the batched SMO solver (`uses_batched_smo_path`).  `batch_smo` (None, True,
     False) forces that choice where the configuration allows it; None leaves it to the number of classes (`takes_batched_smo`).
+
+    `batch_smo='rows'` (opt-in; optimizer='smo', storage='stream'): the classes are solved together by the batched panel-free SMO
+    (`RowSMOBatch`, `bq_mrsmo_*`) — one cache of kernel rows for all classes, missing rows made 16 at a time — instead of one
+    `RowSMOClassifier` fit per class; `rows_` says so.  Every estimator has the attributes its own fit sets; prediction is unchanged.
     """
     batch_smo = None
 
@@ -92,11 +98,17 @@ class OneVsRestSVC(_MultiClassSVC):
         if isinstance(proto.class_weight, dict):
             # every class is fitted on the labels 0 / 1 of its own binary problem: a dict's keys, the data's labels, name none of them
             raise ValueError("OneVsRestSVC takes class_weight=None or 'balanced': the binary problems' labels are not the data's")
+        self.rows_ = takes_row_batch(proto, self.batch_smo, Hinge)
         self.lagrangian_ = uses_batched_lagrangian_path(proto, get_context().world, X.shape[0])
-        self.smo_ = uses_batched_smo_path(proto, get_context().world) and takes_batched_smo(len(Y), self.batch_smo)
-        self.batched_ = self.lagrangian_ or self.smo_ or uses_batched_path(proto, get_context().world)
-        self.batched_decision_ = uses_batched_decision(proto.kernel, len(Y), get_context().world, self.batched_)
+        self.smo_ = (not self.rows_ and uses_batched_smo_path(proto, get_context().world) and
+                     takes_batched_smo(len(Y), self.batch_smo))
+        self.batched_ = self.rows_ or self.lagrangian_ or self.smo_ or uses_batched_path(proto, get_context().world)
+        # the rows route leaves prediction to the estimators, as the per-class route of its configuration does
+        self.batched_decision_ = not self.rows_ and uses_batched_decision(proto.kernel, len(Y), get_context().world, self.batched_)
         self.decision_batch_ = None
+        if self.rows_:
+            self.estimators_ = self._fit_rows(proto, X, Y)
+            return self
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, (Yc > 0).astype(int)) for Yc in Y]
             return self
@@ -126,6 +138,23 @@ class OneVsRestSVC(_MultiClassSVC):
                                                                         est.optimizer.iter, est.optimizer.steps))
         if self.batched_decision_:
             self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
+        return ests
+
+    def _fit_rows(self, proto, X, Y):
+        """SVC.fit's SMO branch on a streamed problem for every class at once: one problem, one `RowSMOClassifier` per class with
+        the boxes of its own binary problem, one batched solve."""
+        k, n = Y.shape
+        obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=Y[0], storage=proto.storage, rank_one=False, compact=False)
+        boxes = [row_boxes(proto.C, (Yc > 0).astype(int), np.arange(2), proto.class_weight) for Yc in Y]
+        cols = solve_row_batch([RowSMOClassifier(obj, X, Yc, None, proto.kernel, proto.C, proto.tol, False, box)
+                                for Yc, box in zip(Y, boxes)])
+        ests = [self._prototype() for _ in range(k)]
+        for c, est in enumerate(ests):
+            est.obj, est.optimizer = ClassQuadratic(obj, Y[c]), cols[c]
+            _svc_attributes(est, X, Y[c], cols[c].alphas)
+            if isinstance(proto.kernel, LinearKernel):
+                est.coef_ = cols[c].w
+            est.intercept_ = cols[c].b
         return ests
 
     def _fit_batched(self, proto, X, Y):

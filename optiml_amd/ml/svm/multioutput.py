@@ -23,8 +23,10 @@ from ... import _lib
 from ._base import has_class_weight
 from ._batched import (DecisionBatch, TargetQuadratic, _DeviceALSolver, _DeviceSVRSolver, _MultiTargetSVR, _gram_matmat,
                        _svr_attributes, fitted_lagrangian, fitted_smo_svr, fitted_svr, lagrangian_columns, solve_batched,
-                       solve_batched_al, solve_batched_smo, solver_kind, svr_intercept, takes_batched_smo, uses_batched_decision,
-                       uses_batched_lagrangian, uses_batched_smo)
+                       solve_batched_al, solve_batched_smo, solve_row_batch, solver_kind, svr_intercept, takes_batched_smo,
+                       takes_row_batch, uses_batched_decision, uses_batched_lagrangian, uses_batched_smo)
+from .kernels import LinearKernel
+from .smo_rows import RowSMORegression
 from .losses import EpsilonInsensitive, SquaredEpsilonInsensitive
 
 __all__ = ['MultiOutputSVR', 'uses_batched_svr_path', 'uses_batched_lagrangian_svr_path', 'uses_batched_smo_svr_path']
@@ -70,6 +72,10 @@ class MultiOutputSVR(_MultiTargetSVR):
 
     `smo_`: the targets were solved together by the batched SMO solver (`uses_batched_smo_svr_path`).  `batch_smo` (None, True,
     False) forces that choice where the configuration allows it; None leaves it to the number of targets (`takes_batched_smo`).
+
+    `batch_smo='rows'` (opt-in; optimizer='smo', storage='stream'): the targets are solved together by the batched panel-free SMO
+    (`RowSMOBatch`, `bq_mrsmo_*`) instead of one `RowSMORegression` fit per target; `rows_` says so.  Every estimator has the
+    attributes its own fit sets; prediction is unchanged.
     """
     batch_smo = None
 
@@ -79,11 +85,17 @@ class MultiOutputSVR(_MultiTargetSVR):
         if Y.ndim == 1:
             raise ValueError('y must have at least two dimensions for multi-output regression but has only one.')
         proto = self._prototype()
+        self.rows_ = takes_row_batch(proto, self.batch_smo, EpsilonInsensitive)
         self.lagrangian_ = uses_batched_lagrangian_svr_path(proto, get_context().world, 2 * X.shape[0])
-        self.smo_ = uses_batched_smo_svr_path(proto, get_context().world) and takes_batched_smo(Y.shape[1], self.batch_smo)
-        self.batched_ = self.lagrangian_ or self.smo_ or uses_batched_svr_path(proto, get_context().world)
-        self.batched_decision_ = uses_batched_decision(proto.kernel, Y.shape[1], get_context().world, self.batched_)
+        self.smo_ = (not self.rows_ and uses_batched_smo_svr_path(proto, get_context().world) and
+                     takes_batched_smo(Y.shape[1], self.batch_smo))
+        self.batched_ = self.rows_ or self.lagrangian_ or self.smo_ or uses_batched_svr_path(proto, get_context().world)
+        # the rows route leaves prediction to the estimators, as the per-target route of its configuration does
+        self.batched_decision_ = not self.rows_ and uses_batched_decision(proto.kernel, Y.shape[1], get_context().world, self.batched_)
         self.decision_batch_ = None
+        if self.rows_:
+            self.estimators_ = self._fit_rows(proto, X, np.ascontiguousarray(Y.T))
+            return self
         if not self.batched_:
             self.estimators_ = [self._prototype().fit(X, Y[:, c]) for c in range(Y.shape[1])]
             return self
@@ -109,6 +121,23 @@ class MultiOutputSVR(_MultiTargetSVR):
                 print('target %d: %d outer iterations, %d pair steps' % (c, est.optimizer.iter, est.optimizer.steps))
         if self.batched_decision_:
             self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
+        return ests
+
+    def _fit_rows(self, proto, X, Y):
+        """SVR.fit's SMO branch on a streamed problem for every target at once: one problem, one `RowSMORegression` per target
+        (epsilon enters through its linear term), one batched solve."""
+        k, n = Y.shape
+        QL = np.hstack((-Y, Y)) + proto.epsilon   # row c: SVR.fit's q of target c
+        obj = KernelQuadratic(X, QL[0], 'svr', proto.kernel, storage=proto.storage, rank_one=False, compact=False)
+        cols = solve_row_batch([RowSMORegression(obj, X, Yc, None, proto.kernel, proto.C, proto.epsilon, proto.tol, False)
+                                for Yc in Y])
+        ests = [self._prototype() for _ in range(k)]
+        for c, est in enumerate(ests):
+            est.obj, est.optimizer = TargetQuadratic(obj, QL[c]), cols[c]
+            _svr_attributes(est, X, Y[c], np.concatenate((cols[c].alphas_p, cols[c].alphas_n)))
+            if isinstance(proto.kernel, LinearKernel):
+                est.coef_ = cols[c].w
+            est.intercept_ = cols[c].b
         return ests
 
     def _fit_batched(self, proto, X, Y):

@@ -20,7 +20,7 @@ from ...device import get_context
 from ...opti import KernelQuadratic
 from .kernels import LinearKernel
 
-__all__ = ['RowSMO', 'RowSMOClassifier', 'RowSMORegression']
+__all__ = ['RowSMO', 'RowSMOClassifier', 'RowSMORegression', 'RowSMOBatch']
 
 
 class RowSMO(ABC):
@@ -108,14 +108,26 @@ class RowSMO(ABC):
             self._scalars(lib, h)
             st = np.empty(3)
             _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_STATS, _lib.ptr(st)))
-            self.cache_stats = {'hits': int(st[0]), 'misses': int(st[1]), 'cache_rows': int(st[2])}
-            if isinstance(self.kernel, LinearKernel):
-                self.w = self._coefficients() @ self.X
+            self._finished(st)
             if self.verbose:
                 print()
         finally:
             lib.bq_rsmo_destroy(h)
         return self
+
+    def _finished(self, st):
+        """the read-back every run ends with: the cache's counts (hits, misses, rows) and the linear kernel's w"""
+        self.cache_stats = {'hits': int(st[0]), 'misses': int(st[1]), 'cache_rows': int(st[2])}
+        if isinstance(self.kernel, LinearKernel):
+            self.w = self._coefficients() @ self.X
+
+    def _dual(self):
+        """(signs, linear term, boxes) of this dual on its N variables, as `bq_rsmo_create` builds them"""
+        raise NotImplementedError
+
+    def _take(self, alpha, gradient, scalars):
+        """the solver's vectors and (rho, Gmax, Gmax2, ...) of this dual, from a solver that ran it as one of its columns"""
+        raise NotImplementedError
 
     def _objective(self):
         """1/2 a'Qa + p'a from the solver's own gradient: 1/2 a'(G + p), as libsvm reports it (no product with K)"""
@@ -145,6 +157,14 @@ class RowSMOClassifier(RowSMO):
     def _all_alphas(self):
         return self.alphas
 
+    def _dual(self):
+        return self.y, -np.ones(len(self.y)), self.box
+
+    def _take(self, alpha, gradient, scalars):
+        self.alphas, self.gradient = alpha, gradient
+        self.rho, self.gmax, self.gmax2 = scalars[:3]
+        self.b = -self.rho
+
     def _coefficients(self):
         return self.alphas * self.y
 
@@ -173,9 +193,69 @@ class RowSMORegression(RowSMO):
     def _all_alphas(self):
         return np.concatenate((self.alphas_p, self.alphas_n))
 
+    def _dual(self):
+        n = len(self.y)
+        return (np.concatenate((np.ones(n), -np.ones(n))), np.concatenate((self.epsilon - self.y, self.epsilon + self.y)),
+                np.concatenate((self.box, self.box)))
+
+    def _take(self, alpha, gradient, scalars):
+        self.alphas_p, self.alphas_n = alpha[:len(alpha) // 2].copy(), alpha[len(alpha) // 2:].copy()
+        self.gradient = gradient
+        self.rho, self.gmax, self.gmax2 = scalars[:3]
+        self.b = -self.rho
+
     def _coefficients(self):
         return self.alphas_p - self.alphas_n
 
     def _objective(self):
         p = np.concatenate((self.epsilon - self.y, self.epsilon + self.y))
         return 0.5 * float(self._all_alphas() @ (self.gradient + p))
+
+
+class RowSMOBatch:
+    """k `RowSMOClassifier` / `RowSMORegression` duals on ONE streamed problem, solved together (`bq_mrsmo_*`, csrc/bq_mrsmo.hip):
+    one cache of kernel rows for all columns, the rows a step misses made 16 at a time by the fp64-MFMA row-block kernel.  `columns`
+    are unrun solvers of one type on the same `quad`, X, kernel and tol; after `minimize()` each holds what its own `minimize()`
+    would have set (alphas, gradient, rho / b, iter, status, w), from rows with the row-block kernel's bits, and `cache_stats` of
+    the shared cache.  A column's trajectory does not depend on the other columns or on the cache."""
+    run_steps = RowSMO.run_steps
+
+    def __init__(self, columns, cache_rows=0, ctx=None):
+        first = columns[0]
+        if any(type(c) is not type(first) or c.quad is not first.quad for c in columns):
+            raise TypeError('the columns of a batch are solvers of one type on one quad')
+        if not (cache_rows == 0 or cache_rows >= 2 * len(columns)):
+            raise ValueError('cache_rows must be 0 (as many as fit) or >= 2 per column')
+        self.columns = list(columns)
+        self.cache_rows = int(cache_rows)
+        self.ctx = ctx
+
+    def minimize(self):
+        lib = _lib.load()
+        ctx = self.ctx or get_context()
+        if ctx.world != 1:
+            raise NotImplementedError('the row-based SMO runs on a single-rank context')
+        cols, k = self.columns, len(self.columns)
+        dev = cols[0].quad.device_problem(ctx)
+        signs, lin, boxes = (np.ascontiguousarray(np.stack(part), dtype=float) for part in zip(*(c._dual() for c in cols)))
+        N = signs.shape[1]
+        h = C.c_void_p()
+        _lib.check(lib.bq_mrsmo_create(dev.handle, k, N, _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes), float(cols[0].tol), 0,
+                                       self.cache_rows, C.byref(h)))
+        try:
+            steps, fin = (C.c_int64 * k)(), (C.c_int * k)()
+            while not all(fin):
+                _lib.check(lib.bq_mrsmo_run(h, self.run_steps, steps, fin))
+            st = np.empty(3)
+            _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+            for c, col in enumerate(cols):
+                alpha, grad, sc = np.empty(N), np.empty(N), np.empty(6)
+                for what, out in ((_lib.RSMO_ALPHAS, alpha), (_lib.RSMO_GRADIENT, grad), (_lib.RSMO_SCALARS, sc)):
+                    _lib.check(lib.bq_mrsmo_get(h, what, c, _lib.ptr(out)))
+                col._take(alpha, grad, sc)
+                col.iter = int(steps[c])
+                col.status = _lib.RSMO_STATUS[int(fin[c])]
+                col._finished(st)
+        finally:
+            lib.bq_mrsmo_destroy(h)
+        return self

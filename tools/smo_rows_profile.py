@@ -15,6 +15,11 @@ RBF with gamma='scale', d = 128, C = 1, tol 1e-3, seed 0) and write profiles/smo
         RowOneClassSVM (nu = 0.1) and RowNuSVC (nu = 0.2) on the same blobs: at a = 100 000 beside the resident OneClassSVM / NuSVC
         at the same tol, at b = 400 000 beside one streamed product
     python tools/smo_rows_profile.py nu-fit --model oneclass|nusvc --route rows|resident --n N --json FILE   one such fit
+    python tools/smo_rows_profile.py batch-rate --n N --steps K --route rows|columns --json FILE    K steps of the ten columns, no verdict
+    python tools/smo_rows_profile.py kernels --trace DIR --json FILE          kernel durations from a rocprofv3 --kernel-trace run's database
+    python tools/smo_rows_profile.py batch --n N --route rows|columns --json FILE
+        OneVsRestSVC(optimizer='smo', storage='stream') on the same blobs relabelled into 10 classes (blob x quintile of feature 0):
+        batch_smo='rows' (RowSMOBatch, bq_mrsmo_*) or one fit per class; profiles/smo_rows_batched/ keeps the records
 
 Every measurement runs in a process of its own under its own time limit, after a warm-up fit of n = 4000 on the same route; a wall
 time ends after the solver's last read-back, which synchronises the stream."""
@@ -74,6 +79,105 @@ def cmd_fit(args):
         rec.update(steps=int(opt.steps), outer_iterations=int(opt.iter), per_step_us=1e6 * wall / max(opt.steps, 1),
                    objective=float(est.obj.function(est.alphas_)), b_up_minus_b_low=float(opt.b_up - opt.b_low), labels_checksum=float(yb.sum()))
     est.obj.release()
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+def _data10(n):
+    """the blobs relabelled into 10 classes: blob x quintile of feature 0"""
+    X, y = _data(n)
+    blob = (y == np.unique(y)[-1]).astype(int)
+    quint = np.zeros(n, dtype=int)
+    for b in (0, 1):
+        rows = np.flatnonzero(blob == b)
+        quint[rows[np.argsort(X[rows, 0], kind='stable')]] = np.arange(len(rows)) * 5 // len(rows)
+    return X, 5 * blob + quint
+
+
+def cmd_batch_rate(args):
+    """K steps of the ten one-vs-rest columns on one streamed problem, no verdict: route rows = one bq_mrsmo solver (a step serves
+    all columns), route columns = one bq_rsmo solver per column, one after the other, each with its own cache, K steps each"""
+    import ctypes as C
+    from optiml_amd import _lib
+    from optiml_amd.device import get_context
+    from optiml_amd.ml.svm.kernels import gaussian
+    from optiml_amd.opti import KernelQuadratic
+    lib = _lib.load()
+    X, y = _data10(args.n)
+    Y = np.ascontiguousarray(np.stack([np.where(y == c, 1., -1.) for c in range(10)]))
+    quad = KernelQuadratic(X, -np.ones(args.n), 'svc', gaussian, y=Y[0], storage='stream', rank_one=False)
+    dev, ones, st = quad.device_problem(), np.ones((10, args.n)), np.empty(3)
+    rec = {'what': 'rate of ten columns (NOT a fit)', 'n': args.n, 'd': D, 'route': args.route, 'window_steps': args.steps,
+           'image_bytes_per_pass': _image_bytes(args.n), 'read_GBs': get_context().probe_bandwidth()[0]}
+    h = C.c_void_p()
+    if args.route == 'rows':
+        _lib.check(lib.bq_mrsmo_create(dev.handle, 10, args.n, _lib.ptr(Y), _lib.ptr(-ones), _lib.ptr(ones), TOL, 0, 0, C.byref(h)))
+        steps, fin = (C.c_int64 * 10)(), (C.c_int * 10)()
+        _lib.check(lib.bq_mrsmo_run(h, 8, steps, fin))   # warm
+        _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+        before = st.copy()
+        t0 = time.perf_counter()
+        _lib.check(lib.bq_mrsmo_run(h, args.steps, steps, fin))
+        wall = time.perf_counter() - t0
+        _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+        lib.bq_mrsmo_destroy(h)
+        rec.update(finished=list(fin), hits=int(st[0] - before[0]), misses=int(st[1] - before[1]), cache_rows=int(st[2]),
+                   rows_made_per_pass=float(st[1] - before[1]) / (2 * args.steps))
+    else:
+        wall, hits, misses = 0.0, 0, 0
+        for c in range(10):
+            _lib.check(lib.bq_rsmo_create(dev.handle, _lib.SVC, _lib.ptr(Y[c]), _lib.ptr(ones[c]), 0.0, TOL, 0, C.byref(h)))
+            steps, fin = C.c_int64(0), C.c_int(0)
+            _lib.check(lib.bq_rsmo_run(h, 8, C.byref(steps), C.byref(fin)))
+            t0 = time.perf_counter()
+            _lib.check(lib.bq_rsmo_run(h, args.steps, C.byref(steps), C.byref(fin)))
+            wall += time.perf_counter() - t0
+            _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_STATS, _lib.ptr(st)))
+            hits, misses = hits + int(st[0]), misses + int(st[1])
+            lib.bq_rsmo_destroy(h)
+        rec.update(hits=hits, misses=misses, cache_rows=int(st[2]), note='solver create / destroy are outside the window')
+    rec.update(window_s=wall, per_step_of_all_columns_us=1e6 * wall / args.steps)
+    quad.release()
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+def cmd_kernels(args):
+    """the durations of the named kernels in the database a `rocprofv3 --kernel-trace --stats -d DIR` run left"""
+    rec = _row_kernel_stats(args.trace, tuple(args.kernels.split(',')))
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+def cmd_batch(args):
+    """one OneVsRestSVC fit of 10 classes in this (fresh) process after a warm-up fit of n = 4000 on the same route"""
+    from optiml_amd.device import get_context
+    from optiml_amd.ml.svm import OneVsRestSVC
+    from optiml_amd.ml.svm.kernels import gaussian
+    from optiml_amd.ml.svm.losses import hinge
+
+    data = _data10
+
+    def model():
+        m = OneVsRestSVC(loss=hinge, kernel=gaussian, C=1., dual=True, optimizer='smo', tol=TOL, storage='stream')
+        m.batch_smo = 'rows' if args.route == 'rows' else None
+        return m
+    model().fit(*data(4000))
+    X, y = data(args.n)
+    t0 = time.perf_counter()
+    est = model().fit(X, y)
+    wall = time.perf_counter() - t0
+    opts = [e.optimizer for e in est.estimators_]
+    steps = [int(o.iter) for o in opts]
+    stats = [opts[0].cache_stats] if args.route == 'rows' else [o.cache_stats for o in opts]
+    hits, misses = sum(s['hits'] for s in stats), sum(s['misses'] for s in stats)
+    rec = {'what': 'one-vs-rest fit, 10 classes', 'n': args.n, 'd': D, 'route': args.route, 'tol': TOL, 'wall_s': wall,
+           'includes': 'problem build(s) + solve + read-back', 'steps_per_column': steps, 'status': [o.status for o in opts],
+           'hits': hits, 'misses': misses, 'hit_rate': hits / max(hits + misses, 1), 'cache_rows': stats[0]['cache_rows'],
+           'image_bytes_per_pass': _image_bytes(args.n), 'read_GBs': get_context().probe_bandwidth()[0]}
+    if args.route == 'rows':   # a batched step serves every live column: the longest column counts the steps
+        rec.update(batched_steps=max(steps), per_batched_step_us=1e6 * wall / max(max(steps), 1),
+                   rows_made_per_pass_upper=misses / max(2 * max(steps), 1))
     json.dump(rec, open(args.json, 'w'), indent=1)
     print(json.dumps(rec))
 
@@ -231,23 +335,25 @@ def _write_nu(out, R, sizes):
     open(os.path.join(out, 'README.md'), 'w').write('\n'.join(lines) + '\n')
 
 
-def _row_kernel_stats(trace_dir):
-    """per kernel of bq_rsmo.hip: all launches, and those that computed a row (a launch on a hit only reads the cache: the two
-    populations are split at the midpoint of the 10th and 99th percentile)"""
+def _row_kernel_stats(trace_dir, keys=('rsmo_select_kernel', 'rsmo_update_kernel')):
+    """per kernel: launches, total and median; for the kernels of bq_rsmo.hip, which make their row inside the launch, also the
+    launches that computed a row (a launch on a hit only reads the cache: the two populations are split at the midpoint of the
+    10th and 99th percentile).  The batched kernels make rows in a launch of their own: no such split exists for them."""
     dbs = glob.glob(os.path.join(trace_dir, '**', '*_results.db'), recursive=True)
     if not dbs:
         return None
     cur = sqlite3.connect(dbs[0]).cursor()
     out = {}
-    for key in ('rsmo_select_kernel', 'rsmo_update_kernel'):
+    for key in keys:
         d = np.array([r[0] for r in cur.execute('select duration from kernels where name like ?', ('%' + key + '%',))], dtype=float)
         if not len(d):
             continue
-        cut = 0.5 * (np.percentile(d, 10) + np.percentile(d, 99))
-        big = d[d >= cut]
-        out[key] = {'launches': int(len(d)), 'total_ms': float(d.sum() / 1e6), 'median_us': float(np.median(d) / 1e3),
-                    'row_launches': int(len(big)), 'row_mean_us': float(big.mean() / 1e3) if len(big) else None,
-                    'cache_only_mean_us': float(d[d < cut].mean() / 1e3) if (d < cut).any() else None}
+        out[key] = {'launches': int(len(d)), 'total_ms': float(d.sum() / 1e6), 'median_us': float(np.median(d) / 1e3)}
+        if key.startswith('rsmo_'):
+            cut = 0.5 * (np.percentile(d, 10) + np.percentile(d, 99))
+            big = d[d >= cut]
+            out[key].update(row_launches=int(len(big)), row_mean_us=float(big.mean() / 1e3) if len(big) else None,
+                            cache_only_mean_us=float(d[d < cut].mean() / 1e3) if (d < cut).any() else None)
     return out
 
 
@@ -345,6 +451,22 @@ def main():
     p.add_argument('--reps', type=int, default=3)
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_stages)
+    p = sub.add_parser('batch')
+    p.add_argument('--n', type=int, required=True)
+    p.add_argument('--route', default='rows', choices=['rows', 'columns'])
+    p.add_argument('--json', required=True)
+    p.set_defaults(fn=cmd_batch)
+    p = sub.add_parser('batch-rate')
+    p.add_argument('--n', type=int, required=True)
+    p.add_argument('--steps', type=int, default=2000)
+    p.add_argument('--route', default='rows', choices=['rows', 'columns'])
+    p.add_argument('--json', required=True)
+    p.set_defaults(fn=cmd_batch_rate)
+    p = sub.add_parser('kernels')
+    p.add_argument('--trace', required=True)
+    p.add_argument('--kernels', default='mr_rows_kernel,mr_select_kernel,mr_update_kernel,rsmo_select_kernel,rsmo_update_kernel')
+    p.add_argument('--json', required=True)
+    p.set_defaults(fn=cmd_kernels)
     p = sub.add_parser('nu-all')
     p.add_argument('--out', default='profiles/smo_nu_rows')
     p.add_argument('--sizes', default='100000,400000')
