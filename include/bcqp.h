@@ -68,6 +68,7 @@ extern "C" {
 /* (still 3: bq_rsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
 /* (still 3: bq_rsmo_create_general and BQ_RSMO_NU_SCALARS were added; nothing existing changed) */
 /* (still 3: bq_mrsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
+/* (still 3: bq_mrsmo_create_lists was added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -854,6 +855,18 @@ int bq_rsmo_destroy(bq_rsmo *s);
 typedef struct bq_mrsmo bq_mrsmo;
 int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
                     int64_t max_steps, int64_t cache_rows, bq_mrsmo **out);
+/* The row-list form: column c is the dual on the m_c = offsets[c + 1] - offsets[c] rows rows[offsets[c] ..) of the problem, strictly
+ * ascending; its variables are the positions 0 .. m_c - 1 of that list (N = m_c: the SVC form) and (signs, lin, boxes) are packed
+ * at the same offsets.  Every tie of WSS2 breaks on the position, so a column is the solver run on K[rows][:, rows] — the fit of
+ * the list's rows in their order.  Rows are requested, made and cached as whole rows under their global index (a row serves every
+ * column that lists it); select / update read them through the list (csrc/bq_mrsmo.hip, the ml_* kernels: a flat grid over a work
+ * table of (column, slice), wide slices, no workgroup outside a column's list).  The same handle: bq_mrsmo_run / _destroy as above;
+ * bq_mrsmo_get gives m_c alphas / gradient entries and i / j of the scalars as positions; bq_mrsmo_rows stays in global rows.
+ * A column with one sign only is legal and finishes at its first selection (0 steps), as in libsvm.
+ * BQ_ERR_BADARG: a list that is not strictly ascending or leaves 0 .. n - 1, an empty column, offsets that do not ascend from 0,
+ * and what bq_mrsmo_create refuses (k, cache_rows, tol, signs, boxes, lin, a resident problem). */
+int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offsets, const int32_t *rows, const double *signs, const double *lin,
+                          const double *boxes, double tol, int64_t max_steps, int64_t cache_rows, bq_mrsmo **out);
 int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int *finished);
 int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out);
 int bq_mrsmo_rows(bq_mrsmo *s, int m, const int64_t *idx, double *out);

@@ -65,6 +65,7 @@ void bq_set_error(const char *fmt, ...);
 //   chol_fwd_slice=N (columns per slice of the block-by-block forward sweep; default 16384)
 //   hessian_image_gain=G (the image is kept if its product is G times faster than the panel's; default 1, 0: always)
 //   rsmo_max_steps=N (the iteration cap of a row-based SMO created under the hook, in place of libsvm's max(10^7, 100 N))
+//   mrsmo_list_per=2|4|8 (positions per thread of the row-list select / update kernels of a solver created under the hook; default 8)
 // ---------------------------------------------------------------------------------------------
 bool bq_hook(const char *name, double *value);                       // true (and *value) when the hook is set
 static inline double bq_hook_value(const char *name, double dflt) {

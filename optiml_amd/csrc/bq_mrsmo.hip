@@ -21,8 +21,24 @@
 // time, zero where the group has fewer than 16 rows or the feature index is beyond d - 1 (the image is not read there either).
 // v_mfma_f64_16x16x4_f64 keeps rows and columns of D apart, and every element is the same ascending sequence of k-blocks: the bits
 // of K[r][t] depend on x_r, x_t and d only, and (r, t) and (t, r) are the same products in the same order.
+//
+// The row-list form (bq_mrsmo_create_lists).  Column c is the dual on the m_c rows of its strictly ascending list (a class pair of
+// one-vs-one: about 2 n / classes rows); its variables are the POSITIONS 0 .. m_c - 1, every tie breaks on the position, so the
+// column is the solver run on K[rows][:, rows].  The state of all columns is packed, each column at an offset that is a multiple of
+// ML_PAD, with the list beside it as int32; requests, the cache, the row-block kernel and QD stay in global rows, so a row made
+// for one pair serves every pair of its class.  ml_select_kernel / ml_update_kernel replace launches 2 and 4:
+//   - the grid is FLAT: workgroup w reads (column, first position) from a work table the host builds at create; the launch is
+//     sum_c ceil(m_c / slice) workgroups, none outside a list, where the (slices of n) x (columns) grid above would launch
+//     45 n / 256 workgroups for the 45 pairs of ten classes to touch 45 * 2 n / 10 positions;
+//   - a workgroup owns a slice of RSMO_T * PER consecutive positions, a thread PER consecutive ones: alpha / G / y / Cb come in as
+//     8 PER contiguous bytes each and the list as 4 PER, and the only scattered reads are the kernel values k = row[list[q]] (and
+//     QD[list[q]], n doubles that stay in L2).  Per-workgroup cost — the block pick, the partials, the fence and the ticket — is
+//     paid once per RSMO_T * PER positions instead of once per 256;
+//   - a column's ticket counts its own slices, the solver's ticket the live columns, as above.
+// Scans inside a thread go through the same total orders as the picks, so no result depends on PER or on the work table.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "bq_common.h"
@@ -39,6 +55,9 @@ constexpr int MR_COLS = 256;   // image columns per workgroup of the row-block k
 constexpr int MR_G = 16;       // rows per pass: the MFMA's M
 constexpr int MR_KC = 256;     // features of the 16 rows staged at a time (32 KiB of LDS)
 constexpr int MR_REQ = 1024;   // requests per resolution (the tables of the last workgroup): columns of a batch, rows of a bq_mrsmo_rows call
+constexpr int ML_PER = 8;      // list form: positions per thread, MR_SLICE = RSMO_T * ML_PER per workgroup; 8 measured best of 2, 4, 8
+                               // (profiles/ovo_smo_rows/; hook mrsmo_list_per switches a solver to 2 or 4)
+constexpr int ML_PAD = 8;      // list form: a column's packed offset is a multiple of this, so the widest thread's loads are aligned
 
 struct mr_col {   // a column's control block
     long long steps;
@@ -55,6 +74,13 @@ struct mr_glob {
     int live;     // columns still running: the arrivals of the solver's ticket
     int n_miss;   // the miss list's length
     unsigned int ticket;
+};
+struct ml_info {   // a column of the list form
+    int64_t off;   // where its state and its list start in the packed arrays (a multiple of ML_PAD)
+    int m;         // its positions
+    int nsl;       // its slices: the arrivals of its ticket
+    int part0;     // its first partial
+    int pad_;
 };
 struct mr_dev {
     int64_t n, N, mp, d, pitch;
@@ -73,6 +99,10 @@ struct mr_dev {
     int *res_req, *res_slot, *res_pin;   // MR_REQ each: the tables of a resolution, touched by the launch's last workgroup only
     double *part_v, *part_k, *part_w;   // k x nblk
     long long *part_i;
+    // the list form: alpha / G / y / Cb are packed at info[c].off instead of c N, N is 0
+    const int *rows;        // the lists, packed like the state; the pad positions of a column repeat its last row
+    const ml_info *info;    // k
+    const int2 *work;       // per workgroup of ml_select / ml_update: (column, first position of its slice)
 };
 // The tables of a resolution (requests, their slots, the pins) live in global memory, not in LDS: one workgroup of a launch uses
 // them, and 12 KiB of LDS in every workgroup of the (slices x columns) grid would be carried for nothing.  That workgroup writes
@@ -391,6 +421,234 @@ __global__ __launch_bounds__(RSMO_T) void mr_update_kernel(mr_dev P, int first) 
     mr_resolve_last(P, shl, false);
 }
 
+// ---- the row-list form of launches 2 and 4 ------------------------------------------------------------------------------------------
+// a thread's PER consecutive doubles / list entries: 16-byte loads at an address that is a multiple of 8 PER / 4 PER bytes
+template <int PER>
+__device__ __forceinline__ void ml_load(const double *p, double (&v)[PER]) {
+#pragma unroll
+    for (int u = 0; u < PER / 2; ++u) {
+        const bq_d2 t = reinterpret_cast<const bq_d2 *>(p)[u];
+        v[2 * u] = t.x;
+        v[2 * u + 1] = t.y;
+    }
+}
+template <int PER>
+__device__ __forceinline__ void ml_load(const int *p, int (&v)[PER]) {
+    if constexpr (PER == 2) {
+        const int2 t = *reinterpret_cast<const int2 *>(p);
+        v[0] = t.x;
+        v[1] = t.y;
+    } else {
+#pragma unroll
+        for (int u = 0; u < PER / 4; ++u) {
+            const int4 t = reinterpret_cast<const int4 *>(p)[u];
+            v[4 * u] = t.x;
+            v[4 * u + 1] = t.y;
+            v[4 * u + 2] = t.z;
+            v[4 * u + 3] = t.w;
+        }
+    }
+}
+
+template <int PER>
+__global__ __launch_bounds__(RSMO_T) void ml_select_kernel(mr_dev P) {
+    const int2 wk = P.work[blockIdx.x];
+    const int c = wk.x;
+    mr_col *cc = &P.col[c];
+    const int live = P.glob->live;
+    if (cc->finished) return;
+    __shared__ rsmo_pick_smem<double> sh;
+    __shared__ rsmo_pick_smem<long long> shl;
+    const ml_info in = P.info[c];
+    const double *alpha = P.alpha + in.off, *G = P.G + in.off, *y = P.y + in.off, *Cb = P.Cb + in.off;
+    const int *rows = P.rows + in.off;
+    const int i = cc->i, slot_i = cc->slot_i;
+    const double gmax = cc->gmax;
+    const double *row = P.cache + (int64_t)(slot_i < 0 ? 0 : slot_i) * P.pitch;
+    const double qd_i = P.QD[rows[i]];
+    const int q0 = wk.y + PER * (int)threadIdx.x;
+    double bv = BQ_RSMO_INF, bk = 0.0;
+    long long bi = -1;
+    if (q0 < in.m) {   // q0 + PER - 1 lies inside the column's padded length: the pad positions hold a valid row and are not scanned
+        double a_t[PER], g_t[PER], y_t[PER], C_t[PER], k_t[PER], qd_t[PER];
+        int r_t[PER];
+        ml_load<PER>(rows + q0, r_t);
+        ml_load<PER>(y + q0, y_t);
+        ml_load<PER>(alpha + q0, a_t);
+        ml_load<PER>(Cb + q0, C_t);
+        ml_load<PER>(G + q0, g_t);
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {   // the gathers go out together
+            k_t[e] = row[r_t[e]];
+            qd_t[e] = P.QD[r_t[e]];
+        }
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            if (q0 + e >= in.m || !bq_rsmo_in_low(y_t[e], a_t[e], C_t[e])) continue;
+            bool ok;
+            const double sc = bq_rsmo_score(gmax, y_t[e], g_t[e], qd_i, qd_t[e], k_t[e], &ok);
+            if (ok && bq_rsmo_min_before(sc, q0 + e, bv, bi)) {
+                bv = sc;
+                bi = q0 + e;
+                bk = k_t[e];
+            }
+        }
+    }
+    rsmo_block_pick<rsmo_min_order>(bv, bi, bk, sh);
+    const int64_t pb = in.part0, mine = pb + wk.y / (RSMO_T * PER);
+    if (threadIdx.x == 0) {
+        bq_part_put(&P.part_v[mine], bv);
+        bq_part_put(&P.part_i[mine], bi);
+        bq_part_put(&P.part_k[mine], bk);
+    }
+    if (!bq_last_block(&cc->ticket, (unsigned int)in.nsl)) return;
+    bv = BQ_RSMO_INF;
+    bi = -1;
+    bk = 0.0;
+    for (int b = threadIdx.x; b < in.nsl; b += RSMO_T) {
+        const double v2 = bq_part_get(&P.part_v[pb + b]);
+        const long long i2 = bq_part_get(&P.part_i[pb + b]);
+        const double k2 = bq_part_get(&P.part_k[pb + b]);
+        if (bq_rsmo_min_before(v2, i2, bv, bi)) {
+            bv = v2;
+            bi = i2;
+            bk = k2;
+        }
+    }
+    rsmo_block_pick<rsmo_min_order>(bv, bi, bk, sh);
+    if (threadIdx.x == 0) {
+        int req = -1;
+        if (bi < 0) {   // no partner: libsvm's Gmin_idx == -1
+            cc->finished = 1;
+        } else {
+            const int j = (int)bi, rj = rows[j];
+            double *al = P.alpha + in.off;
+            const double y_i = y[i], y_j = y[j];
+            const double old_i = al[i], old_j = al[j];
+            double a_i = old_i, a_j = old_j;
+            bq_rsmo_pair_update(y_i, y_j, G[i], G[j], qd_i, P.QD[rj], bk, Cb[i], Cb[j], &a_i, &a_j);
+            al[i] = a_i;
+            al[j] = a_j;
+            cc->d_i = a_i - old_i;
+            cc->d_j = a_j - old_j;
+            cc->y_i = y_i;
+            cc->y_j = y_j;
+            cc->j = j;
+            cc->last_i = i;
+            cc->last_j = j;
+            req = rj;
+        }
+        bq_part_put(&P.req_row[c], req);
+    }
+    if (!bq_last_block(&P.glob->ticket, (unsigned int)live)) return;
+    mr_resolve_last(P, shl, true);
+}
+
+template <int PER>
+__global__ __launch_bounds__(RSMO_T) void ml_update_kernel(mr_dev P, int first) {
+    const int2 wk = P.work[blockIdx.x];
+    const int c = wk.x;
+    mr_col *cc = &P.col[c];
+    const int live = P.glob->live;
+    if (cc->finished) return;
+    __shared__ rsmo_pick_smem<double> sh;
+    __shared__ rsmo_pick_smem<long long> shl;
+    __shared__ double shw[RSMO_T / 64];
+    const ml_info in = P.info[c];
+    const double *alpha = P.alpha + in.off, *y = P.y + in.off, *Cb = P.Cb + in.off;
+    double *G = P.G + in.off;
+    const int *rows = P.rows + in.off;
+    const int q0 = wk.y + PER * (int)threadIdx.x;
+    double uv = -BQ_RSMO_INF, rider = 0.0, low = -BQ_RSMO_INF;
+    long long ui = -1;
+    if (q0 < in.m) {
+        double a_t[PER], g_t[PER], y_t[PER], C_t[PER];
+        ml_load<PER>(y + q0, y_t);
+        ml_load<PER>(G + q0, g_t);
+        if (!first) {
+            int r_t[PER];
+            double ki[PER], kj[PER];
+            ml_load<PER>(rows + q0, r_t);
+            const double d_i = cc->d_i, d_j = cc->d_j, y_i = cc->y_i, y_j = cc->y_j;
+            const double *row_i = P.cache + (int64_t)(cc->slot_i < 0 ? 0 : cc->slot_i) * P.pitch;
+            const double *row_j = P.cache + (int64_t)(cc->slot_j < 0 ? 0 : cc->slot_j) * P.pitch;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) {
+                ki[e] = row_i[r_t[e]];
+                kj[e] = row_j[r_t[e]];
+            }
+#pragma unroll
+            for (int e = 0; e < PER; ++e) {   // (a pad position follows its column's last row; nobody reads it)
+                const double s_i = y_i * y_t[e], s_j = y_j * y_t[e];   // +-1: exact
+                const double q_i = s_i * ki[e], q_j = s_j * kj[e];
+                g_t[e] = bq_rsmo_grad(g_t[e], q_i, d_i, q_j, d_j);
+            }
+#pragma unroll
+            for (int u = 0; u < PER / 2; ++u) reinterpret_cast<bq_d2 *>(G + q0)[u] = (bq_d2){g_t[2 * u], g_t[2 * u + 1]};
+        }
+        ml_load<PER>(alpha + q0, a_t);
+        ml_load<PER>(Cb + q0, C_t);
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            if (q0 + e >= in.m) continue;
+            if (bq_rsmo_in_up(y_t[e], a_t[e], C_t[e])) {
+                const double val = bq_rsmo_up_value(y_t[e], g_t[e]);
+                if (bq_rsmo_max_before(val, q0 + e, uv, ui)) {
+                    uv = val;
+                    ui = q0 + e;
+                }
+            }
+            if (bq_rsmo_in_low(y_t[e], a_t[e], C_t[e])) low = fmax(low, bq_rsmo_low_value(y_t[e], g_t[e]));
+        }
+    }
+    rsmo_block_pick<rsmo_max_order>(uv, ui, rider, sh);
+    bq_wave_put<bq_op_max>(low, shw);
+    __syncthreads();
+    const int64_t pb = in.part0, mine = pb + wk.y / (RSMO_T * PER);
+    if (threadIdx.x == 0) {
+        double w = shw[0];
+        for (int q = 1; q < RSMO_T / 64; ++q) w = fmax(w, shw[q]);
+        bq_part_put(&P.part_v[mine], uv);
+        bq_part_put(&P.part_i[mine], ui);
+        bq_part_put(&P.part_w[mine], w);
+    }
+    if (!bq_last_block(&cc->ticket, (unsigned int)in.nsl)) return;
+    uv = -BQ_RSMO_INF;
+    ui = -1;
+    low = -BQ_RSMO_INF;
+    for (int b = threadIdx.x; b < in.nsl; b += RSMO_T) {
+        const double v2 = bq_part_get(&P.part_v[pb + b]);
+        const long long i2 = bq_part_get(&P.part_i[pb + b]);
+        if (bq_rsmo_max_before(v2, i2, uv, ui)) {
+            uv = v2;
+            ui = i2;
+        }
+        low = fmax(low, bq_part_get(&P.part_w[pb + b]));
+    }
+    rsmo_block_pick<rsmo_max_order>(uv, ui, rider, sh);
+    __syncthreads();
+    bq_wave_put<bq_op_max>(low, shw);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        low = shw[0];
+        for (int q = 1; q < RSMO_T / 64; ++q) low = fmax(low, shw[q]);
+        const long long steps = cc->steps + (first ? 0 : 1);
+        int fin = 0;
+        if (ui < 0 || bq_rsmo_stop(uv, low, P.tol))
+            fin = 1;
+        else if (steps >= P.glob->cap)
+            fin = 2;
+        cc->steps = steps;
+        cc->gmax = uv;
+        cc->gmax2 = low;
+        cc->i = (int)ui;
+        cc->finished = fin;
+        bq_part_put(&P.req_row[c], fin ? -1 : rows[ui]);
+    }
+    if (!bq_last_block(&P.glob->ticket, (unsigned int)live)) return;
+    mr_resolve_last(P, shl, false);
+}
+
 // ---- bq_mrsmo_rows: m requested rows through the cache, the rows the live columns wait for pinned ------------------------------------
 __global__ __launch_bounds__(RSMO_T) void mr_request_kernel(mr_dev P, int m) {
     __shared__ rsmo_pick_smem<long long> shl;
@@ -415,9 +673,13 @@ struct bq_mrsmo {
     mr_dev P = {};
     unsigned int nblk = 0;
     int64_t R = 0;
-    std::vector<double> y, Cb;   // host copies for calculate_rho
+    std::vector<double> y, Cb;   // host copies for calculate_rho (the list form: packed like the device's)
     std::vector<mr_col> host;
     bool done = false;
+    // the list form: the columns' packed offsets and lengths, the positions per thread and the flat grid
+    std::vector<ml_info> info;
+    int per = 0;   // 0: the full-column form
+    unsigned int grid = 0;
 };
 
 extern "C" int bq_mrsmo_destroy(bq_mrsmo *s) {
@@ -445,34 +707,32 @@ static void mr_launch_rows(KD, const bq_mrsmo *s, hipStream_t st) {
     mr_rows_kernel<KD::kind, KD::deg><<<blocks, RSMO_T, 0, st>>>(s->P);
 }
 
-extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
-                               int64_t max_steps, int64_t cache_rows, bq_mrsmo **out) {
-    BQ_ARG(p && signs && lin && boxes && out, "NULL argument");
+// what both forms of create refuse before they look at a column
+static int mr_check(const bq_problem *p, int k, double tol, int64_t max_steps, int64_t cache_rows) {
     BQ_ARG(p->kernel >= 0 && p->streamed && p->stream_img != nullptr && p->ctx->world == 1,
            "the row-based SMO needs a kernel-built streamed problem (BQ_STREAM) on a single-rank context");
     BQ_ARG(k >= 1 && k <= MR_REQ, "k must lie in 1 .. 1024");
     BQ_ARG(tol > 0.0, "tol must be > 0");
     BQ_ARG(max_steps >= 0, "max_steps must be >= 0 (0: libsvm's cap)");
     BQ_ARG(cache_rows == 0 || cache_rows >= 2 * (int64_t)k, "cache_rows must be 0 (automatic) or >= 2 k: a step holds two rows per column");
-    const int64_t n = p->n;
-    BQ_ARG(N == n || N == 2 * n, "N must be n or 2n");
-    BQ_ARG(N < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
-    for (int64_t v = 0; v < (int64_t)k * N; ++v) {
-        BQ_ARG(std::isfinite(boxes[v]) && boxes[v] > 0.0, "every box must be finite and > 0");
-        BQ_ARG(signs[v] == 1.0 || signs[v] == -1.0, "signs must be +1 / -1");
-        BQ_ARG(N == n || signs[v] == (v % N < n ? 1.0 : -1.0), "the signs of 2n variables must be [+1 ..; -1 ..]");
-        BQ_ARG(std::isfinite(lin[v]), "the linear term must be finite");
-    }
-    bq_ctx *c = p->ctx;
-    BQ_HIP(hipSetDevice(c->device));
+    return BQ_OK;
+}
+static int mr_check_entry(double sign, double lin, double box) {
+    BQ_ARG(std::isfinite(box) && box > 0.0, "every box must be finite and > 0");
+    BQ_ARG(sign == 1.0 || sign == -1.0, "signs must be +1 / -1");
+    BQ_ARG(std::isfinite(lin), "the linear term must be finite");
+    return BQ_OK;
+}
+
+// a solver on p with the problem's side of mr_dev filled in
+static bq_mrsmo *mr_new(bq_problem *p, int k, double tol) {
     bq_mrsmo *s = new bq_mrsmo();
     s->p = p;
     p->refs += 1;
     mr_dev &P = s->P;
     int64_t dp = 0;
     bq_stream_image_view(p->stream_img, &P.At, &P.a2, &P.mp, &dp);
-    P.n = n;
-    P.N = N;
+    P.n = p->n;
     P.k = k;
     P.d = p->d;
     P.X = p->X;
@@ -481,11 +741,22 @@ extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *si
     P.degree = p->degree;
     P.tol = tol;
     P.pitch = P.mp;
-    s->nblk = (unsigned int)((n + RSMO_T - 1) / RSMO_T);
-    const size_t kN = (size_t)k * (size_t)N, parts = (size_t)k * s->nblk;
-    s->y.assign(signs, signs + kN);
-    s->Cb.assign(boxes, boxes + kN);
     s->host.resize((size_t)k);
+    return s;
+}
+
+// What both forms of create share once s->y / s->Cb hold the columns' signs and boxes in the device's layout (`total` entries) and
+// `G0` the linear terms in the same layout: the vectors, `parts` partials, the cache, the start state, QD and the first selection
+// (`first()` launches it, after QD).  `dual` is the longest column's dimension (libsvm's cap).  On failure s is destroyed.
+template <typename FIRST>
+static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, int64_t dual, int64_t max_steps, int64_t cache_rows,
+                    FIRST first, bq_mrsmo **out) {
+    bq_problem *p = s->p;
+    bq_ctx *c = p->ctx;
+    mr_dev &P = s->P;
+    const int k = P.k;
+    const int64_t n = P.n;
+    const size_t kN = total;
     auto fail = [&](hipError_t e, const char *what) {
         bq_set_error("%s failed: %s", what, hipGetErrorString(e));
         hipStreamSynchronize(c->stream);
@@ -530,7 +801,7 @@ extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *si
     if (e == hipSuccess) e = hipMemsetAsync(cache.row_of, 0xFF, sizeof(int) * (size_t)R, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(P.req_row, 0xFF, sizeof(int) * (size_t)k, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(P.alpha, 0, sizeof(double) * kN, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(P.G, lin, sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);   // zero start: G0 = lin
+    if (e == hipSuccess) e = hipMemcpyAsync(P.G, G0, sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);   // zero start: G0 = lin
     if (e == hipSuccess) e = hipMemcpyAsync(P.y, s->y.data(), sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(P.Cb, s->Cb.data(), sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
     mr_col c0 = {};
@@ -539,7 +810,7 @@ extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *si
     std::fill(s->host.begin(), s->host.end(), c0);
     mr_glob g0 = {};
     g0.cache = cache;
-    g0.cap = max_steps > 0 ? (long long)max_steps : std::max<long long>(10000000LL, 100LL * (long long)N);   // libsvm's max_iter
+    g0.cap = max_steps > 0 ? (long long)max_steps : std::max<long long>(10000000LL, 100LL * (long long)dual);   // libsvm's max_iter
     g0.cap = (long long)bq_hook_value("rsmo_max_steps", (double)g0.cap);
     g0.live = k;
     if (e == hipSuccess) e = hipMemcpyAsync(P.col, s->host.data(), sizeof(mr_col) * (size_t)k, hipMemcpyHostToDevice, c->stream);
@@ -548,7 +819,7 @@ extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *si
     int rc = rsmo_dispatch(p, [&](auto kd) {
         const unsigned int waves = (unsigned int)(P.mp / 16), per = RSMO_T / 64;
         mr_diag_kernel<decltype(kd)::kind, decltype(kd)::deg><<<(waves + per - 1) / per, RSMO_T, 0, c->stream>>>(P);
-        mr_update_kernel<<<dim3(s->nblk, (unsigned int)k), RSMO_T, 0, c->stream>>>(P, 1);
+        first();
     });
     if (rc == BQ_OK && (e = hipGetLastError()) != hipSuccess) return fail(e, "the batched row-based SMO's first selection");
     if (rc == BQ_OK) rc = mr_read_cols(s);   // (g0, c0 and the caller's vectors are read by then)
@@ -559,6 +830,126 @@ extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *si
     }
     *out = s;
     return BQ_OK;
+}
+
+extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
+                               int64_t max_steps, int64_t cache_rows, bq_mrsmo **out) {
+    BQ_ARG(p && signs && lin && boxes && out, "NULL argument");
+    BQ_TRY(mr_check(p, k, tol, max_steps, cache_rows));
+    const int64_t n = p->n;
+    BQ_ARG(N == n || N == 2 * n, "N must be n or 2n");
+    BQ_ARG(N < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
+    for (int64_t v = 0; v < (int64_t)k * N; ++v) {
+        BQ_TRY(mr_check_entry(signs[v], lin[v], boxes[v]));
+        BQ_ARG(N == n || signs[v] == (v % N < n ? 1.0 : -1.0), "the signs of 2n variables must be [+1 ..; -1 ..]");
+    }
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    bq_mrsmo *s = mr_new(p, k, tol);
+    s->P.N = N;
+    s->nblk = (unsigned int)((n + RSMO_T - 1) / RSMO_T);
+    const size_t kN = (size_t)k * (size_t)N;
+    s->y.assign(signs, signs + kN);
+    s->Cb.assign(boxes, boxes + kN);
+    return mr_start(s, lin, kN, (size_t)k * s->nblk, N, max_steps, cache_rows, [&] {
+        mr_update_kernel<<<dim3(s->nblk, (unsigned int)k), RSMO_T, 0, p->ctx->stream>>>(s->P, 1);
+    }, out);
+}
+
+// the list form's launches 2 and 4 at the solver's positions per thread
+static void ml_launch(const bq_mrsmo *s, bool select, int first, hipStream_t st) {
+    auto go = [&](auto per) {
+        constexpr int PER = decltype(per)::value;
+        if (select)
+            ml_select_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P);
+        else
+            ml_update_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P, first);
+    };
+    if (s->per == 2)
+        go(std::integral_constant<int, 2>());
+    else if (s->per == 4)
+        go(std::integral_constant<int, 4>());
+    else
+        go(std::integral_constant<int, ML_PER>());
+}
+
+extern "C" int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offsets, const int32_t *rows, const double *signs,
+                                     const double *lin, const double *boxes, double tol, int64_t max_steps, int64_t cache_rows,
+                                     bq_mrsmo **out) {
+    BQ_ARG(p && offsets && rows && signs && lin && boxes && out, "NULL argument");
+    BQ_TRY(mr_check(p, k, tol, max_steps, cache_rows));
+    const int64_t n = p->n;
+    BQ_ARG(offsets[0] == 0, "offsets must ascend from 0");
+    for (int c = 0; c < k; ++c) {
+        BQ_ARG(offsets[c + 1] > offsets[c], "every column needs at least one row: offsets must ascend strictly");
+        BQ_ARG(offsets[c + 1] - offsets[c] <= n, "a list cannot be longer than the problem has rows");
+        for (int64_t v = offsets[c]; v < offsets[c + 1]; ++v) {
+            BQ_ARG(rows[v] >= 0 && rows[v] < n, "a listed row lies outside the problem");
+            BQ_ARG(v == offsets[c] || rows[v] > rows[v - 1], "a column's rows must ascend strictly");
+            BQ_TRY(mr_check_entry(signs[v], lin[v], boxes[v]));
+        }
+    }
+    BQ_ARG(n < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
+    int per = (int)bq_hook_value("mrsmo_list_per", (double)ML_PER);   // the slice-width comparison of profiles/ovo_smo_rows/
+    if (per != 2 && per != 4) per = ML_PER;
+    const int slice = RSMO_T * per;
+    // the packed layout (each column at a multiple of ML_PAD; pad positions: the list's last row, +1, box 0 — never scanned) and
+    // the work table: one (column, first position) per slice, column by column
+    std::vector<ml_info> info((size_t)k);
+    std::vector<int2> work;
+    int64_t total = 0, parts = 0, longest = 0;
+    for (int c = 0; c < k; ++c) {
+        const int64_t m = offsets[c + 1] - offsets[c], nsl = (m + slice - 1) / slice;
+        info[(size_t)c] = ml_info{total, (int)m, (int)nsl, (int)parts, 0};
+        for (int64_t b = 0; b < nsl; ++b) work.push_back(make_int2(c, (int)(b * slice)));
+        total += (m + ML_PAD - 1) / ML_PAD * ML_PAD;
+        parts += nsl;
+        longest = std::max(longest, m);
+    }
+    BQ_ARG(parts < ((int64_t)1 << 31) && total < ((int64_t)1 << 40), "the lists are too long for one solver");
+    std::vector<double> G0((size_t)total, 0.0);
+    std::vector<int> list((size_t)total, 0);
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    bq_mrsmo *s = mr_new(p, k, tol);
+    s->P.N = 0;
+    s->per = per;
+    s->grid = (unsigned int)parts;
+    s->y.assign((size_t)total, 1.0);
+    s->Cb.assign((size_t)total, 0.0);
+    for (int c = 0; c < k; ++c) {
+        const ml_info &in = info[(size_t)c];
+        const int64_t src = offsets[c], mpad = (in.m + ML_PAD - 1) / ML_PAD * ML_PAD;
+        for (int64_t q = 0; q < mpad; ++q) {
+            const bool live = q < in.m;
+            list[(size_t)(in.off + q)] = rows[src + (live ? q : in.m - 1)];
+            if (!live) continue;
+            s->y[(size_t)(in.off + q)] = signs[src + q];
+            s->Cb[(size_t)(in.off + q)] = boxes[src + q];
+            G0[(size_t)(in.off + q)] = lin[src + q];
+        }
+    }
+    s->info = info;
+    // the tables go up before mr_start's own uploads; mr_start synchronises the stream before it returns, on every path
+    bq_ctx *c = p->ctx;
+    int *d_rows = nullptr;
+    ml_info *d_info = nullptr;
+    int2 *d_work = nullptr;
+    hipError_t e = s->mem.dev(&d_rows, (size_t)total);
+    if (e == hipSuccess) e = s->mem.dev(&d_info, (size_t)k);
+    if (e == hipSuccess) e = s->mem.dev(&d_work, work.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, list.data(), sizeof(int) * (size_t)total, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_info, info.data(), sizeof(ml_info) * (size_t)k, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_work, work.data(), sizeof(int2) * work.size(), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        bq_set_error("the row lists failed: %s", hipGetErrorString(e));
+        hipStreamSynchronize(c->stream);
+        bq_mrsmo_destroy(s);
+        return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    s->P.rows = d_rows;
+    s->P.info = d_info;
+    s->P.work = d_work;
+    return mr_start(s, G0.data(), (size_t)total, (size_t)parts, longest, max_steps, cache_rows,
+                    [&] { ml_launch(s, false, 1, c->stream); }, out);
 }
 
 extern "C" int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int *finished) {
@@ -572,9 +963,15 @@ extern "C" int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int 
         BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
             for (int64_t q = 0; q < max_steps; ++q) {
                 mr_launch_rows(kd, s, c->stream);
-                mr_select_kernel<<<grid, RSMO_T, 0, c->stream>>>(P);
+                if (s->per)
+                    ml_launch(s, true, 0, c->stream);
+                else
+                    mr_select_kernel<<<grid, RSMO_T, 0, c->stream>>>(P);
                 mr_launch_rows(kd, s, c->stream);
-                mr_update_kernel<<<grid, RSMO_T, 0, c->stream>>>(P, 0);
+                if (s->per)
+                    ml_launch(s, false, 0, c->stream);
+                else
+                    mr_update_kernel<<<grid, RSMO_T, 0, c->stream>>>(P, 0);
             }
         }));
         BQ_HIP(hipGetLastError());
@@ -594,7 +991,10 @@ extern "C" int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out) {
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     const mr_dev &P = s->P;
-    const size_t N = (size_t)P.N, off = what == BQ_RSMO_STATS ? 0 : (size_t)column * N;
+    // a column's entries and where they start: c N in the full-column form, the packed offset of its list in the list form
+    const bool stats = what == BQ_RSMO_STATS;
+    const size_t N = stats || !s->per ? (size_t)P.N : (size_t)s->info[(size_t)column].m;
+    const size_t off = stats ? 0 : s->per ? (size_t)s->info[(size_t)column].off : (size_t)column * N;
     if (what == BQ_RSMO_ALPHAS || what == BQ_RSMO_GRADIENT) {
         BQ_HIP(hipMemcpyAsync(out, (what == BQ_RSMO_ALPHAS ? P.alpha : P.G) + off, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
         BQ_HIP(hipStreamSynchronize(c->stream));

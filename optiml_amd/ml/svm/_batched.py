@@ -326,10 +326,10 @@ def takes_row_batch(est, batch_smo, loss):
     return True
 
 
-def solve_row_batch(cols):
-    """Run the unrun row-based solvers `cols` (one type, one quad) as the columns of one `RowSMOBatch`; a column that ends at
-    libsvm's iteration cap warns as its own fit does."""
-    RowSMOBatch(cols).minimize()
+def solve_row_batch(cols, rows=None):
+    """Run the unrun row-based solvers `cols` (one type, one quad) as the columns of one `RowSMOBatch` (rows: its row lists, one
+    per column, or None); a column that ends at libsvm's iteration cap warns as its own fit does."""
+    RowSMOBatch(cols, rows=rows).minimize()
     if any(col.status == 'stopped' for col in cols):
         warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
     return cols

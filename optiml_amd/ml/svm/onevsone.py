@@ -37,24 +37,30 @@ import numpy as np
 from ... import _lib
 from ...device import get_context
 from ...opti import KernelQuadratic
-from ._batched import (MEMORY_SHARE, DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _pair_array, column_bytes,
+from ._batched import (MEMORY_SHARE, DecisionBatch, _DeviceMultiSolver, _MultiClassSVC, _pair_array, _svc_attributes, column_bytes,
                        device_free_bytes, fitted_smo_svc, fitted_svc, gram_matmat_pairs, intercept, solve_batched,
-                       solve_batched_smo, solver_kind, takes_batched_smo, uses_batched_decision)
+                       solve_batched_smo, solve_row_batch, solver_kind, takes_batched_smo, takes_row_batch,
+                       uses_batched_decision)
 from ._base import has_class_weight, row_boxes
 from .kernels import LinearKernel
+from .losses import Hinge
 from .multiclass import uses_batched_path, uses_batched_smo_path
+from .smo_rows import RowSMOClassifier
 
 __all__ = ['OneVsOneSVC', 'uses_batched_ovo', 'uses_batched_ovo_smo', 'sort_plan', 'ovo_pairs', 'pair_problem', 'ovo_decision']
 
 TILE = 256
 
 
+def _rows_independent(kernel):
+    """the kernel's parameters do not depend on the rows it is built on: a linear kernel, a numeric gamma or gamma='auto'"""
+    return isinstance(kernel, LinearKernel) or getattr(kernel, 'gamma', None) != 'scale'
+
+
 def uses_batched_ovo(svc, world):
     """True when `OneVsOneSVC` solves the pairs of `svc`'s configuration together on one panel: `uses_batched_path` holds and the
     kernel's parameters do not depend on the rows (numeric gamma, gamma='auto' or a linear kernel)."""
-    if not uses_batched_path(svc, world):
-        return False
-    return isinstance(svc.kernel, LinearKernel) or getattr(svc.kernel, 'gamma', None) != 'scale'
+    return uses_batched_path(svc, world) and _rows_independent(svc.kernel)
 
 
 def uses_batched_ovo_smo(svc, world):
@@ -62,9 +68,7 @@ def uses_batched_ovo_smo(svc, world):
     unsorted panel: `uses_batched_smo_path` holds and the kernel's parameters do not depend on the rows (numeric gamma,
     gamma='auto' or a linear kernel).  Whether a fit then does is `takes_batched_smo`'s answer (`OneVsOneSVC.batch_smo`).  A
     `class_weight` stays on this path: every pair's column gets the boxes of the pair's own fit."""
-    if not uses_batched_smo_path(svc, world):
-        return False
-    return isinstance(svc.kernel, LinearKernel) or getattr(svc.kernel, 'gamma', None) != 'scale'
+    return uses_batched_smo_path(svc, world) and _rows_independent(svc.kernel)
 
 
 def ovo_pairs(ncls):
@@ -168,6 +172,13 @@ class OneVsOneSVC(_MultiClassSVC):
     `smo_`: the pairs were solved together as row-list columns of the batched SMO solver (`uses_batched_ovo_smo`); `batched_` is
     True when either batched path ran.  `batch_smo` (None, True, False) forces that choice where the configuration allows it; None
     leaves it to the number of pairs (`takes_batched_smo`: two and three classes stay one `SVC.fit` per pair).
+
+    `batch_smo='rows'` (opt-in; optimizer='smo', storage='stream', anything else is a ValueError): the pairs are solved together
+    as row-list columns of the batched panel-free SMO (`RowSMOBatch(rows=...)`, `bq_mrsmo_create_lists`) on ONE streamed problem
+    of all rows — one cache of kernel rows, a row made once for the k - 1 pairs of its class, missing rows made 16 at a time —
+    instead of one streamed `SVC.fit` per pair; `rows_` says so.  Every pair is the fit of its rows in their order on the shared
+    problem's kernel values, and every estimator has the attributes its own fit sets (`optimizer` a `RowSMOClassifier`).  With
+    gamma='scale' the per-pair calls stay.  Prediction follows `batched_decision_` as on the other batched routes.
     """
     batch_smo = None
 
@@ -189,8 +200,11 @@ class OneVsOneSVC(_MultiClassSVC):
                     raise ValueError('class_weight names the label %r, which is not among the classes %r' % (label, list(self.classes_)))
         ncls = len(self.classes_)
         P = ncls * (ncls - 1) // 2
-        self.smo_ = uses_batched_ovo_smo(proto, get_context().world) and takes_batched_smo(P, self.batch_smo)
-        self.batched_ = self.smo_ or uses_batched_ovo(proto, get_context().world)
+        # 'rows' outside the streamed SMO branch is a ValueError; with gamma='scale' one image cannot serve every pair
+        self.rows_ = takes_row_batch(proto, self.batch_smo, Hinge) and _rows_independent(proto.kernel)
+        self.smo_ = (not self.rows_ and uses_batched_ovo_smo(proto, get_context().world) and
+                     takes_batched_smo(P, self.batch_smo))
+        self.batched_ = self.rows_ or self.smo_ or uses_batched_ovo(proto, get_context().world)
         self.batched_decision_ = uses_batched_decision(proto.kernel, P, get_context().world, self.batched_)
         self.decision_batch_ = None
         if not self.batched_:
@@ -199,8 +213,38 @@ class OneVsOneSVC(_MultiClassSVC):
                 rows, yp = pair_problem(codes, i, j)
                 self.estimators_.append(self._pair_prototype(i, j).fit(X[rows], (yp > 0).astype(int)))
             return self
-        self.estimators_ = (self._fit_smo if self.smo_ else self._fit_batched)(proto, X, codes)
+        fit = self._fit_rows if self.rows_ else self._fit_smo if self.smo_ else self._fit_batched
+        self.estimators_ = fit(proto, X, codes)
         return self
+
+    def _fit_rows(self, proto, X, codes):
+        """SVC.fit's SMO branch on a streamed problem for every pair at once: ONE streamed problem of all rows, pair (i, j) a
+        row-list column of the batched panel-free SMO (`RowSMOBatch(rows=...)`, `bq_mrsmo_create_lists`) — a `RowSMOClassifier` on
+        the pair's rows in their order, +1 on class j, with the boxes of the pair's own fit.  A kernel row is made once and serves
+        the k - 1 pairs of its class."""
+        n = len(codes)
+        pairs = ovo_pairs(len(self.classes_))
+        problems = [pair_problem(codes, i, j) for i, j in pairs]
+        obj = KernelQuadratic(X, -np.ones(n), 'svc', proto.kernel, y=np.where(codes == pairs[0][1], 1., -1.),
+                              storage=proto.storage, rank_one=False, compact=False)
+        ests = [self._pair_prototype(i, j) for i, j in pairs]
+        cols = [RowSMOClassifier(obj, X[rows], yp, None, proto.kernel, proto.C, proto.tol, False,
+                                 row_boxes(proto.C, (yp > 0).astype(int), np.arange(2), est.class_weight))
+                for est, (rows, yp) in zip(ests, problems)]
+        solve_row_batch(cols, rows=[rows for rows, _ in problems])
+        coefs = []
+        for est, col, (rows, yp) in zip(ests, cols, problems):
+            est.obj, est.optimizer = obj, col
+            sv = _svc_attributes(est, X[rows], yp, col.alphas)
+            if isinstance(proto.kernel, LinearKernel):
+                est.coef_ = col.w
+            est.intercept_ = col.b
+            w = np.zeros(n)
+            w[rows[sv]] = est.dual_coef_
+            coefs.append(w)
+        if self.batched_decision_:
+            self.decision_batch_ = DecisionBatch(proto.kernel, X, coefs, [est.intercept_ for est in ests])
+        return ests
 
     def _pair_prototype(self, i, j):
         """The SVC of pair (i, j), fitted on the labels 0 (class i) / 1 (class j): a `class_weight` dict, whose keys are the data's

@@ -217,18 +217,48 @@ class RowSMOBatch:
     one cache of kernel rows for all columns, the rows a step misses made 16 at a time by the fp64-MFMA row-block kernel.  `columns`
     are unrun solvers of one type on the same `quad`, X, kernel and tol; after `minimize()` each holds what its own `minimize()`
     would have set (alphas, gradient, rho / b, iter, status, w), from rows with the row-block kernel's bits, and `cache_stats` of
-    the shared cache.  A column's trajectory does not depend on the other columns or on the cache."""
+    the shared cache.  A column's trajectory does not depend on the other columns or on the cache.
+
+    `rows` (one strictly ascending list of rows of the quad per column) makes every column a row-list column
+    (`bq_mrsmo_create_lists`): column c is a `RowSMOClassifier` built on `X[rows[c]], y[rows[c]]` — a class pair of one-vs-one — and
+    is solved on the kernel values `K[rows[c]][:, rows[c]]` of the shared quad, its variables the positions of its list: the fit of
+    those rows in their order.  Kernel rows are made and cached whole, so a row serves every column that lists it; the select and
+    update kernels run over the lists only.  Each column holds m_c-long alphas and gradient afterwards."""
     run_steps = RowSMO.run_steps
 
-    def __init__(self, columns, cache_rows=0, ctx=None):
+    def __init__(self, columns, cache_rows=0, ctx=None, rows=None):
         first = columns[0]
         if any(type(c) is not type(first) or c.quad is not first.quad for c in columns):
             raise TypeError('the columns of a batch are solvers of one type on one quad')
         if not (cache_rows == 0 or cache_rows >= 2 * len(columns)):
             raise ValueError('cache_rows must be 0 (as many as fit) or >= 2 per column')
+        if rows is not None:
+            if not isinstance(first, RowSMOClassifier):
+                raise TypeError('row-list columns are RowSMOClassifier duals (N = m); the 2n form covers all rows')
+            if len(rows) != len(columns) or any(len(r) != len(c.y) for r, c in zip(rows, columns)):
+                raise ValueError('rows must hold one list per column, as long as the column')
+            rows = [np.ascontiguousarray(r, dtype=np.int32) for r in rows]
         self.columns = list(columns)
+        self.rows = rows
         self.cache_rows = int(cache_rows)
         self.ctx = ctx
+
+    def _create(self, lib, dev, h):
+        """create the device solver of the columns into `h`; returns every column's number of variables"""
+        cols, k = self.columns, len(self.columns)
+        duals = [c._dual() for c in cols]
+        if self.rows is None:
+            signs, lin, boxes = (np.ascontiguousarray(np.stack(part), dtype=float) for part in zip(*duals))
+            _lib.check(lib.bq_mrsmo_create(dev.handle, k, signs.shape[1], _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes),
+                                           float(cols[0].tol), 0, self.cache_rows, C.byref(h)))
+            return [signs.shape[1]] * k
+        signs, lin, boxes = (np.ascontiguousarray(np.concatenate(part), dtype=float) for part in zip(*duals))
+        offsets = np.concatenate(([0], np.cumsum([len(r) for r in self.rows]))).astype(np.int64)
+        rows = np.ascontiguousarray(np.concatenate(self.rows), dtype=np.int32)
+        _lib.check(lib.bq_mrsmo_create_lists(dev.handle, k, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _lib.iptr(rows),
+                                             _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes), float(cols[0].tol), 0, self.cache_rows,
+                                             C.byref(h)))
+        return [len(r) for r in self.rows]
 
     def minimize(self):
         lib = _lib.load()
@@ -237,11 +267,8 @@ class RowSMOBatch:
             raise NotImplementedError('the row-based SMO runs on a single-rank context')
         cols, k = self.columns, len(self.columns)
         dev = cols[0].quad.device_problem(ctx)
-        signs, lin, boxes = (np.ascontiguousarray(np.stack(part), dtype=float) for part in zip(*(c._dual() for c in cols)))
-        N = signs.shape[1]
         h = C.c_void_p()
-        _lib.check(lib.bq_mrsmo_create(dev.handle, k, N, _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes), float(cols[0].tol), 0,
-                                       self.cache_rows, C.byref(h)))
+        sizes = self._create(lib, dev, h)
         try:
             steps, fin = (C.c_int64 * k)(), (C.c_int * k)()
             while not all(fin):
@@ -249,7 +276,7 @@ class RowSMOBatch:
             st = np.empty(3)
             _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
             for c, col in enumerate(cols):
-                alpha, grad, sc = np.empty(N), np.empty(N), np.empty(6)
+                alpha, grad, sc = np.empty(sizes[c]), np.empty(sizes[c]), np.empty(6)
                 for what, out in ((_lib.RSMO_ALPHAS, alpha), (_lib.RSMO_GRADIENT, grad), (_lib.RSMO_SCALARS, sc)):
                     _lib.check(lib.bq_mrsmo_get(h, what, c, _lib.ptr(out)))
                 col._take(alpha, grad, sc)

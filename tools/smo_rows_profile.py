@@ -20,6 +20,11 @@ RBF with gamma='scale', d = 128, C = 1, tol 1e-3, seed 0) and write profiles/smo
     python tools/smo_rows_profile.py batch --n N --route rows|columns --json FILE
         OneVsRestSVC(optimizer='smo', storage='stream') on the same blobs relabelled into 10 classes (blob x quintile of feature 0):
         batch_smo='rows' (RowSMOBatch, bq_mrsmo_*) or one fit per class; profiles/smo_rows_batched/ keeps the records
+    python tools/smo_rows_profile.py ovo --n N --route rows|pairs --json FILE
+        OneVsOneSVC(optimizer='smo', storage='stream') on the same 10 classes with a numeric gamma: batch_smo='rows' (the row-list
+        columns of bq_mrsmo_create_lists) or one streamed fit per pair; profiles/ovo_smo_rows/ keeps the records
+    python tools/smo_rows_profile.py ovo-rate --n N --steps K --route rows|pairs --json FILE    K steps of the 45 pair columns
+        (the slice width of the list kernels is the test hook mrsmo_list_per = 2 | 4 | 8 in BQ_TEST_HOOKS)
 
 Every measurement runs in a process of its own under its own time limit, after a warm-up fit of n = 4000 on the same route; a wall
 time ends after the solver's last read-back, which synchronises the stream."""
@@ -178,6 +183,94 @@ def cmd_batch(args):
     if args.route == 'rows':   # a batched step serves every live column: the longest column counts the steps
         rec.update(batched_steps=max(steps), per_batched_step_us=1e6 * wall / max(max(steps), 1),
                    rows_made_per_pass_upper=misses / max(2 * max(steps), 1))
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+GAMMA10 = 1.0 / (D * SIGMA * SIGMA)   # a numeric gamma near 'scale' on these blobs: one image must serve every pair
+
+
+def _ovo_model(route):
+    from optiml_amd.ml.svm import OneVsOneSVC
+    from optiml_amd.ml.svm.kernels import GaussianKernel
+    from optiml_amd.ml.svm.losses import hinge
+    m = OneVsOneSVC(loss=hinge, kernel=GaussianKernel(GAMMA10), C=1., dual=True, optimizer='smo', tol=TOL, storage='stream')
+    m.batch_smo = 'rows' if route == 'rows' else None
+    return m
+
+
+def cmd_ovo(args):
+    """one OneVsOneSVC fit of the 10-class blobs (45 pairs) in this (fresh) process after a warm-up fit of n = 4000 on the same
+    route: rows = one bq_mrsmo_create_lists solver for all pairs, pairs = one streamed SVC.fit per pair"""
+    _ovo_model(args.route).fit(*_data10(4000))
+    X, y = _data10(args.n)
+    t0 = time.perf_counter()
+    est = _ovo_model(args.route).fit(X, y)
+    wall = time.perf_counter() - t0
+    opts = [e.optimizer for e in est.estimators_]
+    steps = [int(o.iter) for o in opts]
+    stats = [opts[0].cache_stats] if args.route == 'rows' else [o.cache_stats for o in opts]
+    hits, misses = sum(s['hits'] for s in stats), sum(s['misses'] for s in stats)
+    rec = {'what': 'one-vs-one fit, 10 classes, 45 pairs', 'n': args.n, 'd': D, 'gamma': GAMMA10, 'route': args.route, 'tol': TOL,
+           'wall_s': wall, 'includes': 'problem build(s) + solve + read-back', 'steps_per_pair': steps,
+           'status': sorted(set(o.status for o in opts)), 'hits': hits, 'misses': misses, 'hit_rate': hits / max(hits + misses, 1),
+           'cache_rows': stats[0]['cache_rows'], 'list_per': os.environ.get('BQ_TEST_HOOKS', '')}
+    if args.route == 'rows':   # a batched step serves every live pair: the longest pair counts the steps
+        rec.update(batched_steps=max(steps), per_batched_step_us=1e6 * wall / max(max(steps), 1))
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+def cmd_ovo_rate(args):
+    """K steps of the 45 pair columns on one streamed problem, no verdict (the batch-rate method): route rows = one
+    bq_mrsmo_create_lists solver, route pairs = one bq_rsmo solver per pair on a streamed problem of the pair's own rows"""
+    import ctypes as C
+    from optiml_amd import _lib
+    from optiml_amd.ml.svm.kernels import GaussianKernel
+    from optiml_amd.ml.svm.onevsone import ovo_pairs, pair_problem
+    from optiml_amd.opti import KernelQuadratic
+    lib = _lib.load()
+    X, y = _data10(args.n)
+    problems = [pair_problem(y, i, j) for i, j in ovo_pairs(10)]
+    rec = {'what': 'rate of 45 pair columns (NOT a fit)', 'n': args.n, 'd': D, 'route': args.route, 'window_steps': args.steps,
+           'list_per': os.environ.get('BQ_TEST_HOOKS', ''), 'positions': int(sum(len(r) for r, _ in problems))}
+    h, st = C.c_void_p(), np.empty(3)
+    if args.route == 'rows':
+        quad = KernelQuadratic(X, -np.ones(args.n), 'svc', GaussianKernel(GAMMA10), y=np.ones(args.n), storage='stream', rank_one=False)
+        offsets = np.concatenate(([0], np.cumsum([len(r) for r, _ in problems]))).astype(np.int64)
+        rows = np.ascontiguousarray(np.concatenate([r for r, _ in problems]), dtype=np.int32)
+        signs = np.ascontiguousarray(np.concatenate([yp for _, yp in problems]))
+        ones = np.ones(len(signs))
+        _lib.check(lib.bq_mrsmo_create_lists(quad.device_problem().handle, 45, offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             _lib.iptr(rows), _lib.ptr(signs), _lib.ptr(-ones), _lib.ptr(ones), TOL, 0, 0, C.byref(h)))
+        steps, fin = (C.c_int64 * 45)(), (C.c_int * 45)()
+        _lib.check(lib.bq_mrsmo_run(h, 8, steps, fin))   # warm
+        _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+        before = st.copy()
+        t0 = time.perf_counter()
+        _lib.check(lib.bq_mrsmo_run(h, args.steps, steps, fin))
+        wall = time.perf_counter() - t0
+        _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+        lib.bq_mrsmo_destroy(h)
+        quad.release()
+        rec.update(finished=int(sum(fin)), hits=int(st[0] - before[0]), misses=int(st[1] - before[1]), cache_rows=int(st[2]))
+    else:
+        wall, hits, misses = 0.0, 0, 0
+        for r, yp in problems:
+            quad = KernelQuadratic(X[r], -np.ones(len(r)), 'svc', GaussianKernel(GAMMA10), y=yp, storage='stream', rank_one=False)
+            _lib.check(lib.bq_rsmo_create(quad.device_problem().handle, _lib.SVC, _lib.ptr(yp), _lib.ptr(np.ones(len(r))), 0.0, TOL, 0,
+                                          C.byref(h)))
+            steps, fin = C.c_int64(0), C.c_int(0)
+            _lib.check(lib.bq_rsmo_run(h, 8, C.byref(steps), C.byref(fin)))
+            t0 = time.perf_counter()
+            _lib.check(lib.bq_rsmo_run(h, args.steps, C.byref(steps), C.byref(fin)))
+            wall += time.perf_counter() - t0
+            _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_STATS, _lib.ptr(st)))
+            hits, misses = hits + int(st[0]), misses + int(st[1])
+            lib.bq_rsmo_destroy(h)
+            quad.release()
+        rec.update(hits=hits, misses=misses, note='problem and solver create / destroy are outside the window')
+    rec.update(window_s=wall, per_step_of_all_pairs_us=1e6 * wall / args.steps)
     json.dump(rec, open(args.json, 'w'), indent=1)
     print(json.dumps(rec))
 
@@ -462,9 +555,17 @@ def main():
     p.add_argument('--route', default='rows', choices=['rows', 'columns'])
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_batch_rate)
+    for name, fn in (('ovo', cmd_ovo), ('ovo-rate', cmd_ovo_rate)):
+        p = sub.add_parser(name)
+        p.add_argument('--n', type=int, required=True)
+        p.add_argument('--steps', type=int, default=2000)
+        p.add_argument('--route', default='rows', choices=['rows', 'pairs'])
+        p.add_argument('--json', required=True)
+        p.set_defaults(fn=fn)
     p = sub.add_parser('kernels')
     p.add_argument('--trace', required=True)
-    p.add_argument('--kernels', default='mr_rows_kernel,mr_select_kernel,mr_update_kernel,rsmo_select_kernel,rsmo_update_kernel')
+    p.add_argument('--kernels', default='mr_rows_kernel,mr_select_kernel,mr_update_kernel,ml_select_kernel,ml_update_kernel,'
+                   'rsmo_select_kernel,rsmo_update_kernel')
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_kernels)
     p = sub.add_parser('nu-all')
