@@ -69,6 +69,7 @@ extern "C" {
 /* (still 3: bq_rsmo_create_general and BQ_RSMO_NU_SCALARS were added; nothing existing changed) */
 /* (still 3: bq_mrsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
 /* (still 3: bq_mrsmo_create_lists was added; nothing existing changed) */
+/* (still 3: bq_mrsmo_create_general / _create_lists_general were added, bq_mrsmo_get takes BQ_RSMO_NU_SCALARS; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -867,6 +868,24 @@ int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const 
  * and what bq_mrsmo_create refuses (k, cache_rows, tol, signs, boxes, lin, a resident problem). */
 int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offsets, const int32_t *rows, const double *signs, const double *lin,
                           const double *boxes, double tol, int64_t max_steps, int64_t cache_rows, bq_mrsmo **out);
+/* The general entries: `rule` (BQ_RSMO_RULE_PLAIN or BQ_RSMO_RULE_NU, one for all columns) and a start `alpha0`, laid out like `signs`;
+ * bq_mrsmo_create / _create_lists are these with BQ_RSMO_RULE_PLAIN and alpha0 = 0.  Under BQ_RSMO_RULE_NU a step is libsvm's
+ * Solver_NU per column (csrc/bq_mrsmo_nu.h): one maximal violator per sign, two row requests per column resolved together (ip
+ * and in on one row share a slot), every variable scored against the row of its own sign, row j requested with both pinned.
+ * The start gradient is DEFINED, so that it can be restated bit for bit: b_r = sum of s_v alpha0_v over the variables of row r
+ * (per position in the list form); acc = 0; for the rows r of the column with b_r != 0, ascending, acc <- acc + fl(K[row(v)][r] b_r);
+ * G0_v = lin_v + s_v acc.  A column with b = 0 everywhere keeps lin's bits.  The rows with b != 0 in any column go through the
+ * cache once, 16 per MFMA pass (they count as requests in BQ_RSMO_STATS), and one start kernel folds them into every column; no
+ * start kernel runs when every b is 0.
+ * bq_mrsmo_get(BQ_RSMO_NU_SCALARS, column) of a NU solver: the seven values of bq_rsmo_get (i and j as positions in the list form);
+ * BQ_RSMO_SCALARS of a NU solver as bq_rsmo_get gives them.
+ * BQ_ERR_BADARG: what the entries above refuse, an unknown rule, a start outside [0, box], and for BQ_RSMO_RULE_NU a column with
+ * one sign only, k > 512 (two requests per column at once) and cache_rows in 1 .. 3k - 1 (a step holds three rows per column). */
+int bq_mrsmo_create_general(bq_problem *p, int rule, int k, int64_t N, const double *signs, const double *lin, const double *boxes,
+                            const double *alpha0, double tol, int64_t max_steps, int64_t cache_rows, bq_mrsmo **out);
+int bq_mrsmo_create_lists_general(bq_problem *p, int rule, int k, const int64_t *offsets, const int32_t *rows, const double *signs,
+                                  const double *lin, const double *boxes, const double *alpha0, double tol, int64_t max_steps,
+                                  int64_t cache_rows, bq_mrsmo **out);
 int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int *finished);
 int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out);
 int bq_mrsmo_rows(bq_mrsmo *s, int m, const int64_t *idx, double *out);

@@ -180,6 +180,9 @@ PROTOTYPES = {
     'bq_rsmo_destroy': (C.c_int, [_vp]),
     'bq_mrsmo_create': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, C.c_double, _i64, _i64, C.POINTER(_vp)]),
     'bq_mrsmo_create_lists': (C.c_int, [_vp, C.c_int, C.POINTER(_i64), _ip, _dp, _dp, _dp, C.c_double, _i64, _i64, C.POINTER(_vp)]),
+    'bq_mrsmo_create_general': (C.c_int, [_vp, C.c_int, C.c_int, _i64, _dp, _dp, _dp, _dp, C.c_double, _i64, _i64, C.POINTER(_vp)]),
+    'bq_mrsmo_create_lists_general': (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_i64), _ip, _dp, _dp, _dp, _dp, C.c_double, _i64, _i64,
+                                                C.POINTER(_vp)]),
     'bq_mrsmo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),
     'bq_mrsmo_get': (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     'bq_mrsmo_rows': (C.c_int, [_vp, C.c_int, C.POINTER(_i64), _dp]),

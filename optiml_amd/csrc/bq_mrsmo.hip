@@ -1,5 +1,5 @@
-// Batched panel-free SMO (bq_mrsmo_*, bcqp.h): k columns of libsvm's WSS2 decomposition (the scalar rules of bq_rsmo_step.h, rule
-// BQ_RSMO_RULE_PLAIN, zero start) on ONE streamed problem, ONE cache of kernel rows, and kernel rows made 16 at a time by fp64 MFMA.
+// Batched panel-free SMO (bq_mrsmo_*, bcqp.h): k columns of libsvm's WSS2 decomposition (the scalar rules of bq_rsmo_step.h; rule
+// BQ_RSMO_RULE_PLAIN here, BQ_RSMO_RULE_NU and the start gradient of nonzero starts in bq_mrsmo_nu.h) on ONE streamed problem, ONE cache of kernel rows, and kernel rows made 16 at a time by fp64 MFMA.
 // A row of K does not depend on the labels: every column asks for rows of the same matrix, so the rows all columns need in a phase
 // of a step are resolved together (bq_mrsmo_cache.h) and the missing ones are made in one pass over the k-major image.
 //
@@ -67,6 +67,10 @@ struct mr_col {   // a column's control block
     int last_i, last_j;
     unsigned int ticket;
     double gmax, gmax2, d_i, d_j, y_i, y_j;
+    // BQ_RSMO_RULE_NU: i / slot_i / gmax / gmax2 are the positive side's (ip, Gmaxp, Gmaxp2), these the negative side's
+    int i2, slot_2;
+    int slot_u, pad_;       // the slot of the row of the i that the select kernel paired with j (slot_i or slot_2)
+    double gmaxn, gmaxn2;
 };
 struct mr_glob {
     bq_mrsmo_cache cache;
@@ -93,12 +97,16 @@ struct mr_dev {
     double *cache;                // R x pitch
     mr_col *col;                  // k
     mr_glob *glob;
-    int *req_row;                 // k: the row each column asks for in the phase in hand, -1: none
+    int *req_row;                 // k: the row each column asks for in the phase in hand, -1: none; BQ_RSMO_RULE_NU: 3 k, the j
+                                  // phase's request of column c at [c], the i phase's two (ip, in) at [k + 2 c], [k + 2 c + 1]
+    int nreq;                     // requests per column in the i phase = rows a live column waits for between steps: 1, NU 2
     int *miss_row, *miss_slot;    // MR_REQ: the distinct missing rows and their slots
     int *req_in, *req_out;        // MR_REQ: bq_mrsmo_rows' requests and their slots
     int *res_req, *res_slot, *res_pin;   // MR_REQ each: the tables of a resolution, touched by the launch's last workgroup only
     double *part_v, *part_k, *part_w;   // k x nblk
     long long *part_i;
+    double *part_v2, *part_w2;          // BQ_RSMO_RULE_NU: the negative side's candidate and maximum
+    long long *part_i2;
     // the list form: alpha / G / y / Cb are packed at info[c].off instead of c N, N is 0
     const int *rows;        // the lists, packed like the state; the pad positions of a column repeat its last row
     const ml_info *info;    // k
@@ -219,26 +227,37 @@ __global__ __launch_bounds__(RSMO_T) void mr_diag_kernel(mr_dev P) {
 }
 
 // ---- the resolution of a phase: every thread of the launch's LAST workgroup --------------------------------------------------------
-// phase_j: the rows j are asked for while the rows i of the same columns are still to be read (pins)
+// phase_j: the rows j are asked for while the rows i of the same columns are still to be read (pins).  NQ: the requests (and the
+// pinned rows) per column of the i phase — 1, Solver_NU 2 (ip, in), whose i-phase requests live behind the k of the j phase.
+template <int NQ = 1>
 __device__ __forceinline__ void mr_resolve_last(const mr_dev &P, rsmo_pick_smem<long long> &pick, bool phase_j) {
-    for (int c = threadIdx.x; c < P.k; c += RSMO_T) {
-        const int req = bq_part_get(&P.req_row[c]);
-        P.res_req[c] = req;
-        P.res_pin[c] = phase_j && req >= 0 ? P.col[c].slot_i : -1;
+    const int nq = phase_j ? 1 : NQ, m = nq * P.k;
+    const int *req_row = P.req_row + (NQ > 1 && !phase_j ? P.k : 0);
+    for (int e = threadIdx.x; e < m; e += RSMO_T) P.res_req[e] = bq_part_get(&req_row[e]);
+    for (int e = threadIdx.x; e < NQ * P.k; e += RSMO_T) {
+        const int c = e / NQ;
+        P.res_pin[e] = phase_j && bq_part_get(&P.req_row[c]) >= 0 ? (e % NQ ? P.col[c].slot_2 : P.col[c].slot_i) : -1;
     }
     __syncthreads();
     mr_par par{pick};
-    bq_mrsmo_resolve(&P.glob->cache, phase_j ? P.k : 0, P.res_pin, P.k, P.res_req, P.res_slot, P.miss_row, P.miss_slot, &P.glob->n_miss, par);
+    bq_mrsmo_resolve(&P.glob->cache, phase_j ? NQ * P.k : 0, P.res_pin, m, P.res_req, P.res_slot, P.miss_row, P.miss_slot, &P.glob->n_miss,
+                     par);
     __syncthreads();
     for (int c = threadIdx.x; c < P.k; c += RSMO_T) {
-        if (phase_j)
+        if (phase_j) {
             P.col[c].slot_j = P.res_slot[c];
-        else
-            P.col[c].slot_i = P.res_slot[c];
+        } else {
+            P.col[c].slot_i = P.res_slot[NQ * c];
+            if (NQ > 1) P.col[c].slot_2 = P.res_slot[NQ * c + 1];
+        }
     }
     if (threadIdx.x == 0) {
         int live = 0;
-        for (int c = 0; c < P.k; ++c) live += P.res_req[c] >= 0 ? 1 : 0;   // a column that goes on asks for a row in either phase
+        for (int c = 0; c < P.k; ++c) {   // a column that goes on asks for a row in either phase
+            bool asks = false;
+            for (int h = 0; h < nq; ++h) asks = asks || P.res_req[nq * c + h] >= 0;
+            live += asks ? 1 : 0;
+        }
         P.glob->live = live;
     }
 }
@@ -649,16 +668,21 @@ __global__ __launch_bounds__(RSMO_T) void ml_update_kernel(mr_dev P, int first) 
     mr_resolve_last(P, shl, false);
 }
 
+}   // namespace
+#include "bq_mrsmo_nu.h"   // Solver_NU's select / update in both forms and the start gradient of nonzero starts
+namespace {
+
 // ---- bq_mrsmo_rows: m requested rows through the cache, the rows the live columns wait for pinned ------------------------------------
 __global__ __launch_bounds__(RSMO_T) void mr_request_kernel(mr_dev P, int m) {
     __shared__ rsmo_pick_smem<long long> shl;
     for (int q = threadIdx.x; q < MR_REQ; q += RSMO_T) {
         P.res_req[q] = q < m ? P.req_in[q] : -1;
-        P.res_pin[q] = q < P.k && !P.col[q].finished ? P.col[q].slot_i : -1;
+        const int c = q / P.nreq;   // (Solver_NU: a live column waits for the rows of ip and in)
+        P.res_pin[q] = c < P.k && !P.col[c].finished ? (q % P.nreq ? P.col[c].slot_2 : P.col[c].slot_i) : -1;
     }
     __syncthreads();
     mr_par par{shl};
-    bq_mrsmo_resolve(&P.glob->cache, P.k, P.res_pin, m, P.res_req, P.res_slot, P.miss_row, P.miss_slot, &P.glob->n_miss, par);
+    bq_mrsmo_resolve(&P.glob->cache, P.nreq * P.k, P.res_pin, m, P.res_req, P.res_slot, P.miss_row, P.miss_slot, &P.glob->n_miss, par);
     __syncthreads();
     for (int q = threadIdx.x; q < m; q += RSMO_T) P.req_out[q] = P.res_slot[q];
 }
@@ -669,6 +693,7 @@ __global__ void mr_clear_kernel(mr_dev P) { P.glob->n_miss = 0; }
 
 struct bq_mrsmo {
     bq_problem *p = nullptr;
+    int rule = BQ_RSMO_RULE_PLAIN;
     bq_owner mem;
     mr_dev P = {};
     unsigned int nblk = 0;
@@ -708,26 +733,36 @@ static void mr_launch_rows(KD, const bq_mrsmo *s, hipStream_t st) {
 }
 
 // what both forms of create refuse before they look at a column
-static int mr_check(const bq_problem *p, int k, double tol, int64_t max_steps, int64_t cache_rows) {
+static int mr_check(const bq_problem *p, int rule, int k, double tol, int64_t max_steps, int64_t cache_rows) {
+    BQ_ARG(rule == BQ_RSMO_RULE_PLAIN || rule == BQ_RSMO_RULE_NU, "rule must be BQ_RSMO_RULE_PLAIN or BQ_RSMO_RULE_NU");
     BQ_ARG(p->kernel >= 0 && p->streamed && p->stream_img != nullptr && p->ctx->world == 1,
            "the row-based SMO needs a kernel-built streamed problem (BQ_STREAM) on a single-rank context");
     BQ_ARG(k >= 1 && k <= MR_REQ, "k must lie in 1 .. 1024");
     BQ_ARG(tol > 0.0, "tol must be > 0");
     BQ_ARG(max_steps >= 0, "max_steps must be >= 0 (0: libsvm's cap)");
     BQ_ARG(cache_rows == 0 || cache_rows >= 2 * (int64_t)k, "cache_rows must be 0 (automatic) or >= 2 k: a step holds two rows per column");
+    if (rule == BQ_RSMO_RULE_NU) {
+        BQ_ARG(k <= MR_REQ / 2, "Solver_NU asks for two rows per column at once: k must lie in 1 .. 512");
+        BQ_ARG(cache_rows == 0 || cache_rows >= 3 * (int64_t)k, "a Solver_NU step holds three rows per column: cache_rows must be 0 or >= 3 k");
+    }
     return BQ_OK;
 }
-static int mr_check_entry(double sign, double lin, double box) {
+static int mr_check_entry(double sign, double lin, double box, double alpha0) {
     BQ_ARG(std::isfinite(box) && box > 0.0, "every box must be finite and > 0");
     BQ_ARG(sign == 1.0 || sign == -1.0, "signs must be +1 / -1");
     BQ_ARG(std::isfinite(lin), "the linear term must be finite");
+    BQ_ARG(alpha0 >= 0.0 && alpha0 <= box, "the start must lie in its box");
     return BQ_OK;
 }
+// a column's nonzeros of the folded start, ascending by row: (row, b)
+typedef std::vector<std::pair<int, double>> mr_fold;
 
 // a solver on p with the problem's side of mr_dev filled in
-static bq_mrsmo *mr_new(bq_problem *p, int k, double tol) {
+static bq_mrsmo *mr_new(bq_problem *p, int rule, int k, double tol) {
     bq_mrsmo *s = new bq_mrsmo();
     s->p = p;
+    s->rule = rule;
+    s->P.nreq = rule == BQ_RSMO_RULE_NU ? 2 : 1;
     p->refs += 1;
     mr_dev &P = s->P;
     int64_t dp = 0;
@@ -745,18 +780,21 @@ static bq_mrsmo *mr_new(bq_problem *p, int k, double tol) {
     return s;
 }
 
-// What both forms of create share once s->y / s->Cb hold the columns' signs and boxes in the device's layout (`total` entries) and
-// `G0` the linear terms in the same layout: the vectors, `parts` partials, the cache, the start state, QD and the first selection
-// (`first()` launches it, after QD).  `dual` is the longest column's dimension (libsvm's cap).  On failure s is destroyed.
-template <typename FIRST>
-static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, int64_t dual, int64_t max_steps, int64_t cache_rows,
-                    FIRST first, bq_mrsmo **out) {
+// What both forms of create share once s->y / s->Cb hold the columns' signs and boxes in the device's layout (`total` entries),
+// `G0` the linear terms and `a0` the start in the same layout and `fold` every column's folded start: the vectors, `parts`
+// partials, the cache, the start state, the start gradient (`start(S, batch, last)` launches the form's start kernel; nothing is
+// launched when every folded start is zero), QD and the first selection (`first()` launches it, after QD).  `dual` is the longest
+// column's dimension (libsvm's cap).  On failure s is destroyed.
+template <typename START, typename FIRST>
+static int mr_start(bq_mrsmo *s, const double *G0, const double *a0, const std::vector<mr_fold> &fold, size_t total, size_t parts,
+                    int64_t dual, int64_t max_steps, int64_t cache_rows, START start, FIRST first, bq_mrsmo **out) {
     bq_problem *p = s->p;
     bq_ctx *c = p->ctx;
     mr_dev &P = s->P;
     const int k = P.k;
     const int64_t n = P.n;
     const size_t kN = total;
+    const bool nu = s->rule == BQ_RSMO_RULE_NU;
     auto fail = [&](hipError_t e, const char *what) {
         bq_set_error("%s failed: %s", what, hipGetErrorString(e));
         hipStreamSynchronize(c->stream);
@@ -764,6 +802,7 @@ static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, i
         return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
     };
     bq_mrsmo_cache cache = {};
+    const size_t nreq_row = (size_t)(nu ? 3 : 1) * (size_t)k;
     hipError_t e = s->mem.dev(&P.alpha, kN);
     if (e == hipSuccess) e = s->mem.dev(&P.G, kN);
     if (e == hipSuccess) e = s->mem.dev(&P.y, kN);
@@ -772,7 +811,7 @@ static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, i
     if (e == hipSuccess) e = s->mem.dev(&cache.slot_of, (size_t)n);
     if (e == hipSuccess) e = s->mem.dev(&P.col, (size_t)k);
     if (e == hipSuccess) e = s->mem.dev(&P.glob, 1);
-    if (e == hipSuccess) e = s->mem.dev(&P.req_row, (size_t)k);
+    if (e == hipSuccess) e = s->mem.dev(&P.req_row, nreq_row);
     if (e == hipSuccess) e = s->mem.dev(&P.miss_row, (size_t)MR_REQ);
     if (e == hipSuccess) e = s->mem.dev(&P.miss_slot, (size_t)MR_REQ);
     if (e == hipSuccess) e = s->mem.dev(&P.req_in, (size_t)MR_REQ);
@@ -784,13 +823,18 @@ static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, i
     if (e == hipSuccess) e = s->mem.dev(&P.part_k, parts);
     if (e == hipSuccess) e = s->mem.dev(&P.part_w, parts);
     if (e == hipSuccess) e = s->mem.dev(&P.part_i, parts);
+    if (nu) {
+        if (e == hipSuccess) e = s->mem.dev(&P.part_v2, parts);
+        if (e == hipSuccess) e = s->mem.dev(&P.part_w2, parts);
+        if (e == hipSuccess) e = s->mem.dev(&P.part_i2, parts);
+    }
     if (e != hipSuccess) return fail(e, "the batched row-based SMO's vectors");
     // the cache: the rows asked for, or what half of the free memory holds; n rows hold every row there is
     int64_t R = cache_rows;
     if (R == 0) {
         size_t free_b = 0, total_b = 0;
         if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return fail(e, "hipMemGetInfo");
-        R = std::max<int64_t>((int64_t)(free_b / 2 / (sizeof(double) * (size_t)P.pitch)), 2 * (int64_t)k);
+        R = std::max<int64_t>((int64_t)(free_b / 2 / (sizeof(double) * (size_t)P.pitch)), (nu ? 3 : 2) * (int64_t)k);
     }
     if (R > n) R = n;
     s->R = cache.R = R;
@@ -799,14 +843,14 @@ static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, i
     e = bq_dev_zeroed(e, s->mem, &cache.stamp, (size_t)R, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(cache.slot_of, 0xFF, sizeof(int) * (size_t)n, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(cache.row_of, 0xFF, sizeof(int) * (size_t)R, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(P.req_row, 0xFF, sizeof(int) * (size_t)k, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(P.alpha, 0, sizeof(double) * kN, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(P.G, G0, sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);   // zero start: G0 = lin
+    if (e == hipSuccess) e = hipMemsetAsync(P.req_row, 0xFF, sizeof(int) * nreq_row, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(P.alpha, a0, sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(P.G, G0, sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);   // b = 0: G0 = lin
     if (e == hipSuccess) e = hipMemcpyAsync(P.y, s->y.data(), sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(P.Cb, s->Cb.data(), sizeof(double) * kN, hipMemcpyHostToDevice, c->stream);
     mr_col c0 = {};
-    c0.i = c0.j = c0.last_i = c0.last_j = c0.slot_i = c0.slot_j = -1;
-    c0.gmax = c0.gmax2 = -INFINITY;
+    c0.i = c0.j = c0.i2 = c0.last_i = c0.last_j = c0.slot_i = c0.slot_j = c0.slot_2 = c0.slot_u = -1;
+    c0.gmax = c0.gmax2 = c0.gmaxn = c0.gmaxn2 = -INFINITY;
     std::fill(s->host.begin(), s->host.end(), c0);
     mr_glob g0 = {};
     g0.cache = cache;
@@ -816,51 +860,90 @@ static int mr_start(bq_mrsmo *s, const double *G0, size_t total, size_t parts, i
     if (e == hipSuccess) e = hipMemcpyAsync(P.col, s->host.data(), sizeof(mr_col) * (size_t)k, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(P.glob, &g0, sizeof(g0), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return fail(e, "the batched row-based SMO's start");
+    // the start gradient: the ascending union of the rows with b != 0, each column's entries against it, and per batch of at most
+    // min(MR_REQ, R) rows of the union each column's range of entries
+    std::vector<int> uni;
+    for (const mr_fold &f : fold)
+        for (const auto &rb : f) uni.push_back(rb.first);
+    std::sort(uni.begin(), uni.end());
+    uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
+    const int64_t B = std::min<int64_t>(MR_REQ, R), nbatch = ((int64_t)uni.size() + B - 1) / B;
+    ms_tab S = {};
+    std::vector<ms_ent> ent;
+    std::vector<int2> range((size_t)(nbatch * k));
+    std::vector<int> has((size_t)k, 0);
+    if (!uni.empty()) {
+        for (int q = 0; q < k; ++q) {
+            const mr_fold &f = fold[(size_t)q];
+            has[(size_t)q] = f.empty() ? 0 : 1;
+            const int e0 = (int)ent.size();
+            for (const auto &rb : f)
+                ent.push_back(ms_ent{rb.second, (int)(std::lower_bound(uni.begin(), uni.end(), rb.first) - uni.begin()), 0});
+            int at = e0;   // (the entries ascend in u: one walk serves every batch)
+            for (int64_t b = 0; b < nbatch; ++b) {
+                const int lo = at;
+                while (at < (int)ent.size() && ent[(size_t)at].u < (b + 1) * B) ++at;
+                range[(size_t)(b * k + q)] = make_int2(lo, at);
+            }
+        }
+        ms_ent *d_ent = nullptr;
+        int2 *d_range = nullptr;
+        int *d_has = nullptr;
+        e = s->mem.dev(&d_ent, ent.size());
+        if (e == hipSuccess) e = s->mem.dev(&d_range, range.size());
+        if (e == hipSuccess) e = s->mem.dev(&d_has, (size_t)k);
+        e = bq_dev_zeroed(e, s->mem, &S.acc, s->per ? kN : (size_t)k * (size_t)n, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ent, ent.data(), sizeof(ms_ent) * ent.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_range, range.data(), sizeof(int2) * range.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_has, has.data(), sizeof(int) * (size_t)k, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return fail(e, "the start gradient's tables");
+        S.ent = d_ent;
+        S.range = d_range;
+        S.has = d_has;
+    }
     int rc = rsmo_dispatch(p, [&](auto kd) {
+        for (int64_t b = 0; b < nbatch && e == hipSuccess; ++b) {   // a batch: its rows into slots (made 16 at a time), folded into every column
+            const int cnt = (int)std::min<int64_t>(B, (int64_t)uni.size() - b * B);
+            e = hipMemcpyAsync(P.req_in, uni.data() + b * B, sizeof(int) * (size_t)cnt, hipMemcpyHostToDevice, c->stream);
+            mr_request_kernel<<<1, RSMO_T, 0, c->stream>>>(P, cnt);
+            mr_launch_rows(kd, s, c->stream);
+            S.u0 = (int)(b * B);
+            start(S, (int)b, b == nbatch - 1 ? 1 : 0);
+            mr_clear_kernel<<<1, 1, 0, c->stream>>>(P);
+        }
         const unsigned int waves = (unsigned int)(P.mp / 16), per = RSMO_T / 64;
         mr_diag_kernel<decltype(kd)::kind, decltype(kd)::deg><<<(waves + per - 1) / per, RSMO_T, 0, c->stream>>>(P);
         first();
     });
+    if (rc == BQ_OK && e != hipSuccess) return fail(e, "the batched row-based SMO's start gradient");
     if (rc == BQ_OK && (e = hipGetLastError()) != hipSuccess) return fail(e, "the batched row-based SMO's first selection");
-    if (rc == BQ_OK) rc = mr_read_cols(s);   // (g0, c0 and the caller's vectors are read by then)
+    if (rc == BQ_OK) rc = mr_read_cols(s);   // (g0, c0, the tables and the caller's vectors are read by then)
     if (rc != BQ_OK) {
         hipStreamSynchronize(c->stream);
         bq_mrsmo_destroy(s);
         return rc;
     }
+    s->mem.release(S.ent);   // the start's tables served the set-up only
+    s->mem.release(S.range);
+    s->mem.release(S.has);
+    s->mem.release(S.acc);
     *out = s;
     return BQ_OK;
 }
 
-extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
-                               int64_t max_steps, int64_t cache_rows, bq_mrsmo **out) {
-    BQ_ARG(p && signs && lin && boxes && out, "NULL argument");
-    BQ_TRY(mr_check(p, k, tol, max_steps, cache_rows));
-    const int64_t n = p->n;
-    BQ_ARG(N == n || N == 2 * n, "N must be n or 2n");
-    BQ_ARG(N < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
-    for (int64_t v = 0; v < (int64_t)k * N; ++v) {
-        BQ_TRY(mr_check_entry(signs[v], lin[v], boxes[v]));
-        BQ_ARG(N == n || signs[v] == (v % N < n ? 1.0 : -1.0), "the signs of 2n variables must be [+1 ..; -1 ..]");
-    }
-    BQ_HIP(hipSetDevice(p->ctx->device));
-    bq_mrsmo *s = mr_new(p, k, tol);
-    s->P.N = N;
-    s->nblk = (unsigned int)((n + RSMO_T - 1) / RSMO_T);
-    const size_t kN = (size_t)k * (size_t)N;
-    s->y.assign(signs, signs + kN);
-    s->Cb.assign(boxes, boxes + kN);
-    return mr_start(s, lin, kN, (size_t)k * s->nblk, N, max_steps, cache_rows, [&] {
-        mr_update_kernel<<<dim3(s->nblk, (unsigned int)k), RSMO_T, 0, p->ctx->stream>>>(s->P, 1);
-    }, out);
-}
-
-// the list form's launches 2 and 4 at the solver's positions per thread
-static void ml_launch(const bq_mrsmo *s, bool select, int first, hipStream_t st) {
+// the list form's launches 2 and 4 at the solver's positions per thread and rule (start: the start kernel of a batch)
+static void ml_launch(const bq_mrsmo *s, bool select, int first, hipStream_t st, const ms_tab *start = nullptr, int batch = 0) {
+    const bool nu = s->rule == BQ_RSMO_RULE_NU;
     auto go = [&](auto per) {
         constexpr int PER = decltype(per)::value;
-        if (select)
+        if (start)
+            ml_start_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P, *start, batch, first);
+        else if (select && nu)
+            ml_nu_select_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P);
+        else if (select)
             ml_select_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P);
+        else if (nu)
+            ml_nu_update_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P, first);
         else
             ml_update_kernel<PER><<<s->grid, RSMO_T, 0, st>>>(s->P, first);
     };
@@ -871,22 +954,90 @@ static void ml_launch(const bq_mrsmo *s, bool select, int first, hipStream_t st)
     else
         go(std::integral_constant<int, ML_PER>());
 }
+// launches 2 and 4 of either form
+static void mr_launch_step(const bq_mrsmo *s, bool select, int first, hipStream_t st) {
+    if (s->per) return ml_launch(s, select, first, st);
+    const dim3 grid(s->nblk, (unsigned int)s->P.k);
+    const bool nu = s->rule == BQ_RSMO_RULE_NU;
+    if (select && nu)
+        mr_nu_select_kernel<<<grid, RSMO_T, 0, st>>>(s->P);
+    else if (select)
+        mr_select_kernel<<<grid, RSMO_T, 0, st>>>(s->P);
+    else if (nu)
+        mr_nu_update_kernel<<<grid, RSMO_T, 0, st>>>(s->P, first);
+    else
+        mr_update_kernel<<<grid, RSMO_T, 0, st>>>(s->P, first);
+}
 
-extern "C" int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offsets, const int32_t *rows, const double *signs,
-                                     const double *lin, const double *boxes, double tol, int64_t max_steps, int64_t cache_rows,
-                                     bq_mrsmo **out) {
-    BQ_ARG(p && offsets && rows && signs && lin && boxes && out, "NULL argument");
-    BQ_TRY(mr_check(p, k, tol, max_steps, cache_rows));
+extern "C" int bq_mrsmo_create_general(bq_problem *p, int rule, int k, int64_t N, const double *signs, const double *lin,
+                                       const double *boxes, const double *alpha0, double tol, int64_t max_steps, int64_t cache_rows,
+                                       bq_mrsmo **out) {
+    BQ_ARG(p && signs && lin && boxes && alpha0 && out, "NULL argument");
+    BQ_TRY(mr_check(p, rule, k, tol, max_steps, cache_rows));
+    const int64_t n = p->n;
+    BQ_ARG(N == n || N == 2 * n, "N must be n or 2n");
+    BQ_ARG(N < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
+    std::vector<mr_fold> fold((size_t)k);
+    for (int c = 0; c < k; ++c) {
+        const double *sg = signs + (int64_t)c * N, *a0 = alpha0 + (int64_t)c * N;
+        bool pos = false, neg = false;
+        for (int64_t v = 0; v < N; ++v) {
+            BQ_TRY(mr_check_entry(sg[v], lin[(int64_t)c * N + v], boxes[(int64_t)c * N + v], a0[v]));
+            BQ_ARG(N == n || sg[v] == (v < n ? 1.0 : -1.0), "the signs of 2n variables must be [+1 ..; -1 ..]");
+            pos |= sg[v] > 0.0;
+            neg |= sg[v] < 0.0;
+        }
+        BQ_ARG(rule != BQ_RSMO_RULE_NU || (pos && neg), "Solver_NU needs both signs");
+        for (int64_t t = 0; t < n; ++t) {   // b, folded to the rows
+            double b = sg[t] * a0[t];
+            if (N > n) b = b + sg[t + n] * a0[t + n];
+            if (b != 0.0) fold[(size_t)c].push_back({(int)t, b});
+        }
+    }
+    BQ_HIP(hipSetDevice(p->ctx->device));
+    bq_mrsmo *s = mr_new(p, rule, k, tol);
+    s->P.N = N;
+    s->nblk = (unsigned int)((n + RSMO_T - 1) / RSMO_T);
+    const size_t kN = (size_t)k * (size_t)N;
+    s->y.assign(signs, signs + kN);
+    s->Cb.assign(boxes, boxes + kN);
+    hipStream_t st = p->ctx->stream;
+    const dim3 grid(s->nblk, (unsigned int)k);
+    return mr_start(s, lin, alpha0, fold, kN, (size_t)k * s->nblk, N, max_steps, cache_rows,
+                    [&](const ms_tab &S, int batch, int last) { mr_start_kernel<<<grid, RSMO_T, 0, st>>>(s->P, S, batch, last); },
+                    [&] { mr_launch_step(s, false, 1, st); }, out);
+}
+
+// libsvm's Solver from a zero start: the general entry with BQ_RSMO_RULE_PLAIN and alpha0 = 0 (G0 = lin, no start kernel)
+extern "C" int bq_mrsmo_create(bq_problem *p, int k, int64_t N, const double *signs, const double *lin, const double *boxes, double tol,
+                               int64_t max_steps, int64_t cache_rows, bq_mrsmo **out) {
+    BQ_ARG(p && k >= 1 && k <= MR_REQ && N >= 1, "NULL argument, or k outside 1 .. 1024");
+    const std::vector<double> zero((size_t)k * (size_t)N, 0.0);
+    return bq_mrsmo_create_general(p, BQ_RSMO_RULE_PLAIN, k, N, signs, lin, boxes, zero.data(), tol, max_steps, cache_rows, out);
+}
+
+extern "C" int bq_mrsmo_create_lists_general(bq_problem *p, int rule, int k, const int64_t *offsets, const int32_t *rows,
+                                             const double *signs, const double *lin, const double *boxes, const double *alpha0, double tol,
+                                             int64_t max_steps, int64_t cache_rows, bq_mrsmo **out) {
+    BQ_ARG(p && offsets && rows && signs && lin && boxes && alpha0 && out, "NULL argument");
+    BQ_TRY(mr_check(p, rule, k, tol, max_steps, cache_rows));
     const int64_t n = p->n;
     BQ_ARG(offsets[0] == 0, "offsets must ascend from 0");
+    std::vector<mr_fold> fold((size_t)k);
     for (int c = 0; c < k; ++c) {
         BQ_ARG(offsets[c + 1] > offsets[c], "every column needs at least one row: offsets must ascend strictly");
         BQ_ARG(offsets[c + 1] - offsets[c] <= n, "a list cannot be longer than the problem has rows");
+        bool pos = false, neg = false;
         for (int64_t v = offsets[c]; v < offsets[c + 1]; ++v) {
             BQ_ARG(rows[v] >= 0 && rows[v] < n, "a listed row lies outside the problem");
             BQ_ARG(v == offsets[c] || rows[v] > rows[v - 1], "a column's rows must ascend strictly");
-            BQ_TRY(mr_check_entry(signs[v], lin[v], boxes[v]));
+            BQ_TRY(mr_check_entry(signs[v], lin[v], boxes[v], alpha0[v]));
+            pos |= signs[v] > 0.0;
+            neg |= signs[v] < 0.0;
+            const double b = signs[v] * alpha0[v];   // per position
+            if (b != 0.0) fold[(size_t)c].push_back({(int)rows[v], b});
         }
+        BQ_ARG(rule != BQ_RSMO_RULE_NU || (pos && neg), "Solver_NU needs both signs");
     }
     BQ_ARG(n < ((int64_t)1 << 31), "the dual dimension must stay below 2^31");
     int per = (int)bq_hook_value("mrsmo_list_per", (double)ML_PER);   // the slice-width comparison of profiles/ovo_smo_rows/
@@ -906,10 +1057,10 @@ extern "C" int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offset
         longest = std::max(longest, m);
     }
     BQ_ARG(parts < ((int64_t)1 << 31) && total < ((int64_t)1 << 40), "the lists are too long for one solver");
-    std::vector<double> G0((size_t)total, 0.0);
+    std::vector<double> G0((size_t)total, 0.0), a0((size_t)total, 0.0);
     std::vector<int> list((size_t)total, 0);
     BQ_HIP(hipSetDevice(p->ctx->device));
-    bq_mrsmo *s = mr_new(p, k, tol);
+    bq_mrsmo *s = mr_new(p, rule, k, tol);
     s->P.N = 0;
     s->per = per;
     s->grid = (unsigned int)parts;
@@ -925,6 +1076,7 @@ extern "C" int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offset
             s->y[(size_t)(in.off + q)] = signs[src + q];
             s->Cb[(size_t)(in.off + q)] = boxes[src + q];
             G0[(size_t)(in.off + q)] = lin[src + q];
+            a0[(size_t)(in.off + q)] = alpha0[src + q];
         }
     }
     s->info = info;
@@ -948,8 +1100,19 @@ extern "C" int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offset
     s->P.rows = d_rows;
     s->P.info = d_info;
     s->P.work = d_work;
-    return mr_start(s, G0.data(), (size_t)total, (size_t)parts, longest, max_steps, cache_rows,
+    return mr_start(s, G0.data(), a0.data(), fold, (size_t)total, (size_t)parts, longest, max_steps, cache_rows,
+                    [&](const ms_tab &S, int batch, int last) { ml_launch(s, false, last, c->stream, &S, batch); },
                     [&] { ml_launch(s, false, 1, c->stream); }, out);
+}
+
+extern "C" int bq_mrsmo_create_lists(bq_problem *p, int k, const int64_t *offsets, const int32_t *rows, const double *signs,
+                                     const double *lin, const double *boxes, double tol, int64_t max_steps, int64_t cache_rows,
+                                     bq_mrsmo **out) {
+    BQ_ARG(p && offsets && k >= 1 && k <= MR_REQ, "NULL argument, or k outside 1 .. 1024");
+    BQ_ARG(offsets[0] == 0 && offsets[k] >= 0, "offsets must ascend from 0");
+    const std::vector<double> zero((size_t)offsets[k], 0.0);
+    return bq_mrsmo_create_lists_general(p, BQ_RSMO_RULE_PLAIN, k, offsets, rows, signs, lin, boxes, zero.data(), tol, max_steps,
+                                         cache_rows, out);
 }
 
 extern "C" int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int *finished) {
@@ -958,20 +1121,12 @@ extern "C" int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int 
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     if (!s->done) {
-        const mr_dev &P = s->P;
-        const dim3 grid(s->nblk, (unsigned int)P.k);
         BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
             for (int64_t q = 0; q < max_steps; ++q) {
                 mr_launch_rows(kd, s, c->stream);
-                if (s->per)
-                    ml_launch(s, true, 0, c->stream);
-                else
-                    mr_select_kernel<<<grid, RSMO_T, 0, c->stream>>>(P);
+                mr_launch_step(s, true, 0, c->stream);
                 mr_launch_rows(kd, s, c->stream);
-                if (s->per)
-                    ml_launch(s, false, 0, c->stream);
-                else
-                    mr_update_kernel<<<grid, RSMO_T, 0, c->stream>>>(P, 0);
+                mr_launch_step(s, false, 0, c->stream);
             }
         }));
         BQ_HIP(hipGetLastError());
@@ -986,7 +1141,8 @@ extern "C" int bq_mrsmo_run(bq_mrsmo *s, int64_t max_steps, int64_t *steps, int 
 
 extern "C" int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out) {
     BQ_ARG(s && out, "NULL argument");
-    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_STATS, "what");
+    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_NU_SCALARS, "what");
+    BQ_ARG(what != BQ_RSMO_NU_SCALARS || s->rule == BQ_RSMO_RULE_NU, "BQ_RSMO_NU_SCALARS needs a BQ_RSMO_RULE_NU solver");
     BQ_ARG(what == BQ_RSMO_STATS || (column >= 0 && column < s->P.k), "column");
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
@@ -1014,10 +1170,26 @@ extern "C" int bq_mrsmo_get(bq_mrsmo *s, int what, int column, double *out) {
     BQ_HIP(hipMemcpyAsync(a.data(), P.alpha + off, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
     BQ_HIP(hipMemcpyAsync(g.data(), P.G + off, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
     BQ_TRY(mr_read_cols(s));
-    bq_rsmo_rho rho;
-    for (size_t t = 0; t < N; ++t) bq_rsmo_rho_add(&rho, s->y[off + t], a[t], s->Cb[off + t], g[t]);
     const mr_col &cc = s->host[(size_t)column];
-    out[0] = bq_rsmo_rho_value(&rho);
+    if (s->rule == BQ_RSMO_RULE_NU) {   // Solver_NU::calculate_rho; BQ_RSMO_SCALARS: the same rho, then the positive side's maxima
+        bq_rsmo_nu_rho nu;
+        for (size_t t = 0; t < N; ++t) bq_rsmo_nu_rho_add(&nu, s->y[off + t], a[t], s->Cb[off + t], g[t]);
+        double r = 0.0;
+        bq_rsmo_nu_rho_value(&nu, &out[0], &r);
+        if (what == BQ_RSMO_NU_SCALARS) {
+            out[1] = r;
+            out[2] = bq_rsmo_nu_gap(cc.gmax, cc.gmax2);
+            out[3] = bq_rsmo_nu_gap(cc.gmaxn, cc.gmaxn2);
+            out[4] = (double)cc.last_i;
+            out[5] = (double)cc.last_j;
+            out[6] = (double)cc.steps;
+            return BQ_OK;
+        }
+    } else {
+        bq_rsmo_rho rho;
+        for (size_t t = 0; t < N; ++t) bq_rsmo_rho_add(&rho, s->y[off + t], a[t], s->Cb[off + t], g[t]);
+        out[0] = bq_rsmo_rho_value(&rho);
+    }
     out[1] = cc.gmax;
     out[2] = cc.gmax2;
     out[3] = (double)cc.last_i;
@@ -1034,7 +1206,7 @@ extern "C" int bq_mrsmo_rows(bq_mrsmo *s, int m, const int64_t *idx, double *out
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     // a call resolves what fits beside the rows the live columns wait for
-    const int batch = (int)std::min<int64_t>(MR_REQ, std::max<int64_t>(1, s->R - P.k));
+    const int batch = (int)std::min<int64_t>(MR_REQ, std::max<int64_t>(1, s->R - (int64_t)P.nreq * P.k));
     std::vector<int> rows((size_t)batch), slots((size_t)batch);
     int rc = BQ_OK;
     for (int q0 = 0; q0 < m && rc == BQ_OK; q0 += batch) {

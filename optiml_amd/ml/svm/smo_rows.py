@@ -223,18 +223,37 @@ class RowSMOBatch:
     (`bq_mrsmo_create_lists`): column c is a `RowSMOClassifier` built on `X[rows[c]], y[rows[c]]` — a class pair of one-vs-one — and
     is solved on the kernel values `K[rows[c]][:, rows[c]]` of the shared quad, its variables the positions of its list: the fit of
     those rows in their order.  Kernel rows are made and cached whole, so a row serves every column that lists it; the select and
-    update kernels run over the lists only.  Each column holds m_c-long alphas and gradient afterwards."""
+    update kernels run over the lists only.  Each column holds m_c-long alphas and gradient afterwards.
+
+    `alpha0` (one start per column, inside its boxes) and `rule` ('plain': libsvm's Solver; 'nu': Solver_NU, which keeps the mass of
+    each sign) reach the general entries (`bq_mrsmo_create_general` / `_create_lists_general`), in both forms; `GeneralRowSMO`
+    columns (nu_rows.py) bring their own start and rule.  The start gradient of every column is made from ONE pass over the rows
+    that carry a nonzero start in any column.  After `minimize()` every column has `alphas`, `gradient`, `rho`, `iter`, `status`,
+    `violation` (the stop measure at the last selection) and, for 'nu', `r`."""
     run_steps = RowSMO.run_steps
 
-    def __init__(self, columns, cache_rows=0, ctx=None, rows=None):
+    def __init__(self, columns, cache_rows=0, ctx=None, rows=None, alpha0=None, rule='plain'):
         first = columns[0]
         if any(type(c) is not type(first) or c.quad is not first.quad for c in columns):
             raise TypeError('the columns of a batch are solvers of one type on one quad')
-        if not (cache_rows == 0 or cache_rows >= 2 * len(columns)):
-            raise ValueError('cache_rows must be 0 (as many as fit) or >= 2 per column')
+        if rule not in ('plain', 'nu'):
+            raise ValueError(f'unknown rule {rule}')
+        general = hasattr(first, 'alpha0')   # GeneralRowSMO columns: the dual as data, with its own start and rule
+        if general:
+            rule = first.rule if rule == 'plain' else rule
+            if any(c.rule != rule for c in columns):
+                raise ValueError('the columns of a batch run under one rule')
+            alpha0 = [c.alpha0 for c in columns] if alpha0 is None else alpha0
+        held = 3 if rule == 'nu' else 2   # rows a step holds per column
+        if not (cache_rows == 0 or cache_rows >= held * len(columns)):
+            raise ValueError(f'cache_rows must be 0 (as many as fit) or >= {held} per column')
+        if rule == 'nu' and len(columns) > 512:
+            raise ValueError('a Solver_NU batch holds at most 512 columns')
+        if alpha0 is not None and len(alpha0) != len(columns):
+            raise ValueError('alpha0 must hold one start per column')
         if rows is not None:
-            if not isinstance(first, RowSMOClassifier):
-                raise TypeError('row-list columns are RowSMOClassifier duals (N = m); the 2n form covers all rows')
+            if not (isinstance(first, RowSMOClassifier) or general):
+                raise TypeError('row-list columns are RowSMOClassifier or GeneralRowSMO duals (N = m); the 2n form covers all rows')
             if len(rows) != len(columns) or any(len(r) != len(c.y) for r, c in zip(rows, columns)):
                 raise ValueError('rows must hold one list per column, as long as the column')
             rows = [np.ascontiguousarray(r, dtype=np.int32) for r in rows]
@@ -242,22 +261,41 @@ class RowSMOBatch:
         self.rows = rows
         self.cache_rows = int(cache_rows)
         self.ctx = ctx
+        self.rule = rule
+        self.alpha0 = None if alpha0 is None else [np.ascontiguousarray(a, dtype=float) for a in alpha0]
+        self.max_steps = int(getattr(first, 'max_steps', 0))
 
     def _create(self, lib, dev, h):
         """create the device solver of the columns into `h`; returns every column's number of variables"""
         cols, k = self.columns, len(self.columns)
         duals = [c._dual() for c in cols]
+        general = self.alpha0 is not None or self.rule == 'nu'   # anything else keeps the entries (and launches) it always had
+        rule = _lib.RSMO_RULE_NU if self.rule == 'nu' else _lib.RSMO_RULE_PLAIN
+        if general:
+            duals = [d + (np.zeros(len(d[0])) if self.alpha0 is None else self.alpha0[c],) for c, d in enumerate(duals)]
+            if any(len(d[3]) != len(d[0]) for d in duals):
+                raise ValueError('a start is as long as its column')
         if self.rows is None:
-            signs, lin, boxes = (np.ascontiguousarray(np.stack(part), dtype=float) for part in zip(*duals))
-            _lib.check(lib.bq_mrsmo_create(dev.handle, k, signs.shape[1], _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes),
-                                           float(cols[0].tol), 0, self.cache_rows, C.byref(h)))
+            signs, lin, boxes, *start = (np.ascontiguousarray(np.stack(part), dtype=float) for part in zip(*duals))
+            if general:
+                _lib.check(lib.bq_mrsmo_create_general(dev.handle, rule, k, signs.shape[1], _lib.ptr(signs), _lib.ptr(lin),
+                                                       _lib.ptr(boxes), _lib.ptr(start[0]), float(cols[0].tol), self.max_steps,
+                                                       self.cache_rows, C.byref(h)))
+            else:
+                _lib.check(lib.bq_mrsmo_create(dev.handle, k, signs.shape[1], _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes),
+                                               float(cols[0].tol), 0, self.cache_rows, C.byref(h)))
             return [signs.shape[1]] * k
-        signs, lin, boxes = (np.ascontiguousarray(np.concatenate(part), dtype=float) for part in zip(*duals))
+        signs, lin, boxes, *start = (np.ascontiguousarray(np.concatenate(part), dtype=float) for part in zip(*duals))
         offsets = np.concatenate(([0], np.cumsum([len(r) for r in self.rows]))).astype(np.int64)
         rows = np.ascontiguousarray(np.concatenate(self.rows), dtype=np.int32)
-        _lib.check(lib.bq_mrsmo_create_lists(dev.handle, k, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _lib.iptr(rows),
-                                             _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes), float(cols[0].tol), 0, self.cache_rows,
-                                             C.byref(h)))
+        optr = offsets.ctypes.data_as(C.POINTER(C.c_int64))
+        if general:
+            _lib.check(lib.bq_mrsmo_create_lists_general(dev.handle, rule, k, optr, _lib.iptr(rows), _lib.ptr(signs), _lib.ptr(lin),
+                                                         _lib.ptr(boxes), _lib.ptr(start[0]), float(cols[0].tol), self.max_steps,
+                                                         self.cache_rows, C.byref(h)))
+        else:
+            _lib.check(lib.bq_mrsmo_create_lists(dev.handle, k, optr, _lib.iptr(rows), _lib.ptr(signs), _lib.ptr(lin), _lib.ptr(boxes),
+                                                 float(cols[0].tol), 0, self.cache_rows, C.byref(h)))
         return [len(r) for r in self.rows]
 
     def minimize(self):
@@ -276,10 +314,15 @@ class RowSMOBatch:
             st = np.empty(3)
             _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
             for c, col in enumerate(cols):
-                alpha, grad, sc = np.empty(sizes[c]), np.empty(sizes[c]), np.empty(6)
-                for what, out in ((_lib.RSMO_ALPHAS, alpha), (_lib.RSMO_GRADIENT, grad), (_lib.RSMO_SCALARS, sc)):
+                nu = self.rule == 'nu'
+                alpha, grad, sc = np.empty(sizes[c]), np.empty(sizes[c]), np.empty(7 if nu else 6)
+                for what, out in ((_lib.RSMO_ALPHAS, alpha), (_lib.RSMO_GRADIENT, grad),
+                                  (_lib.RSMO_NU_SCALARS if nu else _lib.RSMO_SCALARS, sc)):
                     _lib.check(lib.bq_mrsmo_get(h, what, c, _lib.ptr(out)))
                 col._take(alpha, grad, sc)
+                col.violation = max(sc[2], sc[3]) if nu else sc[1] + sc[2]
+                if nu:
+                    col.r = sc[1]
                 col.iter = int(steps[c])
                 col.status = _lib.RSMO_STATUS[int(fin[c])]
                 col._finished(st)

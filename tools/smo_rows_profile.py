@@ -275,6 +275,82 @@ def cmd_ovo_rate(args):
     print(json.dumps(rec))
 
 
+def _nu_ovo_model(route):
+    from optiml_amd.ml.svm import RowNuSVC, RowOneVsOneNuSVC
+    from optiml_amd.ml.svm.kernels import GaussianKernel
+    return (RowOneVsOneNuSVC if route == 'rows' else RowNuSVC)(kernel=GaussianKernel(GAMMA10), nu=0.2, tol=TOL)
+
+
+def cmd_nu_ovo(args):
+    """one one-vs-one nu-SVC fit (nu = 0.2) of the 10-class blobs (45 pairs) in this (fresh) process after a warm-up fit of n = 4000 on
+    the same route: rows = RowOneVsOneNuSVC (one bq_mrsmo_create_lists_general solver for all pairs), pairs = one RowNuSVC.fit per
+    pair on the pair's rows (the only route without this solver)"""
+    from optiml_amd.ml.svm.onevsone import ovo_pairs, pair_problem
+
+    def fit(X, y):
+        if args.route == 'rows':
+            return _nu_ovo_model('rows').fit(X, y).estimators_
+        return [_nu_ovo_model('pairs').fit(X[r], (yp > 0).astype(int)) for r, yp in (pair_problem(y, i, j) for i, j in ovo_pairs(10))]
+    fit(*_data10(4000))
+    X, y = _data10(args.n)
+    t0 = time.perf_counter()
+    ests = fit(X, y)
+    wall = time.perf_counter() - t0
+    steps = [int(e.n_iter_) for e in ests]
+    stats = [ests[0].cache_stats_] if args.route == 'rows' else [e.cache_stats_ for e in ests]
+    rec = {'what': 'one-vs-one nu-SVC fit, 10 classes, 45 pairs, nu = 0.2', 'n': args.n, 'd': D, 'gamma': GAMMA10, 'route': args.route,
+           'tol': TOL, 'wall_s': wall, 'includes': 'problem build(s) + start + solve + read-back', 'steps_per_pair': steps,
+           'steps_total': sum(steps), 'status': sorted(set(e.status_ for e in ests)), 'hits': sum(s['hits'] for s in stats),
+           'misses': sum(s['misses'] for s in stats), 'cache_rows': stats[0]['cache_rows'],
+           'rows_made_note': 'misses = kernel rows made; route rows counts the rows of the start among its requests, route pairs '
+                             'makes its start gradient by one streamed product per pair instead'}
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
+def cmd_nu_ovo_rate(args):
+    """the start (create: the rows with a nonzero start through the cache, folded into all 45 pair columns) and then K Solver_NU
+    steps of all columns on one streamed problem, no verdict: bq_mrsmo_create_lists_general with libsvm's nu-SVC starts"""
+    import ctypes as C
+    from optiml_amd import _lib
+    from optiml_amd.ml.svm.kernels import GaussianKernel
+    from optiml_amd.ml.svm.nu_rows import nu_svc_start
+    from optiml_amd.ml.svm.onevsone import ovo_pairs, pair_problem
+    from optiml_amd.opti import KernelQuadratic
+    lib = _lib.load()
+    X, y = _data10(args.n)
+    problems = [pair_problem(y, i, j) for i, j in ovo_pairs(10)]
+    quad = KernelQuadratic(X, np.zeros(args.n), 'plain', GaussianKernel(GAMMA10), storage='stream')
+    dev = quad.device_problem().handle
+    offsets = np.concatenate(([0], np.cumsum([len(r) for r, _ in problems]))).astype(np.int64)
+    rows = np.ascontiguousarray(np.concatenate([r for r, _ in problems]), dtype=np.int32)
+    signs = np.ascontiguousarray(np.concatenate([yp for _, yp in problems]))
+    start = np.ascontiguousarray(np.concatenate([nu_svc_start(yp, 0.2) for _, yp in problems]))
+    ones, h, st = np.ones(len(signs)), C.c_void_p(), np.empty(3)
+    t0 = time.perf_counter()
+    _lib.check(lib.bq_mrsmo_create_lists_general(dev, _lib.RSMO_RULE_NU, 45, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _lib.iptr(rows),
+                                                 _lib.ptr(signs), _lib.ptr(0 * ones), _lib.ptr(ones), _lib.ptr(start), TOL, 0, 0, C.byref(h)))
+    create = time.perf_counter() - t0
+    _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+    before = st.copy()
+    steps, fin = (C.c_int64 * 45)(), (C.c_int * 45)()
+    _lib.check(lib.bq_mrsmo_run(h, 8, steps, fin))   # warm
+    t0 = time.perf_counter()
+    _lib.check(lib.bq_mrsmo_run(h, args.steps, steps, fin))
+    wall = time.perf_counter() - t0
+    _lib.check(lib.bq_mrsmo_get(h, _lib.RSMO_STATS, 0, _lib.ptr(st)))
+    lib.bq_mrsmo_destroy(h)
+    quad.release()
+    rec = {'what': 'start and rate of 45 Solver_NU pair columns (NOT a fit)', 'n': args.n, 'd': D, 'window_steps': args.steps,
+           'positions': int(len(signs)), 'start_rows_union': int(len(np.unique(rows[start != 0]))), 'create_s': create,
+           'create_includes': 'allocation, uploads, the start (its rows and its kernels), QD, the first selection',
+           'requests_at_create': int(before[0] + before[1]), 'misses_at_create': int(before[1]), 'cache_rows': int(st[2]),
+           'finished': int(sum(fin)), 'window_s': wall, 'per_step_of_all_pairs_us': 1e6 * wall / args.steps,
+           'hits_in_window': int(st[0] - before[0]), 'misses_in_window': int(st[1] - before[1])}
+    json.dump(rec, open(args.json, 'w'), indent=1)
+    print(json.dumps(rec))
+
+
 def cmd_rate(args):
     import ctypes as C
     from optiml_amd import _lib
@@ -562,9 +638,20 @@ def main():
         p.add_argument('--route', default='rows', choices=['rows', 'pairs'])
         p.add_argument('--json', required=True)
         p.set_defaults(fn=fn)
+    p = sub.add_parser('nu-ovo')
+    p.add_argument('--n', type=int, required=True)
+    p.add_argument('--route', default='rows', choices=['rows', 'pairs'])
+    p.add_argument('--json', required=True)
+    p.set_defaults(fn=cmd_nu_ovo)
+    p = sub.add_parser('nu-ovo-rate')
+    p.add_argument('--n', type=int, required=True)
+    p.add_argument('--steps', type=int, default=2000)
+    p.add_argument('--json', required=True)
+    p.set_defaults(fn=cmd_nu_ovo_rate)
     p = sub.add_parser('kernels')
     p.add_argument('--trace', required=True)
-    p.add_argument('--kernels', default='mr_rows_kernel,mr_select_kernel,mr_update_kernel,ml_select_kernel,ml_update_kernel,'
+    p.add_argument('--kernels', default='mr_rows_kernel,mr_select_kernel,mr_update_kernel,ml_select_kernel,ml_update_kernel,ml_nu_select_kernel,'
+                   'ml_nu_update_kernel,ml_start_kernel,mr_nu_select_kernel,mr_nu_update_kernel,mr_start_kernel,'
                    'rsmo_select_kernel,rsmo_update_kernel')
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_kernels)
