@@ -70,6 +70,7 @@ extern "C" {
 /* (still 3: bq_mrsmo_create / _run / _get / _rows / _destroy were added; nothing existing changed) */
 /* (still 3: bq_mrsmo_create_lists was added; nothing existing changed) */
 /* (still 3: bq_mrsmo_create_general / _create_lists_general were added, bq_mrsmo_get takes BQ_RSMO_NU_SCALARS; nothing existing changed) */
+/* (still 3: bq_rsmo_set_shrinking and BQ_RSMO_SHRINK_STATS were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -792,7 +793,7 @@ int bq_msmo_svc_heldout(bq_msmo *s, int nsets, const int *set_of, const unsigned
                         int64_t *n_neg, int *flags, double *dec);
 
 /* ---- panel-free SMO: libsvm's WSS2 decomposition on kernel rows made on demand (bq_rsmo.hip) ---------------------------------
- * libsvm's Solver::Solve without shrinking (svm.cpp; the scalar rules are csrc/bq_rsmo_step.h, the NumPy restatement
+ * libsvm's Solver::Solve, shrinking opt-in (svm.cpp; the scalar rules are csrc/bq_rsmo_step.h, the NumPy restatement
  * tests/smo_rows_reference.py) on  min 1/2 a'Qa + p'a, y'a = 0, 0 <= a_t <= C_t:
  *   BQ_SVC  Q = diag(y) K diag(y), p = -1;   BQ_SVR  2n variables, Q = [[K, -K], [-K, K]], p = [epsilon - y; epsilon + y], signs
  *   [+1 ..; -1 ..], variables t and t + n share kernel row t.
@@ -814,7 +815,9 @@ enum { BQ_RSMO_ALPHAS = 0,    /* n (BQ_SVC) or [alpha; alpha*] 2n (BQ_SVR) */
        BQ_RSMO_GRADIENT = 1,  /* n | 2n */
        BQ_RSMO_SCALARS = 2,   /* 6: rho, Gmax, Gmax2 (of the last selection), last i, last j (of the last update; -1: none), steps */
        BQ_RSMO_STATS = 3,     /* 3: cache hits, misses, cache_rows */
-       BQ_RSMO_NU_SCALARS = 4 /* 7, BQ_RSMO_RULE_NU only: rho, r, Gmaxp + Gmaxp2, Gmaxn + Gmaxn2, last i, last j, steps */ };
+       BQ_RSMO_NU_SCALARS = 4, /* 7, BQ_RSMO_RULE_NU only: rho, r, Gmaxp + Gmaxp2, Gmaxn + Gmaxn2, last i, last j, steps */
+       BQ_RSMO_SHRINK_STATS = 5 /* 4, after bq_rsmo_set_shrinking only: the active count now, the smallest reached, shrink passes,
+                                   gradient reconstructions */ };
 int bq_rsmo_create(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
                    int64_t cache_rows, bq_rsmo **out);
 /* The general dual  min 1/2 a'Qa + lin'a,  0 <= a_v <= boxes_v,  Q_uv = s_u s_v K_row(u) row(v), from a start alpha0:
@@ -835,6 +838,23 @@ int bq_rsmo_create(bq_problem *p, int task, const double *y, const double *Cw, d
 enum { BQ_RSMO_RULE_PLAIN = 0, BQ_RSMO_RULE_NU = 1 };
 int bq_rsmo_create_general(bq_problem *p, int rule, int64_t N, const double *signs, const double *lin, const double *boxes,
                            const double *alpha0, double tol, int64_t max_steps, int64_t cache_rows, bq_rsmo **out);
+/* Shrinking (libsvm's do_shrinking; opt-in, BQ_RSMO_RULE_PLAIN only; csrc/bq_rsmo_shrink.h).  Every min(N, every) steps (every = 0:
+ * libsvm's 1000) the variables at a bound that cannot become violators (be_shrunk, strict inequalities, on the Gmax1 / Gmax2 of the
+ * active set) leave an ascending active list kept on the device; kernel rows, the selection and the gradient update then run on the
+ * list only.  The control flow is Solver::Solve's: the first shrink pass with Gmax1 + Gmax2 <= 10 tol reconstructs the gradient and
+ * shrinks from everything; a stop test that holds on a shrunk list reconstructs, makes everything active and selects again (finished
+ * if it still holds, else a shrink pass after the next step); a run that ends shrunk reconstructs before rho, so BQ_RSMO_GRADIENT of
+ * a finished run is the full gradient (during a run its inactive entries are stale).  A reconstruction is ONE streamed Gram product
+ * (G_v = lin_v + s_v (K b)_row(v) at the inactive variables) in place of libsvm's G_bar: libsvm's values up to rounding.  Until the
+ * first reconstruction the pairs, alpha and the active entries of G have the bits of the run without shrinking; ties go to the larger
+ * variable index (libsvm: to the later position of its permuted order).  A cached row made on a shrunk list serves the steps' requests
+ * until the next reconstruction; bq_rsmo_rows still returns whole rows: a request for such a row is a miss that makes it whole in its
+ * slot.  BQ_RSMO_STATS counts two requests per step, plus one for every stop that a selection without a partner raises on a shrunk
+ * list (the row asked before it is asked again after the reconstruction).  bq_rsmo_run may enqueue fewer launches than max_steps
+ * steps when the device waits for a reconstruction, and takes them up again in the same call.
+ * BQ_ERR_BADARG: every < 0, a BQ_RSMO_RULE_NU solver, a solver that has taken a step or has shrinking set already.  A solver on which
+ * this is never called runs the kernels and launches it always ran. */
+int bq_rsmo_set_shrinking(bq_rsmo *s, int64_t every);
 int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished);
 int bq_rsmo_get(bq_rsmo *s, int what, double *out);
 int bq_rsmo_rows(bq_rsmo *s, int m, const int64_t *idx, double *out);

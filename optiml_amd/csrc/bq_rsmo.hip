@@ -50,6 +50,11 @@ struct rsmo_ctl {
     int i2, slot_2, hit_2;
     int slot_u;              // the slot of the row of the i that the select kernel paired with j (slot_i or slot_2)
     double gmaxn, gmaxn2;
+    // bq_rsmo_set_shrinking (bq_rsmo_shrink.h): the active list's length and buffer, the cache's epoch, what the device waits for
+    int nact, cur, epoch, pause, stop_pending, unshrunk;
+    int scatter, nact_new;   // between the two launches of a shrink pass
+    int min_act;
+    long long nshrink;
 };
 
 struct rsmo_dev {
@@ -520,6 +525,8 @@ __global__ __launch_bounds__(RSMO_T) void rsmo_fill_kernel(rsmo_dev P, int64_t r
 
 }   // namespace
 
+#include "bq_rsmo_shrink.h"   // the active list: select / update over positions, the shrink pass, reconstruction
+
 struct bq_rsmo {
     bq_problem *p = nullptr;
     int rule = BQ_RSMO_RULE_PLAIN;
@@ -528,6 +535,13 @@ struct bq_rsmo {
     unsigned int nblk = 0;
     std::vector<double> y, Cb;   // host copies for calculate_rho
     rsmo_ctl host = {};
+    // bq_rsmo_set_shrinking
+    bool shrinking = false;
+    rsmo_shr S = {};
+    std::vector<double> lin;         // the linear term, for the device copy shrinking keeps
+    long long period = 0;            // libsvm's min(N, every)
+    long long next_shrink = 0;       // a shrink pass runs before the step that starts from this many steps
+    long long reconstructions = 0;
 };
 
 extern "C" int bq_rsmo_destroy(bq_rsmo *s) {
@@ -632,6 +646,7 @@ extern "C" int bq_rsmo_create_general(bq_problem *p, int rule, int64_t N, const 
     // host images of the dual for calculate_rho
     s->y.assign(signs, signs + N);
     s->Cb.assign(boxes, boxes + N);
+    s->lin.assign(lin, lin + N);
     auto fail = [&](hipError_t e, const char *what) {
         bq_set_error("%s failed: %s", what, hipGetErrorString(e));
         hipStreamSynchronize(c->stream);
@@ -751,12 +766,139 @@ extern "C" int bq_rsmo_create(bq_problem *p, int task, const double *y, const do
     return bq_rsmo_create_general(p, BQ_RSMO_RULE_PLAIN, N, signs.data(), lin.data(), boxes.data(), zero.data(), tol, 0, cache_rows, out);
 }
 
+// ---- shrinking: the host side of bq_rsmo_shrink.h ----------------------------------------------------------------------------------------
+static unsigned int rsmo_grid(long long count, int per) { return (unsigned int)std::max<long long>(1, (count + per - 1) / per); }
+
+extern "C" int bq_rsmo_set_shrinking(bq_rsmo *s, int64_t every) {
+    BQ_ARG(s, "NULL argument");
+    BQ_ARG(every >= 0, "every must be >= 0 (0: libsvm's 1000)");
+    BQ_ARG(s->rule == BQ_RSMO_RULE_PLAIN, "shrinking is built for BQ_RSMO_RULE_PLAIN (libsvm's Solver), not for Solver_NU's rule");
+    BQ_ARG(s->host.steps == 0 && !s->shrinking, "shrinking is set once, before the first step");
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    const rsmo_dev &P = s->P;
+    rsmo_shr &S = s->S;
+    const size_t N = (size_t)P.N, padded = (N + RSMO_LW - 1) / RSMO_LW * RSMO_LW, nwg = rsmo_grid((long long)N, RSMO_T);
+    hipError_t e = s->mem.dev(&S.act[0], padded);
+    if (e == hipSuccess) e = s->mem.dev(&S.act[1], padded);
+    if (e == hipSuccess) e = s->mem.dev(&S.lin, N);
+    if (e == hipSuccess) e = s->mem.dev(&S.wg_count, nwg);
+    if (e == hipSuccess) e = s->mem.dev(&S.wg_off, nwg);
+    e = bq_dev_zeroed(e, s->mem, &S.slot_epoch, (size_t)P.R, c->stream);   // what the cache holds by now are full rows
+    e = bq_dev_zeroed(e, s->mem, &S.flag, N, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(S.lin, s->lin.data(), sizeof(double) * N, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        rsmo_all_active_kernel<<<(unsigned int)nwg, RSMO_T, 0, c->stream>>>(P, S, 1);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        bq_set_error("the active list failed: %s", hipGetErrorString(e));
+        hipStreamSynchronize(c->stream);
+        return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    BQ_TRY(rsmo_read_ctl(s));
+    s->period = std::min<long long>((long long)P.N, every > 0 ? (long long)every : 1000LL);
+    s->next_shrink = s->period;
+    s->shrinking = true;
+    return BQ_OK;
+}
+
+static void rsmo_launch_shrink(bq_rsmo *s, long long count) {
+    const unsigned int grid = rsmo_grid(count, RSMO_T);
+    rsmo_shrink_count_kernel<<<grid, RSMO_T, 0, s->p->ctx->stream>>>(s->P, s->S);
+    rsmo_shrink_scatter_kernel<<<grid, RSMO_T, 0, s->p->ctx->stream>>>(s->P, s->S);
+}
+
+// libsvm's reconstruct_gradient, then active_size = l.  G_v at the inactive variables is lin_v + s_v (K b)_row(v), b the fold of
+// s o alpha onto rows, K b ONE streamed Gram product of the problem (the product of the start gradient): it replaces libsvm's G_bar,
+// which needs a full-width row whenever a variable reaches or leaves its upper bound.  The result differs from libsvm's (a sum of
+// alpha_j Q_j over the free variables, plus G_bar) in rounding only: the summation order is the product's.  The device waits
+// (`pause`, `finished`) while this runs; the control block has just been read.
+static int rsmo_reconstruct(bq_rsmo *s) {
+    const rsmo_dev &P = s->P;
+    bq_problem *p = s->p;
+    bq_ctx *c = p->ctx;
+    const unsigned int all = rsmo_grid(P.N, RSMO_T);
+    if (s->host.nact < P.N) {
+        std::vector<double> a((size_t)P.N), b((size_t)P.n);
+        BQ_HIP(hipMemcpyAsync(a.data(), P.alpha, sizeof(double) * (size_t)P.N, hipMemcpyDeviceToHost, c->stream));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+        for (int64_t t = 0; t < P.n; ++t) {
+            double acc = s->y[t] * a[t];
+            if (P.N > P.n) acc = acc + s->y[t + P.n] * a[t + P.n];
+            b[t] = acc;
+        }
+        BQ_HIP(hipMemsetAsync(p->w, 0, sizeof(double) * (size_t)p->ld, c->stream));
+        BQ_HIP(hipMemcpyAsync(p->w, b.data(), sizeof(double) * (size_t)P.n, hipMemcpyHostToDevice, c->stream));
+        BQ_TRY(bq_panel_product(p, false, p->w, nullptr));
+        const int stamp = (int)(s->reconstructions + 1);
+        rsmo_mark_kernel<<<rsmo_grid(s->host.nact, RSMO_T), RSMO_T, 0, c->stream>>>(P, s->S, stamp);
+        rsmo_rebuild_kernel<<<all, RSMO_T, 0, c->stream>>>(P, s->S, p->s, stamp);
+        BQ_HIP(hipGetLastError());
+        BQ_HIP(hipStreamSynchronize(c->stream));   // b is read
+        s->reconstructions += 1;
+    }
+    rsmo_all_active_kernel<<<all, RSMO_T, 0, c->stream>>>(P, s->S, 0);
+    BQ_HIP(hipGetLastError());
+    s->host.nact = (int)P.N;
+    return BQ_OK;
+}
+
+// bq_rsmo_run with shrinking: the steps of the call in batches that end where the device waits for a reconstruction
+static int rsmo_run_shrinking(bq_rsmo *s, int64_t max_steps) {
+    bq_ctx *c = s->p->ctx;
+    const rsmo_dev &P = s->P;
+    const rsmo_shr &S = s->S;
+    const long long goal = s->host.steps + max_steps;
+    while (!s->host.finished && s->host.steps < goal) {
+        const long long from = s->host.steps;
+        const unsigned int grid = rsmo_grid(s->host.nact, RSMO_LTILE);
+        BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
+            using KD = decltype(kd);
+            for (long long at = from; at < goal; ++at) {
+                if (at == s->next_shrink) {
+                    rsmo_launch_shrink(s, s->host.nact);
+                    s->next_shrink = at + s->period;
+                }
+                rsmo_lselect_kernel<KD::kind, KD::deg><<<grid, RSMO_T, 0, c->stream>>>(P, S);
+                rsmo_lupdate_kernel<KD::kind, KD::deg><<<grid, RSMO_T, 0, c->stream>>>(P, S, 0, at + 1 == s->next_shrink ? 1 : 0);
+            }
+        }));
+        BQ_HIP(hipGetLastError());
+        BQ_TRY(rsmo_read_ctl(s));
+        while (s->host.pause != RSMO_PAUSE_NONE) {
+            const long long at = s->host.steps;
+            const int why = s->host.pause;
+            BQ_TRY(rsmo_reconstruct(s));
+            if (why == RSMO_PAUSE_UNSHRINK) {   // do_shrinking goes on with the Gmax values taken before
+                rsmo_launch_shrink(s, P.N);
+                s->next_shrink = at + s->period;
+            } else {
+                s->next_shrink = at + 1;   // libsvm's counter = 1: a shrink pass after the next step
+            }
+            BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
+                using KD = decltype(kd);
+                rsmo_lupdate_kernel<KD::kind, KD::deg><<<rsmo_grid(P.N, RSMO_LTILE), RSMO_T, 0, c->stream>>>(P, S, 1, 0);
+            }));
+            BQ_HIP(hipGetLastError());
+            BQ_TRY(rsmo_read_ctl(s));
+        }
+    }
+    if (s->host.finished && s->host.nact < P.N) {   // stopped at the cap on a shrunk list: the full gradient before rho
+        BQ_TRY(rsmo_reconstruct(s));
+        BQ_HIP(hipStreamSynchronize(c->stream));
+    }
+    return BQ_OK;
+}
+
 extern "C" int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished) {
     BQ_ARG(s && steps && finished, "NULL argument");
     BQ_ARG(max_steps > 0, "max_steps must be > 0");
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
-    if (!s->host.finished) {
+    if (s->shrinking) {
+        BQ_TRY(rsmo_run_shrinking(s, max_steps));
+    } else if (!s->host.finished) {
         const rsmo_dev &P = s->P;
         BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
             for (int64_t k = 0; k < max_steps; ++k) {
@@ -774,8 +916,9 @@ extern "C" int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *f
 
 extern "C" int bq_rsmo_get(bq_rsmo *s, int what, double *out) {
     BQ_ARG(s && out, "NULL argument");
-    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_NU_SCALARS, "what");
+    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_SHRINK_STATS, "what");
     BQ_ARG(what != BQ_RSMO_NU_SCALARS || s->rule == BQ_RSMO_RULE_NU, "BQ_RSMO_NU_SCALARS needs a BQ_RSMO_RULE_NU solver");
+    BQ_ARG(what != BQ_RSMO_SHRINK_STATS || s->shrinking, "BQ_RSMO_SHRINK_STATS needs bq_rsmo_set_shrinking");
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     const rsmo_dev &P = s->P;
@@ -789,6 +932,13 @@ extern "C" int bq_rsmo_get(bq_rsmo *s, int what, double *out) {
         out[0] = (double)s->host.hits;
         out[1] = (double)s->host.misses;
         out[2] = (double)P.R;
+        return BQ_OK;
+    }
+    if (what == BQ_RSMO_SHRINK_STATS) {
+        out[0] = (double)s->host.nact;
+        out[1] = (double)s->host.min_act;
+        out[2] = (double)s->host.nshrink;
+        out[3] = (double)s->reconstructions;
         return BQ_OK;
     }
     // calculate_rho in libsvm's order, on the host: one pass over the two vectors, once per fit
@@ -833,7 +983,10 @@ extern "C" int bq_rsmo_rows(bq_rsmo *s, int m, const int64_t *idx, double *out) 
     BQ_HIP(hipSetDevice(c->device));
     for (int q = 0; q < m; ++q) {
         const int64_t r = idx[q];
-        rsmo_request_kernel<<<1, RSMO_T, 0, c->stream>>>(P, r);
+        if (s->shrinking)
+            rsmo_lrequest_kernel<<<1, RSMO_T, 0, c->stream>>>(P, s->S, r);
+        else
+            rsmo_request_kernel<<<1, RSMO_T, 0, c->stream>>>(P, r);
         BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
             rsmo_fill_kernel<decltype(kd)::kind, decltype(kd)::deg><<<s->nblk, RSMO_T, 0, c->stream>>>(P, r);
         }));

@@ -1,5 +1,5 @@
 // The scalar rules of the row-based SMO (bq_rsmo.hip), ONE definition for the device and for the host check
-// (tests/c/rsmo_step_check.cpp, run by tests/test_rsmo_step_host.py): libsvm's Solver without shrinking (svm.cpp: select_working_set,
+// (tests/c/rsmo_step_check.cpp, run by tests/test_rsmo_step_host.py): libsvm's Solver (svm.cpp: select_working_set, be_shrunk,
 // the two-variable update of Solve, calculate_rho), restated on
 //     min 1/2 a'Qa + p'a,  y'a = 0,  0 <= a_t <= C_t,   Q_st = y_s y_t K_st,
 // plus the victim rule of the row cache; and, for the general entry (bq_rsmo_create_general; host check tests/c/rsmo_nu_step_check.cpp,
@@ -66,6 +66,21 @@ BQ_RSMO_FN double bq_rsmo_score(double gmax, double y_t, double g_t, double qd_i
 BQ_RSMO_FN bool bq_rsmo_stop(double gmax, double gmax2, double tol) {
     const double gap = gmax + gmax2;
     return gap < tol;
+}
+
+// ---- shrinking (svm.cpp: Solver::be_shrunk, do_shrinking) -------------------------------------------------------------------------
+// A variable at a bound leaves the active set when its gradient lies strictly beyond the maximum of the set it could violate with:
+// gmax1 the maximum of -y G over I_up, gmax2 of y G over I_low, both over the active set.  Free variables stay.
+BQ_RSMO_FN bool bq_rsmo_be_shrunk(double y, double a, double C, double G, double gmax1, double gmax2) {
+    if (a >= C) return y > 0.0 ? -G > gmax1 : -G > gmax2;
+    if (a <= 0.0) return y > 0.0 ? G > gmax2 : G > gmax1;
+    return false;
+}
+// do_shrinking's one-time "unshrink": the first pass that sees Gmax1 + Gmax2 <= 10 tol reconstructs the gradient first
+BQ_RSMO_FN bool bq_rsmo_unshrink(double gmax1, double gmax2, double tol) {
+    const double gap = gmax1 + gmax2;
+    const double limit = tol * 10.0;
+    return gap <= limit;
 }
 
 // ---- the two-variable update, both clipping cascades in libsvm's order -----------------------------------------------------------------

@@ -212,6 +212,11 @@ class SVM(BaseEstimator, ABC):
     def _is_smo(self):
         return self.dual and (self.optimizer == 'smo' or self.optimizer is SMO)
 
+    # libsvm's shrinking for the panel-free SMO (`RowSMO(shrinking=...)`, smo_rows.py): False, True (libsvm's interval, 1000 steps) or
+    # the interval.  A class-or-instance attribute like `tune_placement`, since the constructors keep the reference's arguments; read
+    # on the optimizer='smo', storage='stream' route only (the meta-estimators' batch_smo='rows' route does not shrink).
+    shrinking = False
+
     def _smo_solver(self, resident, rows, obj, *args):
         """The SMO branch of `fit`: the walker on the resident panel (`resident`), or, with storage='stream', libsvm's decomposition
         on kernel rows made on demand (`rows`; single-rank contexts).  The two read `tol` differently: the walker compares every
@@ -221,7 +226,7 @@ class SVM(BaseEstimator, ABC):
             return resident(obj, *args).minimize()
         if get_context().world != 1:
             raise NotImplementedError("optimizer='smo' with storage='stream' runs on a single-rank context")
-        opt = rows(obj, *args).minimize()
+        opt = rows(obj, *args, shrinking=self.shrinking).minimize()
         if opt.status == 'stopped':
             import warnings
             warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)

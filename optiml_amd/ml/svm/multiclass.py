@@ -87,7 +87,7 @@ class OneVsRestSVC(_MultiClassSVC):
 
     `batch_smo='rows'` (opt-in; optimizer='smo', storage='stream'): the classes are solved together by the batched panel-free SMO
     (`RowSMOBatch`, `bq_mrsmo_*`) — one cache of kernel rows for all classes, missing rows made 16 at a time — instead of one
-    `RowSMOClassifier` fit per class; `rows_` says so.  Every estimator has the attributes its own fit sets; prediction is unchanged.
+    `RowSMOClassifier` fit per class; `rows_` says so (the batched solver does not shrink: the attribute `shrinking` is ignored on that route).  Every estimator has the attributes its own fit sets; prediction is unchanged.
     """
     batch_smo = None
 

@@ -19,7 +19,9 @@ that carry a start.  `RowOneVsOneNuSVC` solves every class pair as one row-list 
 `row_one_class_nu_path` solve every parameter as one full column.  A column's bits do not depend on the batch it runs in; they are
 NOT the bits of the single fit, whose start gradient is a streamed product and whose rows are fma chains.
 
-Not here: shrinking, the Laplacian kernel (a streamed problem refuses it).
+Shrinking is opt-in for the one dual here that runs under libsvm's plain Solver (`RowOneClassSVM(shrinking=True)`); Solver_NU's own
+shrink rule is not built, so `RowNuSVC` / `RowNuSVR` and the batched paths run without.  Not here: the Laplacian kernel (a streamed
+problem refuses it).
 """
 import ctypes as C
 import warnings
@@ -89,13 +91,15 @@ class GeneralRowSMO(RowSMO):
     `alpha0`, under libsvm's Solver (`rule` 'plain') or Solver_NU ('nu').  After `minimize()`: `alphas`, `gradient`, `rho`, `iter`,
     `status`, `cache_stats`, `violation` (the stop measure at the last selection), and for 'nu' `r`."""
 
-    def __init__(self, quad, X, signs, lin, boxes, alpha0, rule, tol=1e-3, max_steps=0, cache_rows=0, ctx=None):
+    def __init__(self, quad, X, signs, lin, boxes, alpha0, rule, tol=1e-3, max_steps=0, cache_rows=0, ctx=None, shrinking=False):
         if rule not in ('plain', 'nu'):
             raise ValueError(f'unknown rule {rule}')
+        if rule == 'nu' and shrinking:
+            raise ValueError('shrinking is built for libsvm\'s Solver (rule \'plain\'), not for Solver_NU')
         if rule == 'nu' and cache_rows == 2:
             raise ValueError('a Solver_NU step holds three rows: cache_rows must be 0 or >= 3')
         N = len(signs)
-        self._setup(quad, X, _lib.as_f64(signs, N, 'signs'), None, tol, False, cache_rows, ctx)
+        self._setup(quad, X, _lib.as_f64(signs, N, 'signs'), None, tol, False, cache_rows, ctx, shrinking)
         self.lin = _lib.as_f64(lin, N, 'lin')
         self.box = _lib.as_f64(boxes, N, 'boxes')
         self.alpha0 = _lib.as_f64(alpha0, N, 'alpha0')
@@ -167,7 +171,8 @@ class _RowFit:
         kernel = _resolved(self.kernel, X)
         quad = KernelQuadratic(X, np.zeros(X.shape[0]), 'plain', kernel, storage='stream')
         try:
-            opt = GeneralRowSMO(quad, X, signs, lin, boxes, alpha0, rule, self.tol, self.max_iter or 0, self.cache_rows).minimize()
+            opt = GeneralRowSMO(quad, X, signs, lin, boxes, alpha0, rule, self.tol, self.max_iter or 0, self.cache_rows,
+                                shrinking=getattr(self, 'shrinking', False)).minimize()
         finally:
             quad.release()
         return self._ran(kernel, opt)
@@ -180,6 +185,7 @@ class _RowFit:
         self.status_ = opt.status
         self.kkt_violation_ = float(opt.violation)
         self.cache_stats_ = opt.cache_stats
+        self.shrink_stats_ = opt.shrink_stats
         if self.status_ == 'stopped':
             warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
         return opt
@@ -189,15 +195,18 @@ class RowOneClassSVM(_RowFit, OneClassSVM):
     """`OneClassSVM` without a Gram panel: libsvm's Solver on kernel rows made on demand.  `max_iter` None is libsvm's cap
     max(10^7, 100 n); `cache_rows` rows are kept in an LRU cache on the device (0: as many as fit).  Fitted attributes are
     `OneClassSVM`'s with the same meaning (`n_iter_` counts pair updates; no `train_loss_history`), plus `cache_stats_`
-    ({'hits', 'misses', 'cache_rows'}).  A multi-rank context raises NotImplementedError."""
+    ({'hits', 'misses', 'cache_rows'}).  `shrinking` (False, True = libsvm's interval of 1000 steps, or the interval) turns on
+    libsvm's shrinking (`RowSMO`); `shrink_stats_` is then the solver's `shrink_stats`, else None.  `row_one_class_nu_path` runs the
+    batched solver, which does not shrink.  A multi-rank context raises NotImplementedError."""
 
-    def __init__(self, kernel=gaussian, nu=0.5, tol=1e-3, max_iter=None, cache_rows=0):
+    def __init__(self, kernel=gaussian, nu=0.5, tol=1e-3, max_iter=None, cache_rows=0, shrinking=False):
         _check(kernel, nu, tol, max_iter, cache_rows)
         self.kernel = kernel
         self.nu = nu
         self.tol = tol
         self.max_iter = max_iter
         self.cache_rows = cache_rows
+        self.shrinking = shrinking
 
     def fit(self, X, y=None):
         _check(self.kernel, self.nu, self.tol, self.max_iter, self.cache_rows)   # set_params may have changed them

@@ -5,7 +5,10 @@
 rows in HBM, 0 = as many as fit) the two kernel rows it touches from the k-major image of X.  This is what
 `SVC` / `SVR(optimizer='smo', storage='stream').fit` run.
 
-The algorithm is libsvm's `Solver::Solve` without shrinking, NOT the Keerthi / Shevade walker of `smo.py`, and `tol` is libsvm's
+The algorithm is libsvm's `Solver::Solve`, shrinking opt-in (`shrinking=True`: libsvm's interval of 1000 steps; an int: the
+interval; `bq_rsmo_set_shrinking`, csrc/bq_rsmo_shrink.h — variables at a bound that cannot become violators leave a device-side
+active list, rows, selection and update run on the list, and the full gradient is rebuilt by one streamed product when libsvm
+reconstructs it; `shrink_stats` reports the list's length, its smallest length, the shrink passes and the reconstructions), NOT the Keerthi / Shevade walker of `smo.py`, and `tol` is libsvm's
 (sklearn's): the run ends when Gmax + Gmax2 < tol, the largest violation of the KKT conditions over the pair sets, where the
 resident walker compares every example with its two thresholds b_up / b_low under 2 tol.  Same dual, same optimum, different
 trajectories and different distances from it at equal `tol`.  `b` = -rho with libsvm's rho (`calculate_rho`).
@@ -27,15 +30,18 @@ class RowSMO(ABC):
     _task = None
     run_steps = 512   # steps enqueued between two looks at the device's `finished` word
 
-    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None):
-        self._setup(quad, X, y, kernel, tol, verbose, cache_rows, ctx)
+    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False):
+        self._setup(quad, X, y, kernel, tol, verbose, cache_rows, ctx, shrinking)
         self.K = K
         self.C = C
         n = len(self.X)
         self.box = np.full(n, float(C)) if box is None else _lib.as_f64(box, n, 'box')
 
-    def _setup(self, quad, X, y, kernel, tol, verbose, cache_rows, ctx):
+    def _setup(self, quad, X, y, kernel, tol, verbose, cache_rows, ctx, shrinking=False):
         """what every dual on rows needs: the streamed problem, the data, the run's parameters and its (empty) results"""
+        if shrinking is not True and shrinking is not False and not (isinstance(shrinking, (int, np.integer)) and shrinking > 0):
+            raise ValueError('shrinking must be False, True (libsvm\'s 1000 steps) or a positive interval')
+        self.shrinking = shrinking
         if not isinstance(quad, KernelQuadratic) or quad.storage != 'stream':
             raise TypeError("the row-based SMO needs a KernelQuadratic(storage='stream') as quad")
         if not (cache_rows == 0 or cache_rows >= 2):
@@ -54,6 +60,7 @@ class RowSMO(ABC):
         self.iter = 0
         self.status = 'unknown'
         self.cache_stats = {'hits': 0, 'misses': 0, 'cache_rows': 0}
+        self.shrink_stats = None   # with shrinking: {'active', 'min_active', 'shrinks', 'reconstructions'}
         self.verbose = verbose
 
     def _epsilon(self):
@@ -90,6 +97,8 @@ class RowSMO(ABC):
         h = C.c_void_p()
         self._create(lib, dev, h)
         try:
+            if self.shrinking:
+                _lib.check(lib.bq_rsmo_set_shrinking(h, 0 if self.shrinking is True else int(self.shrinking)))
             if self.verbose:
                 print('iter\t cost')
             steps, fin = C.c_int64(0), C.c_int(0)
@@ -109,6 +118,10 @@ class RowSMO(ABC):
             st = np.empty(3)
             _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_STATS, _lib.ptr(st)))
             self._finished(st)
+            if self.shrinking:
+                sh = np.empty(4)
+                _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_SHRINK_STATS, _lib.ptr(sh)))
+                self.shrink_stats = dict(zip(('active', 'min_active', 'shrinks', 'reconstructions'), (int(v) for v in sh)))
             if self.verbose:
                 print()
         finally:
@@ -146,9 +159,9 @@ class RowSMO(ABC):
 class RowSMOClassifier(RowSMO):
     _task = _lib.SVC
 
-    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None):
+    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False):
         self.alphas = np.zeros(len(X))
-        super(RowSMOClassifier, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx)
+        super(RowSMOClassifier, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx, shrinking)
 
     def _pull(self, lib, h):
         _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_ALPHAS, _lib.ptr(self.alphas)))
@@ -175,10 +188,10 @@ class RowSMOClassifier(RowSMO):
 class RowSMORegression(RowSMO):
     _task = _lib.SVR
 
-    def __init__(self, quad, X, y, K, kernel, C, epsilon, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None):
+    def __init__(self, quad, X, y, K, kernel, C, epsilon, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False):
         self.alphas_p = np.zeros(len(X))
         self.alphas_n = np.zeros(len(X))
-        super(RowSMORegression, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx)
+        super(RowSMORegression, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx, shrinking)
         self.epsilon = epsilon
 
     def _epsilon(self):
@@ -217,7 +230,8 @@ class RowSMOBatch:
     one cache of kernel rows for all columns, the rows a step misses made 16 at a time by the fp64-MFMA row-block kernel.  `columns`
     are unrun solvers of one type on the same `quad`, X, kernel and tol; after `minimize()` each holds what its own `minimize()`
     would have set (alphas, gradient, rho / b, iter, status, w), from rows with the row-block kernel's bits, and `cache_stats` of
-    the shared cache.  A column's trajectory does not depend on the other columns or on the cache.
+    the shared cache.  A column's trajectory does not depend on the other columns or on the cache.  The batched solver does not
+    shrink: a column's `shrinking` is ignored here.
 
     `rows` (one strictly ascending list of rows of the quad per column) makes every column a row-list column
     (`bq_mrsmo_create_lists`): column c is a `RowSMOClassifier` built on `X[rows[c]], y[rows[c]]` — a class pair of one-vs-one — and
