@@ -71,6 +71,7 @@ extern "C" {
 /* (still 3: bq_mrsmo_create_lists was added; nothing existing changed) */
 /* (still 3: bq_mrsmo_create_general / _create_lists_general were added, bq_mrsmo_get takes BQ_RSMO_NU_SCALARS; nothing existing changed) */
 /* (still 3: bq_rsmo_set_shrinking and BQ_RSMO_SHRINK_STATS were added; nothing existing changed) */
+/* (still 3: bq_rsmo_set_working_set and BQ_RSMO_WS_STATS were added; nothing existing changed) */
 #define BQ_ABI_VERSION 3
 
 typedef struct bq_ctx bq_ctx;
@@ -816,8 +817,9 @@ enum { BQ_RSMO_ALPHAS = 0,    /* n (BQ_SVC) or [alpha; alpha*] 2n (BQ_SVR) */
        BQ_RSMO_SCALARS = 2,   /* 6: rho, Gmax, Gmax2 (of the last selection), last i, last j (of the last update; -1: none), steps */
        BQ_RSMO_STATS = 3,     /* 3: cache hits, misses, cache_rows */
        BQ_RSMO_NU_SCALARS = 4, /* 7, BQ_RSMO_RULE_NU only: rho, r, Gmaxp + Gmaxp2, Gmaxn + Gmaxn2, last i, last j, steps */
-       BQ_RSMO_SHRINK_STATS = 5 /* 4, after bq_rsmo_set_shrinking only: the active count now, the smallest reached, shrink passes,
-                                   gradient reconstructions */ };
+       BQ_RSMO_SHRINK_STATS = 5, /* 4, after bq_rsmo_set_shrinking only: the active count now, the smallest reached, shrink passes,
+                                   gradient reconstructions */
+       BQ_RSMO_WS_STATS = 6   /* 3, after bq_rsmo_set_working_set only: q, outer iterations, pair updates inside working sets */ };
 int bq_rsmo_create(bq_problem *p, int task, const double *y, const double *Cw, double epsilon, double tol,
                    int64_t cache_rows, bq_rsmo **out);
 /* The general dual  min 1/2 a'Qa + lin'a,  0 <= a_v <= boxes_v,  Q_uv = s_u s_v K_row(u) row(v), from a start alpha0:
@@ -855,6 +857,18 @@ int bq_rsmo_create_general(bq_problem *p, int rule, int64_t N, const double *sig
  * BQ_ERR_BADARG: every < 0, a BQ_RSMO_RULE_NU solver, a solver that has taken a step or has shrinking set already.  A solver on which
  * this is never called runs the kernels and launches it always ran. */
 int bq_rsmo_set_shrinking(bq_rsmo *s, int64_t every);
+/* Working-set decomposition (opt-in, BQ_RSMO_RULE_PLAIN only; csrc/bq_rsmo_ws.h), the second stepping mode.  An OUTER iteration takes
+ * up to q violators (the q / 2 best of I_up, the best of I_low not among them, either side filling up for the other), solves the dual
+ * restricted to them on one compute unit (K_WW, 128 x 128 fp64 from one MFMA tile, in LDS; libsvm's step on it until the local
+ * gap is below max(tol, 0.1 x its value at entry) or 100 q updates), and applies the whole change of alpha to the gradient in ONE
+ * MFMA pass over the image; the row cache is not used.  bq_rsmo_run then counts and enqueues outer iterations (*steps, and `steps`
+ * of BQ_RSMO_SCALARS; last i / j are the last inner pair); the stop test, tol, the cap, rho and `finished` keep their meaning, and
+ * BQ_RSMO_STATS reports no hits and no misses unless bq_rsmo_rows is called.  Kernel values are MFMA sums, not the fma chains of
+ * bq_rsmo_rows: the run reaches the same optimum within tol on another trajectory, with the same bits on every run and for every
+ * max_steps.
+ * BQ_ERR_BADARG: q odd or outside 2 .. 128, a BQ_RSMO_RULE_NU solver, a solver with shrinking set (and bq_rsmo_set_shrinking on a
+ * solver with a working set), a call after the first bq_rsmo_run or a second call. */
+int bq_rsmo_set_working_set(bq_rsmo *s, int q);
 int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished);
 int bq_rsmo_get(bq_rsmo *s, int what, double *out);
 int bq_rsmo_rows(bq_rsmo *s, int m, const int64_t *idx, double *out);

@@ -27,7 +27,7 @@ PLACE_PANEL = 64
 PLAIN_PANEL = 128
 DENSE_ROWS, DENSE_LOWER = 256, 512   # OR-ed into the storage of bq_problem_create_dense
 SMO_ALPHAS, SMO_ERRORS, SMO_SCALARS, SMO_STATS = range(4)
-RSMO_ALPHAS, RSMO_GRADIENT, RSMO_SCALARS, RSMO_STATS, RSMO_NU_SCALARS, RSMO_SHRINK_STATS = range(6)
+RSMO_ALPHAS, RSMO_GRADIENT, RSMO_SCALARS, RSMO_STATS, RSMO_NU_SCALARS, RSMO_SHRINK_STATS, RSMO_WS_STATS = range(7)
 RSMO_RULE_PLAIN, RSMO_RULE_NU = range(2)   # bq_rsmo_create_general's `rule`
 RSMO_STATUS = {0: 'unknown', 1: 'optimal', 2: 'stopped'}   # bq_rsmo_run's `finished`
 RULE_SGD, RULE_ADAM, RULE_AMSGRAD, RULE_ADAMAX, RULE_ADAGRAD, RULE_ADADELTA, RULE_RMSPROP = range(7)
@@ -175,6 +175,7 @@ PROTOTYPES = {
     'bq_rsmo_create': (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, _i64, C.POINTER(_vp)]),
     'bq_rsmo_create_general': (C.c_int, [_vp, C.c_int, _i64, _dp, _dp, _dp, _dp, C.c_double, _i64, _i64, C.POINTER(_vp)]),
     'bq_rsmo_set_shrinking': (C.c_int, [_vp, _i64]),
+    'bq_rsmo_set_working_set': (C.c_int, [_vp, C.c_int]),
     'bq_rsmo_run': (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),
     'bq_rsmo_get': (C.c_int, [_vp, C.c_int, _dp]),
     'bq_rsmo_rows': (C.c_int, [_vp, C.c_int, C.POINTER(_i64), _dp]),

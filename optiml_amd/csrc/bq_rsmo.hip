@@ -22,6 +22,9 @@
 // A row is one ascending-feature fma chain per column over the image, x_i staged in LDS; <x_i, x_t> and <x_t, x_i> are the same
 // chain (fma(a, b, c) = fma(b, a, c)) and the two norms are added to each other first, so K[i][t] and K[t][i] have the same bits, and
 // a row has the same bits whenever it is computed: nothing in a trajectory depends on the cache.
+//
+// bq_rsmo_set_working_set switches a BQ_RSMO_RULE_PLAIN solver to working-set decomposition (bq_rsmo_ws.h): up to 128 variables per outer
+// iteration, their sub-dual solved in LDS, one MFMA pass over the image per iteration, no kernel row and no cache.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -55,6 +58,9 @@ struct rsmo_ctl {
     int scatter, nact_new;   // between the two launches of a shrink pass
     int min_act;
     long long nshrink;
+    // bq_rsmo_set_working_set (bq_rsmo_ws.h): the length of the working set in hand, the pair updates made inside working sets
+    int wn;
+    long long inner;
 };
 
 struct rsmo_dev {
@@ -526,6 +532,7 @@ __global__ __launch_bounds__(RSMO_T) void rsmo_fill_kernel(rsmo_dev P, int64_t r
 }   // namespace
 
 #include "bq_rsmo_shrink.h"   // the active list: select / update over positions, the shrink pass, reconstruction
+#include "bq_rsmo_ws.h"       // working sets of up to 128 variables: the sub-dual in LDS, one MFMA pass over the image per set
 
 struct bq_rsmo {
     bq_problem *p = nullptr;
@@ -542,6 +549,14 @@ struct bq_rsmo {
     long long period = 0;            // libsvm's min(N, every)
     long long next_shrink = 0;       // a shrink pass runs before the step that starts from this many steps
     long long reconstructions = 0;
+    // bq_rsmo_set_working_set
+    bool working_set = false, ran = false;
+    int64_t dp = 0;                  // features of the image, padded
+    rsmo_ws W = {};
+    struct ws_level {
+        int in, count, out, last;
+    };
+    std::vector<ws_level> levels;    // the launches of the merge tree
 };
 
 extern "C" int bq_rsmo_destroy(bq_rsmo *s) {
@@ -633,6 +648,7 @@ extern "C" int bq_rsmo_create_general(bq_problem *p, int rule, int64_t N, const 
     rsmo_dev &P = s->P;
     int64_t dp = 0;
     bq_stream_image_view(p->stream_img, &P.At, &P.a2, &P.mp, &dp);
+    s->dp = dp;
     P.n = n;
     P.N = N;
     P.d = p->d;
@@ -774,6 +790,7 @@ extern "C" int bq_rsmo_set_shrinking(bq_rsmo *s, int64_t every) {
     BQ_ARG(every >= 0, "every must be >= 0 (0: libsvm's 1000)");
     BQ_ARG(s->rule == BQ_RSMO_RULE_PLAIN, "shrinking is built for BQ_RSMO_RULE_PLAIN (libsvm's Solver), not for Solver_NU's rule");
     BQ_ARG(s->host.steps == 0 && !s->shrinking, "shrinking is set once, before the first step");
+    BQ_ARG(!s->working_set, "shrinking and a working set (bq_rsmo_set_working_set) exclude each other");
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
     const rsmo_dev &P = s->P;
@@ -891,12 +908,89 @@ static int rsmo_run_shrinking(bq_rsmo *s, int64_t max_steps) {
     return BQ_OK;
 }
 
+// ---- working sets: the host side of bq_rsmo_ws.h --------------------------------------------------------------------------------------
+// one outer iteration (first: only the selection that makes the first W), enqueued without a look at the device
+template <typename KD>
+static void rsmo_ws_iteration(KD, const bq_rsmo *s, int first) {
+    const rsmo_dev &P = s->P;
+    const rsmo_ws &W = s->W;
+    hipStream_t st = s->p->ctx->stream;
+    if (!first) {
+        ws_gather_kernel<<<1, RSMO_T, 0, st>>>(P, W);
+        ws_kww_kernel<KD::kind, KD::deg><<<1, RSMO_T, 0, st>>>(P, W);
+        ws_local_kernel<<<1, RSMO_T, WS_LDS, st>>>(P, W);
+    }
+    ws_update_kernel<KD::kind, KD::deg><<<(unsigned int)(P.mp / BQ_GT), RSMO_T, 0, st>>>(P, W, first);
+    for (const auto &lv : s->levels) {
+        const dim3 grid(lv.last ? 1u : (unsigned int)((lv.count + WS_FAN - 1) / WS_FAN), lv.last ? 1u : 2u);
+        ws_merge_kernel<<<grid, RSMO_T, 0, st>>>(P, W, lv.in, lv.count, lv.out, lv.last, first);
+    }
+}
+
+extern "C" int bq_rsmo_set_working_set(bq_rsmo *s, int q) {
+    BQ_ARG(s, "NULL argument");
+    BQ_ARG(s->rule == BQ_RSMO_RULE_PLAIN, "working sets are built for BQ_RSMO_RULE_PLAIN (libsvm's Solver), not for Solver_NU's rule");
+    BQ_ARG(q >= 2 && q <= WS_Q && q % 2 == 0, "q must be even, 2 <= q <= 128");
+    BQ_ARG(!s->shrinking, "a working set and shrinking (bq_rsmo_set_shrinking) exclude each other");
+    BQ_ARG(!s->ran && !s->working_set, "the working set is set once, before the first bq_rsmo_run");
+    bq_ctx *c = s->p->ctx;
+    BQ_HIP(hipSetDevice(c->device));
+    BQ_HIP(hipFuncSetAttribute((const void *)ws_local_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WS_LDS));
+    const rsmo_dev &P = s->P;
+    rsmo_ws &W = s->W;
+    W.q = q;
+    W.dp = s->dp;
+    // the merge tree: level 0 reads the update kernel's lists, one per workgroup; every level but the last writes one per workgroup
+    s->levels.clear();   // (a call that failed below may be repeated: the tree is built again, a buffer it already has is kept)
+    int in = 0, count = (int)(P.mp / BQ_GT), next = count;
+    for (;;) {
+        const int last = count <= WS_FAN ? 1 : 0;
+        s->levels.push_back({in, count, next, last});
+        if (last) break;
+        in = next;
+        count = (count + WS_FAN - 1) / WS_FAN;
+        next += count;
+    }
+    const size_t entries = (size_t)next * 2 * WS_Q;
+    hipError_t e = hipSuccess;
+    auto need = [&](auto **field, size_t count) {   // (no size depends on q)
+        if (e == hipSuccess && *field == nullptr) e = s->mem.dev(field, count);
+    };
+    need(&W.W, (size_t)WS_Q);
+    need(&W.rowW, (size_t)WS_Q);
+    need(&W.Wt, (size_t)W.dp * WS_Q);
+    need(&W.pack, (size_t)WS_PACK * WS_Q);
+    need(&W.Kww, (size_t)WS_Q * WS_Q);
+    need(&W.delta, (size_t)WS_Q);
+    need(&W.list_v, entries);
+    need(&W.list_i, entries);
+    if (e != hipSuccess) {
+        bq_set_error("the working set's buffers failed: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP;
+    }
+    ws_init_kernel<<<1, 1, 0, c->stream>>>(P);
+    BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) { rsmo_ws_iteration(kd, s, 1); }));
+    BQ_HIP(hipGetLastError());
+    BQ_TRY(rsmo_read_ctl(s));
+    s->working_set = true;
+    return BQ_OK;
+}
+
 extern "C" int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *finished) {
     BQ_ARG(s && steps && finished, "NULL argument");
     BQ_ARG(max_steps > 0, "max_steps must be > 0");
     bq_ctx *c = s->p->ctx;
     BQ_HIP(hipSetDevice(c->device));
-    if (s->shrinking) {
+    s->ran = true;
+    if (s->working_set) {
+        if (!s->host.finished) {
+            BQ_TRY(rsmo_dispatch(s->p, [&](auto kd) {
+                for (int64_t k = 0; k < max_steps; ++k) rsmo_ws_iteration(kd, s, 0);
+            }));
+            BQ_HIP(hipGetLastError());
+            BQ_TRY(rsmo_read_ctl(s));
+        }
+    } else if (s->shrinking) {
         BQ_TRY(rsmo_run_shrinking(s, max_steps));
     } else if (!s->host.finished) {
         const rsmo_dev &P = s->P;
@@ -916,7 +1010,8 @@ extern "C" int bq_rsmo_run(bq_rsmo *s, int64_t max_steps, int64_t *steps, int *f
 
 extern "C" int bq_rsmo_get(bq_rsmo *s, int what, double *out) {
     BQ_ARG(s && out, "NULL argument");
-    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_SHRINK_STATS, "what");
+    BQ_ARG(what >= BQ_RSMO_ALPHAS && what <= BQ_RSMO_WS_STATS, "what");
+    BQ_ARG(what != BQ_RSMO_WS_STATS || s->working_set, "BQ_RSMO_WS_STATS needs bq_rsmo_set_working_set");
     BQ_ARG(what != BQ_RSMO_NU_SCALARS || s->rule == BQ_RSMO_RULE_NU, "BQ_RSMO_NU_SCALARS needs a BQ_RSMO_RULE_NU solver");
     BQ_ARG(what != BQ_RSMO_SHRINK_STATS || s->shrinking, "BQ_RSMO_SHRINK_STATS needs bq_rsmo_set_shrinking");
     bq_ctx *c = s->p->ctx;
@@ -932,6 +1027,12 @@ extern "C" int bq_rsmo_get(bq_rsmo *s, int what, double *out) {
         out[0] = (double)s->host.hits;
         out[1] = (double)s->host.misses;
         out[2] = (double)P.R;
+        return BQ_OK;
+    }
+    if (what == BQ_RSMO_WS_STATS) {
+        out[0] = (double)s->W.q;
+        out[1] = (double)s->host.steps;
+        out[2] = (double)s->host.inner;
         return BQ_OK;
     }
     if (what == BQ_RSMO_SHRINK_STATS) {

@@ -216,6 +216,9 @@ class SVM(BaseEstimator, ABC):
     # the interval.  A class-or-instance attribute like `tune_placement`, since the constructors keep the reference's arguments; read
     # on the optimizer='smo', storage='stream' route only (the meta-estimators' batch_smo='rows' route does not shrink).
     shrinking = False
+    # working-set decomposition on the same route (`RowSMO(working_set=...)`): False, True (128 variables per outer iteration) or an even
+    # size in 2 .. 128; excludes `shrinking`
+    working_set = False
 
     def _smo_solver(self, resident, rows, obj, *args):
         """The SMO branch of `fit`: the walker on the resident panel (`resident`), or, with storage='stream', libsvm's decomposition
@@ -226,7 +229,7 @@ class SVM(BaseEstimator, ABC):
             return resident(obj, *args).minimize()
         if get_context().world != 1:
             raise NotImplementedError("optimizer='smo' with storage='stream' runs on a single-rank context")
-        opt = rows(obj, *args, shrinking=self.shrinking).minimize()
+        opt = rows(obj, *args, shrinking=self.shrinking, working_set=self.working_set).minimize()
         if opt.status == 'stopped':
             import warnings
             warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)

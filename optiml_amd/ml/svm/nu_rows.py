@@ -91,15 +91,18 @@ class GeneralRowSMO(RowSMO):
     `alpha0`, under libsvm's Solver (`rule` 'plain') or Solver_NU ('nu').  After `minimize()`: `alphas`, `gradient`, `rho`, `iter`,
     `status`, `cache_stats`, `violation` (the stop measure at the last selection), and for 'nu' `r`."""
 
-    def __init__(self, quad, X, signs, lin, boxes, alpha0, rule, tol=1e-3, max_steps=0, cache_rows=0, ctx=None, shrinking=False):
+    def __init__(self, quad, X, signs, lin, boxes, alpha0, rule, tol=1e-3, max_steps=0, cache_rows=0, ctx=None, shrinking=False,
+                 working_set=False):
         if rule not in ('plain', 'nu'):
             raise ValueError(f'unknown rule {rule}')
         if rule == 'nu' and shrinking:
             raise ValueError('shrinking is built for libsvm\'s Solver (rule \'plain\'), not for Solver_NU')
+        if rule == 'nu' and working_set:
+            raise ValueError('working sets are built for libsvm\'s Solver (rule \'plain\'), not for Solver_NU')
         if rule == 'nu' and cache_rows == 2:
             raise ValueError('a Solver_NU step holds three rows: cache_rows must be 0 or >= 3')
         N = len(signs)
-        self._setup(quad, X, _lib.as_f64(signs, N, 'signs'), None, tol, False, cache_rows, ctx, shrinking)
+        self._setup(quad, X, _lib.as_f64(signs, N, 'signs'), None, tol, False, cache_rows, ctx, shrinking, working_set)
         self.lin = _lib.as_f64(lin, N, 'lin')
         self.box = _lib.as_f64(boxes, N, 'boxes')
         self.alpha0 = _lib.as_f64(alpha0, N, 'alpha0')
@@ -111,7 +114,7 @@ class GeneralRowSMO(RowSMO):
     def _create(self, lib, dev, h):
         rule = _lib.RSMO_RULE_NU if self.rule == 'nu' else _lib.RSMO_RULE_PLAIN
         _lib.check(lib.bq_rsmo_create_general(dev.handle, rule, len(self.y), _lib.ptr(self.y), _lib.ptr(self.lin), _lib.ptr(self.box),
-                                              _lib.ptr(self.alpha0), float(self.tol), self.max_steps, self.cache_rows, C.byref(h)))
+                                              _lib.ptr(self.alpha0), float(self.tol), self.max_steps, self._cache_rows(), C.byref(h)))
 
     def _pull(self, lib, h):
         _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_ALPHAS, _lib.ptr(self.alphas)))
@@ -162,6 +165,11 @@ def _check(kernel, nu, tol, max_iter, cache_rows, C_=1.0, min_rows=2):
         raise ValueError(f'cache_rows must be 0 (as many as fit) or >= {min_rows}')
 
 
+def _no_working_set(working_set):
+    if working_set:
+        raise ValueError('working sets are built for libsvm\'s Solver, not for Solver_NU: RowNuSVC / RowNuSVR run without')
+
+
 class _RowFit:
     """what the three estimators share: the streamed problem, the run, the solver-independent fitted attributes"""
 
@@ -172,7 +180,7 @@ class _RowFit:
         quad = KernelQuadratic(X, np.zeros(X.shape[0]), 'plain', kernel, storage='stream')
         try:
             opt = GeneralRowSMO(quad, X, signs, lin, boxes, alpha0, rule, self.tol, self.max_iter or 0, self.cache_rows,
-                                shrinking=getattr(self, 'shrinking', False)).minimize()
+                                shrinking=getattr(self, 'shrinking', False), working_set=getattr(self, 'working_set', False)).minimize()
         finally:
             quad.release()
         return self._ran(kernel, opt)
@@ -186,6 +194,7 @@ class _RowFit:
         self.kkt_violation_ = float(opt.violation)
         self.cache_stats_ = opt.cache_stats
         self.shrink_stats_ = opt.shrink_stats
+        self.ws_stats_ = opt.ws_stats
         if self.status_ == 'stopped':
             warnings.warn('max_iter reached but the optimization has not converged yet', ConvergenceWarning)
         return opt
@@ -196,10 +205,12 @@ class RowOneClassSVM(_RowFit, OneClassSVM):
     max(10^7, 100 n); `cache_rows` rows are kept in an LRU cache on the device (0: as many as fit).  Fitted attributes are
     `OneClassSVM`'s with the same meaning (`n_iter_` counts pair updates; no `train_loss_history`), plus `cache_stats_`
     ({'hits', 'misses', 'cache_rows'}).  `shrinking` (False, True = libsvm's interval of 1000 steps, or the interval) turns on
-    libsvm's shrinking (`RowSMO`); `shrink_stats_` is then the solver's `shrink_stats`, else None.  `row_one_class_nu_path` runs the
+    libsvm's shrinking (`RowSMO`); `shrink_stats_` is then the solver's `shrink_stats`, else None.  `working_set` (False, True = 128,
+    or an even size in 2 .. 128) switches to working-set decomposition (`RowSMO`): `n_iter_` then counts outer iterations and
+    `ws_stats_` is the solver's `ws_stats`, else None.  `row_one_class_nu_path` runs the
     batched solver, which does not shrink.  A multi-rank context raises NotImplementedError."""
 
-    def __init__(self, kernel=gaussian, nu=0.5, tol=1e-3, max_iter=None, cache_rows=0, shrinking=False):
+    def __init__(self, kernel=gaussian, nu=0.5, tol=1e-3, max_iter=None, cache_rows=0, shrinking=False, working_set=False):
         _check(kernel, nu, tol, max_iter, cache_rows)
         self.kernel = kernel
         self.nu = nu
@@ -207,6 +218,7 @@ class RowOneClassSVM(_RowFit, OneClassSVM):
         self.max_iter = max_iter
         self.cache_rows = cache_rows
         self.shrinking = shrinking
+        self.working_set = working_set
 
     def fit(self, X, y=None):
         _check(self.kernel, self.nu, self.tol, self.max_iter, self.cache_rows)   # set_params may have changed them
@@ -232,8 +244,10 @@ class RowNuSVC(_RowFit, NuSVC):
     any device work) and the fitted attributes are `NuSVC`'s (`margin_scale_` = r, `dual_coef_` = y alpha / r, `intercept_` =
     -rho / r), plus `cache_stats_`; `max_iter` and `cache_rows` (0 or >= 3) as in `RowOneClassSVM`."""
 
-    def __init__(self, kernel=gaussian, nu=0.5, tol=1e-3, max_iter=None, cache_rows=0):
+    def __init__(self, kernel=gaussian, nu=0.5, tol=1e-3, max_iter=None, cache_rows=0, working_set=False):
         _check(kernel, nu, tol, max_iter, cache_rows, min_rows=3)
+        _no_working_set(working_set)
+        self.working_set = working_set
         self.kernel = kernel
         self.nu = nu
         self.tol = tol
@@ -267,8 +281,10 @@ class RowNuSVR(_RowFit, NuSVR):
     Fitted attributes are `NuSVR`'s (`dual_coef_` = alpha - alpha*, `intercept_` = -rho, `epsilon_` = -r), plus `cache_stats_`;
     `max_iter` and `cache_rows` (0 or >= 3) as in `RowOneClassSVM`."""
 
-    def __init__(self, kernel=gaussian, nu=0.5, C=1.0, tol=1e-3, max_iter=None, cache_rows=0):
+    def __init__(self, kernel=gaussian, nu=0.5, C=1.0, tol=1e-3, max_iter=None, cache_rows=0, working_set=False):
         _check(kernel, nu, tol, max_iter, cache_rows, C, min_rows=3)
+        _no_working_set(working_set)
+        self.working_set = working_set
         self.kernel = kernel
         self.nu = nu
         self.C = C

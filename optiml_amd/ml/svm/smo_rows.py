@@ -12,6 +12,13 @@ reconstructs it; `shrink_stats` reports the list's length, its smallest length, 
 (sklearn's): the run ends when Gmax + Gmax2 < tol, the largest violation of the KKT conditions over the pair sets, where the
 resident walker compares every example with its two thresholds b_up / b_low under 2 tol.  Same dual, same optimum, different
 trajectories and different distances from it at equal `tol`.  `b` = -rho with libsvm's rho (`calculate_rho`).
+
+`working_set` (False; True = 128; or an even size in 2 .. 128; `bq_rsmo_set_working_set`, csrc/bq_rsmo_ws.h) switches to working-set
+decomposition: an outer iteration takes that many violators, solves the dual restricted to them in the LDS of one compute unit
+and applies the whole change to the gradient in one matrix-core pass over the image.  `iter` then counts outer iterations,
+`ws_stats` is {'working_set', 'outer', 'inner'} (inner: pair updates inside working sets), no kernel row is made or cached
+(`cache_rows` 0 asks for the smallest cache), and the stop test is unchanged: the same optimum within `tol`, on another trajectory,
+with the same bits on every run.  It excludes `shrinking` and is not built for Solver_NU.
 """
 import ctypes as C
 from abc import ABC
@@ -30,15 +37,21 @@ class RowSMO(ABC):
     _task = None
     run_steps = 512   # steps enqueued between two looks at the device's `finished` word
 
-    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False):
-        self._setup(quad, X, y, kernel, tol, verbose, cache_rows, ctx, shrinking)
+    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False, working_set=False):
+        self._setup(quad, X, y, kernel, tol, verbose, cache_rows, ctx, shrinking, working_set)
         self.K = K
         self.C = C
         n = len(self.X)
         self.box = np.full(n, float(C)) if box is None else _lib.as_f64(box, n, 'box')
 
-    def _setup(self, quad, X, y, kernel, tol, verbose, cache_rows, ctx, shrinking=False):
+    def _setup(self, quad, X, y, kernel, tol, verbose, cache_rows, ctx, shrinking=False, working_set=False):
         """what every dual on rows needs: the streamed problem, the data, the run's parameters and its (empty) results"""
+        if working_set is not True and working_set is not False and not (
+                isinstance(working_set, (int, np.integer)) and 2 <= working_set <= 128 and working_set % 2 == 0):
+            raise ValueError('working_set must be False, True (128 variables) or an even size in 2 .. 128')
+        if working_set and shrinking:
+            raise ValueError('working_set and shrinking exclude each other')
+        self.working_set = working_set
         if shrinking is not True and shrinking is not False and not (isinstance(shrinking, (int, np.integer)) and shrinking > 0):
             raise ValueError('shrinking must be False, True (libsvm\'s 1000 steps) or a positive interval')
         self.shrinking = shrinking
@@ -61,6 +74,7 @@ class RowSMO(ABC):
         self.status = 'unknown'
         self.cache_stats = {'hits': 0, 'misses': 0, 'cache_rows': 0}
         self.shrink_stats = None   # with shrinking: {'active', 'min_active', 'shrinks', 'reconstructions'}
+        self.ws_stats = None       # with a working set: {'working_set', 'outer', 'inner'}
         self.verbose = verbose
 
     def _epsilon(self):
@@ -79,7 +93,11 @@ class RowSMO(ABC):
     def _create(self, lib, dev, h):
         """the device solver of this dual on the problem `dev`, into the handle `h`"""
         _lib.check(lib.bq_rsmo_create(dev.handle, self._task, _lib.ptr(self.y), _lib.ptr(self.box), float(self._epsilon()),
-                                      float(self.tol), self.cache_rows, C.byref(h)))
+                                      float(self.tol), self._cache_rows(), C.byref(h)))
+
+    def _cache_rows(self):
+        """a working-set run makes no kernel row: the smallest cache in place of the automatic one (half of the free memory)"""
+        return 2 if self.working_set and self.cache_rows == 0 else self.cache_rows
 
     def _scalars(self, lib, h):
         """the offsets and the stop measure of the finished run"""
@@ -99,6 +117,8 @@ class RowSMO(ABC):
         try:
             if self.shrinking:
                 _lib.check(lib.bq_rsmo_set_shrinking(h, 0 if self.shrinking is True else int(self.shrinking)))
+            if self.working_set:
+                _lib.check(lib.bq_rsmo_set_working_set(h, 128 if self.working_set is True else int(self.working_set)))
             if self.verbose:
                 print('iter\t cost')
             steps, fin = C.c_int64(0), C.c_int(0)
@@ -122,6 +142,10 @@ class RowSMO(ABC):
                 sh = np.empty(4)
                 _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_SHRINK_STATS, _lib.ptr(sh)))
                 self.shrink_stats = dict(zip(('active', 'min_active', 'shrinks', 'reconstructions'), (int(v) for v in sh)))
+            if self.working_set:
+                ws = np.empty(3)
+                _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_WS_STATS, _lib.ptr(ws)))
+                self.ws_stats = dict(zip(('working_set', 'outer', 'inner'), (int(v) for v in ws)))
             if self.verbose:
                 print()
         finally:
@@ -159,9 +183,9 @@ class RowSMO(ABC):
 class RowSMOClassifier(RowSMO):
     _task = _lib.SVC
 
-    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False):
+    def __init__(self, quad, X, y, K, kernel, C, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False, working_set=False):
         self.alphas = np.zeros(len(X))
-        super(RowSMOClassifier, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx, shrinking)
+        super(RowSMOClassifier, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx, shrinking, working_set)
 
     def _pull(self, lib, h):
         _lib.check(lib.bq_rsmo_get(h, _lib.RSMO_ALPHAS, _lib.ptr(self.alphas)))
@@ -188,10 +212,10 @@ class RowSMOClassifier(RowSMO):
 class RowSMORegression(RowSMO):
     _task = _lib.SVR
 
-    def __init__(self, quad, X, y, K, kernel, C, epsilon, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False):
+    def __init__(self, quad, X, y, K, kernel, C, epsilon, tol=1e-3, verbose=False, box=None, cache_rows=0, ctx=None, shrinking=False, working_set=False):
         self.alphas_p = np.zeros(len(X))
         self.alphas_n = np.zeros(len(X))
-        super(RowSMORegression, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx, shrinking)
+        super(RowSMORegression, self).__init__(quad, X, y, K, kernel, C, tol, verbose, box, cache_rows, ctx, shrinking, working_set)
         self.epsilon = epsilon
 
     def _epsilon(self):

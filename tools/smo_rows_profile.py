@@ -28,6 +28,8 @@ RBF with gamma='scale', d = 128, C = 1, tol 1e-3, seed 0) and write profiles/smo
     fit (--model svc|svr) and nu-fit --model oneclass take --shrinking EVERY (libsvm's shrinking, bq_rsmo_set_shrinking; 1000 is
         libsvm's interval): the record gains the shrink statistics and the cost of one reconstruction (one streamed product);
         profiles/smo_rows_shrinking/ keeps the records
+    ... and --working-set Q (working-set decomposition, bq_rsmo_set_working_set; 128 is the full size): steps are then outer
+        iterations and the record gains `ws_stats`; profiles/smo_working_set/ keeps the records
 
 Every measurement runs in a process of its own under its own time limit, after a warm-up fit of n = 4000 on the same route; a wall
 time ends after the solver's last read-back, which synchronises the stream."""
@@ -48,14 +50,16 @@ sys.path.insert(0, REPO)
 D, SIGMA, TOL = 128, 8.0, 1e-3
 
 
-def _svc(storage, shrinking=0, model='svc'):
-    """shrinking: 0 off, else the interval of libsvm's shrinking (1000 is libsvm's own); model 'svr': SVR(epsilon=0.1) on sin(x_0)"""
+def _svc(storage, shrinking=0, model='svc', working_set=0):
+    """shrinking: 0 off, else the interval of libsvm's shrinking (1000 is libsvm's own); model 'svr': SVR(epsilon=0.1) on sin(x_0);
+    working_set: 0 off, else the variables per outer iteration"""
     from optiml_amd.ml.svm import SVC, SVR
     from optiml_amd.ml.svm.kernels import gaussian
     from optiml_amd.ml.svm.losses import epsilon_insensitive, hinge
     kw = dict(kernel=gaussian, C=1., dual=True, optimizer='smo', tol=TOL, storage=storage)
     est = SVC(loss=hinge, **kw) if model == 'svc' else SVR(loss=epsilon_insensitive, epsilon=0.1, **kw)
     est.shrinking = int(shrinking) if shrinking else False
+    est.working_set = int(working_set) if working_set else False
     return est
 
 
@@ -79,11 +83,11 @@ def cmd_fit(args):
     from optiml_amd.device import get_context
     target = (lambda X, y: y) if args.model == 'svc' else (lambda X, y: np.sin(X[:, 0]))
     Xw, yw = _data(4000)
-    _svc(args.storage, args.shrinking, args.model).fit(Xw, target(Xw, yw)).obj.release()
+    _svc(args.storage, args.shrinking, args.model, args.working_set).fit(Xw, target(Xw, yw)).obj.release()
     X, y = _data(args.n)
     y = target(X, y)
     t0 = time.perf_counter()
-    est = _svc(args.storage, args.shrinking, args.model).fit(X, y)
+    est = _svc(args.storage, args.shrinking, args.model, args.working_set).fit(X, y)
     wall = time.perf_counter() - t0
     opt = est.optimizer
     rec = {'what': 'fit', 'model': args.model, 'n': args.n, 'd': D, 'storage': args.storage, 'tol': TOL, 'wall_s': wall, 'n_sv': int(len(est.support_)),
@@ -96,6 +100,7 @@ def cmd_fit(args):
         if not args.no_probe:
             rec['read_GBs'] = get_context().probe_bandwidth()[0]
         _shrink_record(rec, opt.shrink_stats, est.obj)
+        rec['ws_stats'] = opt.ws_stats
     else:
         yb = np.where(y == np.unique(y)[-1], 1., -1.)
         rec.update(steps=int(opt.steps), outer_iterations=int(opt.iter), per_step_us=1e6 * wall / max(opt.steps, 1),
@@ -450,11 +455,12 @@ def cmd_product(args):
 NU = {'oneclass': 0.1, 'nusvc': 0.2}
 
 
-def _nu_model(model, route, shrinking=0):
+def _nu_model(model, route, shrinking=0, working_set=0):
     from optiml_amd.ml.svm import NuSVC, OneClassSVM, RowNuSVC, RowOneClassSVM
     from optiml_amd.ml.svm.kernels import gaussian
     if route == 'rows' and model == 'oneclass':
-        return RowOneClassSVM(kernel=gaussian, nu=NU[model], tol=TOL, shrinking=int(shrinking) if shrinking else False)
+        return RowOneClassSVM(kernel=gaussian, nu=NU[model], tol=TOL, shrinking=int(shrinking) if shrinking else False,
+                              working_set=int(working_set) if working_set else False)
     if route == 'rows':
         return RowNuSVC(kernel=gaussian, nu=NU[model], tol=TOL)
     return (OneClassSVM if model == 'oneclass' else NuSVC)(kernel=gaussian, nu=NU[model], tol=TOL, max_iter=100000, storage='f64')
@@ -465,10 +471,10 @@ def cmd_nu_fit(args):
     also the streamed product of the same data — the start gradient of these duals is one such product"""
     from optiml_amd.opti import KernelQuadratic
     fit = (lambda m, X, y: m.fit(X)) if args.model == 'oneclass' else (lambda m, X, y: m.fit(X, y))
-    fit(_nu_model(args.model, args.route, args.shrinking), *_data(4000))
+    fit(_nu_model(args.model, args.route, args.shrinking, args.working_set), *_data(4000))
     X, y = _data(args.n)
     t0 = time.perf_counter()
-    est = fit(_nu_model(args.model, args.route, args.shrinking), X, y)
+    est = fit(_nu_model(args.model, args.route, args.shrinking, args.working_set), X, y)
     wall = time.perf_counter() - t0
     rec = {'what': 'nu fit', 'model': type(est).__name__, 'nu': NU[args.model], 'n': args.n, 'd': D, 'route': args.route, 'tol': TOL,
            'wall_s': wall, 'steps': int(est.n_iter_), 'status': est.status_, 'n_sv': int(len(est.support_)),
@@ -482,7 +488,7 @@ def cmd_nu_fit(args):
         quad = KernelQuadratic(X, np.zeros(args.n), 'plain', est.kernel_, storage='stream')
         rec['start_product_s'] = quad.device_problem().time_matvec(3) / 1e3
         quad.release()
-        rec.update(shrinking=est.shrink_stats_ is not None, shrink_stats=est.shrink_stats_)
+        rec.update(shrinking=est.shrink_stats_ is not None, shrink_stats=est.shrink_stats_, ws_stats=getattr(est, 'ws_stats_', None))
     json.dump(rec, open(args.json, 'w'), indent=1)
     print(json.dumps(rec))
 
@@ -629,6 +635,7 @@ def main():
     p.add_argument('--no-probe', action='store_true')
     p.add_argument('--model', default='svc', choices=['svc', 'svr'])
     p.add_argument('--shrinking', type=int, default=0, help="interval of libsvm's shrinking on the stream route (0: off; libsvm's is 1000)")
+    p.add_argument('--working-set', type=int, default=0, help='variables per outer iteration of the working-set mode on the stream route (0: off)')
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_fit)
     p = sub.add_parser('rate')
@@ -688,6 +695,7 @@ def main():
     p.add_argument('--route', default='rows', choices=['rows', 'resident'])
     p.add_argument('--n', type=int, required=True)
     p.add_argument('--shrinking', type=int, default=0, help="oneclass on rows: interval of libsvm's shrinking (0: off; libsvm's is 1000)")
+    p.add_argument('--working-set', type=int, default=0, help='oneclass on rows: variables per outer iteration of the working-set mode (0: off)')
     p.add_argument('--json', required=True)
     p.set_defaults(fn=cmd_nu_fit)
     p = sub.add_parser('product')
